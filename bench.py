@@ -6,9 +6,15 @@ Contract (driver):  python bench.py --gpus N --steps K --warmup W   -> ONE JSON 
               the token feedback loop are resident in HBM when the timed region starts).
   workload  = BASELINE.json configs[1]: Qwen3-0.6B Q8 group=64 single-stream greedy decode on 1xMI355X --
               synthetic checkpoint (seed 1234) in the reference's format, 8-token prompt, the reference's
-              `generate` call pattern (first forward at pos 7 over a zero KV prefix, generation.rs:26-29), ctx 1024.
+              `generate` call pattern (first forward at pos 7 over a zero KV prefix, generation.rs:26-29), ctx 1024
+              (raised to the next multiple of 1024 that holds 7 + max(K, W) positions when the steps need more).
   N > 1     = N independent replicas, one process + one engine per GPU, no collective on the data path
               (the path does not shard: every listed model fits one GPU).  value = sum of tokens / max time.
+  --dump-outputs DIR = after the timed steps, rank 0 writes what the timed loop handed back (tokens.npy: the K greedy
+              tokens, float64) and the logits of its last step, recomputed after the timing (last_logits.npy, float32).
+
+A plain run sets up, warms up, times the K steps and prints the line (value, ms_per_step, the end-to-end share of the
+HBM roofline from the byte count).  Everything below needs runs of its own and comes only with --full:
   roofline  = the weight-streaming GEMV kernel (all instantiations of k_gemv): algorithmic weight bytes per
               launch / average launch period measured with HIP events on the engine's stream.
   forward_surface = the reference's own tok/s definition (TokenMetrics, generation.rs:198-233) on the reference's
@@ -54,8 +60,12 @@ def parse_args(argv=None):
     ap.add_argument("--steps", type=int, default=128)
     ap.add_argument("--warmup", type=int, default=8)
     ap.add_argument("--shape", default="qwen3-0.6b")
-    ap.add_argument("--ctx", type=int, default=1024)
+    ap.add_argument("--ctx", type=int, default=None, help="context length (default 1024, or more when the steps need it)")
     ap.add_argument("--fast", action="store_true", help="opt-in tree-reduction mode (not bit-exact)")
+    ap.add_argument("--full", action="store_true",
+                    help="also roofline, forward_surface, tolerance_mode, cpu_baseline + parity, graph-replay stamps and other_configs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-other-configs", action="store_true", help="skip the configs 3/4/5 sub-results")
     ap.add_argument("--no-graph-stamps", action="store_true", help="roofline from eager HIP events only (skip the graph-replay stamp run)")
@@ -77,8 +87,13 @@ def run_setup(args):
     shape = ck.SHAPES[args.shape]
     prompt = ck.iter_prompt_tokens(shape, SEED, 8)
     first_tok, first_pos = prompt[-1], len(prompt) - 1
-    if first_pos + max(args.steps, args.warmup) > args.ctx:
-        raise SystemExit("steps exceed ctx")
+    need = first_pos + max(args.steps, args.warmup)
+    if args.ctx is None:
+        # whole multiples of 1024 positions: the engine takes the context as seq_len, and its product attention forms need
+        # seq_len % 8 == 0 (k_attn_short2) and % 4 == 0 (the transposed value cache of k_attn_out); other lengths fall back
+        args.ctx = min(-(-need // 1024) * 1024, shape.max_seq_len)
+    if need > min(args.ctx, shape.max_seq_len):
+        raise SystemExit(f"steps exceed ctx ({need} positions, ctx {args.ctx}, model {shape.max_seq_len})")
     return shape, first_tok, first_pos
 
 
@@ -147,16 +162,16 @@ def dist_setup():
 
 
 def barrier():
-    try:
-        import torch.distributed as dist
-        if dist.is_available() and dist.is_initialized():
-            dist.barrier()
-    except ImportError:
-        pass
+    # one replica never imports torch (its import alone takes seconds); dist_setup imported it when there are more
+    dist = sys.modules.get("torch.distributed")
+    if dist is not None and dist.is_available() and dist.is_initialized():
+        dist.barrier()
 
 
 def aggregate_over_ranks(local_tokens, local_seconds):
     """(sum of tokens over ranks, max of seconds over ranks).  Single process: identity."""
+    if "torch.distributed" not in sys.modules:
+        return int(local_tokens), float(local_seconds)
     try:
         import torch
         import torch.distributed as dist
@@ -171,15 +186,20 @@ def aggregate_over_ranks(local_tokens, local_seconds):
     return int(local_tokens), float(local_seconds)
 
 
-def device_sync(stub):
-    if stub:
-        return
-    try:
-        import torch
-        if torch.cuda.is_available():
-            torch.cuda.synchronize()
-    except ImportError:
-        pass
+def dump_outputs(out_dir, eng, tokens, first_tok, first_pos):
+    """What the timed loop computed in its last step: the K tokens it handed back (float64 holds them exactly) and the
+    logits of its last step.  q3_generate_greedy keeps those logits on the device, so the last step's forward is run once
+    more (q3_forward) on the same KV prefix, after the timing; their argmax must be the loop's last token."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "tokens.npy"), np.asarray(tokens, dtype=np.float64))
+    if hasattr(eng, "forward"):
+        feed = [first_tok] + [int(t) for t in tokens]
+        logits = np.array(eng.forward(feed[-2], first_pos + len(tokens) - 1), dtype=np.float32)
+        last_max = logits.size - 1 - int(np.argmax(logits[::-1]))         # sample_argmax: the last maximum
+        if last_max != int(tokens[-1]):
+            raise RuntimeError(f"recomputed last-step logits pick token {last_max}, the timed loop gave {tokens[-1]}")
+        np.save(os.path.join(out_dir, "last_logits.npy"), logits)
 
 
 def worker_main(args):
@@ -201,18 +221,19 @@ def worker_main(args):
         eng = q3.TransformerBuilder(path).with_ctx_length(args.ctx).with_device(local_rank).with_strict(not args.fast).build()
     if W > 0:
         eng.generate_greedy(first_tok, first_pos, W)      # untimed warmup steps
-    eng.reset_kv()
+    eng.reset_kv()                                         # ends in a stream synchronise, like generate_greedy
 
-    barrier(); device_sync(args.stub_engine)
+    barrier()
     t0 = time.perf_counter()
     tokens = eng.generate_greedy(first_tok, first_pos, K)   # exactly K steps; returns after the stream drained
-    device_sync(args.stub_engine)
     dt = time.perf_counter() - t0
     barrier()
     total_tokens, max_dt = aggregate_over_ranks(K, dt)
     if rank != 0:
         eng.close()
         return None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, eng, tokens, first_tok, first_pos)
 
     value = total_tokens / max_dt
     wq, ws = shape.weight_bytes_per_token()
@@ -236,6 +257,9 @@ def worker_main(args):
         return out
     # which binary produced the numbers: the id baked into the loaded library next to the hash of the sources here
     out["build_id"] = {"library": q3.load_library().q3_build_id().decode(), "sources": q3.source_build_id()}
+    if not args.full:
+        eng.close()
+        return out
 
     # ---- roofline of the dominant kernel: HIP events on the engine stream, one forward per rep (eager launches)
     reps = 20
@@ -508,6 +532,10 @@ def spawn_workers(args, n, timeout_s=1500.0):
            "--warmup", str(args.warmup), "--shape", args.shape, "--ctx", str(args.ctx), "--ckpt-dir", args.ckpt_dir]
     if args.fast:
         cmd.append("--fast")
+    if args.full:
+        cmd.append("--full")
+    if args.dump_outputs:
+        cmd += ["--dump-outputs", os.path.abspath(args.dump_outputs)]
     if args.stub_engine:
         cmd.append("--stub-engine")
     procs = []
@@ -579,7 +607,7 @@ def other_configs(args):
          [py, os.path.join(tools, "bench_batch.py"), "--ckpt-dir", args.ckpt_dir, "--steps", "256"] +
          ([] if args.no_tolerance_mode else ["--tolerance", "64"])),
         ("config5 DeepSeek-R1-0528-Qwen3-8B, one replica of the data-parallel set",
-         [py, os.path.abspath(__file__), "--shape", "deepseek-r1-0528-qwen3-8b", "--steps", "32", "--warmup", "4",
+         [py, os.path.abspath(__file__), "--shape", "deepseek-r1-0528-qwen3-8b", "--steps", "32", "--warmup", "4", "--full",
           "--no-cpu-baseline", "--no-other-configs", "--ckpt-dir", args.ckpt_dir]),
     ]
     t0, res = time.time(), {}
@@ -659,7 +687,7 @@ def parent_main(args):
     tokens = out.pop("_tokens")
     parity = None                      # None: not checked (no CPU leg); True/False: tokens compared
     unchecked = False
-    if n == 1 and not args.no_cpu_baseline and not args.stub_engine:
+    if args.full and n == 1 and not args.no_cpu_baseline and not args.stub_engine:
         try:
             cb, match = cpu_baseline(path, args.ctx, first_tok, first_pos, tokens)
             out["cpu_baseline"] = cb
@@ -676,7 +704,7 @@ def parent_main(args):
         out["parity"] = parity
         if parity is False:
             log("[bench] FATAL: GPU tokens differ from the CPU oracle")
-    if n == 1 and not args.stub_engine and not args.no_graph_stamps and isinstance(out.get("roofline"), dict):
+    if args.full and n == 1 and not args.stub_engine and not args.no_graph_stamps and isinstance(out.get("roofline"), dict):
         try:
             roofline_from_graph_stamps(out, args, shape, first_tok, first_pos, path)
         except Exception as e:
@@ -687,7 +715,7 @@ def parent_main(args):
         parity = False
         out["parity"] = False
         log("[bench] FATAL: q3_forward host loop and the device-resident loop disagree")
-    if n == 1 and args.shape == "qwen3-0.6b" and not args.no_other_configs and not args.stub_engine:
+    if args.full and n == 1 and args.shape == "qwen3-0.6b" and not args.no_other_configs and not args.stub_engine:
         out["other_configs"] = other_configs(args)
     print(json.dumps(out), flush=True)
     return 1 if parity is False else (2 if unchecked else 0)
@@ -701,6 +729,10 @@ def main():
             if not args.worker:          # launched by torchrun: this IS the result line
                 out.pop("_tokens", None)
             print(json.dumps(out), flush=True)
+        # a gloo group still alive at interpreter exit can abort the process ("terminate called without an active exception")
+        dist = sys.modules.get("torch.distributed")
+        if dist is not None and dist.is_available() and dist.is_initialized():
+            dist.destroy_process_group()
         return 0
     return parent_main(args)
 

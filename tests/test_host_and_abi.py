@@ -334,6 +334,142 @@ def test_bench_two_replicas_stub_engine_same_body_as_the_two_gpu_test():
     assert d["value"] > 1.5 * d1["value"], (d["value"], d1["value"])
 
 
+def _bench_dump_run(out_dir, extra):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--dump-outputs", str(out_dir)] + list(extra),
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    return json.loads(lines[0])
+
+
+def test_bench_context_grows_in_whole_kilopositions():
+    """Steps past the default context of 1,024 positions raise it to the next multiple of 1,024 (the engine's product attention forms
+    need a context of whole 8-row steps), capped at the model's length; an explicit --ctx stays as given."""
+    sys.path.insert(0, ROOT)
+    import bench
+    for steps, ctx in ((128, 1024), (1017, 1024), (1018, 2048), (1500, 2048), (2000, 2048), (4090, 5120), (40953, 40960)):
+        a = bench.parse_args(["--steps", str(steps)])
+        _, _, first_pos = bench.run_setup(a)
+        assert first_pos == 7 and a.ctx == ctx and a.ctx % 8 == 0, (steps, a.ctx)
+    with pytest.raises(SystemExit):
+        bench.run_setup(bench.parse_args(["--steps", "40954"]))
+    a = bench.parse_args(["--steps", "100", "--ctx", "300"])
+    bench.run_setup(a)
+    assert a.ctx == 300
+    with pytest.raises(SystemExit):
+        bench.run_setup(bench.parse_args(["--steps", "1500", "--ctx", "1024"]))
+
+
+class _Reached(Exception):
+    pass
+
+
+def test_bench_full_gates_the_secondary_blocks(monkeypatch, capsys):
+    """A plain run measures the timed steps and nothing else; --full adds the blocks that take runs of their own.  Worker side: the
+    engine's profile run (the roofline block, the first of them) happens only with --full.  Parent side: the CPU baseline + parity,
+    the graph-replay stamps and the other configs run only with --full.  (Host fakes stand in for the engine and those legs.)"""
+    sys.path.insert(0, ROOT)
+    import bench
+    import qwen3_rs_amd as q3
+    from qwen3_rs_amd import checkpoint as ck
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        monkeypatch.delenv(k, raising=False)
+    calls = []
+
+    class Engine:
+        def generate_greedy(self, tok, pos, n):
+            return [(tok + pos + k) % 1000 for k in range(n)]
+
+        def reset_kv(self):
+            pass
+
+        def close(self):
+            pass
+
+        def profile(self, *a):
+            calls.append("profile")
+            raise _Reached
+
+    class Builder:
+        def __init__(self, path):
+            pass
+
+        def with_ctx_length(self, n):
+            return self
+
+        with_device = with_strict = with_ctx_length
+
+        def build(self):
+            return Engine()
+
+    class Lib:
+        def q3_build_id(self):
+            return b"abc"
+
+    monkeypatch.setattr(q3, "TransformerBuilder", Builder)
+    monkeypatch.setattr(q3, "load_library", lambda: Lib())
+    monkeypatch.setattr(q3, "source_build_id", lambda: "abc")
+    out = bench.worker_main(bench.parse_args(["--worker", "--steps", "6", "--warmup", "1"]))
+    assert calls == [] and out["steps"] == 6 and out["build_id"] == {"library": "abc", "sources": "abc"}
+    assert not {"roofline", "forward_surface", "value_128", "tolerance_mode"} & set(out)
+    with pytest.raises(_Reached):
+        bench.worker_main(bench.parse_args(["--worker", "--full", "--steps", "6", "--warmup", "1"]))
+    assert calls == ["profile"]
+
+    for k, v in (("OMP_PROC_BIND", "close"), ("OMP_PLACES", "cores"), ("OMP_WAIT_POLICY", "active")):
+        monkeypatch.setenv(k, v)
+    monkeypatch.setattr(ck, "ensure_synthetic_checkpoint", lambda *a, **kw: None)
+    monkeypatch.setattr(bench, "spawn_workers", lambda args, n: {"_tokens": [1, 2, 3], "roofline": {}, "steps": args.steps})
+    monkeypatch.setattr(bench, "cpu_baseline", lambda *a, **kw: calls.append("cpu_baseline") or ({}, True))
+    monkeypatch.setattr(bench, "roofline_from_graph_stamps", lambda *a, **kw: calls.append("graph_stamps"))
+    monkeypatch.setattr(bench, "other_configs", lambda args: calls.append("other_configs") or {})
+    del calls[:]
+    assert bench.parent_main(bench.parse_args(["--steps", "6"])) == 0
+    assert calls == [] and "parity" not in json.loads(capsys.readouterr().out)
+    assert bench.parent_main(bench.parse_args(["--steps", "6", "--full"])) == 0
+    assert calls == ["cpu_baseline", "graph_stamps", "other_configs"] and json.loads(capsys.readouterr().out)["parity"] is True
+
+
+def test_bench_steps_and_dump_outputs_stub_engine(tmp_path):
+    """--steps is the number of timed steps, also past the default context of 1,024 positions; --dump-outputs writes the tokens the
+    timed loop handed back, the same from run to run."""
+    dumps = []
+    for k in range(2):
+        d = _bench_dump_run(tmp_path / f"out{k}", ["--steps", "1500", "--warmup", "2", "--stub-engine"])
+        assert d["steps"] == 1500 and d["ms_per_step"] > 0 and "ctx 2048, 1500 tokens" in d["config"]["workload"]
+        assert abs(d["value"] - 1500 / (d["ms_per_step"] * 1500 / 1e3)) / d["value"] < 1e-3
+        t = np.load(tmp_path / f"out{k}" / "tokens.npy")
+        assert t.dtype == np.float64 and t.shape == (1500,)
+        dumps.append(t)
+    assert np.array_equal(dumps[0], dumps[1])
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_match_the_oracle(oracle, tmp_path):
+    """`bench.py --dump-outputs` on the device: the dumped tokens are the oracle's greedy tokens and the dumped logits are the
+    oracle's logits of the last step, bit for bit (a small model: the oracle runs the same steps on the host)."""
+    sys.path.insert(0, ROOT)
+    import bench
+    args = ["--shape", "tiny-g64", "--steps", "12", "--warmup", "3", "--ckpt-dir", str(tmp_path)]
+    d = _bench_dump_run(tmp_path / "out", args)
+    assert d["steps"] == 12
+    a = bench.parse_args(args)
+    _, tok, pos = bench.run_setup(a)
+    m = oracle.OracleModel(bench.ckpt_path(a), 96)
+    toks = []
+    for k in range(12):
+        logits = m.forward(tok, pos + k)
+        tok = oracle.sample_argmax(logits)
+        toks.append(tok)
+    m.close()
+    got = np.load(tmp_path / "out" / "tokens.npy")
+    assert got.dtype == np.float64 and got.tolist() == toks
+    last = np.load(tmp_path / "out" / "last_logits.npy")
+    assert last.dtype == np.float32
+    assert np.array_equal(last.view(np.int32), np.ascontiguousarray(logits, dtype=np.float32).view(np.int32))
+
+
 @pytest.mark.gpu
 def test_bench_two_real_replicas_on_two_devices():
     """`bench.py --gpus 2` with REAL engines: one process + one engine per GPU (devices 0 and 1), no collective on the data

@@ -15,8 +15,8 @@ from qwen3_rs_amd import checkpoint as ck
 ck.ensure_synthetic_checkpoint('/tmp/q3_$1.bin', ck.SHAPES['$1'], seed=1234)"; }
 for sec in "$@"; do
   case $sec in
-    bench)    ensure qwen3-0.6b; Q3_EAGER_LAUNCH=1 trace bench python3 bench.py --worker --steps 128 --warmup 8 --no-tolerance-mode ;;
-    bench8b)  ensure qwen3-8b; Q3_EAGER_LAUNCH=1 trace bench_qwen3-8b python3 bench.py --worker --shape qwen3-8b --steps 32 --warmup 4 --no-tolerance-mode ;;
+    bench)    ensure qwen3-0.6b; Q3_EAGER_LAUNCH=1 trace bench python3 bench.py --worker --full --steps 128 --warmup 8 --no-tolerance-mode ;;
+    bench8b)  ensure qwen3-8b; Q3_EAGER_LAUNCH=1 trace bench_qwen3-8b python3 bench.py --worker --full --shape qwen3-8b --steps 32 --warmup 4 --no-tolerance-mode ;;
     batch)    Q3_EAGER_LAUNCH=1 trace batch python3 tools/bench_batch.py --steps 16 --verify 0 ;;
     prefill)  Q3_EAGER_LAUNCH=1 trace prefill python3 tools/prefill_prof.py ;;
     long4b)   Q3_EAGER_LAUNCH=1 Q3_PROFILE_FAMILIES=0 trace chat_decode_pos2300 python3 tools/longctx_prof.py qwen3-4b 2300 32 ;;
