@@ -30,9 +30,9 @@
  *                               on the ticket.  Measured cost of the ordered form: +1.4 ... +4.8 us per token
  *                               (profiles/r05_ticket_order.txt: a release is a buffer_wbl2 in each of ~590 workgroups).
  *                               Build it when porting to another target or toolchain.
- * Every other Q3_* switch of earlier rounds (kernel-form A/B, tile and workgroup overrides, ablation bits, in-kernel
- * timelines) exists only in the developer build, libqwen3_hip_dev.so (`make -C qwen3-rs_amd dev`, -DQ3_DEV), together with
- * the kernel forms that lost their A/B; results are identical in both builds.
+ * Every other Q3_* switch (a choice between kernel forms that the product runs for other shapes, workgroup overrides,
+ * in-kernel timelines) exists only in the developer build, libqwen3_hip_dev.so (`make -C qwen3-rs_amd dev`, -DQ3_DEV);
+ * results are identical in both builds.
  */
 #ifndef QWEN3_HIP_H
 #define QWEN3_HIP_H

@@ -15,14 +15,6 @@
 #pragma once
 #include "q3_kernels.h"
 
-// developer ablation of the batched matmul, compile-time only (-DQ3_BABLATE=bits): 1 no B loads, 4 no term
-// formation / LDS term writes, 8 no A loads, 16 no fold.  Runtime switches would make the loads conditional and change what is being measured.
-#ifdef Q3_BABLATE
-#define Q3_BABL(bit) ((Q3_BABLATE & (bit)) != 0)
-#else
-#define Q3_BABL(bit) false
-#endif
-
 #ifdef Q3_DEV
 #define BG_STAMP(i) do { if (a.stamps != nullptr && blockIdx.x == 0 && threadIdx.x == 0 && sidx < 12) a.stamps[sidx * 8 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
 #else
@@ -245,8 +237,6 @@ struct BGemmArgs {
     unsigned long long* stamps;  // developer timeline (Q3_DEV builds, block 0 thread 0): 5 stamps per phase
     unsigned long long* slots;   // LOGITS: [stream][nslots] argmax keys, one per wave of the launch
     int nslots;
-    int8_t* pack_q;          // k_dgemm SWIGLU: hq = quantize(hb) in packed operand order (W2's activation), or nullptr
-    float* pack_s;
 };
 
 // One workgroup (8 waves) per row task (RT row tiles of 16 rows), the contraction walked in phases of PG groups:
@@ -314,13 +304,12 @@ __global__ __launch_bounds__(kBThreads) void k_bgemm(const BGemmArgs a) {
         for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
             for (int j = 0; j < NJ; ++j)
-                F.a[rt][k][j] = Q3_BABL(8) ? (v4i){lane, g, rt, j}
-                                           : __builtin_nontemporal_load((const v4i*)a.wq + (size_t)(task * RT + rt) * tile_v4 + ((size_t)g * NJ + j) * 64 + lane);
+                F.a[rt][k][j] = __builtin_nontemporal_load((const v4i*)a.wq + (size_t)(task * RT + rt) * tile_v4 + ((size_t)g * NJ + j) * 64 + lane);
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
             for (int j = 0; j < NJ; ++j)
-                F.b[nt][k][j] = Q3_BABL(1) ? (v4i){lane, g, nt, j} : ((const v4i*)a.xq)[(size_t)nt * tile_v4 + ((size_t)g * NJ + j) * 64 + lane];
+                F.b[nt][k][j] = ((const v4i*)a.xq)[(size_t)nt * tile_v4 + ((size_t)g * NJ + j) * 64 + lane];
     };
     auto issue = [&](Frag& F, int task, int p) {
         issue_scales(F, task, p);                                 // oldest loads: their LDS write comes first
@@ -366,9 +355,7 @@ __global__ __launch_bounds__(kBThreads) void k_bgemm(const BGemmArgs a) {
                     cacc[rt][nt] = c;
                 }
             if (more) issue_group(nxt, ntask, np, k);
-            if (Q3_BABL(4)) {
-                if (cacc[0][0].x == 0x7fffffff) terms[tid] = 1.0f;      // keep the MFMAs alive
-            } else if (g0 + gg < ng) {
+            if (g0 + gg < ng) {
 #pragma unroll
                 for (int rt = 0; rt < RT; ++rt) {
                     const v4f wsv = *(const v4f*)(wsl + (rt * PG + gg) * 16 + 4 * q);
@@ -392,7 +379,7 @@ __global__ __launch_bounds__(kBThreads) void k_bgemm(const BGemmArgs a) {
         BG_STAMP(3);
         // ---- fold: one (stream, row) accumulator per thread, ascending groups
         const int cnt = min(PG, ng - g0);
-        if (fold_thread && !Q3_BABL(16)) {
+        if (fold_thread) {
             // (requesting all of the phase's terms before the first add was measured 2 % slower than these 8-term batches)
 #pragma unroll
             for (int rt = 0; rt < RT; ++rt) {
@@ -698,22 +685,14 @@ __global__ __launch_bounds__(kPgThreads) void k_pgemm(const BGemmArgs a) {
 // tiles -- W1|W3 of the 4B shape has 608 tiles of 4 x 8 on 512 resident workgroup slots (two full rounds for 1.19 rounds of work),
 // 1,216 of 4 x 4 run as three rounds of half the length; QKV goes from 192 tiles (fewer than CUs) to 384.
 constexpr int kP2Waves = 8, kP2Threads = 512, kP2RT = 4, kP2D = 4;
-__host__ __device__ inline size_t pgemm2_slot_bytes(int ptw, int rtw) { return (size_t)(rtw + ptw) * 1024 + (size_t)(rtw + ptw) * 64; }     // fragments + scales of one group
-__host__ __device__ inline size_t pgemm2_smem_bytes(int ptw, int rtw = 4) { return (ptw == 4 ? 3 : 2) * pgemm2_slot_bytes(ptw, rtw); }
-
-// developer ablation of k_pgemm2, compile-time only (-DQ3_PABLATE=bits; wrong results, time only): 1 no global requests in the
-// loop, 2 no convert / scale / add chain, 4 no MFMAs, 8 no barrier in the group loop, 16 no LDS commits
-#ifdef Q3_PABLATE
-#define Q3_PABL(bit) ((Q3_PABLATE & (bit)) != 0)
-#else
-#define Q3_PABL(bit) false
-#endif
-template <int EPI, int PTW, int RTW = 4>
+__host__ __device__ inline size_t pgemm2_slot_bytes(int ptw) { return (size_t)(kP2RT + ptw) * 1024 + (size_t)(kP2RT + ptw) * 64; }     // fragments + scales of one group
+__host__ __device__ inline size_t pgemm2_smem_bytes(int ptw) { return (ptw == 4 ? 3 : 2) * pgemm2_slot_bytes(ptw); }
+template <int EPI, int PTW>
 __global__ __launch_bounds__(kP2Threads, 4) void k_pgemm2(const BGemmArgs a) {
     constexpr int D = kP2D;
+    constexpr int RTW = kP2RT;                                   // row tiles per workgroup
     constexpr int NF = RTW + PTW;                                // fragments per group: [A0..A(RTW-1)][B0..B(PTW-1)]
-    constexpr int NRW = RTW / 2;                                 // row tiles per wave (SwiGLU: the w1 and the w3 tile -> RTW = 4)
-    static_assert(RTW == 4 || (RTW == 2 && EPI != EPI_SWIGLU), "2-row-tile workgroups: one row tile per wave");
+    constexpr int NRW = RTW / 2;                                 // row tiles per wave (SwiGLU: the w1 and the w3 tile)
     constexpr int NPW = PTW / 4;                                 // position tiles per wave
     constexpr size_t kSlot = (size_t)NF * 1024 + (size_t)NF * 64;
     static_assert(PTW == 4 || PTW == 8, "workgroup tile: 4 row tiles x 4 or 8 position tiles");
@@ -748,14 +727,12 @@ __global__ __launch_bounds__(kP2Threads, 4) void k_pgemm2(const BGemmArgs a) {
         v4i r0_[D], r1_[D];
         float rs_[D];
         auto issue = [&](int sl, int g) {                        // group g -> register slot sl
-            if (Q3_PABL(1) && g >= D + 2) return;
             const int gg = min(g, ng - 1);
             r0_[sl] = src0[(size_t)gg * 64];                     // (unconditional: a wave without a fragment re-reads fragment 0 and drops it --
             if (two) r1_[sl] = src1[(size_t)gg * 64];            //  a branch around the first request made hipcc give up its counted waits: 45 -> 76 us)
             if (ld_ws || ld_xs) rs_[sl] = ssrc[(size_t)gg * 16];
         };
         auto commit = [&](int sl, int ls) {                      // register slot sl -> LDS slot ls
-            if (Q3_PABL(16)) return;
             v4i* f = slot_frag(ls);
             if (one) f[wave * 64 + lane] = r0_[sl];
             if (two) f[(wave + 8) * 64 + lane] = r1_[sl];
@@ -797,7 +774,6 @@ __global__ __launch_bounds__(kP2Threads, 4) void k_pgemm2(const BGemmArgs a) {
 #pragma unroll
                 for (int j = 0; j < NPW; ++j) {
                     const v4i c = cg[i][j];
-                    if (Q3_PABL(2)) { acc[i][j].x = __int_as_float(__float_as_int(acc[i][j].x) ^ c.x ^ c.y ^ c.z ^ c.w ^ __float_as_int(w[i].x) ^ __float_as_int(x[j])); continue; }
                     // tensor.rs:59  ((dot as f32) * ws) * xs, then the g-ascending add; pairs (rows 4q, 4q+1), (4q+2, 4q+3)
                     pk2 t01 = (pk2){(float)c.x, (float)c.y} * (pk2){w[i].x, w[i].y};
                     pk2 t23 = (pk2){(float)c.z, (float)c.w} * (pk2){w[i].z, w[i].w};
@@ -860,7 +836,7 @@ __global__ __launch_bounds__(kP2Threads, 4) void k_pgemm2(const BGemmArgs a) {
                 for (int i = 0; i < NRW; ++i)
 #pragma unroll
                     for (int j = 0; j < NPW; ++j)
-                        cc[i][j] = Q3_PABL(4) ? fa2[par][i] ^ fb2[par][j] : __builtin_amdgcn_mfma_i32_16x16x64_i8(fa2[par][i], fb2[par][j], (v4i){0, 0, 0, 0}, 0, 0, 0);
+                        cc[i][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(fa2[par][i], fb2[par][j], (v4i){0, 0, 0, 0}, 0, 0, 0);
                 math_group(cc, w2[par], x2[par]);
             };
 #pragma unroll
@@ -880,7 +856,7 @@ __global__ __launch_bounds__(kP2Threads, 4) void k_pgemm2(const BGemmArgs a) {
                     issue((u + 2) % D, g + 2 + D);
                     read_group(l1, (u + 1) & 1);                 // group g + 1 (past the row: a re-read group, dropped)
                     compute(u & 1);
-                    if (!Q3_PABL(8)) __syncthreads();            // group g + 2 visible; slot g % 3 free for group g + 3
+                    __syncthreads();                             // group g + 2 visible; slot g % 3 free for group g + 3
                     l1 = l2;
                     l2 = l2 == 2 ? 0 : l2 + 1;
                     __builtin_amdgcn_sched_barrier(0);
@@ -937,11 +913,12 @@ __global__ __launch_bounds__(kP2Threads, 4) void k_pgemm2(const BGemmArgs a) {
 // stage the GS groups are independent until the ordered adds, so their LDS reads, MFMAs and multiply chains overlap.
 // Same accumulation order per (row, position): groups ascending, acc += ((f32)idot * ws) * xs from -0.0 (tensor.rs:53-60).
 // ------------------------------------------------------------------------------------------------
-__host__ __device__ inline size_t pgemm3_slot_bytes(int ptw, int rtw, int gs) { return (size_t)gs * ((size_t)(rtw + ptw) * 1024 + (size_t)(rtw + ptw) * 64); }
-__host__ __device__ inline size_t pgemm3_smem_bytes(int ptw, int rtw, int gs) { return 2 * pgemm3_slot_bytes(ptw, rtw, gs); }
+__host__ __device__ inline size_t pgemm3_slot_bytes(int ptw, int gs) { return (size_t)gs * ((size_t)(kP2RT + ptw) * 1024 + (size_t)(kP2RT + ptw) * 64); }
+__host__ __device__ inline size_t pgemm3_smem_bytes(int ptw, int gs) { return 2 * pgemm3_slot_bytes(ptw, gs); }
 
-template <int EPI, int PTW, int RTW, int GS>
+template <int EPI, int PTW, int GS>
 __global__ __launch_bounds__(kP2Threads, 4) void k_pgemm3(const BGemmArgs a) {
+    constexpr int RTW = kP2RT;                                   // row tiles per workgroup
     constexpr int NF = RTW + PTW;                                // fragments per group: [A0..A(RTW-1)][B0..B(PTW-1)]
     constexpr int NRW = RTW / 2, NPW = PTW / 4;                  // row / position tiles per wave
     constexpr int NJ = GS * NF;                                  // fragment jobs (1 KiB each) per stage
@@ -949,7 +926,6 @@ __global__ __launch_bounds__(kP2Threads, 4) void k_pgemm3(const BGemmArgs a) {
     constexpr int NSC = GS * NF * 16;                            // scale floats per stage
     constexpr int SW = (NSC + kP2Threads - 1) / kP2Threads;      // ... per thread (1)
     constexpr size_t kSlot = (size_t)GS * ((size_t)NF * 1024 + (size_t)NF * 64);
-    static_assert(RTW == 8 || RTW == 4 || (RTW == 2 && EPI != EPI_SWIGLU), "2-row-tile workgroups: one row tile per wave");
     static_assert(SW == 1, "one scale dword per thread and stage");
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1003,70 +979,65 @@ __global__ __launch_bounds__(kP2Threads, 4) void k_pgemm3(const BGemmArgs a) {
         for (int i = 0; i < NRW; ++i)
 #pragma unroll
             for (int j = 0; j < NPW; ++j) acc[i][j] = (v4f){-0.0f, -0.0f, -0.0f, -0.0f};    // Iterator::sum::<f32>() identity
-        // a stage is computed HS groups x IS row tiles at a time (their reads, MFMAs and multiply chains are independent and overlap;
-        // everything at once needs ~155 VGPRs), the ordered adds of a sub-step follow its terms.  Per accumulator the order is
-        // unchanged: groups ascending.
+        // a stage is computed HS groups at a time (their reads, MFMAs and multiply chains are independent and overlap), the
+        // ordered adds of a sub-step follow its terms.  Per accumulator the order is unchanged: groups ascending.
         constexpr int HS = (GS >= 2 && NPW == 1) ? 2 : 1;
-        constexpr int IS = NRW > 2 ? 2 : NRW;
         auto compute = [&](int ls) {
             const v4i* f = slot_frag(ls);
             const float* sc = slot_sc(ls);
 #pragma unroll
             for (int k0 = 0; k0 < GS; k0 += HS) {
+                v4i cc[HS][NRW][NPW];
+                v4f w[HS][NRW];
+                float x[HS][NPW];
 #pragma unroll
-                for (int i0 = 0; i0 < NRW; i0 += IS) {
-                    v4i cc[HS][IS][NPW];
-                    v4f w[HS][IS];
-                    float x[HS][NPW];
+                for (int h = 0; h < HS; ++h) {
+                    const int k = k0 + h;
+                    v4i fa[NRW], fb[NPW];
 #pragma unroll
-                    for (int h = 0; h < HS; ++h) {
-                        const int k = k0 + h;
-                        v4i fa[IS], fb[NPW];
+                    for (int i = 0; i < NRW; ++i) fa[i] = f[(size_t)(k * NF + NRW * wr + i) * 64 + lane];
 #pragma unroll
-                        for (int i = 0; i < IS; ++i) fa[i] = f[(size_t)(k * NF + NRW * wr + i0 + i) * 64 + lane];
+                    for (int j = 0; j < NPW; ++j) fb[j] = f[(size_t)(k * NF + RTW + NPW * wp + j) * 64 + lane];
 #pragma unroll
-                        for (int j = 0; j < NPW; ++j) fb[j] = f[(size_t)(k * NF + RTW + NPW * wp + j) * 64 + lane];
+                    for (int i = 0; i < NRW; ++i) w[h][i] = *(const v4f*)(sc + (k * NF + NRW * wr + i) * 16 + 4 * q);
 #pragma unroll
-                        for (int i = 0; i < IS; ++i) w[h][i] = *(const v4f*)(sc + (k * NF + NRW * wr + i0 + i) * 16 + 4 * q);
+                    for (int j = 0; j < NPW; ++j) x[h][j] = sc[(k * NF + RTW + NPW * wp + j) * 16 + s];
 #pragma unroll
-                        for (int j = 0; j < NPW; ++j) x[h][j] = sc[(k * NF + RTW + NPW * wp + j) * 16 + s];
+                    for (int i = 0; i < NRW; ++i)
 #pragma unroll
-                        for (int i = 0; i < IS; ++i)
-#pragma unroll
-                            for (int j = 0; j < NPW; ++j)
-                                cc[h][i][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(fa[i], fb[j], (v4i){0, 0, 0, 0}, 0, 0, 0);
-                    }
-                    pk2 t01[HS][IS][NPW], t23[HS][IS][NPW];
-#pragma unroll
-                    for (int h = 0; h < HS; ++h)
-#pragma unroll
-                        for (int i = 0; i < IS; ++i)
-#pragma unroll
-                            for (int j = 0; j < NPW; ++j) {
-                                const v4i c = cc[h][i][j];
-                                // tensor.rs:59  ((dot as f32) * ws) * xs; pairs (rows 4q, 4q+1), (4q+2, 4q+3)
-                                pk2 u01 = (pk2){(float)c.x, (float)c.y} * (pk2){w[h][i].x, w[h][i].y};
-                                pk2 u23 = (pk2){(float)c.z, (float)c.w} * (pk2){w[h][i].z, w[h][i].w};
-                                asm("" : "+v"(u01)); asm("" : "+v"(u23));
-                                pk2 xb = (pk2){x[h][j], x[h][j]};
-                                asm("" : "+v"(xb));
-                                u01 = u01 * xb; u23 = u23 * xb;
-                                asm("" : "+v"(u01)); asm("" : "+v"(u23));
-                                t01[h][i][j] = u01; t23[h][i][j] = u23;
-                            }
-#pragma unroll
-                    for (int h = 0; h < HS; ++h)
-#pragma unroll
-                        for (int i = 0; i < IS; ++i)
-#pragma unroll
-                            for (int j = 0; j < NPW; ++j) {
-                                v4f& ac = acc[i0 + i][j];
-                                pk2 a01 = (pk2){ac.x, ac.y} + t01[h][i][j], a23 = (pk2){ac.z, ac.w} + t23[h][i][j];
-                                asm("" : "+v"(a01)); asm("" : "+v"(a23));
-                                ac.x = a01.x; ac.y = a01.y; ac.z = a23.x; ac.w = a23.y;
-                            }
-                    __builtin_amdgcn_sched_barrier(0);
+                        for (int j = 0; j < NPW; ++j)
+                            cc[h][i][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(fa[i], fb[j], (v4i){0, 0, 0, 0}, 0, 0, 0);
                 }
+                pk2 t01[HS][NRW][NPW], t23[HS][NRW][NPW];
+#pragma unroll
+                for (int h = 0; h < HS; ++h)
+#pragma unroll
+                    for (int i = 0; i < NRW; ++i)
+#pragma unroll
+                        for (int j = 0; j < NPW; ++j) {
+                            const v4i c = cc[h][i][j];
+                            // tensor.rs:59  ((dot as f32) * ws) * xs; pairs (rows 4q, 4q+1), (4q+2, 4q+3)
+                            pk2 u01 = (pk2){(float)c.x, (float)c.y} * (pk2){w[h][i].x, w[h][i].y};
+                            pk2 u23 = (pk2){(float)c.z, (float)c.w} * (pk2){w[h][i].z, w[h][i].w};
+                            asm("" : "+v"(u01)); asm("" : "+v"(u23));
+                            pk2 xb = (pk2){x[h][j], x[h][j]};
+                            asm("" : "+v"(xb));
+                            u01 = u01 * xb; u23 = u23 * xb;
+                            asm("" : "+v"(u01)); asm("" : "+v"(u23));
+                            t01[h][i][j] = u01; t23[h][i][j] = u23;
+                        }
+#pragma unroll
+                for (int h = 0; h < HS; ++h)
+#pragma unroll
+                    for (int i = 0; i < NRW; ++i)
+#pragma unroll
+                        for (int j = 0; j < NPW; ++j) {
+                            v4f& ac = acc[i][j];
+                            pk2 a01 = (pk2){ac.x, ac.y} + t01[h][i][j], a23 = (pk2){ac.z, ac.w} + t23[h][i][j];
+                            asm("" : "+v"(a01)); asm("" : "+v"(a23));
+                            ac.x = a01.x; ac.y = a01.y; ac.z = a23.x; ac.w = a23.y;
+                        }
+                __builtin_amdgcn_sched_barrier(0);
             }
         };
         // ---- pipeline: register set of stage x is x % 2, LDS slot x % 2
@@ -1131,128 +1102,66 @@ __global__ __launch_bounds__(kP2Threads, 4) void k_pgemm3(const BGemmArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// Batched decode matmul, round 4: in-lane accumulation at 16-32 columns (k_dgemm).
+// Batched decode matmul, round 4: in-lane accumulation at 16-32 columns (k_dgemm), the residual launches (Wo, W2).
 // k_bgemm splits K over the 8 waves of a workgroup and pays, per phase of 16-32 groups, a 64 KiB LDS term tile, two
 // barriers and a 16-32-term dependent fold behind LDS reads: with the weight loads compiled out its launches kept 70 % of
 // their time (profiles/r03_batch32_ablation.txt).  Here a WAVE owns one (16-row tile, 16-stream tile) accumulator tile for
 // the whole contraction exactly like k_pgemm -- per group one MFMA, four converts and three packed operations, the
 // g-ascending add of tensor.rs:53-60 done by the lane that holds the accumulator -- but sized for decode:
-//   * one row tile x one stream tile per wave (SwiGLU: the w1 and the w3 tile of 16 hidden units), so a 256-tile matrix
-//     gives 512 waves, two per CU on different SIMDs (k_pgemm's 2 x 2 tiles would leave half the CUs idle);
+//   * one row tile x one stream tile per wave, so a 256-tile matrix gives 512 waves, two per CU on different SIMDs (k_pgemm's
+//     2 x 2 tiles would leave half the CUs idle);
 //   * a DEEP register ring (16 groups = 16 KiB of weights per wave in flight): with one wave per SIMD the whole register
 //     file is there for it, and 512 waves x 16 KiB = 8 MB is what the HBM stream needs to stay busy;
-//   * the group scales of the wave's row tile(s) and stream tile travel as one float4 load per tile per DEPTH groups
-//     (chunk k + 1 requested at the head of ring iteration k, committed to a double-buffered wave-private LDS slice at its
-//     end) and are read back per group (ds_read_b128 / b32, broadcast): 2 VMEM instructions per group instead of 4, and
-//     no DPP broadcast.  (LDS-DMA for the scale tiles was tried first: with a global_load_lds anywhere in the function
-//     hipcc waits vmcnt(0) at the head of the ring loop -- the guide's caveat -- and the ring never runs ahead);
-//   * SwiGLU epilogue quantizes hb on the spot (tensor.rs:91-119): the four waves of a workgroup hold the 64 hidden units
-//     of one quantization group for the same 16 streams, so W2's operand leaves this kernel packed and the separate
-//     k_bquant_split<PRO_QUANT> launch (4.8 us per layer) is gone;
-//   * classifier epilogue: logits + per-stream argmax slot per wave (sampler.rs:57-59 last-maximum rule).
+//   * the group scales of the wave's row tile and stream tile travel as one float4 load per tile per DEPTH groups
+//     (chunk k + 1 requested at the head of ring iteration k, committed to a wave-private LDS slice at its end) and are read
+//     back per group (ds_read_b128 / b32, broadcast): 2 VMEM instructions per group instead of 4, and no DPP broadcast.
+//     (LDS-DMA for the scale tiles was tried first: with a global_load_lds anywhere in the function hipcc waits vmcnt(0) at
+//     the head of the ring loop -- the guide's caveat -- and the ring never runs ahead);
+//   * B operand (the step's packed int8 activations): every wave pulls its B fragments from L2 inside its ring, waves
+//     numbered stream-tile-minor over the grid (the two stream tiles of a row tile are neighbouring waves and share the
+//     weight lines through L1).
+// The QKV, W1|W3 (hb quantized in the epilogue) and classifier launches in this form, and the B operand staged in LDS, lost
+// their same-box A/B to k_bgemm (profiles/r04_batch32_dgemm.md); so did a 32-group ring against 16 (r06, batch 32: 9,631 /
+// 9,592 / 9,546 vs 9,813 / 9,801 / 9,750 tok/s -- not request depth).
 // Same operations in the same order per (row, stream) as k_bgemm / k_gemv: bit-identical results.
 // ------------------------------------------------------------------------------------------------
 typedef unsigned dg_v4u __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ v4i dg_as_v4i(dg_v4u v) { return (v4i){(int)v.x, (int)v.y, (int)v.z, (int)v.w}; }
-// B operand (the step's packed int8 activations) of a workgroup:
-//   BMODE 0  every wave pulls its B fragments from L2 inside its ring (waves numbered stream-tile-minor over the grid: the two
-//            stream tiles of a row tile are neighbouring waves and share the weight lines through L1)
-//   BMODE 1  the workgroup's waves work on ONE stream tile, staged in LDS once (ng KiB); the nst workgroups of a row group get
-//            block ids 8 apart -- the same XCD under the observed round-robin placement -- and share the weights through its L2
-//   BMODE 2  BOTH stream tiles in LDS (2 ng KiB, one workgroup per CU) and every wave computes both (PT = 2): a weight
-//            fragment is requested ONCE per CU and feeds two MFMAs.  (Measured first: the two stream tiles as two waves
-//            sharing the weight lines "through L1" -- both requests travel to L2, the CU's fill path carries the weights
-//            twice and saturates at ~32 GB/s per CU: W1|W3 25.7-27.5 us, classifier 148 us whatever the depth or balance.)
-// LDS per workgroup: [BMODE tiles] + per wave two chunks (double buffer) of DEPTH groups x 16 scales for each of its RT row
-// tiles and PT stream tiles + [2][4][16] group maxima of the fused quantizer
-__host__ __device__ inline size_t dgemm_smem_bytes(int rt, int waves, int depth, int bmode, int ng) {
-    const int pt = bmode == 2 ? 2 : 1;
-    return (size_t)bmode * ng * 1024 + 4 * ((size_t)waves * (rt + pt) * depth * 16 + 2 * 4 * 16);
-}
+constexpr int kDgWaves = 2;                                      // waves per workgroup
+// LDS per workgroup: per wave the DEPTH groups x 16 scales of its row tile and of its stream tile
+__host__ __device__ inline size_t dgemm_smem_bytes(int depth) { return 4 * (size_t)kDgWaves * 2 * depth * 16; }
 
-// EPI_SWIGLU: RT = 2 (the w1 and the w3 tile of 16 hidden units); the fused quantizer (a.pack_q) needs the four unit tiles of a
-// quantization group of the hidden vector in one workgroup: 4 waves.
 // A wave walks its row tasks (rtask, rtask + rstride, ...) as ONE stream of groups: the ring, the scale chunks and the B
-// prefetch run across task boundaries (the classifier gives every wave ~10-40 tasks; restarting the ring per task left the
-// HBM stream idle for a round trip per 64 groups).  Needs ng % DEPTH == 0 (host).
-__device__ __attribute__((noinline)) void dg_fill_lds(const v4i* src, char* lds, int kib, int wave, int nwaves, int lane) {
-    for (int g = wave; g < kib; g += nwaves)
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + (size_t)g * 64 + lane),
-                                         (__attribute__((address_space(3))) void*)(lds + (size_t)g * 1024), 16, 0, 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-}
-// developer ablation of k_dgemm, compile-time only (-DQ3_DABLATE=bits; results are wrong by construction, only time is read):
-// 1 no weight (A) loads, 2 no convert / scale / add chain, 4 no MFMAs, 8 no B fragment reads (LDS or L2)
-#ifdef Q3_DABLATE
-#define Q3_DABL(bit) ((Q3_DABLATE & (bit)) != 0)
-#else
-#define Q3_DABL(bit) false
-#endif
-template <int EPI, int DEPTH, int WAVES, int BMODE>
-__global__ __launch_bounds__(WAVES * 64) void k_dgemm(const BGemmArgs a) {
-    constexpr int RT = (EPI == EPI_SWIGLU) ? 2 : 1;
-    constexpr int PT = (BMODE == 2) ? 2 : 1;                     // stream tiles per wave
+// prefetch run across task boundaries (restarting the ring per task left the HBM stream idle for a round trip per 64 groups).
+// Needs ng % DEPTH == 0 (host).
+template <int DEPTH>
+__global__ __launch_bounds__(kDgWaves * 64) void k_dgemm(const BGemmArgs a) {
+    constexpr int WAVES = kDgWaves;
+    constexpr int RT = 1, PT = 1;                                // row tiles / stream tiles per wave
     // scale chunk = the DEPTH groups of one ring iteration, requested in stage 0 of the iteration BEFORE (so it travels with
     // the fragments of the same groups: a chunk requested only 8 groups ahead of its use made every commit wait out a full
     // memory round trip and drained the ring to 8 groups whatever DEPTH was -- r04 ablation: 12 us of a 28 us W1|W3 launch),
     // committed to the wave's single LDS slice in the last stage, after the last scale read of the current chunk
     constexpr int CH = DEPTH;
-    static_assert(DEPTH * 4 <= 128, "a scale chunk is two float4 per lane at most");
-    constexpr int SCN = (CH * 4 + 63) / 64;                      // float4 of a tile's scale chunk per lane (1; 2 for the 32-group ring)
+    static_assert(DEPTH * 4 <= 64, "a scale chunk is one float4 per lane");
     constexpr int CF = CH * 16;                                  // floats per scale chunk (CH groups x 16 rows / streams)
-    static_assert(DEPTH % CH == 0, "whole chunks per ring iteration");
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int q = lane >> 4, s = lane & 15;
     const int ng = a.ng;
-    const int nst = (a.n_streams + 15) >> 4;                    // stream tiles (1 or 2; BMODE 2: 2)
+    const int nst = (a.n_streams + 15) >> 4;                    // stream tiles (1 or 2)
     const size_t tile_v4 = (size_t)ng * 64;                      // v4i per packed tile (weights or activations)
-    float* lsc0 = (float*)(smem_raw + (size_t)BMODE * ng * 1024);
-    float* lsc = lsc0 + (size_t)wave * (RT + PT) * CF;          // [RT row tiles + PT stream tiles][CF]
-    float* red = lsc0 + (size_t)WAVES * (RT + PT) * CF;         // SwiGLU: [2 stream tiles][4 unit tiles][16 streams] maxima
+    float* lsc = (float*)smem_raw + (size_t)wave * (RT + PT) * CF;   // [RT row tiles + PT stream tiles][CF]
     const int nrt = a.ntiles / RT;                               // row tasks
-    int rtask, rstride, pt, slot, ri = wave;                     // ri: row task of the wave inside the workgroup
-    if constexpr (BMODE == 0) {
-        const int t = blockIdx.x * WAVES + wave;
-        rtask = t / nst;
-        pt = t - rtask * nst;
-        rstride = ((int)gridDim.x * WAVES) / nst;                // (gridDim.x * WAVES is a multiple of nst: host)
-        slot = rtask;
-    } else if constexpr (BMODE == 1) {
-        const int b = blockIdx.x;
-        int rg = b / nst;
-        pt = b - rg * nst;
-        if (nst == 2 && (b | 15) < (int)gridDim.x) { rg = (b >> 4) * 8 + (b & 7); pt = (b >> 3) & 1; }
-        rtask = rg * WAVES + wave;
-        rstride = ((int)gridDim.x / nst) * WAVES;
-        slot = rtask;
-    } else {
-        pt = 0;                                                  // (both stream tiles)
-        rtask = (int)blockIdx.x * WAVES + wave;
-        rstride = (int)gridDim.x * WAVES;
-        slot = rtask;
-    }
-    const v4i* lb = (const v4i*)smem_raw;                        // the stream tile(s) in LDS: [PT][ng][64 lanes]
+    const int t = blockIdx.x * WAVES + wave;
+    const int rtask = t / nst;
+    const int pt = t - rtask * nst;
     const v4i* xbase = (const v4i*)a.xq + (size_t)pt * tile_v4;
-    const v4f* gxs = (const v4f*)(a.xs + (size_t)pt * ng * 16);  // (PT = 2: the second tile's scales follow at ng * 16 floats)
-    if constexpr (BMODE != 0) {
-        // activations -> LDS by LDS-DMA: ng KiB per stream tile, wave w copies every WAVES-th KiB, every request in flight at
-        // once (through registers it was 16 requests per wave and round trip: three dependent round trips before the first
-        // MFMA of the W1|W3 launch).  The copy lives in a function of its own: with a global_load_lds in THIS function hipcc
-        // waits vmcnt(0) at the head of the ring loop (see the header comment); a call boundary resets its bookkeeping.
-        const int kib = BMODE * ng;                              // BMODE 2: the two tiles are adjacent in a.xq
-        dg_fill_lds((const v4i*)a.xq + (BMODE == 2 ? 0 : (size_t)pt * tile_v4), smem_raw, kib, wave, WAVES, lane);
-        __syncthreads();
-    }
-    unsigned long long best[PT];                                 // EPI_LOGITS: running argmax key of stream s (over this lane's rows)
-#pragma unroll
-    for (int p = 0; p < PT; ++p) best[p] = 0ull;
+    const v4f* gxs = (const v4f*)(a.xs + (size_t)pt * ng * 16);
+    const int rstride = ((int)gridDim.x * WAVES) / nst;          // (gridDim.x * WAVES is a multiple of nst)
     if (rtask < nrt) {
         const int ntk = (nrt - rtask + rstride - 1) / rstride;   // row tasks of this wave
-        int sl[SCN];                                             // scale chunk: float4 indices of this lane (upper lanes idle)
-#pragma unroll
-        for (int i = 0; i < SCN; ++i) sl[i] = min(lane + 64 * i, CH * 4 - 1);
-        const int nsv = ng * 4;                                  // float4 per scale tile
+        const int sl = min(lane, CH * 4 - 1);                    // scale chunk: float4 index of this lane (upper lanes idle)
         // fragments by buffer loads: resource = the packed matrix (SGPRs), scalar offset = tile * ng KiB + group * 1 KiB, vector
         // offset = lane * 16 -- no vector ALU in the address path (flat global loads cost a 64-bit v_lshl_add per request)
         const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc((void*)a.wq, 0, 0x7fffffff, 0x00020000);
@@ -1260,35 +1169,26 @@ __global__ __launch_bounds__(WAVES * 64) void k_dgemm(const BGemmArgs a) {
         const int tile_b = ng << 10;                             // bytes per packed tile
         int cur = rtask, nxt = ntk > 1 ? rtask + rstride : rtask;        // current / next row task (a wave without a next one re-reads)
         int k = 0;
-        v4f sc[RT + PT][SCN];                                    // scale chunk in flight (global -> registers -> LDS)
+        v4f sc[RT + PT];                                         // scale chunk in flight (global -> registers -> LDS)
         auto chunk_load = [&](int task, int c) {                 // chunk c = groups [c*CH, +CH) of row task `task`
             const v4f* gws = (const v4f*)(a.ws + (size_t)(task * RT) * ng * 16);
-#pragma unroll
-            for (int i = 0; i < SCN; ++i) {
-                const int f0 = c * (CH * 4) + sl[i];
-#pragma unroll
-                for (int rt = 0; rt < RT; ++rt) sc[rt][i] = (gws + (size_t)rt * nsv)[f0];
-#pragma unroll
-                for (int p = 0; p < PT; ++p) sc[RT + p][i] = (gxs + (size_t)p * nsv)[f0];
-            }
+            const int f0 = c * (CH * 4) + sl;
+            sc[0] = gws[f0];
+            sc[RT] = gxs[f0];
         };
         auto chunk_commit = [&]() {
+            if (lane < CH * 4) {
 #pragma unroll
-            for (int i = 0; i < SCN; ++i) {
-                if (lane + 64 * i < CH * 4) {
-#pragma unroll
-                    for (int kk = 0; kk < RT + PT; ++kk) ((v4f*)(lsc + (size_t)kk * CF))[lane + 64 * i] = sc[kk][i];
-                }
+                for (int kk = 0; kk < RT + PT; ++kk) ((v4f*)(lsc + (size_t)kk * CF))[lane] = sc[kk];
             }
         };
-        v4i fa[DEPTH][RT], fb[BMODE != 0 ? 1 : DEPTH];
+        v4i fa[DEPTH][RT], fb[DEPTH];
         auto load_ab = [&](int slot_, int task, int g) {
             const int goff = g << 10;
 #pragma unroll
             for (int rt = 0; rt < RT; ++rt)
-                fa[slot_][rt] = Q3_DABL(1) ? (v4i){lane, goff, task, rt}
-                                           : dg_as_v4i(__builtin_amdgcn_raw_buffer_load_b128(wr, lane << 4, (task * RT + rt) * tile_b + goff, 0));
-            if constexpr (BMODE == 0) fb[slot_] = Q3_DABL(8) ? (v4i){lane, goff, 1, 2} : dg_as_v4i(__builtin_amdgcn_raw_buffer_load_b128(xr, lane << 4, goff, 0));
+                fa[slot_][rt] = dg_as_v4i(__builtin_amdgcn_raw_buffer_load_b128(wr, lane << 4, (task * RT + rt) * tile_b + goff, 0));
+            fb[slot_] = dg_as_v4i(__builtin_amdgcn_raw_buffer_load_b128(xr, lane << 4, goff, 0));
         };
         chunk_load(cur, 0);                                      // oldest loads
 #pragma unroll
@@ -1303,29 +1203,18 @@ __global__ __launch_bounds__(WAVES * 64) void k_dgemm(const BGemmArgs a) {
         v4i cc[RT][PT], cn[RT][PT];
         v4f wsc[RT], wsn[RT];
         float xsc[PT], xsn[PT];
-        v4i bc[PT], bn[PT];                                      // BMODE 1/2: B fragments of the group whose MFMAs are issued next
-#pragma unroll
-        for (int p = 0; p < PT; ++p) bc[p] = bn[p] = (v4i){0, 0, 0, 0};
-        auto bfrag = [&](v4i (&b)[PT], int g) {
-            if constexpr (BMODE != 0) {
-#pragma unroll
-                for (int p = 0; p < PT; ++p) b[p] = Q3_DABL(8) ? (v4i){lane, g, p, 3} : lb[(size_t)p * tile_v4 + (size_t)(g >= ng ? g - ng : g) * 64 + lane];
-            }
-        };
-        auto mfma_group = [&](v4i (&c)[RT][PT], int slot_, const v4i (&bl)[PT]) {
+        auto mfma_group = [&](v4i (&c)[RT][PT], int slot_) {
 #pragma unroll
             for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
                 for (int p = 0; p < PT; ++p)
-                    c[rt][p] = Q3_DABL(4) ? fa[slot_][rt] + (BMODE != 0 ? bl[p] : fb[BMODE != 0 ? 0 : slot_])
-                                          : __builtin_amdgcn_mfma_i32_16x16x64_i8(fa[slot_][rt], BMODE != 0 ? bl[p] : fb[BMODE != 0 ? 0 : slot_], (v4i){0, 0, 0, 0}, 0, 0, 0);
+                    c[rt][p] = __builtin_amdgcn_mfma_i32_16x16x64_i8(fa[slot_][rt], fb[slot_], (v4i){0, 0, 0, 0}, 0, 0, 0);
         };
         auto scales = [&](v4f (&w)[RT], float (&x)[PT], int u) {      // scales of group u of the chunk in LDS
-            const float* b0 = lsc;
 #pragma unroll
-            for (int rt = 0; rt < RT; ++rt) w[rt] = *(const v4f*)(b0 + rt * CF + u * 16 + 4 * q);
+            for (int rt = 0; rt < RT; ++rt) w[rt] = *(const v4f*)(lsc + rt * CF + u * 16 + 4 * q);
 #pragma unroll
-            for (int p = 0; p < PT; ++p) x[p] = b0[(RT + p) * CF + u * 16 + s];
+            for (int p = 0; p < PT; ++p) x[p] = lsc[(RT + p) * CF + u * 16 + s];
         };
         auto math_group = [&](const v4i (&cg)[RT][PT], const v4f (&w)[RT], const float (&x)[PT]) {
 #pragma unroll
@@ -1333,7 +1222,6 @@ __global__ __launch_bounds__(WAVES * 64) void k_dgemm(const BGemmArgs a) {
 #pragma unroll
                 for (int p = 0; p < PT; ++p) {
                     const v4i c = cg[rt][p];
-                    if (Q3_DABL(2)) { acc[rt][p].x = __int_as_float(__float_as_int(acc[rt][p].x) ^ c.x ^ c.y ^ c.z ^ c.w); continue; }
                     // tensor.rs:59  ((dot as f32) * ws) * xs, then the g-ascending add; pairs (rows 4q, 4q+1), (4q+2, 4q+3)
                     pk2 t01 = (pk2){(float)c.x, (float)c.y} * (pk2){w[rt].x, w[rt].y};
                     pk2 t23 = (pk2){(float)c.z, (float)c.w} * (pk2){w[rt].z, w[rt].w};
@@ -1354,92 +1242,26 @@ __global__ __launch_bounds__(WAVES * 64) void k_dgemm(const BGemmArgs a) {
                 for (int p = 0; p < PT; ++p) cc[rt][p] = cn[rt][p];
             }
 #pragma unroll
-            for (int p = 0; p < PT; ++p) { xsc[p] = xsn[p]; if constexpr (BMODE != 0) bc[p] = bn[p]; }
+            for (int p = 0; p < PT; ++p) xsc[p] = xsn[p];
         };
-        // ---- epilogue of row task `task`: lane (s, q) owns out[stream (pt + p)*16 + s][rows 4q .. 4q+3 of the row tile]
+        // ---- epilogue of row task `task`: lane (s, q) adds its accumulators to x[stream pt*16 + s][rows 4q .. 4q+3 of the row tile]
         auto epilogue = [&](int task) {
-#pragma unroll
-            for (int p = 0; p < PT; ++p) {
-                const int tp = pt + p;                            // stream tile
-                const int sb = tp * 16 + s;
-                const bool live = sb < a.n_streams;
-                if constexpr (EPI == EPI_SWIGLU) {
-                    // packed tiles alternate w1 | w3 of the same 16 hidden units            layers.rs:468-475
-                    v4f o;
-                    const v4f g1 = acc[0][p], up = acc[RT - 1][p];
-                    { const float den = 1.0f + q3_expf(-g1.x); o.x = (g1.x * (1.0f / den)) * up.x; }
-                    { const float den = 1.0f + q3_expf(-g1.y); o.y = (g1.y * (1.0f / den)) * up.y; }
-                    { const float den = 1.0f + q3_expf(-g1.z); o.z = (g1.z * (1.0f / den)) * up.z; }
-                    { const float den = 1.0f + q3_expf(-g1.w); o.w = (g1.w * (1.0f / den)) * up.w; }
-                    if (a.out0 != nullptr && live) *(v4f*)(a.out0 + (size_t)sb * a.out0_stride + (size_t)task * 16 + 4 * q) = o;
-                    if (a.pack_q != nullptr) {
-                        // hq = quantize(hb) (tensor.rs:91-119) for W2: group = the 64 hidden units of this workgroup (unit tile =
-                        // wave), stream s; the packed operand piece (q' = wave, s) takes this lane's four bytes at 4q.  (host: one
-                        // row task per wave, four waves per workgroup)
-                        float* rd = red + p * 64;
-                        float m = fmaxf(fmaxf(fabsf(o.x), fabsf(o.y)), fmaxf(fabsf(o.z), fabsf(o.w)));
-                        m = fmaxf(m, __shfl_xor(m, 16));
-                        m = fmaxf(m, __shfl_xor(m, 32));
-                        if (q == 0) rd[ri * 16 + s] = m;
-                        __syncthreads();
-                        m = fmaxf(fmaxf(rd[s], rd[16 + s]), fmaxf(rd[32 + s], rd[48 + s]));
-                        const float scale = m / 127.0f;
-                        int q0 = 0, q1 = 0, q2 = 0, q3 = 0;
-                        if (scale != 0.0f) {
-                            q0 = quant_round_i8(o.x / scale);
-                            q1 = quant_round_i8(o.y / scale);
-                            q2 = quant_round_i8(o.z / scale);
-                            q3 = quant_round_i8(o.w / scale);
-                        }
-                        const int gh = task >> 2, ngh = a.ntiles >> 3;               // group index / groups per row of W2's contraction
-                        if (live) {
-                            int8_t* dst = a.pack_q + ((((size_t)tp * ngh + gh) * 64 + (ri * 16 + s)) * 16 + 4 * q);
-                            *(int*)dst = (q0 & 0xff) | ((q1 & 0xff) << 8) | ((q2 & 0xff) << 16) | ((q3 & 0xff) << 24);
-                            if (ri == 0 && q == 0) a.pack_s[((size_t)tp * ngh + gh) * 16 + s] = scale;
-                        }
-                    }
-                } else {
-                    const int r0 = task * 16 + 4 * q;
-                    const v4f o = acc[0][p];
-                    if constexpr (EPI == EPI_QKV) {
-                        if (live) {
-                            float* dst;
-                            if (r0 < a.rows0) dst = a.out0 + (size_t)sb * a.out0_stride + r0;
-                            else if (r0 < a.rows0 + a.rows1) dst = a.out1 + (size_t)sb * a.out1_stride + (r0 - a.rows0);
-                            else dst = a.out2 + (size_t)sb * a.out2_stride + (size_t)a.st[sb].pos * a.pos_stride + (r0 - a.rows0 - a.rows1);
-                            *(v4f*)dst = o;
-                        }
-                    } else if constexpr (EPI == EPI_RESID) {
-                        if (live) {
-                            v4f* dst = (v4f*)(a.out0 + (size_t)sb * a.out0_stride + r0);
-                            v4f x = *dst;
-                            x.x = x.x + o.x; x.y = x.y + o.y; x.z = x.z + o.z; x.w = x.w + o.w;      // layers.rs:249-259
-                            *dst = x;
-                        }
-                    } else if constexpr (EPI == EPI_LOGITS) {
-                        if (live) {
-                            if (a.out0 != nullptr) *(v4f*)(a.out0 + (size_t)sb * a.out0_stride + r0) = o;
-                            const float ov[4] = {o.x, o.y, o.z, o.w};
-#pragma unroll
-                            for (int i = 0; i < 4; ++i) {
-                                const unsigned long long key = ((unsigned long long)total_order_key(ov[i]) << 32) | (unsigned)(r0 + i);
-                                best[p] = key > best[p] ? key : best[p];
-                            }
-                        }
-                    } else {
-                        if (live) *(v4f*)(a.out0 + (size_t)sb * a.out0_stride + r0) = o;
-                    }
-                }
+            const int sb = pt * 16 + s;
+            const int r0 = task * 16 + 4 * q;
+            const v4f o = acc[0][0];
+            if (sb < a.n_streams) {
+                v4f* dst = (v4f*)(a.out0 + (size_t)sb * a.out0_stride + r0);
+                v4f x = *dst;
+                x.x = x.x + o.x; x.y = x.y + o.y; x.z = x.z + o.z; x.w = x.w + o.w;      // layers.rs:249-259
+                *dst = x;
             }
         };
-        // software pipeline (k_pgemm's): stage u requests the group DEPTH - 1 ahead, issues the MFMAs and the LDS scale reads
-        // of the next group (BMODE 1/2: and the B fragment of the one after), then runs the convert / scale / add chain of
-        // its own group while those are in flight.  An iteration = DEPTH groups of one row task; it also carries the NEXT
-        // iteration's scale chunk: requested in stage 0, committed to the other LDS buffer in the last stage, just before
-        // that chunk's first scales are read.  In the last iteration of a row task "ahead" means the next row task.
-        bfrag(bc, 0);
-        mfma_group(cc, 0, bc);
-        bfrag(bc, 1);
+        // software pipeline (k_pgemm's): stage u requests the group DEPTH - 1 ahead, issues the MFMA and the LDS scale reads of
+        // the next group, then runs the convert / scale / add chain of its own group while those are in flight.  An iteration =
+        // DEPTH groups of one row task; it also carries the NEXT iteration's scale chunk: requested in stage 0, committed to the
+        // wave's LDS slice in the last stage, just before that chunk's first scales are read.  In the last iteration of a row
+        // task "ahead" means the next row task.
+        mfma_group(cc, 0);
         scales(wsc, xsc, 0);
         int g0 = 0;
         for (;;) {
@@ -1451,8 +1273,7 @@ __global__ __launch_bounds__(WAVES * 64) void k_dgemm(const BGemmArgs a) {
                 if (u == 0) load_ab(DEPTH - 1, cur, g0 + DEPTH - 1);
                 else load_ab(u - 1, ptask, pg0 + u + DEPTH - 1);
                 if (u == 0) chunk_load(ptask, (pg0 + DEPTH) / CH);    // the next iteration's scales (maybe the next task's chunk 0)
-                mfma_group(cn, (u + 1) % DEPTH, bc);
-                bfrag(bn, g0 + u + 2);
+                mfma_group(cn, (u + 1) % DEPTH);
                 if (u == DEPTH - 1) { wave_lds_sync(); chunk_commit(); wave_lds_sync(); scales(wsn, xsn, 0); }
                 else scales(wsn, xsn, u + 1);
                 math_group(cc, wsc, xsc);
@@ -1471,23 +1292,6 @@ __global__ __launch_bounds__(WAVES * 64) void k_dgemm(const BGemmArgs a) {
                 cur = nxt;
                 nxt = k + 1 < ntk ? cur + rstride : cur;
             }
-        }
-    }
-    if constexpr (EPI == EPI_LOGITS) {
-        // sampler.rs:57-59 (last maximum): max over the rows this wave saw for stream s -- lanes s, s+16, s+32, s+48 --
-        // one slot per wave of a stream tile (slot = its first row task: < rstride); k_next_batch reduces the slots
-#pragma unroll
-        for (int p = 0; p < PT; ++p) {
-            unsigned long long bp = best[p];
-#pragma unroll
-            for (int m = 16; m < 64; m <<= 1) {
-                const unsigned lo = __shfl_xor((unsigned)bp, m);
-                const unsigned hi = __shfl_xor((unsigned)(bp >> 32), m);
-                const unsigned long long o = ((unsigned long long)hi << 32) | lo;
-                bp = o > bp ? o : bp;
-            }
-            const int sbl = (pt + p) * 16 + s;
-            if (q == 0 && sbl < a.n_streams && slot < a.nslots) a.slots[(size_t)sbl * a.nslots + slot] = bp;
         }
     }
 }

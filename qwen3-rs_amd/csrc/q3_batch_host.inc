@@ -31,8 +31,6 @@ struct BatchCtx {
     float *key = nullptr, *value = nullptr, *att = nullptr;
     int8_t* xq_p = nullptr;
     float* xs_p = nullptr;
-    int8_t* xq_p2 = nullptr;     // second packed operand: hq = quantize(hb), written by k_dgemm's SwiGLU epilogue while it reads xq_p
-    float* xs_p2 = nullptr;
     State* st = nullptr;
     unsigned long long* slots = nullptr;
     int nslots = 0, nslots_used = 0;
@@ -76,59 +74,16 @@ BGemmFn pick_bgemm_nj(int NJ) {
 }
 template <int EPI>
 BGemmFn pick_pgemm(int RT, int PT) {
-    // (the planner picks RT, PT in {1, 2}; the 4-wide forms are reachable through Q3_PGEMM_TILE in the developer build only)
-#ifdef Q3_DEV
-    if (RT == 4) return PT == 2 ? (BGemmFn)k_pgemm<EPI, 4, 2, 4> : (PT == 1 ? (BGemmFn)k_pgemm<EPI, 4, 1, 6> : nullptr);
-    if (RT == 2 && PT == 4) return (BGemmFn)k_pgemm<EPI, 2, 4, 4>;
-    if constexpr (EPI != EPI_SWIGLU) { if (RT == 1 && PT == 4) return (BGemmFn)k_pgemm<EPI, 1, 4, 4>; }
-#endif
     if (RT == 2) return PT == 2 ? (BGemmFn)k_pgemm<EPI, 2, 2, 6> : (PT == 1 ? (BGemmFn)k_pgemm<EPI, 2, 1, 8> : nullptr);
     if constexpr (EPI != EPI_SWIGLU) {
         if (RT == 1) return PT == 2 ? (BGemmFn)k_pgemm<EPI, 1, 2, 8> : (PT == 1 ? (BGemmFn)k_pgemm<EPI, 1, 1, 8> : nullptr);
     }
     return nullptr;
 }
-// k_dgemm configuration of one launch (q3_batch.h: BMODE 0 B fragments from L2, 1 one stream tile in LDS, 2 both)
-struct DgCfg { int depth, waves, rt, bmode; BGemmFn fn; };
-// W1|W3 forms (Q3_DGEMM_W13_MODE): 1 = both stream tiles in LDS and in every wave, 4 waves = the four unit tiles of a
-// quantization group, W2's operand quantized in the epilogue; 2 = the same with 3 waves (one workgroup per CU on the 8B
-// shape, no fused quantizer); 0 = one stream tile per workgroup, 4 waves, fused
-int dgemm_w13_mode(int NT) { return NT == 2 ? dev_knob("Q3_DGEMM_W13_MODE", 1) : 0; }
-DgCfg dgemm_cfg(int epi, int ng, int NT) {
-    const bool lds_ok = dev_knob("Q3_DGEMM_BLDS", 1) != 0;
-    const bool fits1 = ng <= 64 && lds_ok, fits2 = fits1 && NT == 2;
-    if (ng % 8 != 0) return {0, 0, 0, 0, nullptr};
-    const int deep = dev_knob("Q3_DGEMM_DEEP", 1);               // ring depth: 0 = 8 groups, 1 = 16
-    (void)fits2; (void)deep;
-    switch (epi) {
-#ifdef Q3_DEV   // (the product runs k_dgemm for the residual launches only, Q3_DGEMM_FAMILIES = 2: profiles/r04_batch32_dgemm.md)
-        case EPI_SWIGLU: {
-            const int mode = dgemm_w13_mode(NT);
-            if (fits2 && mode == 1 && deep && ng % 16 == 0) return {16, 4, 2, 2, (BGemmFn)k_dgemm<EPI_SWIGLU, 16, 4, 2>};
-            if (fits2 && mode == 1) return {8, 4, 2, 2, (BGemmFn)k_dgemm<EPI_SWIGLU, 8, 4, 2>};
-            if (fits2 && mode == 2) return {8, 3, 2, 2, (BGemmFn)k_dgemm<EPI_SWIGLU, 8, 3, 2>};
-            if (fits1) return {8, 4, 2, 1, (BGemmFn)k_dgemm<EPI_SWIGLU, 8, 4, 1>};
-            return {0, 0, 0, 0, nullptr};
-        }
-        case EPI_LOGITS:
-            if (fits2 && deep && ng % 16 == 0) return {16, 8, 1, 2, (BGemmFn)k_dgemm<EPI_LOGITS, 16, 8, 2>};
-            if (fits2) return {8, 8, 1, 2, (BGemmFn)k_dgemm<EPI_LOGITS, 8, 8, 2>};
-            if (fits1) return {8, 4, 1, 1, (BGemmFn)k_dgemm<EPI_LOGITS, 8, 4, 1>};
-            return {8, 2, 1, 0, (BGemmFn)k_dgemm<EPI_LOGITS, 8, 2, 0>};
-        case EPI_QKV:
-            if (deep == 2 && ng % 32 == 0) return {32, 2, 1, 0, (BGemmFn)k_dgemm<EPI_QKV, 32, 2, 0>};
-            if (ng % 16 == 0) return {16, 2, 1, 0, (BGemmFn)k_dgemm<EPI_QKV, 16, 2, 0>};
-            return {8, 2, 1, 0, (BGemmFn)k_dgemm<EPI_QKV, 8, 2, 0>};
-#endif
-        case EPI_RESID:
-#ifdef Q3_DEV
-            // 32-group ring (r06 A/B, Q3_DGEMM_DEEP=2): 9,631 / 9,592 / 9,546 vs 9,813 / 9,801 / 9,750 tok/s for 16 -- not request depth
-            if (deep == 2 && ng % 32 == 0) return {32, 2, 1, 0, (BGemmFn)k_dgemm<EPI_RESID, 32, 2, 0>};
-#endif
-            if (ng % 16 == 0) return {16, 2, 1, 0, (BGemmFn)k_dgemm<EPI_RESID, 16, 2, 0>};
-            return {8, 2, 1, 0, (BGemmFn)k_dgemm<EPI_RESID, 8, 2, 0>};
-        default: return {0, 0, 0, 0, nullptr};
-    }
+// k_dgemm of a residual launch (Wo, W2) at group 64: the 16-group ring where the row length allows it, else 8; nullptr: k_bgemm
+BGemmFn pick_dgemm(int ng, int& depth) {
+    depth = ng % 16 == 0 ? 16 : (ng % 8 == 0 ? 8 : 0);
+    return depth == 16 ? (BGemmFn)k_dgemm<16> : (depth == 8 ? (BGemmFn)k_dgemm<8> : nullptr);
 }
 template <int EPI>
 BGemmFn pick_bgemm(int RT, int NT, int NJ) {
@@ -183,7 +138,7 @@ void batch_free(q3_engine* e) {
     if (!b) return;
     if (b->graph_exec) (void)hipGraphExecDestroy(b->graph_exec);
     if (b->graph) (void)hipGraphDestroy(b->graph);
-    void* dptrs[] = {b->att_pf, b->qn, b->pq, b->ps, b->x, b->q, b->kraw, b->xb, b->hb, b->logits, b->key, b->value, b->att, b->xq_p, b->xs_p, b->xq_p2, b->xs_p2,
+    void* dptrs[] = {b->att_pf, b->qn, b->pq, b->ps, b->x, b->q, b->kraw, b->xb, b->hb, b->logits, b->key, b->value, b->att, b->xq_p, b->xs_p,
                      b->st, b->slots, b->out_tokens, b->stamps, b->d_sampler, b->d_probs, b->d_sp, b->d_keys};
     for (void* p : dptrs)
         if (p) (void)hipFree(p);
@@ -207,14 +162,9 @@ int batch_build_plan(q3_engine* e, int n, bool prefill = false) {
     const int NT = n <= 16 ? 1 : 2, NJ = G / 64;
     // dense prefill (round 3): more than 32 positions per weight pass -> every wave owns an output tile (k_pgemm)
     const bool dense = prefill && n > 32;
-    // batched decode / short prefill blocks at group 64: in-lane accumulation (k_dgemm, round 4); Q3_BATCH_DGEMM=0 keeps k_bgemm
+    // batched decode / short prefill blocks at group 64: in-lane accumulation for the residual launches (k_dgemm, round 4);
+    // Q3_BATCH_DGEMM=0 keeps k_bgemm
     const bool dgemm = !dense && G == 64 && dev_knob("Q3_BATCH_DGEMM", 1) != 0;
-    // W2's operand from W13's epilogue: when the W1|W3 launch is a k_dgemm form with four unit tiles per workgroup
-    bool fuse_hq = false;
-    if (dgemm && (H % 128) == 0 && dev_knob("Q3_BATCH_FUSE_HQ", 1) != 0 && (dev_knob("Q3_DGEMM_FAMILIES", 2) & 4) != 0) {
-        const DgCfg dc = dgemm_cfg(EPI_SWIGLU, dim / 64, NT);
-        fuse_hq = dc.fn != nullptr && dc.waves == 4;
-    }
     if (dense && G != 64) return fail(Q3_ERR_UNSUPPORTED, "dense prefill needs group_size 64");
     const int nptiles = (n + 15) / 16;
     const int att_tch = dev_knob("Q3_BATCH_ATT_TCH", 32);
@@ -299,7 +249,8 @@ int batch_build_plan(q3_engine* e, int n, bool prefill = false) {
         Ln.fam = fam;
         a.wq = b->pq + m.q_off;
         a.ws = b->ps + m.s_off;
-        if (a.xq == nullptr) { a.xq = b->xq_p; a.xs = b->xs_p; }
+        a.xq = b->xq_p;
+        a.xs = b->xs_p;
         a.ng = m.ng;
         a.ntiles = m.ntiles;
         a.n_streams = n;
@@ -314,42 +265,18 @@ int batch_build_plan(q3_engine* e, int n, bool prefill = false) {
             const long t8 = nrb * ((nptiles + 7) / 8), t4 = nrb * ((nptiles + 3) / 4), slots = 2L * e->n_cu;
             int ptw = dev_knob("Q3_PGEMM2_PT", 0);
             if (ptw != 4 && ptw != 8) ptw = t8 >= slots ? 8 : 4;
-            // Q3_PGEMM2_RT=2: 2 row tiles x 4 position tiles (one tile per wave), twice the workgroups for the matrices whose 4 x 4 tiles
-            // do not reach every CU (Wo / W2 of the 4B shape: 160 on 256 CUs) -- measured 36.1 vs 34.5 us, so not the default; not for
-            // SwiGLU (w1 | w3 pairs stay in one wave)
-            int rtw = dev_knob("Q3_PGEMM2_RT", 4) == 2 ? 2 : 4;
-            if (epi == EPI_SWIGLU || ptw == 8 || (m.ntiles % 2) != 0) rtw = 4;
-            const long nblk = (ptw == 8 ? t8 : t4) * (4 / rtw);
-            // 8 row tiles x 8 position tiles per workgroup (wave: 4 x 2 tiles, computed two row tiles at a time: 114 VGPRs, two workgroups
-            // per CU): 256 B of fragments per MFMA instead of 384.  (First cut, all eight tiles of a wave at once: ~132 VGPRs = one
-            // workgroup per CU, 30.1-30.9k tok/s against 32.1k for 4 x 8.)  Q3_PGEMM3_RT = 8 / 4 forces the choice.
-#ifdef Q3_DEV
-            {
-                const long nb8 = (m.ntiles / 8) * ((nptiles + 7) / 8);
-                const int rt8 = dev_knob("Q3_PGEMM3_RT", 0);
-                if (((rt8 == 8) || (rt8 == 0 && nb8 >= 2 * slots && dev_knob("Q3_PGEMM3_RT8_DEFAULT", 0))) && ptw == 8 && (m.ntiles % 8) == 0 && (m.ng % 2) == 0 &&
-                    dev_knob("Q3_PGEMM3", 1) != 0) {
-                    Ln.kind = 11;
-                    Ln.grid = (unsigned)(nb8 < slots ? nb8 : slots);
-                    Ln.block = kP2Threads;
-                    Ln.smem = pgemm3_smem_bytes(8, 8, 1);
-                    Ln.gfn = epi == EPI_QKV ? (BGemmFn)k_pgemm3<EPI_QKV, 8, 8, 1> : (epi == EPI_RESID ? (BGemmFn)k_pgemm3<EPI_RESID, 8, 8, 1> : (BGemmFn)k_pgemm3<EPI_SWIGLU, 8, 8, 1>);
-                    if ((rc = set_max_smem((const void*)Ln.gfn, Ln.smem))) return rc;
-                    Ln.ba = a;
-                    b->plan.push_back(Ln);
-                    return Q3_OK;
-                }
-            }
-#endif
+            const long nblk = ptw == 8 ? t8 : t4;
+            // (2 row tiles x 4 position tiles per workgroup, Wo / W2 of the 4B shape: 36.1 vs 34.5 us; 8 x 8 tiles: 30.1-30.9k tok/s
+            // against 32.1k for 4 x 8 -- neither kept)
             // k_pgemm3: the same workgroup tile with 4 (4 x 4 tiles) / 2 (4 x 8) quantization groups per barrier (Q3_PGEMM3=0: k_pgemm2)
             const int gs = ptw == 4 ? 4 : 2;
-            if (rtw == 4 && (m.ng % (2 * gs)) == 0 && dev_knob("Q3_PGEMM3", 1) != 0) {
+            if ((m.ng % (2 * gs)) == 0 && dev_knob("Q3_PGEMM3", 1) != 0) {
                 Ln.kind = 11;
                 Ln.grid = (unsigned)(nblk < slots ? nblk : slots);
                 Ln.block = kP2Threads;
-                Ln.smem = pgemm3_smem_bytes(ptw, rtw, gs);
-                if (ptw == 8) Ln.gfn = epi == EPI_QKV ? (BGemmFn)k_pgemm3<EPI_QKV, 8, 4, 2> : (epi == EPI_RESID ? (BGemmFn)k_pgemm3<EPI_RESID, 8, 4, 2> : (BGemmFn)k_pgemm3<EPI_SWIGLU, 8, 4, 2>);
-                else Ln.gfn = epi == EPI_QKV ? (BGemmFn)k_pgemm3<EPI_QKV, 4, 4, 4> : (epi == EPI_RESID ? (BGemmFn)k_pgemm3<EPI_RESID, 4, 4, 4> : (BGemmFn)k_pgemm3<EPI_SWIGLU, 4, 4, 4>);
+                Ln.smem = pgemm3_smem_bytes(ptw, gs);
+                if (ptw == 8) Ln.gfn = epi == EPI_QKV ? (BGemmFn)k_pgemm3<EPI_QKV, 8, 2> : (epi == EPI_RESID ? (BGemmFn)k_pgemm3<EPI_RESID, 8, 2> : (BGemmFn)k_pgemm3<EPI_SWIGLU, 8, 2>);
+                else Ln.gfn = epi == EPI_QKV ? (BGemmFn)k_pgemm3<EPI_QKV, 4, 4> : (epi == EPI_RESID ? (BGemmFn)k_pgemm3<EPI_RESID, 4, 4> : (BGemmFn)k_pgemm3<EPI_SWIGLU, 4, 4>);
                 if ((rc = set_max_smem((const void*)Ln.gfn, Ln.smem))) return rc;
                 Ln.ba = a;
                 b->plan.push_back(Ln);
@@ -359,11 +286,8 @@ int batch_build_plan(q3_engine* e, int n, bool prefill = false) {
                 Ln.kind = 11;
                 Ln.grid = (unsigned)(nblk < slots ? nblk : slots);
                 Ln.block = kP2Threads;
-                Ln.smem = pgemm2_smem_bytes(ptw, rtw);
+                Ln.smem = pgemm2_smem_bytes(ptw);
                 if (ptw == 8) Ln.gfn = epi == EPI_QKV ? (BGemmFn)k_pgemm2<EPI_QKV, 8> : (epi == EPI_RESID ? (BGemmFn)k_pgemm2<EPI_RESID, 8> : (BGemmFn)k_pgemm2<EPI_SWIGLU, 8>);
-#ifdef Q3_DEV
-                else if (rtw == 2) Ln.gfn = epi == EPI_QKV ? (BGemmFn)k_pgemm2<EPI_QKV, 4, 2> : (BGemmFn)k_pgemm2<EPI_RESID, 4, 2>;
-#endif
                 else Ln.gfn = epi == EPI_QKV ? (BGemmFn)k_pgemm2<EPI_QKV, 4> : (epi == EPI_RESID ? (BGemmFn)k_pgemm2<EPI_RESID, 4> : (BGemmFn)k_pgemm2<EPI_SWIGLU, 4>);
                 if ((rc = set_max_smem((const void*)Ln.gfn, Ln.smem))) return rc;
                 Ln.ba = a;
@@ -377,11 +301,6 @@ int batch_build_plan(q3_engine* e, int n, bool prefill = false) {
             int RT = 2, PT = nptiles >= 2 ? 2 : 1;
             auto tasks = [&](int rt, int pt) { return (long)(m.ntiles / rt) * ((nptiles + pt - 1) / pt); };
             if (epi != EPI_SWIGLU && ((m.ntiles & 1) || tasks(RT, PT) < 8L * e->n_cu)) RT = 1;
-            { const int f = dev_knob("Q3_PGEMM_TILE", 0);
-              // A/B knob "<RT><PT>": only the instantiated tile shapes (RT, PT in {1, 2, 4}); anything else is ignored
-              const int frt = f / 10, fpt = f % 10;
-              const bool okv = (frt == 1 || frt == 2 || frt == 4) && (fpt == 1 || fpt == 2 || fpt == 4);
-              if (okv && (m.ntiles % frt) == 0 && (epi != EPI_SWIGLU || (frt & 1) == 0)) { RT = frt; PT = fpt; } }
             const long nt_ = tasks(RT, PT);
             long grid = (nt_ + 3) / 4;
             if (grid > 3L * e->n_cu) grid = 3L * e->n_cu;
@@ -398,37 +317,18 @@ int batch_build_plan(q3_engine* e, int n, bool prefill = false) {
             b->plan.push_back(Ln);
             return Q3_OK;
         }
-        // which launches take k_dgemm (bit mask Q3_DGEMM_FAMILIES: 1 QKV, 2 Wo / W2, 4 W1|W3, 8 classifier).  Default 2: same-box
-        // A/B on the 8B shape (profiles/r04_batch32_dgemm.md): the residual launches gain 3-4 % of the step, QKV (11.6 vs 12.9 us),
-        // W1|W3 with the fused quantizer (27.7 vs 22.5 + 4.8 us) and the classifier (131-136 vs 130 us) do not beat k_bgemm
-        const int fam_bit = epi == EPI_QKV ? 1 : (epi == EPI_RESID ? 2 : (epi == EPI_SWIGLU ? 4 : 8));
-        const bool fam_on = (dev_knob("Q3_DGEMM_FAMILIES", 2) & fam_bit) != 0;
-        const DgCfg dc = (dgemm && fam_on) ? dgemm_cfg(epi, m.ng, NT) : DgCfg{0, 0, 0, 0, nullptr};
-        if (dc.fn && (epi != EPI_SWIGLU || (m.ntiles % 8) == 0)) {
-            // decode, group 64: every wave owns a (row tile, stream tile) accumulator tile for the whole contraction (k_dgemm)
-            const long nrt = m.ntiles / dc.rt;
-            long grid, per_wg;                                       // per_wg: row tasks one workgroup covers per pass
-            if (dc.bmode == 0) per_wg = 0, grid = (nrt * NT + dc.waves - 1) / dc.waves;
-            else if (dc.bmode == 1) per_wg = dc.waves, grid = ((nrt + per_wg - 1) / per_wg) * NT;
-            else per_wg = dc.waves, grid = (nrt + per_wg - 1) / per_wg;
-            if (dc.bmode == 0 && NT == 2 && ((grid * dc.waves) & 1)) ++grid;
-            if (epi == EPI_LOGITS) {
-                // streaming launch: the resident set, every wave walks row tiles with a grid stride
-                long cap = (long)e->n_cu * dev_knob("Q3_DGEMM_LM_WG_PER_CU", dc.bmode == 2 ? 1 : 2);
-                if (dc.bmode == 1) cap -= cap % NT;
-                if (grid > cap) grid = cap;
-                const long nsl = dc.bmode == 0 ? grid * dc.waves / NT : (dc.bmode == 1 ? (grid / NT) * dc.waves : grid * dc.waves);
-                if (nsl > b->nslots) return fail(Q3_ERR_HIP, "argmax slot capacity");
-                a.slots = b->slots;
-                a.nslots = b->nslots;
-                b->nslots_used = (int)nsl;
-            }
-            if (epi == EPI_SWIGLU && a.pack_q != nullptr && per_wg != 4) return fail(Q3_ERR_HIP, "fused quantizer needs four unit tiles per workgroup");
+        // decode, group 64, residual launches (Wo, W2): every wave owns a (row tile, stream tile) accumulator tile for the whole
+        // contraction (k_dgemm).  Same-box A/B on the 8B shape (profiles/r04_batch32_dgemm.md): the residual launches gain 3-4 % of
+        // the step; QKV (11.6 vs 12.9 us), W1|W3 with the fused quantizer (27.7 vs 22.5 + 4.8 us) and the classifier (131-136 vs
+        // 130 us) in this form do not beat k_bgemm
+        int depth = 0;
+        const BGemmFn dfn = (dgemm && epi == EPI_RESID) ? pick_dgemm(m.ng, depth) : nullptr;
+        if (dfn) {
             Ln.kind = 10;
-            Ln.grid = (unsigned)grid;
-            Ln.block = (unsigned)dc.waves * 64;
-            Ln.smem = dgemm_smem_bytes(dc.rt, dc.waves, dc.depth, dc.bmode, m.ng);
-            Ln.gfn = dc.fn;
+            Ln.grid = (unsigned)(((long)m.ntiles * NT + kDgWaves - 1) / kDgWaves);
+            Ln.block = (unsigned)kDgWaves * 64;
+            Ln.smem = dgemm_smem_bytes(depth);
+            Ln.gfn = dfn;
             if ((rc = set_max_smem((const void*)Ln.gfn, Ln.smem))) return rc;
             Ln.ba = a;
             b->plan.push_back(Ln);
@@ -586,14 +486,12 @@ int batch_build_plan(q3_engine* e, int n, bool prefill = false) {
         {
             BGemmArgs a{};
             a.out0 = b->hb; a.out0_stride = H;
-            if (fuse_hq) { a.out0 = nullptr; a.pack_q = b->xq_p2; a.pack_s = b->xs_p2; }
             if ((rc = gemm(F_W13, EPI_SWIGLU, b->m_w13[l], a))) return rc;
         }
-        if (!fuse_hq && (rc = quant(F_W2, PRO_QUANT, b->hb, H, H, nullptr, false))) return rc;
+        if ((rc = quant(F_W2, PRO_QUANT, b->hb, H, H, nullptr, false))) return rc;
         {
             BGemmArgs a{};
             a.out0 = b->x; a.out0_stride = dim;
-            if (fuse_hq) { a.xq = b->xq_p2; a.xs = b->xs_p2; }
             if ((rc = gemm(F_W2, EPI_RESID, b->m_w2[l], a))) return rc;
         }
     }
@@ -751,10 +649,6 @@ int batch_alloc(q3_engine* e, int max_streams, uint32_t ctx_len, bool with_kv, i
     HIP_TRY(hipMalloc((void**)&b->xs_p, 4 * nt_max * 16 * (maxn / G)));
     HIP_TRY(hipMemsetAsync(b->xq_p, 0, nt_max * 16 * maxn, e->stream));          // idle stream columns: finite operands
     HIP_TRY(hipMemsetAsync(b->xs_p, 0, 4 * nt_max * 16 * (maxn / G), e->stream));
-    HIP_TRY(hipMalloc((void**)&b->xq_p2, nt_max * 16 * (size_t)H));
-    HIP_TRY(hipMalloc((void**)&b->xs_p2, 4 * nt_max * 16 * ((size_t)H / G)));
-    HIP_TRY(hipMemsetAsync(b->xq_p2, 0, nt_max * 16 * (size_t)H, e->stream));
-    HIP_TRY(hipMemsetAsync(b->xs_p2, 0, 4 * nt_max * 16 * ((size_t)H / G), e->stream));
     if (S > (size_t)dev_knob("Q3_ATT_LDS_MAX", 4096)) HIP_TRY(hipMalloc((void**)&b->att, 4 * B * c.n_heads * S));
     HIP_TRY(hipMalloc((void**)&b->st, sizeof(State) * C));
     HIP_TRY(hipMemsetAsync(b->st, 0, sizeof(State) * C, e->stream));

@@ -147,7 +147,7 @@ namespace q3inst {
 typedef void (*GemvFn)(const q3::GemvArgs);
 struct GemvCfg { int pro, epi, n, wgt, ept, ru, ju, pf; GemvFn fn; };
 GemvFn gemv_pick(int pro, int epi, int G, int RU, int JU, int FIN, int PF);       // generic run-time-n kernels
-const GemvCfg* find_cfg(int pro, int epi, int n, int G, int which, bool fast = false);              // shape-specialised kernels
+const GemvCfg* find_cfg(int pro, int epi, int n, int G, bool fast = false);              // shape-specialised kernels
 }
 using q3inst::GemvCfg;
 using q3inst::find_cfg;
@@ -162,7 +162,7 @@ int set_max_smem(const void* fn, size_t bytes) {
 }
 
 // Environment variables.  The product library reads only the documented ones (include/qwen3_hip.h, "Environment"):
-// env_int().  Everything else -- A/B switches between kernel forms, tile / workgroup overrides, ablation and timeline
+// env_int().  Everything else -- A/B switches between kernel forms that are product code for other shapes, workgroup overrides, timeline
 // switches -- exists in the developer build only (make dev, -DQ3_DEV): dev_knob() is its default in the product.
 int env_int(const char* name, int dflt) {
     const char* v = getenv(name);
@@ -173,16 +173,6 @@ int env_int(const char* name, int dflt) {
 #else
 #define dev_knob(name, dflt) (dflt)
 #endif
-// activation requests ahead of the weight requests (GemvArgs::xfirst): 2 = workgroup barrier between them, 1 = wait for wave 0's
-// block of x, 0 = program order only.  r03 A/B in reference-order mode (tools/gen_loop.py, Q3_STRICT=1): the barrier costs the QKV
-// launch 0.15 us at every shape (0.6B: 1,572 -> 1,527 tok/s), gains W13 0.4 us at dim 1024 (+0.3 %) and nothing at 2560 / 4096;
-// in Q3_FLAG_FAST mode (no exact sum in front of the quantizer) it is worth +6 % on the 0.6B shape.
-// r05 re-sweep: only the 16-wave forms still carried the barrier (8B QKV / W1|W3): 1,895.7 with it vs 1,885.9 us per token without
-// (three alternations) -- off everywhere in reference-order mode now; the developer switch keeps the form for the FAST-mode A/B.
-// r06, the same question in Q3_FLAG_FAST mode (64-token device loop, two alternations, tok/s without / with the barrier): 0.6B
-// 1,827 / 1,820 vs 1,815 / 1,817; 4B 741 / 742 vs 739 / 739; 8B 535 / 535 vs 537 / 540 -- the r03 "+6 %" is gone (the block loads
-// of x are coalesced since then): off in both modes.
-int xfirst_dflt(int wgt) { return wgt >= 1024 ? dev_knob("Q3_XFIRST_DEFAULT", 0) : 0; }
 
 
 }  // namespace
@@ -337,7 +327,7 @@ static void launch_attn_scores(const AttnArgs& a, int kvm, unsigned gx, unsigned
 
 // Short-context attention (pos < 256): k_attn_short2 (round 5: coalesced key / value staging, product tile, 8 waves) for
 // head_dim 128 on caches of a whole number of 8-row steps; k_attn_short (head_dim 64, odd test contexts) otherwise.
-static bool attn_short2_ok(const AttnArgs& a) { return a.hd == 128 && a.seq_len >= 8 && (a.seq_len % 8) == 0 && a.att_short_form != 1; }
+static bool attn_short2_ok(const AttnArgs& a) { return a.hd == 128 && a.seq_len >= 8 && (a.seq_len % 8) == 0; }
 static int set_attn_short_smem(const AttnArgs& a) {
     if (!attn_short2_ok(a)) return Q3_OK;
     return set_max_smem((const void*)k_attn_short2<128>, attn_short2_smem_bytes(128, kS2MaxT));
@@ -406,8 +396,6 @@ GemvShape plan_gemv(int units, int n, int G, bool swiglu, int row_align, int n_c
             if (waste < best_waste) { best_waste = waste; g.JU = ju; }
         }
     }
-    const int force_ju = dev_knob("Q3_GEMV_JU", 0);
-    if (force_ju >= 1 && force_ju <= 4) g.JU = force_ju;
     const int ru_max = 8 / g.JU, ru_min = swiglu ? 2 : 1;
     const int waves = n_cu * wg_per_cu * kWaves;
     // rows that are a whole number of tiles fold the group terms in registers (k_gemv FIN = 1)
@@ -688,7 +676,7 @@ int q3_engine::build_plan() {
         a.n = n;
         a.group = G;
         a.strict = strict;
-        a.debug = dev_knob("Q3_ABLATE", 0) | (kstamps ? 64 : 0);
+        a.debug = kstamps ? 64 : 0;
         a.st = d_state;
         a.seq_len = S;
         return a;
@@ -698,17 +686,15 @@ int q3_engine::build_plan() {
     std::vector<Launch> wo_long;       // the long-context plan's Wo launches (k_attn_out emits no quantized operand)
     HIP_TRY(hipMalloc((void**)&d_xbq, (size_t)ahd));
     HIP_TRY(hipMalloc((void**)&d_xbs, 4 * (size_t)(ahd / G)));
-    const int alias0 = dev_knob("Q3_DEBUG_ALIAS_LAYER0", 0);   // experiment: every layer streams layer 0's weights
     for (int l = 0; l < L; ++l) {
         const size_t kv_off = (size_t)l * S * kvd;
-        const int lw = alias0 ? 0 : l;
         {   // xb = RMSNorm_att(x); xq = quantize(xb); q,k,v = W{q,k,v} xq         qwen3.rs:134-136, layers.rs:334-337
             Launch Ln;
             Ln.fam = F_QKV;
             GemvArgs a = base_args(dim);
-            a.seg[0] = Seg{wq[lw].q, wq[lw].s, d_q, ahd, 0};
-            a.seg[1] = Seg{wk[lw].q, wk[lw].s, d_kraw, kvd, 0};
-            a.seg[2] = Seg{wv[lw].q, wv[lw].s, d_value + kv_off, kvd, kvd};
+            a.seg[0] = Seg{wq[l].q, wq[l].s, d_q, ahd, 0};
+            a.seg[1] = Seg{wk[l].q, wk[l].s, d_kraw, kvd, 0};
+            a.seg[2] = Seg{wv[l].q, wv[l].s, d_value + kv_off, kvd, kvd};
             a.v_t = d_value_t ? d_value_t + kv_off : nullptr;
             a.total_rows = ahd + 2 * kvd;
             for (int k = 0; k < 2; ++k) {
@@ -718,7 +704,7 @@ int q3_engine::build_plan() {
             }
             a.norm_w = rms_att + (size_t)l * dim;
             a.in = d_x;
-            const GemvCfg* cfg = find_cfg(l == 0 ? PRO_EMBED_NORM : PRO_NORM, EPI_QKV, dim, G, dev_knob("Q3_CFG_QKV", 0), fast_fold);
+            const GemvCfg* cfg = find_cfg(l == 0 ? PRO_EMBED_NORM : PRO_NORM, EPI_QKV, dim, G, fast_fold);
             if (cfg && (hd % cfg->ru) != 0) cfg = nullptr;           // batches must not straddle the q|k|v segments
             if (l == 0) {
                 a.emb_q = tok.q;
@@ -726,7 +712,6 @@ int q3_engine::build_plan() {
                 a.x_out = d_x;
             }
             if (cfg) {
-                a.xfirst = dev_knob("Q3_XFIRST", (flags & Q3_FLAG_FAST) ? xfirst_dflt(cfg->wgt) : 0);
                 apply_cfg(Ln, a, *cfg, a.total_rows, n_cu);
             } else {
                 const GemvShape gs = plan_gemv(a.total_rows, dim, G, false, hd, n_cu, small_cap);
@@ -764,7 +749,7 @@ int q3_engine::build_plan() {
             a.seq_len = S;
             a.strict = strict;
             a.write_q = 0;
-            a.debug = dev_knob("Q3_ABLATE", 0) | (kstamps ? 64 : 0);
+            a.debug = kstamps ? 64 : 0;
             a.stamps = d_stamps ? (kstamps ? d_kslots + 2 * (size_t)kKstampSlots * plan.size() : d_stamps + 16 * plan.size()) : nullptr;
             Ln.aa = a;
             Ln.grid = (unsigned)cfg.n_heads;
@@ -773,11 +758,10 @@ int q3_engine::build_plan() {
             // the short plan only ever runs at pos < split_pos
             if ((hd == 64 || hd == 128) && split_pos <= kShortMaxT && dev_knob("Q3_ATT_SHORT", 1)) {
                 Ln.attn_kind = 3;
-                Ln.aa.att_short_form = dev_knob("Q3_ATT_SHORT", 1) == 2 ? 1 : 0;      // 2: the round 2-4 kernel (A/B)
                 if ((rc = set_attn_short_smem(Ln.aa))) return rc;
             }
             // k_attn_short can hand Wo its operand quantized (qwen3.rs:152 fused into the attention epilogue)
-            wo_preq = Ln.attn_kind == 3 ? find_cfg(PRO_PREQR, EPI_RESID, ahd, G, dev_knob("Q3_CFG_WO", 0), fast_fold) : nullptr;
+            wo_preq = Ln.attn_kind == 3 ? find_cfg(PRO_PREQR, EPI_RESID, ahd, G, fast_fold) : nullptr;
             if (wo_preq) {
                 Ln.aa.xbq = d_xbq;
                 Ln.aa.xbs = d_xbs;
@@ -789,7 +773,7 @@ int q3_engine::build_plan() {
             Launch Ln;
             Ln.fam = F_WO;
             GemvArgs a = base_args(ahd);
-            a.seg[0] = Seg{wo[lw].q, wo[lw].s, d_x, dim, 0};
+            a.seg[0] = Seg{wo[l].q, wo[l].s, d_x, dim, 0};
             a.total_rows = dim;
             a.in = d_xb;
             a.pre_q = d_xbq;
@@ -797,7 +781,7 @@ int q3_engine::build_plan() {
             // quantize-in-prologue form: the long-context plan always, the short plan when attention emits no int8
             Launch Lq = Ln;
             GemvArgs aq = a;
-            if (const GemvCfg* cq = find_cfg(PRO_QUANT, EPI_RESID, ahd, G, dev_knob("Q3_CFG_WO_LONG", 0), fast_fold)) {
+            if (const GemvCfg* cq = find_cfg(PRO_QUANT, EPI_RESID, ahd, G, fast_fold)) {
                 apply_cfg(Lq, aq, *cq, dim, n_cu);
             } else {
                 const GemvShape gs = plan_gemv(dim, ahd, G, false, 1, n_cu, small_cap);
@@ -824,13 +808,12 @@ int q3_engine::build_plan() {
             Launch Ln;
             Ln.fam = F_W13;
             GemvArgs a = base_args(dim);
-            a.seg[0] = Seg{w1[lw].q, w1[lw].s, d_hb, H, 0};
-            a.seg[1] = Seg{w3[lw].q, w3[lw].s, nullptr, H, 0};
+            a.seg[0] = Seg{w1[l].q, w1[l].s, d_hb, H, 0};
+            a.seg[1] = Seg{w3[l].q, w3[l].s, nullptr, H, 0};
             a.total_rows = 2 * H;
             a.norm_w = rms_ffn + (size_t)l * dim;
             a.in = d_x;
-            if (const GemvCfg* cfg = find_cfg(PRO_NORM, EPI_SWIGLU, dim, G, dev_knob("Q3_CFG_W13", 0), fast_fold)) {
-                a.xfirst = dev_knob("Q3_XFIRST_W13", dim < 2048 ? xfirst_dflt(cfg->wgt) : 0);
+            if (const GemvCfg* cfg = find_cfg(PRO_NORM, EPI_SWIGLU, dim, G, fast_fold)) {
                 apply_cfg(Ln, a, *cfg, H, n_cu);
             } else {
                 const GemvShape gs = plan_gemv(H, dim, G, true, 1, n_cu, small_cap);
@@ -849,11 +832,10 @@ int q3_engine::build_plan() {
             Launch Ln;
             Ln.fam = F_W2;
             GemvArgs a = base_args(H);
-            a.seg[0] = Seg{w2[lw].q, w2[lw].s, d_x, dim, 0};
+            a.seg[0] = Seg{w2[l].q, w2[l].s, d_x, dim, 0};
             a.total_rows = dim;
             a.in = d_hb;
-            if (const GemvCfg* cfg = find_cfg(PRO_QUANT, EPI_RESID, H, G, dev_knob("Q3_CFG_W2", 0), fast_fold)) {
-                a.xfirst = dev_knob("Q3_XFIRST_W2", 0);
+            if (const GemvCfg* cfg = find_cfg(PRO_QUANT, EPI_RESID, H, G, fast_fold)) {
                 apply_cfg(Ln, a, *cfg, dim, n_cu);
             } else {
                 const GemvShape gs = plan_gemv(dim, H, G, false, 1, n_cu, small_cap);
@@ -879,9 +861,8 @@ int q3_engine::build_plan() {
         a.in = d_x;
         a.tap_out = d_tap;
         GemvShape gs = plan_gemv(V, dim, G, false, 1, n_cu, big_cap, false);
-        const GemvCfg* lcfg = find_cfg(PRO_NORM, EPI_LOGITS, dim, G, dev_knob("Q3_CFG_LMHEAD", 0), fast_fold);
+        const GemvCfg* lcfg = find_cfg(PRO_NORM, EPI_LOGITS, dim, G, fast_fold);
         if (lcfg) {
-            a.xfirst = dev_knob("Q3_XFIRST_LM", 0);
             apply_cfg(Ln, a, *lcfg, V, n_cu);
             // streaming launch: cap the grid at the resident set (grid-stride over the row batches)
             const unsigned cap = (unsigned)(n_cu * (lcfg->wgt >= 512 ? 1 : 2));
@@ -1767,7 +1748,6 @@ int q3_op_attention(float* xb, float* q, float* key_cache_layer, const float* va
         if ((rc = op_end())) return rc;
         HIP_TRY(hipMemcpy(dq.p, dqout.p, 4 * ahd, hipMemcpyDeviceToDevice));
     } else if ((head_dim == 64 || head_dim == 128) && dev_knob("Q3_ATT_SHORT", 1)) {
-        a.att_short_form = dev_knob("Q3_ATT_SHORT", 1) == 2 ? 1 : 0;
         if ((rc = set_attn_short_smem(a))) return rc;
         launch_attn_short(a, (unsigned)n_heads, 0);
     } else {

@@ -22,13 +22,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-// Developer instrumentation (ablation switches, in-kernel s_memtime timelines) is compiled in only with -DQ3_DEV
-// (`make dev` -> libqwen3_hip_dev.so); the product build carries none of it.
-#ifdef Q3_DEV
-#define Q3_DEV_ABLATE(args, bit) (((args).debug & (bit)) != 0)
-#else
-#define Q3_DEV_ABLATE(args, bit) false
-#endif
+// Developer instrumentation (in-kernel s_memtime timelines) is compiled in only with -DQ3_DEV (`make dev` ->
+// libqwen3_hip_dev.so); the product build carries none of it.
 
 namespace q3 {
 
@@ -261,7 +256,7 @@ struct GemvArgs {
     Seg seg[3];
     long long qkv_dw[2], qkv_ds[2], qkv_do[2];  // EPI_QKV: byte deltas seg1-seg0, seg2-seg1 (wq, ws, out)
     int vr;              // rows per wave batch == the kernel's RU template parameter (host bookkeeping)
-    int debug;           // developer ablation bits (Q3_ABLATE): 1 skip prologue math, 2 skip tiles, 4 skip ordered sum
+    int debug;           // developer: bit 64 = kernel-duration stamps (Q3_KSTAMPS)
     unsigned long long* stamps;  // developer timeline: 8 s_memtime stamps written by (block stamp_block, wave 0)
     int stamp_block;
     // other prologue inputs
@@ -281,7 +276,10 @@ struct GemvArgs {
     const int32_t* prompt;
     // specialised NORM launches whose weight stream is shorter than their prologue (QKV of the 4B / 8B shapes): request the
     // weights only after wave 0 holds its block of x -- otherwise x queues behind tens of MB of weight requests of the other
-    // workgroups and the exact sum starts ~3.5 us late (r03 stamps, 8B QKV: x after 8,955 cycles)
+    // workgroups and the exact sum starts ~3.5 us late (r03 stamps, 8B QKV: x after 8,955 cycles).  1 = wait for wave 0's
+    // block, 2 = also a workgroup barrier.  Measured off in both modes since r06 (Q3_FLAG_FAST, tok/s without / with the
+    // barrier: 0.6B 1,827 / 1,820 vs 1,815 / 1,817; 4B 741 / 742 vs 739 / 739; 8B 535 / 535 vs 537 / 540): the planner leaves
+    // it 0.  The kernel keeps the run-time branches -- removing them changes the product's k_gemv code.
     int xfirst;
     // EPI_QKV: transposed copy of this layer's value cache, [kv_dim][seq_len] (nullptr: none).  The long-context output kernel walks
     // 16-element slices of the value rows over thousands of timesteps: in the row-major cache that is a 64-byte piece every 4 KB,
@@ -1125,7 +1123,7 @@ __global__ __launch_bounds__(WGT) void k_gemv(const GemvArgs a) {
         }
     } else if constexpr (kPro2) {
         if constexpr (PRO == PRO_NORM || PRO == PRO_EMBED_NORM) {
-            if (a.xfirst) {                   // wave-uniform (A/B knob, off by default): wave 0's block of x travels alone, everything else behind it
+            if (a.xfirst) {                   // wave-uniform (GemvArgs::xfirst, 0 from the planner): wave 0's block of x travels alone, everything else behind it
                 pro2_issue<PRO, N_T, WGT, EPT>(a, pr2, 1);
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 __syncthreads();
@@ -1352,7 +1350,7 @@ __global__ __launch_bounds__(WGT) void k_gemv(const GemvArgs a) {
                 acc = pick(0);
                 if constexpr (EPI == EPI_SWIGLU) up = pick(HU);
             } else {
-                acc = Q3_DEV_ABLATE(a, 4) ? term[lane * ng] : ordered_row_sum(term + lane * ng, ng);
+                acc = ordered_row_sum(term + lane * ng, ng);
             }
             if (EPI == EPI_STORE) {
                 rs.out[lane] = acc;
@@ -1398,19 +1396,13 @@ __global__ __launch_bounds__(WGT) void k_gemv(const GemvArgs a) {
     }
     __builtin_amdgcn_sched_barrier(0);
     stamp(a, 1);
-    if (Q3_DEV_ABLATE(a, 1)) {
-        for (int i = threadIdx.x; i < (a.n >> 2); i += kWG) ((int*)sm.xq)[i] = 0x01010101;
-        for (int i = threadIdx.x; i < a.n / a.group; i += kWG) sm.xs[i] = 1.0f;
-        __syncthreads();
-    } else {
     if (EPI == EPI_SWIGLU && threadIdx.x < 32) sm.etab[threadIdx.x] = etv;   // visible after the prologue's barrier
     if constexpr (PRO == PRO_PREQR) { if (EPI == EPI_SWIGLU) __syncthreads(); }
     else if constexpr (kPro2) pro2_finish<PRO, N_T, WGT, EPT>(a, sm, pr2);
     else gemv_prologue_finish<PRO, LPG_T>(a, sm, pr);     // ... and norm + quantize run under the weight loads
-    }
     if constexpr (EPI == EPI_QKV) pos = __builtin_amdgcn_readfirstlane(pos_v);   // older than every weight load: a counted wait
     stamp(a, 2);
-    if (any && !Q3_DEV_ABLATE(a, 2)) {
+    if (any) {
         bool enter_mid = false;               // PF: the loop is entered at its midpoint (current tile in TB)
         if constexpr (PF != 0) {
             compute_tile(TA, RA, cjt);        // TB's loads are younger: counted wait

@@ -58,20 +58,12 @@ namespace {
 // ------------------------------------------------------------------------------------------------
 // Shape-specialised GEMV launches (k_gemv with N_T > 0): every (prologue, epilogue, contraction length) of the listed
 // models (0.6B dim 1024 / hidden 3072, 4B 2560 / 9728, 8B 4096 / 12288, all heads x head_dim 2048 / 4096)
-// has one or more tile / workgroup-width candidates; the first entry of a role is the default, Q3_CFG_<FAMILY>=k picks the
-// k-th (sweeps: tools/cfg_sweep.py), -1 forces the generic run-time-n kernel.  Anything not listed (test shapes,
-// other group sizes) takes the generic path.
+// has one tile / workgroup-width form, the winner of its sweep (the notes below give the runners-up and their numbers).
+// Anything not listed (test shapes, other group sizes) takes the generic path.
 // ------------------------------------------------------------------------------------------------
 #define Q3_CFG(PRO, EPI, N, WGT, EPT, RU, JU, PF) \
     {PRO, EPI, N, WGT, EPT, RU, JU, PF, (GemvFn)k_gemv<PRO, EPI, 4, RU, JU, Q3_CFG_FIN, PF, N, WGT, EPT>}
 #define Q3_CFG_NORM_QKV(N, WGT, EPT, RU, JU, PF) Q3_CFG(PRO_NORM, EPI_QKV, N, WGT, EPT, RU, JU, PF), Q3_CFG(PRO_EMBED_NORM, EPI_QKV, N, WGT, EPT, RU, JU, PF)
-// The first entry of a role is what the product runs.  The other candidates of a role (the forms that lost their A/B; they stay
-// selectable through Q3_CFG_<FAMILY>=k for re-sweeps) exist in the developer build only: Q3_ALT(...).
-#ifdef Q3_DEV
-#define Q3_ALT(...) __VA_ARGS__,
-#else
-#define Q3_ALT(...)
-#endif
 // Notes on the entries of Q3_CFG_LIST (a macro: the list is expanded twice, reference-order fold and tolerance-mode tree fold):
 // --- QKV: RMSNorm_att + quantize + wq|wk|wv
 // (dim 1024, end of r03: the 512-thread / two-rows-per-wave forms lead the 1024-thread ones by 0.1 us per launch since the
@@ -89,47 +81,27 @@ namespace {
 // --- final RMSNorm + classifier (streaming: two tiles requested before the prologue)
 #define Q3_CFG_LIST \
     Q3_CFG_NORM_QKV(1024, 512, 2, 2, 1, 0), \
-    Q3_ALT(Q3_CFG_NORM_QKV(1024, 1024, 1, 1, 1, 0), Q3_CFG_NORM_QKV(1024, 1024, 4, 1, 1, 0), Q3_CFG_NORM_QKV(1024, 256, 4, 2, 1, 0)) \
     Q3_CFG_NORM_QKV(2560, 768, 4, 2, 3, 0), \
-    Q3_ALT(Q3_CFG_NORM_QKV(2560, 1024, 4, 1, 3, 0), Q3_CFG_NORM_QKV(2560, 1024, 4, 1, 3, 1), Q3_CFG_NORM_QKV(2560, 1024, 4, 2, 3, 0)) \
     Q3_CFG_NORM_QKV(4096, 1024, 4, 1, 4, 0), \
-    Q3_ALT(Q3_CFG_NORM_QKV(4096, 1024, 4, 1, 4, 1), Q3_CFG_NORM_QKV(4096, 1024, 4, 2, 4, 0), Q3_CFG_NORM_QKV(4096, 768, 4, 2, 4, 0)) \
     Q3_CFG(PRO_NORM, EPI_SWIGLU, 1024, 512, 2, 4, 1, 0), \
-    Q3_ALT(Q3_CFG(PRO_NORM, EPI_SWIGLU, 1024, 1024, 1, 2, 1, 0), Q3_CFG(PRO_NORM, EPI_SWIGLU, 1024, 1024, 4, 2, 1, 0), \
-           Q3_CFG(PRO_NORM, EPI_SWIGLU, 1024, 256, 4, 4, 1, 0)) \
     Q3_CFG(PRO_NORM, EPI_SWIGLU, 2560, 512, 4, 2, 3, 0), \
-    Q3_ALT(Q3_CFG(PRO_NORM, EPI_SWIGLU, 2560, 512, 4, 2, 3, 1), Q3_CFG(PRO_NORM, EPI_SWIGLU, 2560, 1024, 4, 2, 3, 0)) \
     Q3_CFG(PRO_NORM, EPI_SWIGLU, 4096, 1024, 4, 2, 4, 0), \
-    Q3_ALT(Q3_CFG(PRO_NORM, EPI_SWIGLU, 4096, 512, 4, 2, 4, 1), Q3_CFG(PRO_NORM, EPI_SWIGLU, 4096, 512, 4, 2, 4, 0)) \
     Q3_CFG(PRO_PREQR, EPI_RESID, 2048, 256, 4, 1, 2, 0), \
-    Q3_ALT(Q3_CFG(PRO_PREQR, EPI_RESID, 2048, 512, 4, 1, 2, 0)) \
     Q3_CFG(PRO_PREQR, EPI_RESID, 4096, 256, 4, 1, 4, 0), \
-    Q3_ALT(Q3_CFG(PRO_PREQR, EPI_RESID, 4096, 256, 4, 2, 4, 0), Q3_CFG(PRO_PREQR, EPI_RESID, 4096, 512, 4, 1, 4, 0), \
-           Q3_CFG(PRO_PREQR, EPI_RESID, 4096, 1024, 4, 1, 4, 0)) \
     Q3_CFG(PRO_QUANT, EPI_RESID, 3072, 256, 4, 1, 3, 0), \
-    Q3_ALT(Q3_CFG(PRO_QUANT, EPI_RESID, 3072, 512, 4, 1, 3, 0), Q3_CFG(PRO_QUANT, EPI_RESID, 3072, 1024, 4, 1, 3, 0)) \
     Q3_CFG(PRO_QUANT, EPI_RESID, 9728, 1024, 4, 1, 2, 1), \
-    Q3_ALT(Q3_CFG(PRO_QUANT, EPI_RESID, 9728, 512, 4, 1, 2, 1)) \
     Q3_CFG(PRO_QUANT, EPI_RESID, 12288, 1024, 4, 1, 4, 1), \
-    Q3_ALT(Q3_CFG(PRO_QUANT, EPI_RESID, 12288, 512, 4, 1, 4, 1)) \
     Q3_CFG(PRO_QUANT, EPI_RESID, 2048, 512, 4, 1, 2, 0), \
-    Q3_ALT(Q3_CFG(PRO_QUANT, EPI_RESID, 2048, 256, 4, 1, 2, 0)) \
     Q3_CFG(PRO_QUANT, EPI_RESID, 4096, 1024, 4, 1, 4, 0), \
-    Q3_ALT(Q3_CFG(PRO_QUANT, EPI_RESID, 4096, 512, 4, 1, 4, 0)) \
     Q3_CFG(PRO_NORM, EPI_LOGITS, 1024, 512, 4, 8, 1, 1), \
-    Q3_ALT(Q3_CFG(PRO_NORM, EPI_LOGITS, 1024, 256, 4, 8, 1, 1)) \
     Q3_CFG(PRO_NORM, EPI_LOGITS, 2560, 512, 4, 2, 3, 1), \
-    Q3_ALT(Q3_CFG(PRO_NORM, EPI_LOGITS, 2560, 256, 4, 2, 3, 1)) \
-    Q3_CFG(PRO_NORM, EPI_LOGITS, 4096, 512, 4, 2, 4, 1), \
-    Q3_ALT(Q3_CFG(PRO_NORM, EPI_LOGITS, 4096, 256, 4, 2, 4, 1))
+    Q3_CFG(PRO_NORM, EPI_LOGITS, 4096, 512, 4, 2, 4, 1)
 #define Q3_CFG_FIN 1
 const GemvCfg kGemvCfgs[] = {
 Q3_CFG_LIST
 };
 #undef Q3_CFG_FIN
-// Q3_FLAG_FAST engines: the default form of every role with the wavefront-tree group fold (k_gemv FIN = 2); no alternates
-#undef Q3_ALT
-#define Q3_ALT(...)
+// Q3_FLAG_FAST engines: the same forms with the wavefront-tree group fold (k_gemv FIN = 2)
 #define Q3_CFG_FIN 2
 const GemvCfg kGemvCfgsFast[] = {
 Q3_CFG_LIST
@@ -138,19 +110,12 @@ Q3_CFG_LIST
 }  // namespace
 
 namespace q3inst {
-const GemvCfg* find_cfg(int pro, int epi, int n, int G, int which, bool fast) {
-    if (G != 64 || which < 0) return nullptr;
-    if (fast) {                      // tolerance mode: the default form of the role with the tree fold (candidate 0 only)
-        if (which != 0) return nullptr;
-        for (const GemvCfg& c : kGemvCfgsFast)
-            if (c.pro == pro && c.epi == epi && c.n == n) return &c;
-        return nullptr;
-    }
-    for (const GemvCfg& c : kGemvCfgs)
-        if (c.pro == pro && c.epi == epi && c.n == n && which-- == 0) return &c;
-    return nullptr;                  // no such candidate: the caller falls back to the generic kernel (a sweep sees "generic", not a mislabel)
+const GemvCfg* find_cfg(int pro, int epi, int n, int G, bool fast) {
+    if (G != 64) return nullptr;
+    for (const GemvCfg& c : fast ? kGemvCfgsFast : kGemvCfgs)   // (fast: tolerance mode, the same forms with the tree fold)
+        if (c.pro == pro && c.epi == epi && c.n == n) return &c;
+    return nullptr;                  // not a listed shape: the caller takes the generic kernel
 }
-
 
 // the (prologue, epilogue) pairs the engine and the operator entry points use
 GemvFn gemv_pick(int pro, int epi, int G, int RU, int JU, int FIN, int PF) {

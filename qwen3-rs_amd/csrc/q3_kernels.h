@@ -75,7 +75,7 @@ struct AttnArgs {
     float* q_out;             // split path: normalised q goes here (other chunk workgroups still read the raw q)
     float* att_priv;          // split path: [n_heads][slices][att_stride] private probability rows of k_attn_out
     int att_stride;           // floats per score row (>= seq_len rounded up to 256)
-    int debug;                // ablation: 8 = return right after the q/k norm+rope
+    int debug;                // developer: bit 64 = kernel-duration stamps (Q3_KSTAMPS)
     unsigned long long* stamps;   // developer timeline (block 0, thread 0)
     // batched decode: blockIdx.y = stream; float strides between streams (all 0 for the single-stream engine)
     long long sb_q, sb_kraw, sb_kv, sb_xb, sb_att;
@@ -96,7 +96,6 @@ struct AttnArgs {
     float* xbs;
     int xb_group;
     int n_pos;                // k_attn_pf2 (dense prefill): positions in the block
-    int att_short_form;       // host bookkeeping: 1 = keep k_attn_short where k_attn_short2 is eligible (A/B)
     int row_steps;            // k_attn_short2: > 0 = 8-row steps of K / V to request at kernel entry (the graph of a position range < 64)
     const float* value_t;     // k_attn_out: transposed value cache of this layer, [kv_dim][seq_len] (nullptr: stage from value_cache)
     // k_attn_short2 / k_attn_out: n_heads / n_kv_heads and ceil(2^20 / n_kv_heads), set by attn_set_heads -- the workgroup -> head mapping
@@ -284,7 +283,6 @@ __device__ __forceinline__ void attn_body(const AttnArgs& a) {
         for (int i = tid; i < hd; i += kWG) krow[i] = k_s[i];   // K is normalised + rotated in place in the cache
     if (a.write_q)
         for (int i = tid; i < hd; i += kWG) a.q[(size_t)h * hd + i] = q_s[i];
-    if (Q3_DEV_ABLATE(a, 8)) { if (tid < hd) a.xb[(size_t)h * hd + tid] = q_s[tid]; return; }
 
     const float scale = 1.0f / sqrtf((float)hd);  // (head_dim as f32).sqrt().recip()
 
@@ -496,8 +494,6 @@ __global__ __launch_bounds__(kWG) void k_attn_short(const AttnArgs a) {
     __shared__ __attribute__((aligned(16))) float att_p[kShortMaxT];   // probabilities
     __shared__ unsigned long long etab[32];                            // exp2 table of q3_expf, staged once
     ATTS_STAMP(0, 0);
-    if (Q3_DEV_ABLATE(a, 16) && blockIdx.x != 3) return;      // developer: one workgroup only (launch-period experiments)
-    if (Q3_DEV_ABLATE(a, 32)) return;                         // developer: empty kernel with this kernel's resources
     Q3_PIN_S(a.st); Q3_PIN_S(a.pos_override); Q3_PIN_S(a.q); Q3_PIN_S(a.k_raw); Q3_PIN_S(a.key_cache); Q3_PIN_S(a.value_cache);
     Q3_PIN_S(a.q_norm_w); Q3_PIN_S(a.k_norm_w); Q3_PIN_S(a.rope); Q3_PIN_S(a.xb); Q3_PIN_S(a.n_heads); Q3_PIN_S(a.n_kv_heads);
     Q3_PIN_S(a.write_q);
@@ -1175,10 +1171,7 @@ __global__ __launch_bounds__(kAoThreads) void k_attn_out(const AttnArgs a) {
                 const int e = idx / KQ, tq = idx % KQ;
                 const int tt = min(c0 + 4 * tq, a.seq_len - 4);      // (seq_len % 4 == 0: host)
                 const float* ptr = vtbase + (size_t)e * a.seq_len + tt;
-                // (developer ablation 1024, timing only: the slice's rows read as if they were stored back to back)
-                const float* pab = a.value_cache + ((size_t)((blockIdx.x & 7) * gridDim.y + blockIdx.y) * a.seq_len + t) * w + 4 * c4;
-                // (developer ablation 8192, timing only: every request of the launch reads the same 16 bytes)
-                R.v[u] = *(const v4f*)(Q3_DEV_ABLATE(a, 8192) ? a.value_cache : (Q3_DEV_ABLATE(a, 1024) ? pab : (vtr ? ptr : prm)));
+                R.v[u] = *(const v4f*)(vtr ? ptr : prm);
             }
         }
     };
@@ -1348,7 +1341,7 @@ __global__ __launch_bounds__(kAoThreads) void k_attn_out(const AttnArgs a) {
     // ---- out[e] = sum_t p[t] * V[t][e]  (layers.rs:406-417), V slices staged kVChunk timesteps at a time
     constexpr int VLD = kVChunk + kVPad;
     auto v_commit = [&](const VRegs& R, int c0, int buf) {
-        if (!stager || Q3_DEV_ABLATE(a, 512)) return;
+        if (!stager) return;
         float* vbuf = vbuf0 + buf * (kVChunk + kVPad) * w;
         float* pbuf = pbuf0 + buf * kVChunk;
         if (vtr) {
@@ -1478,10 +1471,10 @@ __global__ __launch_bounds__(kAoThreads) void k_attn_out(const AttnArgs a) {
                 // set requested a phase ago, 32 adds -- 1.28 instructions per timestep (a read + a wait behind every fourth add: 1.5)
                 // (the explicit lgkmcnt(8) = "everything but the burst just issued has landed": without it hipcc waits once per float4)
                 const unsigned la = (unsigned)(size_t)(vr + q + 8);          // LDS byte address of the next 8 float4
-                if (!Q3_DEV_ABLATE(a, 2048)) chain_request8(bv, la);
-                if (!Q3_DEV_ABLATE(a, 4096)) { chain_add16(o_s, av[0], av[1], av[2], av[3]); chain_add16(o_s, av[4], av[5], av[6], av[7]); }
-                if (!Q3_DEV_ABLATE(a, 2048)) chain_request8(av, la + 128u);
-                if (!Q3_DEV_ABLATE(a, 4096)) { chain_add16(o_s, bv[0], bv[1], bv[2], bv[3]); chain_add16(o_s, bv[4], bv[5], bv[6], bv[7]); }
+                chain_request8(bv, la);
+                chain_add16(o_s, av[0], av[1], av[2], av[3]); chain_add16(o_s, av[4], av[5], av[6], av[7]);
+                chain_request8(av, la + 128u);
+                chain_add16(o_s, bv[0], bv[1], bv[2], bv[3]); chain_add16(o_s, bv[4], bv[5], bv[6], bv[7]);
             }
             {
                 // the chunk's last 64 timesteps meet the staging waves' barrier.  (Round 5 tried LDS counters instead -- arrival count of
@@ -1494,7 +1487,7 @@ __global__ __launch_bounds__(kAoThreads) void k_attn_out(const AttnArgs a) {
                 chain_add16(o_s, av[4], av[5], av[6], av[7]);
                 // (developer timeline: the chain wave in front of / behind the barriers of chunks 2..5)
                 if (c0 >= 2 * K && c0 < 6 * K) ATT_STAMP(7 + 2 * (c0 / K - 2));
-                if (!Q3_DEV_ABLATE(a, 256)) __syncthreads();     // the staging waves' barrier of this chunk: tile c+1 is complete
+                __syncthreads();                                 // the staging waves' barrier of this chunk: tile c+1 is complete
                 if (c0 >= 2 * K && c0 < 6 * K) ATT_STAMP(8 + 2 * (c0 / K - 2));
                 chain_request8(av, (unsigned)(size_t)vn);        // head of the next tile (past the last chunk: a valid address, unused);
                                                                  // its wait = bv has landed
@@ -1511,14 +1504,14 @@ __global__ __launch_bounds__(kAoThreads) void k_attn_out(const AttnArgs a) {
             if (c0 + 3 * K < np) v_issue(vrb, c0 + 3 * K);
         }
         fold(c0, 0);
-        if (!Q3_DEV_ABLATE(a, 256)) __syncthreads();
+        __syncthreads();
         if (c0 + K >= np) break;
         if (c0 + 2 * K < np) {
             v_commit(vra, c0 + 2 * K, 0);
             if (c0 + 4 * K < np) v_issue(vra, c0 + 4 * K);
         }
         fold(c0 + K, 1);
-        if (!Q3_DEV_ABLATE(a, 256)) __syncthreads();
+        __syncthreads();
     }
     ATT_STAMP(6);
     float* out = a.xb + (size_t)h * hd + (size_t)sl * w;

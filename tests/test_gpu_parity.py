@@ -645,15 +645,16 @@ def test_batched_prefill_block_sizes_agree(q3, block, shape_name, tmp_path_facto
     """Q3_PREFILL_M picks the positions per weight pass: 32 = the batch-32 kernels (k_bgemm + LDS term tile), larger blocks
     the dense kernels (k_pgemm in-lane fold, k_attn_pf).  Every block size must give the cache rows and tokens of the
     sequential prompt loop (generation.rs:116-123) bit for bit, including a ragged last block and a non-zero start.
-    Blocks of 128 / 256 run the LDS-tiled matmul k_pgemm2 with 4 x 4 position-tile workgroups by default on these shapes;
-    negative block: the same size with its other forms -- -128: 2 row tiles per workgroup (Q3_PGEMM2_RT=2), -256: 4 x 8 tiles
-    (Q3_PGEMM2_PT=8), -512: 8 x 8 tiles (Q3_PGEMM3_RT=8); 48 positions (3 tiles) stay on k_pgemm."""
+    Blocks of 128 / 256 run the LDS-tiled matmul (k_pgemm2 / k_pgemm3) with 4 x 4 position-tile workgroups by default on these shapes;
+    negative block: the same size with a form the planner takes on other shapes -- -128: k_pgemm2 in place of k_pgemm3
+    (Q3_PGEMM3=0), -256: the 4 x 8 tiles of larger matrices (Q3_PGEMM2_PT=8), -512: the per-wave k_pgemm of short blocks
+    (Q3_PGEMM2=0); 48 positions (3 tiles) stay on k_pgemm."""
     if block == -128:
-        dev_forms({"Q3_PGEMM2_RT": "2"})
+        dev_forms({"Q3_PGEMM3": "0"})
     if block == -256:
         dev_forms({"Q3_PGEMM2_PT": "8"})
-    if block == -512:                                   # 8 x 8 workgroup tiles (k_pgemm3<.., 8, 8, 1>)
-        dev_forms({"Q3_PGEMM2_PT": "8", "Q3_PGEMM3_RT": "8"})
+    if block == -512:
+        dev_forms({"Q3_PGEMM2": "0"})
     block = abs(block)
     ck = q3.checkpoint
     shape = ck.SHAPES[shape_name]
@@ -721,12 +722,12 @@ def test_batched_prefill_kv_and_token_vs_oracle(q3, oracle, tmp_path_factory):
             assert_biteq(t.read_state("value", layer * 128 * kvd, 70 * kvd), ov[layer].reshape(-1)[:70 * kvd], f"value rows layer {layer}")
 
 
-# k_dgemm launch forms (round 4; the plan is built at batch_init, the knobs are read from the environment then): the default
-# (residual launches), every family in-lane with the fused hq quantizer and both ring depths, the one-stream-tile-per-workgroup
-# and three-wave W1|W3 forms, and k_bgemm everywhere
-_DGEMM_FORMS = [{}, {"Q3_DGEMM_FAMILIES": "15"}, {"Q3_DGEMM_FAMILIES": "15", "Q3_DGEMM_DEEP": "0"},
-                {"Q3_DGEMM_FAMILIES": "15", "Q3_DGEMM_W13_MODE": "0"}, {"Q3_DGEMM_FAMILIES": "15", "Q3_DGEMM_W13_MODE": "2"},
-                {"Q3_DGEMM_FAMILIES": "15", "Q3_DGEMM_BLDS": "0"}, {"Q3_BATCH_DGEMM": "0"}]
+# forms of the batched decode step (the plan is built at batch_init, the knobs are read from the environment then), each one the
+# planner takes on other shapes: the default (k_dgemm for the residual launches, k_bgemm for the others), single-row-tile k_bgemm
+# tasks, k_attn_gqa in place of k_attn_gqa2, Wo's activation quantized by its own launch, unsplit prologues, the generic-length
+# prologue kernels, and k_bgemm everywhere
+_DGEMM_FORMS = [{}, {"Q3_BATCH_RT": "1"}, {"Q3_BATCH_ATT_GQA2": "0"}, {"Q3_BATCH_FUSE_XB_QUANT": "0"}, {"Q3_BQUANT_SPLIT": "0"},
+                {"Q3_BQUANT_SPEC": "0"}, {"Q3_BATCH_DGEMM": "0"}]
 
 
 @pytest.mark.parametrize("form", range(len(_DGEMM_FORMS)))
@@ -734,7 +735,7 @@ def test_batched_decode_8b_layer_dims_vs_forward_and_oracle(q3, oracle, form, de
     """BASELINE config 4's matrix shapes on the batched path: row lengths 4096 / 12288 (64 and 192 groups per row), 32
     heads over 8 kv heads, untied classifier -- 2 layers, reduced vocabulary.  32 streams x 8 steps: every stream's
     logits bit-identical to q3_forward on the same (token, pos) sequence for the first 4 streams, and 2 streams
-    against the oracle.  Run for every matmul form of the batched path (_DGEMM_FORMS)."""
+    against the oracle.  Run for every form of the batched step in _DGEMM_FORMS."""
     dev_forms(_DGEMM_FORMS[form])
     ck = q3.checkpoint
     name = "qwen3-8b-dims-l2"
@@ -777,7 +778,8 @@ def test_batched_decode_8b_layer_dims_vs_forward_and_oracle(q3, oracle, form, de
 def test_batched_decode_4b_layer_dims_vs_forward(q3, form, dev_forms):
     """The 4B matrix shapes on the batched path: row lengths 2560 / 9728 are 40 / 152 quantization groups -- not a multiple of
     16, so k_dgemm runs its 8-group ring (and k_bgemm ragged phases) -- 20 streams (a ragged second stream tile), 6 steps: logits
-    of four streams bit-identical to q3_forward.  Forms as in _DGEMM_FORMS (default, every family in-lane at both depths, k_bgemm)."""
+    of four streams bit-identical to q3_forward.  Forms as in _DGEMM_FORMS (default, single-row-tile k_bgemm tasks,
+    k_attn_gqa, k_bgemm everywhere)."""
     dev_forms(_DGEMM_FORMS[form])
     ck = q3.checkpoint
     name = "qwen3-4b-dims-l2"
