@@ -75,11 +75,14 @@ typedef struct q3_engine q3_engine;
 /* q3_create flags.
  * Default (flags = 0): every f32 sum is reduced in the reference's sequential order, so logits are
  * BIT-IDENTICAL to the CPU path and greedy token sequences are identical by construction. */
-#define Q3_FLAG_FAST 1u /* opt-in: wavefront-tree reductions for the RMSNorm / attention sums.  Not
-                           bit-exact: a 28-layer W8A8 stack amplifies a 1e-7 reordering difference to its
-                           own int8 quantization-noise floor (logit deltas of ~0.1), so
-                           greedy tokens can differ from the CPU path.  The int8 group-quant matmul itself
-                           is bit-exact in both modes. */
+#define Q3_FLAG_FAST 1u /* opt-in: wavefront-tree reductions for the RMSNorm / attention sums and, for the listed shapes
+                           (group 64), for the fold of a matmul row's group terms.  Not bit-exact: a 28-layer W8A8 stack
+                           amplifies a 1e-7 reordering difference to its own int8 quantization-noise floor (logit deltas of
+                           ~0.1), so greedy tokens can differ from the CPU path.  Of the int8
+                           group-quant matmul, the integer group dots and each group term ((dot as f32) * ws) * xs
+                           (tensor.rs:53-60) are exact in both modes; only the ORDER in which a row's group terms are
+                           added differs (a tree instead of the ascending chain).  quantize, SwiGLU, expf and the
+                           sampler are identical in both modes. */
 #define Q3_FLAG_NO_GRAPH 2u /* launch kernels eagerly instead of replaying a captured hipGraph */
 #define Q3_FLAG_NO_VALUE_T 4u /* do not keep the TRANSPOSED copy of the value cache.  Reference-order engines whose context
                            can reach the split attention path (seq_len > 256, a multiple of 4) keep the value cache twice:
@@ -226,7 +229,9 @@ int q3_batch_read_state(q3_engine* e, int stream, int kind, size_t offset, size_
 /* ------------------------------------------------------------------------------------------------
  * 3. Operator-level entry points: the reference's public free functions (tensor.rs, layers.rs) run on
  *    the device over caller (host) buffers.  Used by the parity tests; same kernels/device functions
- *    as the fused forward.  `device` as in q3_create; flags: 0 (reference order) or Q3_FLAG_FAST.
+ *    as the fused forward.  `device` as in q3_create.  q3_op_rmsnorm, q3_op_softmax, q3_op_attention and
+ *    q3_op_gemv_role take flags: 0 (reference order) or Q3_FLAG_FAST; the others (quantize, dequantize, matmul,
+ *    swiglu, expf, sample, argmax) have one form, identical in both modes.
  * ---------------------------------------------------------------------------------------------- */
 
 /* tensor::quantize(qx, x, size, group_size)                             tensor.rs:91-119 */
@@ -236,6 +241,26 @@ int q3_op_dequantize(const int8_t* q, const float* s, float* x, size_t size, siz
 /* tensor::matmul(xout, x, w, n, d, group_size)                          tensor.rs:23-62 */
 int q3_op_matmul(float* xout, const int8_t* xq, const float* xs, const int8_t* wq, const float* ws, size_t n,
                  size_t d, size_t group_size, int device);
+/* One fused GEMV launch of the decode plan, alone: the kernel, grid, workgroup width and LDS size the planner picks for this
+ * (prologue, epilogue, n, rows, group_size, flags) -- the shape-specialised table entry when the shape is listed (group 64, n of
+ * a listed model; flags selects the reference-order or the tolerance-mode table), the generic kernel otherwise.
+ *   Q3_ROLE_NORM_QKV     xb = RMSNorm(in, norm_w); out = [Wq; Wk; Wv] quantize(xb)   wq: [rows + 2*rows_kv][n], out the same count
+ *                        (rows = query rows, rows_kv = key rows = value rows, all multiples of head_dim)
+ *   Q3_ROLE_NORM_SWIGLU  out[r] = silu(W1 xq)[r] * (W3 xq)[r]                        wq: W1 then W3, [2*rows][n]; out [rows]
+ *   Q3_ROLE_QUANT_RESID  out += W quantize(in)                                        out [rows], read and written
+ *   Q3_ROLE_PREQR_RESID  out += W (pre_q, pre_s)          listed n only (the planner's fallback is QUANT_RESID): else Q3_ERR_UNSUPPORTED
+ *   Q3_ROLE_NORM_LOGITS  out = Wcls quantize(RMSNorm(in, norm_w)); *argmax_index = Sampler::sample_argmax(out) as the launch computes it
+ * ws: [weight rows][n / group_size].  tap_out (NORM roles, may be NULL): the kernel's own copy of the normalised vector, [n] --
+ * the operand it quantizes.  launch_info (may be NULL): {1 if a table entry was launched else 0, grid, threads per workgroup,
+ * rows per wave batch}.  rows_kv / head_dim are read for Q3_ROLE_NORM_QKV only.  Unused inputs of a role may be NULL. */
+#define Q3_ROLE_NORM_QKV 0
+#define Q3_ROLE_NORM_SWIGLU 1
+#define Q3_ROLE_QUANT_RESID 2
+#define Q3_ROLE_PREQR_RESID 3
+#define Q3_ROLE_NORM_LOGITS 4
+int q3_op_gemv_role(int role, float* out, float* tap_out, int32_t* argmax_index, int32_t* launch_info, const float* in,
+                    const float* norm_w, const int8_t* pre_q, const float* pre_s, const int8_t* wq, const float* ws, size_t n,
+                    size_t rows, size_t rows_kv, size_t head_dim, size_t group_size, uint32_t flags, int device);
 /* RMSNorm::forward                                                      layers.rs:109-119 */
 int q3_op_rmsnorm(float* out, const float* in, const float* weight, size_t n, uint32_t flags, int device);
 /* layers::softmax                                                       layers.rs:495-506 */

@@ -447,6 +447,35 @@ void apply_cfg(Launch& Ln, GemvArgs& a, const GemvCfg& c, int units, int n_cu) {
     Ln.smem = gemv_smem_bytes(c.n, 64, c.ru, stage, waves, true);
 }
 
+// Kernel, grid, block and LDS size of one fused GEMV role (prologue, epilogue) at contraction length n: the shape-specialised
+// table entry when there is one, the generic run-time-n kernel otherwise.  units = output rows (SwiGLU: hidden units);
+// hd = head_dim for EPI_QKV (row batches must not straddle the q|k|v segments), 1 otherwise.  build_plan and the operator
+// entry point q3_op_gemv_role both select through this function.
+int plan_role(Launch& Ln, GemvArgs& a, int pro, int epi, int n, int units, int G, bool fast_fold, int hd, int n_cu) {
+    const int small_cap = dev_knob("Q3_WG_PER_CU_SMALL", 2);   // two workgroups per CU: half the rows (and fold chains) per wave
+    const int big_cap = dev_knob("Q3_WG_PER_CU_LMHEAD", 2);   // all workgroups resident at once (the NORM prologue keeps ~190 VGPRs live)
+    const bool norm = pro == PRO_NORM || pro == PRO_EMBED_NORM;
+    const GemvCfg* cfg = find_cfg(pro, epi, n, G, fast_fold);
+    if (cfg && epi == EPI_QKV && (hd % cfg->ru) != 0) cfg = nullptr;           // batches must not straddle the q|k|v segments
+    if (cfg) {
+        apply_cfg(Ln, a, *cfg, units, n_cu);
+        if (epi == EPI_LOGITS) {
+            // streaming launch: cap the grid at the resident set (grid-stride over the row batches)
+            const unsigned cap = (unsigned)(n_cu * (cfg->wgt >= 512 ? 1 : 2));
+            if (Ln.grid > cap) Ln.grid = cap;
+        }
+    } else {
+        const GemvShape gs = epi == EPI_LOGITS ? plan_gemv(units, n, G, false, 1, n_cu, big_cap, false)
+                                               : plan_gemv(units, n, G, epi == EPI_SWIGLU, epi == EPI_QKV ? hd : 1, n_cu, small_cap);
+        Ln.fn = q3inst::gemv_pick(pro, epi, G, gs.RU, gs.JU, epi == EPI_LOGITS ? 0 : gs.FIN, gs.PF);
+        a.vr = gs.RU;
+        Ln.grid = gs.grid;
+        Ln.smem = gemv_smem_bytes(n, G, a.vr, norm);
+    }
+    if (!Ln.fn) return fail(Q3_ERR_UNSUPPORTED, "no kernel instantiated for this tile shape");
+    return set_max_smem((const void*)Ln.fn, Ln.smem);
+}
+
 }  // namespace
 
 void q3_engine::release() {
@@ -642,8 +671,6 @@ int q3_engine::build_plan() {
     const int G = cfg.group_size, ahd = cfg.n_heads * hd, kvd = cfg.n_kv_heads * hd, S = cfg.seq_len;
     const int strict = (flags & Q3_FLAG_FAST) ? 0 : 1;
     const bool fast_fold = !strict && dev_knob("Q3_FAST_FOLD", 1) != 0;   // tolerance mode: tree fold of the GEMV group terms too
-    const int small_cap = dev_knob("Q3_WG_PER_CU_SMALL", 2);   // two workgroups per CU: half the rows (and fold chains) per wave
-    const int big_cap = dev_knob("Q3_WG_PER_CU_LMHEAD", 2);   // all workgroups resident at once (the NORM prologue keeps ~190 VGPRs live)
     const int att_lds_max = dev_knob("Q3_ATT_LDS_MAX", 4096);
 
     att_stride = (S + 255) & ~255;
@@ -704,26 +731,13 @@ int q3_engine::build_plan() {
             }
             a.norm_w = rms_att + (size_t)l * dim;
             a.in = d_x;
-            const GemvCfg* cfg = find_cfg(l == 0 ? PRO_EMBED_NORM : PRO_NORM, EPI_QKV, dim, G, fast_fold);
-            if (cfg && (hd % cfg->ru) != 0) cfg = nullptr;           // batches must not straddle the q|k|v segments
             if (l == 0) {
                 a.emb_q = tok.q;
                 a.emb_s = tok.s;
                 a.x_out = d_x;
             }
-            if (cfg) {
-                apply_cfg(Ln, a, *cfg, a.total_rows, n_cu);
-            } else {
-                const GemvShape gs = plan_gemv(a.total_rows, dim, G, false, hd, n_cu, small_cap);
-                if (l == 0) Ln.fn = pick<PRO_EMBED_NORM, EPI_QKV>(G, gs.RU, gs.JU, gs.FIN, gs.PF);
-                else Ln.fn = pick<PRO_NORM, EPI_QKV>(G, gs.RU, gs.JU, gs.FIN, gs.PF);
-                a.vr = gs.RU;
-                Ln.grid = gs.grid;
-                Ln.smem = gemv_smem_bytes(dim, G, a.vr, true);
-            }
+            if ((rc = plan_role(Ln, a, l == 0 ? PRO_EMBED_NORM : PRO_NORM, EPI_QKV, dim, a.total_rows, G, fast_fold, hd, n_cu))) return rc;
             Ln.ga = a;
-            if (!Ln.fn) return fail(Q3_ERR_UNSUPPORTED, "no kernel instantiated for this tile shape");
-            if ((rc = set_max_smem((const void*)Ln.fn, Ln.smem))) return rc;
             if (d_stamps) { Ln.ga.stamps = kstamps ? d_kslots + 2 * (size_t)kKstampSlots * plan.size() : d_stamps + 16 * plan.size(); Ln.ga.stamp_block = dev_knob("Q3_STAMP_BLOCK", 7); }
             plan.push_back(Ln);
         }
@@ -781,23 +795,12 @@ int q3_engine::build_plan() {
             // quantize-in-prologue form: the long-context plan always, the short plan when attention emits no int8
             Launch Lq = Ln;
             GemvArgs aq = a;
-            if (const GemvCfg* cq = find_cfg(PRO_QUANT, EPI_RESID, ahd, G, fast_fold)) {
-                apply_cfg(Lq, aq, *cq, dim, n_cu);
-            } else {
-                const GemvShape gs = plan_gemv(dim, ahd, G, false, 1, n_cu, small_cap);
-                Lq.fn = pick<PRO_QUANT, EPI_RESID>(G, gs.RU, gs.JU, gs.FIN, gs.PF);
-                aq.vr = gs.RU;
-                Lq.grid = gs.grid;
-                Lq.smem = gemv_smem_bytes(ahd, G, aq.vr, false);
-            }
+            if ((rc = plan_role(Lq, aq, PRO_QUANT, EPI_RESID, ahd, dim, G, fast_fold, 1, n_cu))) return rc;
             Lq.ga = aq;
-            if (!Lq.fn) return fail(Q3_ERR_UNSUPPORTED, "no kernel instantiated for this tile shape");
-            if ((rc = set_max_smem((const void*)Lq.fn, Lq.smem))) return rc;
             wo_long.push_back(Lq);
             if (wo_preq) {
-                apply_cfg(Ln, a, *wo_preq, dim, n_cu);
+                if ((rc = plan_role(Ln, a, PRO_PREQR, EPI_RESID, ahd, dim, G, fast_fold, 1, n_cu))) return rc;
                 Ln.ga = a;
-                if ((rc = set_max_smem((const void*)Ln.fn, Ln.smem))) return rc;
             } else {
                 Ln = Lq;
             }
@@ -813,18 +816,8 @@ int q3_engine::build_plan() {
             a.total_rows = 2 * H;
             a.norm_w = rms_ffn + (size_t)l * dim;
             a.in = d_x;
-            if (const GemvCfg* cfg = find_cfg(PRO_NORM, EPI_SWIGLU, dim, G, fast_fold)) {
-                apply_cfg(Ln, a, *cfg, H, n_cu);
-            } else {
-                const GemvShape gs = plan_gemv(H, dim, G, true, 1, n_cu, small_cap);
-                Ln.fn = pick<PRO_NORM, EPI_SWIGLU>(G, gs.RU, gs.JU, gs.FIN, gs.PF);
-                a.vr = gs.RU;
-                Ln.grid = gs.grid;
-                Ln.smem = gemv_smem_bytes(dim, G, a.vr, true);
-            }
+            if ((rc = plan_role(Ln, a, PRO_NORM, EPI_SWIGLU, dim, H, G, fast_fold, 1, n_cu))) return rc;
             Ln.ga = a;
-            if (!Ln.fn) return fail(Q3_ERR_UNSUPPORTED, "no kernel instantiated for this tile shape");
-            if ((rc = set_max_smem((const void*)Ln.fn, Ln.smem))) return rc;
             if (d_stamps) { Ln.ga.stamps = kstamps ? d_kslots + 2 * (size_t)kKstampSlots * plan.size() : d_stamps + 16 * plan.size(); Ln.ga.stamp_block = dev_knob("Q3_STAMP_BLOCK", 7); }
             plan.push_back(Ln);
         }
@@ -835,18 +828,8 @@ int q3_engine::build_plan() {
             a.seg[0] = Seg{w2[l].q, w2[l].s, d_x, dim, 0};
             a.total_rows = dim;
             a.in = d_hb;
-            if (const GemvCfg* cfg = find_cfg(PRO_QUANT, EPI_RESID, H, G, fast_fold)) {
-                apply_cfg(Ln, a, *cfg, dim, n_cu);
-            } else {
-                const GemvShape gs = plan_gemv(dim, H, G, false, 1, n_cu, small_cap);
-                Ln.fn = pick<PRO_QUANT, EPI_RESID>(G, gs.RU, gs.JU, gs.FIN, gs.PF);
-                a.vr = gs.RU;
-                Ln.grid = gs.grid;
-                Ln.smem = gemv_smem_bytes(H, G, a.vr, false);
-            }
+            if ((rc = plan_role(Ln, a, PRO_QUANT, EPI_RESID, H, dim, G, fast_fold, 1, n_cu))) return rc;
             Ln.ga = a;
-            if (!Ln.fn) return fail(Q3_ERR_UNSUPPORTED, "no kernel instantiated for this tile shape");
-            if ((rc = set_max_smem((const void*)Ln.fn, Ln.smem))) return rc;
             if (d_stamps) { Ln.ga.stamps = kstamps ? d_kslots + 2 * (size_t)kKstampSlots * plan.size() : d_stamps + 16 * plan.size(); Ln.ga.stamp_block = dev_knob("Q3_STAMP_BLOCK", 7); }
             plan.push_back(Ln);
         }
@@ -860,16 +843,8 @@ int q3_engine::build_plan() {
         a.norm_w = rms_final;
         a.in = d_x;
         a.tap_out = d_tap;
-        GemvShape gs = plan_gemv(V, dim, G, false, 1, n_cu, big_cap, false);
-        const GemvCfg* lcfg = find_cfg(PRO_NORM, EPI_LOGITS, dim, G, fast_fold);
-        if (lcfg) {
-            apply_cfg(Ln, a, *lcfg, V, n_cu);
-            // streaming launch: cap the grid at the resident set (grid-stride over the row batches)
-            const unsigned cap = (unsigned)(n_cu * (lcfg->wgt >= 512 ? 1 : 2));
-            if (Ln.grid > cap) Ln.grid = cap;
-            gs.grid = Ln.grid;
-        }
-        n_argmax_slots = (int)gs.grid;
+        if ((rc = plan_role(Ln, a, PRO_NORM, EPI_LOGITS, dim, V, G, fast_fold, 1, n_cu))) return rc;
+        n_argmax_slots = (int)Ln.grid;
         HIP_TRY(hipMalloc((void**)&d_argmax_slots, 8 * (size_t)n_argmax_slots));
         HIP_TRY(hipMemset(d_argmax_slots, 0, 8 * (size_t)n_argmax_slots));
         a.argmax_slots = d_argmax_slots;
@@ -882,15 +857,7 @@ int q3_engine::build_plan() {
             a.out_cap = out_cap;
             a.prompt = d_prompt;
         }
-        if (!lcfg) {
-            Ln.fn = pick<PRO_NORM, EPI_LOGITS>(G, gs.RU, gs.JU, 0, gs.PF);
-            a.vr = gs.RU;
-            Ln.grid = gs.grid;
-            Ln.smem = gemv_smem_bytes(dim, G, a.vr, true);
-        }
         Ln.ga = a;
-        if (!Ln.fn) return fail(Q3_ERR_UNSUPPORTED, "no kernel instantiated for this tile shape");
-        if ((rc = set_max_smem((const void*)Ln.fn, Ln.smem))) return rc;
         if (d_stamps) { Ln.ga.stamps = kstamps ? d_kslots + 2 * (size_t)kKstampSlots * plan.size() : d_stamps + 16 * plan.size(); Ln.ga.stamp_block = dev_knob("Q3_STAMP_BLOCK", 7); }
         plan.push_back(Ln);
     }
@@ -1618,6 +1585,117 @@ int q3_op_matmul(float* xout, const int8_t* xq, const float* xs, const int8_t* w
     hipLaunchKernelGGL(fn, dim3(grid), dim3(kWG), smem, 0, a);
     if ((rc = op_end())) return rc;
     HIP_TRY(hipMemcpy(xout, dout.p, 4 * d, hipMemcpyDeviceToHost));
+    return Q3_OK;
+}
+
+int q3_op_gemv_role(int role, float* out, float* tap_out, int32_t* argmax_index, int32_t* launch_info, const float* in,
+                    const float* norm_w, const int8_t* pre_q, const float* pre_s, const int8_t* wq, const float* ws, size_t n,
+                    size_t rows, size_t rows_kv, size_t head_dim, size_t group_size, uint32_t flags, int device) {
+    int rc = op_begin(device);
+    if (rc) return rc;
+    int pro, epi;
+    switch (role) {
+        case Q3_ROLE_NORM_QKV: pro = PRO_NORM; epi = EPI_QKV; break;
+        case Q3_ROLE_NORM_SWIGLU: pro = PRO_NORM; epi = EPI_SWIGLU; break;
+        case Q3_ROLE_QUANT_RESID: pro = PRO_QUANT; epi = EPI_RESID; break;
+        case Q3_ROLE_PREQR_RESID: pro = PRO_PREQR; epi = EPI_RESID; break;
+        case Q3_ROLE_NORM_LOGITS: pro = PRO_NORM; epi = EPI_LOGITS; break;
+        default: return fail(Q3_ERR_ARG, "unknown GEMV role %d", role);
+    }
+    const bool norm = pro == PRO_NORM, qkv = epi == EPI_QKV;
+    if (!out || !wq || !ws || (pro == PRO_PREQR ? (!pre_q || !pre_s) : !in) || (norm && !norm_w) ||
+        (epi == EPI_LOGITS && !argmax_index))
+        return fail(Q3_ERR_ARG, "null pointer");
+    if (flags & ~Q3_FLAG_FAST) return fail(Q3_ERR_ARG, "unknown flag bits 0x%x (0 or Q3_FLAG_FAST expected)", (unsigned)flags);
+    // the limits of check_supported() for the vector this role contracts over
+    if (!group_ok(group_size) || n == 0 || n % group_size || n % 16 || n > (norm ? 16384u : 65536u) || rows == 0 ||
+        rows > (1u << 22))
+        return fail(Q3_ERR_UNSUPPORTED, "unsupported n/group_size/rows");
+    if (qkv && (rows_kv == 0 || rows_kv > (1u << 22) || head_dim % 8 || head_dim > 256 || (head_dim & (head_dim - 1)) ||
+                rows % head_dim || rows_kv % head_dim))
+        return fail(Q3_ERR_UNSUPPORTED, "unsupported q/k/v segment shape");
+    // (build_plan additionally gates the tree fold on the developer knob Q3_FAST_FOLD, 1 in every build's default; the operator
+    // follows the flag alone, i.e. the product's selection)
+    const bool fast = (flags & Q3_FLAG_FAST) != 0;
+    const int G = (int)group_size;
+    if (pro == PRO_PREQR && !find_cfg(pro, epi, (int)n, G, fast))     // the planner falls back to PRO_QUANT: no generic kernel reads xq into registers
+        return fail(Q3_ERR_UNSUPPORTED, "PRO_PREQR has no kernel for n = %zu, group %d", n, G);
+    hipDeviceProp_t prop;
+    HIP_TRY(hipGetDeviceProperties(&prop, device));
+    const size_t wrows = qkv ? rows + 2 * rows_kv : (epi == EPI_SWIGLU ? 2 * rows : rows);   // weight rows
+    const size_t orows = qkv ? rows + 2 * rows_kv : rows;                                    // output floats
+    DevBuf din, dnw, dpq, dps, dwq, dws, dout, dtap, dst, dcell, dslots, dtok;
+    if ((rc = dwq.upload(wq, wrows * n)) || (rc = dws.upload(ws, 4 * (wrows * n / group_size)))) return rc;
+    if (pro == PRO_PREQR) {
+        if ((rc = dpq.upload(pre_q, n)) || (rc = dps.upload(pre_s, 4 * (n / group_size)))) return rc;
+    } else if ((rc = din.upload(in, 4 * n))) return rc;
+    if (norm && ((rc = dnw.upload(norm_w, 4 * n)) || (rc = dtap.alloc(4 * n)))) return rc;
+    if (epi == EPI_RESID) rc = dout.upload(out, 4 * orows);      // x += W xq
+    else rc = dout.alloc(4 * orows);
+    if (rc) return rc;
+    State st0{};                                                 // token 0, position 0, no prompt
+    if ((rc = dst.upload(&st0, sizeof(State)))) return rc;
+
+    Launch Ln;
+    GemvArgs a{};
+    a.n = (int)n;
+    a.group = G;
+    a.strict = fast ? 0 : 1;
+    a.st = dst.as<State>();
+    a.seq_len = 1;
+    a.in = din.as<float>();
+    a.norm_w = dnw.as<float>();
+    a.pre_q = dpq.as<int8_t>();
+    a.pre_s = dps.as<float>();
+    if (norm && tap_out) a.tap_out = dtap.as<float>();
+    const size_t ng = n / group_size;
+    int units = (int)rows;
+    if (qkv) {
+        const int8_t* w0 = dwq.as<int8_t>();
+        const float* s0 = dws.as<float>();
+        float* o0 = dout.as<float>();
+        a.seg[0] = Seg{w0, s0, o0, (int)rows, 0};
+        a.seg[1] = Seg{w0 + rows * n, s0 + rows * ng, o0 + rows, (int)rows_kv, 0};
+        a.seg[2] = Seg{w0 + (rows + rows_kv) * n, s0 + (rows + rows_kv) * ng, o0 + rows + rows_kv, (int)rows_kv, (int)rows_kv};
+        a.total_rows = units = (int)orows;
+        for (int k = 0; k < 2; ++k) {
+            a.qkv_dw[k] = (const char*)a.seg[k + 1].wq - (const char*)a.seg[k].wq;
+            a.qkv_ds[k] = (const char*)a.seg[k + 1].ws - (const char*)a.seg[k].ws;
+            a.qkv_do[k] = (const char*)a.seg[k + 1].out - (const char*)a.seg[k].out;
+        }
+    } else if (epi == EPI_SWIGLU) {
+        a.seg[0] = Seg{dwq.as<int8_t>(), dws.as<float>(), dout.as<float>(), (int)rows, 0};
+        a.seg[1] = Seg{dwq.as<int8_t>() + rows * n, dws.as<float>() + rows * ng, nullptr, (int)rows, 0};
+        a.total_rows = 2 * (int)rows;
+    } else {
+        a.seg[0] = Seg{dwq.as<int8_t>(), dws.as<float>(), dout.as<float>(), (int)rows, 0};
+        a.total_rows = (int)rows;
+    }
+    if ((rc = plan_role(Ln, a, pro, epi, (int)n, units, G, fast, qkv ? (int)head_dim : 1, prop.multiProcessorCount))) return rc;
+    if (epi == EPI_LOGITS) {    // the engine's form: the argmax bookkeeping of k_next folded into the classifier launch
+        if ((rc = dslots.alloc(8 * (size_t)Ln.grid)) || (rc = dcell.alloc(16)) || (rc = dtok.alloc(4))) return rc;
+        HIP_TRY(hipMemset(dcell.p, 0, 16));
+        a.argmax_slots = dslots.as<unsigned long long>();
+        a.next_cell = dcell.as<unsigned long long>();
+        a.out_tokens = dtok.as<int32_t>();
+        a.out_cap = 1;
+    }
+    Ln.ga = a;
+    hipLaunchKernelGGL(Ln.fn, dim3(Ln.grid), dim3(Ln.block), Ln.smem, 0, Ln.ga);
+    if ((rc = op_end())) return rc;
+    HIP_TRY(hipMemcpy(out, dout.p, 4 * orows, hipMemcpyDeviceToHost));
+    if (a.tap_out) HIP_TRY(hipMemcpy(tap_out, dtap.p, 4 * n, hipMemcpyDeviceToHost));
+    if (epi == EPI_LOGITS) {
+        HIP_TRY(hipMemcpy(&st0, dst.p, sizeof(State), hipMemcpyDeviceToHost));
+        *argmax_index = (int32_t)(unsigned)(st0.argmax & 0xffffffffull);
+    }
+    if (launch_info) {
+        const GemvCfg* c = find_cfg(pro, epi, (int)n, G, fast);
+        launch_info[0] = (c != nullptr && Ln.fn == c->fn) ? 1 : 0;
+        launch_info[1] = (int32_t)Ln.grid;
+        launch_info[2] = (int32_t)Ln.block;
+        launch_info[3] = a.vr;
+    }
     return Q3_OK;
 }
 

@@ -1253,8 +1253,9 @@ __global__ __launch_bounds__(WGT) void k_gemv(const GemvArgs a) {
 #pragma unroll
             for (int j = 0; j < JU; ++j) {
                 // rows that are not a whole number of wave-loads (2560, 9728): lanes past the row end hold a re-read chunk;
-                // their term is forced to +0.0, which leaves every running sum unchanged (a sum is -0.0 only before its first
-                // term, and the padding comes after the row's last group)
+                // their term is forced to -0.0, the additive identity of EVERY f32 (x + -0.0 == x, for x == -0.0 too).  +0.0 is
+                // not: a row whose every term is -0.0 (products that underflow) must stay -0.0 (tensor.rs:53-60 folds from -0.0),
+                // and the padding behind it turned the sum into +0.0
                 const int c = lane + 64 * (jt * JU + j);
                 const bool cok = chunks_fit || c < nchunks;
                 const int cc = chunks_fit ? c : min(c, nchunks - 1);
@@ -1272,7 +1273,7 @@ __global__ __launch_bounds__(WGT) void k_gemv(const GemvArgs a) {
                     d = group_sum_i32_t<4>(d);
                     t[r] = (float)d * T.sc[r][j];   // tensor.rs:59  ((dot as f32) * ws) * xs -- identical in the 4 lanes of a group
                     t[r] = t[r] * xsc;
-                    t[r] = cok ? t[r] : 0.0f;
+                    t[r] = cok ? t[r] : -0.0f;
                     acc[r] = racc[r] + t[r];
                 }
                 if constexpr (FIN == 2) {

@@ -11,6 +11,8 @@ import numpy as np
 FLAG_FAST = 1
 FLAG_NO_GRAPH = 2
 FLAG_NO_VALUE_T = 4
+# q3_op_gemv_role roles (Q3_ROLE_* of include/qwen3_hip.h)
+ROLE_NORM_QKV, ROLE_NORM_SWIGLU, ROLE_QUANT_RESID, ROLE_PREQR_RESID, ROLE_NORM_LOGITS = range(5)
 
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 _DIST_DIR = os.path.dirname(_PKG_DIR)
@@ -21,7 +23,7 @@ EXPORTED_SYMBOLS = [
     "q3_generate_greedy", "q3_host_generate", "q3_host_sample_argmax", "q3_prefill", "q3_reset_kv", "q3_read_state", "q3_batch_init", "q3_forward_batch",
     "q3_generate_greedy_batch", "q3_batch_reset_kv", "q3_batch_read_state", "q3_prefill_batched", "q3_batch_sampler_set", "q3_sampler_set", "q3_sampler_get_rng", "q3_forward_sample", "q3_generate_sampled", "q3_profile", "q3_profile_name", "q3_parse_header",
     "q3_abi_version", "q3_build_id", "q3_op_quantize", "q3_op_dequantize", "q3_op_matmul", "q3_op_rmsnorm", "q3_op_softmax",
-    "q3_op_swiglu", "q3_op_expf", "q3_op_attention", "q3_op_argmax", "q3_op_sample",
+    "q3_op_swiglu", "q3_op_expf", "q3_op_attention", "q3_op_argmax", "q3_op_sample", "q3_op_gemv_role",
 ]
 
 
@@ -161,6 +163,7 @@ def _bind(path: str) -> C.CDLL:
     L.q3_op_quantize.argtypes = [i8p, fp, fp, sz, sz, C.c_int]
     L.q3_op_dequantize.argtypes = [i8p, fp, fp, sz, sz, C.c_int]
     L.q3_op_matmul.argtypes = [fp, i8p, fp, i8p, fp, sz, sz, sz, C.c_int]
+    L.q3_op_gemv_role.argtypes = [C.c_int, fp, fp, i32p, i32p, fp, fp, i8p, fp, i8p, fp, sz, sz, sz, sz, sz, C.c_uint32, C.c_int]
     L.q3_op_rmsnorm.argtypes = [fp, fp, fp, sz, C.c_uint32, C.c_int]
     L.q3_op_softmax.argtypes = [fp, sz, C.c_uint32, C.c_int]
     L.q3_op_swiglu.argtypes = [fp, fp, sz, C.c_int]
@@ -218,6 +221,15 @@ class Transformer:
     def forward_argmax(self, token: int, pos: int) -> int:
         out = C.c_int32(-1)
         rc = self._lib.q3_forward_argmax(self._h, token, pos, C.byref(out))
+        if rc == -3:
+            raise IndexError(self._lib.q3_last_error().decode(errors="replace"))
+        _check(rc)
+        return int(out.value)
+
+    def forward_sample(self, token: int, pos: int) -> int:
+        """forward + the device sampler's draw (q3_forward_sample; argmax while no sampler with temperature > 0 is set)"""
+        out = C.c_int32(-1)
+        rc = self._lib.q3_forward_sample(self._h, token, pos, C.byref(out))
         if rc == -3:
             raise IndexError(self._lib.q3_last_error().decode(errors="replace"))
         _check(rc)
@@ -430,6 +442,49 @@ class _Ops:
         _check(load_library().q3_op_matmul(self._fp(out), self._i8(xq), self._fp(xs), self._i8(wq), self._fp(ws), n, d,
                                            group_size, self.device))
         return out
+
+    def gemv_role(self, role: int, wq, ws, n: int, rows: int, group_size: int, x=None, norm_w=None, pre_q=None, pre_s=None,
+                  out=None, rows_kv: int = 0, head_dim: int = 0, strict: bool = True) -> dict:
+        """one fused GEMV launch of the decode plan (q3_op_gemv_role; role = ROLE_*).  Returns {"out", "tap" (NORM roles),
+        "argmax" (LOGITS), "info": [table entry?, grid, threads per workgroup, rows per wave batch]}."""
+        wq = np.ascontiguousarray(wq, dtype=np.int8)
+        ws = np.ascontiguousarray(ws, dtype=np.float32)
+        n_out = rows + 2 * rows_kv if role == ROLE_NORM_QKV else rows
+        n_w = n_out if role != ROLE_NORM_SWIGLU else 2 * rows
+        if wq.size != n_w * n or ws.size != n_w * (n // group_size):
+            raise ValueError(f"weights: {n_w} rows of {n} expected")
+        norm = role in (ROLE_NORM_QKV, ROLE_NORM_SWIGLU, ROLE_NORM_LOGITS)
+        o = np.zeros(n_out, dtype=np.float32) if out is None else np.array(out, dtype=np.float32, copy=True)
+        if o.size != n_out:
+            raise ValueError("out: one float per output row")
+        null_f, null_b = C.POINTER(C.c_float)(), C.POINTER(C.c_int8)()
+        keep = []
+
+        def f32(a, size):
+            if a is None:
+                return null_f
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            if a.size != size:
+                raise ValueError(f"{size} floats expected, got {a.size}")
+            keep.append(a)
+            return self._fp(a)
+
+        def i32(a):
+            return a.ctypes.data_as(C.POINTER(C.c_int32))
+        pq = null_b
+        if pre_q is not None:
+            pre_q = np.ascontiguousarray(pre_q, dtype=np.int8)
+            if pre_q.size != n:
+                raise ValueError("pre_q: n int8 expected")
+            pq = self._i8(pre_q)
+        tap = np.zeros(n, dtype=np.float32) if norm else None
+        am = np.full(1, -1, dtype=np.int32)
+        info = np.zeros(4, dtype=np.int32)
+        _check(load_library().q3_op_gemv_role(role, self._fp(o), self._fp(tap) if norm else null_f, i32(am), i32(info),
+                                              f32(x, n), f32(norm_w, n), pq, f32(pre_s, n // group_size), self._i8(wq),
+                                              self._fp(ws), n, rows, rows_kv, head_dim, group_size,
+                                              0 if strict else FLAG_FAST, self.device))
+        return {"out": o, "tap": tap, "argmax": int(am[0]), "info": [int(v) for v in info]}
 
     def rmsnorm(self, x, w, strict: bool = True) -> np.ndarray:
         x = np.ascontiguousarray(x, dtype=np.float32)
