@@ -227,6 +227,60 @@ int q3_prefill_batched(q3_engine* e, const int32_t* tokens, size_t n_tokens, siz
 int q3_batch_read_state(q3_engine* e, int stream, int kind, size_t offset, size_t count, float* out);
 
 /* ------------------------------------------------------------------------------------------------
+ * 2c. Lossless draft verification and prompt-lookup speculative greedy decode: several tokens per pass over the
+ * weights for ONE stream.  A block of up to 32 consecutive positions -- the current token and drafted continuations -- goes
+ * through the short-block kernels of q3_prefill_batched over the engine's own KV cache and through the n-column
+ * classifier of the batched decode; a draft is accepted exactly when it equals the argmax of the position in front of it,
+ * so every returned token is the token q3_generate_greedy returns, bit-identical logits and cache rows included.
+ * Refused with Q3_ERR_UNSUPPORTED: a Q3_FLAG_FAST engine (its block and single-stream kernels are not bit-equal to each
+ * other), an engine whose sampler is set to a temperature > 0 (speculative sampling is not implemented), and the shapes
+ * q3_batch_init refuses.  The packed weight copy of q3_prefill_batched is allocated on first use and shared with it and
+ * with q3_batch_init.  No environment variable: everything is an argument.
+ * ------------------------------------------------------------------------------------------------ */
+#define Q3_VERIFY_MAX 32
+
+/* Forward tokens[0..n_tokens) at first_pos, first_pos + 1, ... in ONE weight pass.  tokens[0] is certain, tokens[1..) are drafts.
+ *   next_tokens[i] = sample_argmax(forward(tokens[i], first_pos + i)) with tokens[0..i] as the sequence so far   (i < n_tokens)
+ *   *n_accepted    = a = the number of leading drafts with tokens[j] == next_tokens[j - 1]   (j = 1, 2, ...)
+ * next_tokens[0..a] are the a + 1 tokens q3_generate_greedy returns for (tokens[0], first_pos, a + 1), and on return the
+ * engine is in the state that call leaves: cache rows first_pos .. first_pos + a written (the transposed value cache too),
+ * rows first_pos + a + 1 .. first_pos + n_tokens - 1 RESTORED to their content before the call.
+ * logits_out (may be NULL): [n_tokens][vocab_size]; row i is bit-identical to q3_forward on the same token prefix, rows
+ * behind a rejected draft included (they are the logits of the sequence the caller proposed).
+ * Q3_ERR_ARG: n_tokens 0 or > Q3_VERIFY_MAX, first_pos + n_tokens > seq_len, a token outside the vocabulary. */
+int q3_verify(q3_engine* e, const int32_t* tokens, size_t n_tokens, size_t first_pos, int32_t* next_tokens, size_t* n_accepted,
+              float* logits_out);
+
+/* The prompt-lookup drafter alone (host only, never touches the GPU).  With S = seq[0..n) and g = ngram: take the LARGEST
+ * i < n - g with S[i..i+g) == S[n-g..n); the draft is S[i+g .. min(i+g+draft_len, n)), copied to `draft` (room for draft_len
+ * tokens).  Returns the number of tokens written; 0 (no draft) when there is no such i, when n <= g, or when draft_len < 1. */
+size_t q3_lookup_draft(const int32_t* seq, size_t n, int ngram, int draft_len, int32_t* draft);
+
+/* The incremental form of the same drafter, as q3_generate_lookup runs it (a hash of n-grams, O(1) amortised per token; host
+ * only): seq[0..n_corpus) is entered first, then seq grows one token at a time.  For every length m = n_corpus .. n, the draft
+ * over seq[0..m) goes to drafts[(m - n_corpus) * draft_len ..] and its length to lens[m - n_corpus] (n - n_corpus + 1 entries). */
+int q3_lookup_trace(const int32_t* seq, size_t n, size_t n_corpus, int ngram, int draft_len, int32_t* drafts, int32_t* lens);
+
+typedef struct q3_spec_stats {
+    uint64_t verify_passes; /* block passes over the weights */
+    uint64_t single_steps;  /* ordinary single-stream steps (no draft) */
+    uint64_t drafted;       /* draft tokens put through a pass */
+    uint64_t accepted;      /* ... of which accepted */
+} q3_spec_stats;
+
+/* q3_generate_greedy with prompt-lookup drafts: the same out_tokens and the same engine state, in fewer weight passes.
+ * S = corpus ++ [first_token] ++ the tokens generated so far.  Each round drafts from S (the rule above, at most draft_len
+ * tokens, cut so that the round yields no more tokens than are still wanted, and cut in front of a corpus token outside the
+ * vocabulary); no draft -> one ordinary single-stream step through the decode graph; a draft of d tokens -> one pass of the
+ * block [current token, d drafts] that yields accepted + 1 tokens.  A call uses one block width, draft_len + 1 columns:
+ * shorter drafts are padded with repeats of their last column, no plan or graph is rebuilt between rounds.  `corpus` is
+ * the text to look continuations up in -- in real use the prompt -- and need not be what the KV cache holds.  Only the
+ * accepted count and the token ids cross PCIe.  stats may be NULL.
+ * Q3_ERR_ARG: ngram < 1, draft_len outside 0 .. Q3_VERIFY_MAX - 1, first_pos + n_tokens > seq_len. */
+int q3_generate_lookup(q3_engine* e, const int32_t* corpus, size_t n_corpus, size_t first_token, size_t first_pos, size_t n_tokens,
+                       int ngram, int draft_len, int32_t* out_tokens, q3_spec_stats* stats);
+
+/* ------------------------------------------------------------------------------------------------
  * 3. Operator-level entry points: the reference's public free functions (tensor.rs, layers.rs) run on
  *    the device over caller (host) buffers.  Used by the parity tests; same kernels/device functions
  *    as the fused forward.  `device` as in q3_create.  q3_op_rmsnorm, q3_op_softmax, q3_op_attention and

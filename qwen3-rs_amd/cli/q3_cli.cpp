@@ -206,8 +206,38 @@ int fail_engine(const char* what) {
     return 1;
 }
 
+// --lookup N: greedy decode through q3_generate_lookup in rounds of up to N + 1 tokens, handed out one by one.  history = the
+// window's tokens so far, its last one the token to forward next; everything before it is the corpus the drafts are looked up in
+// (n-gram length 2).  Rows a round writes past the point where the caller stops are rewritten before they are read.
+constexpr int kLookupNgram = 2;
+struct Lookup {
+    int draft_len = 0;
+    std::vector<int32_t> history, pending;
+    size_t head = 0;
+    void reset() { history.clear(); pending.clear(); head = 0; }
+    void restart(const std::vector<int>& ids, int32_t next) {
+        history.insert(history.end(), ids.begin(), ids.end());
+        history.push_back(next);
+        pending.clear();
+        head = 0;
+    }
+    int next(q3_engine* e, size_t pos, int seq_len, int32_t* out) {
+        if (head == pending.size()) {
+            const size_t room = (size_t)seq_len - pos, n = room < (size_t)draft_len + 1 ? room : (size_t)draft_len + 1;
+            pending.assign(n, 0);
+            head = 0;
+            const int rc = q3_generate_lookup(e, history.data(), history.size() - 1, (size_t)history.back(), pos, n, kLookupNgram, draft_len,
+                                              pending.data(), nullptr);
+            if (rc != Q3_OK) return rc;
+        }
+        *out = pending[head++];
+        history.push_back(*out);
+        return Q3_OK;
+    }
+};
+
 // generation.rs:9-48
-int run_generate(q3_engine* e, const Tokenizer& tok, int seq_len, const std::string* prompt) {
+int run_generate(q3_engine* e, const Tokenizer& tok, int seq_len, const std::string* prompt, int lookup) {
     const std::vector<int> pt = tok.encode(prompt ? *prompt : std::string());
     if (pt.empty()) {
         fprintf(stderr, "Please provide a prompt\n");
@@ -217,10 +247,15 @@ int run_generate(q3_engine* e, const Tokenizer& tok, int seq_len, const std::str
     int token = pt.back();
     size_t pos = pt.size() - 1;
     Metrics m;
+    Lookup lk;
+    lk.draft_len = lookup;
+    lk.history.assign(pt.begin(), pt.end());
     while (pos < (size_t)seq_len) {
         m.start();
         int32_t nxt = -1;
-        if (q3_forward_argmax(e, (size_t)token, pos, &nxt) != Q3_OK) return fail_engine("forward");
+        if (lookup) {
+            if (lk.next(e, pos, seq_len, &nxt) != Q3_OK) return fail_engine("lookup decode");
+        } else if (q3_forward_argmax(e, (size_t)token, pos, &nxt) != Q3_OK) return fail_engine("forward");
         ++m.n;
         if ((uint32_t)nxt == tok.bos || (uint32_t)nxt == tok.eos) break;
         out_bytes(tok.decode(token));
@@ -245,15 +280,18 @@ int prefill(q3_engine* e, const std::vector<int>& ids, size_t pos, int32_t* next
 }
 
 // generation.rs:50-151, loop for loop (see qwen3_rs_amd/cli.py::run_chat)
-int run_chat(q3_engine* e, const Tokenizer& tok, int seq_len, const std::string* cli_prompt, const std::string* system_prompt) {
+int run_chat(q3_engine* e, const Tokenizer& tok, int seq_len, const std::string* cli_prompt, const std::string* system_prompt, int lookup) {
     size_t pos = 0;
     bool user_turn = true;
     int32_t nxt = 0;
     Metrics m;
+    Lookup lk;
+    lk.draft_len = lookup;
     for (;;) {
         if (pos >= (size_t)seq_len) {      // "Reset context if window exceeded": the cache is not cleared
             pos = 0;
             user_turn = true;
+            lk.reset();
             out_bytes("\n");
         }
         if (user_turn) {
@@ -274,6 +312,7 @@ int run_chat(q3_engine* e, const Tokenizer& tok, int seq_len, const std::string*
             if (!ids.empty()) {
                 if (prefill(e, ids, pos, &nxt) != Q3_OK) return fail_engine("prefill");
                 pos += ids.size();
+                lk.restart(ids, nxt);
             }
             user_turn = false;
         } else {
@@ -286,7 +325,9 @@ int run_chat(q3_engine* e, const Tokenizer& tok, int seq_len, const std::string*
             m.start();
             out_bytes(tok.decode(nxt));
             int32_t n2 = -1;
-            if (q3_forward_argmax(e, (size_t)nxt, pos, &n2) != Q3_OK) return fail_engine("forward");
+            if (lookup && !lk.history.empty()) {
+                if (lk.next(e, pos, seq_len, &n2) != Q3_OK) return fail_engine("lookup decode");
+            } else if (q3_forward_argmax(e, (size_t)nxt, pos, &n2) != Q3_OK) return fail_engine("forward");
             nxt = n2;
             ++m.n;
             ++pos;
@@ -299,11 +340,12 @@ void usage() {
     fprintf(stderr,
             "Qwen3 inference on the MI355X engine\n\n"
             "Usage: q3_cli inference <checkpoint> [-t TEMPERATURE] [-p TOPP] [-s SEED] [-c CONTEXT] [-m generate|chat]\n"
-            "                                     [-i INPUT] [-y SYSTEM] [-r 0|1]\n"
+            "                                     [-i INPUT] [-y SYSTEM] [-r 0|1] [--lookup DRAFT_LEN]\n"
             "  -t, --temperature  [0, inf)   default 1.0\n  -p, --topp         [0, 1]     default 0.9\n"
             "  -s, --seed         random seed (default: time)\n  -c, --context      context window size (default: the checkpoint's)\n"
             "  -m, --mode         generate | chat (default chat)\n  -i, --input        input prompt\n"
-            "  -y, --system       system prompt (chat mode)\n  -r, --reasoning    0 = no thinking, 1 = thinking (default 0)\n");
+            "  -y, --system       system prompt (chat mode)\n  -r, --reasoning    0 = no thinking, 1 = thinking (default 0)\n"
+            "      --lookup       greedy only (-t 0): draft up to DRAFT_LEN (1..31) tokens per weight pass by prompt lookup; 0 = off\n");
 }
 
 }  // namespace
@@ -335,7 +377,7 @@ int main(int argc, char** argv) {
     double temperature = 1.0, topp = 0.9;
     bool have_seed = false, have_input = false, have_system = false;
     unsigned long long seed = 0;
-    long context = 0, reasoning = 0;
+    long context = 0, reasoning = 0, lookup = 0;
     std::string mode = "chat", input, system_prompt;
     for (int i = 3; i < argc; ++i) {
         const std::string a = argv[i];
@@ -354,6 +396,7 @@ int main(int argc, char** argv) {
         else if (a == "-i" || a == "--input") { input = val(); have_input = true; }
         else if (a == "-y" || a == "--system") { system_prompt = val(); have_system = true; }
         else if (a == "-r" || a == "--reasoning") reasoning = atol(val());
+        else if (a == "--lookup") lookup = atol(val());
         else {
             fprintf(stderr, "Error: unknown argument %s\n", a.c_str());
             usage();
@@ -362,6 +405,11 @@ int main(int argc, char** argv) {
     }
     if (mode != "generate" && mode != "chat") {
         fprintf(stderr, "Error: Unknown mode: %s\n", mode.c_str());
+        return 1;
+    }
+    if (lookup != 0 && (temperature > 0.0 || lookup < 1 || lookup > Q3_VERIFY_MAX - 1)) {
+        fprintf(stderr, "Error: --lookup takes a draft length of 1..31 and needs -t 0: speculative decoding is greedy only "
+                        "(speculative sampling is not implemented)\n");
         return 1;
     }
     q3_engine* e = nullptr;
@@ -376,8 +424,8 @@ int main(int argc, char** argv) {
     if (!have_seed) seed = (unsigned long long)time(nullptr);      // lib.rs: SystemTime seconds when no seed is given
     const float t = (float)(temperature < 0.0 ? 0.0 : temperature), p = (float)(topp < 0.0 ? 0.0 : (topp > 1.0 ? 1.0 : topp));
     if (q3_sampler_set(e, t, p, (uint64_t)seed) != Q3_OK) return fail_engine("sampler");
-    const int rc = mode == "generate" ? run_generate(e, tok, cfg.seq_len, have_input ? &input : nullptr)
-                                      : run_chat(e, tok, cfg.seq_len, have_input ? &input : nullptr, have_system ? &system_prompt : nullptr);
+    const int rc = mode == "generate" ? run_generate(e, tok, cfg.seq_len, have_input ? &input : nullptr, (int)lookup)
+                                      : run_chat(e, tok, cfg.seq_len, have_input ? &input : nullptr, have_system ? &system_prompt : nullptr, (int)lookup);
     q3_destroy(e);
     return rc;
 }

@@ -2345,4 +2345,119 @@ __global__ __launch_bounds__(kWG) void k_next_batch(State* st, const unsigned lo
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Draft verification (q3_verify / q3_generate_lookup): a block of n positions of ONE sequence -- tokens[0] certain,
+// tokens[1..n) drafts -- goes through the short-block prefill layers over the engine's own KV cache and the n-column
+// classifier in one weight pass.  Three small kernels around that pass keep the engine where the sequential greedy
+// loop would have left it.  Everything they need sits in device memory (SpecIO, uploaded before the pass), so the
+// whole pass is one linear captured graph.
+// ------------------------------------------------------------------------------------------------
+constexpr int kSpecMax = 32;            // positions per verify pass (Q3_VERIFY_MAX)
+struct SpecIO {
+    int first_pos, n_real;              // in: block start, live columns (the plan may be wider: see k_spec_snapshot)
+    int tokens[kSpecMax];               // in
+    int n_accepted;                     // out: leading drafts equal to the argmax in front of them
+    int next[kSpecMax];                 // out: sample_argmax of every live column
+};
+
+// In front of the layers: the states of the block's columns, and a copy of the key / value rows first_pos + 1 ..
+// first_pos + n_real - 1 of every layer (the rows a rejected draft would leave behind).  Row first_pos is always kept.
+// Columns past n_real repeat the last live column (same token, same position): they compute and store the same bits into
+// the same rows, so a plan of fixed width serves every draft length without touching a row the block does not own.
+// snap: [2][layers][kSpecMax - 1][kvd] (keys, then values).  The transposed value cache is not written by the pass.
+__global__ __launch_bounds__(kWG) void k_spec_snapshot(State* st, const SpecIO* __restrict__ io, int n_plan, const float* __restrict__ key,
+                                                       const float* __restrict__ value, float* __restrict__ snap, int n_layers, int seq_len, int kvd) {
+    const int first_pos = io->first_pos, n_real = io->n_real;
+    if (blockIdx.x == 0 && (int)threadIdx.x < n_plan) {
+        const int i = (int)threadIdx.x < n_real ? (int)threadIdx.x : n_real - 1;
+        State s;
+        s.token = io->tokens[i];
+        s.pos = first_pos + i;
+        s.step = 0;
+        s.prompt_len = 0;
+        s.argmax = 0ull;
+        st[threadIdx.x] = s;
+    }
+    const int kv4 = kvd >> 2;
+    const long per_layer = (long)(n_real - 1) * kv4, total = (long)n_layers * per_layer;
+    const size_t half = (size_t)n_layers * (kSpecMax - 1) * kvd;
+    for (long idx = (long)blockIdx.x * kWG + threadIdx.x; idx < total; idx += (long)gridDim.x * kWG) {
+        const int l = (int)(idx / per_layer);
+        const int rem = (int)(idx - (long)l * per_layer);
+        const int r = rem / kv4, c = rem - r * kv4;
+        const size_t src = ((size_t)l * seq_len + (size_t)(first_pos + 1 + r)) * kvd + 4 * (size_t)c;
+        const size_t dst = ((size_t)l * (kSpecMax - 1) + r) * kvd + 4 * (size_t)c;
+        *(v4f*)(snap + dst) = *(const v4f*)(key + src);
+        *(v4f*)(snap + half + dst) = *(const v4f*)(value + src);
+    }
+}
+
+// Behind the classifier, one workgroup: the argmax of every live column (the same last-maximum keys k_next_batch folds), the
+// accept walk (draft j is accepted while it equals the argmax of column j - 1), and the single-stream state after
+// n_accepted + 1 greedy steps: token, position, step count, argmax cell and the first n_accepted + 1 output tokens.
+__global__ __launch_bounds__(kWG) void k_spec_commit(SpecIO* io, const unsigned long long* __restrict__ slots, int slot_stride, int nslots,
+                                                     State* est, int32_t* out_tokens, int out_cap) {
+    __shared__ unsigned long long bests[kSpecMax];
+    const int n_real = io->n_real, lane = threadIdx.x & 63;
+    for (int col = threadIdx.x >> 6; col < n_real; col += kWaves) {
+        const unsigned long long* s = slots + (size_t)col * slot_stride;
+        unsigned long long best = 0ull;
+        for (int i = lane; i < nslots; i += 64) best = s[i] > best ? s[i] : best;
+        for (int m = 1; m < 64; m <<= 1) {
+            const unsigned lo = __shfl_xor((unsigned)best, m);
+            const unsigned hi = __shfl_xor((unsigned)(best >> 32), m);
+            const unsigned long long o = ((unsigned long long)hi << 32) | lo;
+            best = o > best ? o : best;
+        }
+        if (lane == 0) bests[col] = best;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int a = 0;
+        while (a + 1 < n_real && io->tokens[a + 1] == (int)(unsigned)(bests[a] & 0xffffffffull)) ++a;
+        io->n_accepted = a;
+        for (int i = 0; i < n_real; ++i) {
+            const int idx = (int)(unsigned)(bests[i] & 0xffffffffull);
+            io->next[i] = idx;
+            if (i <= a && i < out_cap) out_tokens[i] = idx;
+        }
+        est->token = (int)(unsigned)(bests[a] & 0xffffffffull);
+        est->pos = io->first_pos + a + 1;
+        est->step = a + 1;
+        est->prompt_len = 0;
+        est->argmax = bests[a];
+    }
+}
+
+// Behind the commit: rows of rejected drafts (first_pos + a + 1 .. first_pos + n_real - 1) get their snapshot back in the key and
+// value caches; rows first_pos .. first_pos + a get their columns in the transposed value cache (the pass wrote the row-major
+// cache only; value_t = nullptr when the engine keeps none).  Consecutive threads take consecutive positions of one element there:
+// runs of a + 1 floats in the destination.
+__global__ __launch_bounds__(kWG) void k_spec_restore(const SpecIO* __restrict__ io, float* __restrict__ key, float* __restrict__ value,
+                                                      float* __restrict__ value_t, const float* __restrict__ snap, int n_layers, int seq_len, int kvd) {
+    const int first_pos = io->first_pos, n_real = io->n_real, a = io->n_accepted;
+    const int kv4 = kvd >> 2, nrej = n_real - 1 - a;
+    const size_t half = (size_t)n_layers * (kSpecMax - 1) * kvd;
+    const long per_layer = (long)nrej * kv4, total = (long)n_layers * per_layer;
+    for (long idx = (long)blockIdx.x * kWG + threadIdx.x; idx < total; idx += (long)gridDim.x * kWG) {
+        const int l = (int)(idx / per_layer);
+        const int rem = (int)(idx - (long)l * per_layer);
+        const int r = a + rem / kv4, c = rem % kv4;                  // snapshot row r holds position first_pos + 1 + r
+        const size_t dst = ((size_t)l * seq_len + (size_t)(first_pos + 1 + r)) * kvd + 4 * (size_t)c;
+        const size_t src = ((size_t)l * (kSpecMax - 1) + r) * kvd + 4 * (size_t)c;
+        *(v4f*)(key + dst) = *(const v4f*)(snap + src);
+        *(v4f*)(value + dst) = *(const v4f*)(snap + half + src);
+    }
+    if (value_t != nullptr) {
+        const int nacc = a + 1;
+        const long tt = (long)n_layers * kvd * nacc;
+        for (long idx = (long)blockIdx.x * kWG + threadIdx.x; idx < tt; idx += (long)gridDim.x * kWG) {
+            const int r = (int)(idx % nacc);
+            const long le = idx / nacc;                              // layer * kvd + element
+            const int l = (int)(le / kvd), el = (int)(le - (long)l * kvd);
+            value_t[(size_t)le * seq_len + (size_t)(first_pos + r)] = value[((size_t)l * seq_len + (size_t)(first_pos + r)) * kvd + el];
+        }
+    }
+}
+
 }  // namespace q3

@@ -43,6 +43,11 @@ struct BatchCtx {
     std::vector<BatchLaunch> plan;
     int plan_streams = 0;        // number of streams the plan / graph were built for
     bool plan_prefill = false;   // plan built for batched prefill: positions of one sequence over the engine's own KV cache
+    bool plan_verify = false;    // plan built for draft verification: the prefill layers + the n-column classifier + k_spec_*
+    // draft verification (q3_verify / q3_generate_lookup)
+    SpecIO* spec_io = nullptr;   // device: block input and result
+    SpecIO* h_spec = nullptr;    // pinned staging of the same
+    float* spec_snap = nullptr;  // key / value rows a rejected draft would leave behind, [2][layers][kSpecMax - 1][kv_dim]
     size_t plan_head = 0;        // index of the first launch of the classifier tail (prefill blocks before the last skip it)
     bool has_kv = false;         // per-stream KV caches allocated (q3_batch_init); prefill-only contexts have none
     // per-stream device samplers (q3_batch_sampler_set)
@@ -130,6 +135,12 @@ void batch_launch_one(const BatchLaunch& L, q3_engine* e, int n) {
             hipLaunchKernelGGL(k_knorm_rope_blk, dim3((unsigned)((nvec + kKnbVec - 1) / kKnbVec)), dim3(256), knorm_blk_smem_bytes(), e->stream, L.aa, n, with_q);
         } else hipLaunchKernelGGL(k_knorm_rope, dim3(L.grid, n), dim3(64), 0, e->stream, L.aa);
     }
+    else if (L.kind == 12) hipLaunchKernelGGL(k_spec_snapshot, dim3(L.grid), dim3(kWG), 0, e->stream, b->st, b->spec_io, n, e->d_key, e->d_value, b->spec_snap,
+                                              e->cfg.n_layers, e->cfg.seq_len, e->cfg.n_kv_heads * e->cfg.head_dim);
+    else if (L.kind == 13) hipLaunchKernelGGL(k_spec_commit, dim3(1), dim3(kWG), 0, e->stream, b->spec_io, b->slots, b->nslots, b->nslots_used, e->d_state,
+                                              e->d_out_tokens, e->out_cap);
+    else if (L.kind == 14) hipLaunchKernelGGL(k_spec_restore, dim3(L.grid), dim3(kWG), 0, e->stream, b->spec_io, e->d_key, e->d_value, e->d_value_t, b->spec_snap,
+                                              e->cfg.n_layers, e->cfg.seq_len, e->cfg.n_kv_heads * e->cfg.head_dim);
     else hipLaunchKernelGGL(k_next_batch, dim3(n), dim3(kWG), 0, e->stream, b->st, b->slots, b->nslots, b->nslots_used, b->out_tokens, b->out_cap);
 }
 
@@ -139,18 +150,20 @@ void batch_free(q3_engine* e) {
     if (b->graph_exec) (void)hipGraphExecDestroy(b->graph_exec);
     if (b->graph) (void)hipGraphDestroy(b->graph);
     void* dptrs[] = {b->att_pf, b->qn, b->pq, b->ps, b->x, b->q, b->kraw, b->xb, b->hb, b->logits, b->key, b->value, b->att, b->xq_p, b->xs_p,
-                     b->st, b->slots, b->out_tokens, b->stamps, b->d_sampler, b->d_probs, b->d_sp, b->d_keys};
+                     b->st, b->slots, b->out_tokens, b->stamps, b->d_sampler, b->d_probs, b->d_sp, b->d_keys, b->spec_io, b->spec_snap};
     for (void* p : dptrs)
         if (p) (void)hipFree(p);
     if (b->h_st) (void)hipHostFree(b->h_st);
     if (b->h_tokens) (void)hipHostFree(b->h_tokens);
     if (b->h_logits) (void)hipHostFree(b->h_logits);
+    if (b->h_spec) (void)hipHostFree(b->h_spec);
     delete b;
     e->batch = nullptr;
 }
 
 // (re)build the launch list for n streams; grids and the stream-tile count are baked into the launches
-int batch_build_plan(q3_engine* e, int n, bool prefill = false) {
+// verify (with prefill): the short-block prefill layers between k_spec_snapshot and the n-column classifier + k_spec_commit + k_spec_restore
+int batch_build_plan(q3_engine* e, int n, bool prefill = false, bool verify = false) {
     BatchCtx* b = e->batch;
     const q3_config& c = e->cfg;
     const int dim = c.dim, L = c.n_layers, hd = c.head_dim, V = c.vocab_size, H = c.hidden_dim, G = c.group_size;
@@ -173,8 +186,18 @@ int batch_build_plan(q3_engine* e, int n, bool prefill = false) {
     if (b->graph) { (void)hipGraphDestroy(b->graph); b->graph = nullptr; }
     b->plan.clear();
     b->plan_streams = n;
-    b->plan_prefill = prefill;
+    b->plan_prefill = prefill && !verify;
+    b->plan_verify = verify;
     int rc;
+    // the copies of k_spec_snapshot / k_spec_restore: up to (n - 1) rows of kv_dim floats per layer and cache, a float4 per thread
+    const unsigned spec_grid = (unsigned)std::min<long>(8L * e->n_cu, std::max<long>(1, ((long)L * (kSpecMax - 1) * (kvd / 4) + kWG - 1) / kWG));
+    if (verify) {
+        BatchLaunch Ln;
+        Ln.kind = 12;
+        Ln.fam = F_NEXT;
+        Ln.grid = spec_grid;
+        b->plan.push_back(Ln);
+    }
 
     auto quant = [&](Family fam, int pro, const float* in, long long in_stride, int nn, const float* norm_w, bool embed) -> int {
         BatchLaunch Ln;
@@ -496,14 +519,22 @@ int batch_build_plan(q3_engine* e, int n, bool prefill = false) {
         }
     }
     b->plan_head = b->plan.size();
-    if (prefill) return Q3_OK;          // the classifier runs once, on the last position, through the single-stream launch
+    if (prefill && !verify) return Q3_OK;          // the classifier runs once, on the last position, through the single-stream launch
     if ((rc = quant(F_LMHEAD, PRO_NORM, b->x, dim, dim, e->rms_final, false))) return rc;
     {
         BGemmArgs a{};
         a.out0 = b->logits; a.out0_stride = V;
         if ((rc = gemm(F_LMHEAD, EPI_LOGITS, b->m_cls, a))) return rc;
     }
-    {
+    if (verify) {
+        BatchLaunch Ln;
+        Ln.kind = 13;
+        Ln.fam = F_NEXT;
+        b->plan.push_back(Ln);
+        Ln.kind = 14;
+        Ln.grid = spec_grid;
+        b->plan.push_back(Ln);
+    } else {
         BatchLaunch Ln;
         Ln.kind = 3;
         Ln.fam = F_NEXT;
@@ -521,7 +552,7 @@ int batch_build_plan(q3_engine* e, int n, bool prefill = false) {
         Ln.fam = F_NEXT;
         b->plan.push_back(Ln);
     }
-    if (!(e->flags & Q3_FLAG_NO_GRAPH) && !prefill) {
+    if (!(e->flags & Q3_FLAG_NO_GRAPH) && (!prefill || verify)) {
         HIP_TRY(hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal));
         for (const BatchLaunch& Ln : b->plan) batch_launch_one(Ln, e, n);
         HIP_TRY(hipStreamEndCapture(e->stream, &b->graph));
@@ -557,7 +588,7 @@ int batch_set_state(q3_engine* e, const int32_t* tokens, const int32_t* pos, int
         b->h_st[i].argmax = 0ull;
     }
     HIP_TRY(hipSetDevice(e->device));
-    if (b->plan_streams != n || b->plan_prefill) {
+    if (b->plan_streams != n || b->plan_prefill || b->plan_verify) {
         int rc = batch_build_plan(e, n);
         if (rc) return rc;
     }
@@ -587,7 +618,8 @@ int batch_alloc(q3_engine* e, int max_streams, uint32_t ctx_len, bool with_kv, i
     b->max_streams = max_streams;
     b->cap = cap;
     b->ctx = (ctx_len != 0 && (int64_t)ctx_len < (int64_t)c.seq_len) ? (int)ctx_len : c.seq_len;
-    const size_t S = b->ctx, B = max_streams, C = (size_t)cap;
+    // scratch columns: a verify pass (q3_verify) is up to kSpecMax positions wide whatever max_streams is
+    const size_t S = b->ctx, B = max_streams, C = (size_t)(cap > kSpecMax ? cap : kSpecMax), BL = kSpecMax;
 
     // ---- packed weight directory
     size_t qbytes = 0, sfloats = 0;
@@ -636,7 +668,7 @@ int batch_alloc(q3_engine* e, int max_streams, uint32_t ctx_len, bool with_kv, i
     HIP_TRY(hipMalloc((void**)&b->kraw, 4 * C * kvd));
     HIP_TRY(hipMalloc((void**)&b->xb, 4 * C * ahd));
     HIP_TRY(hipMalloc((void**)&b->hb, 4 * C * H));
-    HIP_TRY(hipMalloc((void**)&b->logits, 4 * B * V));
+    HIP_TRY(hipMalloc((void**)&b->logits, 4 * BL * V));
     b->has_kv = with_kv;
     if (with_kv) {
         HIP_TRY(hipMalloc((void**)&b->key, 4 * B * b->kv_stream));
@@ -658,8 +690,12 @@ int batch_alloc(q3_engine* e, int max_streams, uint32_t ctx_len, bool with_kv, i
         HIP_TRY(hipMemset(b->stamps, 0, 8 * nst));
     }
     b->nslots = e->n_cu * 4 * kWaves;
-    HIP_TRY(hipMalloc((void**)&b->slots, 8 * B * (size_t)b->nslots));
-    HIP_TRY(hipMemsetAsync(b->slots, 0, 8 * B * (size_t)b->nslots, e->stream));
+    HIP_TRY(hipMalloc((void**)&b->slots, 8 * BL * (size_t)b->nslots));
+    HIP_TRY(hipMemsetAsync(b->slots, 0, 8 * BL * (size_t)b->nslots, e->stream));
+    HIP_TRY(hipMalloc((void**)&b->spec_io, sizeof(SpecIO)));
+    HIP_TRY(hipMemsetAsync(b->spec_io, 0, sizeof(SpecIO), e->stream));
+    HIP_TRY(hipMalloc((void**)&b->spec_snap, 4 * 2 * (size_t)L * (kSpecMax - 1) * kvd));
+    HIP_TRY(hipHostMalloc((void**)&b->h_spec, sizeof(SpecIO), hipHostMallocDefault));
     b->out_cap = (int)S;
     HIP_TRY(hipMalloc((void**)&b->out_tokens, 4 * B * S));
     HIP_TRY(hipMemsetAsync(b->out_tokens, 0, 4 * B * S, e->stream));
@@ -668,6 +704,16 @@ int batch_alloc(q3_engine* e, int max_streams, uint32_t ctx_len, bool with_kv, i
     HIP_TRY(hipHostMalloc((void**)&b->h_logits, 4 * B * V, hipHostMallocDefault));
     HIP_TRY(hipStreamSynchronize(e->stream));
     return Q3_OK;
+}
+
+// positions per weight pass of a prefill-only context (Q3_PREFILL_M)
+int prefill_block_cap(const q3_engine* e) {
+    int M = env_int("Q3_PREFILL_M", 2048);
+    if (M < 16) M = 16;
+    if (M > 4096) M = 4096;
+    M = (M + 15) & ~15;
+    if (e->cfg.group_size != 64 && M > kMaxStreams) M = kMaxStreams;
+    return M;
 }
 
 }  // namespace
@@ -695,12 +741,7 @@ int q3_prefill_batched(q3_engine* e, const int32_t* tokens, size_t n_tokens, siz
     // Round 4: default 2,048 (was 256, and capped there by a 256-thread state kernel): the launches of a block cover more tiles -- 4B
     // shape, 2,048-token prompt: 23.5k tok/s at 256, 25.5k at 512, 30.6k at 1,024, 32.3k at 2,048 (profiles/r04_prefill_ab.txt).
     // The score rows of k_attn_pf2 take 4 * M * n_heads * context bytes (1 GiB at M = 2,048, 32 heads, 4,096 positions).
-    int M = env_int("Q3_PREFILL_M", 2048);
-    if (M < 16) M = 16;
-    if (M > 4096) M = 4096;
-    M = (M + 15) & ~15;
-    if (e->cfg.group_size != 64 && M > kMaxStreams) M = kMaxStreams;
-    if (!e->batch && (rc = batch_alloc(e, kMaxStreams, 0, false, M))) return rc;
+    if (!e->batch && (rc = batch_alloc(e, kMaxStreams, 0, false, prefill_block_cap(e)))) return rc;
     BatchCtx* b = e->batch;
     HIP_TRY(hipSetDevice(e->device));
     const size_t B = (size_t)b->cap;
@@ -877,6 +918,144 @@ int q3_batch_read_state(q3_engine* e, int stream, int kind, size_t offset, size_
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(hipStreamSynchronize(e->stream));
     HIP_TRY(hipMemcpy(out, src + offset, 4 * count, hipMemcpyDeviceToHost));
+    return Q3_OK;
+}
+
+
+}  // extern "C"
+
+namespace {
+
+// what every entry point of section 2c refuses, and the shared context (packed weights + block scratch, q3_prefill_batched's)
+int spec_prepare(q3_engine* e, const char* who) {
+    if (e->flags & Q3_FLAG_FAST)
+        return fail(Q3_ERR_UNSUPPORTED, "%s needs a reference-order engine: with Q3_FLAG_FAST the block kernels and the single-stream kernels are not bit-equal, "
+                    "so a verified token need not be the token the greedy loop produces", who);
+    if (e->sampling)
+        return fail(Q3_ERR_UNSUPPORTED, "%s is greedy only: the engine's sampler is set to a temperature > 0 (speculative sampling is not implemented)", who);
+    int rc;
+    if (!e->batch && (rc = batch_alloc(e, kMaxStreams, 0, false, prefill_block_cap(e)))) return rc;
+    return Q3_OK;
+}
+
+// One verify pass over a plan of n_plan columns, n_real <= n_plan of them live.  The result is left in b->h_spec.
+int spec_pass(q3_engine* e, const int32_t* tokens, int n_real, int n_plan, size_t first_pos, float* logits_out) {
+    BatchCtx* b = e->batch;
+    int rc;
+    HIP_TRY(hipSetDevice(e->device));
+    if (b->plan_streams != n_plan || !b->plan_verify)
+        if ((rc = batch_build_plan(e, n_plan, true, true))) return rc;
+    b->h_spec->first_pos = (int)first_pos;
+    b->h_spec->n_real = n_real;
+    for (int i = 0; i < kSpecMax; ++i) b->h_spec->tokens[i] = i < n_real ? tokens[i] : 0;
+    HIP_TRY(hipMemcpyAsync(b->spec_io, b->h_spec, offsetof(SpecIO, n_accepted), hipMemcpyHostToDevice, e->stream));
+    if ((rc = batch_enqueue_step(e, n_plan))) return rc;
+    HIP_TRY(hipMemcpyAsync(&b->h_spec->n_accepted, &b->spec_io->n_accepted, sizeof(SpecIO) - offsetof(SpecIO, n_accepted), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    if (logits_out) HIP_TRY(hipMemcpy(logits_out, b->logits, 4 * (size_t)e->cfg.vocab_size * (size_t)n_real, hipMemcpyDeviceToHost));
+    return Q3_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int q3_verify(q3_engine* e, const int32_t* tokens, size_t n_tokens, size_t first_pos, int32_t* next_tokens, size_t* n_accepted, float* logits_out) {
+    g_err[0] = 0;
+    if (!e || !tokens || !next_tokens || !n_accepted) return fail(Q3_ERR_ARG, "null argument");
+    if (n_tokens == 0 || n_tokens > (size_t)kSpecMax) return fail(Q3_ERR_ARG, "n_tokens %zu out of range (1..%d)", n_tokens, kSpecMax);
+    if (first_pos >= (size_t)e->cfg.seq_len || first_pos + n_tokens > (size_t)e->cfg.seq_len)
+        return fail(Q3_ERR_ARG, "first_pos %zu + n_tokens %zu exceeds seq_len %d", first_pos, n_tokens, e->cfg.seq_len);
+    for (size_t i = 0; i < n_tokens; ++i)
+        if (tokens[i] < 0 || tokens[i] >= e->cfg.vocab_size)
+            return fail(Q3_ERR_ARG, "index out of range: token %d (vocab_size %d)", tokens[i], e->cfg.vocab_size);
+    int rc;
+    if ((rc = spec_prepare(e, "q3_verify"))) return rc;
+    if ((rc = spec_pass(e, tokens, (int)n_tokens, (int)n_tokens, first_pos, logits_out))) return rc;
+    const SpecIO* r = e->batch->h_spec;
+    *n_accepted = (size_t)r->n_accepted;
+    for (size_t i = 0; i < n_tokens; ++i) next_tokens[i] = r->next[i];
+    return Q3_OK;
+}
+
+size_t q3_lookup_draft(const int32_t* seq, size_t n, int ngram, int draft_len, int32_t* draft) {
+    if (!draft) return 0;
+    return lookup_draft_rescan(seq, n, ngram, draft_len, draft);
+}
+
+int q3_lookup_trace(const int32_t* seq, size_t n, size_t n_corpus, int ngram, int draft_len, int32_t* drafts, int32_t* lens) {
+    g_err[0] = 0;
+    if ((!seq && n) || !drafts || !lens || n_corpus > n) return fail(Q3_ERR_ARG, "null argument or n_corpus > n");
+    if (ngram < 1 || draft_len < 0) return fail(Q3_ERR_ARG, "ngram %d must be >= 1 and draft_len %d >= 0", ngram, draft_len);
+    LookupIndex idx(ngram);
+    idx.reserve(n);
+    for (size_t i = 0; i < n_corpus; ++i) idx.push(seq[i]);
+    for (size_t m = n_corpus; m <= n; ++m) {
+        lens[m - n_corpus] = (int32_t)idx.draft(draft_len, drafts + (m - n_corpus) * (size_t)draft_len);
+        if (m < n) idx.push(seq[m]);
+    }
+    return Q3_OK;
+}
+
+int q3_generate_lookup(q3_engine* e, const int32_t* corpus, size_t n_corpus, size_t first_token, size_t first_pos, size_t n_tokens, int ngram,
+                       int draft_len, int32_t* out_tokens, q3_spec_stats* stats) {
+    g_err[0] = 0;
+    if (stats) *stats = q3_spec_stats{0, 0, 0, 0};
+    if (!e || (!out_tokens && n_tokens) || (!corpus && n_corpus)) return fail(Q3_ERR_ARG, "null argument");
+    if (ngram < 1) return fail(Q3_ERR_ARG, "ngram %d must be at least 1", ngram);
+    if (draft_len < 0 || draft_len > kSpecMax - 1) return fail(Q3_ERR_ARG, "draft_len %d out of range (0..%d)", draft_len, kSpecMax - 1);
+    if (n_tokens == 0) return Q3_OK;
+    if (first_token >= (size_t)e->cfg.vocab_size || first_pos >= (size_t)e->cfg.seq_len)
+        return fail(Q3_ERR_ARG, "index out of range: token %zu (vocab_size %d), pos %zu (seq_len %d)", first_token, e->cfg.vocab_size, first_pos, e->cfg.seq_len);
+    if (first_pos + n_tokens > (size_t)e->cfg.seq_len)
+        return fail(Q3_ERR_ARG, "first_pos %zu + n_tokens %zu exceeds seq_len %d", first_pos, n_tokens, e->cfg.seq_len);
+    int rc;
+    if ((rc = spec_prepare(e, "q3_generate_lookup"))) return rc;
+    HIP_TRY(hipSetDevice(e->device));
+    q3_spec_stats st{0, 0, 0, 0};
+    LookupIndex idx(ngram);
+    idx.reserve(n_corpus + 1 + n_tokens);
+    for (size_t i = 0; i < n_corpus; ++i) idx.push(corpus[i]);
+    idx.push((int32_t)first_token);
+    // one block width per call: a shorter draft leaves the trailing columns as repeats of its last one (k_spec_snapshot)
+    const int n_plan = draft_len + 1;
+    int32_t block[kSpecMax];
+    int32_t cur = (int32_t)first_token;
+    size_t done = 0;
+    while (done < n_tokens) {
+        const size_t pos = first_pos + done, left = n_tokens - done;
+        // a pass with d drafts yields up to d + 1 tokens: never more than are still wanted (which also keeps it inside seq_len)
+        size_t d = idx.draft(draft_len, block + 1);
+        if (d > left - 1) d = left - 1;
+        // a drafted token outside the vocabulary (the corpus is the caller's) can never be accepted: the draft ends in front of it
+        for (size_t k = 0; k < d; ++k)
+            if (block[1 + k] < 0 || block[1 + k] >= e->cfg.vocab_size) { d = k; break; }
+        if (d == 0) {
+            // no draft: an ordinary single-stream step through the decode graph
+            if ((rc = e->set_state((size_t)cur, pos))) return rc;
+            if ((rc = e->enqueue_forward(false, pos))) return rc;
+            HIP_TRY(hipMemcpyAsync(e->h_tokens, e->d_out_tokens, 4, hipMemcpyDeviceToHost, e->stream));
+            HIP_TRY(hipStreamSynchronize(e->stream));
+            cur = e->h_tokens[0];
+            out_tokens[done++] = cur;
+            idx.push(cur);
+            st.single_steps++;
+            continue;
+        }
+        block[0] = cur;
+        if ((rc = spec_pass(e, block, (int)d + 1, n_plan, pos, nullptr))) return rc;
+        const SpecIO* r = e->batch->h_spec;
+        const size_t a = (size_t)r->n_accepted;
+        for (size_t i = 0; i <= a; ++i) {
+            out_tokens[done++] = r->next[i];
+            idx.push(r->next[i]);
+        }
+        cur = r->next[a];
+        st.verify_passes++;
+        st.drafted += d;
+        st.accepted += a;
+    }
+    if (stats) *stats = st;
     return Q3_OK;
 }
 

@@ -24,6 +24,7 @@
 #include <time.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <string>
 #include <vector>
 
@@ -31,6 +32,7 @@
 #include "q3_kernels.h"
 #include "q3_batch.h"
 #include "q3_sampler.h"
+#include "q3_lookup.h"
 
 namespace {
 

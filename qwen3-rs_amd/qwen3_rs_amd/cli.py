@@ -2,12 +2,14 @@
 
     python -m qwen3_rs_amd.cli export <MODEL_PATH> <OUTPUT_PATH> [--group-size 64]
     python -m qwen3_rs_amd.cli inference <checkpoint> [-t 1.0] [-p 0.9] [-s SEED] [-c CTX] [-m generate|chat]
-                                         [-i INPUT] [-y SYSTEM] [-r 0|1]
+                                         [-i INPUT] [-y SYSTEM] [-r 0|1] [--lookup DRAFT_LEN]
 
 `inference` follows generation.rs: `generate` echoes the prompt and decodes from its last token over a zero KV prefix
 (:9-48); `chat` renders the template, forwards every prompt token (one rng coin each) and decodes until BOS/EOS
 (:50-151).  Forward, sampling (temperature / top-p / xorshift64*) and the prompt loop all run on the device
 (q3_prefill, q3_forward_sample); the host only tokenizes, prints and checks for the termination tokens.
+`--lookup N` (greedy only, -t 0) decodes through q3_generate_lookup: up to N tokens drafted from the text so far (the latest
+earlier occurrence of the last two tokens) are checked in one pass over the weights; the output is the same, byte for byte.
 """
 from __future__ import annotations
 
@@ -33,7 +35,16 @@ def _out(raw: bytes):
     sys.stdout.flush()
 
 
-def run_generate(t, tok: Tokenizer, prompt: str) -> int:
+LOOKUP_NGRAM = 2
+
+
+def _lookup_round(t, history, pos: int, seq_len: int, lookup: int):
+    """one round of up to lookup + 1 greedy tokens: history[-1] is forwarded at pos, everything before it is the corpus"""
+    toks, _ = t.generate_lookup(history[:-1], history[-1], pos, min(lookup + 1, seq_len - pos), ngram=LOOKUP_NGRAM, draft_len=lookup)
+    return toks
+
+
+def run_generate(t, tok: Tokenizer, prompt: str, lookup: int = 0) -> int:
     """generation.rs:9-48"""
     prompt_tokens = tok.encode(prompt or "")
     if not prompt_tokens:
@@ -42,10 +53,17 @@ def run_generate(t, tok: Tokenizer, prompt: str) -> int:
     for p in prompt_tokens[:-1][:seq_len]:                 # echoed, never forwarded (zero KV prefix)
         _emit(tok, p)
     token, pos, n_gen, t0 = prompt_tokens[-1], len(prompt_tokens) - 1, 0, None
+    history, pending = list(prompt_tokens), []
     while pos < seq_len:
         if t0 is None:
             t0 = time.perf_counter()
-        nxt = t.forward_argmax(token, pos)                 # Sampler::sample on the device when temperature > 0
+        if lookup:                                         # a round of tokens per call, handed out one by one
+            if not pending:
+                pending = _lookup_round(t, history, pos, seq_len, lookup)
+            nxt = pending.pop(0)
+            history.append(nxt)
+        else:
+            nxt = t.forward_argmax(token, pos)             # Sampler::sample on the device when temperature > 0
         n_gen += 1
         if nxt in (tok.bos_token_id, tok.eos_token_id):
             break
@@ -74,16 +92,18 @@ def _prefill(t, ids, pos) -> int:
     return t.prefill(ids, pos)
 
 
-def run_chat(t, tok: Tokenizer, cli_prompt, system_prompt) -> int:
+def run_chat(t, tok: Tokenizer, cli_prompt, system_prompt, lookup: int = 0) -> int:
     """generation.rs:50-151, loop for loop: when the window is exhausted the position goes back to 0 and a user turn begins
     (generation.rs:65-69) -- the KV cache is NOT cleared, rows are simply rewritten from the front, and with a `-i` prompt
     the prompt is fed again exactly as the reference does (get_user_input, generation.rs:174-188)."""
     seq_len = t.get_config().seq_len
     pos, user_turn, nxt = 0, True, 0
     n_gen, t0 = 0, None
+    history, pending = [], []                              # --lookup: the window's tokens so far, tokens of the current round
     while True:
         if pos >= seq_len:                                 # "Reset context if window exceeded"
             pos, user_turn = 0, True
+            history, pending = [], []
             _out(b"\n")
         if user_turn:
             _report(n_gen, t0)
@@ -101,6 +121,7 @@ def run_chat(t, tok: Tokenizer, cli_prompt, system_prompt) -> int:
             if ids:
                 nxt = _prefill(t, ids, pos)
                 pos += len(ids)
+                history, pending = history + ids + [nxt], []
             user_turn = False
         else:
             if nxt in (tok.bos_token_id, tok.eos_token_id):
@@ -112,7 +133,13 @@ def run_chat(t, tok: Tokenizer, cli_prompt, system_prompt) -> int:
             if t0 is None:
                 t0 = time.perf_counter()
             _emit(tok, nxt)
-            nxt = t.forward_argmax(nxt, pos)
+            if lookup and history:
+                if not pending:                            # (rows a round writes past a turn's end are rewritten before they are read)
+                    pending = _lookup_round(t, history, pos, seq_len, lookup)
+                nxt = pending.pop(0)
+                history.append(nxt)
+            else:
+                nxt = t.forward_argmax(nxt, pos)
             n_gen += 1
             pos += 1
     return 0
@@ -135,6 +162,8 @@ def main(argv=None) -> int:
     inf.add_argument("-i", "--input", default=None)
     inf.add_argument("-y", "--system", default=None)
     inf.add_argument("-r", "--reasoning", type=int, default=0)
+    inf.add_argument("--lookup", type=int, default=0, metavar="DRAFT_LEN",
+                     help="greedy only (-t 0): draft up to DRAFT_LEN (1..31) tokens per weight pass by prompt lookup; 0 = off")
     a = ap.parse_args(argv)
     if a.cmd == "export":
         if not os.path.isdir(a.MODEL_PATH):
@@ -161,6 +190,10 @@ def main(argv=None) -> int:
         if a.mode not in ("generate", "chat"):
             print(f"Error: Unknown mode: {a.mode}", file=sys.stderr)
             return 1
+        if a.lookup and (a.temperature > 0.0 or not 0 < a.lookup < 32):
+            print("Error: --lookup takes a draft length of 1..31 and needs -t 0: speculative decoding is greedy only "
+                  "(speculative sampling is not implemented)", file=sys.stderr)
+            return 1
         b = TransformerBuilder(a.checkpoint)
         if a.context:
             b = b.with_ctx_length(a.context)
@@ -169,8 +202,8 @@ def main(argv=None) -> int:
             seed = a.seed if a.seed is not None else int(time.time())      # lib.rs: SystemTime seconds when no seed is given
             t.set_sampler(max(a.temperature, 0.0), min(max(a.topp, 0.0), 1.0), seed)
             if a.mode == "generate":
-                return run_generate(t, tok, a.input)
-            return run_chat(t, tok, a.input, a.system)
+                return run_generate(t, tok, a.input, a.lookup)
+            return run_chat(t, tok, a.input, a.system, a.lookup)
     ap.print_help()
     return 1
 

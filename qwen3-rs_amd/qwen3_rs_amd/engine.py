@@ -24,7 +24,9 @@ EXPORTED_SYMBOLS = [
     "q3_generate_greedy_batch", "q3_batch_reset_kv", "q3_batch_read_state", "q3_prefill_batched", "q3_batch_sampler_set", "q3_sampler_set", "q3_sampler_get_rng", "q3_forward_sample", "q3_generate_sampled", "q3_profile", "q3_profile_name", "q3_parse_header",
     "q3_abi_version", "q3_build_id", "q3_op_quantize", "q3_op_dequantize", "q3_op_matmul", "q3_op_rmsnorm", "q3_op_softmax",
     "q3_op_swiglu", "q3_op_expf", "q3_op_attention", "q3_op_argmax", "q3_op_sample", "q3_op_gemv_role",
+    "q3_verify", "q3_lookup_draft", "q3_lookup_trace", "q3_generate_lookup",
 ]
+VERIFY_MAX = 32          # Q3_VERIFY_MAX
 
 
 class Q3Error(RuntimeError):
@@ -38,6 +40,19 @@ class _Config(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         "architecture_id", "dim", "hidden_dim", "n_layers", "n_heads", "n_kv_heads", "head_dim", "seq_len",
         "vocab_size", "group_size", "shared_classifier")]
+
+
+class _SpecStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("verify_passes", "single_steps", "drafted", "accepted")]
+
+
+@dataclasses.dataclass(frozen=True)
+class SpecStats:
+    """q3_spec_stats: what a generate_lookup call did"""
+    verify_passes: int
+    single_steps: int
+    drafted: int
+    accepted: int
 
 
 @dataclasses.dataclass(frozen=True)
@@ -156,6 +171,11 @@ def _bind(path: str) -> C.CDLL:
     L.q3_batch_sampler_set.argtypes = [C.c_void_p, C.c_float, C.c_float, C.POINTER(C.c_uint64)]
     L.q3_batch_reset_kv.argtypes = [C.c_void_p]
     L.q3_batch_read_state.argtypes = [C.c_void_p, C.c_int, C.c_int, sz, sz, fp]
+    L.q3_verify.argtypes = [C.c_void_p, i32p, sz, sz, i32p, C.POINTER(sz), fp]
+    L.q3_lookup_draft.argtypes = [i32p, sz, C.c_int, C.c_int, i32p]
+    L.q3_lookup_draft.restype = sz
+    L.q3_lookup_trace.argtypes = [i32p, sz, sz, C.c_int, C.c_int, i32p, i32p]
+    L.q3_generate_lookup.argtypes = [C.c_void_p, i32p, sz, sz, sz, sz, C.c_int, C.c_int, i32p, C.POINTER(_SpecStats)]
     L.q3_profile.argtypes = [C.c_void_p, sz, sz, C.c_int, fp, C.POINTER(C.c_int32), C.c_int]
     L.q3_profile_name.argtypes = [C.c_int]
     L.q3_profile_name.restype = C.c_char_p
@@ -178,6 +198,27 @@ def _bind(path: str) -> C.CDLL:
 def _check(rc: int):
     if rc != 0:
         raise Q3Error(rc, load_library().q3_last_error().decode(errors="replace"))
+
+
+def _i32_array(tokens):
+    return (C.c_int32 * max(1, len(tokens)))(*[int(t) for t in tokens])
+
+
+def lookup_draft(seq, ngram: int, draft_len: int) -> List[int]:
+    """The prompt-lookup drafter (q3_lookup_draft, host only): the continuation of the latest earlier occurrence of the last
+    `ngram` tokens of seq, at most draft_len tokens; [] = no draft."""
+    out = (C.c_int32 * max(1, draft_len))()
+    k = load_library().q3_lookup_draft(_i32_array(seq), len(seq), ngram, draft_len, out)
+    return [int(out[i]) for i in range(k)]
+
+
+def lookup_trace(seq, n_corpus: int, ngram: int, draft_len: int) -> List[List[int]]:
+    """The incremental drafter of generate_lookup (q3_lookup_trace, host only): the drafts over seq[:m] for m = n_corpus .. len(seq)."""
+    rows = len(seq) - n_corpus + 1
+    drafts = (C.c_int32 * max(1, rows * draft_len))()
+    lens = (C.c_int32 * max(1, rows))()
+    _check(load_library().q3_lookup_trace(_i32_array(seq), len(seq), n_corpus, ngram, draft_len, drafts, lens))
+    return [[int(drafts[r * draft_len + k]) for k in range(lens[r])] for r in range(rows)]
 
 
 def parse_header(data: bytes) -> ModelConfig:
@@ -265,6 +306,35 @@ class Transformer:
             raise IndexError(self._lib.q3_last_error().decode(errors="replace"))
         _check(rc)
         return int(out.value)
+
+    # ---- draft verification and prompt-lookup decode (include/qwen3_hip.h section 2c)
+    def verify(self, tokens, first_pos: int, want_logits: bool = False):
+        """One weight pass over tokens (tokens[0] certain, the rest drafts) at first_pos..: returns (next_tokens, n_accepted) or,
+        with want_logits, (next_tokens, n_accepted, logits [n, vocab]).  next_tokens[:n_accepted + 1] are the greedy tokens and
+        the engine is left as generate_greedy(tokens[0], first_pos, n_accepted + 1) leaves it."""
+        n = len(tokens)
+        nxt = (C.c_int32 * max(1, n))()
+        acc = C.c_size_t(0)
+        logits = np.zeros((n, self._config.vocab_size), dtype=np.float32) if want_logits else None
+        lp = logits.ctypes.data_as(C.POINTER(C.c_float)) if want_logits else None
+        rc = self._lib.q3_verify(self._h, _i32_array(tokens), n, first_pos, nxt, C.byref(acc), lp)
+        if rc == -3:
+            raise IndexError(self._lib.q3_last_error().decode(errors="replace"))
+        _check(rc)
+        out = [int(nxt[i]) for i in range(n)]
+        return (out, int(acc.value), logits) if want_logits else (out, int(acc.value))
+
+    def generate_lookup(self, corpus, first_token: int, first_pos: int, n_tokens: int, ngram: int = 2, draft_len: int = 8):
+        """generate_greedy with prompt-lookup drafts (q3_generate_lookup): the same tokens and engine state in fewer weight
+        passes.  corpus: the tokens to look continuations up in (the prompt).  Returns (tokens, SpecStats)."""
+        buf = (C.c_int32 * max(1, n_tokens))()
+        st = _SpecStats()
+        rc = self._lib.q3_generate_lookup(self._h, _i32_array(corpus), len(corpus), first_token, first_pos, n_tokens, ngram, draft_len,
+                                          buf, C.byref(st))
+        if rc == -3:
+            raise IndexError(self._lib.q3_last_error().decode(errors="replace"))
+        _check(rc)
+        return [int(buf[i]) for i in range(n_tokens)], SpecStats(st.verify_passes, st.single_steps, st.drafted, st.accepted)
 
     def set_sampler(self, temperature: float, topp: float, rng_seed: int):
         """Sampler::new (sampler.rs:29-42) on the device: subsequent forward_argmax / generate_greedy / prefill calls draw

@@ -42,9 +42,43 @@ class TokenMetrics:
         return self.generated_count, self.elapsed, tps
 
 
+def _lookup_decode(transformer, history: List[int], pos: int, budget: int, stop, lookup, metrics, out: List[int], stop_first: bool):
+    """The greedy decode of both call patterns through Transformer.generate_lookup (q3_generate_lookup) with everything seen so
+    far as the corpus: rounds of draft_len + 1 tokens, so a caller sees tokens pass by pass.  history[-1] is the token to forward
+    at pos.  stop_first: chat's order (a stop token ends the turn before it is output); else generate's (it is output, then ends).
+    Returns the next position."""
+    ngram, draft_len = lookup
+    while budget > 0:
+        if stop_first and history[-1] in stop:
+            break
+        n = min(budget, draft_len + 1)
+        metrics.start_generation()
+        toks, _ = transformer.generate_lookup(history[:-1], history[-1], pos, n, ngram=ngram, draft_len=draft_len)
+        for i, nxt in enumerate(toks):
+            if stop_first:
+                out.append(history[-1])
+            else:
+                out.append(nxt)
+            metrics.increment_token()
+            history.append(nxt)
+            pos += 1
+            budget -= 1
+            if nxt in stop:                          # rows the round wrote past this point are rewritten before they are read
+                return pos
+    return pos
+
+
+def _check_lookup(lookup, sample, on_logits):
+    if sample is not sample_argmax or on_logits is not None:
+        raise ValueError("lookup= is greedy decoding on the device: no sample= / on_logits= (speculative sampling is not implemented)")
+    ngram, draft_len = lookup
+    if ngram < 1 or not 0 < draft_len < 32:
+        raise ValueError("lookup=(ngram >= 1, 0 < draft_len < 32)")
+
+
 def generate(transformer, prompt_tokens: Sequence[int], max_new_tokens: Optional[int] = None,
              stop_tokens: Iterable[int] = (), sample: Callable[[np.ndarray], int] = sample_argmax,
-             on_logits: Optional[Callable[[int, int, np.ndarray], None]] = None):
+             on_logits: Optional[Callable[[int, int, np.ndarray], None]] = None, lookup: Optional[Tuple[int, int]] = None):
     """`generate` (generation.rs:9-48).  Prompt tokens 0..n-2 never reach forward(): the first call is
     forward(prompt[n-1], n-1) over a zero KV prefix.  Returns (generated tokens incl. a terminating one,
     TokenMetrics).  max_new_tokens bounds the loop (the reference only stops at seq_len / BOS / EOS)."""
@@ -54,6 +88,14 @@ def generate(transformer, prompt_tokens: Sequence[int], max_new_tokens: Optional
     seq_len = transformer.get_config().seq_len
     metrics = TokenMetrics()
     out: List[int] = []
+    if lookup is not None:
+        # lookup=(ngram, draft_len): the same tokens through prompt-lookup speculative decoding, the prompt as corpus
+        _check_lookup(lookup, sample, on_logits)
+        pos = len(prompt_tokens) - 1
+        budget = max(seq_len - pos, 0) if max_new_tokens is None else min(max(seq_len - pos, 0), max_new_tokens)
+        _lookup_decode(transformer, [int(t) for t in prompt_tokens], pos, budget, stop, lookup, metrics, out, False)
+        metrics.report()
+        return out, metrics
     pos, token = 0, prompt_tokens[0]
     while pos < seq_len:
         if pos < len(prompt_tokens) - 1:
@@ -78,7 +120,7 @@ def generate(transformer, prompt_tokens: Sequence[int], max_new_tokens: Optional
 
 def chat_turn(transformer, prompt_tokens: Sequence[int], pos: int, max_new_tokens: int,
               stop_tokens: Iterable[int] = (), sample: Callable[[np.ndarray], int] = sample_argmax,
-              on_logits: Optional[Callable[[int, int, np.ndarray], None]] = None):
+              on_logits: Optional[Callable[[int, int, np.ndarray], None]] = None, lookup: Optional[Tuple[int, int]] = None):
     """One user turn + assistant turn of `chat` (generation.rs:94-151): every prompt token goes through
     forward() one at a time (sequential prefill, a sample drawn and discarded for each), then decode until
     a stop token.  Returns (generated tokens, next pos, TokenMetrics)."""
@@ -95,6 +137,14 @@ def chat_turn(transformer, prompt_tokens: Sequence[int], pos: int, max_new_token
         pos += 1
     metrics = TokenMetrics()
     out: List[int] = []
+    if lookup is not None:
+        # lookup=(ngram, draft_len): the assistant turn through prompt-lookup speculative decoding, the turn's prompt as corpus
+        _check_lookup(lookup, sample, on_logits)
+        if prompt_tokens:
+            history = [int(t) for t in prompt_tokens] + [int(next_token)]
+            pos = _lookup_decode(transformer, history, pos, min(max_new_tokens, max(seq_len - pos, 0)), stop, lookup, metrics, out, True)
+        metrics.report()
+        return out, pos, metrics
     while len(out) < max_new_tokens and pos < seq_len:   # handle_assistant_turn, generation.rs:127-151
         if next_token in stop:
             break
