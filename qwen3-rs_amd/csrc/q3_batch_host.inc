@@ -4,20 +4,10 @@
 // weights are streamed once per step through the int8 matrix cores (q3_batch.h).  The caller pattern this serves is
 // N concurrent `generate` loops (generation.rs:9-48) -- the reference runs them as N processes.
 
-struct BatchLaunch {
-    int kind = 0;            // 0 activation prologue, 1 matmul, 2 attention (per head), 3 bookkeeping, 4 attention (per kv head),
-                             // 7 dense prefill matmul (k_pgemm), 8 prefill attention (k_attn_pf2), 10 decode matmul (k_dgemm), 11 LDS-tiled prefill matmul (k_pgemm2)
-    Family fam = F_QKV;
-    void (*qfn)(const GemvArgs, const BQuantArgs) = nullptr;
-    void (*gfn)(const BGemmArgs) = nullptr;
-    GemvArgs ga{};
-    BQuantArgs qa{};
-    BGemmArgs ba{};
-    AttnArgs aa{};
-    unsigned grid = 1, block = 0, grid_y = 1;
-    size_t smem = 0;
-    bool gqa2 = false;       // kind 4: k_attn_gqa2 (staging and arithmetic on separate waves)
-};
+// what a BatchCtx's plan was built for.  Decode: n streams, each over its own KV cache.  Prefill: n positions of one sequence over
+// the engine's own KV cache, layers only (the classifier runs once, on the last position, through the single-stream launch).
+// Verify: the prefill layers between k_spec_snapshot and the n-column classifier + k_spec_commit + k_spec_restore.
+enum class PlanKind { Decode, Prefill, Verify };
 
 struct BatchCtx {
     int max_streams = 0, ctx = 0;
@@ -40,10 +30,9 @@ struct BatchCtx {
     State* h_st = nullptr;
     int32_t* h_tokens = nullptr;
     float* h_logits = nullptr;
-    std::vector<BatchLaunch> plan;
+    std::vector<Launch> plan;    // grids and the stream-tile count are baked in: rebuilt whenever plan_streams or plan_kind changes
     int plan_streams = 0;        // number of streams the plan / graph were built for
-    bool plan_prefill = false;   // plan built for batched prefill: positions of one sequence over the engine's own KV cache
-    bool plan_verify = false;    // plan built for draft verification: the prefill layers + the n-column classifier + k_spec_*
+    PlanKind plan_kind = PlanKind::Decode;
     // draft verification (q3_verify / q3_generate_lookup)
     SpecIO* spec_io = nullptr;   // device: block input and result
     SpecIO* h_spec = nullptr;    // pinned staging of the same
@@ -56,8 +45,7 @@ struct BatchCtx {
     float *d_probs = nullptr, *d_sp = nullptr;
     unsigned long long* d_keys = nullptr;
     SampleArgs sargs{};
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t graph_exec = nullptr;
+    Graph graph;
     size_t kv_stream = 0;        // floats per stream in key / value
     // packed-matrix directory
     struct PM { size_t q_off, s_off; int ntiles, ng; };
@@ -70,6 +58,29 @@ namespace {
 typedef void (*BGemmFn)(const BGemmArgs);
 typedef void (*BQuantFn)(const GemvArgs, const BQuantArgs);
 
+// ---- one resolver per kernel family
+// k_bquant (parts == 1) / k_bquant_split: prologue x vector length x parts.  spec: the listed models' vector lengths at group 64 as
+// compile-time n (everything that is a division in the generic kernel folds)
+BQuantFn bquant_fn(int pro, int nn, int parts, bool spec) {
+#define Q3_BQ_PICK(PRO_, N_) if (nn == N_) return (BQuantFn)k_bquant<PRO_, N_>
+#define Q3_BQS_PICK(PRO_, N_, P_) if (nn == N_) return (BQuantFn)k_bquant_split<PRO_, N_, P_>
+    if (parts == 1) {
+        if (spec && pro == PRO_QUANT) { Q3_BQ_PICK(PRO_QUANT, 2048); Q3_BQ_PICK(PRO_QUANT, 3072); Q3_BQ_PICK(PRO_QUANT, 4096); Q3_BQ_PICK(PRO_QUANT, 9728); Q3_BQ_PICK(PRO_QUANT, 12288); }
+        else if (spec && pro == PRO_EMBED_NORM) { Q3_BQ_PICK(PRO_EMBED_NORM, 1024); Q3_BQ_PICK(PRO_EMBED_NORM, 2560); Q3_BQ_PICK(PRO_EMBED_NORM, 4096); }
+        else if (spec) { Q3_BQ_PICK(PRO_NORM, 1024); Q3_BQ_PICK(PRO_NORM, 2560); Q3_BQ_PICK(PRO_NORM, 4096); }
+        return pro == PRO_QUANT ? (BQuantFn)k_bquant<PRO_QUANT> : (pro == PRO_EMBED_NORM ? (BQuantFn)k_bquant<PRO_EMBED_NORM> : (BQuantFn)k_bquant<PRO_NORM>);
+    }
+    if (spec && pro == PRO_NORM && parts == 4) { Q3_BQS_PICK(PRO_NORM, 1024, 4); Q3_BQS_PICK(PRO_NORM, 2560, 4); Q3_BQS_PICK(PRO_NORM, 4096, 4); }
+    if (spec && pro == PRO_QUANT && parts == 8) { Q3_BQS_PICK(PRO_QUANT, 2048, 8); Q3_BQS_PICK(PRO_QUANT, 3072, 8); Q3_BQS_PICK(PRO_QUANT, 4096, 8); Q3_BQS_PICK(PRO_QUANT, 9728, 8); Q3_BQS_PICK(PRO_QUANT, 12288, 8); }
+    return pro == PRO_QUANT ? (BQuantFn)k_bquant_split<PRO_QUANT> : (BQuantFn)k_bquant_split<PRO_NORM>;
+#undef Q3_BQ_PICK
+#undef Q3_BQS_PICK
+}
+
+// the matmul families are templates over the epilogue: F<EPI>(shape...) for the run-time epi (nullptr: not instantiated)
+#define Q3_BY_EPI(epi, F, ...)                                                                     \
+    ((epi) == EPI_QKV ? F<EPI_QKV>(__VA_ARGS__) : (epi) == EPI_RESID ? F<EPI_RESID>(__VA_ARGS__) : \
+     (epi) == EPI_SWIGLU ? F<EPI_SWIGLU>(__VA_ARGS__) : F<EPI_LOGITS>(__VA_ARGS__))
 template <int EPI, int RT, int NT>
 BGemmFn pick_bgemm_nj(int NJ) {
     if (NJ == 1) return (BGemmFn)k_bgemm<EPI, RT, NT, 1>;
@@ -78,11 +89,30 @@ BGemmFn pick_bgemm_nj(int NJ) {
     return nullptr;
 }
 template <int EPI>
+BGemmFn pick_bgemm(int RT, int NT, int NJ) {
+    if (RT == 2) return NT == 1 ? pick_bgemm_nj<EPI, 2, 1>(NJ) : pick_bgemm_nj<EPI, 2, 2>(NJ);
+    if constexpr (EPI != EPI_SWIGLU) return NT == 1 ? pick_bgemm_nj<EPI, 1, 1>(NJ) : pick_bgemm_nj<EPI, 1, 2>(NJ);
+    return nullptr;
+}
+// the dense prefill kernels have no classifier form
+template <int EPI>
 BGemmFn pick_pgemm(int RT, int PT) {
-    if (RT == 2) return PT == 2 ? (BGemmFn)k_pgemm<EPI, 2, 2, 6> : (PT == 1 ? (BGemmFn)k_pgemm<EPI, 2, 1, 8> : nullptr);
-    if constexpr (EPI != EPI_SWIGLU) {
-        if (RT == 1) return PT == 2 ? (BGemmFn)k_pgemm<EPI, 1, 2, 8> : (PT == 1 ? (BGemmFn)k_pgemm<EPI, 1, 1, 8> : nullptr);
+    if constexpr (EPI != EPI_LOGITS) {
+        if (RT == 2) return PT == 2 ? (BGemmFn)k_pgemm<EPI, 2, 2, 6> : (PT == 1 ? (BGemmFn)k_pgemm<EPI, 2, 1, 8> : nullptr);
+        if constexpr (EPI != EPI_SWIGLU) {
+            if (RT == 1) return PT == 2 ? (BGemmFn)k_pgemm<EPI, 1, 2, 8> : (PT == 1 ? (BGemmFn)k_pgemm<EPI, 1, 1, 8> : nullptr);
+        }
     }
+    return nullptr;
+}
+template <int EPI>
+BGemmFn pick_pgemm2(int ptw) {
+    if constexpr (EPI != EPI_LOGITS) return ptw == 8 ? (BGemmFn)k_pgemm2<EPI, 8> : (BGemmFn)k_pgemm2<EPI, 4>;
+    return nullptr;
+}
+template <int EPI>
+BGemmFn pick_pgemm3(int ptw) {      // 2 quantization groups per barrier for 4 x 8 tiles, 4 for 4 x 4
+    if constexpr (EPI != EPI_LOGITS) return ptw == 8 ? (BGemmFn)k_pgemm3<EPI, 8, 2> : (BGemmFn)k_pgemm3<EPI, 4, 4>;
     return nullptr;
 }
 // k_dgemm of a residual launch (Wo, W2) at group 64: the 16-group ring where the row length allows it, else 8; nullptr: k_bgemm
@@ -90,65 +120,23 @@ BGemmFn pick_dgemm(int ng, int& depth) {
     depth = ng % 16 == 0 ? 16 : (ng % 8 == 0 ? 8 : 0);
     return depth == 16 ? (BGemmFn)k_dgemm<16> : (depth == 8 ? (BGemmFn)k_dgemm<8> : nullptr);
 }
-template <int EPI>
-BGemmFn pick_bgemm(int RT, int NT, int NJ) {
-    if (RT == 2) return NT == 1 ? pick_bgemm_nj<EPI, 2, 1>(NJ) : pick_bgemm_nj<EPI, 2, 2>(NJ);
-    if constexpr (EPI != EPI_SWIGLU) return NT == 1 ? pick_bgemm_nj<EPI, 1, 1>(NJ) : pick_bgemm_nj<EPI, 1, 2>(NJ);
-    return nullptr;
+// per-kv-head decode attention: k_attn_gqa2 (staging and arithmetic on separate waves; head_dim 128, 2 or 4 query heads per kv head)
+// or k_attn_gqa, specialised for head_dim 128 with the same two ratios
+AttnFn attn_gqa_fn(bool gqa2, int hd, int kvm) {
+    if (gqa2) return kvm == 4 ? (AttnFn)k_attn_gqa2<4> : (AttnFn)k_attn_gqa2<2>;
+    if (hd == 128 && kvm == 4) return (AttnFn)k_attn_gqa<128, 4>;
+    if (hd == 128 && kvm == 2) return (AttnFn)k_attn_gqa<128, 2>;
+    return (AttnFn)k_attn_gqa<0, 0>;
 }
-
-void batch_launch_one(const BatchLaunch& L, q3_engine* e, int n) {
-    BatchCtx* b = e->batch;
-    if (L.kind == 0) hipLaunchKernelGGL(L.qfn, dim3(L.grid, n), dim3(kWG), L.smem, e->stream, L.ga, L.qa);
-    else if (L.kind == 1) hipLaunchKernelGGL(L.gfn, dim3(L.grid), dim3(kBThreads), L.smem, e->stream, L.ba);
-    else if (L.kind == 2) hipLaunchKernelGGL(k_attn_streams, dim3(L.grid, n), dim3(kWG), L.smem, e->stream, L.aa);
-    else if (L.kind == 4) {
-        const int kvm = L.aa.n_heads / L.aa.n_kv_heads;
-        if (L.gqa2 && kvm == 4) hipLaunchKernelGGL((k_attn_gqa2<4>), dim3(L.grid, n), dim3(kG2Threads), L.smem, e->stream, L.aa);
-        else if (L.gqa2 && kvm == 2) hipLaunchKernelGGL((k_attn_gqa2<2>), dim3(L.grid, n), dim3(kG2Threads), L.smem, e->stream, L.aa);
-        else if (L.aa.hd == 128 && kvm == 4) hipLaunchKernelGGL((k_attn_gqa<128, 4>), dim3(L.grid, n), dim3(L.block), L.smem, e->stream, L.aa);
-        else if (L.aa.hd == 128 && kvm == 2) hipLaunchKernelGGL((k_attn_gqa<128, 2>), dim3(L.grid, n), dim3(L.block), L.smem, e->stream, L.aa);
-        else hipLaunchKernelGGL((k_attn_gqa<0, 0>), dim3(L.grid, n), dim3(L.block), L.smem, e->stream, L.aa);
-    }
-    else if (L.kind == 7) hipLaunchKernelGGL(L.gfn, dim3(L.grid), dim3(kPgThreads), 0, e->stream, L.ba);
-    else if (L.kind == 10 || L.kind == 11) hipLaunchKernelGGL(L.gfn, dim3(L.grid), dim3(L.block), L.smem, e->stream, L.ba);
-    else if (L.kind == 8) {
-        const int kvm = L.aa.n_heads / L.aa.n_kv_heads;
-        if (L.gqa2) {
-            const dim3 g(L.grid, L.grid_y), blk(L.block);
-            if (L.block == (unsigned)attn_pf2_threads(kvm, 8)) {
-                if (kvm == 4) hipLaunchKernelGGL((k_attn_pf2<4, 8>), g, blk, L.smem, e->stream, L.aa);
-                else hipLaunchKernelGGL((k_attn_pf2<2, 8>), g, blk, L.smem, e->stream, L.aa);
-            } else {
-                if (kvm == 4) hipLaunchKernelGGL((k_attn_pf2<4, 4>), g, blk, L.smem, e->stream, L.aa);
-                else hipLaunchKernelGGL((k_attn_pf2<2, 4>), g, blk, L.smem, e->stream, L.aa);
-            }
-        }
-    }
-    else if (L.kind == 9) hipLaunchKernelGGL(k_sample_exp, dim3(64, n), dim3(256), 0, e->stream, b->sargs);
-    else if (L.kind == 6) hipLaunchKernelGGL(k_sample, dim3(n), dim3(kSampThreads), 4 * kSegFloats, e->stream, b->sargs);
-    else if (L.kind == 5) {
-        // long blocks of head_dim-128 models: 64 vectors per workgroup, one chain per lane (k_knorm_rope_blk); Q3_KNORM_BLK=0: one wave per vector
-        if (n >= 64 && L.aa.hd == kG2Hd && dev_knob("Q3_KNORM_BLK", 1)) {
-            const int with_q = L.grid > (unsigned)L.aa.n_kv_heads ? 1 : 0;
-            const long nvec = (long)n * (L.aa.n_kv_heads + (with_q ? L.aa.n_heads : 0));
-            hipLaunchKernelGGL(k_knorm_rope_blk, dim3((unsigned)((nvec + kKnbVec - 1) / kKnbVec)), dim3(256), knorm_blk_smem_bytes(), e->stream, L.aa, n, with_q);
-        } else hipLaunchKernelGGL(k_knorm_rope, dim3(L.grid, n), dim3(64), 0, e->stream, L.aa);
-    }
-    else if (L.kind == 12) hipLaunchKernelGGL(k_spec_snapshot, dim3(L.grid), dim3(kWG), 0, e->stream, b->st, b->spec_io, n, e->d_key, e->d_value, b->spec_snap,
-                                              e->cfg.n_layers, e->cfg.seq_len, e->cfg.n_kv_heads * e->cfg.head_dim);
-    else if (L.kind == 13) hipLaunchKernelGGL(k_spec_commit, dim3(1), dim3(kWG), 0, e->stream, b->spec_io, b->slots, b->nslots, b->nslots_used, e->d_state,
-                                              e->d_out_tokens, e->out_cap);
-    else if (L.kind == 14) hipLaunchKernelGGL(k_spec_restore, dim3(L.grid), dim3(kWG), 0, e->stream, b->spec_io, e->d_key, e->d_value, e->d_value_t, b->spec_snap,
-                                              e->cfg.n_layers, e->cfg.seq_len, e->cfg.n_kv_heads * e->cfg.head_dim);
-    else hipLaunchKernelGGL(k_next_batch, dim3(n), dim3(kWG), 0, e->stream, b->st, b->slots, b->nslots, b->nslots_used, b->out_tokens, b->out_cap);
+// dense prefill attention: query heads per kv head (2 | 4) x positions per workgroup (4 | 8)
+AttnFn attn_pf2_fn(int kvm, int np) {
+    if (np == 8) return kvm == 4 ? (AttnFn)k_attn_pf2<4, 8> : (AttnFn)k_attn_pf2<2, 8>;
+    return kvm == 4 ? (AttnFn)k_attn_pf2<4, 4> : (AttnFn)k_attn_pf2<2, 4>;
 }
 
 void batch_free(q3_engine* e) {
     BatchCtx* b = e->batch;
     if (!b) return;
-    if (b->graph_exec) (void)hipGraphExecDestroy(b->graph_exec);
-    if (b->graph) (void)hipGraphDestroy(b->graph);
     void* dptrs[] = {b->att_pf, b->qn, b->pq, b->ps, b->x, b->q, b->kraw, b->xb, b->hb, b->logits, b->key, b->value, b->att, b->xq_p, b->xs_p,
                      b->st, b->slots, b->out_tokens, b->stamps, b->d_sampler, b->d_probs, b->d_sp, b->d_keys, b->spec_io, b->spec_snap};
     for (void* p : dptrs)
@@ -161,10 +149,10 @@ void batch_free(q3_engine* e) {
     e->batch = nullptr;
 }
 
-// (re)build the launch list for n streams; grids and the stream-tile count are baked into the launches
-// verify (with prefill): the short-block prefill layers between k_spec_snapshot and the n-column classifier + k_spec_commit + k_spec_restore
-int batch_build_plan(q3_engine* e, int n, bool prefill = false, bool verify = false) {
+// (re)build the launch list for n streams (Decode) or n block positions (Prefill, Verify)
+int batch_build_plan(q3_engine* e, int n, PlanKind kind) {
     BatchCtx* b = e->batch;
+    const bool prefill = kind != PlanKind::Decode, verify = kind == PlanKind::Verify;
     const q3_config& c = e->cfg;
     const int dim = c.dim, L = c.n_layers, hd = c.head_dim, V = c.vocab_size, H = c.hidden_dim, G = c.group_size;
     const int ahd = c.n_heads * hd, kvd = c.n_kv_heads * hd, S = prefill ? c.seq_len : b->ctx;
@@ -182,27 +170,25 @@ int batch_build_plan(q3_engine* e, int n, bool prefill = false, bool verify = fa
     const int nptiles = (n + 15) / 16;
     const int att_tch = dev_knob("Q3_BATCH_ATT_TCH", 32);
     const int att_lds_max = dev_knob("Q3_ATT_LDS_MAX", 4096);
-    if (b->graph_exec) { (void)hipGraphExecDestroy(b->graph_exec); b->graph_exec = nullptr; }
-    if (b->graph) { (void)hipGraphDestroy(b->graph); b->graph = nullptr; }
+    const bool bq_spec = G == 64 && dev_knob("Q3_BQUANT_SPEC", 1) != 0;
+    b->graph.reset();
     b->plan.clear();
     b->plan_streams = n;
-    b->plan_prefill = prefill && !verify;
-    b->plan_verify = verify;
+    b->plan_kind = kind;
     int rc;
+    Launch Ln;
+    // developer timeline: the cells of the launch about to be appended
+    auto stamp_cells = [&]() -> unsigned long long* { return b->stamps ? b->stamps + 96 * (size_t)b->plan.size() : nullptr; };
     // the copies of k_spec_snapshot / k_spec_restore: up to (n - 1) rows of kv_dim floats per layer and cache, a float4 per thread
     const unsigned spec_grid = (unsigned)std::min<long>(8L * e->n_cu, std::max<long>(1, ((long)L * (kSpecMax - 1) * (kvd / 4) + kWG - 1) / kWG));
     if (verify) {
-        BatchLaunch Ln;
-        Ln.kind = 12;
-        Ln.fam = F_NEXT;
-        Ln.grid = spec_grid;
+        if ((rc = make_launch(Ln, F_NEXT, k_spec_snapshot, dim3(spec_grid), dim3(kWG), 0, b->st, b->spec_io, n, e->d_key, e->d_value, b->spec_snap,
+                              L, c.seq_len, kvd))) return rc;
         b->plan.push_back(Ln);
     }
 
-    auto quant = [&](Family fam, int pro, const float* in, long long in_stride, int nn, const float* norm_w, bool embed) -> int {
-        BatchLaunch Ln;
-        Ln.kind = 0;
-        Ln.fam = fam;
+    auto quant = [&](Family fam, int pro, const float* in, long long in_stride, int nn, const float* norm_w) -> int {
+        const bool embed = pro == PRO_EMBED_NORM, stage = pro != PRO_QUANT;
         GemvArgs a{};
         a.n = nn;
         a.group = G;
@@ -212,13 +198,12 @@ int batch_build_plan(q3_engine* e, int n, bool prefill = false, bool verify = fa
         a.in = in;
         a.norm_w = norm_w;
         if (embed) { a.emb_q = e->tok.q; a.emb_s = e->tok.s; a.x_out = b->x; }
-        Ln.ga = a;
-        Ln.qa.in_stride = in_stride;
-        Ln.qa.x_out_stride = dim;
-        Ln.qa.xq_p = b->xq_p;
-        Ln.qa.xs_p = b->xs_p;
-        Ln.qa.n_streams = n;
-        const bool stage = pro != PRO_QUANT;
+        BQuantArgs qa{};
+        qa.in_stride = in_stride;
+        qa.x_out_stride = dim;
+        qa.xq_p = b->xq_p;
+        qa.xs_p = b->xs_p;
+        qa.n_streams = n;
         // several workgroups per stream (k_bquant_split): 4 parts for the RMSNorm prologues, 8 for the plain quantize --
         // as long as a part is a whole number of quantization groups and at most two float4 slots per thread
         // (not for position blocks of 256 and more: the parts repeat the exact sum and a block that size fills the chip with one
@@ -229,47 +214,17 @@ int batch_build_plan(q3_engine* e, int n, bool prefill = false, bool verify = fa
             for (int c = (pro == PRO_QUANT ? 8 : 4); c > 1; c >>= 1)
                 if (nn % (c * G) == 0 && nn / c >= 256 && nn / c <= 8 * kWG) { parts = c; break; }
         }
+        size_t smem = gemv_smem_bytes(nn, G, 1, stage);
         if (parts > 1) {
-            if (b->stamps) Ln.ga.stamps = b->stamps + 96 * (size_t)b->plan.size();
-            Ln.grid = (unsigned)parts;
+            a.stamps = stamp_cells();
             const size_t slice = align16((size_t)(nn / parts)) + align16(4 * (size_t)(nn / parts / G));
-            Ln.smem = slice + (stage ? 4 * (size_t)(term_floats(nn) + 128) : 0);
-            Ln.qfn = pro == PRO_QUANT ? (BQuantFn)k_bquant_split<PRO_QUANT> : (BQuantFn)k_bquant_split<PRO_NORM>;
-            // the listed models' vector lengths at group 64: everything that is a division in the generic kernel folds
-            if (G == 64 && dev_knob("Q3_BQUANT_SPEC", 1)) {
-                if (pro == PRO_NORM && parts == 4) {
-                    if (nn == 1024) Ln.qfn = (BQuantFn)k_bquant_split<PRO_NORM, 1024, 4>;
-                    else if (nn == 2560) Ln.qfn = (BQuantFn)k_bquant_split<PRO_NORM, 2560, 4>;
-                    else if (nn == 4096) Ln.qfn = (BQuantFn)k_bquant_split<PRO_NORM, 4096, 4>;
-                } else if (pro == PRO_QUANT && parts == 8) {
-                    if (nn == 2048) Ln.qfn = (BQuantFn)k_bquant_split<PRO_QUANT, 2048, 8>;
-                    else if (nn == 3072) Ln.qfn = (BQuantFn)k_bquant_split<PRO_QUANT, 3072, 8>;
-                    else if (nn == 4096) Ln.qfn = (BQuantFn)k_bquant_split<PRO_QUANT, 4096, 8>;
-                    else if (nn == 9728) Ln.qfn = (BQuantFn)k_bquant_split<PRO_QUANT, 9728, 8>;
-                    else if (nn == 12288) Ln.qfn = (BQuantFn)k_bquant_split<PRO_QUANT, 12288, 8>;
-                }
-            }
-            if ((rc = set_max_smem((const void*)Ln.qfn, Ln.smem))) return rc;
-            b->plan.push_back(Ln);
-            return Q3_OK;
+            smem = slice + (stage ? 4 * (size_t)(term_floats(nn) + 128) : 0);
         }
-        Ln.smem = gemv_smem_bytes(nn, G, 1, stage);
-        Ln.qfn = pro == PRO_QUANT ? (BQuantFn)k_bquant<PRO_QUANT> : (embed ? (BQuantFn)k_bquant<PRO_EMBED_NORM> : (BQuantFn)k_bquant<PRO_NORM>);
-        if (G == 64 && dev_knob("Q3_BQUANT_SPEC", 1)) {          // the listed models' vector lengths: compile-time n (see k_bquant)
-#define Q3_BQ_PICK(PRO_, N_) if (nn == N_) Ln.qfn = (BQuantFn)k_bquant<PRO_, N_>
-            if (pro == PRO_QUANT) { Q3_BQ_PICK(PRO_QUANT, 2048); Q3_BQ_PICK(PRO_QUANT, 3072); Q3_BQ_PICK(PRO_QUANT, 4096); Q3_BQ_PICK(PRO_QUANT, 9728); Q3_BQ_PICK(PRO_QUANT, 12288); }
-            else if (embed) { Q3_BQ_PICK(PRO_EMBED_NORM, 1024); Q3_BQ_PICK(PRO_EMBED_NORM, 2560); Q3_BQ_PICK(PRO_EMBED_NORM, 4096); }
-            else { Q3_BQ_PICK(PRO_NORM, 1024); Q3_BQ_PICK(PRO_NORM, 2560); Q3_BQ_PICK(PRO_NORM, 4096); }
-#undef Q3_BQ_PICK
-        }
-        if ((rc = set_max_smem((const void*)Ln.qfn, Ln.smem))) return rc;
+        if ((rc = make_launch(Ln, fam, bquant_fn(pro, nn, parts, bq_spec), dim3((unsigned)parts, (unsigned)n), dim3(kWG), smem, a, qa))) return rc;
         b->plan.push_back(Ln);
         return Q3_OK;
     };
     auto gemm = [&](Family fam, int epi, const BatchCtx::PM& m, BGemmArgs a) -> int {
-        BatchLaunch Ln;
-        Ln.kind = 1;
-        Ln.fam = fam;
         a.wq = b->pq + m.q_off;
         a.ws = b->ps + m.s_off;
         a.xq = b->xq_p;
@@ -278,6 +233,10 @@ int batch_build_plan(q3_engine* e, int n, bool prefill = false, bool verify = fa
         a.ntiles = m.ntiles;
         a.n_streams = n;
         a.st = b->st;
+        BGemmFn fn = nullptr;
+        unsigned grid = 1, block = 0;
+        size_t smem = 0;
+        int depth = 0;
         // LDS-staged workgroup tiles of 4 row tiles x 8 or 4 position tiles (k_pgemm2, round 4), two workgroups per CU, the grid walks
         // the (row block, position block) list.  Tile width by measurement (4B shape, us per 256 positions, profiles/r04_prefill_ab.txt):
         // W1|W3 (608 tiles of 4 x 8) 45.5 vs 50.8 for 4 x 4 vs 53.2 k_pgemm; Wo / W2 (80 tiles of 4 x 8) 46.5 vs 33.9 vs 39.0; QKV 22.2 vs
@@ -293,103 +252,58 @@ int batch_build_plan(q3_engine* e, int n, bool prefill = false, bool verify = fa
             // against 32.1k for 4 x 8 -- neither kept)
             // k_pgemm3: the same workgroup tile with 4 (4 x 4 tiles) / 2 (4 x 8) quantization groups per barrier (Q3_PGEMM3=0: k_pgemm2)
             const int gs = ptw == 4 ? 4 : 2;
-            if ((m.ng % (2 * gs)) == 0 && dev_knob("Q3_PGEMM3", 1) != 0) {
-                Ln.kind = 11;
-                Ln.grid = (unsigned)(nblk < slots ? nblk : slots);
-                Ln.block = kP2Threads;
-                Ln.smem = pgemm3_smem_bytes(ptw, gs);
-                if (ptw == 8) Ln.gfn = epi == EPI_QKV ? (BGemmFn)k_pgemm3<EPI_QKV, 8, 2> : (epi == EPI_RESID ? (BGemmFn)k_pgemm3<EPI_RESID, 8, 2> : (BGemmFn)k_pgemm3<EPI_SWIGLU, 8, 2>);
-                else Ln.gfn = epi == EPI_QKV ? (BGemmFn)k_pgemm3<EPI_QKV, 4, 4> : (epi == EPI_RESID ? (BGemmFn)k_pgemm3<EPI_RESID, 4, 4> : (BGemmFn)k_pgemm3<EPI_SWIGLU, 4, 4>);
-                if ((rc = set_max_smem((const void*)Ln.gfn, Ln.smem))) return rc;
-                Ln.ba = a;
-                b->plan.push_back(Ln);
-                return Q3_OK;
-            }
-            {
-                Ln.kind = 11;
-                Ln.grid = (unsigned)(nblk < slots ? nblk : slots);
-                Ln.block = kP2Threads;
-                Ln.smem = pgemm2_smem_bytes(ptw);
-                if (ptw == 8) Ln.gfn = epi == EPI_QKV ? (BGemmFn)k_pgemm2<EPI_QKV, 8> : (epi == EPI_RESID ? (BGemmFn)k_pgemm2<EPI_RESID, 8> : (BGemmFn)k_pgemm2<EPI_SWIGLU, 8>);
-                else Ln.gfn = epi == EPI_QKV ? (BGemmFn)k_pgemm2<EPI_QKV, 4> : (epi == EPI_RESID ? (BGemmFn)k_pgemm2<EPI_RESID, 4> : (BGemmFn)k_pgemm2<EPI_SWIGLU, 4>);
-                if ((rc = set_max_smem((const void*)Ln.gfn, Ln.smem))) return rc;
-                Ln.ba = a;
-                b->plan.push_back(Ln);
-                return Q3_OK;
-            }
-        }
-        if (dense) {
+            const bool p3 = (m.ng % (2 * gs)) == 0 && dev_knob("Q3_PGEMM3", 1) != 0;
+            fn = p3 ? Q3_BY_EPI(epi, pick_pgemm3, ptw) : Q3_BY_EPI(epi, pick_pgemm2, ptw);
+            grid = (unsigned)(nblk < slots ? nblk : slots);
+            block = kP2Threads;
+            smem = p3 ? pgemm3_smem_bytes(ptw, gs) : pgemm2_smem_bytes(ptw);
+        } else if (dense) {
             // wave tasks of RT row tiles x PT position tiles; smaller tiles for the small matrices so that every SIMD has work
             // (r03 sweep, 4B shape: 2 x 2 tiles with a 6-deep ring for the big matrices, 1 x 2 / 8-deep for the 160-tile ones)
             int RT = 2, PT = nptiles >= 2 ? 2 : 1;
             auto tasks = [&](int rt, int pt) { return (long)(m.ntiles / rt) * ((nptiles + pt - 1) / pt); };
             if (epi != EPI_SWIGLU && ((m.ntiles & 1) || tasks(RT, PT) < 8L * e->n_cu)) RT = 1;
             const long nt_ = tasks(RT, PT);
-            long grid = (nt_ + 3) / 4;
-            if (grid > 3L * e->n_cu) grid = 3L * e->n_cu;
-            Ln.kind = 7;
-            Ln.grid = (unsigned)grid;
-            switch (epi) {
-                case EPI_QKV: Ln.gfn = pick_pgemm<EPI_QKV>(RT, PT); break;
-                case EPI_RESID: Ln.gfn = pick_pgemm<EPI_RESID>(RT, PT); break;
-                case EPI_SWIGLU: Ln.gfn = pick_pgemm<EPI_SWIGLU>(RT, PT); break;
-                default: return fail(Q3_ERR_UNSUPPORTED, "dense prefill has no classifier launch");
+            if (epi == EPI_LOGITS) return fail(Q3_ERR_UNSUPPORTED, "dense prefill has no classifier launch");
+            if (!(fn = Q3_BY_EPI(epi, pick_pgemm, RT, PT))) return fail(Q3_ERR_UNSUPPORTED, "no dense prefill kernel for tile %d x %d", RT, PT);
+            grid = (unsigned)std::min<long>((nt_ + 3) / 4, 3L * e->n_cu);
+            block = kPgThreads;
+        } else if ((fn = (dgemm && epi == EPI_RESID) ? pick_dgemm(m.ng, depth) : nullptr)) {
+            // decode, group 64, residual launches (Wo, W2): every wave owns a (row tile, stream tile) accumulator tile for the whole
+            // contraction (k_dgemm).  Same-box A/B on the 8B shape (profiles/r04_batch32_dgemm.md): the residual launches gain 3-4 % of
+            // the step; QKV (11.6 vs 12.9 us), W1|W3 with the fused quantizer (27.7 vs 22.5 + 4.8 us) and the classifier (131-136 vs
+            // 130 us) in this form do not beat k_bgemm
+            grid = (unsigned)(((long)m.ntiles * NT + kDgWaves - 1) / kDgWaves);
+            block = (unsigned)kDgWaves * 64;
+            smem = dgemm_smem_bytes(depth);
+        } else {
+            a.stamps = stamp_cells();
+            // one workgroup per row task (RT tiles), two workgroups per CU (64 KiB term tile each).  Two tiles per task
+            // share the activation fragments (cost ~1.7x one tile) -- worth it once that saves rounds over the CUs.
+            const long slots = (long)e->n_cu * dev_knob("Q3_BATCH_WG_PER_CU", 2);
+            int RT = 2;
+            if (epi != EPI_SWIGLU) {
+                const long r1 = (m.ntiles + slots - 1) / slots, r2 = (m.ntiles / 2 + slots - 1) / slots;
+                RT = (m.ntiles % 2 == 0 && r2 * 17 < r1 * 10) ? 2 : 1;
+                // between one and two row tiles per CU (QKV of the 4B / 8B shapes: 384 tiles) single-tile tasks put two workgroups
+                // on half of the CUs and one on the rest; pairs give 192 CUs one task each (r04 same-box A/B: 3.376 -> 3.358 ms / step)
+                if (m.ntiles % 2 == 0 && m.ntiles > e->n_cu && m.ntiles / 2 <= e->n_cu) RT = 2;
+                const int force_rt = dev_knob("Q3_BATCH_RT", 0);
+                if (force_rt && (m.ntiles % force_rt) == 0) RT = force_rt;
             }
-            if (!Ln.gfn) return fail(Q3_ERR_UNSUPPORTED, "no dense prefill kernel for tile %d x %d", RT, PT);
-            Ln.ba = a;
-            b->plan.push_back(Ln);
-            return Q3_OK;
+            const long ntasks = m.ntiles / RT;
+            grid = (unsigned)(ntasks < slots ? ntasks : slots);
+            block = kBThreads;
+            smem = bgemm_smem_bytes(RT, NT);
+            if (epi == EPI_LOGITS) {
+                if ((int)grid > b->nslots) return fail(Q3_ERR_HIP, "argmax slot capacity");
+                a.slots = b->slots;
+                a.nslots = b->nslots;
+                b->nslots_used = (int)grid;
+            }
+            if (!(fn = Q3_BY_EPI(epi, pick_bgemm, RT, NT, NJ))) return fail(Q3_ERR_UNSUPPORTED, "no batched kernel for group size %d", G);
         }
-        // decode, group 64, residual launches (Wo, W2): every wave owns a (row tile, stream tile) accumulator tile for the whole
-        // contraction (k_dgemm).  Same-box A/B on the 8B shape (profiles/r04_batch32_dgemm.md): the residual launches gain 3-4 % of
-        // the step; QKV (11.6 vs 12.9 us), W1|W3 with the fused quantizer (27.7 vs 22.5 + 4.8 us) and the classifier (131-136 vs
-        // 130 us) in this form do not beat k_bgemm
-        int depth = 0;
-        const BGemmFn dfn = (dgemm && epi == EPI_RESID) ? pick_dgemm(m.ng, depth) : nullptr;
-        if (dfn) {
-            Ln.kind = 10;
-            Ln.grid = (unsigned)(((long)m.ntiles * NT + kDgWaves - 1) / kDgWaves);
-            Ln.block = (unsigned)kDgWaves * 64;
-            Ln.smem = dgemm_smem_bytes(depth);
-            Ln.gfn = dfn;
-            if ((rc = set_max_smem((const void*)Ln.gfn, Ln.smem))) return rc;
-            Ln.ba = a;
-            b->plan.push_back(Ln);
-            return Q3_OK;
-        }
-        if (b->stamps) a.stamps = b->stamps + 96 * (size_t)b->plan.size();
-        // one workgroup per row task (RT tiles), two workgroups per CU (64 KiB term tile each).  Two tiles per task
-        // share the activation fragments (cost ~1.7x one tile) -- worth it once that saves rounds over the CUs.
-        const long slots = (long)e->n_cu * dev_knob("Q3_BATCH_WG_PER_CU", 2);
-        int RT = 2;
-        if (epi != EPI_SWIGLU) {
-            const long r1 = (m.ntiles + slots - 1) / slots, r2 = (m.ntiles / 2 + slots - 1) / slots;
-            RT = (m.ntiles % 2 == 0 && r2 * 17 < r1 * 10) ? 2 : 1;
-            // between one and two row tiles per CU (QKV of the 4B / 8B shapes: 384 tiles) single-tile tasks put two workgroups
-            // on half of the CUs and one on the rest; pairs give 192 CUs one task each (r04 same-box A/B: 3.376 -> 3.358 ms / step)
-            if (m.ntiles % 2 == 0 && m.ntiles > e->n_cu && m.ntiles / 2 <= e->n_cu) RT = 2;
-            const int force_rt = dev_knob("Q3_BATCH_RT", 0);
-            if (force_rt && (m.ntiles % force_rt) == 0) RT = force_rt;
-        }
-        const long ntasks = m.ntiles / RT;
-        long grid = ntasks < slots ? ntasks : slots;
-        Ln.grid = (unsigned)grid;
-        Ln.smem = bgemm_smem_bytes(RT, NT);
-        if (epi == EPI_LOGITS) {
-            if ((int)grid > b->nslots) return fail(Q3_ERR_HIP, "argmax slot capacity");
-            a.slots = b->slots;
-            a.nslots = b->nslots;
-            b->nslots_used = (int)grid;
-        }
-        switch (epi) {
-            case EPI_QKV: Ln.gfn = pick_bgemm<EPI_QKV>(RT, NT, NJ); break;
-            case EPI_RESID: Ln.gfn = pick_bgemm<EPI_RESID>(RT, NT, NJ); break;
-            case EPI_SWIGLU: Ln.gfn = pick_bgemm<EPI_SWIGLU>(RT, NT, NJ); break;
-            default: Ln.gfn = pick_bgemm<EPI_LOGITS>(RT, NT, NJ); break;
-        }
-        if (!Ln.gfn) return fail(Q3_ERR_UNSUPPORTED, "no batched kernel for group size %d", G);
-        if ((rc = set_max_smem((const void*)Ln.gfn, Ln.smem))) return rc;
-        Ln.ba = a;
+        if ((rc = make_launch(Ln, fam, fn, dim3(grid), dim3(block), smem, a))) return rc;
         b->plan.push_back(Ln);
         return Q3_OK;
     };
@@ -397,7 +311,7 @@ int batch_build_plan(q3_engine* e, int n, bool prefill = false, bool verify = fa
     for (int l = 0; l < L; ++l) {
         const size_t kv_off = (size_t)l * S * kvd;
         bool fused_xb_quant = false;
-        if ((rc = quant(F_QKV, l == 0 ? PRO_EMBED_NORM : PRO_NORM, b->x, dim, dim, e->rms_att + (size_t)l * dim, l == 0))) return rc;
+        if ((rc = quant(F_QKV, l == 0 ? PRO_EMBED_NORM : PRO_NORM, b->x, dim, dim, e->rms_att + (size_t)l * dim))) return rc;
         {
             BGemmArgs a{};
             a.out0 = b->q; a.out0_stride = ahd;
@@ -407,9 +321,6 @@ int batch_build_plan(q3_engine* e, int n, bool prefill = false, bool verify = fa
             if ((rc = gemm(F_QKV, EPI_QKV, b->m_qkv[l], a))) return rc;
         }
         {
-            BatchLaunch Ln;
-            Ln.kind = 2;
-            Ln.fam = F_ATTN;
             AttnArgs a{};
             a.q = b->q;
             a.key_cache = key_base + kv_off;
@@ -435,16 +346,18 @@ int batch_build_plan(q3_engine* e, int n, bool prefill = false, bool verify = fa
                              attn_gqa_smem_bytes(hd, kv_mul, S) <= 150 * 1024 && dev_knob("Q3_BATCH_ATT_GQA", 1);
             // dense prefill, head_dim 128 with 2 or 4 query heads per kv head: k_attn_pf2 (Q3_PREFILL_ATT_PF=0: k_attn_gqa2)
             const bool use_pf = dense && hd == kG2Hd && (kv_mul == 2 || kv_mul == 4) && b->att_pf != nullptr && dev_knob("Q3_PREFILL_ATT_PF", 1);
-            const bool use_pf2 = use_pf;
             if (prefill && !gqa && !use_pf) return fail(Q3_ERR_UNSUPPORTED, "batched prefill needs the per-kv-head attention kernel");
             if (prefill) {   // all key rows of the block enter the cache before any position attends
-                BatchLaunch Kn;
-                Kn.kind = 5;
-                Kn.fam = F_ATTN;
-                if (use_pf2) a.q_out = b->qn;                       // the same launch normalises + rotates the block's query heads
-                Kn.aa = a;
-                Kn.grid = (unsigned)(c.n_kv_heads + (use_pf2 ? c.n_heads : 0));
-                b->plan.push_back(Kn);
+                if (use_pf) a.q_out = b->qn;                        // the same launch normalises + rotates the block's query heads
+                // long blocks of head_dim-128 models: 64 vectors per workgroup, one chain per lane (k_knorm_rope_blk); Q3_KNORM_BLK=0: one wave per vector
+                if (n >= 64 && hd == kG2Hd && dev_knob("Q3_KNORM_BLK", 1)) {
+                    const long nvec = (long)n * (c.n_kv_heads + (use_pf ? c.n_heads : 0));
+                    rc = make_launch(Ln, F_ATTN, k_knorm_rope_blk, dim3((unsigned)((nvec + kKnbVec - 1) / kKnbVec)), dim3(256), knorm_blk_smem_bytes(), a, n, use_pf ? 1 : 0);
+                } else {
+                    rc = make_launch(Ln, F_ATTN, k_knorm_rope, dim3((unsigned)(c.n_kv_heads + (use_pf ? c.n_heads : 0)), (unsigned)n), dim3(64), 0, a);
+                }
+                if (rc) return rc;
+                b->plan.push_back(Ln);
                 a.k_in_cache = 1;
             }
             if (use_pf) {
@@ -456,18 +369,11 @@ int batch_build_plan(q3_engine* e, int n, bool prefill = false, bool verify = fa
                 a.pack_s = b->xs_p;
                 a.group = G;
                 fused_xb_quant = true;
-                Ln.kind = 8;
-                if (b->stamps) a.stamps = b->stamps + 96 * (size_t)b->plan.size();
-                Ln.aa = a;
+                a.stamps = stamp_cells();
                 // 8 positions per workgroup once that still gives every CU a workgroup
                 const int npw = (dev_knob("Q3_PREFILL_ATT_NP", 0) == 8 || (dev_knob("Q3_PREFILL_ATT_NP", 0) == 0 && (long)c.n_kv_heads * ((n + 7) / 8) >= e->n_cu)) ? 8 : 4;
-                Ln.grid = (unsigned)c.n_kv_heads;
-                Ln.grid_y = (unsigned)((n + npw - 1) / npw);
-                Ln.block = (unsigned)attn_pf2_threads(kv_mul, npw);
-                Ln.smem = attn_pf2_smem_bytes();
-                Ln.gqa2 = use_pf2;
-                if ((rc = set_max_smem((const void*)k_attn_pf2<4, 4>, Ln.smem)) || (rc = set_max_smem((const void*)k_attn_pf2<2, 4>, Ln.smem)) ||
-                    (rc = set_max_smem((const void*)k_attn_pf2<4, 8>, Ln.smem)) || (rc = set_max_smem((const void*)k_attn_pf2<2, 8>, Ln.smem))) return rc;
+                rc = make_launch(Ln, F_ATTN, attn_pf2_fn(kv_mul, npw), dim3((unsigned)c.n_kv_heads, (unsigned)((n + npw - 1) / npw)),
+                                 dim3((unsigned)attn_pf2_threads(kv_mul, npw)), attn_pf2_smem_bytes(), a);
             } else if (gqa) {
                 // one workgroup per (stream, kv head): K/V staged once for the kv_mul query heads sharing it
                 a.att_global = nullptr;
@@ -477,41 +383,31 @@ int batch_build_plan(q3_engine* e, int n, bool prefill = false, bool verify = fa
                     a.group = G;
                     fused_xb_quant = true;
                 }
-                Ln.kind = 4;
-                if (b->stamps) a.stamps = b->stamps + 96 * (size_t)b->plan.size();
-                Ln.aa = a;
-                Ln.grid = (unsigned)c.n_kv_heads;
-                Ln.block = (unsigned)(kv_mul + 1) * 64;
-                Ln.smem = attn_gqa_smem_bytes(hd, kv_mul, S);
+                a.stamps = stamp_cells();
                 // head_dim 128 with 2 or 4 query heads per kv head: staging and arithmetic on separate waves, two LDS tiles
-                if (hd == kG2Hd && (kv_mul == 2 || kv_mul == 4) && attn_gqa2_smem_bytes(kv_mul, S) <= 150 * 1024 && dev_knob("Q3_BATCH_ATT_GQA2", 1)) {
-                    Ln.gqa2 = true;
-                    Ln.smem = attn_gqa2_smem_bytes(kv_mul, S);
-                    if ((rc = set_max_smem((const void*)k_attn_gqa2<4>, Ln.smem)) || (rc = set_max_smem((const void*)k_attn_gqa2<2>, Ln.smem))) return rc;
-                }
-                if ((rc = set_max_smem((const void*)k_attn_gqa<128, 4>, Ln.smem)) || (rc = set_max_smem((const void*)k_attn_gqa<128, 2>, Ln.smem)) ||
-                    (rc = set_max_smem((const void*)k_attn_gqa<0, 0>, Ln.smem))) return rc;
+                const bool gqa2 = hd == kG2Hd && (kv_mul == 2 || kv_mul == 4) && attn_gqa2_smem_bytes(kv_mul, S) <= 150 * 1024 && dev_knob("Q3_BATCH_ATT_GQA2", 1);
+                rc = make_launch(Ln, F_ATTN, attn_gqa_fn(gqa2, hd, kv_mul), dim3((unsigned)c.n_kv_heads, (unsigned)n),
+                                 dim3(gqa2 ? (unsigned)kG2Threads : (unsigned)(kv_mul + 1) * 64),
+                                 gqa2 ? attn_gqa2_smem_bytes(kv_mul, S) : attn_gqa_smem_bytes(hd, kv_mul, S), a);
             } else {
-                Ln.aa = a;
-                Ln.grid = (unsigned)c.n_heads;
-                Ln.smem = attn_smem_bytes(hd, a.att_global ? 0 : S, a.tch);
-                if ((rc = set_max_smem((const void*)k_attn_streams, Ln.smem))) return rc;
+                rc = make_launch(Ln, F_ATTN, k_attn_streams, dim3((unsigned)c.n_heads, (unsigned)n), dim3(kWG), attn_smem_bytes(hd, a.att_global ? 0 : S, a.tch), a);
             }
+            if (rc) return rc;
             b->plan.push_back(Ln);
         }
-        if (!fused_xb_quant && (rc = quant(F_WO, PRO_QUANT, b->xb, ahd, ahd, nullptr, false))) return rc;
+        if (!fused_xb_quant && (rc = quant(F_WO, PRO_QUANT, b->xb, ahd, ahd, nullptr))) return rc;
         {
             BGemmArgs a{};
             a.out0 = b->x; a.out0_stride = dim;
             if ((rc = gemm(F_WO, EPI_RESID, b->m_wo[l], a))) return rc;
         }
-        if ((rc = quant(F_W13, PRO_NORM, b->x, dim, dim, e->rms_ffn + (size_t)l * dim, false))) return rc;
+        if ((rc = quant(F_W13, PRO_NORM, b->x, dim, dim, e->rms_ffn + (size_t)l * dim))) return rc;
         {
             BGemmArgs a{};
             a.out0 = b->hb; a.out0_stride = H;
             if ((rc = gemm(F_W13, EPI_SWIGLU, b->m_w13[l], a))) return rc;
         }
-        if ((rc = quant(F_W2, PRO_QUANT, b->hb, H, H, nullptr, false))) return rc;
+        if ((rc = quant(F_W2, PRO_QUANT, b->hb, H, H, nullptr))) return rc;
         {
             BGemmArgs a{};
             a.out0 = b->x; a.out0_stride = dim;
@@ -520,55 +416,44 @@ int batch_build_plan(q3_engine* e, int n, bool prefill = false, bool verify = fa
     }
     b->plan_head = b->plan.size();
     if (prefill && !verify) return Q3_OK;          // the classifier runs once, on the last position, through the single-stream launch
-    if ((rc = quant(F_LMHEAD, PRO_NORM, b->x, dim, dim, e->rms_final, false))) return rc;
+    if ((rc = quant(F_LMHEAD, PRO_NORM, b->x, dim, dim, e->rms_final))) return rc;
     {
         BGemmArgs a{};
         a.out0 = b->logits; a.out0_stride = V;
         if ((rc = gemm(F_LMHEAD, EPI_LOGITS, b->m_cls, a))) return rc;
     }
     if (verify) {
-        BatchLaunch Ln;
-        Ln.kind = 13;
-        Ln.fam = F_NEXT;
+        if ((rc = make_launch(Ln, F_NEXT, k_spec_commit, dim3(1), dim3(kWG), 0, b->spec_io, b->slots, b->nslots, b->nslots_used, e->d_state,
+                              e->d_out_tokens, e->out_cap))) return rc;
         b->plan.push_back(Ln);
-        Ln.kind = 14;
-        Ln.grid = spec_grid;
+        if ((rc = make_launch(Ln, F_NEXT, k_spec_restore, dim3(spec_grid), dim3(kWG), 0, b->spec_io, e->d_key, e->d_value, e->d_value_t, b->spec_snap,
+                              L, c.seq_len, kvd))) return rc;
         b->plan.push_back(Ln);
     } else {
-        BatchLaunch Ln;
-        Ln.kind = 3;
-        Ln.fam = F_NEXT;
+        if ((rc = make_launch(Ln, F_NEXT, k_next_batch, dim3((unsigned)n), dim3(kWG), 0, b->st, b->slots, b->nslots, b->nslots_used, b->out_tokens, b->out_cap))) return rc;
         b->plan.push_back(Ln);
     }
     if (b->sampling && !prefill) {      // Sampler::sample per stream on the logits of this step (one workgroup per stream)
         if (b->sargs.pre_exp) {         // ... behind its element-wise passes spread over the chip
-            BatchLaunch Le;
-            Le.kind = 9;
-            Le.fam = F_NEXT;
-            b->plan.push_back(Le);
+            if ((rc = make_launch(Ln, F_NEXT, k_sample_exp, dim3(64, (unsigned)n), dim3(256), 0, b->sargs))) return rc;
+            b->plan.push_back(Ln);
         }
-        BatchLaunch Ln;
-        Ln.kind = 6;
-        Ln.fam = F_NEXT;
+        if ((rc = make_launch(Ln, F_NEXT, k_sample, dim3((unsigned)n), dim3(kSampThreads), 4 * kSegFloats, b->sargs))) return rc;
         b->plan.push_back(Ln);
     }
-    if (!(e->flags & Q3_FLAG_NO_GRAPH) && (!prefill || verify)) {
-        HIP_TRY(hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal));
-        for (const BatchLaunch& Ln : b->plan) batch_launch_one(Ln, e, n);
-        HIP_TRY(hipStreamEndCapture(e->stream, &b->graph));
-        HIP_TRY(hipGraphInstantiate(&b->graph_exec, b->graph, nullptr, nullptr, 0));
-    }
+    if (!(e->flags & Q3_FLAG_NO_GRAPH) && kind != PlanKind::Prefill)
+        return b->graph.capture(e->stream, [&] {
+            for (const Launch& K : b->plan) launch(K, e->stream);
+            return Q3_OK;
+        });
     return Q3_OK;
 }
 
-int batch_enqueue_step(q3_engine* e, int n) {
+int batch_enqueue_step(q3_engine* e) {
     BatchCtx* b = e->batch;
-    if (b->graph_exec) {
-        HIP_TRY(hipGraphLaunch(b->graph_exec, e->stream));
-    } else {
-        for (const BatchLaunch& Ln : b->plan) batch_launch_one(Ln, e, n);
-        HIP_TRY(hipGetLastError());
-    }
+    if (b->graph) return b->graph.launch(e->stream);
+    for (const Launch& Ln : b->plan) launch(Ln, e->stream);
+    HIP_TRY(hipGetLastError());
     return Q3_OK;
 }
 
@@ -588,8 +473,8 @@ int batch_set_state(q3_engine* e, const int32_t* tokens, const int32_t* pos, int
         b->h_st[i].argmax = 0ull;
     }
     HIP_TRY(hipSetDevice(e->device));
-    if (b->plan_streams != n || b->plan_prefill || b->plan_verify) {
-        int rc = batch_build_plan(e, n);
+    if (b->plan_streams != n || b->plan_kind != PlanKind::Decode) {
+        int rc = batch_build_plan(e, n, PlanKind::Decode);
         if (rc) return rc;
     }
     HIP_TRY(hipMemcpyAsync(b->st, b->h_st, sizeof(State) * (size_t)n, hipMemcpyHostToDevice, e->stream));
@@ -772,10 +657,10 @@ int q3_prefill_batched(q3_engine* e, const int32_t* tokens, size_t n_tokens, siz
     for (size_t base = 0; base < n_tokens; base += B) {
         const int n = (int)((n_tokens - base < B) ? n_tokens - base : B);
         n_last = n;
-        if (b->plan_streams != n || !b->plan_prefill)
-            if ((rc = batch_build_plan(e, n, true))) return rc;
+        if (b->plan_streams != n || b->plan_kind != PlanKind::Prefill)
+            if ((rc = batch_build_plan(e, n, PlanKind::Prefill))) return rc;
         hipLaunchKernelGGL(k_set_prefill_states, dim3((n + 255) / 256), dim3(256), 0, e->stream, b->st, e->d_prompt, (int)base, (int)first_pos, n);
-        for (size_t i = 0; i < b->plan_head; ++i) batch_launch_one(b->plan[i], e, n);
+        for (size_t i = 0; i < b->plan_head; ++i) launch(b->plan[i], e->stream);
         HIP_TRY(hipGetLastError());
     }
     // the matmul epilogues of the blocks wrote value rows into the row-major cache only: the transposed copy the long-context output
@@ -790,7 +675,7 @@ int q3_prefill_batched(q3_engine* e, const int32_t* tokens, size_t n_tokens, siz
     HIP_TRY(hipMemcpyAsync(e->d_x, b->x + (size_t)(n_last - 1) * e->cfg.dim, 4 * (size_t)e->cfg.dim, hipMemcpyDeviceToDevice, e->stream));
     if ((rc = e->set_state((size_t)tokens[n_tokens - 1], first_pos + n_tokens - 1))) return rc;
     for (const Launch& L : e->plan)
-        if (L.fam == F_LMHEAD || L.is_next) launch_one(L, e);
+        if (L.fam == F_LMHEAD) launch(L, e->stream);
     HIP_TRY(hipGetLastError());
     if (e->sampling) {
         // the reference draws one (discarded) sample per prompt position: n_tokens - 1 coins, then the real draw
@@ -809,7 +694,7 @@ int q3_forward_batch(q3_engine* e, const int32_t* tokens, const int32_t* pos, in
     int rc = batch_set_state(e, tokens, pos, n_streams);
     if (rc) return rc;
     BatchCtx* b = e->batch;
-    if ((rc = batch_enqueue_step(e, n_streams))) return rc;
+    if ((rc = batch_enqueue_step(e))) return rc;
     const size_t V = e->cfg.vocab_size;
     if (logits_out) HIP_TRY(hipMemcpyAsync(b->h_logits, b->logits, 4 * V * n_streams, hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipMemcpyAsync(b->h_st, b->st, sizeof(State) * (size_t)n_streams, hipMemcpyDeviceToHost, e->stream));
@@ -832,7 +717,7 @@ int q3_generate_greedy_batch(q3_engine* e, const int32_t* first_tokens, const in
         if ((size_t)first_pos[i] + n_steps > (size_t)b->ctx)
             return fail(Q3_ERR_ARG, "stream %d: first_pos %d + n_steps %zu exceeds seq_len %d", i, first_pos[i], n_steps, b->ctx);
     for (size_t k = 0; k < n_steps; ++k)
-        if ((rc = batch_enqueue_step(e, n_streams))) return rc;
+        if ((rc = batch_enqueue_step(e))) return rc;
     for (int i = 0; i < n_streams; ++i)
         HIP_TRY(hipMemcpyAsync(b->h_tokens + (size_t)i * n_steps, b->out_tokens + (size_t)i * b->out_cap, 4 * n_steps,
                                hipMemcpyDeviceToHost, e->stream));
@@ -864,8 +749,6 @@ int q3_batch_sampler_set(q3_engine* e, float temperature, float topp, const uint
     std::vector<SamplerState> h(B);
     for (int i = 0; i < B; ++i) h[i] = SamplerState{rng_seeds ? rng_seeds[i] : 0ull, temperature, topp, {0, 0, 0, 0}};
     HIP_TRY(hipMemcpy(b->d_sampler, h.data(), sizeof(SamplerState) * B, hipMemcpyHostToDevice));
-    int rc = set_max_smem((const void*)k_sample, 4 * kSegFloats);
-    if (rc) return rc;
     SampleArgs a{};
     a.logits = b->logits;
     a.n = n;
@@ -884,7 +767,7 @@ int q3_batch_sampler_set(q3_engine* e, float temperature, float topp, const uint
     a.pre_exp = dev_knob("Q3_SAMPLER_PRE_EXP", 1);
     b->sargs = a;
     const bool on = temperature != 0.0f;
-    if (on != b->sampling) b->plan_streams = 0;          // the step's launch list changes: re-plan on the next call
+    b->plan_streams = 0;                                  // the step's launches carry these arguments: re-plan on the next call
     b->sampling = on;
     return Q3_OK;
 }
@@ -943,13 +826,13 @@ int spec_pass(q3_engine* e, const int32_t* tokens, int n_real, int n_plan, size_
     BatchCtx* b = e->batch;
     int rc;
     HIP_TRY(hipSetDevice(e->device));
-    if (b->plan_streams != n_plan || !b->plan_verify)
-        if ((rc = batch_build_plan(e, n_plan, true, true))) return rc;
+    if (b->plan_streams != n_plan || b->plan_kind != PlanKind::Verify)
+        if ((rc = batch_build_plan(e, n_plan, PlanKind::Verify))) return rc;
     b->h_spec->first_pos = (int)first_pos;
     b->h_spec->n_real = n_real;
     for (int i = 0; i < kSpecMax; ++i) b->h_spec->tokens[i] = i < n_real ? tokens[i] : 0;
     HIP_TRY(hipMemcpyAsync(b->spec_io, b->h_spec, offsetof(SpecIO, n_accepted), hipMemcpyHostToDevice, e->stream));
-    if ((rc = batch_enqueue_step(e, n_plan))) return rc;
+    if ((rc = batch_enqueue_step(e))) return rc;
     HIP_TRY(hipMemcpyAsync(&b->h_spec->n_accepted, &b->spec_io->n_accepted, sizeof(SpecIO) - offsetof(SpecIO, n_accepted), hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     if (logits_out) HIP_TRY(hipMemcpy(logits_out, b->logits, 4 * (size_t)e->cfg.vocab_size * (size_t)n_real, hipMemcpyDeviceToHost));
@@ -1033,7 +916,7 @@ int q3_generate_lookup(q3_engine* e, const int32_t* corpus, size_t n_corpus, siz
         if (d == 0) {
             // no draft: an ordinary single-stream step through the decode graph
             if ((rc = e->set_state((size_t)cur, pos))) return rc;
-            if ((rc = e->enqueue_forward(false, pos))) return rc;
+            if ((rc = e->enqueue_forward(pos))) return rc;
             HIP_TRY(hipMemcpyAsync(e->h_tokens, e->d_out_tokens, 4, hipMemcpyDeviceToHost, e->stream));
             HIP_TRY(hipStreamSynchronize(e->stream));
             cur = e->h_tokens[0];

@@ -25,7 +25,10 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <new>
 #include <string>
+#include <tuple>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/qwen3_hip.h"
@@ -125,22 +128,21 @@ enum Family { F_QKV = 0, F_ATTN, F_WO, F_W13, F_W2, F_LMHEAD, F_NEXT, F_COUNT };
 const char* kFamilyNames[F_COUNT] = {"qkv", "attn", "wo", "w13", "w2", "lm_head", "next"};
 
 typedef void (*GemvFn)(const GemvArgs);
+typedef void (*AttnFn)(const AttnArgs);
 
+// One kernel launch of a plan, resolved when the plan is built: the kernel, its grid, block and dynamic LDS bytes, and the
+// kernel's own arguments (a std::tuple of its parameter types in `args`, built and read back by the typed `thunk`).
+// Copyable: plans are std::vectors.  make_launch() fills one, launch() enqueues it without looking at what it is.
+constexpr size_t kLaunchArgBytes = 512;
 struct Launch {
-    Family fam;
-    bool is_attn = false, is_next = false;
-    bool is_kfold = false; // developer (Q3_KSTAMPS): k_kstamp_fold behind the token's last launch
-    int scores_kvm = 0;    // attn_kind 1: > 0 = k_attn_scores_kv<scores_kvm> (K chunk shared by the heads of a kv head)
-    int attn_kind = 0;     // 0: single-kernel attention, 1: k_attn_scores, 2: k_attn_out (long-context split),
-                           // 3: k_attn_short (pos < 256, head_dim 64/128: K rows in registers, no LDS staging)
-    unsigned grid_y = 1;
-    GemvFn fn = nullptr;
-    GemvArgs ga{};
-    AttnArgs aa{};
-    unsigned grid = 1;
-    unsigned block = kWG;  // threads per workgroup (specialised GEMV shapes: 256 / 512 / 1024)
+    Family fam = F_QKV;
+    void (*thunk)(const Launch&, hipStream_t) = nullptr;
+    void (*kernel)() = nullptr;
+    dim3 grid, block;
     size_t smem = 0;
+    alignas(16) unsigned char args[kLaunchArgBytes] = {};
 };
+inline void launch(const Launch& L, hipStream_t st) { L.thunk(L, st); }
 
 }  // namespace
 
@@ -162,6 +164,74 @@ int set_max_smem(const void* fn, size_t bytes) {
     if (bytes > 48 * 1024) HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
     return Q3_OK;
 }
+
+template <class... KA>
+struct LaunchThunk {
+    typedef std::tuple<KA...> Args;
+    static_assert(sizeof(Args) <= kLaunchArgBytes && alignof(Args) <= 16, "kernel arguments do not fit the launch record");
+    static_assert(std::is_trivially_copy_constructible<Args>::value && std::is_trivially_destructible<Args>::value,
+                  "launch records are copied as plain bytes");
+    static void run(const Launch& L, hipStream_t st) {
+        std::apply([&](const KA&... a) { hipLaunchKernelGGL(reinterpret_cast<void (*)(KA...)>(L.kernel), L.grid, L.block, L.smem, st, a...); },
+                   *reinterpret_cast<const Args*>(L.args));
+    }
+};
+// The one place a launch record is made: the arguments are checked against the kernel's signature here, and the kernel's
+// dynamic-LDS limit is raised here (nowhere else).
+template <class... KA, class... A>
+int make_launch(Launch& L, Family fam, void (*kernel)(KA...), dim3 grid, dim3 block, size_t smem, const A&... args) {
+    static_assert(sizeof...(KA) == sizeof...(A), "argument count differs from the kernel's");
+    L = Launch{};
+    L.fam = fam;
+    L.thunk = &LaunchThunk<KA...>::run;
+    L.kernel = reinterpret_cast<void (*)()>(kernel);
+    L.grid = grid;
+    L.block = block;
+    L.smem = smem;
+    new (L.args) std::tuple<KA...>(args...);
+    return set_max_smem(reinterpret_cast<const void*>(kernel), smem);
+}
+// launches outside any plan (operator entry points, weight packing, state setup)
+template <class... KA, class... A>
+int launch_now(hipStream_t st, void (*kernel)(KA...), dim3 grid, dim3 block, size_t smem, const A&... args) {
+    Launch L;
+    const int rc = make_launch(L, F_NEXT, kernel, grid, block, smem, args...);
+    if (rc == Q3_OK) launch(L, st);
+    return rc;
+}
+
+// A captured stream graph and its executable instance.
+struct Graph {
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+    Graph() = default;
+    Graph(const Graph&) = delete;
+    Graph& operator=(const Graph&) = delete;
+    ~Graph() { reset(); }
+    explicit operator bool() const { return exec != nullptr; }
+    void reset() {
+        if (exec) (void)hipGraphExecDestroy(exec);
+        if (graph) (void)hipGraphDestroy(graph);
+        exec = nullptr;
+        graph = nullptr;
+    }
+    // body() enqueues on `st` and returns a Q3 status
+    template <class Body>
+    int capture(hipStream_t st, Body body) {
+        reset();
+        HIP_TRY(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
+        const int rc = body();
+        const hipError_t end = hipStreamEndCapture(st, &graph);
+        if (rc) return rc;
+        HIP_TRY(end);
+        HIP_TRY(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
+        return Q3_OK;
+    }
+    int launch(hipStream_t st) const {
+        HIP_TRY(hipGraphLaunch(exec, st));
+        return Q3_OK;
+    }
+};
 
 // Environment variables.  The product library reads only the documented ones (include/qwen3_hip.h, "Environment"):
 // env_int().  Everything else -- A/B switches between kernel forms that are product code for other shapes, workgroup overrides, timeline
@@ -220,30 +290,12 @@ struct q3_engine {
     // launch plans: `plan` (one attention kernel per layer) for short contexts, `plan_long` (scores + out
     // kernels over many workgroups) once pos >= split_pos; the host knows pos of every forward it enqueues
     std::vector<Launch> plan, plan_long;
-    hipGraph_t graph = nullptr, graph_long = nullptr;
-    hipGraphExec_t graph_exec = nullptr, graph_long_exec = nullptr;
-    // q3_forward as ONE graph launch: state upload (pinned h_state) -> the token's kernels -> logits download (pinned h_logits)
-    hipGraph_t graph_fwd = nullptr, graph_fwd_long = nullptr;
-    hipGraphExec_t graph_fwd_exec = nullptr, graph_fwd_long_exec = nullptr;
-    // position ranges below 64 (k_attn_short2 only; developer build, Q3_ATT_RANGES=1): one more captured pair per range, whose
-    // attention launches request their key / value rows at kernel entry (AttnArgs::row_steps) -- the host knows the position of
-    // every forward it enqueues.  Measured in round 5 (three alternations, 0.6B device loop): 577.8-582.8 us per token against
-    // 569.1-576.2 without -- the early row requests stand in the CU's address path in front of the raw q / k values the norm
-    // chains wait for.  Off; the product captures no range graphs.
-    static constexpr int kNRange = 6;
-    static constexpr int kRangeSteps[kNRange] = {1, 2, 3, 4, 6, 8};      // 8-row steps: positions < 8, 16, 24, 32, 48, 64
-    hipGraph_t graph_rng[kNRange] = {}, graph_fwd_rng[kNRange] = {};
-    hipGraphExec_t graph_rng_exec[kNRange] = {}, graph_fwd_rng_exec[kNRange] = {};
-    bool ranges = false;
-    int range_of(size_t pos) const {
-        if (!ranges) return -1;
-        for (int i = 0; i < kNRange; ++i)
-            if (pos < (size_t)(8 * kRangeSteps[i])) return i;
-        return -1;
-    }
+    Launch lm_plain;                           // the classifier launch without the folded bookkeeping (q3_profile replays launches without advancing the state)
+    size_t n_token_launches = 0;               // launches of a token in `plan` (the developer Q3_KSTAMPS reduce / fold launches follow them)
+    // captured chains, indexed [short, long]: `decode` is the token's kernels; `forward` is q3_forward as ONE graph launch -- state
+    // upload (pinned h_state) -> the token's kernels -> logits download (pinned h_logits)
+    Graph decode[2], forward[2];
     float* d_att_priv = nullptr;
-    int cmax_stride = 0;
-    int att_stride = 0;
     int split_pos = 256;
     // the transposed value cache exists iff the long-context output kernel will read it: reference-order mode (k_attn_out reads it
     // only when strict), a context that reaches split_pos, rows of whole float4, and the caller did not opt out
@@ -260,117 +312,79 @@ struct q3_engine {
     float *d_probs = nullptr, *d_sp = nullptr;
     unsigned long long* d_keys = nullptr;
     size_t keys_n2 = 0;
-    SampleArgs sargs{};
+    std::vector<Launch> sample_plan;     // the draw behind a forward (q3_sampler_set)
     int enqueue_sample();
 
     int load(const char* path, uint32_t ctx_len);
     int build_plan();
     int capture();
-    int enqueue_forward(bool eager, size_t pos, bool draw = true);
+    int enqueue_forward(size_t pos, bool draw = true);
     int set_state(size_t token, size_t pos);
     void release();
 };
 
 namespace {
 
-template <bool P_LDS>
-void launch_attn_out_t(const AttnArgs& aa, unsigned gx, unsigned gy, size_t smem, hipStream_t st) {
-    switch (aa.slice_w) {
-        case 8: hipLaunchKernelGGL((k_attn_out<8, P_LDS>), dim3(gx, gy), dim3(kAoThreads), smem, st, aa); break;
-        case 16: hipLaunchKernelGGL((k_attn_out<16, P_LDS>), dim3(gx, gy), dim3(kAoThreads), smem, st, aa); break;
-        case 32: hipLaunchKernelGGL((k_attn_out<32, P_LDS>), dim3(gx, gy), dim3(kAoThreads), smem, st, aa); break;
-        default: hipLaunchKernelGGL((k_attn_out<0, P_LDS>), dim3(gx, gy), dim3(kAoThreads), smem, st, aa); break;
+// ---- attention: one resolver per kernel family (the only place an instantiation is named), and the launch shape that goes with it
+struct AttnShape { AttnFn fn; dim3 grid, block; size_t smem; int kvm; };
+
+AttnFn attn_out_fn(int slice_w, bool p_lds) {
+    switch (slice_w) {
+        case 8: return p_lds ? (AttnFn)k_attn_out<8, true> : (AttnFn)k_attn_out<8, false>;
+        case 16: return p_lds ? (AttnFn)k_attn_out<16, true> : (AttnFn)k_attn_out<16, false>;
+        case 32: return p_lds ? (AttnFn)k_attn_out<32, true> : (AttnFn)k_attn_out<32, false>;
+        default: return p_lds ? (AttnFn)k_attn_out<0, true> : (AttnFn)k_attn_out<0, false>;
     }
 }
-void launch_attn_out(const AttnArgs& aa, unsigned gx, unsigned gy, size_t smem, hipStream_t st) {
-    if (attn_out_p_in_lds(aa.seq_len)) launch_attn_out_t<true>(aa, gx, gy, smem, st);
-    else launch_attn_out_t<false>(aa, gx, gy, smem, st);
-}
-template <bool P_LDS>
-int set_attn_out_smem_t(size_t bytes) {
-    int rc;
-    if ((rc = set_max_smem((const void*)k_attn_out<8, P_LDS>, bytes)) || (rc = set_max_smem((const void*)k_attn_out<16, P_LDS>, bytes)) ||
-        (rc = set_max_smem((const void*)k_attn_out<32, P_LDS>, bytes)) || (rc = set_max_smem((const void*)k_attn_out<0, P_LDS>, bytes))) return rc;
-    return Q3_OK;
-}
-int set_attn_out_smem(size_t bytes) {
-    int rc;
-    if ((rc = set_attn_out_smem_t<true>(bytes)) || (rc = set_attn_out_smem_t<false>(bytes))) return rc;
-    return Q3_OK;
-}
-
+AttnFn attn_scores_fn(int kvm) { return kvm == 4 ? (AttnFn)k_attn_scores_kv<4> : kvm == 2 ? (AttnFn)k_attn_scores_kv<2> : (AttnFn)k_attn_scores; }
 
 // k_attn_scores_kv applies to head_dim 128 with 2 or 4 query heads per kv head (every listed Qwen3 size up to 8B)
-static int scores_kvm_for(int hd, int n_heads, int n_kv_heads) {
+AttnShape attn_scores_shape(int hd, int n_heads, int n_kv_heads, int S) {
     const int kv_mul = n_heads / n_kv_heads;
-    if (hd != kSgHd || (kv_mul != 2 && kv_mul != 4) || !dev_knob("Q3_ATT_SCORES_KV", 1)) return 0;
-    return kv_mul;
-}
-struct ScoresShape { int kvm; unsigned gx, gy; size_t smem; };
-static ScoresShape scores_shape(int hd, int n_heads, int n_kv_heads, int S) {
-    ScoresShape r;
-    r.kvm = scores_kvm_for(hd, n_heads, n_kv_heads);
+    AttnShape r;
+    r.kvm = (hd != kSgHd || (kv_mul != 2 && kv_mul != 4) || !dev_knob("Q3_ATT_SCORES_KV", 1)) ? 0 : kv_mul;
     const int tch = r.kvm == 4 ? sg_tch<4>() : r.kvm == 2 ? sg_tch<2>() : attn_tch(hd);
-    r.gx = (unsigned)(r.kvm ? n_kv_heads : n_heads);
-    r.gy = (unsigned)((S + tch - 1) / tch);
+    r.fn = attn_scores_fn(r.kvm);
+    r.grid = dim3((unsigned)(r.kvm ? n_kv_heads : n_heads), (unsigned)((S + tch - 1) / tch));
+    r.block = dim3(kWG);
     r.smem = r.kvm == 4 ? attn_scores_kv_smem_bytes<4>() : r.kvm == 2 ? attn_scores_kv_smem_bytes<2>() : attn_scores_smem_bytes(hd);
     return r;
 }
-static int set_attn_scores_smem(const ScoresShape& sh) {
-    if (sh.kvm == 4) return set_max_smem((const void*)k_attn_scores_kv<4>, sh.smem);
-    if (sh.kvm == 2) return set_max_smem((const void*)k_attn_scores_kv<2>, sh.smem);
-    return set_max_smem((const void*)k_attn_scores, sh.smem);
+AttnShape attn_out_shape(int hd, int n_heads, int S, int slice_w) {
+    return AttnShape{attn_out_fn(slice_w, attn_out_p_in_lds(S)), dim3((unsigned)n_heads, (unsigned)(hd / slice_w)), dim3(kAoThreads),
+                     attn_out_smem_bytes(hd, S, slice_w), 0};
 }
-static void launch_attn_scores(const AttnArgs& a, int kvm, unsigned gx, unsigned gy, size_t smem, hipStream_t st) {
-    if (kvm == 4) hipLaunchKernelGGL(k_attn_scores_kv<4>, dim3(gx, gy), dim3(kWG), smem, st, a);
-    else if (kvm == 2) hipLaunchKernelGGL(k_attn_scores_kv<2>, dim3(gx, gy), dim3(kWG), smem, st, a);
-    else hipLaunchKernelGGL(k_attn_scores, dim3(gx, gy), dim3(kWG), smem, st, a);
-}
-
 // Short-context attention (pos < 256): k_attn_short2 (round 5: coalesced key / value staging, product tile, 8 waves) for
 // head_dim 128 on caches of a whole number of 8-row steps; k_attn_short (head_dim 64, odd test contexts) otherwise.
-static bool attn_short2_ok(const AttnArgs& a) { return a.hd == 128 && a.seq_len >= 8 && (a.seq_len % 8) == 0; }
-static int set_attn_short_smem(const AttnArgs& a) {
-    if (!attn_short2_ok(a)) return Q3_OK;
-    return set_max_smem((const void*)k_attn_short2<128>, attn_short2_smem_bytes(128, kS2MaxT));
-}
-static void launch_attn_short(const AttnArgs& a0, unsigned n_heads, hipStream_t st, int row_steps = 0) {
-    AttnArgs a = a0;
-    if (attn_short2_ok(a)) {
-        a.row_steps = row_steps;          // > 0: a position range below 64 -- rows requested at entry, one workgroup per head
-        hipLaunchKernelGGL(k_attn_short2<128>, dim3(n_heads, row_steps > 0 ? 1 : 2), dim3(kS2Threads), attn_short2_smem_bytes(128, kS2MaxT), st, a);
-    }
-    else if (a.hd == 128) hipLaunchKernelGGL(k_attn_short<128>, dim3(n_heads), dim3(kWG), 0, st, a);
-    else hipLaunchKernelGGL(k_attn_short<64>, dim3(n_heads), dim3(kWG), 0, st, a);
+AttnShape attn_short_shape(int hd, int n_heads, int S) {
+    if (hd == 128 && S >= 8 && (S % 8) == 0)
+        return AttnShape{(AttnFn)k_attn_short2<128>, dim3((unsigned)n_heads, 2), dim3(kS2Threads), attn_short2_smem_bytes(128, kS2MaxT), 0};
+    return AttnShape{hd == 128 ? (AttnFn)k_attn_short<128> : (AttnFn)k_attn_short<64>, dim3((unsigned)n_heads), dim3(kWG), 0, 0};
 }
 
-// no_next: the classifier launch without the folded bookkeeping (q3_profile replays launches without advancing the state)
-void launch_one(const Launch& L, q3_engine* e, bool no_next = false, int row_steps = 0) {
-    if (no_next && L.fam == F_LMHEAD && L.ga.next_cell != nullptr) {
-        Launch M = L;
-        M.ga.next_cell = nullptr;
-        hipLaunchKernelGGL(M.fn, dim3(M.grid), dim3(M.block), M.smem, e->stream, M.ga);
-        return;
-    }
-#ifdef Q3_DEV
-    if (L.is_kfold) {
-        const int nl = (int)e->plan.size() - 1;
-        hipLaunchKernelGGL(k_kstamp_reduce, dim3((unsigned)nl), dim3(256), 0, e->stream, e->d_kslots, e->d_knslots, e->d_kcells);
-        hipLaunchKernelGGL(k_kstamp_fold, dim3(1), dim3(256), 0, e->stream, e->d_kcells, nl, e->d_kacc);
-        return;
-    }
-#endif
-    if (L.is_attn) {
-        if (L.attn_kind == 1) launch_attn_scores(L.aa, L.scores_kvm, L.grid, L.grid_y, L.smem, e->stream);
-        else if (L.attn_kind == 2) launch_attn_out(L.aa, L.grid, L.grid_y, L.smem, e->stream);
-        else if (L.attn_kind == 3) launch_attn_short(L.aa, L.grid, e->stream, row_steps);
-        else hipLaunchKernelGGL(k_attn, dim3(L.grid), dim3(kWG), L.smem, e->stream, L.aa);
-    } else if (L.is_next) {
-        hipLaunchKernelGGL(k_next, dim3(1), dim3(kWG), 0, e->stream, e->d_state, e->d_argmax_slots, e->n_argmax_slots,
-                           e->d_out_tokens, e->out_cap, e->d_prompt);
-    } else {
-        hipLaunchKernelGGL(L.fn, dim3(L.grid), dim3(L.block), L.smem, e->stream, L.ga);
-    }
+inline int att_stride_for(size_t S) { return (int)((S + 255) & ~(size_t)255); }                    // floats per score row
+inline int cmax_stride_for(size_t S) { return (int)(((S + 63) / 64 + 63) & ~(size_t)63); }         // 64-block maxima per score row
+
+// Long-context split of one attention launch `a`: A = k_attn_scores[_kv] over (heads | kv heads) x T-chunks, B = k_attn_out over
+// heads x slices.  att: [n_heads][att_stride] score rows; cmax: [n_heads][cmax_stride] their 64-block maxima (k_attn_scores_kv only);
+// att_priv: [n_heads][slices][att_stride].  The engine's long plan and q3_op_attention both build the pair here.
+int make_split_attn(Launch& A, Launch& B, AttnArgs a, float* att, float* cmax, float* att_priv, int n_cu) {
+    const AttnShape ss = attn_scores_shape(a.hd, a.n_heads, a.n_kv_heads, a.seq_len);
+    a.xbq = nullptr;                  // the split kernels write f32 xb only; Wo quantizes in its prologue
+    a.att_global = att;
+    a.att_stride = att_stride_for(a.seq_len);
+    a.att_cmax = (ss.kvm && dev_knob("Q3_ATT_CMAX", 1)) ? cmax : nullptr;
+    a.cmax_stride = cmax_stride_for(a.seq_len);
+    AttnArgs sa = a, oa = a;
+    // developer timeline of the long plan: k_attn_out's (Q3_STAMP_SCORES=1: k_attn_scores')
+    if (dev_knob("Q3_STAMP_SCORES", 0)) oa.stamps = nullptr;
+    else sa.stamps = nullptr;
+    oa.att_priv = att_priv;
+    oa.slice_w = attn_slice_w(a.hd, a.n_heads, n_cu);
+    const AttnShape os = attn_out_shape(a.hd, a.n_heads, a.seq_len, oa.slice_w);
+    int rc;
+    if ((rc = make_launch(A, F_ATTN, ss.fn, ss.grid, ss.block, ss.smem, sa))) return rc;
+    return make_launch(B, F_ATTN, os.fn, os.grid, os.block, os.smem, oa);
 }
 
 // Tile shape + grid for one GEMV launch.  units = output rows (SwiGLU: hidden units, each 2 weight rows).
@@ -431,7 +445,8 @@ GemvShape plan_gemv(int units, int n, int G, bool swiglu, int row_align, int n_c
 
 // grid / block / LDS of a specialised launch: one row batch (hu rows or hidden units) per wave and round; at least one
 // workgroup per CU as long as there are batches for it (fewer batches than waves: see k_gemv's wave numbering)
-void apply_cfg(Launch& Ln, GemvArgs& a, const GemvCfg& c, int units, int n_cu) {
+struct GemvLaunch { GemvFn fn = nullptr; unsigned grid = 1, block = kWG; size_t smem = 0; };
+void apply_cfg(GemvLaunch& Ln, GemvArgs& a, const GemvCfg& c, int units, int n_cu) {
     const int waves = c.wgt / 64;
     const int hu = (c.epi == EPI_SWIGLU) ? c.ru / 2 : c.ru;
     const long nb = ((long)units + hu - 1) / hu;
@@ -453,7 +468,7 @@ void apply_cfg(Launch& Ln, GemvArgs& a, const GemvCfg& c, int units, int n_cu) {
 // table entry when there is one, the generic run-time-n kernel otherwise.  units = output rows (SwiGLU: hidden units);
 // hd = head_dim for EPI_QKV (row batches must not straddle the q|k|v segments), 1 otherwise.  build_plan and the operator
 // entry point q3_op_gemv_role both select through this function.
-int plan_role(Launch& Ln, GemvArgs& a, int pro, int epi, int n, int units, int G, bool fast_fold, int hd, int n_cu) {
+int plan_role(GemvLaunch& Ln, GemvArgs& a, int pro, int epi, int n, int units, int G, bool fast_fold, int hd, int n_cu) {
     const int small_cap = dev_knob("Q3_WG_PER_CU_SMALL", 2);   // two workgroups per CU: half the rows (and fold chains) per wave
     const int big_cap = dev_knob("Q3_WG_PER_CU_LMHEAD", 2);   // all workgroups resident at once (the NORM prologue keeps ~190 VGPRs live)
     const bool norm = pro == PRO_NORM || pro == PRO_EMBED_NORM;
@@ -475,27 +490,14 @@ int plan_role(Launch& Ln, GemvArgs& a, int pro, int epi, int n, int units, int G
         Ln.smem = gemv_smem_bytes(n, G, a.vr, norm);
     }
     if (!Ln.fn) return fail(Q3_ERR_UNSUPPORTED, "no kernel instantiated for this tile shape");
-    return set_max_smem((const void*)Ln.fn, Ln.smem);
+    return Q3_OK;
 }
 
 }  // namespace
 
 void q3_engine::release() {
     batch_free(this);
-    if (graph_exec) (void)hipGraphExecDestroy(graph_exec);
-    if (graph) (void)hipGraphDestroy(graph);
-    if (graph_long_exec) (void)hipGraphExecDestroy(graph_long_exec);
-    if (graph_long) (void)hipGraphDestroy(graph_long);
-    if (graph_fwd_exec) (void)hipGraphExecDestroy(graph_fwd_exec);
-    if (graph_fwd) (void)hipGraphDestroy(graph_fwd);
-    if (graph_fwd_long_exec) (void)hipGraphExecDestroy(graph_fwd_long_exec);
-    for (int i = 0; i < kNRange; ++i) {
-        if (graph_rng_exec[i]) (void)hipGraphExecDestroy(graph_rng_exec[i]);
-        if (graph_rng[i]) (void)hipGraphDestroy(graph_rng[i]);
-        if (graph_fwd_rng_exec[i]) (void)hipGraphExecDestroy(graph_fwd_rng_exec[i]);
-        if (graph_fwd_rng[i]) (void)hipGraphDestroy(graph_fwd_rng[i]);
-    }
-    if (graph_fwd_long) (void)hipGraphDestroy(graph_fwd_long);
+    for (int i = 0; i < 2; ++i) { decode[i].reset(); forward[i].reset(); }
     void* dptrs[] = {d_value_t, d_kacc, d_kslots, d_kcells, d_knslots, d_next_cell, d_xbq, d_xbs, d_samp_hist, d_samp_counts, d_sampler, d_probs, d_sp, d_keys, d_prompt, d_att_priv, d_argmax_slots, d_stamps, d_blob, d_x, d_q, d_kraw, d_xb, d_hb, d_logits, d_tap, d_key, d_value, d_rope, d_att, d_state, d_out_tokens};
     for (void* p : dptrs)
         if (p) (void)hipFree(p);
@@ -675,11 +677,10 @@ int q3_engine::build_plan() {
     const bool fast_fold = !strict && dev_knob("Q3_FAST_FOLD", 1) != 0;   // tolerance mode: tree fold of the GEMV group terms too
     const int att_lds_max = dev_knob("Q3_ATT_LDS_MAX", 4096);
 
-    att_stride = (S + 255) & ~255;
+    const int att_stride = att_stride_for(S), cmax_stride = cmax_stride_for(S);
     const int slice_w = attn_slice_w(hd, cfg.n_heads, n_cu);
     const int nsl = hd / slice_w;
     const bool use_att_global = S > att_lds_max;
-    cmax_stride = (int)((((size_t)S + 63) / 64 + 63) & ~(size_t)63);
     HIP_TRY(hipMalloc((void**)&d_att, 4 * (size_t)cfg.n_heads * ((size_t)att_stride + cmax_stride)));   // score rows, then their 64-block maxima
     HIP_TRY(hipMalloc((void**)&d_att_priv, 4 * (size_t)cfg.n_heads * nsl * att_stride));
     kstamps = dev_knob("Q3_KSTAMPS", 0) != 0;
@@ -711,15 +712,28 @@ int q3_engine::build_plan() {
         return a;
     };
     int rc;
-    const GemvCfg* wo_preq = nullptr;
-    std::vector<Launch> wo_long;       // the long-context plan's Wo launches (k_attn_out emits no quantized operand)
+    // developer timelines: the cells of the launch about to be appended to `plan` (tools/kstamps.py and the *_stamps.py tools index by it)
+    auto stamp_cells = [&]() -> unsigned long long* {
+        if (!d_stamps) return nullptr;
+        return kstamps ? d_kslots + 2 * (size_t)kKstampSlots * plan.size() : d_stamps + 16 * plan.size();
+    };
+    auto stamp = [&](GemvArgs& a) {
+        if (d_stamps) { a.stamps = stamp_cells(); a.stamp_block = dev_knob("Q3_STAMP_BLOCK", 7); }
+    };
+    // one fused GEMV role: resolve kernel and shape (plan_role), stamp, record
+    auto gemv = [&](Launch& Ln, Family fam, GemvArgs a, int pro, int epi, int n, int units, int qkv_hd, bool stamped) -> int {
+        GemvLaunch g;
+        if ((rc = plan_role(g, a, pro, epi, n, units, G, fast_fold, qkv_hd, n_cu))) return rc;
+        if (stamped) stamp(a);
+        return make_launch(Ln, fam, g.fn, dim3(g.grid), dim3(g.block), g.smem, a);
+    };
+    auto push_both = [&](const Launch& Ln) { plan.push_back(Ln); plan_long.push_back(Ln); };
     HIP_TRY(hipMalloc((void**)&d_xbq, (size_t)ahd));
     HIP_TRY(hipMalloc((void**)&d_xbs, 4 * (size_t)(ahd / G)));
+    Launch Ln;
     for (int l = 0; l < L; ++l) {
         const size_t kv_off = (size_t)l * S * kvd;
         {   // xb = RMSNorm_att(x); xq = quantize(xb); q,k,v = W{q,k,v} xq         qwen3.rs:134-136, layers.rs:334-337
-            Launch Ln;
-            Ln.fam = F_QKV;
             GemvArgs a = base_args(dim);
             a.seg[0] = Seg{wq[l].q, wq[l].s, d_q, ahd, 0};
             a.seg[1] = Seg{wk[l].q, wk[l].s, d_kraw, kvd, 0};
@@ -738,15 +752,14 @@ int q3_engine::build_plan() {
                 a.emb_s = tok.s;
                 a.x_out = d_x;
             }
-            if ((rc = plan_role(Ln, a, l == 0 ? PRO_EMBED_NORM : PRO_NORM, EPI_QKV, dim, a.total_rows, G, fast_fold, hd, n_cu))) return rc;
-            Ln.ga = a;
-            if (d_stamps) { Ln.ga.stamps = kstamps ? d_kslots + 2 * (size_t)kKstampSlots * plan.size() : d_stamps + 16 * plan.size(); Ln.ga.stamp_block = dev_knob("Q3_STAMP_BLOCK", 7); }
-            plan.push_back(Ln);
+            if ((rc = gemv(Ln, F_QKV, a, l == 0 ? PRO_EMBED_NORM : PRO_NORM, EPI_QKV, dim, a.total_rows, hd, true))) return rc;
+            push_both(Ln);
         }
+        // the short plan only ever runs at pos < split_pos
+        const bool att_short = (hd == 64 || hd == 128) && split_pos <= kShortMaxT && dev_knob("Q3_ATT_SHORT", 1);
+        // k_attn_short can hand Wo its operand quantized (qwen3.rs:152 fused into the attention epilogue)
+        const GemvCfg* wo_preq = att_short ? find_cfg(PRO_PREQR, EPI_RESID, ahd, G, fast_fold) : nullptr;
         {   // QK-norm + RoPE + attention                                        layers.rs:346-419
-            Launch Ln;
-            Ln.fam = F_ATTN;
-            Ln.is_attn = true;
             AttnArgs a{};
             a.q = d_q;
             a.key_cache = d_key + kv_off;
@@ -766,246 +779,142 @@ int q3_engine::build_plan() {
             a.strict = strict;
             a.write_q = 0;
             a.debug = kstamps ? 64 : 0;
-            a.stamps = d_stamps ? (kstamps ? d_kslots + 2 * (size_t)kKstampSlots * plan.size() : d_stamps + 16 * plan.size()) : nullptr;
-            Ln.aa = a;
-            Ln.grid = (unsigned)cfg.n_heads;
-            Ln.smem = attn_smem_bytes(hd, use_att_global ? 0 : S);
-            if ((rc = set_max_smem((const void*)k_attn, Ln.smem))) return rc;
-            // the short plan only ever runs at pos < split_pos
-            if ((hd == 64 || hd == 128) && split_pos <= kShortMaxT && dev_knob("Q3_ATT_SHORT", 1)) {
-                Ln.attn_kind = 3;
-                if ((rc = set_attn_short_smem(Ln.aa))) return rc;
-            }
-            // k_attn_short can hand Wo its operand quantized (qwen3.rs:152 fused into the attention epilogue)
-            wo_preq = Ln.attn_kind == 3 ? find_cfg(PRO_PREQR, EPI_RESID, ahd, G, fast_fold) : nullptr;
+            a.stamps = stamp_cells();
             if (wo_preq) {
-                Ln.aa.xbq = d_xbq;
-                Ln.aa.xbs = d_xbs;
-                Ln.aa.xb_group = G;
+                a.xbq = d_xbq;
+                a.xbs = d_xbs;
+                a.xb_group = G;
             }
+            // long-context plan: the attention launch becomes k_attn_scores (heads x T-chunks) + k_attn_out (heads x slices)
+            Launch A, B;
+            if ((rc = make_split_attn(A, B, a, d_att, d_att + (size_t)cfg.n_heads * att_stride, d_att_priv, n_cu))) return rc;
+            plan_long.push_back(A);
+            plan_long.push_back(B);
+            if (att_short) {
+                const AttnShape sh = attn_short_shape(hd, cfg.n_heads, S);
+                rc = make_launch(Ln, F_ATTN, sh.fn, sh.grid, sh.block, sh.smem, a);
+            } else {
+                rc = make_launch(Ln, F_ATTN, k_attn, dim3((unsigned)cfg.n_heads), dim3(kWG), attn_smem_bytes(hd, use_att_global ? 0 : S), a);
+            }
+            if (rc) return rc;
             plan.push_back(Ln);
         }
         {   // xq = quantize(xb); x += Wo xq                                      qwen3.rs:152-156
-            Launch Ln;
-            Ln.fam = F_WO;
             GemvArgs a = base_args(ahd);
             a.seg[0] = Seg{wo[l].q, wo[l].s, d_x, dim, 0};
             a.total_rows = dim;
             a.in = d_xb;
             a.pre_q = d_xbq;
             a.pre_s = d_xbs;
-            // quantize-in-prologue form: the long-context plan always, the short plan when attention emits no int8
-            Launch Lq = Ln;
-            GemvArgs aq = a;
-            if ((rc = plan_role(Lq, aq, PRO_QUANT, EPI_RESID, ahd, dim, G, fast_fold, 1, n_cu))) return rc;
-            Lq.ga = aq;
-            wo_long.push_back(Lq);
-            if (wo_preq) {
-                if ((rc = plan_role(Ln, a, PRO_PREQR, EPI_RESID, ahd, dim, G, fast_fold, 1, n_cu))) return rc;
-                Ln.ga = a;
-            } else {
-                Ln = Lq;
-            }
-            if (d_stamps) { Ln.ga.stamps = kstamps ? d_kslots + 2 * (size_t)kKstampSlots * plan.size() : d_stamps + 16 * plan.size(); Ln.ga.stamp_block = dev_knob("Q3_STAMP_BLOCK", 7); }
+            // quantize-in-prologue form: the long-context plan always (k_attn_out emits no quantized operand; no timeline), the short
+            // plan when attention emits no int8
+            if ((rc = gemv(Ln, F_WO, a, PRO_QUANT, EPI_RESID, ahd, dim, 1, false))) return rc;
+            plan_long.push_back(Ln);
+            if ((rc = gemv(Ln, F_WO, a, wo_preq ? PRO_PREQR : PRO_QUANT, EPI_RESID, ahd, dim, 1, true))) return rc;
             plan.push_back(Ln);
         }
         {   // xb = RMSNorm_ffn(x); xq = quantize(xb); hb = silu(W1 xq) * (W3 xq)   qwen3.rs:159-161, layers.rs:468-475
-            Launch Ln;
-            Ln.fam = F_W13;
             GemvArgs a = base_args(dim);
             a.seg[0] = Seg{w1[l].q, w1[l].s, d_hb, H, 0};
             a.seg[1] = Seg{w3[l].q, w3[l].s, nullptr, H, 0};
             a.total_rows = 2 * H;
             a.norm_w = rms_ffn + (size_t)l * dim;
             a.in = d_x;
-            if ((rc = plan_role(Ln, a, PRO_NORM, EPI_SWIGLU, dim, H, G, fast_fold, 1, n_cu))) return rc;
-            Ln.ga = a;
-            if (d_stamps) { Ln.ga.stamps = kstamps ? d_kslots + 2 * (size_t)kKstampSlots * plan.size() : d_stamps + 16 * plan.size(); Ln.ga.stamp_block = dev_knob("Q3_STAMP_BLOCK", 7); }
-            plan.push_back(Ln);
+            if ((rc = gemv(Ln, F_W13, a, PRO_NORM, EPI_SWIGLU, dim, H, 1, true))) return rc;
+            push_both(Ln);
         }
         {   // hq = quantize(hb); x += W2 hq                                      layers.rs:478-479, qwen3.rs:175
-            Launch Ln;
-            Ln.fam = F_W2;
             GemvArgs a = base_args(H);
             a.seg[0] = Seg{w2[l].q, w2[l].s, d_x, dim, 0};
             a.total_rows = dim;
             a.in = d_hb;
-            if ((rc = plan_role(Ln, a, PRO_QUANT, EPI_RESID, H, dim, G, fast_fold, 1, n_cu))) return rc;
-            Ln.ga = a;
-            if (d_stamps) { Ln.ga.stamps = kstamps ? d_kslots + 2 * (size_t)kKstampSlots * plan.size() : d_stamps + 16 * plan.size(); Ln.ga.stamp_block = dev_knob("Q3_STAMP_BLOCK", 7); }
-            plan.push_back(Ln);
+            if ((rc = gemv(Ln, F_W2, a, PRO_QUANT, EPI_RESID, H, dim, 1, true))) return rc;
+            push_both(Ln);
         }
     }
-    {   // x = RMSNorm_final(x); xq = quantize(x); logits = Wcls xq (+ argmax)      qwen3.rs:72-76
-        Launch Ln;
-        Ln.fam = F_LMHEAD;
+    {   // x = RMSNorm_final(x); xq = quantize(x); logits = Wcls xq + argmax, state update and token store (qwen3.rs:72-76, generation.rs)
         GemvArgs a = base_args(dim);
         a.seg[0] = Seg{wcls.q, wcls.s, d_logits, V, 0};
         a.total_rows = V;
         a.norm_w = rms_final;
         a.in = d_x;
         a.tap_out = d_tap;
-        if ((rc = plan_role(Ln, a, PRO_NORM, EPI_LOGITS, dim, V, G, fast_fold, 1, n_cu))) return rc;
-        n_argmax_slots = (int)Ln.grid;
+        GemvLaunch g;
+        if ((rc = plan_role(g, a, PRO_NORM, EPI_LOGITS, dim, V, G, fast_fold, 1, n_cu))) return rc;
+        n_argmax_slots = (int)g.grid;
         HIP_TRY(hipMalloc((void**)&d_argmax_slots, 8 * (size_t)n_argmax_slots));
         HIP_TRY(hipMemset(d_argmax_slots, 0, 8 * (size_t)n_argmax_slots));
         a.argmax_slots = d_argmax_slots;
-        const bool fuse_next = dev_knob("Q3_FUSE_NEXT", 1) != 0;
-        if (fuse_next) {
-            HIP_TRY(hipMalloc((void**)&d_next_cell, 16));
-            HIP_TRY(hipMemset(d_next_cell, 0, 16));
-            a.next_cell = d_next_cell;
-            a.out_tokens = d_out_tokens;
-            a.out_cap = out_cap;
-            a.prompt = d_prompt;
-        }
-        Ln.ga = a;
-        if (d_stamps) { Ln.ga.stamps = kstamps ? d_kslots + 2 * (size_t)kKstampSlots * plan.size() : d_stamps + 16 * plan.size(); Ln.ga.stamp_block = dev_knob("Q3_STAMP_BLOCK", 7); }
-        plan.push_back(Ln);
+        stamp(a);
+        HIP_TRY(hipMalloc((void**)&d_next_cell, 16));
+        HIP_TRY(hipMemset(d_next_cell, 0, 16));
+        a.next_cell = d_next_cell;
+        a.out_tokens = d_out_tokens;
+        a.out_cap = out_cap;
+        a.prompt = d_prompt;
+        if ((rc = make_launch(Ln, F_LMHEAD, g.fn, dim3(g.grid), dim3(g.block), g.smem, a))) return rc;
+        push_both(Ln);
+        a.next_cell = nullptr;
+        if ((rc = make_launch(lm_plain, F_LMHEAD, g.fn, dim3(g.grid), dim3(g.block), g.smem, a))) return rc;
     }
-    if (d_next_cell == nullptr) {
-        Launch Ln;
-        Ln.fam = F_NEXT;
-        Ln.is_next = true;
-        plan.push_back(Ln);
-    }
-    if (kstamps) {          // (developer build only: kstamps is false in the product)
+    n_token_launches = plan.size();
+#ifdef Q3_DEV
+    if (kstamps) {
+        // per launch: live wave slots; behind the token's last launch: k_kstamp_reduce + k_kstamp_fold
+        const int nl = (int)n_token_launches;
         std::vector<int> ns(plan.size(), 0);
         for (size_t i = 0; i < plan.size(); ++i) {
-            const bool s2 = plan[i].is_attn && plan[i].attn_kind == 3 && attn_short2_ok(plan[i].aa);
-            const long w = (long)plan[i].grid * (s2 ? 2 : 1) * ((plan[i].is_attn ? (s2 ? kS2Threads : kWG) : (long)plan[i].block) / 64);
+            const long w = (long)plan[i].grid.x * plan[i].grid.y * (plan[i].block.x / 64);
             ns[i] = (int)(w < kKstampSlots ? w : kKstampSlots);
         }
         HIP_TRY(hipMemcpy(d_knslots, ns.data(), 4 * ns.size(), hipMemcpyHostToDevice));
-        Launch Ln;
-        Ln.fam = F_NEXT;
-        Ln.is_kfold = true;
-        plan.push_back(Ln);
+        if ((rc = make_launch(Ln, F_NEXT, k_kstamp_reduce, dim3((unsigned)nl), dim3(256), 0, d_kslots, d_knslots, d_kcells))) return rc;
+        push_both(Ln);
+        if ((rc = make_launch(Ln, F_NEXT, k_kstamp_fold, dim3(1), dim3(256), 0, d_kcells, nl, d_kacc))) return rc;
+        push_both(Ln);
     }
-    // long-context plan: every attention launch becomes k_attn_scores (heads x T-chunks) + k_attn_out (heads x slices)
-    size_t wo_i = 0;
-    for (const Launch& L0 : plan) {
-        if (L0.fam == F_WO) { plan_long.push_back(wo_long[wo_i++]); continue; }
-        if (!L0.is_attn) { plan_long.push_back(L0); continue; }
-        Launch A = L0, B = L0;
-        A.aa.xbq = B.aa.xbq = nullptr;    // the split kernels write f32 xb only; Wo quantizes in its prologue
-        A.attn_kind = 1;
-        A.aa.stamps = nullptr;            // developer timeline of the long plan: k_attn_out's (Q3_STAMP_SCORES=1: k_attn_scores')
-        if (dev_knob("Q3_STAMP_SCORES", 0)) { A.aa.stamps = L0.aa.stamps; B.aa.stamps = nullptr; }
-        A.aa.att_global = d_att;
-        A.aa.att_stride = att_stride;
-        A.aa.q_out = nullptr;
-        const ScoresShape ss = scores_shape(hd, A.aa.n_heads, A.aa.n_kv_heads, S);
-        A.scores_kvm = ss.kvm;
-        A.aa.att_cmax = B.aa.att_cmax = (ss.kvm && dev_knob("Q3_ATT_CMAX", 1)) ? d_att + (size_t)A.aa.n_heads * att_stride : nullptr;
-        A.aa.cmax_stride = B.aa.cmax_stride = cmax_stride;
-        A.grid = ss.gx;
-        A.grid_y = ss.gy;
-        A.smem = ss.smem;
-        B.attn_kind = 2;
-        B.aa.att_global = d_att;
-        B.aa.att_priv = d_att_priv;
-        B.aa.att_stride = att_stride;
-        B.grid_y = (unsigned)nsl;
-        B.aa.slice_w = slice_w;
-        B.smem = attn_out_smem_bytes(hd, S, slice_w);
-        if ((rc = set_attn_scores_smem(ss))) return rc;
-        if ((rc = set_attn_out_smem(B.smem))) return rc;
-        plan_long.push_back(A);
-        plan_long.push_back(B);
-    }
+#endif
     return Q3_OK;
 }
 
 int q3_engine::capture() {
-    HIP_TRY(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
-    for (const Launch& L : plan) launch_one(L, this);
-    HIP_TRY(hipStreamEndCapture(stream, &graph));
-    HIP_TRY(hipGraphInstantiate(&graph_exec, graph, nullptr, nullptr, 0));
-    HIP_TRY(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
-    for (const Launch& L : plan_long) launch_one(L, this);
-    HIP_TRY(hipStreamEndCapture(stream, &graph_long));
-    HIP_TRY(hipGraphInstantiate(&graph_long_exec, graph_long, nullptr, nullptr, 0));
-    // position ranges: only where the short plan runs k_attn_short2 (head_dim 128, cache a whole number of 8-row steps)
-    for (const Launch& L : plan)
-        if (L.is_attn && L.attn_kind == 3 && attn_short2_ok(L.aa)) ranges = dev_knob("Q3_ATT_RANGES", 0) != 0 && dev_knob("Q3_FWD_LOGITS_HOST", 0) == 0;
-    if (ranges)
-        for (int i = 0; i < kNRange; ++i) {
-            HIP_TRY(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
-            for (const Launch& L : plan) launch_one(L, this, false, kRangeSteps[i]);
-            HIP_TRY(hipStreamEndCapture(stream, &graph_rng[i]));
-            HIP_TRY(hipGraphInstantiate(&graph_rng_exec[i], graph_rng[i], nullptr, nullptr, 0));
-        }
-    if (dev_knob("Q3_FWD_GRAPH", 1)) {
-        const size_t lbytes = 4 * (size_t)cfg.vocab_size;
-        if (ranges)
-            for (int i = 0; i < kNRange; ++i) {
-                HIP_TRY(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
+    const size_t lbytes = 4 * (size_t)cfg.vocab_size;
+    const bool fwd = dev_knob("Q3_FWD_GRAPH", 1) != 0;
+    for (int lng = 0; lng < 2; ++lng) {
+        const std::vector<Launch>& P = lng ? plan_long : plan;
+        int rc = decode[lng].capture(stream, [&] {
+            for (const Launch& L : P) launch(L, stream);
+            return Q3_OK;
+        });
+        if (rc == Q3_OK && fwd)
+            rc = forward[lng].capture(stream, [&]() -> int {
                 HIP_TRY(hipMemcpyAsync(d_state, h_state, sizeof(State), hipMemcpyHostToDevice, stream));
-                for (const Launch& L : plan) launch_one(L, this, false, kRangeSteps[i]);
+                for (const Launch& L : P) launch(L, stream);
                 HIP_TRY(hipMemcpyAsync(h_logits, d_logits, lbytes, hipMemcpyDeviceToHost, stream));
-                HIP_TRY(hipStreamEndCapture(stream, &graph_fwd_rng[i]));
-                HIP_TRY(hipGraphInstantiate(&graph_fwd_rng_exec[i], graph_fwd_rng[i], nullptr, nullptr, 0));
-            }
-        for (int lng = 0; lng < 2; ++lng) {
-            HIP_TRY(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
-            HIP_TRY(hipMemcpyAsync(d_state, h_state, sizeof(State), hipMemcpyHostToDevice, stream));
-            // (developer build, forward-only experiment: d_logits is NOT filled, so device-side sampling after q3_forward is undefined)
-            // Q3_FWD_LOGITS_HOST=1: the classifier stores its logits straight into the pinned host buffer (device-visible,
-            // fine-grained) and the download node disappears (SURVEY section 7 "Logits egress"; measured in docs/HISTORY.md section 7)
-            const bool host_out = dev_knob("Q3_FWD_LOGITS_HOST", 0) != 0;
-            for (const Launch& L : (lng ? plan_long : plan)) {
-                if (host_out && L.fam == F_LMHEAD && !L.is_attn && !L.is_next) {
-                    Launch M = L;
-                    M.ga.seg[0].out = h_logits;
-                    launch_one(M, this);
-                } else launch_one(L, this);
-            }
-            if (!host_out) HIP_TRY(hipMemcpyAsync(h_logits, d_logits, lbytes, hipMemcpyDeviceToHost, stream));
-            HIP_TRY(hipStreamEndCapture(stream, lng ? &graph_fwd_long : &graph_fwd));
-            HIP_TRY(hipGraphInstantiate(lng ? &graph_fwd_long_exec : &graph_fwd_exec, lng ? graph_fwd_long : graph_fwd, nullptr, nullptr, 0));
-        }
+                return Q3_OK;
+            });
+        if (rc) return rc;
     }
     return Q3_OK;
 }
 
 // draw = false: logits only (q3_forward: the caller samples, the device sampler must not consume a coin)
-int q3_engine::enqueue_forward(bool eager, size_t pos, bool draw) {
-    const bool lng = (int64_t)pos >= (int64_t)split_pos;
-    const int rng = lng ? -1 : range_of(pos);
-    if (graph_exec && !eager) {
-        HIP_TRY(hipGraphLaunch(lng ? graph_long_exec : (rng >= 0 ? graph_rng_exec[rng] : graph_exec), stream));
+int q3_engine::enqueue_forward(size_t pos, bool draw) {
+    const int lng = (int64_t)pos >= (int64_t)split_pos ? 1 : 0;
+    if (decode[lng]) {
+        int rc = decode[lng].launch(stream);
+        if (rc) return rc;
     } else {
-        // (eager launches: the same row-request hint the captured range graphs carry -- only when the engine keeps range graphs
-        // (developer build, Q3_ATT_RANGES=1): an eager launch is the SAME launch as the captured one, grid (heads, 2) included, so
-        // that eager rocprofv3 traces time the kernel shape the graph replays)
-        int steps = 0;
-        if (!lng && ranges)
-            for (int i = kNRange - 1; i >= 0; --i)
-                if (pos < (size_t)(8 * kRangeSteps[i])) steps = kRangeSteps[i];
-        for (const Launch& L : (lng ? plan_long : plan)) launch_one(L, this, false, steps);
+        for (const Launch& L : (lng ? plan_long : plan)) launch(L, stream);
         HIP_TRY(hipGetLastError());
     }
     return draw ? enqueue_sample() : Q3_OK;
 }
 
-// Sampler::sample on the logits of the forward just enqueued (after k_next has advanced the state)
+// Sampler::sample on the logits of the forward just enqueued (after the classifier launch has advanced the state)
 int q3_engine::enqueue_sample() {
     if (!sampling) return Q3_OK;
-    if (sargs.pre_exp) hipLaunchKernelGGL(k_sample_exp, dim3((unsigned)n_cu, 1), dim3(256), 0, stream, sargs);
-    if (sargs.phase == 1) {
-        // pipelined draw: the single-workgroup kernel keeps the order-sensitive parts (exact sum; sort + exact walks), the
-        // element-wise passes over the vocabulary in between run on the whole chip
-        SampleArgs tail = sargs;
-        tail.phase = 2;
-        hipLaunchKernelGGL(k_sample, dim3(1), dim3(kSampThreads), 4 * kSegFloats, stream, sargs);
-        hipLaunchKernelGGL(k_sample_norm_hist, dim3(kSampGrid), dim3(256), 0, stream, sargs);
-        hipLaunchKernelGGL(k_sample_count, dim3(kSampGrid), dim3(256), 0, stream, sargs);
-        hipLaunchKernelGGL(k_sample_scatter, dim3(kSampGrid), dim3(256), 0, stream, sargs);
-        hipLaunchKernelGGL(k_sample, dim3(1), dim3(kSampThreads), 4 * kSegFloats, stream, tail);
-    } else {
-        hipLaunchKernelGGL(k_sample, dim3(1), dim3(kSampThreads), 4 * kSegFloats, stream, sargs);
-    }
+    for (const Launch& L : sample_plan) launch(L, stream);
     HIP_TRY(hipGetLastError());
     return Q3_OK;
 }
@@ -1084,7 +993,8 @@ const float* q3_forward(q3_engine* e, size_t token, size_t pos) {
     struct timespec t0, t1, t2, t3, t4;
     if (dbg) clock_gettime(CLOCK_MONOTONIC, &t0);
     if (hipSetDevice(e->device) != hipSuccess) { fail(Q3_ERR_HIP, "hipSetDevice failed"); return nullptr; }
-    if (e->graph_fwd_exec && !e->sampling) {
+    const int lng = (int64_t)pos >= (int64_t)e->split_pos ? 1 : 0;
+    if (e->forward[lng] && !e->sampling) {
         // one graph launch: state upload, kernels, logits download (the three separate enqueues cost ~25 us of host time)
         if (token >= (size_t)e->cfg.vocab_size || pos >= (size_t)e->cfg.seq_len) {
             fail(Q3_ERR_ARG, "index out of range: token %zu (vocab_size %d), pos %zu (seq_len %d)", token, e->cfg.vocab_size, pos, e->cfg.seq_len);
@@ -1095,8 +1005,7 @@ const float* q3_forward(q3_engine* e, size_t token, size_t pos) {
         e->h_state->step = 0;
         e->h_state->prompt_len = 0;
         e->h_state->argmax = 0ull;
-        const int rng = (int64_t)pos >= (int64_t)e->split_pos ? -1 : e->range_of(pos);
-        hipError_t ge = hipGraphLaunch((int64_t)pos >= (int64_t)e->split_pos ? e->graph_fwd_long_exec : (rng >= 0 && e->graph_fwd_rng_exec[rng] ? e->graph_fwd_rng_exec[rng] : e->graph_fwd_exec), e->stream);
+        hipError_t ge = hipGraphLaunch(e->forward[lng].exec, e->stream);
         if (ge == hipSuccess) ge = hipStreamSynchronize(e->stream);
         if (ge != hipSuccess) {
             fail(Q3_ERR_HIP, "forward failed: %s", hipGetErrorString(ge));
@@ -1106,7 +1015,7 @@ const float* q3_forward(q3_engine* e, size_t token, size_t pos) {
     }
     if (e->set_state(token, pos) != Q3_OK) return nullptr;
     if (dbg) clock_gettime(CLOCK_MONOTONIC, &t1);
-    if (e->enqueue_forward(false, pos, false) != Q3_OK) return nullptr;
+    if (e->enqueue_forward(pos, false) != Q3_OK) return nullptr;
     if (dbg) clock_gettime(CLOCK_MONOTONIC, &t2);
     hipError_t err = hipMemcpyAsync(e->h_logits, e->d_logits, 4 * (size_t)e->cfg.vocab_size, hipMemcpyDeviceToHost, e->stream);
     if (dbg) clock_gettime(CLOCK_MONOTONIC, &t3);
@@ -1132,7 +1041,7 @@ int q3_forward_argmax(q3_engine* e, size_t token, size_t pos, int32_t* next_toke
     HIP_TRY(hipSetDevice(e->device));
     int rc = e->set_state(token, pos);
     if (rc) return rc;
-    if ((rc = e->enqueue_forward(false, pos))) return rc;
+    if ((rc = e->enqueue_forward(pos))) return rc;
     HIP_TRY(hipMemcpyAsync(e->h_tokens, e->d_out_tokens, 4, hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     *next_token = e->h_tokens[0];
@@ -1151,7 +1060,7 @@ int q3_generate_greedy(q3_engine* e, size_t first_token, size_t first_pos, size_
     struct timespec t0, t1, t2;
     clock_gettime(CLOCK_MONOTONIC, &t0);
     for (size_t k = 0; k < n_tokens; ++k)
-        if ((rc = e->enqueue_forward(false, first_pos + k))) return rc;
+        if ((rc = e->enqueue_forward(first_pos + k))) return rc;
     clock_gettime(CLOCK_MONOTONIC, &t1);
     HIP_TRY(hipMemcpyAsync(e->h_tokens, e->d_out_tokens, 4 * n_tokens, hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
@@ -1162,7 +1071,7 @@ int q3_generate_greedy(q3_engine* e, size_t first_token, size_t first_pos, size_
         HIP_TRY(hipMemcpy(h.data(), e->d_stamps, 8 * 16 * nl, hipMemcpyDeviceToHost));
         double acc[F_COUNT][16] = {}; int cnt[F_COUNT] = {};
         for (size_t i = 0; i < nl; ++i) {
-            if (e->plan[i].is_next || h[16 * i] == 0) continue;
+            if (e->plan[i].fam == F_NEXT || h[16 * i] == 0) continue;
             for (int k = 1; k < 16; ++k)
                 if (h[16 * i + k] >= h[16 * i]) acc[e->plan[i].fam][k] += (double)(h[16 * i + k] - h[16 * i]);
             cnt[e->plan[i].fam]++;
@@ -1188,7 +1097,7 @@ int q3_generate_greedy(q3_engine* e, size_t first_token, size_t first_pos, size_
         // per family: average duration of a launch (first wave in .. last wave out) and average gap to its predecessor's end,
         // both from the in-kernel 100 MHz clock, averaged over every token folded so far; the sum over a token against the
         // host's wall clock for this call
-        const size_t nl = e->plan.size() - 1;
+        const size_t nl = e->n_token_launches;
         std::vector<unsigned long long> h(2 + 2 * nl);
         HIP_TRY(hipMemcpy(h.data(), e->d_kacc, 8 * h.size(), hipMemcpyDeviceToHost));
         const double ntok = (double)h[0];
@@ -1238,7 +1147,7 @@ int q3_prefill(q3_engine* e, const int32_t* tokens, size_t n_tokens, size_t firs
     e->h_state->prompt_len = (int)n_tokens;
     HIP_TRY(hipMemcpyAsync(e->d_state, e->h_state, sizeof(State), hipMemcpyHostToDevice, e->stream));
     for (size_t k = 0; k < n_tokens; ++k)
-        if ((rc = e->enqueue_forward(false, first_pos + k))) return rc;
+        if ((rc = e->enqueue_forward(first_pos + k))) return rc;
     HIP_TRY(hipMemcpyAsync(e->h_tokens, e->d_out_tokens + (n_tokens - 1), 4, hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     if (next_token) *next_token = e->h_tokens[0];
@@ -1267,8 +1176,6 @@ int q3_sampler_set(q3_engine* e, float temperature, float topp, uint64_t rng_see
     }
     SamplerState h{};
     h.rng = rng_seed; h.temperature = temperature; h.topp = topp;
-    int rc = set_max_smem((const void*)k_sample, 4 * kSegFloats);
-    if (rc) return rc;
     HIP_TRY(hipMemcpy(e->d_sampler, &h, sizeof(h), hipMemcpyHostToDevice));
     SampleArgs a{};
     a.logits = e->d_logits;
@@ -1287,7 +1194,25 @@ int q3_sampler_set(q3_engine* e, float temperature, float topp, uint64_t rng_see
     a.hist = e->d_samp_hist;
     a.counts = e->d_samp_counts;
     a.stamps = e->d_stamps ? e->d_stamps + 16 * (size_t)(5 * e->cfg.n_layers + 3) : nullptr;
-    e->sargs = a;
+    // the draw behind every forward.  Pipelined (phase 1): the single-workgroup kernel keeps the order-sensitive parts (exact sum;
+    // sort + exact walks), the element-wise passes over the vocabulary in between run on the whole chip
+    e->sample_plan.clear();
+    int rc = Q3_OK;
+    auto add = [&](void (*k)(const SampleArgs), dim3 grid, dim3 block, size_t smem, const SampleArgs& sa) {
+        Launch L;
+        if (rc == Q3_OK && (rc = make_launch(L, F_NEXT, k, grid, block, smem, sa)) == Q3_OK) e->sample_plan.push_back(L);
+    };
+    if (a.pre_exp) add(k_sample_exp, dim3((unsigned)e->n_cu, 1), dim3(256), 0, a);
+    add(k_sample, dim3(1), dim3(kSampThreads), 4 * kSegFloats, a);
+    if (a.phase == 1) {
+        SampleArgs tail = a;
+        tail.phase = 2;
+        add(k_sample_norm_hist, dim3(kSampGrid), dim3(256), 0, a);
+        add(k_sample_count, dim3(kSampGrid), dim3(256), 0, a);
+        add(k_sample_scatter, dim3(kSampGrid), dim3(256), 0, a);
+        add(k_sample, dim3(1), dim3(kSampThreads), 4 * kSegFloats, tail);
+    }
+    if (rc) return rc;
     e->sampling = temperature != 0.0f;                       // sampler.rs:119-120: temperature 0 is the argmax path
     return Q3_OK;
 }
@@ -1318,7 +1243,7 @@ int q3_reset_kv(q3_engine* e) {
     if (e->d_value_t) HIP_TRY(hipMemsetAsync(e->d_value_t, 0, bytes, e->stream));
     // the classifier's {argmax cell, ticket} pair is self-clearing per token; a reset also recovers it after a launch that
     // did not run to completion
-    if (e->d_next_cell) HIP_TRY(hipMemsetAsync(e->d_next_cell, 0, 16, e->stream));
+    HIP_TRY(hipMemsetAsync(e->d_next_cell, 0, 16, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     return Q3_OK;
 }
@@ -1363,11 +1288,12 @@ int q3_profile(q3_engine* e, size_t token, size_t pos, int reps, float* ms, int3
         // one full forward first so every family runs on live data, then each family's launches back to back
         // between ONE pair of events: the average is the launch period (kernel + boundary), the same quantity
         // rocprofv3's per-dispatch durations sum to on a serialised stream.
-        for (size_t i = 0; i < nl; ++i) if (!P[i].is_next) launch_one(P[i], e, true);
+        auto replay = [&](const Launch& L) { launch(L.fam == F_LMHEAD ? e->lm_plain : L, e->stream); };
+        for (size_t i = 0; i < nl; ++i) replay(P[i]);
         for (int f = 0; f < F_COUNT; ++f) {
             HIP_TRY(hipEventRecord(ev[2 * f], e->stream));
             for (size_t i = 0; i < nl; ++i)
-                if (P[i].fam == f) { launch_one(P[i], e, true); launches[f] += 1; }
+                if (P[i].fam == f) { replay(P[i]); launches[f] += 1; }
             HIP_TRY(hipEventRecord(ev[2 * f + 1], e->stream));
         }
         HIP_TRY(hipStreamSynchronize(e->stream));
@@ -1583,9 +1509,7 @@ int q3_op_matmul(float* xout, const int8_t* xq, const float* xs, const int8_t* w
     const size_t smem = gemv_smem_bytes((int)n, (int)group_size, a.vr, false);
     GemvFn fn = pick<PRO_PREQ, EPI_STORE>((int)group_size, gs.RU, gs.JU, gs.FIN, gs.PF);
     if (!fn) return fail(Q3_ERR_UNSUPPORTED, "no kernel for tile %dx%d", gs.RU, gs.JU);
-    if ((rc = set_max_smem((const void*)fn, smem))) return rc;
-    hipLaunchKernelGGL(fn, dim3(grid), dim3(kWG), smem, 0, a);
-    if ((rc = op_end())) return rc;
+    if ((rc = launch_now(0, fn, dim3(grid), dim3(kWG), smem, a)) || (rc = op_end())) return rc;
     HIP_TRY(hipMemcpy(xout, dout.p, 4 * d, hipMemcpyDeviceToHost));
     return Q3_OK;
 }
@@ -1638,7 +1562,7 @@ int q3_op_gemv_role(int role, float* out, float* tap_out, int32_t* argmax_index,
     State st0{};                                                 // token 0, position 0, no prompt
     if ((rc = dst.upload(&st0, sizeof(State)))) return rc;
 
-    Launch Ln;
+    GemvLaunch Ln;
     GemvArgs a{};
     a.n = (int)n;
     a.group = G;
@@ -1682,9 +1606,7 @@ int q3_op_gemv_role(int role, float* out, float* tap_out, int32_t* argmax_index,
         a.out_tokens = dtok.as<int32_t>();
         a.out_cap = 1;
     }
-    Ln.ga = a;
-    hipLaunchKernelGGL(Ln.fn, dim3(Ln.grid), dim3(Ln.block), Ln.smem, 0, Ln.ga);
-    if ((rc = op_end())) return rc;
+    if ((rc = launch_now(0, Ln.fn, dim3(Ln.grid), dim3(Ln.block), Ln.smem, a)) || (rc = op_end())) return rc;
     HIP_TRY(hipMemcpy(out, dout.p, 4 * orows, hipMemcpyDeviceToHost));
     if (a.tap_out) HIP_TRY(hipMemcpy(tap_out, dtap.p, 4 * n, hipMemcpyDeviceToHost));
     if (epi == EPI_LOGITS) {
@@ -1708,10 +1630,8 @@ int q3_op_rmsnorm(float* out, const float* in, const float* weight, size_t n, ui
     DevBuf di, dw, dout;
     if ((rc = di.upload(in, 4 * n)) || (rc = dw.upload(weight, 4 * n)) || (rc = dout.alloc(4 * n))) return rc;
     const size_t smem = 4 * (size_t)term_floats((int)n) + 512;
-    if ((rc = set_max_smem((const void*)k_op_rmsnorm, smem))) return rc;
-    hipLaunchKernelGGL(k_op_rmsnorm, dim3(1), dim3(kWG), smem, 0, dout.as<float>(), di.as<float>(), dw.as<float>(), (int)n,
-                       (flags & Q3_FLAG_FAST) ? 0 : 1);
-    if ((rc = op_end())) return rc;
+    if ((rc = launch_now(0, k_op_rmsnorm, dim3(1), dim3(kWG), smem, dout.as<float>(), di.as<float>(), dw.as<float>(), (int)n,
+                         (flags & Q3_FLAG_FAST) ? 0 : 1)) || (rc = op_end())) return rc;
     HIP_TRY(hipMemcpy(out, dout.p, 4 * n, hipMemcpyDeviceToHost));
     return Q3_OK;
 }
@@ -1777,12 +1697,13 @@ int q3_op_attention(float* xb, float* q, float* key_cache_layer, const float* va
     if ((rc = drope.upload(tab.data(), 4 * tab.size()))) return rc;
     const bool split = pos >= 256;                       // same rule as the engine's long-context plan
     const bool att_global = split || seq_len > 4096;
-    const int att_stride = (int)((seq_len + 255) & ~(size_t)255);
-    const int slice_w = attn_slice_w((int)head_dim, (int)n_heads, 256);
-    const int nsl = (int)head_dim / slice_w;
-    DevBuf dpriv, dqout;
+    const int att_stride = att_stride_for(seq_len);
+    const int nsl = (int)head_dim / attn_slice_w((int)head_dim, (int)n_heads, 256);
+    DevBuf dpriv, dqout, dcmax, dvt;
     if (att_global && (rc = datt.alloc(4 * n_heads * (size_t)att_stride))) return rc;
-    if (split && ((rc = dpriv.alloc(4 * n_heads * nsl * (size_t)att_stride)) || (rc = dqout.alloc(4 * ahd)))) return rc;
+    if (split && ((rc = dpriv.alloc(4 * n_heads * nsl * (size_t)att_stride)) || (rc = dqout.alloc(4 * ahd)) ||
+                  (rc = dcmax.alloc(4 * n_heads * (size_t)cmax_stride_for(seq_len)))))
+        return rc;
     AttnArgs a{};
     a.q = dq.as<float>();
     a.key_cache = dk.as<float>();
@@ -1801,7 +1722,6 @@ int q3_op_attention(float* xb, float* q, float* key_cache_layer, const float* va
     a.strict = (flags & Q3_FLAG_FAST) ? 0 : 1;
     a.write_q = 1;
     a.stamps = nullptr;
-    DevBuf dvt;
     if (split && (seq_len % 4) == 0) {
         // the engine's long-context plan streams a transposed copy of the value rows: the operator builds it the same way
         if ((rc = dvt.alloc(4 * seq_len * kvd))) return rc;
@@ -1810,30 +1730,18 @@ int q3_op_attention(float* xb, float* q, float* key_cache_layer, const float* va
         a.value_t = dvt.as<float>();
     }
     if (split) {
-        a.att_stride = att_stride;
-        a.att_priv = dpriv.as<float>();
         a.q_out = dqout.as<float>();
-        const size_t sm2 = attn_out_smem_bytes((int)head_dim, (int)seq_len, slice_w);
-        a.slice_w = slice_w;
-        const ScoresShape ss = scores_shape((int)head_dim, (int)n_heads, (int)n_kv_heads, (int)seq_len);
-        if ((rc = set_attn_scores_smem(ss)) || (rc = set_attn_out_smem(sm2))) return rc;
-        DevBuf dcmax;
-        if (ss.kvm && dev_knob("Q3_ATT_CMAX", 1)) {               // 64-timestep block maxima, as in the engine's long plan
-            a.cmax_stride = (int)(((seq_len + 63) / 64 + 63) & ~(size_t)63);
-            if ((rc = dcmax.alloc(4 * n_heads * (size_t)a.cmax_stride))) return rc;
-            a.att_cmax = dcmax.as<float>();
-        }
-        launch_attn_scores(a, ss.kvm, ss.gx, ss.gy, ss.smem, 0);
-        launch_attn_out(a, (unsigned)n_heads, (unsigned)nsl, sm2, 0);
+        Launch A, B;
+        if ((rc = make_split_attn(A, B, a, datt.as<float>(), dcmax.as<float>(), dpriv.as<float>(), 256))) return rc;
+        launch(A, 0);
+        launch(B, 0);
         if ((rc = op_end())) return rc;
         HIP_TRY(hipMemcpy(dq.p, dqout.p, 4 * ahd, hipMemcpyDeviceToDevice));
     } else if ((head_dim == 64 || head_dim == 128) && dev_knob("Q3_ATT_SHORT", 1)) {
-        if ((rc = set_attn_short_smem(a))) return rc;
-        launch_attn_short(a, (unsigned)n_heads, 0);
+        const AttnShape sh = attn_short_shape((int)head_dim, (int)n_heads, (int)seq_len);
+        if ((rc = launch_now(0, sh.fn, sh.grid, sh.block, sh.smem, a))) return rc;
     } else {
-        const size_t smem = attn_smem_bytes((int)head_dim, att_global ? 0 : (int)seq_len);
-        if ((rc = set_max_smem((const void*)k_attn, smem))) return rc;
-        hipLaunchKernelGGL(k_attn, dim3((unsigned)n_heads), dim3(kWG), smem, 0, a);
+        if ((rc = launch_now(0, k_attn, dim3((unsigned)n_heads), dim3(kWG), attn_smem_bytes((int)head_dim, att_global ? 0 : (int)seq_len), a))) return rc;
     }
     if ((rc = op_end())) return rc;
     HIP_TRY(hipMemcpy(xb, dxb.p, 4 * ahd, hipMemcpyDeviceToHost));
@@ -1877,26 +1785,25 @@ int q3_dev_bench_gemv(size_t n, size_t d, size_t group_size, int wg_per_cu, int 
     GemvFn fn = pick<PRO_PREQ, EPI_STORE>((int)group_size, gs.RU, gs.JU, gs.FIN, gs.PF);
     if (!fn) return fail(Q3_ERR_UNSUPPORTED, "no kernel for tile %dx%d", gs.RU, gs.JU);
     const size_t smem = gemv_smem_bytes((int)n, (int)group_size, gs.RU, false);
-    if ((rc = set_max_smem((const void*)fn, smem))) return rc;
     hipEvent_t e0, e1;
     HIP_TRY(hipEventCreate(&e0));
     HIP_TRY(hipEventCreate(&e1));
-    auto launch = [&](int i) {
+    std::vector<Launch> ls(copies);              // one record per weight copy
+    for (size_t i = 0; i < copies; ++i) {
         GemvArgs a{};
         a.n = (int)n;
         a.group = (int)group_size;
         a.vr = gs.RU;
-        a.seg[0] = Seg{dw.as<int8_t>() + (size_t)(i % copies) * wbytes, (const float*)((char*)ds.p + (size_t)(i % copies) * sbytes),
-                       dout.as<float>(), (int)d, 0};
+        a.seg[0] = Seg{dw.as<int8_t>() + i * wbytes, (const float*)((char*)ds.p + i * sbytes), dout.as<float>(), (int)d, 0};
         a.total_rows = (int)d;
         a.pre_q = dxq.as<int8_t>();
         a.pre_s = dxs.as<float>();
-        hipLaunchKernelGGL(fn, dim3(gs.grid), dim3(kWG), smem, 0, a);
-    };
-    for (int i = 0; i < 3; ++i) launch(i);
+        if ((rc = make_launch(ls[i], F_NEXT, fn, dim3(gs.grid), dim3(kWG), smem, a))) return rc;
+    }
+    for (int i = 0; i < 3; ++i) launch(ls[(size_t)i % copies], 0);
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipEventRecord(e0, 0));
-    for (int i = 0; i < reps; ++i) launch(i);
+    for (int i = 0; i < reps; ++i) launch(ls[(size_t)i % copies], 0);
     HIP_TRY(hipEventRecord(e1, 0));
     HIP_TRY(hipEventSynchronize(e1));
     float ms = 0.f;
@@ -1927,7 +1834,6 @@ int q3_op_sample(const float* logits, size_t n, float temperature, float topp, u
         (rc = ds.alloc(4 * (size_t)kSampThreads * blen)) || (rc = dk.alloc(2 * 8 * n2)) || (rc = dss.upload(&h, sizeof(h))) ||
         (rc = dst.upload(&st, sizeof(st))) || (rc = dout.alloc(16)))
         return rc;
-    if ((rc = set_max_smem((const void*)k_sample, 4 * kSegFloats))) return rc;
     SampleArgs a{};
     a.logits = dl.as<float>();
     a.n = (int)n;
@@ -1940,8 +1846,7 @@ int q3_op_sample(const float* logits, size_t n, float temperature, float topp, u
     a.st = dst.as<State>();
     a.out_tokens = dout.as<int32_t>();
     a.out_cap = 4;
-    hipLaunchKernelGGL(k_sample, dim3(1), dim3(kSampThreads), 4 * kSegFloats, 0, a);
-    if ((rc = op_end())) return rc;
+    if ((rc = launch_now(0, k_sample, dim3(1), dim3(kSampThreads), 4 * kSegFloats, a)) || (rc = op_end())) return rc;
     HIP_TRY(hipMemcpy(&h, dss.p, sizeof(h), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(index, dout.p, 4, hipMemcpyDeviceToHost));
     *rng_state = h.rng;

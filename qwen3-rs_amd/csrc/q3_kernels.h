@@ -1535,35 +1535,8 @@ __global__ __launch_bounds__(kAoThreads) void k_attn_out(const AttnArgs a) {
     }
 }
 
-// ------------------------------------------------------------------------------------------------
-// Bookkeeping: consume the argmax cell, advance (token, pos, step)
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kWG) void k_next(State* st, const unsigned long long* slots, int nslots, int32_t* out_tokens,
-                                              int out_cap, const int32_t* prompt) {
-    __shared__ unsigned long long red[kWaves];
-    unsigned long long best = 0ull;
-    for (int i = threadIdx.x; i < nslots; i += kWG) best = slots[i] > best ? slots[i] : best;
-    for (int m = 1; m < 64; m <<= 1) {
-        const unsigned lo = __shfl_xor((unsigned)best, m);
-        const unsigned hi = __shfl_xor((unsigned)(best >> 32), m);
-        const unsigned long long o = ((unsigned long long)hi << 32) | lo;
-        best = o > best ? o : best;
-    }
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = best;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < kWaves; ++w) best = red[w] > best ? red[w] : best;
-        const int idx = (int)(unsigned)(best & 0xffffffffull);
-        const int step = st->step;
-        if (step < out_cap) out_tokens[step] = idx;       // the sample is drawn for every forward (generation.rs:120)
-        // chat-mode prefill (generation.rs:116-123): inside the prompt the next input is the next prompt token and
-        // the sample is discarded; afterwards the sample is fed back (generation.rs:143-147)
-        st->token = (step + 1 < st->prompt_len) ? prompt[step + 1] : idx;
-        st->pos = st->pos + 1;
-        st->step = step + 1;
-        st->argmax = best;
-    }
-}
+// (Bookkeeping -- consume the argmax cell, advance (token, pos, step): what used to be the single-workgroup kernel k_next is folded into
+// the classifier launch (q3_gemv.h, EPI_LOGITS with next_cell); its per-stream form is k_next_batch in q3_batch.h.)
 
 // ------------------------------------------------------------------------------------------------
 // Stand-alone operator kernels (operator-level C ABI; same device functions as above)
