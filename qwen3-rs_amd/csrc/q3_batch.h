@@ -239,6 +239,81 @@ struct BGemmArgs {
     int nslots;
 };
 
+// ---- what the in-lane kernels (k_pgemm, k_pgemm3, k_dgemm) share: a lane holds rows 4q .. 4q+3 of one position / stream as a v4f ----
+typedef float pk2 __attribute__((ext_vector_type(2)));
+
+template <int R, int P>
+__device__ __forceinline__ void acc_clear(v4f (&acc)[R][P]) {
+#pragma unroll
+    for (int i = 0; i < R; ++i)
+#pragma unroll
+        for (int j = 0; j < P; ++j) acc[i][j] = (v4f){-0.0f, -0.0f, -0.0f, -0.0f};     // Iterator::sum::<f32>() identity
+}
+
+// The term of the ordered sum for one (row tile, position tile) and one quantization group: tensor.rs:59  ((dot as f32) * ws) * xs
+// for the lane's four rows.  The pairs are chosen by hand -- (rows 4q, 4q+1) and (4q+2, 4q+3): their row scales are the two halves
+// of one v4f, xs is the same for both halves -- two packed multiplies per pair.
+// Pinning rule: EVERY value of the chain passes through an opaque register (asm("" : "+v")) between two operations.
+//   * products and sums: otherwise the SLP vectoriser re-pairs them across tiles, and its pairs forced copies of in-flight ring slots
+//     (k_pgemm, r04 disassembly: s_waitcnt vmcnt(4) with 32 loads in the ring);
+//   * the position scale, as a REAL register pair {xs, xs}: left to the compiler the packed multiply broadcast one half of whatever
+//     64-bit pair held xs (op_sel) and so formally read the partner register too -- usually the scale of a ring slot still in
+//     flight, and hipcc waited for that slot's loads (k_pgemm, r04: s_waitcnt vmcnt(6) with 28 loads in the ring, vmcnt(12-20) with 40).
+// Where the pair is pinned is the one thing the kernels do not share (XS_PIN: each kernel keeps the placement it was tuned and
+// measured with; k_dgemm's stream is unchanged by the extraction, k_pgemm's and k_pgemm3's keep their counted waits --
+// profiles/r08_matmul_helpers_isa.txt):
+//   * kXsPinFirst, before the first multiply: k_pgemm, whose xs sits in a register ring slot next to slots in flight.  Pinned
+//     after the first multiply its counted waits in the ring loop drop from vmcnt(25) to vmcnt(23) (1 x 1 tiles) and 37 to 35 (1 x 2);
+//   * kXsPinLate, between the two multiplies: k_pgemm3, whose xs is a fresh LDS read -- the placement it was measured with;
+//   * kXsPinNone: k_dgemm, same source of xs but one tile per wave: nothing to pair it with, and the pin costs a v_mov per group.
+enum { kXsPinFirst, kXsPinLate, kXsPinNone };
+template <int XS_PIN>
+__device__ __forceinline__ void mm_term(const v4i c, const v4f ws, const float xs, pk2& t01, pk2& t23) {
+    pk2 xb = (pk2){xs, xs};
+    if constexpr (XS_PIN == kXsPinFirst) asm("" : "+v"(xb));
+    pk2 u01 = (pk2){(float)c.x, (float)c.y} * (pk2){ws.x, ws.y};
+    pk2 u23 = (pk2){(float)c.z, (float)c.w} * (pk2){ws.z, ws.w};
+    asm("" : "+v"(u01)); asm("" : "+v"(u23));
+    if constexpr (XS_PIN == kXsPinLate) asm("" : "+v"(xb));
+    u01 = u01 * xb; u23 = u23 * xb;
+    asm("" : "+v"(u01)); asm("" : "+v"(u23));
+    t01 = u01; t23 = u23;
+}
+// ... and its add: the caller walks the groups in ascending order (tensor.rs:53-60)
+__device__ __forceinline__ void mm_add(v4f& ac, const pk2 t01, const pk2 t23) {
+    pk2 a01 = (pk2){ac.x, ac.y} + t01, a23 = (pk2){ac.z, ac.w} + t23;
+    asm("" : "+v"(a01)); asm("" : "+v"(a23));
+    ac.x = a01.x; ac.y = a01.y; ac.z = a23.x; ac.w = a23.y;
+}
+
+// out[position / stream sb][rows r0 .. r0+3] of a QKV, residual or plain launch
+template <int EPI>
+__device__ __forceinline__ void mm_store(const BGemmArgs& a, int sb, int r0, const v4f o) {
+    if constexpr (EPI == EPI_QKV) {
+        float* dst;
+        if (r0 < a.rows0) dst = a.out0 + (size_t)sb * a.out0_stride + r0;
+        else if (r0 < a.rows0 + a.rows1) dst = a.out1 + (size_t)sb * a.out1_stride + (r0 - a.rows0);
+        else dst = a.out2 + (size_t)sb * a.out2_stride + (size_t)a.st[sb].pos * a.pos_stride + (r0 - a.rows0 - a.rows1);
+        *(v4f*)dst = o;
+    } else if constexpr (EPI == EPI_RESID) {
+        v4f* dst = (v4f*)(a.out0 + (size_t)sb * a.out0_stride + r0);
+        v4f x = *dst;
+        x.x = x.x + o.x; x.y = x.y + o.y; x.z = x.z + o.z; x.w = x.w + o.w;      // layers.rs:249-259
+        *dst = x;
+    } else {
+        *(v4f*)(a.out0 + (size_t)sb * a.out0_stride + r0) = o;
+    }
+}
+// SwiGLU of four hidden units (the packed tiles alternate w1 | w3 of the same 16 units)            layers.rs:468-475
+__device__ __forceinline__ v4f mm_swiglu(const v4f g1, const v4f up) {
+    v4f o;
+    { const float den = 1.0f + q3_expf(-g1.x); o.x = (g1.x * (1.0f / den)) * up.x; }
+    { const float den = 1.0f + q3_expf(-g1.y); o.y = (g1.y * (1.0f / den)) * up.y; }
+    { const float den = 1.0f + q3_expf(-g1.z); o.z = (g1.z * (1.0f / den)) * up.z; }
+    { const float den = 1.0f + q3_expf(-g1.w); o.w = (g1.w * (1.0f / den)) * up.w; }
+    return o;
+}
+
 // One workgroup (8 waves) per row task (RT row tiles of 16 rows), the contraction walked in phases of PG groups:
 //   1. the 8 waves split the phase's groups; each wave issues ALL of its A/B fragment loads at once (a phase of a
 //      16-row tile is 64 KiB of weights in flight per CU), runs its MFMAs and writes the f32 group terms
@@ -485,7 +560,6 @@ __global__ __launch_bounds__(kBThreads) void k_bgemm(const BGemmArgs a) {
 // requested two groups ahead: the same 1 KiB-per-wave contiguous loads of the packed layout as k_bgemm.
 // ------------------------------------------------------------------------------------------------
 constexpr int kPgThreads = 256;
-typedef float pk2 __attribute__((ext_vector_type(2)));
 template <int EPI, int RT, int PT, int DEPTH = 4>
 __global__ __launch_bounds__(kPgThreads) void k_pgemm(const BGemmArgs a) {
     static_assert(EPI != EPI_SWIGLU || (RT % 2) == 0, "SwiGLU tasks hold w1 tiles and their w3 tiles");
@@ -545,10 +619,7 @@ __global__ __launch_bounds__(kPgThreads) void k_pgemm(const BGemmArgs a) {
             }
         };
         v4f acc[RT][PT];
-#pragma unroll
-        for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-            for (int pt = 0; pt < PT; ++pt) acc[rt][pt] = (v4f){-0.0f, -0.0f, -0.0f, -0.0f};     // Iterator::sum::<f32>() identity
+        acc_clear(acc);
 #pragma unroll
         for (int d = 0; d < DA - 1; ++d) { load_a(d, d); load_b(d, d); }
         // A group's work is split in two so that the matrix core and the VALU overlap: mfma_group(g + 1) is issued, then the
@@ -573,27 +644,9 @@ __global__ __launch_bounds__(kPgThreads) void k_pgemm(const BGemmArgs a) {
                 wsv.w = __int_as_float(__builtin_amdgcn_mov_dpp(wsr, 0x153, 0xf, 0xf, true));
 #pragma unroll
                 for (int pt = 0; pt < PT; ++pt) {
-                    const v4i c = cg[rt][pt];
-                    // the position scale as a REAL register pair {xs, xs}, materialised here.  Left to the compiler the packed
-                    // multiply broadcast one half of whatever 64-bit pair held xs (op_sel) and so formally read the partner
-                    // register too -- usually the scale of a slot still in flight, and hipcc waited for that slot's loads
-                    // (r04 disassembly: s_waitcnt vmcnt(6) with 28 loads in the ring, vmcnt(12-20) with 40)
-                    pk2 xbc = (pk2){fxs[slot][pt], fxs[slot][pt]};
-                    asm("" : "+v"(xbc));
-                    // tensor.rs:59  ((dot as f32) * ws) * xs, then the g-ascending add.  The pairs are chosen by hand -- (rows 4q,
-                    // 4q+1) and (4q+2, 4q+3) of one (row tile, position tile): their scales are the two halves of the v4f the ring
-                    // loaded, xs is broadcast by op_sel -- three packed operations per pair.  Every value passes through an opaque
-                    // register so that the SLP vectoriser does not re-pair them across tiles (its pairs forced copies of in-flight
-                    // ring slots: s_waitcnt vmcnt(4) with 32 loads in the ring).
-                    pk2 t01 = (pk2){(float)c.x, (float)c.y} * (pk2){wsv.x, wsv.y};
-                    pk2 t23 = (pk2){(float)c.z, (float)c.w} * (pk2){wsv.z, wsv.w};
-                    asm("" : "+v"(t01)); asm("" : "+v"(t23));
-                    t01 = t01 * xbc; t23 = t23 * xbc;
-                    asm("" : "+v"(t01)); asm("" : "+v"(t23));
-                    v4f& ac = acc[rt][pt];
-                    pk2 a01 = (pk2){ac.x, ac.y} + t01, a23 = (pk2){ac.z, ac.w} + t23;
-                    asm("" : "+v"(a01)); asm("" : "+v"(a23));
-                    ac.x = a01.x; ac.y = a01.y; ac.z = a23.x; ac.w = a23.y;
+                    pk2 t01, t23;
+                    mm_term<kXsPinFirst>(cg[rt][pt], wsv, fxs[slot][pt], t01, t23);
+                    mm_add(acc[rt][pt], t01, t23);
                 }
             }
         };
@@ -634,285 +687,37 @@ __global__ __launch_bounds__(kPgThreads) void k_pgemm(const BGemmArgs a) {
             const int sb = (pg * PT + pt) * 16 + s;
             if (pg * PT + pt >= nptiles || sb >= a.n_streams) continue;
             if constexpr (EPI == EPI_SWIGLU) {
-                // packed tiles alternate w1 | w3 of the same 16 hidden units            layers.rs:468-475
 #pragma unroll
-                for (int k = 0; k < RT / 2; ++k) {
-                    v4f o;
-                    const v4f g1 = acc[2 * k][pt], up = acc[2 * k + 1][pt];
-                    { const float den = 1.0f + q3_expf(-g1.x); o.x = (g1.x * (1.0f / den)) * up.x; }
-                    { const float den = 1.0f + q3_expf(-g1.y); o.y = (g1.y * (1.0f / den)) * up.y; }
-                    { const float den = 1.0f + q3_expf(-g1.z); o.z = (g1.z * (1.0f / den)) * up.z; }
-                    { const float den = 1.0f + q3_expf(-g1.w); o.w = (g1.w * (1.0f / den)) * up.w; }
-                    *(v4f*)(a.out0 + (size_t)sb * a.out0_stride + (size_t)(rtask * (RT / 2) + k) * 16 + 4 * q) = o;
-                }
+                for (int k = 0; k < RT / 2; ++k)
+                    *(v4f*)(a.out0 + (size_t)sb * a.out0_stride + (size_t)(rtask * (RT / 2) + k) * 16 + 4 * q) = mm_swiglu(acc[2 * k][pt], acc[2 * k + 1][pt]);
             } else {
 #pragma unroll
-                for (int rt = 0; rt < RT; ++rt) {
-                    const int r0 = (rtask * RT + rt) * 16 + 4 * q;
-                    const v4f o = acc[rt][pt];
-                    if constexpr (EPI == EPI_QKV) {
-                        float* dst;
-                        if (r0 < a.rows0) dst = a.out0 + (size_t)sb * a.out0_stride + r0;
-                        else if (r0 < a.rows0 + a.rows1) dst = a.out1 + (size_t)sb * a.out1_stride + (r0 - a.rows0);
-                        else dst = a.out2 + (size_t)sb * a.out2_stride + (size_t)a.st[sb].pos * a.pos_stride + (r0 - a.rows0 - a.rows1);
-                        *(v4f*)dst = o;
-                    } else if constexpr (EPI == EPI_RESID) {
-                        v4f* dst = (v4f*)(a.out0 + (size_t)sb * a.out0_stride + r0);
-                        v4f x = *dst;
-                        x.x = x.x + o.x; x.y = x.y + o.y; x.z = x.z + o.z; x.w = x.w + o.w;      // layers.rs:249-259
-                        *dst = x;
-                    } else {
-                        *(v4f*)(a.out0 + (size_t)sb * a.out0_stride + r0) = o;
-                    }
-                }
+                for (int rt = 0; rt < RT; ++rt) mm_store<EPI>(a, sb, (rtask * RT + rt) * 16 + 4 * q, acc[rt][pt]);
             }
         }
     }
 }
 
 // ------------------------------------------------------------------------------------------------
-// Dense prefill matmul, round 4: workgroup tile staged in LDS (k_pgemm2).
+// Dense prefill matmul, round 4: workgroup tile staged in LDS (k_pgemm3).
 // k_pgemm gives every WAVE its own RT x PT output tiles and lets it pull its own fragments: 1 KiB through the CU's L1 path
-// per MFMA (1.3 GB per W1|W3 pass, r03), the matrix cores 9.8 % busy.  Here a workgroup of 8 waves owns 4 row tiles x 8
-// position tiles (64 rows x 128 positions); per quantization group its 4 weight fragments, 8 activation fragments and their
-// scales (12.75 KiB) are fetched ONCE by the workgroup (each wave requests one or two KiB, a register ring 4 groups ahead),
-// committed to one of two LDS slots, and read back by the waves: wave (wr, wp) computes row tiles {2wr, 2wr+1} x position
-// tiles {2wp, 2wp+1} -- 4 MFMAs per group from 4 KiB of ds_read_b128 -- and keeps the four accumulator tiles in its lanes:
-// acc += ((f32)idot * ws) * xs, g ascending from -0.0 (tensor.rs:53-60), the same operations in the same order as every other
-// matmul of this library.  Global traffic per MFMA drops from 1 KiB to 0.4 KiB (weights: 128 B), one barrier per group.
+// per MFMA (1.3 GB per W1|W3 pass, r03), the matrix cores 9.8 % busy.  Here a workgroup of 8 waves owns 4 row tiles x PTW = 8 or 4
+// position tiles; per quantization group its 4 weight fragments, PTW activation fragments and their scales (12.75 / 8.5 KiB) are
+// fetched ONCE by the workgroup, committed to LDS, and read back by the waves: wave (wr, wp) computes row tiles {2wr, 2wr+1} x
+// position tiles {2wp, 2wp+1} (PTW = 4: tile wp) and keeps the accumulator tiles in its lanes: acc += ((f32)idot * ws) * xs, g
+// ascending from -0.0 (tensor.rs:53-60), the same operations in the same order as every other matmul of this library.  Global
+// traffic per MFMA drops from 1 KiB to 0.4 KiB (weights: 128 B).
+// The smaller tile doubles the number of workgroup tiles -- W1|W3 of the 4B shape has 608 tiles of 4 x 8 on 512 resident workgroup
+// slots (two full rounds for 1.19 rounds of work), 1,216 of 4 x 4 run as three rounds of half the length; QKV goes from 192 tiles
+// (fewer than CUs) to 384.
+// One barrier covers a stage of GS groups.  (With one group per barrier -- k_pgemm2, docs/HISTORY.md 4.5 -- a stage was a serial
+// chain of latencies: barrier -> ds_read -> MFMA -> convert / scale / add chain -> commit of the next group -> barrier, ~700 cycles
+// for ~100 cycles of pipe work, the arithmetic itself free: profiles/r04_prefill_ab.txt.)  A stage's fragments and scales
+// (GS x 8.5 KiB for 4 x 4 tiles) sit in one of two LDS slots, every wave requests its share of stage s + 2 into registers while
+// stage s is computed, and commits stage s + 1 (requested two stages ago) after its own compute; inside a stage the GS groups are
+// independent until the ordered adds, so their LDS reads, MFMAs and multiply chains overlap.
 // ------------------------------------------------------------------------------------------------
-// PTW = 8 position tiles per workgroup (wave: 2 x 2 tiles) or 4 (wave: 2 x 1): the smaller tile doubles the number of workgroup
-// tiles -- W1|W3 of the 4B shape has 608 tiles of 4 x 8 on 512 resident workgroup slots (two full rounds for 1.19 rounds of work),
-// 1,216 of 4 x 4 run as three rounds of half the length; QKV goes from 192 tiles (fewer than CUs) to 384.
-constexpr int kP2Waves = 8, kP2Threads = 512, kP2RT = 4, kP2D = 4;
-__host__ __device__ inline size_t pgemm2_slot_bytes(int ptw) { return (size_t)(kP2RT + ptw) * 1024 + (size_t)(kP2RT + ptw) * 64; }     // fragments + scales of one group
-__host__ __device__ inline size_t pgemm2_smem_bytes(int ptw) { return (ptw == 4 ? 3 : 2) * pgemm2_slot_bytes(ptw); }
-template <int EPI, int PTW>
-__global__ __launch_bounds__(kP2Threads, 4) void k_pgemm2(const BGemmArgs a) {
-    constexpr int D = kP2D;
-    constexpr int RTW = kP2RT;                                   // row tiles per workgroup
-    constexpr int NF = RTW + PTW;                                // fragments per group: [A0..A(RTW-1)][B0..B(PTW-1)]
-    constexpr int NRW = RTW / 2;                                 // row tiles per wave (SwiGLU: the w1 and the w3 tile)
-    constexpr int NPW = PTW / 4;                                 // position tiles per wave
-    constexpr size_t kSlot = (size_t)NF * 1024 + (size_t)NF * 64;
-    static_assert(PTW == 4 || PTW == 8, "workgroup tile: 4 row tiles x 4 or 8 position tiles");
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int q = lane >> 4, s = lane & 15;
-    const int wr = wave >> 2, wp = wave & 3;                     // this wave's row-tile pair / position-tile slot inside the workgroup tile
-    const int ng = a.ng;
-    const int nptiles = (a.n_streams + 15) >> 4;
-    const int npb = (nptiles + PTW - 1) / PTW;                   // position blocks
-    const int nrb = a.ntiles / RTW;                            // row blocks (host: ntiles % 4 == 0)
-    const size_t tile_v4 = (size_t)ng * 64;
-    // LDS slot: [NF fragments] v4i x 64, then [4][16] ws, [PTW][16] xs floats
-    auto slot_frag = [&](int sl) { return (v4i*)(smem_raw + (size_t)sl * kSlot); };
-    auto slot_sc = [&](int sl) { return (float*)(smem_raw + (size_t)sl * kSlot + (size_t)NF * 1024); };
-    for (int blk = blockIdx.x; blk < nrb * npb; blk += gridDim.x) {
-        const int rb = blk / npb, pb = blk - rb * npb;           // the position blocks of a row block run on neighbouring workgroups
-        // ---- loader roles (wave-uniform).  Fragment f of the group goes to wave f % 8 (waves 0..NF-9 carry two); the scales:
-        // wave 7 the row scales (4 tiles x 16 lanes), wave 6 / 5 the position scales of tiles 0-3 / 4-7
-        auto frag_src = [&](int f) -> const v4i* {
-            if (f < RTW) return (const v4i*)a.wq + (size_t)(rb * RTW + f) * tile_v4 + lane;
-            return (const v4i*)a.xq + (size_t)min(pb * PTW + (f - RTW), nptiles - 1) * tile_v4 + lane;      // (tiles past the block re-read the last one)
-        };
-        const bool one = wave < NF;                              // (2 x 4 tiles: six fragments, waves 6 and 7 only carry scales)
-        const v4i* src0 = frag_src(one ? wave : 0);
-        const bool two = wave + 8 < NF;
-        const v4i* src1 = frag_src(two ? wave + 8 : wave);
-        const bool ld_ws = wave == 7, ld_xs = wave == 6 || (PTW == 8 && wave == 5);
-        const float* ssrc = a.ws;                                // one scale dword per lane and group for the scale loaders
-        if (ld_ws) ssrc = a.ws + (size_t)(rb * RTW + min(lane >> 4, RTW - 1)) * ng * 16 + (lane & 15);
-        if (ld_xs) ssrc = a.xs + (size_t)min(pb * PTW + (wave == 5 ? 4 : 0) + (lane >> 4), nptiles - 1) * ng * 16 + (lane & 15);
-        v4i r0_[D], r1_[D];
-        float rs_[D];
-        auto issue = [&](int sl, int g) {                        // group g -> register slot sl
-            const int gg = min(g, ng - 1);
-            r0_[sl] = src0[(size_t)gg * 64];                     // (unconditional: a wave without a fragment re-reads fragment 0 and drops it --
-            if (two) r1_[sl] = src1[(size_t)gg * 64];            //  a branch around the first request made hipcc give up its counted waits: 45 -> 76 us)
-            if (ld_ws || ld_xs) rs_[sl] = ssrc[(size_t)gg * 16];
-        };
-        auto commit = [&](int sl, int ls) {                      // register slot sl -> LDS slot ls
-            v4i* f = slot_frag(ls);
-            if (one) f[wave * 64 + lane] = r0_[sl];
-            if (two) f[(wave + 8) * 64 + lane] = r1_[sl];
-            float* sc = slot_sc(ls);
-            if (ld_ws && lane < RTW * 16) sc[lane] = rs_[sl];                            // ws [RTW][16]
-            if (ld_xs) sc[RTW * 16 + (wave == 5 ? 64 : 0) + lane] = rs_[sl];         // xs [PTW][16]
-        };
-        v4f acc[NRW][NPW];
-#pragma unroll
-        for (int i = 0; i < NRW; ++i)
-#pragma unroll
-            for (int j = 0; j < NPW; ++j) acc[i][j] = (v4f){-0.0f, -0.0f, -0.0f, -0.0f};    // Iterator::sum::<f32>() identity
-        // (no software pipeline inside a wave: at 4 waves per SIMD the other waves' MFMAs cover this wave's convert / scale / add
-        // chain, and a second set of MFMA results would push the kernel past 128 VGPRs, i.e. to one workgroup per CU)
-        v4i cc[NRW][NPW];
-        v4f wsc[NRW];
-        float xsc[NPW];
-        auto mfma_group = [&](int ls, v4i (&c)[NRW][NPW], v4f (&w)[NRW], float (&x)[NPW]) {    // MFMAs of the group in LDS slot ls -> c; its scales -> w, x
-            const v4i* f = slot_frag(ls);
-            const float* sc = slot_sc(ls);
-            v4i fa[NRW], fb[NPW];
-#pragma unroll
-            for (int i = 0; i < NRW; ++i) fa[i] = f[(NRW * wr + i) * 64 + lane];
-#pragma unroll
-            for (int j = 0; j < NPW; ++j) fb[j] = f[(RTW + NPW * wp + j) * 64 + lane];
-#pragma unroll
-            for (int i = 0; i < NRW; ++i) w[i] = *(const v4f*)(sc + (NRW * wr + i) * 16 + 4 * q);
-#pragma unroll
-            for (int j = 0; j < NPW; ++j) x[j] = sc[RTW * 16 + (NPW * wp + j) * 16 + s];
-#pragma unroll
-            for (int i = 0; i < NRW; ++i)
-#pragma unroll
-                for (int j = 0; j < NPW; ++j)
-                    c[i][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(fa[i], fb[j], (v4i){0, 0, 0, 0}, 0, 0, 0);
-        };
-        auto math_group = [&](const v4i (&cg)[NRW][NPW], const v4f (&w)[NRW], const float (&x)[NPW]) {
-#pragma unroll
-            for (int i = 0; i < NRW; ++i)
-#pragma unroll
-                for (int j = 0; j < NPW; ++j) {
-                    const v4i c = cg[i][j];
-                    // tensor.rs:59  ((dot as f32) * ws) * xs, then the g-ascending add; pairs (rows 4q, 4q+1), (4q+2, 4q+3)
-                    pk2 t01 = (pk2){(float)c.x, (float)c.y} * (pk2){w[i].x, w[i].y};
-                    pk2 t23 = (pk2){(float)c.z, (float)c.w} * (pk2){w[i].z, w[i].w};
-                    asm("" : "+v"(t01)); asm("" : "+v"(t23));
-                    pk2 xb = (pk2){x[j], x[j]};
-                    asm("" : "+v"(xb));
-                    t01 = t01 * xb; t23 = t23 * xb;
-                    asm("" : "+v"(t01)); asm("" : "+v"(t23));
-                    v4f& ac = acc[i][j];
-                    pk2 a01 = (pk2){ac.x, ac.y} + t01, a23 = (pk2){ac.z, ac.w} + t23;
-                    asm("" : "+v"(a01)); asm("" : "+v"(a23));
-                    ac.x = a01.x; ac.y = a01.y; ac.z = a23.x; ac.w = a23.y;
-                }
-        };
-        if constexpr (PTW == 8) {
-#pragma unroll
-            for (int d = 0; d < D; ++d) issue(d, d);
-            commit(0, 0);
-            issue(0, D);
-            __syncthreads();
-            // ---- pipeline.  Register slot of group x is x % D, LDS slot x % 2.  Stage g: the MFMAs and the convert / scale / add
-            // chain of group g (LDS slot g % 2); meanwhile group g + 1 (requested D - 1 stages ago) goes to the other LDS slot and
-            // group g + D is requested into the register slot it leaves; one barrier per group.
-            for (int g0 = 0; g0 < ng; g0 += D) {
-#pragma unroll
-                for (int u = 0; u < D; ++u) {
-                    const int g = g0 + u;
-                    commit((u + 1) % D, (u + 1) & 1);            // group g + 1 -> the other LDS slot (past the row: a re-read group)
-                    issue((u + 1) % D, g + 1 + D);
-                    mfma_group(u & 1, cc, wsc, xsc);
-                    math_group(cc, wsc, xsc);
-                    __syncthreads();                             // group g + 1 visible; slot g % 2 free for group g + 2
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-        } else {
-            // ---- 4 x 4 tiles (78 VGPRs: room for a second fragment set): THREE LDS slots, the fragments of group g + 1 are read into
-            // registers while the MFMAs and the chain of group g run, so neither the LDS latency nor the barrier wait sits between a
-            // group's read and its MFMAs (a lone workgroup per CU -- Wo / W2 -- had nothing else to cover them: 33.7 us).  Stage g:
-            // commit group g + 2 -> slot (g + 2) % 3, request group g + 2 + D - 2, read group g + 1 (slot (g + 1) % 3, visible since
-            // the barrier of stage g - 1), compute group g from the registers read in stage g - 1, barrier.
-            static_assert((D & 1) == 0, "register-set parity is compile-time");
-            v4i fa2[2][NRW], fb2[2][NPW];                          // [parity][...]: fragments of the group computed in this / the next stage
-            v4f w2[2][NRW];
-            float x2[2][NPW];
-            auto read_group = [&](int ls, int par) {
-                const v4i* f = slot_frag(ls);
-                const float* sc = slot_sc(ls);
-#pragma unroll
-                for (int i = 0; i < NRW; ++i) fa2[par][i] = f[(NRW * wr + i) * 64 + lane];
-#pragma unroll
-                for (int j = 0; j < NPW; ++j) fb2[par][j] = f[(RTW + NPW * wp + j) * 64 + lane];
-#pragma unroll
-                for (int i = 0; i < NRW; ++i) w2[par][i] = *(const v4f*)(sc + (NRW * wr + i) * 16 + 4 * q);
-#pragma unroll
-                for (int j = 0; j < NPW; ++j) x2[par][j] = sc[RTW * 16 + (NPW * wp + j) * 16 + s];
-            };
-            auto compute = [&](int par) {
-#pragma unroll
-                for (int i = 0; i < NRW; ++i)
-#pragma unroll
-                    for (int j = 0; j < NPW; ++j)
-                        cc[i][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(fa2[par][i], fb2[par][j], (v4i){0, 0, 0, 0}, 0, 0, 0);
-                math_group(cc, w2[par], x2[par]);
-            };
-#pragma unroll
-            for (int d = 0; d < D; ++d) issue(d, d);
-            commit(0, 0);                                        // groups 0 and 1 -> LDS slots 0 and 1
-            commit(1, 1);
-            issue(0, D);
-            issue(1, D + 1);
-            __syncthreads();
-            read_group(0, 0);                                    // group 0 -> register set 0
-            int l1 = 1, l2 = 2;                                  // LDS slots of groups g + 1 and g + 2 (run-time: g % 3 does not divide the unroll)
-            for (int g0 = 0; g0 < ng; g0 += D) {
-#pragma unroll
-                for (int u = 0; u < D; ++u) {
-                    const int g = g0 + u;
-                    commit((u + 2) % D, l2);                     // group g + 2 (requested D - 2 stages ago)
-                    issue((u + 2) % D, g + 2 + D);
-                    read_group(l1, (u + 1) & 1);                 // group g + 1 (past the row: a re-read group, dropped)
-                    compute(u & 1);
-                    __syncthreads();                             // group g + 2 visible; slot g % 3 free for group g + 3
-                    l1 = l2;
-                    l2 = l2 == 2 ? 0 : l2 + 1;
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-        }
-        // ---- epilogue: lane (s, q) owns out[position (pb*PTW + NPW*wp + j)*16 + s][rows 4q .. 4q+3 of row tile rb*4 + 2wr + i]
-#pragma unroll
-        for (int j = 0; j < NPW; ++j) {
-            const int ptj = pb * PTW + NPW * wp + j;
-            const int sb = ptj * 16 + s;
-            if (ptj >= nptiles || sb >= a.n_streams) continue;
-            if constexpr (EPI == EPI_SWIGLU) {
-                // packed tiles alternate w1 | w3 of the same 16 hidden units            layers.rs:468-475
-                v4f o;
-                const v4f g1 = acc[0][j], up = acc[1][j];
-                { const float den = 1.0f + q3_expf(-g1.x); o.x = (g1.x * (1.0f / den)) * up.x; }
-                { const float den = 1.0f + q3_expf(-g1.y); o.y = (g1.y * (1.0f / den)) * up.y; }
-                { const float den = 1.0f + q3_expf(-g1.z); o.z = (g1.z * (1.0f / den)) * up.z; }
-                { const float den = 1.0f + q3_expf(-g1.w); o.w = (g1.w * (1.0f / den)) * up.w; }
-                *(v4f*)(a.out0 + (size_t)sb * a.out0_stride + (size_t)(rb * (RTW / 2) + wr) * 16 + 4 * q) = o;
-            } else {
-#pragma unroll
-                for (int i = 0; i < NRW; ++i) {
-                    const int r0 = (rb * RTW + NRW * wr + i) * 16 + 4 * q;
-                    const v4f o = acc[i][j];
-                    if constexpr (EPI == EPI_QKV) {
-                        float* dst;
-                        if (r0 < a.rows0) dst = a.out0 + (size_t)sb * a.out0_stride + r0;
-                        else if (r0 < a.rows0 + a.rows1) dst = a.out1 + (size_t)sb * a.out1_stride + (r0 - a.rows0);
-                        else dst = a.out2 + (size_t)sb * a.out2_stride + (size_t)a.st[sb].pos * a.pos_stride + (r0 - a.rows0 - a.rows1);
-                        *(v4f*)dst = o;
-                    } else if constexpr (EPI == EPI_RESID) {
-                        v4f* dst = (v4f*)(a.out0 + (size_t)sb * a.out0_stride + r0);
-                        v4f x = *dst;
-                        x.x = x.x + o.x; x.y = x.y + o.y; x.z = x.z + o.z; x.w = x.w + o.w;      // layers.rs:249-259
-                        *dst = x;
-                    } else {
-                        *(v4f*)(a.out0 + (size_t)sb * a.out0_stride + r0) = o;
-                    }
-                }
-            }
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// k_pgemm3: k_pgemm2's workgroup tile with GS quantization groups per pipeline stage.
-// The ablation of k_pgemm2 (profiles/r04_prefill_ab.txt) showed a stage that is a serial chain of latencies -- barrier -> ds_read ->
-// MFMA -> convert / scale / add chain -> commit of the next group -> barrier, ~700 cycles for ~100 cycles of pipe work -- with
-// the arithmetic itself free (no-VALU and no-MFMA builds run at the same speed).  Here one barrier covers GS groups: a stage's
-// fragments and scales (GS x 8.5 KiB for 4 x 4 tiles) sit in one of two LDS slots, every wave requests its share of stage s + 2
-// into registers while stage s is computed, and commits stage s + 1 (requested two stages ago) after its own compute; inside a
-// stage the GS groups are independent until the ordered adds, so their LDS reads, MFMAs and multiply chains overlap.
-// Same accumulation order per (row, position): groups ascending, acc += ((f32)idot * ws) * xs from -0.0 (tensor.rs:53-60).
-// ------------------------------------------------------------------------------------------------
+constexpr int kP2Threads = 512, kP2RT = 4;
 __host__ __device__ inline size_t pgemm3_slot_bytes(int ptw, int gs) { return (size_t)gs * ((size_t)(kP2RT + ptw) * 1024 + (size_t)(kP2RT + ptw) * 64); }
 __host__ __device__ inline size_t pgemm3_smem_bytes(int ptw, int gs) { return 2 * pgemm3_slot_bytes(ptw, gs); }
 
@@ -975,10 +780,7 @@ __global__ __launch_bounds__(kP2Threads, 4) void k_pgemm3(const BGemmArgs a) {
             if (tid < NSC) slot_sc(ls)[tid] = rsc[rs];
         };
         v4f acc[NRW][NPW];
-#pragma unroll
-        for (int i = 0; i < NRW; ++i)
-#pragma unroll
-            for (int j = 0; j < NPW; ++j) acc[i][j] = (v4f){-0.0f, -0.0f, -0.0f, -0.0f};    // Iterator::sum::<f32>() identity
+        acc_clear(acc);
         // a stage is computed HS groups at a time (their reads, MFMAs and multiply chains are independent and overlap), the
         // ordered adds of a sub-step follow its terms.  Per accumulator the order is unchanged: groups ascending.
         constexpr int HS = (GS >= 2 && NPW == 1) ? 2 : 1;
@@ -1014,29 +816,13 @@ __global__ __launch_bounds__(kP2Threads, 4) void k_pgemm3(const BGemmArgs a) {
 #pragma unroll
                     for (int i = 0; i < NRW; ++i)
 #pragma unroll
-                        for (int j = 0; j < NPW; ++j) {
-                            const v4i c = cc[h][i][j];
-                            // tensor.rs:59  ((dot as f32) * ws) * xs; pairs (rows 4q, 4q+1), (4q+2, 4q+3)
-                            pk2 u01 = (pk2){(float)c.x, (float)c.y} * (pk2){w[h][i].x, w[h][i].y};
-                            pk2 u23 = (pk2){(float)c.z, (float)c.w} * (pk2){w[h][i].z, w[h][i].w};
-                            asm("" : "+v"(u01)); asm("" : "+v"(u23));
-                            pk2 xb = (pk2){x[h][j], x[h][j]};
-                            asm("" : "+v"(xb));
-                            u01 = u01 * xb; u23 = u23 * xb;
-                            asm("" : "+v"(u01)); asm("" : "+v"(u23));
-                            t01[h][i][j] = u01; t23[h][i][j] = u23;
-                        }
+                        for (int j = 0; j < NPW; ++j) mm_term<kXsPinLate>(cc[h][i][j], w[h][i], x[h][j], t01[h][i][j], t23[h][i][j]);
 #pragma unroll
                 for (int h = 0; h < HS; ++h)
 #pragma unroll
                     for (int i = 0; i < NRW; ++i)
 #pragma unroll
-                        for (int j = 0; j < NPW; ++j) {
-                            v4f& ac = acc[i][j];
-                            pk2 a01 = (pk2){ac.x, ac.y} + t01[h][i][j], a23 = (pk2){ac.z, ac.w} + t23[h][i][j];
-                            asm("" : "+v"(a01)); asm("" : "+v"(a23));
-                            ac.x = a01.x; ac.y = a01.y; ac.z = a23.x; ac.w = a23.y;
-                        }
+                        for (int j = 0; j < NPW; ++j) mm_add(acc[i][j], t01[h][i][j], t23[h][i][j]);
                 __builtin_amdgcn_sched_barrier(0);
             }
         };
@@ -1064,37 +850,12 @@ __global__ __launch_bounds__(kP2Threads, 4) void k_pgemm3(const BGemmArgs a) {
             const int sb = ptj * 16 + s;
             if (ptj >= nptiles || sb >= a.n_streams) continue;
             if constexpr (EPI == EPI_SWIGLU) {
-                // packed tiles alternate w1 | w3 of the same 16 hidden units            layers.rs:468-475
 #pragma unroll
-                for (int pr = 0; pr < NRW / 2; ++pr) {
-                    v4f o;
-                    const v4f g1 = acc[2 * pr][j], up = acc[2 * pr + 1][j];
-                    { const float den = 1.0f + q3_expf(-g1.x); o.x = (g1.x * (1.0f / den)) * up.x; }
-                    { const float den = 1.0f + q3_expf(-g1.y); o.y = (g1.y * (1.0f / den)) * up.y; }
-                    { const float den = 1.0f + q3_expf(-g1.z); o.z = (g1.z * (1.0f / den)) * up.z; }
-                    { const float den = 1.0f + q3_expf(-g1.w); o.w = (g1.w * (1.0f / den)) * up.w; }
-                    *(v4f*)(a.out0 + (size_t)sb * a.out0_stride + (size_t)(rb * (RTW / 2) + wr * (NRW / 2) + pr) * 16 + 4 * q) = o;
-                }
+                for (int pr = 0; pr < NRW / 2; ++pr)
+                    *(v4f*)(a.out0 + (size_t)sb * a.out0_stride + (size_t)(rb * (RTW / 2) + wr * (NRW / 2) + pr) * 16 + 4 * q) = mm_swiglu(acc[2 * pr][j], acc[2 * pr + 1][j]);
             } else {
 #pragma unroll
-                for (int i = 0; i < NRW; ++i) {
-                    const int r0 = (rb * RTW + NRW * wr + i) * 16 + 4 * q;
-                    const v4f o = acc[i][j];
-                    if constexpr (EPI == EPI_QKV) {
-                        float* dst;
-                        if (r0 < a.rows0) dst = a.out0 + (size_t)sb * a.out0_stride + r0;
-                        else if (r0 < a.rows0 + a.rows1) dst = a.out1 + (size_t)sb * a.out1_stride + (r0 - a.rows0);
-                        else dst = a.out2 + (size_t)sb * a.out2_stride + (size_t)a.st[sb].pos * a.pos_stride + (r0 - a.rows0 - a.rows1);
-                        *(v4f*)dst = o;
-                    } else if constexpr (EPI == EPI_RESID) {
-                        v4f* dst = (v4f*)(a.out0 + (size_t)sb * a.out0_stride + r0);
-                        v4f x = *dst;
-                        x.x = x.x + o.x; x.y = x.y + o.y; x.z = x.z + o.z; x.w = x.w + o.w;      // layers.rs:249-259
-                        *dst = x;
-                    } else {
-                        *(v4f*)(a.out0 + (size_t)sb * a.out0_stride + r0) = o;
-                    }
-                }
+                for (int i = 0; i < NRW; ++i) mm_store<EPI>(a, sb, (rb * RTW + NRW * wr + i) * 16 + 4 * q, acc[i][j]);
             }
         }
         __syncthreads();                                         // the next block's prologue overwrites slot 0
@@ -1196,10 +957,7 @@ __global__ __launch_bounds__(kDgWaves * 64) void k_dgemm(const BGemmArgs a) {
         chunk_commit();                                          // (counted wait: the ring fill stays in flight)
         wave_lds_sync();
         v4f acc[RT][PT];
-#pragma unroll
-        for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-            for (int p = 0; p < PT; ++p) acc[rt][p] = (v4f){-0.0f, -0.0f, -0.0f, -0.0f};   // Iterator::sum::<f32>() identity
+        acc_clear(acc);
         v4i cc[RT][PT], cn[RT][PT];
         v4f wsc[RT], wsn[RT];
         float xsc[PT], xsn[PT];
@@ -1221,17 +979,9 @@ __global__ __launch_bounds__(kDgWaves * 64) void k_dgemm(const BGemmArgs a) {
             for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
                 for (int p = 0; p < PT; ++p) {
-                    const v4i c = cg[rt][p];
-                    // tensor.rs:59  ((dot as f32) * ws) * xs, then the g-ascending add; pairs (rows 4q, 4q+1), (4q+2, 4q+3)
-                    pk2 t01 = (pk2){(float)c.x, (float)c.y} * (pk2){w[rt].x, w[rt].y};
-                    pk2 t23 = (pk2){(float)c.z, (float)c.w} * (pk2){w[rt].z, w[rt].w};
-                    asm("" : "+v"(t01)); asm("" : "+v"(t23));
-                    t01 = t01 * (pk2){x[p], x[p]}; t23 = t23 * (pk2){x[p], x[p]};
-                    asm("" : "+v"(t01)); asm("" : "+v"(t23));
-                    v4f& ac = acc[rt][p];
-                    pk2 a01 = (pk2){ac.x, ac.y} + t01, a23 = (pk2){ac.z, ac.w} + t23;
-                    asm("" : "+v"(a01)); asm("" : "+v"(a23));
-                    ac.x = a01.x; ac.y = a01.y; ac.z = a23.x; ac.w = a23.y;
+                    pk2 t01, t23;
+                    mm_term<kXsPinNone>(cg[rt][p], w[rt], x[p], t01, t23);
+                    mm_add(acc[rt][p], t01, t23);
                 }
         };
         auto rotate = [&]() {
@@ -1247,14 +997,7 @@ __global__ __launch_bounds__(kDgWaves * 64) void k_dgemm(const BGemmArgs a) {
         // ---- epilogue of row task `task`: lane (s, q) adds its accumulators to x[stream pt*16 + s][rows 4q .. 4q+3 of the row tile]
         auto epilogue = [&](int task) {
             const int sb = pt * 16 + s;
-            const int r0 = task * 16 + 4 * q;
-            const v4f o = acc[0][0];
-            if (sb < a.n_streams) {
-                v4f* dst = (v4f*)(a.out0 + (size_t)sb * a.out0_stride + r0);
-                v4f x = *dst;
-                x.x = x.x + o.x; x.y = x.y + o.y; x.z = x.z + o.z; x.w = x.w + o.w;      // layers.rs:249-259
-                *dst = x;
-            }
+            if (sb < a.n_streams) mm_store<EPI_RESID>(a, sb, task * 16 + 4 * q, acc[0][0]);
         };
         // software pipeline (k_pgemm's): stage u requests the group DEPTH - 1 ahead, issues the MFMA and the LDS scale reads of
         // the next group, then runs the convert / scale / add chain of its own group while those are in flight.  An iteration =
@@ -1284,10 +1027,7 @@ __global__ __launch_bounds__(kDgWaves * 64) void k_dgemm(const BGemmArgs a) {
             if (last) {
                 epilogue(cur);
                 if (++k == ntk) break;
-#pragma unroll
-                for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-                    for (int p = 0; p < PT; ++p) acc[rt][p] = (v4f){-0.0f, -0.0f, -0.0f, -0.0f};
+                acc_clear(acc);
                 g0 = 0;
                 cur = nxt;
                 nxt = k + 1 < ntk ? cur + rstride : cur;

@@ -106,13 +106,11 @@ BGemmFn pick_pgemm(int RT, int PT) {
     return nullptr;
 }
 template <int EPI>
-BGemmFn pick_pgemm2(int ptw) {
-    if constexpr (EPI != EPI_LOGITS) return ptw == 8 ? (BGemmFn)k_pgemm2<EPI, 8> : (BGemmFn)k_pgemm2<EPI, 4>;
-    return nullptr;
-}
-template <int EPI>
-BGemmFn pick_pgemm3(int ptw) {      // 2 quantization groups per barrier for 4 x 8 tiles, 4 for 4 x 4
-    if constexpr (EPI != EPI_LOGITS) return ptw == 8 ? (BGemmFn)k_pgemm3<EPI, 8, 2> : (BGemmFn)k_pgemm3<EPI, 4, 4>;
+BGemmFn pick_pgemm3(int ptw, int gs) {      // quantization groups per barrier: 2 for 4 x 8 tiles; 4 for 4 x 4, 2 where ng % 8 != 0
+    if constexpr (EPI != EPI_LOGITS) {
+        if (ptw == 8) return (BGemmFn)k_pgemm3<EPI, 8, 2>;
+        return gs == 4 ? (BGemmFn)k_pgemm3<EPI, 4, 4> : (BGemmFn)k_pgemm3<EPI, 4, 2>;
+    }
     return nullptr;
 }
 // k_dgemm of a residual launch (Wo, W2) at group 64: the 16-group ring where the row length allows it, else 8; nullptr: k_bgemm
@@ -237,12 +235,12 @@ int batch_build_plan(q3_engine* e, int n, PlanKind kind) {
         unsigned grid = 1, block = 0;
         size_t smem = 0;
         int depth = 0;
-        // LDS-staged workgroup tiles of 4 row tiles x 8 or 4 position tiles (k_pgemm2, round 4), two workgroups per CU, the grid walks
+        // LDS-staged workgroup tiles of 4 row tiles x 8 or 4 position tiles (k_pgemm3, round 4), two workgroups per CU, the grid walks
         // the (row block, position block) list.  Tile width by measurement (4B shape, us per 256 positions, profiles/r04_prefill_ab.txt):
         // W1|W3 (608 tiles of 4 x 8) 45.5 vs 50.8 for 4 x 4 vs 53.2 k_pgemm; Wo / W2 (80 tiles of 4 x 8) 46.5 vs 33.9 vs 39.0; QKV 22.2 vs
         // 22.6 vs 25.2 -- 4 x 8 where that fills the resident slots, 4 x 4 otherwise.  Q3_PGEMM2_PT = 8 / 4 forces a width,
         // Q3_PGEMM2=0 keeps k_pgemm.
-        if (dense && nptiles >= 6 && (m.ntiles % kP2RT) == 0 && (m.ng % kP2D) == 0 && epi != EPI_LOGITS && dev_knob("Q3_PGEMM2", 1) != 0) {
+        if (dense && nptiles >= 6 && (m.ntiles % kP2RT) == 0 && (m.ng % 4) == 0 && epi != EPI_LOGITS && dev_knob("Q3_PGEMM2", 1) != 0) {
             const long nrb = m.ntiles / kP2RT;
             const long t8 = nrb * ((nptiles + 7) / 8), t4 = nrb * ((nptiles + 3) / 4), slots = 2L * e->n_cu;
             int ptw = dev_knob("Q3_PGEMM2_PT", 0);
@@ -250,13 +248,13 @@ int batch_build_plan(q3_engine* e, int n, PlanKind kind) {
             const long nblk = ptw == 8 ? t8 : t4;
             // (2 row tiles x 4 position tiles per workgroup, Wo / W2 of the 4B shape: 36.1 vs 34.5 us; 8 x 8 tiles: 30.1-30.9k tok/s
             // against 32.1k for 4 x 8 -- neither kept)
-            // k_pgemm3: the same workgroup tile with 4 (4 x 4 tiles) / 2 (4 x 8) quantization groups per barrier (Q3_PGEMM3=0: k_pgemm2)
-            const int gs = ptw == 4 ? 4 : 2;
-            const bool p3 = (m.ng % (2 * gs)) == 0 && dev_knob("Q3_PGEMM3", 1) != 0;
-            fn = p3 ? Q3_BY_EPI(epi, pick_pgemm3, ptw) : Q3_BY_EPI(epi, pick_pgemm2, ptw);
+            // quantization groups per barrier (the kernel walks stage pairs: ng % (2 gs) == 0): 2 for 4 x 8 tiles; 4 for 4 x 4, or 2
+            // where the row has an odd number of 4-group stages (ng % 8 == 4; Q3_PGEMM3_GS=2 forces that form on 4 x 4 tiles -- 2 is the only value with a meaning, any other keeps the choice above)
+            const int gs = ptw == 8 ? 2 : ((m.ng % 8) == 0 && dev_knob("Q3_PGEMM3_GS", 4) != 2 ? 4 : 2);
+            fn = Q3_BY_EPI(epi, pick_pgemm3, ptw, gs);
             grid = (unsigned)(nblk < slots ? nblk : slots);
             block = kP2Threads;
-            smem = p3 ? pgemm3_smem_bytes(ptw, gs) : pgemm2_smem_bytes(ptw);
+            smem = pgemm3_smem_bytes(ptw, gs);
         } else if (dense) {
             // wave tasks of RT row tiles x PT position tiles; smaller tiles for the small matrices so that every SIMD has work
             // (r03 sweep, 4B shape: 2 x 2 tiles with a 6-deep ring for the big matrices, 1 x 2 / 8-deep for the 160-tile ones)

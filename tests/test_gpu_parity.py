@@ -645,12 +645,13 @@ def test_batched_prefill_block_sizes_agree(q3, block, shape_name, tmp_path_facto
     """Q3_PREFILL_M picks the positions per weight pass: 32 = the batch-32 kernels (k_bgemm + LDS term tile), larger blocks
     the dense kernels (k_pgemm in-lane fold, k_attn_pf).  Every block size must give the cache rows and tokens of the
     sequential prompt loop (generation.rs:116-123) bit for bit, including a ragged last block and a non-zero start.
-    Blocks of 128 / 256 run the LDS-tiled matmul (k_pgemm2 / k_pgemm3) with 4 x 4 position-tile workgroups by default on these shapes;
-    negative block: the same size with a form the planner takes on other shapes -- -128: k_pgemm2 in place of k_pgemm3
-    (Q3_PGEMM3=0), -256: the 4 x 8 tiles of larger matrices (Q3_PGEMM2_PT=8), -512: the per-wave k_pgemm of short blocks
+    Blocks of 128 / 256 run the LDS-tiled matmul (k_pgemm3) with 4 x 4 position-tile workgroups by default on these shapes: four
+    quantization groups per barrier where the row has a multiple of 8 groups, two otherwise (the 256-wide rows of small-longctx);
+    negative block: the same size with a form the planner takes on other shapes -- -128: two groups per barrier on every row
+    (Q3_PGEMM3_GS=2), -256: the 4 x 8 tiles of larger matrices (Q3_PGEMM2_PT=8), -512: the per-wave k_pgemm of short blocks
     (Q3_PGEMM2=0); 48 positions (3 tiles) stay on k_pgemm."""
     if block == -128:
-        dev_forms({"Q3_PGEMM3": "0"})
+        dev_forms({"Q3_PGEMM3_GS": "2"})
     if block == -256:
         dev_forms({"Q3_PGEMM2_PT": "8"})
     if block == -512:
