@@ -233,8 +233,8 @@ int q3_batch_read_state(q3_engine* e, int stream, int kind, size_t offset, size_
  * classifier of the batched decode; a draft is accepted exactly when it equals the argmax of the position in front of it,
  * so every returned token is the token q3_generate_greedy returns, bit-identical logits and cache rows included.
  * Refused with Q3_ERR_UNSUPPORTED: a Q3_FLAG_FAST engine (its block and single-stream kernels are not bit-equal to each
- * other), an engine whose sampler is set to a temperature > 0 (speculative sampling is not implemented), and the shapes
- * q3_batch_init refuses.  The packed weight copy of q3_prefill_batched is allocated on first use and shared with it and
+ * other), an engine whose sampler is set to a temperature > 0 (these two names are greedy only: section 2d holds for any
+ * sampler setting), and the shapes q3_batch_init refuses.  The packed weight copy of q3_prefill_batched is allocated on first use and shared with it and
  * with q3_batch_init.  No environment variable: everything is an argument.
  * ------------------------------------------------------------------------------------------------ */
 #define Q3_VERIFY_MAX 32
@@ -333,6 +333,39 @@ int q3_op_attention(float* xb, float* q, float* key_cache_layer, const float* va
 int q3_op_sample(const float* logits, size_t n, float temperature, float topp, uint64_t* rng_state, int32_t* index, int device);
 /* Sampler::sample_argmax                                                sampler.rs:57-59 */
 int q3_op_argmax(const float* logits, size_t n, int32_t* index, int device);
+
+/* ------------------------------------------------------------------------------------------------
+ * 2d. (behind section 3 so that section 2c stays as it was.)  Draft verification under the sampler: section 2c for any
+ * setting of q3_sampler_set.  Sampler::sample is a deterministic
+ * function of (logits, rng state) with one xorshift64* coin per draw (sampler.rs:44-54,118-139), so the token the sequential
+ * loop (generation.rs:153-162) draws at position first_pos + i depends only on the logits of the prefix and on the coin i + 1
+ * steps behind the rng state at entry.  The rule: a draft is accepted exactly when it is the token the sampler draws -- the
+ * draw of the column in front of it, made with that coin.  No rejection sampling, no second distribution: every returned
+ * token, every cache row and the rng afterwards are bit-identical to q3_generate_sampled.  The pass is section 2c's with the
+ * per-stream draws of the batched decode (one workgroup per column) in place of the argmax; the draw scratch of 32 columns
+ * (~5.3 MB per column at a 151,936-entry vocabulary) is allocated by the first pass that samples.  Refused with
+ * Q3_ERR_UNSUPPORTED: a Q3_FLAG_FAST engine and the shapes q3_batch_init refuses.
+ * ------------------------------------------------------------------------------------------------ */
+
+/* q3_verify under the sampler.  With the engine's temperature / top-p and R = the rng state at entry:
+ *   next_tokens[i] = Sampler::sample(forward(tokens[i], first_pos + i)) drawn with the rng state i coins behind R   (sampler.rs:118-139)
+ *   *n_accepted    = a = the number of leading drafts with tokens[j] == next_tokens[j - 1]
+ * On return the engine is where q3_generate_sampled(tokens[0], first_pos, a + 1) leaves it: rows first_pos .. first_pos + a
+ * written (the transposed value cache too), later rows restored, the single-stream state and output tokens set, and
+ * q3_sampler_get_rng = R advanced a + 1 coins -- the draws behind a rejection are not consumed.  next_tokens[a + 1 ..) are
+ * the draws the rejected columns made on the proposed prefix with their own coins; they change nothing.
+ * logits_out: as for q3_verify, the raw logits (bit-identical to q3_forward; the sampler does not touch them).
+ * With temperature 0 (or no q3_sampler_set) it is q3_verify: same results, no coin drawn.  Q3_ERR_ARG as for q3_verify. */
+int q3_verify_draw(q3_engine* e, const int32_t* tokens, size_t n_tokens, size_t first_pos, int32_t* next_tokens, size_t* n_accepted,
+                   float* logits_out);
+
+/* q3_generate_lookup under the sampler: out_tokens, the engine state and the final rng equal those of
+ * q3_generate_sampled(first_token, first_pos, n_tokens) (generation.rs:153-162 with Sampler::sample).  Rounds as in
+ * q3_generate_lookup: no draft -> one ordinary sampled single-stream step through the decode graph; d drafts -> one pass.
+ * stats as there.  A caller that stops at a token inside a call (BOS / EOS) has drawn the coins behind it: both front ends put
+ * the rng back with q3_sampler_get_rng before and q3_sampler_set after such a round (cli/q3_cli.cpp). */
+int q3_generate_lookup_draw(q3_engine* e, const int32_t* corpus, size_t n_corpus, size_t first_token, size_t first_pos, size_t n_tokens,
+                            int ngram, int draft_len, int32_t* out_tokens, q3_spec_stats* stats);
 
 #ifdef __cplusplus
 }

@@ -209,9 +209,16 @@ int fail_engine(const char* what) {
 // --lookup N: greedy decode through q3_generate_lookup in rounds of up to N + 1 tokens, handed out one by one.  history = the
 // window's tokens so far, its last one the token to forward next; everything before it is the corpus the drafts are looked up in
 // (n-gram length 2).  Rows a round writes past the point where the caller stops are rewritten before they are read.
+// --speculate N: the same rounds through q3_generate_lookup_draw, at any temperature: a draft is accepted exactly when it is the
+// token the sampler draws, so the tokens are those of the plain loop.  A round that runs past a BOS / EOS token has drawn coins
+// the plain loop never draws (it ends the turn there): the round is cut behind that token and the rng put back to where the
+// token's draw left it, so the next turn samples as it would have.
 constexpr int kLookupNgram = 2;
 struct Lookup {
     int draft_len = 0;
+    bool draw = false;                  // --speculate
+    float temperature = 0.0f, topp = 0.0f;
+    uint32_t bos = 0, eos = 0;
     std::vector<int32_t> history, pending;
     size_t head = 0;
     void reset() { history.clear(); pending.clear(); head = 0; }
@@ -226,9 +233,20 @@ struct Lookup {
             const size_t room = (size_t)seq_len - pos, n = room < (size_t)draft_len + 1 ? room : (size_t)draft_len + 1;
             pending.assign(n, 0);
             head = 0;
-            const int rc = q3_generate_lookup(e, history.data(), history.size() - 1, (size_t)history.back(), pos, n, kLookupNgram, draft_len,
-                                              pending.data(), nullptr);
+            const bool coins = draw && temperature > 0.0f;
+            uint64_t rng = 0;
+            int rc = coins ? q3_sampler_get_rng(e, &rng) : Q3_OK;
             if (rc != Q3_OK) return rc;
+            rc = (draw ? q3_generate_lookup_draw : q3_generate_lookup)(e, history.data(), history.size() - 1, (size_t)history.back(), pos, n,
+                                                                       kLookupNgram, draft_len, pending.data(), nullptr);
+            if (rc != Q3_OK) return rc;
+            for (size_t k = 0; coins && k + 1 < n; ++k)
+                if ((uint32_t)pending[k] == bos || (uint32_t)pending[k] == eos) {
+                    for (size_t c = 0; c <= k; ++c) { rng ^= rng >> 12; rng ^= rng << 25; rng ^= rng >> 27; }    // sampler.rs:44-49
+                    pending.resize(k + 1);
+                    if ((rc = q3_sampler_set(e, temperature, topp, rng)) != Q3_OK) return rc;
+                    break;
+                }
         }
         *out = pending[head++];
         history.push_back(*out);
@@ -237,7 +255,8 @@ struct Lookup {
 };
 
 // generation.rs:9-48
-int run_generate(q3_engine* e, const Tokenizer& tok, int seq_len, const std::string* prompt, int lookup) {
+int run_generate(q3_engine* e, const Tokenizer& tok, int seq_len, const std::string* prompt, const Lookup& lk0) {
+    const int lookup = lk0.draft_len;
     const std::vector<int> pt = tok.encode(prompt ? *prompt : std::string());
     if (pt.empty()) {
         fprintf(stderr, "Please provide a prompt\n");
@@ -247,8 +266,7 @@ int run_generate(q3_engine* e, const Tokenizer& tok, int seq_len, const std::str
     int token = pt.back();
     size_t pos = pt.size() - 1;
     Metrics m;
-    Lookup lk;
-    lk.draft_len = lookup;
+    Lookup lk = lk0;
     lk.history.assign(pt.begin(), pt.end());
     while (pos < (size_t)seq_len) {
         m.start();
@@ -280,13 +298,13 @@ int prefill(q3_engine* e, const std::vector<int>& ids, size_t pos, int32_t* next
 }
 
 // generation.rs:50-151, loop for loop (see qwen3_rs_amd/cli.py::run_chat)
-int run_chat(q3_engine* e, const Tokenizer& tok, int seq_len, const std::string* cli_prompt, const std::string* system_prompt, int lookup) {
+int run_chat(q3_engine* e, const Tokenizer& tok, int seq_len, const std::string* cli_prompt, const std::string* system_prompt, const Lookup& lk0) {
+    const int lookup = lk0.draft_len;
     size_t pos = 0;
     bool user_turn = true;
     int32_t nxt = 0;
     Metrics m;
-    Lookup lk;
-    lk.draft_len = lookup;
+    Lookup lk = lk0;
     for (;;) {
         if (pos >= (size_t)seq_len) {      // "Reset context if window exceeded": the cache is not cleared
             pos = 0;
@@ -340,12 +358,13 @@ void usage() {
     fprintf(stderr,
             "Qwen3 inference on the MI355X engine\n\n"
             "Usage: q3_cli inference <checkpoint> [-t TEMPERATURE] [-p TOPP] [-s SEED] [-c CONTEXT] [-m generate|chat]\n"
-            "                                     [-i INPUT] [-y SYSTEM] [-r 0|1] [--lookup DRAFT_LEN]\n"
+            "                                     [-i INPUT] [-y SYSTEM] [-r 0|1] [--lookup DRAFT_LEN] [--speculate DRAFT_LEN]\n"
             "  -t, --temperature  [0, inf)   default 1.0\n  -p, --topp         [0, 1]     default 0.9\n"
             "  -s, --seed         random seed (default: time)\n  -c, --context      context window size (default: the checkpoint's)\n"
             "  -m, --mode         generate | chat (default chat)\n  -i, --input        input prompt\n"
             "  -y, --system       system prompt (chat mode)\n  -r, --reasoning    0 = no thinking, 1 = thinking (default 0)\n"
-            "      --lookup       greedy only (-t 0): draft up to DRAFT_LEN (1..31) tokens per weight pass by prompt lookup; 0 = off\n");
+            "      --lookup       greedy only (-t 0): draft up to DRAFT_LEN (1..31) tokens per weight pass by prompt lookup; 0 = off\n"
+            "      --speculate    any -t: the same drafts, each accepted exactly when it is the token the sampler draws; same output\n");
 }
 
 }  // namespace
@@ -377,7 +396,7 @@ int main(int argc, char** argv) {
     double temperature = 1.0, topp = 0.9;
     bool have_seed = false, have_input = false, have_system = false;
     unsigned long long seed = 0;
-    long context = 0, reasoning = 0, lookup = 0;
+    long context = 0, reasoning = 0, lookup = 0, speculate = 0;
     std::string mode = "chat", input, system_prompt;
     for (int i = 3; i < argc; ++i) {
         const std::string a = argv[i];
@@ -397,6 +416,7 @@ int main(int argc, char** argv) {
         else if (a == "-y" || a == "--system") { system_prompt = val(); have_system = true; }
         else if (a == "-r" || a == "--reasoning") reasoning = atol(val());
         else if (a == "--lookup") lookup = atol(val());
+        else if (a == "--speculate") speculate = atol(val());
         else {
             fprintf(stderr, "Error: unknown argument %s\n", a.c_str());
             usage();
@@ -412,6 +432,10 @@ int main(int argc, char** argv) {
                         "(speculative sampling is not implemented)\n");
         return 1;
     }
+    if (speculate != 0 && (lookup != 0 || speculate < 1 || speculate > Q3_VERIFY_MAX - 1)) {
+        fprintf(stderr, "Error: --speculate takes a draft length of 1..31 and cannot be combined with --lookup\n");
+        return 1;
+    }
     q3_engine* e = nullptr;
     if (q3_create(ckpt.c_str(), context > 0 ? (uint32_t)context : 0u, 0, 0u, &e) != Q3_OK) return fail_engine("cannot load the checkpoint");
     q3_config cfg;
@@ -424,8 +448,15 @@ int main(int argc, char** argv) {
     if (!have_seed) seed = (unsigned long long)time(nullptr);      // lib.rs: SystemTime seconds when no seed is given
     const float t = (float)(temperature < 0.0 ? 0.0 : temperature), p = (float)(topp < 0.0 ? 0.0 : (topp > 1.0 ? 1.0 : topp));
     if (q3_sampler_set(e, t, p, (uint64_t)seed) != Q3_OK) return fail_engine("sampler");
-    const int rc = mode == "generate" ? run_generate(e, tok, cfg.seq_len, have_input ? &input : nullptr, (int)lookup)
-                                      : run_chat(e, tok, cfg.seq_len, have_input ? &input : nullptr, have_system ? &system_prompt : nullptr, (int)lookup);
+    Lookup lk;
+    lk.draft_len = (int)(speculate ? speculate : lookup);
+    lk.draw = speculate != 0;
+    lk.temperature = t;
+    lk.topp = p;
+    lk.bos = tok.bos;
+    lk.eos = tok.eos;
+    const int rc = mode == "generate" ? run_generate(e, tok, cfg.seq_len, have_input ? &input : nullptr, lk)
+                                      : run_chat(e, tok, cfg.seq_len, have_input ? &input : nullptr, have_system ? &system_prompt : nullptr, lk);
     q3_destroy(e);
     return rc;
 }

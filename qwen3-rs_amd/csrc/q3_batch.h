@@ -2132,40 +2132,67 @@ __global__ __launch_bounds__(kWG) void k_spec_snapshot(State* st, const SpecIO* 
     }
 }
 
+// The argmax key of one classifier column: the last-maximum fold k_next_batch does over the column's slots, by one wave
+// (every lane returns the result).
+__device__ __forceinline__ unsigned long long spec_col_best(const unsigned long long* __restrict__ s, int nslots) {
+    const int lane = threadIdx.x & 63;
+    unsigned long long best = 0ull;
+    for (int i = lane; i < nslots; i += 64) best = s[i] > best ? s[i] : best;
+    for (int m = 1; m < 64; m <<= 1) {
+        const unsigned lo = __shfl_xor((unsigned)best, m);
+        const unsigned hi = __shfl_xor((unsigned)(best >> 32), m);
+        const unsigned long long o = ((unsigned long long)hi << 32) | lo;
+        best = o > best ? o : best;
+    }
+    return best;
+}
+
+// The accept walk, by one thread: draft j is accepted while it equals the token column j - 1 chose (next_of(j - 1): its argmax, or
+// its draw), and the single-stream state after n_accepted + 1 steps: token, position, step count, argmax cell (best_of(a): the
+// key of column a's largest logit) and the first n_accepted + 1 output tokens.  Returns n_accepted.
+template <class NextOf, class BestOf>
+__device__ __forceinline__ int spec_accept(SpecIO* io, NextOf&& next_of, BestOf&& best_of, State* est, int32_t* out_tokens, int out_cap) {
+    const int n_real = io->n_real;
+    int a = 0;
+    while (a + 1 < n_real && io->tokens[a + 1] == next_of(a)) ++a;
+    io->n_accepted = a;
+    for (int i = 0; i < n_real; ++i) {
+        const int idx = next_of(i);
+        io->next[i] = idx;
+        if (i <= a && i < out_cap) out_tokens[i] = idx;
+    }
+    est->token = next_of(a);
+    est->pos = io->first_pos + a + 1;
+    est->step = a + 1;
+    est->prompt_len = 0;
+    est->argmax = best_of(a);
+    return a;
+}
+
 // Behind the classifier, one workgroup: the argmax of every live column (the same last-maximum keys k_next_batch folds), the
 // accept walk (draft j is accepted while it equals the argmax of column j - 1), and the single-stream state after
-// n_accepted + 1 greedy steps: token, position, step count, argmax cell and the first n_accepted + 1 output tokens.
+// n_accepted + 1 greedy steps.
 __global__ __launch_bounds__(kWG) void k_spec_commit(SpecIO* io, const unsigned long long* __restrict__ slots, int slot_stride, int nslots,
                                                      State* est, int32_t* out_tokens, int out_cap) {
     __shared__ unsigned long long bests[kSpecMax];
     const int n_real = io->n_real, lane = threadIdx.x & 63;
     for (int col = threadIdx.x >> 6; col < n_real; col += kWaves) {
-        const unsigned long long* s = slots + (size_t)col * slot_stride;
-        unsigned long long best = 0ull;
-        for (int i = lane; i < nslots; i += 64) best = s[i] > best ? s[i] : best;
-        for (int m = 1; m < 64; m <<= 1) {
-            const unsigned lo = __shfl_xor((unsigned)best, m);
-            const unsigned hi = __shfl_xor((unsigned)(best >> 32), m);
-            const unsigned long long o = ((unsigned long long)hi << 32) | lo;
-            best = o > best ? o : best;
-        }
+        const unsigned long long best = spec_col_best(slots + (size_t)col * slot_stride, nslots);
         if (lane == 0) bests[col] = best;
     }
     __syncthreads();
-    if (threadIdx.x == 0) {
-        int a = 0;
-        while (a + 1 < n_real && io->tokens[a + 1] == (int)(unsigned)(bests[a] & 0xffffffffull)) ++a;
-        io->n_accepted = a;
-        for (int i = 0; i < n_real; ++i) {
-            const int idx = (int)(unsigned)(bests[i] & 0xffffffffull);
-            io->next[i] = idx;
-            if (i <= a && i < out_cap) out_tokens[i] = idx;
-        }
-        est->token = (int)(unsigned)(bests[a] & 0xffffffffull);
-        est->pos = io->first_pos + a + 1;
-        est->step = a + 1;
-        est->prompt_len = 0;
-        est->argmax = bests[a];
+    if (threadIdx.x == 0)
+        spec_accept(io, [&](int i) { return (int)(unsigned)(bests[i] & 0xffffffffull); }, [&](int i) { return bests[i]; }, est, out_tokens, out_cap);
+}
+
+// Sampled pass (q3_verify_draw): the same fold in front of the draws.  k_sample_exp takes the maximum of a column's logits from its
+// State::argmax, which the batched decode gets from k_next_batch; a verify plan runs no k_next_batch, so this launch puts the key
+// there for all n_plan columns (padding columns repeat the last live one: same logits, same key).
+__global__ __launch_bounds__(kWG) void k_spec_colmax(State* st, const unsigned long long* __restrict__ slots, int slot_stride, int nslots, int n_plan) {
+    const int lane = threadIdx.x & 63;
+    for (int col = threadIdx.x >> 6; col < n_plan; col += kWaves) {
+        const unsigned long long best = spec_col_best(slots + (size_t)col * slot_stride, nslots);
+        if (lane == 0) st[col].argmax = best;
     }
 }
 

@@ -6,7 +6,8 @@
 
 // what a BatchCtx's plan was built for.  Decode: n streams, each over its own KV cache.  Prefill: n positions of one sequence over
 // the engine's own KV cache, layers only (the classifier runs once, on the last position, through the single-stream launch).
-// Verify: the prefill layers between k_spec_snapshot and the n-column classifier + k_spec_commit + k_spec_restore.
+// Verify: the prefill layers between k_spec_snapshot and the n-column classifier + k_spec_commit + k_spec_restore; with the
+// sampler on (plan_draw), the per-column draws of the batched decode and k_spec_commit_draw stand in for k_spec_commit.
 enum class PlanKind { Decode, Prefill, Verify };
 
 struct BatchCtx {
@@ -33,10 +34,16 @@ struct BatchCtx {
     std::vector<Launch> plan;    // grids and the stream-tile count are baked in: rebuilt whenever plan_streams or plan_kind changes
     int plan_streams = 0;        // number of streams the plan / graph were built for
     PlanKind plan_kind = PlanKind::Decode;
+    bool plan_draw = false;      // Verify only: the plan samples every column (part of the plan key: sampler on / off)
     // draft verification (q3_verify / q3_generate_lookup)
     SpecIO* spec_io = nullptr;   // device: block input and result
     SpecIO* h_spec = nullptr;    // pinned staging of the same
     float* spec_snap = nullptr;  // key / value rows a rejected draft would leave behind, [2][layers][kSpecMax - 1][kv_dim]
+    // ... under the sampler (q3_verify_draw / q3_generate_lookup_draw): allocated by the first sampled pass (spec_draw_alloc)
+    SamplerState* spec_samp = nullptr;   // [kSpecMax] column sampler states
+    float *spec_probs = nullptr, *spec_sp = nullptr;
+    unsigned long long* spec_keys = nullptr;
+    SampleArgs spec_sargs{};
     size_t plan_head = 0;        // index of the first launch of the classifier tail (prefill blocks before the last skip it)
     bool has_kv = false;         // per-stream KV caches allocated (q3_batch_init); prefill-only contexts have none
     // per-stream device samplers (q3_batch_sampler_set)
@@ -136,7 +143,8 @@ void batch_free(q3_engine* e) {
     BatchCtx* b = e->batch;
     if (!b) return;
     void* dptrs[] = {b->att_pf, b->qn, b->pq, b->ps, b->x, b->q, b->kraw, b->xb, b->hb, b->logits, b->key, b->value, b->att, b->xq_p, b->xs_p,
-                     b->st, b->slots, b->out_tokens, b->stamps, b->d_sampler, b->d_probs, b->d_sp, b->d_keys, b->spec_io, b->spec_snap};
+                     b->st, b->slots, b->out_tokens, b->stamps, b->d_sampler, b->d_probs, b->d_sp, b->d_keys, b->spec_io, b->spec_snap,
+                     b->spec_samp, b->spec_probs, b->spec_sp, b->spec_keys};
     for (void* p : dptrs)
         if (p) (void)hipFree(p);
     if (b->h_st) (void)hipHostFree(b->h_st);
@@ -147,8 +155,8 @@ void batch_free(q3_engine* e) {
     e->batch = nullptr;
 }
 
-// (re)build the launch list for n streams (Decode) or n block positions (Prefill, Verify)
-int batch_build_plan(q3_engine* e, int n, PlanKind kind) {
+// (re)build the launch list for n streams (Decode) or n block positions (Prefill, Verify; draw: Verify under the sampler)
+int batch_build_plan(q3_engine* e, int n, PlanKind kind, bool draw = false) {
     BatchCtx* b = e->batch;
     const bool prefill = kind != PlanKind::Decode, verify = kind == PlanKind::Verify;
     const q3_config& c = e->cfg;
@@ -173,6 +181,7 @@ int batch_build_plan(q3_engine* e, int n, PlanKind kind) {
     b->plan.clear();
     b->plan_streams = n;
     b->plan_kind = kind;
+    b->plan_draw = draw;
     int rc;
     Launch Ln;
     // developer timeline: the cells of the launch about to be appended
@@ -183,6 +192,10 @@ int batch_build_plan(q3_engine* e, int n, PlanKind kind) {
         if ((rc = make_launch(Ln, F_NEXT, k_spec_snapshot, dim3(spec_grid), dim3(kWG), 0, b->st, b->spec_io, n, e->d_key, e->d_value, b->spec_snap,
                               L, c.seq_len, kvd))) return rc;
         b->plan.push_back(Ln);
+        if (draw) {
+            if ((rc = make_launch(Ln, F_NEXT, k_spec_sampler_states, dim3(1), dim3(64), 0, b->spec_io, n, e->d_sampler, b->spec_samp, b->st))) return rc;
+            b->plan.push_back(Ln);
+        }
     }
 
     auto quant = [&](Family fam, int pro, const float* in, long long in_stride, int nn, const float* norm_w) -> int {
@@ -420,7 +433,22 @@ int batch_build_plan(q3_engine* e, int n, PlanKind kind) {
         a.out0 = b->logits; a.out0_stride = V;
         if ((rc = gemm(F_LMHEAD, EPI_LOGITS, b->m_cls, a))) return rc;
     }
-    if (verify) {
+    if (verify && draw) {
+        // Sampler::sample of every column on the block's logits, exactly the batched decode's launches (one workgroup per column
+        // behind the element-wise passes spread over the chip), between the per-column maximum they read and the sampled commit
+        if ((rc = make_launch(Ln, F_NEXT, k_spec_colmax, dim3(1), dim3(kWG), 0, b->st, b->slots, b->nslots, b->nslots_used, n))) return rc;
+        b->plan.push_back(Ln);
+        if ((rc = make_launch(Ln, F_NEXT, k_sample_exp, dim3(64, (unsigned)n), dim3(256), 0, b->spec_sargs))) return rc;
+        b->plan.push_back(Ln);
+        if ((rc = make_launch(Ln, F_NEXT, k_sample, dim3((unsigned)n), dim3(kSampThreads), 4 * kSegFloats, b->spec_sargs))) return rc;
+        b->plan.push_back(Ln);
+        if ((rc = make_launch(Ln, F_NEXT, k_spec_commit_draw, dim3(1), dim3(64), 0, b->spec_io, b->st, b->spec_samp, e->d_state, e->d_sampler,
+                              e->d_out_tokens, e->out_cap))) return rc;
+        b->plan.push_back(Ln);
+        if ((rc = make_launch(Ln, F_NEXT, k_spec_restore, dim3(spec_grid), dim3(kWG), 0, b->spec_io, e->d_key, e->d_value, e->d_value_t, b->spec_snap,
+                              L, c.seq_len, kvd))) return rc;
+        b->plan.push_back(Ln);
+    } else if (verify) {
         if ((rc = make_launch(Ln, F_NEXT, k_spec_commit, dim3(1), dim3(kWG), 0, b->spec_io, b->slots, b->nslots, b->nslots_used, e->d_state,
                               e->d_out_tokens, e->out_cap))) return rc;
         b->plan.push_back(Ln);
@@ -807,15 +835,52 @@ int q3_batch_read_state(q3_engine* e, int stream, int kind, size_t offset, size_
 
 namespace {
 
+// Column sampler states and the draw scratch of up to kSpecMax columns (probs / sp / keys: ~5.3 MB per column at a 151,936-entry
+// vocabulary), allocated by the first pass that samples -- greedy users of the context never pay for it -- and freed with it.
+int spec_draw_alloc(q3_engine* e) {
+    BatchCtx* b = e->batch;
+    HIP_TRY(hipSetDevice(e->device));
+    const int n = e->cfg.vocab_size;
+    const int blen = 4 * ((n + 4095) / 4096);
+    size_t n2 = 1;
+    while (n2 < (size_t)n) n2 <<= 1;
+    const size_t scratch = (size_t)kSampThreads * blen;
+    HIP_TRY(hipMalloc((void**)&b->spec_samp, sizeof(SamplerState) * kSpecMax));
+    HIP_TRY(hipMemsetAsync(b->spec_samp, 0, sizeof(SamplerState) * kSpecMax, e->stream));
+    HIP_TRY(hipMalloc((void**)&b->spec_probs, 4 * scratch * kSpecMax));
+    HIP_TRY(hipMalloc((void**)&b->spec_sp, 4 * scratch * kSpecMax));
+    HIP_TRY(hipMalloc((void**)&b->spec_keys, 2 * 8 * n2 * kSpecMax));
+    SampleArgs a{};
+    a.logits = b->logits;
+    a.n = n;
+    a.blen = blen;
+    a.probs = b->spec_probs;
+    a.keys = b->spec_keys;
+    a.sp = b->spec_sp;
+    a.ss = b->spec_samp;
+    a.st = b->st;
+    a.out_tokens = e->d_out_tokens;      // never written: a column's State::step stays 0, and out_cap 0 closes the window
+    a.out_cap = 0;
+    a.sb_logits = n;
+    a.sb_scratch = (long long)scratch;
+    a.sb_keys = 2 * (long long)n2;
+    a.keys2_off = (long long)n2;
+    a.pre_exp = 1;
+    b->spec_sargs = a;
+    return Q3_OK;
+}
+
 // what every entry point of section 2c refuses, and the shared context (packed weights + block scratch, q3_prefill_batched's)
-int spec_prepare(q3_engine* e, const char* who) {
+// draw: the entry points of section 2d, which hold for any sampler setting
+int spec_prepare(q3_engine* e, const char* who, bool draw = false) {
     if (e->flags & Q3_FLAG_FAST)
         return fail(Q3_ERR_UNSUPPORTED, "%s needs a reference-order engine: with Q3_FLAG_FAST the block kernels and the single-stream kernels are not bit-equal, "
                     "so a verified token need not be the token the greedy loop produces", who);
-    if (e->sampling)
+    if (e->sampling && !draw)
         return fail(Q3_ERR_UNSUPPORTED, "%s is greedy only: the engine's sampler is set to a temperature > 0 (speculative sampling is not implemented)", who);
     int rc;
     if (!e->batch && (rc = batch_alloc(e, kMaxStreams, 0, false, prefill_block_cap(e)))) return rc;
+    if (e->sampling && !e->batch->spec_samp && (rc = spec_draw_alloc(e))) return rc;
     return Q3_OK;
 }
 
@@ -824,8 +889,8 @@ int spec_pass(q3_engine* e, const int32_t* tokens, int n_real, int n_plan, size_
     BatchCtx* b = e->batch;
     int rc;
     HIP_TRY(hipSetDevice(e->device));
-    if (b->plan_streams != n_plan || b->plan_kind != PlanKind::Verify)
-        if ((rc = batch_build_plan(e, n_plan, PlanKind::Verify))) return rc;
+    if (b->plan_streams != n_plan || b->plan_kind != PlanKind::Verify || b->plan_draw != e->sampling)
+        if ((rc = batch_build_plan(e, n_plan, PlanKind::Verify, e->sampling))) return rc;
     b->h_spec->first_pos = (int)first_pos;
     b->h_spec->n_real = n_real;
     for (int i = 0; i < kSpecMax; ++i) b->h_spec->tokens[i] = i < n_real ? tokens[i] : 0;
@@ -841,7 +906,12 @@ int spec_pass(q3_engine* e, const int32_t* tokens, int n_real, int n_plan, size_
 
 extern "C" {
 
-int q3_verify(q3_engine* e, const int32_t* tokens, size_t n_tokens, size_t first_pos, int32_t* next_tokens, size_t* n_accepted, float* logits_out) {
+}  // extern "C"
+
+namespace {
+
+int verify_block(q3_engine* e, const int32_t* tokens, size_t n_tokens, size_t first_pos, int32_t* next_tokens, size_t* n_accepted, float* logits_out,
+                 const char* who, bool draw) {
     g_err[0] = 0;
     if (!e || !tokens || !next_tokens || !n_accepted) return fail(Q3_ERR_ARG, "null argument");
     if (n_tokens == 0 || n_tokens > (size_t)kSpecMax) return fail(Q3_ERR_ARG, "n_tokens %zu out of range (1..%d)", n_tokens, kSpecMax);
@@ -851,12 +921,24 @@ int q3_verify(q3_engine* e, const int32_t* tokens, size_t n_tokens, size_t first
         if (tokens[i] < 0 || tokens[i] >= e->cfg.vocab_size)
             return fail(Q3_ERR_ARG, "index out of range: token %d (vocab_size %d)", tokens[i], e->cfg.vocab_size);
     int rc;
-    if ((rc = spec_prepare(e, "q3_verify"))) return rc;
+    if ((rc = spec_prepare(e, who, draw))) return rc;
     if ((rc = spec_pass(e, tokens, (int)n_tokens, (int)n_tokens, first_pos, logits_out))) return rc;
     const SpecIO* r = e->batch->h_spec;
     *n_accepted = (size_t)r->n_accepted;
     for (size_t i = 0; i < n_tokens; ++i) next_tokens[i] = r->next[i];
     return Q3_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int q3_verify(q3_engine* e, const int32_t* tokens, size_t n_tokens, size_t first_pos, int32_t* next_tokens, size_t* n_accepted, float* logits_out) {
+    return verify_block(e, tokens, n_tokens, first_pos, next_tokens, n_accepted, logits_out, "q3_verify", false);
+}
+
+int q3_verify_draw(q3_engine* e, const int32_t* tokens, size_t n_tokens, size_t first_pos, int32_t* next_tokens, size_t* n_accepted, float* logits_out) {
+    return verify_block(e, tokens, n_tokens, first_pos, next_tokens, n_accepted, logits_out, "q3_verify_draw", true);
 }
 
 size_t q3_lookup_draft(const int32_t* seq, size_t n, int ngram, int draft_len, int32_t* draft) {
@@ -878,8 +960,12 @@ int q3_lookup_trace(const int32_t* seq, size_t n, size_t n_corpus, int ngram, in
     return Q3_OK;
 }
 
-int q3_generate_lookup(q3_engine* e, const int32_t* corpus, size_t n_corpus, size_t first_token, size_t first_pos, size_t n_tokens, int ngram,
-                       int draft_len, int32_t* out_tokens, q3_spec_stats* stats) {
+}  // extern "C"
+
+namespace {
+
+int generate_lookup(q3_engine* e, const int32_t* corpus, size_t n_corpus, size_t first_token, size_t first_pos, size_t n_tokens, int ngram,
+                    int draft_len, int32_t* out_tokens, q3_spec_stats* stats, const char* who, bool draw) {
     g_err[0] = 0;
     if (stats) *stats = q3_spec_stats{0, 0, 0, 0};
     if (!e || (!out_tokens && n_tokens) || (!corpus && n_corpus)) return fail(Q3_ERR_ARG, "null argument");
@@ -891,7 +977,7 @@ int q3_generate_lookup(q3_engine* e, const int32_t* corpus, size_t n_corpus, siz
     if (first_pos + n_tokens > (size_t)e->cfg.seq_len)
         return fail(Q3_ERR_ARG, "first_pos %zu + n_tokens %zu exceeds seq_len %d", first_pos, n_tokens, e->cfg.seq_len);
     int rc;
-    if ((rc = spec_prepare(e, "q3_generate_lookup"))) return rc;
+    if ((rc = spec_prepare(e, who, draw))) return rc;
     HIP_TRY(hipSetDevice(e->device));
     q3_spec_stats st{0, 0, 0, 0};
     LookupIndex idx(ngram);
@@ -912,7 +998,7 @@ int q3_generate_lookup(q3_engine* e, const int32_t* corpus, size_t n_corpus, siz
         for (size_t k = 0; k < d; ++k)
             if (block[1 + k] < 0 || block[1 + k] >= e->cfg.vocab_size) { d = k; break; }
         if (d == 0) {
-            // no draft: an ordinary single-stream step through the decode graph
+            // no draft: an ordinary single-stream step through the decode graph (and, with the sampler on, its draw)
             if ((rc = e->set_state((size_t)cur, pos))) return rc;
             if ((rc = e->enqueue_forward(pos))) return rc;
             HIP_TRY(hipMemcpyAsync(e->h_tokens, e->d_out_tokens, 4, hipMemcpyDeviceToHost, e->stream));
@@ -938,6 +1024,20 @@ int q3_generate_lookup(q3_engine* e, const int32_t* corpus, size_t n_corpus, siz
     }
     if (stats) *stats = st;
     return Q3_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int q3_generate_lookup(q3_engine* e, const int32_t* corpus, size_t n_corpus, size_t first_token, size_t first_pos, size_t n_tokens, int ngram,
+                       int draft_len, int32_t* out_tokens, q3_spec_stats* stats) {
+    return generate_lookup(e, corpus, n_corpus, first_token, first_pos, n_tokens, ngram, draft_len, out_tokens, stats, "q3_generate_lookup", false);
+}
+
+int q3_generate_lookup_draw(q3_engine* e, const int32_t* corpus, size_t n_corpus, size_t first_token, size_t first_pos, size_t n_tokens, int ngram,
+                            int draft_len, int32_t* out_tokens, q3_spec_stats* stats) {
+    return generate_lookup(e, corpus, n_corpus, first_token, first_pos, n_tokens, ngram, draft_len, out_tokens, stats, "q3_generate_lookup_draw", true);
 }
 
 #ifdef Q3_DEV

@@ -12,6 +12,7 @@
 // leaves the order of EQUAL probabilities unspecified; the CPU restatement used by the tests makes the same choice.
 #pragma once
 #include "q3_kernels.h"
+#include "q3_batch.h"
 
 namespace q3 {
 
@@ -697,6 +698,38 @@ __global__ void k_rng_skip(SamplerState* ss, int count) {
         rs ^= rs >> 27;
     }
     ss->rng = rs;
+}
+
+// ---- draft verification under the sampler (q3_verify_draw / q3_generate_lookup_draw, q3_batch.h): column i of a verify block is
+// drawn by the per-stream k_sample_exp / k_sample of the batched decode with a sampler state of its own.
+// Behind k_spec_snapshot, one workgroup: column i gets the engine's temperature / top-p as they are NOW (a later q3_sampler_set
+// needs no new plan) and the engine's rng advanced i coins -- the state the sequential loop has in front of its draw at position
+// first_pos + i; k_sample takes the next coin itself (sampler.rs:44-54).  Columns past n_real are marked as discarded draws
+// (State::prompt_len: k_sample_exp and k_sample return at once), their logits repeat the last live column's.
+__global__ void k_spec_sampler_states(const SpecIO* __restrict__ io, int n_plan, const SamplerState* __restrict__ es, SamplerState* cs, State* st) {
+    const int i = threadIdx.x;
+    if (i >= n_plan) return;
+    const int n_real = io->n_real, coins = i < n_real ? i : n_real - 1;
+    SamplerState s = *es;
+    unsigned long long rs = s.rng;
+    for (int k = 0; k < coins; ++k) {
+        rs ^= rs >> 12;
+        rs ^= rs << 25;
+        rs ^= rs >> 27;
+    }
+    s.rng = rs;
+    cs[i] = s;
+    if (i >= n_real) st[i].prompt_len = 1;
+}
+
+// Behind the draws, one thread: the accept walk over the drawn tokens (k_sample left column i's in its State::token), the
+// single-stream state after n_accepted + 1 sampled steps, and the engine's rng = column a's after its draw: a + 1 coins past the
+// entry state, the draws behind a rejection not consumed.
+__global__ void k_spec_commit_draw(SpecIO* io, const State* __restrict__ st, const SamplerState* __restrict__ cs, State* est, SamplerState* es,
+                                   int32_t* out_tokens, int out_cap) {
+    if (threadIdx.x != 0) return;
+    const int a = spec_accept(io, [&](int i) { return st[i].token; }, [&](int i) { return st[i].argmax; }, est, out_tokens, out_cap);
+    es->rng = cs[a].rng;
 }
 
 }  // namespace q3

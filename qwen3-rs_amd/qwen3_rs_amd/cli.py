@@ -2,7 +2,7 @@
 
     python -m qwen3_rs_amd.cli export <MODEL_PATH> <OUTPUT_PATH> [--group-size 64]
     python -m qwen3_rs_amd.cli inference <checkpoint> [-t 1.0] [-p 0.9] [-s SEED] [-c CTX] [-m generate|chat]
-                                         [-i INPUT] [-y SYSTEM] [-r 0|1] [--lookup DRAFT_LEN]
+                                         [-i INPUT] [-y SYSTEM] [-r 0|1] [--lookup DRAFT_LEN] [--speculate DRAFT_LEN]
 
 `inference` follows generation.rs: `generate` echoes the prompt and decodes from its last token over a zero KV prefix
 (:9-48); `chat` renders the template, forwards every prompt token (one rng coin each) and decodes until BOS/EOS
@@ -10,6 +10,8 @@
 (q3_prefill, q3_forward_sample); the host only tokenizes, prints and checks for the termination tokens.
 `--lookup N` (greedy only, -t 0) decodes through q3_generate_lookup: up to N tokens drafted from the text so far (the latest
 earlier occurrence of the last two tokens) are checked in one pass over the weights; the output is the same, byte for byte.
+`--speculate N` does the same at any temperature through q3_generate_lookup_draw: a draft is accepted exactly when it is the
+token the sampler draws, so the output is again the same, byte for byte.
 """
 from __future__ import annotations
 
@@ -38,18 +40,24 @@ def _out(raw: bytes):
 LOOKUP_NGRAM = 2
 
 
-def _lookup_round(t, history, pos: int, seq_len: int, lookup: int):
-    """one round of up to lookup + 1 greedy tokens: history[-1] is forwarded at pos, everything before it is the corpus"""
+def _lookup_round(t, history, pos: int, seq_len: int, lookup: int, stop=None):
+    """one round of up to lookup + 1 greedy tokens: history[-1] is forwarded at pos, everything before it is the corpus.
+    stop (--speculate): the round is drawn by the device sampler and ends with the first of these tokens, no coin drawn behind it"""
+    if stop is not None:
+        toks, _ = t.generate_lookup_draw(history[:-1], history[-1], pos, min(lookup + 1, seq_len - pos), ngram=LOOKUP_NGRAM,
+                                         draft_len=lookup, stop_tokens=stop)
+        return toks
     toks, _ = t.generate_lookup(history[:-1], history[-1], pos, min(lookup + 1, seq_len - pos), ngram=LOOKUP_NGRAM, draft_len=lookup)
     return toks
 
 
-def run_generate(t, tok: Tokenizer, prompt: str, lookup: int = 0) -> int:
+def run_generate(t, tok: Tokenizer, prompt: str, lookup: int = 0, speculate: bool = False) -> int:
     """generation.rs:9-48"""
     prompt_tokens = tok.encode(prompt or "")
     if not prompt_tokens:
         raise SystemExit("Please provide a prompt")
     seq_len = t.get_config().seq_len
+    stop = (tok.bos_token_id, tok.eos_token_id) if speculate else None
     for p in prompt_tokens[:-1][:seq_len]:                 # echoed, never forwarded (zero KV prefix)
         _emit(tok, p)
     token, pos, n_gen, t0 = prompt_tokens[-1], len(prompt_tokens) - 1, 0, None
@@ -59,7 +67,7 @@ def run_generate(t, tok: Tokenizer, prompt: str, lookup: int = 0) -> int:
             t0 = time.perf_counter()
         if lookup:                                         # a round of tokens per call, handed out one by one
             if not pending:
-                pending = _lookup_round(t, history, pos, seq_len, lookup)
+                pending = _lookup_round(t, history, pos, seq_len, lookup, stop)
             nxt = pending.pop(0)
             history.append(nxt)
         else:
@@ -92,11 +100,12 @@ def _prefill(t, ids, pos) -> int:
     return t.prefill(ids, pos)
 
 
-def run_chat(t, tok: Tokenizer, cli_prompt, system_prompt, lookup: int = 0) -> int:
+def run_chat(t, tok: Tokenizer, cli_prompt, system_prompt, lookup: int = 0, speculate: bool = False) -> int:
     """generation.rs:50-151, loop for loop: when the window is exhausted the position goes back to 0 and a user turn begins
     (generation.rs:65-69) -- the KV cache is NOT cleared, rows are simply rewritten from the front, and with a `-i` prompt
     the prompt is fed again exactly as the reference does (get_user_input, generation.rs:174-188)."""
     seq_len = t.get_config().seq_len
+    stop = (tok.bos_token_id, tok.eos_token_id) if speculate else None
     pos, user_turn, nxt = 0, True, 0
     n_gen, t0 = 0, None
     history, pending = [], []                              # --lookup: the window's tokens so far, tokens of the current round
@@ -135,7 +144,7 @@ def run_chat(t, tok: Tokenizer, cli_prompt, system_prompt, lookup: int = 0) -> i
             _emit(tok, nxt)
             if lookup and history:
                 if not pending:                            # (rows a round writes past a turn's end are rewritten before they are read)
-                    pending = _lookup_round(t, history, pos, seq_len, lookup)
+                    pending = _lookup_round(t, history, pos, seq_len, lookup, stop)
                 nxt = pending.pop(0)
                 history.append(nxt)
             else:
@@ -164,6 +173,8 @@ def main(argv=None) -> int:
     inf.add_argument("-r", "--reasoning", type=int, default=0)
     inf.add_argument("--lookup", type=int, default=0, metavar="DRAFT_LEN",
                      help="greedy only (-t 0): draft up to DRAFT_LEN (1..31) tokens per weight pass by prompt lookup; 0 = off")
+    inf.add_argument("--speculate", type=int, default=0, metavar="DRAFT_LEN",
+                     help="any -t: the same drafts, each accepted exactly when it is the token the sampler draws; same output; 0 = off")
     a = ap.parse_args(argv)
     if a.cmd == "export":
         if not os.path.isdir(a.MODEL_PATH):
@@ -194,6 +205,9 @@ def main(argv=None) -> int:
             print("Error: --lookup takes a draft length of 1..31 and needs -t 0: speculative decoding is greedy only "
                   "(speculative sampling is not implemented)", file=sys.stderr)
             return 1
+        if a.speculate and (a.lookup or not 0 < a.speculate < 32):
+            print("Error: --speculate takes a draft length of 1..31 and cannot be combined with --lookup", file=sys.stderr)
+            return 1
         b = TransformerBuilder(a.checkpoint)
         if a.context:
             b = b.with_ctx_length(a.context)
@@ -202,8 +216,8 @@ def main(argv=None) -> int:
             seed = a.seed if a.seed is not None else int(time.time())      # lib.rs: SystemTime seconds when no seed is given
             t.set_sampler(max(a.temperature, 0.0), min(max(a.topp, 0.0), 1.0), seed)
             if a.mode == "generate":
-                return run_generate(t, tok, a.input, a.lookup)
-            return run_chat(t, tok, a.input, a.system, a.lookup)
+                return run_generate(t, tok, a.input, a.lookup or a.speculate, bool(a.speculate))
+            return run_chat(t, tok, a.input, a.system, a.lookup or a.speculate, bool(a.speculate))
     ap.print_help()
     return 1
 

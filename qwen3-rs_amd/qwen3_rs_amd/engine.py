@@ -25,6 +25,7 @@ EXPORTED_SYMBOLS = [
     "q3_abi_version", "q3_build_id", "q3_op_quantize", "q3_op_dequantize", "q3_op_matmul", "q3_op_rmsnorm", "q3_op_softmax",
     "q3_op_swiglu", "q3_op_expf", "q3_op_attention", "q3_op_argmax", "q3_op_sample", "q3_op_gemv_role",
     "q3_verify", "q3_lookup_draft", "q3_lookup_trace", "q3_generate_lookup",
+    "q3_verify_draw", "q3_generate_lookup_draw",
 ]
 VERIFY_MAX = 32          # Q3_VERIFY_MAX
 
@@ -172,10 +173,12 @@ def _bind(path: str) -> C.CDLL:
     L.q3_batch_reset_kv.argtypes = [C.c_void_p]
     L.q3_batch_read_state.argtypes = [C.c_void_p, C.c_int, C.c_int, sz, sz, fp]
     L.q3_verify.argtypes = [C.c_void_p, i32p, sz, sz, i32p, C.POINTER(sz), fp]
+    L.q3_verify_draw.argtypes = L.q3_verify.argtypes
     L.q3_lookup_draft.argtypes = [i32p, sz, C.c_int, C.c_int, i32p]
     L.q3_lookup_draft.restype = sz
     L.q3_lookup_trace.argtypes = [i32p, sz, sz, C.c_int, C.c_int, i32p, i32p]
     L.q3_generate_lookup.argtypes = [C.c_void_p, i32p, sz, sz, sz, sz, C.c_int, C.c_int, i32p, C.POINTER(_SpecStats)]
+    L.q3_generate_lookup_draw.argtypes = L.q3_generate_lookup.argtypes
     L.q3_profile.argtypes = [C.c_void_p, sz, sz, C.c_int, fp, C.POINTER(C.c_int32), C.c_int]
     L.q3_profile_name.argtypes = [C.c_int]
     L.q3_profile_name.restype = C.c_char_p
@@ -239,6 +242,7 @@ class Transformer:
         cfg = _Config()
         _check(lib.q3_get_config(self._h, C.byref(cfg)))
         self._config = ModelConfig._from_c(cfg)
+        self._sampler = None                     # (temperature, topp) of the last set_sampler
 
     # -- the reference surface ------------------------------------------------------------------
     def forward(self, token: int, pos: int) -> np.ndarray:
@@ -312,12 +316,21 @@ class Transformer:
         """One weight pass over tokens (tokens[0] certain, the rest drafts) at first_pos..: returns (next_tokens, n_accepted) or,
         with want_logits, (next_tokens, n_accepted, logits [n, vocab]).  next_tokens[:n_accepted + 1] are the greedy tokens and
         the engine is left as generate_greedy(tokens[0], first_pos, n_accepted + 1) leaves it."""
+        return self._verify(self._lib.q3_verify, tokens, first_pos, want_logits)
+
+    def verify_draw(self, tokens, first_pos: int, want_logits: bool = False):
+        """verify() under the device sampler (q3_verify_draw, section 2d): next_tokens[i] is the sampler's draw on column i with
+        the rng i coins past its state at entry; the engine and the rng are left as generate_sampled(tokens[0], first_pos,
+        n_accepted + 1) leaves them.  With temperature 0 it is verify()."""
+        return self._verify(self._lib.q3_verify_draw, tokens, first_pos, want_logits)
+
+    def _verify(self, fn, tokens, first_pos: int, want_logits: bool):
         n = len(tokens)
         nxt = (C.c_int32 * max(1, n))()
         acc = C.c_size_t(0)
         logits = np.zeros((n, self._config.vocab_size), dtype=np.float32) if want_logits else None
         lp = logits.ctypes.data_as(C.POINTER(C.c_float)) if want_logits else None
-        rc = self._lib.q3_verify(self._h, _i32_array(tokens), n, first_pos, nxt, C.byref(acc), lp)
+        rc = fn(self._h, _i32_array(tokens), n, first_pos, nxt, C.byref(acc), lp)
         if rc == -3:
             raise IndexError(self._lib.q3_last_error().decode(errors="replace"))
         _check(rc)
@@ -327,10 +340,35 @@ class Transformer:
     def generate_lookup(self, corpus, first_token: int, first_pos: int, n_tokens: int, ngram: int = 2, draft_len: int = 8):
         """generate_greedy with prompt-lookup drafts (q3_generate_lookup): the same tokens and engine state in fewer weight
         passes.  corpus: the tokens to look continuations up in (the prompt).  Returns (tokens, SpecStats)."""
+        return self._generate_lookup(self._lib.q3_generate_lookup, corpus, first_token, first_pos, n_tokens, ngram, draft_len)
+
+    def generate_lookup_draw(self, corpus, first_token: int, first_pos: int, n_tokens: int, ngram: int = 2, draft_len: int = 8,
+                             stop_tokens=()):
+        """generate_sampled with prompt-lookup drafts (q3_generate_lookup_draw, section 2d): a draft is accepted exactly when it
+        is the token the sampler draws, so tokens, engine state and final rng equal generate_sampled's at any temperature.
+        Returns (tokens, SpecStats).
+        stop_tokens: a loop that ends at a stop token never draws behind it, a call of n_tokens does.  With stop_tokens the
+        returned tokens end with the first stop token and the rng is put back to where that token's draw left it, so whatever
+        is sampled next is what the token-by-token loop would sample (cache rows written behind it are rewritten before they
+        are read, as after any shorter call)."""
+        coins = bool(stop_tokens) and self._sampler is not None and self._sampler[0] > 0.0
+        rng = self.sampler_rng_state() if coins else 0
+        toks, stats = self._generate_lookup(self._lib.q3_generate_lookup_draw, corpus, first_token, first_pos, n_tokens, ngram, draft_len)
+        k = next((i for i, t in enumerate(toks) if t in stop_tokens), None)
+        if k is not None:
+            if coins and k + 1 < len(toks):
+                for _ in range(k + 1):                    # sampler.rs:44-49
+                    rng ^= rng >> 12
+                    rng = (rng ^ (rng << 25)) & 0xFFFFFFFFFFFFFFFF
+                    rng ^= rng >> 27
+                self.set_sampler(self._sampler[0], self._sampler[1], rng)
+            toks = toks[:k + 1]
+        return toks, stats
+
+    def _generate_lookup(self, fn, corpus, first_token: int, first_pos: int, n_tokens: int, ngram: int, draft_len: int):
         buf = (C.c_int32 * max(1, n_tokens))()
         st = _SpecStats()
-        rc = self._lib.q3_generate_lookup(self._h, _i32_array(corpus), len(corpus), first_token, first_pos, n_tokens, ngram, draft_len,
-                                          buf, C.byref(st))
+        rc = fn(self._h, _i32_array(corpus), len(corpus), first_token, first_pos, n_tokens, ngram, draft_len, buf, C.byref(st))
         if rc == -3:
             raise IndexError(self._lib.q3_last_error().decode(errors="replace"))
         _check(rc)
@@ -340,6 +378,7 @@ class Transformer:
         """Sampler::new (sampler.rs:29-42) on the device: subsequent forward_argmax / generate_greedy / prefill calls draw
         with Sampler::sample; temperature 0 restores greedy decoding."""
         _check(self._lib.q3_sampler_set(self._h, temperature, topp, rng_seed))
+        self._sampler = (temperature, topp)
 
     def sampler_rng_state(self) -> int:
         out = C.c_uint64(0)

@@ -42,10 +42,12 @@ class TokenMetrics:
         return self.generated_count, self.elapsed, tps
 
 
-def _lookup_decode(transformer, history: List[int], pos: int, budget: int, stop, lookup, metrics, out: List[int], stop_first: bool):
+def _lookup_decode(transformer, history: List[int], pos: int, budget: int, stop, lookup, metrics, out: List[int], stop_first: bool,
+                   draw: bool = False):
     """The greedy decode of both call patterns through Transformer.generate_lookup (q3_generate_lookup) with everything seen so
     far as the corpus: rounds of draft_len + 1 tokens, so a caller sees tokens pass by pass.  history[-1] is the token to forward
     at pos.  stop_first: chat's order (a stop token ends the turn before it is output); else generate's (it is output, then ends).
+    draw: the device sampler's decode at any temperature through Transformer.generate_lookup_draw (speculate=).
     Returns the next position."""
     ngram, draft_len = lookup
     while budget > 0:
@@ -53,7 +55,10 @@ def _lookup_decode(transformer, history: List[int], pos: int, budget: int, stop,
             break
         n = min(budget, draft_len + 1)
         metrics.start_generation()
-        toks, _ = transformer.generate_lookup(history[:-1], history[-1], pos, n, ngram=ngram, draft_len=draft_len)
+        if draw:
+            toks, _ = transformer.generate_lookup_draw(history[:-1], history[-1], pos, n, ngram=ngram, draft_len=draft_len, stop_tokens=stop)
+        else:
+            toks, _ = transformer.generate_lookup(history[:-1], history[-1], pos, n, ngram=ngram, draft_len=draft_len)
         for i, nxt in enumerate(toks):
             if stop_first:
                 out.append(history[-1])
@@ -76,24 +81,40 @@ def _check_lookup(lookup, sample, on_logits):
         raise ValueError("lookup=(ngram >= 1, 0 < draft_len < 32)")
 
 
+def _check_speculate(speculate, lookup, sample, on_logits):
+    if lookup is not None or sample is not sample_argmax or on_logits is not None:
+        raise ValueError("speculate= decodes with the device sampler (Transformer.set_sampler): no lookup= / sample= / on_logits=")
+    ngram, draft_len = speculate
+    if ngram < 1 or not 0 < draft_len < 32:
+        raise ValueError("speculate=(ngram >= 1, 0 < draft_len < 32)")
+
+
 def generate(transformer, prompt_tokens: Sequence[int], max_new_tokens: Optional[int] = None,
              stop_tokens: Iterable[int] = (), sample: Callable[[np.ndarray], int] = sample_argmax,
-             on_logits: Optional[Callable[[int, int, np.ndarray], None]] = None, lookup: Optional[Tuple[int, int]] = None):
+             on_logits: Optional[Callable[[int, int, np.ndarray], None]] = None, lookup: Optional[Tuple[int, int]] = None,
+             speculate: Optional[Tuple[int, int]] = None):
     """`generate` (generation.rs:9-48).  Prompt tokens 0..n-2 never reach forward(): the first call is
     forward(prompt[n-1], n-1) over a zero KV prefix.  Returns (generated tokens incl. a terminating one,
-    TokenMetrics).  max_new_tokens bounds the loop (the reference only stops at seq_len / BOS / EOS)."""
+    TokenMetrics).  max_new_tokens bounds the loop (the reference only stops at seq_len / BOS / EOS).
+    speculate=(ngram, draft_len): every token is drawn on the device by the sampler of Transformer.set_sampler (any temperature;
+    argmax when none is set), several per weight pass where prompt-lookup drafts are accepted -- a draft is accepted exactly when
+    it is the token the sampler draws, so the tokens are those of this loop with `sample` = the same Sampler."""
     if len(prompt_tokens) == 0:
         raise ValueError("Please provide a prompt")
     stop = set(stop_tokens)
     seq_len = transformer.get_config().seq_len
     metrics = TokenMetrics()
     out: List[int] = []
-    if lookup is not None:
+    if lookup is not None or speculate is not None:
         # lookup=(ngram, draft_len): the same tokens through prompt-lookup speculative decoding, the prompt as corpus
-        _check_lookup(lookup, sample, on_logits)
+        if speculate is not None:
+            _check_speculate(speculate, lookup, sample, on_logits)
+        else:
+            _check_lookup(lookup, sample, on_logits)
         pos = len(prompt_tokens) - 1
         budget = max(seq_len - pos, 0) if max_new_tokens is None else min(max(seq_len - pos, 0), max_new_tokens)
-        _lookup_decode(transformer, [int(t) for t in prompt_tokens], pos, budget, stop, lookup, metrics, out, False)
+        _lookup_decode(transformer, [int(t) for t in prompt_tokens], pos, budget, stop, speculate or lookup, metrics, out, False,
+                       draw=speculate is not None)
         metrics.report()
         return out, metrics
     pos, token = 0, prompt_tokens[0]
@@ -120,13 +141,28 @@ def generate(transformer, prompt_tokens: Sequence[int], max_new_tokens: Optional
 
 def chat_turn(transformer, prompt_tokens: Sequence[int], pos: int, max_new_tokens: int,
               stop_tokens: Iterable[int] = (), sample: Callable[[np.ndarray], int] = sample_argmax,
-              on_logits: Optional[Callable[[int, int, np.ndarray], None]] = None, lookup: Optional[Tuple[int, int]] = None):
+              on_logits: Optional[Callable[[int, int, np.ndarray], None]] = None, lookup: Optional[Tuple[int, int]] = None,
+              speculate: Optional[Tuple[int, int]] = None):
     """One user turn + assistant turn of `chat` (generation.rs:94-151): every prompt token goes through
     forward() one at a time (sequential prefill, a sample drawn and discarded for each), then decode until
-    a stop token.  Returns (generated tokens, next pos, TokenMetrics)."""
+    a stop token.  Returns (generated tokens, next pos, TokenMetrics).
+    speculate=(ngram, draft_len): the turn on the device under the sampler of Transformer.set_sampler -- the prompt through
+    Transformer.prefill (which draws and discards the per-prompt coins itself), the assistant turn as in generate(speculate=)."""
     stop = set(stop_tokens)
     seq_len = transformer.get_config().seq_len
     next_token = 0
+    if speculate is not None:
+        _check_speculate(speculate, lookup, sample, on_logits)
+        metrics = TokenMetrics()
+        out: List[int] = []
+        ids = [int(t) for t in prompt_tokens][: max(seq_len - pos, 0)]
+        if ids:
+            next_token = transformer.prefill(ids, pos)
+            pos += len(ids)
+            pos = _lookup_decode(transformer, ids + [int(next_token)], pos, min(max_new_tokens, max(seq_len - pos, 0)), stop, speculate,
+                                 metrics, out, True, draw=True)
+        metrics.report()
+        return out, pos, metrics
     for tok in prompt_tokens:                       # handle_user_turn, generation.rs:116-123
         if pos >= seq_len:
             break

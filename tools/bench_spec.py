@@ -10,7 +10,10 @@ Every model is measured in a child process of its own under a time limit (one fa
     step time - 1;
   * tok/s with every draft right (q3_verify fed the greedy tokens in blocks of 32), of q3_generate_lookup with ngram 64 (never a
     draft: the price of one host read-back per token against the device-resident loop) and of self-lookup at ngram 2 / 3 with
-    the simulated acceptance beside it.
+    the simulated acceptance beside it;
+  * under the sampler (section 2d; temperature 1.0, top-p 0.9, the reference's defaults): q3_generate_sampled tok/s (untouched by
+    section 2d: the yardstick of these rows) and the time of one q3_verify_draw pass for n in {2, 8, 32} at position ~64 with every
+    draft right, and its break-even accepted drafts = pass time / sampled step time - 1.
 Synthetic checkpoints fall into cycles under greedy decoding, which flatters self-lookup and says nothing about trained weights:
 read the pass costs and break-even counts, not the self-lookup speed-up.  Writes <out>/spec_decode.json and spec_decode.md.
 """
@@ -107,6 +110,34 @@ def worker(name, ctx, ckpt_dir, seed):
             assert (st.verify_passes, st.single_steps, st.drafted, st.accepted) == (sim["verify_passes"], sim["single_steps"], sim["drafted"], sim["accepted"])
             res["lookup"][label] = {"tok_s": n_run / median(ts), "verify_passes": st.verify_passes, "single_steps": st.single_steps,
                                     "drafted": st.drafted, "accepted": st.accepted, "distinct_tokens": len(set(G[:n_run])), "tokens": n_run}
+    # section 2d: the same pass with every column drawn by the device sampler, against the sampled single-stream step
+    T, topp, seed, p = 1.0, 0.9, 42, 64
+    with build() as t:
+        t.set_sampler(T, topp, seed)
+        GS = t.generate_greedy(tok0, 0, N)                              # q3_generate_sampled: warm-up + the reference tokens
+        times = []
+        for _ in range(3):
+            t.set_sampler(T, topp, seed)
+            t0 = time.perf_counter()
+            assert t.generate_greedy(tok0, 0, N) == GS
+            times.append(time.perf_counter() - t0)
+        sstep_ms = 1e3 * median(times) / N
+        res["draw"] = {"temperature": T, "topp": topp, "sampled_tok_s": N / median(times), "sampled_step_ms": sstep_ms, "verify_ms": {}}
+        t.set_sampler(T, topp, seed)
+        t.generate_greedy(tok0, 0, p)
+        rng_p = t.sampler_rng_state()                                   # the seed IS the state: every repeat draws the same coins
+        seq = [GS[p - 1]] + GS[p:p + 40]
+        for n in (2, 8, 32):
+            t.verify_draw(seq[:n], p)                                   # scratch, plan + warm-up
+            ts = []
+            for _ in range(20):
+                t.set_sampler(T, topp, rng_p)
+                t0 = time.perf_counter()
+                _, a = t.verify_draw(seq[:n], p)
+                ts.append(time.perf_counter() - t0)
+            assert a == n - 1
+            ms = 1e3 * median(ts)
+            res["draw"]["verify_ms"][f"graph/pos{p}/n{n}"] = {"ms": ms, "break_even_accepted": ms / sstep_ms - 1.0}
     print("BENCH_SPEC " + json.dumps(res), flush=True)
 
 
@@ -156,6 +187,13 @@ def main():
         md += [f"| {k} | {v['tok_s']:.1f} | {v['verify_passes']} | {v['single_steps']} | {v['drafted']} | {v['accepted']} | {v['distinct_tokens']} / {v['tokens']} |"
                for k, v in r["lookup"].items()]
         md.append("")
+        if "draw" in r:
+            d = r["draw"]
+            md += [f"under the sampler (temperature {d['temperature']}, top-p {d['topp']}): {d['sampled_tok_s']:.1f} tok/s "
+                   f"({d['sampled_step_ms']:.3f} ms per sampled step)", "",
+                   "| sampled pass (every draft right) | ms | break-even accepted drafts |", "|---|---|---|"]
+            md += [f"| {k} | {v['ms']:.3f} | {v['break_even_accepted']:.2f} |" for k, v in d["verify_ms"].items()]
+            md.append("")
     with open(os.path.join(a.out, "spec_decode.md"), "w") as f:
         f.write("\n".join(md))
     print(json.dumps({"models": [r["model"] for r in results], "out": a.out}))
