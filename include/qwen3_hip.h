@@ -367,6 +367,67 @@ int q3_verify_draw(q3_engine* e, const int32_t* tokens, size_t n_tokens, size_t 
 int q3_generate_lookup_draw(q3_engine* e, const int32_t* corpus, size_t n_corpus, size_t first_token, size_t first_pos, size_t n_tokens,
                             int ngram, int draft_len, int32_t* out_tokens, q3_spec_stats* stats);
 
+/* ------------------------------------------------------------------------------------------------
+ * 2e. (behind 2d so that the earlier sections stay as they were.)  Ragged column passes over the batched state of section 2b:
+ * every column of a pass is a (slot, token, position) triple, so one pass over the packed weights can hold decode columns of
+ * some streams next to several consecutive prompt positions of others.  This is what chunked prompts, slot reuse and serving
+ * more requests than slots need; section 2b's "stream i uses KV slot i, one position per stream" is the special case
+ * slots = 0 .. n - 1.  The layers are the short block's of q3_prefill_batched (all key and value rows of the pass enter the
+ * caches before any column attends) with every column's cache base taken from a slot table; the classifier is the n-column
+ * one of the batched decode.  The standard is section 2b's: logits and cache rows are bit-identical to feeding the slot's
+ * token history through q3_forward on a fresh engine of the same context.  Greedy only.
+ * ------------------------------------------------------------------------------------------------ */
+#define Q3_COLS_MAX 32
+
+/* One pass of n_cols (1 .. Q3_COLS_MAX) columns: column j runs forward(tokens[j], pos[j]) over the KV cache of slot slots[j].
+ * The columns of one slot form a RUN: they are adjacent, their positions are consecutive and ascending, and a slot has at most
+ * one run in a pass.  Column j of a run sees the rows the run's earlier columns write in the same pass; like q3_forward, a
+ * column reads rows 0 .. pos[j] of its slot and nothing else, so a slot need not be cleared between two sequences.
+ * next_out[j] = sample_argmax of column j; logits_out row j = its logits.  Each may be NULL.
+ * A pass of n_cols columns runs a plan of the next width in {1, 2, 4, 8, 16, 32}, the columns past n_cols repeating the last
+ * one (same slot, token and position: the same bits to the same rows); the plans are built on first use and kept, so passes
+ * of changing width rebuild nothing, and neither do calls of section 2b in between after their first.
+ * Q3_ERR_ARG: no q3_batch_init; n_cols outside 1 .. Q3_COLS_MAX; a slot outside 0 .. max_streams - 1; a slot in two runs; a run
+ * whose positions are not consecutive; a token outside the vocabulary; a position >= the batch context.
+ * Q3_ERR_UNSUPPORTED: a Q3_FLAG_FAST engine (its block and decode kernels are not bit-equal to each other, as in section 2c);
+ * a batch sampler set to a temperature > 0 (q3_batch_sampler_set); the shapes the short prefill block refuses ("needs the
+ * per-kv-head attention kernel"). */
+int q3_batch_step_cols(q3_engine* e, const int32_t* slots, const int32_t* tokens, const int32_t* pos, int n_cols,
+                       float* logits_out /* [n_cols][vocab] or NULL */, int32_t* next_out /* [n_cols] or NULL */);
+
+typedef struct q3_cols_stats { uint64_t passes, live_columns, prompt_columns, decode_columns; } q3_cols_stats;
+
+/* The pass table q3_generate_many_greedy runs, as a pure function of the lengths (host only, never touches the GPU).  Request r
+ * has a prompt of prompt_len[r] >= 1 tokens and wants n_new[r] >= 1 tokens.  A slot holding a request is in its PROMPT phase
+ * until the last prompt token has been through a pass and in its DECODE phase afterwards.  Pass after pass, until no request is
+ * queued or held:
+ *   1. Admit.  While a slot is free and requests are queued, the next request, in ascending index, takes the lowest free slot.
+ *   2. Decode columns first: one column per decode-phase slot, in ascending slot order; its token is the slot's last produced
+ *      token, its position prompt_len + g - 1 with g tokens produced so far.
+ *   3. Prompt columns fill the rest of the Q3_COLS_MAX columns: prompt-phase slots in ascending slot order, each taking
+ *      min(remaining prompt, remaining columns) consecutive positions (a slot that finds no column left waits).
+ *   4. A run that reaches its prompt's last token produces y_0 in that pass; the slot decodes from the next pass.
+ *   5. A request that has produced n_new tokens frees its slot for the next pass.
+ * (A prompt-phase slot at the front always gets a column: it holds a slot itself, so at most 31 slots decode beside it.)
+ * table (may be NULL: count only): one entry {pass, slot, position, request} per column, passes ascending, columns in pass
+ * order; *n_entries = the number of columns whether or not they fit; stats as for the loop.  n_entries, stats may be NULL.
+ * Q3_ERR_ARG: no request, a prompt_len or n_new of 0, max_streams outside 1 .. 32, a table smaller than the schedule. */
+int q3_cols_schedule(const size_t* prompt_len, const size_t* n_new, size_t n_requests, int max_streams,
+                     int32_t* table /* [cap][4]: pass, slot, pos, request */, size_t cap, size_t* n_entries, q3_cols_stats* stats);
+
+/* n_requests greedy generations through the max_streams slots of the batched state, by the schedule above.  Request r yields
+ * y_0 .. y_{n_new[r] - 1} at out_tokens[n_new[0] + .. + n_new[r - 1] ..]: y_0 = q3_prefill(prompt_r, 0) and the rest
+ * q3_generate_greedy(y_0, prompt_len[r], n_new[r] - 1), both on a fresh engine -- bit-identical whatever else shares its passes
+ * and whatever the slot held before (slots are not cleared between occupants).  No EOS check, as in q3_generate_greedy.
+ * Device-resident: the pass table and the prompts are uploaded once, a small kernel between two passes resolves every column's
+ * token (a prompt token or the slot's last token), writes the states and the slot table of the next pass and stores the tokens
+ * the last pass produced; the passes replay one captured graph per plan width; only token ids cross PCIe and the call
+ * synchronises once, at its end.  stats may be NULL.
+ * Q3_ERR_ARG: an empty prompt, n_new[r] == 0, prompt_len[r] + n_new[r] - 1 > the batch context, a token outside the vocabulary;
+ * otherwise as q3_batch_step_cols. */
+int q3_generate_many_greedy(q3_engine* e, const int32_t* prompts /* concatenated */, const size_t* prompt_len, const size_t* n_new,
+                            size_t n_requests, int32_t* out_tokens /* concatenated, n_new[r] each */, q3_cols_stats* stats);
+
 #ifdef __cplusplus
 }
 #endif

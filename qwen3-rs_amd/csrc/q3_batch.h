@@ -237,6 +237,7 @@ struct BGemmArgs {
     unsigned long long* stamps;  // developer timeline (Q3_DEV builds, block 0 thread 0): 5 stamps per phase
     unsigned long long* slots;   // LOGITS: [stream][nslots] argmax keys, one per wave of the launch
     int nslots;
+    const int* col_slot;         // QKV of a column pass: out2 of column sb is the cache of slot col_slot[sb] (nullptr: slot = column)
 };
 
 // ---- what the in-lane kernels (k_pgemm, k_pgemm3, k_dgemm) share: a lane holds rows 4q .. 4q+3 of one position / stream as a v4f ----
@@ -293,7 +294,7 @@ __device__ __forceinline__ void mm_store(const BGemmArgs& a, int sb, int r0, con
         float* dst;
         if (r0 < a.rows0) dst = a.out0 + (size_t)sb * a.out0_stride + r0;
         else if (r0 < a.rows0 + a.rows1) dst = a.out1 + (size_t)sb * a.out1_stride + (r0 - a.rows0);
-        else dst = a.out2 + (size_t)sb * a.out2_stride + (size_t)a.st[sb].pos * a.pos_stride + (r0 - a.rows0 - a.rows1);
+        else dst = a.out2 + col_slot_of(a.col_slot, (size_t)sb) * a.out2_stride + (size_t)a.st[sb].pos * a.pos_stride + (r0 - a.rows0 - a.rows1);
         *(v4f*)dst = o;
     } else if constexpr (EPI == EPI_RESID) {
         v4f* dst = (v4f*)(a.out0 + (size_t)sb * a.out0_stride + r0);
@@ -498,7 +499,7 @@ __global__ __launch_bounds__(kBThreads) void k_bgemm(const BGemmArgs a) {
                             float* dst;
                             if (r0 < a.rows0) dst = a.out0 + (size_t)sb * a.out0_stride + r0;
                             else if (r0 < a.rows0 + a.rows1) dst = a.out1 + (size_t)sb * a.out1_stride + (r0 - a.rows0);
-                            else dst = a.out2 + (size_t)sb * a.out2_stride + (size_t)a.st[sb].pos * a.pos_stride + (r0 - a.rows0 - a.rows1);
+                            else dst = a.out2 + col_slot_of(a.col_slot, (size_t)sb) * a.out2_stride + (size_t)a.st[sb].pos * a.pos_stride + (r0 - a.rows0 - a.rows1);
                             dst[f_row] = o;
                         } else if (EPI == EPI_RESID) {
                             float* dst = a.out0 + (size_t)sb * a.out0_stride + r0 + f_row;
@@ -1128,9 +1129,10 @@ __global__ __launch_bounds__(512) void k_attn_gqa(const AttnArgs a0) {
     const int np = pos + 1;
     const float* qsrc = a0.q + sbi * a0.sb_q + (size_t)h * hd;
     const float* ksrc = a0.k_raw + sbi * a0.sb_kraw + (size_t)kvh * hd;
-    float* key_cache = a0.key_cache + sbi * a0.sb_kv;
+    const size_t kvs = col_slot_of(a0.col_slot, sbi) * a0.sb_kv;      // this column's KV slot
+    float* key_cache = a0.key_cache + kvs;
     const float* kbase = key_cache + (size_t)kvh * hd;
-    const float* vbase = a0.value_cache + sbi * a0.sb_kv + (size_t)kvh * hd;
+    const float* vbase = a0.value_cache + kvs + (size_t)kvh * hd;
     float* att = att_l + (size_t)(kwave ? 0 : wave) * ast;
     const float* cs = a0.rope + (size_t)pos * hd;
 
@@ -1369,9 +1371,10 @@ __global__ __launch_bounds__(kG2Threads) void k_attn_gqa2(const AttnArgs a0) {
     const int np = pos + 1;
     const float* qsrc = a0.q + sbi * a0.sb_q + (size_t)h * hd;
     const float* ksrc = a0.k_raw + sbi * a0.sb_kraw + (size_t)kvh * hd;
-    float* key_cache = a0.key_cache + sbi * a0.sb_kv;
+    const size_t kvs = col_slot_of(a0.col_slot, sbi) * a0.sb_kv;      // this column's KV slot
+    float* key_cache = a0.key_cache + kvs;
     const float* kbase = key_cache + (size_t)kvh * hd;
-    const float* vbase = a0.value_cache + sbi * a0.sb_kv + (size_t)kvh * hd;
+    const float* vbase = a0.value_cache + kvs + (size_t)kvh * hd;
     float* att = att_l + (size_t)(head ? wave : 0) * ast;
     const float* cs = a0.rope + (size_t)pos * hd;
     const int skip = own_k ? pos : -1;             // this row of the K cache is produced here, not read
@@ -1938,7 +1941,7 @@ __global__ __launch_bounds__(64) void k_knorm_rope(const AttnArgs a) {
     wave_lds_sync();
     wave_norm_rope(dst, raw, sq, rr, hd, 1);
     wave_lds_sync();
-    float* krow = a.key_cache + (size_t)pos * kvd + (size_t)kvh * hd;
+    float* krow = a.key_cache + col_slot_of(a.col_slot, sbi) * a.sb_kv + (size_t)pos * kvd + (size_t)kvh * hd;
     for (int i = lane; i < hd; i += 64) krow[i] = dst[i];
 }
 
@@ -2224,6 +2227,75 @@ __global__ __launch_bounds__(kWG) void k_spec_restore(const SpecIO* __restrict__
             const int l = (int)(le / kvd), el = (int)(le - (long)l * kvd);
             value_t[(size_t)le * seq_len + (size_t)(first_pos + r)] = value[((size_t)l * seq_len + (size_t)(first_pos + r)) * kvd + el];
         }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Column passes (q3_batch_step_cols / q3_generate_many_greedy): every column of a pass is a (slot, token, position) triple over
+// the per-stream caches of the batched state.  The layers are the short prefill block's (k_knorm_rope writes every key row, the QKV
+// epilogue every value row, then attention with k_in_cache) with the cache base of column j taken from the slot table; the
+// classifier is the n-column one.  One small kernel sits between two passes: it commits the pass behind it and sets up the
+// pass in front of it, from a pass table in device memory -- a loop over many passes never returns to the host.
+// ------------------------------------------------------------------------------------------------
+constexpr int kColsMax = 32;            // columns per pass (Q3_COLS_MAX)
+struct ColEnt {
+    int slot, pos;
+    int src;                            // >= 0: the token is prompts[src]; -1: the last token this slot produced
+    int out;                            // >= 0: the column's argmax goes to out_tokens[out] and becomes the slot's last token; -1: dropped
+};
+struct ColsCtl {
+    int cursor, n_passes;               // next pass of the table to set up / passes in the table (0: a single host-made pass)
+    int n_live;                         // live columns of the pass in flight (0: nothing to commit)
+    int pad_;
+    int out[kColsMax];                  // ColEnt::out of the pass in flight
+    int next[kColsMax];                 // sample_argmax of every live column of the pass committed last
+    int slot_last[kColsMax];            // per KV slot: the last token it produced
+    const ColEnt* table;                // [n_passes][kColsMax], columns past a pass's live ones repeat its last live column with out = -1
+    const int* ncols;                   // [n_passes] live columns
+    const int32_t* prompts;
+    int32_t* out_tokens;
+};
+
+// Commit: the argmax of every live column (the last-maximum fold of k_next_batch), stored where the table says.  Set-up: the
+// States and the slot table of all kColsMax columns of the next pass (whatever width its plan has), tokens resolved from the
+// prompts or from the slot's last token -- the one this very launch may just have committed.  One workgroup.
+__global__ __launch_bounds__(kWG) void k_cols_turn(ColsCtl* ctl, const unsigned long long* __restrict__ slots, int slot_stride, int nslots, State* st,
+                                                   int* col_slot) {
+    const int lane = threadIdx.x & 63;
+    const int n_live = ctl->n_live, p = ctl->cursor, n_passes = ctl->n_passes;
+    for (int col = threadIdx.x >> 6; col < n_live; col += kWaves) {
+        const unsigned long long best = spec_col_best(slots + (size_t)col * slot_stride, nslots);
+        if (lane == 0) {
+            const int idx = (int)(unsigned)(best & 0xffffffffull);
+            ctl->next[col] = idx;
+            st[col].argmax = best;
+            const int o = ctl->out[col];
+            if (o >= 0) {
+                ctl->out_tokens[o] = idx;
+                ctl->slot_last[col_slot[col]] = idx;
+            }
+        }
+    }
+    __syncthreads();
+    if (p >= n_passes) {
+        if (threadIdx.x == 0) ctl->n_live = 0;
+        return;
+    }
+    if ((int)threadIdx.x < kColsMax) {
+        const ColEnt e = ctl->table[(size_t)p * kColsMax + threadIdx.x];
+        State s;
+        s.token = e.src >= 0 ? ctl->prompts[e.src] : ctl->slot_last[e.slot];
+        s.pos = e.pos;
+        s.step = 0;
+        s.prompt_len = 0;
+        s.argmax = 0ull;
+        st[threadIdx.x] = s;
+        col_slot[threadIdx.x] = e.slot;
+        ctl->out[threadIdx.x] = e.out;
+    }
+    if (threadIdx.x == 0) {
+        ctl->n_live = ctl->ncols[p];
+        ctl->cursor = p + 1;
     }
 }
 

@@ -8,7 +8,23 @@
 // the engine's own KV cache, layers only (the classifier runs once, on the last position, through the single-stream launch).
 // Verify: the prefill layers between k_spec_snapshot and the n-column classifier + k_spec_commit + k_spec_restore; with the
 // sampler on (plan_draw), the per-column draws of the batched decode and k_spec_commit_draw stand in for k_spec_commit.
-enum class PlanKind { Decode, Prefill, Verify };
+// Cols: n columns of (slot, token, position) over the per-stream caches (q3_batch_step_cols): the prefill layers with the cache base
+// of every column taken from the slot table, the n-column classifier and k_cols_turn.  Its plans live in BatchCtx::cols_plans.
+enum class PlanKind { Decode, Prefill, Verify, Cols };
+
+// the plan widths of a column pass: a pass of n live columns runs the narrowest plan that holds it, padded with repeats of
+// its last column
+constexpr int kColsWidths[] = {1, 2, 4, 8, 16, 32};
+constexpr int kColsNW = 6;
+struct ColsPlan {
+    std::vector<Launch> plan;
+    Graph graph;
+};
+struct ColsHost {               // pinned staging of one host-made pass
+    ColsCtl ctl;
+    State st[kColsMax];
+    int slot[kColsMax];
+};
 
 struct BatchCtx {
     int max_streams = 0, ctx = 0;
@@ -54,6 +70,15 @@ struct BatchCtx {
     SampleArgs sargs{};
     Graph graph;
     size_t kv_stream = 0;        // floats per stream in key / value
+    // column passes (q3_batch_step_cols / q3_generate_many_greedy)
+    int* col_slot = nullptr;     // device [kColsMax]: KV slot of every column of the pass in flight
+    ColsCtl* cols_ctl = nullptr; // device
+    ColsHost* h_cols = nullptr;
+    ColsPlan cols_plans[kColsNW];                       // by width, built on first use (q3_batch_init starts over)
+    ColEnt* cols_table = nullptr;                       // the loop's pass table, prompts and output: grow-only device buffers
+    int* cols_ncols = nullptr;
+    int32_t *cols_prompts = nullptr, *cols_out = nullptr;
+    size_t cols_table_cap = 0, cols_ncols_cap = 0, cols_prompts_cap = 0, cols_out_cap = 0;
     // packed-matrix directory
     struct PM { size_t q_off, s_off; int ntiles, ng; };
     std::vector<PM> m_qkv, m_wo, m_w13, m_w2;
@@ -144,21 +169,26 @@ void batch_free(q3_engine* e) {
     if (!b) return;
     void* dptrs[] = {b->att_pf, b->qn, b->pq, b->ps, b->x, b->q, b->kraw, b->xb, b->hb, b->logits, b->key, b->value, b->att, b->xq_p, b->xs_p,
                      b->st, b->slots, b->out_tokens, b->stamps, b->d_sampler, b->d_probs, b->d_sp, b->d_keys, b->spec_io, b->spec_snap,
-                     b->spec_samp, b->spec_probs, b->spec_sp, b->spec_keys};
+                     b->spec_samp, b->spec_probs, b->spec_sp, b->spec_keys, b->col_slot, b->cols_ctl, b->cols_table, b->cols_ncols, b->cols_prompts,
+                     b->cols_out};
     for (void* p : dptrs)
         if (p) (void)hipFree(p);
     if (b->h_st) (void)hipHostFree(b->h_st);
     if (b->h_tokens) (void)hipHostFree(b->h_tokens);
     if (b->h_logits) (void)hipHostFree(b->h_logits);
     if (b->h_spec) (void)hipHostFree(b->h_spec);
+    if (b->h_cols) (void)hipHostFree(b->h_cols);
     delete b;
     e->batch = nullptr;
 }
 
-// (re)build the launch list for n streams (Decode) or n block positions (Prefill, Verify; draw: Verify under the sampler)
+// (re)build the launch list for n streams (Decode), n block positions (Prefill, Verify; draw: Verify under the sampler) or n
+// columns (Cols)
 int batch_build_plan(q3_engine* e, int n, PlanKind kind, bool draw = false) {
     BatchCtx* b = e->batch;
-    const bool prefill = kind != PlanKind::Decode, verify = kind == PlanKind::Verify;
+    const bool cols = kind == PlanKind::Cols;
+    const bool prefill = kind == PlanKind::Prefill || kind == PlanKind::Verify, verify = kind == PlanKind::Verify;
+    const bool block = prefill || cols;          // columns may share a cache: all key rows enter it before any column attends
     const q3_config& c = e->cfg;
     const int dim = c.dim, L = c.n_layers, hd = c.head_dim, V = c.vocab_size, H = c.hidden_dim, G = c.group_size;
     const int ahd = c.n_heads * hd, kvd = c.n_kv_heads * hd, S = prefill ? c.seq_len : b->ctx;
@@ -329,6 +359,7 @@ int batch_build_plan(q3_engine* e, int n, PlanKind kind, bool draw = false) {
             a.out1 = b->kraw; a.out1_stride = kvd;
             a.out2 = value_base + kv_off; a.out2_stride = kv_stride;
             a.rows0 = ahd; a.rows1 = kvd; a.pos_stride = kvd;
+            a.col_slot = cols ? b->col_slot : nullptr;
             if ((rc = gemm(F_QKV, EPI_QKV, b->m_qkv[l], a))) return rc;
         }
         {
@@ -351,14 +382,15 @@ int batch_build_plan(q3_engine* e, int n, PlanKind kind, bool draw = false) {
             a.strict = strict;
             a.sb_q = ahd; a.sb_kraw = kvd; a.sb_kv = kv_stride; a.sb_xb = ahd;
             a.sb_att = (long long)c.n_heads * S;
+            a.col_slot = cols ? b->col_slot : nullptr;
             a.tch = att_tch < attn_tch(hd) ? att_tch : attn_tch(hd);
             const int kv_mul = c.n_heads / c.n_kv_heads;
             const bool gqa = kv_mul <= 7 && hd <= 256 && (hd & (hd - 1)) == 0 && hd >= 16 &&
                              attn_gqa_smem_bytes(hd, kv_mul, S) <= 150 * 1024 && dev_knob("Q3_BATCH_ATT_GQA", 1);
             // dense prefill, head_dim 128 with 2 or 4 query heads per kv head: k_attn_pf2 (Q3_PREFILL_ATT_PF=0: k_attn_gqa2)
             const bool use_pf = dense && hd == kG2Hd && (kv_mul == 2 || kv_mul == 4) && b->att_pf != nullptr && dev_knob("Q3_PREFILL_ATT_PF", 1);
-            if (prefill && !gqa && !use_pf) return fail(Q3_ERR_UNSUPPORTED, "batched prefill needs the per-kv-head attention kernel");
-            if (prefill) {   // all key rows of the block enter the cache before any position attends
+            if (block && !gqa && !use_pf) return fail(Q3_ERR_UNSUPPORTED, "batched prefill needs the per-kv-head attention kernel");
+            if (block) {   // all key rows of the block enter the cache before any position attends
                 if (use_pf) a.q_out = b->qn;                        // the same launch normalises + rotates the block's query heads
                 // long blocks of head_dim-128 models: 64 vectors per workgroup, one chain per lane (k_knorm_rope_blk); Q3_KNORM_BLK=0: one wave per vector
                 if (n >= 64 && hd == kG2Hd && dev_knob("Q3_KNORM_BLK", 1)) {
@@ -448,6 +480,9 @@ int batch_build_plan(q3_engine* e, int n, PlanKind kind, bool draw = false) {
         if ((rc = make_launch(Ln, F_NEXT, k_spec_restore, dim3(spec_grid), dim3(kWG), 0, b->spec_io, e->d_key, e->d_value, e->d_value_t, b->spec_snap,
                               L, c.seq_len, kvd))) return rc;
         b->plan.push_back(Ln);
+    } else if (cols) {
+        if ((rc = make_launch(Ln, F_NEXT, k_cols_turn, dim3(1), dim3(kWG), 0, b->cols_ctl, b->slots, b->nslots, b->nslots_used, b->st, b->col_slot))) return rc;
+        b->plan.push_back(Ln);
     } else if (verify) {
         if ((rc = make_launch(Ln, F_NEXT, k_spec_commit, dim3(1), dim3(kWG), 0, b->spec_io, b->slots, b->nslots, b->nslots_used, e->d_state,
                               e->d_out_tokens, e->out_cap))) return rc;
@@ -459,7 +494,7 @@ int batch_build_plan(q3_engine* e, int n, PlanKind kind, bool draw = false) {
         if ((rc = make_launch(Ln, F_NEXT, k_next_batch, dim3((unsigned)n), dim3(kWG), 0, b->st, b->slots, b->nslots, b->nslots_used, b->out_tokens, b->out_cap))) return rc;
         b->plan.push_back(Ln);
     }
-    if (b->sampling && !prefill) {      // Sampler::sample per stream on the logits of this step (one workgroup per stream)
+    if (b->sampling && !block) {      // Sampler::sample per stream on the logits of this step (one workgroup per stream)
         if (b->sargs.pre_exp) {         // ... behind its element-wise passes spread over the chip
             if ((rc = make_launch(Ln, F_NEXT, k_sample_exp, dim3(64, (unsigned)n), dim3(256), 0, b->sargs))) return rc;
             b->plan.push_back(Ln);
@@ -612,7 +647,12 @@ int batch_alloc(q3_engine* e, int max_streams, uint32_t ctx_len, bool with_kv, i
     HIP_TRY(hipMemsetAsync(b->out_tokens, 0, 4 * B * S, e->stream));
     HIP_TRY(hipHostMalloc((void**)&b->h_st, sizeof(State) * B, hipHostMallocDefault));
     HIP_TRY(hipHostMalloc((void**)&b->h_tokens, 4 * B * S, hipHostMallocDefault));
-    HIP_TRY(hipHostMalloc((void**)&b->h_logits, 4 * B * V, hipHostMallocDefault));
+    HIP_TRY(hipHostMalloc((void**)&b->h_logits, 4 * BL * V, hipHostMallocDefault));     // a column pass is kColsMax rows whatever max_streams is
+    HIP_TRY(hipMalloc((void**)&b->col_slot, 4 * kColsMax));
+    HIP_TRY(hipMemsetAsync(b->col_slot, 0, 4 * kColsMax, e->stream));
+    HIP_TRY(hipMalloc((void**)&b->cols_ctl, sizeof(ColsCtl)));
+    HIP_TRY(hipMemsetAsync(b->cols_ctl, 0, sizeof(ColsCtl), e->stream));
+    HIP_TRY(hipHostMalloc((void**)&b->h_cols, sizeof(ColsHost), hipHostMallocDefault));
     HIP_TRY(hipStreamSynchronize(e->stream));
     return Q3_OK;
 }

@@ -209,6 +209,10 @@ struct Graph {
     Graph& operator=(const Graph&) = delete;
     ~Graph() { reset(); }
     explicit operator bool() const { return exec != nullptr; }
+    void swap(Graph& o) {
+        std::swap(graph, o.graph);
+        std::swap(exec, o.exec);
+    }
     void reset() {
         if (exec) (void)hipGraphExecDestroy(exec);
         if (graph) (void)hipGraphDestroy(graph);
@@ -1872,3 +1876,4 @@ int q3_op_argmax(const float* logits, size_t n, int32_t* index, int device) {
 }  // extern "C"
 
 #include "q3_batch_host.inc"
+#include "q3_cols_host.inc"

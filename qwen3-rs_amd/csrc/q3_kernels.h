@@ -102,7 +102,12 @@ struct AttnArgs {
     // without two integer divisions (~55 scalar instructions in front of the first address that needs the head)
     int kv_mul;
     unsigned kvh_magic;
+    // column pass (q3_batch_step_cols): column -> KV slot of the batched state, [columns] on the device.  Only the cache base goes
+    // through it (slot * sb_kv); q, k_raw, xb, the packed activations and State stay indexed by column.  nullptr: column = slot.
+    const int* col_slot;
 };
+// the KV slot of column sb
+__device__ __forceinline__ size_t col_slot_of(const int* __restrict__ table, size_t sb) { return table != nullptr ? (size_t)table[sb] : sb; }
 inline void attn_set_heads(AttnArgs& a, int n_heads, int n_kv_heads) {
     a.n_heads = n_heads;
     a.n_kv_heads = n_kv_heads;

@@ -26,8 +26,10 @@ EXPORTED_SYMBOLS = [
     "q3_op_swiglu", "q3_op_expf", "q3_op_attention", "q3_op_argmax", "q3_op_sample", "q3_op_gemv_role",
     "q3_verify", "q3_lookup_draft", "q3_lookup_trace", "q3_generate_lookup",
     "q3_verify_draw", "q3_generate_lookup_draw",
+    "q3_batch_step_cols", "q3_cols_schedule", "q3_generate_many_greedy",
 ]
 VERIFY_MAX = 32          # Q3_VERIFY_MAX
+COLS_MAX = 32            # Q3_COLS_MAX
 
 
 class Q3Error(RuntimeError):
@@ -54,6 +56,19 @@ class SpecStats:
     single_steps: int
     drafted: int
     accepted: int
+
+
+class _ColsStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("passes", "live_columns", "prompt_columns", "decode_columns")]
+
+
+@dataclasses.dataclass(frozen=True)
+class ColsStats:
+    """q3_cols_stats: the passes of a generate_many_greedy call and what their columns held"""
+    passes: int
+    live_columns: int
+    prompt_columns: int
+    decode_columns: int
 
 
 @dataclasses.dataclass(frozen=True)
@@ -179,6 +194,10 @@ def _bind(path: str) -> C.CDLL:
     L.q3_lookup_trace.argtypes = [i32p, sz, sz, C.c_int, C.c_int, i32p, i32p]
     L.q3_generate_lookup.argtypes = [C.c_void_p, i32p, sz, sz, sz, sz, C.c_int, C.c_int, i32p, C.POINTER(_SpecStats)]
     L.q3_generate_lookup_draw.argtypes = L.q3_generate_lookup.argtypes
+    szp = C.POINTER(sz)
+    L.q3_batch_step_cols.argtypes = [C.c_void_p, i32p, i32p, i32p, C.c_int, fp, i32p]
+    L.q3_cols_schedule.argtypes = [szp, szp, sz, C.c_int, i32p, sz, szp, C.POINTER(_ColsStats)]
+    L.q3_generate_many_greedy.argtypes = [C.c_void_p, i32p, szp, szp, sz, i32p, C.POINTER(_ColsStats)]
     L.q3_profile.argtypes = [C.c_void_p, sz, sz, C.c_int, fp, C.POINTER(C.c_int32), C.c_int]
     L.q3_profile_name.argtypes = [C.c_int]
     L.q3_profile_name.restype = C.c_char_p
@@ -222,6 +241,24 @@ def lookup_trace(seq, n_corpus: int, ngram: int, draft_len: int) -> List[List[in
     lens = (C.c_int32 * max(1, rows))()
     _check(load_library().q3_lookup_trace(_i32_array(seq), len(seq), n_corpus, ngram, draft_len, drafts, lens))
     return [[int(drafts[r * draft_len + k]) for k in range(lens[r])] for r in range(rows)]
+
+
+def _size_array(values):
+    return (C.c_size_t * max(1, len(values)))(*[int(v) for v in values])
+
+
+def cols_schedule(prompt_len, n_new, max_streams: int):
+    """The pass table of generate_many_greedy (q3_cols_schedule, host only): ([(pass, slot, pos, request), ...] in column order,
+    ColsStats) for requests of prompt_len[r] prompt tokens and n_new[r] new tokens through max_streams slots."""
+    if len(prompt_len) != len(n_new):
+        raise ValueError("one n_new per prompt")
+    L = load_library()
+    pl, nn, n, st = _size_array(prompt_len), _size_array(n_new), C.c_size_t(0), _ColsStats()
+    _check(L.q3_cols_schedule(pl, nn, len(prompt_len), max_streams, None, 0, C.byref(n), C.byref(st)))
+    table = (C.c_int32 * max(1, 4 * n.value))()
+    _check(L.q3_cols_schedule(pl, nn, len(prompt_len), max_streams, table, n.value, C.byref(n), C.byref(st)))
+    rows = [tuple(int(table[4 * i + k]) for k in range(4)) for i in range(n.value)]
+    return rows, ColsStats(st.passes, st.live_columns, st.prompt_columns, st.decode_columns)
 
 
 def parse_header(data: bytes) -> ModelConfig:
@@ -426,6 +463,40 @@ class Transformer:
         out = np.zeros((n, n_steps), dtype=np.int32)
         self._batch_rc(self._lib.q3_generate_greedy_batch(self._h, tk, ps, n, n_steps, out.ctypes.data_as(C.POINTER(C.c_int32))))
         return out
+
+    # ---- ragged column passes over the batched state (include/qwen3_hip.h section 2e)
+    def batch_step_cols(self, slots, tokens, pos, want_logits: bool = False):
+        """One weight pass of up to 32 columns: column j runs forward(tokens[j], pos[j]) over the KV cache of slot slots[j]; the
+        columns of a slot are adjacent with consecutive positions.  Returns the argmax list or, with want_logits,
+        (logits [n, vocab], argmax list)."""
+        n = len(slots)
+        if not (len(tokens) == n and len(pos) == n):
+            raise ValueError("one token and one position per column")
+        nxt = (C.c_int32 * max(1, n))()
+        logits = np.zeros((n, self._config.vocab_size), dtype=np.float32) if want_logits else None
+        lp = logits.ctypes.data_as(C.POINTER(C.c_float)) if want_logits else None
+        self._batch_rc(self._lib.q3_batch_step_cols(self._h, _i32_array(slots), _i32_array(tokens), _i32_array(pos), n, lp, nxt))
+        out = [int(nxt[i]) for i in range(n)]
+        return (logits, out) if want_logits else out
+
+    def generate_many_greedy(self, prompts, n_new):
+        """Greedy generations of many requests through the slots of batch_init, the whole loop on the device
+        (q3_generate_many_greedy): prompts enter in chunks next to the decode columns of other slots, finished requests hand
+        their slot to the next one.  prompts: one token list per request; n_new: tokens wanted per request (the first is the
+        token behind the prompt).  Returns ([n_new[r] tokens] per request, ColsStats)."""
+        if len(prompts) != len(n_new):
+            raise ValueError("one n_new per prompt")
+        flat = [int(t) for p in prompts for t in p]
+        total = sum(int(k) for k in n_new)
+        out = (C.c_int32 * max(1, total))()
+        st = _ColsStats()
+        self._batch_rc(self._lib.q3_generate_many_greedy(self._h, _i32_array(flat), _size_array([len(p) for p in prompts]), _size_array(n_new),
+                                                         len(prompts), out, C.byref(st)))
+        rows, at = [], 0
+        for k in n_new:
+            rows.append([int(out[at + i]) for i in range(int(k))])
+            at += int(k)
+        return rows, ColsStats(st.passes, st.live_columns, st.prompt_columns, st.decode_columns)
 
     def set_batch_sampler(self, temperature: float, topp: float, rng_seeds):
         """one Sampler per stream (sampler.rs:29-42), stream i seeded with rng_seeds[i]; temperature 0 = greedy"""

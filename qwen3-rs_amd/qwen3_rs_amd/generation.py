@@ -139,6 +139,29 @@ def generate(transformer, prompt_tokens: Sequence[int], max_new_tokens: Optional
     return out, metrics
 
 
+def generate_many(transformer, prompts: Sequence[Sequence[int]], max_new_tokens: int, stop_tokens: Iterable[int] = ()):
+    """Many greedy generations served through the slots of Transformer.batch_init in ragged column passes
+    (Transformer.generate_many_greedy).  Row r holds what Transformer.prefill(prompts[r], 0) followed by generate_greedy returns on
+    an engine of its own: every prompt token goes through the model (chat's prompt loop, generation.rs:116-123), then up to
+    max_new_tokens tokens are decoded (fewer where the batch context ends first).  The device loop checks no stop token; each
+    row is cut behind its first stop token afterwards, the way generate ends at BOS / EOS (generation.rs:35).
+    Returns (rows, ColsStats)."""
+    if any(len(p) == 0 for p in prompts):
+        raise ValueError("Please provide a prompt")
+    stop = set(stop_tokens)
+    ctx = getattr(transformer, "_batch_ctx", transformer.get_config().seq_len)
+    n_new = [max(min(max_new_tokens, ctx - len(p) + 1), 0) for p in prompts]
+    live = [r for r, k in enumerate(n_new) if k > 0]
+    rows: List[List[int]] = [[] for _ in prompts]
+    stats = None
+    if live:
+        got, stats = transformer.generate_many_greedy([prompts[r] for r in live], [n_new[r] for r in live])
+        for r, toks in zip(live, got):
+            k = next((i for i, t in enumerate(toks) if t in stop), None)
+            rows[r] = toks if k is None else toks[:k + 1]
+    return rows, stats
+
+
 def chat_turn(transformer, prompt_tokens: Sequence[int], pos: int, max_new_tokens: int,
               stop_tokens: Iterable[int] = (), sample: Callable[[np.ndarray], int] = sample_argmax,
               on_logits: Optional[Callable[[int, int, np.ndarray], None]] = None, lookup: Optional[Tuple[int, int]] = None,

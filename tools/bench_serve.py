@@ -1,0 +1,178 @@
+#!/usr/bin/env python3
+"""What ragged column passes (include/qwen3_hip.h section 2e) cost and gain on the full-size synthetic checkpoints.
+
+    python tools/bench_serve.py [--models qwen3-0.6b,qwen3-8b] [--ctx 1024] [--out profiles] [--limit 420]
+
+Every model is measured in a child process of its own under a time limit (one faulting run never starts the next).  Per model:
+  (a) pass cost: wall time of a 32-column pass of 32 single-position slots (q3_batch_step_cols, no logits) against a
+      q3_forward_batch step (no logits) at the same positions, both with one host round trip per step;
+  (b) requests through q3_generate_many_greedy against the only way section 2b offers -- every prompt token stepped through
+      q3_forward_batch, one token per stream and weight pass, a slot refilled when its request ends, one host round trip per
+      step: 8 requests of 256 prompt tokens + 64 new through 8 slots, and 64 requests of mixed lengths through 32 slots.  Passes
+      and tok/s (prompt + generated tokens per second, and generated tokens per second) for both; the tokens must be equal.
+Writes <out>/serve_cols.json and serve_cols.md (a batch-32 A/B section already in the .md is kept).
+"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "qwen3-rs_amd"))
+
+AB_MARK = "## Batch-32 decode A/B"
+
+
+def median(xs):
+    xs = sorted(xs)
+    return xs[len(xs) // 2]
+
+
+def stepped(t, prompts, n_new, max_streams):
+    """section 2b only: one token per slot and pass; returns (rows, passes)"""
+    queue = list(range(len(prompts)))
+    slots = [None] * max_streams
+    rows = [[] for _ in prompts]
+    passes = 0
+    while queue or any(s is not None for s in slots):
+        for i in range(max_streams):
+            if slots[i] is None and queue:
+                slots[i] = [queue.pop(0), 0]                           # request, position
+        n = max(i for i in range(max_streams) if slots[i] is not None) + 1
+        toks, pos = [], []
+        for i in range(n):
+            if slots[i] is None:                                       # no compaction: a hole below a live slot is stepped too
+                toks.append(0)
+                pos.append(0)
+                continue
+            r, p = slots[i]
+            toks.append(prompts[r][p] if p < len(prompts[r]) else rows[r][p - len(prompts[r])])
+            pos.append(p)
+        _, am = t.forward_batch(toks, pos, want_logits=False)
+        passes += 1
+        for i in range(n):
+            if slots[i] is None:
+                continue
+            r, p = slots[i]
+            if p >= len(prompts[r]) - 1:
+                rows[r].append(am[i])
+            slots[i][1] = p + 1
+            if len(rows[r]) == n_new[r]:
+                slots[i] = None
+    return rows, passes
+
+
+def worker(name, ctx, ckpt_dir, seed):
+    import numpy as np
+    import qwen3_rs_amd as q3
+    ck = q3.checkpoint
+    shape = ck.SHAPES[name]
+    path = os.path.join(ckpt_dir, f"{name}-seed{seed}.q3bin")
+    ck.ensure_synthetic_checkpoint(path, shape, seed=seed)
+    res = {"model": name, "ctx": ctx}
+    rng = np.random.default_rng(7)
+    with q3.TransformerBuilder(path).with_ctx_length(ctx).build() as t:
+        # ---- (a) one pass
+        t.batch_init(32, ctx)
+        toks = [int(v) for v in rng.integers(0, shape.vocab_size, 32)]
+        for p0 in (8, 256):
+            pos = [p0] * 32
+            t.forward_batch(toks, pos, want_logits=False)
+            t.batch_step_cols(list(range(32)), toks, pos)
+            fb, sc = [], []
+            for _ in range(15):                                        # alternating
+                t0 = time.perf_counter()
+                t.forward_batch(toks, pos, want_logits=False)
+                fb.append(time.perf_counter() - t0)
+                t0 = time.perf_counter()
+                t.batch_step_cols(list(range(32)), toks, pos)
+                sc.append(time.perf_counter() - t0)
+            res[f"pass_ms_pos{p0}"] = {"forward_batch": 1e3 * median(fb), "step_cols": 1e3 * median(sc)}
+        # ---- (b) requests
+        cases = {
+            "8x(256+64), 8 slots": ([256] * 8, [64] * 8, 8),
+            "64 mixed, 32 slots": ([int(v) for v in rng.integers(1, 200, 64)], [int(v) for v in rng.integers(1, 96, 64)], 32),
+        }
+        res["requests"] = {}
+        for label, (plen, nnew, ms) in cases.items():
+            prompts = [ck.iter_prompt_tokens(shape, seed + 50 + r, n) for r, n in enumerate(plen)]
+            t.batch_init(ms, ctx)
+            n_tok, n_gen = sum(plen) + sum(nnew) - len(plen), sum(nnew)
+            t.generate_many_greedy(prompts[:2], [2, 2])                # plans
+            t0 = time.perf_counter()
+            rows, st = t.generate_many_greedy(prompts, nnew)
+            dt_many = time.perf_counter() - t0
+            t0 = time.perf_counter()
+            rows2, st2 = t.generate_many_greedy(prompts, nnew)         # every plan width of this schedule now exists
+            dt_many = min(dt_many, time.perf_counter() - t0)
+            stepped(t, prompts[:2], [2, 2], ms)
+            t0 = time.perf_counter()
+            ref, ref_passes = stepped(t, prompts, nnew, ms)
+            dt_step = time.perf_counter() - t0
+            res["requests"][label] = {
+                "tokens_equal": rows == ref and rows2 == ref, "model_tokens": n_tok, "generated": n_gen,
+                "many": {"passes": st.passes, "live_columns": st.live_columns, "seconds": dt_many, "tok_s": n_tok / dt_many,
+                         "gen_tok_s": n_gen / dt_many},
+                "stepped": {"passes": ref_passes, "seconds": dt_step, "tok_s": n_tok / dt_step, "gen_tok_s": n_gen / dt_step},
+            }
+    print("RESULT " + json.dumps(res))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--models", default="qwen3-0.6b,qwen3-8b")
+    ap.add_argument("--ctx", type=int, default=1024)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles"))
+    ap.add_argument("--limit", type=int, default=420, help="seconds per model")
+    ap.add_argument("--seed", type=int, default=1236)
+    ap.add_argument("--ckpt-dir", default=os.environ.get("Q3_CKPT_DIR", "/tmp"))
+    ap.add_argument("--worker")
+    a = ap.parse_args()
+    if a.worker:
+        worker(a.worker, a.ctx, a.ckpt_dir, a.seed)
+        return 0
+    results = []
+    for name in a.models.split(","):
+        cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--worker", name, "--ctx", str(a.ctx),
+               "--ckpt-dir", a.ckpt_dir, "--seed", str(a.seed)]
+        p = subprocess.run(cmd, capture_output=True, text=True)
+        sys.stderr.write(p.stderr[-2000:])
+        if p.returncode != 0:
+            print(f"[bench_serve] {name}: exit status {p.returncode}; stopping here", file=sys.stderr)
+            break
+        results.append(json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")][-1][7:]))
+    os.makedirs(a.out, exist_ok=True)
+    with open(os.path.join(a.out, "serve_cols.json"), "w") as f:
+        json.dump(results, f, indent=1)
+    md_path = os.path.join(a.out, "serve_cols.md")
+    keep = ""
+    if os.path.exists(md_path):
+        old = open(md_path).read()
+        if AB_MARK in old:
+            keep = old[old.index(AB_MARK):]
+    lines = ["# Ragged column passes: pass cost and request throughput", "",
+             "Written by `tools/bench_serve.py` (synthetic full-size checkpoints, one MI355X, context %d per slot)." % a.ctx, "",
+             "## (a) One 32-column pass of 32 single-position slots against a `q3_forward_batch` step", "",
+             "Wall time per call, no logits read back, median of 15 alternating calls.", "",
+             "| model | position | forward_batch ms | step_cols ms | ratio |", "|---|---|---|---|---|"]
+    for r in results:
+        for p0 in (8, 256):
+            d = r[f"pass_ms_pos{p0}"]
+            lines.append(f"| {r['model']} | {p0} | {d['forward_batch']:.3f} | {d['step_cols']:.3f} | {d['step_cols'] / d['forward_batch']:.3f} |")
+    lines += ["", "## (b) Requests: `q3_generate_many_greedy` against prompts stepped through `q3_forward_batch`", "",
+              "tok/s counts every token that goes through the model (prompt + generated); gen tok/s the generated ones only.", "",
+              "| model | requests | path | passes | seconds | tok/s | gen tok/s | tokens equal |", "|---|---|---|---|---|---|---|---|"]
+    for r in results:
+        for label, d in r["requests"].items():
+            for k in ("many", "stepped"):
+                lines.append(f"| {r['model']} | {label} | {k} | {d[k]['passes']} | {d[k]['seconds']:.3f} | {d[k]['tok_s']:.0f} | "
+                             f"{d[k]['gen_tok_s']:.0f} | {d['tokens_equal']} |")
+    with open(md_path, "w") as f:
+        f.write("\n".join(lines) + "\n" + ("\n" + keep if keep else ""))
+    return 0 if len(results) == len(a.models.split(",")) else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())
