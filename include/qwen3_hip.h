@@ -428,6 +428,48 @@ int q3_cols_schedule(const size_t* prompt_len, const size_t* n_new, size_t n_req
 int q3_generate_many_greedy(q3_engine* e, const int32_t* prompts /* concatenated */, const size_t* prompt_len, const size_t* n_new,
                             size_t n_requests, int32_t* out_tokens /* concatenated, n_new[r] each */, q3_cols_stats* stats);
 
+/* ------------------------------------------------------------------------------------------------
+ * 2f. (behind 2e so that the earlier sections stay as they were.)  Column passes under the sampler: section 2e for any sampler
+ * setting, per slot and per request.  Sampler::sample is a deterministic function of (logits, rng state) with one xorshift64* coin
+ * per draw (sampler.rs:44-54,118-139), and the prompt loop of `chat` draws and discards one sample per prompt position
+ * (generation.rs:116-123), which q3_prefill reproduces.  The rule: column k of a slot's run is drawn with the slot's rng advanced
+ * k coins, and after the pass the slot's rng is advanced by the run's length.  Only the draw behind a prompt's last position and
+ * the draws of decode columns are made and kept; an interior prompt column consumes its coin and does no sampling work.  No
+ * rejection sampling, no second distribution: tokens and cache rows are bit-identical to q3_sampler_set + q3_prefill +
+ * q3_generate_sampled on a fresh single-stream engine, whatever else shares the passes, whichever slot a request lands in and
+ * whatever that slot held before.  (generate-mode coin accounting -- generation.rs:25-39, no coin on interior prompt positions --
+ * is not offered: this section follows q3_prefill, as q3_generate_many_greedy does.)
+ * A pass is section 2e's plan with the per-column draws of section 2d behind the classifier (their scratch of 32 columns is
+ * allocated by the first pass that samples) and a turn kernel that commits draws; the plans are a second set of six, built on
+ * first use.  Temperature and top-p are read from device memory when a pass runs: changing them rebuilds nothing.  The names of
+ * section 2e launch exactly what they launched before.
+ * ------------------------------------------------------------------------------------------------ */
+
+/* q3_batch_step_cols under the per-slot samplers of q3_batch_sampler_set (slot i = stream i: the same rng stream q3_forward_batch
+ * advances).  Column j at index k of its slot's run is drawn with that slot's rng advanced k coins; afterwards the slot's rng is
+ * advanced by the run's length.  keep[j] == 0: the coin is consumed, no draw is made and next_out[j] = -1 (the prompt loop's
+ * discarded sample); otherwise next_out[j] is the draw, the token q3_forward_sample returns at that point of the slot's history on
+ * an engine seeded like the slot.  logits_out: the raw logits, as in q3_verify_draw.  With temperature 0, or no batch sampler
+ * set, it is q3_batch_step_cols: argmax, no coin, keep ignored.  Errors: those of q3_batch_step_cols, except that a sampling
+ * batch is accepted. */
+int q3_batch_step_cols_draw(q3_engine* e, const int32_t* slots, const int32_t* tokens, const int32_t* pos, int n_cols,
+                            const uint8_t* keep /* [n_cols] or NULL = all kept */, float* logits_out, int32_t* next_out);
+
+/* q3_generate_many_greedy under one sampler per request: the schedule of q3_cols_schedule, unchanged, and the same output layout.
+ * Request r yields the tokens of a fresh single-stream engine after q3_sampler_set(temperature[r], topp[r], seeds[r]):
+ * y_0 = q3_prefill(prompt_r, 0), y_1 .. = q3_generate_sampled(y_0, prompt_len[r], n_new[r] - 1).  A request's first column loads
+ * its sampler into the slot it landed in.  temperature[r] == 0: the request is greedy (argmax, no coin, seed ignored); greedy and
+ * sampled requests may share passes.  Device-resident like the greedy loop: the table, the prompts and the per-request sampler
+ * parameters are uploaded once, the passes replay one captured graph per plan width, only token ids cross PCIe and the call
+ * synchronises once.  It keeps per-slot sampler states of its own and needs no q3_batch_sampler_set; the per-stream sampler
+ * states of section 2b are unspecified after the call: call q3_batch_sampler_set again before the next sampled call of section 2b
+ * or q3_batch_step_cols_draw.
+ * Q3_ERR_ARG: a null array, a negative or NaN temperature, a top-p outside [0, 1], and everything q3_generate_many_greedy rejects.
+ * Q3_ERR_UNSUPPORTED: a Q3_FLAG_FAST engine, the shapes the short prefill block refuses. */
+int q3_generate_many_sampled(q3_engine* e, const int32_t* prompts /* concatenated */, const size_t* prompt_len, const size_t* n_new,
+                             size_t n_requests, const float* temperature, const float* topp, const uint64_t* seeds /* [n_requests] each */,
+                             int32_t* out_tokens /* concatenated, n_new[r] each */, q3_cols_stats* stats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,6 +25,16 @@ struct ColsHost {               // pinned staging of one host-made pass
     State st[kColsMax];
     int slot[kColsMax];
 };
+struct ColsStep {               // the one-pass table of a host-made sampled pass (q3_batch_step_cols_draw), device and pinned copy
+    ColEnt table[kColsMax];
+    ColAux aux[kColsMax];
+    int32_t tokens[kColsMax];
+    int ncols;
+};
+struct ColsDrawHost {           // pinned staging of the sampled passes
+    ColsDraw dr;
+    ColsStep step;
+};
 
 struct BatchCtx {
     int max_streams = 0, ctx = 0;
@@ -79,6 +89,17 @@ struct BatchCtx {
     int* cols_ncols = nullptr;
     int32_t *cols_prompts = nullptr, *cols_out = nullptr;
     size_t cols_table_cap = 0, cols_ncols_cap = 0, cols_prompts_cap = 0, cols_out_cap = 0;
+    // ... under the sampler (q3_batch_step_cols_draw / q3_generate_many_sampled): allocated by the first sampled pass (cols_draw_alloc),
+    // the column sampler states and the draw scratch are those of spec_draw_alloc
+    ColsPlan cols_plans_draw[kColsNW];                  // the same layers and classifier, then the draws and k_cols_turn_draw
+    ColsDraw* cols_draw = nullptr;                      // device
+    ColsDrawHost* h_cols_draw = nullptr;
+    ColsStep* cols_step = nullptr;                      // device
+    SamplerState* cols_slot_samp = nullptr;             // [kMaxStreams] the loop's per-slot states (a single pass uses d_sampler)
+    ColAux* cols_aux = nullptr;                         // the loop's table of ColAux and per-request sampler parameters: grow-only
+    float *cols_temp = nullptr, *cols_topp = nullptr;
+    unsigned long long* cols_seeds = nullptr;
+    size_t cols_aux_cap = 0, cols_temp_cap = 0, cols_topp_cap = 0, cols_seeds_cap = 0;
     // packed-matrix directory
     struct PM { size_t q_off, s_off; int ntiles, ng; };
     std::vector<PM> m_qkv, m_wo, m_w13, m_w2;
@@ -170,7 +191,7 @@ void batch_free(q3_engine* e) {
     void* dptrs[] = {b->att_pf, b->qn, b->pq, b->ps, b->x, b->q, b->kraw, b->xb, b->hb, b->logits, b->key, b->value, b->att, b->xq_p, b->xs_p,
                      b->st, b->slots, b->out_tokens, b->stamps, b->d_sampler, b->d_probs, b->d_sp, b->d_keys, b->spec_io, b->spec_snap,
                      b->spec_samp, b->spec_probs, b->spec_sp, b->spec_keys, b->col_slot, b->cols_ctl, b->cols_table, b->cols_ncols, b->cols_prompts,
-                     b->cols_out};
+                     b->cols_out, b->cols_draw, b->cols_step, b->cols_slot_samp, b->cols_aux, b->cols_temp, b->cols_topp, b->cols_seeds};
     for (void* p : dptrs)
         if (p) (void)hipFree(p);
     if (b->h_st) (void)hipHostFree(b->h_st);
@@ -178,12 +199,13 @@ void batch_free(q3_engine* e) {
     if (b->h_logits) (void)hipHostFree(b->h_logits);
     if (b->h_spec) (void)hipHostFree(b->h_spec);
     if (b->h_cols) (void)hipHostFree(b->h_cols);
+    if (b->h_cols_draw) (void)hipHostFree(b->h_cols_draw);
     delete b;
     e->batch = nullptr;
 }
 
 // (re)build the launch list for n streams (Decode), n block positions (Prefill, Verify; draw: Verify under the sampler) or n
-// columns (Cols)
+// columns (Cols; draw: the sampled column plan)
 int batch_build_plan(q3_engine* e, int n, PlanKind kind, bool draw = false) {
     BatchCtx* b = e->batch;
     const bool cols = kind == PlanKind::Cols;
@@ -479,6 +501,17 @@ int batch_build_plan(q3_engine* e, int n, PlanKind kind, bool draw = false) {
         b->plan.push_back(Ln);
         if ((rc = make_launch(Ln, F_NEXT, k_spec_restore, dim3(spec_grid), dim3(kWG), 0, b->spec_io, e->d_key, e->d_value, e->d_value_t, b->spec_snap,
                               L, c.seq_len, kvd))) return rc;
+        b->plan.push_back(Ln);
+    } else if (cols && draw) {
+        // the draws of the verify pass above over the column sampler states k_cols_turn_draw set up; columns that do not draw
+        // (interior prompt positions, pads, temperature-0 slots) return at once in both sampler launches
+        if ((rc = make_launch(Ln, F_NEXT, k_spec_colmax, dim3(1), dim3(kWG), 0, b->st, b->slots, b->nslots, b->nslots_used, n))) return rc;
+        b->plan.push_back(Ln);
+        if ((rc = make_launch(Ln, F_NEXT, k_sample_exp, dim3(64, (unsigned)n), dim3(256), 0, b->spec_sargs))) return rc;
+        b->plan.push_back(Ln);
+        if ((rc = make_launch(Ln, F_NEXT, k_sample, dim3((unsigned)n), dim3(kSampThreads), 4 * kSegFloats, b->spec_sargs))) return rc;
+        b->plan.push_back(Ln);
+        if ((rc = make_launch(Ln, F_NEXT, k_cols_turn_draw, dim3(1), dim3(kWG), 0, b->cols_ctl, b->cols_draw, b->spec_samp, b->st, b->col_slot))) return rc;
         b->plan.push_back(Ln);
     } else if (cols) {
         if ((rc = make_launch(Ln, F_NEXT, k_cols_turn, dim3(1), dim3(kWG), 0, b->cols_ctl, b->slots, b->nslots, b->nslots_used, b->st, b->col_slot))) return rc;

@@ -1,10 +1,12 @@
-// q3_cols_host.inc -- host side of the column passes (include/qwen3_hip.h section 2e; included by q3_engine.hip behind
+// q3_cols_host.inc -- host side of the column passes (include/qwen3_hip.h sections 2e and 2f; included by q3_engine.hip behind
 // q3_batch_host.inc, same translation unit).
 //
 // A pass is up to 32 columns of (slot, token, position) over the per-stream KV caches of the batched state: decode columns of some
 // slots next to runs of consecutive prompt positions of others, one pass over the packed weights (PlanKind::Cols).  The loop
 // q3_generate_many_greedy walks a pass table that is a pure function of the request lengths (cols_schedule_run): the host
 // knows every pass's width in advance, the device resolves every pass's tokens itself (k_cols_turn).
+// Section 2f is the same under the sampler: a second set of plans whose classifier is followed by the per-column draws and
+// k_cols_turn_draw (q3_sampler.h), the greedy plans and their launches untouched.
 
 namespace {
 
@@ -73,25 +75,26 @@ int cols_width_index(int n) {
     return w;
 }
 
-// what every entry point of section 2e refuses
-int cols_prepare(q3_engine* e, const char* who) {
+// what every entry point of section 2e refuses.  draw: the names of section 2f, which hold for any batch sampler
+int cols_prepare(q3_engine* e, const char* who, bool draw = false) {
     if (!e) return fail(Q3_ERR_ARG, "null engine");
     if (!e->batch || !e->batch->has_kv) return fail(Q3_ERR_ARG, "q3_batch_init has not been called");
     if (e->flags & Q3_FLAG_FAST)
         return fail(Q3_ERR_UNSUPPORTED, "%s needs a reference-order engine: with Q3_FLAG_FAST the block kernels and the decode kernels are not bit-equal", who);
-    if (e->batch->sampling)
+    if (e->batch->sampling && !draw)
         return fail(Q3_ERR_UNSUPPORTED, "%s is greedy only: the batch sampler is set to a temperature > 0", who);
     return Q3_OK;
 }
 
 // the plan of width kColsWidths[wi], built on first use.  batch_build_plan leaves it in b->plan / b->graph: it moves to the
 // cache, and the shared plan is marked stale (the next decode / prefill / verify call rebuilds its own, as after any change of kind).
-int cols_plan_get(q3_engine* e, int wi, ColsPlan** out) {
+// draw: the sampled plan of that width (cols_draw_alloc has run: its launches carry the buffers allocated there).
+int cols_plan_get(q3_engine* e, int wi, ColsPlan** out, bool draw = false) {
     BatchCtx* b = e->batch;
-    ColsPlan& p = b->cols_plans[wi];
+    ColsPlan& p = draw ? b->cols_plans_draw[wi] : b->cols_plans[wi];
     if (p.plan.empty()) {
         HIP_TRY(hipSetDevice(e->device));
-        const int rc = batch_build_plan(e, kColsWidths[wi], PlanKind::Cols);
+        const int rc = batch_build_plan(e, kColsWidths[wi], PlanKind::Cols, draw);
         if (rc == Q3_OK) {
             p.plan.swap(b->plan);
             p.graph.swap(b->graph);
@@ -123,15 +126,30 @@ int cols_grow(T*& ptr, size_t& cap, size_t need) {
     return Q3_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int q3_batch_step_cols(q3_engine* e, const int32_t* slots, const int32_t* tokens, const int32_t* pos, int n_cols, float* logits_out,
-                       int32_t* next_out) {
-    g_err[0] = 0;
+// The buffers of the sampled passes, on first use: the column sampler states and the draw scratch of the verify pass
+// (spec_draw_alloc, 32 columns wide whatever max_streams is), the control block of k_cols_turn_draw, the one-pass table of a
+// host-made pass and the loop's per-slot sampler states.  Freed with the context.
+int cols_draw_alloc(q3_engine* e) {
+    BatchCtx* b = e->batch;
     int rc;
-    if ((rc = cols_prepare(e, "q3_batch_step_cols"))) return rc;
+    if (!b->spec_samp && (rc = spec_draw_alloc(e))) return rc;
+    if (b->h_cols_draw) return Q3_OK;
+    HIP_TRY(hipSetDevice(e->device));
+    if (!b->cols_draw) HIP_TRY(hipMalloc((void**)&b->cols_draw, sizeof(ColsDraw)));
+    HIP_TRY(hipMemsetAsync(b->cols_draw, 0, sizeof(ColsDraw), e->stream));
+    if (!b->cols_step) HIP_TRY(hipMalloc((void**)&b->cols_step, sizeof(ColsStep)));
+    if (!b->cols_slot_samp) HIP_TRY(hipMalloc((void**)&b->cols_slot_samp, sizeof(SamplerState) * kMaxStreams));
+    HIP_TRY(hipMemsetAsync(b->cols_slot_samp, 0, sizeof(SamplerState) * kMaxStreams, e->stream));
+    HIP_TRY(hipHostMalloc((void**)&b->h_cols_draw, sizeof(ColsDrawHost), hipHostMallocDefault));
+    return Q3_OK;
+}
+
+// One host-made pass.  draw = false: the states and the slot table are written here and the greedy plan commits the argmaxes.
+// draw = true: the pass goes through a one-pass table, set up by a k_cols_turn_draw launch in front of the sampled plan -- the
+// column sampler states derive from the slot states in device memory (the batch sampler's d_sampler: slot i = stream i).
+int cols_step(q3_engine* e, const int32_t* slots, const int32_t* tokens, const int32_t* pos, int n_cols, const uint8_t* keep, float* logits_out,
+              int32_t* next_out, bool draw) {
+    int rc;
     BatchCtx* b = e->batch;
     if (!slots || !tokens || !pos) return fail(Q3_ERR_ARG, "null argument");
     if (n_cols < 1 || n_cols > kColsMax) return fail(Q3_ERR_ARG, "n_cols %d out of range (1..%d)", n_cols, kColsMax);
@@ -149,25 +167,52 @@ int q3_batch_step_cols(q3_engine* e, const int32_t* slots, const int32_t* tokens
             seen[slots[j]] = true;
         }
     }
+    if (draw && (rc = cols_draw_alloc(e))) return rc;
     ColsPlan* plan;
-    if ((rc = cols_plan_get(e, cols_width_index(n_cols), &plan))) return rc;
+    if ((rc = cols_plan_get(e, cols_width_index(n_cols), &plan, draw))) return rc;
     HIP_TRY(hipSetDevice(e->device));
     ColsHost* h = b->h_cols;
     memset(&h->ctl, 0, sizeof(ColsCtl));
-    h->ctl.n_live = n_cols;
-    for (int j = 0; j < kColsMax; ++j) {
-        const int i = j < n_cols ? j : n_cols - 1;           // pads repeat the last live column: the same bits to the same rows
-        h->ctl.out[j] = -1;
-        h->st[j].token = tokens[i];
-        h->st[j].pos = pos[i];
-        h->st[j].step = 0;
-        h->st[j].prompt_len = 0;
-        h->st[j].argmax = 0ull;
-        h->slot[j] = slots[i];
+    if (draw) {
+        ColsDrawHost* hd = b->h_cols_draw;
+        h->ctl.n_passes = 1;
+        h->ctl.table = b->cols_step->table;
+        h->ctl.ncols = &b->cols_step->ncols;
+        h->ctl.prompts = b->cols_step->tokens;
+        memset(&hd->dr, 0, sizeof(ColsDraw));
+        hd->dr.slot_ss = b->d_sampler;
+        hd->dr.aux = b->cols_step->aux;
+        hd->step.ncols = n_cols;
+        for (int j = 0; j < kColsMax; ++j) {
+            const int i = j < n_cols ? j : n_cols - 1;       // pads repeat the last live column and neither draw nor commit
+            hd->step.table[j] = ColEnt{slots[i], pos[i], i, -1};
+            hd->step.tokens[j] = tokens[i];
+            ColAux& x = hd->step.aux[j];
+            x.req = -1;
+            x.k = (i > 0 && slots[i] == slots[i - 1]) ? hd->step.aux[i - 1].k + 1 : 0;
+            x.keep = j < n_cols && (!keep || keep[j]) ? 1 : 0;
+            x.last = j < n_cols && (j == n_cols - 1 || slots[j + 1] != slots[j]) ? 1 : 0;
+        }
+        HIP_TRY(hipMemcpyAsync(b->cols_ctl, &h->ctl, sizeof(ColsCtl), hipMemcpyHostToDevice, e->stream));
+        HIP_TRY(hipMemcpyAsync(b->cols_draw, &hd->dr, sizeof(ColsDraw), hipMemcpyHostToDevice, e->stream));
+        HIP_TRY(hipMemcpyAsync(b->cols_step, &hd->step, sizeof(ColsStep), hipMemcpyHostToDevice, e->stream));
+        if ((rc = launch_now(e->stream, k_cols_turn_draw, dim3(1), dim3(kWG), 0, b->cols_ctl, b->cols_draw, b->spec_samp, b->st, b->col_slot))) return rc;
+    } else {
+        h->ctl.n_live = n_cols;
+        for (int j = 0; j < kColsMax; ++j) {
+            const int i = j < n_cols ? j : n_cols - 1;           // pads repeat the last live column: the same bits to the same rows
+            h->ctl.out[j] = -1;
+            h->st[j].token = tokens[i];
+            h->st[j].pos = pos[i];
+            h->st[j].step = 0;
+            h->st[j].prompt_len = 0;
+            h->st[j].argmax = 0ull;
+            h->slot[j] = slots[i];
+        }
+        HIP_TRY(hipMemcpyAsync(b->cols_ctl, &h->ctl, sizeof(ColsCtl), hipMemcpyHostToDevice, e->stream));
+        HIP_TRY(hipMemcpyAsync(b->st, h->st, sizeof(State) * kColsMax, hipMemcpyHostToDevice, e->stream));
+        HIP_TRY(hipMemcpyAsync(b->col_slot, h->slot, 4 * kColsMax, hipMemcpyHostToDevice, e->stream));
     }
-    HIP_TRY(hipMemcpyAsync(b->cols_ctl, &h->ctl, sizeof(ColsCtl), hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipMemcpyAsync(b->st, h->st, sizeof(State) * kColsMax, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipMemcpyAsync(b->col_slot, h->slot, 4 * kColsMax, hipMemcpyHostToDevice, e->stream));
     if ((rc = cols_enqueue(e, *plan))) return rc;
     const size_t V = e->cfg.vocab_size;
     if (logits_out) HIP_TRY(hipMemcpyAsync(b->h_logits, b->logits, 4 * V * (size_t)n_cols, hipMemcpyDeviceToHost, e->stream));
@@ -177,6 +222,138 @@ int q3_batch_step_cols(q3_engine* e, const int32_t* slots, const int32_t* tokens
     if (next_out)
         for (int j = 0; j < n_cols; ++j) next_out[j] = h->ctl.next[j];
     return Q3_OK;
+}
+
+// The device-resident loop of q3_generate_many_greedy (temperature == nullptr) and q3_generate_many_sampled: the same schedule and
+// table; under the sampler a parallel table of ColAux, the per-request sampler parameters and the sampled plans.
+int cols_generate(q3_engine* e, const int32_t* prompts, const size_t* prompt_len, const size_t* n_new, size_t n_requests, const float* temperature,
+                  const float* topp, const uint64_t* seeds, int32_t* out_tokens, q3_cols_stats* stats) {
+    int rc;
+    const bool draw = temperature != nullptr;
+    BatchCtx* b = e->batch;
+    if (!prompts || !out_tokens) return fail(Q3_ERR_ARG, "null argument");
+    if ((rc = cols_schedule_check(prompt_len, n_new, n_requests, b->max_streams))) return rc;
+    std::vector<size_t> p_off(n_requests), o_off(n_requests);
+    size_t n_prompt = 0, n_out = 0;
+    for (size_t r = 0; r < n_requests; ++r) {
+        if (prompt_len[r] + n_new[r] - 1 > (size_t)b->ctx)
+            return fail(Q3_ERR_ARG, "request %zu: prompt of %zu + %zu new tokens exceeds seq_len %d", r, prompt_len[r], n_new[r], b->ctx);
+        p_off[r] = n_prompt;
+        o_off[r] = n_out;
+        n_prompt += prompt_len[r];
+        n_out += n_new[r];
+    }
+    for (size_t i = 0; i < n_prompt; ++i)
+        if (prompts[i] < 0 || prompts[i] >= e->cfg.vocab_size)
+            return fail(Q3_ERR_ARG, "index out of range: token %d (vocab_size %d)", prompts[i], e->cfg.vocab_size);
+    if (n_prompt > (size_t)INT32_MAX || n_out > (size_t)INT32_MAX) return fail(Q3_ERR_ARG, "more than 2^31 tokens in one call");
+
+    // the pass table: kColsMax entries per pass, pads repeat the pass's last live column and emit nothing
+    std::vector<ColEnt> table;
+    std::vector<ColAux> aux;
+    std::vector<int> ncols;
+    q3_cols_stats st;
+    cols_schedule_run(prompt_len, n_new, n_requests, b->max_streams, [&](uint64_t pass, int slot, size_t pos, size_t req) {
+        if (pass == ncols.size()) {
+            ncols.push_back(0);
+            table.resize(table.size() + kColsMax);
+            if (draw) aux.resize(table.size());
+        }
+        ColEnt c;
+        c.slot = slot;
+        c.pos = (int)pos;
+        c.src = pos < prompt_len[req] ? (int)(p_off[req] + pos) : -1;
+        c.out = pos + 1 >= prompt_len[req] ? (int)(o_off[req] + (pos + 1 - prompt_len[req])) : -1;
+        const size_t at = (size_t)pass * kColsMax + ncols[pass]++;
+        table[at] = c;
+        if (draw) {          // a request enters at position 0; the run's earlier column is the entry in front (one run per slot)
+            const bool in_run = ncols[pass] > 1 && table[at - 1].slot == slot;
+            aux[at] = ColAux{pos == 0 ? (int)req : -1, in_run ? aux[at - 1].k + 1 : 0, c.out >= 0 ? 1 : 0, 1};
+            if (in_run) aux[at - 1].last = 0;
+        }
+    }, st);
+    const size_t n_passes = ncols.size();
+    bool width_used[kColsNW] = {false};
+    for (size_t p = 0; p < n_passes; ++p) {
+        ColEnt pad = table[p * kColsMax + ncols[p] - 1];
+        pad.out = -1;
+        for (int j = ncols[p]; j < kColsMax; ++j) table[p * kColsMax + j] = pad;
+        if (draw)
+            for (int j = ncols[p]; j < kColsMax; ++j) aux[p * kColsMax + j] = ColAux{-1, aux[p * kColsMax + ncols[p] - 1].k, 0, 0};
+        width_used[cols_width_index(ncols[p])] = true;
+    }
+    // every plan the call needs exists before the first pass is enqueued
+    if (draw && (rc = cols_draw_alloc(e))) return rc;
+    ColsPlan* plans[kColsNW] = {nullptr};
+    for (int w = 0; w < kColsNW; ++w)
+        if (width_used[w] && (rc = cols_plan_get(e, w, &plans[w], draw))) return rc;
+
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipStreamSynchronize(e->stream));              // nothing in flight reads the buffers that may be re-allocated
+    if ((rc = cols_grow(b->cols_table, b->cols_table_cap, n_passes * kColsMax))) return rc;
+    if ((rc = cols_grow(b->cols_ncols, b->cols_ncols_cap, n_passes))) return rc;
+    if ((rc = cols_grow(b->cols_prompts, b->cols_prompts_cap, n_prompt))) return rc;
+    if ((rc = cols_grow(b->cols_out, b->cols_out_cap, n_out))) return rc;
+    // the only uploads of the call
+    HIP_TRY(hipMemcpyAsync(b->cols_table, table.data(), sizeof(ColEnt) * n_passes * kColsMax, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(b->cols_ncols, ncols.data(), 4 * n_passes, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(b->cols_prompts, prompts, 4 * n_prompt, hipMemcpyHostToDevice, e->stream));
+    if (draw) {
+        if ((rc = cols_grow(b->cols_aux, b->cols_aux_cap, n_passes * kColsMax))) return rc;
+        if ((rc = cols_grow(b->cols_temp, b->cols_temp_cap, n_requests))) return rc;
+        if ((rc = cols_grow(b->cols_topp, b->cols_topp_cap, n_requests))) return rc;
+        if ((rc = cols_grow(b->cols_seeds, b->cols_seeds_cap, n_requests))) return rc;
+        HIP_TRY(hipMemcpyAsync(b->cols_aux, aux.data(), sizeof(ColAux) * n_passes * kColsMax, hipMemcpyHostToDevice, e->stream));
+        HIP_TRY(hipMemcpyAsync(b->cols_temp, temperature, 4 * n_requests, hipMemcpyHostToDevice, e->stream));
+        HIP_TRY(hipMemcpyAsync(b->cols_topp, topp, 4 * n_requests, hipMemcpyHostToDevice, e->stream));
+        HIP_TRY(hipMemcpyAsync(b->cols_seeds, seeds, 8 * n_requests, hipMemcpyHostToDevice, e->stream));
+        ColsDraw& dr = b->h_cols_draw->dr;
+        memset(&dr, 0, sizeof(ColsDraw));
+        dr.slot_ss = b->cols_slot_samp;
+        dr.aux = b->cols_aux;
+        dr.temperature = b->cols_temp;
+        dr.topp = b->cols_topp;
+        dr.seeds = b->cols_seeds;
+        HIP_TRY(hipMemcpyAsync(b->cols_draw, &dr, sizeof(ColsDraw), hipMemcpyHostToDevice, e->stream));
+    }
+    ColsHost* h = b->h_cols;
+    memset(&h->ctl, 0, sizeof(ColsCtl));
+    h->ctl.n_passes = (int)n_passes;
+    h->ctl.table = b->cols_table;
+    h->ctl.ncols = b->cols_ncols;
+    h->ctl.prompts = b->cols_prompts;
+    h->ctl.out_tokens = b->cols_out;
+    HIP_TRY(hipMemcpyAsync(b->cols_ctl, &h->ctl, sizeof(ColsCtl), hipMemcpyHostToDevice, e->stream));
+    // pass 0 is set up by a launch of its own (nothing to commit); every later pass by the k_cols_turn that ends the pass before it
+    if (draw) {
+        if ((rc = launch_now(e->stream, k_cols_turn_draw, dim3(1), dim3(kWG), 0, b->cols_ctl, b->cols_draw, b->spec_samp, b->st, b->col_slot))) return rc;
+    } else if ((rc = launch_now(e->stream, k_cols_turn, dim3(1), dim3(kWG), 0, b->cols_ctl, b->slots, b->nslots, 0, b->st, b->col_slot))) return rc;
+    for (size_t p = 0; p < n_passes; ++p)
+        if ((rc = cols_enqueue(e, *plans[cols_width_index(ncols[p])]))) return rc;
+    HIP_TRY(hipMemcpyAsync(out_tokens, b->cols_out, 4 * n_out, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    if (stats) *stats = st;
+    return Q3_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int q3_batch_step_cols(q3_engine* e, const int32_t* slots, const int32_t* tokens, const int32_t* pos, int n_cols, float* logits_out,
+                       int32_t* next_out) {
+    g_err[0] = 0;
+    int rc;
+    if ((rc = cols_prepare(e, "q3_batch_step_cols"))) return rc;
+    return cols_step(e, slots, tokens, pos, n_cols, nullptr, logits_out, next_out, false);
+}
+
+int q3_batch_step_cols_draw(q3_engine* e, const int32_t* slots, const int32_t* tokens, const int32_t* pos, int n_cols, const uint8_t* keep,
+                            float* logits_out, int32_t* next_out) {
+    g_err[0] = 0;
+    int rc;
+    if ((rc = cols_prepare(e, "q3_batch_step_cols_draw", true))) return rc;
+    return cols_step(e, slots, tokens, pos, n_cols, keep, logits_out, next_out, e->batch->sampling);   // temperature 0: the greedy pass
 }
 
 int q3_cols_schedule(const size_t* prompt_len, const size_t* n_new, size_t n_requests, int max_streams, int32_t* table, size_t cap,
@@ -207,79 +384,22 @@ int q3_generate_many_greedy(q3_engine* e, const int32_t* prompts, const size_t* 
     if (stats) *stats = q3_cols_stats{0, 0, 0, 0};
     int rc;
     if ((rc = cols_prepare(e, "q3_generate_many_greedy"))) return rc;
-    BatchCtx* b = e->batch;
-    if (!prompts || !out_tokens) return fail(Q3_ERR_ARG, "null argument");
-    if ((rc = cols_schedule_check(prompt_len, n_new, n_requests, b->max_streams))) return rc;
-    std::vector<size_t> p_off(n_requests), o_off(n_requests);
-    size_t n_prompt = 0, n_out = 0;
+    return cols_generate(e, prompts, prompt_len, n_new, n_requests, nullptr, nullptr, nullptr, out_tokens, stats);
+}
+
+int q3_generate_many_sampled(q3_engine* e, const int32_t* prompts, const size_t* prompt_len, const size_t* n_new, size_t n_requests,
+                             const float* temperature, const float* topp, const uint64_t* seeds, int32_t* out_tokens, q3_cols_stats* stats) {
+    g_err[0] = 0;
+    if (stats) *stats = q3_cols_stats{0, 0, 0, 0};
+    int rc;
+    if ((rc = cols_prepare(e, "q3_generate_many_sampled", true))) return rc;
+    if (!temperature || !topp || !seeds) return fail(Q3_ERR_ARG, "null argument");
+    if (!prompt_len || !n_new || n_requests == 0) return fail(Q3_ERR_ARG, "null or empty request list");
     for (size_t r = 0; r < n_requests; ++r) {
-        if (prompt_len[r] + n_new[r] - 1 > (size_t)b->ctx)
-            return fail(Q3_ERR_ARG, "request %zu: prompt of %zu + %zu new tokens exceeds seq_len %d", r, prompt_len[r], n_new[r], b->ctx);
-        p_off[r] = n_prompt;
-        o_off[r] = n_out;
-        n_prompt += prompt_len[r];
-        n_out += n_new[r];
+        if (!(temperature[r] >= 0.0f)) return fail(Q3_ERR_ARG, "request %zu: Temperature must be non-negative", r);
+        if (!(topp[r] >= 0.0f && topp[r] <= 1.0f)) return fail(Q3_ERR_ARG, "request %zu: Top-p must be between 0.0 and 1.0", r);
     }
-    for (size_t i = 0; i < n_prompt; ++i)
-        if (prompts[i] < 0 || prompts[i] >= e->cfg.vocab_size)
-            return fail(Q3_ERR_ARG, "index out of range: token %d (vocab_size %d)", prompts[i], e->cfg.vocab_size);
-    if (n_prompt > (size_t)INT32_MAX || n_out > (size_t)INT32_MAX) return fail(Q3_ERR_ARG, "more than 2^31 tokens in one call");
-
-    // the pass table: kColsMax entries per pass, pads repeat the pass's last live column and emit nothing
-    std::vector<ColEnt> table;
-    std::vector<int> ncols;
-    q3_cols_stats st;
-    cols_schedule_run(prompt_len, n_new, n_requests, b->max_streams, [&](uint64_t pass, int slot, size_t pos, size_t req) {
-        if (pass == ncols.size()) {
-            ncols.push_back(0);
-            table.resize(table.size() + kColsMax);
-        }
-        ColEnt c;
-        c.slot = slot;
-        c.pos = (int)pos;
-        c.src = pos < prompt_len[req] ? (int)(p_off[req] + pos) : -1;
-        c.out = pos + 1 >= prompt_len[req] ? (int)(o_off[req] + (pos + 1 - prompt_len[req])) : -1;
-        table[(size_t)pass * kColsMax + ncols[pass]++] = c;
-    }, st);
-    const size_t n_passes = ncols.size();
-    bool width_used[kColsNW] = {false};
-    for (size_t p = 0; p < n_passes; ++p) {
-        ColEnt pad = table[p * kColsMax + ncols[p] - 1];
-        pad.out = -1;
-        for (int j = ncols[p]; j < kColsMax; ++j) table[p * kColsMax + j] = pad;
-        width_used[cols_width_index(ncols[p])] = true;
-    }
-    // every plan the call needs exists before the first pass is enqueued
-    ColsPlan* plans[kColsNW] = {nullptr};
-    for (int w = 0; w < kColsNW; ++w)
-        if (width_used[w] && (rc = cols_plan_get(e, w, &plans[w]))) return rc;
-
-    HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(hipStreamSynchronize(e->stream));              // nothing in flight reads the buffers that may be re-allocated
-    if ((rc = cols_grow(b->cols_table, b->cols_table_cap, n_passes * kColsMax))) return rc;
-    if ((rc = cols_grow(b->cols_ncols, b->cols_ncols_cap, n_passes))) return rc;
-    if ((rc = cols_grow(b->cols_prompts, b->cols_prompts_cap, n_prompt))) return rc;
-    if ((rc = cols_grow(b->cols_out, b->cols_out_cap, n_out))) return rc;
-    // the only uploads of the call
-    HIP_TRY(hipMemcpyAsync(b->cols_table, table.data(), sizeof(ColEnt) * n_passes * kColsMax, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipMemcpyAsync(b->cols_ncols, ncols.data(), 4 * n_passes, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipMemcpyAsync(b->cols_prompts, prompts, 4 * n_prompt, hipMemcpyHostToDevice, e->stream));
-    ColsHost* h = b->h_cols;
-    memset(&h->ctl, 0, sizeof(ColsCtl));
-    h->ctl.n_passes = (int)n_passes;
-    h->ctl.table = b->cols_table;
-    h->ctl.ncols = b->cols_ncols;
-    h->ctl.prompts = b->cols_prompts;
-    h->ctl.out_tokens = b->cols_out;
-    HIP_TRY(hipMemcpyAsync(b->cols_ctl, &h->ctl, sizeof(ColsCtl), hipMemcpyHostToDevice, e->stream));
-    // pass 0 is set up by a launch of its own (nothing to commit); every later pass by the k_cols_turn that ends the pass before it
-    if ((rc = launch_now(e->stream, k_cols_turn, dim3(1), dim3(kWG), 0, b->cols_ctl, b->slots, b->nslots, 0, b->st, b->col_slot))) return rc;
-    for (size_t p = 0; p < n_passes; ++p)
-        if ((rc = cols_enqueue(e, *plans[cols_width_index(ncols[p])]))) return rc;
-    HIP_TRY(hipMemcpyAsync(out_tokens, b->cols_out, 4 * n_out, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    if (stats) *stats = st;
-    return Q3_OK;
+    return cols_generate(e, prompts, prompt_len, n_new, n_requests, temperature, topp, seeds, out_tokens, stats);
 }
 
 }  // extern "C"

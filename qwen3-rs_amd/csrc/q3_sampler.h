@@ -732,4 +732,95 @@ __global__ void k_spec_commit_draw(SpecIO* io, const State* __restrict__ st, con
     es->rng = cs[a].rng;
 }
 
+// ---- column passes under the sampler (q3_batch_step_cols_draw / q3_generate_many_sampled): the column pass of q3_batch.h with the
+// per-column draws above in place of the argmax.  Every KV slot has a sampler state (temperature, top-p, rng); column j at index k
+// of its slot's run is drawn with a state of its own, the slot's with the rng advanced k coins, and after the pass the slot's
+// rng is the state of the run's last column behind its coin: advanced by the run's length.  Interior prompt columns consume their
+// coin and draw nothing (generation.rs:116-123: the prompt loop's discarded samples), temperature-0 slots take the argmax.
+struct ColAux {
+    int req;                            // >= 0: the column is the first of request `req`, whose sampler the slot takes over; -1: none
+    int k;                              // index of the column in its run
+    int keep;                           // 1: the draw is made and kept; 0: the coin is consumed, nothing is drawn
+    int last;                           // 1: the last column of its run: its rng behind the coin becomes the slot's
+};
+enum { kColArgmax = 0, kColDrawn = 1, kColCoin = 2 };
+struct ColsDraw {
+    SamplerState* slot_ss;              // [max_streams] per KV slot
+    const ColAux* aux;                  // [n_passes][kColsMax], next to ColsCtl::table; padding columns: {-1, *, 0, 0}
+    const float* temperature;           // per request (read where ColAux::req >= 0 only)
+    const float* topp;
+    const unsigned long long* seeds;
+    int mode[kColsMax];                 // of the pass in flight: kColArgmax / kColDrawn / kColCoin
+    int last[kColsMax];                 // ColAux::last of the pass in flight
+};
+
+// k_cols_turn for a sampled plan, one workgroup, a thread per column.  Commit: the token of every live column -- the draw k_sample
+// left in State::token, the last-maximum fold k_spec_colmax left in State::argmax for a temperature-0 slot, -1 where only the
+// coin was taken -- stored where the table says, and the slot's rng.  Set-up of the next pass as k_cols_turn does it, plus the
+// sampler: a request's first column loads its (temperature, top-p, seed) into the slot, then every column gets its sampler state
+// and is marked as a discarded draw (State::prompt_len: k_sample_exp and k_sample return at once) unless it draws.  Temperature
+// and top-p are read here, at run time: a captured plan holds for any sampler setting.
+__global__ __launch_bounds__(kWG) void k_cols_turn_draw(ColsCtl* ctl, ColsDraw* dr, SamplerState* cs, State* st, int* col_slot) {
+    const int j = threadIdx.x;
+    const int n_live = ctl->n_live, p = ctl->cursor, n_passes = ctl->n_passes;
+    SamplerState* slot_ss = dr->slot_ss;
+    if (j < n_live) {
+        const int mode = dr->mode[j], slot = col_slot[j];
+        const int idx = mode == kColArgmax ? (int)(unsigned)(st[j].argmax & 0xffffffffull) : (mode == kColDrawn ? st[j].token : -1);
+        ctl->next[j] = idx;
+        const int o = ctl->out[j];
+        if (o >= 0) {
+            ctl->out_tokens[o] = idx;
+            ctl->slot_last[slot] = idx;
+        }
+        if (mode != kColArgmax && dr->last[j]) slot_ss[slot].rng = cs[j].rng;
+    }
+    __syncthreads();
+    if (p >= n_passes) {
+        if (j == 0) ctl->n_live = 0;
+        return;
+    }
+    ColEnt e{};
+    ColAux x{};
+    if (j < kColsMax) {
+        e = ctl->table[(size_t)p * kColsMax + j];
+        x = dr->aux[(size_t)p * kColsMax + j];
+        if (x.req >= 0) {
+            SamplerState s{};
+            s.rng = dr->seeds[x.req];
+            s.temperature = dr->temperature[x.req];
+            s.topp = dr->topp[x.req];
+            slot_ss[e.slot] = s;
+        }
+    }
+    __syncthreads();
+    if (j < kColsMax) {
+        SamplerState s = slot_ss[e.slot];
+        unsigned long long rs = s.rng;
+        for (int k = 0; k < x.k; ++k) {
+            rs ^= rs >> 12;
+            rs ^= rs << 25;
+            rs ^= rs >> 27;
+        }
+        s.rng = rs;
+        cs[j] = s;
+        const int mode = s.temperature == 0.0f ? kColArgmax : (x.keep ? kColDrawn : kColCoin);
+        State t;
+        t.token = e.src >= 0 ? ctl->prompts[e.src] : ctl->slot_last[e.slot];
+        t.pos = e.pos;
+        t.step = 0;
+        t.prompt_len = mode == kColDrawn ? 0 : 1;
+        t.argmax = 0ull;
+        st[j] = t;
+        col_slot[j] = e.slot;
+        ctl->out[j] = e.out;
+        dr->mode[j] = mode;
+        dr->last[j] = x.last;
+    }
+    if (j == 0) {
+        ctl->n_live = ctl->ncols[p];
+        ctl->cursor = p + 1;
+    }
+}
+
 }  // namespace q3

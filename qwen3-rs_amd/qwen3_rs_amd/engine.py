@@ -27,6 +27,7 @@ EXPORTED_SYMBOLS = [
     "q3_verify", "q3_lookup_draft", "q3_lookup_trace", "q3_generate_lookup",
     "q3_verify_draw", "q3_generate_lookup_draw",
     "q3_batch_step_cols", "q3_cols_schedule", "q3_generate_many_greedy",
+    "q3_batch_step_cols_draw", "q3_generate_many_sampled",
 ]
 VERIFY_MAX = 32          # Q3_VERIFY_MAX
 COLS_MAX = 32            # Q3_COLS_MAX
@@ -198,6 +199,8 @@ def _bind(path: str) -> C.CDLL:
     L.q3_batch_step_cols.argtypes = [C.c_void_p, i32p, i32p, i32p, C.c_int, fp, i32p]
     L.q3_cols_schedule.argtypes = [szp, szp, sz, C.c_int, i32p, sz, szp, C.POINTER(_ColsStats)]
     L.q3_generate_many_greedy.argtypes = [C.c_void_p, i32p, szp, szp, sz, i32p, C.POINTER(_ColsStats)]
+    L.q3_batch_step_cols_draw.argtypes = [C.c_void_p, i32p, i32p, i32p, C.c_int, u8p, fp, i32p]
+    L.q3_generate_many_sampled.argtypes = [C.c_void_p, i32p, szp, szp, sz, fp, fp, C.POINTER(C.c_uint64), i32p, C.POINTER(_ColsStats)]
     L.q3_profile.argtypes = [C.c_void_p, sz, sz, C.c_int, fp, C.POINTER(C.c_int32), C.c_int]
     L.q3_profile_name.argtypes = [C.c_int]
     L.q3_profile_name.restype = C.c_char_p
@@ -492,6 +495,52 @@ class Transformer:
         st = _ColsStats()
         self._batch_rc(self._lib.q3_generate_many_greedy(self._h, _i32_array(flat), _size_array([len(p) for p in prompts]), _size_array(n_new),
                                                          len(prompts), out, C.byref(st)))
+        rows, at = [], 0
+        for k in n_new:
+            rows.append([int(out[at + i]) for i in range(int(k))])
+            at += int(k)
+        return rows, ColsStats(st.passes, st.live_columns, st.prompt_columns, st.decode_columns)
+
+    # ---- column passes under the sampler (include/qwen3_hip.h section 2f)
+    def batch_step_cols_draw(self, slots, tokens, pos, keep=None, want_logits: bool = False):
+        """batch_step_cols under the per-slot samplers of set_batch_sampler (q3_batch_step_cols_draw): column j at index k of its
+        slot's run is drawn with the slot's rng advanced k coins, and the slot's rng moves on by the run's length.  keep: one
+        flag per column (None = all kept); a column with keep 0 consumes its coin, draws nothing and returns -1.  Returns the
+        list of draws or, with want_logits, (raw logits [n, vocab], draws)."""
+        n = len(slots)
+        if not (len(tokens) == n and len(pos) == n and (keep is None or len(keep) == n)):
+            raise ValueError("one token, one position and one keep flag per column")
+        nxt = (C.c_int32 * max(1, n))()
+        kp = None if keep is None else (C.c_uint8 * max(1, n))(*[1 if k else 0 for k in keep])
+        logits = np.zeros((n, self._config.vocab_size), dtype=np.float32) if want_logits else None
+        lp = logits.ctypes.data_as(C.POINTER(C.c_float)) if want_logits else None
+        self._batch_rc(self._lib.q3_batch_step_cols_draw(self._h, _i32_array(slots), _i32_array(tokens), _i32_array(pos), n, kp, lp, nxt))
+        out = [int(nxt[i]) for i in range(n)]
+        return (logits, out) if want_logits else out
+
+    def generate_many_sampled(self, prompts, n_new, temperature, topp, seeds):
+        """generate_many_greedy with one sampler per request (q3_generate_many_sampled): request r is drawn as a fresh engine after
+        set_sampler(temperature[r], topp[r], seeds[r]) draws prefill + generate_greedy; temperature 0 makes a request greedy.
+        temperature / topp / seeds: one value per request, or a scalar for all.  Returns (rows, ColsStats).  The per-stream
+        states of set_batch_sampler are unspecified afterwards: set them again before using them."""
+        n = len(prompts)
+        if len(n_new) != n:
+            raise ValueError("one n_new per prompt")
+
+        def per_request(v, what):
+            vals = [v] * n if np.isscalar(v) else list(v)
+            if len(vals) != n:
+                raise ValueError(f"one {what} per request, or a scalar")
+            return vals
+        tv = (C.c_float * max(1, n))(*[float(v) for v in per_request(temperature, "temperature")])
+        pv = (C.c_float * max(1, n))(*[float(v) for v in per_request(topp, "topp")])
+        sv = (C.c_uint64 * max(1, n))(*[int(v) & 0xFFFFFFFFFFFFFFFF for v in per_request(seeds, "seed")])
+        flat = [int(t) for p in prompts for t in p]
+        total = sum(int(k) for k in n_new)
+        out = (C.c_int32 * max(1, total))()
+        st = _ColsStats()
+        self._batch_rc(self._lib.q3_generate_many_sampled(self._h, _i32_array(flat), _size_array([len(p) for p in prompts]), _size_array(n_new),
+                                                          n, tv, pv, sv, out, C.byref(st)))
         rows, at = [], 0
         for k in n_new:
             rows.append([int(out[at + i]) for i in range(int(k))])

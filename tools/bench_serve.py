@@ -10,7 +10,15 @@ Every model is measured in a child process of its own under a time limit (one fa
       q3_forward_batch, one token per stream and weight pass, a slot refilled when its request ends, one host round trip per
       step: 8 requests of 256 prompt tokens + 64 new through 8 slots, and 64 requests of mixed lengths through 32 slots.  Passes
       and tok/s (prompt + generated tokens per second, and generated tokens per second) for both; the tokens must be equal.
-Writes <out>/serve_cols.json and serve_cols.md (a batch-32 A/B section already in the .md is kept).
+Writes <out>/serve_cols.json and serve_cols.md (a batch-32 A/B section and a sampler section already in the .md are kept).
+
+    python tools/bench_serve.py --temperature 0.6 --topp 0.95 [--models qwen3-0.6b]
+
+The same workloads under the sampler (section 2f).  Per model: (c) the wall time of a q3_batch_step_cols_draw pass of 1, 8 and 32
+single-position columns with one column and with all columns drawing, against the greedy q3_batch_step_cols pass of the same
+width (temperature 0 set on the same engine); (d) the two request workloads through q3_generate_many_sampled against
+q3_generate_many_greedy.  Appends a section to <out>/serve_cols.md (an earlier section of the same name is replaced, the rest of
+the file is kept) and writes <out>/serve_cols_sampled.json.
 """
 import argparse
 import json
@@ -23,6 +31,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "qwen3-rs_amd"))
 
 AB_MARK = "## Batch-32 decode A/B"
+SAMPLED_MARK = "## Under the sampler"
 
 
 def median(xs):
@@ -120,6 +129,99 @@ def worker(name, ctx, ckpt_dir, seed):
     print("RESULT " + json.dumps(res))
 
 
+def worker_sampled(name, ctx, ckpt_dir, seed, temperature, topp):
+    import numpy as np
+    import qwen3_rs_amd as q3
+    ck = q3.checkpoint
+    shape = ck.SHAPES[name]
+    path = os.path.join(ckpt_dir, f"{name}-seed{seed}.q3bin")
+    ck.ensure_synthetic_checkpoint(path, shape, seed=seed)
+    res = {"model": name, "ctx": ctx, "temperature": temperature, "topp": topp, "pass_ms": {}, "requests": {}}
+    rng = np.random.default_rng(7)
+    seeds = list(range(1, 33))
+
+    def timed(call):
+        call()
+        xs = []
+        for _ in range(15):
+            t0 = time.perf_counter()
+            call()
+            xs.append(time.perf_counter() - t0)
+        return 1e3 * median(xs)
+    with q3.TransformerBuilder(path).with_ctx_length(ctx).build() as t:
+        t.batch_init(32, ctx)
+        toks = [int(v) for v in rng.integers(0, shape.vocab_size, 32)]
+        for w in (1, 8, 32):
+            slots, tk, pos = list(range(w)), toks[:w], [8] * w
+            t.set_batch_sampler(0.0, topp, seeds)
+            greedy = timed(lambda: t.batch_step_cols(slots, tk, pos))
+            t.set_batch_sampler(temperature, topp, seeds)
+            one = timed(lambda: t.batch_step_cols_draw(slots, tk, pos, keep=[1] + [0] * (w - 1)))
+            every = timed(lambda: t.batch_step_cols_draw(slots, tk, pos))
+            res["pass_ms"][str(w)] = {"greedy": greedy, "one_draw": one, "all_draw": every}
+        t.set_batch_sampler(0.0, topp, seeds)
+        cases = {
+            "8x(256+64), 8 slots": ([256] * 8, [64] * 8, 8),
+            "64 mixed, 32 slots": ([int(v) for v in rng.integers(1, 200, 64)], [int(v) for v in rng.integers(1, 96, 64)], 32),
+        }
+        for label, (plen, nnew, ms) in cases.items():
+            prompts = [ck.iter_prompt_tokens(shape, seed + 50 + r, n) for r, n in enumerate(plen)]
+            rs = list(range(1, len(plen) + 1))
+            t.batch_init(ms, ctx)
+            n_tok, n_gen = sum(plen) + sum(nnew) - len(plen), sum(nnew)
+            out = {}
+            for k, call in (("greedy", lambda: t.generate_many_greedy(prompts, nnew)),
+                            ("sampled", lambda: t.generate_many_sampled(prompts, nnew, temperature, topp, rs))):
+                call()                                                 # plans
+                dts = []
+                for _ in range(2):
+                    t0 = time.perf_counter()
+                    _, st = call()
+                    dts.append(time.perf_counter() - t0)
+                out[k] = {"passes": st.passes, "seconds": min(dts), "tok_s": n_tok / min(dts), "gen_tok_s": n_gen / min(dts)}
+            res["requests"][label] = out
+    print("RESULT " + json.dumps(res))
+
+
+def main_sampled(a):
+    results = []
+    for name in a.models.split(","):
+        cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--worker", name, "--ctx", str(a.ctx),
+               "--ckpt-dir", a.ckpt_dir, "--seed", str(a.seed), "--temperature", str(a.temperature), "--topp", str(a.topp)]
+        p = subprocess.run(cmd, capture_output=True, text=True)
+        sys.stderr.write(p.stderr[-2000:])
+        if p.returncode != 0:
+            print(f"[bench_serve] {name}: exit status {p.returncode}; stopping here", file=sys.stderr)
+            break
+        results.append(json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")][-1][7:]))
+    os.makedirs(a.out, exist_ok=True)
+    with open(os.path.join(a.out, "serve_cols_sampled.json"), "w") as f:
+        json.dump(results, f, indent=1)
+    lines = [SAMPLED_MARK + f" (temperature {a.temperature}, top-p {a.topp})", "",
+             "Written by `tools/bench_serve.py --temperature --topp` (context %d per slot).  Wall time per call of one pass of" % a.ctx,
+             "single-position columns at position 8, no logits read back, median of 15 calls per form, the forms measured one after",
+             "the other on one engine: greedy = `q3_batch_step_cols` with the batch sampler at temperature 0.", "",
+             "| model | columns | greedy ms | 1 column draws ms | all columns draw ms |", "|---|---|---|---|---|"]
+    for r in results:
+        for w, d in r["pass_ms"].items():
+            lines.append(f"| {r['model']} | {w} | {d['greedy']:.3f} | {d['one_draw']:.3f} | {d['all_draw']:.3f} |")
+    lines += ["", "Requests through `q3_generate_many_sampled` against `q3_generate_many_greedy` (best of 2 calls each; tok/s counts",
+              "prompt + generated tokens):", "", "| model | requests | loop | passes | seconds | tok/s | gen tok/s |", "|---|---|---|---|---|---|---|"]
+    for r in results:
+        for label, d in r["requests"].items():
+            for k in ("greedy", "sampled"):
+                lines.append(f"| {r['model']} | {label} | {k} | {d[k]['passes']} | {d[k]['seconds']:.3f} | {d[k]['tok_s']:.0f} | {d[k]['gen_tok_s']:.0f} |")
+    md_path = os.path.join(a.out, "serve_cols.md")
+    old = open(md_path).read() if os.path.exists(md_path) else ""
+    if SAMPLED_MARK in old:                                            # replace the earlier section, up to the next heading of its level
+        at = old.index(SAMPLED_MARK)
+        nxt = old.find("\n## ", at + 1)
+        old = old[:at].rstrip("\n") + "\n" + (old[nxt:] if nxt >= 0 else "")
+    with open(md_path, "w") as f:
+        f.write(old.rstrip("\n") + "\n\n" + "\n".join(lines) + "\n")
+    return 0 if len(results) == len(a.models.split(",")) else 1
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--models", default="qwen3-0.6b,qwen3-8b")
@@ -129,7 +231,14 @@ def main():
     ap.add_argument("--seed", type=int, default=1236)
     ap.add_argument("--ckpt-dir", default=os.environ.get("Q3_CKPT_DIR", "/tmp"))
     ap.add_argument("--worker")
+    ap.add_argument("--temperature", type=float, help="with --topp: the workloads under the sampler (appends to serve_cols.md)")
+    ap.add_argument("--topp", type=float, default=0.95)
     a = ap.parse_args()
+    if a.temperature is not None:
+        if a.worker:
+            worker_sampled(a.worker, a.ctx, a.ckpt_dir, a.seed, a.temperature, a.topp)
+            return 0
+        return main_sampled(a)
     if a.worker:
         worker(a.worker, a.ctx, a.ckpt_dir, a.seed)
         return 0
@@ -150,8 +259,9 @@ def main():
     keep = ""
     if os.path.exists(md_path):
         old = open(md_path).read()
-        if AB_MARK in old:
-            keep = old[old.index(AB_MARK):]
+        marks = [old.index(m) for m in (AB_MARK, SAMPLED_MARK) if m in old]      # sections other runs wrote
+        if marks:
+            keep = old[min(marks):]
     lines = ["# Ragged column passes: pass cost and request throughput", "",
              "Written by `tools/bench_serve.py` (synthetic full-size checkpoints, one MI355X, context %d per slot)." % a.ctx, "",
              "## (a) One 32-column pass of 32 single-position slots against a `q3_forward_batch` step", "",
