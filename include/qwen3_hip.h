@@ -14,8 +14,8 @@
  * message.  There is NO CPU fallback: without a usable HIP device q3_create fails.
  *
  * Environment: libqwen3_hip.so reads exactly these variables (tests/test_host_and_abi.py checks the binary):
- *     Q3_PREFILL_M=<16..4096>   positions per weight pass of q3_prefill_batched (default 2048; <= 32 selects the batch-32
- *                               kernels).  The dense attention scratch grows with it: 4 * M * n_heads * context bytes.
+ *     Q3_PREFILL_M=<16..4096>   positions per weight pass of q3_prefill_batched and of section 2g (default 2048; <= 32 selects
+ *                               the batch-32 kernels).  The dense attention scratch grows with it: 4 * M * n_heads * context bytes.
  *     Q3_DEBUG_TIMING=1         host-side timing of q3_forward / q3_host_generate phases on stderr.
  *
  * Build options (qwen3-rs_amd/Makefile, `make abl EXTRA=-D... ABL=name` -> libq3_<name>.so; never part of libqwen3_hip.so):
@@ -469,6 +469,71 @@ int q3_batch_step_cols_draw(q3_engine* e, const int32_t* slots, const int32_t* t
 int q3_generate_many_sampled(q3_engine* e, const int32_t* prompts /* concatenated */, const size_t* prompt_len, const size_t* n_new,
                              size_t n_requests, const float* temperature, const float* topp, const uint64_t* seeds /* [n_requests] each */,
                              int32_t* out_tokens /* concatenated, n_new[r] each */, q3_cols_stats* stats);
+
+/* ------------------------------------------------------------------------------------------------
+ * 2g. (behind 2f so that the earlier sections stay as they were.)  Dense blocks over the slots: many prompts per weight pass.
+ * A column pass holds 32 columns, so a 2,048-token prompt enters its slot in 64 passes over the weights.  q3_prefill_batched
+ * moves such a prompt through the dense kernels in one block, but only into the single-stream cache.  Here the columns of a dense
+ * block are RUNS of several slots of section 2b's state: a run is a slot and consecutive ascending positions of that slot, a slot
+ * has at most one run in a block, every run starts at a column that is a multiple of 8, and the columns between a run's end and
+ * the next run's start (or the block's end, rounded up to 8) repeat the run's last column -- same slot, token and position, the
+ * same bits to the same rows: the pad rule of sections 2c and 2e.  Every column takes its cache base from a slot table as long
+ * as the block.  The standard is section 2e's: cache rows and every token are bit-identical to q3_prefill on a fresh engine,
+ * whichever slot a prompt lands in, whatever shares its block and whatever the slot held before.  A block forms no logits (the
+ * reference computes and discards them for prompt positions): a prompt's last token goes through a column pass.
+ * Blocks hold up to Q3_PREFILL_M columns (default 2,048, as for q3_prefill_batched).  Their scratch -- the per-column buffers and the
+ * attention score rows, 4 * M * n_heads * (largest first_pos + length of a call, rounded up to 256) bytes -- sits beside the
+ * 32-column scratch of q3_batch_init, is allocated by the first call that needs it and released with the batched state
+ * (q3_batch_init starts it over); using it rebuilds none of the kept plans of sections 2b, 2e and 2f.  A block of 32 columns or
+ * fewer is an ordinary column pass of its live columns (under a sampler every one with keep = 0); a shape the dense kernels do not
+ * take (group size other than 64, head_dim other than 128, other than 2 or 4 query heads per kv head) packs with a cap of 32, so
+ * every shape q3_batch_step_cols accepts works.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct q3_dense_stats { uint64_t blocks, live_columns, pad_columns; } q3_dense_stats;
+
+/* How runs are packed into blocks, as a pure function of the lengths (host only, never touches the GPU):
+ *   1. Runs are taken in index order.
+ *   2. A run starts at the next multiple of 8 behind the last piece of the current block; where that is block_cap, the block is
+ *      closed and the run starts the next one at column 0.
+ *   3. It takes min(what is left of it, block_cap - start) columns; what did not fit continues as the first piece of the next
+ *      block.  A run therefore never has two pieces in one block, and its pieces are consecutive in the table.
+ * A block's width is the end of its last piece rounded up to 8; pad_columns counts, over all blocks, width - live columns.
+ * table (may be NULL: count only): one entry {block, first column, run, offset in the run} per piece, in order; a piece ends where
+ * the run's next piece starts or the run ends.  *n_entries = the number of pieces whether or not they fit.  n_entries, stats may
+ * be NULL.  Q3_ERR_ARG: no run, a run_len of 0, block_cap below 16 or not a multiple of 16, a table smaller than the packing. */
+int q3_dense_pack(const size_t* run_len, size_t n_runs, int block_cap, int32_t* table /* [cap][4]: block, first column, run, offset in the run */,
+                  size_t cap, size_t* n_entries, q3_dense_stats* stats);
+
+/* Cache rows only: run r feeds tokens[run_len[0] + .. + run_len[r - 1] ..] into slot slots[r] at positions first_pos[r] ..
+ * first_pos[r] + run_len[r] - 1, the runs packed by q3_dense_pack with block_cap = Q3_PREFILL_M.  Afterwards those rows of the
+ * slot's key and value caches are bit-identical to what q3_prefill writes -- to what q3_forward of the same tokens at those
+ * positions writes on a fresh engine holding the same earlier rows -- and no other row of any slot has changed.  No logits, no
+ * token: send the prompt's last token through q3_batch_step_cols.
+ * Under a sampling batch (q3_batch_sampler_set, temperature > 0) the rng of slot slots[r] is advanced by run_len[r] coins, the
+ * rule of section 2f; q3_batch_step_cols_draw of the prompt's last token then draws the token q3_prefill returns.  With
+ * temperature 0, or no batch sampler, no rng is touched.  The call synchronises once.  stats may be NULL.
+ * Q3_ERR_ARG: no q3_batch_init; no run; a slot outside 0 .. max_streams - 1; a slot named twice; an empty run; a position at or past
+ * the batch context; a token outside the vocabulary.
+ * Q3_ERR_UNSUPPORTED: a Q3_FLAG_FAST engine; the shapes q3_batch_step_cols refuses. */
+int q3_batch_prefill_slots(q3_engine* e, const int32_t* slots, const int32_t* tokens /* concatenated */, const size_t* run_len,
+                           const int32_t* first_pos, size_t n_runs, q3_dense_stats* stats);
+
+/* q3_generate_many_greedy (temperature, topp and seeds all NULL) or q3_generate_many_sampled with long prompts entered through
+ * dense blocks.  The output layout and every output token are theirs, for any dense_min.
+ *   Request r is DENSE when dense_min > 0 and prompt_len[r] - 1 >= dense_min; dense_min == 0 runs the loops of sections 2e / 2f
+ *   unchanged.  The column schedule is q3_cols_schedule with a dense request's prompt length taken as 1: its one prompt column is
+ *   its last prompt token at position prompt_len[r] - 1, and its decode columns follow from there.
+ *   In front of every pass, the dense requests whose prompt column the pass holds are packed by q3_dense_pack in ascending
+ *   request index, each a run of prompt_len[r] - 1 tokens at position 0 of the slot the schedule gave it, and their blocks are
+ *   enqueued on the stream in front of the pass (a block of 32 columns or fewer as a column pass of its own).
+ *   Under the sampler a dense request's first column pass column loads its (temperature, top-p, seed) into the slot, and its
+ *   prompt column is drawn with the seed state advanced prompt_len[r] - 1 coins.
+ * The host knows all of this from the lengths: the loop stays device-resident and synchronises once.  stats counts the passes of
+ * the column schedule as q3_cols_schedule does for the lengths above; dstats the blocks (narrow ones included).  Either may be NULL.
+ * Errors as for q3_generate_many_greedy / q3_generate_many_sampled; some but not all of the three sampler arrays NULL: Q3_ERR_ARG. */
+int q3_generate_many_dense(q3_engine* e, const int32_t* prompts /* concatenated */, const size_t* prompt_len, const size_t* n_new,
+                           size_t n_requests, const float* temperature, const float* topp, const uint64_t* seeds /* all three NULL: greedy */,
+                           size_t dense_min, int32_t* out_tokens /* concatenated, n_new[r] each */, q3_cols_stats* stats, q3_dense_stats* dstats);
 
 #ifdef __cplusplus
 }

@@ -1681,9 +1681,15 @@ __global__ __launch_bounds__(64 * NP * (KVM / 2), NP * (KVM / 2) / 4) void k_att
     const int ast = a0.att_stride;
     const int pos = __builtin_amdgcn_readfirstlane(a0.st[pi].pos);
     const int pos_last = __builtin_amdgcn_readfirstlane(a0.st[min(pi0 + NP - 1, n_pos - 1)].pos);
-    const int np = pos + 1, np_max = pos_last + 1;                 // positions of a block are consecutive and ascending
-    const float* kbase = a0.key_cache + (size_t)kvh * hd;
-    const float* vbase = a0.value_cache + (size_t)kvh * hd;
+    // Within a workgroup positions are non-decreasing and all of one slot: a block is one ascending run (q3_prefill_batched), or runs
+    // of several slots that each start at a column that is a multiple of 8 >= NP, the columns up to the next run repeating the run's
+    // last one (dense_pack_run, q3_dense_host.inc).  So the workgroup's last column holds its largest position, and rows
+    // 0 .. np_max - 1 of that one slot are all that its waves read.  The host packing rule is what makes this hold.
+    const int np = pos + 1, np_max = pos_last + 1;
+    // a block over a slot table: runs start at multiples of 8 columns, so the workgroup's NP positions are one slot's (uniform: scalar)
+    const size_t kvs = col_slot_of(a0.col_slot, (size_t)pi0) * a0.sb_kv;
+    const float* kbase = a0.key_cache + kvs + (size_t)kvh * hd;
+    const float* vbase = a0.value_cache + kvs + (size_t)kvh * hd;
     GQA_STAMP(0);
     __builtin_amdgcn_s_dcache_inv();
     if (tid < 32) etab[tid] = kExp2Tab[tid];
@@ -2029,7 +2035,7 @@ __global__ __launch_bounds__(256) void k_knorm_rope_blk(const AttnArgs a, int n_
             dst_lo = a.q_out + ((size_t)p * a.n_heads + (size_t)(h & ~1)) * hd + (h & 1);     // pair-interleaved: [d][2]
             dstep = 2;
         } else {
-            dst_lo = a.key_cache + (size_t)pos * ((size_t)a.n_kv_heads * hd) + (size_t)hs * hd;
+            dst_lo = a.key_cache + col_slot_of(a.col_slot, (size_t)p) * a.sb_kv + (size_t)pos * ((size_t)a.n_kv_heads * hd) + (size_t)hs * hd;
             dstep = 1;
         }
 #pragma unroll
@@ -2056,6 +2062,32 @@ __global__ void k_set_prefill_states(State* st, const int32_t* prompt, int base,
         st[i].prompt_len = 0;
         st[i].argmax = 0ull;
     }
+}
+
+// A dense block over the per-stream caches (q3_batch_prefill_slots): its columns are runs, one per slot, every run starting at a
+// column that is a multiple of 8 (the larger NP of k_attn_pf2); the columns between a run's end and the next run's start, or
+// the block's end, repeat the run's last column -- same slot, token and position, the same bits to the same rows.
+struct DenseRun {
+    int col0, slot, pos0;               // first column of the run in its block, KV slot, position of its first token
+    int src0;                           // prompts[src0 ..): its tokens
+    int len;
+};
+// states and slot table of all n columns of such a block, pads included: a thread per column, runs ascending in col0
+__global__ void k_dense_states(State* st, int* col_slot, const DenseRun* __restrict__ runs, int n_runs, const int32_t* __restrict__ prompts, int n) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    int r = 0;
+    while (r + 1 < n_runs && runs[r + 1].col0 <= j) ++r;
+    const DenseRun R = runs[r];
+    const int i = min(j - R.col0, R.len - 1);
+    State s;
+    s.token = prompts[R.src0 + i];
+    s.pos = R.pos0 + i;
+    s.step = 0;
+    s.prompt_len = 0;
+    s.argmax = 0ull;
+    st[j] = s;
+    col_slot[j] = R.slot;
 }
 
 // per-stream k_next: grid = streams

@@ -10,7 +10,22 @@
 // sampler on (plan_draw), the per-column draws of the batched decode and k_spec_commit_draw stand in for k_spec_commit.
 // Cols: n columns of (slot, token, position) over the per-stream caches (q3_batch_step_cols): the prefill layers with the cache base
 // of every column taken from the slot table, the n-column classifier and k_cols_turn.  Its plans live in BatchCtx::cols_plans.
-enum class PlanKind { Decode, Prefill, Verify, Cols };
+// SlotPrefill: the dense Prefill layers over the per-stream caches, n > 32 columns of runs of several slots with a slot table as
+// long as the block (q3_batch_prefill_slots), on a scratch of their own (BatchCtx::dense); no classifier.  Its plans live in
+// BatchCtx::dense_plans.
+enum class PlanKind { Decode, Prefill, Verify, Cols, SlotPrefill };
+
+// the per-column buffers the layers of a plan work on: the context's own, or the dense block scratch of SlotPrefill
+struct BlockScratch {
+    float *x = nullptr, *q = nullptr, *qn = nullptr, *kraw = nullptr, *xb = nullptr, *hb = nullptr;
+    int8_t* xq_p = nullptr;
+    float* xs_p = nullptr;
+    State* st = nullptr;
+    int* col_slot = nullptr;
+    float* att_pf = nullptr;
+    int att_pf_stride = 0;
+    int cap = 0;                 // columns (SlotPrefill scratch; 0: not allocated)
+};
 
 // the plan widths of a column pass: a pass of n live columns runs the narrowest plan that holds it, padded with repeats of
 // its last column
@@ -100,6 +115,14 @@ struct BatchCtx {
     float *cols_temp = nullptr, *cols_topp = nullptr;
     unsigned long long* cols_seeds = nullptr;
     size_t cols_aux_cap = 0, cols_temp_cap = 0, cols_topp_cap = 0, cols_seeds_cap = 0;
+    // dense blocks over the per-stream caches (q3_batch_prefill_slots / q3_generate_many_dense): scratch of prefill_block_cap()
+    // columns beside the 32-column one, allocated on first use; plans by block width, kept (no graph: the launches are enqueued
+    // as they are, like q3_prefill_batched's); the run tables of a call, grow-only
+    BlockScratch dense;
+    int dense_cap = 0;           // columns per block, fixed by the first dense call (Q3_PREFILL_M as read then): packing and scratch agree
+    std::map<int, std::vector<Launch>> dense_plans;
+    DenseRun* dense_runs = nullptr;
+    size_t dense_runs_cap = 0;
     // packed-matrix directory
     struct PM { size_t q_off, s_off; int ntiles, ng; };
     std::vector<PM> m_qkv, m_wo, m_w13, m_w2;
@@ -191,7 +214,9 @@ void batch_free(q3_engine* e) {
     void* dptrs[] = {b->att_pf, b->qn, b->pq, b->ps, b->x, b->q, b->kraw, b->xb, b->hb, b->logits, b->key, b->value, b->att, b->xq_p, b->xs_p,
                      b->st, b->slots, b->out_tokens, b->stamps, b->d_sampler, b->d_probs, b->d_sp, b->d_keys, b->spec_io, b->spec_snap,
                      b->spec_samp, b->spec_probs, b->spec_sp, b->spec_keys, b->col_slot, b->cols_ctl, b->cols_table, b->cols_ncols, b->cols_prompts,
-                     b->cols_out, b->cols_draw, b->cols_step, b->cols_slot_samp, b->cols_aux, b->cols_temp, b->cols_topp, b->cols_seeds};
+                     b->cols_out, b->cols_draw, b->cols_step, b->cols_slot_samp, b->cols_aux, b->cols_temp, b->cols_topp, b->cols_seeds,
+                     b->dense.x, b->dense.q, b->dense.qn, b->dense.kraw, b->dense.xb, b->dense.hb, b->dense.xq_p, b->dense.xs_p, b->dense.st,
+                     b->dense.col_slot, b->dense.att_pf, b->dense_runs};
     for (void* p : dptrs)
         if (p) (void)hipFree(p);
     if (b->h_st) (void)hipHostFree(b->h_st);
@@ -205,12 +230,19 @@ void batch_free(q3_engine* e) {
 }
 
 // (re)build the launch list for n streams (Decode), n block positions (Prefill, Verify; draw: Verify under the sampler) or n
-// columns (Cols; draw: the sampled column plan)
+// columns (Cols; draw: the sampled column plan) or n columns of a dense block over the slots (SlotPrefill)
 int batch_build_plan(q3_engine* e, int n, PlanKind kind, bool draw = false) {
     BatchCtx* b = e->batch;
-    const bool cols = kind == PlanKind::Cols;
+    const bool cols = kind == PlanKind::Cols, slotpf = kind == PlanKind::SlotPrefill;
     const bool prefill = kind == PlanKind::Prefill || kind == PlanKind::Verify, verify = kind == PlanKind::Verify;
-    const bool block = prefill || cols;          // columns may share a cache: all key rows enter it before any column attends
+    const bool block = prefill || cols || slotpf;   // columns may share a cache: all key rows enter it before any column attends
+    BlockScratch sc = b->dense;
+    if (!slotpf) {
+        sc.x = b->x; sc.q = b->q; sc.qn = b->qn; sc.kraw = b->kraw; sc.xb = b->xb; sc.hb = b->hb;
+        sc.xq_p = b->xq_p; sc.xs_p = b->xs_p; sc.st = b->st;
+        sc.col_slot = cols ? b->col_slot : nullptr;
+        sc.att_pf = b->att_pf; sc.att_pf_stride = b->att_pf_stride;
+    }
     const q3_config& c = e->cfg;
     const int dim = c.dim, L = c.n_layers, hd = c.head_dim, V = c.vocab_size, H = c.hidden_dim, G = c.group_size;
     const int ahd = c.n_heads * hd, kvd = c.n_kv_heads * hd, S = prefill ? c.seq_len : b->ctx;
@@ -220,7 +252,7 @@ int batch_build_plan(q3_engine* e, int n, PlanKind kind, bool draw = false) {
     const int strict = (e->flags & Q3_FLAG_FAST) ? 0 : 1;
     const int NT = n <= 16 ? 1 : 2, NJ = G / 64;
     // dense prefill (round 3): more than 32 positions per weight pass -> every wave owns an output tile (k_pgemm)
-    const bool dense = prefill && n > 32;
+    const bool dense = (prefill || slotpf) && n > 32;
     // batched decode / short prefill blocks at group 64: in-lane accumulation for the residual launches (k_dgemm, round 4);
     // Q3_BATCH_DGEMM=0 keeps k_bgemm
     const bool dgemm = !dense && G == 64 && dev_knob("Q3_BATCH_DGEMM", 1) != 0;
@@ -256,16 +288,16 @@ int batch_build_plan(q3_engine* e, int n, PlanKind kind, bool draw = false) {
         a.n = nn;
         a.group = G;
         a.strict = strict;
-        a.st = b->st;
+        a.st = sc.st;
         a.seq_len = S;
         a.in = in;
         a.norm_w = norm_w;
-        if (embed) { a.emb_q = e->tok.q; a.emb_s = e->tok.s; a.x_out = b->x; }
+        if (embed) { a.emb_q = e->tok.q; a.emb_s = e->tok.s; a.x_out = sc.x; }
         BQuantArgs qa{};
         qa.in_stride = in_stride;
         qa.x_out_stride = dim;
-        qa.xq_p = b->xq_p;
-        qa.xs_p = b->xs_p;
+        qa.xq_p = sc.xq_p;
+        qa.xs_p = sc.xs_p;
         qa.n_streams = n;
         // several workgroups per stream (k_bquant_split): 4 parts for the RMSNorm prologues, 8 for the plain quantize --
         // as long as a part is a whole number of quantization groups and at most two float4 slots per thread
@@ -290,12 +322,12 @@ int batch_build_plan(q3_engine* e, int n, PlanKind kind, bool draw = false) {
     auto gemm = [&](Family fam, int epi, const BatchCtx::PM& m, BGemmArgs a) -> int {
         a.wq = b->pq + m.q_off;
         a.ws = b->ps + m.s_off;
-        a.xq = b->xq_p;
-        a.xs = b->xs_p;
+        a.xq = sc.xq_p;
+        a.xs = sc.xs_p;
         a.ng = m.ng;
         a.ntiles = m.ntiles;
         a.n_streams = n;
-        a.st = b->st;
+        a.st = sc.st;
         BGemmFn fn = nullptr;
         unsigned grid = 1, block = 0;
         size_t smem = 0;
@@ -374,28 +406,28 @@ int batch_build_plan(q3_engine* e, int n, PlanKind kind, bool draw = false) {
     for (int l = 0; l < L; ++l) {
         const size_t kv_off = (size_t)l * S * kvd;
         bool fused_xb_quant = false;
-        if ((rc = quant(F_QKV, l == 0 ? PRO_EMBED_NORM : PRO_NORM, b->x, dim, dim, e->rms_att + (size_t)l * dim))) return rc;
+        if ((rc = quant(F_QKV, l == 0 ? PRO_EMBED_NORM : PRO_NORM, sc.x, dim, dim, e->rms_att + (size_t)l * dim))) return rc;
         {
             BGemmArgs a{};
-            a.out0 = b->q; a.out0_stride = ahd;
-            a.out1 = b->kraw; a.out1_stride = kvd;
+            a.out0 = sc.q; a.out0_stride = ahd;
+            a.out1 = sc.kraw; a.out1_stride = kvd;
             a.out2 = value_base + kv_off; a.out2_stride = kv_stride;
             a.rows0 = ahd; a.rows1 = kvd; a.pos_stride = kvd;
-            a.col_slot = cols ? b->col_slot : nullptr;
+            a.col_slot = sc.col_slot;
             if ((rc = gemm(F_QKV, EPI_QKV, b->m_qkv[l], a))) return rc;
         }
         {
             AttnArgs a{};
-            a.q = b->q;
+            a.q = sc.q;
             a.key_cache = key_base + kv_off;
-            a.k_raw = b->kraw;
+            a.k_raw = sc.kraw;
             a.value_cache = value_base + kv_off;
             a.q_norm_w = e->q_ln + (size_t)l * hd;
             a.k_norm_w = e->k_ln + (size_t)l * hd;
             a.rope = e->d_rope;
-            a.xb = b->xb;
+            a.xb = sc.xb;
             a.att_global = S > att_lds_max ? b->att : nullptr;
-            a.st = b->st;
+            a.st = sc.st;
             a.pos_override = -1;
             a.n_heads = c.n_heads;
             a.n_kv_heads = c.n_kv_heads;
@@ -404,16 +436,17 @@ int batch_build_plan(q3_engine* e, int n, PlanKind kind, bool draw = false) {
             a.strict = strict;
             a.sb_q = ahd; a.sb_kraw = kvd; a.sb_kv = kv_stride; a.sb_xb = ahd;
             a.sb_att = (long long)c.n_heads * S;
-            a.col_slot = cols ? b->col_slot : nullptr;
+            a.col_slot = sc.col_slot;
             a.tch = att_tch < attn_tch(hd) ? att_tch : attn_tch(hd);
             const int kv_mul = c.n_heads / c.n_kv_heads;
             const bool gqa = kv_mul <= 7 && hd <= 256 && (hd & (hd - 1)) == 0 && hd >= 16 &&
                              attn_gqa_smem_bytes(hd, kv_mul, S) <= 150 * 1024 && dev_knob("Q3_BATCH_ATT_GQA", 1);
             // dense prefill, head_dim 128 with 2 or 4 query heads per kv head: k_attn_pf2 (Q3_PREFILL_ATT_PF=0: k_attn_gqa2)
-            const bool use_pf = dense && hd == kG2Hd && (kv_mul == 2 || kv_mul == 4) && b->att_pf != nullptr && dev_knob("Q3_PREFILL_ATT_PF", 1);
+            const bool use_pf = dense && hd == kG2Hd && (kv_mul == 2 || kv_mul == 4) && sc.att_pf != nullptr && dev_knob("Q3_PREFILL_ATT_PF", 1);
+            if (slotpf && !use_pf) return fail(Q3_ERR_UNSUPPORTED, "a dense block over the slots needs k_attn_pf2 (head_dim 128, 2 or 4 query heads per kv head)");
             if (block && !gqa && !use_pf) return fail(Q3_ERR_UNSUPPORTED, "batched prefill needs the per-kv-head attention kernel");
             if (block) {   // all key rows of the block enter the cache before any position attends
-                if (use_pf) a.q_out = b->qn;                        // the same launch normalises + rotates the block's query heads
+                if (use_pf) a.q_out = sc.qn;                        // the same launch normalises + rotates the block's query heads
                 // long blocks of head_dim-128 models: 64 vectors per workgroup, one chain per lane (k_knorm_rope_blk); Q3_KNORM_BLK=0: one wave per vector
                 if (n >= 64 && hd == kG2Hd && dev_knob("Q3_KNORM_BLK", 1)) {
                     const long nvec = (long)n * (c.n_kv_heads + (use_pf ? c.n_heads : 0));
@@ -427,11 +460,11 @@ int batch_build_plan(q3_engine* e, int n, PlanKind kind, bool draw = false) {
             }
             if (use_pf) {
                 // NP consecutive positions x the kv head's query heads per workgroup, one wave per (position, head pair)
-                a.att_global = b->att_pf;
-                a.att_stride = b->att_pf_stride;
+                a.att_global = sc.att_pf;
+                a.att_stride = sc.att_pf_stride;
                 a.n_pos = n;
-                a.pack_q = b->xq_p;
-                a.pack_s = b->xs_p;
+                a.pack_q = sc.xq_p;
+                a.pack_s = sc.xs_p;
                 a.group = G;
                 fused_xb_quant = true;
                 a.stamps = stamp_cells();
@@ -443,8 +476,8 @@ int batch_build_plan(q3_engine* e, int n, PlanKind kind, bool draw = false) {
                 // one workgroup per (stream, kv head): K/V staged once for the kv_mul query heads sharing it
                 a.att_global = nullptr;
                 if (hd % G == 0 && dev_knob("Q3_BATCH_FUSE_XB_QUANT", 1)) {   // Wo's activation prologue rides in the epilogue
-                    a.pack_q = b->xq_p;
-                    a.pack_s = b->xs_p;
+                    a.pack_q = sc.xq_p;
+                    a.pack_s = sc.xs_p;
                     a.group = G;
                     fused_xb_quant = true;
                 }
@@ -460,27 +493,27 @@ int batch_build_plan(q3_engine* e, int n, PlanKind kind, bool draw = false) {
             if (rc) return rc;
             b->plan.push_back(Ln);
         }
-        if (!fused_xb_quant && (rc = quant(F_WO, PRO_QUANT, b->xb, ahd, ahd, nullptr))) return rc;
+        if (!fused_xb_quant && (rc = quant(F_WO, PRO_QUANT, sc.xb, ahd, ahd, nullptr))) return rc;
         {
             BGemmArgs a{};
-            a.out0 = b->x; a.out0_stride = dim;
+            a.out0 = sc.x; a.out0_stride = dim;
             if ((rc = gemm(F_WO, EPI_RESID, b->m_wo[l], a))) return rc;
         }
-        if ((rc = quant(F_W13, PRO_NORM, b->x, dim, dim, e->rms_ffn + (size_t)l * dim))) return rc;
+        if ((rc = quant(F_W13, PRO_NORM, sc.x, dim, dim, e->rms_ffn + (size_t)l * dim))) return rc;
         {
             BGemmArgs a{};
-            a.out0 = b->hb; a.out0_stride = H;
+            a.out0 = sc.hb; a.out0_stride = H;
             if ((rc = gemm(F_W13, EPI_SWIGLU, b->m_w13[l], a))) return rc;
         }
-        if ((rc = quant(F_W2, PRO_QUANT, b->hb, H, H, nullptr))) return rc;
+        if ((rc = quant(F_W2, PRO_QUANT, sc.hb, H, H, nullptr))) return rc;
         {
             BGemmArgs a{};
-            a.out0 = b->x; a.out0_stride = dim;
+            a.out0 = sc.x; a.out0_stride = dim;
             if ((rc = gemm(F_W2, EPI_RESID, b->m_w2[l], a))) return rc;
         }
     }
     b->plan_head = b->plan.size();
-    if (prefill && !verify) return Q3_OK;          // the classifier runs once, on the last position, through the single-stream launch
+    if ((prefill && !verify) || slotpf) return Q3_OK;   // Prefill: the classifier runs once, on the last position, through the single-stream launch; SlotPrefill: cache rows only
     if ((rc = quant(F_LMHEAD, PRO_NORM, b->x, dim, dim, e->rms_final))) return rc;
     {
         BGemmArgs a{};

@@ -224,16 +224,199 @@ int cols_step(q3_engine* e, const int32_t* slots, const int32_t* tokens, const i
     return Q3_OK;
 }
 
+// What a call enqueues, in stream order: column passes from a pass table and dense blocks over the slots (q3_dense_host.inc) in
+// between.  The table is walked by the turn kernels on the device, one pass per step that is not wide; a wide step is the block
+// of n columns over runs [r0, r0 + nr) of the run table.
+struct ColsJobStep { bool wide; int n; size_t r0, nr; };
+struct ColsJob {
+    std::vector<ColEnt> table;          // [passes][kColsMax]
+    std::vector<ColAux> aux;            // under the sampler: next to the table
+    std::vector<int> ncols;             // live columns of every pass
+    std::vector<DenseRun> runs;
+    std::vector<ColsJobStep> steps;
+    size_t max_end = 0;                 // the largest position + 1 a wide block attends over
+    // a new pass of the table; returns its index
+    size_t add_pass(bool draw) {
+        ncols.push_back(0);
+        table.resize(table.size() + kColsMax);
+        if (draw) aux.resize(table.size());
+        steps.push_back(ColsJobStep{false, 0, 0, 0});
+        return ncols.size() - 1;
+    }
+};
+struct ColsJobSampler {                 // the sampler side of a job (draw)
+    SamplerState* slot_ss;              // per-slot states the passes draw from and commit to
+    const float *temperature, *topp;    // per request (loaded where ColAux::req >= 0), or nullptr
+    const uint64_t* seeds;
+    size_t n_requests;
+    bool skip_wide;                     // the wide blocks' runs advance slot_ss of their slots by their lengths (k_dense_rng_skip), ahead of the passes
+};
+
+// pads of every pass (they repeat the pass's last live column and emit nothing), then the whole job on the stream: the only
+// uploads of the call are the table, the run table, the prompts and the per-request sampler parameters; one synchronisation.
+int cols_job_run(q3_engine* e, ColsJob& job, bool draw, const ColsJobSampler& smp, const int32_t* prompts, size_t n_prompt, int32_t* out_tokens, size_t n_out) {
+    int rc;
+    BatchCtx* b = e->batch;
+    const size_t n_passes = job.ncols.size();
+    bool width_used[kColsNW] = {false};
+    for (size_t p = 0; p < n_passes; ++p) {
+        ColEnt pad = job.table[p * kColsMax + job.ncols[p] - 1];
+        pad.out = -1;
+        for (int j = job.ncols[p]; j < kColsMax; ++j) job.table[p * kColsMax + j] = pad;
+        if (draw)
+            for (int j = job.ncols[p]; j < kColsMax; ++j) job.aux[p * kColsMax + j] = ColAux{-1, job.aux[p * kColsMax + job.ncols[p] - 1].k, 0, 0};
+        width_used[cols_width_index(job.ncols[p])] = true;
+    }
+    // every plan and buffer the call needs exists before the first launch is enqueued
+    if (draw && n_passes && (rc = cols_draw_alloc(e))) return rc;
+    ColsPlan* plans[kColsNW] = {nullptr};
+    for (int w = 0; w < kColsNW; ++w)
+        if (width_used[w] && (rc = cols_plan_get(e, w, &plans[w], draw))) return rc;
+    std::vector<const std::vector<Launch>*> wide_plans(job.steps.size(), nullptr);
+    if (!job.runs.empty()) {
+        if ((rc = dense_scratch_get(e))) return rc;
+        if ((rc = dense_att_grow(e, job.max_end))) return rc;
+        for (size_t i = 0; i < job.steps.size(); ++i)
+            if (job.steps[i].wide && (rc = dense_plan_get(e, job.steps[i].n, &wide_plans[i]))) return rc;
+    }
+
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipStreamSynchronize(e->stream));              // nothing in flight reads the buffers that may be re-allocated
+    if ((rc = cols_grow(b->cols_table, b->cols_table_cap, n_passes * kColsMax))) return rc;
+    if ((rc = cols_grow(b->cols_ncols, b->cols_ncols_cap, n_passes))) return rc;
+    if ((rc = cols_grow(b->cols_prompts, b->cols_prompts_cap, n_prompt))) return rc;
+    if ((rc = cols_grow(b->cols_out, b->cols_out_cap, n_out))) return rc;
+    if ((rc = cols_grow(b->dense_runs, b->dense_runs_cap, job.runs.size()))) return rc;
+    if (n_passes) {
+        HIP_TRY(hipMemcpyAsync(b->cols_table, job.table.data(), sizeof(ColEnt) * n_passes * kColsMax, hipMemcpyHostToDevice, e->stream));
+        HIP_TRY(hipMemcpyAsync(b->cols_ncols, job.ncols.data(), 4 * n_passes, hipMemcpyHostToDevice, e->stream));
+    }
+    HIP_TRY(hipMemcpyAsync(b->cols_prompts, prompts, 4 * n_prompt, hipMemcpyHostToDevice, e->stream));
+    if (!job.runs.empty()) HIP_TRY(hipMemcpyAsync(b->dense_runs, job.runs.data(), sizeof(DenseRun) * job.runs.size(), hipMemcpyHostToDevice, e->stream));
+    if (draw && n_passes) {
+        if ((rc = cols_grow(b->cols_aux, b->cols_aux_cap, n_passes * kColsMax))) return rc;
+        HIP_TRY(hipMemcpyAsync(b->cols_aux, job.aux.data(), sizeof(ColAux) * n_passes * kColsMax, hipMemcpyHostToDevice, e->stream));
+        if (smp.temperature) {
+            if ((rc = cols_grow(b->cols_temp, b->cols_temp_cap, smp.n_requests))) return rc;
+            if ((rc = cols_grow(b->cols_topp, b->cols_topp_cap, smp.n_requests))) return rc;
+            if ((rc = cols_grow(b->cols_seeds, b->cols_seeds_cap, smp.n_requests))) return rc;
+            HIP_TRY(hipMemcpyAsync(b->cols_temp, smp.temperature, 4 * smp.n_requests, hipMemcpyHostToDevice, e->stream));
+            HIP_TRY(hipMemcpyAsync(b->cols_topp, smp.topp, 4 * smp.n_requests, hipMemcpyHostToDevice, e->stream));
+            HIP_TRY(hipMemcpyAsync(b->cols_seeds, smp.seeds, 8 * smp.n_requests, hipMemcpyHostToDevice, e->stream));
+        }
+        ColsDraw& dr = b->h_cols_draw->dr;
+        memset(&dr, 0, sizeof(ColsDraw));
+        dr.slot_ss = smp.slot_ss;
+        dr.aux = b->cols_aux;
+        dr.temperature = b->cols_temp;
+        dr.topp = b->cols_topp;
+        dr.seeds = b->cols_seeds;
+        HIP_TRY(hipMemcpyAsync(b->cols_draw, &dr, sizeof(ColsDraw), hipMemcpyHostToDevice, e->stream));
+    }
+    // the coins of the wide blocks first: a turn kernel reads a slot's rng when it sets a pass up, one pass ahead of the stream, so
+    // a skip enqueued next to its block would be overwritten by the commit of a pass of the same slot set up before it.  One
+    // launch per block: the pieces of a run that spans blocks are the same slot's
+    if (draw && smp.skip_wide)
+        for (const ColsJobStep& s : job.steps)
+            if (s.wide && (rc = launch_now(e->stream, k_dense_rng_skip, dim3(1), dim3(64), 0, smp.slot_ss, (const DenseRun*)(b->dense_runs + s.r0), (int)s.nr))) return rc;
+    if (n_passes) {
+        ColsHost* h = b->h_cols;
+        memset(&h->ctl, 0, sizeof(ColsCtl));
+        h->ctl.n_passes = (int)n_passes;
+        h->ctl.table = b->cols_table;
+        h->ctl.ncols = b->cols_ncols;
+        h->ctl.prompts = b->cols_prompts;
+        h->ctl.out_tokens = b->cols_out;
+        HIP_TRY(hipMemcpyAsync(b->cols_ctl, &h->ctl, sizeof(ColsCtl), hipMemcpyHostToDevice, e->stream));
+        // pass 0 is set up by a launch of its own (nothing to commit); every later pass by the k_cols_turn that ends the pass before it
+        if (draw) {
+            if ((rc = launch_now(e->stream, k_cols_turn_draw, dim3(1), dim3(kWG), 0, b->cols_ctl, b->cols_draw, b->spec_samp, b->st, b->col_slot))) return rc;
+        } else if ((rc = launch_now(e->stream, k_cols_turn, dim3(1), dim3(kWG), 0, b->cols_ctl, b->slots, b->nslots, 0, b->st, b->col_slot))) return rc;
+    }
+    size_t p = 0;
+    for (size_t i = 0; i < job.steps.size(); ++i) {
+        const ColsJobStep& s = job.steps[i];
+        if (!s.wide) {
+            if ((rc = cols_enqueue(e, *plans[cols_width_index(job.ncols[p++])]))) return rc;
+            continue;
+        }
+        if ((rc = dense_enqueue_block(e, *wide_plans[i], b->dense_runs + s.r0, (int)s.nr, s.n, b->cols_prompts))) return rc;
+    }
+    HIP_TRY(hipGetLastError());
+    if (n_out) HIP_TRY(hipMemcpyAsync(out_tokens, b->cols_out, 4 * n_out, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return Q3_OK;
+}
+
+// One set of runs that enter their slots together, packed into blocks by dense_pack_run and added to the job: a block of more
+// than 32 columns is a wide step; a narrower one (and every block of a shape the dense kernels refuse: its cap is 32) is a
+// column pass of its live columns, which emit nothing and under the sampler consume their coins (keep = 0).
+// runs: slot, first position, prompt offset and length of every run.  first_req (sampled loop only, else nullptr): run i belongs
+// to request first_req[i]; loaded / wide_coins are the loop's per-request records of whether a pass has loaded the request's
+// sampler into its slot and how many coins its wide pieces stand for.
+struct DenseIn { int slot, pos0, src0; size_t len; };
+void dense_job_add(q3_engine* e, ColsJob& job, const std::vector<DenseIn>& in, bool draw, const size_t* first_req, std::vector<char>* loaded,
+                   std::vector<size_t>* wide_coins, q3_dense_stats& total) {
+    std::vector<size_t> lens(in.size());
+    for (size_t i = 0; i < in.size(); ++i) lens[i] = in[i].len;
+    struct Piece { uint64_t block; int col0; size_t run, off; int len; };
+    std::vector<Piece> pieces;
+    q3_dense_stats st;
+    dense_pack_run(lens.data(), lens.size(), dense_block_cap(e), [&](uint64_t block, int col0, size_t run, size_t off, int len) {
+        pieces.push_back(Piece{block, col0, run, off, len});
+    }, st);
+    total.blocks += st.blocks;
+    total.live_columns += st.live_columns;
+    total.pad_columns += st.pad_columns;
+    for (size_t i0 = 0; i0 < pieces.size();) {
+        size_t i1 = i0;
+        while (i1 < pieces.size() && pieces[i1].block == pieces[i0].block) ++i1;
+        const int n = (pieces[i1 - 1].col0 + pieces[i1 - 1].len + 7) & ~7;
+        if (n > kColsMax) {
+            job.steps.push_back(ColsJobStep{true, n, job.runs.size(), i1 - i0});
+            for (size_t i = i0; i < i1; ++i) {
+                const Piece& pc = pieces[i];
+                const DenseIn& r = in[pc.run];
+                job.runs.push_back(DenseRun{pc.col0, r.slot, r.pos0 + (int)pc.off, r.src0 + (int)pc.off, pc.len});
+                job.max_end = std::max(job.max_end, (size_t)r.pos0 + pc.off + (size_t)pc.len);
+                if (wide_coins) (*wide_coins)[first_req[pc.run]] += (size_t)pc.len;
+            }
+        } else {
+            const size_t p = job.add_pass(draw);
+            for (size_t i = i0; i < i1; ++i) {
+                const Piece& pc = pieces[i];
+                const DenseIn& r = in[pc.run];
+                for (int k = 0; k < pc.len; ++k) {
+                    const size_t at = p * kColsMax + job.ncols[p]++;
+                    job.table[at] = ColEnt{r.slot, r.pos0 + (int)pc.off + k, r.src0 + (int)pc.off + k, -1};
+                    if (!draw) continue;
+                    int req = -1;
+                    if (loaded && k == 0 && !(*loaded)[first_req[pc.run]]) {
+                        req = (int)first_req[pc.run];
+                        (*loaded)[first_req[pc.run]] = 1;
+                    }
+                    job.aux[at] = ColAux{req, k, 0, k == pc.len - 1 ? 1 : 0};
+                }
+            }
+        }
+        i0 = i1;
+    }
+}
+
 // The device-resident loop of q3_generate_many_greedy (temperature == nullptr) and q3_generate_many_sampled: the same schedule and
 // table; under the sampler a parallel table of ColAux, the per-request sampler parameters and the sampled plans.
+// dense_min > 0 (q3_generate_many_dense): a request with prompt_len - 1 >= dense_min enters the schedule with a prompt of one
+// column, its last prompt token; the tokens in front of it go through dense blocks enqueued in front of the pass that holds it.
 int cols_generate(q3_engine* e, const int32_t* prompts, const size_t* prompt_len, const size_t* n_new, size_t n_requests, const float* temperature,
-                  const float* topp, const uint64_t* seeds, int32_t* out_tokens, q3_cols_stats* stats) {
+                  const float* topp, const uint64_t* seeds, int32_t* out_tokens, q3_cols_stats* stats, size_t dense_min = 0,
+                  q3_dense_stats* dstats = nullptr) {
     int rc;
     const bool draw = temperature != nullptr;
     BatchCtx* b = e->batch;
     if (!prompts || !out_tokens) return fail(Q3_ERR_ARG, "null argument");
     if ((rc = cols_schedule_check(prompt_len, n_new, n_requests, b->max_streams))) return rc;
-    std::vector<size_t> p_off(n_requests), o_off(n_requests);
+    std::vector<size_t> p_off(n_requests), o_off(n_requests), eff_len(n_requests);
+    std::vector<char> dense(n_requests, 0);
     size_t n_prompt = 0, n_out = 0;
     for (size_t r = 0; r < n_requests; ++r) {
         if (prompt_len[r] + n_new[r] - 1 > (size_t)b->ctx)
@@ -242,97 +425,67 @@ int cols_generate(q3_engine* e, const int32_t* prompts, const size_t* prompt_len
         o_off[r] = n_out;
         n_prompt += prompt_len[r];
         n_out += n_new[r];
+        dense[r] = dense_min > 0 && prompt_len[r] - 1 >= dense_min;
+        eff_len[r] = dense[r] ? 1 : prompt_len[r];
     }
     for (size_t i = 0; i < n_prompt; ++i)
         if (prompts[i] < 0 || prompts[i] >= e->cfg.vocab_size)
             return fail(Q3_ERR_ARG, "index out of range: token %d (vocab_size %d)", prompts[i], e->cfg.vocab_size);
     if (n_prompt > (size_t)INT32_MAX || n_out > (size_t)INT32_MAX) return fail(Q3_ERR_ARG, "more than 2^31 tokens in one call");
 
-    // the pass table: kColsMax entries per pass, pads repeat the pass's last live column and emit nothing
-    std::vector<ColEnt> table;
-    std::vector<ColAux> aux;
-    std::vector<int> ncols;
+    // the schedule's columns, pass by pass (positions in the schedule's terms: a dense request's prompt is one column)
+    struct Col { uint64_t pass; int slot; size_t pos, req; };
+    std::vector<Col> sched;
     q3_cols_stats st;
-    cols_schedule_run(prompt_len, n_new, n_requests, b->max_streams, [&](uint64_t pass, int slot, size_t pos, size_t req) {
-        if (pass == ncols.size()) {
-            ncols.push_back(0);
-            table.resize(table.size() + kColsMax);
-            if (draw) aux.resize(table.size());
-        }
-        ColEnt c;
-        c.slot = slot;
-        c.pos = (int)pos;
-        c.src = pos < prompt_len[req] ? (int)(p_off[req] + pos) : -1;
-        c.out = pos + 1 >= prompt_len[req] ? (int)(o_off[req] + (pos + 1 - prompt_len[req])) : -1;
-        const size_t at = (size_t)pass * kColsMax + ncols[pass]++;
-        table[at] = c;
-        if (draw) {          // a request enters at position 0; the run's earlier column is the entry in front (one run per slot)
-            const bool in_run = ncols[pass] > 1 && table[at - 1].slot == slot;
-            aux[at] = ColAux{pos == 0 ? (int)req : -1, in_run ? aux[at - 1].k + 1 : 0, c.out >= 0 ? 1 : 0, 1};
-            if (in_run) aux[at - 1].last = 0;
-        }
+    cols_schedule_run(eff_len.data(), n_new, n_requests, b->max_streams, [&](uint64_t pass, int slot, size_t pos, size_t req) {
+        sched.push_back(Col{pass, slot, pos, req});
     }, st);
-    const size_t n_passes = ncols.size();
-    bool width_used[kColsNW] = {false};
-    for (size_t p = 0; p < n_passes; ++p) {
-        ColEnt pad = table[p * kColsMax + ncols[p] - 1];
-        pad.out = -1;
-        for (int j = ncols[p]; j < kColsMax; ++j) table[p * kColsMax + j] = pad;
-        if (draw)
-            for (int j = ncols[p]; j < kColsMax; ++j) aux[p * kColsMax + j] = ColAux{-1, aux[p * kColsMax + ncols[p] - 1].k, 0, 0};
-        width_used[cols_width_index(ncols[p])] = true;
+    // the pass table: kColsMax entries per pass.  In front of a pass, the blocks of the dense requests whose column it holds
+    ColsJob job;
+    q3_dense_stats dst{0, 0, 0};
+    std::vector<char> loaded(n_requests, 0);
+    std::vector<size_t> wide_coins(n_requests, 0);
+    for (size_t i0 = 0; i0 < sched.size();) {
+        size_t i1 = i0;
+        while (i1 < sched.size() && sched[i1].pass == sched[i0].pass) ++i1;
+        std::vector<DenseIn> in;
+        std::vector<size_t> in_req;
+        for (size_t i = i0; i < i1; ++i)
+            if (dense[sched[i].req] && sched[i].pos == 0) in_req.push_back(sched[i].req);
+        std::sort(in_req.begin(), in_req.end());             // admission order
+        for (size_t r : in_req) {
+            int slot = -1;
+            for (size_t i = i0; i < i1; ++i)
+                if (sched[i].req == r && sched[i].pos == 0) slot = sched[i].slot;
+            in.push_back(DenseIn{slot, 0, (int)p_off[r], prompt_len[r] - 1});
+        }
+        if (!in.empty()) dense_job_add(e, job, in, draw, in_req.data(), draw ? &loaded : nullptr, draw ? &wide_coins : nullptr, dst);
+        const size_t p = job.add_pass(draw);
+        for (size_t i = i0; i < i1; ++i) {
+            const Col& s = sched[i];
+            const size_t shift = dense[s.req] ? prompt_len[s.req] - 1 : 0, el = eff_len[s.req];
+            ColEnt c;
+            c.slot = s.slot;
+            c.pos = (int)(s.pos + shift);
+            c.src = s.pos < el ? (int)(p_off[s.req] + s.pos + shift) : -1;
+            c.out = s.pos + 1 >= el ? (int)(o_off[s.req] + (s.pos + 1 - el)) : -1;
+            const size_t at = p * kColsMax + job.ncols[p]++;
+            job.table[at] = c;
+            if (draw) {          // a request enters at position 0; the run's earlier column is the entry in front (one run per slot)
+                const bool in_run = job.ncols[p] > 1 && job.table[at - 1].slot == s.slot;
+                // a dense request's column stands wide_coins coins into its rng: the discarded samples of the positions its blocks took
+                const int k = in_run ? job.aux[at - 1].k + 1 : (int)(dense[s.req] && s.pos == 0 ? wide_coins[s.req] : 0);
+                job.aux[at] = ColAux{s.pos == 0 && !loaded[s.req] ? (int)s.req : -1, k, c.out >= 0 ? 1 : 0, 1};
+                if (in_run) job.aux[at - 1].last = 0;
+            }
+        }
+        i0 = i1;
     }
-    // every plan the call needs exists before the first pass is enqueued
-    if (draw && (rc = cols_draw_alloc(e))) return rc;
-    ColsPlan* plans[kColsNW] = {nullptr};
-    for (int w = 0; w < kColsNW; ++w)
-        if (width_used[w] && (rc = cols_plan_get(e, w, &plans[w], draw))) return rc;
-
-    HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(hipStreamSynchronize(e->stream));              // nothing in flight reads the buffers that may be re-allocated
-    if ((rc = cols_grow(b->cols_table, b->cols_table_cap, n_passes * kColsMax))) return rc;
-    if ((rc = cols_grow(b->cols_ncols, b->cols_ncols_cap, n_passes))) return rc;
-    if ((rc = cols_grow(b->cols_prompts, b->cols_prompts_cap, n_prompt))) return rc;
-    if ((rc = cols_grow(b->cols_out, b->cols_out_cap, n_out))) return rc;
-    // the only uploads of the call
-    HIP_TRY(hipMemcpyAsync(b->cols_table, table.data(), sizeof(ColEnt) * n_passes * kColsMax, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipMemcpyAsync(b->cols_ncols, ncols.data(), 4 * n_passes, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipMemcpyAsync(b->cols_prompts, prompts, 4 * n_prompt, hipMemcpyHostToDevice, e->stream));
-    if (draw) {
-        if ((rc = cols_grow(b->cols_aux, b->cols_aux_cap, n_passes * kColsMax))) return rc;
-        if ((rc = cols_grow(b->cols_temp, b->cols_temp_cap, n_requests))) return rc;
-        if ((rc = cols_grow(b->cols_topp, b->cols_topp_cap, n_requests))) return rc;
-        if ((rc = cols_grow(b->cols_seeds, b->cols_seeds_cap, n_requests))) return rc;
-        HIP_TRY(hipMemcpyAsync(b->cols_aux, aux.data(), sizeof(ColAux) * n_passes * kColsMax, hipMemcpyHostToDevice, e->stream));
-        HIP_TRY(hipMemcpyAsync(b->cols_temp, temperature, 4 * n_requests, hipMemcpyHostToDevice, e->stream));
-        HIP_TRY(hipMemcpyAsync(b->cols_topp, topp, 4 * n_requests, hipMemcpyHostToDevice, e->stream));
-        HIP_TRY(hipMemcpyAsync(b->cols_seeds, seeds, 8 * n_requests, hipMemcpyHostToDevice, e->stream));
-        ColsDraw& dr = b->h_cols_draw->dr;
-        memset(&dr, 0, sizeof(ColsDraw));
-        dr.slot_ss = b->cols_slot_samp;
-        dr.aux = b->cols_aux;
-        dr.temperature = b->cols_temp;
-        dr.topp = b->cols_topp;
-        dr.seeds = b->cols_seeds;
-        HIP_TRY(hipMemcpyAsync(b->cols_draw, &dr, sizeof(ColsDraw), hipMemcpyHostToDevice, e->stream));
-    }
-    ColsHost* h = b->h_cols;
-    memset(&h->ctl, 0, sizeof(ColsCtl));
-    h->ctl.n_passes = (int)n_passes;
-    h->ctl.table = b->cols_table;
-    h->ctl.ncols = b->cols_ncols;
-    h->ctl.prompts = b->cols_prompts;
-    h->ctl.out_tokens = b->cols_out;
-    HIP_TRY(hipMemcpyAsync(b->cols_ctl, &h->ctl, sizeof(ColsCtl), hipMemcpyHostToDevice, e->stream));
-    // pass 0 is set up by a launch of its own (nothing to commit); every later pass by the k_cols_turn that ends the pass before it
-    if (draw) {
-        if ((rc = launch_now(e->stream, k_cols_turn_draw, dim3(1), dim3(kWG), 0, b->cols_ctl, b->cols_draw, b->spec_samp, b->st, b->col_slot))) return rc;
-    } else if ((rc = launch_now(e->stream, k_cols_turn, dim3(1), dim3(kWG), 0, b->cols_ctl, b->slots, b->nslots, 0, b->st, b->col_slot))) return rc;
-    for (size_t p = 0; p < n_passes; ++p)
-        if ((rc = cols_enqueue(e, *plans[cols_width_index(ncols[p])]))) return rc;
-    HIP_TRY(hipMemcpyAsync(out_tokens, b->cols_out, 4 * n_out, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
+    if (draw && (rc = cols_draw_alloc(e))) return rc;        // the loop's per-slot sampler states are allocated there
+    const ColsJobSampler smp{b->cols_slot_samp, temperature, topp, seeds, n_requests, false};
+    if ((rc = cols_job_run(e, job, draw, smp, prompts, n_prompt, out_tokens, n_out))) return rc;
     if (stats) *stats = st;
+    if (dstats) *dstats = dst;
     return Q3_OK;
 }
 
@@ -400,6 +553,64 @@ int q3_generate_many_sampled(q3_engine* e, const int32_t* prompts, const size_t*
         if (!(topp[r] >= 0.0f && topp[r] <= 1.0f)) return fail(Q3_ERR_ARG, "request %zu: Top-p must be between 0.0 and 1.0", r);
     }
     return cols_generate(e, prompts, prompt_len, n_new, n_requests, temperature, topp, seeds, out_tokens, stats);
+}
+
+/* ---- section 2g: dense blocks over the slots ---- */
+
+int q3_batch_prefill_slots(q3_engine* e, const int32_t* slots, const int32_t* tokens, const size_t* run_len, const int32_t* first_pos, size_t n_runs,
+                           q3_dense_stats* stats) {
+    g_err[0] = 0;
+    if (stats) *stats = q3_dense_stats{0, 0, 0};
+    int rc;
+    if ((rc = cols_prepare(e, "q3_batch_prefill_slots", true))) return rc;
+    BatchCtx* b = e->batch;
+    if (!slots || !tokens || !run_len || !first_pos || n_runs == 0) return fail(Q3_ERR_ARG, "null or empty run list");
+    bool seen[kMaxStreams] = {false};
+    std::vector<DenseIn> in;
+    size_t n_tok = 0;
+    for (size_t r = 0; r < n_runs; ++r) {
+        if (slots[r] < 0 || slots[r] >= b->max_streams) return fail(Q3_ERR_ARG, "run %zu: slot %d out of range (0..%d)", r, slots[r], b->max_streams - 1);
+        if (seen[slots[r]]) return fail(Q3_ERR_ARG, "run %zu: slot %d is named twice", r, slots[r]);
+        seen[slots[r]] = true;
+        if (run_len[r] == 0) return fail(Q3_ERR_ARG, "run %zu is empty", r);
+        if (first_pos[r] < 0 || run_len[r] > (size_t)b->ctx || (size_t)first_pos[r] + run_len[r] > (size_t)b->ctx)
+            return fail(Q3_ERR_ARG, "run %zu: first_pos %d + %zu tokens exceeds seq_len %d", r, first_pos[r], run_len[r], b->ctx);
+        in.push_back(DenseIn{slots[r], first_pos[r], (int)n_tok, run_len[r]});
+        n_tok += run_len[r];
+    }
+    for (size_t i = 0; i < n_tok; ++i)
+        if (tokens[i] < 0 || tokens[i] >= e->cfg.vocab_size)
+            return fail(Q3_ERR_ARG, "index out of range: token %d (vocab_size %d)", tokens[i], e->cfg.vocab_size);
+    const bool draw = b->sampling;                  // temperature 0, or no batch sampler: no rng is touched
+    ColsJob job;
+    q3_dense_stats dst{0, 0, 0};
+    dense_job_add(e, job, in, draw, nullptr, nullptr, nullptr, dst);
+    const ColsJobSampler smp{b->d_sampler, nullptr, nullptr, nullptr, 0, true};
+    if ((rc = cols_job_run(e, job, draw, smp, tokens, n_tok, nullptr, 0))) return rc;
+    if (stats) *stats = dst;
+    return Q3_OK;
+}
+
+int q3_generate_many_dense(q3_engine* e, const int32_t* prompts, const size_t* prompt_len, const size_t* n_new, size_t n_requests,
+                           const float* temperature, const float* topp, const uint64_t* seeds, size_t dense_min, int32_t* out_tokens,
+                           q3_cols_stats* stats, q3_dense_stats* dstats) {
+    g_err[0] = 0;
+    if (stats) *stats = q3_cols_stats{0, 0, 0, 0};
+    if (dstats) *dstats = q3_dense_stats{0, 0, 0};
+    if (!temperature && !topp && !seeds) {
+        int rc;
+        if ((rc = cols_prepare(e, "q3_generate_many_dense"))) return rc;
+        return cols_generate(e, prompts, prompt_len, n_new, n_requests, nullptr, nullptr, nullptr, out_tokens, stats, dense_min, dstats);
+    }
+    int rc;
+    if ((rc = cols_prepare(e, "q3_generate_many_dense", true))) return rc;
+    if (!temperature || !topp || !seeds) return fail(Q3_ERR_ARG, "null argument");
+    if (!prompt_len || !n_new || n_requests == 0) return fail(Q3_ERR_ARG, "null or empty request list");
+    for (size_t r = 0; r < n_requests; ++r) {
+        if (!(temperature[r] >= 0.0f)) return fail(Q3_ERR_ARG, "request %zu: Temperature must be non-negative", r);
+        if (!(topp[r] >= 0.0f && topp[r] <= 1.0f)) return fail(Q3_ERR_ARG, "request %zu: Top-p must be between 0.0 and 1.0", r);
+    }
+    return cols_generate(e, prompts, prompt_len, n_new, n_requests, temperature, topp, seeds, out_tokens, stats, dense_min, dstats);
 }
 
 }  // extern "C"

@@ -25,6 +25,7 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <map>
 #include <new>
 #include <string>
 #include <tuple>
@@ -1876,4 +1877,5 @@ int q3_op_argmax(const float* logits, size_t n, int32_t* index, int device) {
 }  // extern "C"
 
 #include "q3_batch_host.inc"
+#include "q3_dense_host.inc"
 #include "q3_cols_host.inc"

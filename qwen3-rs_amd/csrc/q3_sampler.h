@@ -700,6 +700,20 @@ __global__ void k_rng_skip(SamplerState* ss, int count) {
     ss->rng = rs;
 }
 
+// k_rng_skip over a run table (q3_batch_prefill_slots under the batch sampler): a thread per run, the rng of the run's slot moves
+// on by the run's length -- the rule of the column passes (one discarded sample per prompt position), no column drawn
+__global__ void k_dense_rng_skip(SamplerState* ss, const DenseRun* __restrict__ runs, int n_runs) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n_runs) return;
+    unsigned long long rs = ss[runs[r].slot].rng;
+    for (int i = 0; i < runs[r].len; ++i) {
+        rs ^= rs >> 12;
+        rs ^= rs << 25;
+        rs ^= rs >> 27;
+    }
+    ss[runs[r].slot].rng = rs;
+}
+
 // ---- draft verification under the sampler (q3_verify_draw / q3_generate_lookup_draw, q3_batch.h): column i of a verify block is
 // drawn by the per-stream k_sample_exp / k_sample of the batched decode with a sampler state of its own.
 // Behind k_spec_snapshot, one workgroup: column i gets the engine's temperature / top-p as they are NOW (a later q3_sampler_set

@@ -28,6 +28,7 @@ EXPORTED_SYMBOLS = [
     "q3_verify_draw", "q3_generate_lookup_draw",
     "q3_batch_step_cols", "q3_cols_schedule", "q3_generate_many_greedy",
     "q3_batch_step_cols_draw", "q3_generate_many_sampled",
+    "q3_dense_pack", "q3_batch_prefill_slots", "q3_generate_many_dense",
 ]
 VERIFY_MAX = 32          # Q3_VERIFY_MAX
 COLS_MAX = 32            # Q3_COLS_MAX
@@ -70,6 +71,18 @@ class ColsStats:
     live_columns: int
     prompt_columns: int
     decode_columns: int
+
+
+class _DenseStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("blocks", "live_columns", "pad_columns")]
+
+
+@dataclasses.dataclass(frozen=True)
+class DenseStats:
+    """q3_dense_stats: the dense blocks of a call, their live columns and their pads"""
+    blocks: int
+    live_columns: int
+    pad_columns: int
 
 
 @dataclasses.dataclass(frozen=True)
@@ -201,6 +214,10 @@ def _bind(path: str) -> C.CDLL:
     L.q3_generate_many_greedy.argtypes = [C.c_void_p, i32p, szp, szp, sz, i32p, C.POINTER(_ColsStats)]
     L.q3_batch_step_cols_draw.argtypes = [C.c_void_p, i32p, i32p, i32p, C.c_int, u8p, fp, i32p]
     L.q3_generate_many_sampled.argtypes = [C.c_void_p, i32p, szp, szp, sz, fp, fp, C.POINTER(C.c_uint64), i32p, C.POINTER(_ColsStats)]
+    L.q3_dense_pack.argtypes = [szp, sz, C.c_int, i32p, sz, szp, C.POINTER(_DenseStats)]
+    L.q3_batch_prefill_slots.argtypes = [C.c_void_p, i32p, i32p, szp, i32p, sz, C.POINTER(_DenseStats)]
+    L.q3_generate_many_dense.argtypes = [C.c_void_p, i32p, szp, szp, sz, fp, fp, C.POINTER(C.c_uint64), sz, i32p, C.POINTER(_ColsStats),
+                                         C.POINTER(_DenseStats)]
     L.q3_profile.argtypes = [C.c_void_p, sz, sz, C.c_int, fp, C.POINTER(C.c_int32), C.c_int]
     L.q3_profile_name.argtypes = [C.c_int]
     L.q3_profile_name.restype = C.c_char_p
@@ -262,6 +279,18 @@ def cols_schedule(prompt_len, n_new, max_streams: int):
     _check(L.q3_cols_schedule(pl, nn, len(prompt_len), max_streams, table, n.value, C.byref(n), C.byref(st)))
     rows = [tuple(int(table[4 * i + k]) for k in range(4)) for i in range(n.value)]
     return rows, ColsStats(st.passes, st.live_columns, st.prompt_columns, st.decode_columns)
+
+
+def dense_pack(run_len, block_cap: int):
+    """How runs of run_len[r] columns are packed into dense blocks of up to block_cap columns (q3_dense_pack, host only):
+    ([(block, first column, run, offset in the run), ...] in order, DenseStats)."""
+    L = load_library()
+    rl, n, st = _size_array(run_len), C.c_size_t(0), _DenseStats()
+    _check(L.q3_dense_pack(rl, len(run_len), block_cap, None, 0, C.byref(n), C.byref(st)))
+    table = (C.c_int32 * max(1, 4 * n.value))()
+    _check(L.q3_dense_pack(rl, len(run_len), block_cap, table, n.value, C.byref(n), C.byref(st)))
+    rows = [tuple(int(table[4 * i + k]) for k in range(4)) for i in range(n.value)]
+    return rows, DenseStats(st.blocks, st.live_columns, st.pad_columns)
 
 
 def parse_header(data: bytes) -> ModelConfig:
@@ -546,6 +575,53 @@ class Transformer:
             rows.append([int(out[at + i]) for i in range(int(k))])
             at += int(k)
         return rows, ColsStats(st.passes, st.live_columns, st.prompt_columns, st.decode_columns)
+
+    # ---- dense blocks over the slots (include/qwen3_hip.h section 2g)
+    dense_pack = staticmethod(dense_pack)
+
+    def batch_prefill_slots(self, slots, prompts, first_pos):
+        """Cache rows of many slots in dense blocks (q3_batch_prefill_slots): prompts[r] enters slot slots[r] at positions
+        first_pos[r] ..; several runs share one pass over the weights.  No logits and no token: the prompt's last token goes
+        through batch_step_cols.  Under a sampling batch the slot's rng moves on by the run's length.  Returns DenseStats."""
+        n = len(slots)
+        if not (len(prompts) == n and len(first_pos) == n):
+            raise ValueError("one prompt and one first position per slot")
+        flat = [int(t) for p in prompts for t in p]
+        st = _DenseStats()
+        self._batch_rc(self._lib.q3_batch_prefill_slots(self._h, _i32_array(slots), _i32_array(flat), _size_array([len(p) for p in prompts]),
+                                                        _i32_array(first_pos), n, C.byref(st)))
+        return DenseStats(st.blocks, st.live_columns, st.pad_columns)
+
+    def generate_many_dense(self, prompts, n_new, sampler=None, dense_min: int = 64):
+        """generate_many_greedy (sampler None) or generate_many_sampled (sampler = (temperature, topp, seeds), one value per
+        request or a scalar) with every prompt of more than dense_min tokens entered through dense blocks
+        (q3_generate_many_dense): the same rows for any dense_min; 0 runs the column loops unchanged.
+        Returns (rows, ColsStats, DenseStats)."""
+        n = len(prompts)
+        if len(n_new) != n:
+            raise ValueError("one n_new per prompt")
+        tv = pv = sv = None
+        if sampler is not None:
+            def per_request(v, what):
+                vals = [v] * n if np.isscalar(v) else list(v)
+                if len(vals) != n:
+                    raise ValueError(f"one {what} per request, or a scalar")
+                return vals
+            temperature, topp, seeds = sampler
+            tv = (C.c_float * max(1, n))(*[float(v) for v in per_request(temperature, "temperature")])
+            pv = (C.c_float * max(1, n))(*[float(v) for v in per_request(topp, "topp")])
+            sv = (C.c_uint64 * max(1, n))(*[int(v) & 0xFFFFFFFFFFFFFFFF for v in per_request(seeds, "seed")])
+        flat = [int(t) for p in prompts for t in p]
+        total = sum(int(k) for k in n_new)
+        out = (C.c_int32 * max(1, total))()
+        st, ds = _ColsStats(), _DenseStats()
+        self._batch_rc(self._lib.q3_generate_many_dense(self._h, _i32_array(flat), _size_array([len(p) for p in prompts]), _size_array(n_new),
+                                                        n, tv, pv, sv, int(dense_min), out, C.byref(st), C.byref(ds)))
+        rows, at = [], 0
+        for k in n_new:
+            rows.append([int(out[at + i]) for i in range(int(k))])
+            at += int(k)
+        return rows, ColsStats(st.passes, st.live_columns, st.prompt_columns, st.decode_columns), DenseStats(ds.blocks, ds.live_columns, ds.pad_columns)
 
     def set_batch_sampler(self, temperature: float, topp: float, rng_seeds):
         """one Sampler per stream (sampler.rs:29-42), stream i seeded with rng_seeds[i]; temperature 0 = greedy"""

@@ -139,7 +139,8 @@ def generate(transformer, prompt_tokens: Sequence[int], max_new_tokens: Optional
     return out, metrics
 
 
-def generate_many(transformer, prompts: Sequence[Sequence[int]], max_new_tokens: int, stop_tokens: Iterable[int] = (), sampler=None):
+def generate_many(transformer, prompts: Sequence[Sequence[int]], max_new_tokens: int, stop_tokens: Iterable[int] = (), sampler=None,
+                  dense_min: int = 0):
     """Many greedy generations served through the slots of Transformer.batch_init in ragged column passes
     (Transformer.generate_many_greedy).  Row r holds what Transformer.prefill(prompts[r], 0) followed by generate_greedy returns on
     an engine of its own: every prompt token goes through the model (chat's prompt loop, generation.rs:116-123), then up to
@@ -147,6 +148,8 @@ def generate_many(transformer, prompts: Sequence[Sequence[int]], max_new_tokens:
     row is cut behind its first stop token afterwards, the way generate ends at BOS / EOS (generation.rs:35).
     sampler=(temperature, topp, seeds), each one value per prompt or a scalar for all: the same through
     Transformer.generate_many_sampled -- row r is what an engine of its own draws after set_sampler(temperature, topp, seed of r).
+    dense_min > 0: prompts of more than dense_min tokens enter their slots through dense blocks, many prompts per weight pass
+    (Transformer.generate_many_dense); the rows are the same for any value, 0 keeps the column loops.
     Returns (rows, ColsStats)."""
     if any(len(p) == 0 for p in prompts):
         raise ValueError("Please provide a prompt")
@@ -157,10 +160,14 @@ def generate_many(transformer, prompts: Sequence[Sequence[int]], max_new_tokens:
     rows: List[List[int]] = [[] for _ in prompts]
     stats = None
     if live:
-        if sampler is None:
+        if sampler is not None:
+            temperature, topp, seeds = ([v] * len(prompts) if np.isscalar(v) else list(v) for v in sampler)
+        if dense_min > 0:
+            per_live = None if sampler is None else tuple([v[r] for r in live] for v in (temperature, topp, seeds))
+            got, stats, _ = transformer.generate_many_dense([prompts[r] for r in live], [n_new[r] for r in live], per_live, dense_min)
+        elif sampler is None:
             got, stats = transformer.generate_many_greedy([prompts[r] for r in live], [n_new[r] for r in live])
         else:
-            temperature, topp, seeds = ([v] * len(prompts) if np.isscalar(v) else list(v) for v in sampler)
             got, stats = transformer.generate_many_sampled([prompts[r] for r in live], [n_new[r] for r in live], [temperature[r] for r in live],
                                                            [topp[r] for r in live], [seeds[r] for r in live])
         for r, toks in zip(live, got):

@@ -19,6 +19,14 @@ single-position columns with one column and with all columns drawing, against th
 width (temperature 0 set on the same engine); (d) the two request workloads through q3_generate_many_sampled against
 q3_generate_many_greedy.  Appends a section to <out>/serve_cols.md (an earlier section of the same name is replaced, the rest of
 the file is kept) and writes <out>/serve_cols_sampled.json.
+
+    python tools/bench_serve.py --dense-min 64 [--models qwen3-0.6b,qwen3-8b]
+
+Long prompts through dense blocks (section 2g).  Per model, context 2,304 per slot: (e) 8 requests of 256 + 64 tokens on 8 slots
+and 32 requests of 2,048 + 64 on 32 slots through q3_generate_many_dense with that dense_min against q3_generate_many_greedy on the
+same engine (best of 2 calls each, the rows must be equal); prompt tok/s is measured by the same mixes with one new token per
+request; (f) one block: q3_batch_prefill_slots of 8 runs of 256 tokens against q3_prefill_batched of one 2,048-token prompt.
+Appends a section to <out>/serve_cols.md and writes <out>/serve_cols_dense.json.
 """
 import argparse
 import json
@@ -31,6 +39,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "qwen3-rs_amd"))
 
 AB_MARK = "## Batch-32 decode A/B"
+DENSE_MARK = "## Dense blocks over the slots"
 SAMPLED_MARK = "## Under the sampler"
 
 
@@ -183,6 +192,89 @@ def worker_sampled(name, ctx, ckpt_dir, seed, temperature, topp):
     print("RESULT " + json.dumps(res))
 
 
+def worker_dense(name, ctx, ckpt_dir, seed, dense_min):
+    import qwen3_rs_amd as q3
+    ck = q3.checkpoint
+    shape = ck.SHAPES[name]
+    path = os.path.join(ckpt_dir, f"{name}-seed{seed}.q3bin")
+    ck.ensure_synthetic_checkpoint(path, shape, seed=seed)
+    res = {"model": name, "ctx": ctx, "dense_min": dense_min, "requests": {}}
+
+    def best(call, n=2):
+        call()                                                         # plans, scratch
+        dts = []
+        for _ in range(n):
+            t0 = time.perf_counter()
+            out = call()
+            dts.append(time.perf_counter() - t0)
+        return min(dts), out
+    with q3.TransformerBuilder(path).with_ctx_length(ctx).build() as t:
+        for label, n_req, plen, nnew in (("8x(256+64), 8 slots", 8, 256, 64), ("32x(2048+64), 32 slots", 32, 2048, 64)):
+            prompts = [ck.iter_prompt_tokens(shape, seed + 50 + r, plen) for r in range(n_req)]
+            t.batch_init(n_req, ctx)
+            out = {}
+            for k, call in (("columns", lambda nn: t.generate_many_greedy(prompts, nn)),
+                            ("dense", lambda nn: t.generate_many_dense(prompts, nn, None, dense_min))):
+                dt, got = best(lambda: call([nnew] * n_req))
+                dt1, _ = best(lambda: call([1] * n_req))                # the prompts alone: one token behind each
+                out[k] = {"passes": got[1].passes, "seconds": dt, "req_s": n_req / dt, "tok_s": n_req * (plen + nnew - 1) / dt,
+                          "prompt_seconds": dt1, "prompt_tok_s": n_req * plen / dt1, "rows": got[0]}
+                if k == "dense":
+                    out[k]["blocks"] = got[2].blocks
+            out["tokens_equal"] = out["columns"].pop("rows") == out["dense"].pop("rows")
+            res["requests"][label] = out
+        # ---- one block of 8 x 256 columns against one 2,048-token prompt through the single-cache path
+        t.batch_init(8, ctx)
+        prompts = [ck.iter_prompt_tokens(shape, seed + 50 + r, 256) for r in range(8)]
+        dt_slots, _ = best(lambda: t.batch_prefill_slots(list(range(8)), prompts, [0] * 8), 5)
+        res["block_ms"] = {"prefill_slots_8x256": 1e3 * dt_slots}
+    with q3.TransformerBuilder(path).with_ctx_length(ctx).build() as t:
+        one = ck.iter_prompt_tokens(shape, seed + 50, 2048)
+        dt_one, _ = best(lambda: t.prefill(one, 0, batched=True), 5)
+        res["block_ms"]["prefill_batched_1x2048"] = 1e3 * dt_one
+    print("RESULT " + json.dumps(res))
+
+
+def main_dense(a):
+    results = []
+    for name in a.models.split(","):
+        cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--worker", name, "--ctx", str(a.ctx),
+               "--ckpt-dir", a.ckpt_dir, "--seed", str(a.seed), "--dense-min", str(a.dense_min)]
+        p = subprocess.run(cmd, capture_output=True, text=True)
+        sys.stderr.write(p.stderr[-2000:])
+        if p.returncode != 0:
+            print(f"[bench_serve] {name}: exit status {p.returncode}; stopping here", file=sys.stderr)
+            break
+        results.append(json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")][-1][7:]))
+    os.makedirs(a.out, exist_ok=True)
+    with open(os.path.join(a.out, "serve_cols_dense.json"), "w") as f:
+        json.dump(results, f, indent=1)
+    lines = [DENSE_MARK + f" (dense_min {a.dense_min})", "",
+             "Written by `tools/bench_serve.py --dense-min` (context %d per slot).  `q3_generate_many_dense` against" % a.ctx,
+             "`q3_generate_many_greedy` on the same engine, best of 2 calls each behind a warm-up call; tok/s counts prompt + generated",
+             "tokens; prompt tok/s is the same mix with one new token per request.", "",
+             "| model | requests | loop | passes | blocks | seconds | requests/s | tok/s | prompt tok/s | tokens equal |", "|---|---|---|---|---|---|---|---|---|---|"]
+    for r in results:
+        for label, d in r["requests"].items():
+            for k in ("columns", "dense"):
+                lines.append(f"| {r['model']} | {label} | {k} | {d[k]['passes']} | {d[k].get('blocks', '')} | {d[k]['seconds']:.3f} | {d[k]['req_s']:.2f} | "
+                             f"{d[k]['tok_s']:.0f} | {d[k]['prompt_tok_s']:.0f} | {d['tokens_equal']} |")
+    lines += ["", "One block (wall time per call, best of 5): `q3_batch_prefill_slots` of 8 runs of 256 tokens into 8 slots against",
+              "`q3_prefill_batched` of one 2,048-token prompt (which also runs the classifier once and returns a token):", "",
+              "| model | prefill_slots 8 x 256 ms | prefill_batched 1 x 2,048 ms |", "|---|---|---|"]
+    for r in results:
+        lines.append(f"| {r['model']} | {r['block_ms']['prefill_slots_8x256']:.2f} | {r['block_ms']['prefill_batched_1x2048']:.2f} |")
+    md_path = os.path.join(a.out, "serve_cols.md")
+    old = open(md_path).read() if os.path.exists(md_path) else ""
+    if DENSE_MARK in old:                                              # replace the earlier section, up to the next heading of its level
+        at = old.index(DENSE_MARK)
+        nxt = old.find("\n## ", at + 1)
+        old = old[:at].rstrip("\n") + "\n" + (old[nxt:] if nxt >= 0 else "")
+    with open(md_path, "w") as f:
+        f.write(old.rstrip("\n") + "\n\n" + "\n".join(lines) + "\n")
+    return 0 if len(results) == len(a.models.split(",")) else 1
+
+
 def main_sampled(a):
     results = []
     for name in a.models.split(","):
@@ -233,7 +325,14 @@ def main():
     ap.add_argument("--worker")
     ap.add_argument("--temperature", type=float, help="with --topp: the workloads under the sampler (appends to serve_cols.md)")
     ap.add_argument("--topp", type=float, default=0.95)
+    ap.add_argument("--dense-min", type=int, help="long prompts through dense blocks against the column loop (appends to serve_cols.md; context 2,304)")
     a = ap.parse_args()
+    if a.dense_min is not None:
+        a.ctx = max(a.ctx, 2304)
+        if a.worker:
+            worker_dense(a.worker, a.ctx, a.ckpt_dir, a.seed, a.dense_min)
+            return 0
+        return main_dense(a)
     if a.temperature is not None:
         if a.worker:
             worker_sampled(a.worker, a.ctx, a.ckpt_dir, a.seed, a.temperature, a.topp)
@@ -259,7 +358,7 @@ def main():
     keep = ""
     if os.path.exists(md_path):
         old = open(md_path).read()
-        marks = [old.index(m) for m in (AB_MARK, SAMPLED_MARK) if m in old]      # sections other runs wrote
+        marks = [old.index(m) for m in (AB_MARK, SAMPLED_MARK, DENSE_MARK) if m in old]      # sections other runs wrote
         if marks:
             keep = old[min(marks):]
     lines = ["# Ragged column passes: pass cost and request throughput", "",
