@@ -52,7 +52,8 @@ typedef enum q3_status {
     Q3_ERR_FORMAT = -2,    /* bad magic / version / dims / truncated    (configuration.rs:116-146, utils.rs:21-56) */
     Q3_ERR_ARG = -3,       /* null pointer, token/pos out of range (the reference panics: layers.rs:73-75,335) */
     Q3_ERR_HIP = -4,       /* HIP runtime error / no device */
-    Q3_ERR_UNSUPPORTED = -5 /* shape the kernels do not cover (e.g. group_size not a multiple of 16) */
+    Q3_ERR_UNSUPPORTED = -5, /* shape the kernels do not cover (e.g. group_size not a multiple of 16) */
+    Q3_ERR_INTERNAL = -6   /* the library caught itself breaking one of its own invariants (section 2h: a scheduler that does not end) */
 } q3_status;
 
 /* ModelConfig, qwen3-inference/src/configuration.rs:18-30 (seq_len already clamped by ctx_len) */
@@ -534,6 +535,50 @@ int q3_batch_prefill_slots(q3_engine* e, const int32_t* slots, const int32_t* to
 int q3_generate_many_dense(q3_engine* e, const int32_t* prompts /* concatenated */, const size_t* prompt_len, const size_t* n_new,
                            size_t n_requests, const float* temperature, const float* topp, const uint64_t* seeds /* all three NULL: greedy */,
                            size_t dense_min, int32_t* out_tokens /* concatenated, n_new[r] each */, q3_cols_stats* stats, q3_dense_stats* dstats);
+
+/* ------------------------------------------------------------------------------------------------
+ * 2h. (behind 2g so that the earlier sections stay as they were.)  Stop tokens in the loop: requests end at EOS and free their
+ * slot at once.  The loops of sections 2e / 2f run a pass table that is a pure function of (prompt_len, n_new); for chat traffic
+ * n_new is a cap, and a request that emits EOS at token 20 of 512 would hold its slot, and a column of every pass, for 492 more
+ * passes.  Here the device decides after every pass which requests have ended, frees their slots, admits the next queued
+ * requests and lays out the next pass.
+ * With n_emit[r] = the index of the first stop token among request r's tokens plus one, or n_new[r] if there is none: rule 5 of
+ * q3_cols_schedule frees a slot when its request has produced n_new tokens, so a request that ends at its stop token is exactly
+ * a request with n_new[r] = n_emit[r].  The loop runs, pass for pass and column for column, the schedule
+ * q3_cols_schedule(prompt_len, n_emit, ...), and every token it returns is bit-identical to what q3_generate_many_greedy /
+ * q3_generate_many_sampled return for the same request.
+ * A small kernel between two passes applies the five rules to a scheduler state in device memory and writes the next pass as a
+ * table of one row; the kept plans of sections 2e / 2f and their turn kernels run it unchanged.  The host reads one 8-byte status
+ * per pass (the number of live columns picks the plan width): ONE SYNCHRONISATION PER PASS, where the loops of 2e / 2f
+ * synchronise once per call.  The names of the earlier sections launch exactly what they launched before.
+ * Dense blocks (q3_generate_many_dense's dense_min) are not offered in this section: every prompt enters through column passes.
+ * ------------------------------------------------------------------------------------------------ */
+#define Q3_STOP_MAX 8
+
+/* q3_generate_many_greedy (temperature, topp and seeds all NULL) or q3_generate_many_sampled, ending every request at its first
+ * stop token.  The output layout is theirs: request r's tokens start at out_tokens[n_new[0] + .. + n_new[r - 1]]; its first
+ * n_out[r] entries are its tokens, the stop token included as the last one, and the entries behind them are -1.
+ * n_out[r] == n_emit[r] as defined above.  stats counts the passes actually run: those of q3_cols_schedule(prompt_len, n_emit).
+ * Under the sampler the rules of section 2f hold: a request's first column loads its sampler into the slot, greedy and sampled
+ * requests may share passes, and no coin is drawn behind a stop token.  n_stop == 0: the call equals the loops of 2e / 2f.
+ * Q3_ERR_ARG: n_stop > Q3_STOP_MAX; a null stop_tokens with n_stop > 0; a stop token outside the vocabulary; a null n_out; some
+ * but not all of the three sampler arrays NULL; everything q3_generate_many_greedy / q3_generate_many_sampled reject.
+ * Q3_ERR_UNSUPPORTED: as for those two.
+ * Q3_ERR_INTERNAL: the scheduler asked for more than sum(prompt_len[r] + n_new[r]) passes (every pass advances at least one
+ * column, so it cannot): a bug ends as an error code, never as an endless loop. */
+int q3_generate_many_stop(q3_engine* e, const int32_t* prompts /* concatenated */, const size_t* prompt_len, const size_t* n_new,
+                          size_t n_requests, const float* temperature, const float* topp, const uint64_t* seeds /* all three NULL: greedy */,
+                          const int32_t* stop_tokens, size_t n_stop, int32_t* out_tokens /* concatenated, n_new[r] each */,
+                          size_t* n_out /* [n_requests] */, q3_cols_stats* stats);
+
+/* The passes q3_generate_many_stop runs when request r would produce the tokens rows[n_new[0] + .. + n_new[r - 1] ..] (host only,
+ * never touches the GPU): the scheduler step of the device loop, run pass by pass on the host and fed from rows.  table,
+ * n_entries and stats as for q3_cols_schedule; n_out as for q3_generate_many_stop; each may be NULL.
+ * Q3_ERR_ARG: what q3_cols_schedule rejects, null rows, n_stop > Q3_STOP_MAX, a null stop_tokens with n_stop > 0. */
+int q3_cols_schedule_stop(const size_t* prompt_len, const size_t* n_new, size_t n_requests, int max_streams,
+                          const int32_t* rows /* concatenated, n_new[r] each */, const int32_t* stop_tokens, size_t n_stop,
+                          int32_t* table /* [cap][4]: pass, slot, pos, request */, size_t cap, size_t* n_entries, size_t* n_out,
+                          q3_cols_stats* stats);
 
 #ifdef __cplusplus
 }

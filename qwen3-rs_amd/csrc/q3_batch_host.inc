@@ -115,6 +115,12 @@ struct BatchCtx {
     float *cols_temp = nullptr, *cols_topp = nullptr;
     unsigned long long* cols_seeds = nullptr;
     size_t cols_aux_cap = 0, cols_temp_cap = 0, cols_topp_cap = 0, cols_seeds_cap = 0;
+    // ... with stop tokens (q3_generate_many_stop): the scheduler state and its one-row table, the per-request records (grow-only),
+    // the pinned status word the host reads after every pass; allocated by the first call
+    ColsStopDev* cols_stop = nullptr;                   // device
+    SchedStatus* h_cols_stop = nullptr;
+    int* cols_req = nullptr;
+    size_t cols_req_cap = 0;
     // dense blocks over the per-stream caches (q3_batch_prefill_slots / q3_generate_many_dense): scratch of prefill_block_cap()
     // columns beside the 32-column one, allocated on first use; plans by block width, kept (no graph: the launches are enqueued
     // as they are, like q3_prefill_batched's); the run tables of a call, grow-only
@@ -214,7 +220,7 @@ void batch_free(q3_engine* e) {
     void* dptrs[] = {b->att_pf, b->qn, b->pq, b->ps, b->x, b->q, b->kraw, b->xb, b->hb, b->logits, b->key, b->value, b->att, b->xq_p, b->xs_p,
                      b->st, b->slots, b->out_tokens, b->stamps, b->d_sampler, b->d_probs, b->d_sp, b->d_keys, b->spec_io, b->spec_snap,
                      b->spec_samp, b->spec_probs, b->spec_sp, b->spec_keys, b->col_slot, b->cols_ctl, b->cols_table, b->cols_ncols, b->cols_prompts,
-                     b->cols_out, b->cols_draw, b->cols_step, b->cols_slot_samp, b->cols_aux, b->cols_temp, b->cols_topp, b->cols_seeds,
+                     b->cols_out, b->cols_draw, b->cols_step, b->cols_slot_samp, b->cols_aux, b->cols_temp, b->cols_topp, b->cols_seeds, b->cols_stop, b->cols_req,
                      b->dense.x, b->dense.q, b->dense.qn, b->dense.kraw, b->dense.xb, b->dense.hb, b->dense.xq_p, b->dense.xs_p, b->dense.st,
                      b->dense.col_slot, b->dense.att_pf, b->dense_runs};
     for (void* p : dptrs)
@@ -225,6 +231,7 @@ void batch_free(q3_engine* e) {
     if (b->h_spec) (void)hipHostFree(b->h_spec);
     if (b->h_cols) (void)hipHostFree(b->h_cols);
     if (b->h_cols_draw) (void)hipHostFree(b->h_cols_draw);
+    if (b->h_cols_stop) (void)hipHostFree(b->h_cols_stop);
     delete b;
     e->batch = nullptr;
 }

@@ -29,9 +29,11 @@ EXPORTED_SYMBOLS = [
     "q3_batch_step_cols", "q3_cols_schedule", "q3_generate_many_greedy",
     "q3_batch_step_cols_draw", "q3_generate_many_sampled",
     "q3_dense_pack", "q3_batch_prefill_slots", "q3_generate_many_dense",
+    "q3_generate_many_stop", "q3_cols_schedule_stop",
 ]
 VERIFY_MAX = 32          # Q3_VERIFY_MAX
 COLS_MAX = 32            # Q3_COLS_MAX
+STOP_MAX = 8             # Q3_STOP_MAX
 
 
 class Q3Error(RuntimeError):
@@ -218,6 +220,8 @@ def _bind(path: str) -> C.CDLL:
     L.q3_batch_prefill_slots.argtypes = [C.c_void_p, i32p, i32p, szp, i32p, sz, C.POINTER(_DenseStats)]
     L.q3_generate_many_dense.argtypes = [C.c_void_p, i32p, szp, szp, sz, fp, fp, C.POINTER(C.c_uint64), sz, i32p, C.POINTER(_ColsStats),
                                          C.POINTER(_DenseStats)]
+    L.q3_generate_many_stop.argtypes = [C.c_void_p, i32p, szp, szp, sz, fp, fp, C.POINTER(C.c_uint64), i32p, sz, i32p, szp, C.POINTER(_ColsStats)]
+    L.q3_cols_schedule_stop.argtypes = [szp, szp, sz, C.c_int, i32p, i32p, sz, i32p, sz, szp, szp, C.POINTER(_ColsStats)]
     L.q3_profile.argtypes = [C.c_void_p, sz, sz, C.c_int, fp, C.POINTER(C.c_int32), C.c_int]
     L.q3_profile_name.argtypes = [C.c_int]
     L.q3_profile_name.restype = C.c_char_p
@@ -279,6 +283,23 @@ def cols_schedule(prompt_len, n_new, max_streams: int):
     _check(L.q3_cols_schedule(pl, nn, len(prompt_len), max_streams, table, n.value, C.byref(n), C.byref(st)))
     rows = [tuple(int(table[4 * i + k]) for k in range(4)) for i in range(n.value)]
     return rows, ColsStats(st.passes, st.live_columns, st.prompt_columns, st.decode_columns)
+
+
+def cols_schedule_stop(prompt_len, n_new, max_streams: int, rows, stop_tokens):
+    """The passes generate_many_stop runs when request r would produce the tokens rows[r] (n_new[r] of them) and ends at its first
+    token of stop_tokens (q3_cols_schedule_stop, host only: the scheduler step of the device loop, run on the host).
+    Returns ([(pass, slot, pos, request), ...] in column order, n_out per request, ColsStats)."""
+    if len(prompt_len) != len(n_new) or len(rows) != len(n_new) or any(len(r) != int(k) for r, k in zip(rows, n_new)):
+        raise ValueError("one n_new and one row of n_new tokens per prompt")
+    L = load_library()
+    nr = len(prompt_len)
+    pl, nn, n, st = _size_array(prompt_len), _size_array(n_new), C.c_size_t(0), _ColsStats()
+    flat, stop, n_out = _i32_array([t for r in rows for t in r]), _i32_array(stop_tokens), _size_array([0] * nr)
+    _check(L.q3_cols_schedule_stop(pl, nn, nr, max_streams, flat, stop, len(stop_tokens), None, 0, C.byref(n), n_out, C.byref(st)))
+    table = (C.c_int32 * max(1, 4 * n.value))()
+    _check(L.q3_cols_schedule_stop(pl, nn, nr, max_streams, flat, stop, len(stop_tokens), table, n.value, C.byref(n), n_out, C.byref(st)))
+    cols = [tuple(int(table[4 * i + k]) for k in range(4)) for i in range(n.value)]
+    return cols, [int(n_out[r]) for r in range(nr)], ColsStats(st.passes, st.live_columns, st.prompt_columns, st.decode_columns)
 
 
 def dense_pack(run_len, block_cap: int):
@@ -622,6 +643,46 @@ class Transformer:
             rows.append([int(out[at + i]) for i in range(int(k))])
             at += int(k)
         return rows, ColsStats(st.passes, st.live_columns, st.prompt_columns, st.decode_columns), DenseStats(ds.blocks, ds.live_columns, ds.pad_columns)
+
+    # ---- stop tokens in the device loop (include/qwen3_hip.h section 2h)
+    cols_schedule_stop = staticmethod(cols_schedule_stop)
+
+    def generate_many_stop(self, prompts, n_new, stop_tokens, sampler=None, raw: bool = False):
+        """generate_many_greedy (sampler None) or generate_many_sampled (sampler = (temperature, topp, seeds), one value per
+        request or a scalar) with every request ended on the device at its first token of stop_tokens (at most 8;
+        q3_generate_many_stop): its slot goes to the next queued request at once, n_new[r] is a cap.  Returns (rows, ColsStats):
+        row r holds the request's tokens up to and including the stop token, the stats count the passes actually run.
+        raw=True: (the whole output buffer as the library filled it, n_out per request, ColsStats)."""
+        n = len(prompts)
+        if len(n_new) != n:
+            raise ValueError("one n_new per prompt")
+        tv = pv = sv = None
+        if sampler is not None:
+            def per_request(v, what):
+                vals = [v] * n if np.isscalar(v) else list(v)
+                if len(vals) != n:
+                    raise ValueError(f"one {what} per request, or a scalar")
+                return vals
+            temperature, topp, seeds = sampler
+            tv = (C.c_float * max(1, n))(*[float(v) for v in per_request(temperature, "temperature")])
+            pv = (C.c_float * max(1, n))(*[float(v) for v in per_request(topp, "topp")])
+            sv = (C.c_uint64 * max(1, n))(*[int(v) & 0xFFFFFFFFFFFFFFFF for v in per_request(seeds, "seed")])
+        stop = [int(t) for t in stop_tokens]
+        flat = [int(t) for p in prompts for t in p]
+        total = sum(int(k) for k in n_new)
+        out = (C.c_int32 * max(1, total))()
+        n_out = _size_array([0] * n)
+        st = _ColsStats()
+        self._batch_rc(self._lib.q3_generate_many_stop(self._h, _i32_array(flat), _size_array([len(p) for p in prompts]), _size_array(n_new),
+                                                       n, tv, pv, sv, _i32_array(stop), len(stop), out, n_out, C.byref(st)))
+        stats = ColsStats(st.passes, st.live_columns, st.prompt_columns, st.decode_columns)
+        if raw:
+            return [int(out[i]) for i in range(total)], [int(n_out[r]) for r in range(n)], stats
+        rows, at = [], 0
+        for r, k in enumerate(n_new):
+            rows.append([int(out[at + i]) for i in range(int(n_out[r]))])
+            at += int(k)
+        return rows, stats
 
     def set_batch_sampler(self, temperature: float, topp: float, rng_seeds):
         """one Sampler per stream (sampler.rs:29-42), stream i seeded with rng_seeds[i]; temperature 0 = greedy"""

@@ -140,12 +140,16 @@ def generate(transformer, prompt_tokens: Sequence[int], max_new_tokens: Optional
 
 
 def generate_many(transformer, prompts: Sequence[Sequence[int]], max_new_tokens: int, stop_tokens: Iterable[int] = (), sampler=None,
-                  dense_min: int = 0):
+                  dense_min: int = 0, stop_on_device: bool = False):
     """Many greedy generations served through the slots of Transformer.batch_init in ragged column passes
     (Transformer.generate_many_greedy).  Row r holds what Transformer.prefill(prompts[r], 0) followed by generate_greedy returns on
     an engine of its own: every prompt token goes through the model (chat's prompt loop, generation.rs:116-123), then up to
-    max_new_tokens tokens are decoded (fewer where the batch context ends first).  The device loop checks no stop token; each
-    row is cut behind its first stop token afterwards, the way generate ends at BOS / EOS (generation.rs:35).
+    max_new_tokens tokens are decoded (fewer where the batch context ends first).  Each row ends with its first stop token, the way
+    generate ends at BOS / EOS (generation.rs:35).  By default the device loop checks no stop token: every request runs to
+    max_new_tokens and its row is cut afterwards.
+    stop_on_device=True (with stop_tokens, at most 8): the device loop ends a request at its stop token and hands its slot to the
+    next queued request at once (Transformer.generate_many_stop): the same rows in fewer passes, at one synchronisation per
+    pass; the stats are those of the passes actually run.  Not offered together with dense_min > 0 (ValueError).
     sampler=(temperature, topp, seeds), each one value per prompt or a scalar for all: the same through
     Transformer.generate_many_sampled -- row r is what an engine of its own draws after set_sampler(temperature, topp, seed of r).
     dense_min > 0: prompts of more than dense_min tokens enter their slots through dense blocks, many prompts per weight pass
@@ -154,6 +158,8 @@ def generate_many(transformer, prompts: Sequence[Sequence[int]], max_new_tokens:
     if any(len(p) == 0 for p in prompts):
         raise ValueError("Please provide a prompt")
     stop = set(stop_tokens)
+    if stop_on_device and dense_min > 0:
+        raise ValueError("stop_on_device=True runs column passes only: no dense_min > 0")
     ctx = getattr(transformer, "_batch_ctx", transformer.get_config().seq_len)
     n_new = [max(min(max_new_tokens, ctx - len(p) + 1), 0) for p in prompts]
     live = [r for r, k in enumerate(n_new) if k > 0]
@@ -162,7 +168,10 @@ def generate_many(transformer, prompts: Sequence[Sequence[int]], max_new_tokens:
     if live:
         if sampler is not None:
             temperature, topp, seeds = ([v] * len(prompts) if np.isscalar(v) else list(v) for v in sampler)
-        if dense_min > 0:
+        if stop_on_device and stop:
+            per_live = None if sampler is None else tuple([v[r] for r in live] for v in (temperature, topp, seeds))
+            got, stats = transformer.generate_many_stop([prompts[r] for r in live], [n_new[r] for r in live], sorted(stop), per_live)
+        elif dense_min > 0:
             per_live = None if sampler is None else tuple([v[r] for r in live] for v in (temperature, topp, seeds))
             got, stats, _ = transformer.generate_many_dense([prompts[r] for r in live], [n_new[r] for r in live], per_live, dense_min)
         elif sampler is None:

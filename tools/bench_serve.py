@@ -27,6 +27,18 @@ and 32 requests of 2,048 + 64 on 32 slots through q3_generate_many_dense with th
 same engine (best of 2 calls each, the rows must be equal); prompt tok/s is measured by the same mixes with one new token per
 request; (f) one block: q3_batch_prefill_slots of 8 runs of 256 tokens against q3_prefill_batched of one 2,048-token prompt.
 Appends a section to <out>/serve_cols.md and writes <out>/serve_cols_dense.json.
+
+    python tools/bench_serve.py --stop [--models qwen3-0.6b,qwen3-8b]
+
+Stop tokens in the device loop (section 2h).  Per model: 64 requests through 32 slots with a cap of 256 new tokens -- 8 prompts of
+mixed lengths, each sent 8 times, interleaved.  The synthetic checkpoints emit no EOS, so the existing loop runs once at the cap
+and a stop set of at most 8 tokens is picked from its rows (the token that shortens the rows most, again and again) until
+sum(n_emit) <= sum(n_new) / 2.  (The greedy rows of 64 different prompts over a 151,936-token vocabulary share too few tokens for
+8 of them to halve the output; requests that repeat a prompt produce the same row and end at the same token.)  Then, best of 3
+calls each behind a warm-up call: (g) q3_generate_many_greedy at the cap plus the host cut; (h) q3_generate_many_stop; (i)
+q3_generate_many_greedy with n_new = n_emit -- the same passes with one synchronisation, the floor for (h).  (h) and (i) must run
+the same number of passes and all three must give equal rows up to the cut.  Appends a section to <out>/serve_cols.md and writes
+<out>/serve_cols_stop.json.
 """
 import argparse
 import json
@@ -41,6 +53,7 @@ sys.path.insert(0, os.path.join(ROOT, "qwen3-rs_amd"))
 AB_MARK = "## Batch-32 decode A/B"
 DENSE_MARK = "## Dense blocks over the slots"
 SAMPLED_MARK = "## Under the sampler"
+STOP_MARK = "## Stop tokens in the device loop"
 
 
 def median(xs):
@@ -235,6 +248,105 @@ def worker_dense(name, ctx, ckpt_dir, seed, dense_min):
     print("RESULT " + json.dumps(res))
 
 
+def n_emit_of(rows, stop):
+    return [next((i + 1 for i, t in enumerate(r) if t in stop), len(r)) for r in rows]
+
+
+def pick_stop_set(rows, limit=8):
+    """at most `limit` tokens, each the one that shortens the rows most given the ones before it, until the rows are half as long"""
+    total, stop = sum(len(r) for r in rows), []
+    while len(stop) < limit and sum(n_emit_of(rows, set(stop))) > total // 2:
+        emit = n_emit_of(rows, set(stop))
+        cand = sorted({t for r, e in zip(rows, emit) for t in r[:e]} - set(stop))
+        stop.append(min(cand, key=lambda t: (sum(n_emit_of(rows, set(stop) | {t})), t)))
+    return stop
+
+
+def worker_stop(name, ctx, ckpt_dir, seed):
+    import numpy as np
+    import qwen3_rs_amd as q3
+    ck = q3.checkpoint
+    shape = ck.SHAPES[name]
+    path = os.path.join(ckpt_dir, f"{name}-seed{seed}.q3bin")
+    ck.ensure_synthetic_checkpoint(path, shape, seed=seed)
+    rng = np.random.default_rng(7)
+    n_req, ms, cap = 64, 32, 256
+    plen = [int(v) for v in rng.integers(1, 200, 8)]
+    distinct = [ck.iter_prompt_tokens(shape, seed + 50 + r, n) for r, n in enumerate(plen)]
+    prompts = [distinct[r % 8] for r in range(n_req)]
+    nnew = [cap] * n_req
+
+    def best(call, n=3):
+        call()                                                         # plans of every width the schedule uses
+        dts = []
+        for _ in range(n):
+            t0 = time.perf_counter()
+            out = call()
+            dts.append(time.perf_counter() - t0)
+        return min(dts), out
+    with q3.TransformerBuilder(path).with_ctx_length(ctx).build() as t:
+        t.batch_init(ms, ctx)
+        rows, _ = t.generate_many_greedy(prompts, nnew)
+        stop = pick_stop_set(rows)
+        emit = n_emit_of(rows, set(stop))
+        print(f"[bench_serve] {name}: stop set {stop}: {sum(emit)} of {sum(nnew)} tokens", file=sys.stderr)
+        want = [r[:e] for r, e in zip(rows, emit)]
+
+        def at_cap():
+            got, st = t.generate_many_greedy(prompts, nnew)
+            return [r[:e] for r, e in zip(got, n_emit_of(got, set(stop)))], st         # the host cut is part of what is timed
+        dt_a, (rows_a, st_a) = best(at_cap)
+        dt_b, (rows_b, st_b) = best(lambda: t.generate_many_stop(prompts, nnew, stop))
+        dt_c, (rows_c, st_c) = best(lambda: t.generate_many_greedy(prompts, emit))
+    res = {"model": name, "ctx": ctx, "requests": n_req, "slots": ms, "cap": cap, "stop_set": stop, "sum_n_new": sum(nnew), "sum_n_emit": sum(emit),
+           "half_reached": 2 * sum(emit) <= sum(nnew), "rows_equal": rows_a == want and rows_b == want and rows_c == want,
+           "passes_equal": st_b.passes == st_c.passes,
+           "at_cap": {"passes": st_a.passes, "seconds": dt_a}, "stop": {"passes": st_b.passes, "seconds": dt_b},
+           "n_emit": {"passes": st_c.passes, "seconds": dt_c}, "per_pass_us": 1e6 * (dt_b - dt_c) / max(1, st_b.passes)}
+    print("RESULT " + json.dumps(res))
+
+
+def main_stop(a):
+    results = []
+    for name in a.models.split(","):
+        cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--worker", name, "--ctx", str(a.ctx),
+               "--ckpt-dir", a.ckpt_dir, "--seed", str(a.seed), "--stop"]
+        p = subprocess.run(cmd, capture_output=True, text=True)
+        sys.stderr.write(p.stderr[-2000:])
+        if p.returncode != 0:
+            print(f"[bench_serve] {name}: exit status {p.returncode}; stopping here", file=sys.stderr)
+            break
+        results.append(json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")][-1][7:]))
+    os.makedirs(a.out, exist_ok=True)
+    with open(os.path.join(a.out, "serve_cols_stop.json"), "w") as f:
+        json.dump(results, f, indent=1)
+    lines = [STOP_MARK, "",
+             "Written by `tools/bench_serve.py --stop` (context %d per slot): 64 requests through 32 slots (8 prompts of 1 to 199 tokens," % a.ctx,
+             "each sent 8 times, interleaved), a cap of 256 new tokens, and a stop set of at most 8 tokens picked from the rows of the",
+             "existing loop -- the token that shortens them most, again and again -- until the requests emit at most half the cap in total.",
+             "Wall time per call, best of 3 behind a warm-up call.  at the cap = `q3_generate_many_greedy` with n_new = 256 plus the host cut; stop = `q3_generate_many_stop`; n_emit = `q3_generate_many_greedy` with n_new = n_emit,",
+             "the same passes with one synchronisation.  us per pass = (stop - n_emit) / passes: the scheduler launches and the",
+             "synchronisation of one pass.", "",
+             "| model | stop set | tokens emitted / cap | loop | passes | seconds | us per pass | rows equal | passes equal |", "|---|---|---|---|---|---|---|---|---|"]
+    for r in results:
+        for k, label in (("at_cap", "at the cap"), ("stop", "stop"), ("n_emit", "n_emit")):
+            lines.append(f"| {r['model']} | {' '.join(str(t) for t in r['stop_set'])} | {r['sum_n_emit']} / {r['sum_n_new']} | {label} | {r[k]['passes']} | "
+                         f"{r[k]['seconds']:.3f} | {r['per_pass_us']:.1f} | {r['rows_equal']} | {r['passes_equal']} |" if k == "stop" else
+                         f"| {r['model']} | | | {label} | {r[k]['passes']} | {r[k]['seconds']:.3f} | | | |")
+    if not results:
+        lines.append("not taken")
+    md_path = os.path.join(a.out, "serve_cols.md")
+    old = open(md_path).read() if os.path.exists(md_path) else ""
+    if STOP_MARK in old:                                               # replace the earlier section, up to the next heading of its level
+        at = old.index(STOP_MARK)
+        nxt = old.find("\n## ", at + 1)
+        old = old[:at].rstrip("\n") + "\n" + (old[nxt:] if nxt >= 0 else "")
+    with open(md_path, "w") as f:
+        f.write(old.rstrip("\n") + "\n\n" + "\n".join(lines) + "\n")
+    ok = len(results) == len(a.models.split(",")) and all(r["rows_equal"] and r["passes_equal"] and r["half_reached"] for r in results)
+    return 0 if ok else 1
+
+
 def main_dense(a):
     results = []
     for name in a.models.split(","):
@@ -326,7 +438,13 @@ def main():
     ap.add_argument("--temperature", type=float, help="with --topp: the workloads under the sampler (appends to serve_cols.md)")
     ap.add_argument("--topp", type=float, default=0.95)
     ap.add_argument("--dense-min", type=int, help="long prompts through dense blocks against the column loop (appends to serve_cols.md; context 2,304)")
+    ap.add_argument("--stop", action="store_true", help="stop tokens in the device loop against the loop at the cap (appends to serve_cols.md)")
     a = ap.parse_args()
+    if a.stop:
+        if a.worker:
+            worker_stop(a.worker, a.ctx, a.ckpt_dir, a.seed)
+            return 0
+        return main_stop(a)
     if a.dense_min is not None:
         a.ctx = max(a.ctx, 2304)
         if a.worker:
@@ -358,7 +476,7 @@ def main():
     keep = ""
     if os.path.exists(md_path):
         old = open(md_path).read()
-        marks = [old.index(m) for m in (AB_MARK, SAMPLED_MARK, DENSE_MARK) if m in old]      # sections other runs wrote
+        marks = [old.index(m) for m in (AB_MARK, SAMPLED_MARK, DENSE_MARK, STOP_MARK) if m in old]      # sections other runs wrote
         if marks:
             keep = old[min(marks):]
     lines = ["# Ragged column passes: pass cost and request throughput", "",
