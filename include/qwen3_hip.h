@@ -580,6 +580,63 @@ int q3_cols_schedule_stop(const size_t* prompt_len, const size_t* n_new, size_t 
                           int32_t* table /* [cap][4]: pass, slot, pos, request */, size_t cap, size_t* n_entries, size_t* n_out,
                           q3_cols_stats* stats);
 
+/* ------------------------------------------------------------------------------------------------
+ * 2i. (behind 2h so that the earlier sections stay as they were.)  A shared prompt prefix: prefill once, copy its key and value
+ * rows to the slots.  Chat requests begin with the same system prompt, template or few-shot block, and the loops of sections 2e to 2h
+ * send those tokens through the weights again for every request.  Those sections guarantee that a slot's cache rows are bit-identical
+ * whichever slot a request lands in and whatever the slot held before, so the rows of a shared prefix are the same bits in every
+ * slot: sharing them is a copy, with nothing to approximate and no tolerance.
+ * The batched caches are f32 [stream][layer][context][kv_dim], so rows [p, p + n) of one layer of one slot are one contiguous run in
+ * the key cache and one in the value cache.  One kernel launch copies such runs of every layer of both caches from one source to up
+ * to 32 destinations; every source word is read once and written once per destination, as raw 32-bit words (NaN payloads, -0.0 and
+ * denormals pass through).  The prefix is COPIED into each slot and the attention kernels read it there as they read any other
+ * row.  Not offered: dense entry of the suffixes (q3_generate_many_dense's dense_min), a different prefix per request, and
+ * attention that reads a shared prefix in place without the copy.
+ * ------------------------------------------------------------------------------------------------ */
+
+/* Rows first_pos .. first_pos + n_rows - 1 of every layer of src_slot's key and value caches are copied into each of the n_dst slots
+ * dst_slots[i].  No other row of any slot changes and no rng is touched.  This is what forking needs: several samples of one prompt,
+ * or one conversation continued several ways.  Allowed on a Q3_FLAG_FAST engine (it only copies).  The call synchronises once.
+ * Q3_ERR_ARG: no q3_batch_init; n_dst outside 1 .. max_streams - 1; a slot outside 0 .. max_streams - 1; src_slot among the
+ * destinations; a destination named twice; n_rows == 0; first_pos + n_rows > the batch context. */
+int q3_batch_copy_rows(q3_engine* e, int src_slot, const int32_t* dst_slots, int n_dst, size_t first_pos, size_t n_rows);
+
+/* The resident prefix.  tokens[0 .. n) are prefilled at positions 0 .. n - 1 INTO SLOT 0 -- rows 0 .. n - 1 of slot 0 are overwritten
+ * -- by the blocks and passes of q3_batch_prefill_slots (dense blocks where the shape takes them, column passes otherwise), in a form
+ * that touches no slot rng whatever q3_batch_sampler_set says.  The rows are then copied into a prefix store of
+ * 2 * n_layers * n * kv_dim floats, allocated beside the batched state and released with it (q3_batch_init drops it).  The store is
+ * private to this section: no other entry point reads or writes it, q3_batch_reset_kv leaves it alone, and whatever later calls do
+ * to slot 0 does not change it.  The engine keeps n and a copy of the tokens.  n == 0 releases the store; a new prefix replaces the
+ * old one; a call that fails leaves no prefix resident.
+ * Q3_ERR_ARG: no q3_batch_init; n >= the batch context; a token outside the vocabulary.
+ * Q3_ERR_UNSUPPORTED: what q3_batch_prefill_slots refuses (a Q3_FLAG_FAST engine, the shapes q3_batch_step_cols refuses). */
+int q3_batch_prefix_set(q3_engine* e, const int32_t* tokens, size_t n);
+
+/* What is resident: *n = the number of prefix tokens (0: none, also without q3_batch_init); tokens (may be NULL) receives the
+ * first min(*n, cap) of them. */
+int q3_batch_prefix_get(const q3_engine* e, size_t* n, int32_t* tokens, size_t cap);
+
+/* q3_generate_many_stop for requests that all begin with the resident prefix of P tokens.  The arguments are those of
+ * q3_generate_many_stop; prompts and prompt_len are each request's SUFFIX, at least one token, behind the prefix.
+ * For every request r, out_tokens and n_out[r] are exactly what q3_generate_many_stop returns for the full prompt prefix ++ suffix_r
+ * with the same sampler arrays and stop set -- with n_stop == 0, what q3_generate_many_greedy / q3_generate_many_sampled return.
+ * The passes are those of q3_cols_schedule(suffix lengths, n_emit) with P added to every position, and stats counts them: the
+ * schedule no longer contains the prefix.
+ * In front of the first pass one kernel launch copies the store into rows 0 .. P - 1 of the min(n_requests, max_streams) lowest
+ * slots, the slots the schedule can use (rule 1 admits into the lowest free slot).  Requests write only rows >= P and slots are not
+ * cleared between occupants, so the one copy serves every later occupant of a slot.  n_stop == 0 runs the tabled loop of sections
+ * 2e / 2f: device-resident, the copy enqueued on the engine's stream, one synchronisation per call.  n_stop > 0 runs the loop of
+ * section 2h.
+ * Under the sampler the prompt loop draws and discards one coin per prompt position (section 2f), so a sampled request enters its
+ * first column with its seed state advanced P coins; a greedy request draws no coin.
+ * Dense entry of the suffixes (dense_min) is not offered in this section: every suffix enters through column passes.
+ * Q3_ERR_ARG: no resident prefix; P + prompt_len[r] + n_new[r] - 1 > the batch context; everything q3_generate_many_stop rejects.
+ * Q3_ERR_UNSUPPORTED, Q3_ERR_INTERNAL: as for q3_generate_many_stop. */
+int q3_generate_many_prefix(q3_engine* e, const int32_t* prompts /* suffixes, concatenated */, const size_t* prompt_len, const size_t* n_new,
+                            size_t n_requests, const float* temperature, const float* topp, const uint64_t* seeds /* all three NULL: greedy */,
+                            const int32_t* stop_tokens, size_t n_stop, int32_t* out_tokens /* concatenated, n_new[r] each */,
+                            size_t* n_out /* [n_requests] */, q3_cols_stats* stats);
+
 #ifdef __cplusplus
 }
 #endif

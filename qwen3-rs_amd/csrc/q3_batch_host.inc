@@ -129,6 +129,11 @@ struct BatchCtx {
     std::map<int, std::vector<Launch>> dense_plans;
     DenseRun* dense_runs = nullptr;
     size_t dense_runs_cap = 0;
+    // the resident shared prefix (q3_batch_prefix_set): key and value rows 0 .. prefix_n - 1 of every layer, [2][n_layers][prefix_n][kv_dim],
+    // beside the per-stream caches and private to section 2i; the tokens they were computed from
+    float* prefix_store = nullptr;
+    size_t prefix_n = 0;
+    std::vector<int32_t> prefix_tokens;
     // packed-matrix directory
     struct PM { size_t q_off, s_off; int ntiles, ng; };
     std::vector<PM> m_qkv, m_wo, m_w13, m_w2;
@@ -222,7 +227,7 @@ void batch_free(q3_engine* e) {
                      b->spec_samp, b->spec_probs, b->spec_sp, b->spec_keys, b->col_slot, b->cols_ctl, b->cols_table, b->cols_ncols, b->cols_prompts,
                      b->cols_out, b->cols_draw, b->cols_step, b->cols_slot_samp, b->cols_aux, b->cols_temp, b->cols_topp, b->cols_seeds, b->cols_stop, b->cols_req,
                      b->dense.x, b->dense.q, b->dense.qn, b->dense.kraw, b->dense.xb, b->dense.hb, b->dense.xq_p, b->dense.xs_p, b->dense.st,
-                     b->dense.col_slot, b->dense.att_pf, b->dense_runs};
+                     b->dense.col_slot, b->dense.att_pf, b->dense_runs, b->prefix_store};
     for (void* p : dptrs)
         if (p) (void)hipFree(p);
     if (b->h_st) (void)hipHostFree(b->h_st);

@@ -10,6 +10,9 @@
 
 namespace {
 
+// q3_prefix_host.inc: one launch on the stream that copies the resident prefix into rows 0 .. P - 1 of slots 0 .. n_slots - 1
+int prefix_bcast_slots(q3_engine* e, int n_slots);
+
 // The schedule of q3_generate_many_greedy (stated in the header): emit(pass, slot, pos, request) for every column, in column order.
 template <class Emit>
 void cols_schedule_run(const size_t* prompt_len, const size_t* n_new, size_t n_requests, int max_streams, Emit&& emit, q3_cols_stats& st) {
@@ -235,6 +238,7 @@ struct ColsJob {
     std::vector<DenseRun> runs;
     std::vector<ColsJobStep> steps;
     size_t max_end = 0;                 // the largest position + 1 a wide block attends over
+    int bcast_slots = 0;                // > 0: the resident prefix goes into the lowest bcast_slots slots in front of the first pass (section 2i)
     // a new pass of the table; returns its index
     size_t add_pass(bool draw) {
         ncols.push_back(0);
@@ -316,6 +320,7 @@ int cols_job_run(q3_engine* e, ColsJob& job, bool draw, const ColsJobSampler& sm
     // the coins of the wide blocks first: a turn kernel reads a slot's rng when it sets a pass up, one pass ahead of the stream, so
     // a skip enqueued next to its block would be overwritten by the commit of a pass of the same slot set up before it.  One
     // launch per block: the pieces of a run that spans blocks are the same slot's
+    if (job.bcast_slots && (rc = prefix_bcast_slots(e, job.bcast_slots))) return rc;
     if (draw && smp.skip_wide)
         for (const ColsJobStep& s : job.steps)
             if (s.wide && (rc = launch_now(e->stream, k_dense_rng_skip, dim3(1), dim3(64), 0, smp.slot_ss, (const DenseRun*)(b->dense_runs + s.r0), (int)s.nr))) return rc;
@@ -407,9 +412,11 @@ void dense_job_add(q3_engine* e, ColsJob& job, const std::vector<DenseIn>& in, b
 // table; under the sampler a parallel table of ColAux, the per-request sampler parameters and the sampled plans.
 // dense_min > 0 (q3_generate_many_dense): a request with prompt_len - 1 >= dense_min enters the schedule with a prompt of one
 // column, its last prompt token; the tokens in front of it go through dense blocks enqueued in front of the pass that holds it.
+// pos_base > 0 (q3_generate_many_prefix, dense_min 0): the prompts are suffixes behind the resident prefix of pos_base tokens, which
+// is copied into the slots in front of the first pass; every position of the table moves up by pos_base, nothing else changes.
 int cols_generate(q3_engine* e, const int32_t* prompts, const size_t* prompt_len, const size_t* n_new, size_t n_requests, const float* temperature,
                   const float* topp, const uint64_t* seeds, int32_t* out_tokens, q3_cols_stats* stats, size_t dense_min = 0,
-                  q3_dense_stats* dstats = nullptr) {
+                  q3_dense_stats* dstats = nullptr, size_t pos_base = 0) {
     int rc;
     const bool draw = temperature != nullptr;
     BatchCtx* b = e->batch;
@@ -419,8 +426,8 @@ int cols_generate(q3_engine* e, const int32_t* prompts, const size_t* prompt_len
     std::vector<char> dense(n_requests, 0);
     size_t n_prompt = 0, n_out = 0;
     for (size_t r = 0; r < n_requests; ++r) {
-        if (prompt_len[r] + n_new[r] - 1 > (size_t)b->ctx)
-            return fail(Q3_ERR_ARG, "request %zu: prompt of %zu + %zu new tokens exceeds seq_len %d", r, prompt_len[r], n_new[r], b->ctx);
+        if (pos_base + prompt_len[r] + n_new[r] - 1 > (size_t)b->ctx)
+            return fail(Q3_ERR_ARG, "request %zu: prompt of %zu + %zu new tokens exceeds seq_len %d", r, pos_base + prompt_len[r], n_new[r], b->ctx);
         p_off[r] = n_prompt;
         o_off[r] = n_out;
         n_prompt += prompt_len[r];
@@ -442,6 +449,7 @@ int cols_generate(q3_engine* e, const int32_t* prompts, const size_t* prompt_len
     }, st);
     // the pass table: kColsMax entries per pass.  In front of a pass, the blocks of the dense requests whose column it holds
     ColsJob job;
+    if (pos_base) job.bcast_slots = (int)std::min<size_t>(n_requests, (size_t)b->max_streams);
     q3_dense_stats dst{0, 0, 0};
     std::vector<char> loaded(n_requests, 0);
     std::vector<size_t> wide_coins(n_requests, 0);
@@ -466,7 +474,7 @@ int cols_generate(q3_engine* e, const int32_t* prompts, const size_t* prompt_len
             const size_t shift = dense[s.req] ? prompt_len[s.req] - 1 : 0, el = eff_len[s.req];
             ColEnt c;
             c.slot = s.slot;
-            c.pos = (int)(s.pos + shift);
+            c.pos = (int)(s.pos + shift + pos_base);
             c.src = s.pos < el ? (int)(p_off[s.req] + s.pos + shift) : -1;
             c.out = s.pos + 1 >= el ? (int)(o_off[s.req] + (s.pos + 1 - el)) : -1;
             const size_t at = p * kColsMax + job.ncols[p]++;

@@ -37,6 +37,7 @@
 #include "q3_batch.h"
 #include "q3_sampler.h"
 #include "q3_stop.h"
+#include "q3_prefix.h"
 #include "q3_lookup.h"
 
 namespace {
@@ -1881,3 +1882,4 @@ int q3_op_argmax(const float* logits, size_t n, int32_t* index, int device) {
 #include "q3_dense_host.inc"
 #include "q3_cols_host.inc"
 #include "q3_stop_host.inc"
+#include "q3_prefix_host.inc"

@@ -24,6 +24,8 @@ struct ColsSched {
     int next;                           // queue head: the next request to admit
     int n_stop;
     int stop[kStopMax];
+    int pos_base;                       // added to every column's position: the rows in front of it hold a shared prefix (section 2i)
+    int pad_;
     const int* p_off;                   // per request: offset of the prompt in ColsCtl::prompts
     const int* prompt_len;
     const int* n_new;
@@ -83,7 +85,7 @@ __host__ __device__ inline void cols_sched_step(ColsSched& s, const int* slot_la
     for (int i = 0; i < ms; ++i) {
         SchedSlot& t = s.slot[i];
         if (t.req < 0 || t.fed != t.plen) continue;
-        row[cols] = ColEnt{i, t.fed + t.g - 1, -1, t.ooff + t.g};
+        row[cols] = ColEnt{i, s.pos_base + t.fed + t.g - 1, -1, t.ooff + t.g};
         if (aux) aux[cols] = ColAux{-1, 0, 1, 1};
         t.took = -1;
         ++cols;
@@ -98,7 +100,7 @@ __host__ __device__ inline void cols_sched_step(ColsSched& s, const int* slot_la
         for (int k = 0; k < n; ++k) {
             const int pos = t.fed + k;
             const int out = pos + 1 == pl ? t.ooff : -1;       // the run's last column emits y_0
-            row[cols] = ColEnt{i, pos, t.poff + pos, out};
+            row[cols] = ColEnt{i, s.pos_base + pos, t.poff + pos, out};
             if (aux) aux[cols] = ColAux{pos == 0 ? t.req : -1, k, out >= 0 ? 1 : 0, k == n - 1 ? 1 : 0};
             ++cols;
         }

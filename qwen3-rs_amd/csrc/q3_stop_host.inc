@@ -50,7 +50,7 @@ void stop_sched_init(ColsSched& s, int max_streams, size_t n_requests, const int
 
 int cols_generate_stop(q3_engine* e, const int32_t* prompts, const size_t* prompt_len, const size_t* n_new, size_t n_requests,
                        const float* temperature, const float* topp, const uint64_t* seeds, const int32_t* stop_tokens, size_t n_stop,
-                       int32_t* out_tokens, size_t* n_out, q3_cols_stats* stats) {
+                       int32_t* out_tokens, size_t* n_out, q3_cols_stats* stats, size_t pos_base = 0) {
     int rc;
     const bool draw = temperature != nullptr;
     BatchCtx* b = e->batch;
@@ -61,8 +61,8 @@ int cols_generate_stop(q3_engine* e, const int32_t* prompts, const size_t* promp
             return fail(Q3_ERR_ARG, "index out of range: stop token %d (vocab_size %d)", stop_tokens[k], e->cfg.vocab_size);
     if ((rc = cols_schedule_check(prompt_len, n_new, n_requests, b->max_streams))) return rc;
     for (size_t r = 0; r < n_requests; ++r)
-        if (prompt_len[r] + n_new[r] - 1 > (size_t)b->ctx)
-            return fail(Q3_ERR_ARG, "request %zu: prompt of %zu + %zu new tokens exceeds seq_len %d", r, prompt_len[r], n_new[r], b->ctx);
+        if (pos_base + prompt_len[r] + n_new[r] - 1 > (size_t)b->ctx)
+            return fail(Q3_ERR_ARG, "request %zu: prompt of %zu + %zu new tokens exceeds seq_len %d", r, pos_base + prompt_len[r], n_new[r], b->ctx);
     StopRequests rq;
     if ((rc = stop_requests(prompt_len, n_new, n_requests, rq))) return rc;
     for (size_t i = 0; i < rq.n_prompt; ++i)
@@ -91,6 +91,7 @@ int cols_generate_stop(q3_engine* e, const int32_t* prompts, const size_t* promp
     ColsStopDev* d = b->cols_stop;
     ColsSched sched;
     stop_sched_init(sched, b->max_streams, n_requests, stop_tokens, n_stop);
+    sched.pos_base = (int)pos_base;
     sched.p_off = dreq;
     sched.prompt_len = dreq + n_requests;
     sched.n_new = dreq + 2 * n_requests;
@@ -122,6 +123,8 @@ int cols_generate_stop(q3_engine* e, const int32_t* prompts, const size_t* promp
     h->ctl.prompts = b->cols_prompts;
     h->ctl.out_tokens = b->cols_out;
     HIP_TRY(hipMemcpyAsync(b->cols_ctl, &h->ctl, sizeof(ColsCtl), hipMemcpyHostToDevice, e->stream));
+    // the shared prefix in front of every request: rows 0 .. pos_base - 1 of the slots the scheduler can use
+    if (pos_base && (rc = prefix_bcast_slots(e, (int)std::min<size_t>(n_requests, (size_t)b->max_streams)))) return rc;
 
     // every pass advances at least one column of a request that has prompt_len + n_new - 1 of them at the most: a scheduler that
     // asks for more passes than that is wrong, and the call ends with an error code

@@ -30,6 +30,7 @@ EXPORTED_SYMBOLS = [
     "q3_batch_step_cols_draw", "q3_generate_many_sampled",
     "q3_dense_pack", "q3_batch_prefill_slots", "q3_generate_many_dense",
     "q3_generate_many_stop", "q3_cols_schedule_stop",
+    "q3_batch_copy_rows", "q3_batch_prefix_set", "q3_batch_prefix_get", "q3_generate_many_prefix",
 ]
 VERIFY_MAX = 32          # Q3_VERIFY_MAX
 COLS_MAX = 32            # Q3_COLS_MAX
@@ -222,6 +223,10 @@ def _bind(path: str) -> C.CDLL:
                                          C.POINTER(_DenseStats)]
     L.q3_generate_many_stop.argtypes = [C.c_void_p, i32p, szp, szp, sz, fp, fp, C.POINTER(C.c_uint64), i32p, sz, i32p, szp, C.POINTER(_ColsStats)]
     L.q3_cols_schedule_stop.argtypes = [szp, szp, sz, C.c_int, i32p, i32p, sz, i32p, sz, szp, szp, C.POINTER(_ColsStats)]
+    L.q3_batch_copy_rows.argtypes = [C.c_void_p, C.c_int, i32p, C.c_int, sz, sz]
+    L.q3_batch_prefix_set.argtypes = [C.c_void_p, i32p, sz]
+    L.q3_batch_prefix_get.argtypes = [C.c_void_p, szp, i32p, sz]
+    L.q3_generate_many_prefix.argtypes = L.q3_generate_many_stop.argtypes
     L.q3_profile.argtypes = [C.c_void_p, sz, sz, C.c_int, fp, C.POINTER(C.c_int32), C.c_int]
     L.q3_profile_name.argtypes = [C.c_int]
     L.q3_profile_name.restype = C.c_char_p
@@ -653,6 +658,9 @@ class Transformer:
         q3_generate_many_stop): its slot goes to the next queued request at once, n_new[r] is a cap.  Returns (rows, ColsStats):
         row r holds the request's tokens up to and including the stop token, the stats count the passes actually run.
         raw=True: (the whole output buffer as the library filled it, n_out per request, ColsStats)."""
+        return self._generate_many_stop(self._lib.q3_generate_many_stop, prompts, n_new, stop_tokens, sampler, raw)
+
+    def _generate_many_stop(self, fn, prompts, n_new, stop_tokens, sampler, raw):
         n = len(prompts)
         if len(n_new) != n:
             raise ValueError("one n_new per prompt")
@@ -673,8 +681,8 @@ class Transformer:
         out = (C.c_int32 * max(1, total))()
         n_out = _size_array([0] * n)
         st = _ColsStats()
-        self._batch_rc(self._lib.q3_generate_many_stop(self._h, _i32_array(flat), _size_array([len(p) for p in prompts]), _size_array(n_new),
-                                                       n, tv, pv, sv, _i32_array(stop), len(stop), out, n_out, C.byref(st)))
+        self._batch_rc(fn(self._h, _i32_array(flat), _size_array([len(p) for p in prompts]), _size_array(n_new),
+                        n, tv, pv, sv, _i32_array(stop), len(stop), out, n_out, C.byref(st)))
         stats = ColsStats(st.passes, st.live_columns, st.prompt_columns, st.decode_columns)
         if raw:
             return [int(out[i]) for i in range(total)], [int(n_out[r]) for r in range(n)], stats
@@ -683,6 +691,34 @@ class Transformer:
             rows.append([int(out[at + i]) for i in range(int(n_out[r]))])
             at += int(k)
         return rows, stats
+
+    # ---- a shared prompt prefix (include/qwen3_hip.h section 2i)
+    def batch_copy_rows(self, src_slot: int, dst_slots, first_pos: int, n_rows: int):
+        """Key and value rows first_pos .. first_pos + n_rows - 1 of every layer of slot src_slot are copied into each slot of
+        dst_slots by one kernel launch (q3_batch_copy_rows); nothing else changes.  What forking a prompt needs."""
+        if first_pos < 0 or n_rows < 0:
+            raise IndexError("negative index")
+        self._batch_rc(self._lib.q3_batch_copy_rows(self._h, int(src_slot), _i32_array(dst_slots), len(dst_slots), first_pos, n_rows))
+
+    def batch_prefix_set(self, tokens):
+        """Make `tokens` the resident shared prefix (q3_batch_prefix_set): they are prefilled once at positions 0 .. into slot 0,
+        whose rows 0 .. len(tokens) - 1 are overwritten, and kept in a store of their own for generate_many_prefix.  [] releases it."""
+        self._batch_rc(self._lib.q3_batch_prefix_set(self._h, _i32_array(tokens), len(tokens)))
+
+    def batch_prefix_get(self) -> List[int]:
+        """The tokens of the resident shared prefix ([]: none)"""
+        n = C.c_size_t(0)
+        _check(self._lib.q3_batch_prefix_get(self._h, C.byref(n), None, 0))
+        buf = (C.c_int32 * max(1, n.value))()
+        _check(self._lib.q3_batch_prefix_get(self._h, C.byref(n), buf, n.value))
+        return [int(buf[i]) for i in range(n.value)]
+
+    def generate_many_prefix(self, suffixes, n_new, stop_tokens=(), sampler=None, raw: bool = False):
+        """generate_many_stop for requests that all begin with the resident prefix (q3_generate_many_prefix): suffixes[r] is what
+        follows the prefix in request r (at least one token).  The rows are those of generate_many_stop -- without stop tokens, of
+        generate_many_greedy / generate_many_sampled -- on the full prompts prefix + suffixes[r]; the passes are those of the
+        suffixes alone.  Arguments and return value as for generate_many_stop."""
+        return self._generate_many_stop(self._lib.q3_generate_many_prefix, suffixes, n_new, stop_tokens, sampler, raw)
 
     def set_batch_sampler(self, temperature: float, topp: float, rng_seeds):
         """one Sampler per stream (sampler.rs:29-42), stream i seeded with rng_seeds[i]; temperature 0 = greedy"""

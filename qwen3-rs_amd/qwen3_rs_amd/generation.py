@@ -139,8 +139,20 @@ def generate(transformer, prompt_tokens: Sequence[int], max_new_tokens: Optional
     return out, metrics
 
 
+def common_prefix_len(prompts: Sequence[Sequence[int]]) -> int:
+    """The length of the longest prefix all prompts share that leaves every prompt at least one token behind it."""
+    if not prompts:
+        return 0
+    n = min(len(p) for p in prompts) - 1
+    first = prompts[0]
+    k = 0
+    while k < n and all(p[k] == first[k] for p in prompts):
+        k += 1
+    return k
+
+
 def generate_many(transformer, prompts: Sequence[Sequence[int]], max_new_tokens: int, stop_tokens: Iterable[int] = (), sampler=None,
-                  dense_min: int = 0, stop_on_device: bool = False):
+                  dense_min: int = 0, stop_on_device: bool = False, shared_prefix=None):
     """Many greedy generations served through the slots of Transformer.batch_init in ragged column passes
     (Transformer.generate_many_greedy).  Row r holds what Transformer.prefill(prompts[r], 0) followed by generate_greedy returns on
     an engine of its own: every prompt token goes through the model (chat's prompt loop, generation.rs:116-123), then up to
@@ -154,21 +166,41 @@ def generate_many(transformer, prompts: Sequence[Sequence[int]], max_new_tokens:
     Transformer.generate_many_sampled -- row r is what an engine of its own draws after set_sampler(temperature, topp, seed of r).
     dense_min > 0: prompts of more than dense_min tokens enter their slots through dense blocks, many prompts per weight pass
     (Transformer.generate_many_dense); the rows are the same for any value, 0 keeps the column loops.
+    shared_prefix: a token list that every request begins with; `prompts` are then the SUFFIXES behind it.  The prefix is prefilled
+    once (Transformer.batch_prefix_set, unless it is already resident; rows 0 .. of slot 0 are overwritten), its cache rows are
+    copied into the slots, and only the suffixes go through the weights (Transformer.generate_many_prefix): the rows are those of the
+    full prompts prefix + suffix, the stats those of the suffixes.  shared_prefix=True takes the longest common prefix of `prompts`
+    that leaves every prompt a token (common_prefix_len); where the prompts share nothing it is shared_prefix=None.  None (the
+    default) keeps the behaviour above.  Not offered together with dense_min > 0 (ValueError).
     Returns (rows, ColsStats)."""
     if any(len(p) == 0 for p in prompts):
         raise ValueError("Please provide a prompt")
     stop = set(stop_tokens)
     if stop_on_device and dense_min > 0:
         raise ValueError("stop_on_device=True runs column passes only: no dense_min > 0")
+    if shared_prefix is not None and shared_prefix is not False and dense_min > 0:
+        raise ValueError("shared_prefix runs column passes only: no dense_min > 0")
+    prefix: List[int] = []
+    if shared_prefix is True:
+        k = common_prefix_len(prompts)
+        prefix, prompts = [int(t) for t in prompts[0][:k]], [p[k:] for p in prompts]
+    elif shared_prefix is not None and shared_prefix is not False:
+        prefix = [int(t) for t in shared_prefix]
     ctx = getattr(transformer, "_batch_ctx", transformer.get_config().seq_len)
-    n_new = [max(min(max_new_tokens, ctx - len(p) + 1), 0) for p in prompts]
+    n_new = [max(min(max_new_tokens, ctx - len(prefix) - len(p) + 1), 0) for p in prompts]
     live = [r for r, k in enumerate(n_new) if k > 0]
     rows: List[List[int]] = [[] for _ in prompts]
     stats = None
     if live:
         if sampler is not None:
             temperature, topp, seeds = ([v] * len(prompts) if np.isscalar(v) else list(v) for v in sampler)
-        if stop_on_device and stop:
+        if prefix:
+            if transformer.batch_prefix_get() != prefix:
+                transformer.batch_prefix_set(prefix)
+            per_live = None if sampler is None else tuple([v[r] for r in live] for v in (temperature, topp, seeds))
+            got, stats = transformer.generate_many_prefix([prompts[r] for r in live], [n_new[r] for r in live],
+                                                          sorted(stop) if stop_on_device else (), per_live)
+        elif stop_on_device and stop:
             per_live = None if sampler is None else tuple([v[r] for r in live] for v in (temperature, topp, seeds))
             got, stats = transformer.generate_many_stop([prompts[r] for r in live], [n_new[r] for r in live], sorted(stop), per_live)
         elif dense_min > 0:

@@ -39,6 +39,16 @@ calls each behind a warm-up call: (g) q3_generate_many_greedy at the cap plus th
 q3_generate_many_greedy with n_new = n_emit -- the same passes with one synchronisation, the floor for (h).  (h) and (i) must run
 the same number of passes and all three must give equal rows up to the cut.  Appends a section to <out>/serve_cols.md and writes
 <out>/serve_cols_stop.json.
+
+    python tools/bench_serve.py --prefix 512 [--models qwen3-0.6b,qwen3-8b]
+
+A shared prompt prefix (section 2i).  Per model: 64 requests through 32 slots that all begin with the same N-token prefix, suffixes of
+1 to 64 tokens, 32 new tokens each.  Best of 3 calls each behind a warm-up call: (j) q3_generate_many_greedy on the full prompts;
+(k) q3_generate_many_dense(dense_min 64) on the full prompts, the stronger baseline; (l) q3_generate_many_prefix on the suffixes
+with the prefix resident; the rows must be equal.  Also: q3_batch_prefix_set on its own; the copy of the N prefix rows from slot 0 to
+the 31 other slots through q3_batch_copy_rows (one launch of k_kv_rows_bcast, the loop's broadcast but for one destination) with
+its achieved bytes per second (read once + written 31 times), next to a loop of 2 * layers * 31 hipMemcpyAsync calls that move the
+same bytes between buffers of the same layout.  Appends a section to <out>/serve_cols.md and writes <out>/serve_cols_prefix.json.
 """
 import argparse
 import json
@@ -54,6 +64,7 @@ AB_MARK = "## Batch-32 decode A/B"
 DENSE_MARK = "## Dense blocks over the slots"
 SAMPLED_MARK = "## Under the sampler"
 STOP_MARK = "## Stop tokens in the device loop"
+PREFIX_MARK = "## Shared prompt prefix"
 
 
 def median(xs):
@@ -347,6 +358,138 @@ def main_stop(a):
     return 0 if ok else 1
 
 
+def memcpy_loop_seconds(n_layers, row_floats, n_rows, ctx, n_dst, reps=3):
+    """the yardstick of the broadcast: 2 * n_layers * n_dst hipMemcpyAsync calls, device to device, that move the rows of every layer of
+    both caches from one block to n_dst blocks laid out like slots of `ctx` rows; best of `reps` behind a warm-up round"""
+    import ctypes as C
+    try:
+        hip = C.CDLL("libamdhip64.so")
+    except OSError:
+        hip = C.CDLL("/opt/rocm/lib/libamdhip64.so")
+    hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
+    hip.hipMemcpyAsync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+    hip.hipMemset.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
+    hip.hipFree.argtypes = [C.c_void_p]
+    layer = 4 * ctx * row_floats                                       # bytes between two layers of a slot's cache
+    slot = n_layers * layer
+    run = 4 * n_rows * row_floats
+    bufs = []
+    for _ in range(2):                                                 # key and value: n_dst + 1 slots each
+        ptr = C.c_void_p()
+        if hip.hipMalloc(C.byref(ptr), (n_dst + 1) * slot) != 0:
+            raise RuntimeError("hipMalloc failed")
+        hip.hipMemset(ptr, 1, (n_dst + 1) * slot)
+        bufs.append(ptr.value)
+    best = None
+    for rep in range(reps + 1):
+        hip.hipDeviceSynchronize()
+        t0 = time.perf_counter()
+        for base in bufs:
+            for l in range(n_layers):
+                for d in range(1, n_dst + 1):
+                    if hip.hipMemcpyAsync(base + d * slot + l * layer, base + l * layer, run, 3, None) != 0:      # hipMemcpyDeviceToDevice
+                        raise RuntimeError("hipMemcpyAsync failed")
+        if hip.hipDeviceSynchronize() != 0:
+            raise RuntimeError("hipDeviceSynchronize failed")
+        dt = time.perf_counter() - t0
+        if rep > 0:
+            best = dt if best is None else min(best, dt)
+    for b in bufs:
+        hip.hipFree(b)
+    return best
+
+
+def worker_prefix(name, ctx, ckpt_dir, seed, n_prefix):
+    import numpy as np
+    import qwen3_rs_amd as q3
+    ck = q3.checkpoint
+    shape = ck.SHAPES[name]
+    path = os.path.join(ckpt_dir, f"{name}-seed{seed}.q3bin")
+    ck.ensure_synthetic_checkpoint(path, shape, seed=seed)
+    rng = np.random.default_rng(7)
+    n_req, ms, n_gen = 64, 32, 32
+    pre = ck.iter_prompt_tokens(shape, seed + 40, n_prefix)
+    suf = [ck.iter_prompt_tokens(shape, seed + 50 + r, int(n)) for r, n in enumerate(rng.integers(1, 65, n_req))]
+    full = [pre + s for s in suf]
+    nnew = [n_gen] * n_req
+
+    def best(call, n=3):
+        call()                                                         # plans, scratch
+        dts = []
+        for _ in range(n):
+            t0 = time.perf_counter()
+            out = call()
+            dts.append(time.perf_counter() - t0)
+        return min(dts), out
+    with q3.TransformerBuilder(path).with_ctx_length(ctx).build() as t:
+        t.batch_init(ms, ctx)
+        dt_cols, (rows_cols, st_cols) = best(lambda: t.generate_many_greedy(full, nnew))
+        dt_dense, (rows_dense, st_dense, ds_dense) = best(lambda: t.generate_many_dense(full, nnew, None, 64))
+        dt_set, _ = best(lambda: t.batch_prefix_set(pre))
+        dt_pre, (rows_pre, st_pre) = best(lambda: t.generate_many_prefix(suf, nnew))
+        n_dst = ms - 1
+        dt_bcast, _ = best(lambda: t.batch_copy_rows(0, list(range(1, ms)), 0, n_prefix), 5)
+    moved = 2 * shape.n_layers * n_prefix * shape.kv_dim * 4 * (1 + n_dst)                 # read once, written n_dst times
+    dt_memcpy = memcpy_loop_seconds(shape.n_layers, shape.kv_dim, n_prefix, ctx, n_dst)
+    res = {"model": name, "ctx": ctx, "prefix": n_prefix, "requests": n_req, "slots": ms, "n_new": n_gen,
+           "rows_equal": rows_cols == rows_dense == rows_pre,
+           "columns": {"passes": st_cols.passes, "blocks": 0, "seconds": dt_cols},
+           "dense": {"passes": st_dense.passes, "blocks": ds_dense.blocks, "seconds": dt_dense},
+           "prefix_loop": {"passes": st_pre.passes, "blocks": 0, "seconds": dt_pre},
+           "prefix_set_seconds": dt_set,
+           "bcast": {"n_dst": n_dst, "bytes": moved, "seconds": dt_bcast, "bytes_per_s": moved / dt_bcast},
+           "memcpy_loop": {"calls": 2 * shape.n_layers * n_dst, "bytes": 2 * moved * n_dst // (1 + n_dst), "seconds": dt_memcpy,
+                           "bytes_per_s": (2 * moved * n_dst // (1 + n_dst)) / dt_memcpy}}
+    print("RESULT " + json.dumps(res))
+
+
+def main_prefix(a):
+    results = []
+    for name in a.models.split(","):
+        cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--worker", name, "--ctx", str(a.ctx),
+               "--ckpt-dir", a.ckpt_dir, "--seed", str(a.seed), "--prefix", str(a.prefix)]
+        p = subprocess.run(cmd, capture_output=True, text=True)
+        sys.stderr.write(p.stderr[-2000:])
+        if p.returncode != 0:
+            print(f"[bench_serve] {name}: exit status {p.returncode}; stopping here", file=sys.stderr)
+            break
+        results.append(json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")][-1][7:]))
+    os.makedirs(a.out, exist_ok=True)
+    with open(os.path.join(a.out, "serve_cols_prefix.json"), "w") as f:
+        json.dump(results, f, indent=1)
+    lines = [PREFIX_MARK + f" (prefix of {a.prefix} tokens)", "",
+             "Written by `tools/bench_serve.py --prefix` (context %d per slot): 64 requests through 32 slots that all begin with the same" % a.ctx,
+             "prefix, suffixes of 1 to 64 tokens, 32 new tokens each.  Wall time per call, best of 3 behind a warm-up call.  columns =",
+             "`q3_generate_many_greedy` on the full prompts; dense = `q3_generate_many_dense` (dense_min 64) on the full prompts; prefix =",
+             "`q3_generate_many_prefix` on the suffixes with the prefix resident (its broadcast into the 32 slots included); prefix_set =",
+             "`q3_batch_prefix_set` on its own, paid once per prefix.", "",
+             "| model | loop | passes | blocks | seconds | against dense | rows equal |", "|---|---|---|---|---|---|---|"]
+    for r in results:
+        for k, label in (("columns", "columns"), ("dense", "dense"), ("prefix_loop", "prefix")):
+            lines.append(f"| {r['model']} | {label} | {r[k]['passes']} | {r[k]['blocks']} | {r[k]['seconds']:.3f} | "
+                         f"{r['dense']['seconds'] / r[k]['seconds']:.2f}x | {r['rows_equal']} |")
+        lines.append(f"| {r['model']} | prefix_set | | | {r['prefix_set_seconds']:.3f} | | |")
+    lines += ["", "The copy of the prefix rows from slot 0 to the 31 other slots: one launch of `k_kv_rows_bcast` through `q3_batch_copy_rows` (wall time",
+              "of the call, its synchronisation included, best of 5; bytes = read once + written 31 times) next to a loop of",
+              "2 x layers x 31 `hipMemcpyAsync` calls between buffers of the same layout (bytes = read 31 times + written 31 times; best of 3):", "",
+              "| model | path | calls | MB moved | ms | GB/s |", "|---|---|---|---|---|---|"]
+    for r in results:
+        b, m = r["bcast"], r["memcpy_loop"]
+        lines.append(f"| {r['model']} | k_kv_rows_bcast | 1 | {b['bytes'] / 1e6:.0f} | {1e3 * b['seconds']:.3f} | {b['bytes_per_s'] / 1e9:.0f} |")
+        lines.append(f"| {r['model']} | hipMemcpyAsync loop | {m['calls']} | {m['bytes'] / 1e6:.0f} | {1e3 * m['seconds']:.3f} | {m['bytes_per_s'] / 1e9:.0f} |")
+    if not results:
+        lines.append("not taken")
+    md_path = os.path.join(a.out, "serve_cols.md")
+    old = open(md_path).read() if os.path.exists(md_path) else ""
+    if PREFIX_MARK in old:                                             # replace the earlier section, up to the next heading of its level
+        at = old.index(PREFIX_MARK)
+        nxt = old.find("\n## ", at + 1)
+        old = old[:at].rstrip("\n") + "\n" + (old[nxt:] if nxt >= 0 else "")
+    with open(md_path, "w") as f:
+        f.write(old.rstrip("\n") + "\n\n" + "\n".join(lines) + "\n")
+    return 0 if len(results) == len(a.models.split(",")) and all(r["rows_equal"] for r in results) else 1
+
+
 def main_dense(a):
     results = []
     for name in a.models.split(","):
@@ -439,7 +582,14 @@ def main():
     ap.add_argument("--topp", type=float, default=0.95)
     ap.add_argument("--dense-min", type=int, help="long prompts through dense blocks against the column loop (appends to serve_cols.md; context 2,304)")
     ap.add_argument("--stop", action="store_true", help="stop tokens in the device loop against the loop at the cap (appends to serve_cols.md)")
+    ap.add_argument("--prefix", type=int, help="requests that share a prefix of this many tokens against the loops on the full prompts (appends to serve_cols.md)")
     a = ap.parse_args()
+    if a.prefix is not None:
+        a.ctx = max(a.ctx, (a.prefix + 64 + 32 + 255) // 256 * 256)
+        if a.worker:
+            worker_prefix(a.worker, a.ctx, a.ckpt_dir, a.seed, a.prefix)
+            return 0
+        return main_prefix(a)
     if a.stop:
         if a.worker:
             worker_stop(a.worker, a.ctx, a.ckpt_dir, a.seed)
@@ -476,7 +626,7 @@ def main():
     keep = ""
     if os.path.exists(md_path):
         old = open(md_path).read()
-        marks = [old.index(m) for m in (AB_MARK, SAMPLED_MARK, DENSE_MARK, STOP_MARK) if m in old]      # sections other runs wrote
+        marks = [old.index(m) for m in (AB_MARK, SAMPLED_MARK, DENSE_MARK, STOP_MARK, PREFIX_MARK) if m in old]      # sections other runs wrote
         if marks:
             keep = old[min(marks):]
     lines = ["# Ragged column passes: pass cost and request throughput", "",
