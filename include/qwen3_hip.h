@@ -412,7 +412,9 @@ typedef struct q3_cols_stats { uint64_t passes, live_columns, prompt_columns, de
  * (A prompt-phase slot at the front always gets a column: it holds a slot itself, so at most 31 slots decode beside it.)
  * table (may be NULL: count only): one entry {pass, slot, position, request} per column, passes ascending, columns in pass
  * order; *n_entries = the number of columns whether or not they fit; stats as for the loop.  n_entries, stats may be NULL.
- * Q3_ERR_ARG: no request, a prompt_len or n_new of 0, max_streams outside 1 .. 32, a table smaller than the schedule. */
+ * Q3_ERR_ARG: no request, a prompt_len or n_new of 0, max_streams outside 1 .. 32, a table smaller than the schedule; a prompt_len
+ * or n_new above INT32_MAX, or lengths whose running sum is (the table is int32_t, and so are the scheduler's records: refused at
+ * once, as q3_cols_schedule_stop and the loops refuse them). */
 int q3_cols_schedule(const size_t* prompt_len, const size_t* n_new, size_t n_requests, int max_streams,
                      int32_t* table /* [cap][4]: pass, slot, pos, request */, size_t cap, size_t* n_entries, q3_cols_stats* stats);
 

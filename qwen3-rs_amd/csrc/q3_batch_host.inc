@@ -873,8 +873,7 @@ int q3_generate_greedy_batch(q3_engine* e, const int32_t* first_tokens, const in
 int q3_batch_sampler_set(q3_engine* e, float temperature, float topp, const uint64_t* rng_seeds) {
     g_err[0] = 0;
     if (!e || !e->batch || !e->batch->has_kv) return fail(Q3_ERR_ARG, "q3_batch_init has not been called");
-    if (!(temperature >= 0.0f)) return fail(Q3_ERR_ARG, "Temperature must be non-negative");
-    if (!(topp >= 0.0f && topp <= 1.0f)) return fail(Q3_ERR_ARG, "Top-p must be between 0.0 and 1.0");
+    if (int rc = sampler_check(temperature, topp)) return rc;
     if (!rng_seeds && temperature != 0.0f) return fail(Q3_ERR_ARG, "null seeds");
     BatchCtx* b = e->batch;
     HIP_TRY(hipSetDevice(e->device));

@@ -3,8 +3,8 @@
 //
 // A pass is up to 32 columns of (slot, token, position) over the per-stream KV caches of the batched state: decode columns of some
 // slots next to runs of consecutive prompt positions of others, one pass over the packed weights (PlanKind::Cols).  The loop
-// q3_generate_many_greedy walks a pass table that is a pure function of the request lengths (cols_schedule_run): the host
-// knows every pass's width in advance, the device resolves every pass's tokens itself (k_cols_turn).
+// q3_generate_many_greedy walks a pass table that is a pure function of the request lengths (cols_sched_step of q3_stop.h, stepped
+// here on the host): the host knows every pass's width in advance, the device resolves every pass's tokens itself (k_cols_turn).
 // Section 2f is the same under the sampler: a second set of plans whose classifier is followed by the per-column draws and
 // k_cols_turn_draw (q3_sampler.h), the greedy plans and their launches untouched.
 
@@ -13,62 +13,138 @@ namespace {
 // q3_prefix_host.inc: one launch on the stream that copies the resident prefix into rows 0 .. P - 1 of slots 0 .. n_slots - 1
 int prefix_bcast_slots(q3_engine* e, int n_slots);
 
-// The schedule of q3_generate_many_greedy (stated in the header): emit(pass, slot, pos, request) for every column, in column order.
-template <class Emit>
-void cols_schedule_run(const size_t* prompt_len, const size_t* n_new, size_t n_requests, int max_streams, Emit&& emit, q3_cols_stats& st) {
-    struct Slot { long req = -1; size_t fed = 0, g = 0; };
-    Slot s[kColsMax];
-    size_t next = 0, active = 0;
-    st = q3_cols_stats{0, 0, 0, 0};
-    while (next < n_requests || active > 0) {
-        // 1. admit: the next request, in ascending index, takes the lowest free slot
-        for (int i = 0; i < max_streams && next < n_requests; ++i)
-            if (s[i].req < 0) {
-                s[i] = Slot{(long)next++, 0, 0};
-                ++active;
-            }
-        int cols = 0, took[kColsMax] = {0};
-        bool dec[kColsMax] = {false};
-        // 2. one column per decode-phase slot
-        for (int i = 0; i < max_streams; ++i)
-            if (s[i].req >= 0 && s[i].fed == prompt_len[s[i].req]) {
-                emit(st.passes, i, s[i].fed + s[i].g - 1, (size_t)s[i].req);
-                dec[i] = true;
-                ++cols;
-                ++st.decode_columns;
-            }
-        // 3. prompt-phase slots share what is left of the pass
-        for (int i = 0; i < max_streams && cols < kColsMax; ++i)
-            if (s[i].req >= 0 && !dec[i]) {
-                const size_t left = prompt_len[s[i].req] - s[i].fed;
-                took[i] = (int)std::min<size_t>(left, (size_t)(kColsMax - cols));
-                for (int k = 0; k < took[i]; ++k) emit(st.passes, i, s[i].fed + k, (size_t)s[i].req);
-                cols += took[i];
-                st.prompt_columns += took[i];
-            }
-        // 4. / 5. phase changes and finished requests
-        for (int i = 0; i < max_streams; ++i) {
-            if (s[i].req < 0) continue;
-            if (dec[i]) ++s[i].g;
-            else if (took[i]) {
-                s[i].fed += took[i];
-                if (s[i].fed == prompt_len[s[i].req]) s[i].g = 1;      // the run's last column emitted y_0
-            }
-            if (s[i].g == n_new[s[i].req]) {
-                s[i].req = -1;
-                --active;
-            }
-        }
-        st.live_columns += cols;
-        ++st.passes;
-    }
-}
-
 int cols_schedule_check(const size_t* prompt_len, const size_t* n_new, size_t n_requests, int max_streams) {
     if (!prompt_len || !n_new || n_requests == 0) return fail(Q3_ERR_ARG, "null or empty request list");
     if (max_streams < 1 || max_streams > kMaxStreams) return fail(Q3_ERR_ARG, "max_streams %d out of range (1..%d)", max_streams, kMaxStreams);
     for (size_t r = 0; r < n_requests; ++r)
         if (prompt_len[r] == 0 || n_new[r] == 0) return fail(Q3_ERR_ARG, "request %zu: empty prompt or n_new 0", r);
+    return Q3_OK;
+}
+
+// The checked requests of a call: the per-request records of the scheduler (q3_stop.h keeps them as int) and, for the loops, the
+// arrays they index.  draw: the three sampler arrays, all given.
+struct ColsRequests {
+    std::vector<int> p_off, prompt_len, n_new, o_off;
+    size_t n_prompt = 0, n_out = 0;
+    const int32_t* prompts = nullptr;
+    size_t pos_base = 0;
+    const float *temperature = nullptr, *topp = nullptr;
+    const uint64_t* seeds = nullptr;
+    size_t size() const { return prompt_len.size(); }
+    bool draw() const { return temperature != nullptr; }
+};
+
+// the lengths alone: what q3_cols_schedule and q3_cols_schedule_stop check
+int cols_requests_lengths(const size_t* prompt_len, const size_t* n_new, size_t n_requests, int max_streams, ColsRequests& rq) {
+    int rc;
+    if ((rc = cols_schedule_check(prompt_len, n_new, n_requests, max_streams))) return rc;
+    rq.p_off.resize(n_requests);
+    rq.prompt_len.resize(n_requests);
+    rq.n_new.resize(n_requests);
+    rq.o_off.resize(n_requests);
+    for (size_t r = 0; r < n_requests; ++r) {
+        if (prompt_len[r] > (size_t)INT32_MAX || n_new[r] > (size_t)INT32_MAX || rq.n_prompt + prompt_len[r] > (size_t)INT32_MAX ||
+            rq.n_out + n_new[r] > (size_t)INT32_MAX)
+            return fail(Q3_ERR_ARG, "more than 2^31 tokens in one call");
+        rq.p_off[r] = (int)rq.n_prompt;
+        rq.o_off[r] = (int)rq.n_out;
+        rq.prompt_len[r] = (int)prompt_len[r];
+        rq.n_new[r] = (int)n_new[r];
+        rq.n_prompt += prompt_len[r];
+        rq.n_out += n_new[r];
+    }
+    return Q3_OK;
+}
+
+// everything the five q3_generate_many_* entry points refuse about their requests (cols_prepare has run).  draw: the call is a
+// sampled one, which needs all three sampler arrays.  pos_base: the rows in front of every prompt (section 2i)
+int cols_requests_check(q3_engine* e, const int32_t* prompts, const size_t* prompt_len, const size_t* n_new, size_t n_requests, bool draw,
+                        const float* temperature, const float* topp, const uint64_t* seeds, size_t pos_base, const int32_t* out_tokens, ColsRequests& rq) {
+    int rc;
+    const BatchCtx* b = e->batch;
+    if (!prompts || !out_tokens || (draw && (!temperature || !topp || !seeds))) return fail(Q3_ERR_ARG, "null argument");
+    if ((rc = cols_requests_lengths(prompt_len, n_new, n_requests, b->max_streams, rq))) return rc;
+    for (size_t r = 0; r < n_requests; ++r)
+        if (pos_base + prompt_len[r] + n_new[r] - 1 > (size_t)b->ctx)
+            return fail(Q3_ERR_ARG, "request %zu: prompt of %zu + %zu new tokens exceeds seq_len %d", r, pos_base + prompt_len[r], n_new[r], b->ctx);
+    for (size_t i = 0; i < rq.n_prompt; ++i)
+        if (prompts[i] < 0 || prompts[i] >= e->cfg.vocab_size)
+            return fail(Q3_ERR_ARG, "index out of range: token %d (vocab_size %d)", prompts[i], e->cfg.vocab_size);
+    if (n_requests > (size_t)INT32_MAX / 5) return fail(Q3_ERR_ARG, "more than 2^31 / 5 requests in one call");
+    for (size_t r = 0; draw && r < n_requests; ++r)
+        if ((rc = sampler_check(temperature[r], topp[r], (long)r))) return rc;
+    rq.prompts = prompts;
+    rq.pos_base = pos_base;
+    rq.temperature = temperature;
+    rq.topp = topp;
+    rq.seeds = seeds;
+    return Q3_OK;
+}
+
+// a scheduler state over the records of rq, nothing admitted yet.  n_out: per request, written when the request ends
+void cols_sched_init(ColsSched& s, int max_streams, const ColsRequests& rq, const int32_t* stop_tokens, size_t n_stop, int* n_out) {
+    memset(&s, 0, sizeof(ColsSched));
+    for (int i = 0; i < kColsMax; ++i) s.slot[i] = SchedSlot{-1, 0, 0, 0, 0, 0, 0, 0};
+    s.max_streams = max_streams;
+    s.n_requests = (int)rq.size();
+    s.n_stop = (int)n_stop;
+    for (size_t k = 0; k < n_stop; ++k) s.stop[k] = stop_tokens[k];
+    s.pos_base = (int)rq.pos_base;
+    s.p_off = rq.p_off.data();
+    s.prompt_len = rq.prompt_len.data();
+    s.n_new = rq.n_new.data();
+    s.o_off = rq.o_off.data();
+    s.n_out = n_out;
+}
+
+// The schedule on the host: cols_sched_step (q3_stop.h) pass after pass until no request is queued or held.  on_pass(pass, row,
+// aux, slot_last) sees every pass as the step wrote it and may set slot_last[i], the token slot i produced in it (zero unless set:
+// with an empty stop list no value of it is looked at).  Every pass advances at least one column of a request that has
+// prompt_len + n_new - 1 of them at the most: a scheduler that asks for more passes than that is wrong
+template <class OnPass>
+int cols_sched_walk(ColsSched& s, const ColsRequests& rq, OnPass&& on_pass) {
+    const size_t pass_cap = rq.n_prompt + rq.n_out;
+    ColEnt row[kColsMax];
+    ColAux aux[kColsMax];
+    int slot_last[kColsMax] = {0};
+    for (size_t pass = 0;; ++pass) {
+        cols_sched_step(s, slot_last, row, aux);
+        if (s.status.done) return Q3_OK;
+        if (s.status.n_live < 1) return fail(Q3_ERR_INTERNAL, "the scheduler laid out a pass of %d columns", s.status.n_live);
+        if (pass >= pass_cap) return fail(Q3_ERR_INTERNAL, "the scheduler asks for more than %zu passes", pass_cap);
+        on_pass(pass, row, aux, slot_last);
+    }
+}
+
+// q3_cols_schedule (rows == nullptr, no stop list) and q3_cols_schedule_stop: the table of the walk above
+int cols_schedule_table(const size_t* prompt_len, const size_t* n_new, size_t n_requests, int max_streams, const int32_t* rows,
+                        const int32_t* stop_tokens, size_t n_stop, int32_t* table, size_t cap, size_t* n_entries, size_t* n_out, q3_cols_stats* stats) {
+    int rc;
+    ColsRequests rq;
+    if ((rc = cols_requests_lengths(prompt_len, n_new, n_requests, max_streams, rq))) return rc;
+    std::vector<int> got(n_requests, 0);
+    ColsSched s;
+    cols_sched_init(s, max_streams, rq, stop_tokens, n_stop, got.data());
+    size_t n = 0;
+    if ((rc = cols_sched_walk(s, rq, [&](size_t pass, const ColEnt* row, const ColAux*, int* slot_last) {
+            for (int j = 0; j < s.status.n_live; ++j) {
+                const ColEnt& c = row[j];
+                if (table && n < cap) {
+                    table[4 * n + 0] = (int32_t)pass;
+                    table[4 * n + 1] = c.slot;
+                    table[4 * n + 2] = c.pos;
+                    table[4 * n + 3] = s.slot[c.slot].req;
+                }
+                ++n;
+                if (rows && c.out >= 0) slot_last[c.slot] = rows[c.out];       // what the turn kernel commits: the token this column produces
+            }
+        })))
+        return rc;
+    if (n_entries) *n_entries = n;
+    if (n_out)
+        for (size_t r = 0; r < n_requests; ++r) n_out[r] = (size_t)got[r];
+    if (stats) *stats = s.stats;
+    if (table && n > cap) return fail(Q3_ERR_ARG, "the schedule has %zu entries, the table holds %zu", n, cap);
     return Q3_OK;
 }
 
@@ -147,6 +223,39 @@ int cols_draw_alloc(q3_engine* e) {
     return Q3_OK;
 }
 
+// The sampler side of a loop's passes, on the stream: the per-request parameters (temperature null: none, no request is loaded from
+// them) and the control block of k_cols_turn_draw over the per-slot states slot_ss and the ColAux table aux.
+int cols_sampler_upload(q3_engine* e, SamplerState* slot_ss, const ColAux* aux, const float* temperature, const float* topp, const uint64_t* seeds,
+                        size_t n_requests) {
+    int rc;
+    BatchCtx* b = e->batch;
+    if (temperature) {
+        if ((rc = cols_grow(b->cols_temp, b->cols_temp_cap, n_requests))) return rc;
+        if ((rc = cols_grow(b->cols_topp, b->cols_topp_cap, n_requests))) return rc;
+        if ((rc = cols_grow(b->cols_seeds, b->cols_seeds_cap, n_requests))) return rc;
+        HIP_TRY(hipMemcpyAsync(b->cols_temp, temperature, 4 * n_requests, hipMemcpyHostToDevice, e->stream));
+        HIP_TRY(hipMemcpyAsync(b->cols_topp, topp, 4 * n_requests, hipMemcpyHostToDevice, e->stream));
+        HIP_TRY(hipMemcpyAsync(b->cols_seeds, seeds, 8 * n_requests, hipMemcpyHostToDevice, e->stream));
+    }
+    ColsDraw& dr = b->h_cols_draw->dr;
+    memset(&dr, 0, sizeof(ColsDraw));
+    dr.slot_ss = slot_ss;
+    dr.aux = aux;
+    dr.temperature = b->cols_temp;
+    dr.topp = b->cols_topp;
+    dr.seeds = b->cols_seeds;
+    HIP_TRY(hipMemcpyAsync(b->cols_draw, &dr, sizeof(ColsDraw), hipMemcpyHostToDevice, e->stream));
+    return Q3_OK;
+}
+
+// The launch that sets up the pass at the table's cursor with nothing to commit: pass 0 of a table, or the one pass of a table
+// of one row.  Every later pass of a table is set up by the turn kernel that ends the pass before it.
+int cols_turn_setup(q3_engine* e, bool draw) {
+    BatchCtx* b = e->batch;
+    if (draw) return launch_now(e->stream, k_cols_turn_draw, dim3(1), dim3(kWG), 0, b->cols_ctl, b->cols_draw, b->spec_samp, b->st, b->col_slot);
+    return launch_now(e->stream, k_cols_turn, dim3(1), dim3(kWG), 0, b->cols_ctl, b->slots, b->nslots, 0, b->st, b->col_slot);
+}
+
 // One host-made pass.  draw = false: the states and the slot table are written here and the greedy plan commits the argmaxes.
 // draw = true: the pass goes through a one-pass table, set up by a k_cols_turn_draw launch in front of the sampled plan -- the
 // column sampler states derive from the slot states in device memory (the batch sampler's d_sampler: slot i = stream i).
@@ -199,7 +308,7 @@ int cols_step(q3_engine* e, const int32_t* slots, const int32_t* tokens, const i
         HIP_TRY(hipMemcpyAsync(b->cols_ctl, &h->ctl, sizeof(ColsCtl), hipMemcpyHostToDevice, e->stream));
         HIP_TRY(hipMemcpyAsync(b->cols_draw, &hd->dr, sizeof(ColsDraw), hipMemcpyHostToDevice, e->stream));
         HIP_TRY(hipMemcpyAsync(b->cols_step, &hd->step, sizeof(ColsStep), hipMemcpyHostToDevice, e->stream));
-        if ((rc = launch_now(e->stream, k_cols_turn_draw, dim3(1), dim3(kWG), 0, b->cols_ctl, b->cols_draw, b->spec_samp, b->st, b->col_slot))) return rc;
+        if ((rc = cols_turn_setup(e, true))) return rc;
     } else {
         h->ctl.n_live = n_cols;
         for (int j = 0; j < kColsMax; ++j) {
@@ -300,22 +409,7 @@ int cols_job_run(q3_engine* e, ColsJob& job, bool draw, const ColsJobSampler& sm
     if (draw && n_passes) {
         if ((rc = cols_grow(b->cols_aux, b->cols_aux_cap, n_passes * kColsMax))) return rc;
         HIP_TRY(hipMemcpyAsync(b->cols_aux, job.aux.data(), sizeof(ColAux) * n_passes * kColsMax, hipMemcpyHostToDevice, e->stream));
-        if (smp.temperature) {
-            if ((rc = cols_grow(b->cols_temp, b->cols_temp_cap, smp.n_requests))) return rc;
-            if ((rc = cols_grow(b->cols_topp, b->cols_topp_cap, smp.n_requests))) return rc;
-            if ((rc = cols_grow(b->cols_seeds, b->cols_seeds_cap, smp.n_requests))) return rc;
-            HIP_TRY(hipMemcpyAsync(b->cols_temp, smp.temperature, 4 * smp.n_requests, hipMemcpyHostToDevice, e->stream));
-            HIP_TRY(hipMemcpyAsync(b->cols_topp, smp.topp, 4 * smp.n_requests, hipMemcpyHostToDevice, e->stream));
-            HIP_TRY(hipMemcpyAsync(b->cols_seeds, smp.seeds, 8 * smp.n_requests, hipMemcpyHostToDevice, e->stream));
-        }
-        ColsDraw& dr = b->h_cols_draw->dr;
-        memset(&dr, 0, sizeof(ColsDraw));
-        dr.slot_ss = smp.slot_ss;
-        dr.aux = b->cols_aux;
-        dr.temperature = b->cols_temp;
-        dr.topp = b->cols_topp;
-        dr.seeds = b->cols_seeds;
-        HIP_TRY(hipMemcpyAsync(b->cols_draw, &dr, sizeof(ColsDraw), hipMemcpyHostToDevice, e->stream));
+        if ((rc = cols_sampler_upload(e, smp.slot_ss, b->cols_aux, smp.temperature, smp.topp, smp.seeds, smp.n_requests))) return rc;
     }
     // the coins of the wide blocks first: a turn kernel reads a slot's rng when it sets a pass up, one pass ahead of the stream, so
     // a skip enqueued next to its block would be overwritten by the commit of a pass of the same slot set up before it.  One
@@ -333,10 +427,7 @@ int cols_job_run(q3_engine* e, ColsJob& job, bool draw, const ColsJobSampler& sm
         h->ctl.prompts = b->cols_prompts;
         h->ctl.out_tokens = b->cols_out;
         HIP_TRY(hipMemcpyAsync(b->cols_ctl, &h->ctl, sizeof(ColsCtl), hipMemcpyHostToDevice, e->stream));
-        // pass 0 is set up by a launch of its own (nothing to commit); every later pass by the k_cols_turn that ends the pass before it
-        if (draw) {
-            if ((rc = launch_now(e->stream, k_cols_turn_draw, dim3(1), dim3(kWG), 0, b->cols_ctl, b->cols_draw, b->spec_samp, b->st, b->col_slot))) return rc;
-        } else if ((rc = launch_now(e->stream, k_cols_turn, dim3(1), dim3(kWG), 0, b->cols_ctl, b->slots, b->nslots, 0, b->st, b->col_slot))) return rc;
+        if ((rc = cols_turn_setup(e, draw))) return rc;
     }
     size_t p = 0;
     for (size_t i = 0; i < job.steps.size(); ++i) {
@@ -408,91 +499,74 @@ void dense_job_add(q3_engine* e, ColsJob& job, const std::vector<DenseIn>& in, b
     }
 }
 
-// The device-resident loop of q3_generate_many_greedy (temperature == nullptr) and q3_generate_many_sampled: the same schedule and
-// table; under the sampler a parallel table of ColAux, the per-request sampler parameters and the sampled plans.
+// The device-resident loop of q3_generate_many_greedy and (rq.draw) q3_generate_many_sampled: the table is the schedule's rows,
+// stepped on the host before the first launch; under the sampler the ColAux rows next to it, the per-request sampler parameters
+// and the sampled plans.
 // dense_min > 0 (q3_generate_many_dense): a request with prompt_len - 1 >= dense_min enters the schedule with a prompt of one
 // column, its last prompt token; the tokens in front of it go through dense blocks enqueued in front of the pass that holds it.
-// pos_base > 0 (q3_generate_many_prefix, dense_min 0): the prompts are suffixes behind the resident prefix of pos_base tokens, which
-// is copied into the slots in front of the first pass; every position of the table moves up by pos_base, nothing else changes.
-int cols_generate(q3_engine* e, const int32_t* prompts, const size_t* prompt_len, const size_t* n_new, size_t n_requests, const float* temperature,
-                  const float* topp, const uint64_t* seeds, int32_t* out_tokens, q3_cols_stats* stats, size_t dense_min = 0,
-                  q3_dense_stats* dstats = nullptr, size_t pos_base = 0) {
+// rq.pos_base > 0 (q3_generate_many_prefix, dense_min 0): the prompts are suffixes behind the resident prefix of pos_base tokens,
+// which is copied into the slots in front of the first pass; the scheduler moves every position up by pos_base.
+int cols_generate(q3_engine* e, const ColsRequests& rq, int32_t* out_tokens, q3_cols_stats* stats, size_t dense_min = 0, q3_dense_stats* dstats = nullptr) {
     int rc;
-    const bool draw = temperature != nullptr;
+    const bool draw = rq.draw();
     BatchCtx* b = e->batch;
-    if (!prompts || !out_tokens) return fail(Q3_ERR_ARG, "null argument");
-    if ((rc = cols_schedule_check(prompt_len, n_new, n_requests, b->max_streams))) return rc;
-    std::vector<size_t> p_off(n_requests), o_off(n_requests), eff_len(n_requests);
-    std::vector<char> dense(n_requests, 0);
-    size_t n_prompt = 0, n_out = 0;
-    for (size_t r = 0; r < n_requests; ++r) {
-        if (pos_base + prompt_len[r] + n_new[r] - 1 > (size_t)b->ctx)
-            return fail(Q3_ERR_ARG, "request %zu: prompt of %zu + %zu new tokens exceeds seq_len %d", r, pos_base + prompt_len[r], n_new[r], b->ctx);
-        p_off[r] = n_prompt;
-        o_off[r] = n_out;
-        n_prompt += prompt_len[r];
-        n_out += n_new[r];
-        dense[r] = dense_min > 0 && prompt_len[r] - 1 >= dense_min;
-        eff_len[r] = dense[r] ? 1 : prompt_len[r];
-    }
-    for (size_t i = 0; i < n_prompt; ++i)
-        if (prompts[i] < 0 || prompts[i] >= e->cfg.vocab_size)
-            return fail(Q3_ERR_ARG, "index out of range: token %d (vocab_size %d)", prompts[i], e->cfg.vocab_size);
-    if (n_prompt > (size_t)INT32_MAX || n_out > (size_t)INT32_MAX) return fail(Q3_ERR_ARG, "more than 2^31 tokens in one call");
-
-    // the schedule's columns, pass by pass (positions in the schedule's terms: a dense request's prompt is one column)
-    struct Col { uint64_t pass; int slot; size_t pos, req; };
-    std::vector<Col> sched;
-    q3_cols_stats st;
-    cols_schedule_run(eff_len.data(), n_new, n_requests, b->max_streams, [&](uint64_t pass, int slot, size_t pos, size_t req) {
-        sched.push_back(Col{pass, slot, pos, req});
-    }, st);
-    // the pass table: kColsMax entries per pass.  In front of a pass, the blocks of the dense requests whose column it holds
+    const size_t n_requests = rq.size();
+    // what the scheduler sees of a dense request; shift: the positions its blocks take, which the step function does not know of
+    ColsRequests seen = rq;
+    std::vector<int> shift(n_requests, 0);
+    for (size_t r = 0; r < n_requests; ++r)
+        if (dense_min > 0 && (size_t)rq.prompt_len[r] - 1 >= dense_min) {
+            shift[r] = rq.prompt_len[r] - 1;
+            seen.p_off[r] += shift[r];
+            seen.prompt_len[r] = 1;
+        }
+    std::vector<int> got(n_requests, 0);
+    ColsSched s;
+    cols_sched_init(s, b->max_streams, seen, nullptr, 0, got.data());
     ColsJob job;
-    if (pos_base) job.bcast_slots = (int)std::min<size_t>(n_requests, (size_t)b->max_streams);
+    if (rq.pos_base) job.bcast_slots = (int)std::min<size_t>(n_requests, (size_t)b->max_streams);
     q3_dense_stats dst{0, 0, 0};
     std::vector<char> loaded(n_requests, 0);
     std::vector<size_t> wide_coins(n_requests, 0);
-    for (size_t i0 = 0; i0 < sched.size();) {
-        size_t i1 = i0;
-        while (i1 < sched.size() && sched[i1].pass == sched[i0].pass) ++i1;
-        std::vector<DenseIn> in;
-        std::vector<size_t> in_req;
-        for (size_t i = i0; i < i1; ++i)
-            if (dense[sched[i].req] && sched[i].pos == 0) in_req.push_back(sched[i].req);
-        std::sort(in_req.begin(), in_req.end());             // admission order
-        for (size_t r : in_req) {
-            int slot = -1;
-            for (size_t i = i0; i < i1; ++i)
-                if (sched[i].req == r && sched[i].pos == 0) slot = sched[i].slot;
-            in.push_back(DenseIn{slot, 0, (int)p_off[r], prompt_len[r] - 1});
-        }
-        if (!in.empty()) dense_job_add(e, job, in, draw, in_req.data(), draw ? &loaded : nullptr, draw ? &wide_coins : nullptr, dst);
-        const size_t p = job.add_pass(draw);
-        for (size_t i = i0; i < i1; ++i) {
-            const Col& s = sched[i];
-            const size_t shift = dense[s.req] ? prompt_len[s.req] - 1 : 0, el = eff_len[s.req];
-            ColEnt c;
-            c.slot = s.slot;
-            c.pos = (int)(s.pos + shift + pos_base);
-            c.src = s.pos < el ? (int)(p_off[s.req] + s.pos + shift) : -1;
-            c.out = s.pos + 1 >= el ? (int)(o_off[s.req] + (s.pos + 1 - el)) : -1;
-            const size_t at = p * kColsMax + job.ncols[p]++;
-            job.table[at] = c;
-            if (draw) {          // a request enters at position 0; the run's earlier column is the entry in front (one run per slot)
-                const bool in_run = job.ncols[p] > 1 && job.table[at - 1].slot == s.slot;
-                // a dense request's column stands wide_coins coins into its rng: the discarded samples of the positions its blocks took
-                const int k = in_run ? job.aux[at - 1].k + 1 : (int)(dense[s.req] && s.pos == 0 ? wide_coins[s.req] : 0);
-                job.aux[at] = ColAux{s.pos == 0 && !loaded[s.req] ? (int)s.req : -1, k, c.out >= 0 ? 1 : 0, 1};
-                if (in_run) job.aux[at - 1].last = 0;
+    if ((rc = cols_sched_walk(s, seen, [&](size_t, const ColEnt* row, const ColAux* aux, int*) {
+            const int n_live = s.status.n_live;
+            const auto req_of = [&](const ColEnt& c) { return (size_t)s.slot[c.slot].req; };
+            // in front of the pass, the blocks of the dense requests it admits (their one prompt column: src >= 0), in admission order
+            std::vector<std::pair<size_t, int>> enter;
+            for (int j = 0; j < n_live; ++j)
+                if (shift[req_of(row[j])] && row[j].src >= 0) enter.emplace_back(req_of(row[j]), row[j].slot);
+            if (!enter.empty()) {
+                std::sort(enter.begin(), enter.end());
+                std::vector<DenseIn> in;
+                std::vector<size_t> in_req;
+                for (const auto& en : enter) {
+                    in_req.push_back(en.first);
+                    in.push_back(DenseIn{en.second, 0, rq.p_off[en.first], (size_t)shift[en.first]});
+                }
+                dense_job_add(e, job, in, draw, in_req.data(), draw ? &loaded : nullptr, draw ? &wide_coins : nullptr, dst);
             }
-        }
-        i0 = i1;
-    }
+            // the pass as the step wrote it (cols_job_run makes the pads), but for what a dense request's blocks have done
+            const size_t p = job.add_pass(draw);
+            job.ncols[p] = n_live;
+            for (int j = 0; j < n_live; ++j) {
+                const size_t at = p * kColsMax + j, r = req_of(row[j]);
+                job.table[at] = row[j];
+                job.table[at].pos += shift[r];
+                if (!draw) continue;
+                job.aux[at] = aux[j];
+                if (shift[r] && row[j].src >= 0) {
+                    // the column stands wide_coins coins into its rng (the discarded samples of the positions its wide blocks took),
+                    // and a narrow block may have loaded the request's sampler already
+                    job.aux[at].k = (int)wide_coins[r];
+                    if (loaded[r]) job.aux[at].req = -1;
+                }
+            }
+        })))
+        return rc;
     if (draw && (rc = cols_draw_alloc(e))) return rc;        // the loop's per-slot sampler states are allocated there
-    const ColsJobSampler smp{b->cols_slot_samp, temperature, topp, seeds, n_requests, false};
-    if ((rc = cols_job_run(e, job, draw, smp, prompts, n_prompt, out_tokens, n_out))) return rc;
-    if (stats) *stats = st;
+    const ColsJobSampler smp{b->cols_slot_samp, rq.temperature, rq.topp, rq.seeds, n_requests, false};
+    if ((rc = cols_job_run(e, job, draw, smp, rq.prompts, rq.n_prompt, out_tokens, rq.n_out))) return rc;
+    if (stats) *stats = s.stats;
     if (dstats) *dstats = dst;
     return Q3_OK;
 }
@@ -520,23 +594,7 @@ int q3_batch_step_cols_draw(q3_engine* e, const int32_t* slots, const int32_t* t
 int q3_cols_schedule(const size_t* prompt_len, const size_t* n_new, size_t n_requests, int max_streams, int32_t* table, size_t cap,
                      size_t* n_entries, q3_cols_stats* stats) {
     g_err[0] = 0;
-    int rc;
-    if ((rc = cols_schedule_check(prompt_len, n_new, n_requests, max_streams))) return rc;
-    size_t n = 0;
-    q3_cols_stats st;
-    cols_schedule_run(prompt_len, n_new, n_requests, max_streams, [&](uint64_t pass, int slot, size_t pos, size_t req) {
-        if (table && n < cap) {
-            table[4 * n + 0] = (int32_t)pass;
-            table[4 * n + 1] = slot;
-            table[4 * n + 2] = (int32_t)pos;
-            table[4 * n + 3] = (int32_t)req;
-        }
-        ++n;
-    }, st);
-    if (n_entries) *n_entries = n;
-    if (stats) *stats = st;
-    if (table && n > cap) return fail(Q3_ERR_ARG, "the schedule has %zu entries, the table holds %zu", n, cap);
-    return Q3_OK;
+    return cols_schedule_table(prompt_len, n_new, n_requests, max_streams, nullptr, nullptr, 0, table, cap, n_entries, nullptr, stats);
 }
 
 int q3_generate_many_greedy(q3_engine* e, const int32_t* prompts, const size_t* prompt_len, const size_t* n_new, size_t n_requests,
@@ -544,8 +602,10 @@ int q3_generate_many_greedy(q3_engine* e, const int32_t* prompts, const size_t* 
     g_err[0] = 0;
     if (stats) *stats = q3_cols_stats{0, 0, 0, 0};
     int rc;
+    ColsRequests rq;
     if ((rc = cols_prepare(e, "q3_generate_many_greedy"))) return rc;
-    return cols_generate(e, prompts, prompt_len, n_new, n_requests, nullptr, nullptr, nullptr, out_tokens, stats);
+    if ((rc = cols_requests_check(e, prompts, prompt_len, n_new, n_requests, false, nullptr, nullptr, nullptr, 0, out_tokens, rq))) return rc;
+    return cols_generate(e, rq, out_tokens, stats);
 }
 
 int q3_generate_many_sampled(q3_engine* e, const int32_t* prompts, const size_t* prompt_len, const size_t* n_new, size_t n_requests,
@@ -553,14 +613,10 @@ int q3_generate_many_sampled(q3_engine* e, const int32_t* prompts, const size_t*
     g_err[0] = 0;
     if (stats) *stats = q3_cols_stats{0, 0, 0, 0};
     int rc;
+    ColsRequests rq;
     if ((rc = cols_prepare(e, "q3_generate_many_sampled", true))) return rc;
-    if (!temperature || !topp || !seeds) return fail(Q3_ERR_ARG, "null argument");
-    if (!prompt_len || !n_new || n_requests == 0) return fail(Q3_ERR_ARG, "null or empty request list");
-    for (size_t r = 0; r < n_requests; ++r) {
-        if (!(temperature[r] >= 0.0f)) return fail(Q3_ERR_ARG, "request %zu: Temperature must be non-negative", r);
-        if (!(topp[r] >= 0.0f && topp[r] <= 1.0f)) return fail(Q3_ERR_ARG, "request %zu: Top-p must be between 0.0 and 1.0", r);
-    }
-    return cols_generate(e, prompts, prompt_len, n_new, n_requests, temperature, topp, seeds, out_tokens, stats);
+    if ((rc = cols_requests_check(e, prompts, prompt_len, n_new, n_requests, true, temperature, topp, seeds, 0, out_tokens, rq))) return rc;
+    return cols_generate(e, rq, out_tokens, stats);
 }
 
 /* ---- section 2g: dense blocks over the slots ---- */
@@ -605,20 +661,12 @@ int q3_generate_many_dense(q3_engine* e, const int32_t* prompts, const size_t* p
     g_err[0] = 0;
     if (stats) *stats = q3_cols_stats{0, 0, 0, 0};
     if (dstats) *dstats = q3_dense_stats{0, 0, 0};
-    if (!temperature && !topp && !seeds) {
-        int rc;
-        if ((rc = cols_prepare(e, "q3_generate_many_dense"))) return rc;
-        return cols_generate(e, prompts, prompt_len, n_new, n_requests, nullptr, nullptr, nullptr, out_tokens, stats, dense_min, dstats);
-    }
     int rc;
-    if ((rc = cols_prepare(e, "q3_generate_many_dense", true))) return rc;
-    if (!temperature || !topp || !seeds) return fail(Q3_ERR_ARG, "null argument");
-    if (!prompt_len || !n_new || n_requests == 0) return fail(Q3_ERR_ARG, "null or empty request list");
-    for (size_t r = 0; r < n_requests; ++r) {
-        if (!(temperature[r] >= 0.0f)) return fail(Q3_ERR_ARG, "request %zu: Temperature must be non-negative", r);
-        if (!(topp[r] >= 0.0f && topp[r] <= 1.0f)) return fail(Q3_ERR_ARG, "request %zu: Top-p must be between 0.0 and 1.0", r);
-    }
-    return cols_generate(e, prompts, prompt_len, n_new, n_requests, temperature, topp, seeds, out_tokens, stats, dense_min, dstats);
+    ColsRequests rq;
+    const bool draw = temperature || topp || seeds;
+    if ((rc = cols_prepare(e, "q3_generate_many_dense", draw))) return rc;
+    if ((rc = cols_requests_check(e, prompts, prompt_len, n_new, n_requests, draw, temperature, topp, seeds, 0, out_tokens, rq))) return rc;
+    return cols_generate(e, rq, out_tokens, stats, dense_min, dstats);
 }
 
 }  // extern "C"

@@ -61,6 +61,15 @@ int fail(int code, const char* fmt, ...) {
             return fail(Q3_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
     } while (0)
 
+// Sampler::new's refusals (sampler.rs:32-33), for every entry point that takes sampler parameters.  req >= 0: they are request req's
+int sampler_check(float temperature, float topp, long req = -1) {
+    const bool bad_t = !(temperature >= 0.0f), bad_p = !(topp >= 0.0f && topp <= 1.0f);
+    if (!bad_t && !bad_p) return Q3_OK;
+    char who[40] = "";
+    if (req >= 0) snprintf(who, sizeof who, "request %ld: ", req);
+    return bad_t ? fail(Q3_ERR_ARG, "%sTemperature must be non-negative", who) : fail(Q3_ERR_ARG, "%sTop-p must be between 0.0 and 1.0", who);
+}
+
 constexpr int32_t kMagic = 0x616a6331;   // configuration.rs:8
 constexpr int32_t kVersion = 1;          // configuration.rs:10
 constexpr size_t kHeaderSize = 256;      // configuration.rs:12
@@ -1164,8 +1173,7 @@ int q3_prefill(q3_engine* e, const int32_t* tokens, size_t n_tokens, size_t firs
 int q3_sampler_set(q3_engine* e, float temperature, float topp, uint64_t rng_seed) {
     g_err[0] = 0;
     if (!e) return fail(Q3_ERR_ARG, "null engine");
-    if (!(temperature >= 0.0f)) return fail(Q3_ERR_ARG, "Temperature must be non-negative");            // sampler.rs:32
-    if (!(topp >= 0.0f && topp <= 1.0f)) return fail(Q3_ERR_ARG, "Top-p must be between 0.0 and 1.0");  // sampler.rs:33
+    if (int rc = sampler_check(temperature, topp)) return rc;
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(hipStreamSynchronize(e->stream));
     const int n = e->cfg.vocab_size;
@@ -1829,7 +1837,7 @@ int q3_op_sample(const float* logits, size_t n, float temperature, float topp, u
     if (rc) return rc;
     if (!logits || !rng_state || !index || n == 0) return fail(Q3_ERR_ARG, "null argument");
     if (!(temperature > 0.0f)) return fail(Q3_ERR_ARG, "temperature must be positive (0 is q3_op_argmax)");
-    if (!(topp >= 0.0f && topp <= 1.0f)) return fail(Q3_ERR_ARG, "Top-p must be between 0.0 and 1.0");
+    if ((rc = sampler_check(temperature, topp))) return rc;
     const int blen = 4 * (((int)n + 4095) / 4096);
     size_t n2 = 1;
     while (n2 < n) n2 <<= 1;

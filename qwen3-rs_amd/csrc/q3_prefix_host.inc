@@ -3,7 +3,7 @@
 //
 // A prefix that many requests share is prefilled once (q3_batch_prefix_set), kept in a store beside the per-stream caches, and copied
 // into rows 0 .. P - 1 of the slots a loop call can use by ONE launch of k_kv_rows_bcast (q3_prefix.h) in front of its first pass.
-// The loops are the kept ones with every position moved up by P (cols_generate / cols_generate_stop, pos_base): the attention
+// The loops are the kept ones with every position moved up by P (cols_generate / cols_generate_stop, ColsRequests::pos_base): the attention
 // kernels read the copied rows as they read any other row of the slot.
 
 namespace {
@@ -167,31 +167,26 @@ int q3_generate_many_prefix(q3_engine* e, const int32_t* prompts, const size_t* 
     g_err[0] = 0;
     if (stats) *stats = q3_cols_stats{0, 0, 0, 0};
     int rc;
+    ColsRequests rq;
     const bool draw = temperature || topp || seeds;
     if ((rc = cols_prepare(e, "q3_generate_many_prefix", draw))) return rc;
     const size_t P = e->batch->prefix_n;
     if (P == 0) return fail(Q3_ERR_ARG, "no prefix is resident: call q3_batch_prefix_set first");
     if (!n_out) return fail(Q3_ERR_ARG, "null argument");
     if ((rc = stop_list_check(stop_tokens, n_stop))) return rc;
+    if ((rc = cols_requests_check(e, prompts, prompt_len, n_new, n_requests, draw, temperature, topp, seeds, P, out_tokens, rq))) return rc;
+    // the prompt loop draws and discards one sample per prompt position (section 2f): a sampled request enters its first column
+    // with its seed state P coins on.  A greedy request draws no coin
     std::vector<uint64_t> seeds_p;
     if (draw) {
-        if (!temperature || !topp || !seeds) return fail(Q3_ERR_ARG, "null argument");
-        if (!prompt_len || !n_new || n_requests == 0) return fail(Q3_ERR_ARG, "null or empty request list");
-        for (size_t r = 0; r < n_requests; ++r) {
-            if (!(temperature[r] >= 0.0f)) return fail(Q3_ERR_ARG, "request %zu: Temperature must be non-negative", r);
-            if (!(topp[r] >= 0.0f && topp[r] <= 1.0f)) return fail(Q3_ERR_ARG, "request %zu: Top-p must be between 0.0 and 1.0", r);
-        }
-        // the prompt loop draws and discards one sample per prompt position (section 2f): a sampled request enters its first column
-        // with its seed state P coins on.  A greedy request draws no coin
         seeds_p.assign(seeds, seeds + n_requests);
         for (size_t r = 0; r < n_requests; ++r)
             if (temperature[r] > 0.0f) seeds_p[r] = rng_skip(seeds[r], P);
-        seeds = seeds_p.data();
+        rq.seeds = seeds_p.data();
     }
-    if (n_stop > 0)
-        return cols_generate_stop(e, prompts, prompt_len, n_new, n_requests, temperature, topp, seeds, stop_tokens, n_stop, out_tokens, n_out, stats, P);
+    if (n_stop > 0) return cols_generate_stop(e, rq, stop_tokens, n_stop, out_tokens, n_out, stats);
     // no stop token: the tabled, device-resident loop of sections 2e / 2f
-    if ((rc = cols_generate(e, prompts, prompt_len, n_new, n_requests, temperature, topp, seeds, out_tokens, stats, 0, nullptr, P))) return rc;
+    if ((rc = cols_generate(e, rq, out_tokens, stats))) return rc;
     for (size_t r = 0; r < n_requests; ++r) n_out[r] = n_new[r];
     return Q3_OK;
 }

@@ -1,10 +1,13 @@
-// q3_stop.h -- stop tokens in the loop over column passes (include/qwen3_hip.h section 2h).
+// q3_stop.h -- the scheduler of every loop over column passes (include/qwen3_hip.h sections 2e to 2i), and the device side of the
+// stop-token loop (section 2h).
 //
-// The loops of sections 2e / 2f walk a pass table the host made from (prompt_len, n_new).  A request that ends at a stop token is a
-// request whose n_new is not known in advance, so here the table is made one pass at a time, behind the pass whose tokens decide
-// it: cols_sched_step applies the header's five rules to a state that lives next to the table, once per pass.  The same function
-// runs in k_cols_sched on the device (one thread, between two passes) and in q3_cols_schedule_stop on the host, which is how the
-// CPU tests reach it.
+// cols_sched_step is the one statement of the header's five rules: it applies them to a state that lives next to the table, once
+// per pass, and writes the pass as one row of the table.  Where every request's n_new is known in advance (sections 2e / 2f / 2g
+// and section 2i without stop tokens) the host steps it with an empty stop list before the first launch and uploads the rows as
+// one table (cols_generate); q3_cols_schedule and q3_cols_schedule_stop step it on the host too, which is how the CPU tests reach
+// it.  A request that ends at a stop token is a request whose n_new is not known in advance, so there the table is made one pass
+// at a time, behind the pass whose tokens decide it: the same function runs in k_cols_sched on the device (one thread, between
+// two passes).
 #pragma once
 
 namespace q3 {
@@ -37,8 +40,8 @@ struct ColsSched {
 
 // One step: rules 4 and 5 for the pass just committed (slot_last[i] = the token slot i produced in it), then rules 1 to 3 for the
 // next pass, written as one row of kColsMax entries -- pads as cols_job_run makes them -- and, where aux is not null, the
-// ColAux row of the sampled plans as cols_generate forms it.  No arrays of its own: the per-slot record of the pass in flight
-// is SchedSlot::took.
+// ColAux row of the sampled plans.  With n_stop == 0 the values of slot_last decide nothing.  No arrays of its own: the per-slot
+// record of the pass in flight is SchedSlot::took.
 __host__ __device__ inline void cols_sched_step(ColsSched& s, const int* slot_last, ColEnt* row, ColAux* aux) {
     const int ms = s.max_streams;
     // 4. a run that reached its prompt's last token produced y_0; 5. a request ends at n_new tokens or at a stop token

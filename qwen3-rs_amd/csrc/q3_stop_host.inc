@@ -8,67 +8,24 @@
 
 namespace {
 
-// the per-request records of the scheduler, as the device holds them
-struct StopRequests {
-    std::vector<int> p_off, prompt_len, n_new, o_off;
-    size_t n_prompt = 0, n_out = 0;
-};
-
-int stop_requests(const size_t* prompt_len, const size_t* n_new, size_t n_requests, StopRequests& rq) {
-    rq.p_off.resize(n_requests);
-    rq.prompt_len.resize(n_requests);
-    rq.n_new.resize(n_requests);
-    rq.o_off.resize(n_requests);
-    for (size_t r = 0; r < n_requests; ++r) {
-        if (prompt_len[r] > (size_t)INT32_MAX || n_new[r] > (size_t)INT32_MAX || rq.n_prompt + prompt_len[r] > (size_t)INT32_MAX ||
-            rq.n_out + n_new[r] > (size_t)INT32_MAX)
-            return fail(Q3_ERR_ARG, "more than 2^31 tokens in one call");
-        rq.p_off[r] = (int)rq.n_prompt;
-        rq.o_off[r] = (int)rq.n_out;
-        rq.prompt_len[r] = (int)prompt_len[r];
-        rq.n_new[r] = (int)n_new[r];
-        rq.n_prompt += prompt_len[r];
-        rq.n_out += n_new[r];
-    }
-    return Q3_OK;
-}
-
 int stop_list_check(const int32_t* stop_tokens, size_t n_stop) {
     if (n_stop > (size_t)Q3_STOP_MAX) return fail(Q3_ERR_ARG, "%zu stop tokens, at most %d", n_stop, Q3_STOP_MAX);
     if (n_stop > 0 && !stop_tokens) return fail(Q3_ERR_ARG, "null stop_tokens with n_stop %zu", n_stop);
     return Q3_OK;
 }
 
-void stop_sched_init(ColsSched& s, int max_streams, size_t n_requests, const int32_t* stop_tokens, size_t n_stop) {
-    memset(&s, 0, sizeof(ColsSched));
-    for (int i = 0; i < kColsMax; ++i) s.slot[i] = SchedSlot{-1, 0, 0, 0, 0, 0, 0, 0};
-    s.max_streams = max_streams;
-    s.n_requests = (int)n_requests;
-    s.n_stop = (int)n_stop;
-    for (size_t k = 0; k < n_stop; ++k) s.stop[k] = stop_tokens[k];
-}
-
-int cols_generate_stop(q3_engine* e, const int32_t* prompts, const size_t* prompt_len, const size_t* n_new, size_t n_requests,
-                       const float* temperature, const float* topp, const uint64_t* seeds, const int32_t* stop_tokens, size_t n_stop,
-                       int32_t* out_tokens, size_t* n_out, q3_cols_stats* stats, size_t pos_base = 0) {
+// rq: checked by cols_requests_check, with the prefix in front of the prompts as its pos_base
+int cols_generate_stop(q3_engine* e, const ColsRequests& rq, const int32_t* stop_tokens, size_t n_stop, int32_t* out_tokens, size_t* n_out,
+                       q3_cols_stats* stats) {
     int rc;
-    const bool draw = temperature != nullptr;
+    const bool draw = rq.draw();
+    const size_t n_requests = rq.size();
     BatchCtx* b = e->batch;
-    if (!prompts || !out_tokens || !n_out) return fail(Q3_ERR_ARG, "null argument");
+    if (!n_out) return fail(Q3_ERR_ARG, "null argument");
     if ((rc = stop_list_check(stop_tokens, n_stop))) return rc;
     for (size_t k = 0; k < n_stop; ++k)
         if (stop_tokens[k] < 0 || stop_tokens[k] >= e->cfg.vocab_size)
             return fail(Q3_ERR_ARG, "index out of range: stop token %d (vocab_size %d)", stop_tokens[k], e->cfg.vocab_size);
-    if ((rc = cols_schedule_check(prompt_len, n_new, n_requests, b->max_streams))) return rc;
-    for (size_t r = 0; r < n_requests; ++r)
-        if (pos_base + prompt_len[r] + n_new[r] - 1 > (size_t)b->ctx)
-            return fail(Q3_ERR_ARG, "request %zu: prompt of %zu + %zu new tokens exceeds seq_len %d", r, pos_base + prompt_len[r], n_new[r], b->ctx);
-    StopRequests rq;
-    if ((rc = stop_requests(prompt_len, n_new, n_requests, rq))) return rc;
-    for (size_t i = 0; i < rq.n_prompt; ++i)
-        if (prompts[i] < 0 || prompts[i] >= e->cfg.vocab_size)
-            return fail(Q3_ERR_ARG, "index out of range: token %d (vocab_size %d)", prompts[i], e->cfg.vocab_size);
-    if (n_requests > (size_t)INT32_MAX / 5) return fail(Q3_ERR_ARG, "more than 2^31 / 5 requests in one call");
 
     if (draw && (rc = cols_draw_alloc(e))) return rc;
     HIP_TRY(hipSetDevice(e->device));
@@ -81,7 +38,7 @@ int cols_generate_stop(q3_engine* e, const int32_t* prompts, const size_t* promp
 
     // uploaded once: the prompts, the per-request records, the sampler parameters, the scheduler state with the stop list
     int* dreq = b->cols_req;
-    HIP_TRY(hipMemcpyAsync(b->cols_prompts, prompts, 4 * rq.n_prompt, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(b->cols_prompts, rq.prompts, 4 * rq.n_prompt, hipMemcpyHostToDevice, e->stream));
     HIP_TRY(hipMemcpyAsync(dreq + 0 * n_requests, rq.p_off.data(), 4 * n_requests, hipMemcpyHostToDevice, e->stream));
     HIP_TRY(hipMemcpyAsync(dreq + 1 * n_requests, rq.prompt_len.data(), 4 * n_requests, hipMemcpyHostToDevice, e->stream));
     HIP_TRY(hipMemcpyAsync(dreq + 2 * n_requests, rq.n_new.data(), 4 * n_requests, hipMemcpyHostToDevice, e->stream));
@@ -90,31 +47,14 @@ int cols_generate_stop(q3_engine* e, const int32_t* prompts, const size_t* promp
     HIP_TRY(hipMemsetAsync(b->cols_out, 0xFF, 4 * rq.n_out, e->stream));          // -1 behind every request's last token
     ColsStopDev* d = b->cols_stop;
     ColsSched sched;
-    stop_sched_init(sched, b->max_streams, n_requests, stop_tokens, n_stop);
-    sched.pos_base = (int)pos_base;
-    sched.p_off = dreq;
+    cols_sched_init(sched, b->max_streams, rq, stop_tokens, n_stop, dreq + 4 * n_requests);
+    sched.p_off = dreq;                                    // the records as the device holds them
     sched.prompt_len = dreq + n_requests;
     sched.n_new = dreq + 2 * n_requests;
     sched.o_off = dreq + 3 * n_requests;
-    sched.n_out = dreq + 4 * n_requests;
     HIP_TRY(hipMemsetAsync(d, 0, sizeof(ColsStopDev), e->stream));
     HIP_TRY(hipMemcpyAsync(&d->sched, &sched, sizeof(ColsSched), hipMemcpyHostToDevice, e->stream));
-    if (draw) {
-        if ((rc = cols_grow(b->cols_temp, b->cols_temp_cap, n_requests))) return rc;
-        if ((rc = cols_grow(b->cols_topp, b->cols_topp_cap, n_requests))) return rc;
-        if ((rc = cols_grow(b->cols_seeds, b->cols_seeds_cap, n_requests))) return rc;
-        HIP_TRY(hipMemcpyAsync(b->cols_temp, temperature, 4 * n_requests, hipMemcpyHostToDevice, e->stream));
-        HIP_TRY(hipMemcpyAsync(b->cols_topp, topp, 4 * n_requests, hipMemcpyHostToDevice, e->stream));
-        HIP_TRY(hipMemcpyAsync(b->cols_seeds, seeds, 8 * n_requests, hipMemcpyHostToDevice, e->stream));
-        ColsDraw& dr = b->h_cols_draw->dr;
-        memset(&dr, 0, sizeof(ColsDraw));
-        dr.slot_ss = b->cols_slot_samp;
-        dr.aux = d->aux;
-        dr.temperature = b->cols_temp;
-        dr.topp = b->cols_topp;
-        dr.seeds = b->cols_seeds;
-        HIP_TRY(hipMemcpyAsync(b->cols_draw, &dr, sizeof(ColsDraw), hipMemcpyHostToDevice, e->stream));
-    }
+    if (draw && (rc = cols_sampler_upload(e, b->cols_slot_samp, d->aux, rq.temperature, rq.topp, rq.seeds, n_requests))) return rc;
     // the control block of the turn kernels: a table of one row, empty until k_cols_sched fills it
     ColsHost* h = b->h_cols;
     memset(&h->ctl, 0, sizeof(ColsCtl));
@@ -124,20 +64,17 @@ int cols_generate_stop(q3_engine* e, const int32_t* prompts, const size_t* promp
     h->ctl.out_tokens = b->cols_out;
     HIP_TRY(hipMemcpyAsync(b->cols_ctl, &h->ctl, sizeof(ColsCtl), hipMemcpyHostToDevice, e->stream));
     // the shared prefix in front of every request: rows 0 .. pos_base - 1 of the slots the scheduler can use
-    if (pos_base && (rc = prefix_bcast_slots(e, (int)std::min<size_t>(n_requests, (size_t)b->max_streams)))) return rc;
+    if (rq.pos_base && (rc = prefix_bcast_slots(e, (int)std::min<size_t>(n_requests, (size_t)b->max_streams)))) return rc;
 
     // every pass advances at least one column of a request that has prompt_len + n_new - 1 of them at the most: a scheduler that
     // asks for more passes than that is wrong, and the call ends with an error code
-    size_t pass_cap = 0;
-    for (size_t r = 0; r < n_requests; ++r) pass_cap += prompt_len[r] + n_new[r];
+    const size_t pass_cap = rq.n_prompt + rq.n_out;
     SchedStatus* hs = b->h_cols_stop;
     size_t passes = 0;
     for (;;) {
         if ((rc = launch_now(e->stream, k_cols_sched, dim3(1), dim3(64), 0, d, b->cols_ctl, draw ? 1 : 0))) return rc;
         // the pass is set up by a launch of its own, like pass 0 of the kept loops (n_live is 0: nothing to commit)
-        if (draw) {
-            if ((rc = launch_now(e->stream, k_cols_turn_draw, dim3(1), dim3(kWG), 0, b->cols_ctl, b->cols_draw, b->spec_samp, b->st, b->col_slot))) return rc;
-        } else if ((rc = launch_now(e->stream, k_cols_turn, dim3(1), dim3(kWG), 0, b->cols_ctl, b->slots, b->nslots, 0, b->st, b->col_slot))) return rc;
+        if ((rc = cols_turn_setup(e, draw))) return rc;
         HIP_TRY(hipMemcpyAsync(hs, &d->status, sizeof(SchedStatus), hipMemcpyDeviceToHost, e->stream));
         HIP_TRY(hipStreamSynchronize(e->stream));
         if (hs->done) break;
@@ -169,17 +106,11 @@ int q3_generate_many_stop(q3_engine* e, const int32_t* prompts, const size_t* pr
     g_err[0] = 0;
     if (stats) *stats = q3_cols_stats{0, 0, 0, 0};
     int rc;
+    ColsRequests rq;
     const bool draw = temperature || topp || seeds;
     if ((rc = cols_prepare(e, "q3_generate_many_stop", draw))) return rc;
-    if (draw) {
-        if (!temperature || !topp || !seeds) return fail(Q3_ERR_ARG, "null argument");
-        if (!prompt_len || !n_new || n_requests == 0) return fail(Q3_ERR_ARG, "null or empty request list");
-        for (size_t r = 0; r < n_requests; ++r) {
-            if (!(temperature[r] >= 0.0f)) return fail(Q3_ERR_ARG, "request %zu: Temperature must be non-negative", r);
-            if (!(topp[r] >= 0.0f && topp[r] <= 1.0f)) return fail(Q3_ERR_ARG, "request %zu: Top-p must be between 0.0 and 1.0", r);
-        }
-    }
-    return cols_generate_stop(e, prompts, prompt_len, n_new, n_requests, temperature, topp, seeds, stop_tokens, n_stop, out_tokens, n_out, stats);
+    if ((rc = cols_requests_check(e, prompts, prompt_len, n_new, n_requests, draw, temperature, topp, seeds, 0, out_tokens, rq))) return rc;
+    return cols_generate_stop(e, rq, stop_tokens, n_stop, out_tokens, n_out, stats);
 }
 
 int q3_cols_schedule_stop(const size_t* prompt_len, const size_t* n_new, size_t n_requests, int max_streams, const int32_t* rows,
@@ -187,47 +118,9 @@ int q3_cols_schedule_stop(const size_t* prompt_len, const size_t* n_new, size_t 
                           q3_cols_stats* stats) {
     g_err[0] = 0;
     int rc;
-    if ((rc = cols_schedule_check(prompt_len, n_new, n_requests, max_streams))) return rc;
     if (!rows) return fail(Q3_ERR_ARG, "null rows");
     if ((rc = stop_list_check(stop_tokens, n_stop))) return rc;
-    StopRequests rq;
-    if ((rc = stop_requests(prompt_len, n_new, n_requests, rq))) return rc;
-    std::vector<int> got(n_requests, 0);
-    ColsSched s;
-    stop_sched_init(s, max_streams, n_requests, stop_tokens, n_stop);
-    s.p_off = rq.p_off.data();
-    s.prompt_len = rq.prompt_len.data();
-    s.n_new = rq.n_new.data();
-    s.o_off = rq.o_off.data();
-    s.n_out = got.data();
-    size_t pass_cap = 0, n = 0;
-    for (size_t r = 0; r < n_requests; ++r) pass_cap += prompt_len[r] + n_new[r];
-    ColEnt row[kColsMax];
-    ColAux aux[kColsMax];
-    int slot_last[kColsMax] = {0};
-    for (size_t pass = 0;; ++pass) {
-        cols_sched_step(s, slot_last, row, aux);
-        if (s.status.done) break;
-        if (pass >= pass_cap) return fail(Q3_ERR_INTERNAL, "the scheduler asks for more than %zu passes", pass_cap);
-        for (int j = 0; j < s.status.n_live; ++j) {
-            const ColEnt& c = row[j];
-            const int req = s.slot[c.slot].req;
-            if (table && n < cap) {
-                table[4 * n + 0] = (int32_t)pass;
-                table[4 * n + 1] = c.slot;
-                table[4 * n + 2] = c.pos;
-                table[4 * n + 3] = req;
-            }
-            ++n;
-            if (c.out >= 0) slot_last[c.slot] = rows[c.out];       // what the turn kernel commits: the token this column produces
-        }
-    }
-    if (n_entries) *n_entries = n;
-    if (n_out)
-        for (size_t r = 0; r < n_requests; ++r) n_out[r] = (size_t)got[r];
-    if (stats) *stats = s.stats;
-    if (table && n > cap) return fail(Q3_ERR_ARG, "the schedule has %zu entries, the table holds %zu", n, cap);
-    return Q3_OK;
+    return cols_schedule_table(prompt_len, n_new, n_requests, max_streams, rows, stop_tokens, n_stop, table, cap, n_entries, n_out, stats);
 }
 
 }  // extern "C"

@@ -542,19 +542,39 @@ class Transformer:
         (q3_generate_many_greedy): prompts enter in chunks next to the decode columns of other slots, finished requests hand
         their slot to the next one.  prompts: one token list per request; n_new: tokens wanted per request (the first is the
         token behind the prompt).  Returns ([n_new[r] tokens] per request, ColsStats)."""
-        if len(prompts) != len(n_new):
+        return self._generate_many(prompts, n_new, None, lambda rq, smp, out, st: self._batch_rc(self._lib.q3_generate_many_greedy(*rq, out, st)))[:2]
+
+    def _generate_many(self, prompts, n_new, sampler, call):
+        """What every generate_many_* does around its library function.  call(rq, smp, out, st) runs it: rq = (handle, concatenated
+        prompts, prompt lengths, n_new, number of requests), smp = the three per-request sampler arrays made from sampler =
+        (temperature, topp, seeds), one value per request or a scalar each (sampler None: three None), out the output buffer,
+        st the q3_cols_stats.  It returns the function's n_out array, to which the rows are cut, or None: rows of n_new tokens.
+        Returns (rows, ColsStats, the output buffer as the library filled it, tokens per row)."""
+        n = len(prompts)
+        if len(n_new) != n:
             raise ValueError("one n_new per prompt")
+
+        def per_request(v, what, ctype, conv):
+            vals = [v] * n if np.isscalar(v) else list(v)
+            if len(vals) != n:
+                raise ValueError(f"one {what} per request, or a scalar")
+            return (ctype * max(1, n))(*[conv(x) for x in vals])
+        smp = (None, None, None)
+        if sampler is not None:
+            temperature, topp, seeds = sampler
+            smp = (per_request(temperature, "temperature", C.c_float, float), per_request(topp, "topp", C.c_float, float),
+                   per_request(seeds, "seed", C.c_uint64, lambda x: int(x) & 0xFFFFFFFFFFFFFFFF))
         flat = [int(t) for p in prompts for t in p]
         total = sum(int(k) for k in n_new)
         out = (C.c_int32 * max(1, total))()
         st = _ColsStats()
-        self._batch_rc(self._lib.q3_generate_many_greedy(self._h, _i32_array(flat), _size_array([len(p) for p in prompts]), _size_array(n_new),
-                                                         len(prompts), out, C.byref(st)))
-        rows, at = [], 0
-        for k in n_new:
-            rows.append([int(out[at + i]) for i in range(int(k))])
+        n_out = call((self._h, _i32_array(flat), _size_array([len(p) for p in prompts]), _size_array(n_new), n), smp, out, C.byref(st))
+        got = [int(k) for k in n_new] if n_out is None else [int(n_out[r]) for r in range(n)]
+        buf, rows, at = out[:total], [], 0
+        for k, g in zip(n_new, got):
+            rows.append(buf[at:at + g])
             at += int(k)
-        return rows, ColsStats(st.passes, st.live_columns, st.prompt_columns, st.decode_columns)
+        return rows, ColsStats(st.passes, st.live_columns, st.prompt_columns, st.decode_columns), buf, got
 
     # ---- column passes under the sampler (include/qwen3_hip.h section 2f)
     def batch_step_cols_draw(self, slots, tokens, pos, keep=None, want_logits: bool = False):
@@ -578,29 +598,8 @@ class Transformer:
         set_sampler(temperature[r], topp[r], seeds[r]) draws prefill + generate_greedy; temperature 0 makes a request greedy.
         temperature / topp / seeds: one value per request, or a scalar for all.  Returns (rows, ColsStats).  The per-stream
         states of set_batch_sampler are unspecified afterwards: set them again before using them."""
-        n = len(prompts)
-        if len(n_new) != n:
-            raise ValueError("one n_new per prompt")
-
-        def per_request(v, what):
-            vals = [v] * n if np.isscalar(v) else list(v)
-            if len(vals) != n:
-                raise ValueError(f"one {what} per request, or a scalar")
-            return vals
-        tv = (C.c_float * max(1, n))(*[float(v) for v in per_request(temperature, "temperature")])
-        pv = (C.c_float * max(1, n))(*[float(v) for v in per_request(topp, "topp")])
-        sv = (C.c_uint64 * max(1, n))(*[int(v) & 0xFFFFFFFFFFFFFFFF for v in per_request(seeds, "seed")])
-        flat = [int(t) for p in prompts for t in p]
-        total = sum(int(k) for k in n_new)
-        out = (C.c_int32 * max(1, total))()
-        st = _ColsStats()
-        self._batch_rc(self._lib.q3_generate_many_sampled(self._h, _i32_array(flat), _size_array([len(p) for p in prompts]), _size_array(n_new),
-                                                          n, tv, pv, sv, out, C.byref(st)))
-        rows, at = [], 0
-        for k in n_new:
-            rows.append([int(out[at + i]) for i in range(int(k))])
-            at += int(k)
-        return rows, ColsStats(st.passes, st.live_columns, st.prompt_columns, st.decode_columns)
+        return self._generate_many(prompts, n_new, (temperature, topp, seeds),
+                                   lambda rq, smp, out, st: self._batch_rc(self._lib.q3_generate_many_sampled(*rq, *smp, out, st)))[:2]
 
     # ---- dense blocks over the slots (include/qwen3_hip.h section 2g)
     dense_pack = staticmethod(dense_pack)
@@ -623,31 +622,10 @@ class Transformer:
         request or a scalar) with every prompt of more than dense_min tokens entered through dense blocks
         (q3_generate_many_dense): the same rows for any dense_min; 0 runs the column loops unchanged.
         Returns (rows, ColsStats, DenseStats)."""
-        n = len(prompts)
-        if len(n_new) != n:
-            raise ValueError("one n_new per prompt")
-        tv = pv = sv = None
-        if sampler is not None:
-            def per_request(v, what):
-                vals = [v] * n if np.isscalar(v) else list(v)
-                if len(vals) != n:
-                    raise ValueError(f"one {what} per request, or a scalar")
-                return vals
-            temperature, topp, seeds = sampler
-            tv = (C.c_float * max(1, n))(*[float(v) for v in per_request(temperature, "temperature")])
-            pv = (C.c_float * max(1, n))(*[float(v) for v in per_request(topp, "topp")])
-            sv = (C.c_uint64 * max(1, n))(*[int(v) & 0xFFFFFFFFFFFFFFFF for v in per_request(seeds, "seed")])
-        flat = [int(t) for p in prompts for t in p]
-        total = sum(int(k) for k in n_new)
-        out = (C.c_int32 * max(1, total))()
-        st, ds = _ColsStats(), _DenseStats()
-        self._batch_rc(self._lib.q3_generate_many_dense(self._h, _i32_array(flat), _size_array([len(p) for p in prompts]), _size_array(n_new),
-                                                        n, tv, pv, sv, int(dense_min), out, C.byref(st), C.byref(ds)))
-        rows, at = [], 0
-        for k in n_new:
-            rows.append([int(out[at + i]) for i in range(int(k))])
-            at += int(k)
-        return rows, ColsStats(st.passes, st.live_columns, st.prompt_columns, st.decode_columns), DenseStats(ds.blocks, ds.live_columns, ds.pad_columns)
+        ds = _DenseStats()
+        rows, stats = self._generate_many(prompts, n_new, sampler, lambda rq, smp, out, st: self._batch_rc(
+            self._lib.q3_generate_many_dense(*rq, *smp, int(dense_min), out, st, C.byref(ds))))[:2]
+        return rows, stats, DenseStats(ds.blocks, ds.live_columns, ds.pad_columns)
 
     # ---- stop tokens in the device loop (include/qwen3_hip.h section 2h)
     cols_schedule_stop = staticmethod(cols_schedule_stop)
@@ -661,36 +639,12 @@ class Transformer:
         return self._generate_many_stop(self._lib.q3_generate_many_stop, prompts, n_new, stop_tokens, sampler, raw)
 
     def _generate_many_stop(self, fn, prompts, n_new, stop_tokens, sampler, raw):
-        n = len(prompts)
-        if len(n_new) != n:
-            raise ValueError("one n_new per prompt")
-        tv = pv = sv = None
-        if sampler is not None:
-            def per_request(v, what):
-                vals = [v] * n if np.isscalar(v) else list(v)
-                if len(vals) != n:
-                    raise ValueError(f"one {what} per request, or a scalar")
-                return vals
-            temperature, topp, seeds = sampler
-            tv = (C.c_float * max(1, n))(*[float(v) for v in per_request(temperature, "temperature")])
-            pv = (C.c_float * max(1, n))(*[float(v) for v in per_request(topp, "topp")])
-            sv = (C.c_uint64 * max(1, n))(*[int(v) & 0xFFFFFFFFFFFFFFFF for v in per_request(seeds, "seed")])
-        stop = [int(t) for t in stop_tokens]
-        flat = [int(t) for p in prompts for t in p]
-        total = sum(int(k) for k in n_new)
-        out = (C.c_int32 * max(1, total))()
-        n_out = _size_array([0] * n)
-        st = _ColsStats()
-        self._batch_rc(fn(self._h, _i32_array(flat), _size_array([len(p) for p in prompts]), _size_array(n_new),
-                        n, tv, pv, sv, _i32_array(stop), len(stop), out, n_out, C.byref(st)))
-        stats = ColsStats(st.passes, st.live_columns, st.prompt_columns, st.decode_columns)
-        if raw:
-            return [int(out[i]) for i in range(total)], [int(n_out[r]) for r in range(n)], stats
-        rows, at = [], 0
-        for r, k in enumerate(n_new):
-            rows.append([int(out[at + i]) for i in range(int(n_out[r]))])
-            at += int(k)
-        return rows, stats
+        def call(rq, smp, out, st):
+            stop, n_out = [int(t) for t in stop_tokens], _size_array([0] * len(prompts))
+            self._batch_rc(fn(*rq, *smp, _i32_array(stop), len(stop), out, n_out, st))
+            return n_out
+        rows, stats, out, got = self._generate_many(prompts, n_new, sampler, call)
+        return (out, got, stats) if raw else (rows, stats)
 
     # ---- a shared prompt prefix (include/qwen3_hip.h section 2i)
     def batch_copy_rows(self, src_slot: int, dst_slots, first_pos: int, n_rows: int):

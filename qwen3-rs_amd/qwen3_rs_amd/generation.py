@@ -192,25 +192,23 @@ def generate_many(transformer, prompts: Sequence[Sequence[int]], max_new_tokens:
     rows: List[List[int]] = [[] for _ in prompts]
     stats = None
     if live:
+        live_prompts, live_new = [prompts[r] for r in live], [n_new[r] for r in live]
+        per_live = None
         if sampler is not None:
             temperature, topp, seeds = ([v] * len(prompts) if np.isscalar(v) else list(v) for v in sampler)
+            per_live = tuple([v[r] for r in live] for v in (temperature, topp, seeds))
         if prefix:
             if transformer.batch_prefix_get() != prefix:
                 transformer.batch_prefix_set(prefix)
-            per_live = None if sampler is None else tuple([v[r] for r in live] for v in (temperature, topp, seeds))
-            got, stats = transformer.generate_many_prefix([prompts[r] for r in live], [n_new[r] for r in live],
-                                                          sorted(stop) if stop_on_device else (), per_live)
+            got, stats = transformer.generate_many_prefix(live_prompts, live_new, sorted(stop) if stop_on_device else (), per_live)
         elif stop_on_device and stop:
-            per_live = None if sampler is None else tuple([v[r] for r in live] for v in (temperature, topp, seeds))
-            got, stats = transformer.generate_many_stop([prompts[r] for r in live], [n_new[r] for r in live], sorted(stop), per_live)
+            got, stats = transformer.generate_many_stop(live_prompts, live_new, sorted(stop), per_live)
         elif dense_min > 0:
-            per_live = None if sampler is None else tuple([v[r] for r in live] for v in (temperature, topp, seeds))
-            got, stats, _ = transformer.generate_many_dense([prompts[r] for r in live], [n_new[r] for r in live], per_live, dense_min)
+            got, stats, _ = transformer.generate_many_dense(live_prompts, live_new, per_live, dense_min)
         elif sampler is None:
-            got, stats = transformer.generate_many_greedy([prompts[r] for r in live], [n_new[r] for r in live])
+            got, stats = transformer.generate_many_greedy(live_prompts, live_new)
         else:
-            got, stats = transformer.generate_many_sampled([prompts[r] for r in live], [n_new[r] for r in live], [temperature[r] for r in live],
-                                                           [topp[r] for r in live], [seeds[r] for r in live])
+            got, stats = transformer.generate_many_sampled(live_prompts, live_new, *per_live)
         for r, toks in zip(live, got):
             k = next((i for i, t in enumerate(toks) if t in stop), None)
             rows[r] = toks if k is None else toks[:k + 1]

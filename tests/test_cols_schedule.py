@@ -77,5 +77,6 @@ def test_schedule_arguments(q3):
     assert L.q3_cols_schedule(one, one, 0, 1, None, 0, None, None) == -3
     for ms in (0, 33):
         assert L.q3_cols_schedule(one, one, 1, ms, None, 0, None, None) == -3
+    assert L.q3_cols_schedule((sz * 1)(2 ** 31), one, 1, 1, None, 0, None, None) == -3                  # a length past INT32_MAX
     with pytest.raises(q3.Q3Error):
         q3.cols_schedule([3], [0], 2)
