@@ -195,7 +195,11 @@ const char* q3_build_id(void);
 /* Allocate the batched state: an MFMA-ordered copy of the weights, max_streams (1..32) zero-filled KV caches
  * of min(ctx_len, engine seq_len) rows (0 = engine seq_len) and scratch.  Needs group_size 64/128/256 and
  * every matrix height a multiple of 16 (Q3_ERR_UNSUPPORTED otherwise).  Calling it again re-allocates
- * (and clears) the state. */
+ * (and clears) the state.
+ * Group sizes 512 and 1024 are single-stream only: q3_forward, q3_prefill, the greedy / sampled loops and the operator entry
+ * points take them (any power of two in [16, 1024]), while q3_batch_init -- and with it everything of sections 2b to 2i,
+ * q3_prefill_batched and q3_verify included -- answers Q3_ERR_UNSUPPORTED ("batched decode needs group_size 64, 128 or 256 ...")
+ * and leaves the engine usable.  At 128 and 256 every batched block holds at most 32 columns (no dense kernels). */
 int q3_batch_init(q3_engine* e, int max_streams, uint32_t ctx_len);
 
 /* One step: stream i runs forward(tokens[i], pos[i]).  logits_out ([n_streams][vocab_size], host) and

@@ -190,7 +190,7 @@ __global__ __launch_bounds__(kWG) void k_bquant_split(const GemvArgs a, const BQ
             y = (PRO == PRO_NORM) ? norm4(w, f, t) : t;
         }
         if constexpr (N_T > 0) quantize4_to_lds<16>(y, vl, 16, valid, xq, xs);
-        else quantize4_to_lds(y, vl, glanes, valid, xq, xs);
+        else quantize4_to_lds<0, false>(y, vl, glanes, valid, xq, xs);      // G <= 256 here (q3_batch_init): a group is at most one wave
     }
     BQ_STAMP(4);
     __syncthreads();

@@ -210,11 +210,13 @@ __device__ __forceinline__ unsigned total_order_key(float f) {
     return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
 }
 
-// Rust `(v).round() as i8`: half away from zero, saturating, NaN -> 0
+// Rust `(v).round() as i8`: half away from zero, saturating, NaN -> 0.  v_cvt_i32_f32 is that cast (NaN -> 0, saturating; the
+// value is already an integer) and the clamp follows in integers: a float clamp in front of the conversion loses the NaN --
+// fmaxf / fminf return their other operand -- and turned a NaN quotient (an infinite value under an infinite scale) into -128.
 __device__ __forceinline__ int quant_round_i8(float v) {
-    float r = roundf(v);
-    r = fminf(fmaxf(r, -128.0f), 127.0f);
-    return (r != r) ? 0 : (int)r;
+    int i;
+    asm("v_cvt_i32_f32 %0, %1" : "=v"(i) : "v"(roundf(v)));
+    return min(max(i, -128), 127);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -540,12 +542,28 @@ __device__ __forceinline__ float seq_sum_terms(const float* t, int n, const floa
 
 // quantize 4 consecutive values held by this thread; its quantization group spans `glanes` = G/4
 // consecutive threads (tensor.rs:91-119).  Writes the packed int8 dword and (group leader) the scale.
-template <int GL_T = 0>
+// XWAVE = false (run-time lanes only): the caller never sees a group wider than one wave -- k_bquant_split of q3_batch.h,
+// whose state q3_batch_init refuses above group 256 -- and keeps the barrier-free body.
+template <int GL_T = 0, bool XWAVE = true>
 __device__ __forceinline__ void quantize4_to_lds(v4f y, int v_idx, int glanes, bool valid, int8_t* xq, float* xs) {
     float m = fmaxf(fmaxf(fabsf(y.x), fabsf(y.y)), fmaxf(fabsf(y.z), fabsf(y.w)));
     if (!valid) m = 0.0f;
-    if (GL_T > 0) { m = group_max_f32_t<GL_T>(m); glanes = GL_T; }
-    else m = group_max_f32(m, glanes);
+    if constexpr (GL_T > 0) { m = group_max_f32_t<GL_T>(m); glanes = GL_T; }
+    else {
+        m = group_max_f32(m, glanes);
+        if constexpr (XWAVE) if (glanes > 64) {
+            // groups of 512 / 1024 elements span 2 / 4 waves of the 256-thread workgroup: the wave maxima meet in LDS.  Every caller
+            // walks its slots in workgroup-uniform loops (`valid` masks the tail), so all threads reach these barriers together;
+            // the first one keeps a slower wave's reads of the previous slot's maxima ahead of this slot's writes.
+            __shared__ float wave_max[kWG / 64];
+            const int wave = threadIdx.x >> 6, wpg = glanes >> 6, w0 = wave & ~(wpg - 1);
+            __syncthreads();
+            if ((threadIdx.x & 63) == 0) wave_max[wave] = m;
+            __syncthreads();
+            m = wave_max[w0];
+            for (int i = 1; i < wpg; ++i) m = fmaxf(m, wave_max[w0 + i]);
+        }
+    }
     const float scale = m / 127.0f;
     if (valid) {
         int q0 = 0, q1 = 0, q2 = 0, q3 = 0;

@@ -10,6 +10,7 @@ import os
 import numpy as np
 import pytest
 
+import group_cases
 from conftest import assert_biteq, golden_path
 
 pytestmark = pytest.mark.gpu
@@ -28,7 +29,7 @@ def test_extension_is_the_code_that_runs(q3):
     assert "libqwen3_hip.so" in maps
 
 
-@pytest.mark.parametrize("G", [16, 32, 64, 128])
+@pytest.mark.parametrize("G", [16, 32, 64, 128, 256, 512, 1024])
 def test_quantize_bitexact(ops, oracle, G):
     rng = np.random.default_rng(G)
     x = (rng.standard_normal(3072) * 3).astype(np.float32)
@@ -41,7 +42,7 @@ def test_quantize_bitexact(ops, oracle, G):
     assert_biteq(ops.dequantize(qa, sa, G), oracle.dequantize(qb, sb, G), "dequantize")
 
 
-@pytest.mark.parametrize("G", [64, 32])
+@pytest.mark.parametrize("G", [64, 32, 256, 1024])
 def test_quantize_half_integer_quotients_and_extreme_scales(ops, oracle, G):
     """tensor.rs:108-111 `(x / scale).round() as i8` on the inputs where a shortcut would show: every group holds quotients AT and a
     few ulps around k + 0.5 for every k, both signs -- the exact ties that round-half-away and round-half-even disagree on, and
@@ -78,9 +79,26 @@ def test_quantize_half_integer_quotients_and_extreme_scales(ops, oracle, G):
     assert bad.size == 0, f"{bad.size} quantized values differ, first at {bad[:5]}: x={x[bad[:5]]} device={qa[bad[:5]]} oracle={qb[bad[:5]]}"
 
 
+@pytest.mark.parametrize("G", [16, 64, 128, 256, 512, 1024])
+def test_quantize_group_maximum_at_every_thread(ops, oracle, G):
+    """group_cases.max_sweep_vector: group i carries its maximum in float4 slot i, so every thread of a group -- every lane of every
+    wave the group spans (two at 512, four at 1024) -- holds the maximum once; more than 1,024 elements, so threads take several slots"""
+    x = group_cases.max_sweep_vector(G)
+    assert x.size > 1024 and x.size % G == 0
+    qa, sa = ops.quantize(x, G)
+    qb, sb = oracle.quantize(x, G)
+    assert_biteq(sa, sb, "scales")
+    assert_biteq(sa, np.full(x.size // G, np.float32(3.0) / np.float32(127.0), np.float32), "scales: 3 / 127")
+    bad = np.nonzero(qa != qb)[0]
+    assert bad.size == 0, f"{bad.size} quantized values differ, first at {bad[:5]}"
+
+
 @pytest.mark.parametrize("n,d,G", [(64, 40, 16), (1024, 2048, 64), (2048, 1024, 64), (3072, 1024, 64), (2560, 96, 64),
                                    (9728, 24, 64), (12288, 16, 64), (4096, 100, 128), (1024, 333, 32), (128, 1, 64),
-                                   (1024, 151936 // 8, 64)])
+                                   (1024, 151936 // 8, 64),
+                                   # groups of 256 / 512 / 1024: ng = 1, odd counts and multiples of 4
+                                   (256, 40, 256), (3072, 100, 256), (512, 1, 512), (2560, 96, 512), (1024, 333, 1024),
+                                   (3072, 24, 1024), (12288, 16, 1024)])
 def test_matmul_bitexact(ops, oracle, n, d, G):
     """tensor.rs:23-62 incl. ragged row counts, n not a multiple of 1 KiB, every model's inner dims."""
     rng = np.random.default_rng(n + d)

@@ -52,6 +52,9 @@ TABLE = ([(r, n) for r in (QKV, SWIGLU, LOGITS) for n in (1024, 2560, 4096)] + [
          [(QUANT, n) for n in (3072, 9728, 12288, 2048, 4096)])
 # generic path: an unlisted n at group 64, and group sizes 32 / 128 (find_cfg returns nothing for G != 64)
 GENERIC = [(r, 1536, 64) for r in (QKV, SWIGLU, QUANT, LOGITS)] + [(r, 1024, G) for r in (QKV, SWIGLU, QUANT, LOGITS) for G in (32, 128)]
+# group sizes of 4 and more 64-byte steps: a quantization group is a whole wave of float4 slots (256), two waves (512), the whole
+# 256-thread workgroup (1024): the prologue's group maximum crosses waves from 512 on
+GENERIC += [(r, n, G) for n, G in ((1024, 256), (2048, 512), (2048, 1024)) for r in (QKV, SWIGLU, QUANT, LOGITS)]
 HD = 64                        # head_dim of the QKV launches: q rows 256, k / v rows 128 (segments must be whole heads)
 
 
@@ -274,7 +277,7 @@ def test_norm_prologue_tree_counts_every_term_once(ops, oracle, role, n):
 @pytest.mark.parametrize("strict", [True, False], ids=["strict", "fast"])
 @pytest.mark.parametrize("role,n,G", GENERIC, ids=[f"{ROLE_NAMES[r]}-{n}-g{G}" for r, n, G in GENERIC])
 def test_gemv_role_generic_path(ops, oracle, role, n, G, strict):
-    """Shapes without a table entry (an unlisted n; group sizes 32 and 128) take the run-time-n kernels."""
+    """Shapes without a table entry (an unlisted n; group sizes 32, 128, 256, 512 and 1024) take the run-time-n kernels."""
     run_families(ops, oracle, role, n, G, strict, want_table=False)
 
 
