@@ -643,6 +643,57 @@ int q3_generate_many_prefix(q3_engine* e, const int32_t* prompts /* suffixes, co
                             const int32_t* stop_tokens, size_t n_stop, int32_t* out_tokens /* concatenated, n_new[r] each */,
                             size_t* n_out /* [n_requests] */, q3_cols_stats* stats);
 
+/* ------------------------------------------------------------------------------------------------
+ * 2j. (behind 2i so that the earlier sections stay as they were.)  Embeddings: the last-token vectors of many prompts through
+ * dense blocks.  A Qwen3 checkpoint that is an embedding model (the Qwen3-Embedding family: the same architecture, the same Q8
+ * export) never uses the classifier: its output is the hidden state of the last prompt token behind the final RMSNorm,
+ * L2-normalised and possibly cut to a leading sub-vector.  The blocks of section 2g run every layer in full for every column and
+ * launch nothing behind the layers, so when a block ends its scratch x[column][dim] holds the last layer's residual of every
+ * column.  One more kernel (k_embed_rows, csrc/q3_embed.h), one workgroup per prompt that ENDS in the block, computes for that
+ * column, in f32 with no FMA contraction, exactly
+ *     ss  = (((-0.0 + x0*x0) + x1*x1) + ... )       over dim terms
+ *     f   = 1.0f / sqrtf(ss / (float)dim + 1e-6f)
+ *     y_i = w_i * (f * x_i)                          i < dim, w = the final norm's weight          (RMSNorm::forward, layers.rs:109-119)
+ * and with Q3_EMBED_L2, over the FIRST out_dim components only,
+ *     s2  = (((-0.0 + y0*y0) + y1*y1) + ... )       over out_dim terms
+ *     nrm = sqrtf(s2);  d = nrm > 1e-12f ? nrm : 1e-12f     (torch F.normalize's eps; a NaN nrm takes the eps)
+ *     out_i = y_i / d                                IEEE divide, i < out_dim
+ * Without the flag out_i = y_i for i < out_dim.  No classifier runs anywhere in the call: a block of 32 columns or fewer, and
+ * every block of a shape the dense kernels refuse, runs the layer launches of the kept column plan of section 2e and stops in
+ * front of its classifier, its columns set up from a run table as a wide block's are.
+ * ------------------------------------------------------------------------------------------------ */
+#define Q3_EMBED_L2     1u   /* L2-normalise the (possibly truncated) vector */
+#define Q3_EMBED_PREFIX 2u   /* prompts are SUFFIXES behind the resident prefix of section 2i */
+typedef struct q3_embed_stats { uint64_t waves, blocks, live_columns, pad_columns; } q3_embed_stats;
+
+/* out[r][0 .. out_dim) = the vector of request r, whose prompt is prompts[prompt_len[0] + .. + prompt_len[r - 1] ..] -- with
+ * Q3_EMBED_PREFIX the resident prefix of P tokens followed by those tokens.  out_dim 0 means dim.
+ * Standard: row r without Q3_EMBED_L2 and with out_dim = dim is bit-identical to q3_read_state kind 2 after q3_prefill(t[0 .. n - 1))
+ * followed by q3_forward(t[n - 1], n - 1) on a fresh engine of the same context, t the request's n prompt tokens.  It does not
+ * depend on the slot, on the neighbours in the block, on the slot's earlier contents or on the wave.  The other flag and out_dim
+ * apply the arithmetic above to that row.
+ * Schedule, a pure function of the lengths: requests go in index order; with S = max_streams, wave w holds requests
+ * [w S, (w + 1) S); the i-th request of a wave uses slot i from position 0 (with Q3_EMBED_PREFIX from position P); each wave is
+ * packed on its own by the rule of q3_dense_pack with block_cap = Q3_PREFILL_M (32 for a shape the dense kernels refuse), so a
+ * slot has at most one run per block; blocks are enqueued in order, and behind each block one k_embed_rows launch covers the runs
+ * that end in it (a run whose last piece lies in a later block is not named; pad columns never are).  stats (may be NULL): the
+ * number of waves and the sums of the per-wave q3_dense_stats.
+ * Execution: everything is enqueued on the engine's stream -- the uploads of the prompts, the run tables and the gather tables,
+ * with Q3_EMBED_PREFIX one launch that copies the store into rows 0 .. P - 1 of the min(n_requests, S) lowest slots, then the
+ * blocks and their gathers -- followed by ONE device-to-host copy and ONE synchronisation.  (A call that has to enlarge one of
+ * its device buffers waits for the stream before it does.)  The device output rows belong to the batched state: grown on
+ * demand, released with it.  The blocks run in the form q3_batch_prefix_set uses: no slot rng is touched whatever
+ * q3_batch_sampler_set says.  The kept decode, column and dense plans and their graphs are not rebuilt.
+ * Afterwards rows first .. first + len - 1 of the slots used hold the prompts' cache rows, as after q3_batch_prefill_slots, and
+ * no other row has changed.  THE SLOTS ARE OVERWRITTEN FROM SLOT 0 UP: A CALLER WITH LIVE REQUESTS IN THE SLOTS MUST NOT CALL THIS.
+ * Every failing call leaves the engine usable.
+ * Q3_ERR_ARG: a null engine (checked before anything touches the GPU) or null arrays; n_requests == 0; no q3_batch_init; an empty
+ * prompt; a token outside the vocabulary; P + prompt_len[r] > the batch context; out_dim > dim; unknown flag bits;
+ * Q3_EMBED_PREFIX with no resident prefix.
+ * Q3_ERR_UNSUPPORTED: what q3_batch_prefill_slots refuses (a Q3_FLAG_FAST engine, the shapes q3_batch_step_cols refuses). */
+int q3_embed_many(q3_engine* e, const int32_t* prompts /* concatenated */, const size_t* prompt_len, size_t n_requests,
+                  uint32_t flags, size_t out_dim /* 0 = dim */, float* out /* host, [n_requests][out_dim] */, q3_embed_stats* stats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -34,6 +34,7 @@ constexpr int kColsNW = 6;
 struct ColsPlan {
     std::vector<Launch> plan;
     Graph graph;
+    size_t head = 0;             // index of the first launch behind the layers (q3_embed_many launches [0, head) alone)
 };
 struct ColsHost {               // pinned staging of one host-made pass
     ColsCtl ctl;
@@ -134,6 +135,10 @@ struct BatchCtx {
     float* prefix_store = nullptr;
     size_t prefix_n = 0;
     std::vector<int32_t> prefix_tokens;
+    // embeddings (q3_embed_many): the gather tables of a call's blocks and its output rows [n_requests][out_dim], grow-only
+    EmbedRow* embed_rows = nullptr;
+    float* embed_out = nullptr;
+    size_t embed_rows_cap = 0, embed_out_cap = 0;
     // packed-matrix directory
     struct PM { size_t q_off, s_off; int ntiles, ng; };
     std::vector<PM> m_qkv, m_wo, m_w13, m_w2;
@@ -227,7 +232,7 @@ void batch_free(q3_engine* e) {
                      b->spec_samp, b->spec_probs, b->spec_sp, b->spec_keys, b->col_slot, b->cols_ctl, b->cols_table, b->cols_ncols, b->cols_prompts,
                      b->cols_out, b->cols_draw, b->cols_step, b->cols_slot_samp, b->cols_aux, b->cols_temp, b->cols_topp, b->cols_seeds, b->cols_stop, b->cols_req,
                      b->dense.x, b->dense.q, b->dense.qn, b->dense.kraw, b->dense.xb, b->dense.hb, b->dense.xq_p, b->dense.xs_p, b->dense.st,
-                     b->dense.col_slot, b->dense.att_pf, b->dense_runs, b->prefix_store};
+                     b->dense.col_slot, b->dense.att_pf, b->dense_runs, b->prefix_store, b->embed_rows, b->embed_out};
     for (void* p : dptrs)
         if (p) (void)hipFree(p);
     if (b->h_st) (void)hipHostFree(b->h_st);

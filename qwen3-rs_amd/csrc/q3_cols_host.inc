@@ -177,6 +177,7 @@ int cols_plan_get(q3_engine* e, int wi, ColsPlan** out, bool draw = false) {
         if (rc == Q3_OK) {
             p.plan.swap(b->plan);
             p.graph.swap(b->graph);
+            p.head = b->plan_head;
         }
         b->plan.clear();
         b->graph.reset();

@@ -3,6 +3,8 @@
     python -m qwen3_rs_amd.cli export <MODEL_PATH> <OUTPUT_PATH> [--group-size 64]
     python -m qwen3_rs_amd.cli inference <checkpoint> [-t 1.0] [-p 0.9] [-s SEED] [-c CTX] [-m generate|chat]
                                          [-i INPUT] [-y SYSTEM] [-r 0|1] [--lookup DRAFT_LEN] [--speculate DRAFT_LEN]
+    python -m qwen3_rs_amd.cli embed <checkpoint> -i TEXT [-i TEXT ...] [--instruct TEXT] [--dim N] [--no-normalize]
+                                     [--append-token ID] [-o out.npy] [--streams N] [--context N]
 
 `inference` follows generation.rs: `generate` echoes the prompt and decodes from its last token over a zero KV prefix
 (:9-48); `chat` renders the template, forwards every prompt token (one rng coin each) and decodes until BOS/EOS
@@ -12,6 +14,10 @@
 earlier occurrence of the last two tokens) are checked in one pass over the weights; the output is the same, byte for byte.
 `--speculate N` does the same at any temperature through q3_generate_lookup_draw: a draft is accepted exactly when it is the
 token the sampler draws, so the output is again the same, byte for byte.
+`embed` reads a checkpoint out as an embedding model (q3_embed_many): every -i text is tokenized, `--append-token ID` adds one
+token id to each (Qwen3-Embedding's tokenizer appends its end-of-text token; which id that is in a given .tokenizer is the
+user's to state), `--instruct` is tokenized once and becomes the prefix all inputs share.  One line per input: index, dimension,
+first 8 components; `-o` saves the matrix.
 """
 from __future__ import annotations
 
@@ -154,7 +160,30 @@ def run_chat(t, tok: Tokenizer, cli_prompt, system_prompt, lookup: int = 0, spec
     return 0
 
 
-def main(argv=None) -> int:
+def run_embed(a) -> int:
+    import numpy as np
+    from .generation import embed
+    b = TransformerBuilder(a.checkpoint)
+    if a.context:
+        b = b.with_ctx_length(a.context)
+    with b.build() as t:
+        tok = Tokenizer(a.checkpoint, t.get_config().vocab_size, False)
+        tail = [] if a.append_token is None else [a.append_token]
+        prompts = [tok.encode(text) + tail for text in a.input]
+        if any(not p for p in prompts):
+            print("Error: an input has no token", file=sys.stderr)
+            return 1
+        prefix = tok.encode(a.instruct) if a.instruct else []
+        t.batch_init(max(1, min(a.streams, 32, len(prompts))))
+        rows = embed(t, prompts, normalize=not a.no_normalize, out_dim=a.dim, shared_prefix=prefix or None)
+    for r, row in enumerate(rows):
+        print(r, row.size, " ".join(f"{v:.6f}" for v in row[:8]))
+    if a.output:
+        np.save(a.output, rows)
+    return 0
+
+
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog="qwen3", description="Qwen3 CLI on the MI355X engine: export and inference")
     sub = ap.add_subparsers(dest="cmd")
     ex = sub.add_parser("export", help="Export a HuggingFace Qwen3 directory to the Q8 checkpoint (+ .tokenizer)")
@@ -175,6 +204,21 @@ def main(argv=None) -> int:
                      help="greedy only (-t 0): draft up to DRAFT_LEN (1..31) tokens per weight pass by prompt lookup; 0 = off")
     inf.add_argument("--speculate", type=int, default=0, metavar="DRAFT_LEN",
                      help="any -t: the same drafts, each accepted exactly when it is the token the sampler draws; same output; 0 = off")
+    em = sub.add_parser("embed", help="Last-token embeddings of texts (a Qwen3-Embedding checkpoint)")
+    em.add_argument("checkpoint")
+    em.add_argument("-i", "--input", action="append", required=True, metavar="TEXT", help="a text to embed; repeat for more")
+    em.add_argument("--instruct", default=None, metavar="TEXT", help="tokenized once: the prefix every input shares")
+    em.add_argument("--dim", type=int, default=None, metavar="N", help="keep the first N components (default: all)")
+    em.add_argument("--no-normalize", action="store_true", help="no L2 normalisation")
+    em.add_argument("--append-token", type=int, default=None, metavar="ID", help="a token id added behind every input")
+    em.add_argument("-o", "--output", default=None, metavar="out.npy", help="save the matrix [inputs, dim]")
+    em.add_argument("--streams", type=int, default=8, metavar="N", help="slots of the batched state (1..32)")
+    em.add_argument("-c", "--context", type=int, default=None)
+    return ap
+
+
+def main(argv=None) -> int:
+    ap = build_parser()
     a = ap.parse_args(argv)
     if a.cmd == "export":
         if not os.path.isdir(a.MODEL_PATH):
@@ -218,6 +262,13 @@ def main(argv=None) -> int:
             if a.mode == "generate":
                 return run_generate(t, tok, a.input, a.lookup or a.speculate, bool(a.speculate))
             return run_chat(t, tok, a.input, a.system, a.lookup or a.speculate, bool(a.speculate))
+    if a.cmd == "embed":
+        from .engine import Q3Error
+        try:
+            return run_embed(a)
+        except (Q3Error, IndexError, ValueError) as err:
+            print(f"Error: {err}", file=sys.stderr)
+            return 1
     ap.print_help()
     return 1
 

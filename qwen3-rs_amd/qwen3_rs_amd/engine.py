@@ -31,10 +31,12 @@ EXPORTED_SYMBOLS = [
     "q3_dense_pack", "q3_batch_prefill_slots", "q3_generate_many_dense",
     "q3_generate_many_stop", "q3_cols_schedule_stop",
     "q3_batch_copy_rows", "q3_batch_prefix_set", "q3_batch_prefix_get", "q3_generate_many_prefix",
+    "q3_embed_many",
 ]
 VERIFY_MAX = 32          # Q3_VERIFY_MAX
 COLS_MAX = 32            # Q3_COLS_MAX
 STOP_MAX = 8             # Q3_STOP_MAX
+EMBED_L2, EMBED_PREFIX = 1, 2   # Q3_EMBED_L2, Q3_EMBED_PREFIX
 
 
 class Q3Error(RuntimeError):
@@ -83,6 +85,19 @@ class _DenseStats(C.Structure):
 @dataclasses.dataclass(frozen=True)
 class DenseStats:
     """q3_dense_stats: the dense blocks of a call, their live columns and their pads"""
+    blocks: int
+    live_columns: int
+    pad_columns: int
+
+
+class _EmbedStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("waves", "blocks", "live_columns", "pad_columns")]
+
+
+@dataclasses.dataclass(frozen=True)
+class EmbedStats:
+    """q3_embed_stats: the waves of an embed_many call and the sums of their DenseStats"""
+    waves: int
     blocks: int
     live_columns: int
     pad_columns: int
@@ -227,6 +242,7 @@ def _bind(path: str) -> C.CDLL:
     L.q3_batch_prefix_set.argtypes = [C.c_void_p, i32p, sz]
     L.q3_batch_prefix_get.argtypes = [C.c_void_p, szp, i32p, sz]
     L.q3_generate_many_prefix.argtypes = L.q3_generate_many_stop.argtypes
+    L.q3_embed_many.argtypes = [C.c_void_p, i32p, szp, sz, C.c_uint32, sz, fp, C.POINTER(_EmbedStats)]
     L.q3_profile.argtypes = [C.c_void_p, sz, sz, C.c_int, fp, C.POINTER(C.c_int32), C.c_int]
     L.q3_profile_name.argtypes = [C.c_int]
     L.q3_profile_name.restype = C.c_char_p
@@ -673,6 +689,26 @@ class Transformer:
         generate_many_greedy / generate_many_sampled -- on the full prompts prefix + suffixes[r]; the passes are those of the
         suffixes alone.  Arguments and return value as for generate_many_stop."""
         return self._generate_many_stop(self._lib.q3_generate_many_prefix, suffixes, n_new, stop_tokens, sampler, raw)
+
+    # ---- embeddings (include/qwen3_hip.h section 2j)
+    def embed_many(self, prompts, normalize: bool = True, out_dim: Optional[int] = None, use_prefix: bool = False):
+        """The last-token vectors of many prompts (q3_embed_many): row r is the final RMSNorm of prompts[r]'s last token, cut to its
+        first out_dim components (None: dim) and, with normalize, L2-normalised.  The prompts go through the slots of batch_init
+        in waves of dense blocks, from slot 0 up -- whatever the slots held is overwritten -- and no classifier runs.
+        use_prefix: the prompts are suffixes behind the resident prefix of batch_prefix_set.
+        Returns (float32 array [len(prompts), out_dim], EmbedStats)."""
+        n = len(prompts)
+        dim = self._config.dim
+        if out_dim is not None and out_dim < 1:
+            raise IndexError("out_dim must be at least 1")
+        od = dim if out_dim is None else int(out_dim)
+        flat = [int(t) for p in prompts for t in p]
+        out = np.zeros((n, min(od, dim)), dtype=np.float32)
+        st = _EmbedStats()
+        flags = (EMBED_L2 if normalize else 0) | (EMBED_PREFIX if use_prefix else 0)
+        self._batch_rc(self._lib.q3_embed_many(self._h, _i32_array(flat), _size_array([len(p) for p in prompts]), n, flags, od,
+                                               out.ctypes.data_as(C.POINTER(C.c_float)), C.byref(st)))
+        return out, EmbedStats(st.waves, st.blocks, st.live_columns, st.pad_columns)
 
     def set_batch_sampler(self, temperature: float, topp: float, rng_seeds):
         """one Sampler per stream (sampler.rs:29-42), stream i seeded with rng_seeds[i]; temperature 0 = greedy"""

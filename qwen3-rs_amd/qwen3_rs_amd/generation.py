@@ -215,6 +215,26 @@ def generate_many(transformer, prompts: Sequence[Sequence[int]], max_new_tokens:
     return rows, stats
 
 
+def embed(transformer, prompts: Sequence[Sequence[int]], normalize: bool = True, out_dim: Optional[int] = None, shared_prefix=None):
+    """The embeddings of many prompts: the hidden state of each prompt's last token behind the final RMSNorm, cut to its first
+    out_dim components (None: all) and, with normalize, L2-normalised -- what a Qwen3-Embedding checkpoint is read out by.
+    The prompts go through the slots of Transformer.batch_init in dense blocks (Transformer.embed_many); the slots' contents
+    are overwritten.  shared_prefix as in generate_many: a token list every prompt begins with (`prompts` are then the suffixes
+    behind it; it is made resident with Transformer.batch_prefix_set unless it already is), True for the longest common prefix
+    of `prompts` (common_prefix_len), None for no prefix.  Returns a float32 array [len(prompts), out_dim]."""
+    if any(len(p) == 0 for p in prompts):
+        raise ValueError("Please provide a prompt")
+    prefix: List[int] = []
+    if shared_prefix is True:
+        k = common_prefix_len(prompts)
+        prefix, prompts = [int(t) for t in prompts[0][:k]], [p[k:] for p in prompts]
+    elif shared_prefix is not None and shared_prefix is not False:
+        prefix = [int(t) for t in shared_prefix]
+    if prefix and transformer.batch_prefix_get() != prefix:
+        transformer.batch_prefix_set(prefix)
+    return transformer.embed_many(prompts, normalize=normalize, out_dim=out_dim, use_prefix=bool(prefix))[0]
+
+
 def chat_turn(transformer, prompt_tokens: Sequence[int], pos: int, max_new_tokens: int,
               stop_tokens: Iterable[int] = (), sample: Callable[[np.ndarray], int] = sample_argmax,
               on_logits: Optional[Callable[[int, int, np.ndarray], None]] = None, lookup: Optional[Tuple[int, int]] = None,
