@@ -1,0 +1,1223 @@
+"""Call sequences over the batched state (helper module of tests/test_call_sequences_host.py and tests/test_call_sequences.py, not a
+conftest).  One BatchCtx serves every entry point of include/qwen3_hip.h sections 2b to 2j, and its plans, graphs and grow-only buffers
+are shared or cached between them; this module generates seeded sequences of calls, knows from the C oracle alone what every call
+must return, and checks an engine op by op.
+
+    make_sequence(seed, n_ops)  a deterministic list of ops (plain dicts, printable as a literal)
+    Reference                   the oracle side: cache rows, logits and final-norm taps of any token sequence, memoised in a trie,
+                                and the request rule of the header ("row r is what a fresh engine gives after prefill + generate_greedy")
+    FakeEngine                  the Transformer surface answered from Reference with explicit Python state; a switch injects a leak
+    run(engine, ops, reference) executes the ops, checks outputs, untouched caches and filled rows after every op
+
+Shape: small-hd128 (dim 512, 8 heads over 4 kv heads, head_dim 128, group 64, vocabulary 2,048) with 576 positions declared instead
+of 256: the score rows of the dense blocks (att_pf) are sized to the context end rounded up to 256, so on 256 positions they are
+allocated once and can never grow."""
+import dataclasses
+import functools
+import random
+
+import numpy as np
+
+VOCAB, SEQ, DIM = 2048, 576, 512
+NAME = "small-hd128"
+DENSE_CAP = 2048                      # Q3_PREFILL_M as the tests leave it
+COLS_MAX = 32
+WIDTHS = (1, 2, 4, 8, 16, 32)
+BUFFERS = ("cols_table", "cols_ncols", "cols_prompts", "cols_out", "cols_aux", "cols_temp", "cols_topp", "cols_seeds", "cols_req",
+           "dense_runs", "embed_rows", "embed_out", "att_pf")
+
+
+def shape(q3):
+    return dataclasses.replace(q3.checkpoint.SHAPES[NAME], max_seq_len=SEQ)
+
+
+def _q3():
+    import qwen3_rs_amd          # host-only functions: cols_schedule, cols_schedule_stop, dense_pack
+    return qwen3_rs_amd
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# tokens: every prompt is a slice of one of a few fixed base sequences, so that the oracle's rows are shared by all ops and seeds.
+# The bases repeat themselves with a short period: the prompt-lookup drafter finds drafts in them.
+# ---------------------------------------------------------------------------------------------------------------------------------
+N_BASES, BASE_LEN = 6, 560
+
+
+def _make_bases():
+    rng = np.random.default_rng(20240)
+    out = []
+    for k in range(N_BASES):
+        t = [int(v) for v in rng.integers(0, VOCAB, BASE_LEN)]
+        for i in range(5 + k, BASE_LEN):
+            if rng.random() < 0.6:
+                t[i] = t[i - 5 - k]
+        out.append(tuple(t))
+    return out
+
+
+BASES = _make_bases()
+
+
+def toks(spec):
+    """(base, end) or (base, start, end) -> the tokens"""
+    k, a, b = (spec[0], 0, spec[1]) if len(spec) == 2 else spec
+    return list(BASES[k][a:b])
+
+
+# request templates: (base, prompt length, n_new, temperature, top-p, seed).  0 .. 11 small (2-10 tokens), 12 .. 17 medium (past 32
+# columns and past every dense_min in use), 18 .. 87 the large lists (3 .. 120 tokens, most of them dense)
+def _make_catalogue():
+    rng = random.Random(77)
+    temps, topps = (0.0, 0.7, 0.9, 1.1), (0.9, 0.95, 1.0, 0.0)
+    cat = []
+    for i in range(88):
+        if i < 12:
+            n = 2 + i % 9
+        elif i < 18:
+            n = 34 + 5 * (i - 12)
+        else:
+            n = rng.choice((3, 9, 20, 33, 35, 41, 48, 57, 64, 65, 70, 83, 97, 110, 120))
+        cat.append((i % N_BASES, n, 1 + rng.randrange(4), temps[(i // 2) % 4], topps[i % 4], 1000 + i))
+    return cat
+
+
+CAT = _make_catalogue()
+SMALL, MEDIUM, LARGE = range(0, 12), range(12, 18), range(18, 88)
+PREFIXES = ((5, 7), (4, 37), (3, 44))          # resident prefixes: base, length (one narrow, two wide)
+DEEP = {1: (2, 300), 2: (2, 530)}              # the runs that end past 256 and past 512 positions
+
+
+def xorshift(state, coins=1):
+    """sampler.rs:44-49: the rng state `coins` coins on"""
+    for _ in range(coins):
+        state ^= state >> 12
+        state = (state ^ (state << 25)) & 0xFFFFFFFFFFFFFFFF
+        state ^= state >> 27
+    return state
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# op kinds
+# ---------------------------------------------------------------------------------------------------------------------------------
+KINDS = (
+    "forward_batch", "forward_batch_s", "generate_greedy_batch", "generate_greedy_batch_s", "prefill_batched",
+    "verify", "generate_lookup", "verify_draw", "generate_lookup_draw",
+    "batch_step_cols", "generate_many_greedy", "batch_step_cols_draw", "generate_many_sampled",
+    "batch_prefill_slots", "generate_many_dense", "generate_many_stop",
+    "batch_copy_rows", "batch_prefix_set", "generate_many_prefix", "embed_many", "embed_many_prefix",
+    "set_batch_sampler_on", "set_batch_sampler_off", "set_sampler", "batch_reset_kv", "reset_kv", "batch_init",
+    "forward", "generate_greedy",
+    "refused_batch", "refused_prefill_batched", "refused_verify", "refused_cols", "refused_dense", "refused_stop", "refused_prefix",
+    "refused_embed", "refused_forward", "refused_greedy_only",
+)
+GREEDY_ONLY = ("forward_batch", "generate_greedy_batch", "batch_step_cols", "generate_many_greedy")     # refused under a sampling batch
+NEED_DRAWS = ("forward_batch_s", "generate_greedy_batch_s")                                              # need known per-stream rng states
+SAMPLING_ONLY = NEED_DRAWS + ("refused_greedy_only",)
+MANY = ("generate_many_greedy", "generate_many_sampled", "generate_many_dense", "generate_many_stop", "generate_many_prefix")
+
+# ordered pairs the API makes illegal, one line of reason each
+ILLEGAL = {}
+for _a in GREEDY_ONLY:
+    for _b in SAMPLING_ONLY:
+        ILLEGAL[(_a, _b)] = "the first needs the batch sampler off, the second on, and neither changes it"
+        ILLEGAL[(_b, _a)] = "the first needs the batch sampler on, the second off, and neither changes it"
+    ILLEGAL[("set_batch_sampler_on", _a)] = "greedy only: refused (-5) right behind a batch sampler with temperature > 0"
+for _b in SAMPLING_ONLY:
+    ILLEGAL[("set_batch_sampler_off", _b)] = "needs a sampling batch, which the call in front has just switched off"
+    ILLEGAL[("batch_init", _b)] = "q3_batch_init starts the batched state over: no batch sampler is set"
+for _a in ("generate_many_sampled", "generate_many_dense", "generate_many_stop", "generate_many_prefix"):
+    for _b in NEED_DRAWS:
+        ILLEGAL[(_a, _b)] = ("the per-stream sampler states are unspecified behind a sampled loop (and behind a greedy one the batch "
+                             "sampler is off): q3_batch_sampler_set has to come first")
+for _b in ("generate_many_prefix", "embed_many_prefix"):
+    ILLEGAL[("batch_init", _b)] = "q3_batch_init drops the resident prefix"
+for _a in ("batch_init", "batch_reset_kv"):
+    ILLEGAL[(_a, "batch_copy_rows")] = "legal in the API, but the sequences copy only rows whose tokens they know: every slot has just been cleared"
+ALL_PAIRS = [(a, b) for a in KINDS for b in KINDS]
+
+
+def pairs_of(ops):
+    return {(a["op"], b["op"]) for a, b in zip(ops, ops[1:])}
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# schedules of the loops, from the library's host-only functions
+# ---------------------------------------------------------------------------------------------------------------------------------
+def dense_block(lens):
+    """one pack of runs (always a single block here) -> (width, wide)"""
+    _, st = _q3().dense_pack(list(lens), DENSE_CAP)
+    assert st.blocks == 1, lens
+    w = st.live_columns + st.pad_columns
+    return w, w > COLS_MAX
+
+
+def width_index(n):
+    return next(i for i, w in enumerate(WIDTHS) if w >= n)
+
+
+def _pass_sizes(table):
+    sizes = {}
+    for p, _, _, _ in table:
+        sizes[p] = sizes.get(p, 0) + 1
+    return [sizes[p] for p in sorted(sizes)]
+
+
+def many_plan(lens, n_new, streams, dense_min=0, rows=None, stop=()):
+    """What a generate_many call does with requests of lens[r] prompt tokens: dict(table, stats, n_out, occupants = per slot the
+    requests it held in order, passes = live columns per column pass, blocks = [(width, wide, run lengths)] of the dense requests
+    in order)."""
+    q3 = _q3()
+    dense = [bool(dense_min) and n - 1 >= dense_min for n in lens]
+    seen = [1 if d else n for n, d in zip(lens, dense)]
+    if stop:
+        table, n_out, stats = q3.cols_schedule_stop(seen, list(n_new), streams, rows, list(stop))
+    else:
+        table, stats = q3.cols_schedule(seen, list(n_new), streams)
+        n_out = list(n_new)
+    occupants = {}
+    first_pass = {}
+    for p, s, _, r in table:
+        if r not in first_pass:
+            first_pass[r] = p
+            occupants.setdefault(s, []).append(r)
+    blocks = []
+    for p in sorted(set(first_pass.values())):
+        entering = sorted(r for r, fp in first_pass.items() if fp == p and dense[r])
+        if entering:
+            run_lens = [lens[r] - 1 for r in entering]
+            blocks.append(dense_block(run_lens) + (run_lens,))
+    return dict(table=table, stats=stats, n_out=n_out, occupants=occupants, passes=_pass_sizes(table), blocks=blocks)
+
+
+def op_requests(op):
+    """(prompt lengths, n_new) of a generate_many / embed op"""
+    return [CAT[i][1] for i in op["reqs"]], [CAT[i][2] for i in op["reqs"]]
+
+
+def needs(op, streams, sampling, prefix_len, rows=None, stop=()):
+    """What an op asks of the grow-only buffers, by the sizes at the call sites of cols_job_run, cols_generate_stop, cols_sampler_upload
+    and q3_embed_many, and which kept plans it runs: dict(buffer -> elements), cols = {(draw, width index)}, dense = {block width}."""
+    kind = op["op"]
+    need, cols, dense = {}, set(), set()
+
+    def job(n_passes, n_prompt, n_out, n_runs, draw, per_request, max_end):
+        need.update(cols_table=n_passes * COLS_MAX, cols_ncols=n_passes, cols_prompts=n_prompt, cols_out=n_out, dense_runs=n_runs)
+        if draw and n_passes:
+            need["cols_aux"] = n_passes * COLS_MAX
+            if per_request:
+                need.update(cols_temp=per_request, cols_topp=per_request, cols_seeds=per_request)
+        if max_end:
+            need["att_pf"] = (max_end + 255) & ~255
+
+    if kind in MANY:
+        lens, n_new = op_requests(op)
+        draw = kind == "generate_many_sampled" or bool(op.get("sampled"))
+        if kind == "generate_many_stop" or (kind == "generate_many_prefix" and stop):
+            plan = many_plan(lens, n_new, streams, 0, rows, stop)
+            need.update(cols_req=5 * len(lens), cols_prompts=sum(lens), cols_out=sum(n_new))
+            if draw:
+                need.update(cols_temp=len(lens), cols_topp=len(lens), cols_seeds=len(lens))
+        else:
+            plan = many_plan(lens, n_new, streams, op.get("dense_min", 0))
+            narrow = [b for b in plan["blocks"] if not b[1]]
+            wide = [b for b in plan["blocks"] if b[1]]
+            job(len(plan["passes"]) + len(narrow), sum(lens), sum(n_new), sum(len(b[2]) for b in wide), draw, len(lens),
+                max([max(b[2]) for b in wide], default=0))
+            cols |= {(draw, width_index(sum(b[2]))) for b in narrow}
+            dense |= {b[0] for b in wide}
+        cols |= {(draw, width_index(n)) for n in plan["passes"]}
+    elif kind in ("batch_prefill_slots", "batch_prefix_set"):
+        runs = [(0, len(toks(op["prompt"])))] if kind == "batch_prefix_set" else [(f, len(toks(p))) for p, f in zip(op["prompts"], op["first"])]
+        draw = sampling and kind == "batch_prefill_slots"
+        w, wide = dense_block([n for _, n in runs])
+        n_tok = sum(n for _, n in runs)
+        if wide:
+            job(0, n_tok, 0, len(runs), draw, 0, max(f + n for f, n in runs))
+            dense.add(w)
+        else:
+            job(1, n_tok, 0, 0, draw, 0, 0)
+            cols.add((draw, width_index(n_tok)))
+    elif kind in ("embed_many", "embed_many_prefix"):
+        lens, _ = op_requests(op)
+        P = prefix_len if kind == "embed_many_prefix" else 0
+        max_end = 0
+        for w0 in range(0, len(lens), streams):
+            wave = lens[w0:w0 + streams]
+            w, wide = dense_block(wave)
+            if wide:
+                dense.add(w)
+                max_end = max(max_end, P + max(wave))
+            else:
+                cols.add((False, width_index(sum(wave))))
+        need.update(cols_prompts=sum(lens), dense_runs=len(lens), embed_rows=len(lens), embed_out=len(lens) * (op.get("out_dim") or DIM))
+        if max_end:
+            need["att_pf"] = (max_end + 255) & ~255
+    elif kind in ("batch_step_cols", "batch_step_cols_draw"):
+        cols.add((sampling and kind == "batch_step_cols_draw", width_index(len(op["slots"]))))
+    return dict(need=need, cols=cols, dense=dense)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the generator
+# ---------------------------------------------------------------------------------------------------------------------------------
+SEEDS = (11, 12, 13, 14, 15, 16, 17, 18)
+N_OPS = 240
+
+
+class _Gen:
+    """State the generator tracks: for the single cache and every slot the base prefix its rows are known to hold, the two samplers,
+    the resident prefix, the batch shape."""
+
+    def __init__(self, seed, avoid):
+        self.rng = random.Random(seed)
+        self.avoid = avoid                   # pairs other sequences cover already
+        self.ops = []
+        self.single = None                   # (base, n): rows 0 .. n - 1 hold that prefix
+        self.slots = []
+        self.streams = self.ctx = 0
+        self.bs_on = self.bs_known = False
+        self.ss_on = False
+        self.prefix = None
+        self.size = "S"
+        self.large_calls = 0
+        self.growth = False                  # inside the epoch whose buffers have to grow: no q3_batch_init
+
+    # -- legality
+    def legal(self, kind):
+        if kind in GREEDY_ONLY and self.bs_on:
+            return False
+        if kind in NEED_DRAWS and not (self.bs_on and self.bs_known):
+            return False
+        if kind == "refused_greedy_only" and not self.bs_on:
+            return False
+        if kind == "batch_step_cols_draw" and self.bs_on and not self.bs_known:
+            return False
+        if kind in ("generate_many_prefix", "embed_many_prefix") and self.prefix is None:
+            return False
+        if kind == "batch_copy_rows" and not (self.streams >= 2 and any(s for s in self.slots)):
+            return False
+        if kind in ("verify", "generate_lookup") and self.ss_on:
+            return False
+        if kind == "batch_init" and self.growth:
+            return False
+        return True
+
+    # -- helpers
+    def _place(self, held, room, m=1):
+        """continue a cache that holds (base, n) by m tokens, or start a base over: (base, first position)"""
+        if held and held[1] + m + 8 <= room and self.rng.random() < 0.6:
+            return held[0], held[1]
+        return self.rng.randrange(N_BASES), 0
+
+    def _reqs(self, dense=False):
+        r = self.rng
+        if self.size == "S":
+            out = r.sample(SMALL, r.randint(1, 3))
+            if dense or r.random() < 0.3:
+                out[r.randrange(len(out))] = r.choice(MEDIUM)
+            return out
+        self.large_calls += 1                                  # every large list is longer than the one before it
+        n = min(38, 18 + 2 * self.large_calls) if self.size == "L1" else min(70, 50 + 2 * self.large_calls)
+        return list(LARGE[:n])
+
+    # -- one emitter per kind
+    def emit(self, kind, **force):
+        r = self.rng
+        op = {"op": kind}
+        S, ctx = self.streams, self.ctx
+        if kind in ("forward_batch", "forward_batch_s", "generate_greedy_batch", "generate_greedy_batch_s", "refused_batch"):
+            n = r.randint(1, S)
+            steps = r.randint(1, 4) if "generate" in kind else 1
+            tk, ps = [], []
+            for i in range(n):
+                k, p = self._place(self.slots[i], ctx, steps)
+                tk.append(BASES[k][p])
+                ps.append(p)
+                if kind != "refused_batch":
+                    self.slots[i] = (k, p + 1)
+            if kind == "refused_batch":
+                tk[r.randrange(n)] = VOCAB
+            if "generate" in kind:
+                op.update(first=tk, pos=ps, steps=steps)
+            else:
+                op.update(tokens=tk, pos=ps)
+        elif kind in ("prefill_batched", "refused_prefill_batched"):
+            m = r.choice((2, 5, 9, 33, 40, 47)) if self.size == "S" else r.choice((70, 100, 120))
+            k, p = self._place(self.single, SEQ, m)
+            if kind == "refused_prefill_batched":
+                op.update(prompt=(k, 0, m), pos=SEQ - m + 1)
+            else:
+                op.update(prompt=(k, p, p + m), pos=p)
+                self.single = (k, p + m)
+        elif kind in ("verify", "verify_draw", "refused_verify"):
+            n = r.randint(1, 9)
+            k, p = self._place(self.single, SEQ, n)
+            t = list(BASES[k][p:p + n])
+            if n > 2 and r.random() < 0.5:
+                t[r.randrange(1, n)] = r.randrange(VOCAB)      # a draft the model need not even see: rejected unless drawn
+            if kind == "refused_verify":
+                t[-1] = VOCAB
+                op.update(tokens=t, pos=p, draw=self.ss_on)
+            else:
+                op.update(tokens=t, pos=p)
+                self.single = (k, p + 1)
+        elif kind in ("generate_lookup", "generate_lookup_draw", "generate_greedy"):
+            n = r.randint(1, 6)
+            k, p = self._place(self.single, SEQ, n)
+            op.update(first=BASES[k][p], pos=p, n=n)
+            if kind != "generate_greedy":
+                op.update(corpus=(k, 0, max(p, 12)), ngram=r.choice((1, 2)), draft_len=r.choice((0, 3, 7)))
+            self.single = (k, p + 1)
+        elif kind in ("forward", "refused_forward"):
+            k, p = self._place(self.single, SEQ)
+            if kind == "refused_forward":
+                op.update(token=BASES[k][p], pos=SEQ)
+            else:
+                op.update(token=BASES[k][p], pos=p)
+                self.single = (k, p + 1)
+        elif kind in ("batch_step_cols", "batch_step_cols_draw", "refused_cols", "refused_greedy_only"):
+            slots = r.sample(range(S), r.randint(1, min(S, 3)))
+            left = COLS_MAX
+            sl, tk, ps = [], [], []
+            for j, s in enumerate(slots):
+                m = r.randint(1, min(left - (len(slots) - 1 - j), r.choice((1, 3, 12))))
+                left -= m
+                k, p = self._place(self.slots[s], ctx, m)
+                sl += [s] * m
+                tk += list(BASES[k][p:p + m])
+                ps += list(range(p, p + m))
+                if not kind.startswith("refused"):
+                    self.slots[s] = (k, p + m)
+            if kind == "refused_cols":
+                sl[-1] = S
+                op["draw"] = self.bs_on
+            op.update(slots=sl, tokens=tk, pos=ps)
+            if kind == "batch_step_cols_draw" and r.random() < 0.4:
+                op["keep"] = [int(j + 1 == len(sl) or sl[j + 1] != sl[j] or r.random() < 0.5) for j in range(len(sl))]
+        elif kind in MANY or kind == "refused_stop":
+            op["reqs"] = self._reqs(dense=kind == "generate_many_dense")
+            if kind == "generate_many_dense":
+                op.update(sampled=self.bs_on or r.random() < 0.5, dense_min=r.choice((8, 32, 64)))
+            elif kind in ("generate_many_stop", "generate_many_prefix", "refused_stop"):
+                op["sampled"] = self.bs_on or r.random() < 0.5
+                cand = [(i, j) for i in op["reqs"] for j in range(CAT[i][2])]
+                k = 0 if kind == "generate_many_prefix" and r.random() < 0.5 else min(len(cand), r.randint(1, 4))
+                op["stop_at"] = r.sample(cand, k)              # (request, index): that token of the request's own row is a stop token
+            if kind == "refused_stop":
+                op["bad"] = r.randrange(len(op["reqs"]))       # that request's prompt ends with a token outside the vocabulary
+            else:
+                used = min(len(op["reqs"]), S)
+                self.slots[:used] = [None] * used
+                if kind == "generate_many_sampled" or op.get("sampled"):
+                    self.bs_known = False
+        elif kind in ("batch_prefill_slots", "refused_dense"):
+            if force.get("wide"):                              # one run of 41 tokens: a block of 48 columns
+                op.update(slots=[0], prompts=[(1, 0, 41)], first=[0])
+                self.slots[0] = (1, 41)
+            elif self.size != "S" and kind == "batch_prefill_slots":
+                s = r.randrange(S)
+                op.update(slots=[s], prompts=[DEEP[int(self.size[1])]], first=[0])
+                self.slots[s] = DEEP[int(self.size[1])]
+            else:
+                slots = r.sample(range(S), r.randint(1, min(S, 3)))
+                prompts, first = [], []
+                for s in slots:
+                    m = r.choice((3, 8, 20, 34, 41, 60))
+                    k, p = self._place(self.slots[s], ctx, m)
+                    prompts.append((k, p, p + m))
+                    first.append(p)
+                    if kind == "batch_prefill_slots":
+                        self.slots[s] = (k, p + m)
+                if kind == "refused_dense":
+                    slots[-1] = S
+                op.update(slots=slots, prompts=prompts, first=first)
+        elif kind in ("batch_copy_rows", "refused_prefix"):
+            held = [s for s in range(S) if self.slots[s]] if kind == "batch_copy_rows" else list(range(S))
+            src = r.choice(held)
+            k, n = self.slots[src] or (0, 8)
+            dst = r.sample([s for s in range(S) if s != src], r.randint(1, max(1, min(S - 1, 3)))) if S > 1 else [0]
+            ext = [s for s in dst if self.slots[s] and self.slots[s][0] == k and self.slots[s][1] < n]
+            if kind == "batch_copy_rows" and ext and r.random() < 0.5:
+                dst = ext[:1]
+                first = self.slots[dst[0]][1]
+                rows = r.randint(1, n - first)
+            else:
+                first, rows = 0, r.randint(1, n)
+            if kind == "refused_prefix":
+                dst[-1] = S
+            else:
+                for s in dst:
+                    self.slots[s] = (k, first + rows)
+            op.update(src=src, dst=dst, first=first, n=rows)
+        elif kind == "batch_prefix_set":
+            self.prefix = r.choice(PREFIXES)
+            op["prompt"] = self.prefix
+            self.slots[0] = self.prefix
+        elif kind in ("embed_many", "embed_many_prefix", "refused_embed"):
+            op.update(reqs=self._reqs(), normalize=r.random() < 0.5, out_dim=r.choice((None, None, 64, 30)) if self.size == "S" else None)
+            if kind == "refused_embed":
+                op["bad"] = r.randrange(len(op["reqs"]))
+            else:
+                used = min(len(op["reqs"]), S)
+                self.slots[:used] = [None] * used
+        elif kind in ("set_batch_sampler_on", "set_batch_sampler_off"):
+            on = kind.endswith("_on")
+            op.update(T=r.choice((0.7, 0.9, 1.2)) if on else 0.0, P=r.choice((0.9, 0.95, 1.0)), seeds=[r.getrandbits(48) + 1 for _ in range(S)])
+            self.bs_on, self.bs_known = on, True
+        elif kind == "set_sampler":
+            op.update(T=0.0 if self.ss_on else r.choice((0.8, 1.1)), P=r.choice((0.9, 1.0)), seed=r.getrandbits(48) + 1)
+            self.ss_on = op["T"] > 0
+        elif kind == "batch_reset_kv":
+            self.slots = [None] * S
+        elif kind == "reset_kv":
+            self.single = None
+        elif kind == "batch_init":
+            streams = force.get("streams") or r.choice([s for s in (2, 3, 5, 8) if s != S])
+            ctx = force.get("ctx", r.choice((192, 256, 0) if streams <= 3 else (192, 256)))
+            op.update(streams=streams, ctx=ctx)
+            self.streams, self.ctx = streams, min(ctx, SEQ) if ctx else SEQ
+            self.slots = [None] * streams
+            self.bs_on = self.bs_known = False
+            self.prefix = None
+        self.ops.append(op)
+        return op
+
+    # -- the walk
+    def pick(self, must):
+        prev = self.ops[-1]["op"]
+        legal = [k for k in KINDS if self.legal(k) and (prev, k) not in ILLEGAL]
+        seen = pairs_of(self.ops) | self.avoid
+
+        def score(k):
+            new = (prev, k) not in seen
+            onward = sum(1 for b in KINDS if (k, b) not in seen and (k, b) not in ILLEGAL)
+            return 1000 * new + 400 * (k in must) + onward + self.rng.random()
+        return max(legal, key=score)
+
+    def enable(self, kind):
+        """the state changers that make `kind` legal, if any are needed"""
+        if kind in SAMPLING_ONLY and not (self.bs_on and self.bs_known):
+            self.emit("set_batch_sampler_on")
+        if kind in GREEDY_ONLY and self.bs_on:
+            self.emit("set_batch_sampler_off")
+        if kind == "batch_step_cols_draw" and self.bs_on and not self.bs_known:
+            self.emit("set_batch_sampler_on")
+        if kind in ("verify", "generate_lookup") and self.ss_on:
+            self.emit("set_sampler")
+        if kind in ("generate_many_prefix", "embed_many_prefix") and self.prefix is None:
+            self.emit("batch_prefix_set")
+        if kind == "batch_copy_rows" and not any(self.slots):
+            self.emit("batch_prefill_slots")
+
+    def target(self, must):
+        """a pair of kinds that no sequence has adjacent yet: the state both need, then the two ops (one, where the first is the last op)"""
+        seen = pairs_of(self.ops) | self.avoid
+        prev = self.ops[-1]["op"]
+        off = ("batch_init",) if self.growth else ()
+        todo = [p for p in ALL_PAIRS if p not in seen and p not in ILLEGAL and p[0] not in off and p[1] not in off]
+        if not todo:
+            return self.emit(self.pick(must))
+        ready = [p for p in todo if self.legal(p[0]) and self.legal(p[1]) and (prev, p[0]) not in ILLEGAL]
+        owed = [p for p in todo if p[0] in must or p[1] in must]
+        for pool in ([p for p in todo if p[0] == prev and self.legal(p[1])], [p for p in ready if (prev, p[0]) in todo], ready, todo):
+            if pool:
+                a, b = self.rng.choice([p for p in pool if p in owed] or pool)
+                break
+        if a != prev:
+            self.enable(b)
+            self.enable(a)
+            if not self.legal(a) or (self.ops[-1]["op"], a) in ILLEGAL:
+                return self.emit(self.pick(must))
+            self.emit(a)
+        if self.legal(b):
+            self.emit(b)
+
+    def phase(self, size, n_ops, must):
+        """about n_ops ops of one size class, every kind of `must` among them"""
+        self.size = size
+        must = list(must)
+        start = len(self.ops)
+        self.large_calls = 0
+        if size != "S":                                        # the kinds that have to grow the buffers come first
+            for k in must:
+                self.enable(k)
+                self.emit(k)
+            must = []
+        while len(self.ops) < start + n_ops:
+            at = len(self.ops)
+            if len(must) + 4 >= start + n_ops - at:                # no room left: the kinds the phase owes, in a legal order
+                k = next((m for m in must if self.legal(m) and (self.ops[-1]["op"], m) not in ILLEGAL), None)
+                if k is None and must:
+                    k = "set_batch_sampler_off" if self.bs_on else "set_batch_sampler_on"
+                self.emit(k or self.pick(()))
+            else:
+                self.target(must)
+            for o in self.ops[at:]:
+                if o["op"] in must:
+                    must.remove(o["op"])
+        assert not must, (size, must)
+
+
+GROW = ("generate_many_greedy", "generate_many_sampled", "generate_many_dense", "generate_many_stop", "embed_many", "batch_prefill_slots")
+
+
+def _sequence(seed, n_ops, avoid):
+    g = _Gen(seed, avoid)
+    r = g.rng
+    a, c = r.sample((2, 3, 5, 8), 2)
+    b = r.choice([s for s in (2, 3, 4) if s != a])
+    unit = n_ops // 10
+    # epoch 0, 256 positions: everything small; the first dense call fixes dense_cap
+    g.emit("batch_init", streams=a, ctx=256)
+    g.phase("S", 2 * unit, ("generate_many_dense", "set_batch_sampler_on", "set_batch_sampler_off", "batch_prefix_set"))
+    # epoch 1, the whole context, few slots: small - large - small - larger - small, no q3_batch_init in between, so that every
+    # grow-only buffer is re-allocated twice behind plans that were cached while it was small
+    g.emit("batch_init", streams=b if b != g.streams else 4, ctx=0)
+    g.growth = True
+    warm = ("generate_many_greedy", "generate_many_greedy", "generate_many_sampled", "generate_many_sampled", "generate_many_dense",
+            "generate_many_dense", "batch_prefill_slots", "batch_prefill_slots", "embed_many", "embed_many", "generate_many_stop",
+            "set_batch_sampler_on", "set_batch_sampler_off")
+    g.phase("S", 2 * unit, warm)
+    for _ in range(2):                                         # the second one runs the kept plan of that width
+        g.emit("batch_prefill_slots", wide=True)
+    for size in ("L1", "L2"):
+        g.phase(size, unit, GROW)
+        g.phase("S", unit - 1, GROW)
+        g.emit("batch_prefill_slots", wide=True)               # small again: score rows of 256 positions would do
+    g.growth = False
+    # epoch 2: another number of slots, 256 positions again
+    g.emit("batch_init", streams=c if c != g.streams else 6, ctx=256)
+    g.phase("S", max(unit, n_ops - len(g.ops)), ("generate_many_dense", "set_batch_sampler_on", "set_batch_sampler_off"))
+    return g.ops
+
+
+@functools.lru_cache(maxsize=None)
+def _cached_sequence(seed, n_ops):
+    avoid = set()
+    if seed in SEEDS:                                           # a seed of the suite steers away from the pairs of the seeds in front of it
+        for s in SEEDS[:SEEDS.index(seed)]:
+            avoid |= pairs_of(_cached_sequence(s, n_ops))
+    return _sequence(seed, n_ops, frozenset(avoid))
+
+
+def make_sequence(seed, n_ops=N_OPS):
+    """The ops of a seed: deterministic, legal in the state the ops before them leave, sizes small - large - small - larger - small"""
+    import copy
+    return copy.deepcopy(_cached_sequence(seed, n_ops))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the reference: the C oracle, memoised
+# ---------------------------------------------------------------------------------------------------------------------------------
+class _Node:
+    __slots__ = ("parent", "tok", "pos", "k", "v", "logits", "x", "kids")
+
+    def __init__(self, parent, tok):
+        self.parent, self.tok, self.pos, self.kids = parent, tok, (parent.pos + 1 if parent else -1), {}
+
+
+class Reference:
+    """Everything the tests expect comes from here, and everything here comes from oracle.OracleModel.forward, oracle.Sampler and
+    oracle.sample_argmax.  A trie over token sequences holds, per sequence, the key and value rows its last token writes, its logits
+    and its final-norm tap; the oracle's cache is loaded with a node's path before the node's children are computed (its rows depend on
+    the tokens in front of them and on nothing else)."""
+
+    def __init__(self, oracle, path):
+        self.oracle = oracle
+        self.om = oracle.OracleModel(path, SEQ)
+        c = self.om.config
+        assert (c.seq_len, c.vocab_size, c.dim) == (SEQ, VOCAB, DIM)
+        self.L, self.kvd = c.n_layers, c.n_kv_heads * c.head_dim
+        lib = oracle.lib()
+        shp = (c.n_layers, c.seq_len, self.kvd)
+        self._K = np.ctypeslib.as_array(lib.q3o_key_cache(self.om._h), shape=shp)        # the oracle's own caches, not copies
+        self._V = np.ctypeslib.as_array(lib.q3o_value_cache(self.om._h), shape=shp)
+        self.root = _Node(None, -1)
+        self._at = self.root
+        self._memo = {}
+        self.forwards = 0
+
+    @staticmethod
+    def _path(node):
+        out = []
+        while node.parent is not None:
+            out.append(node)
+            node = node.parent
+        return out[::-1]
+
+    def _load(self, node):
+        if self._at is node:
+            return
+        want, have = self._path(node), self._path(self._at)
+        c = 0
+        while c < len(want) and c < len(have) and want[c] is have[c]:
+            c += 1
+        for n in want[c:]:
+            self._K[:, n.pos] = n.k
+            self._V[:, n.pos] = n.v
+        self._at = node
+
+    def child(self, node, tok):
+        n = node.kids.get(tok)
+        if n is None:
+            self._load(node)
+            n = _Node(node, tok)
+            n.logits = self.om.forward(tok, n.pos)
+            n.k, n.v, n.x = self._K[:, n.pos].copy(), self._V[:, n.pos].copy(), self.om.tap_x()
+            node.kids[tok] = n
+            self._at = n
+            self.forwards += 1
+        return n
+
+    def node(self, seq):
+        n = self.root
+        for t in seq:
+            n = self.child(n, t)
+        return n
+
+    def draw(self, logits, T, P, state):
+        """(token, rng state afterwards): Sampler::sample with that state, the argmax and no coin at temperature 0"""
+        if not T > 0:
+            return self.oracle.sample_argmax(logits), state
+        s = self.oracle.Sampler(VOCAB, T, P, state)
+        tok = s.sample(logits)
+        return tok, int(s.rng_state.value)
+
+    def generate(self, prompt, n_new, sampler=None):
+        """The header's rule for request rows: what a fresh engine returns for prefill(prompt) and generate_greedy behind it, after
+        set_sampler(temperature, topp, seed) when sampler = (temperature, topp, seed) -- one discarded sample per prompt position
+        in front of the last.  Returns (the n_new tokens, the rng state afterwards)."""
+        key = (tuple(prompt), n_new, sampler)
+        if key not in self._memo:
+            T, P, state = sampler if sampler else (0.0, 1.0, 0)
+            n, tok, out = self.root, None, []
+            for t in prompt:
+                n = self.child(n, t)
+                if T > 0:
+                    tok, state = self.draw(n.logits, T, P, state)
+            if not T > 0:
+                tok = self.oracle.sample_argmax(n.logits)
+            out.append(tok)
+            while len(out) < n_new:
+                n = self.child(n, tok)
+                tok, state = self.draw(n.logits, T, P, state)
+                out.append(tok)
+            self._memo[key] = (out, state)
+        return self._memo[key]
+
+
+def cut_at_stop(row, stop):
+    for i, t in enumerate(row):
+        if t in stop:
+            return row[:i + 1]
+    return row
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the fake engine: explicit state, answers from the reference
+# ---------------------------------------------------------------------------------------------------------------------------------
+class Refused(RuntimeError):
+    def __init__(self, code, msg=""):
+        super().__init__(f"[status {code}] {msg}")
+        self.code = code
+
+
+class _Cache:
+    def __init__(self, ref, ctx):
+        self.K = np.zeros((ref.L, ctx, ref.kvd), dtype=np.float32)
+        self.V = np.zeros_like(self.K)
+        self.hist, self.node, self.ctx = [], ref.root, ctx
+
+
+LEAKS = ("sampler", "prefix", "length")
+
+
+class FakeEngine:
+    """The calls of Transformer that touch the batched state, and the single-stream ones that share the engine, over explicit state:
+    per cache its rows and the tokens they were computed from, the two samplers with their rng states, the resident prefix, the batch
+    shape.  Every number comes from Reference.  leak: one of LEAKS --
+        "sampler": a slot's sampler state is carried from one generate_many_sampled call into the next instead of being loaded
+        "prefix":  the resident prefix survives q3_batch_init
+        "length":  batch_reset_kv leaves the rows of every slot's occupant in place"""
+
+    def __init__(self, ref, leak=None):
+        assert leak is None or leak in LEAKS
+        self.ref, self.leak = ref, leak
+        self.single = _Cache(ref, SEQ)
+        self.slots, self.streams, self.ctx = [], 0, 0
+        self.sT, self.sP, self.srng = 0.0, 1.0, None
+        self.bT, self.bP, self.brng = 0.0, 1.0, []
+        self.prefix = []
+        self.loop_rng = {}
+        self.touched = {}
+
+    # -- state
+    def _cache(self, cid):
+        return self.single if cid == "single" else self.slots[cid]
+
+    def _touch(self, cid, lo, hi):
+        if self.touched.get(cid) != "all":
+            a, b = self.touched.get(cid, (lo, hi))
+            self.touched[cid] = (min(a, lo), max(b, hi))
+
+    def _feed(self, cid, tok, pos):
+        """forward(tok, pos) over that cache: the node of its history with tok behind it; the row is written"""
+        c = self._cache(cid)
+        assert len(c.hist) >= pos, f"the model does not know rows {len(c.hist)} .. {pos - 1} of cache {cid}"
+        if len(c.hist) > pos:
+            c.hist = c.hist[:pos]
+            c.node = self.ref.node(c.hist)
+        c.node = self.ref.child(c.node, tok)
+        c.hist.append(tok)
+        c.K[:, pos], c.V[:, pos] = c.node.k, c.node.v
+        self._touch(cid, pos, pos + 1)
+        return c.node
+
+    def _check_tokens(self, tokens):
+        if any(t < 0 or t >= VOCAB for t in tokens):
+            raise IndexError("token outside the vocabulary")
+
+    def _sdraw(self, logits):
+        tok, self.srng = self.ref.draw(logits, self.sT, self.sP, self.srng)
+        return tok
+
+    # -- the single stream
+    def forward(self, token, pos):
+        self._check_tokens([token])
+        if pos >= SEQ:
+            raise IndexError("position out of range")
+        return self._feed("single", token, pos).logits.copy()
+
+    def generate_greedy(self, first, pos, n):
+        out, tok = [], first
+        for i in range(n):
+            tok = self._sdraw(self._feed("single", tok, pos + i).logits)
+            out.append(tok)
+        return out
+
+    def prefill(self, tokens, pos=0, batched=False):
+        self._check_tokens(tokens)
+        if pos + len(tokens) > SEQ:
+            raise IndexError("the prompt ends past the context")
+        for i, t in enumerate(tokens):
+            tok = self._sdraw(self._feed("single", t, pos + i).logits)        # one (discarded) sample per prompt position
+        return tok
+
+    def _verify(self, tokens, pos):
+        self._check_tokens(tokens)
+        if not 1 <= len(tokens) <= COLS_MAX or pos + len(tokens) > SEQ:
+            raise IndexError("block out of range")
+        c, n = self.single, len(tokens)
+        keep = (c.K[:, pos:pos + n].copy(), c.V[:, pos:pos + n].copy())
+        logits, nxt = [], []
+        for i, t in enumerate(tokens):
+            lg = self._feed("single", t, pos + i).logits
+            logits.append(lg)
+            nxt.append(self.ref.draw(lg, self.sT, self.sP, xorshift(self.srng, i) if self.sT > 0 else 0)[0])
+        a = 0
+        while a + 1 < n and tokens[a + 1] == nxt[a]:
+            a += 1
+        c.K[:, pos + a + 1:pos + n], c.V[:, pos + a + 1:pos + n] = keep[0][:, a + 1:], keep[1][:, a + 1:]
+        c.hist = c.hist[:pos + a + 1]
+        c.node = self.ref.node(c.hist)
+        self.touched["single"] = (pos, pos + a + 1)
+        if self.sT > 0:
+            self.srng = xorshift(self.srng, a + 1)
+        return nxt, a, np.stack(logits)
+
+    def verify(self, tokens, pos, want_logits=True):
+        if self.sT > 0:
+            raise Refused(-5, "greedy only")
+        return self._verify(tokens, pos)
+
+    def verify_draw(self, tokens, pos, want_logits=True):
+        return self._verify(tokens, pos)
+
+    def generate_lookup(self, corpus, first, pos, n, ngram=2, draft_len=8):
+        if self.sT > 0:
+            raise Refused(-5, "greedy only")
+        return self.generate_greedy(first, pos, n), None
+
+    def generate_lookup_draw(self, corpus, first, pos, n, ngram=2, draft_len=8):
+        return self.generate_greedy(first, pos, n), None
+
+    def set_sampler(self, T, P, seed):
+        self.sT, self.sP, self.srng = T, P, seed
+
+    def sampler_rng_state(self):
+        return self.srng
+
+    def reset_kv(self):
+        self.single = _Cache(self.ref, SEQ)
+        self.touched["single"] = "all"
+
+    def read_state(self, kind):
+        return (self.single.K if kind == "key" else self.single.V).reshape(-1)
+
+    # -- the batched state
+    def batch_init(self, streams, ctx=0):
+        self.streams, self.ctx = streams, min(ctx, SEQ) if ctx else SEQ
+        self.slots = [_Cache(self.ref, self.ctx) for _ in range(streams)]
+        self.bT, self.brng, self.loop_rng = 0.0, [], {}
+        if self.leak != "prefix":
+            self.prefix = []
+        self.touched.update({s: "all" for s in range(streams)})
+
+    def batch_read_state(self, slot, kind):
+        return (self.slots[slot].K if kind == "key" else self.slots[slot].V).reshape(-1)
+
+    def set_batch_sampler(self, T, P, seeds):
+        self.bT, self.bP, self.brng = T, P, [int(s) for s in seeds][:self.streams]
+
+    def batch_reset_kv(self):
+        for s in range(self.streams):
+            old = self.slots[s]
+            self.slots[s] = _Cache(self.ref, self.ctx)
+            if self.leak == "length":
+                n = len(old.hist)
+                self.slots[s].K[:, :n], self.slots[s].V[:, :n] = old.K[:, :n], old.V[:, :n]
+            self.touched[s] = "all"
+
+    def _bdraw(self, slot, logits):
+        if not self.bT > 0:
+            return self.ref.draw(logits, 0.0, 1.0, 0)[0]
+        tok, self.brng[slot] = self.ref.draw(logits, self.bT, self.bP, self.brng[slot])
+        return tok
+
+    def _batch_args(self, tokens, pos):
+        if not 1 <= len(tokens) <= self.streams or any(p < 0 or p >= self.ctx for p in pos):
+            raise IndexError("stream or position out of range")
+        self._check_tokens(tokens)
+
+    def forward_batch(self, tokens, pos, want_logits=True):
+        self._batch_args(tokens, pos)
+        logits = [self._feed(i, t, p).logits for i, (t, p) in enumerate(zip(tokens, pos))]
+        return np.stack(logits), [self._bdraw(i, lg) for i, lg in enumerate(logits)]
+
+    def generate_greedy_batch(self, first, pos, steps):
+        self._batch_args(first, pos)
+        out = np.zeros((len(first), steps), dtype=np.int32)
+        for i, (tok, p) in enumerate(zip(first, pos)):
+            for k in range(steps):
+                tok = self._bdraw(i, self._feed(i, tok, p + k).logits)
+                out[i, k] = tok
+        return out
+
+    def _cols(self, slots, tokens, pos, keep, draw):
+        if not 1 <= len(slots) <= COLS_MAX or any(s < 0 or s >= self.streams for s in slots) or any(p >= self.ctx for p in pos):
+            raise IndexError("column out of range")
+        self._check_tokens(tokens)
+        logits, out, k = [], [], 0
+        for j, (s, t, p) in enumerate(zip(slots, tokens, pos)):
+            k = k + 1 if j and slots[j - 1] == s else 0
+            lg = self._feed(s, t, p).logits
+            logits.append(lg)
+            if draw and keep is not None and not keep[j]:
+                out.append(-1)
+            else:
+                out.append(self.ref.draw(lg, self.bT if draw else 0.0, self.bP, xorshift(self.brng[s], k) if draw else 0)[0])
+            if draw and (j + 1 == len(slots) or slots[j + 1] != s):
+                self.brng[s] = xorshift(self.brng[s], k + 1)
+        return np.stack(logits), out
+
+    def batch_step_cols(self, slots, tokens, pos, want_logits=True):
+        if self.bT > 0:
+            raise Refused(-5, "greedy only")
+        return self._cols(slots, tokens, pos, None, False)
+
+    def batch_step_cols_draw(self, slots, tokens, pos, keep=None, want_logits=True):
+        return self._cols(slots, tokens, pos, keep, self.bT > 0)
+
+    def batch_prefill_slots(self, slots, prompts, first):
+        if any(s < 0 or s >= self.streams for s in slots):
+            raise IndexError("slot out of range")
+        for p in prompts:
+            self._check_tokens(p)
+        for s, p, f in zip(slots, prompts, first):
+            for i, t in enumerate(p):
+                self._feed(s, t, f + i)
+            if self.bT > 0:
+                self.brng[s] = xorshift(self.brng[s], len(p))
+        return _q3().dense_pack([len(p) for p in prompts], DENSE_CAP)[1]
+
+    def _many(self, prompts, n_new, sampler, dense_min=0, stop=(), prefix=(), carry=False):
+        for p in prompts:
+            self._check_tokens(p)
+        if sampler is None and self.bT > 0:
+            raise Refused(-5, "greedy only")
+        n = len(prompts)
+        per = [None] * n
+        if sampler is not None:
+            T, P, seeds = [v if isinstance(v, (list, tuple)) else [v] * n for v in sampler]
+            per = [(T[r], P[r], seeds[r]) if T[r] > 0 else None for r in range(n)]
+        full = [list(prefix) + list(p) for p in prompts]
+        lens = [len(p) for p in prompts]
+        plan = None
+        if carry and self.leak == "sampler":
+            plan = many_plan(lens, n_new, self.streams)
+            for s, occ in plan["occupants"].items():
+                for r in occ:
+                    if per[r]:
+                        if s in self.loop_rng:
+                            per[r] = (per[r][0], per[r][1], self.loop_rng[s])
+                        self.loop_rng[s] = self.ref.generate(full[r], n_new[r], per[r])[1]
+        rows = [self.ref.generate(full[r], n_new[r], per[r])[0] for r in range(n)]
+        plan = plan or many_plan(lens, n_new, self.streams, dense_min, rows, stop)
+        out = [cut_at_stop(r, stop) for r in rows]
+        assert [len(r) for r in out] == list(plan["n_out"])
+        for s, occ in sorted(plan["occupants"].items()):
+            for r in occ:
+                for i, t in enumerate(full[r] + out[r][:-1]):
+                    self._feed(s, t, i)
+        return out, plan
+
+    def generate_many_greedy(self, prompts, n_new):
+        out, plan = self._many(prompts, n_new, None)
+        return out, plan["stats"]
+
+    def generate_many_sampled(self, prompts, n_new, T, P, seeds):
+        out, plan = self._many(prompts, n_new, (T, P, seeds), carry=True)
+        return out, plan["stats"]
+
+    def generate_many_dense(self, prompts, n_new, sampler=None, dense_min=64):
+        out, plan = self._many(prompts, n_new, sampler, dense_min)
+        live = sum(sum(b[2]) for b in plan["blocks"])
+        return out, plan["stats"], _q3().DenseStats(len(plan["blocks"]), live, sum(b[0] for b in plan["blocks"]) - live)
+
+    def generate_many_stop(self, prompts, n_new, stop_tokens, sampler=None):
+        out, plan = self._many(prompts, n_new, sampler, 0, tuple(stop_tokens))
+        return out, plan["stats"]
+
+    def generate_many_prefix(self, suffixes, n_new, stop_tokens=(), sampler=None):
+        if not self.prefix:
+            raise IndexError("no resident prefix")
+        out, plan = self._many(suffixes, n_new, sampler, 0, tuple(stop_tokens), self.prefix)
+        return out, plan["stats"]
+
+    def batch_copy_rows(self, src, dst, first, n):
+        if not 1 <= len(dst) <= self.streams - 1 or any(s < 0 or s >= self.streams or s == src for s in dst) or first + n > self.ctx:
+            raise IndexError("slot or rows out of range")
+        a = self.slots[src]
+        assert len(a.hist) >= first + n, "the model does not know the rows it copies"
+        for s in dst:
+            c = self.slots[s]
+            assert c.hist[:first] == a.hist[:first], "the model does not know what the copied rows stand behind"
+            c.K[:, first:first + n], c.V[:, first:first + n] = a.K[:, first:first + n], a.V[:, first:first + n]
+            c.hist = a.hist[:first + n]
+            c.node = self.ref.node(c.hist)
+            self._touch(s, first, first + n)
+
+    def batch_prefix_set(self, tokens):
+        self._check_tokens(tokens)
+        for i, t in enumerate(tokens):
+            self._feed(0, t, i)
+        self.prefix = list(tokens)
+
+    def batch_prefix_get(self):
+        return list(self.prefix)
+
+    def embed_many(self, prompts, normalize=True, out_dim=None, use_prefix=False):
+        import embed_ref
+        for p in prompts:
+            self._check_tokens(p)
+        if use_prefix and not self.prefix:
+            raise IndexError("no resident prefix")
+        full = [(self.prefix if use_prefix else []) + list(p) for p in prompts]
+        rows = []
+        for r, p in enumerate(full):
+            for i, t in enumerate(p):
+                n = self._feed(r % self.streams, t, i)
+            rows.append(n.x)
+        rows = np.stack(rows)
+        out = embed_ref.l2(rows, out_dim) if normalize else rows[:, :out_dim or DIM].copy()
+        waves = [[len(p) for p in prompts[i:i + self.streams]] for i in range(0, len(prompts), self.streams)]
+        st = [_q3().dense_pack(w, DENSE_CAP)[1] for w in waves]
+        return out, _q3().EmbedStats(len(waves), sum(s.blocks for s in st), sum(s.live_columns for s in st), sum(s.pad_columns for s in st))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# running a sequence
+# ---------------------------------------------------------------------------------------------------------------------------------
+def _requests(op, ref, prefix):
+    """prompts, n_new, the sampler triple or None, and the stop tokens of a loop op"""
+    reqs = [CAT[i] for i in op["reqs"]]
+    prompts = [toks((k, n)) for k, n, *_ in reqs]
+    n_new = [c[2] for c in reqs]
+    sampled = op["op"] == "generate_many_sampled" or op.get("sampled")
+    sampler = ([c[3] for c in reqs], [c[4] for c in reqs], [c[5] for c in reqs]) if sampled else None
+    stop = []
+    for i, j in op.get("stop_at", ()):
+        k, n, nn, T, P, seed = CAT[i]
+        row = ref.generate(tuple(list(prefix) + toks((k, n))), nn, (T, P, seed) if sampled and T > 0 else None)[0]
+        if row[j] not in stop:
+            stop.append(row[j])
+    return prompts, n_new, sampler, stop
+
+
+def call(e, op, ref, prefix=()):
+    """One op on an engine (a Transformer or a FakeEngine): what it returned, in a form that compares with ==/bitwise"""
+    k = op["op"]
+    if k in ("forward_batch", "forward_batch_s", "refused_batch"):
+        lg, am = e.forward_batch(op["tokens"], op["pos"])
+        return lg, am
+    if k in ("generate_greedy_batch", "generate_greedy_batch_s"):
+        return np.array(e.generate_greedy_batch(op["first"], op["pos"], op["steps"]))
+    if k in ("prefill_batched", "refused_prefill_batched"):
+        return e.prefill(toks(op["prompt"]), op["pos"], batched=True)
+    if k in ("verify", "verify_draw", "refused_verify"):
+        fn = e.verify_draw if k == "verify_draw" or op.get("draw") else e.verify
+        nxt, a, lg = fn(op["tokens"], op["pos"], want_logits=True)
+        return [int(t) for t in nxt], a, lg
+    if k in ("generate_lookup", "generate_lookup_draw"):
+        fn = e.generate_lookup if k == "generate_lookup" else e.generate_lookup_draw
+        out, st = fn(toks(op["corpus"]), op["first"], op["pos"], op["n"], op["ngram"], op["draft_len"])
+        if st is not None:
+            assert st.single_steps + st.verify_passes + st.accepted == op["n"] and st.accepted <= st.drafted, st
+        return [int(t) for t in out]
+    if k == "generate_greedy":
+        return [int(t) for t in e.generate_greedy(op["first"], op["pos"], op["n"])]
+    if k in ("forward", "refused_forward"):
+        return np.array(e.forward(op["token"], op["pos"]), copy=True)
+    if k in ("batch_step_cols", "refused_greedy_only") or (k == "refused_cols" and not op["draw"]):
+        return e.batch_step_cols(op["slots"], op["tokens"], op["pos"], want_logits=True)
+    if k in ("batch_step_cols_draw", "refused_cols"):
+        return e.batch_step_cols_draw(op["slots"], op["tokens"], op["pos"], keep=op.get("keep"), want_logits=True)
+    if k in MANY or k == "refused_stop":
+        prompts, n_new, sampler, stop = _requests(op, ref, prefix if k == "generate_many_prefix" else ())
+        if k == "generate_many_greedy":
+            return e.generate_many_greedy(prompts, n_new)
+        if k == "generate_many_sampled":
+            return e.generate_many_sampled(prompts, n_new, *sampler)
+        if k == "generate_many_dense":
+            return e.generate_many_dense(prompts, n_new, sampler, op["dense_min"])
+        if k == "generate_many_prefix":
+            return e.generate_many_prefix(prompts, n_new, stop, sampler)
+        if k == "refused_stop":
+            prompts[op["bad"]][-1] = VOCAB
+        return e.generate_many_stop(prompts, n_new, stop, sampler)
+    if k in ("batch_prefill_slots", "refused_dense"):
+        return e.batch_prefill_slots(op["slots"], [toks(p) for p in op["prompts"]], op["first"])
+    if k in ("batch_copy_rows", "refused_prefix"):
+        return e.batch_copy_rows(op["src"], op["dst"], op["first"], op["n"])
+    if k == "batch_prefix_set":
+        return e.batch_prefix_set(toks(op["prompt"]))
+    if k in ("embed_many", "embed_many_prefix", "refused_embed"):
+        prompts = [toks(CAT[i][:2]) for i in op["reqs"]]
+        if k == "refused_embed":
+            prompts[op["bad"]][0] = VOCAB
+        return e.embed_many(prompts, normalize=op["normalize"], out_dim=op["out_dim"], use_prefix=k == "embed_many_prefix")
+    if k in ("set_batch_sampler_on", "set_batch_sampler_off"):
+        return e.set_batch_sampler(op["T"], op["P"], op["seeds"])
+    if k == "set_sampler":
+        return e.set_sampler(op["T"], op["P"], op["seed"])
+    if k == "batch_reset_kv":
+        return e.batch_reset_kv()
+    if k == "reset_kv":
+        return e.reset_kv()
+    if k == "batch_init":
+        return e.batch_init(op["streams"], op["ctx"])
+    raise ValueError(k)
+
+
+def outcome(e, op, ref, prefix):
+    """call(), with a refusal turned into ("refused", code): IndexError is how the binding reports Q3_ERR_ARG"""
+    try:
+        return call(e, op, ref, prefix)
+    except IndexError:
+        return ("refused", -3)
+    except RuntimeError as err:
+        if getattr(err, "code", None) is None:
+            raise
+        return ("refused", err.code)
+
+
+def _bits(a):
+    a = np.asarray(a)
+    return a.view(np.int32) if a.dtype == np.float32 else a
+
+
+def same(a, b):
+    """equal: arrays bit for bit, everything else by =="""
+    if isinstance(a, np.ndarray) or isinstance(b, np.ndarray):
+        a, b = np.asarray(a), np.asarray(b)
+        return a.shape == b.shape and a.dtype == b.dtype and bool(np.array_equal(_bits(a), _bits(b)))
+    if isinstance(a, (list, tuple)) and isinstance(b, (list, tuple)):
+        return len(a) == len(b) and all(same(x, y) for x, y in zip(a, b))
+    return a == b
+
+
+def _read(e, cid, L, ctx, kvd):
+    if cid == "single":
+        return e.read_state("key").reshape(L, SEQ, kvd), e.read_state("value").reshape(L, SEQ, kvd)
+    return e.batch_read_state(cid, "key").reshape(L, ctx, kvd), e.batch_read_state(cid, "value").reshape(L, ctx, kvd)
+
+
+class _Lane:
+    """one engine under test, the clean model beside it and the last verified copy of every cache"""
+
+    def __init__(self, engine, ref):
+        self.e, self.ref, self.m = engine, ref, FakeEngine(ref)
+        self.snap = {"single": tuple(np.array(a, copy=True) for a in _read(engine, "single", ref.L, SEQ, ref.kvd))}
+
+    def step(self, op):
+        m, ref = self.m, self.ref
+        refusal = op["op"].startswith("refused")
+        m.touched = {}
+        prefix = list(m.prefix)
+        want = outcome(m, op, ref, prefix)
+        got = outcome(self.e, op, ref, prefix)
+        if refusal:
+            assert isinstance(want, tuple) and want[0] == "refused", f"the model accepts this call: {want!r}"
+            assert not m.touched
+        assert same(got, want), f"the call returned {_short(got)}, the reference gives {_short(want)}"
+        if op["op"] == "batch_init":
+            self.snap = {"single": self.snap["single"]}
+        for cid in ["single"] + list(range(m.streams)):
+            c = m._cache(cid)
+            cur = _read(self.e, cid, ref.L, c.ctx, ref.kvd)
+            t = m.touched.get(cid)
+            for what, now, model in (("key", cur[0], c.K), ("value", cur[1], c.V)):
+                if t == "all":
+                    assert same(now, model), f"{what} rows of cache {cid}: not what a cleared cache holds"
+                    continue
+                old = self.snap[cid][what == "value"]
+                if t is None:                        # not named by the op: one pass over the whole cache
+                    assert np.array_equal(now.reshape(-1).view(np.uint64), old.reshape(-1).view(np.uint64)), \
+                        f"{what} rows of cache {cid}, which the op does not name, changed" + _where(now, old, 0, 0)
+                    continue
+                lo, hi = t
+                assert same(now[:, :lo], old[:, :lo]) and same(now[:, hi:], old[:, hi:]), \
+                    f"{what} rows of cache {cid} outside {lo} .. {hi - 1} changed" + _where(now, old, lo, hi)
+                n = len(c.hist)
+                assert same(now[:, :n], model[:, :n]), f"{what} rows 0 .. {n - 1} of cache {cid} differ from the oracle's" + _where(now[:, :n], model[:, :n], 0, 0)
+            if t or cid not in self.snap:
+                self.snap[cid] = tuple(np.array(a, copy=True) for a in cur)
+        assert self.e.batch_prefix_get() == m.prefix, f"resident prefix of {len(self.e.batch_prefix_get())} tokens, the reference holds {len(m.prefix)}"
+        if m.srng is not None:
+            assert self.e.sampler_rng_state() == m.srng, "single-stream rng state"
+
+
+def _where(a, b, lo, hi):
+    bad = np.argwhere(_bits(np.ascontiguousarray(a)) != _bits(np.ascontiguousarray(b)))
+    bad = [x for x in bad if not lo <= x[1] < hi]
+    return f" (first at layer {bad[0][0]}, row {bad[0][1]}; {len({int(x[1]) for x in bad})} rows)" if bad else ""
+
+
+def _short(v):
+    s = repr(v)
+    return s if len(s) < 400 else s[:400] + " ..."
+
+
+def run(engines, ops, ref, seed=None):
+    """The ops on one engine, or on several engines interleaved op by op.  After every op: its outputs equal the reference's (logits
+    and embeddings bit for bit); every cache the op does not name, and every row of a named cache outside what the op writes, is
+    bit-unchanged against the copy taken before it; the rows a cache is known to hold equal the oracle's; the resident prefix and the
+    single-stream rng state are the reference's."""
+    lanes = [_Lane(e, ref) for e in (engines if isinstance(engines, (list, tuple)) else [engines])]
+    for i, op in enumerate(ops):
+        for j, lane in enumerate(lanes):
+            try:
+                lane.step(op)
+            except AssertionError as err:
+                raise AssertionError(f"seed {seed}, engine {j}, op {i} ({op['op']}): {err}\nops = {ops[:i + 1]!r}") from None
+    return lanes
