@@ -148,12 +148,6 @@ int cols_schedule_table(const size_t* prompt_len, const size_t* n_new, size_t n_
     return Q3_OK;
 }
 
-int cols_width_index(int n) {
-    int w = 0;
-    while (kColsWidths[w] < n) ++w;
-    return w;
-}
-
 // what every entry point of section 2e refuses.  draw: the names of section 2f, which hold for any batch sampler
 int cols_prepare(q3_engine* e, const char* who, bool draw = false) {
     if (!e) return fail(Q3_ERR_ARG, "null engine");
@@ -165,35 +159,9 @@ int cols_prepare(q3_engine* e, const char* who, bool draw = false) {
     return Q3_OK;
 }
 
-// the plan of width kColsWidths[wi], built on first use.  batch_build_plan leaves it in b->plan / b->graph: it moves to the
-// cache, and the shared plan is marked stale (the next decode / prefill / verify call rebuilds its own, as after any change of kind).
-// draw: the sampled plan of that width (cols_draw_alloc has run: its launches carry the buffers allocated there).
-int cols_plan_get(q3_engine* e, int wi, ColsPlan** out, bool draw = false) {
-    BatchCtx* b = e->batch;
-    ColsPlan& p = draw ? b->cols_plans_draw[wi] : b->cols_plans[wi];
-    if (p.plan.empty()) {
-        HIP_TRY(hipSetDevice(e->device));
-        const int rc = batch_build_plan(e, kColsWidths[wi], PlanKind::Cols, draw);
-        if (rc == Q3_OK) {
-            p.plan.swap(b->plan);
-            p.graph.swap(b->graph);
-            p.head = b->plan_head;
-        }
-        b->plan.clear();
-        b->graph.reset();
-        b->plan_streams = 0;
-        if (rc) return rc;
-    }
-    *out = &p;
-    return Q3_OK;
-}
-
-int cols_enqueue(q3_engine* e, const ColsPlan& p) {
-    if (p.graph) return p.graph.launch(e->stream);
-    for (const Launch& Ln : p.plan) launch(Ln, e->stream);
-    HIP_TRY(hipGetLastError());
-    return Q3_OK;
-}
+// the key of the column plan a pass of n live columns runs: the narrowest width that holds it.  draw: the sampled plan of that
+// width (cols_draw_alloc has run by the time it is built: its launches carry the buffers allocated there).
+PlanKey cols_key(int n, bool draw) { return PlanKey{PlanKind::Cols, kColsWidths[cols_width_index(n)], draw}; }
 
 template <class T>
 int cols_grow(T*& ptr, size_t& cap, size_t need) {
@@ -281,8 +249,8 @@ int cols_step(q3_engine* e, const int32_t* slots, const int32_t* tokens, const i
         }
     }
     if (draw && (rc = cols_draw_alloc(e))) return rc;
-    ColsPlan* plan;
-    if ((rc = cols_plan_get(e, cols_width_index(n_cols), &plan, draw))) return rc;
+    Plan* plan;
+    if ((rc = plan_get(e, cols_key(n_cols, draw), &plan))) return rc;
     HIP_TRY(hipSetDevice(e->device));
     ColsHost* h = b->h_cols;
     memset(&h->ctl, 0, sizeof(ColsCtl));
@@ -326,7 +294,7 @@ int cols_step(q3_engine* e, const int32_t* slots, const int32_t* tokens, const i
         HIP_TRY(hipMemcpyAsync(b->st, h->st, sizeof(State) * kColsMax, hipMemcpyHostToDevice, e->stream));
         HIP_TRY(hipMemcpyAsync(b->col_slot, h->slot, 4 * kColsMax, hipMemcpyHostToDevice, e->stream));
     }
-    if ((rc = cols_enqueue(e, *plan))) return rc;
+    if ((rc = plan_enqueue(e, *plan))) return rc;
     const size_t V = e->cfg.vocab_size;
     if (logits_out) HIP_TRY(hipMemcpyAsync(b->h_logits, b->logits, 4 * V * (size_t)n_cols, hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipMemcpyAsync(&h->ctl, b->cols_ctl, sizeof(ColsCtl), hipMemcpyDeviceToHost, e->stream));
@@ -383,15 +351,15 @@ int cols_job_run(q3_engine* e, ColsJob& job, bool draw, const ColsJobSampler& sm
     }
     // every plan and buffer the call needs exists before the first launch is enqueued
     if (draw && n_passes && (rc = cols_draw_alloc(e))) return rc;
-    ColsPlan* plans[kColsNW] = {nullptr};
+    Plan* plans[kColsNW] = {nullptr};
     for (int w = 0; w < kColsNW; ++w)
-        if (width_used[w] && (rc = cols_plan_get(e, w, &plans[w], draw))) return rc;
-    std::vector<const std::vector<Launch>*> wide_plans(job.steps.size(), nullptr);
+        if (width_used[w] && (rc = plan_get(e, cols_key(kColsWidths[w], draw), &plans[w]))) return rc;
+    std::vector<Plan*> wide_plans(job.steps.size(), nullptr);
     if (!job.runs.empty()) {
         if ((rc = dense_scratch_get(e))) return rc;
         if ((rc = dense_att_grow(e, job.max_end))) return rc;
         for (size_t i = 0; i < job.steps.size(); ++i)
-            if (job.steps[i].wide && (rc = dense_plan_get(e, job.steps[i].n, &wide_plans[i]))) return rc;
+            if (job.steps[i].wide && (rc = plan_get(e, PlanKey{PlanKind::SlotPrefill, job.steps[i].n, false}, &wide_plans[i]))) return rc;
     }
 
     HIP_TRY(hipSetDevice(e->device));
@@ -434,7 +402,7 @@ int cols_job_run(q3_engine* e, ColsJob& job, bool draw, const ColsJobSampler& sm
     for (size_t i = 0; i < job.steps.size(); ++i) {
         const ColsJobStep& s = job.steps[i];
         if (!s.wide) {
-            if ((rc = cols_enqueue(e, *plans[cols_width_index(job.ncols[p++])]))) return rc;
+            if ((rc = plan_enqueue(e, *plans[cols_width_index(job.ncols[p++])]))) return rc;
             continue;
         }
         if ((rc = dense_enqueue_block(e, *wide_plans[i], b->dense_runs + s.r0, (int)s.nr, s.n, b->cols_prompts))) return rc;

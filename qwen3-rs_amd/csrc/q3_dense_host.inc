@@ -125,7 +125,7 @@ int dense_att_grow(q3_engine* e, size_t max_end) {
     if (d.att_pf) (void)hipFree(d.att_pf);
     d.att_pf = nullptr;
     d.att_pf_stride = 0;
-    b->dense_plans.clear();
+    plans_drop(b, PlanDrop::Dense);
     const size_t bytes = 4 * (size_t)d.cap * (size_t)e->cfg.n_heads * (size_t)need;
     size_t free_b = 0, total_b = 0;
     (void)hipMemGetInfo(&free_b, &total_b);
@@ -137,46 +137,13 @@ int dense_att_grow(q3_engine* e, size_t max_end) {
     return Q3_OK;
 }
 
-// the plan of a block of n columns (32 < n <= the scratch's columns), built on first use and kept.  batch_build_plan works in
-// b->plan: the shared plan, its graph and its key step aside and come back, so the next decode call rebuilds nothing.
-int dense_plan_get(q3_engine* e, int n, const std::vector<Launch>** out) {
-    BatchCtx* b = e->batch;
-    if (n <= kColsMax || n > b->dense.cap)
-        return fail(Q3_ERR_ARG, "a dense block of %d columns does not fit the block scratch (33..%d columns)", n, b->dense.cap);
-    auto it = b->dense_plans.find(n);
-    if (it == b->dense_plans.end()) {
-        HIP_TRY(hipSetDevice(e->device));
-        std::vector<Launch> kept_plan;
-        Graph kept_graph;
-        kept_plan.swap(b->plan);
-        kept_graph.swap(b->graph);
-        const int kept_streams = b->plan_streams;
-        const PlanKind kept_kind = b->plan_kind;
-        const bool kept_draw = b->plan_draw;
-        const size_t kept_head = b->plan_head;
-        const int rc = batch_build_plan(e, n, PlanKind::SlotPrefill);
-        if (rc == Q3_OK) it = b->dense_plans.emplace(n, std::move(b->plan)).first;
-        b->plan.clear();
-        b->plan.swap(kept_plan);
-        b->graph.swap(kept_graph);
-        b->plan_streams = kept_streams;
-        b->plan_kind = kept_kind;
-        b->plan_draw = kept_draw;
-        b->plan_head = kept_head;
-        if (rc) return rc;
-    }
-    *out = &it->second;
-    return Q3_OK;
-}
-
-// one block: the states and the slot table of its n columns from the device run table, then the layers
-int dense_enqueue_block(q3_engine* e, const std::vector<Launch>& plan, const DenseRun* d_runs, int n_runs, int n, const int32_t* d_prompts) {
+// one block: the states and the slot table of its n columns from the device run table, then the layers (the kept
+// PlanKind::SlotPrefill plan of its width)
+int dense_enqueue_block(q3_engine* e, const Plan& plan, const DenseRun* d_runs, int n_runs, int n, const int32_t* d_prompts) {
     const BlockScratch& d = e->batch->dense;
     if (n > d.cap) return fail(Q3_ERR_ARG, "a dense block of %d columns does not fit the block scratch (%d columns)", n, d.cap);
     hipLaunchKernelGGL(k_dense_states, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e->stream, d.st, d.col_slot, d_runs, n_runs, d_prompts, n);
-    for (const Launch& Ln : plan) launch(Ln, e->stream);
-    HIP_TRY(hipGetLastError());
-    return Q3_OK;
+    return plan_enqueue(e, plan);
 }
 
 }  // namespace

@@ -3,7 +3,7 @@
 //
 // The prompts of a call go through the slots of the batched state in waves of max_streams, every wave packed into blocks by the
 // rule of q3_dense_pack.  A block runs the layers and nothing behind them: a wide one is the kept PlanKind::SlotPrefill plan of
-// its width (q3_dense_host.inc), one of 32 columns or fewer the launches [0, ColsPlan::head) of the kept column plan that holds
+// its width (q3_dense_host.inc), one of 32 columns or fewer the launches [0, Plan::head) of the kept column plan that holds
 // its live columns, with the states and the slot table written by k_dense_states as for a wide block.  Behind each block
 // k_embed_rows (q3_embed.h) turns the residuals of the prompts that end in it into their output rows.
 
@@ -95,15 +95,15 @@ int q3_embed_many(q3_engine* e, const int32_t* prompts, const size_t* prompt_len
     }
 
     // every plan and buffer the call needs exists before the first launch is enqueued; a shape the kernels refuse ends here
-    ColsPlan* plans[kColsNW] = {nullptr};
+    Plan* plans[kColsNW] = {nullptr};
     for (int w = 0; w < kColsNW; ++w)
-        if (width_used[w] && (rc = cols_plan_get(e, w, &plans[w]))) return rc;
-    std::vector<const std::vector<Launch>*> wide_plans(steps.size(), nullptr);
+        if (width_used[w] && (rc = plan_get(e, cols_key(kColsWidths[w], false), &plans[w]))) return rc;
+    std::vector<Plan*> wide_plans(steps.size(), nullptr);
     if (max_end) {
         if ((rc = dense_scratch_get(e))) return rc;
         if ((rc = dense_att_grow(e, max_end))) return rc;
         for (size_t i = 0; i < steps.size(); ++i)
-            if (steps[i].wide && (rc = dense_plan_get(e, steps[i].n, &wide_plans[i]))) return rc;
+            if (steps[i].wide && (rc = plan_get(e, PlanKey{PlanKind::SlotPrefill, steps[i].n, false}, &wide_plans[i]))) return rc;
     }
     HIP_TRY(hipSetDevice(e->device));
     const size_t n_out = n_requests * out_dim;
@@ -130,11 +130,9 @@ int q3_embed_many(q3_engine* e, const int32_t* prompts, const size_t* prompt_len
             // the layers of the column plan and nothing behind them: no classifier, no turn kernel.  The plan's columns past the
             // live ones repeat the last live column, as k_dense_states lays out the columns behind a block's last run
             const int wi = cols_width_index(s.n);
-            const ColsPlan& p = *plans[wi];
             hipLaunchKernelGGL(k_dense_states, dim3(1), dim3(256), 0, e->stream, b->st, b->col_slot, (const DenseRun*)(b->dense_runs + s.r0), (int)s.nr,
                                (const int32_t*)b->cols_prompts, kColsWidths[wi]);
-            for (size_t k = 0; k < p.head; ++k) launch(p.plan[k], e->stream);
-            HIP_TRY(hipGetLastError());
+            if ((rc = plan_enqueue(e, *plans[wi], plans[wi]->head))) return rc;
             x = b->x;
         }
         if (s.ng && (rc = launch_now(e->stream, k_embed_rows, dim3((unsigned)s.ng), dim3(kWG), smem, (const EmbedRow*)(b->embed_rows + s.g0), x,

@@ -221,6 +221,14 @@ struct Graph {
     Graph(const Graph&) = delete;
     Graph& operator=(const Graph&) = delete;
     ~Graph() { reset(); }
+    Graph(Graph&& o) noexcept { swap(o); }
+    Graph& operator=(Graph&& o) noexcept {
+        if (this != &o) {
+            reset();
+            swap(o);
+        }
+        return *this;
+    }
     explicit operator bool() const { return exec != nullptr; }
     void swap(Graph& o) {
         std::swap(graph, o.graph);
@@ -1888,6 +1896,7 @@ int q3_op_argmax(const float* logits, size_t n, int32_t* index, int device) {
 }  // extern "C"
 
 #include "q3_batch_host.inc"
+#include "q3_plan_host.inc"
 #include "q3_dense_host.inc"
 #include "q3_cols_host.inc"
 #include "q3_stop_host.inc"

@@ -80,9 +80,9 @@ int cols_generate_stop(q3_engine* e, const ColsRequests& rq, const int32_t* stop
         if (hs->done) break;
         if (hs->n_live < 1 || hs->n_live > kColsMax) return fail(Q3_ERR_INTERNAL, "the scheduler laid out a pass of %d columns", hs->n_live);
         if (++passes > pass_cap) return fail(Q3_ERR_INTERNAL, "the scheduler asks for more than %zu passes", pass_cap);
-        ColsPlan* plan;                                    // built on first use of a width: the stream is idle here
-        if ((rc = cols_plan_get(e, cols_width_index(hs->n_live), &plan, draw))) return rc;
-        if ((rc = cols_enqueue(e, *plan))) return rc;      // ends with the turn kernel: cursor == n_passes, it commits and sets nothing up
+        Plan* plan;                                        // built on first use of a width: the stream is idle here
+        if ((rc = plan_get(e, cols_key(hs->n_live, draw), &plan))) return rc;
+        if ((rc = plan_enqueue(e, *plan))) return rc;      // ends with the turn kernel: cursor == n_passes, it commits and sets nothing up
     }
     std::vector<int> got(n_requests);
     q3_cols_stats st;
