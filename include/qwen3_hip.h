@@ -694,6 +694,48 @@ typedef struct q3_embed_stats { uint64_t waves, blocks, live_columns, pad_column
 int q3_embed_many(q3_engine* e, const int32_t* prompts /* concatenated */, const size_t* prompt_len, size_t n_requests,
                   uint32_t flags, size_t out_dim /* 0 = dim */, float* out /* host, [n_requests][out_dim] */, q3_embed_stats* stats);
 
+/* ------------------------------------------------------------------------------------------------
+ * 2k. (behind 2j so that the earlier sections stay as they were.)  Choice logits: the classifier's scores of a few candidate tokens
+ * behind the last position of many prompts.  A reranker (the Qwen3-Reranker family: the same architecture, the same Q8 export, read
+ * out as softmax([logit("no"), logit("yes")])[1]), a multiple-choice evaluator or a yes/no classifier asks for k numbers of the
+ * vocab_size the classifier can produce.  The prompts go through the blocks of section 2j, which run no classifier, and behind each
+ * block one more kernel (k_choice_rows, csrc/q3_choice.h), one workgroup per (prompt that ENDS in the block, part of 32
+ * candidates), computes for the column x of the prompt's last token and a candidate id c, in f32 with no FMA contraction, exactly
+ *     ss   = (((-0.0 + x0*x0) + x1*x1) + ... )      over dim terms
+ *     f    = 1.0f / sqrtf(ss / (float)dim + 1e-6f)
+ *     y_i  = w_i * (f * x_i)                         w = the final norm's weight                    (RMSNorm::forward, layers.rs:109-119)
+ *   per group g of G = group_size consecutive i:
+ *     xs_g = max|y_i| / 127.0f;   xq_i = round-half-away(y_i / xs_g) as i8, IEEE divide, saturating, NaN -> 0;  xs_g == 0: xq_i = 0
+ *                                                                                                    (tensor.rs:91-119)
+ *     d_g  = sum over the group of wq[c][i] * xq_i   in int32, exact
+ *     t_g  = ((float)d_g * ws[c][g]) * xs_g          two roundings                                  (tensor.rs:59)
+ *   logit  = (((t_0 + t_1) + t_2) + ... )            groups ascending
+ * with wq / ws the classifier matrix: the token embedding table under shared_classifier, lm_head otherwise.  This is the arithmetic
+ * of the single-stream classifier launch, restated for k rows: the norm and the quantizer are that launch's own prologue code.  No
+ * other row of the matrix is read, no full-vocabulary pass runs, and nothing is normalised on the device: softmax over the
+ * candidates is the caller's (generation.choose does it on the host in float64).
+ * ------------------------------------------------------------------------------------------------ */
+#define Q3_CHOICE_PREFIX      2u   /* prompts are SUFFIXES behind the resident prefix of section 2i (the bit of Q3_EMBED_PREFIX) */
+#define Q3_CHOICE_PER_REQUEST 4u   /* cand holds one list of k ids per request, [n_requests][k]; otherwise one list [k] for all */
+#define Q3_CHOICE_MAX 256
+
+/* out[r][j] = the logit of token cand_r[j] behind the last token of request r, cand_r = cand + r k with Q3_CHOICE_PER_REQUEST and
+ * cand otherwise.  Prompts, prompt_len and the prefix flag are those of q3_embed_many.
+ * Standard: out[r][j] is bit-identical to logits[cand_r[j]] of q3_forward(t[n - 1], n - 1) after q3_prefill(t[0 .. n - 1)) on a fresh
+ * single-stream engine of the same context, t the request's n prompt tokens.  An id may appear more than once in a list and gives
+ * equal values.  The value does not depend on the slot, the neighbours in the block, the other candidates or the wave.
+ * Schedule, slots, execution and stats: exactly those of q3_embed_many (one walk serves both), with k_choice_rows in the place of
+ * k_embed_rows and one more upload, the candidate ids; ONE device-to-host copy of [n_requests][k] floats and ONE synchronisation.
+ * The uploaded ids and the device output rows belong to the batched state: grown on demand (the stream is waited for first),
+ * released with it.  No slot rng is touched.  THE SLOTS ARE OVERWRITTEN FROM SLOT 0 UP, as by q3_embed_many.
+ * Every failing call leaves the engine usable.
+ * Q3_ERR_ARG: everything q3_embed_many refuses (out_dim aside); a null cand; k == 0 or k > Q3_CHOICE_MAX; a candidate outside
+ * [0, vocab_size); unknown flag bits.
+ * Q3_ERR_UNSUPPORTED: what q3_embed_many refuses; dim > 4096, more than the norm prologue holds (refused before anything is
+ * enqueued). */
+int q3_choice_many(q3_engine* e, const int32_t* prompts /* concatenated */, const size_t* prompt_len, size_t n_requests,
+                   const int32_t* cand, size_t k, uint32_t flags, float* out /* host, [n_requests][k] */, q3_embed_stats* stats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -144,6 +144,10 @@ struct BatchCtx {
     EmbedRow* embed_rows = nullptr;
     float* embed_out = nullptr;
     size_t embed_rows_cap = 0, embed_out_cap = 0;
+    // choice logits (q3_choice_many): the uploaded candidate ids and the output rows [n_requests][k], grow-only
+    int32_t* choice_cand = nullptr;
+    float* choice_out = nullptr;
+    size_t choice_cand_cap = 0, choice_out_cap = 0;
     // packed-matrix directory
     struct PM { size_t q_off, s_off; int ntiles, ng; };
     std::vector<PM> m_qkv, m_wo, m_w13, m_w2;
@@ -166,7 +170,7 @@ void batch_free(q3_engine* e) {
                      b->spec_samp, b->spec_probs, b->spec_sp, b->spec_keys, b->col_slot, b->cols_ctl, b->cols_table, b->cols_ncols, b->cols_prompts,
                      b->cols_out, b->cols_draw, b->cols_step, b->cols_slot_samp, b->cols_aux, b->cols_temp, b->cols_topp, b->cols_seeds, b->cols_stop, b->cols_req,
                      b->dense.x, b->dense.q, b->dense.qn, b->dense.kraw, b->dense.xb, b->dense.hb, b->dense.xq_p, b->dense.xs_p, b->dense.st,
-                     b->dense.col_slot, b->dense.att_pf, b->dense_runs, b->prefix_store, b->embed_rows, b->embed_out};
+                     b->dense.col_slot, b->dense.att_pf, b->dense_runs, b->prefix_store, b->embed_rows, b->embed_out, b->choice_cand, b->choice_out};
     for (void* p : dptrs)
         if (p) (void)hipFree(p);
     if (b->h_st) (void)hipHostFree(b->h_st);

@@ -6,31 +6,30 @@
 // its width (q3_dense_host.inc), one of 32 columns or fewer the launches [0, Plan::head) of the kept column plan that holds
 // its live columns, with the states and the slot table written by k_dense_states as for a wide block.  Behind each block
 // k_embed_rows (q3_embed.h) turns the residuals of the prompts that end in it into their output rows.
+// The walk itself is embed_walk, which takes the launch behind a block as a callable: q3_choice_many (q3_choice_host.inc) runs the
+// same walk with k_choice_rows in that place.
 
 namespace {
 
 // n: the columns of a wide block, pads included; the live columns of a narrow one, which stand side by side from column 0
 struct EmbedStep { bool wide; int n; size_t r0, nr, g0, ng; };
 
-}  // namespace
-
-extern "C" {
-
-int q3_embed_many(q3_engine* e, const int32_t* prompts, const size_t* prompt_len, size_t n_requests, uint32_t flags, size_t out_dim, float* out,
-                  q3_embed_stats* stats) {
-    g_err[0] = 0;
-    if (stats) *stats = q3_embed_stats{0, 0, 0, 0};
-    if (!e) return fail(Q3_ERR_ARG, "null engine");
-    int rc;
-    if ((rc = cols_prepare(e, "q3_embed_many", true))) return rc;
+// The walk q3_embed_many and q3_choice_many (q3_choice_host.inc) share: the lengths become waves, blocks, runs and a row table; the
+// plans and the buffers of the walk are made; the prompts and tables go up, the prefix rows into the slots, and block after block is
+// enqueued, each followed by the caller's tail launch.  Nothing is copied back and nothing is waited for: that is the caller's.
+//   regrow: the caller's grow() re-allocates a buffer, so the stream is waited for first, as for the walk's own buffers
+//   grow(): called once, behind the walk's own allocations and in front of the first enqueue: the caller's buffers and uploads
+//   tail(rows, n_rows, x): the rows {column, request} of the prompts that end in the block just enqueued (n_rows > 0, device table)
+//                          and the block's residuals x[column][dim]: enqueue the kernel that reads them
+// st: the schedule's stats, valid when the walk returns Q3_OK.
+template <class Grow, class Tail>
+int embed_walk(q3_engine* e, const int32_t* prompts, const size_t* prompt_len, size_t n_requests, bool use_prefix, bool regrow, Grow grow, Tail tail,
+               q3_embed_stats& st) {
     BatchCtx* b = e->batch;
-    if (!prompts || !prompt_len || !out || n_requests == 0) return fail(Q3_ERR_ARG, "null or empty request list");
-    if (flags & ~(uint32_t)(Q3_EMBED_L2 | Q3_EMBED_PREFIX)) return fail(Q3_ERR_ARG, "unknown flag bits 0x%x", flags);
-    const size_t dim = (size_t)e->cfg.dim;
-    if (out_dim > dim) return fail(Q3_ERR_ARG, "out_dim %zu exceeds dim %zu", out_dim, dim);
-    if (out_dim == 0) out_dim = dim;
-    const size_t P = (flags & Q3_EMBED_PREFIX) ? b->prefix_n : 0;
-    if ((flags & Q3_EMBED_PREFIX) && P == 0) return fail(Q3_ERR_ARG, "no prefix is resident: call q3_batch_prefix_set first");
+    int rc;
+    st = q3_embed_stats{0, 0, 0, 0};
+    const size_t P = use_prefix ? b->prefix_n : 0;
+    if (use_prefix && P == 0) return fail(Q3_ERR_ARG, "no prefix is resident: call q3_batch_prefix_set first");
     if (n_requests > (size_t)INT32_MAX) return fail(Q3_ERR_ARG, "more than 2^31 requests in one call");
     std::vector<size_t> off(n_requests);
     size_t n_tok = 0;
@@ -52,7 +51,6 @@ int q3_embed_many(q3_engine* e, const int32_t* prompts, const size_t* prompt_len
     std::vector<DenseRun> runs;
     std::vector<EmbedRow> rows;
     std::vector<EmbedStep> steps;
-    q3_embed_stats st{0, 0, 0, 0};
     size_t max_end = 0;
     bool width_used[kColsNW] = {false};
     struct Piece { uint64_t block; int col0; size_t run, off; int len; };
@@ -106,20 +104,18 @@ int q3_embed_many(q3_engine* e, const int32_t* prompts, const size_t* prompt_len
             if (steps[i].wide && (rc = plan_get(e, PlanKey{PlanKind::SlotPrefill, steps[i].n, false}, &wide_plans[i]))) return rc;
     }
     HIP_TRY(hipSetDevice(e->device));
-    const size_t n_out = n_requests * out_dim;
-    if (n_tok > b->cols_prompts_cap || runs.size() > b->dense_runs_cap || rows.size() > b->embed_rows_cap || n_out > b->embed_out_cap)
+    if (n_tok > b->cols_prompts_cap || runs.size() > b->dense_runs_cap || rows.size() > b->embed_rows_cap || regrow)
         HIP_TRY(hipStreamSynchronize(e->stream));          // nothing in flight reads a buffer that is re-allocated
     if ((rc = cols_grow(b->cols_prompts, b->cols_prompts_cap, n_tok))) return rc;
     if ((rc = cols_grow(b->dense_runs, b->dense_runs_cap, runs.size()))) return rc;
     if ((rc = cols_grow(b->embed_rows, b->embed_rows_cap, rows.size()))) return rc;
-    if ((rc = cols_grow(b->embed_out, b->embed_out_cap, n_out))) return rc;
+    if ((rc = grow())) return rc;
 
-    // the call on the stream: three uploads, the prefix rows, block after block with its gather, one copy back
+    // the call on the stream: three uploads, the prefix rows, block after block with its tail
     HIP_TRY(hipMemcpyAsync(b->cols_prompts, prompts, 4 * n_tok, hipMemcpyHostToDevice, e->stream));
     HIP_TRY(hipMemcpyAsync(b->dense_runs, runs.data(), sizeof(DenseRun) * runs.size(), hipMemcpyHostToDevice, e->stream));
     HIP_TRY(hipMemcpyAsync(b->embed_rows, rows.data(), sizeof(EmbedRow) * rows.size(), hipMemcpyHostToDevice, e->stream));
     if (P && (rc = prefix_bcast_slots(e, (int)std::min(n_requests, S)))) return rc;
-    const size_t smem = 4 * (size_t)term_floats((int)dim);
     for (size_t i = 0; i < steps.size(); ++i) {
         const EmbedStep& s = steps[i];
         const float* x = nullptr;
@@ -135,11 +131,40 @@ int q3_embed_many(q3_engine* e, const int32_t* prompts, const size_t* prompt_len
             if ((rc = plan_enqueue(e, *plans[wi], plans[wi]->head))) return rc;
             x = b->x;
         }
-        if (s.ng && (rc = launch_now(e->stream, k_embed_rows, dim3((unsigned)s.ng), dim3(kWG), smem, (const EmbedRow*)(b->embed_rows + s.g0), x,
-                                     (const float*)e->rms_final, (int)dim, (int)out_dim, (flags & Q3_EMBED_L2) ? kEmbedL2 : 0u, b->embed_out)))
-            return rc;
+        if (s.ng && (rc = tail((const EmbedRow*)(b->embed_rows + s.g0), s.ng, x))) return rc;
     }
     HIP_TRY(hipGetLastError());
+    return Q3_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int q3_embed_many(q3_engine* e, const int32_t* prompts, const size_t* prompt_len, size_t n_requests, uint32_t flags, size_t out_dim, float* out,
+                  q3_embed_stats* stats) {
+    g_err[0] = 0;
+    if (stats) *stats = q3_embed_stats{0, 0, 0, 0};
+    if (!e) return fail(Q3_ERR_ARG, "null engine");
+    int rc;
+    if ((rc = cols_prepare(e, "q3_embed_many", true))) return rc;
+    BatchCtx* b = e->batch;
+    if (!prompts || !prompt_len || !out || n_requests == 0) return fail(Q3_ERR_ARG, "null or empty request list");
+    if (flags & ~(uint32_t)(Q3_EMBED_L2 | Q3_EMBED_PREFIX)) return fail(Q3_ERR_ARG, "unknown flag bits 0x%x", flags);
+    const size_t dim = (size_t)e->cfg.dim;
+    if (out_dim > dim) return fail(Q3_ERR_ARG, "out_dim %zu exceeds dim %zu", out_dim, dim);
+    if (out_dim == 0) out_dim = dim;
+    const size_t n_out = n_requests * out_dim;
+    const size_t smem = 4 * (size_t)term_floats((int)dim);
+    q3_embed_stats st;
+    if ((rc = embed_walk(e, prompts, prompt_len, n_requests, (flags & Q3_EMBED_PREFIX) != 0, n_out > b->embed_out_cap,
+                         [&] { return cols_grow(b->embed_out, b->embed_out_cap, n_out); },
+                         [&](const EmbedRow* rows, size_t n_rows, const float* x) {
+                             return launch_now(e->stream, k_embed_rows, dim3((unsigned)n_rows), dim3(kWG), smem, rows, x, (const float*)e->rms_final,
+                                               (int)dim, (int)out_dim, (flags & Q3_EMBED_L2) ? kEmbedL2 : 0u, b->embed_out);
+                         }, st)))
+        return rc;
+    // one copy back, one synchronisation
     HIP_TRY(hipMemcpyAsync(out, b->embed_out, 4 * n_out, hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     if (stats) *stats = st;

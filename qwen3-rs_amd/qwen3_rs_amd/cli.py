@@ -5,6 +5,8 @@
                                          [-i INPUT] [-y SYSTEM] [-r 0|1] [--lookup DRAFT_LEN] [--speculate DRAFT_LEN]
     python -m qwen3_rs_amd.cli embed <checkpoint> -i TEXT [-i TEXT ...] [--instruct TEXT] [--dim N] [--no-normalize]
                                      [--append-token ID] [-o out.npy] [--streams N] [--context N]
+    python -m qwen3_rs_amd.cli rerank <checkpoint> -q QUERY -d DOC [-d DOC ...] [--instruct TEXT] [--yes TEXT] [--no TEXT]
+                                      [--streams N] [-c N] [-o out.npy]
 
 `inference` follows generation.rs: `generate` echoes the prompt and decodes from its last token over a zero KV prefix
 (:9-48); `chat` renders the template, forwards every prompt token (one rng coin each) and decodes until BOS/EOS
@@ -18,6 +20,9 @@ token the sampler draws, so the output is again the same, byte for byte.
 token id to each (Qwen3-Embedding's tokenizer appends its end-of-text token; which id that is in a given .tokenizer is the
 user's to state), `--instruct` is tokenized once and becomes the prefix all inputs share.  One line per input: index, dimension,
 first 8 components; `-o` saves the matrix.
+`rerank` reads a checkpoint out as a reranker (q3_choice_many): one prompt per -d document from the Qwen3-Reranker template
+(generation.RERANK_TEMPLATE), the logits of the `--no` and `--yes` tokens behind it, softmax over the two.  One line per document:
+index and P(yes); `-o` saves the scores.
 """
 from __future__ import annotations
 
@@ -183,6 +188,23 @@ def run_embed(a) -> int:
     return 0
 
 
+def run_rerank(a) -> int:
+    import numpy as np
+    from .generation import rerank
+    b = TransformerBuilder(a.checkpoint)
+    if a.context:
+        b = b.with_ctx_length(a.context)
+    with b.build() as t:
+        tok = Tokenizer(a.checkpoint, t.get_config().vocab_size, False)
+        t.batch_init(max(1, min(a.streams, 32, len(a.document))))
+        scores = rerank(t, tok, a.query, a.document, instruction=a.instruct, yes=a.yes, no=a.no)
+    for r, v in enumerate(scores):
+        print(r, f"{v:.6f}")
+    if a.output:
+        np.save(a.output, scores)
+    return 0
+
+
 def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog="qwen3", description="Qwen3 CLI on the MI355X engine: export and inference")
     sub = ap.add_subparsers(dest="cmd")
@@ -214,6 +236,16 @@ def build_parser() -> argparse.ArgumentParser:
     em.add_argument("-o", "--output", default=None, metavar="out.npy", help="save the matrix [inputs, dim]")
     em.add_argument("--streams", type=int, default=8, metavar="N", help="slots of the batched state (1..32)")
     em.add_argument("-c", "--context", type=int, default=None)
+    rr = sub.add_parser("rerank", help="P(yes) of documents for a query (a Qwen3-Reranker checkpoint)")
+    rr.add_argument("checkpoint")
+    rr.add_argument("-q", "--query", required=True, metavar="QUERY")
+    rr.add_argument("-d", "--document", action="append", required=True, metavar="DOC", help="a document to score; repeat for more")
+    rr.add_argument("--instruct", default=None, metavar="TEXT", help="the task instruction (default: the model card's web-search one)")
+    rr.add_argument("--yes", default="yes", metavar="TEXT", help="the answer word that counts as relevant: one token")
+    rr.add_argument("--no", default="no", metavar="TEXT", help="the other answer word: one token")
+    rr.add_argument("--streams", type=int, default=8, metavar="N", help="slots of the batched state (1..32)")
+    rr.add_argument("-c", "--context", type=int, default=None)
+    rr.add_argument("-o", "--output", default=None, metavar="out.npy", help="save the scores [documents]")
     return ap
 
 
@@ -266,6 +298,13 @@ def main(argv=None) -> int:
         from .engine import Q3Error
         try:
             return run_embed(a)
+        except (Q3Error, IndexError, ValueError) as err:
+            print(f"Error: {err}", file=sys.stderr)
+            return 1
+    if a.cmd == "rerank":
+        from .engine import Q3Error
+        try:
+            return run_rerank(a)
         except (Q3Error, IndexError, ValueError) as err:
             print(f"Error: {err}", file=sys.stderr)
             return 1

@@ -32,11 +32,14 @@ EXPORTED_SYMBOLS = [
     "q3_generate_many_stop", "q3_cols_schedule_stop",
     "q3_batch_copy_rows", "q3_batch_prefix_set", "q3_batch_prefix_get", "q3_generate_many_prefix",
     "q3_embed_many",
+    "q3_choice_many",
 ]
 VERIFY_MAX = 32          # Q3_VERIFY_MAX
 COLS_MAX = 32            # Q3_COLS_MAX
 STOP_MAX = 8             # Q3_STOP_MAX
 EMBED_L2, EMBED_PREFIX = 1, 2   # Q3_EMBED_L2, Q3_EMBED_PREFIX
+CHOICE_PREFIX, CHOICE_PER_REQUEST = 2, 4   # Q3_CHOICE_PREFIX, Q3_CHOICE_PER_REQUEST
+CHOICE_MAX = 256         # Q3_CHOICE_MAX
 
 
 class Q3Error(RuntimeError):
@@ -243,6 +246,7 @@ def _bind(path: str) -> C.CDLL:
     L.q3_batch_prefix_get.argtypes = [C.c_void_p, szp, i32p, sz]
     L.q3_generate_many_prefix.argtypes = L.q3_generate_many_stop.argtypes
     L.q3_embed_many.argtypes = [C.c_void_p, i32p, szp, sz, C.c_uint32, sz, fp, C.POINTER(_EmbedStats)]
+    L.q3_choice_many.argtypes = [C.c_void_p, i32p, szp, sz, i32p, sz, C.c_uint32, fp, C.POINTER(_EmbedStats)]
     L.q3_profile.argtypes = [C.c_void_p, sz, sz, C.c_int, fp, C.POINTER(C.c_int32), C.c_int]
     L.q3_profile_name.argtypes = [C.c_int]
     L.q3_profile_name.restype = C.c_char_p
@@ -708,6 +712,34 @@ class Transformer:
         flags = (EMBED_L2 if normalize else 0) | (EMBED_PREFIX if use_prefix else 0)
         self._batch_rc(self._lib.q3_embed_many(self._h, _i32_array(flat), _size_array([len(p) for p in prompts]), n, flags, od,
                                                out.ctypes.data_as(C.POINTER(C.c_float)), C.byref(st)))
+        return out, EmbedStats(st.waves, st.blocks, st.live_columns, st.pad_columns)
+
+    # ---- choice logits (include/qwen3_hip.h section 2k)
+    def choice_many(self, prompts, candidates, use_prefix: bool = False):
+        """The logits of a few candidate tokens behind the last token of many prompts (q3_choice_many): out[r][j] is, bit for bit,
+        forward(prompts[r][-1], len - 1)[candidates_r[j]] behind a prefill of the rest, with no classifier pass over the vocabulary.
+        candidates: one list of token ids for every prompt, or one list per prompt, all of the same length k (1 .. CHOICE_MAX).
+        The prompts go through the slots of batch_init as in embed_many, from slot 0 up -- whatever the slots held is overwritten.
+        use_prefix: the prompts are suffixes behind the resident prefix of batch_prefix_set.
+        Returns (float32 array [len(prompts), k], EmbedStats)."""
+        n = len(prompts)
+        cands = list(candidates)
+        per_request = len(cands) > 0 and all(hasattr(c, "__len__") for c in cands)
+        if per_request:
+            if len(cands) != n:
+                raise IndexError("one candidate list per prompt")
+            k = len(cands[0])
+            if any(len(c) != k for c in cands):
+                raise IndexError("the candidate lists differ in length")
+            ids = [int(t) for c in cands for t in c]
+        else:
+            k, ids = len(cands), [int(t) for t in cands]
+        flat = [int(t) for p in prompts for t in p]
+        out = np.zeros((n, k), dtype=np.float32)
+        st = _EmbedStats()
+        flags = (CHOICE_PREFIX if use_prefix else 0) | (CHOICE_PER_REQUEST if per_request else 0)
+        self._batch_rc(self._lib.q3_choice_many(self._h, _i32_array(flat), _size_array([len(p) for p in prompts]), n, _i32_array(ids), k, flags,
+                                                out.ctypes.data_as(C.POINTER(C.c_float)), C.byref(st)))
         return out, EmbedStats(st.waves, st.blocks, st.live_columns, st.pad_columns)
 
     def set_batch_sampler(self, temperature: float, topp: float, rng_seeds):

@@ -224,6 +224,12 @@ def embed(transformer, prompts: Sequence[Sequence[int]], normalize: bool = True,
     of `prompts` (common_prefix_len), None for no prefix.  Returns a float32 array [len(prompts), out_dim]."""
     if any(len(p) == 0 for p in prompts):
         raise ValueError("Please provide a prompt")
+    prompts, use_prefix = _split_prefix(transformer, prompts, shared_prefix)
+    return transformer.embed_many(prompts, normalize=normalize, out_dim=out_dim, use_prefix=use_prefix)[0]
+
+
+def _split_prefix(transformer, prompts, shared_prefix):
+    """shared_prefix of embed / choose: (the prompts behind the prefix, whether one is in use); the prefix is made resident"""
     prefix: List[int] = []
     if shared_prefix is True:
         k = common_prefix_len(prompts)
@@ -232,7 +238,60 @@ def embed(transformer, prompts: Sequence[Sequence[int]], normalize: bool = True,
         prefix = [int(t) for t in shared_prefix]
     if prefix and transformer.batch_prefix_get() != prefix:
         transformer.batch_prefix_set(prefix)
-    return transformer.embed_many(prompts, normalize=normalize, out_dim=out_dim, use_prefix=bool(prefix))[0]
+    return prompts, bool(prefix)
+
+
+def normalise_logits(logits: np.ndarray, output: str) -> np.ndarray:
+    """softmax / log_softmax over the last axis of float32 logits, in float64: the row maximum is subtracted, then exp, the sum and
+    log.  Nothing is special-cased: a NaN makes its whole row NaN, and a row whose maximum is not finite (all -inf, or a +inf)
+    gives NaN as numpy's -inf - -inf and inf - inf do; -inf beside finite logits gives probability 0 and log-probability -inf."""
+    z = np.asarray(logits, dtype=np.float32).astype(np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        z = z - z.max(axis=-1, keepdims=True)
+        ez = np.exp(z)
+        tot = ez.sum(axis=-1, keepdims=True)
+        return ez / tot if output == "softmax" else z - np.log(tot)
+
+
+def choose(transformer, prompts: Sequence[Sequence[int]], candidates, shared_prefix=None, output: str = "logits"):
+    """The scores of a few candidate tokens behind each prompt's last token: what a reranker, a multiple-choice evaluator or a yes/no
+    classifier reads.  candidates: one list of token ids for all prompts, or one list per prompt, all of one length k.  The logits
+    are bit for bit those of forward() (Transformer.choice_many: the prompts go through the slots of Transformer.batch_init in
+    dense blocks, no classifier pass over the vocabulary runs, the slots' contents are overwritten).  shared_prefix as in embed.
+    output: "logits" returns the float32 array [len(prompts), k]; "softmax" and "log_softmax" normalise over the k candidates
+    only, on the host, and return float64 (normalise_logits, which also says what NaN and infinite logits give)."""
+    if output not in ("logits", "softmax", "log_softmax"):
+        raise ValueError(f"unknown output {output!r}")
+    if any(len(p) == 0 for p in prompts):
+        raise ValueError("Please provide a prompt")
+    prompts, use_prefix = _split_prefix(transformer, prompts, shared_prefix)
+    logits = transformer.choice_many(prompts, candidates, use_prefix=use_prefix)[0]
+    return logits if output == "logits" else normalise_logits(logits, output)
+
+
+# The prompt of the Qwen3-Reranker family, as its model card gives it.  Written from memory: no such checkpoint or card was at hand
+# when this was written, so the wording is unverified (DESIGN.md section 4.11).
+RERANK_INSTRUCTION = "Given a web search query, retrieve relevant passages that answer the query"
+RERANK_TEMPLATE = ("<|im_start|>system\nJudge whether the Document meets the requirements based on the Query and the Instruct provided. "
+                   "Note that the answer can only be \"yes\" or \"no\".<|im_end|>\n"
+                   "<|im_start|>user\n<Instruct>: {instruction}\n<Query>: {query}\n<Document>: {document}<|im_end|>\n"
+                   "<|im_start|>assistant\n<think>\n\n</think>\n\n")
+
+
+def rerank(transformer, tokenizer, query: str, documents: Sequence[str], instruction: Optional[str] = None, yes: str = "yes", no: str = "no"):
+    """P(yes) of every document for the query, the way a Qwen3-Reranker checkpoint is read out: one prompt per document from
+    RERANK_TEMPLATE, each tokenized as a whole string; the logits of the tokens `no` and `yes` behind it (choose, the prompts'
+    longest common token prefix resident and computed once); softmax over the two.  `yes` and `no` must each be exactly one token
+    of the tokenizer.  Returns a float64 array [len(documents)]."""
+    ids = []
+    for word in (no, yes):
+        enc = tokenizer.encode(word)
+        if len(enc) != 1:
+            raise ValueError(f"{word!r} is {len(enc)} tokens in this tokenizer: the answer words must be one token each")
+        ids.append(int(enc[0]))
+    instruction = RERANK_INSTRUCTION if instruction is None else instruction
+    prompts = [tokenizer.encode(RERANK_TEMPLATE.format(instruction=instruction, query=query, document=d)) for d in documents]
+    return choose(transformer, prompts, ids, shared_prefix=True, output="softmax")[:, 1]
 
 
 def chat_turn(transformer, prompt_tokens: Sequence[int], pos: int, max_new_tokens: int,
