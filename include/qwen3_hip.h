@@ -736,6 +736,62 @@ int q3_embed_many(q3_engine* e, const int32_t* prompts /* concatenated */, const
 int q3_choice_many(q3_engine* e, const int32_t* prompts /* concatenated */, const size_t* prompt_len, size_t n_requests,
                    const int32_t* cand, size_t k, uint32_t flags, float* out /* host, [n_requests][k] */, q3_embed_stats* stats);
 
+/* ------------------------------------------------------------------------------------------------
+ * 2l. (behind 2k so that the earlier sections stay as they were.)  Scores: what the model says about every next token of many
+ * given sequences -- perplexity, the log-likelihood of a continuation of several tokens, "is this continuation the greedy one",
+ * filtering by loss.  For position i of a sequence t that needs log P(t[i+1] | t[0..i]): a log-softmax over the whole vocabulary
+ * at every position.  The prompts go through the blocks of section 2j.  Behind each block its SCORED columns are copied, up to 32
+ * at a time, into the 32-column scratch (k_score_gather, csrc/q3_score.h) and run through the classifier of a kept column plan of
+ * section 2e -- the final norm, the quantizer and the int8 matrix-core launch: for all V = vocab_size rows c the logit l[c] of
+ * section 2k, bit-identical to q3_forward's -- and two more kernels reduce each row l[0 .. V) on the device to a record, in f32
+ * with no FMA contraction:
+ *     target = l[t[i+1]]
+ *     max    = fmaxf(... fmaxf(fmaxf(-inf, l[0]), l[1]) ..., l[V-1])                                    (layers.rs:496)
+ *     sum    = ((-0.0f + expf(l[0] - max)) + expf(l[1] - max)) + ...          in index order, V terms   (layers.rs:497-503)
+ *     argmax = the last index of the maximum in total order (-0.0 below +0.0)                          (sampler.rs:57-59)
+ * sum is the denominator Sampler::sample forms at temperature 1 (k_score_exp spreads the exps over the chip; k_score_sum walks them
+ * with the verified sequential sum of the device sampler).  max and argmax are read from the keys the classifier launch leaves per
+ * workgroup.  Nothing else is computed on the device: there is no logf; log P = (target - max) - log(sum) is the caller's
+ * (generation.logprobs_of forms it in float64).  No logit leaves the GPU, and none becomes an address.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct q3_score_rec { float target; float max; float sum; int32_t argmax; } q3_score_rec;
+typedef struct q3_score_stats { uint64_t waves, blocks, live_columns, pad_columns, chunks, scored; } q3_score_stats;
+#define Q3_SCORE_PREFIX 2u   /* prompts are SUFFIXES behind the resident prefix of section 2i (the bit of Q3_EMBED_PREFIX) */
+
+/* Request r of n = prompt_len[r] tokens t gets n - score_from[r] records, the requests' records concatenated in out.  Record j
+ * describes the logits behind token t[i], i = score_from[r] - 1 + j, with target t[i + 1].  1 <= score_from[r] <= n; score_from NULL
+ * means 1 for every request (every position but the last is scored).  score_from[r] == n, and so every one-token request, gives no
+ * record.  With Q3_SCORE_PREFIX the tokens are suffixes behind the resident prefix, as for q3_embed_many; the first suffix token is
+ * never a target.  out may be NULL only if the call produces no record.
+ * Standard: target and sum are bit-identical to the numbers above formed on the host, expf glibc's, from the logits of
+ * q3_forward(t[i], i) after q3_prefill(t[0 .. i)) on a fresh single-stream engine of the same context; argmax is equal; max is equal
+ * as a float value (a maximum that is a zero may carry either sign; sum does not depend on which).  A row that holds a NaN logit is
+ * outside the standard; the call does not fault on it.  The values do not depend on the slot, the wave, the neighbours, the chunk a
+ * column lands in or score_from.
+ * Schedule: waves, blocks, runs, slots and the prefix copy are exactly those of q3_embed_many.  Behind each block, the block's scored
+ * columns -- live columns whose token has a successor in its request at or behind score_from -- are cut in column order into chunks
+ * of up to 32; a chunk of m columns runs k_score_gather (not for a block of 32 columns or fewer whose column j is the chunk's row
+ * j: it stands in the scratch already), the two classifier launches of the column plan of the narrowest width that holds m (columns
+ * m and up repeat the last one), k_score_exp and k_score_sum.  Pads and unscored columns cost no classifier work; a block with no
+ * scored column launches nothing behind its layers.  stats (may be NULL): q3_embed_stats' four, chunks = the sum over the blocks of
+ * ceil(scored columns / 32), scored = the number of records: pure functions of the lengths and score_from (q3_score_pack).
+ * Execution: everything on the engine's stream, then ONE device-to-host copy of the records and ONE synchronisation.  The table of
+ * scored columns, the records and the exps of a chunk belong to the batched state: grown on demand (the stream is waited for
+ * first), released with it.  No slot rng is touched; no kept plan or graph is rebuilt.  THE SLOTS ARE OVERWRITTEN FROM SLOT 0 UP, as
+ * by q3_embed_many.  Every failing call leaves the engine usable.
+ * Q3_ERR_ARG: everything q3_embed_many refuses (out_dim aside; a null engine before anything touches the GPU); a score_from entry
+ * outside [1, prompt_len[r]]; a null out with records to write; unknown flag bits.
+ * Q3_ERR_UNSUPPORTED: what q3_embed_many refuses (a Q3_FLAG_FAST engine). */
+int q3_score_many(q3_engine* e, const int32_t* prompts /* concatenated */, const size_t* prompt_len, size_t n_requests,
+                  const size_t* score_from /* [n_requests] or NULL = all 1 */, uint32_t flags,
+                  q3_score_rec* out /* host, concatenated */, q3_score_stats* stats);
+
+/* The schedule of q3_score_many without an engine or a GPU: stats as that call fills them for max_streams slots and blocks of
+ * block_cap columns (q3_dense_pack's rule per wave).  Q3_ERR_ARG: what q3_score_many refuses of the lengths and score_from;
+ * max_streams outside 1..32; a block_cap q3_dense_pack refuses. */
+int q3_score_pack(const size_t* prompt_len, size_t n_requests, const size_t* score_from /* or NULL */, int max_streams, int block_cap,
+                  q3_score_stats* stats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -148,6 +148,12 @@ struct BatchCtx {
     int32_t* choice_cand = nullptr;
     float* choice_out = nullptr;
     size_t choice_cand_cap = 0, choice_out_cap = 0;
+    // scores (q3_score_many): the table of a call's scored columns, its records, and the exps of one chunk [32][vocab_size up to a
+    // multiple of 4], grow-only
+    ScoreRow* score_rows = nullptr;
+    ScoreRec* score_out = nullptr;
+    float* score_probs = nullptr;
+    size_t score_rows_cap = 0, score_out_cap = 0, score_probs_cap = 0;
     // packed-matrix directory
     struct PM { size_t q_off, s_off; int ntiles, ng; };
     std::vector<PM> m_qkv, m_wo, m_w13, m_w2;
@@ -159,6 +165,7 @@ namespace {
 // q3_plan_host.inc
 int plan_get(q3_engine* e, PlanKey key, Plan** out);
 int plan_enqueue(q3_engine* e, const Plan& p, size_t n_launches = SIZE_MAX);
+int plan_enqueue_range(q3_engine* e, const Plan& p, size_t first, size_t end);
 enum class PlanDrop { Step, Dense };
 void plans_drop(BatchCtx* b, PlanDrop what);
 
@@ -170,7 +177,8 @@ void batch_free(q3_engine* e) {
                      b->spec_samp, b->spec_probs, b->spec_sp, b->spec_keys, b->col_slot, b->cols_ctl, b->cols_table, b->cols_ncols, b->cols_prompts,
                      b->cols_out, b->cols_draw, b->cols_step, b->cols_slot_samp, b->cols_aux, b->cols_temp, b->cols_topp, b->cols_seeds, b->cols_stop, b->cols_req,
                      b->dense.x, b->dense.q, b->dense.qn, b->dense.kraw, b->dense.xb, b->dense.hb, b->dense.xq_p, b->dense.xs_p, b->dense.st,
-                     b->dense.col_slot, b->dense.att_pf, b->dense_runs, b->prefix_store, b->embed_rows, b->embed_out, b->choice_cand, b->choice_out};
+                     b->dense.col_slot, b->dense.att_pf, b->dense_runs, b->prefix_store, b->embed_rows, b->embed_out, b->choice_cand, b->choice_out,
+                     b->score_rows, b->score_out, b->score_probs};
     for (void* p : dptrs)
         if (p) (void)hipFree(p);
     if (b->h_st) (void)hipHostFree(b->h_st);

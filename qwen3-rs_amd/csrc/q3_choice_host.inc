@@ -40,7 +40,7 @@ int q3_choice_many(q3_engine* e, const int32_t* prompts, const size_t* prompt_le
     const unsigned parts = (unsigned)((k + kChoicePart - 1) / kChoicePart);
     q3_embed_stats st;
     if ((rc = embed_walk(e, prompts, prompt_len, n_requests, (flags & Q3_CHOICE_PREFIX) != 0, n_cand > b->choice_cand_cap || n_out > b->choice_out_cap,
-                         [&] {
+                         [&](const std::vector<DenseRun>&, const std::vector<EmbedStep>&) {
                              int rc2;
                              if ((rc2 = cols_grow(b->choice_cand, b->choice_cand_cap, n_cand))) return rc2;
                              if ((rc2 = cols_grow(b->choice_out, b->choice_out_cap, n_out))) return rc2;
@@ -49,7 +49,7 @@ int q3_choice_many(q3_engine* e, const int32_t* prompts, const size_t* prompt_le
                              a.out = b->choice_out;
                              return (int)Q3_OK;
                          },
-                         [&](const EmbedRow* rows, size_t n_rows, const float* x) {
+                         [&](const EmbedRow* rows, size_t n_rows, const float* x, size_t) {
                              a.rows = rows;
                              a.x = x;
                              return launch_now(e->stream, k_choice_rows, dim3((unsigned)n_rows, parts), dim3(kWG), smem, a);

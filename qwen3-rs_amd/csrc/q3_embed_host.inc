@@ -7,7 +7,7 @@
 // its live columns, with the states and the slot table written by k_dense_states as for a wide block.  Behind each block
 // k_embed_rows (q3_embed.h) turns the residuals of the prompts that end in it into their output rows.
 // The walk itself is embed_walk, which takes the launch behind a block as a callable: q3_choice_many (q3_choice_host.inc) runs the
-// same walk with k_choice_rows in that place.
+// same walk with k_choice_rows in that place, q3_score_many (q3_score_host.inc) with the classifier chunks of a block's scored columns.
 
 namespace {
 
@@ -18,13 +18,16 @@ struct EmbedStep { bool wide; int n; size_t r0, nr, g0, ng; };
 // plans and the buffers of the walk are made; the prompts and tables go up, the prefix rows into the slots, and block after block is
 // enqueued, each followed by the caller's tail launch.  Nothing is copied back and nothing is waited for: that is the caller's.
 //   regrow: the caller's grow() re-allocates a buffer, so the stream is waited for first, as for the walk's own buffers
-//   grow(): called once, behind the walk's own allocations and in front of the first enqueue: the caller's buffers and uploads
-//   tail(rows, n_rows, x): the rows {column, request} of the prompts that end in the block just enqueued (n_rows > 0, device table)
-//                          and the block's residuals x[column][dim]: enqueue the kernel that reads them
+//   grow(runs, steps): called once, behind the walk's own allocations and in front of the first enqueue: the caller's buffers and
+//                          uploads.  It sees the schedule: steps[i] is block i, runs[steps[i].r0 .. + steps[i].nr) ALL of its runs in
+//                          column order (q3_score_many, q3_score_host.inc, makes its table of scored columns from them)
+//   tail(rows, n_rows, x, i): the rows {column, request} of the prompts that end in block i, just enqueued (device table), and the
+//                          block's residuals x[column][dim]: enqueue the kernel that reads them.  Called for a block in which a
+//                          prompt ends (n_rows > 0); with every_block, for every block
 // st: the schedule's stats, valid when the walk returns Q3_OK.
 template <class Grow, class Tail>
 int embed_walk(q3_engine* e, const int32_t* prompts, const size_t* prompt_len, size_t n_requests, bool use_prefix, bool regrow, Grow grow, Tail tail,
-               q3_embed_stats& st) {
+               q3_embed_stats& st, bool every_block = false) {
     BatchCtx* b = e->batch;
     int rc;
     st = q3_embed_stats{0, 0, 0, 0};
@@ -109,7 +112,7 @@ int embed_walk(q3_engine* e, const int32_t* prompts, const size_t* prompt_len, s
     if ((rc = cols_grow(b->cols_prompts, b->cols_prompts_cap, n_tok))) return rc;
     if ((rc = cols_grow(b->dense_runs, b->dense_runs_cap, runs.size()))) return rc;
     if ((rc = cols_grow(b->embed_rows, b->embed_rows_cap, rows.size()))) return rc;
-    if ((rc = grow())) return rc;
+    if ((rc = grow(runs, steps))) return rc;
 
     // the call on the stream: three uploads, the prefix rows, block after block with its tail
     HIP_TRY(hipMemcpyAsync(b->cols_prompts, prompts, 4 * n_tok, hipMemcpyHostToDevice, e->stream));
@@ -131,7 +134,7 @@ int embed_walk(q3_engine* e, const int32_t* prompts, const size_t* prompt_len, s
             if ((rc = plan_enqueue(e, *plans[wi], plans[wi]->head))) return rc;
             x = b->x;
         }
-        if (s.ng && (rc = tail((const EmbedRow*)(b->embed_rows + s.g0), s.ng, x))) return rc;
+        if ((s.ng || every_block) && (rc = tail((const EmbedRow*)(b->embed_rows + s.g0), s.ng, x, i))) return rc;
     }
     HIP_TRY(hipGetLastError());
     return Q3_OK;
@@ -158,8 +161,8 @@ int q3_embed_many(q3_engine* e, const int32_t* prompts, const size_t* prompt_len
     const size_t smem = 4 * (size_t)term_floats((int)dim);
     q3_embed_stats st;
     if ((rc = embed_walk(e, prompts, prompt_len, n_requests, (flags & Q3_EMBED_PREFIX) != 0, n_out > b->embed_out_cap,
-                         [&] { return cols_grow(b->embed_out, b->embed_out_cap, n_out); },
-                         [&](const EmbedRow* rows, size_t n_rows, const float* x) {
+                         [&](const std::vector<DenseRun>&, const std::vector<EmbedStep>&) { return cols_grow(b->embed_out, b->embed_out_cap, n_out); },
+                         [&](const EmbedRow* rows, size_t n_rows, const float* x, size_t) {
                              return launch_now(e->stream, k_embed_rows, dim3((unsigned)n_rows), dim3(kWG), smem, rows, x, (const float*)e->rms_final,
                                                (int)dim, (int)out_dim, (flags & Q3_EMBED_L2) ? kEmbedL2 : 0u, b->embed_out);
                          }, st)))

@@ -40,6 +40,7 @@
 #include "q3_prefix.h"
 #include "q3_embed.h"
 #include "q3_choice.h"
+#include "q3_score.h"
 #include "q3_lookup.h"
 
 namespace {
@@ -1904,3 +1905,4 @@ int q3_op_argmax(const float* logits, size_t n, int32_t* index, int device) {
 #include "q3_prefix_host.inc"
 #include "q3_embed_host.inc"
 #include "q3_choice_host.inc"
+#include "q3_score_host.inc"

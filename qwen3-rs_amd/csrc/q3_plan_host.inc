@@ -487,6 +487,15 @@ int plan_enqueue(q3_engine* e, const Plan& p, size_t n_launches) {
     return Q3_OK;
 }
 
+// the launches [first, end) of a plan as they are, never its graph: q3_score_many runs the classifier of a column plan,
+// [Plan::head, Plan::head + 2), behind a block that ran other layers
+int plan_enqueue_range(q3_engine* e, const Plan& p, size_t first, size_t end) {
+    if (first > end || end > p.launches.size()) return fail(Q3_ERR_INTERNAL, "launches [%zu, %zu) of a plan of %zu", first, end, p.launches.size());
+    for (size_t i = first; i < end; ++i) launch(p.launches[i], e->stream);
+    HIP_TRY(hipGetLastError());
+    return Q3_OK;
+}
+
 // Plans carry the pointers and strides they were built with: whoever replaces what the step plan's launches carry (the batch sampler's
 // arguments, the score rows of a prefill-only context) drops the step plan; whoever frees the dense scratch's score rows, the dense plans.
 void plans_drop(BatchCtx* b, PlanDrop what) {

@@ -7,6 +7,7 @@
                                      [--append-token ID] [-o out.npy] [--streams N] [--context N]
     python -m qwen3_rs_amd.cli rerank <checkpoint> -q QUERY -d DOC [-d DOC ...] [--instruct TEXT] [--yes TEXT] [--no TEXT]
                                       [--streams N] [-c N] [-o out.npy]
+    python -m qwen3_rs_amd.cli score <checkpoint> -i TEXT [-i TEXT ...] [--context TEXT] [--streams N] [--ctx N] [-o out.npy]
 
 `inference` follows generation.rs: `generate` echoes the prompt and decodes from its last token over a zero KV prefix
 (:9-48); `chat` renders the template, forwards every prompt token (one rng coin each) and decodes until BOS/EOS
@@ -23,6 +24,11 @@ first 8 components; `-o` saves the matrix.
 `rerank` reads a checkpoint out as a reranker (q3_choice_many): one prompt per -d document from the Qwen3-Reranker template
 (generation.RERANK_TEMPLATE), the logits of the `--no` and `--yes` tokens behind it, softmax over the two.  One line per document:
 index and P(yes); `-o` saves the scores.
+`score` says how likely the checkpoint finds every -i text (q3_score_many): log P of each of its tokens given the tokens before it,
+the vocabulary-wide sums formed on the device.  With `--context TEXT` every text is a continuation scored behind that context: the
+tokens are encode(context) + encode(text), only the text's tokens are scored, and with more than one text the context is computed
+once and kept resident as a shared prefix.  One line per text: index, scored tokens, sum of log-probs, perplexity; `-o` saves the
+log-probs of all texts, concatenated in order, as one float64 vector.
 """
 from __future__ import annotations
 
@@ -205,6 +211,39 @@ def run_rerank(a) -> int:
     return 0
 
 
+def score_requests(ctx, texts):
+    """What `score` hands to generation.score for the context's tokens and the texts' tokens: (prompts, score_from, shared_prefix).
+    Behind a context every token of a text is a target, the first one predicted from the context's last token: that token leads
+    every prompt when the rest of the context is resident as the prefix (the first token behind a prefix is never a target)."""
+    if not ctx:
+        return [list(x) for x in texts], None, None
+    if len(texts) > 1 and len(ctx) > 1:
+        return [[ctx[-1]] + list(x) for x in texts], [1] * len(texts), list(ctx[:-1])
+    return [list(ctx) + list(x) for x in texts], [len(ctx)] * len(texts), None
+
+
+def run_score(a) -> int:
+    import numpy as np
+    from .generation import perplexity, score
+    b = TransformerBuilder(a.checkpoint)
+    if a.ctx:
+        b = b.with_ctx_length(a.ctx)
+    with b.build() as t:
+        tok = Tokenizer(a.checkpoint, t.get_config().vocab_size, False)
+        texts = [tok.encode(text) for text in a.input]
+        if any(not x for x in texts):
+            print("Error: an input has no token", file=sys.stderr)
+            return 1
+        prompts, score_from, prefix = score_requests(tok.encode(a.context) if a.context else [], texts)
+        t.batch_init(max(1, min(a.streams, 32, len(prompts))))
+        lps = score(t, prompts, score_from, shared_prefix=prefix)
+    for r, lp in enumerate(lps):
+        print(r, lp.size, f"{lp.sum():.6f}", f"{perplexity([lp]):.6f}")
+    if a.output:
+        np.save(a.output, np.concatenate(lps) if lps else np.zeros(0))
+    return 0
+
+
 def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog="qwen3", description="Qwen3 CLI on the MI355X engine: export and inference")
     sub = ap.add_subparsers(dest="cmd")
@@ -246,6 +285,13 @@ def build_parser() -> argparse.ArgumentParser:
     rr.add_argument("--streams", type=int, default=8, metavar="N", help="slots of the batched state (1..32)")
     rr.add_argument("-c", "--context", type=int, default=None)
     rr.add_argument("-o", "--output", default=None, metavar="out.npy", help="save the scores [documents]")
+    sc = sub.add_parser("score", help="log-probabilities and perplexity of texts")
+    sc.add_argument("checkpoint")
+    sc.add_argument("-i", "--input", action="append", required=True, metavar="TEXT", help="a text to score; repeat for more")
+    sc.add_argument("--context", default=None, metavar="TEXT", help="every text is a continuation scored behind this context")
+    sc.add_argument("--streams", type=int, default=8, metavar="N", help="slots of the batched state (1..32)")
+    sc.add_argument("--ctx", type=int, default=None, metavar="N", help="context length of the engine")
+    sc.add_argument("-o", "--output", default=None, metavar="out.npy", help="save the log-probs of all texts, concatenated")
     return ap
 
 
@@ -305,6 +351,13 @@ def main(argv=None) -> int:
         from .engine import Q3Error
         try:
             return run_rerank(a)
+        except (Q3Error, IndexError, ValueError) as err:
+            print(f"Error: {err}", file=sys.stderr)
+            return 1
+    if a.cmd == "score":
+        from .engine import Q3Error
+        try:
+            return run_score(a)
         except (Q3Error, IndexError, ValueError) as err:
             print(f"Error: {err}", file=sys.stderr)
             return 1

@@ -33,6 +33,7 @@ EXPORTED_SYMBOLS = [
     "q3_batch_copy_rows", "q3_batch_prefix_set", "q3_batch_prefix_get", "q3_generate_many_prefix",
     "q3_embed_many",
     "q3_choice_many",
+    "q3_score_many", "q3_score_pack",
 ]
 VERIFY_MAX = 32          # Q3_VERIFY_MAX
 COLS_MAX = 32            # Q3_COLS_MAX
@@ -40,6 +41,9 @@ STOP_MAX = 8             # Q3_STOP_MAX
 EMBED_L2, EMBED_PREFIX = 1, 2   # Q3_EMBED_L2, Q3_EMBED_PREFIX
 CHOICE_PREFIX, CHOICE_PER_REQUEST = 2, 4   # Q3_CHOICE_PREFIX, Q3_CHOICE_PER_REQUEST
 CHOICE_MAX = 256         # Q3_CHOICE_MAX
+SCORE_PREFIX = 2         # Q3_SCORE_PREFIX
+# q3_score_rec as a numpy record: what Transformer.score_many returns per scored position
+SCORE_DTYPE = np.dtype([("target", np.float32), ("max", np.float32), ("sum", np.float32), ("argmax", np.int32)])
 
 
 class Q3Error(RuntimeError):
@@ -104,6 +108,21 @@ class EmbedStats:
     blocks: int
     live_columns: int
     pad_columns: int
+
+
+class _ScoreStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("waves", "blocks", "live_columns", "pad_columns", "chunks", "scored")]
+
+
+@dataclasses.dataclass(frozen=True)
+class ScoreStats:
+    """q3_score_stats: EmbedStats' four, the classifier chunks of up to 32 scored columns and the records of a score_many call"""
+    waves: int
+    blocks: int
+    live_columns: int
+    pad_columns: int
+    chunks: int
+    scored: int
 
 
 @dataclasses.dataclass(frozen=True)
@@ -247,6 +266,8 @@ def _bind(path: str) -> C.CDLL:
     L.q3_generate_many_prefix.argtypes = L.q3_generate_many_stop.argtypes
     L.q3_embed_many.argtypes = [C.c_void_p, i32p, szp, sz, C.c_uint32, sz, fp, C.POINTER(_EmbedStats)]
     L.q3_choice_many.argtypes = [C.c_void_p, i32p, szp, sz, i32p, sz, C.c_uint32, fp, C.POINTER(_EmbedStats)]
+    L.q3_score_many.argtypes = [C.c_void_p, i32p, szp, sz, szp, C.c_uint32, C.c_void_p, C.POINTER(_ScoreStats)]
+    L.q3_score_pack.argtypes = [szp, sz, szp, C.c_int, C.c_int, C.POINTER(_ScoreStats)]
     L.q3_profile.argtypes = [C.c_void_p, sz, sz, C.c_int, fp, C.POINTER(C.c_int32), C.c_int]
     L.q3_profile_name.argtypes = [C.c_int]
     L.q3_profile_name.restype = C.c_char_p
@@ -337,6 +358,20 @@ def dense_pack(run_len, block_cap: int):
     _check(L.q3_dense_pack(rl, len(run_len), block_cap, table, n.value, C.byref(n), C.byref(st)))
     rows = [tuple(int(table[4 * i + k]) for k in range(4)) for i in range(n.value)]
     return rows, DenseStats(st.blocks, st.live_columns, st.pad_columns)
+
+
+def score_pack(prompt_len, score_from, max_streams: int, block_cap: int) -> ScoreStats:
+    """The schedule of score_many (q3_score_pack, host only): its ScoreStats for prompts of prompt_len[r] tokens scored from
+    score_from[r] (None: 1 everywhere) through max_streams slots and dense blocks of up to block_cap columns."""
+    if score_from is not None and len(score_from) != len(prompt_len):
+        raise IndexError("one score_from per prompt")
+    st = _ScoreStats()
+    rc = load_library().q3_score_pack(_size_array(prompt_len), len(prompt_len), None if score_from is None else _size_array(score_from),
+                                      max_streams, block_cap, C.byref(st))
+    if rc == -3:
+        raise IndexError(load_library().q3_last_error().decode(errors="replace"))
+    _check(rc)
+    return ScoreStats(st.waves, st.blocks, st.live_columns, st.pad_columns, st.chunks, st.scored)
 
 
 def parse_header(data: bytes) -> ModelConfig:
@@ -741,6 +776,33 @@ class Transformer:
         self._batch_rc(self._lib.q3_choice_many(self._h, _i32_array(flat), _size_array([len(p) for p in prompts]), n, _i32_array(ids), k, flags,
                                                 out.ctypes.data_as(C.POINTER(C.c_float)), C.byref(st)))
         return out, EmbedStats(st.waves, st.blocks, st.live_columns, st.pad_columns)
+
+    # ---- scores (include/qwen3_hip.h section 2l)
+    def score_many(self, prompts, score_from=None, use_prefix: bool = False):
+        """What the model says about every next token of many prompts (q3_score_many).  Request r of n tokens t gets
+        n - score_from[r] records of SCORE_DTYPE: record j describes the logits l behind t[i], i = score_from[r] - 1 + j --
+        target = l[t[i + 1]], max = the largest logit, sum = the sequential f32 sum of expf(l - max) over the vocabulary, argmax --
+        target and sum bit for bit what forward() per position gives; log P(t[i + 1] | t[..i]) = (target - max) - log(sum)
+        (generation.logprobs_of).  score_from: None (every position but the last is scored) or one value per prompt, 1 .. n.
+        The prompts go through the slots of batch_init as in embed_many, from slot 0 up -- whatever the slots held is overwritten.
+        use_prefix: the prompts are suffixes behind the resident prefix of batch_prefix_set.
+        Returns (one SCORE_DTYPE array per request, ScoreStats)."""
+        n = len(prompts)
+        lens = [len(p) for p in prompts]
+        if score_from is not None:
+            score_from = [int(v) for v in score_from]
+            if len(score_from) != n:
+                raise IndexError("one score_from per prompt")
+        sf = [1] * n if score_from is None else score_from
+        counts = [max(0, ln - f) if f >= 1 else 0 for ln, f in zip(lens, sf)]
+        flat = [int(t) for p in prompts for t in p]
+        out = np.zeros(sum(counts), dtype=SCORE_DTYPE)
+        st = _ScoreStats()
+        self._batch_rc(self._lib.q3_score_many(self._h, _i32_array(flat), _size_array(lens), n, None if score_from is None else _size_array(score_from),
+                                               SCORE_PREFIX if use_prefix else 0, out.ctypes.data_as(C.c_void_p) if out.size else None, C.byref(st)))
+        ends = np.cumsum([0] + counts)
+        return ([out[ends[r]:ends[r + 1]] for r in range(n)],
+                ScoreStats(st.waves, st.blocks, st.live_columns, st.pad_columns, st.chunks, st.scored))
 
     def set_batch_sampler(self, temperature: float, topp: float, rng_seeds):
         """one Sampler per stream (sampler.rs:29-42), stream i seeded with rng_seeds[i]; temperature 0 = greedy"""

@@ -269,6 +269,63 @@ def choose(transformer, prompts: Sequence[Sequence[int]], candidates, shared_pre
     return logits if output == "logits" else normalise_logits(logits, output)
 
 
+def logprobs_of(records) -> np.ndarray:
+    """log P(target) of Transformer.score_many's records: (target - max) - log(sum), in float64 from the three float32 fields.
+    Nothing is special-cased: sum == 0 gives what numpy's log(0) gives (+inf here), an infinite field or a NaN propagates."""
+    t, m, s = (np.asarray(records[k], dtype=np.float32).astype(np.float64) for k in ("target", "max", "sum"))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return (t - m) - np.log(s)
+
+
+def score(transformer, prompts: Sequence[Sequence[int]], score_from=None, shared_prefix=None, records: bool = False):
+    """log P(t[i + 1] | t[0 .. i]) for the positions of many prompts: one float64 array per prompt, entry j for the target
+    t[score_from[r] + j] (score_from None: every token but the first is a target; score_from[r] == len gives an empty array).
+    The prompts go through the slots of Transformer.batch_init in dense blocks and the classifier runs for the scored positions
+    only, 32 at a time; the vocabulary-wide sums stay on the device (Transformer.score_many), the slots' contents are overwritten.
+    shared_prefix as in embed: a token list (`prompts` and score_from are then those of the suffixes behind it), True for the
+    longest common prefix of `prompts` that holds no scored position's input, None for no prefix.
+    records: return (log-prob arrays, the SCORE_DTYPE record arrays) instead."""
+    if any(len(p) == 0 for p in prompts):
+        raise ValueError("Please provide a prompt")
+    sf = None if score_from is None else [int(v) for v in score_from]
+    if shared_prefix is True:
+        # the first suffix token is never a target: the prefix ends in front of the earliest scored position's input
+        k = min(common_prefix_len(prompts), min(sf if sf is not None else [1]) - 1)
+        shared_prefix = None
+        if k > 0:
+            shared_prefix, prompts = [int(t) for t in prompts[0][:k]], [p[k:] for p in prompts]
+            sf = [v - k for v in sf]
+    prompts, use_prefix = _split_prefix(transformer, prompts, shared_prefix)
+    recs = transformer.score_many(prompts, sf, use_prefix=use_prefix)[0]
+    lps = [logprobs_of(r) for r in recs]
+    return (lps, recs) if records else lps
+
+
+def loglikelihood(transformer, contexts: Sequence[Sequence[int]], continuations: Sequence[Sequence[int]], shared_prefix=None):
+    """(log P(continuation | context), whether the continuation is the greedy one) for every pair, lm-eval's `loglikelihood`: one
+    score call over context + continuation with score_from = len(context).  The context must hold at least one token (behind a
+    shared_prefix token list: the part of it behind the prefix).  is_greedy: argmax == target at every continuation position."""
+    if len(contexts) != len(continuations):
+        raise ValueError("one continuation per context")
+    if any(len(c) == 0 for c in contexts):
+        raise ValueError("Please provide a context")
+    prompts = [[int(t) for t in c] + [int(t) for t in k] for c, k in zip(contexts, continuations)]
+    lps, recs = score(transformer, prompts, [len(c) for c in contexts], shared_prefix=shared_prefix, records=True)
+    out = []
+    for p, c, lp, rec in zip(prompts, contexts, lps, recs):
+        targets = np.asarray(p[len(c):], dtype=np.int32)
+        out.append((float(lp.sum()), bool(np.array_equal(rec["argmax"], targets))))
+    return out
+
+
+def perplexity(logprob_arrays) -> float:
+    """exp(-mean log-prob) over all scored tokens of score()'s arrays, in float64 (NaN when nothing was scored)"""
+    arrays = [np.asarray(a, dtype=np.float64).ravel() for a in logprob_arrays]
+    lp = np.concatenate(arrays) if arrays else np.zeros(0)
+    with np.errstate(invalid="ignore", over="ignore"):
+        return float(np.exp(-lp.mean())) if lp.size else float("nan")
+
+
 # The prompt of the Qwen3-Reranker family, as its model card gives it.  Written from memory: no such checkpoint or card was at hand
 # when this was written, so the wording is unverified (DESIGN.md section 4.11).
 RERANK_INSTRUCTION = "Given a web search query, retrieve relevant passages that answer the query"
