@@ -1,5 +1,5 @@
 """Call sequences over the batched state (helper module of tests/test_call_sequences_host.py and tests/test_call_sequences.py, not a
-conftest).  One BatchCtx serves every entry point of include/qwen3_hip.h sections 2b to 2j, and its plans, graphs and grow-only buffers
+conftest).  One BatchCtx serves every entry point of include/qwen3_hip.h sections 2b to 2l, and its plans, graphs and grow-only buffers
 are shared or cached between them; this module generates seeded sequences of calls, knows from the C oracle alone what every call
 must return, and checks an engine op by op.
 
@@ -11,7 +11,8 @@ must return, and checks an engine op by op.
 
 Shape: small-hd128 (dim 512, 8 heads over 4 kv heads, head_dim 128, group 64, vocabulary 2,048) with 576 positions declared instead
 of 256: the score rows of the dense blocks (att_pf) are sized to the context end rounded up to 256, so on 256 positions they are
-allocated once and can never grow."""
+allocated once and can never grow.  score_probs of q3_score_many is sized by the vocabulary alone (32 rows of it), so within an engine
+it is allocated once and can never grow: it is not among BUFFERS."""
 import dataclasses
 import functools
 import random
@@ -24,7 +25,9 @@ DENSE_CAP = 2048                      # Q3_PREFILL_M as the tests leave it
 COLS_MAX = 32
 WIDTHS = (1, 2, 4, 8, 16, 32)
 BUFFERS = ("cols_table", "cols_ncols", "cols_prompts", "cols_out", "cols_aux", "cols_temp", "cols_topp", "cols_seeds", "cols_req",
-           "dense_runs", "embed_rows", "embed_out", "att_pf")
+           "dense_runs", "embed_rows", "embed_out", "att_pf", "score_rows", "score_out", "choice_cand", "choice_out")
+SCORE_COLS = 32                       # kScoreCols: the scored columns of a block go through the classifier that many at a time
+CHOICE_PART = 32                      # kChoicePart: the candidates of one workgroup
 
 
 def shape(q3):
@@ -78,11 +81,13 @@ def _make_catalogue():
         else:
             n = rng.choice((3, 9, 20, 33, 35, 41, 48, 57, 64, 65, 70, 83, 97, 110, 120))
         cat.append((i % N_BASES, n, 1 + rng.randrange(4), temps[(i // 2) % 4], topps[i % 4], 1000 + i))
+    for i in range(88, 91):                     # 88 .. 90: one token, for the calls that generate nothing (a score request without a record)
+        cat.append((i % N_BASES, 1, 1, 0.0, 1.0, 1000 + i))
     return cat
 
 
 CAT = _make_catalogue()
-SMALL, MEDIUM, LARGE = range(0, 12), range(12, 18), range(18, 88)
+SMALL, MEDIUM, LARGE, ONE = range(0, 12), range(12, 18), range(18, 88), range(88, 91)
 PREFIXES = ((5, 7), (4, 37), (3, 44))          # resident prefixes: base, length (one narrow, two wide)
 DEEP = {1: (2, 300), 2: (2, 530)}              # the runs that end past 256 and past 512 positions
 
@@ -105,15 +110,21 @@ KINDS = (
     "batch_step_cols", "generate_many_greedy", "batch_step_cols_draw", "generate_many_sampled",
     "batch_prefill_slots", "generate_many_dense", "generate_many_stop",
     "batch_copy_rows", "batch_prefix_set", "generate_many_prefix", "embed_many", "embed_many_prefix",
+    "choice_many", "choice_many_prefix", "score_many", "score_many_prefix",
     "set_batch_sampler_on", "set_batch_sampler_off", "set_sampler", "batch_reset_kv", "reset_kv", "batch_init",
     "forward", "generate_greedy",
     "refused_batch", "refused_prefill_batched", "refused_verify", "refused_cols", "refused_dense", "refused_stop", "refused_prefix",
-    "refused_embed", "refused_forward", "refused_greedy_only",
+    "refused_embed", "refused_choice", "refused_score", "refused_forward", "refused_greedy_only",
 )
 GREEDY_ONLY = ("forward_batch", "generate_greedy_batch", "batch_step_cols", "generate_many_greedy")     # refused under a sampling batch
 NEED_DRAWS = ("forward_batch_s", "generate_greedy_batch_s")                                              # need known per-stream rng states
 SAMPLING_ONLY = NEED_DRAWS + ("refused_greedy_only",)
 MANY = ("generate_many_greedy", "generate_many_sampled", "generate_many_dense", "generate_many_stop", "generate_many_prefix")
+CHOICE, SCORE = ("choice_many", "choice_many_prefix"), ("score_many", "score_many_prefix")
+# the calls that run q3_embed_many's walk and generate nothing: legal under a sampling batch, and they draw no coin, so the per-stream
+# rng states stay what they were (a NEED_DRAWS op right behind them draws the coins the seeds give)
+WALKS = ("embed_many", "embed_many_prefix") + CHOICE + SCORE
+NEED_PREFIX = ("generate_many_prefix", "embed_many_prefix", "choice_many_prefix", "score_many_prefix")
 
 # ordered pairs the API makes illegal, one line of reason each
 ILLEGAL = {}
@@ -129,7 +140,7 @@ for _a in ("generate_many_sampled", "generate_many_dense", "generate_many_stop",
     for _b in NEED_DRAWS:
         ILLEGAL[(_a, _b)] = ("the per-stream sampler states are unspecified behind a sampled loop (and behind a greedy one the batch "
                              "sampler is off): q3_batch_sampler_set has to come first")
-for _b in ("generate_many_prefix", "embed_many_prefix"):
+for _b in NEED_PREFIX:
     ILLEGAL[("batch_init", _b)] = "q3_batch_init drops the resident prefix"
 for _a in ("batch_init", "batch_reset_kv"):
     ILLEGAL[(_a, "batch_copy_rows")] = "legal in the API, but the sequences copy only rows whose tokens they know: every slot has just been cleared"
@@ -194,9 +205,59 @@ def op_requests(op):
     return [CAT[i][1] for i in op["reqs"]], [CAT[i][2] for i in op["reqs"]]
 
 
+def candidates(op):
+    """The candidate ids of a choice op, from its "cand" = (k, per request, seed): one list of k ids, or one per request.  Seeded draws
+    from the vocabulary that hold 0, VOCAB - 1 and a duplicate as far as k has room for them (k = 1: one of the two edges or a draw;
+    k = 2: the two edges)."""
+    k, per_request, seed = op["cand"]
+    r = random.Random(seed)
+
+    def one():
+        if k == 1:
+            return [r.choice((0, VOCAB - 1, r.randrange(VOCAB)))]
+        ids = [r.randrange(VOCAB) for _ in range(max(0, k - 3))]
+        ids += [0, VOCAB - 1] + ([r.choice(ids)] if ids else [])
+        r.shuffle(ids)
+        return ids[:k]
+    return [one() for _ in op["reqs"]] if per_request else one()
+
+
+def flat_candidates(op):
+    c = candidates(op)
+    return [t for row in c for t in row] if op["cand"][1] else c
+
+
+def score_blocks(op, streams):
+    """The blocks of a score op, one per wave (dense_block asserts it): [(width, wide, scored columns in column order)].  The runs of a
+    narrow block stand side by side from column 0, those of a wide one at multiples of 8."""
+    lens, _ = op_requests(op)
+    sf = op["score_from"] or [1] * len(lens)
+    out = []
+    for w0 in range(0, len(lens), streams):
+        wave, first = lens[w0:w0 + streams], sf[w0:w0 + streams]
+        w, wide = dense_block(wave)
+        cols, at = [], 0
+        for n, f in zip(wave, first):
+            cols += [at + i for i in range(n) if i + 1 < n and i + 1 >= f]
+            at += (n + 7) & ~7 if wide else n
+        out.append((w, wide, cols))
+    return out
+
+
+def score_chunks(op, streams):
+    """[(scored columns of the chunk, the classifier runs on them where they stand: no gather)] of a score op"""
+    out = []
+    for _, wide, cols in score_blocks(op, streams):
+        for c0 in range(0, len(cols), SCORE_COLS):
+            part = cols[c0:c0 + SCORE_COLS]
+            out.append((len(part), not wide and part == list(range(len(part)))))
+    return out
+
+
 def needs(op, streams, sampling, prefix_len, rows=None, stop=()):
-    """What an op asks of the grow-only buffers, by the sizes at the call sites of cols_job_run, cols_generate_stop, cols_sampler_upload
-    and q3_embed_many, and which kept plans it runs: dict(buffer -> elements), cols = {(draw, width index)}, dense = {block width}."""
+    """What an op asks of the grow-only buffers, by the sizes at the call sites of cols_job_run, cols_generate_stop, cols_sampler_upload,
+    q3_embed_many, q3_choice_many and q3_score_many, and which kept plans it runs: dict(buffer -> elements), cols = {(draw, width
+    index)}, dense = {block width}; for a score op also chunk_cols, the column plans that only its classifier chunks run (not its walk)."""
     kind = op["op"]
     need, cols, dense = {}, set(), set()
 
@@ -237,9 +298,9 @@ def needs(op, streams, sampling, prefix_len, rows=None, stop=()):
         else:
             job(1, n_tok, 0, 0, draw, 0, 0)
             cols.add((draw, width_index(n_tok)))
-    elif kind in ("embed_many", "embed_many_prefix"):
+    elif kind in WALKS:
         lens, _ = op_requests(op)
-        P = prefix_len if kind == "embed_many_prefix" else 0
+        P = prefix_len if kind.endswith("_prefix") else 0
         max_end = 0
         for w0 in range(0, len(lens), streams):
             wave = lens[w0:w0 + streams]
@@ -249,9 +310,23 @@ def needs(op, streams, sampling, prefix_len, rows=None, stop=()):
                 max_end = max(max_end, P + max(wave))
             else:
                 cols.add((False, width_index(sum(wave))))
-        need.update(cols_prompts=sum(lens), dense_runs=len(lens), embed_rows=len(lens), embed_out=len(lens) * (op.get("out_dim") or DIM))
+        need.update(cols_prompts=sum(lens), dense_runs=len(lens), embed_rows=len(lens))
+        if kind in CHOICE:
+            k, per_request, _ = op["cand"]
+            need.update(choice_cand=k * len(lens) if per_request else k, choice_out=k * len(lens))
+        elif kind in SCORE:
+            # every chunk runs the classifier part of the kept non-draw column plan of its width, behind wide blocks as well
+            chunks = {(False, width_index(m)) for m, _ in score_chunks(op, streams)}
+            first_use = chunks - cols
+            cols |= chunks
+            n_rec = sum(n - f for n, f in zip(lens, op["score_from"] or [1] * len(lens)))
+            need.update(score_rows=n_rec, score_out=n_rec)
+        else:
+            need["embed_out"] = len(lens) * (op.get("out_dim") or DIM)
         if max_end:
             need["att_pf"] = (max_end + 255) & ~255
+        if kind in SCORE:
+            return dict(need=need, cols=cols, dense=dense, chunk_cols=first_use)
     elif kind in ("batch_step_cols", "batch_step_cols_draw"):
         cols.add((sampling and kind == "batch_step_cols_draw", width_index(len(op["slots"]))))
     return dict(need=need, cols=cols, dense=dense)
@@ -260,8 +335,9 @@ def needs(op, streams, sampling, prefix_len, rows=None, stop=()):
 # ---------------------------------------------------------------------------------------------------------------------------------
 # the generator
 # ---------------------------------------------------------------------------------------------------------------------------------
-SEEDS = (11, 12, 13, 14, 15, 16, 17, 18)
-N_OPS = 240
+SEEDS = (11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22)
+N_OPS = 220
+EDGE_SEED = SEEDS[3]                  # the seed that also runs on the edge-valued checkpoint: it holds the four choice and score kinds
 
 
 class _Gen:
@@ -280,7 +356,9 @@ class _Gen:
         self.prefix = None
         self.size = "S"
         self.large_calls = 0
-        self.growth = False                  # inside the epoch whose buffers have to grow: no q3_batch_init
+        self.grown = set()                   # the choice kinds of a large phase that have made their growing call
+        self.turned_off = set()              # the ops that switch off a batch sampler that was on
+        self.growth = False                 # inside the epoch whose buffers have to grow: no q3_batch_init
 
     # -- legality
     def legal(self, kind):
@@ -292,7 +370,7 @@ class _Gen:
             return False
         if kind == "batch_step_cols_draw" and self.bs_on and not self.bs_known:
             return False
-        if kind in ("generate_many_prefix", "embed_many_prefix") and self.prefix is None:
+        if kind in NEED_PREFIX and self.prefix is None:
             return False
         if kind == "batch_copy_rows" and not (self.streams >= 2 and any(s for s in self.slots)):
             return False
@@ -309,16 +387,46 @@ class _Gen:
             return held[0], held[1]
         return self.rng.randrange(N_BASES), 0
 
-    def _reqs(self, dense=False):
+    def _reqs(self, dense=False, one=False):
         r = self.rng
         if self.size == "S":
             out = r.sample(SMALL, r.randint(1, 3))
             if dense or r.random() < 0.3:
                 out[r.randrange(len(out))] = r.choice(MEDIUM)
+            if one and len(out) > 1 and r.random() < 0.3:      # a one-token request: no record, nothing in front of its last token
+                out[r.randrange(len(out))] = r.choice(ONE)
             return out
         self.large_calls += 1                                  # every large list is longer than the one before it
         n = min(38, 18 + 2 * self.large_calls) if self.size == "L1" else min(70, 50 + 2 * self.large_calls)
         return list(LARGE[:n])
+
+    def _score_from(self, reqs):
+        r = self.rng
+        lens = [CAT[i][1] for i in reqs]
+        if self.size == "S":
+            mode = r.randrange(4)
+            if mode == 0:
+                return None
+            if mode == 1:                                      # the first request alone: its scored columns are the block's first (no gather)
+                sf = [1] + lens[1:]
+            else:
+                sf = [r.choice((1, n, max(1, n - 1), r.randint(1, n))) for n in lens]
+            if self.growth and sf == lens:                     # where the buffers have to grow, the small calls have a record too
+                sf[max(range(len(lens)), key=lens.__getitem__)] = 1
+            return sf
+        # a large list: the first wide blocks that can hold them score 31, 32 and 33 columns, the others all they have (more than 64)
+        sf, targets = [1] * len(lens), [31, 32, 33]
+        for w0 in range(0, len(lens), self.streams):
+            wave = lens[w0:w0 + self.streams]
+            if targets and dense_block(wave)[1] and sum(n - 1 for n in wave) >= targets[0]:
+                left = targets.pop(0)
+                order = list(range(len(wave)))
+                r.shuffle(order)
+                for j in order:
+                    take = min(wave[j] - 1, left)
+                    left -= take
+                    sf[w0 + j] = wave[j] - take
+        return sf
 
     # -- one emitter per kind
     def emit(self, kind, **force):
@@ -376,11 +484,11 @@ class _Gen:
                 op.update(token=BASES[k][p], pos=p)
                 self.single = (k, p + 1)
         elif kind in ("batch_step_cols", "batch_step_cols_draw", "refused_cols", "refused_greedy_only"):
-            slots = r.sample(range(S), r.randint(1, min(S, 3)))
+            slots = r.sample(range(S), 1 if force.get("one") else r.randint(1, min(S, 3)))
             left = COLS_MAX
             sl, tk, ps = [], [], []
             for j, s in enumerate(slots):
-                m = r.randint(1, min(left - (len(slots) - 1 - j), r.choice((1, 3, 12))))
+                m = r.randint(1, min(left - (len(slots) - 1 - j), 1 if force.get("one") else r.choice((1, 3, 12))))
                 left -= m
                 k, p = self._place(self.slots[s], ctx, m)
                 sl += [s] * m
@@ -460,9 +568,34 @@ class _Gen:
             else:
                 used = min(len(op["reqs"]), S)
                 self.slots[:used] = [None] * used
+        elif kind in CHOICE or kind == "refused_choice":
+            op["reqs"] = self._reqs(one=True)
+            if self.size != "S" and kind not in self.grown:    # the call of a large phase that has to grow both buffers
+                self.grown.add(kind)
+                op["cand"] = (33, True, r.getrandbits(24))
+            else:                                              # 33 and 70: a second and a third grid part of kChoicePart candidates
+                op["cand"] = (r.choice((1, 2, 5, 33, 70) if self.size == "S" else (1, 2, 5, 33)), r.random() < 0.5, r.getrandbits(24))
+            if kind == "refused_choice":                       # a candidate equal to VOCAB, no candidate at all, a token out of range
+                op.update(bad=r.choice(("cand", "k0", "token")), at=r.randrange(len(op["reqs"])))
+            else:
+                used = min(len(op["reqs"]), S)
+                self.slots[:used] = [None] * used
+        elif kind in SCORE or kind == "refused_score":
+            if force.get("steer"):                             # 33 scored columns of a wide block: a chunk of 32 and a chunk of 1
+                op.update(reqs=[MEDIUM[0]], score_from=None)
+            else:
+                op["reqs"] = self._reqs(one=True)
+                op["score_from"] = self._score_from(op["reqs"])
+            if kind == "refused_score":                        # score_from 0 or n + 1, a token out of range, an empty prompt
+                op.update(bad=r.choice(("from0", "from_past", "token", "empty")), at=r.randrange(len(op["reqs"])))
+            else:
+                used = min(len(op["reqs"]), S)
+                self.slots[:used] = [None] * used
         elif kind in ("set_batch_sampler_on", "set_batch_sampler_off"):
             on = kind.endswith("_on")
             op.update(T=r.choice((0.7, 0.9, 1.2)) if on else 0.0, P=r.choice((0.9, 0.95, 1.0)), seeds=[r.getrandbits(48) + 1 for _ in range(S)])
+            if self.bs_on and not on:
+                self.turned_off.add(len(self.ops))
             self.bs_on, self.bs_known = on, True
         elif kind == "set_sampler":
             op.update(T=0.0 if self.ss_on else r.choice((0.8, 1.1)), P=r.choice((0.9, 1.0)), seed=r.getrandbits(48) + 1)
@@ -504,7 +637,7 @@ class _Gen:
             self.emit("set_batch_sampler_on")
         if kind in ("verify", "generate_lookup") and self.ss_on:
             self.emit("set_sampler")
-        if kind in ("generate_many_prefix", "embed_many_prefix") and self.prefix is None:
+        if kind in NEED_PREFIX and self.prefix is None:
             self.emit("batch_prefix_set")
         if kind == "batch_copy_rows" and not any(self.slots):
             self.emit("batch_prefill_slots")
@@ -519,7 +652,8 @@ class _Gen:
             return self.emit(self.pick(must))
         ready = [p for p in todo if self.legal(p[0]) and self.legal(p[1]) and (prev, p[0]) not in ILLEGAL]
         owed = [p for p in todo if p[0] in must or p[1] in must]
-        for pool in ([p for p in todo if p[0] == prev and self.legal(p[1])], [p for p in ready if (prev, p[0]) in todo], ready, todo):
+        open_pairs = set(todo)
+        for pool in ([p for p in todo if p[0] == prev and self.legal(p[1])], [p for p in ready if (prev, p[0]) in open_pairs], ready, todo):
             if pool:
                 a, b = self.rng.choice([p for p in pool if p in owed] or pool)
                 break
@@ -538,6 +672,7 @@ class _Gen:
         must = list(must)
         start = len(self.ops)
         self.large_calls = 0
+        self.grown = set()
         if size != "S":                                        # the kinds that have to grow the buffers come first
             for k in must:
                 self.enable(k)
@@ -547,18 +682,21 @@ class _Gen:
             at = len(self.ops)
             if len(must) + 4 >= start + n_ops - at:                # no room left: the kinds the phase owes, in a legal order
                 k = next((m for m in must if self.legal(m) and (self.ops[-1]["op"], m) not in ILLEGAL), None)
+                if k == "set_batch_sampler_off" and not self.bs_on:
+                    k = "set_batch_sampler_on"
                 if k is None and must:
                     k = "set_batch_sampler_off" if self.bs_on else "set_batch_sampler_on"
                 self.emit(k or self.pick(()))
             else:
                 self.target(must)
-            for o in self.ops[at:]:
-                if o["op"] in must:
+            for i, o in enumerate(self.ops[at:], at):              # (switching the batch sampler off counts where it was on)
+                if o["op"] in must and (o["op"] != "set_batch_sampler_off" or i in self.turned_off):
                     must.remove(o["op"])
         assert not must, (size, must)
 
 
-GROW = ("generate_many_greedy", "generate_many_sampled", "generate_many_dense", "generate_many_stop", "embed_many", "batch_prefill_slots")
+GROW = ("generate_many_greedy", "generate_many_sampled", "generate_many_dense", "generate_many_stop", "embed_many", "batch_prefill_slots",
+        "choice_many", "score_many")
 
 
 def _sequence(seed, n_ops, avoid):
@@ -574,9 +712,13 @@ def _sequence(seed, n_ops, avoid):
     # grow-only buffer is re-allocated twice behind plans that were cached while it was small
     g.emit("batch_init", streams=b if b != g.streams else 4, ctx=0)
     g.growth = True
+    # the first use of two column-plan widths (32 and 1, non-draw) is a score chunk's, through plan_get in the walk's grow callback;
+    # the column pass of one column behind it runs the plan the chunk has made
+    g.emit("score_many", steer=True)
+    g.emit("batch_step_cols", one=True)
     warm = ("generate_many_greedy", "generate_many_greedy", "generate_many_sampled", "generate_many_sampled", "generate_many_dense",
             "generate_many_dense", "batch_prefill_slots", "batch_prefill_slots", "embed_many", "embed_many", "generate_many_stop",
-            "set_batch_sampler_on", "set_batch_sampler_off")
+            "choice_many", "choice_many", "score_many", "score_many", "set_batch_sampler_on", "set_batch_sampler_off")
     g.phase("S", 2 * unit, warm)
     for _ in range(2):                                         # the second one runs the kept plan of that width
         g.emit("batch_prefill_slots", wide=True)
@@ -610,10 +752,10 @@ def make_sequence(seed, n_ops=N_OPS):
 # the reference: the C oracle, memoised
 # ---------------------------------------------------------------------------------------------------------------------------------
 class _Node:
-    __slots__ = ("parent", "tok", "pos", "k", "v", "logits", "x", "kids")
+    __slots__ = ("parent", "tok", "pos", "k", "v", "logits", "x", "kids", "wide")
 
     def __init__(self, parent, tok):
-        self.parent, self.tok, self.pos, self.kids = parent, tok, (parent.pos + 1 if parent else -1), {}
+        self.parent, self.tok, self.pos, self.kids, self.wide = parent, tok, (parent.pos + 1 if parent else -1), {}, None
 
 
 class Reference:
@@ -675,6 +817,18 @@ class Reference:
             n = self.child(n, t)
         return n
 
+    @staticmethod
+    def record(node, target):
+        """score_ref.record(node.logits, target).  Its vocabulary-wide part (max, sum, argmax) is kept on the node: score_ref.exps goes
+        through ctypes element by element, once per node and not once per op"""
+        import score_ref
+        if node.wide is None:
+            r = score_ref.record(node.logits, 0)
+            node.wide = (r["max"], r["sum"], r["argmax"])
+        out = np.zeros((), dtype=score_ref.DTYPE)
+        out["target"], (out["max"], out["sum"], out["argmax"]) = node.logits[target], node.wide
+        return out
+
     def draw(self, logits, T, P, state):
         """(token, rng state afterwards): Sampler::sample with that state, the argmax and no coin at temperature 0"""
         if not T > 0:
@@ -729,7 +883,7 @@ class _Cache:
         self.hist, self.node, self.ctx = [], ref.root, ctx
 
 
-LEAKS = ("sampler", "prefix", "length")
+LEAKS = ("sampler", "prefix", "length", "slot_rng", "stale_cand")
 
 
 class FakeEngine:
@@ -738,7 +892,11 @@ class FakeEngine:
     shape.  Every number comes from Reference.  leak: one of LEAKS --
         "sampler": a slot's sampler state is carried from one generate_many_sampled call into the next instead of being loaded
         "prefix":  the resident prefix survives q3_batch_init
-        "length":  batch_reset_kv leaves the rows of every slot's occupant in place"""
+        "length":  batch_reset_kv leaves the rows of every slot's occupant in place
+        "slot_rng": a choice or score call advances the sampler state of every slot it fills by one coin per prompt token, as a dense
+                   generate loop does and these calls must not
+        "stale_cand": choice_many answers with the previous call's candidate ids at every index that call had: a candidate buffer
+                   that is uploaded only where it has grown"""
 
     def __init__(self, ref, leak=None):
         assert leak is None or leak in LEAKS
@@ -749,6 +907,7 @@ class FakeEngine:
         self.bT, self.bP, self.brng = 0.0, 1.0, []
         self.prefix = []
         self.loop_rng = {}
+        self.last_cand = []
         self.touched = {}
 
     # -- state
@@ -858,7 +1017,7 @@ class FakeEngine:
     def batch_init(self, streams, ctx=0):
         self.streams, self.ctx = streams, min(ctx, SEQ) if ctx else SEQ
         self.slots = [_Cache(self.ref, self.ctx) for _ in range(streams)]
-        self.bT, self.brng, self.loop_rng = 0.0, [], {}
+        self.bT, self.brng, self.loop_rng, self.last_cand = 0.0, [], {}, []
         if self.leak != "prefix":
             self.prefix = []
         self.touched.update({s: "all" for s in range(streams)})
@@ -1022,17 +1181,59 @@ class FakeEngine:
             self._check_tokens(p)
         if use_prefix and not self.prefix:
             raise IndexError("no resident prefix")
-        full = [(self.prefix if use_prefix else []) + list(p) for p in prompts]
-        rows = []
-        for r, p in enumerate(full):
-            for i, t in enumerate(p):
-                n = self._feed(r % self.streams, t, i)
-            rows.append(n.x)
-        rows = np.stack(rows)
+        nodes, st = self._walk(prompts, use_prefix)
+        rows = np.stack([n[-1].x for n in nodes])
         out = embed_ref.l2(rows, out_dim) if normalize else rows[:, :out_dim or DIM].copy()
+        return out, st
+
+    def _walk(self, prompts, use_prefix, coins=False):
+        """q3_embed_many's walk: request r goes through slot r % streams from position 0 (behind the prefix).  Returns, per request, the
+        nodes of its own tokens, and the EmbedStats of the schedule"""
+        P = len(self.prefix) if use_prefix else 0
+        nodes = []
+        for r, p in enumerate(prompts):
+            s = r % self.streams
+            got = [self._feed(s, t, i) for i, t in enumerate((self.prefix if use_prefix else []) + list(p))]
+            nodes.append(got[P:])
+            if coins and self.leak == "slot_rng" and self.brng:
+                self.brng[s] = xorshift(self.brng[s], len(p))
         waves = [[len(p) for p in prompts[i:i + self.streams]] for i in range(0, len(prompts), self.streams)]
         st = [_q3().dense_pack(w, DENSE_CAP)[1] for w in waves]
-        return out, _q3().EmbedStats(len(waves), sum(s.blocks for s in st), sum(s.live_columns for s in st), sum(s.pad_columns for s in st))
+        return nodes, _q3().EmbedStats(len(waves), sum(s.blocks for s in st), sum(s.live_columns for s in st), sum(s.pad_columns for s in st))
+
+    def choice_many(self, prompts, candidates, use_prefix=False):
+        cands = [list(c) if hasattr(c, "__len__") else c for c in candidates]
+        per_request = len(cands) > 0 and all(isinstance(c, list) for c in cands)
+        k = len(cands[0]) if per_request else len(cands)
+        flat = [t for c in cands for t in c] if per_request else cands
+        if not 1 <= k <= 256 or (per_request and (len(cands) != len(prompts) or any(len(c) != k for c in cands))):
+            raise IndexError("k out of range, or not one list of k candidates per prompt")
+        self._check_tokens(flat)
+        for p in prompts:
+            self._check_tokens(p)
+        if not prompts or any(len(p) == 0 for p in prompts) or (use_prefix and not self.prefix):
+            raise IndexError("an empty prompt, or no resident prefix")
+        if self.leak == "stale_cand":       # the ids already in the device buffer are not uploaded again
+            flat = self.last_cand[:len(flat)] + flat[len(self.last_cand):]
+        self.last_cand = list(flat)
+        nodes, st = self._walk(prompts, use_prefix, coins=True)
+        out = np.stack([n[-1].logits[flat[r * k:(r + 1) * k] if per_request else flat] for r, n in enumerate(nodes)])
+        return out.astype(np.float32, copy=False), st
+
+    def score_many(self, prompts, score_from=None, use_prefix=False):
+        import score_ref
+        lens = [len(p) for p in prompts]
+        sf = [1] * len(lens) if score_from is None else list(score_from)
+        if not prompts or len(sf) != len(lens) or any(n == 0 or f < 1 or f > n for n, f in zip(lens, sf)) or (use_prefix and not self.prefix):
+            raise IndexError("an empty prompt, score_from out of range, or no resident prefix")
+        for p in prompts:
+            self._check_tokens(p)
+        nodes, st = self._walk(prompts, use_prefix, coins=True)
+        out = [np.array([self.ref.record(n[i], p[i + 1]) for i in range(f - 1, len(p) - 1)], dtype=score_ref.DTYPE).reshape(len(p) - f)
+               for p, n, f in zip(prompts, nodes, sf)]
+        sched = score_ref.schedule(lens, sf, self.streams, DENSE_CAP)
+        assert sched[:4] == (st.waves, st.blocks, st.live_columns, st.pad_columns), (sched, st)
+        return out, _q3().ScoreStats(*sched)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -1106,6 +1307,33 @@ def call(e, op, ref, prefix=()):
         if k == "refused_embed":
             prompts[op["bad"]][0] = VOCAB
         return e.embed_many(prompts, normalize=op["normalize"], out_dim=op["out_dim"], use_prefix=k == "embed_many_prefix")
+    if k in CHOICE or k == "refused_choice":
+        prompts = [toks(CAT[i][:2]) for i in op["reqs"]]
+        cand = candidates(op)
+        if k == "refused_choice":
+            if op["bad"] == "token":
+                prompts[op["at"]][-1] = VOCAB
+            elif op["bad"] == "k0":
+                cand = []
+            else:
+                (cand[op["at"]] if op["cand"][1] else cand)[-1] = VOCAB
+        return e.choice_many(prompts, cand, use_prefix=k == "choice_many_prefix")
+    if k in SCORE or k == "refused_score":
+        prompts = [toks(CAT[i][:2]) for i in op["reqs"]]
+        sf = op["score_from"]
+        if k == "refused_score":
+            at = op["at"]
+            if op["bad"] == "token":
+                prompts[at][-1] = -1
+            elif op["bad"] == "empty":
+                prompts[at] = []
+                sf = sf and sf[:at] + [1] + sf[at + 1:]
+            else:
+                sf = list(sf or [1] * len(prompts))
+                sf[at] = 0 if op["bad"] == "from0" else len(prompts[at]) + 1
+        recs, st = e.score_many(prompts, sf, use_prefix=k == "score_many_prefix")
+        # field by field, so that same() compares the three floats of every record by their bits
+        return [tuple(np.ascontiguousarray(r[f]) for f in ("target", "max", "sum", "argmax")) for r in recs], st
     if k in ("set_batch_sampler_on", "set_batch_sampler_off"):
         return e.set_batch_sampler(op["T"], op["P"], op["seeds"])
     if k == "set_sampler":

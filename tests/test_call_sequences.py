@@ -12,7 +12,8 @@ import seq_model as sm
 
 pytestmark = pytest.mark.gpu
 
-EDGE_SEED = sm.SEEDS[2]           # the seed that also runs on the edge-valued checkpoint
+EDGE_SEED = sm.EDGE_SEED          # the seed that also runs on the edge-valued checkpoint (tests/test_call_sequences_host.py: it holds
+                                  # choice_many and score_many; tied classifier rows make the score argmax the odd row there)
 
 
 @pytest.fixture(scope="module")

@@ -1,7 +1,8 @@
 """What the call sequences of tests/seq_model.py contain, asserted on the host: these are caps on what tests/test_call_sequences.py may
 leave out, not measurements.  Every ordered pair of op kinds is adjacent somewhere, every grow-only buffer of the batched state is
-re-allocated behind cached plans, the batched state is started over with other shapes, and the harness itself catches injected leaks
-(run() over seq_model.FakeEngine, no GPU anywhere)."""
+re-allocated behind cached plans, a score chunk is the first user of a column-plan width, the score and choice calls have the shapes
+at which their kernels take another path, the batched state is started over with other shapes, and the harness itself catches
+injected leaks (run() over seq_model.FakeEngine, no GPU anywhere)."""
 import pytest
 
 import seq_model as sm
@@ -106,7 +107,79 @@ def test_every_grow_only_buffer_grows_twice_behind_cached_plans(sequences, capsy
             assert len(v) >= 2, f"seed {seed}: {b} grows {len(v)} times ({v})"
 
 
+def test_a_score_chunk_is_the_first_use_of_a_column_plan_width(sequences, capsys):
+    """q3_score_many takes the column plan of a chunk's width with plan_get inside the walk's grow callback: per seed, a chunk's
+    (non-draw, width) plan is one no earlier op of the epoch has used -- not the walk of the score op itself either -- and a column pass
+    or narrow block of that width follows in the epoch, on the plan the chunk has made"""
+    for seed, ops in sequences.items():
+        info = walk(ops)
+        built, last_epoch, found = set(), 0, []
+        for i, (epoch, nd, _, _) in enumerate(info):
+            if epoch != last_epoch:
+                built, last_epoch = set(), epoch
+            if nd is None:
+                continue
+            for key in sorted(nd.get("chunk_cols", set()) - built):
+                later = [j for j in range(i + 1, len(ops)) if info[j][0] == epoch and info[j][1] and key in info[j][1]["cols"]
+                         and key not in info[j][1].get("chunk_cols", ())]
+                if later:
+                    found.append((i, sm.WIDTHS[key[1]], later[0]))
+            built |= nd["cols"]
+        with capsys.disabled():
+            print(f"\nseed {seed}: (score op, width first used by its chunk, the first column pass of that width behind it): {found}", end="")
+        assert found, seed
+
+
+def test_score_and_choice_shapes(sequences):
+    scored, skipped, gathered, wide_scored = set(), 0, 0, set()
+    drawn_behind = per_request_parts = False
+    ks, froms = set(), set()
+    for seed, ops in sequences.items():
+        info = walk(ops)
+        sampling = False
+        for i, op in enumerate(ops):
+            k = op["op"]
+            if k in sm.SCORE:
+                streams = info[i][2]
+                for _, wide, cols in sm.score_blocks(op, streams):
+                    scored.add(len(cols))
+                    if wide:
+                        wide_scored.add(len(cols))
+                chunks = sm.score_chunks(op, streams)
+                skipped += sum(1 for _, same in chunks if same)
+                gathered += sum(1 for _, same in chunks if not same)
+                nxt = ops[i + 1]["op"] if i + 1 < len(ops) else None
+                drawn_behind |= sampling and (nxt in sm.NEED_DRAWS or nxt == "batch_step_cols_draw")
+                lens, _ = sm.op_requests(op)
+                for n, f in zip(lens, op["score_from"] or [1] * len(lens)):
+                    froms |= {"one token"} if n == 1 else {"1"} if f == 1 else {"n"} if f == n else {"n - 1"} if f == n - 1 else {"between"}
+            if k in sm.CHOICE:
+                ks.add(op["cand"][0])
+                per_request_parts |= op["cand"][1] and op["cand"][0] > sm.CHOICE_PART
+                flat = sm.flat_candidates(op)
+                assert all(0 <= t < sm.VOCAB for t in flat)
+                for row in (sm.candidates(op) if op["cand"][1] else [flat]):
+                    assert len(row) == op["cand"][0]
+                    if len(row) >= 2:
+                        assert 0 in row and sm.VOCAB - 1 in row
+                    if len(row) >= 5:
+                        assert len(set(row)) < len(row)
+            if k == "set_batch_sampler_on":
+                sampling = True
+            elif k in ("set_batch_sampler_off", "batch_init"):
+                sampling = False
+    # chunk edges behind dense blocks: one chunk short of full, one full, a full one and a chunk of one, three or more
+    assert {31, 32, 33} <= wide_scored and max(wide_scored) >= 65, sorted(wide_scored)
+    assert {31, 32, 33} <= scored
+    assert skipped and gathered, (skipped, gathered)
+    assert drawn_behind, "no score op under a sampling batch with a drawing op right behind it"
+    assert {1, 2, 5, 33, 70} <= ks and per_request_parts, ks
+    assert froms == {"one token", "1", "n", "n - 1", "between"}, froms
+
+
 def test_state_changes(sequences):
+    # the sequence that also runs on the edge-valued checkpoint holds both new calls, under a prefix too
+    assert {"choice_many", "score_many", "choice_many_prefix", "score_many_prefix"} <= {o["op"] for o in sequences[sm.EDGE_SEED]}
     for seed, ops in sequences.items():
         inits = [o for o in ops if o["op"] == "batch_init"]
         assert ops[0]["op"] == "batch_init"
@@ -123,6 +196,11 @@ def test_state_changes(sequences):
         # sizes go small - large - small - larger - small
         sizes = [len(o["reqs"]) for o in ops if o["op"] in sm.MANY]
         assert min(sizes) <= 3 and max(sizes) >= 50 and sizes[-1] <= 3
+        for kind in ("choice_many", "score_many"):
+            sizes = [len(o["reqs"]) for o in ops if o["op"] == kind]
+            big = [i for i, n in enumerate(sizes) if n >= 18]
+            assert sizes[0] <= 3 and sizes[-1] <= 3 and max(sizes) >= 50, (seed, kind, sizes)
+            assert any(sizes[i] < 50 and any(n <= 3 for n in sizes[i:j]) and sizes[j] >= 50 for i in big for j in big if j > i), (seed, kind, sizes)
         assert max(sm.CAT[i][1] for o in ops if o["op"] in sm.MANY for i in o["reqs"]) == 120
 
 
@@ -150,6 +228,8 @@ def test_the_harness_passes_the_fake_engine_and_catches_the_leaks(sequences, ref
         with capsys.disabled():
             print(f"leak {leak!r} caught at (op, kind) per seed: {caught}")
         assert caught, f"leak {leak!r} passes on every seed"
+        if leak in ("slot_rng", "stale_cand"):       # caught on every seed that can show it
+            assert set(caught) == {seed for seed, ops in sequences.items() if first_visible(leak, ops) is not None}, leak
 
 
 def first_visible(leak, ops):
@@ -171,7 +251,8 @@ def first_visible(leak, ops):
                                                                                    "prefill_batched", "verify", "verify_draw", "generate_lookup",
                                                                                    "generate_lookup_draw"):
                 filled = True
-    if leak == "sampler":        # the first generate_many_sampled in which a sampled request is the first of a slot that an earlier call left a state in
+    if leak == "sampler":        # the first generate_many_sampled in which a sampled request enters a slot that a sampled request has left
+                                 # a state in: one of an earlier call, or the slot's occupant in front of it in the same call
         state, streams = set(), 0
         for i, o in enumerate(ops):
             if o["op"] == "batch_init":
@@ -180,7 +261,29 @@ def first_visible(leak, ops):
                 lens, n_new = sm.op_requests(o)
                 occ = sm.many_plan(lens, n_new, streams)["occupants"]
                 sampled = {s: [r for r in rs if sm.CAT[o["reqs"][r]][3] > 0] for s, rs in occ.items()}
-                if any(rs and s in state for s, rs in sampled.items()):
+                if any(rs and (s in state or len(rs) > 1) for s, rs in sampled.items()):
                     return i
                 state |= {s for s, rs in sampled.items() if rs}
+    if leak == "stale_cand":     # the first choice call whose candidates differ from the previous one's at an index both have
+        prev = []
+        for i, o in enumerate(ops):
+            if o["op"] == "batch_init":
+                prev = []
+            if o["op"] in sm.CHOICE:
+                flat = sm.flat_candidates(o)
+                if any(a != b for a, b in zip(flat, prev)):
+                    return i
+                prev = flat
+    if leak == "slot_rng":       # the first op that draws from a slot's known state behind a choice or score call on that slot
+        moved, streams, sampling = set(), 0, False
+        for i, o in enumerate(ops):
+            k = o["op"]
+            if k in ("batch_init", "set_batch_sampler_on", "set_batch_sampler_off"):
+                moved, sampling = set(), k == "set_batch_sampler_on"
+                streams = o["streams"] if k == "batch_init" else streams
+            elif k in sm.CHOICE + sm.SCORE:
+                moved |= set(range(min(len(o["reqs"]), streams)))
+            elif sampling and k in sm.NEED_DRAWS + ("batch_step_cols_draw",):
+                if moved & set(o["slots"] if k == "batch_step_cols_draw" else range(len(o.get("tokens") or o["first"]))):
+                    return i
     return None
