@@ -792,6 +792,48 @@ int q3_score_many(q3_engine* e, const int32_t* prompts /* concatenated */, const
 int q3_score_pack(const size_t* prompt_len, size_t n_requests, const size_t* score_from /* or NULL */, int max_streams, int block_cap,
                   q3_score_stats* stats);
 
+/* ------------------------------------------------------------------------------------------------
+ * 2m. (behind 2l so that the earlier sections stay as they were.)  Top-k log-probabilities: beside the record of section 2l, the k
+ * most likely tokens of every scored position with their logits (the top_logprobs of completion APIs, distillation targets, "what
+ * did the model expect here instead") and the rank of the token that came (top-k accuracy, MRR, filtering by surprise).  The rows
+ * l[0 .. V) are those of section 2l, standing behind the classifier launch of every chunk; two more kernels select from them
+ * (csrc/q3_score_top.h).
+ * THE ORDER.  The key of entry i of a row is
+ *     key(i) = ((uint64)total_order_key(l[i]) << 32) | i
+ * with total_order_key the unsigned image of f32::total_cmp: the key the classifier leaves per workgroup in the argmax slots.
+ *     top[0 .. k)  the entries of the k largest keys, largest first, as {l[i], i}
+ *     rank         the number of entries whose key exceeds key(target): 0 means the target is the argmax
+ * So ties in the logit go to the HIGHER index, as for argmax ("the last index of the maximum in total order"), -0.0 sorts below
+ * +0.0, top[0].index == argmax, and rank < k exactly when the target is top[rank].  Keys are distinct integers: the result does not
+ * depend on how a row is split over workgroups, and there is no tolerance anywhere.  As in 2l nothing is normalised on the device:
+ * log P(top[j]) = (top[j].logit - max) - log(sum) with the record's max and sum (generation.top_logprobs_of, in float64).
+ * ------------------------------------------------------------------------------------------------ */
+#define Q3_SCORE_TOP_MAX 64
+typedef struct q3_score_top { float logit; int32_t index; } q3_score_top;
+
+/* q3_score_many with the k best and the rank of every record: top[j] of record i stands in top[i k + j], its rank in rank[i] (rank
+ * may be NULL: no rank is copied back).  Records, schedule, stats, slots, the prefix flag and the refusals are exactly those of
+ * q3_score_many, and q3_score_pack describes both calls.  1 <= k <= Q3_SCORE_TOP_MAX and k <= vocab_size.
+ * Standard: out as for q3_score_many, bit for bit what that call gives on the same engine.  top[j].logit is bit-identical to
+ * logits[top[j].index] of the q3_forward named there; the indices and the rank are equal to those of a host sort of that row's
+ * keys.  A row that holds a NaN logit is outside the standard; the call does not fault on it: only loop indices, counters and the
+ * host-checked table entries become addresses, no logit and no key read back from memory.
+ * Schedule: every chunk runs, behind k_score_sum, k_score_top_part -- grid (parts, m): the k largest keys of one slice of a row,
+ * sorted, by k rounds of a workgroup-wide maximum, and the slice's count of keys above the target's -- and k_score_top_merge -- one
+ * workgroup per row copies the parts' lists into LDS, and one wave of it merges them and sums the counts.  parts is 64 (the
+ * developer build reads Q3_SCORE_TOP_PARTS, 1 .. 64, in every call: another split, the same results).
+ * Execution: as q3_score_many, with up to two more device-to-host copies in front of the ONE synchronisation: the tops and, if
+ * asked for, the ranks.  The tops, the ranks and the parts' lists of a chunk belong to the batched state: grown on demand (the
+ * stream is waited for first), released with it.  No slot rng is touched; no kept plan or graph is rebuilt.  Every failing call
+ * leaves the engine usable.
+ * Q3_ERR_ARG: k outside 1 .. Q3_SCORE_TOP_MAX (checked first, with the null engine, before anything touches the GPU); everything
+ * q3_score_many refuses; k > vocab_size; a null top with records to write.
+ * Q3_ERR_UNSUPPORTED: what q3_score_many refuses. */
+int q3_score_top_many(q3_engine* e, const int32_t* prompts /* concatenated */, const size_t* prompt_len, size_t n_requests,
+                      const size_t* score_from /* [n_requests] or NULL = all 1 */, uint32_t flags, int k,
+                      q3_score_rec* out /* host, concatenated */, q3_score_top* top /* host, [records][k] */,
+                      int32_t* rank /* host, [records], or NULL */, q3_score_stats* stats);
+
 #ifdef __cplusplus
 }
 #endif

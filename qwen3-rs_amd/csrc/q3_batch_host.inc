@@ -154,6 +154,13 @@ struct BatchCtx {
     ScoreRec* score_out = nullptr;
     float* score_probs = nullptr;
     size_t score_rows_cap = 0, score_out_cap = 0, score_probs_cap = 0;
+    // ... with the k best (q3_score_top_many): the call's [records][k] pairs and ranks, and one chunk's lists and counts per part
+    // ([32][parts][k] keys, [32][parts] counts), grow-only
+    ScoreTop* score_top = nullptr;
+    int* score_rank = nullptr;
+    unsigned long long* score_top_keys = nullptr;
+    int* score_top_above = nullptr;
+    size_t score_top_cap = 0, score_rank_cap = 0, score_top_keys_cap = 0, score_top_above_cap = 0;
     // packed-matrix directory
     struct PM { size_t q_off, s_off; int ntiles, ng; };
     std::vector<PM> m_qkv, m_wo, m_w13, m_w2;
@@ -178,7 +185,7 @@ void batch_free(q3_engine* e) {
                      b->cols_out, b->cols_draw, b->cols_step, b->cols_slot_samp, b->cols_aux, b->cols_temp, b->cols_topp, b->cols_seeds, b->cols_stop, b->cols_req,
                      b->dense.x, b->dense.q, b->dense.qn, b->dense.kraw, b->dense.xb, b->dense.hb, b->dense.xq_p, b->dense.xs_p, b->dense.st,
                      b->dense.col_slot, b->dense.att_pf, b->dense_runs, b->prefix_store, b->embed_rows, b->embed_out, b->choice_cand, b->choice_out,
-                     b->score_rows, b->score_out, b->score_probs};
+                     b->score_rows, b->score_out, b->score_probs, b->score_top, b->score_rank, b->score_top_keys, b->score_top_above};
     for (void* p : dptrs)
         if (p) (void)hipFree(p);
     if (b->h_st) (void)hipHostFree(b->h_st);

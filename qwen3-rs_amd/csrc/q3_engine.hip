@@ -41,6 +41,7 @@
 #include "q3_embed.h"
 #include "q3_choice.h"
 #include "q3_score.h"
+#include "q3_score_top.h"
 #include "q3_lookup.h"
 
 namespace {

@@ -1,4 +1,4 @@
-// q3_score_host.inc -- host side of the scores (include/qwen3_hip.h section 2l; included by q3_engine.hip behind
+// q3_score_host.inc -- host side of the scores (include/qwen3_hip.h sections 2l and 2m; included by q3_engine.hip behind
 // q3_choice_host.inc, same translation unit).
 //
 // The walk is q3_embed_many's (embed_walk, q3_embed_host.inc): the same waves, blocks, runs and plans.  Behind each block its scored
@@ -6,6 +6,8 @@
 // (q3_score.h).  What the two classifier launches read: k_bquant<PRO_NORM> (and k_bquant_split) forms a pointer into the column
 // states and reads it for PRO_EMBED_NORM only; k_bgemm reads State::pos and the slot table in its QKV epilogue only.  Neither
 // consults per-column state for the classifier, so none is set up here.
+// q3_score_many and q3_score_top_many are one body (score_run): with k > 0 every chunk runs k_score_top_part and k_score_top_merge
+// (q3_score_top.h) behind k_score_sum, over the same rows; with k == 0 nothing of that is allocated, enqueued or copied.
 
 namespace {
 
@@ -16,11 +18,12 @@ struct ScoreChunk {
     bool identity;      // column j of the block is row j of the chunk
 };
 
-// Q3_DEBUG_TIMING: event pairs around the launch groups of every chunk (gather | classifier | exps | sum and record), summed and
-// printed to stderr behind the call's synchronisation.  Off: no event is made or recorded.
+// Q3_DEBUG_TIMING: event pairs around the launch groups of every chunk (gather | classifier | exps | sum and record, and with the
+// k best | the selection), summed and printed to stderr behind the call's synchronisation.  Off: no event is made or recorded.
 struct ScoreTiming {
     bool on = false;
-    std::vector<hipEvent_t> ev;         // five per chunk
+    bool top = false;                   // a fifth group
+    std::vector<hipEvent_t> ev;         // five per chunk, six with the k best
     ~ScoreTiming() {
         for (hipEvent_t x : ev) (void)hipEventDestroy(x);
     }
@@ -33,16 +36,21 @@ struct ScoreTiming {
         return Q3_OK;
     }
     void report() const {
-        if (!on || ev.size() < 5) return;
-        double us[4] = {0, 0, 0, 0};
-        for (size_t c = 0; c + 5 <= ev.size(); c += 5)
-            for (int g = 0; g < 4; ++g) {
+        const size_t per = top ? 6 : 5;
+        if (!on || ev.size() < per) return;
+        double us[5] = {0, 0, 0, 0, 0};
+        for (size_t c = 0; c + per <= ev.size(); c += per)
+            for (size_t g = 0; g + 1 < per; ++g) {
                 float ms = 0.0f;
                 if (hipEventElapsedTime(&ms, ev[c + g], ev[c + g + 1]) == hipSuccess) us[g] += 1e3 * ms;
             }
-        const double n = (double)(ev.size() / 5);
-        fprintf(stderr, "[q3_score_many] %zu chunks, us per chunk: gather %.2f classifier %.2f exp %.2f sum %.2f\n", ev.size() / 5, us[0] / n, us[1] / n,
-                us[2] / n, us[3] / n);
+        const double n = (double)(ev.size() / per);
+        if (top)
+            fprintf(stderr, "[q3_score_top_many] %zu chunks, us per chunk: gather %.2f classifier %.2f exp %.2f sum %.2f top %.2f\n", ev.size() / per,
+                    us[0] / n, us[1] / n, us[2] / n, us[3] / n, us[4] / n);
+        else
+            fprintf(stderr, "[q3_score_many] %zu chunks, us per chunk: gather %.2f classifier %.2f exp %.2f sum %.2f\n", ev.size() / per, us[0] / n,
+                    us[1] / n, us[2] / n, us[3] / n);
     }
 };
 
@@ -104,14 +112,26 @@ int q3_score_pack(const size_t* prompt_len, size_t n_requests, const size_t* sco
     return Q3_OK;
 }
 
-int q3_score_many(q3_engine* e, const int32_t* prompts, const size_t* prompt_len, size_t n_requests, const size_t* score_from, uint32_t flags,
-                  q3_score_rec* out, q3_score_stats* stats) {
+}  // extern "C"
+
+namespace {
+
+// the slices per row of k_score_top_part: kScoreTopParts; in the developer build Q3_SCORE_TOP_PARTS (1 .. 64) as every call reads
+// it.  The results do not depend on it (keys are distinct integers); the time does, and fewer parts walk a slice in several tiles.
+int score_top_parts() {
+    const int v = dev_knob("Q3_SCORE_TOP_PARTS", kScoreTopParts);
+    return v >= 1 && v <= kScoreTopParts ? v : kScoreTopParts;
+}
+
+// The body of q3_score_many (k == 0: top and rank are not looked at, and nothing of section 2m is allocated, enqueued or copied)
+// and of q3_score_top_many (1 <= k <= kScoreTopMax, the caller's check).  e is not null.
+int score_run(q3_engine* e, const char* who, const int32_t* prompts, const size_t* prompt_len, size_t n_requests, const size_t* score_from,
+              uint32_t flags, int k, q3_score_rec* out, q3_score_top* top, int32_t* rank, q3_score_stats* stats) {
     static_assert(sizeof(ScoreRec) == sizeof(q3_score_rec) && offsetof(ScoreRec, argmax) == offsetof(q3_score_rec, argmax), "the device record is the header's");
-    g_err[0] = 0;
-    if (stats) *stats = q3_score_stats{0, 0, 0, 0, 0, 0};
-    if (!e) return fail(Q3_ERR_ARG, "null engine");
+    static_assert(sizeof(ScoreTop) == sizeof(q3_score_top) && offsetof(ScoreTop, index) == offsetof(q3_score_top, index), "the device pair is the header's");
+    static_assert(kScoreTopMax == Q3_SCORE_TOP_MAX && kScoreTopMax <= 64 && kScoreTopParts <= 64, "a lane of the merge per list and per winner");
     int rc;
-    if ((rc = cols_prepare(e, "q3_score_many", true))) return rc;
+    if ((rc = cols_prepare(e, who, true))) return rc;
     BatchCtx* b = e->batch;
     if (!prompts || !prompt_len || n_requests == 0) return fail(Q3_ERR_ARG, "null or empty request list");
     if (flags & ~(uint32_t)Q3_SCORE_PREFIX) return fail(Q3_ERR_ARG, "unknown flag bits 0x%x", flags);
@@ -120,6 +140,11 @@ int q3_score_many(q3_engine* e, const int32_t* prompts, const size_t* prompt_len
     if (n_rec && !out) return fail(Q3_ERR_ARG, "null output for %zu records", n_rec);
 
     const int dim = e->cfg.dim, V = e->cfg.vocab_size;
+    if (k > V) return fail(Q3_ERR_ARG, "k %d exceeds vocab_size %d", k, V);
+    if (k && n_rec && !top) return fail(Q3_ERR_ARG, "null top for %zu records", n_rec);
+    const int parts = score_top_parts();
+    const size_t n_top = k ? n_rec * (size_t)k : 0, n_rank = k && rank ? n_rec : 0;
+    const size_t n_keys = k ? (size_t)kScoreCols * (size_t)parts * (size_t)k : 0, n_above = k ? (size_t)kScoreCols * (size_t)parts : 0;
     const size_t probs_stride = ((size_t)V + 3) & ~(size_t)3, n_probs = (size_t)kScoreCols * probs_stride;
     std::vector<ScoreRow> rows;
     std::vector<ScoreChunk> chunks;
@@ -128,8 +153,10 @@ int q3_score_many(q3_engine* e, const int32_t* prompts, const size_t* prompt_len
     q3_embed_stats st;
     ScoreTiming tm;
     tm.on = getenv("Q3_DEBUG_TIMING") != nullptr;
+    tm.top = k > 0;
     rc = embed_walk(e, prompts, prompt_len, n_requests, (flags & Q3_SCORE_PREFIX) != 0,
-                    n_rec > b->score_rows_cap || n_rec > b->score_out_cap || n_probs > b->score_probs_cap,
+                    n_rec > b->score_rows_cap || n_rec > b->score_out_cap || n_probs > b->score_probs_cap || n_top > b->score_top_cap ||
+                        n_rank > b->score_rank_cap || n_keys > b->score_top_keys_cap || n_above > b->score_top_above_cap,
                     [&](const std::vector<DenseRun>& runs, const std::vector<EmbedStep>& steps) {
                         // the record of every token of the call (-1: not scored); the walk has checked the lengths and the tokens
                         std::vector<int32_t> rec_of;
@@ -150,7 +177,7 @@ int q3_score_many(q3_engine* e, const int32_t* prompts, const size_t* prompt_len
                                     if (rec_of[g] < 0) continue;
                                     const ScoreRow R{runs[q].col0 + k, rec_of[g], prompts[g + 1]};
                                     if (R.col < 0 || R.col >= s.n || (size_t)R.out >= n_rec || R.target < 0 || R.target >= V)
-                                        return fail(Q3_ERR_INTERNAL, "q3_score_many: table entry {%d, %d, %d} out of range", R.col, R.out, R.target);
+                                        return fail(Q3_ERR_INTERNAL, "%s: table entry {%d, %d, %d} out of range", who, R.col, R.out, R.target);
                                     rows.push_back(R);
                                 }
                             for (size_t r0 = first; r0 < rows.size(); r0 += kScoreCols) {
@@ -161,17 +188,21 @@ int q3_score_many(q3_engine* e, const int32_t* prompts, const size_t* prompt_len
                             }
                         }
                         step_chunk0.push_back(chunks.size());
-                        if (rows.size() != n_rec) return fail(Q3_ERR_INTERNAL, "q3_score_many: %zu table rows for %zu records", rows.size(), n_rec);
+                        if (rows.size() != n_rec) return fail(Q3_ERR_INTERNAL, "%s: %zu table rows for %zu records", who, rows.size(), n_rec);
                         // the column plans whose classifier the chunks run, kept as the walk's own are
                         int rc2;
                         for (int w = 0; w < kColsNW; ++w) {
                             if (!width_used[w]) continue;
                             if ((rc2 = plan_get(e, cols_key(kColsWidths[w], false), &plans[w]))) return rc2;
-                            if (plans[w]->launches.size() < plans[w]->head + 2) return fail(Q3_ERR_INTERNAL, "q3_score_many: a column plan without a classifier");
+                            if (plans[w]->launches.size() < plans[w]->head + 2) return fail(Q3_ERR_INTERNAL, "%s: a column plan without a classifier", who);
                         }
                         if ((rc2 = cols_grow(b->score_rows, b->score_rows_cap, n_rec))) return rc2;
                         if ((rc2 = cols_grow(b->score_out, b->score_out_cap, n_rec))) return rc2;
                         if ((rc2 = cols_grow(b->score_probs, b->score_probs_cap, n_probs))) return rc2;
+                        if ((rc2 = cols_grow(b->score_top, b->score_top_cap, n_top))) return rc2;
+                        if ((rc2 = cols_grow(b->score_rank, b->score_rank_cap, n_rank))) return rc2;
+                        if ((rc2 = cols_grow(b->score_top_keys, b->score_top_keys_cap, n_keys))) return rc2;
+                        if ((rc2 = cols_grow(b->score_top_above, b->score_top_above_cap, n_above))) return rc2;
                         if (n_rec) HIP_TRY(hipMemcpyAsync(b->score_rows, rows.data(), sizeof(ScoreRow) * n_rec, hipMemcpyHostToDevice, e->stream));
                         return (int)Q3_OK;
                     },
@@ -201,21 +232,58 @@ int q3_score_many(q3_engine* e, const int32_t* prompts, const size_t* prompt_len
                             a.slot_stride = b->nslots;
                             a.nslots = (int)p.launches[p.head + 1].grid.x;      // one key per workgroup of the classifier launch
                             a.n = V;
-                            if (a.nslots < 1 || a.nslots > b->nslots) return fail(Q3_ERR_INTERNAL, "q3_score_many: %d argmax slots of %d", a.nslots, b->nslots);
+                            if (a.nslots < 1 || a.nslots > b->nslots) return fail(Q3_ERR_INTERNAL, "%s: %d argmax slots of %d", who, a.nslots, b->nslots);
                             if ((rc2 = launch_now(e->stream, k_score_exp, dim3(kScoreExpParts, (unsigned)c.m), dim3(256), 0, a))) return rc2;
                             if ((rc2 = tm.mark(e->stream))) return rc2;
                             if ((rc2 = launch_now(e->stream, k_score_sum, dim3((unsigned)c.m), dim3(kSampThreads), 0, a))) return rc2;
+                            if ((rc2 = tm.mark(e->stream))) return rc2;
+                            if (!k) continue;
+                            ScoreTopArgs ta{};
+                            ta.rows = tab;
+                            ta.logits = b->logits;
+                            ta.part_keys = b->score_top_keys;
+                            ta.part_above = b->score_top_above;
+                            ta.top = b->score_top;
+                            ta.rank = rank ? b->score_rank : nullptr;
+                            ta.n = V;
+                            ta.k = k;
+                            ta.parts = parts;
+                            if ((rc2 = launch_now(e->stream, k_score_top_part, dim3((unsigned)parts, (unsigned)c.m), dim3(256), 0, ta))) return rc2;
+                            if ((rc2 = launch_now(e->stream, k_score_top_merge, dim3((unsigned)c.m), dim3(256), 0, ta))) return rc2;
                             if ((rc2 = tm.mark(e->stream))) return rc2;
                         }
                         return (int)Q3_OK;
                     }, st, true);
     if (rc) return rc;
-    // one copy back, one synchronisation
+    // the copies back, one synchronisation
     if (n_rec) HIP_TRY(hipMemcpyAsync(out, b->score_out, sizeof(ScoreRec) * n_rec, hipMemcpyDeviceToHost, e->stream));
+    if (n_top) HIP_TRY(hipMemcpyAsync(top, b->score_top, sizeof(ScoreTop) * n_top, hipMemcpyDeviceToHost, e->stream));
+    if (n_rank) HIP_TRY(hipMemcpyAsync(rank, b->score_rank, sizeof(int32_t) * n_rank, hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     tm.report();
     if (stats) *stats = q3_score_stats{st.waves, st.blocks, st.live_columns, st.pad_columns, (uint64_t)chunks.size(), (uint64_t)n_rec};
     return Q3_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int q3_score_many(q3_engine* e, const int32_t* prompts, const size_t* prompt_len, size_t n_requests, const size_t* score_from, uint32_t flags,
+                  q3_score_rec* out, q3_score_stats* stats) {
+    g_err[0] = 0;
+    if (stats) *stats = q3_score_stats{0, 0, 0, 0, 0, 0};
+    if (!e) return fail(Q3_ERR_ARG, "null engine");
+    return score_run(e, "q3_score_many", prompts, prompt_len, n_requests, score_from, flags, 0, out, nullptr, nullptr, stats);
+}
+
+int q3_score_top_many(q3_engine* e, const int32_t* prompts, const size_t* prompt_len, size_t n_requests, const size_t* score_from, uint32_t flags, int k,
+                      q3_score_rec* out, q3_score_top* top, int32_t* rank, q3_score_stats* stats) {
+    g_err[0] = 0;
+    if (stats) *stats = q3_score_stats{0, 0, 0, 0, 0, 0};
+    if (k < 1 || k > Q3_SCORE_TOP_MAX) return fail(Q3_ERR_ARG, "k %d out of range (1..%d)", k, Q3_SCORE_TOP_MAX);
+    if (!e) return fail(Q3_ERR_ARG, "null engine");
+    return score_run(e, "q3_score_top_many", prompts, prompt_len, n_requests, score_from, flags, k, out, top, rank, stats);
 }
 
 }  // extern "C"

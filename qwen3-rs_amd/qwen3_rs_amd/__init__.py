@@ -9,9 +9,11 @@ the checkpoint format (qwen3-export/src/model_exporter.rs).  All compute runs in
 from .engine import (Q3Error, ModelConfig, Transformer, TransformerBuilder, lib_path, dev_lib_path, load_library, use_library, ops,
                      FLAG_FAST, FLAG_NO_GRAPH, FLAG_NO_VALUE_T, EXPORTED_SYMBOLS, source_build_id, SpecStats, VERIFY_MAX, lookup_draft,
                      lookup_trace, ColsStats, COLS_MAX, cols_schedule, DenseStats, dense_pack, STOP_MAX, cols_schedule_stop, EmbedStats,
-                     EMBED_L2, EMBED_PREFIX, CHOICE_PREFIX, CHOICE_PER_REQUEST, CHOICE_MAX, ScoreStats, SCORE_PREFIX, SCORE_DTYPE, score_pack)
+                     EMBED_L2, EMBED_PREFIX, CHOICE_PREFIX, CHOICE_PER_REQUEST, CHOICE_MAX, ScoreStats, SCORE_PREFIX, SCORE_DTYPE, score_pack,
+                     SCORE_TOP_MAX, TOP_DTYPE)
 from .generation import (generate, chat_turn, generate_many, embed, common_prefix_len, TokenMetrics, sample_argmax, choose, rerank,
-                         normalise_logits, RERANK_TEMPLATE, RERANK_INSTRUCTION, score, loglikelihood, perplexity, logprobs_of)
+                         normalise_logits, RERANK_TEMPLATE, RERANK_INSTRUCTION, score, loglikelihood, perplexity, logprobs_of,
+                         top_logprobs, top_logprobs_of)
 from . import checkpoint
 
 __all__ = ["Q3Error", "ModelConfig", "Transformer", "TransformerBuilder", "lib_path", "dev_lib_path", "load_library", "use_library", "ops",
@@ -20,4 +22,5 @@ __all__ = ["Q3Error", "ModelConfig", "Transformer", "TransformerBuilder", "lib_p
            "ColsStats", "COLS_MAX", "cols_schedule", "generate_many", "DenseStats", "dense_pack",
            "STOP_MAX", "cols_schedule_stop", "common_prefix_len", "embed", "EmbedStats", "EMBED_L2", "EMBED_PREFIX",
            "CHOICE_PREFIX", "CHOICE_PER_REQUEST", "CHOICE_MAX", "choose", "rerank", "normalise_logits", "RERANK_TEMPLATE", "RERANK_INSTRUCTION",
-           "ScoreStats", "SCORE_PREFIX", "SCORE_DTYPE", "score_pack", "score", "loglikelihood", "perplexity", "logprobs_of"]
+           "ScoreStats", "SCORE_PREFIX", "SCORE_DTYPE", "score_pack", "score", "loglikelihood", "perplexity", "logprobs_of",
+           "SCORE_TOP_MAX", "TOP_DTYPE", "top_logprobs", "top_logprobs_of"]

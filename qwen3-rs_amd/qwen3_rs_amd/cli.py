@@ -8,6 +8,7 @@
     python -m qwen3_rs_amd.cli rerank <checkpoint> -q QUERY -d DOC [-d DOC ...] [--instruct TEXT] [--yes TEXT] [--no TEXT]
                                       [--streams N] [-c N] [-o out.npy]
     python -m qwen3_rs_amd.cli score <checkpoint> -i TEXT [-i TEXT ...] [--context TEXT] [--streams N] [--ctx N] [-o out.npy]
+                                     [--top K]
 
 `inference` follows generation.rs: `generate` echoes the prompt and decodes from its last token over a zero KV prefix
 (:9-48); `chat` renders the template, forwards every prompt token (one rng coin each) and decodes until BOS/EOS
@@ -28,7 +29,9 @@ index and P(yes); `-o` saves the scores.
 the vocabulary-wide sums formed on the device.  With `--context TEXT` every text is a continuation scored behind that context: the
 tokens are encode(context) + encode(text), only the text's tokens are scored, and with more than one text the context is computed
 once and kept resident as a shared prefix.  One line per text: index, scored tokens, sum of log-probs, perplexity; `-o` saves the
-log-probs of all texts, concatenated in order, as one float64 vector.
+log-probs of all texts, concatenated in order, as one float64 vector.  `--top K` (q3_score_top_many) adds a fifth column, the scored
+tokens that are among the model's K most likely ones (rank < K), and `-o` then saves an .npz: `logprobs`, `top_ids` [tokens, K],
+`top_logprobs` [tokens, K] and `rank`, concatenated over the texts, and `lengths`, the scored tokens of every text.
 """
 from __future__ import annotations
 
@@ -224,7 +227,10 @@ def score_requests(ctx, texts):
 
 def run_score(a) -> int:
     import numpy as np
-    from .generation import perplexity, score
+    from .generation import perplexity, score, top_logprobs
+    if a.top is not None and not 1 <= a.top <= 64:
+        print("Error: --top takes 1..64", file=sys.stderr)
+        return 1
     b = TransformerBuilder(a.checkpoint)
     if a.ctx:
         b = b.with_ctx_length(a.ctx)
@@ -236,11 +242,19 @@ def run_score(a) -> int:
             return 1
         prompts, score_from, prefix = score_requests(tok.encode(a.context) if a.context else [], texts)
         t.batch_init(max(1, min(a.streams, 32, len(prompts))))
-        lps = score(t, prompts, score_from, shared_prefix=prefix)
+        if a.top is None:
+            lps = score(t, prompts, score_from, shared_prefix=prefix)
+        else:
+            res = top_logprobs(t, prompts, a.top, score_from, shared_prefix=prefix)
+            lps = [x[0] for x in res]
     for r, lp in enumerate(lps):
-        print(r, lp.size, f"{lp.sum():.6f}", f"{perplexity([lp]):.6f}")
-    if a.output:
+        print(r, lp.size, f"{lp.sum():.6f}", f"{perplexity([lp]):.6f}", *([] if a.top is None else [int((res[r][3] < a.top).sum())]))
+    if a.output and a.top is None:
         np.save(a.output, np.concatenate(lps) if lps else np.zeros(0))
+    elif a.output:
+        with open(a.output, "wb") as f:         # the name as given: np.savez would append .npz to a path
+            np.savez(f, logprobs=np.concatenate(lps), top_ids=np.concatenate([x[1] for x in res]), top_logprobs=np.concatenate([x[2] for x in res]),
+                     rank=np.concatenate([x[3] for x in res]), lengths=np.array([lp.size for lp in lps], dtype=np.int64))
     return 0
 
 
@@ -291,7 +305,8 @@ def build_parser() -> argparse.ArgumentParser:
     sc.add_argument("--context", default=None, metavar="TEXT", help="every text is a continuation scored behind this context")
     sc.add_argument("--streams", type=int, default=8, metavar="N", help="slots of the batched state (1..32)")
     sc.add_argument("--ctx", type=int, default=None, metavar="N", help="context length of the engine")
-    sc.add_argument("-o", "--output", default=None, metavar="out.npy", help="save the log-probs of all texts, concatenated")
+    sc.add_argument("-o", "--output", default=None, metavar="out.npy", help="save the log-probs of all texts, concatenated (with --top: an .npz)")
+    sc.add_argument("--top", type=int, default=None, metavar="K", help="also the K most likely tokens of every position and the targets' ranks (1..64)")
     return ap
 
 

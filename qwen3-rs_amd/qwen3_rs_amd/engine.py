@@ -34,6 +34,7 @@ EXPORTED_SYMBOLS = [
     "q3_embed_many",
     "q3_choice_many",
     "q3_score_many", "q3_score_pack",
+    "q3_score_top_many",
 ]
 VERIFY_MAX = 32          # Q3_VERIFY_MAX
 COLS_MAX = 32            # Q3_COLS_MAX
@@ -44,6 +45,9 @@ CHOICE_MAX = 256         # Q3_CHOICE_MAX
 SCORE_PREFIX = 2         # Q3_SCORE_PREFIX
 # q3_score_rec as a numpy record: what Transformer.score_many returns per scored position
 SCORE_DTYPE = np.dtype([("target", np.float32), ("max", np.float32), ("sum", np.float32), ("argmax", np.int32)])
+SCORE_TOP_MAX = 64       # Q3_SCORE_TOP_MAX
+# q3_score_top as a numpy record: one of the k best tokens of a scored position (Transformer.score_top_many)
+TOP_DTYPE = np.dtype([("logit", np.float32), ("index", np.int32)])
 
 
 class Q3Error(RuntimeError):
@@ -268,6 +272,7 @@ def _bind(path: str) -> C.CDLL:
     L.q3_choice_many.argtypes = [C.c_void_p, i32p, szp, sz, i32p, sz, C.c_uint32, fp, C.POINTER(_EmbedStats)]
     L.q3_score_many.argtypes = [C.c_void_p, i32p, szp, sz, szp, C.c_uint32, C.c_void_p, C.POINTER(_ScoreStats)]
     L.q3_score_pack.argtypes = [szp, sz, szp, C.c_int, C.c_int, C.POINTER(_ScoreStats)]
+    L.q3_score_top_many.argtypes = [C.c_void_p, i32p, szp, sz, szp, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(_ScoreStats)]
     L.q3_profile.argtypes = [C.c_void_p, sz, sz, C.c_int, fp, C.POINTER(C.c_int32), C.c_int]
     L.q3_profile_name.argtypes = [C.c_int]
     L.q3_profile_name.restype = C.c_char_p
@@ -787,6 +792,23 @@ class Transformer:
         The prompts go through the slots of batch_init as in embed_many, from slot 0 up -- whatever the slots held is overwritten.
         use_prefix: the prompts are suffixes behind the resident prefix of batch_prefix_set.
         Returns (one SCORE_DTYPE array per request, ScoreStats)."""
+        recs, _, _, stats = self._score(prompts, score_from, use_prefix, None)
+        return recs, stats
+
+    # ---- top-k log-probabilities (include/qwen3_hip.h section 2m)
+    def score_top_many(self, prompts, k: int, score_from=None, use_prefix: bool = False):
+        """score_many with the k most likely tokens of every scored position and the rank of its target (q3_score_top_many).
+        Per request of n_r records: the SCORE_DTYPE records, bit for bit score_many's; an (n_r, k) array of TOP_DTYPE, column j
+        the token of the j-th largest key ((total_order_key(logit) << 32) | index: ties in the logit go to the higher index, as
+        for argmax) with its logit, bit for bit forward()'s; an int32 array of ranks, the number of tokens whose key exceeds the
+        target's -- 0: the target is the argmax; rank < k: the target is column rank.  log P of an alternative is
+        (logit - max) - log(sum) with the record's max and sum (generation.top_logprobs_of).  1 <= k <= SCORE_TOP_MAX, k <=
+        vocab_size.  Everything else as score_many.
+        Returns (records, tops, ranks, ScoreStats), the first three one array per request."""
+        return self._score(prompts, score_from, use_prefix, int(k))
+
+    def _score(self, prompts, score_from, use_prefix, k):
+        """score_many (k None) and score_top_many: (records, tops, ranks, ScoreStats), tops and ranks None for k None"""
         n = len(prompts)
         lens = [len(p) for p in prompts]
         if score_from is not None:
@@ -798,11 +820,18 @@ class Transformer:
         flat = [int(t) for p in prompts for t in p]
         out = np.zeros(sum(counts), dtype=SCORE_DTYPE)
         st = _ScoreStats()
-        self._batch_rc(self._lib.q3_score_many(self._h, _i32_array(flat), _size_array(lens), n, None if score_from is None else _size_array(score_from),
-                                               SCORE_PREFIX if use_prefix else 0, out.ctypes.data_as(C.c_void_p) if out.size else None, C.byref(st)))
+        args = (self._h, _i32_array(flat), _size_array(lens), n, None if score_from is None else _size_array(score_from), SCORE_PREFIX if use_prefix else 0)
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None
+        top = rank = None
+        if k is not None:
+            top = np.zeros((out.size, max(0, min(k, SCORE_TOP_MAX))), dtype=TOP_DTYPE)
+            rank = np.zeros(out.size, dtype=np.int32)
+            self._batch_rc(self._lib.q3_score_top_many(*args, k, ptr(out), ptr(top), ptr(rank), C.byref(st)))
+        else:
+            self._batch_rc(self._lib.q3_score_many(*args, ptr(out), C.byref(st)))
         ends = np.cumsum([0] + counts)
-        return ([out[ends[r]:ends[r + 1]] for r in range(n)],
-                ScoreStats(st.waves, st.blocks, st.live_columns, st.pad_columns, st.chunks, st.scored))
+        cut = lambda a: None if a is None else [a[ends[r]:ends[r + 1]] for r in range(n)]
+        return cut(out), cut(top), cut(rank), ScoreStats(st.waves, st.blocks, st.live_columns, st.pad_columns, st.chunks, st.scored)
 
     def set_batch_sampler(self, temperature: float, topp: float, rng_seeds):
         """one Sampler per stream (sampler.rs:29-42), stream i seeded with rng_seeds[i]; temperature 0 = greedy"""

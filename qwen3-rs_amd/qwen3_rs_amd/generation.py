@@ -277,14 +277,17 @@ def logprobs_of(records) -> np.ndarray:
         return (t - m) - np.log(s)
 
 
-def score(transformer, prompts: Sequence[Sequence[int]], score_from=None, shared_prefix=None, records: bool = False):
-    """log P(t[i + 1] | t[0 .. i]) for the positions of many prompts: one float64 array per prompt, entry j for the target
-    t[score_from[r] + j] (score_from None: every token but the first is a target; score_from[r] == len gives an empty array).
-    The prompts go through the slots of Transformer.batch_init in dense blocks and the classifier runs for the scored positions
-    only, 32 at a time; the vocabulary-wide sums stay on the device (Transformer.score_many), the slots' contents are overwritten.
-    shared_prefix as in embed: a token list (`prompts` and score_from are then those of the suffixes behind it), True for the
-    longest common prefix of `prompts` that holds no scored position's input, None for no prefix.
-    records: return (log-prob arrays, the SCORE_DTYPE record arrays) instead."""
+def top_logprobs_of(records, tops) -> np.ndarray:
+    """log P of the alternatives of Transformer.score_top_many: (logit - max) - log(sum) per column of the (n, k) TOP_DTYPE array
+    `tops`, max and sum those of the n records; float64, the expression of logprobs_of."""
+    m, s = (np.asarray(records[f], dtype=np.float32).astype(np.float64)[:, None] for f in ("max", "sum"))
+    l = np.asarray(tops["logit"], dtype=np.float32).astype(np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return (l - m) - np.log(s)
+
+
+def _score_requests(transformer, prompts, score_from, shared_prefix):
+    """What score and top_logprobs hand to the engine: (prompts, score_from, use_prefix) behind the shared_prefix handling"""
     if any(len(p) == 0 for p in prompts):
         raise ValueError("Please provide a prompt")
     sf = None if score_from is None else [int(v) for v in score_from]
@@ -296,9 +299,33 @@ def score(transformer, prompts: Sequence[Sequence[int]], score_from=None, shared
             shared_prefix, prompts = [int(t) for t in prompts[0][:k]], [p[k:] for p in prompts]
             sf = [v - k for v in sf]
     prompts, use_prefix = _split_prefix(transformer, prompts, shared_prefix)
+    return prompts, sf, use_prefix
+
+
+def score(transformer, prompts: Sequence[Sequence[int]], score_from=None, shared_prefix=None, records: bool = False):
+    """log P(t[i + 1] | t[0 .. i]) for the positions of many prompts: one float64 array per prompt, entry j for the target
+    t[score_from[r] + j] (score_from None: every token but the first is a target; score_from[r] == len gives an empty array).
+    The prompts go through the slots of Transformer.batch_init in dense blocks and the classifier runs for the scored positions
+    only, 32 at a time; the vocabulary-wide sums stay on the device (Transformer.score_many), the slots' contents are overwritten.
+    shared_prefix as in embed: a token list (`prompts` and score_from are then those of the suffixes behind it), True for the
+    longest common prefix of `prompts` that holds no scored position's input, None for no prefix.
+    records: return (log-prob arrays, the SCORE_DTYPE record arrays) instead."""
+    prompts, sf, use_prefix = _score_requests(transformer, prompts, score_from, shared_prefix)
     recs = transformer.score_many(prompts, sf, use_prefix=use_prefix)[0]
     lps = [logprobs_of(r) for r in recs]
     return (lps, recs) if records else lps
+
+
+def top_logprobs(transformer, prompts: Sequence[Sequence[int]], k: int, score_from=None, shared_prefix=None):
+    """score() with the k most likely tokens of every scored position (Transformer.score_top_many): per prompt a tuple
+    (logprobs[n], ids[n, k], top_logprobs[n, k], rank[n]) -- log P of the targets as score() gives them; the ids of the k most
+    likely tokens, most likely first (ties in the logit: the higher id first); their log P; the number of tokens the model ranks
+    above the target (0: the target is the most likely one; rank[j] < k: the target is ids[j, rank[j]]).  score_from and shared_prefix
+    as for score()."""
+    prompts, sf, use_prefix = _score_requests(transformer, prompts, score_from, shared_prefix)
+    recs, tops, ranks, _ = transformer.score_top_many(prompts, k, sf, use_prefix=use_prefix)
+    return [(logprobs_of(r), np.array(t["index"], dtype=np.int32), top_logprobs_of(r, t), np.asarray(q, dtype=np.int32))
+            for r, t, q in zip(recs, tops, ranks)]
 
 
 def loglikelihood(transformer, contexts: Sequence[Sequence[int]], continuations: Sequence[Sequence[int]], shared_prefix=None):

@@ -16,6 +16,21 @@ One more call of (a) runs with Q3_DEBUG_TIMING set: the library then records eve
 and prints their means, which the tool reads back from stderr.
 The log-probs of (a) must lie within 2 V 2^-24 of (d)'s on the 4 prompts (tests/test_score.py holds them to the bits).
 Writes <out>/score.json and <out>/score.md.
+
+    python tools/bench_score.py --top 1,20,64 [--models qwen3-0.6b] [--ab PARENT_TREE] ...
+
+measures the k best instead (section 2m) and writes <out>/score_top.json and <out>/score_top.md; the default run and its two files
+are untouched.  Per model and K, on 64 prompts of 512 tokens, alternating in one process behind a warm-up round:
+  (a) q3_score_top_many over all positions, one call;
+  (b) q3_score_many on the same prompts;
+  (c) the per-token way: q3_forward for every position, the logits read back, np.argpartition and a sort of the K best on the
+      host, on 4 of the prompts, scaled by requests / 4.
+The added cost per chunk is ((a) - (b)) / chunks; one more call of (a) under Q3_DEBUG_TIMING gives the library's own figure for
+the selection's two launches.  On the 4 prompts the answers of (a) are held to q3_forward's rows: the logit listed is the row's
+at the listed id, bit for bit, and the K logits are the row's K largest, in order (ids may differ from (c)'s only where logits
+tie: (c) knows nothing of the order among equals; tests/test_score_top.py holds the ids to a host sort of the keys).
+--ab PARENT_TREE: q3_score_many alone (64 x 512, all positions), a child process per measurement that imports the package and
+loads the library of PARENT_TREE or of this tree by turns, three times each: the A/B of tools/ab_libs.sh for this call.
 """
 import argparse
 import json
@@ -27,7 +42,8 @@ import tempfile
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "qwen3-rs_amd"))
+# (--ab: a child measures the package and the library of another checkout)
+sys.path.insert(0, os.path.join(os.environ.get("Q3_BENCH_TREE", ROOT), "qwen3-rs_amd"))
 
 SLOTS = 32
 PER_TOKEN_PROMPTS = 4
@@ -56,9 +72,13 @@ def timed_groups(call):
             os.close(keep)
         f.seek(0)
         text = f.read().decode(errors="replace")
-    m = re.search(r"(\d+) chunks, us per chunk: gather ([\d.]+) classifier ([\d.]+) exp ([\d.]+) sum ([\d.]+)", text)
-    return None if not m else {"chunks": int(m.group(1)), "gather": float(m.group(2)), "classifier": float(m.group(3)),
-                               "exp": float(m.group(4)), "sum": float(m.group(5))}
+    m = re.search(r"(\d+) chunks, us per chunk: gather ([\d.]+) classifier ([\d.]+) exp ([\d.]+) sum ([\d.]+)(?: top ([\d.]+))?", text)
+    if not m:
+        return None
+    g = {"chunks": int(m.group(1)), "gather": float(m.group(2)), "classifier": float(m.group(3)), "exp": float(m.group(4)), "sum": float(m.group(5))}
+    if m.group(6) is not None:
+        g["top"] = float(m.group(6))
+    return g
 
 
 def worker(name, ctx, ckpt_dir, seed, reps):
@@ -123,6 +143,171 @@ def worker(name, ctx, ckpt_dir, seed, reps):
                 "groups_us_per_chunk": timed_groups(score_all),
             }
     print("RESULT " + json.dumps(res))
+
+
+def worker_top(name, ctx, ckpt_dir, seed, reps, ks):
+    import numpy as np
+    import qwen3_rs_amd as q3
+    ck = q3.checkpoint
+    shape = ck.SHAPES[name]
+    path = os.path.join(ckpt_dir, f"{name}-seed{seed}.q3bin")
+    ck.ensure_synthetic_checkpoint(path, shape, seed=seed)
+    n_req, plen = 64, 512
+    res = {"model": name, "ctx": ctx, "slots": SLOTS, "reps": reps, "requests": n_req, "prompt_len": plen, "k": {}}
+    with q3.TransformerBuilder(path).with_ctx_length(ctx).build() as t:
+        t.batch_init(SLOTS, ctx)
+        prompts = [ck.iter_prompt_tokens(shape, seed + 50 + r, plen) for r in range(n_req)]
+        for k in ks:
+            print(f"[bench_score] {name}: top {k}", file=sys.stderr, flush=True)
+
+            def score_top():
+                return t.score_top_many(prompts, k)
+
+            def score_all():
+                return t.score_many(prompts)
+
+            def per_token():
+                out = []
+                for p in prompts[:PER_TOKEN_PROMPTS]:
+                    ids = np.zeros((plen - 1, k), dtype=np.int64)
+                    for i in range(plen - 1):
+                        z = t.forward(p[i], i)
+                        best = np.argpartition(z, z.size - k)[z.size - k:]
+                        ids[i] = best[np.argsort(z[best])[::-1]]
+                    out.append(ids)
+                return out
+
+            def agrees(got):
+                for r, p in enumerate(prompts[:PER_TOKEN_PROMPTS]):
+                    for i in range(plen - 1):
+                        z = t.forward(p[i], i)
+                        top = got[1][r][i]
+                        if z[top["index"]].tobytes() != top["logit"].tobytes() or not np.array_equal(top["logit"], np.sort(z)[::-1][:k]):
+                            return False
+                return True
+            paths = (("score_top", score_top), ("score_all", score_all), ("per_token", per_token))
+            got = score_top()
+            score_all()
+            per_token()                                                 # (with the two calls above: the warm-up round)
+            same = agrees(got)
+            dts = {n: [] for n, _ in paths}
+            for i in range(reps):                                       # alternating; the two batched calls swap places, per_token stays last
+                for n, call in paths[i % 2:2] + paths[:i % 2] + paths[2:]:
+                    t0 = time.perf_counter()
+                    call()
+                    dts[n].append(time.perf_counter() - t0)
+            med = {n: median(v) for n, v in dts.items()}
+            st = got[3]
+            scaled = med["per_token"] * n_req / PER_TOKEN_PROMPTS
+            res["k"][str(k)] = {"chunks": st.chunks, "scored": st.scored, "agrees_with_forward": bool(same), "seconds": med, "all_seconds": dts,
+                                "added_us_per_chunk": 1e6 * (med["score_top"] - med["score_all"]) / st.chunks,
+                                "per_token_scaled_seconds": scaled, "speedup_over_per_token": scaled / med["score_top"],
+                                "groups_us_per_chunk": timed_groups(score_top)}
+    print("RESULT " + json.dumps(res))
+
+
+def worker_ab(name, ctx, ckpt_dir, seed, reps):
+    """q3_score_many over 64 prompts of 512 tokens with whatever package and library Q3_BENCH_TREE names"""
+    import qwen3_rs_amd as q3
+    ck = q3.checkpoint
+    shape = ck.SHAPES[name]
+    path = os.path.join(ckpt_dir, f"{name}-seed{seed}.q3bin")
+    ck.ensure_synthetic_checkpoint(path, shape, seed=seed)
+    with q3.TransformerBuilder(path).with_ctx_length(ctx).build() as t:
+        t.batch_init(SLOTS, ctx)
+        prompts = [ck.iter_prompt_tokens(shape, seed + 50 + r, 512) for r in range(64)]
+        t.score_many(prompts)
+        dts = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            t.score_many(prompts)
+            dts.append(time.perf_counter() - t0)
+    print("RESULT " + json.dumps({"build_id": q3.load_library().q3_build_id().decode(), "seconds": dts, "median": median(dts)}))
+
+
+def write_top_md(results, ab, a):
+    lines = ["# The k best tokens and the target's rank: `q3_score_top_many`", "",
+             "Written by `tools/bench_score.py --top` (synthetic full-size checkpoints, one MI355X, %d slots, context %d per slot): 64" % (SLOTS, a.ctx),
+             "prompts of 512 tokens, every position scored.  Wall time per call, median of %d repetitions that alternate the paths in one" % a.reps,
+             "process behind a warm-up round.  top K = `q3_score_top_many`; score = `q3_score_many` on the same prompts; per token =",
+             "`q3_forward` for every position, the logits read back, `np.argpartition` and a sort of the K best, measured on %d of the" % PER_TOKEN_PROMPTS,
+             "prompts and scaled by requests / %d.  added us / chunk = (top K - score) / chunks; `top` group = the mean of the event pairs the" % PER_TOKEN_PROMPTS,
+             "library records around k_score_top_part + k_score_top_merge of every chunk under `Q3_DEBUG_TIMING` (one call), beside the",
+             "groups of section 2l from the same call.  Numbers of one box.", "",
+             "| model | K | chunks | top K s | score s | added us / chunk | `top` group us | classifier | exp | sum | per token s (scaled) | times faster | the K largest logits of q3_forward's rows, at their ids |",
+             "|---|---|---|---|---|---|---|---|---|---|---|---|---|"]
+    for r in results:
+        for k, c in r["k"].items():
+            g = c["groups_us_per_chunk"] or {}
+            lines.append(f"| {r['model']} | {k} | {c['chunks']} | {c['seconds']['score_top']:.4f} | {c['seconds']['score_all']:.4f} | {c['added_us_per_chunk']:.1f} | "
+                         + " | ".join(f"{g[n]:.1f}" if n in g else "not taken" for n in ("top", "classifier", "exp", "sum"))
+                         + f" | {c['per_token_scaled_seconds']:.2f} | {c['speedup_over_per_token']:.1f} | {c['agrees_with_forward']} |")
+    lines += ["", "spread of the repetitions, ms (smallest - largest):", ""]
+    for r in results:
+        for k, c in r["k"].items():
+            sp = {n: f"{1e3 * min(v):.2f} - {1e3 * max(v):.2f}" for n, v in c["all_seconds"].items()}
+            lines.append(f"- {r['model']}, K = {k}: top K {sp['score_top']}; score {sp['score_all']}")
+    lines += ["", "## `q3_score_many` against the parent commit", ""]
+    if ab:
+        lines += ["A child process per measurement, the parent's package and library and this tree's by turns (the A/B of `tools/ab_libs.sh` for this",
+                  "call): median seconds of %d calls over the same 64 x 512 prompts, in the order taken." % a.reps, "",
+                  "| model | round | parent (build id) | parent s | this tree (build id) | this tree s |", "|---|---|---|---|---|---|"]
+        for name, rounds in ab.items():
+            for i, (old, new) in enumerate(rounds):
+                lines.append(f"| {name} | {i + 1} | {old['build_id']} | {old['median']:.4f} | {new['build_id']} | {new['median']:.4f} |")
+            olds, news = [o["median"] for o, _ in rounds], [n["median"] for _, n in rounds]
+            lines += ["", f"- {name}: parent {min(olds):.4f} - {max(olds):.4f} s, this tree {min(news):.4f} - {max(news):.4f} s over the rounds; medians "
+                          f"{median(olds):.4f} and {median(news):.4f} s, {100 * (median(news) / median(olds) - 1):+.2f} %; the same build's rounds differ by "
+                          f"{100 * (max(olds) / min(olds) - 1):.2f} % (parent) and {100 * (max(news) / min(news) - 1):.2f} % (this tree)."]
+    else:
+        lines.append("not taken")
+    with open(os.path.join(a.out, "score_top.md"), "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
+def run_child(cmd, name, env=None):
+    """one measurement in a child of its own under the time limit; its RESULT line, or None"""
+    p = subprocess.run(cmd, stdout=subprocess.PIPE, text=True, env=env)      # the worker's progress lines go straight to stderr
+    if p.returncode != 0:
+        print(f"[bench_score] {name}: exit status {p.returncode}; stopping here", file=sys.stderr)
+        return None
+    return json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")][-1][7:])
+
+
+def main_top(a):
+    ks = [int(v) for v in a.top.split(",")]
+    base = ["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--ctx", str(a.ctx), "--ckpt-dir", a.ckpt_dir,
+            "--seed", str(a.seed), "--reps", str(a.reps)]
+    results, ab, ok = [], {}, True
+    for name in a.models.split(","):
+        print(f"[bench_score] {name} --top {a.top} ...", file=sys.stderr, flush=True)
+        r = run_child(base + ["--worker", name, "--top", a.top], name)
+        if r is None:
+            ok = False
+            break
+        results.append(r)
+        if a.ab:
+            rounds = []
+            for _ in range(3):
+                pair = []
+                for tree in (os.path.abspath(a.ab), ROOT):
+                    got = run_child(base + ["--worker-ab", name], name, dict(os.environ, Q3_BENCH_TREE=tree))
+                    if got is None:
+                        break
+                    pair.append(got)
+                if len(pair) < 2:
+                    ok = False
+                    break
+                rounds.append(pair)
+            if rounds:
+                ab[name] = rounds
+            if not ok:
+                break
+    os.makedirs(a.out, exist_ok=True)
+    with open(os.path.join(a.out, "score_top.json"), "w") as f:
+        json.dump({"results": results, "ab": ab}, f, indent=1)
+    write_top_md(results, ab, a)
+    return 0 if ok and all(c["agrees_with_forward"] for r in results for c in r["k"].values()) else 1
 
 
 def write_md(results, a):
@@ -204,13 +389,24 @@ def main():
     ap.add_argument("--ckpt-dir", default=os.environ.get("Q3_CKPT_DIR", "/tmp"))
     ap.add_argument("--worker")
     ap.add_argument("--render", metavar="JSON", help="write <out>/score.md again from a score.json taken earlier; measures nothing")
+    ap.add_argument("--top", default=None, metavar="K[,K...]", help="measure q3_score_top_many instead: <out>/score_top.json and .md")
+    ap.add_argument("--ab", default=None, metavar="PARENT_TREE", help="with --top: q3_score_many of that checkout's build against this tree's")
+    ap.add_argument("--worker-ab")
     a = ap.parse_args()
     if a.render:
         write_md(json.load(open(a.render)), a)
         return 0
+    if a.worker_ab:
+        worker_ab(a.worker_ab, a.ctx, a.ckpt_dir, a.seed, a.reps)
+        return 0
+    if a.worker and a.top:
+        worker_top(a.worker, a.ctx, a.ckpt_dir, a.seed, a.reps, [int(v) for v in a.top.split(",")])
+        return 0
     if a.worker:
         worker(a.worker, a.ctx, a.ckpt_dir, a.seed, a.reps)
         return 0
+    if a.top:
+        return main_top(a)
     results = []
     for name in a.models.split(","):
         cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--worker", name, "--ctx", str(a.ctx),
