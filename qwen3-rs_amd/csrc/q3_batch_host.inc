@@ -29,16 +29,16 @@ struct Plan {
     size_t head = 0;             // index of the first launch behind the layers (q3_embed_many launches [0, head) of a column plan alone)
 };
 
-// the per-column buffers the layers of a plan work on: the context's own, or the dense block scratch of SlotPrefill
+// the per-column buffers the layers of a SlotPrefill plan work on: the dense block scratch, beside the context's own
 struct BlockScratch {
-    float *x = nullptr, *q = nullptr, *qn = nullptr, *kraw = nullptr, *xb = nullptr, *hb = nullptr;
-    int8_t* xq_p = nullptr;
-    float* xs_p = nullptr;
-    State* st = nullptr;
-    int* col_slot = nullptr;
-    float* att_pf = nullptr;
+    DevMem<float> x, q, qn, kraw, xb, hb;
+    DevMem<int8_t> xq_p;
+    DevMem<float> xs_p;
+    DevMem<State> st;
+    DevMem<int> col_slot;
+    DevMem<float> att_pf;
     int att_pf_stride = 0;
-    int cap = 0;                 // columns (SlotPrefill scratch; 0: not allocated)
+    int cap = 0;                 // columns (0: not allocated)
 };
 
 // the plan widths of a column pass: a pass of n live columns runs the narrowest plan that holds it, padded with repeats of
@@ -64,103 +64,95 @@ struct ColsDrawHost {           // pinned staging of the sampled passes
 struct BatchCtx {
     int max_streams = 0, ctx = 0;
     int cap = 0;                 // columns the scratch buffers hold: max_streams, or the dense prefill block (Q3_PREFILL_M)
-    float* att_pf = nullptr;     // k_attn_pf2 score rows [cap][n_heads][att_pf_stride]
+    DevMem<float> att_pf;        // k_attn_pf2 score rows [cap][n_heads][att_pf_stride]
     int att_pf_stride = 0;
-    int8_t* pq = nullptr;        // packed weights, all matrices
-    float* ps = nullptr;
-    float* qn = nullptr;         // k_attn_pf2: normalised + rotated queries of the block, head pairs interleaved [cap][n_heads/2][hd][2]
-    float *x = nullptr, *q = nullptr, *kraw = nullptr, *xb = nullptr, *hb = nullptr, *logits = nullptr;
-    float *key = nullptr, *value = nullptr, *att = nullptr;
-    int8_t* xq_p = nullptr;
-    float* xs_p = nullptr;
-    State* st = nullptr;
-    unsigned long long* slots = nullptr;
+    DevMem<int8_t> pq;           // packed weights, all matrices
+    DevMem<float> ps;
+    DevMem<float> qn;            // k_attn_pf2: normalised + rotated queries of the block, head pairs interleaved [cap][n_heads/2][hd][2]
+    DevMem<float> x, q, kraw, xb, hb, logits;
+    DevMem<float> key, value, att;
+    DevMem<int8_t> xq_p;
+    DevMem<float> xs_p;
+    DevMem<State> st;
+    DevMem<unsigned long long> slots;
     int nslots = 0;
-    unsigned long long* stamps = nullptr;   // developer timeline (Q3_STAMPS=1, dev build)
-    int32_t* out_tokens = nullptr;
+    DevMem<unsigned long long> stamps;      // developer timeline (Q3_STAMPS=1, dev build)
+    DevMem<int32_t> out_tokens;
     int out_cap = 0;
-    State* h_st = nullptr;
-    int32_t* h_tokens = nullptr;
-    float* h_logits = nullptr;
+    PinMem<State> h_st;
+    PinMem<int32_t> h_tokens;
+    PinMem<float> h_logits;
     Plan step;                   // the one plan of Decode, Prefill and Verify: replaced whenever step_key changes (empty: none)
     PlanKey step_key;
     // draft verification (q3_verify / q3_generate_lookup)
-    SpecIO* spec_io = nullptr;   // device: block input and result
-    SpecIO* h_spec = nullptr;    // pinned staging of the same
-    float* spec_snap = nullptr;  // key / value rows a rejected draft would leave behind, [2][layers][kSpecMax - 1][kv_dim]
+    DevMem<SpecIO> spec_io;      // device: block input and result
+    PinMem<SpecIO> h_spec;       // pinned staging of the same
+    DevMem<float> spec_snap;     // key / value rows a rejected draft would leave behind, [2][layers][kSpecMax - 1][kv_dim]
     // ... under the sampler (q3_verify_draw / q3_generate_lookup_draw): allocated by the first sampled pass (spec_draw_alloc)
-    SamplerState* spec_samp = nullptr;   // [kSpecMax] column sampler states
-    float *spec_probs = nullptr, *spec_sp = nullptr;
-    unsigned long long* spec_keys = nullptr;
+    DevMem<SamplerState> spec_samp;      // [kSpecMax] column sampler states
+    DevMem<float> spec_probs, spec_sp;
+    DevMem<unsigned long long> spec_keys;
     SampleArgs spec_sargs{};
     bool has_kv = false;         // per-stream KV caches allocated (q3_batch_init); prefill-only contexts have none
     // per-stream device samplers (q3_batch_sampler_set)
     bool sampling = false;
-    SamplerState* d_sampler = nullptr;
-    float *d_probs = nullptr, *d_sp = nullptr;
-    unsigned long long* d_keys = nullptr;
+    DevMem<SamplerState> d_sampler;
+    DevMem<float> d_probs, d_sp;
+    DevMem<unsigned long long> d_keys;
     SampleArgs sargs{};
     size_t kv_stream = 0;        // floats per stream in key / value
     // column passes (q3_batch_step_cols / q3_generate_many_greedy)
-    int* col_slot = nullptr;     // device [kColsMax]: KV slot of every column of the pass in flight
-    ColsCtl* cols_ctl = nullptr; // device
-    ColsHost* h_cols = nullptr;
+    DevMem<int> col_slot;        // device [kColsMax]: KV slot of every column of the pass in flight
+    DevMem<ColsCtl> cols_ctl;    // device
+    PinMem<ColsHost> h_cols;
     Plan cols_plans[2][kColsNW];                        // [sampled][width], built on first use (q3_batch_init starts over); the sampled
                                                         // ones: the same layers and classifier, then the draws and k_cols_turn_draw
-    ColEnt* cols_table = nullptr;                       // the loop's pass table, prompts and output: grow-only device buffers
-    int* cols_ncols = nullptr;
-    int32_t *cols_prompts = nullptr, *cols_out = nullptr;
-    size_t cols_table_cap = 0, cols_ncols_cap = 0, cols_prompts_cap = 0, cols_out_cap = 0;
+    DevMem<ColEnt> cols_table;                          // the loop's pass table, prompts and output: grow-only device buffers
+    DevMem<int> cols_ncols;
+    DevMem<int32_t> cols_prompts, cols_out;
     // ... under the sampler (q3_batch_step_cols_draw / q3_generate_many_sampled): allocated by the first sampled pass (cols_draw_alloc),
     // the column sampler states and the draw scratch are those of spec_draw_alloc
-    ColsDraw* cols_draw = nullptr;                      // device
-    ColsDrawHost* h_cols_draw = nullptr;
-    ColsStep* cols_step = nullptr;                      // device
-    SamplerState* cols_slot_samp = nullptr;             // [kMaxStreams] the loop's per-slot states (a single pass uses d_sampler)
-    ColAux* cols_aux = nullptr;                         // the loop's table of ColAux and per-request sampler parameters: grow-only
-    float *cols_temp = nullptr, *cols_topp = nullptr;
-    unsigned long long* cols_seeds = nullptr;
-    size_t cols_aux_cap = 0, cols_temp_cap = 0, cols_topp_cap = 0, cols_seeds_cap = 0;
+    DevMem<ColsDraw> cols_draw;                         // device
+    PinMem<ColsDrawHost> h_cols_draw;
+    DevMem<ColsStep> cols_step;                         // device
+    DevMem<SamplerState> cols_slot_samp;                // [kMaxStreams] the loop's per-slot states (a single pass uses d_sampler)
+    DevMem<ColAux> cols_aux;                            // the loop's table of ColAux and per-request sampler parameters: grow-only
+    DevMem<float> cols_temp, cols_topp;
+    DevMem<unsigned long long> cols_seeds;
     // ... with stop tokens (q3_generate_many_stop): the scheduler state and its one-row table, the per-request records (grow-only),
     // the pinned status word the host reads after every pass; allocated by the first call
-    ColsStopDev* cols_stop = nullptr;                   // device
-    SchedStatus* h_cols_stop = nullptr;
-    int* cols_req = nullptr;
-    size_t cols_req_cap = 0;
+    DevMem<ColsStopDev> cols_stop;                      // device
+    PinMem<SchedStatus> h_cols_stop;
+    DevMem<int> cols_req;
     // dense blocks over the per-stream caches (q3_batch_prefill_slots / q3_generate_many_dense): scratch of prefill_block_cap()
     // columns beside the 32-column one, allocated on first use; plans by block width, kept (no graph: the launches are enqueued
     // as they are, like q3_prefill_batched's); the run tables of a call, grow-only
     BlockScratch dense;
     int dense_cap = 0;           // columns per block, fixed by the first dense call (Q3_PREFILL_M as read then): packing and scratch agree
     std::map<int, Plan> dense_plans;
-    DenseRun* dense_runs = nullptr;
-    size_t dense_runs_cap = 0;
+    DevMem<DenseRun> dense_runs;
     // the resident shared prefix (q3_batch_prefix_set): key and value rows 0 .. prefix_n - 1 of every layer, [2][n_layers][prefix_n][kv_dim],
     // beside the per-stream caches and private to section 2i; the tokens they were computed from
-    float* prefix_store = nullptr;
+    DevMem<float> prefix_store;
     size_t prefix_n = 0;
     std::vector<int32_t> prefix_tokens;
     // embeddings (q3_embed_many): the gather tables of a call's blocks and its output rows [n_requests][out_dim], grow-only
-    EmbedRow* embed_rows = nullptr;
-    float* embed_out = nullptr;
-    size_t embed_rows_cap = 0, embed_out_cap = 0;
+    DevMem<EmbedRow> embed_rows;
+    DevMem<float> embed_out;
     // choice logits (q3_choice_many): the uploaded candidate ids and the output rows [n_requests][k], grow-only
-    int32_t* choice_cand = nullptr;
-    float* choice_out = nullptr;
-    size_t choice_cand_cap = 0, choice_out_cap = 0;
+    DevMem<int32_t> choice_cand;
+    DevMem<float> choice_out;
     // scores (q3_score_many): the table of a call's scored columns, its records, and the exps of one chunk [32][vocab_size up to a
     // multiple of 4], grow-only
-    ScoreRow* score_rows = nullptr;
-    ScoreRec* score_out = nullptr;
-    float* score_probs = nullptr;
-    size_t score_rows_cap = 0, score_out_cap = 0, score_probs_cap = 0;
+    DevMem<ScoreRow> score_rows;
+    DevMem<ScoreRec> score_out;
+    DevMem<float> score_probs;
     // ... with the k best (q3_score_top_many): the call's [records][k] pairs and ranks, and one chunk's lists and counts per part
     // ([32][parts][k] keys, [32][parts] counts), grow-only
-    ScoreTop* score_top = nullptr;
-    int* score_rank = nullptr;
-    unsigned long long* score_top_keys = nullptr;
-    int* score_top_above = nullptr;
-    size_t score_top_cap = 0, score_rank_cap = 0, score_top_keys_cap = 0, score_top_above_cap = 0;
+    DevMem<ScoreTop> score_top;
+    DevMem<int> score_rank;
+    DevMem<unsigned long long> score_top_keys;
+    DevMem<int> score_top_above;
     // packed-matrix directory
     struct PM { size_t q_off, s_off; int ntiles, ng; };
     std::vector<PM> m_qkv, m_wo, m_w13, m_w2;
@@ -176,26 +168,9 @@ int plan_enqueue_range(q3_engine* e, const Plan& p, size_t first, size_t end);
 enum class PlanDrop { Step, Dense };
 void plans_drop(BatchCtx* b, PlanDrop what);
 
+// every buffer, plan and graph of the context goes with it
 void batch_free(q3_engine* e) {
-    BatchCtx* b = e->batch;
-    if (!b) return;
-    void* dptrs[] = {b->att_pf, b->qn, b->pq, b->ps, b->x, b->q, b->kraw, b->xb, b->hb, b->logits, b->key, b->value, b->att, b->xq_p, b->xs_p,
-                     b->st, b->slots, b->out_tokens, b->stamps, b->d_sampler, b->d_probs, b->d_sp, b->d_keys, b->spec_io, b->spec_snap,
-                     b->spec_samp, b->spec_probs, b->spec_sp, b->spec_keys, b->col_slot, b->cols_ctl, b->cols_table, b->cols_ncols, b->cols_prompts,
-                     b->cols_out, b->cols_draw, b->cols_step, b->cols_slot_samp, b->cols_aux, b->cols_temp, b->cols_topp, b->cols_seeds, b->cols_stop, b->cols_req,
-                     b->dense.x, b->dense.q, b->dense.qn, b->dense.kraw, b->dense.xb, b->dense.hb, b->dense.xq_p, b->dense.xs_p, b->dense.st,
-                     b->dense.col_slot, b->dense.att_pf, b->dense_runs, b->prefix_store, b->embed_rows, b->embed_out, b->choice_cand, b->choice_out,
-                     b->score_rows, b->score_out, b->score_probs, b->score_top, b->score_rank, b->score_top_keys, b->score_top_above};
-    for (void* p : dptrs)
-        if (p) (void)hipFree(p);
-    if (b->h_st) (void)hipHostFree(b->h_st);
-    if (b->h_tokens) (void)hipHostFree(b->h_tokens);
-    if (b->h_logits) (void)hipHostFree(b->h_logits);
-    if (b->h_spec) (void)hipHostFree(b->h_spec);
-    if (b->h_cols) (void)hipHostFree(b->h_cols);
-    if (b->h_cols_draw) (void)hipHostFree(b->h_cols_draw);
-    if (b->h_cols_stop) (void)hipHostFree(b->h_cols_stop);
-    delete b;
+    delete e->batch;
     e->batch = nullptr;
 }
 
@@ -265,8 +240,8 @@ int batch_alloc(q3_engine* e, int max_streams, uint32_t ctx_len, bool with_kv, i
         b->m_w2.push_back(reserve(dim, H));
     }
     b->m_cls = reserve(V, dim);
-    HIP_TRY(hipMalloc((void**)&b->pq, qbytes));
-    HIP_TRY(hipMalloc((void**)&b->ps, 4 * sfloats));
+    int rc;
+    if ((rc = b->pq.alloc(qbytes)) || (rc = b->ps.alloc(sfloats))) return rc;
     auto pack = [&](const QT& t, int rows, int n, const BatchCtx::PM& m, int tile0, int tile_stride) {
         hipLaunchKernelGGL(k_pack_weights, dim3(e->n_cu * 8), dim3(kWG), 0, e->stream, t.q, t.s, b->pq + m.q_off, b->ps + m.s_off,
                            rows, n, G, tile0, tile_stride);
@@ -287,52 +262,65 @@ int batch_alloc(q3_engine* e, int max_streams, uint32_t ctx_len, bool with_kv, i
     b->kv_stream = (size_t)L * S * kvd;
     const size_t maxn = (size_t)(H > ahd ? (H > dim ? H : dim) : (ahd > dim ? ahd : dim));
     const size_t nt_max = (C + 15) / 16;
-    HIP_TRY(hipMalloc((void**)&b->x, 4 * C * dim));
-    HIP_TRY(hipMalloc((void**)&b->q, 4 * C * ahd));
-    HIP_TRY(hipMalloc((void**)&b->qn, 4 * C * ahd));
-    HIP_TRY(hipMalloc((void**)&b->kraw, 4 * C * kvd));
-    HIP_TRY(hipMalloc((void**)&b->xb, 4 * C * ahd));
-    HIP_TRY(hipMalloc((void**)&b->hb, 4 * C * H));
-    HIP_TRY(hipMalloc((void**)&b->logits, 4 * BL * V));
+    if ((rc = b->x.alloc(C * dim)) || (rc = b->q.alloc(C * ahd)) || (rc = b->qn.alloc(C * ahd)) || (rc = b->kraw.alloc(C * kvd)) ||
+        (rc = b->xb.alloc(C * ahd)) || (rc = b->hb.alloc(C * H)) || (rc = b->logits.alloc(BL * V)))
+        return rc;
     b->has_kv = with_kv;
     if (with_kv) {
-        HIP_TRY(hipMalloc((void**)&b->key, 4 * B * b->kv_stream));
-        HIP_TRY(hipMalloc((void**)&b->value, 4 * B * b->kv_stream));
+        if ((rc = b->key.alloc(B * b->kv_stream)) || (rc = b->value.alloc(B * b->kv_stream))) return rc;
         HIP_TRY(hipMemsetAsync(b->key, 0, 4 * B * b->kv_stream, e->stream));
         HIP_TRY(hipMemsetAsync(b->value, 0, 4 * B * b->kv_stream, e->stream));
     }
     HIP_TRY(hipMemsetAsync(b->x, 0, 4 * C * dim, e->stream));
-    HIP_TRY(hipMalloc((void**)&b->xq_p, nt_max * 16 * maxn));
-    HIP_TRY(hipMalloc((void**)&b->xs_p, 4 * nt_max * 16 * (maxn / G)));
+    if ((rc = b->xq_p.alloc(nt_max * 16 * maxn)) || (rc = b->xs_p.alloc(nt_max * 16 * (maxn / G)))) return rc;
     HIP_TRY(hipMemsetAsync(b->xq_p, 0, nt_max * 16 * maxn, e->stream));          // idle stream columns: finite operands
     HIP_TRY(hipMemsetAsync(b->xs_p, 0, 4 * nt_max * 16 * (maxn / G), e->stream));
-    if (S > (size_t)dev_knob("Q3_ATT_LDS_MAX", 4096)) HIP_TRY(hipMalloc((void**)&b->att, 4 * B * c.n_heads * S));
-    HIP_TRY(hipMalloc((void**)&b->st, sizeof(State) * C));
+    if (S > (size_t)dev_knob("Q3_ATT_LDS_MAX", 4096) && (rc = b->att.alloc(B * c.n_heads * S))) return rc;
+    if ((rc = b->st.alloc(C))) return rc;
     HIP_TRY(hipMemsetAsync(b->st, 0, sizeof(State) * C, e->stream));
     if (dev_knob("Q3_STAMPS", 0)) {
         const size_t nst = 96 * (size_t)(10 * L + 8);
-        HIP_TRY(hipMalloc((void**)&b->stamps, 8 * nst));
+        if ((rc = b->stamps.alloc(nst))) return rc;
         HIP_TRY(hipMemset(b->stamps, 0, 8 * nst));
     }
     b->nslots = e->n_cu * 4 * kWaves;
-    HIP_TRY(hipMalloc((void**)&b->slots, 8 * BL * (size_t)b->nslots));
+    if ((rc = b->slots.alloc(BL * (size_t)b->nslots))) return rc;
     HIP_TRY(hipMemsetAsync(b->slots, 0, 8 * BL * (size_t)b->nslots, e->stream));
-    HIP_TRY(hipMalloc((void**)&b->spec_io, sizeof(SpecIO)));
+    if ((rc = b->spec_io.alloc(1))) return rc;
     HIP_TRY(hipMemsetAsync(b->spec_io, 0, sizeof(SpecIO), e->stream));
-    HIP_TRY(hipMalloc((void**)&b->spec_snap, 4 * 2 * (size_t)L * (kSpecMax - 1) * kvd));
-    HIP_TRY(hipHostMalloc((void**)&b->h_spec, sizeof(SpecIO), hipHostMallocDefault));
+    if ((rc = b->spec_snap.alloc(2 * (size_t)L * (kSpecMax - 1) * kvd)) || (rc = b->h_spec.alloc(1))) return rc;
     b->out_cap = (int)S;
-    HIP_TRY(hipMalloc((void**)&b->out_tokens, 4 * B * S));
+    if ((rc = b->out_tokens.alloc(B * S))) return rc;
     HIP_TRY(hipMemsetAsync(b->out_tokens, 0, 4 * B * S, e->stream));
-    HIP_TRY(hipHostMalloc((void**)&b->h_st, sizeof(State) * B, hipHostMallocDefault));
-    HIP_TRY(hipHostMalloc((void**)&b->h_tokens, 4 * B * S, hipHostMallocDefault));
-    HIP_TRY(hipHostMalloc((void**)&b->h_logits, 4 * BL * V, hipHostMallocDefault));     // a column pass is kColsMax rows whatever max_streams is
-    HIP_TRY(hipMalloc((void**)&b->col_slot, 4 * kColsMax));
+    if ((rc = b->h_st.alloc(B)) || (rc = b->h_tokens.alloc(B * S))) return rc;
+    if ((rc = b->h_logits.alloc(BL * V))) return rc;     // a column pass is kColsMax rows whatever max_streams is
+    if ((rc = b->col_slot.alloc(kColsMax))) return rc;
     HIP_TRY(hipMemsetAsync(b->col_slot, 0, 4 * kColsMax, e->stream));
-    HIP_TRY(hipMalloc((void**)&b->cols_ctl, sizeof(ColsCtl)));
+    if ((rc = b->cols_ctl.alloc(1))) return rc;
     HIP_TRY(hipMemsetAsync(b->cols_ctl, 0, sizeof(ColsCtl), e->stream));
-    HIP_TRY(hipHostMalloc((void**)&b->h_cols, sizeof(ColsHost), hipHostMallocDefault));
+    if ((rc = b->h_cols.alloc(1))) return rc;
     HIP_TRY(hipStreamSynchronize(e->stream));
+    return Q3_OK;
+}
+
+// Score rows of k_attn_pf2, [columns][n_heads][stride floats], for a context of `need` positions (a multiple of 256): grow-only.
+// Nothing may outlive the old buffer: pointer, stride and the kept plans (their launches carry both) go first, so a failed
+// allocation leaves a state the next call rebuilds from instead of replaying launches on freed memory.
+// drop: the plans that carry this buffer; who, noun: the words of the message.
+int att_rows_grow(q3_engine* e, DevMem<float>& att_pf, int& stride, size_t columns, int need, PlanDrop drop, const char* who, const char* noun) {
+    if (need <= stride) return Q3_OK;
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    att_pf.reset();
+    stride = 0;
+    plans_drop(e->batch, drop);
+    const size_t floats = columns * (size_t)e->cfg.n_heads * (size_t)need;
+    size_t free_b = 0, total_b = 0;
+    (void)hipMemGetInfo(&free_b, &total_b);
+    if (4 * floats > free_b)
+        return fail(Q3_ERR_HIP, "%s: %zu MiB of score rows for blocks of %zu %s over %d positions of context do not fit "
+                    "(%zu MiB free): lower Q3_PREFILL_M", who, (4 * floats) >> 20, columns, noun, need, free_b >> 20);
+    if (int rc = att_pf.alloc(floats)) return rc;
+    stride = need;
     return Q3_OK;
 }
 
@@ -376,26 +364,9 @@ int q3_prefill_batched(q3_engine* e, const int32_t* tokens, size_t n_tokens, siz
     HIP_TRY(hipSetDevice(e->device));
     const size_t B = (size_t)b->cap;
     // score rows of k_attn_pf2: [block position][head][context so far, rounded up]
-    if (B > (size_t)kMaxStreams) {
-        const int need = (int)(((first_pos + n_tokens) + 255) & ~(size_t)255);
-        if (need > b->att_pf_stride) {
-            HIP_TRY(hipStreamSynchronize(e->stream));
-            if (b->att_pf) (void)hipFree(b->att_pf);
-            // nothing may outlive the old buffer: pointer, stride and the cached plan (its launches carry both) go first, so a
-            // failed allocation leaves a state the next call rebuilds from instead of replaying launches on freed memory
-            b->att_pf = nullptr;
-            b->att_pf_stride = 0;
-            plans_drop(b, PlanDrop::Step);
-            const size_t bytes = 4 * B * (size_t)e->cfg.n_heads * (size_t)need;
-            size_t free_b = 0, total_b = 0;
-            (void)hipMemGetInfo(&free_b, &total_b);
-            if (bytes > free_b)
-                return fail(Q3_ERR_HIP, "dense prefill: %zu MiB of score rows for blocks of %zu positions over %d positions of context do not fit "
-                            "(%zu MiB free): lower Q3_PREFILL_M", bytes >> 20, B, need, free_b >> 20);
-            HIP_TRY(hipMalloc((void**)&b->att_pf, bytes));
-            b->att_pf_stride = need;
-        }
-    }
+    if (B > (size_t)kMaxStreams &&
+        (rc = att_rows_grow(e, b->att_pf, b->att_pf_stride, B, (int)(((first_pos + n_tokens) + 255) & ~(size_t)255), PlanDrop::Step, "dense prefill", "positions")))
+        return rc;
     memcpy(e->h_tokens, tokens, 4 * n_tokens);
     HIP_TRY(hipMemcpyAsync(e->d_prompt, e->h_tokens, 4 * n_tokens, hipMemcpyHostToDevice, e->stream));
     int n_last = 0;
@@ -485,11 +456,11 @@ int q3_batch_sampler_set(q3_engine* e, float temperature, float topp, const uint
     size_t n2 = 1;
     while (n2 < (size_t)n) n2 <<= 1;
     const size_t scratch = (size_t)kSampThreads * blen;
-    if (!b->d_sampler) {
-        HIP_TRY(hipMalloc((void**)&b->d_sampler, sizeof(SamplerState) * B));
-        HIP_TRY(hipMalloc((void**)&b->d_probs, 4 * scratch * B));
-        HIP_TRY(hipMalloc((void**)&b->d_sp, 4 * scratch * B));
-        HIP_TRY(hipMalloc((void**)&b->d_keys, 2 * 8 * n2 * B));
+    if (!b->d_sampler) {          // one group, committed whole (q3_sampler_set)
+        DevMem<SamplerState> ss; DevMem<float> probs, sp; DevMem<unsigned long long> keys;
+        int rc;
+        if ((rc = ss.alloc(B)) || (rc = probs.alloc(scratch * B)) || (rc = sp.alloc(scratch * B)) || (rc = keys.alloc(2 * n2 * B))) return rc;
+        b->d_sampler = std::move(ss); b->d_probs = std::move(probs); b->d_sp = std::move(sp); b->d_keys = std::move(keys);
     }
     std::vector<SamplerState> h(B);
     for (int i = 0; i < B; ++i) h[i] = SamplerState{rng_seeds ? rng_seeds[i] : 0ull, temperature, topp, {0, 0, 0, 0}};
@@ -563,11 +534,14 @@ int spec_draw_alloc(q3_engine* e) {
     size_t n2 = 1;
     while (n2 < (size_t)n) n2 <<= 1;
     const size_t scratch = (size_t)kSampThreads * blen;
-    HIP_TRY(hipMalloc((void**)&b->spec_samp, sizeof(SamplerState) * kSpecMax));
-    HIP_TRY(hipMemsetAsync(b->spec_samp, 0, sizeof(SamplerState) * kSpecMax, e->stream));
-    HIP_TRY(hipMalloc((void**)&b->spec_probs, 4 * scratch * kSpecMax));
-    HIP_TRY(hipMalloc((void**)&b->spec_sp, 4 * scratch * kSpecMax));
-    HIP_TRY(hipMalloc((void**)&b->spec_keys, 2 * 8 * n2 * kSpecMax));
+    // one group, committed whole (q3_sampler_set): the callers take spec_samp for all four
+    DevMem<SamplerState> samp; DevMem<float> probs, sp; DevMem<unsigned long long> keys;
+    int rc;
+    if ((rc = samp.alloc(kSpecMax)) || (rc = probs.alloc(scratch * kSpecMax)) || (rc = sp.alloc(scratch * kSpecMax)) ||
+        (rc = keys.alloc(2 * n2 * kSpecMax)))
+        return rc;
+    HIP_TRY(hipMemsetAsync(samp, 0, sizeof(SamplerState) * kSpecMax, e->stream));
+    b->spec_samp = std::move(samp); b->spec_probs = std::move(probs); b->spec_sp = std::move(sp); b->spec_keys = std::move(keys);
     SampleArgs a{};
     a.logits = b->logits;
     a.n = n;

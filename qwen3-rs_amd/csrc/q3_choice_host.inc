@@ -39,11 +39,11 @@ int q3_choice_many(q3_engine* e, const int32_t* prompts, const size_t* prompt_le
     const size_t smem = choice_smem_bytes(dim, G);
     const unsigned parts = (unsigned)((k + kChoicePart - 1) / kChoicePart);
     q3_embed_stats st;
-    if ((rc = embed_walk(e, prompts, prompt_len, n_requests, (flags & Q3_CHOICE_PREFIX) != 0, n_cand > b->choice_cand_cap || n_out > b->choice_out_cap,
+    if ((rc = embed_walk(e, prompts, prompt_len, n_requests, (flags & Q3_CHOICE_PREFIX) != 0,
                          [&](const std::vector<DenseRun>&, const std::vector<EmbedStep>&) {
                              int rc2;
-                             if ((rc2 = cols_grow(b->choice_cand, b->choice_cand_cap, n_cand))) return rc2;
-                             if ((rc2 = cols_grow(b->choice_out, b->choice_out_cap, n_out))) return rc2;
+                             if ((rc2 = b->choice_cand.grow(n_cand, e->stream))) return rc2;
+                             if ((rc2 = b->choice_out.grow(n_out, e->stream))) return rc2;
                              HIP_TRY(hipMemcpyAsync(b->choice_cand, cand, 4 * n_cand, hipMemcpyHostToDevice, e->stream));
                              a.cand = b->choice_cand;
                              a.out = b->choice_out;

@@ -163,17 +163,6 @@ int cols_prepare(q3_engine* e, const char* who, bool draw = false) {
 // width (cols_draw_alloc has run by the time it is built: its launches carry the buffers allocated there).
 PlanKey cols_key(int n, bool draw) { return PlanKey{PlanKind::Cols, kColsWidths[cols_width_index(n)], draw}; }
 
-template <class T>
-int cols_grow(T*& ptr, size_t& cap, size_t need) {
-    if (need <= cap) return Q3_OK;
-    if (ptr) (void)hipFree(ptr);
-    ptr = nullptr;
-    cap = 0;
-    HIP_TRY(hipMalloc((void**)&ptr, sizeof(T) * need));
-    cap = need;
-    return Q3_OK;
-}
-
 // The buffers of the sampled passes, on first use: the column sampler states and the draw scratch of the verify pass
 // (spec_draw_alloc, 32 columns wide whatever max_streams is), the control block of k_cols_turn_draw, the one-pass table of a
 // host-made pass and the loop's per-slot sampler states.  Freed with the context.
@@ -183,12 +172,12 @@ int cols_draw_alloc(q3_engine* e) {
     if (!b->spec_samp && (rc = spec_draw_alloc(e))) return rc;
     if (b->h_cols_draw) return Q3_OK;
     HIP_TRY(hipSetDevice(e->device));
-    if (!b->cols_draw) HIP_TRY(hipMalloc((void**)&b->cols_draw, sizeof(ColsDraw)));
-    HIP_TRY(hipMemsetAsync(b->cols_draw, 0, sizeof(ColsDraw), e->stream));
-    if (!b->cols_step) HIP_TRY(hipMalloc((void**)&b->cols_step, sizeof(ColsStep)));
-    if (!b->cols_slot_samp) HIP_TRY(hipMalloc((void**)&b->cols_slot_samp, sizeof(SamplerState) * kMaxStreams));
-    HIP_TRY(hipMemsetAsync(b->cols_slot_samp, 0, sizeof(SamplerState) * kMaxStreams, e->stream));
-    HIP_TRY(hipHostMalloc((void**)&b->h_cols_draw, sizeof(ColsDrawHost), hipHostMallocDefault));
+    // one group, committed whole (q3_sampler_set)
+    DevMem<ColsDraw> draw; DevMem<ColsStep> step; DevMem<SamplerState> slot_samp; PinMem<ColsDrawHost> h_draw;
+    if ((rc = draw.alloc(1)) || (rc = step.alloc(1)) || (rc = slot_samp.alloc(kMaxStreams)) || (rc = h_draw.alloc(1))) return rc;
+    HIP_TRY(hipMemsetAsync(draw, 0, sizeof(ColsDraw), e->stream));
+    HIP_TRY(hipMemsetAsync(slot_samp, 0, sizeof(SamplerState) * kMaxStreams, e->stream));
+    b->cols_draw = std::move(draw); b->cols_step = std::move(step); b->cols_slot_samp = std::move(slot_samp); b->h_cols_draw = std::move(h_draw);
     return Q3_OK;
 }
 
@@ -199,9 +188,9 @@ int cols_sampler_upload(q3_engine* e, SamplerState* slot_ss, const ColAux* aux, 
     int rc;
     BatchCtx* b = e->batch;
     if (temperature) {
-        if ((rc = cols_grow(b->cols_temp, b->cols_temp_cap, n_requests))) return rc;
-        if ((rc = cols_grow(b->cols_topp, b->cols_topp_cap, n_requests))) return rc;
-        if ((rc = cols_grow(b->cols_seeds, b->cols_seeds_cap, n_requests))) return rc;
+        if ((rc = b->cols_temp.grow(n_requests, e->stream))) return rc;
+        if ((rc = b->cols_topp.grow(n_requests, e->stream))) return rc;
+        if ((rc = b->cols_seeds.grow(n_requests, e->stream))) return rc;
         HIP_TRY(hipMemcpyAsync(b->cols_temp, temperature, 4 * n_requests, hipMemcpyHostToDevice, e->stream));
         HIP_TRY(hipMemcpyAsync(b->cols_topp, topp, 4 * n_requests, hipMemcpyHostToDevice, e->stream));
         HIP_TRY(hipMemcpyAsync(b->cols_seeds, seeds, 8 * n_requests, hipMemcpyHostToDevice, e->stream));
@@ -364,11 +353,11 @@ int cols_job_run(q3_engine* e, ColsJob& job, bool draw, const ColsJobSampler& sm
 
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(hipStreamSynchronize(e->stream));              // nothing in flight reads the buffers that may be re-allocated
-    if ((rc = cols_grow(b->cols_table, b->cols_table_cap, n_passes * kColsMax))) return rc;
-    if ((rc = cols_grow(b->cols_ncols, b->cols_ncols_cap, n_passes))) return rc;
-    if ((rc = cols_grow(b->cols_prompts, b->cols_prompts_cap, n_prompt))) return rc;
-    if ((rc = cols_grow(b->cols_out, b->cols_out_cap, n_out))) return rc;
-    if ((rc = cols_grow(b->dense_runs, b->dense_runs_cap, job.runs.size()))) return rc;
+    if ((rc = b->cols_table.grow(n_passes * kColsMax, e->stream))) return rc;
+    if ((rc = b->cols_ncols.grow(n_passes, e->stream))) return rc;
+    if ((rc = b->cols_prompts.grow(n_prompt, e->stream))) return rc;
+    if ((rc = b->cols_out.grow(n_out, e->stream))) return rc;
+    if ((rc = b->dense_runs.grow(job.runs.size(), e->stream))) return rc;
     if (n_passes) {
         HIP_TRY(hipMemcpyAsync(b->cols_table, job.table.data(), sizeof(ColEnt) * n_passes * kColsMax, hipMemcpyHostToDevice, e->stream));
         HIP_TRY(hipMemcpyAsync(b->cols_ncols, job.ncols.data(), 4 * n_passes, hipMemcpyHostToDevice, e->stream));
@@ -376,7 +365,7 @@ int cols_job_run(q3_engine* e, ColsJob& job, bool draw, const ColsJobSampler& sm
     HIP_TRY(hipMemcpyAsync(b->cols_prompts, prompts, 4 * n_prompt, hipMemcpyHostToDevice, e->stream));
     if (!job.runs.empty()) HIP_TRY(hipMemcpyAsync(b->dense_runs, job.runs.data(), sizeof(DenseRun) * job.runs.size(), hipMemcpyHostToDevice, e->stream));
     if (draw && n_passes) {
-        if ((rc = cols_grow(b->cols_aux, b->cols_aux_cap, n_passes * kColsMax))) return rc;
+        if ((rc = b->cols_aux.grow(n_passes * kColsMax, e->stream))) return rc;
         HIP_TRY(hipMemcpyAsync(b->cols_aux, job.aux.data(), sizeof(ColAux) * n_passes * kColsMax, hipMemcpyHostToDevice, e->stream));
         if ((rc = cols_sampler_upload(e, smp.slot_ss, b->cols_aux, smp.temperature, smp.topp, smp.seeds, smp.n_requests))) return rc;
     }

@@ -69,13 +69,6 @@ int dense_block_cap(q3_engine* e) {
     return b->dense_cap;
 }
 
-void dense_scratch_free(BlockScratch& d) {
-    void* ptrs[] = {d.x, d.q, d.qn, d.kraw, d.xb, d.hb, d.xq_p, d.xs_p, d.st, d.col_slot, d.att_pf};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    d = BlockScratch{};
-}
-
 // The scratch of a dense block over the slots, on first use: the per-column buffers of batch_alloc for dense_block_cap() columns.
 // The 32-column scratch, the kept decode / column plans and their graphs are not touched.
 int dense_scratch_get(q3_engine* e) {
@@ -92,49 +85,27 @@ int dense_scratch_get(q3_engine* e) {
     if (bytes > free_b)
         return fail(Q3_ERR_HIP, "dense slot prefill: %zu MiB of block scratch for blocks of %zu columns do not fit (%zu MiB free): lower Q3_PREFILL_M",
                     bytes >> 20, C, free_b >> 20);
-    BlockScratch d;
-    auto get = [&](void** p, size_t n) { return hipMalloc(p, n); };
-    const bool ok = get((void**)&d.x, 4 * C * dim) == hipSuccess && get((void**)&d.q, 4 * C * ahd) == hipSuccess &&
-                    get((void**)&d.qn, 4 * C * ahd) == hipSuccess && get((void**)&d.kraw, 4 * C * kvd) == hipSuccess &&
-                    get((void**)&d.xb, 4 * C * ahd) == hipSuccess && get((void**)&d.hb, 4 * C * H) == hipSuccess &&
-                    get((void**)&d.xq_p, nt * 16 * maxn) == hipSuccess && get((void**)&d.xs_p, 4 * nt * 16 * (maxn / G)) == hipSuccess &&
-                    get((void**)&d.st, sizeof(State) * C) == hipSuccess && get((void**)&d.col_slot, 4 * C) == hipSuccess;
-    if (!ok) {
+    BlockScratch d;              // built here, committed whole: a failure frees what it got on the way out
+    if (d.x.alloc(C * dim) || d.q.alloc(C * ahd) || d.qn.alloc(C * ahd) || d.kraw.alloc(C * kvd) || d.xb.alloc(C * ahd) || d.hb.alloc(C * H) ||
+        d.xq_p.alloc(nt * 16 * maxn) || d.xs_p.alloc(nt * 16 * (maxn / G)) || d.st.alloc(C) || d.col_slot.alloc(C)) {
         (void)hipGetLastError();
-        dense_scratch_free(d);
         return fail(Q3_ERR_HIP, "dense slot prefill: allocating %zu MiB of block scratch for blocks of %zu columns failed: lower Q3_PREFILL_M", bytes >> 20, C);
     }
     d.cap = (int)C;
-    b->dense = d;
-    HIP_TRY(hipMemsetAsync(d.x, 0, 4 * C * dim, e->stream));
-    HIP_TRY(hipMemsetAsync(d.xq_p, 0, nt * 16 * maxn, e->stream));                  // columns past a block's end: finite operands
-    HIP_TRY(hipMemsetAsync(d.xs_p, 0, 4 * nt * 16 * (maxn / G), e->stream));
-    HIP_TRY(hipMemsetAsync(d.st, 0, sizeof(State) * C, e->stream));
-    HIP_TRY(hipMemsetAsync(d.col_slot, 0, 4 * C, e->stream));
+    b->dense = std::move(d);
+    HIP_TRY(hipMemsetAsync(b->dense.x, 0, 4 * C * dim, e->stream));
+    HIP_TRY(hipMemsetAsync(b->dense.xq_p, 0, nt * 16 * maxn, e->stream));           // columns past a block's end: finite operands
+    HIP_TRY(hipMemsetAsync(b->dense.xs_p, 0, 4 * nt * 16 * (maxn / G), e->stream));
+    HIP_TRY(hipMemsetAsync(b->dense.st, 0, sizeof(State) * C, e->stream));
+    HIP_TRY(hipMemsetAsync(b->dense.col_slot, 0, 4 * C, e->stream));
     return Q3_OK;
 }
 
 // score rows of k_attn_pf2 for blocks whose columns attend over up to `max_end` positions: [column][head][context, rounded up],
 // grown as q3_prefill_batched grows its own.  The kept block plans carry pointer and stride: they go with the old buffer.
 int dense_att_grow(q3_engine* e, size_t max_end) {
-    BatchCtx* b = e->batch;
-    BlockScratch& d = b->dense;
-    const int need = (int)((max_end + 255) & ~(size_t)255);
-    if (need <= d.att_pf_stride) return Q3_OK;
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    if (d.att_pf) (void)hipFree(d.att_pf);
-    d.att_pf = nullptr;
-    d.att_pf_stride = 0;
-    plans_drop(b, PlanDrop::Dense);
-    const size_t bytes = 4 * (size_t)d.cap * (size_t)e->cfg.n_heads * (size_t)need;
-    size_t free_b = 0, total_b = 0;
-    (void)hipMemGetInfo(&free_b, &total_b);
-    if (bytes > free_b)
-        return fail(Q3_ERR_HIP, "dense slot prefill: %zu MiB of score rows for blocks of %d columns over %d positions of context do not fit "
-                    "(%zu MiB free): lower Q3_PREFILL_M", bytes >> 20, d.cap, need, free_b >> 20);
-    HIP_TRY(hipMalloc((void**)&d.att_pf, bytes));
-    d.att_pf_stride = need;
-    return Q3_OK;
+    BlockScratch& d = e->batch->dense;
+    return att_rows_grow(e, d.att_pf, d.att_pf_stride, (size_t)d.cap, (int)((max_end + 255) & ~(size_t)255), PlanDrop::Dense, "dense slot prefill", "columns");
 }
 
 // one block: the states and the slot table of its n columns from the device run table, then the layers (the kept

@@ -17,16 +17,16 @@ struct EmbedStep { bool wide; int n; size_t r0, nr, g0, ng; };
 // The walk q3_embed_many and q3_choice_many (q3_choice_host.inc) share: the lengths become waves, blocks, runs and a row table; the
 // plans and the buffers of the walk are made; the prompts and tables go up, the prefix rows into the slots, and block after block is
 // enqueued, each followed by the caller's tail launch.  Nothing is copied back and nothing is waited for: that is the caller's.
-//   regrow: the caller's grow() re-allocates a buffer, so the stream is waited for first, as for the walk's own buffers
 //   grow(runs, steps): called once, behind the walk's own allocations and in front of the first enqueue: the caller's buffers and
-//                          uploads.  It sees the schedule: steps[i] is block i, runs[steps[i].r0 .. + steps[i].nr) ALL of its runs in
-//                          column order (q3_score_many, q3_score_host.inc, makes its table of scored columns from them)
+//                          uploads (a buffer that re-allocates waits for the stream itself: DevMem::grow).  It sees the schedule:
+//                          steps[i] is block i, runs[steps[i].r0 .. + steps[i].nr) ALL of its runs in column order (q3_score_many,
+//                          q3_score_host.inc, makes its table of scored columns from them)
 //   tail(rows, n_rows, x, i): the rows {column, request} of the prompts that end in block i, just enqueued (device table), and the
 //                          block's residuals x[column][dim]: enqueue the kernel that reads them.  Called for a block in which a
 //                          prompt ends (n_rows > 0); with every_block, for every block
 // st: the schedule's stats, valid when the walk returns Q3_OK.
 template <class Grow, class Tail>
-int embed_walk(q3_engine* e, const int32_t* prompts, const size_t* prompt_len, size_t n_requests, bool use_prefix, bool regrow, Grow grow, Tail tail,
+int embed_walk(q3_engine* e, const int32_t* prompts, const size_t* prompt_len, size_t n_requests, bool use_prefix, Grow grow, Tail tail,
                q3_embed_stats& st, bool every_block = false) {
     BatchCtx* b = e->batch;
     int rc;
@@ -107,11 +107,9 @@ int embed_walk(q3_engine* e, const int32_t* prompts, const size_t* prompt_len, s
             if (steps[i].wide && (rc = plan_get(e, PlanKey{PlanKind::SlotPrefill, steps[i].n, false}, &wide_plans[i]))) return rc;
     }
     HIP_TRY(hipSetDevice(e->device));
-    if (n_tok > b->cols_prompts_cap || runs.size() > b->dense_runs_cap || rows.size() > b->embed_rows_cap || regrow)
-        HIP_TRY(hipStreamSynchronize(e->stream));          // nothing in flight reads a buffer that is re-allocated
-    if ((rc = cols_grow(b->cols_prompts, b->cols_prompts_cap, n_tok))) return rc;
-    if ((rc = cols_grow(b->dense_runs, b->dense_runs_cap, runs.size()))) return rc;
-    if ((rc = cols_grow(b->embed_rows, b->embed_rows_cap, rows.size()))) return rc;
+    if ((rc = b->cols_prompts.grow(n_tok, e->stream))) return rc;
+    if ((rc = b->dense_runs.grow(runs.size(), e->stream))) return rc;
+    if ((rc = b->embed_rows.grow(rows.size(), e->stream))) return rc;
     if ((rc = grow(runs, steps))) return rc;
 
     // the call on the stream: three uploads, the prefix rows, block after block with its tail
@@ -160,8 +158,8 @@ int q3_embed_many(q3_engine* e, const int32_t* prompts, const size_t* prompt_len
     const size_t n_out = n_requests * out_dim;
     const size_t smem = 4 * (size_t)term_floats((int)dim);
     q3_embed_stats st;
-    if ((rc = embed_walk(e, prompts, prompt_len, n_requests, (flags & Q3_EMBED_PREFIX) != 0, n_out > b->embed_out_cap,
-                         [&](const std::vector<DenseRun>&, const std::vector<EmbedStep>&) { return cols_grow(b->embed_out, b->embed_out_cap, n_out); },
+    if ((rc = embed_walk(e, prompts, prompt_len, n_requests, (flags & Q3_EMBED_PREFIX) != 0,
+                         [&](const std::vector<DenseRun>&, const std::vector<EmbedStep>&) { return b->embed_out.grow(n_out, e->stream); },
                          [&](const EmbedRow* rows, size_t n_rows, const float* x, size_t) {
                              return launch_now(e->stream, k_embed_rows, dim3((unsigned)n_rows), dim3(kWG), smem, rows, x, (const float*)e->rms_final,
                                                (int)dim, (int)out_dim, (flags & Q3_EMBED_L2) ? kEmbedL2 : 0u, b->embed_out);

@@ -261,6 +261,16 @@ struct Graph {
     }
 };
 
+// The engine's stream: a member declared in front of every buffer and graph that lives on it, so it is destroyed behind them.
+struct Stream {
+    hipStream_t s = nullptr;
+    Stream() = default;
+    Stream(const Stream&) = delete;
+    Stream& operator=(const Stream&) = delete;
+    ~Stream() { if (s) (void)hipStreamDestroy(s); }
+    operator hipStream_t() const { return s; }
+};
+
 // Environment variables.  The product library reads only the documented ones (include/qwen3_hip.h, "Environment"):
 // env_int().  Everything else -- A/B switches between kernel forms that are product code for other shapes, workgroup overrides, timeline
 // switches -- exists in the developer build only (make dev, -DQ3_DEV): dev_knob() is its default in the product.
@@ -277,6 +287,8 @@ int env_int(const char* name, int dflt) {
 
 }  // namespace
 
+#include "q3_mem.h"
+
 struct BatchCtx;
 struct q3_engine;
 namespace { void batch_free(q3_engine* e); }
@@ -286,35 +298,35 @@ struct q3_engine {
     uint32_t flags = 0;
     int device = 0;
     int n_cu = 256;
-    hipStream_t stream = nullptr;
+    Stream stream;
     // device memory
-    uint8_t* d_blob = nullptr;
+    DevMem<uint8_t> d_blob;
     size_t blob_bytes = 0;
     const float *rms_att = nullptr, *rms_ffn = nullptr, *rms_final = nullptr, *q_ln = nullptr, *k_ln = nullptr;
     QT tok, wcls;
     std::vector<QT> wq, wk, wv, wo, w1, w2, w3;
-    float *d_x = nullptr, *d_q = nullptr, *d_kraw = nullptr, *d_xb = nullptr, *d_hb = nullptr, *d_logits = nullptr;
-    float *d_tap = nullptr, *d_key = nullptr, *d_value = nullptr, *d_rope = nullptr, *d_att = nullptr;
-    float* d_value_t = nullptr;                // transposed copy of the value cache, [L][kv_dim][seq_len]: what k_attn_out streams (long contexts)
-    int8_t* d_xbq = nullptr;                   // attention output quantized by k_attn_short (operand of the PRO_PREQR Wo launch)
-    float* d_xbs = nullptr;
-    State* d_state = nullptr;
-    int32_t* d_out_tokens = nullptr;
-    int32_t* d_prompt = nullptr;               // chat-mode prefill: prompt token ids (capacity out_cap)
+    DevMem<float> d_x, d_q, d_kraw, d_xb, d_hb, d_logits;
+    DevMem<float> d_tap, d_key, d_value, d_rope, d_att;
+    DevMem<float> d_value_t;                   // transposed copy of the value cache, [L][kv_dim][seq_len]: what k_attn_out streams (long contexts)
+    DevMem<int8_t> d_xbq;                      // attention output quantized by k_attn_short (operand of the PRO_PREQR Wo launch)
+    DevMem<float> d_xbs;
+    DevMem<State> d_state;
+    DevMem<int32_t> d_out_tokens;
+    DevMem<int32_t> d_prompt;                  // chat-mode prefill: prompt token ids (capacity out_cap)
     int out_cap = 0;
-    unsigned long long* d_stamps = nullptr;   // developer timeline (Q3_STAMPS=1) / kernel begin-end cells (Q3_KSTAMPS=1)
-    unsigned long long* d_kacc = nullptr;     // Q3_KSTAMPS=1: per-launch duration / gap sums (k_kstamp_fold)
-    unsigned long long* d_kslots = nullptr;   //   per-wave begin / end slots of every launch, [launch][kKstampSlots][2]
-    unsigned long long* d_kcells = nullptr;   //   per-launch {begin, end} of the current token (k_kstamp_reduce)
-    int* d_knslots = nullptr;                 //   live wave slots of every launch
+    DevMem<unsigned long long> d_stamps;      // developer timeline (Q3_STAMPS=1) / kernel begin-end cells (Q3_KSTAMPS=1)
+    DevMem<unsigned long long> d_kacc;        // Q3_KSTAMPS=1: per-launch duration / gap sums (k_kstamp_fold)
+    DevMem<unsigned long long> d_kslots;      //   per-wave begin / end slots of every launch, [launch][kKstampSlots][2]
+    DevMem<unsigned long long> d_kcells;      //   per-launch {begin, end} of the current token (k_kstamp_reduce)
+    DevMem<int> d_knslots;                    //   live wave slots of every launch
     bool kstamps = false;
-    unsigned long long* d_argmax_slots = nullptr;
-    unsigned long long* d_next_cell = nullptr;   // {argmax cell, ticket counter} of the classifier launch with k_next folded in
+    DevMem<unsigned long long> d_argmax_slots;
+    DevMem<unsigned long long> d_next_cell;      // {argmax cell, ticket counter} of the classifier launch with k_next folded in
     int n_argmax_slots = 0;
     // pinned host staging
-    float* h_logits = nullptr;
-    State* h_state = nullptr;
-    int32_t* h_tokens = nullptr;
+    PinMem<float> h_logits;
+    PinMem<State> h_state;
+    PinMem<int32_t> h_tokens;
     // launch plans: `plan` (one attention kernel per layer) for short contexts, `plan_long` (scores + out
     // kernels over many workgroups) once pos >= split_pos; the host knows pos of every forward it enqueues
     std::vector<Launch> plan, plan_long;
@@ -323,7 +335,7 @@ struct q3_engine {
     // captured chains, indexed [short, long]: `decode` is the token's kernels; `forward` is q3_forward as ONE graph launch -- state
     // upload (pinned h_state) -> the token's kernels -> logits download (pinned h_logits)
     Graph decode[2], forward[2];
-    float* d_att_priv = nullptr;
+    DevMem<float> d_att_priv;
     int split_pos = 256;
     // the transposed value cache exists iff the long-context output kernel will read it: reference-order mode (k_attn_out reads it
     // only when strict), a context that reaches split_pos, rows of whole float4, and the caller did not opt out
@@ -334,11 +346,11 @@ struct q3_engine {
     BatchCtx* batch = nullptr;                 // batched decode state (q3_batch_init), see q3_batch_host.inc
     // device-side Sampler (q3_sampler_set): temperature > 0 makes every token draw go through k_sample
     bool sampling = false;
-    SamplerState* d_sampler = nullptr;
-    float* d_samp_hist = nullptr;        // pipelined draw: mass histogram, per-workgroup candidate counts
-    int* d_samp_counts = nullptr;
-    float *d_probs = nullptr, *d_sp = nullptr;
-    unsigned long long* d_keys = nullptr;
+    DevMem<SamplerState> d_sampler;
+    DevMem<float> d_samp_hist;           // pipelined draw: mass histogram, per-workgroup candidate counts
+    DevMem<int> d_samp_counts;
+    DevMem<float> d_probs, d_sp;
+    DevMem<unsigned long long> d_keys;
     size_t keys_n2 = 0;
     std::vector<Launch> sample_plan;     // the draw behind a forward (q3_sampler_set)
     int enqueue_sample();
@@ -348,7 +360,7 @@ struct q3_engine {
     int capture();
     int enqueue_forward(size_t pos, bool draw = true);
     int set_state(size_t token, size_t pos);
-    void release();
+    ~q3_engine() { batch_free(this); }       // the batched state, then the members in reverse order: the stream last
 };
 
 namespace {
@@ -523,18 +535,6 @@ int plan_role(GemvLaunch& Ln, GemvArgs& a, int pro, int epi, int n, int units, i
 
 }  // namespace
 
-void q3_engine::release() {
-    batch_free(this);
-    for (int i = 0; i < 2; ++i) { decode[i].reset(); forward[i].reset(); }
-    void* dptrs[] = {d_value_t, d_kacc, d_kslots, d_kcells, d_knslots, d_next_cell, d_xbq, d_xbs, d_samp_hist, d_samp_counts, d_sampler, d_probs, d_sp, d_keys, d_prompt, d_att_priv, d_argmax_slots, d_stamps, d_blob, d_x, d_q, d_kraw, d_xb, d_hb, d_logits, d_tap, d_key, d_value, d_rope, d_att, d_state, d_out_tokens};
-    for (void* p : dptrs)
-        if (p) (void)hipFree(p);
-    if (h_logits) (void)hipHostFree(h_logits);
-    if (h_state) (void)hipHostFree(h_state);
-    if (h_tokens) (void)hipHostFree(h_tokens);
-    if (stream) (void)hipStreamDestroy(stream);
-}
-
 // utils.rs MemoryMapper + qwen3.rs:199-277 load_weights: walk the file with a cursor, upload it once.
 int q3_engine::load(const char* path, uint32_t ctx_len) {
     const int fd = open(path, O_RDONLY);
@@ -616,11 +616,11 @@ int q3_engine::load(const char* path, uint32_t ctx_len) {
     hipDeviceProp_t prop;
     HIP_TRY(hipGetDeviceProperties(&prop, device));
     n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    HIP_TRY(hipStreamCreateWithFlags(&stream.s, hipStreamNonBlocking));
 
     // the whole file becomes one resident HBM blob, layout unchanged (zero repack)
     blob_bytes = off;
-    HIP_TRY(hipMalloc((void**)&d_blob, blob_bytes));
+    if ((rc = d_blob.alloc(blob_bytes))) return rc;
     HIP_TRY(hipMemcpy(d_blob, base, blob_bytes, hipMemcpyHostToDevice));
     auto fp = [&](size_t o) { return (const float*)(d_blob + o); };
     auto qt = [&](const QOff& o) {
@@ -649,35 +649,27 @@ int q3_engine::load(const char* path, uint32_t ctx_len) {
     // run state (qwen3.rs:414-445); KV cache zero-filled: generate mode attends over never-written rows
     const size_t S = cfg.seq_len;
     const size_t kv_elems = L * S * kvd;
-    HIP_TRY(hipMalloc((void**)&d_x, 4 * dim));
-    HIP_TRY(hipMalloc((void**)&d_q, 4 * ahd));
-    HIP_TRY(hipMalloc((void**)&d_kraw, 4 * kvd));
-    HIP_TRY(hipMalloc((void**)&d_xb, 4 * ahd));
-    HIP_TRY(hipMalloc((void**)&d_hb, 4 * H));
-    HIP_TRY(hipMalloc((void**)&d_logits, 4 * V));
-    HIP_TRY(hipMalloc((void**)&d_tap, 4 * dim));
-    HIP_TRY(hipMalloc((void**)&d_key, 4 * kv_elems));
-    HIP_TRY(hipMalloc((void**)&d_value, 4 * kv_elems));
+    if ((rc = d_x.alloc(dim)) || (rc = d_q.alloc(ahd)) || (rc = d_kraw.alloc(kvd)) || (rc = d_xb.alloc(ahd)) || (rc = d_hb.alloc(H)) ||
+        (rc = d_logits.alloc(V)) || (rc = d_tap.alloc(dim)) || (rc = d_key.alloc(kv_elems)) || (rc = d_value.alloc(kv_elems)))
+        return rc;
     HIP_TRY(hipMemset(d_key, 0, 4 * kv_elems));
     HIP_TRY(hipMemset(d_value, 0, 4 * kv_elems));
     // the long-context plan streams a transposed copy of the value rows (k_attn_out, strict mode only; contexts that can reach the
     // split position only -- split_pos is set here, once, and build_plan uses the same value)
     split_pos = dev_knob("Q3_ATT_SPLIT_POS", 256);
     if (wants_value_t()) {
-        HIP_TRY(hipMalloc((void**)&d_value_t, 4 * kv_elems));
+        if ((rc = d_value_t.alloc(kv_elems))) return rc;
         HIP_TRY(hipMemset(d_value_t, 0, 4 * kv_elems));
     }
     HIP_TRY(hipMemset(d_x, 0, 4 * dim));
-    HIP_TRY(hipMalloc((void**)&d_state, sizeof(State)));
+    if ((rc = d_state.alloc(1))) return rc;
     HIP_TRY(hipMemset(d_state, 0, sizeof(State)));
     out_cap = (int)S;
-    HIP_TRY(hipMalloc((void**)&d_out_tokens, 4 * (size_t)out_cap));
+    if ((rc = d_out_tokens.alloc((size_t)out_cap))) return rc;
     HIP_TRY(hipMemset(d_out_tokens, 0, 4 * (size_t)out_cap));
-    HIP_TRY(hipMalloc((void**)&d_prompt, 4 * (size_t)out_cap));
+    if ((rc = d_prompt.alloc((size_t)out_cap))) return rc;
     HIP_TRY(hipMemset(d_prompt, 0, 4 * (size_t)out_cap));
-    HIP_TRY(hipHostMalloc((void**)&h_logits, 4 * V, hipHostMallocDefault));
-    HIP_TRY(hipHostMalloc((void**)&h_state, sizeof(State), hipHostMallocDefault));
-    HIP_TRY(hipHostMalloc((void**)&h_tokens, 4 * (size_t)out_cap, hipHostMallocDefault));
+    if ((rc = h_logits.alloc(V)) || (rc = h_state.alloc(1)) || (rc = h_tokens.alloc((size_t)out_cap))) return rc;
 
     // RoPE table with the host libm, exactly RoPE::compute_freqs (layers.rs:161-171)
     {
@@ -691,7 +683,7 @@ int q3_engine::load(const char* path, uint32_t ctx_len) {
                 tab[p * hd + 2 * i] = cosf(angle);
                 tab[p * hd + 2 * i + 1] = sinf(angle);
             }
-        HIP_TRY(hipMalloc((void**)&d_rope, 4 * tab.size()));
+        if ((rc = d_rope.alloc(tab.size()))) return rc;
         HIP_TRY(hipMemcpy(d_rope, tab.data(), 4 * tab.size(), hipMemcpyHostToDevice));
     }
     return Q3_OK;
@@ -709,22 +701,22 @@ int q3_engine::build_plan() {
     const int slice_w = attn_slice_w(hd, cfg.n_heads, n_cu);
     const int nsl = hd / slice_w;
     const bool use_att_global = S > att_lds_max;
-    HIP_TRY(hipMalloc((void**)&d_att, 4 * (size_t)cfg.n_heads * ((size_t)att_stride + cmax_stride)));   // score rows, then their 64-block maxima
-    HIP_TRY(hipMalloc((void**)&d_att_priv, 4 * (size_t)cfg.n_heads * nsl * att_stride));
+    int rc;
+    if ((rc = d_att.alloc((size_t)cfg.n_heads * ((size_t)att_stride + cmax_stride)))) return rc;   // score rows, then their 64-block maxima
+    if ((rc = d_att_priv.alloc((size_t)cfg.n_heads * nsl * att_stride))) return rc;
     kstamps = dev_knob("Q3_KSTAMPS", 0) != 0;
     if (dev_knob("Q3_STAMPS", 0) || kstamps) {
-        HIP_TRY(hipMalloc((void**)&d_stamps, 8 * 16 * (size_t)(5 * L + 4)));
+        if ((rc = d_stamps.alloc(16 * (size_t)(5 * L + 4)))) return rc;
         HIP_TRY(hipMemset(d_stamps, 0, 8 * 16 * (size_t)(5 * L + 4)));
     }
 #ifdef Q3_DEV
     if (kstamps) {
         const size_t nl = (size_t)(5 * L + 4);
-        HIP_TRY(hipMalloc((void**)&d_kslots, 16 * (size_t)kKstampSlots * nl));
+        if ((rc = d_kslots.alloc(2 * (size_t)kKstampSlots * nl))) return rc;
         HIP_TRY(hipMemset(d_kslots, 0, 16 * (size_t)kKstampSlots * nl));
-        HIP_TRY(hipMalloc((void**)&d_kcells, 16 * nl));
-        HIP_TRY(hipMalloc((void**)&d_knslots, 4 * nl));
+        if ((rc = d_kcells.alloc(2 * nl)) || (rc = d_knslots.alloc(nl))) return rc;
         HIP_TRY(hipMemset(d_knslots, 0, 4 * nl));
-        HIP_TRY(hipMalloc((void**)&d_kacc, 8 * (2 + 2 * nl)));
+        if ((rc = d_kacc.alloc(2 + 2 * nl))) return rc;
         HIP_TRY(hipMemset(d_kacc, 0, 8 * (2 + 2 * nl)));
     }
 #endif
@@ -739,7 +731,6 @@ int q3_engine::build_plan() {
         a.seq_len = S;
         return a;
     };
-    int rc;
     // developer timelines: the cells of the launch about to be appended to `plan` (tools/kstamps.py and the *_stamps.py tools index by it)
     auto stamp_cells = [&]() -> unsigned long long* {
         if (!d_stamps) return nullptr;
@@ -756,8 +747,7 @@ int q3_engine::build_plan() {
         return make_launch(Ln, fam, g.fn, dim3(g.grid), dim3(g.block), g.smem, a);
     };
     auto push_both = [&](const Launch& Ln) { plan.push_back(Ln); plan_long.push_back(Ln); };
-    HIP_TRY(hipMalloc((void**)&d_xbq, (size_t)ahd));
-    HIP_TRY(hipMalloc((void**)&d_xbs, 4 * (size_t)(ahd / G)));
+    if ((rc = d_xbq.alloc((size_t)ahd)) || (rc = d_xbs.alloc((size_t)(ahd / G)))) return rc;
     Launch Ln;
     for (int l = 0; l < L; ++l) {
         const size_t kv_off = (size_t)l * S * kvd;
@@ -870,11 +860,11 @@ int q3_engine::build_plan() {
         GemvLaunch g;
         if ((rc = plan_role(g, a, PRO_NORM, EPI_LOGITS, dim, V, G, fast_fold, 1, n_cu))) return rc;
         n_argmax_slots = (int)g.grid;
-        HIP_TRY(hipMalloc((void**)&d_argmax_slots, 8 * (size_t)n_argmax_slots));
+        if ((rc = d_argmax_slots.alloc((size_t)n_argmax_slots))) return rc;
         HIP_TRY(hipMemset(d_argmax_slots, 0, 8 * (size_t)n_argmax_slots));
         a.argmax_slots = d_argmax_slots;
         stamp(a);
-        HIP_TRY(hipMalloc((void**)&d_next_cell, 16));
+        if ((rc = d_next_cell.alloc(2))) return rc;
         HIP_TRY(hipMemset(d_next_cell, 0, 16));
         a.next_cell = d_next_cell;
         a.out_tokens = d_out_tokens;
@@ -989,7 +979,6 @@ int q3_create(const char* checkpoint_path, uint32_t ctx_len, int device, uint32_
     if (rc == Q3_OK) rc = e->build_plan();
     if (rc == Q3_OK && !(flags & Q3_FLAG_NO_GRAPH)) rc = e->capture();
     if (rc != Q3_OK) {
-        e->release();
         delete e;
         return rc;
     }
@@ -1001,7 +990,6 @@ void q3_destroy(q3_engine* e) {
     if (!e) return;
     (void)hipSetDevice(e->device);
     if (e->stream) (void)hipStreamSynchronize(e->stream);
-    e->release();
     delete e;
 }
 
@@ -1193,12 +1181,14 @@ int q3_sampler_set(q3_engine* e, float temperature, float topp, uint64_t rng_see
     if (!e->d_sampler) {
         size_t n2 = 1;
         while (n2 < (size_t)n) n2 <<= 1;
-        HIP_TRY(hipMalloc((void**)&e->d_sampler, sizeof(SamplerState)));
-        HIP_TRY(hipMalloc((void**)&e->d_probs, 4 * (size_t)kSampThreads * blen));
-        HIP_TRY(hipMalloc((void**)&e->d_sp, 4 * (size_t)kSampThreads * blen));
-        HIP_TRY(hipMalloc((void**)&e->d_keys, 2 * 8 * n2));
-        HIP_TRY(hipMalloc((void**)&e->d_samp_hist, 4 * kSampHistBins));
-        HIP_TRY(hipMalloc((void**)&e->d_samp_counts, 4 * kSampGrid));
+        // one group, committed whole: a failed allocation leaves the engine with none of it, and the next call starts over
+        DevMem<SamplerState> ss; DevMem<float> probs, sp, hist; DevMem<unsigned long long> keys; DevMem<int> counts;
+        int rc;
+        if ((rc = ss.alloc(1)) || (rc = probs.alloc((size_t)kSampThreads * blen)) || (rc = sp.alloc((size_t)kSampThreads * blen)) ||
+            (rc = keys.alloc(2 * n2)) || (rc = hist.alloc(kSampHistBins)) || (rc = counts.alloc(kSampGrid)))
+            return rc;
+        e->d_sampler = std::move(ss); e->d_probs = std::move(probs); e->d_sp = std::move(sp);
+        e->d_keys = std::move(keys); e->d_samp_hist = std::move(hist); e->d_samp_counts = std::move(counts);
         e->keys_n2 = n2;
     }
     SamplerState h{};
@@ -1453,13 +1443,9 @@ int q3_host_generate(q3_engine* e, size_t first_token, size_t first_pos, size_t 
 // operator-level entry points
 // ------------------------------------------------------------------------------------------------
 namespace {
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    int alloc(size_t bytes) {
-        HIP_TRY(hipMalloc(&p, bytes ? bytes : 16));
-        return Q3_OK;
-    }
+// a buffer of an operator entry point, in bytes (a zero-byte request still gets 16)
+struct OpBuf : DevMem<unsigned char> {
+    int alloc(size_t bytes) { return DevMem<unsigned char>::alloc(bytes ? bytes : 16); }
     int upload(const void* src, size_t bytes) {
         int rc = alloc(bytes);
         if (rc) return rc;
@@ -1490,7 +1476,7 @@ int q3_op_quantize(int8_t* q, float* s, const float* x, size_t size, size_t grou
     int rc = op_begin(device);
     if (rc) return rc;
     if (!group_ok(group_size) || size % group_size) return fail(Q3_ERR_UNSUPPORTED, "unsupported size/group_size");
-    DevBuf dx, dq, ds;
+    OpBuf dx, dq, ds;
     if ((rc = dx.upload(x, 4 * size)) || (rc = dq.alloc(size)) || (rc = ds.alloc(4 * (size / group_size)))) return rc;
     hipLaunchKernelGGL(k_op_quantize, dim3(1), dim3(kWG), 0, 0, dq.as<int8_t>(), ds.as<float>(), dx.as<float>(), (int)size, (int)group_size);
     if ((rc = op_end())) return rc;
@@ -1503,7 +1489,7 @@ int q3_op_dequantize(const int8_t* q, const float* s, float* x, size_t size, siz
     int rc = op_begin(device);
     if (rc) return rc;
     if (group_size == 0 || size % group_size) return fail(Q3_ERR_ARG, "size must be a multiple of group_size");
-    DevBuf dx, dq, ds;
+    OpBuf dx, dq, ds;
     if ((rc = dq.upload(q, size)) || (rc = ds.upload(s, 4 * (size / group_size))) || (rc = dx.alloc(4 * size))) return rc;
     hipLaunchKernelGGL(k_op_dequantize, dim3(256), dim3(256), 0, 0, dq.as<int8_t>(), ds.as<float>(), dx.as<float>(), size, (int)group_size);
     if ((rc = op_end())) return rc;
@@ -1519,7 +1505,7 @@ int q3_op_matmul(float* xout, const int8_t* xq, const float* xs, const int8_t* w
         return fail(Q3_ERR_UNSUPPORTED, "unsupported n/group_size");
     hipDeviceProp_t prop;
     HIP_TRY(hipGetDeviceProperties(&prop, device));
-    DevBuf dxq, dxs, dwq, dws, dout;
+    OpBuf dxq, dxs, dwq, dws, dout;
     if ((rc = dxq.upload(xq, n)) || (rc = dxs.upload(xs, 4 * (n / group_size))) || (rc = dwq.upload(wq, n * d)) ||
         (rc = dws.upload(ws, 4 * (n * d / group_size))) || (rc = dout.alloc(4 * d)))
         return rc;
@@ -1577,7 +1563,7 @@ int q3_op_gemv_role(int role, float* out, float* tap_out, int32_t* argmax_index,
     HIP_TRY(hipGetDeviceProperties(&prop, device));
     const size_t wrows = qkv ? rows + 2 * rows_kv : (epi == EPI_SWIGLU ? 2 * rows : rows);   // weight rows
     const size_t orows = qkv ? rows + 2 * rows_kv : rows;                                    // output floats
-    DevBuf din, dnw, dpq, dps, dwq, dws, dout, dtap, dst, dcell, dslots, dtok;
+    OpBuf din, dnw, dpq, dps, dwq, dws, dout, dtap, dst, dcell, dslots, dtok;
     if ((rc = dwq.upload(wq, wrows * n)) || (rc = dws.upload(ws, 4 * (wrows * n / group_size)))) return rc;
     if (pro == PRO_PREQR) {
         if ((rc = dpq.upload(pre_q, n)) || (rc = dps.upload(pre_s, 4 * (n / group_size)))) return rc;
@@ -1654,7 +1640,7 @@ int q3_op_rmsnorm(float* out, const float* in, const float* weight, size_t n, ui
     int rc = op_begin(device);
     if (rc) return rc;
     if (n == 0 || n > 32768) return fail(Q3_ERR_UNSUPPORTED, "unsupported n");
-    DevBuf di, dw, dout;
+    OpBuf di, dw, dout;
     if ((rc = di.upload(in, 4 * n)) || (rc = dw.upload(weight, 4 * n)) || (rc = dout.alloc(4 * n))) return rc;
     const size_t smem = 4 * (size_t)term_floats((int)n) + 512;
     if ((rc = launch_now(0, k_op_rmsnorm, dim3(1), dim3(kWG), smem, dout.as<float>(), di.as<float>(), dw.as<float>(), (int)n,
@@ -1667,7 +1653,7 @@ int q3_op_softmax(float* x, size_t n, uint32_t flags, int device) {
     int rc = op_begin(device);
     if (rc) return rc;
     if (n == 0) return Q3_OK;
-    DevBuf dx;
+    OpBuf dx;
     if ((rc = dx.upload(x, 4 * n))) return rc;
     hipLaunchKernelGGL(k_op_softmax, dim3(1), dim3(kWG), 0, 0, dx.as<float>(), (int)n, (flags & Q3_FLAG_FAST) ? 0 : 1);
     if ((rc = op_end())) return rc;
@@ -1678,7 +1664,7 @@ int q3_op_softmax(float* x, size_t n, uint32_t flags, int device) {
 int q3_op_swiglu(float* hb, const float* hb2, size_t n, int device) {
     int rc = op_begin(device);
     if (rc) return rc;
-    DevBuf a, b;
+    OpBuf a, b;
     if ((rc = a.upload(hb, 4 * n)) || (rc = b.upload(hb2, 4 * n))) return rc;
     hipLaunchKernelGGL(k_op_swiglu, dim3(256), dim3(256), 0, 0, a.as<float>(), b.as<float>(), n);
     if ((rc = op_end())) return rc;
@@ -1689,7 +1675,7 @@ int q3_op_swiglu(float* hb, const float* hb2, size_t n, int device) {
 int q3_op_expf(float* x, size_t n, int device) {
     int rc = op_begin(device);
     if (rc) return rc;
-    DevBuf a;
+    OpBuf a;
     if ((rc = a.upload(x, 4 * n))) return rc;
     hipLaunchKernelGGL(k_op_expf, dim3(512), dim3(256), 0, 0, a.as<float>(), n);
     if ((rc = op_end())) return rc;
@@ -1706,7 +1692,7 @@ int q3_op_attention(float* xb, float* q, float* key_cache_layer, const float* va
         (head_dim & (head_dim - 1)))
         return fail(Q3_ERR_UNSUPPORTED, "unsupported attention shape");
     const size_t ahd = n_heads * head_dim, kvd = n_kv_heads * head_dim;
-    DevBuf dq, dk, dv, dqw, dkw, dxb, drope, dkraw, datt;
+    OpBuf dq, dk, dv, dqw, dkw, dxb, drope, dkraw, datt;
     if ((rc = dq.upload(q, 4 * ahd)) || (rc = dk.upload(key_cache_layer, 4 * seq_len * kvd)) ||
         (rc = dv.upload(value_cache_layer, 4 * seq_len * kvd)) || (rc = dqw.upload(q_norm_w, 4 * head_dim)) ||
         (rc = dkw.upload(k_norm_w, 4 * head_dim)) || (rc = dxb.alloc(4 * ahd)) ||
@@ -1726,7 +1712,7 @@ int q3_op_attention(float* xb, float* q, float* key_cache_layer, const float* va
     const bool att_global = split || seq_len > 4096;
     const int att_stride = att_stride_for(seq_len);
     const int nsl = (int)head_dim / attn_slice_w((int)head_dim, (int)n_heads, 256);
-    DevBuf dpriv, dqout, dcmax, dvt;
+    OpBuf dpriv, dqout, dcmax, dvt;
     if (att_global && (rc = datt.alloc(4 * n_heads * (size_t)att_stride))) return rc;
     if (split && ((rc = dpriv.alloc(4 * n_heads * nsl * (size_t)att_stride)) || (rc = dqout.alloc(4 * ahd)) ||
                   (rc = dcmax.alloc(4 * n_heads * (size_t)cmax_stride_for(seq_len)))))
@@ -1791,7 +1777,7 @@ int q3_dev_bench_gemv(size_t n, size_t d, size_t group_size, int wg_per_cu, int 
     size_t copies = (512ull << 20) / (wbytes + sbytes) + 1;
     if (copies > 16) copies = 16;
     if (copies < 2) copies = 2;
-    DevBuf dw, ds, dxq, dxs, dout;
+    OpBuf dw, ds, dxq, dxs, dout;
     if ((rc = dw.alloc(wbytes * copies)) || (rc = ds.alloc(sbytes * copies)) || (rc = dxq.alloc(n)) ||
         (rc = dxs.alloc(4 * (n / group_size))) || (rc = dout.alloc(4 * d)))
         return rc;
@@ -1853,7 +1839,7 @@ int q3_op_sample(const float* logits, size_t n, float temperature, float topp, u
     const int blen = 4 * (((int)n + 4095) / 4096);
     size_t n2 = 1;
     while (n2 < n) n2 <<= 1;
-    DevBuf dl, dp, ds, dk, dss, dst, dout;
+    OpBuf dl, dp, ds, dk, dss, dst, dout;
     SamplerState h{*rng_state, temperature, topp, {0, 0, 0, 0}};
     State st{};
     st.step = 1;                                            // "one forward done": the draw is stored in out_tokens[0]
@@ -1885,7 +1871,7 @@ int q3_op_argmax(const float* logits, size_t n, int32_t* index, int device) {
     if (rc) return rc;
     if (!index) return fail(Q3_ERR_ARG, "null argument");
     if (n == 0) { *index = 0; return Q3_OK; }   // unwrap_or_default
-    DevBuf dl, dc;
+    OpBuf dl, dc;
     unsigned long long zero = 0;
     if ((rc = dl.upload(logits, 4 * n)) || (rc = dc.upload(&zero, 8))) return rc;
     hipLaunchKernelGGL(k_op_argmax, dim3(256), dim3(kWG), 0, 0, dl.as<float>(), n, dc.as<unsigned long long>());

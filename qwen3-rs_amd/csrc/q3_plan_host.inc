@@ -85,6 +85,11 @@ AttnFn attn_pf2_fn(int kvm, int np) {
 // ---- the builder: the launches of key.n streams (Decode), block positions (Prefill, Verify; draw: Verify under the sampler),
 // columns (Cols; draw: the sampled column plan) or columns of a dense block over the slots (SlotPrefill), appended to `out`.
 // It reads the engine and the context and writes neither.
+struct BlockView {              // the per-column buffers the layers of a plan work on
+    float *x, *q, *qn, *kraw, *xb, *hb;
+    int8_t* xq_p; float* xs_p; State* st; int* col_slot;
+    float* att_pf; int att_pf_stride;
+};
 struct PlanBuilder {
     const q3_engine* const e;
     const PlanKey key;
@@ -104,7 +109,7 @@ struct PlanBuilder {
     float* const value_base = own_cache ? e->d_value : b->value;
     const int S = own_cache ? c.seq_len : b->ctx;
     const long long kv_stride = own_cache ? 0 : (long long)b->kv_stream;
-    const BlockScratch sc = scratch();
+    const BlockView sc = scratch();
 
     const int dim = c.dim, L = c.n_layers, hd = c.head_dim, V = c.vocab_size, H = c.hidden_dim, G = c.group_size;
     const int ahd = c.n_heads * hd, kvd = c.n_kv_heads * hd;
@@ -124,14 +129,17 @@ struct PlanBuilder {
     int nslots_used = 0;         // argmax slots the classifier launch fills: what the tail launches read
 
     // the per-column buffers the layers work on: the context's own, or the dense block scratch of SlotPrefill
-    BlockScratch scratch() const {
-        BlockScratch s = b->dense;
-        if (!slotpf) {
-            s.x = b->x; s.q = b->q; s.qn = b->qn; s.kraw = b->kraw; s.xb = b->xb; s.hb = b->hb;
-            s.xq_p = b->xq_p; s.xs_p = b->xs_p; s.st = b->st;
-            s.col_slot = cols ? b->col_slot : nullptr;
-            s.att_pf = b->att_pf; s.att_pf_stride = b->att_pf_stride;
-        }
+    BlockView scratch() const {
+        // one list of names for both sources: BatchCtx and BlockScratch call their buffers alike
+        const auto view = [](const auto& m) {
+            BlockView s{};
+            s.x = m.x; s.q = m.q; s.qn = m.qn; s.kraw = m.kraw; s.xb = m.xb; s.hb = m.hb;
+            s.xq_p = m.xq_p; s.xs_p = m.xs_p; s.st = m.st; s.col_slot = m.col_slot;
+            s.att_pf = m.att_pf; s.att_pf_stride = m.att_pf_stride;
+            return s;
+        };
+        BlockView s = slotpf ? view(b->dense) : view(*b);
+        if (!slotpf && !cols) s.col_slot = nullptr;
         return s;
     }
 

@@ -47,8 +47,7 @@ int prefix_bcast_slots(q3_engine* e, int n_slots) {
 
 void prefix_release(q3_engine* e) {
     BatchCtx* b = e->batch;
-    if (b->prefix_store) (void)hipFree(b->prefix_store);
-    b->prefix_store = nullptr;
+    b->prefix_store.reset();
     b->prefix_n = 0;
     b->prefix_tokens.clear();
 }
@@ -129,12 +128,11 @@ int q3_batch_prefix_set(q3_engine* e, const int32_t* tokens, size_t n) {
     // slot 0 -> the store: the same kernel, one destination whose layers are n rows apart
     const q3_config& c = e->cfg;
     const size_t kvd = (size_t)c.n_kv_heads * c.head_dim, half = (size_t)c.n_layers * n * kvd;
-    float* store = nullptr;
-    if (hipMalloc((void**)&store, 4 * 2 * half) != hipSuccess) {
+    DevMem<float> store;                                     // moved in once its rows have arrived
+    if (store.alloc(2 * half)) {
         (void)hipGetLastError();
         return fail(Q3_ERR_HIP, "the prefix store of %zu MiB for %zu tokens does not fit", (4 * 2 * half) >> 20, n);
     }
-    b->prefix_store = store;
     KvBcastDst d{};
     d.key[0] = store;
     d.value[0] = store + half;
@@ -142,10 +140,8 @@ int q3_batch_prefix_set(q3_engine* e, const int32_t* tokens, size_t n) {
         const hipError_t err = hipStreamSynchronize(e->stream);
         if (err != hipSuccess) rc = fail(Q3_ERR_HIP, "%s", hipGetErrorString(err));
     }
-    if (rc) {
-        prefix_release(e);
-        return rc;
-    }
+    if (rc) return rc;
+    b->prefix_store = std::move(store);
     b->prefix_n = n;
     b->prefix_tokens.assign(tokens, tokens + n);
     return Q3_OK;

@@ -155,8 +155,6 @@ int score_run(q3_engine* e, const char* who, const int32_t* prompts, const size_
     tm.on = getenv("Q3_DEBUG_TIMING") != nullptr;
     tm.top = k > 0;
     rc = embed_walk(e, prompts, prompt_len, n_requests, (flags & Q3_SCORE_PREFIX) != 0,
-                    n_rec > b->score_rows_cap || n_rec > b->score_out_cap || n_probs > b->score_probs_cap || n_top > b->score_top_cap ||
-                        n_rank > b->score_rank_cap || n_keys > b->score_top_keys_cap || n_above > b->score_top_above_cap,
                     [&](const std::vector<DenseRun>& runs, const std::vector<EmbedStep>& steps) {
                         // the record of every token of the call (-1: not scored); the walk has checked the lengths and the tokens
                         std::vector<int32_t> rec_of;
@@ -196,13 +194,13 @@ int score_run(q3_engine* e, const char* who, const int32_t* prompts, const size_
                             if ((rc2 = plan_get(e, cols_key(kColsWidths[w], false), &plans[w]))) return rc2;
                             if (plans[w]->launches.size() < plans[w]->head + 2) return fail(Q3_ERR_INTERNAL, "%s: a column plan without a classifier", who);
                         }
-                        if ((rc2 = cols_grow(b->score_rows, b->score_rows_cap, n_rec))) return rc2;
-                        if ((rc2 = cols_grow(b->score_out, b->score_out_cap, n_rec))) return rc2;
-                        if ((rc2 = cols_grow(b->score_probs, b->score_probs_cap, n_probs))) return rc2;
-                        if ((rc2 = cols_grow(b->score_top, b->score_top_cap, n_top))) return rc2;
-                        if ((rc2 = cols_grow(b->score_rank, b->score_rank_cap, n_rank))) return rc2;
-                        if ((rc2 = cols_grow(b->score_top_keys, b->score_top_keys_cap, n_keys))) return rc2;
-                        if ((rc2 = cols_grow(b->score_top_above, b->score_top_above_cap, n_above))) return rc2;
+                        if ((rc2 = b->score_rows.grow(n_rec, e->stream))) return rc2;
+                        if ((rc2 = b->score_out.grow(n_rec, e->stream))) return rc2;
+                        if ((rc2 = b->score_probs.grow(n_probs, e->stream))) return rc2;
+                        if ((rc2 = b->score_top.grow(n_top, e->stream))) return rc2;
+                        if ((rc2 = b->score_rank.grow(n_rank, e->stream))) return rc2;
+                        if ((rc2 = b->score_top_keys.grow(n_keys, e->stream))) return rc2;
+                        if ((rc2 = b->score_top_above.grow(n_above, e->stream))) return rc2;
                         if (n_rec) HIP_TRY(hipMemcpyAsync(b->score_rows, rows.data(), sizeof(ScoreRow) * n_rec, hipMemcpyHostToDevice, e->stream));
                         return (int)Q3_OK;
                     },

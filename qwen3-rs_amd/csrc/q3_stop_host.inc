@@ -30,11 +30,11 @@ int cols_generate_stop(q3_engine* e, const ColsRequests& rq, const int32_t* stop
     if (draw && (rc = cols_draw_alloc(e))) return rc;
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(hipStreamSynchronize(e->stream));              // nothing in flight reads the buffers that may be re-allocated
-    if (!b->cols_stop) HIP_TRY(hipMalloc((void**)&b->cols_stop, sizeof(ColsStopDev)));
-    if (!b->h_cols_stop) HIP_TRY(hipHostMalloc((void**)&b->h_cols_stop, sizeof(SchedStatus), hipHostMallocDefault));
-    if ((rc = cols_grow(b->cols_req, b->cols_req_cap, 5 * n_requests))) return rc;
-    if ((rc = cols_grow(b->cols_prompts, b->cols_prompts_cap, rq.n_prompt))) return rc;
-    if ((rc = cols_grow(b->cols_out, b->cols_out_cap, rq.n_out))) return rc;
+    if (!b->cols_stop && (rc = b->cols_stop.alloc(1))) return rc;
+    if (!b->h_cols_stop && (rc = b->h_cols_stop.alloc(1))) return rc;
+    if ((rc = b->cols_req.grow(5 * n_requests, e->stream))) return rc;
+    if ((rc = b->cols_prompts.grow(rq.n_prompt, e->stream))) return rc;
+    if ((rc = b->cols_out.grow(rq.n_out, e->stream))) return rc;
 
     // uploaded once: the prompts, the per-request records, the sampler parameters, the scheduler state with the stop list
     int* dreq = b->cols_req;

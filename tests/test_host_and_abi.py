@@ -75,6 +75,40 @@ def test_product_library_reads_only_the_documented_environment_variables(q3):
     assert found == documented, (sorted(found), sorted(documented))
 
 
+CSRC = os.path.join(ROOT, "qwen3-rs_amd", "csrc")
+
+
+def test_device_memory_is_owned_in_one_place():
+    """csrc/q3_mem.h is the only file that allocates or frees device or pinned memory: every buffer is a DevMem / PinMem value.
+    No hand-kept free list, no (pointer, capacity) pair and no restated re-allocation guard is left to forget an entry of."""
+    src = {f: open(os.path.join(CSRC, f)).read() for f in sorted(os.listdir(CSRC)) if f.endswith((".hip", ".h", ".inc"))}
+    assert "q3_mem.h" in src and len(src) > 10
+    users = sorted(f for f, text in src.items() if re.search(r"\bhip(Malloc|Free|HostMalloc|HostFree)", text))
+    assert users == ["q3_mem.h"], users
+    batch = src["q3_batch_host.inc"]
+    ctx = batch[batch.index("struct BatchCtx {"):]
+    ctx = ctx[:ctx.index("\n};")]
+    assert "DevMem<" in ctx and "PinMem<" in ctx
+    assert not re.search(r"\bsize_t\b[^;]*\b\w+_cap\b", ctx), "BatchCtx keeps a capacity beside a buffer"
+    walk = re.search(r"int embed_walk\(([^)]*)\)", src["q3_embed_host.inc"], re.S)
+    assert walk and "regrow" not in walk.group(1)
+    everything = "\n".join(src.values())
+    for gone in ("regrow", "dense_scratch_free", "cols_grow", "dptrs[]", "struct DevBuf"):
+        assert gone not in everything, gone
+    assert not re.search(r"void\s*\*\s*\w+\[\]\s*=\s*\{", everything), "a hand-kept list of pointers"
+
+
+def test_owned_memory_types_on_the_host(tmp_path):
+    """tests/mem_host.cpp: DevMem / PinMem over a counting allocator that can fail the k-th request, under ASan + UBSan.  A
+    stand-alone program of its own: q3_mem.h compiles without the HIP runtime when the default policies are not instantiated."""
+    exe = str(tmp_path / "mem_host")
+    subprocess.check_call([os.environ.get("CXX", "g++"), "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
+                           "-fno-sanitize-recover=all", "-I", CSRC, "-o", exe, os.path.join(ROOT, "tests", "mem_host.cpp")])
+    out = subprocess.run([exe], capture_output=True, text=True)
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert "mem_host ok" in out.stdout
+
+
 class _Recorder:
     """A fake Transformer recording the (token,pos) calls it receives."""
 
