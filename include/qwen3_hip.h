@@ -834,6 +834,47 @@ int q3_score_top_many(q3_engine* e, const int32_t* prompts /* concatenated */, c
                       q3_score_rec* out /* host, concatenated */, q3_score_top* top /* host, [records][k] */,
                       int32_t* rank /* host, [records], or NULL */, q3_score_stats* stats);
 
+/* ------------------------------------------------------------------------------------------------
+ * 2n. (behind 2m so that the earlier sections stay as they were.)  Top-k sampling: every draw the engine makes at temperature > 0 is
+ * taken among the k most likely tokens (the model cards' third sampling setting, beside temperature and top-p).
+ * THE RULE.  A draw with top_k = k, 1 <= k <= Q3_TOP_K_MAX, is Sampler::sample (sampler.rs:118-139) applied to the logits with
+ * every entry outside the SURVIVOR SET replaced by -inf.  The survivors are the entries of the k largest keys of section 2m,
+ *     key(i) = ((uint64)total_order_key(l[i]) << 32) | i,
+ * so equal logits go to the HIGHER index, as for the argmax, and k = 1 leaves the argmax.  The rest follows from the masking, bit
+ * for bit: the softmax maximum is the scaled top survivor; e = expf(l / T - max) per survivor; the denominator is the sequential
+ * f32 sum from -0.0 over the survivors in ascending token index (a masked entry adds an exact zero); p = e * (1 / sum); ONE
+ * xorshift64* coin per draw, so the rng advances exactly as without top-k.  0 < topp < 1: the cutoff is (1 - topp) / (V - 1) with
+ * the FULL vocabulary size V, the survivors with p >= cutoff are sorted by (probability descending, index ascending), and the
+ * cumulative sum and the cdf walk are sequential.  Otherwise: a sequential cdf over the survivors in ascending index.
+ * One deviation: a multinomial walk whose f32 cdf ends below the coin (37 equal survivors end at 0.9999998) returns the
+ * highest-index SURVIVOR; the masked reference returns index V - 1, which is masked.
+ * At temperature 0 top_k is ignored: argmax, no coin.  A discarded prompt-position draw consumes its coin and selects nothing; a
+ * temperature-0 slot inside a sampled column pass takes the argmax: both as without top-k.  A NaN logit is outside the standard
+ * and harmless: no value read back from memory becomes an address, and the drawn index is clamped to the vocabulary.
+ * What runs (csrc/q3_topk.h).  k_sample_exp, k_sample and the chip-wide passes of a draw are replaced by two launches: k_topk_part
+ * -- grid (64 slices, columns), the k largest keys of every slice, section 2m's selection -- and k_topk_draw -- one wave per
+ * column merges the lists and draws.  On / off is a property of the plan (a second form of every sampled plan, built on first
+ * use); the value of k stands in device memory and is read when a pass runs.  top_k = 0: every entry point launches exactly what
+ * it launched before this section existed.
+ * ------------------------------------------------------------------------------------------------ */
+#define Q3_TOP_K_MAX 64   /* = Q3_SCORE_TOP_MAX */
+
+/* The engine-wide top_k, default 0 = off.  It holds for every draw at temperature > 0 of every entry point: q3_forward_sample,
+ * q3_generate_sampled, the last position of q3_prefill / q3_prefill_batched; q3_forward_batch / q3_generate_greedy_batch under
+ * q3_batch_sampler_set; q3_verify_draw, q3_generate_lookup_draw, q3_batch_step_cols_draw, q3_generate_many_sampled and the
+ * sampled forms of q3_generate_many_dense / _stop / _prefix.  It is independent of q3_sampler_set, q3_batch_sampler_set and
+ * q3_batch_init and survives all of them and every q3_generate_many_* call.
+ * Execution: waits for the stream; the first k > 0 allocates the k word and the slices' lists (32 columns x 64 x 64 keys, 1 MiB).
+ * Changing k between two non-zero values rebuilds and recaptures nothing; switching between 0 and k > 0 selects the other form
+ * of the plans (the one step plan of section 2b is rebuilt on its next use, the kept column plans of both forms stay).
+ * Q3_ERR_ARG: null engine; top_k < 0, > Q3_TOP_K_MAX or > vocab_size. */
+int q3_sampler_top_k(q3_engine* e, int top_k);
+int q3_sampler_get_top_k(const q3_engine* e, int* top_k);
+
+/* q3_op_sample among the top_k largest logits: one draw by the rule above on a host vector.  Arguments and refusals of
+ * q3_op_sample, and Q3_ERR_ARG for top_k outside 1 .. Q3_TOP_K_MAX or > n (0 is an error here: that draw is q3_op_sample). */
+int q3_op_sample_top_k(const float* logits, size_t n, float temperature, float topp, int top_k, uint64_t* rng_state, int32_t* index, int device);
+
 #ifdef __cplusplus
 }
 #endif

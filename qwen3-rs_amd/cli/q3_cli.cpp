@@ -359,7 +359,9 @@ void usage() {
             "Qwen3 inference on the MI355X engine\n\n"
             "Usage: q3_cli inference <checkpoint> [-t TEMPERATURE] [-p TOPP] [-s SEED] [-c CONTEXT] [-m generate|chat]\n"
             "                                     [-i INPUT] [-y SYSTEM] [-r 0|1] [--lookup DRAFT_LEN] [--speculate DRAFT_LEN]\n"
+            "                                     [-k TOP_K]\n"
             "  -t, --temperature  [0, inf)   default 1.0\n  -p, --topp         [0, 1]     default 0.9\n"
+            "  -k, --top-k        draw among the TOP_K most likely tokens only (1..64; 0 = off, the default)\n"
             "  -s, --seed         random seed (default: time)\n  -c, --context      context window size (default: the checkpoint's)\n"
             "  -m, --mode         generate | chat (default chat)\n  -i, --input        input prompt\n"
             "  -y, --system       system prompt (chat mode)\n  -r, --reasoning    0 = no thinking, 1 = thinking (default 0)\n"
@@ -396,7 +398,7 @@ int main(int argc, char** argv) {
     double temperature = 1.0, topp = 0.9;
     bool have_seed = false, have_input = false, have_system = false;
     unsigned long long seed = 0;
-    long context = 0, reasoning = 0, lookup = 0, speculate = 0;
+    long context = 0, reasoning = 0, lookup = 0, speculate = 0, top_k = 0;
     std::string mode = "chat", input, system_prompt;
     for (int i = 3; i < argc; ++i) {
         const std::string a = argv[i];
@@ -417,6 +419,7 @@ int main(int argc, char** argv) {
         else if (a == "-r" || a == "--reasoning") reasoning = atol(val());
         else if (a == "--lookup") lookup = atol(val());
         else if (a == "--speculate") speculate = atol(val());
+        else if (a == "-k" || a == "--top-k") top_k = atol(val());
         else {
             fprintf(stderr, "Error: unknown argument %s\n", a.c_str());
             usage();
@@ -436,6 +439,11 @@ int main(int argc, char** argv) {
         fprintf(stderr, "Error: --speculate takes a draft length of 1..31 and cannot be combined with --lookup\n");
         return 1;
     }
+    const char* top_k_refusal = "Error: --top-k takes 0 (off) or a count of 1..64, at most the vocabulary size\n";
+    if (top_k < 0 || top_k > Q3_TOP_K_MAX) {
+        fputs(top_k_refusal, stderr);
+        return 1;
+    }
     q3_engine* e = nullptr;
     if (q3_create(ckpt.c_str(), context > 0 ? (uint32_t)context : 0u, 0, 0u, &e) != Q3_OK) return fail_engine("cannot load the checkpoint");
     q3_config cfg;
@@ -448,6 +456,12 @@ int main(int argc, char** argv) {
     if (!have_seed) seed = (unsigned long long)time(nullptr);      // lib.rs: SystemTime seconds when no seed is given
     const float t = (float)(temperature < 0.0 ? 0.0 : temperature), p = (float)(topp < 0.0 ? 0.0 : (topp > 1.0 ? 1.0 : topp));
     if (q3_sampler_set(e, t, p, (uint64_t)seed) != Q3_OK) return fail_engine("sampler");
+    if (top_k > cfg.vocab_size) {
+        fputs(top_k_refusal, stderr);
+        q3_destroy(e);
+        return 1;
+    }
+    if (q3_sampler_top_k(e, (int)top_k) != Q3_OK) return fail_engine("top-k");      // the engine's: --speculate's rounds draw under it too
     Lookup lk;
     lk.draft_len = (int)(speculate ? speculate : lookup);
     lk.draw = speculate != 0;

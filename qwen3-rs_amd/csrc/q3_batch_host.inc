@@ -15,12 +15,14 @@
 // BatchCtx::dense_plans.
 enum class PlanKind { Decode, Prefill, Verify, Cols, SlotPrefill };
 // n: streams, block positions or columns; grids and the stream-tile count are baked in.  draw: Verify and Cols under the sampler
-// (the plan samples every column); the sampler of a Decode plan is not part of its key: q3_batch_sampler_set drops the plan
+// (the plan samples every column); the sampler of a Decode plan is not part of its key: q3_batch_sampler_set drops the plan.
+// topk: the draws of the plan are the top-k form (q3_topk.h); plan_get sets it from the engine's top_k wherever the plan draws
 struct PlanKey {
     PlanKind kind = PlanKind::Decode;
     int n = 0;
     bool draw = false;
-    bool operator==(const PlanKey& o) const { return kind == o.kind && n == o.n && draw == o.draw; }
+    bool topk = false;
+    bool operator==(const PlanKey& o) const { return kind == o.kind && n == o.n && draw == o.draw && topk == o.topk; }
 };
 // The launches of one key, built by batch_build_plan (q3_plan_host.inc): a value, moved to where its kind is kept.
 struct Plan {
@@ -105,8 +107,9 @@ struct BatchCtx {
     DevMem<int> col_slot;        // device [kColsMax]: KV slot of every column of the pass in flight
     DevMem<ColsCtl> cols_ctl;    // device
     PinMem<ColsHost> h_cols;
-    Plan cols_plans[2][kColsNW];                        // [sampled][width], built on first use (q3_batch_init starts over); the sampled
-                                                        // ones: the same layers and classifier, then the draws and k_cols_turn_draw
+    Plan cols_plans[3][kColsNW];                        // [greedy | sampled | sampled with top-k][width], built on first use (q3_batch_init
+                                                        // starts over); the sampled ones: the same layers and classifier, then the draws
+                                                        // and k_cols_turn_draw
     DevMem<ColEnt> cols_table;                          // the loop's pass table, prompts and output: grow-only device buffers
     DevMem<int> cols_ncols;
     DevMem<int32_t> cols_prompts, cols_out;

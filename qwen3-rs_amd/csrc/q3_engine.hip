@@ -42,6 +42,7 @@
 #include "q3_choice.h"
 #include "q3_score.h"
 #include "q3_score_top.h"
+#include "q3_topk.h"
 #include "q3_lookup.h"
 
 namespace {
@@ -284,6 +285,14 @@ int env_int(const char* name, int dflt) {
 #define dev_knob(name, dflt) (dflt)
 #endif
 
+// slices per column of the top-k selection (k_topk_part's gridDim.x): one list per lane of the draw's merge.  A slice of the
+// 151,936-entry vocabulary is then 2,374 entries, one tile of the part kernel (Q3_TOPK_PARTS, developer build: another split, the same draws)
+int topk_parts(int n) {
+    (void)n;
+    const int p = dev_knob("Q3_TOPK_PARTS", kScoreTopParts);
+    return p < 1 ? 1 : (p > kScoreTopParts ? kScoreTopParts : p);
+}
+
 
 }  // namespace
 
@@ -353,6 +362,14 @@ struct q3_engine {
     DevMem<unsigned long long> d_keys;
     size_t keys_n2 = 0;
     std::vector<Launch> sample_plan;     // the draw behind a forward (q3_sampler_set)
+    // top-k sampling (q3_sampler_top_k, section 2n): engine-wide, 0 = off.  The value also stands in device memory, where every
+    // top-k pass reads it; the slices' lists hold the columns of the widest pass (kSpecMax).  Allocated by the first k > 0.
+    int top_k = 0;
+    DevMem<int> d_top_k;
+    DevMem<unsigned long long> d_topk_keys;
+    std::vector<Launch> sample_plan_topk;    // the second form of sample_plan: k_topk_part, k_topk_draw
+    TopkArgs topk_args(const SampleArgs& s) const;
+    int build_sample_plan_topk();
     int enqueue_sample();
 
     int load(const char* path, uint32_t ctx_len);
@@ -932,8 +949,45 @@ int q3_engine::enqueue_forward(size_t pos, bool draw) {
 // Sampler::sample on the logits of the forward just enqueued (after the classifier launch has advanced the state)
 int q3_engine::enqueue_sample() {
     if (!sampling) return Q3_OK;
-    for (const Launch& L : sample_plan) launch(L, stream);
+    for (const Launch& L : (top_k > 0 ? sample_plan_topk : sample_plan)) launch(L, stream);
     HIP_TRY(hipGetLastError());
+    return Q3_OK;
+}
+
+// the top-k launches' view of a draw site: its logits, states and outputs are the site's SampleArgs', the lists are the engine's
+TopkArgs q3_engine::topk_args(const SampleArgs& s) const {
+    TopkArgs t{};
+    t.logits = s.logits;
+    t.sb_logits = s.sb_logits;
+    t.n = s.n;
+    t.parts = topk_parts(s.n);
+    t.k = d_top_k;
+    t.part_keys = d_topk_keys;
+    t.ss = s.ss;
+    t.st = s.st;
+    t.out_tokens = s.out_tokens;
+    t.out_cap = s.out_cap;
+    return t;
+}
+
+// sample_plan's second form, once the sampler state and the top-k buffers both exist (q3_sampler_set / q3_sampler_top_k, in either order)
+int q3_engine::build_sample_plan_topk() {
+    sample_plan_topk.clear();
+    if (!d_sampler || !d_top_k) return Q3_OK;
+    SampleArgs s{};
+    s.logits = d_logits;
+    s.n = cfg.vocab_size;
+    s.ss = d_sampler;
+    s.st = d_state;
+    s.out_tokens = d_out_tokens;
+    s.out_cap = out_cap;
+    const TopkArgs t = topk_args(s);
+    Launch part, draw;
+    int rc;
+    if ((rc = make_launch(part, F_NEXT, k_topk_part, dim3((unsigned)t.parts, 1), dim3(256), 0, t)) ||
+        (rc = make_launch(draw, F_NEXT, k_topk_draw, dim3(1), dim3(64), 0, t)))
+        return rc;
+    sample_plan_topk = {part, draw};
     return Q3_OK;
 }
 
@@ -1230,7 +1284,36 @@ int q3_sampler_set(q3_engine* e, float temperature, float topp, uint64_t rng_see
         add(k_sample, dim3(1), dim3(kSampThreads), 4 * kSegFloats, tail);
     }
     if (rc) return rc;
+    if ((rc = e->build_sample_plan_topk())) return rc;
     e->sampling = temperature != 0.0f;                       // sampler.rs:119-120: temperature 0 is the argmax path
+    return Q3_OK;
+}
+
+int q3_sampler_top_k(q3_engine* e, int top_k) {
+    g_err[0] = 0;
+    if (!e) return fail(Q3_ERR_ARG, "null engine");
+    if (top_k < 0 || top_k > kTopkMax || top_k > e->cfg.vocab_size)
+        return fail(Q3_ERR_ARG, "top_k %d out of range (0..%d, at most vocab_size %d)", top_k, kTopkMax, e->cfg.vocab_size);
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    if (top_k > 0 && !e->d_top_k) {
+        // one group, committed whole (q3_sampler_set)
+        DevMem<int> k; DevMem<unsigned long long> keys;
+        int rc;
+        if ((rc = k.alloc(1)) || (rc = keys.alloc((size_t)kSpecMax * kTopkColKeys))) return rc;
+        e->d_top_k = std::move(k); e->d_topk_keys = std::move(keys);
+        if ((rc = e->build_sample_plan_topk())) return rc;
+    }
+    // 0 is never read: the plans without top-k run.  Two non-zero values share every plan and graph
+    if (top_k > 0) HIP_TRY(hipMemcpy(e->d_top_k, &top_k, sizeof(int), hipMemcpyHostToDevice));
+    e->top_k = top_k;
+    return Q3_OK;
+}
+
+int q3_sampler_get_top_k(const q3_engine* e, int* top_k) {
+    g_err[0] = 0;
+    if (!e || !top_k) return fail(Q3_ERR_ARG, "null argument");
+    *top_k = e->top_k;
     return Q3_OK;
 }
 
@@ -1860,6 +1943,41 @@ int q3_op_sample(const float* logits, size_t n, float temperature, float topp, u
     a.out_tokens = dout.as<int32_t>();
     a.out_cap = 4;
     if ((rc = launch_now(0, k_sample, dim3(1), dim3(kSampThreads), 4 * kSegFloats, a)) || (rc = op_end())) return rc;
+    HIP_TRY(hipMemcpy(&h, dss.p, sizeof(h), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(index, dout.p, 4, hipMemcpyDeviceToHost));
+    *rng_state = h.rng;
+    return Q3_OK;
+}
+
+int q3_op_sample_top_k(const float* logits, size_t n, float temperature, float topp, int top_k, uint64_t* rng_state, int32_t* index, int device) {
+    int rc = op_begin(device);
+    if (rc) return rc;
+    if (!logits || !rng_state || !index || n == 0) return fail(Q3_ERR_ARG, "null argument");
+    if (!(temperature > 0.0f)) return fail(Q3_ERR_ARG, "temperature must be positive (0 is q3_op_argmax)");
+    if ((rc = sampler_check(temperature, topp))) return rc;
+    if (n > (size_t)INT32_MAX) return fail(Q3_ERR_ARG, "more than 2^31 logits");
+    if (top_k < 1 || top_k > kTopkMax || (size_t)top_k > n)
+        return fail(Q3_ERR_ARG, "top_k %d out of range (1..%d, at most n %zu)", top_k, kTopkMax, n);
+    OpBuf dl, dk, dkeys, dss, dst, dout;
+    SamplerState h{*rng_state, temperature, topp, {0, 0, 0, 0}};
+    State st{};
+    st.step = 1;                                            // "one forward done": the draw is stored in out_tokens[0]
+    if ((rc = dl.upload(logits, 4 * n)) || (rc = dk.upload(&top_k, sizeof(int))) || (rc = dkeys.alloc(8 * (size_t)kTopkColKeys)) ||
+        (rc = dss.upload(&h, sizeof(h))) || (rc = dst.upload(&st, sizeof(st))) || (rc = dout.alloc(16)))
+        return rc;
+    TopkArgs a{};
+    a.logits = dl.as<float>();
+    a.n = (int)n;
+    a.parts = topk_parts((int)n);
+    a.k = dk.as<int>();
+    a.part_keys = dkeys.as<unsigned long long>();
+    a.ss = dss.as<SamplerState>();
+    a.st = dst.as<State>();
+    a.out_tokens = dout.as<int32_t>();
+    a.out_cap = 4;
+    if ((rc = launch_now(0, k_topk_part, dim3((unsigned)a.parts, 1), dim3(256), 0, a)) ||
+        (rc = launch_now(0, k_topk_draw, dim3(1), dim3(64), 0, a)) || (rc = op_end()))
+        return rc;
     HIP_TRY(hipMemcpy(&h, dss.p, sizeof(h), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(index, dout.p, 4, hipMemcpyDeviceToHost));
     *rng_state = h.rng;

@@ -388,8 +388,15 @@ struct PlanBuilder {
     int draw_columns() {
         int rc;
         if ((rc = add(F_NEXT, k_spec_colmax, dim3(1), dim3(kWG), 0, b->st, b->slots, b->nslots, nslots_used, n))) return rc;
+        if (key.topk) return draw_topk(b->spec_sargs);
         if ((rc = add(F_NEXT, k_sample_exp, dim3(64, (unsigned)n), dim3(256), 0, b->spec_sargs))) return rc;
         return add(F_NEXT, k_sample, dim3((unsigned)n), dim3(kSampThreads), 4 * kSegFloats, b->spec_sargs);
+    }
+    // the top-k form of a site's draws (q3_topk.h): the selection over the slices of every column, then one wave per column
+    int draw_topk(const SampleArgs& s) {
+        const TopkArgs t = e->topk_args(s);
+        if (int rc = add(F_NEXT, k_topk_part, dim3((unsigned)t.parts, (unsigned)n), dim3(256), 0, t)) return rc;
+        return add(F_NEXT, k_topk_draw, dim3((unsigned)n), dim3(64), 0, t);
     }
 
     // what follows the classifier
@@ -417,6 +424,7 @@ struct PlanBuilder {
         if (!b->sampling) return Q3_OK;
         // Sampler::sample per stream on the logits of this step (one workgroup per stream), behind its element-wise passes spread
         // over the chip
+        if (key.topk) return draw_topk(b->sargs);
         if (b->sargs.pre_exp && (rc = add(F_NEXT, k_sample_exp, dim3(64, (unsigned)n), dim3(256), 0, b->sargs))) return rc;
         return add(F_NEXT, k_sample, dim3((unsigned)n), dim3(kSampThreads), 4 * kSegFloats, b->sargs);
     }
@@ -464,8 +472,10 @@ int plan_get(q3_engine* e, PlanKey key, Plan** out) {
     BatchCtx* b = e->batch;
     Plan* home = &b->step;
     bool hit;
+    // the engine's top_k holds wherever the plan draws: the sampled Verify and Cols plans, and the Decode plan under the batch sampler
+    key.topk = e->top_k > 0 && (key.draw || (key.kind == PlanKind::Decode && b->sampling));
     if (key.kind == PlanKind::Cols) {
-        home = &b->cols_plans[key.draw][cols_width_index(key.n)];
+        home = &b->cols_plans[key.draw ? (key.topk ? 2 : 1) : 0][cols_width_index(key.n)];
         hit = !home->launches.empty();
     } else if (key.kind == PlanKind::SlotPrefill) {
         if (key.n <= kColsMax || key.n > b->dense.cap)

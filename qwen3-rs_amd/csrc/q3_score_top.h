@@ -57,19 +57,18 @@ __device__ __forceinline__ unsigned long long wave_max_key(unsigned long long ke
 // workgroup's largest key: every thread keeps the largest it holds, every wave the largest of its threads, and only the wave that
 // held the round's winner forms its next one.  The wave maxima change hands in LDS, two sets by turns, one barrier a round.
 // A slice or a row shorter than k gives what it has.  Key 0 marks "nothing": only a NaN of all ones at index 0 has it.
-__global__ __launch_bounds__(256) void k_score_top_part(const ScoreTopArgs a) {
+// The body is score_top_slice: row l[0 .. n), slice `part` of `parts`, the k largest keys to keys_out[j * parts] (the caller has
+// added the part), and with ABOVE the slice's count of keys above tkey to *above_out.  q3_topk.h selects with ABOVE = false.
+template <bool ABOVE>
+__device__ __forceinline__ void score_top_slice(const float* l, int n, int k, int parts, int part, unsigned long long tkey,
+                                                unsigned long long* keys_out, int* above_out) {
     __shared__ unsigned long long best[kScoreTopMax];       // the largest keys so far, descending
     __shared__ unsigned long long wmax[2][4];
     __shared__ int above_lds[4];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const size_t row = blockIdx.y;
-    const int part = blockIdx.x;
-    const ScoreRow R = a.rows[row];
-    const float* l = a.logits + row * (size_t)a.n;
-    const unsigned long long tkey = ((unsigned long long)total_order_key(l[R.target]) << 32) | (unsigned)R.target;
-    const int per = (a.n + a.parts - 1) / a.parts;
+    const int per = (n + parts - 1) / parts;
     const long long s0 = (long long)part * per;
-    const int i0 = (int)(s0 < (long long)a.n ? s0 : (long long)a.n), i1 = (int)(s0 + per < (long long)a.n ? s0 + per : (long long)a.n);
+    const int i0 = (int)(s0 < (long long)n ? s0 : (long long)n), i1 = (int)(s0 + per < (long long)n ? s0 + per : (long long)n);
     int have = 0, above = 0;
     for (int tile = i0; tile < i1; tile += 256 * kScoreTopE) {
         unsigned hi[kScoreTopE];
@@ -83,7 +82,7 @@ __global__ __launch_bounds__(256) void k_score_top_part(const ScoreTopArgs a) {
             const int i = tile + 256 * e + tid;
             const unsigned h = total_order_key(v[e]);
             hi[e] = i < i1 ? h : 0u;
-            above += (i < i1 && (((unsigned long long)h << 32) | (unsigned)i) > tkey) ? 1 : 0;
+            if (ABOVE) above += (i < i1 && (((unsigned long long)h << 32) | (unsigned)i) > tkey) ? 1 : 0;
         }
         unsigned long long carry = tid < have ? best[tid] : 0ull;
         // the largest key this thread holds and the register it stands in (kScoreTopE: the carry); ties in the high word go to
@@ -103,7 +102,7 @@ __global__ __launch_bounds__(256) void k_score_top_part(const ScoreTopArgs a) {
         unsigned long long wbest = wave_max_key(mine);
         if (lane == 0) wmax[0][wave] = wbest;
         __syncthreads();                                    // the carries are read, set 0 stands
-        const int rounds = min(a.k, have + cnt);
+        const int rounds = min(k, have + cnt);
         for (int r = 0; r < rounds; ++r) {
             const unsigned long long* w = wmax[r & 1];
             const unsigned long long win = max(max(w[0], w[1]), max(w[2], w[3]));
@@ -123,11 +122,39 @@ __global__ __launch_bounds__(256) void k_score_top_part(const ScoreTopArgs a) {
         }
         have = rounds;
     }
-    above = group_sum_i32(above, 64);
-    if (lane == 0) above_lds[wave] = above;
+    if (ABOVE) {
+        above = group_sum_i32(above, 64);
+        if (lane == 0) above_lds[wave] = above;
+    }
     __syncthreads();                                        // also: best[] stands when no tile ran
-    if (tid < a.k) a.part_keys[(row * (size_t)a.k + (size_t)tid) * (size_t)a.parts + (size_t)part] = tid < have ? best[tid] : 0ull;
-    if (tid == 0) a.part_above[row * (size_t)a.parts + (size_t)part] = (above_lds[0] + above_lds[1]) + (above_lds[2] + above_lds[3]);
+    if (tid < k) keys_out[(size_t)tid * (size_t)parts] = tid < have ? best[tid] : 0ull;
+    if (ABOVE && tid == 0) *above_out = (above_lds[0] + above_lds[1]) + (above_lds[2] + above_lds[3]);
+}
+__global__ __launch_bounds__(256) void k_score_top_part(const ScoreTopArgs a) {
+    const size_t row = blockIdx.y;
+    const int part = blockIdx.x;
+    const ScoreRow R = a.rows[row];
+    const float* l = a.logits + row * (size_t)a.n;
+    const unsigned long long tkey = ((unsigned long long)total_order_key(l[R.target]) << 32) | (unsigned)R.target;
+    score_top_slice<true>(l, a.n, a.k, a.parts, part, tkey, a.part_keys + row * (size_t)a.k * (size_t)a.parts + (size_t)part,
+                          a.part_above + row * (size_t)a.parts + (size_t)part);
+}
+
+// One wave merges the lists of a row as they stand in LDS, entry j of part p at [j * parts + p]: lane p walks the list of part p
+// from its head; a round takes the wave's largest head and the lane that held it steps on (its own counter, below k).  Lane j
+// returns the j-th winner (0: none, and in the lanes from k on).
+__device__ __forceinline__ unsigned long long score_top_merge_wave(const unsigned long long* lists, int k, int parts, int lane) {
+    int h = 0;
+    unsigned long long cur = lane < parts ? lists[lane] : 0ull, mine = 0ull;
+    for (int r = 0; r < k; ++r) {
+        const unsigned long long win = wave_max_key(cur);
+        if (lane == r) mine = win;
+        if (cur == win && lane < parts) {
+            ++h;
+            cur = h < k ? lists[h * parts + lane] : 0ull;
+        }
+    }
+    return mine;
 }
 
 // grid = m, 256 threads.  All copy the row's lists into LDS as they stand, entry j of part p at [j][p]; then wave 0 alone goes on.
@@ -144,16 +171,7 @@ __global__ __launch_bounds__(256) void k_score_top_merge(const ScoreTopArgs a) {
     __syncthreads();
     if (threadIdx.x >= 64) return;
     const ScoreRow R = a.rows[row];
-    int h = 0;
-    unsigned long long cur = lane < a.parts ? lists[lane] : 0ull, mine = 0ull;
-    for (int r = 0; r < a.k; ++r) {
-        const unsigned long long win = wave_max_key(cur);
-        if (lane == r) mine = win;
-        if (cur == win && lane < a.parts) {
-            ++h;
-            cur = h < a.k ? lists[h * a.parts + lane] : 0ull;
-        }
-    }
+    const unsigned long long mine = score_top_merge_wave(lists, a.k, a.parts, lane);
     if (lane < a.k) {
         ScoreTop t;
         t.logit = key_to_float((unsigned)(mine >> 32));

@@ -10,7 +10,7 @@ from .engine import (Q3Error, ModelConfig, Transformer, TransformerBuilder, lib_
                      FLAG_FAST, FLAG_NO_GRAPH, FLAG_NO_VALUE_T, EXPORTED_SYMBOLS, source_build_id, SpecStats, VERIFY_MAX, lookup_draft,
                      lookup_trace, ColsStats, COLS_MAX, cols_schedule, DenseStats, dense_pack, STOP_MAX, cols_schedule_stop, EmbedStats,
                      EMBED_L2, EMBED_PREFIX, CHOICE_PREFIX, CHOICE_PER_REQUEST, CHOICE_MAX, ScoreStats, SCORE_PREFIX, SCORE_DTYPE, score_pack,
-                     SCORE_TOP_MAX, TOP_DTYPE)
+                     SCORE_TOP_MAX, TOP_DTYPE, TOP_K_MAX, op_sample_top_k)
 from .generation import (generate, chat_turn, generate_many, embed, common_prefix_len, TokenMetrics, sample_argmax, choose, rerank,
                          normalise_logits, RERANK_TEMPLATE, RERANK_INSTRUCTION, score, loglikelihood, perplexity, logprobs_of,
                          top_logprobs, top_logprobs_of)
@@ -23,4 +23,4 @@ __all__ = ["Q3Error", "ModelConfig", "Transformer", "TransformerBuilder", "lib_p
            "STOP_MAX", "cols_schedule_stop", "common_prefix_len", "embed", "EmbedStats", "EMBED_L2", "EMBED_PREFIX",
            "CHOICE_PREFIX", "CHOICE_PER_REQUEST", "CHOICE_MAX", "choose", "rerank", "normalise_logits", "RERANK_TEMPLATE", "RERANK_INSTRUCTION",
            "ScoreStats", "SCORE_PREFIX", "SCORE_DTYPE", "score_pack", "score", "loglikelihood", "perplexity", "logprobs_of",
-           "SCORE_TOP_MAX", "TOP_DTYPE", "top_logprobs", "top_logprobs_of"]
+           "SCORE_TOP_MAX", "TOP_DTYPE", "top_logprobs", "top_logprobs_of", "TOP_K_MAX", "op_sample_top_k"]

@@ -3,6 +3,7 @@
     python -m qwen3_rs_amd.cli export <MODEL_PATH> <OUTPUT_PATH> [--group-size 64]
     python -m qwen3_rs_amd.cli inference <checkpoint> [-t 1.0] [-p 0.9] [-s SEED] [-c CTX] [-m generate|chat]
                                          [-i INPUT] [-y SYSTEM] [-r 0|1] [--lookup DRAFT_LEN] [--speculate DRAFT_LEN]
+                                         [-k TOP_K]
     python -m qwen3_rs_amd.cli embed <checkpoint> -i TEXT [-i TEXT ...] [--instruct TEXT] [--dim N] [--no-normalize]
                                      [--append-token ID] [-o out.npy] [--streams N] [--context N]
     python -m qwen3_rs_amd.cli rerank <checkpoint> -q QUERY -d DOC [-d DOC ...] [--instruct TEXT] [--yes TEXT] [--no TEXT]
@@ -18,6 +19,8 @@
 earlier occurrence of the last two tokens) are checked in one pass over the weights; the output is the same, byte for byte.
 `--speculate N` does the same at any temperature through q3_generate_lookup_draw: a draft is accepted exactly when it is the
 token the sampler draws, so the output is again the same, byte for byte.
+`-k N` / `--top-k N` (q3_sampler_top_k; 1..64, 0 = off): every draw at -t > 0 is taken among the N most likely tokens; it is a setting
+of the engine, so it holds under `--speculate` too.
 `embed` reads a checkpoint out as an embedding model (q3_embed_many): every -i text is tokenized, `--append-token ID` adds one
 token id to each (Qwen3-Embedding's tokenizer appends its end-of-text token; which id that is in a given .tokenizer is the
 user's to state), `--instruct` is tokenized once and becomes the prefix all inputs share.  One line per input: index, dimension,
@@ -41,7 +44,7 @@ import sys
 import time
 
 from . import export as export_mod
-from .engine import TransformerBuilder
+from .engine import TOP_K_MAX, TransformerBuilder
 from .tokenizer import Tokenizer, export_templates, export_tokenizer
 
 
@@ -269,6 +272,8 @@ def build_parser() -> argparse.ArgumentParser:
     inf.add_argument("checkpoint")
     inf.add_argument("-t", "--temperature", type=float, default=1.0)
     inf.add_argument("-p", "--topp", type=float, default=0.9)
+    inf.add_argument("-k", "--top-k", type=int, default=0, metavar="TOP_K",
+                     help="draw among the TOP_K most likely tokens only (1..64; 0 = off, the default)")
     inf.add_argument("-s", "--seed", type=int, default=None)
     inf.add_argument("-c", "--context", type=int, default=None)
     inf.add_argument("-m", "--mode", default="chat")
@@ -345,6 +350,10 @@ def main(argv=None) -> int:
         if a.speculate and (a.lookup or not 0 < a.speculate < 32):
             print("Error: --speculate takes a draft length of 1..31 and cannot be combined with --lookup", file=sys.stderr)
             return 1
+        top_k_refusal = "Error: --top-k takes 0 (off) or a count of 1..64, at most the vocabulary size"
+        if not 0 <= a.top_k <= TOP_K_MAX:
+            print(top_k_refusal, file=sys.stderr)
+            return 1
         b = TransformerBuilder(a.checkpoint)
         if a.context:
             b = b.with_ctx_length(a.context)
@@ -352,6 +361,10 @@ def main(argv=None) -> int:
             tok = Tokenizer(a.checkpoint, t.get_config().vocab_size, a.reasoning != 0)
             seed = a.seed if a.seed is not None else int(time.time())      # lib.rs: SystemTime seconds when no seed is given
             t.set_sampler(max(a.temperature, 0.0), min(max(a.topp, 0.0), 1.0), seed)
+            if a.top_k > t.get_config().vocab_size:
+                print(top_k_refusal, file=sys.stderr)
+                return 1
+            t.set_top_k(a.top_k)                # the engine's: --speculate's rounds draw under it too
             if a.mode == "generate":
                 return run_generate(t, tok, a.input, a.lookup or a.speculate, bool(a.speculate))
             return run_chat(t, tok, a.input, a.system, a.lookup or a.speculate, bool(a.speculate))

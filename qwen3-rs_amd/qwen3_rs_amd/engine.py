@@ -35,6 +35,7 @@ EXPORTED_SYMBOLS = [
     "q3_choice_many",
     "q3_score_many", "q3_score_pack",
     "q3_score_top_many",
+    "q3_sampler_top_k", "q3_sampler_get_top_k", "q3_op_sample_top_k",
 ]
 VERIFY_MAX = 32          # Q3_VERIFY_MAX
 COLS_MAX = 32            # Q3_COLS_MAX
@@ -48,6 +49,7 @@ SCORE_DTYPE = np.dtype([("target", np.float32), ("max", np.float32), ("sum", np.
 SCORE_TOP_MAX = 64       # Q3_SCORE_TOP_MAX
 # q3_score_top as a numpy record: one of the k best tokens of a scored position (Transformer.score_top_many)
 TOP_DTYPE = np.dtype([("logit", np.float32), ("index", np.int32)])
+TOP_K_MAX = 64           # Q3_TOP_K_MAX
 
 
 class Q3Error(RuntimeError):
@@ -234,6 +236,8 @@ def _bind(path: str) -> C.CDLL:
     L.q3_prefill_batched.argtypes = [C.c_void_p, C.POINTER(C.c_int32), sz, sz, C.POINTER(C.c_int32)]
     L.q3_sampler_set.argtypes = [C.c_void_p, C.c_float, C.c_float, C.c_uint64]
     L.q3_sampler_get_rng.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+    L.q3_sampler_top_k.argtypes = [C.c_void_p, C.c_int]
+    L.q3_sampler_get_top_k.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
     L.q3_forward_sample.argtypes = [C.c_void_p, sz, sz, C.POINTER(C.c_int32)]
     L.q3_generate_sampled.argtypes = [C.c_void_p, sz, sz, sz, C.POINTER(C.c_int32)]
     L.q3_reset_kv.argtypes = [C.c_void_p]
@@ -288,6 +292,7 @@ def _bind(path: str) -> C.CDLL:
     L.q3_op_attention.argtypes = [fp, fp, fp, fp, fp, fp, sz, sz, sz, sz, sz, C.c_uint32, C.c_int]
     L.q3_op_argmax.argtypes = [fp, sz, C.POINTER(C.c_int32), C.c_int]
     L.q3_op_sample.argtypes = [fp, sz, C.c_float, C.c_float, C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.c_int]
+    L.q3_op_sample_top_k.argtypes = [fp, sz, C.c_float, C.c_float, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.c_int]
     _libs[path] = L
     return L
 
@@ -295,6 +300,14 @@ def _bind(path: str) -> C.CDLL:
 def _check(rc: int):
     if rc != 0:
         raise Q3Error(rc, load_library().q3_last_error().decode(errors="replace"))
+
+
+def _check_top_k(k, lowest: int, n: int):
+    """the range q3_sampler_top_k (lowest 0: off) and q3_op_sample_top_k (lowest 1) accept, checked before the call"""
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+        raise TypeError(f"top_k must be an integer, got {k!r}")
+    if k < lowest or k > TOP_K_MAX or k > n:
+        raise ValueError(f"top_k {k} out of range ({lowest}..{TOP_K_MAX}, at most the vocabulary's {n} entries)")
 
 
 def _i32_array(tokens):
@@ -534,6 +547,21 @@ class Transformer:
         with Sampler::sample; temperature 0 restores greedy decoding."""
         _check(self._lib.q3_sampler_set(self._h, temperature, topp, rng_seed))
         self._sampler = (temperature, topp)
+
+    def set_top_k(self, k: int):
+        """Top-k sampling (q3_sampler_top_k, include/qwen3_hip.h section 2n): every draw the engine makes at temperature > 0 -- single
+        stream, batched decode, verify blocks and column passes alike -- is taken among the k most likely tokens; 0 turns it off.
+        The setting is the engine's: it survives set_sampler, batch_init, batch_sampler_set and every generate_many call, and
+        changing it between two non-zero values rebuilds nothing."""
+        _check_top_k(k, 0, self._config.vocab_size)
+        _check(self._lib.q3_sampler_top_k(self._h, k))
+
+    @property
+    def top_k(self) -> int:
+        """the engine's top-k setting (q3_sampler_get_top_k); 0: off"""
+        out = C.c_int(0)
+        _check(self._lib.q3_sampler_get_top_k(self._h, C.byref(out)))
+        return int(out.value)
 
     def sampler_rng_state(self) -> int:
         out = C.c_uint64(0)
@@ -1052,5 +1080,18 @@ class _Ops:
         _check(load_library().q3_op_sample(self._fp(logits), logits.size, temperature, topp, C.byref(st), C.byref(out), self.device))
         return int(out.value), int(st.value)
 
+    def sample_top_k(self, logits, temperature: float, topp: float, top_k: int, rng_state: int):
+        """one Sampler::sample draw among the top_k largest logits on the device (q3_op_sample_top_k); returns (token, new rng_state)"""
+        logits = np.ascontiguousarray(logits, dtype=np.float32)
+        _check_top_k(top_k, 1, logits.size)
+        out, st = C.c_int32(-1), C.c_uint64(rng_state)
+        _check(load_library().q3_op_sample_top_k(self._fp(logits), logits.size, temperature, topp, top_k, C.byref(st), C.byref(out), self.device))
+        return int(out.value), int(st.value)
+
 
 ops = _Ops()
+
+
+def op_sample_top_k(logits, temperature: float, topp: float, top_k: int, rng_state: int):
+    """ops.sample_top_k: the operator entry of top-k sampling, beside ops.sample"""
+    return ops.sample_top_k(logits, temperature, topp, top_k, rng_state)

@@ -89,6 +89,14 @@ def _check_speculate(speculate, lookup, sample, on_logits):
         raise ValueError("speculate=(ngram >= 1, 0 < draft_len < 32)")
 
 
+def _check_top_k(transformer, sample):
+    """Top-k is a setting of the engine's sampler (Transformer.set_top_k): a host sample= callback draws from the whole
+    vocabulary and would ignore it without a word."""
+    if sample is not sample_argmax and getattr(transformer, "top_k", 0):
+        raise ValueError("Transformer.set_top_k holds for the draws of the device sampler: no sample= callback with it "
+                         "(draw on the device, speculate=, or set_top_k(0))")
+
+
 def generate(transformer, prompt_tokens: Sequence[int], max_new_tokens: Optional[int] = None,
              stop_tokens: Iterable[int] = (), sample: Callable[[np.ndarray], int] = sample_argmax,
              on_logits: Optional[Callable[[int, int, np.ndarray], None]] = None, lookup: Optional[Tuple[int, int]] = None,
@@ -98,9 +106,12 @@ def generate(transformer, prompt_tokens: Sequence[int], max_new_tokens: Optional
     TokenMetrics).  max_new_tokens bounds the loop (the reference only stops at seq_len / BOS / EOS).
     speculate=(ngram, draft_len): every token is drawn on the device by the sampler of Transformer.set_sampler (any temperature;
     argmax when none is set), several per weight pass where prompt-lookup drafts are accepted -- a draft is accepted exactly when
-    it is the token the sampler draws, so the tokens are those of this loop with `sample` = the same Sampler."""
+    it is the token the sampler draws, so the tokens are those of this loop with `sample` = the same Sampler.
+    Top-k needs no argument here: it is the engine's (Transformer.set_top_k) and every device draw honours it; together with a host
+    `sample` callback it is a ValueError."""
     if len(prompt_tokens) == 0:
         raise ValueError("Please provide a prompt")
+    _check_top_k(transformer, sample)
     stop = set(stop_tokens)
     seq_len = transformer.get_config().seq_len
     metrics = TokenMetrics()
@@ -172,6 +183,8 @@ def generate_many(transformer, prompts: Sequence[Sequence[int]], max_new_tokens:
     full prompts prefix + suffix, the stats those of the suffixes.  shared_prefix=True takes the longest common prefix of `prompts`
     that leaves every prompt a token (common_prefix_len); where the prompts share nothing it is shared_prefix=None.  None (the
     default) keeps the behaviour above.  Not offered together with dense_min > 0 (ValueError).
+    Top-k needs no argument here: it is the engine's (Transformer.set_top_k), and every sampled request of every path above draws
+    among the k most likely tokens while it is set; temperature-0 requests ignore it.
     Returns (rows, ColsStats)."""
     if any(len(p) == 0 for p in prompts):
         raise ValueError("Please provide a prompt")
@@ -386,7 +399,10 @@ def chat_turn(transformer, prompt_tokens: Sequence[int], pos: int, max_new_token
     forward() one at a time (sequential prefill, a sample drawn and discarded for each), then decode until
     a stop token.  Returns (generated tokens, next pos, TokenMetrics).
     speculate=(ngram, draft_len): the turn on the device under the sampler of Transformer.set_sampler -- the prompt through
-    Transformer.prefill (which draws and discards the per-prompt coins itself), the assistant turn as in generate(speculate=)."""
+    Transformer.prefill (which draws and discards the per-prompt coins itself), the assistant turn as in generate(speculate=).
+    Top-k needs no argument here: it is the engine's (Transformer.set_top_k) and every device draw honours it; together with a host
+    `sample` callback it is a ValueError."""
+    _check_top_k(transformer, sample)
     stop = set(stop_tokens)
     seq_len = transformer.get_config().seq_len
     next_token = 0
