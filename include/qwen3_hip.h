@@ -875,6 +875,59 @@ int q3_sampler_get_top_k(const q3_engine* e, int* top_k);
  * q3_op_sample, and Q3_ERR_ARG for top_k outside 1 .. Q3_TOP_K_MAX or > n (0 is an error here: that draw is q3_op_sample). */
 int q3_op_sample_top_k(const float* logits, size_t n, float temperature, float topp, int top_k, uint64_t* rng_state, int32_t* index, int device);
 
+/* ------------------------------------------------------------------------------------------------
+ * 2o. (behind 2n so that the earlier sections stay as they were.)  Log-probabilities of GENERATED tokens: the records of section 2l,
+ * and with top_n > 0 the tops and ranks of section 2m, for every token the five q3_generate_many_* loops produce, taken inside the
+ * loop (completion-API logprobs / top_logprobs, best-of-n by sequence likelihood, confidence filtering, distillation targets from
+ * sampled text).  Without it a caller sends prompt + output back through q3_score_many: a second pass over the weights.
+ * THE RULE.  Token out_tokens[o] of a call was taken from a row of logits l[0 .. V): the classifier row of the column whose
+ * ColEnt::out == o.  Record o is section 2l's record of that row with target = out_tokens[o]: {l[target], max, sum, argmax};
+ * top[o top_n ..] and rank[o] are section 2m's values for the same row and target.  The records are taken on the RAW logits:
+ * temperature 1, the full vocabulary, in front of top-k and top-p -- the numbers q3_score_many gives, not the sampler's rescaled
+ * distribution.  Nothing is normalised on the device (generation.logprobs_of / top_logprobs_of form log P in float64).  Under
+ * q3_generate_many_stop / _prefix the entries at or behind n_out[r] of a request are all-zero bytes.  Dense blocks and
+ * prompt-interior columns form no record.
+ * Standard (no tolerance anywhere): tokens, cache rows and rng states are bit-identical to the same call with the setting off.  The
+ * records of request r equal what q3_score_many gives for the sequence prompt_r + tokens_r with score_from[r] = prompt_len[r] (with
+ * Q3_SCORE_PREFIX: the suffixes): target and sum by bits, argmax equal, max by value; top and rank equal those of q3_score_top_many
+ * on the same input.  On a greedy request and on a temperature-0 request argmax == token, rank == 0 and bits(target) == bits(max).
+ * A row that holds a NaN is outside the standard and does not fault: the target index used as an address is the committed token
+ * clamped to [0, V); no logit and no key read back from memory becomes an address.
+ * What runs (csrc/q3_genlp.h).  A third axis on the column plans -- off, records, records + top -- built on first use; the existing
+ * forms and their graphs are untouched, and at -1 every entry point launches exactly what it launched before this section existed.
+ * With records, behind the draws of a sampled plan and in front of the turn kernel: k_genlp_exp (grid 64 x width) and k_genlp_sum
+ * (grid width), k_score_exp / k_score_sum with the row table replaced by what the device knows -- row j is column j of the pass,
+ * columns past the pass's live ones or with out < 0 return at once, the target is the token the turn kernel commits (one device
+ * function both call).  With top_n > 0 also k_genlp_top_part (grid 64 x width) and k_genlp_top_merge (grid width), section 2m's
+ * selection.  The value of top_n and the destinations stand in a control block in device memory, uploaded once per call and read
+ * when a pass runs: 1 and 64 share every plan and graph.
+ * IT DOES NOT TOUCH q3_batch_step_cols[_draw], section 2b (q3_forward_batch, q3_generate_greedy_batch), the verify paths or
+ * single-stream decode: none of them forms a record under any setting.  A single-stream caller runs q3_generate_many_* with one
+ * request.
+ * ------------------------------------------------------------------------------------------------ */
+
+/* The engine-wide setting: -1 = off (default).  0: one q3_score_rec per generated token.  1 .. Q3_SCORE_TOP_MAX: also the top_n best
+ * and the rank.  It holds for q3_generate_many_greedy, _sampled, _dense, _stop and _prefix, and survives q3_sampler_set,
+ * q3_batch_sampler_set, q3_batch_init and every generate call.
+ * Execution: waits for the stream.  The first value >= 0 allocates what the kernels need in the batched state (a control block, the
+ * parts' lists of a pass, 1 MiB, and the exps scratch of section 2l); with no batched state yet, the first generate call under the
+ * setting does.  Switching the value rebuilds no kept plan: the plans of each of the three forms stay.
+ * Q3_ERR_ARG: top_n < -1 or > Q3_SCORE_TOP_MAX (checked first, then the null engine, before anything touches the GPU); top_n >
+ * vocab_size.  A failing call leaves the engine usable and the setting as it was. */
+int q3_gen_logprobs(q3_engine* e, int top_n);
+int q3_gen_logprobs_get(const q3_engine* e, int* top_n);
+
+/* Records first .. first + count - 1 of the LAST q3_generate_many_* call, indexed exactly as its out_tokens; top is [count][top_n]
+ * with the top_n that call ran under (NULL only if that was 0), rank [count] or NULL (with top_n 0 nothing is written to either).
+ * Execution: up to three device-to-host copies and ONE synchronisation.  The generate calls keep their synchronisation counts (one
+ * per call; one per pass in the stop loop): the per-call buffers (records, tops, ranks, each as long as out_tokens) belong to the
+ * batched state, are grown behind the call's existing synchronisation, cleared on the stream in front of the first pass and released
+ * with the state.  Results stay valid until the next q3_generate_many_* call, q3_batch_init or q3_destroy.
+ * Q3_ERR_ARG: a null engine; no q3_generate_many_* call has run with the setting on since q3_batch_init, or the last one ran with
+ * it off or failed; first + count past that call's total of n_new; null recs; null top while that call's top_n > 0. */
+int q3_gen_logprobs_read(q3_engine* e, size_t first, size_t count, q3_score_rec* recs, q3_score_top* top /* [count][top_n] or NULL */,
+                         int32_t* rank /* [count] or NULL */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2288,6 +2288,14 @@ struct ColsCtl {
     int32_t* out_tokens;
 };
 
+// What a live column of a pass commits, by its mode: the argmax of its classifier row (best: the row's largest key) in a greedy
+// plan and for a temperature-0 slot of a sampled one, the draw the sampler left in the column's state, or -1 where only the coin
+// was taken (q3_sampler.h).  The turn kernels commit it; the records of q3_genlp.h take it as their target.
+enum { kColArgmax = 0, kColDrawn = 1, kColCoin = 2 };
+__device__ __forceinline__ int cols_commit_token(int mode, unsigned long long best, int drawn) {
+    return mode == kColArgmax ? (int)(unsigned)(best & 0xffffffffull) : (mode == kColDrawn ? drawn : -1);
+}
+
 // Commit: the argmax of every live column (the last-maximum fold of k_next_batch), stored where the table says.  Set-up: the
 // States and the slot table of all kColsMax columns of the next pass (whatever width its plan has), tokens resolved from the
 // prompts or from the slot's last token -- the one this very launch may just have committed.  One workgroup.
@@ -2298,7 +2306,7 @@ __global__ __launch_bounds__(kWG) void k_cols_turn(ColsCtl* ctl, const unsigned 
     for (int col = threadIdx.x >> 6; col < n_live; col += kWaves) {
         const unsigned long long best = spec_col_best(slots + (size_t)col * slot_stride, nslots);
         if (lane == 0) {
-            const int idx = (int)(unsigned)(best & 0xffffffffull);
+            const int idx = cols_commit_token(kColArgmax, best, 0);
             ctl->next[col] = idx;
             st[col].argmax = best;
             const int o = ctl->out[col];

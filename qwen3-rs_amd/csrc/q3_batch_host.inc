@@ -17,12 +17,16 @@ enum class PlanKind { Decode, Prefill, Verify, Cols, SlotPrefill };
 // n: streams, block positions or columns; grids and the stream-tile count are baked in.  draw: Verify and Cols under the sampler
 // (the plan samples every column); the sampler of a Decode plan is not part of its key: q3_batch_sampler_set drops the plan.
 // topk: the draws of the plan are the top-k form (q3_topk.h); plan_get sets it from the engine's top_k wherever the plan draws
+// genlp: Cols plans of the q3_generate_many_* loops only (cols_key sets it from the engine's q3_gen_logprobs): kGenlpRecs, the record
+// launches of q3_genlp.h stand in front of the turn kernel; kGenlpTop, the top launches behind them
+enum { kGenlpOff = 0, kGenlpRecs = 1, kGenlpTop = 2, kGenlpForms = 3 };
 struct PlanKey {
     PlanKind kind = PlanKind::Decode;
     int n = 0;
     bool draw = false;
     bool topk = false;
-    bool operator==(const PlanKey& o) const { return kind == o.kind && n == o.n && draw == o.draw && topk == o.topk; }
+    int genlp = kGenlpOff;
+    bool operator==(const PlanKey& o) const { return kind == o.kind && n == o.n && draw == o.draw && topk == o.topk && genlp == o.genlp; }
 };
 // The launches of one key, built by batch_build_plan (q3_plan_host.inc): a value, moved to where its kind is kept.
 struct Plan {
@@ -107,9 +111,10 @@ struct BatchCtx {
     DevMem<int> col_slot;        // device [kColsMax]: KV slot of every column of the pass in flight
     DevMem<ColsCtl> cols_ctl;    // device
     PinMem<ColsHost> h_cols;
-    Plan cols_plans[3][kColsNW];                        // [greedy | sampled | sampled with top-k][width], built on first use (q3_batch_init
-                                                        // starts over); the sampled ones: the same layers and classifier, then the draws
-                                                        // and k_cols_turn_draw
+    Plan cols_plans[kGenlpForms][3][kColsNW];           // [no records | records | records and top][greedy | sampled | sampled with
+                                                        // top-k][width], built on first use (q3_batch_init starts over); the sampled
+                                                        // ones: the same layers and classifier, then the draws and k_cols_turn_draw;
+                                                        // with records: the launches of q3_genlp.h in front of the turn kernel
     DevMem<ColEnt> cols_table;                          // the loop's pass table, prompts and output: grow-only device buffers
     DevMem<int> cols_ncols;
     DevMem<int32_t> cols_prompts, cols_out;
@@ -156,6 +161,20 @@ struct BatchCtx {
     DevMem<int> score_rank;
     DevMem<unsigned long long> score_top_keys;
     DevMem<int> score_top_above;
+    // log-probabilities of generated tokens (q3_gen_logprobs, section 2o).  Allocated by genlp_alloc, once: the control block the
+    // kernels of q3_genlp.h read and its pinned copy, the parts' lists and counts of a pass ([32][64][64] keys, [32][64] counts; the
+    // exps are score_probs).  Per call, grow-only: the records, tops and ranks, indexed as the call's out_tokens.  genlp_valid: the
+    // last q3_generate_many_* call ran with the setting on and succeeded; it left genlp_count records with genlp_top_n alternatives
+    DevMem<GenlpCtl> genlp_ctl;
+    PinMem<GenlpCtl> h_genlp;
+    DevMem<unsigned long long> genlp_keys;
+    DevMem<int> genlp_above;
+    DevMem<ScoreRec> genlp_recs;
+    DevMem<ScoreTop> genlp_top;
+    DevMem<int> genlp_rank;
+    size_t genlp_count = 0;
+    int genlp_top_n = 0;
+    bool genlp_valid = false;
     // packed-matrix directory
     struct PM { size_t q_off, s_off; int ntiles, ng; };
     std::vector<PM> m_qkv, m_wo, m_w13, m_w2;

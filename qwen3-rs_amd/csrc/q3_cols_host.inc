@@ -7,6 +7,8 @@
 // here on the host): the host knows every pass's width in advance, the device resolves every pass's tokens itself (k_cols_turn).
 // Section 2f is the same under the sampler: a second set of plans whose classifier is followed by the per-column draws and
 // k_cols_turn_draw (q3_sampler.h), the greedy plans and their launches untouched.
+// Section 2o is a third axis on both: under q3_gen_logprobs the loops run plans whose turn kernel is preceded by the record launches
+// of q3_genlp.h, and the call's records, tops and ranks stay in the batched state for q3_gen_logprobs_read.
 
 namespace {
 
@@ -161,7 +163,63 @@ int cols_prepare(q3_engine* e, const char* who, bool draw = false) {
 
 // the key of the column plan a pass of n live columns runs: the narrowest width that holds it.  draw: the sampled plan of that
 // width (cols_draw_alloc has run by the time it is built: its launches carry the buffers allocated there).
-PlanKey cols_key(int n, bool draw) { return PlanKey{PlanKind::Cols, kColsWidths[cols_width_index(n)], draw}; }
+// lp: the q3_gen_logprobs value a q3_generate_many_* loop runs under (-1 off, 0 records, > 0 records and top): the plan's third axis.
+// Every other caller keeps the plans without records.
+PlanKey cols_key(int n, bool draw, int lp = -1) {
+    return PlanKey{PlanKind::Cols, kColsWidths[cols_width_index(n)], draw, false, lp < 0 ? kGenlpOff : (lp == 0 ? kGenlpRecs : kGenlpTop)};
+}
+
+// What the plans with records carry (section 2o), on first use: the control block and its pinned copy, the parts' lists and counts
+// of a pass, and the exps scratch of section 2l at the size q3_score_many grows it to (so neither call ever replaces it).
+// One group, committed whole.  Freed with the context.
+int genlp_alloc(q3_engine* e) {
+    BatchCtx* b = e->batch;
+    int rc;
+    HIP_TRY(hipSetDevice(e->device));
+    const size_t n_probs = (size_t)kScoreCols * (((size_t)e->cfg.vocab_size + 3) & ~(size_t)3);
+    if ((rc = b->score_probs.grow(n_probs, e->stream))) return rc;
+    if (b->genlp_ctl) return Q3_OK;
+    DevMem<GenlpCtl> ctl; PinMem<GenlpCtl> h; DevMem<unsigned long long> keys; DevMem<int> above;
+    if ((rc = ctl.alloc(1)) || (rc = h.alloc(1)) || (rc = keys.alloc((size_t)kColsMax * kScoreTopMax * kScoreTopParts)) ||
+        (rc = above.alloc((size_t)kColsMax * kScoreTopParts)))
+        return rc;
+    HIP_TRY(hipMemsetAsync(ctl, 0, sizeof(GenlpCtl), e->stream));
+    b->genlp_ctl = std::move(ctl); b->h_genlp = std::move(h); b->genlp_keys = std::move(keys); b->genlp_above = std::move(above);
+    return Q3_OK;
+}
+
+// The per-call side of the records, behind the call's synchronisation and in front of its first pass: room for n_out records (and
+// tops and ranks with lp > 0), cleared on the stream -- a request that ends early leaves zero bytes behind its last token -- and the
+// control block.  The pinned copy is free: the call before ended with a synchronisation.
+int genlp_call_begin(q3_engine* e, int lp, size_t n_out) {
+    int rc;
+    BatchCtx* b = e->batch;
+    const size_t k = (size_t)lp;
+    if ((rc = b->genlp_recs.grow(n_out, e->stream))) return rc;
+    if (lp > 0 && ((rc = b->genlp_top.grow(n_out * k, e->stream)) || (rc = b->genlp_rank.grow(n_out, e->stream)))) return rc;
+    if (n_out) {
+        HIP_TRY(hipMemsetAsync(b->genlp_recs, 0, sizeof(ScoreRec) * n_out, e->stream));
+        if (lp > 0) {
+            HIP_TRY(hipMemsetAsync(b->genlp_top, 0, sizeof(ScoreTop) * n_out * k, e->stream));
+            HIP_TRY(hipMemsetAsync(b->genlp_rank, 0, sizeof(int) * n_out, e->stream));
+        }
+    }
+    GenlpCtl* h = b->h_genlp;
+    *h = GenlpCtl{b->genlp_recs, lp > 0 ? (ScoreTop*)b->genlp_top : nullptr, lp > 0 ? (int*)b->genlp_rank : nullptr, lp, 0};
+    HIP_TRY(hipMemcpyAsync(b->genlp_ctl, h, sizeof(GenlpCtl), hipMemcpyHostToDevice, e->stream));
+    return Q3_OK;
+}
+// the call has succeeded: its records are what q3_gen_logprobs_read hands out
+void genlp_call_end(q3_engine* e, int lp, size_t n_out) {
+    BatchCtx* b = e->batch;
+    b->genlp_count = n_out;
+    b->genlp_top_n = lp;
+    b->genlp_valid = true;
+}
+// every q3_generate_many_* call starts here: the records of the call before are gone
+void genlp_call_enter(q3_engine* e) {
+    if (e && e->batch) e->batch->genlp_valid = false;
+}
 
 // The buffers of the sampled passes, on first use: the column sampler states and the draw scratch of the verify pass
 // (spec_draw_alloc, 32 columns wide whatever max_streams is), the control block of k_cols_turn_draw, the one-pass table of a
@@ -325,7 +383,9 @@ struct ColsJobSampler {                 // the sampler side of a job (draw)
 
 // pads of every pass (they repeat the pass's last live column and emit nothing), then the whole job on the stream: the only
 // uploads of the call are the table, the run table, the prompts and the per-request sampler parameters; one synchronisation.
-int cols_job_run(q3_engine* e, ColsJob& job, bool draw, const ColsJobSampler& smp, const int32_t* prompts, size_t n_prompt, int32_t* out_tokens, size_t n_out) {
+// lp >= 0 (the generate loops under q3_gen_logprobs): the passes run the plans with records, which fill the call's n_out records.
+int cols_job_run(q3_engine* e, ColsJob& job, bool draw, const ColsJobSampler& smp, const int32_t* prompts, size_t n_prompt, int32_t* out_tokens, size_t n_out,
+                 int lp = -1) {
     int rc;
     BatchCtx* b = e->batch;
     const size_t n_passes = job.ncols.size();
@@ -340,9 +400,10 @@ int cols_job_run(q3_engine* e, ColsJob& job, bool draw, const ColsJobSampler& sm
     }
     // every plan and buffer the call needs exists before the first launch is enqueued
     if (draw && n_passes && (rc = cols_draw_alloc(e))) return rc;
+    if (lp >= 0 && (rc = genlp_alloc(e))) return rc;
     Plan* plans[kColsNW] = {nullptr};
     for (int w = 0; w < kColsNW; ++w)
-        if (width_used[w] && (rc = plan_get(e, cols_key(kColsWidths[w], draw), &plans[w]))) return rc;
+        if (width_used[w] && (rc = plan_get(e, cols_key(kColsWidths[w], draw, lp), &plans[w]))) return rc;
     std::vector<Plan*> wide_plans(job.steps.size(), nullptr);
     if (!job.runs.empty()) {
         if ((rc = dense_scratch_get(e))) return rc;
@@ -358,6 +419,7 @@ int cols_job_run(q3_engine* e, ColsJob& job, bool draw, const ColsJobSampler& sm
     if ((rc = b->cols_prompts.grow(n_prompt, e->stream))) return rc;
     if ((rc = b->cols_out.grow(n_out, e->stream))) return rc;
     if ((rc = b->dense_runs.grow(job.runs.size(), e->stream))) return rc;
+    if (lp >= 0 && (rc = genlp_call_begin(e, lp, n_out))) return rc;
     if (n_passes) {
         HIP_TRY(hipMemcpyAsync(b->cols_table, job.table.data(), sizeof(ColEnt) * n_passes * kColsMax, hipMemcpyHostToDevice, e->stream));
         HIP_TRY(hipMemcpyAsync(b->cols_ncols, job.ncols.data(), 4 * n_passes, hipMemcpyHostToDevice, e->stream));
@@ -399,6 +461,7 @@ int cols_job_run(q3_engine* e, ColsJob& job, bool draw, const ColsJobSampler& sm
     HIP_TRY(hipGetLastError());
     if (n_out) HIP_TRY(hipMemcpyAsync(out_tokens, b->cols_out, 4 * n_out, hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
+    if (lp >= 0) genlp_call_end(e, lp, n_out);
     return Q3_OK;
 }
 
@@ -523,7 +586,7 @@ int cols_generate(q3_engine* e, const ColsRequests& rq, int32_t* out_tokens, q3_
         return rc;
     if (draw && (rc = cols_draw_alloc(e))) return rc;        // the loop's per-slot sampler states are allocated there
     const ColsJobSampler smp{b->cols_slot_samp, rq.temperature, rq.topp, rq.seeds, n_requests, false};
-    if ((rc = cols_job_run(e, job, draw, smp, rq.prompts, rq.n_prompt, out_tokens, rq.n_out))) return rc;
+    if ((rc = cols_job_run(e, job, draw, smp, rq.prompts, rq.n_prompt, out_tokens, rq.n_out, e->gen_logprobs))) return rc;
     if (stats) *stats = s.stats;
     if (dstats) *dstats = dst;
     return Q3_OK;
@@ -558,6 +621,7 @@ int q3_cols_schedule(const size_t* prompt_len, const size_t* n_new, size_t n_req
 int q3_generate_many_greedy(q3_engine* e, const int32_t* prompts, const size_t* prompt_len, const size_t* n_new, size_t n_requests,
                             int32_t* out_tokens, q3_cols_stats* stats) {
     g_err[0] = 0;
+    genlp_call_enter(e);
     if (stats) *stats = q3_cols_stats{0, 0, 0, 0};
     int rc;
     ColsRequests rq;
@@ -569,6 +633,7 @@ int q3_generate_many_greedy(q3_engine* e, const int32_t* prompts, const size_t* 
 int q3_generate_many_sampled(q3_engine* e, const int32_t* prompts, const size_t* prompt_len, const size_t* n_new, size_t n_requests,
                              const float* temperature, const float* topp, const uint64_t* seeds, int32_t* out_tokens, q3_cols_stats* stats) {
     g_err[0] = 0;
+    genlp_call_enter(e);
     if (stats) *stats = q3_cols_stats{0, 0, 0, 0};
     int rc;
     ColsRequests rq;
@@ -617,6 +682,7 @@ int q3_generate_many_dense(q3_engine* e, const int32_t* prompts, const size_t* p
                            const float* temperature, const float* topp, const uint64_t* seeds, size_t dense_min, int32_t* out_tokens,
                            q3_cols_stats* stats, q3_dense_stats* dstats) {
     g_err[0] = 0;
+    genlp_call_enter(e);
     if (stats) *stats = q3_cols_stats{0, 0, 0, 0};
     if (dstats) *dstats = q3_dense_stats{0, 0, 0};
     int rc;
@@ -625,6 +691,49 @@ int q3_generate_many_dense(q3_engine* e, const int32_t* prompts, const size_t* p
     if ((rc = cols_prepare(e, "q3_generate_many_dense", draw))) return rc;
     if ((rc = cols_requests_check(e, prompts, prompt_len, n_new, n_requests, draw, temperature, topp, seeds, 0, out_tokens, rq))) return rc;
     return cols_generate(e, rq, out_tokens, stats, dense_min, dstats);
+}
+
+/* ---- section 2o: log-probability records of the generated tokens ---- */
+
+int q3_gen_logprobs(q3_engine* e, int top_n) {
+    g_err[0] = 0;
+    if (top_n < -1 || top_n > kScoreTopMax) return fail(Q3_ERR_ARG, "top_n %d out of range (-1..%d)", top_n, kScoreTopMax);
+    if (!e) return fail(Q3_ERR_ARG, "null engine");
+    if (top_n > e->cfg.vocab_size) return fail(Q3_ERR_ARG, "top_n %d exceeds vocab_size %d", top_n, e->cfg.vocab_size);
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    // a batched state that is not there yet gets its buffers from the first generate call that runs under the setting
+    int rc;
+    if (top_n >= 0 && e->batch && e->batch->has_kv && (rc = genlp_alloc(e))) return rc;
+    e->gen_logprobs = top_n;
+    return Q3_OK;
+}
+
+int q3_gen_logprobs_get(const q3_engine* e, int* top_n) {
+    g_err[0] = 0;
+    if (!e || !top_n) return fail(Q3_ERR_ARG, "null argument");
+    *top_n = e->gen_logprobs;
+    return Q3_OK;
+}
+
+int q3_gen_logprobs_read(q3_engine* e, size_t first, size_t count, q3_score_rec* recs, q3_score_top* top, int32_t* rank) {
+    g_err[0] = 0;
+    if (!e) return fail(Q3_ERR_ARG, "null engine");
+    const BatchCtx* b = e->batch;
+    if (!b || !b->genlp_valid) return fail(Q3_ERR_ARG, "the last q3_generate_many_* call left no records: none has run with q3_gen_logprobs on, or it failed");
+    if (first > b->genlp_count || count > b->genlp_count - first)
+        return fail(Q3_ERR_ARG, "records %zu .. %zu of %zu", first, first + count, b->genlp_count);
+    const size_t k = (size_t)b->genlp_top_n;
+    if (!recs) return fail(Q3_ERR_ARG, "null recs");
+    if (k > 0 && !top) return fail(Q3_ERR_ARG, "null top: the call ran with top_n %zu", k);
+    HIP_TRY(hipSetDevice(e->device));
+    if (count) {
+        HIP_TRY(hipMemcpyAsync(recs, b->genlp_recs + first, sizeof(ScoreRec) * count, hipMemcpyDeviceToHost, e->stream));
+        if (k > 0) HIP_TRY(hipMemcpyAsync(top, b->genlp_top + first * k, sizeof(ScoreTop) * count * k, hipMemcpyDeviceToHost, e->stream));
+        if (k > 0 && rank) HIP_TRY(hipMemcpyAsync(rank, b->genlp_rank + first, sizeof(int32_t) * count, hipMemcpyDeviceToHost, e->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return Q3_OK;
 }
 
 }  // extern "C"

@@ -43,6 +43,7 @@
 #include "q3_score.h"
 #include "q3_score_top.h"
 #include "q3_topk.h"
+#include "q3_genlp.h"
 #include "q3_lookup.h"
 
 namespace {
@@ -370,6 +371,10 @@ struct q3_engine {
     std::vector<Launch> sample_plan_topk;    // the second form of sample_plan: k_topk_part, k_topk_draw
     TopkArgs topk_args(const SampleArgs& s) const;
     int build_sample_plan_topk();
+    // log-probabilities of generated tokens (q3_gen_logprobs, section 2o): engine-wide, -1 = off; 0: a record per token the
+    // q3_generate_many_* loops produce; 1 .. kScoreTopMax: also that many best tokens and the rank.  What it needs on the device
+    // belongs to the batched state (genlp_alloc, q3_cols_host.inc)
+    int gen_logprobs = -1;
     int enqueue_sample();
 
     int load(const char* path, uint32_t ctx_len);

@@ -399,6 +399,33 @@ struct PlanBuilder {
         return add(F_NEXT, k_topk_draw, dim3((unsigned)n), dim3(64), 0, t);
     }
 
+    // the records of the columns the turn kernel is about to commit (q3_genlp.h; genlp_alloc has run): the draws are done, the
+    // pass's ColsCtl::n_live / out[] and, sampled, ColsDraw::mode[] still stand
+    int gen_logprobs() {
+        int rc;
+        if (!b->genlp_ctl || !b->genlp_keys || !b->genlp_above || !b->score_probs) return fail(Q3_ERR_INTERNAL, "a plan with records before genlp_alloc");
+        GenlpArgs a{};
+        a.cols = b->cols_ctl;
+        a.draw = key.draw ? (const ColsDraw*)b->cols_draw : nullptr;
+        a.st = b->st;
+        a.ctl = b->genlp_ctl;
+        a.logits = b->logits;
+        a.slots = b->slots;
+        a.probs = b->score_probs;
+        a.part_keys = b->genlp_keys;
+        a.part_above = b->genlp_above;
+        a.probs_stride = (long long)(((size_t)V + 3) & ~(size_t)3);
+        a.slot_stride = b->nslots;
+        a.nslots = nslots_used;
+        a.n = V;
+        a.parts = kScoreTopParts;
+        if ((rc = add(F_NEXT, k_genlp_exp, dim3(kScoreExpParts, (unsigned)n), dim3(256), 0, a))) return rc;
+        if ((rc = add(F_NEXT, k_genlp_sum, dim3((unsigned)n), dim3(kSampThreads), 0, a))) return rc;
+        if (key.genlp != kGenlpTop) return Q3_OK;
+        if ((rc = add(F_NEXT, k_genlp_top_part, dim3((unsigned)a.parts, (unsigned)n), dim3(256), 0, a))) return rc;
+        return add(F_NEXT, k_genlp_top_merge, dim3((unsigned)n), dim3(256), 0, a);
+    }
+
     // what follows the classifier
     int tail() {
         int rc;
@@ -416,8 +443,9 @@ struct PlanBuilder {
         }
         if (cols) {
             // sampled: the draws over the column sampler states k_cols_turn_draw set up
+            if (key.draw && (rc = draw_columns())) return rc;
+            if (key.genlp && (rc = gen_logprobs())) return rc;
             if (!key.draw) return add(F_NEXT, k_cols_turn, dim3(1), dim3(kWG), 0, b->cols_ctl, b->slots, b->nslots, nslots_used, b->st, b->col_slot);
-            if ((rc = draw_columns())) return rc;
             return add(F_NEXT, k_cols_turn_draw, dim3(1), dim3(kWG), 0, b->cols_ctl, b->cols_draw, b->spec_samp, b->st, b->col_slot);
         }
         if ((rc = add(F_NEXT, k_next_batch, dim3((unsigned)n), dim3(kWG), 0, b->st, b->slots, b->nslots, nslots_used, b->out_tokens, b->out_cap))) return rc;
@@ -465,8 +493,8 @@ int cols_width_index(int n) {
 }
 
 // The plan of `key`, from where its kind lives: the one step slot (Decode, Prefill, Verify: replaced when the key changes -- the
-// tail widths of a prefill are arbitrary), the column plans by sampler and width (key.n is one of kColsWidths; kept until
-// q3_batch_init starts over) or the dense block plans by width (kept until dense_att_grow drops them).  Built on a miss, stored
+// tail widths of a prefill are arbitrary), the column plans by records form, sampler and width (key.n is one of kColsWidths; kept
+// until q3_batch_init starts over) or the dense block plans by width (kept until dense_att_grow drops them).  Built on a miss, stored
 // only on success: a shape the kernels refuse is refused again by the next call.
 int plan_get(q3_engine* e, PlanKey key, Plan** out) {
     BatchCtx* b = e->batch;
@@ -474,8 +502,10 @@ int plan_get(q3_engine* e, PlanKey key, Plan** out) {
     bool hit;
     // the engine's top_k holds wherever the plan draws: the sampled Verify and Cols plans, and the Decode plan under the batch sampler
     key.topk = e->top_k > 0 && (key.draw || (key.kind == PlanKind::Decode && b->sampling));
+    if (key.kind != PlanKind::Cols) key.genlp = kGenlpOff;
+    if (key.genlp < kGenlpOff || key.genlp >= kGenlpForms) return fail(Q3_ERR_INTERNAL, "plan form %d", key.genlp);
     if (key.kind == PlanKind::Cols) {
-        home = &b->cols_plans[key.draw ? (key.topk ? 2 : 1) : 0][cols_width_index(key.n)];
+        home = &b->cols_plans[key.genlp][key.draw ? (key.topk ? 2 : 1) : 0][cols_width_index(key.n)];
         hit = !home->launches.empty();
     } else if (key.kind == PlanKind::SlotPrefill) {
         if (key.n <= kColsMax || key.n > b->dense.cap)

@@ -161,6 +161,7 @@ int q3_generate_many_prefix(q3_engine* e, const int32_t* prompts, const size_t* 
                             const float* temperature, const float* topp, const uint64_t* seeds, const int32_t* stop_tokens, size_t n_stop,
                             int32_t* out_tokens, size_t* n_out, q3_cols_stats* stats) {
     g_err[0] = 0;
+    genlp_call_enter(e);
     if (stats) *stats = q3_cols_stats{0, 0, 0, 0};
     int rc;
     ColsRequests rq;

@@ -757,7 +757,6 @@ struct ColAux {
     int keep;                           // 1: the draw is made and kept; 0: the coin is consumed, nothing is drawn
     int last;                           // 1: the last column of its run: its rng behind the coin becomes the slot's
 };
-enum { kColArgmax = 0, kColDrawn = 1, kColCoin = 2 };
 struct ColsDraw {
     SamplerState* slot_ss;              // [max_streams] per KV slot
     const ColAux* aux;                  // [n_passes][kColsMax], next to ColsCtl::table; padding columns: {-1, *, 0, 0}
@@ -780,7 +779,7 @@ __global__ __launch_bounds__(kWG) void k_cols_turn_draw(ColsCtl* ctl, ColsDraw* 
     SamplerState* slot_ss = dr->slot_ss;
     if (j < n_live) {
         const int mode = dr->mode[j], slot = col_slot[j];
-        const int idx = mode == kColArgmax ? (int)(unsigned)(st[j].argmax & 0xffffffffull) : (mode == kColDrawn ? st[j].token : -1);
+        const int idx = cols_commit_token(mode, st[j].argmax, st[j].token);
         ctl->next[j] = idx;
         const int o = ctl->out[j];
         if (o >= 0) {

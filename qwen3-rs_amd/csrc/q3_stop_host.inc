@@ -28,6 +28,8 @@ int cols_generate_stop(q3_engine* e, const ColsRequests& rq, const int32_t* stop
             return fail(Q3_ERR_ARG, "index out of range: stop token %d (vocab_size %d)", stop_tokens[k], e->cfg.vocab_size);
 
     if (draw && (rc = cols_draw_alloc(e))) return rc;
+    const int lp = e->gen_logprobs;                         // >= 0: the passes run the plans with records (section 2o)
+    if (lp >= 0 && (rc = genlp_alloc(e))) return rc;
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(hipStreamSynchronize(e->stream));              // nothing in flight reads the buffers that may be re-allocated
     if (!b->cols_stop && (rc = b->cols_stop.alloc(1))) return rc;
@@ -35,6 +37,7 @@ int cols_generate_stop(q3_engine* e, const ColsRequests& rq, const int32_t* stop
     if ((rc = b->cols_req.grow(5 * n_requests, e->stream))) return rc;
     if ((rc = b->cols_prompts.grow(rq.n_prompt, e->stream))) return rc;
     if ((rc = b->cols_out.grow(rq.n_out, e->stream))) return rc;
+    if (lp >= 0 && (rc = genlp_call_begin(e, lp, rq.n_out))) return rc;
 
     // uploaded once: the prompts, the per-request records, the sampler parameters, the scheduler state with the stop list
     int* dreq = b->cols_req;
@@ -81,7 +84,7 @@ int cols_generate_stop(q3_engine* e, const ColsRequests& rq, const int32_t* stop
         if (hs->n_live < 1 || hs->n_live > kColsMax) return fail(Q3_ERR_INTERNAL, "the scheduler laid out a pass of %d columns", hs->n_live);
         if (++passes > pass_cap) return fail(Q3_ERR_INTERNAL, "the scheduler asks for more than %zu passes", pass_cap);
         Plan* plan;                                        // built on first use of a width: the stream is idle here
-        if ((rc = plan_get(e, cols_key(hs->n_live, draw), &plan))) return rc;
+        if ((rc = plan_get(e, cols_key(hs->n_live, draw, lp), &plan))) return rc;
         if ((rc = plan_enqueue(e, *plan))) return rc;      // ends with the turn kernel: cursor == n_passes, it commits and sets nothing up
     }
     std::vector<int> got(n_requests);
@@ -93,6 +96,7 @@ int cols_generate_stop(q3_engine* e, const ColsRequests& rq, const int32_t* stop
     if (st.passes != passes) return fail(Q3_ERR_INTERNAL, "the scheduler counted %llu passes, the host ran %zu", (unsigned long long)st.passes, passes);
     for (size_t r = 0; r < n_requests; ++r) n_out[r] = (size_t)got[r];
     if (stats) *stats = st;
+    if (lp >= 0) genlp_call_end(e, lp, rq.n_out);
     return Q3_OK;
 }
 
@@ -104,6 +108,7 @@ int q3_generate_many_stop(q3_engine* e, const int32_t* prompts, const size_t* pr
                           const float* temperature, const float* topp, const uint64_t* seeds, const int32_t* stop_tokens, size_t n_stop,
                           int32_t* out_tokens, size_t* n_out, q3_cols_stats* stats) {
     g_err[0] = 0;
+    genlp_call_enter(e);
     if (stats) *stats = q3_cols_stats{0, 0, 0, 0};
     int rc;
     ColsRequests rq;

@@ -36,6 +36,7 @@ EXPORTED_SYMBOLS = [
     "q3_score_many", "q3_score_pack",
     "q3_score_top_many",
     "q3_sampler_top_k", "q3_sampler_get_top_k", "q3_op_sample_top_k",
+    "q3_gen_logprobs", "q3_gen_logprobs_get", "q3_gen_logprobs_read",
 ]
 VERIFY_MAX = 32          # Q3_VERIFY_MAX
 COLS_MAX = 32            # Q3_COLS_MAX
@@ -277,6 +278,9 @@ def _bind(path: str) -> C.CDLL:
     L.q3_score_many.argtypes = [C.c_void_p, i32p, szp, sz, szp, C.c_uint32, C.c_void_p, C.POINTER(_ScoreStats)]
     L.q3_score_pack.argtypes = [szp, sz, szp, C.c_int, C.c_int, C.POINTER(_ScoreStats)]
     L.q3_score_top_many.argtypes = [C.c_void_p, i32p, szp, sz, szp, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(_ScoreStats)]
+    L.q3_gen_logprobs.argtypes = [C.c_void_p, C.c_int]
+    L.q3_gen_logprobs_get.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+    L.q3_gen_logprobs_read.argtypes = [C.c_void_p, sz, sz, C.c_void_p, C.c_void_p, C.c_void_p]
     L.q3_profile.argtypes = [C.c_void_p, sz, sz, C.c_int, fp, C.POINTER(C.c_int32), C.c_int]
     L.q3_profile_name.argtypes = [C.c_int]
     L.q3_profile_name.restype = C.c_char_p
@@ -308,6 +312,14 @@ def _check_top_k(k, lowest: int, n: int):
         raise TypeError(f"top_k must be an integer, got {k!r}")
     if k < lowest or k > TOP_K_MAX or k > n:
         raise ValueError(f"top_k {k} out of range ({lowest}..{TOP_K_MAX}, at most the vocabulary's {n} entries)")
+
+
+def _check_gen_logprobs(top_n, n: int):
+    """the range q3_gen_logprobs accepts (-1: off), checked before the call"""
+    if isinstance(top_n, bool) or not isinstance(top_n, (int, np.integer)):
+        raise TypeError(f"logprobs must be an integer, got {top_n!r}")
+    if top_n < -1 or top_n > SCORE_TOP_MAX or top_n > n:
+        raise ValueError(f"logprobs {top_n} out of range (-1..{SCORE_TOP_MAX}, at most the vocabulary's {n} entries)")
 
 
 def _i32_array(tokens):
@@ -658,6 +670,7 @@ class Transformer:
         st = _ColsStats()
         n_out = call((self._h, _i32_array(flat), _size_array([len(p) for p in prompts]), _size_array(n_new), n), smp, out, C.byref(st))
         got = [int(k) for k in n_new] if n_out is None else [int(n_out[r]) for r in range(n)]
+        self._gen_last = ([int(k) for k in n_new], got, getattr(self, "_gen_lp", -1))    # what read_gen_logprobs cuts the call's records by
         buf, rows, at = out[:total], [], 0
         for k, g in zip(n_new, got):
             rows.append(buf[at:at + g])
@@ -860,6 +873,44 @@ class Transformer:
         ends = np.cumsum([0] + counts)
         cut = lambda a: None if a is None else [a[ends[r]:ends[r + 1]] for r in range(n)]
         return cut(out), cut(top), cut(rank), ScoreStats(st.waves, st.blocks, st.live_columns, st.pad_columns, st.chunks, st.scored)
+
+    # ---- log-probabilities of generated tokens (include/qwen3_hip.h section 2o)
+    def set_gen_logprobs(self, top_n: int):
+        """Records of the tokens every generate_many_* call produces (q3_gen_logprobs): -1 turns them off (the default), 0 takes one
+        SCORE_DTYPE record per generated token, 1 .. SCORE_TOP_MAX also the top_n most likely tokens and the token's rank.  The
+        records are score_many's on prompt + output -- the raw logits, in front of temperature, top-k and top-p -- taken inside
+        the loop; the tokens are the same with the setting on or off.  The setting is the engine's: it survives set_sampler,
+        batch_init and every generate_many call, and it does not touch batch_step_cols, forward_batch, verify or single-stream decode."""
+        _check_gen_logprobs(top_n, self._config.vocab_size)
+        _check(self._lib.q3_gen_logprobs(self._h, int(top_n)))
+        self._gen_lp = int(top_n)
+
+    def get_gen_logprobs(self) -> int:
+        """the engine's setting (q3_gen_logprobs_get); -1: off"""
+        out = C.c_int(-1)
+        _check(self._lib.q3_gen_logprobs_get(self._h, C.byref(out)))
+        return int(out.value)
+
+    def read_gen_logprobs(self, n_per_row=None):
+        """The records of the last generate_many_* call (q3_gen_logprobs_read), which ran under set_gen_logprobs(top_n >= 0): per
+        request (records, tops, ranks) -- SCORE_DTYPE[n], TOP_DTYPE[n, top_n], int32[n], entry j for the request's j-th token; tops
+        has no columns and ranks is empty where the call ran with top_n 0.  n_per_row: entries wanted per request (None: as many
+        as the call gave the request tokens; more than that reads the zero bytes behind a request that ended early)."""
+        cap, got, k = getattr(self, "_gen_last", ([], [], -1))
+        want = got if n_per_row is None else [int(v) for v in n_per_row]
+        if len(want) != len(cap) or any(w < 0 or w > c for w, c in zip(want, cap)):
+            raise IndexError("n_per_row: one count per request of the last call, at most its n_new")
+        total = sum(cap)
+        recs = np.zeros(total, dtype=SCORE_DTYPE)
+        top = np.zeros((total, max(k, 0)), dtype=TOP_DTYPE)
+        rank = np.zeros(total if k > 0 else 0, dtype=np.int32)
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None
+        self._batch_rc(self._lib.q3_gen_logprobs_read(self._h, 0, total, recs.ctypes.data_as(C.c_void_p), ptr(top), ptr(rank)))
+        out, at = [], 0
+        for c, w in zip(cap, want):
+            out.append((recs[at:at + w], top[at:at + w], rank[at:at + w] if k > 0 else rank[:0]))
+            at += c
+        return out
 
     def set_batch_sampler(self, temperature: float, topp: float, rng_seeds):
         """one Sampler per stream (sampler.rs:29-42), stream i seeded with rng_seeds[i]; temperature 0 = greedy"""

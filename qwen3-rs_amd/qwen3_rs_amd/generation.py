@@ -10,6 +10,8 @@ from typing import Callable, Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from .engine import SCORE_DTYPE, TOP_DTYPE
+
 
 def sample_argmax(logits: np.ndarray) -> int:
     """Sampler::sample_argmax (sampler.rs:57-59): Iterator::max_by(total_cmp) keeps the LAST maximum."""
@@ -163,7 +165,7 @@ def common_prefix_len(prompts: Sequence[Sequence[int]]) -> int:
 
 
 def generate_many(transformer, prompts: Sequence[Sequence[int]], max_new_tokens: int, stop_tokens: Iterable[int] = (), sampler=None,
-                  dense_min: int = 0, stop_on_device: bool = False, shared_prefix=None):
+                  dense_min: int = 0, stop_on_device: bool = False, shared_prefix=None, logprobs: Optional[int] = None):
     """Many greedy generations served through the slots of Transformer.batch_init in ragged column passes
     (Transformer.generate_many_greedy).  Row r holds what Transformer.prefill(prompts[r], 0) followed by generate_greedy returns on
     an engine of its own: every prompt token goes through the model (chat's prompt loop, generation.rs:116-123), then up to
@@ -185,9 +187,38 @@ def generate_many(transformer, prompts: Sequence[Sequence[int]], max_new_tokens:
     default) keeps the behaviour above.  Not offered together with dense_min > 0 (ValueError).
     Top-k needs no argument here: it is the engine's (Transformer.set_top_k), and every sampled request of every path above draws
     among the k most likely tokens while it is set; temperature-0 requests ignore it.
-    Returns (rows, ColsStats)."""
+    logprobs: None, or 0 .. 64: the log-probability of every generated token, taken inside the loop (Transformer.set_gen_logprobs,
+    which is set for this call and put back afterwards), and with logprobs > 0 that many most likely tokens at every step.  They
+    are those of score() / top_logprobs() on prompt + row: the model's raw distribution at temperature 1 over the full vocabulary,
+    whatever sampler drew the tokens.  Works with every option above; the rows are the same with or without it.
+    Returns (rows, ColsStats); with logprobs set (rows, ColsStats, per row a tuple (logprobs[n], top_ids[n, k], top_logprobs[n, k],
+    rank[n]) in the shape top_logprobs() uses, n the row's length, k = logprobs; with logprobs=0 the two middle entries are empty
+    and so is rank)."""
     if any(len(p) == 0 for p in prompts):
         raise ValueError("Please provide a prompt")
+    if logprobs is not None:
+        if isinstance(logprobs, bool) or not isinstance(logprobs, (int, np.integer)) or logprobs < 0 or logprobs > 64:
+            raise ValueError(f"logprobs {logprobs!r} out of range (None, or 0..64)")
+        before = transformer.get_gen_logprobs()
+        transformer.set_gen_logprobs(int(logprobs))
+        try:
+            rows, stats, recs = _generate_many(transformer, prompts, max_new_tokens, stop_tokens, sampler, dense_min, stop_on_device, shared_prefix, True)
+        finally:
+            transformer.set_gen_logprobs(before)
+        k = int(logprobs)
+        out = []
+        for row, rec in zip(rows, recs):
+            if rec is None:                                  # a request the context left no room for
+                rec = (np.zeros(0, dtype=SCORE_DTYPE), np.zeros((0, k), dtype=TOP_DTYPE), np.zeros(0, dtype=np.int32))
+            r, t, q = (a[:len(row)] for a in rec)
+            out.append((logprobs_of(r), np.array(t["index"], dtype=np.int32).reshape(len(r), k), top_logprobs_of(r, t).reshape(len(r), k),
+                        np.asarray(q, dtype=np.int32)))
+        return rows, stats, out
+    return _generate_many(transformer, prompts, max_new_tokens, stop_tokens, sampler, dense_min, stop_on_device, shared_prefix, False)[:2]
+
+
+def _generate_many(transformer, prompts, max_new_tokens, stop_tokens, sampler, dense_min, stop_on_device, shared_prefix, read_logprobs):
+    """generate_many behind its logprobs handling: (rows, ColsStats, per row the engine's (records, tops, ranks) or None)"""
     stop = set(stop_tokens)
     if stop_on_device and dense_min > 0:
         raise ValueError("stop_on_device=True runs column passes only: no dense_min > 0")
@@ -203,6 +234,7 @@ def generate_many(transformer, prompts: Sequence[Sequence[int]], max_new_tokens:
     n_new = [max(min(max_new_tokens, ctx - len(prefix) - len(p) + 1), 0) for p in prompts]
     live = [r for r, k in enumerate(n_new) if k > 0]
     rows: List[List[int]] = [[] for _ in prompts]
+    recs = [None] * len(prompts)
     stats = None
     if live:
         live_prompts, live_new = [prompts[r] for r in live], [n_new[r] for r in live]
@@ -225,7 +257,10 @@ def generate_many(transformer, prompts: Sequence[Sequence[int]], max_new_tokens:
         for r, toks in zip(live, got):
             k = next((i for i, t in enumerate(toks) if t in stop), None)
             rows[r] = toks if k is None else toks[:k + 1]
-    return rows, stats
+        if read_logprobs:
+            for r, rec in zip(live, transformer.read_gen_logprobs()):
+                recs[r] = rec
+    return rows, stats, recs
 
 
 def embed(transformer, prompts: Sequence[Sequence[int]], normalize: bool = True, out_dim: Optional[int] = None, shared_prefix=None):
