@@ -776,8 +776,9 @@ typedef struct q3_score_stats { uint64_t waves, blocks, live_columns, pad_column
  * scored column launches nothing behind its layers.  stats (may be NULL): q3_embed_stats' four, chunks = the sum over the blocks of
  * ceil(scored columns / 32), scored = the number of records: pure functions of the lengths and score_from (q3_score_pack).
  * Execution: everything on the engine's stream, then ONE device-to-host copy of the records and ONE synchronisation.  The table of
- * scored columns, the records and the exps of a chunk belong to the batched state: grown on demand (the stream is waited for
- * first), released with it.  No slot rng is touched; no kept plan or graph is rebuilt.  THE SLOTS ARE OVERWRITTEN FROM SLOT 0 UP, as
+ * scored columns and the records belong to the batched state: grown on demand (the stream is waited for first), released with
+ * it.  The exps of a chunk (32 rows of vocab_size floats, up to a multiple of 4) are made once, by the first call or the first plan
+ * with records of section 2o, whichever comes first, and never replaced.  No slot rng is touched; no kept plan or graph is rebuilt.  THE SLOTS ARE OVERWRITTEN FROM SLOT 0 UP, as
  * by q3_embed_many.  Every failing call leaves the engine usable.
  * Q3_ERR_ARG: everything q3_embed_many refuses (out_dim aside; a null engine before anything touches the GPU); a score_from entry
  * outside [1, prompt_len[r]]; a null out with records to write; unknown flag bits.
@@ -823,8 +824,9 @@ typedef struct q3_score_top { float logit; int32_t index; } q3_score_top;
  * workgroup per row copies the parts' lists into LDS, and one wave of it merges them and sums the counts.  parts is 64 (the
  * developer build reads Q3_SCORE_TOP_PARTS, 1 .. 64, in every call: another split, the same results).
  * Execution: as q3_score_many, with up to two more device-to-host copies in front of the ONE synchronisation: the tops and, if
- * asked for, the ranks.  The tops, the ranks and the parts' lists of a chunk belong to the batched state: grown on demand (the
- * stream is waited for first), released with it.  No slot rng is touched; no kept plan or graph is rebuilt.  Every failing call
+ * asked for, the ranks.  The tops and the ranks belong to the batched state: grown on demand (the stream is waited for first),
+ * released with it.  The parts' lists and counts of a chunk are made by the first call with k > 0 at their full size ([32][64][64]
+ * keys, [32][64] counts, about 1 MiB), never replaced, and shared with the plans with records of section 2o.  No slot rng is touched; no kept plan or graph is rebuilt.  Every failing call
  * leaves the engine usable.
  * Q3_ERR_ARG: k outside 1 .. Q3_SCORE_TOP_MAX (checked first, with the null engine, before anything touches the GPU); everything
  * q3_score_many refuses; k > vocab_size; a null top with records to write.
@@ -895,11 +897,12 @@ int q3_op_sample_top_k(const float* logits, size_t n, float temperature, float t
  * clamped to [0, V); no logit and no key read back from memory becomes an address.
  * What runs (csrc/q3_genlp.h).  A third axis on the column plans -- off, records, records + top -- built on first use; the existing
  * forms and their graphs are untouched, and at -1 every entry point launches exactly what it launched before this section existed.
- * With records, behind the draws of a sampled plan and in front of the turn kernel: k_genlp_exp (grid 64 x width) and k_genlp_sum
- * (grid width), k_score_exp / k_score_sum with the row table replaced by what the device knows -- row j is column j of the pass,
- * columns past the pass's live ones or with out < 0 return at once, the target is the token the turn kernel commits (one device
- * function both call).  With top_n > 0 also k_genlp_top_part (grid 64 x width) and k_genlp_top_merge (grid width), section 2m's
- * selection.  The value of top_n and the destinations stand in a control block in device memory, uploaded once per call and read
+ * With records, behind the draws of a sampled plan and in front of the turn kernel: k_score_exp (grid 64 x width) and k_score_sum
+ * (grid width), the kernels of section 2l themselves with their row source -- there a host table -- replaced by what the device
+ * knows (PassRows): row j is column j of the pass, columns past the pass's live ones or with out < 0 return at once, the target is
+ * the token the turn kernel commits (one device function both call).  With top_n > 0 also k_score_top_part (grid 64 x width) and
+ * k_score_top_merge (grid width), section 2m's selection.  The exps and the parts' lists are the scratch of sections 2l and 2m,
+ * one allocation of fixed size per batched state that no call replaces.  The value of top_n and the destinations stand in a control block in device memory, uploaded once per call and read
  * when a pass runs: 1 and 64 share every plan and graph.
  * IT DOES NOT TOUCH q3_batch_step_cols[_draw], section 2b (q3_forward_batch, q3_generate_greedy_batch), the verify paths or
  * single-stream decode: none of them forms a record under any setting.  A single-stream caller runs q3_generate_many_* with one
@@ -909,9 +912,9 @@ int q3_op_sample_top_k(const float* logits, size_t n, float temperature, float t
 /* The engine-wide setting: -1 = off (default).  0: one q3_score_rec per generated token.  1 .. Q3_SCORE_TOP_MAX: also the top_n best
  * and the rank.  It holds for q3_generate_many_greedy, _sampled, _dense, _stop and _prefix, and survives q3_sampler_set,
  * q3_batch_sampler_set, q3_batch_init and every generate call.
- * Execution: waits for the stream.  The first value >= 0 allocates what the kernels need in the batched state (a control block, the
- * parts' lists of a pass, 1 MiB, and the exps scratch of section 2l); with no batched state yet, the first generate call under the
- * setting does.  Switching the value rebuilds no kept plan: the plans of each of the three forms stay.
+ * Execution: waits for the stream.  The first value >= 0 allocates the control block in the batched state; with no batched state yet,
+ * the first generate call under the setting does.  The exps and the parts' lists are the scratch of sections 2l and 2m, made when
+ * the first plan with records is built if no score call has made them.  Switching the value rebuilds no kept plan: the plans of each of the three forms stay.
  * Q3_ERR_ARG: top_n < -1 or > Q3_SCORE_TOP_MAX (checked first, then the null engine, before anything touches the GPU); top_n >
  * vocab_size.  A failing call leaves the engine usable and the setting as it was. */
 int q3_gen_logprobs(q3_engine* e, int top_n);

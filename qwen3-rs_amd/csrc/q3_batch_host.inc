@@ -18,7 +18,7 @@ enum class PlanKind { Decode, Prefill, Verify, Cols, SlotPrefill };
 // (the plan samples every column); the sampler of a Decode plan is not part of its key: q3_batch_sampler_set drops the plan.
 // topk: the draws of the plan are the top-k form (q3_topk.h); plan_get sets it from the engine's top_k wherever the plan draws
 // genlp: Cols plans of the q3_generate_many_* loops only (cols_key sets it from the engine's q3_gen_logprobs): kGenlpRecs, the record
-// launches of q3_genlp.h stand in front of the turn kernel; kGenlpTop, the top launches behind them
+// launches (record_launches, q3_plan_host.inc) stand in front of the turn kernel; kGenlpTop, the top launches behind them
 enum { kGenlpOff = 0, kGenlpRecs = 1, kGenlpTop = 2, kGenlpForms = 3 };
 struct PlanKey {
     PlanKind kind = PlanKind::Decode;
@@ -114,7 +114,7 @@ struct BatchCtx {
     Plan cols_plans[kGenlpForms][3][kColsNW];           // [no records | records | records and top][greedy | sampled | sampled with
                                                         // top-k][width], built on first use (q3_batch_init starts over); the sampled
                                                         // ones: the same layers and classifier, then the draws and k_cols_turn_draw;
-                                                        // with records: the launches of q3_genlp.h in front of the turn kernel
+                                                        // with records: the record launches in front of the turn kernel
     DevMem<ColEnt> cols_table;                          // the loop's pass table, prompts and output: grow-only device buffers
     DevMem<int> cols_ncols;
     DevMem<int32_t> cols_prompts, cols_out;
@@ -150,25 +150,24 @@ struct BatchCtx {
     // choice logits (q3_choice_many): the uploaded candidate ids and the output rows [n_requests][k], grow-only
     DevMem<int32_t> choice_cand;
     DevMem<float> choice_out;
-    // scores (q3_score_many): the table of a call's scored columns, its records, and the exps of one chunk [32][vocab_size up to a
-    // multiple of 4], grow-only
+    // the scratch of the record kernels (q3_score.h), shared by the score calls and the plans with records and made by record_scratch
+    // (q3_plan_host.inc) alone, on first use at its full size, never replaced while the context lives: the exps of 32 rows, and -- from
+    // the first use with k > 0 on -- the parts' lists and counts of 32 rows ([32][64][64] keys, [32][64] counts)
+    DevMem<float> record_exps;
+    DevMem<unsigned long long> record_part_keys;
+    DevMem<int> record_part_above;
+    // scores (q3_score_many): the table of a call's scored columns and its records, grow-only
     DevMem<ScoreRow> score_rows;
     DevMem<ScoreRec> score_out;
-    DevMem<float> score_probs;
-    // ... with the k best (q3_score_top_many): the call's [records][k] pairs and ranks, and one chunk's lists and counts per part
-    // ([32][parts][k] keys, [32][parts] counts), grow-only
+    // ... with the k best (q3_score_top_many): the call's [records][k] pairs and ranks, grow-only
     DevMem<ScoreTop> score_top;
     DevMem<int> score_rank;
-    DevMem<unsigned long long> score_top_keys;
-    DevMem<int> score_top_above;
     // log-probabilities of generated tokens (q3_gen_logprobs, section 2o).  Allocated by genlp_alloc, once: the control block the
-    // kernels of q3_genlp.h read and its pinned copy, the parts' lists and counts of a pass ([32][64][64] keys, [32][64] counts; the
-    // exps are score_probs).  Per call, grow-only: the records, tops and ranks, indexed as the call's out_tokens.  genlp_valid: the
-    // last q3_generate_many_* call ran with the setting on and succeeded; it left genlp_count records with genlp_top_n alternatives
+    // pass source of q3_genlp.h reads and its pinned copy.  Per call, grow-only: the records, tops and ranks, indexed as the call's
+    // out_tokens.  genlp_valid: the last q3_generate_many_* call ran with the setting on and succeeded; it left genlp_count records
+    // with genlp_top_n alternatives
     DevMem<GenlpCtl> genlp_ctl;
     PinMem<GenlpCtl> h_genlp;
-    DevMem<unsigned long long> genlp_keys;
-    DevMem<int> genlp_above;
     DevMem<ScoreRec> genlp_recs;
     DevMem<ScoreTop> genlp_top;
     DevMem<int> genlp_rank;

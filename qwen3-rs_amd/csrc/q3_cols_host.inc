@@ -8,7 +8,7 @@
 // Section 2f is the same under the sampler: a second set of plans whose classifier is followed by the per-column draws and
 // k_cols_turn_draw (q3_sampler.h), the greedy plans and their launches untouched.
 // Section 2o is a third axis on both: under q3_gen_logprobs the loops run plans whose turn kernel is preceded by the record launches
-// of q3_genlp.h, and the call's records, tops and ranks stay in the batched state for q3_gen_logprobs_read.
+// of q3_score.h / q3_score_top.h over the pass in flight (q3_genlp.h), and the call's records, tops and ranks stay in the batched state for q3_gen_logprobs_read.
 
 namespace {
 
@@ -169,22 +169,17 @@ PlanKey cols_key(int n, bool draw, int lp = -1) {
     return PlanKey{PlanKind::Cols, kColsWidths[cols_width_index(n)], draw, false, lp < 0 ? kGenlpOff : (lp == 0 ? kGenlpRecs : kGenlpTop)};
 }
 
-// What the plans with records carry (section 2o), on first use: the control block and its pinned copy, the parts' lists and counts
-// of a pass, and the exps scratch of section 2l at the size q3_score_many grows it to (so neither call ever replaces it).
-// One group, committed whole.  Freed with the context.
+// What the plans with records carry of section 2o's own, on first use: the control block and its pinned copy (the scratch of the
+// record launches is record_args', q3_plan_host.inc).  One group, committed whole.  Freed with the context.
 int genlp_alloc(q3_engine* e) {
     BatchCtx* b = e->batch;
     int rc;
-    HIP_TRY(hipSetDevice(e->device));
-    const size_t n_probs = (size_t)kScoreCols * (((size_t)e->cfg.vocab_size + 3) & ~(size_t)3);
-    if ((rc = b->score_probs.grow(n_probs, e->stream))) return rc;
     if (b->genlp_ctl) return Q3_OK;
-    DevMem<GenlpCtl> ctl; PinMem<GenlpCtl> h; DevMem<unsigned long long> keys; DevMem<int> above;
-    if ((rc = ctl.alloc(1)) || (rc = h.alloc(1)) || (rc = keys.alloc((size_t)kColsMax * kScoreTopMax * kScoreTopParts)) ||
-        (rc = above.alloc((size_t)kColsMax * kScoreTopParts)))
-        return rc;
+    HIP_TRY(hipSetDevice(e->device));
+    DevMem<GenlpCtl> ctl; PinMem<GenlpCtl> h;
+    if ((rc = ctl.alloc(1)) || (rc = h.alloc(1))) return rc;
     HIP_TRY(hipMemsetAsync(ctl, 0, sizeof(GenlpCtl), e->stream));
-    b->genlp_ctl = std::move(ctl); b->h_genlp = std::move(h); b->genlp_keys = std::move(keys); b->genlp_above = std::move(above);
+    b->genlp_ctl = std::move(ctl); b->h_genlp = std::move(h);
     return Q3_OK;
 }
 
@@ -465,8 +460,8 @@ int cols_job_run(q3_engine* e, ColsJob& job, bool draw, const ColsJobSampler& sm
     return Q3_OK;
 }
 
-// One set of runs that enter their slots together, packed into blocks by dense_pack_run and added to the job: a block of more
-// than 32 columns is a wide step; a narrower one (and every block of a shape the dense kernels refuse: its cap is 32) is a
+// One set of runs that enter their slots together, packed into blocks (dense_blocks, q3_dense_host.inc) and added to the job: a
+// wide block is a wide step; a narrower one (and every block of a shape the dense kernels refuse: its cap is 32) is a
 // column pass of its live columns, which emit nothing and under the sampler consume their coins (keep = 0).
 // runs: slot, first position, prompt offset and length of every run.  first_req (sampled loop only, else nullptr): run i belongs
 // to request first_req[i]; loaded / wide_coins are the loop's per-request records of whether a pass has loaded the request's
@@ -476,23 +471,16 @@ void dense_job_add(q3_engine* e, ColsJob& job, const std::vector<DenseIn>& in, b
                    std::vector<size_t>* wide_coins, q3_dense_stats& total) {
     std::vector<size_t> lens(in.size());
     for (size_t i = 0; i < in.size(); ++i) lens[i] = in[i].len;
-    struct Piece { uint64_t block; int col0; size_t run, off; int len; };
-    std::vector<Piece> pieces;
-    q3_dense_stats st;
-    dense_pack_run(lens.data(), lens.size(), dense_block_cap(e), [&](uint64_t block, int col0, size_t run, size_t off, int len) {
-        pieces.push_back(Piece{block, col0, run, off, len});
-    }, st);
-    total.blocks += st.blocks;
-    total.live_columns += st.live_columns;
-    total.pad_columns += st.pad_columns;
-    for (size_t i0 = 0; i0 < pieces.size();) {
-        size_t i1 = i0;
-        while (i1 < pieces.size() && pieces[i1].block == pieces[i0].block) ++i1;
-        const int n = (pieces[i1 - 1].col0 + pieces[i1 - 1].len + 7) & ~7;
-        if (n > kColsMax) {
-            job.steps.push_back(ColsJobStep{true, n, job.runs.size(), i1 - i0});
+    const DenseBlocks db = dense_blocks(lens.data(), lens.size(), dense_block_cap(e));
+    total.blocks += db.stats.blocks;
+    total.live_columns += db.stats.live_columns;
+    total.pad_columns += db.stats.pad_columns;
+    for (const DenseBlock& bl : db.blocks) {
+        const size_t i0 = bl.p0, i1 = bl.p0 + bl.np;
+        if (bl.wide) {
+            job.steps.push_back(ColsJobStep{true, bl.n, job.runs.size(), bl.np});
             for (size_t i = i0; i < i1; ++i) {
-                const Piece& pc = pieces[i];
+                const DensePiece& pc = db.pieces[i];
                 const DenseIn& r = in[pc.run];
                 job.runs.push_back(DenseRun{pc.col0, r.slot, r.pos0 + (int)pc.off, r.src0 + (int)pc.off, pc.len});
                 job.max_end = std::max(job.max_end, (size_t)r.pos0 + pc.off + (size_t)pc.len);
@@ -501,7 +489,7 @@ void dense_job_add(q3_engine* e, ColsJob& job, const std::vector<DenseIn>& in, b
         } else {
             const size_t p = job.add_pass(draw);
             for (size_t i = i0; i < i1; ++i) {
-                const Piece& pc = pieces[i];
+                const DensePiece& pc = db.pieces[i];
                 const DenseIn& r = in[pc.run];
                 for (int k = 0; k < pc.len; ++k) {
                     const size_t at = p * kColsMax + job.ncols[p]++;
@@ -516,7 +504,6 @@ void dense_job_add(q3_engine* e, ColsJob& job, const std::vector<DenseIn>& in, b
                 }
             }
         }
-        i0 = i1;
     }
 }
 

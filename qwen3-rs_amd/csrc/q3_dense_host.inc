@@ -43,6 +43,30 @@ void dense_pack_run(const size_t* run_len, size_t n_runs, int block_cap, Emit&& 
     close();
 }
 
+// The blocks of dense_pack_run as values: what the walks that enqueue them consume (embed_walk, q3_embed_host.inc; dense_job_add,
+// q3_cols_host.inc).  A piece: columns [col0, col0 + len) of its block hold positions [off, off + len) of run `run`.  A block: its
+// columns up to a multiple of 8 behind its last piece, whether that is more than a column pass holds (wide: a PlanKind::SlotPrefill
+// block; otherwise a pass of its live columns), and its pieces [p0, p0 + np) in column order.
+struct DensePiece { int col0; size_t run, off; int len; };
+struct DenseBlock { int n; bool wide; size_t p0, np; };
+struct DenseBlocks {
+    std::vector<DensePiece> pieces;
+    std::vector<DenseBlock> blocks;
+    q3_dense_stats stats;
+};
+DenseBlocks dense_blocks(const size_t* run_len, size_t n_runs, int block_cap) {
+    DenseBlocks d;
+    dense_pack_run(run_len, n_runs, block_cap, [&](uint64_t block, int col0, size_t run, size_t off, int len) {
+        if (block == d.blocks.size()) d.blocks.push_back(DenseBlock{0, false, d.pieces.size(), 0});
+        DenseBlock& bl = d.blocks.back();
+        bl.n = (col0 + len + 7) & ~7;
+        bl.wide = bl.n > kColsMax;
+        bl.np++;
+        d.pieces.push_back(DensePiece{col0, run, off, len});
+    }, d.stats);
+    return d;
+}
+
 int dense_pack_check(const size_t* run_len, size_t n_runs, int block_cap) {
     if (!run_len || n_runs == 0) return fail(Q3_ERR_ARG, "null or empty run list");
     if (block_cap < 16 || block_cap % 16 != 0) return fail(Q3_ERR_ARG, "block_cap %d must be a multiple of 16 and at least 16", block_cap);

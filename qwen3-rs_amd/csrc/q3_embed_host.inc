@@ -56,27 +56,18 @@ int embed_walk(q3_engine* e, const int32_t* prompts, const size_t* prompt_len, s
     std::vector<EmbedStep> steps;
     size_t max_end = 0;
     bool width_used[kColsNW] = {false};
-    struct Piece { uint64_t block; int col0; size_t run, off; int len; };
-    std::vector<Piece> pieces;
     for (size_t w0 = 0; w0 < n_requests; w0 += S) {
         const size_t nw = std::min(S, n_requests - w0);
-        pieces.clear();
-        q3_dense_stats ds;
-        dense_pack_run(prompt_len + w0, nw, cap, [&](uint64_t block, int col0, size_t run, size_t o, int len) {
-            pieces.push_back(Piece{block, col0, run, o, len});
-        }, ds);
+        const DenseBlocks db = dense_blocks(prompt_len + w0, nw, cap);
         st.waves++;
-        st.blocks += ds.blocks;
-        st.live_columns += ds.live_columns;
-        st.pad_columns += ds.pad_columns;
-        for (size_t i0 = 0; i0 < pieces.size();) {
-            size_t i1 = i0;
-            while (i1 < pieces.size() && pieces[i1].block == pieces[i0].block) ++i1;
-            const int n = (pieces[i1 - 1].col0 + pieces[i1 - 1].len + 7) & ~7;
-            EmbedStep s{n > kColsMax, n, runs.size(), i1 - i0, rows.size(), 0};
+        st.blocks += db.stats.blocks;
+        st.live_columns += db.stats.live_columns;
+        st.pad_columns += db.stats.pad_columns;
+        for (const DenseBlock& bl : db.blocks) {
+            EmbedStep s{bl.wide, bl.n, runs.size(), bl.np, rows.size(), 0};
             int col = 0;
-            for (size_t i = i0; i < i1; ++i) {
-                const Piece& pc = pieces[i];
+            for (size_t i = bl.p0; i < bl.p0 + bl.np; ++i) {
+                const DensePiece& pc = db.pieces[i];
                 const size_t r = w0 + pc.run;
                 const int c0 = s.wide ? pc.col0 : col;
                 runs.push_back(DenseRun{c0, (int)pc.run, (int)(P + pc.off), (int)(off[r] + pc.off), pc.len});
@@ -91,7 +82,6 @@ int embed_walk(q3_engine* e, const int32_t* prompts, const size_t* prompt_len, s
             }
             s.ng = rows.size() - s.g0;
             steps.push_back(s);
-            i0 = i1;
         }
     }
 

@@ -82,6 +82,59 @@ AttnFn attn_pf2_fn(int kvm, int np) {
     return kvm == 4 ? (AttnFn)k_attn_pf2<4, 4> : (AttnFn)k_attn_pf2<2, 4>;
 }
 
+// ---- the record launches (q3_score.h, q3_score_top.h): what q3_score_many / q3_score_top_many enqueue behind the classifier of a
+// chunk and what a plan with records holds in front of its turn kernel.
+// The scratch the four kernels work on, made here and nowhere else: on first use, at its full size (kScoreCols rows of exps; with
+// `lists`, the k > 0 launches' part lists and counts at kScoreTopMax and kScoreTopParts), and never again while the context lives --
+// so a captured plan's pointers hold whatever call comes next, and a call without lists makes none.
+size_t record_exps_stride(const q3_engine* e) { return ((size_t)e->cfg.vocab_size + 3) & ~(size_t)3; }
+int record_scratch(q3_engine* e, bool lists) {
+    static_assert(kScoreCols == kColsMax, "a chunk and a pass are as wide as the classifier's output");
+    BatchCtx* b = e->batch;
+    int rc;
+    HIP_TRY(hipSetDevice(e->device));
+    if (!b->record_exps && (rc = b->record_exps.alloc((size_t)kScoreCols * record_exps_stride(e)))) return rc;
+    if (lists && !b->record_part_keys) {
+        // one group, committed whole
+        DevMem<unsigned long long> keys; DevMem<int> above;
+        if ((rc = keys.alloc((size_t)kScoreCols * kScoreTopMax * kScoreTopParts)) || (rc = above.alloc((size_t)kScoreCols * kScoreTopParts))) return rc;
+        b->record_part_keys = std::move(keys); b->record_part_above = std::move(above);
+    }
+    return Q3_OK;
+}
+// The arguments of the four kernels over the classifier's output of the context and that scratch (record_scratch has run; nothing is
+// written here).  nslots: the argmax keys the classifier launch leaves per row; parts: the slices per row of k_score_top_part.
+int record_args(const q3_engine* e, bool lists, int nslots, int parts, RecordArgs& a) {
+    const BatchCtx* b = e->batch;
+    if (nslots < 1 || nslots > b->nslots) return fail(Q3_ERR_INTERNAL, "%d argmax slots of %d", nslots, b->nslots);
+    if (parts < 1 || parts > kScoreTopParts) return fail(Q3_ERR_INTERNAL, "%d slices per row of %d", parts, kScoreTopParts);
+    if (!b->record_exps || (lists && !b->record_part_keys)) return fail(Q3_ERR_INTERNAL, "record launches before record_scratch");
+    a = RecordArgs{};
+    a.logits = b->logits;
+    a.slots = b->slots;
+    a.exps = b->record_exps;
+    a.part_keys = lists ? (unsigned long long*)b->record_part_keys : nullptr;
+    a.part_above = lists ? (int*)b->record_part_above : nullptr;
+    a.exps_stride = (long long)record_exps_stride(e);
+    a.slot_stride = b->nslots;
+    a.nslots = nslots;
+    a.n = e->cfg.vocab_size;
+    a.parts = parts;
+    return Q3_OK;
+}
+
+// The launches over `rows` rows of source `src`, the top pair where a.part_keys stands, stated once.  put(ends_group, kernel, grid,
+// block, a, src) enqueues or appends one; ends_group: the launch is the last of a group Q3_DEBUG_TIMING times (exps | sum | top).
+template <class Src, class Put>
+int record_launches(const RecordArgs& a, const Src& src, int rows, Put&& put) {
+    int rc;
+    if ((rc = put(true, k_score_exp<Src>, dim3(kScoreExpParts, (unsigned)rows), dim3(256), a, src))) return rc;
+    if ((rc = put(true, k_score_sum<Src>, dim3((unsigned)rows), dim3(kSampThreads), a, src))) return rc;
+    if (!a.part_keys) return Q3_OK;
+    if ((rc = put(false, k_score_top_part<Src>, dim3((unsigned)a.parts, (unsigned)rows), dim3(256), a, src))) return rc;
+    return put(true, k_score_top_merge<Src>, dim3((unsigned)rows), dim3(256), a, src);
+}
+
 // ---- the builder: the launches of key.n streams (Decode), block positions (Prefill, Verify; draw: Verify under the sampler),
 // columns (Cols; draw: the sampled column plan) or columns of a dense block over the slots (SlotPrefill), appended to `out`.
 // It reads the engine and the context and writes neither.
@@ -399,31 +452,16 @@ struct PlanBuilder {
         return add(F_NEXT, k_topk_draw, dim3((unsigned)n), dim3(64), 0, t);
     }
 
-    // the records of the columns the turn kernel is about to commit (q3_genlp.h; genlp_alloc has run): the draws are done, the
-    // pass's ColsCtl::n_live / out[] and, sampled, ColsDraw::mode[] still stand
+    // the records of the columns the turn kernel is about to commit (PassRows, q3_genlp.h; genlp_alloc has run, and plan_get has
+    // made the scratch): the draws are done, the pass's ColsCtl::n_live / out[] and, sampled, ColsDraw::mode[] still stand
     int gen_logprobs() {
-        int rc;
-        if (!b->genlp_ctl || !b->genlp_keys || !b->genlp_above || !b->score_probs) return fail(Q3_ERR_INTERNAL, "a plan with records before genlp_alloc");
-        GenlpArgs a{};
-        a.cols = b->cols_ctl;
-        a.draw = key.draw ? (const ColsDraw*)b->cols_draw : nullptr;
-        a.st = b->st;
-        a.ctl = b->genlp_ctl;
-        a.logits = b->logits;
-        a.slots = b->slots;
-        a.probs = b->score_probs;
-        a.part_keys = b->genlp_keys;
-        a.part_above = b->genlp_above;
-        a.probs_stride = (long long)(((size_t)V + 3) & ~(size_t)3);
-        a.slot_stride = b->nslots;
-        a.nslots = nslots_used;
-        a.n = V;
-        a.parts = kScoreTopParts;
-        if ((rc = add(F_NEXT, k_genlp_exp, dim3(kScoreExpParts, (unsigned)n), dim3(256), 0, a))) return rc;
-        if ((rc = add(F_NEXT, k_genlp_sum, dim3((unsigned)n), dim3(kSampThreads), 0, a))) return rc;
-        if (key.genlp != kGenlpTop) return Q3_OK;
-        if ((rc = add(F_NEXT, k_genlp_top_part, dim3((unsigned)a.parts, (unsigned)n), dim3(256), 0, a))) return rc;
-        return add(F_NEXT, k_genlp_top_merge, dim3((unsigned)n), dim3(256), 0, a);
+        if (!b->genlp_ctl) return fail(Q3_ERR_INTERNAL, "a plan with records before genlp_alloc");
+        RecordArgs a;
+        if (int rc = record_args(e, key.genlp == kGenlpTop, nslots_used, kScoreTopParts, a)) return rc;
+        const PassRows src{b->cols_ctl, key.draw ? (const ColsDraw*)b->cols_draw : nullptr, b->st, b->genlp_ctl};
+        return record_launches(a, src, n, [&](bool, auto kernel, dim3 grid, dim3 blk, const RecordArgs& ra, const PassRows& rs) {
+            return add(F_NEXT, kernel, grid, blk, 0, ra, rs);
+        });
     }
 
     // what follows the classifier
@@ -517,6 +555,9 @@ int plan_get(q3_engine* e, PlanKey key, Plan** out) {
     }
     if (!hit) {
         HIP_TRY(hipSetDevice(e->device));
+        // the scratch a plan with records points at exists before the plan does
+        if (key.genlp != kGenlpOff)
+            if (int rc = record_scratch(e, key.genlp == kGenlpTop)) return rc;
         Plan built;
         if (int rc = batch_build_plan(e, key, built)) return rc;
         if (key.kind == PlanKind::SlotPrefill) home = &b->dense_plans[key.n];

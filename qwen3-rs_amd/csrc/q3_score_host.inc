@@ -8,6 +8,9 @@
 // consults per-column state for the classifier, so none is set up here.
 // q3_score_many and q3_score_top_many are one body (score_run): with k > 0 every chunk runs k_score_top_part and k_score_top_merge
 // (q3_score_top.h) behind k_score_sum, over the same rows; with k == 0 nothing of that is allocated, enqueued or copied.
+// The launches behind the classifier and the scratch they work on are record_launches and record_scratch / record_args
+// (q3_plan_host.inc), which the plans with records of the q3_generate_many_* loops use as well; here the rows are the call's table
+// (TableRows, q3_score.h).
 
 namespace {
 
@@ -144,12 +147,11 @@ int score_run(q3_engine* e, const char* who, const int32_t* prompts, const size_
     if (k && n_rec && !top) return fail(Q3_ERR_ARG, "null top for %zu records", n_rec);
     const int parts = score_top_parts();
     const size_t n_top = k ? n_rec * (size_t)k : 0, n_rank = k && rank ? n_rec : 0;
-    const size_t n_keys = k ? (size_t)kScoreCols * (size_t)parts * (size_t)k : 0, n_above = k ? (size_t)kScoreCols * (size_t)parts : 0;
-    const size_t probs_stride = ((size_t)V + 3) & ~(size_t)3, n_probs = (size_t)kScoreCols * probs_stride;
     std::vector<ScoreRow> rows;
     std::vector<ScoreChunk> chunks;
     std::vector<size_t> step_chunk0;            // chunks [step_chunk0[i], step_chunk0[i + 1]) are block i's
     Plan* plans[kColsNW] = {nullptr};
+    RecordArgs args[kColsNW];                   // of the record launches behind plans[w]'s classifier
     q3_embed_stats st;
     ScoreTiming tm;
     tm.on = getenv("Q3_DEBUG_TIMING") != nullptr;
@@ -189,18 +191,18 @@ int score_run(q3_engine* e, const char* who, const int32_t* prompts, const size_
                         if (rows.size() != n_rec) return fail(Q3_ERR_INTERNAL, "%s: %zu table rows for %zu records", who, rows.size(), n_rec);
                         // the column plans whose classifier the chunks run, kept as the walk's own are
                         int rc2;
+                        if ((rc2 = record_scratch(e, k > 0))) return rc2;
                         for (int w = 0; w < kColsNW; ++w) {
                             if (!width_used[w]) continue;
                             if ((rc2 = plan_get(e, cols_key(kColsWidths[w], false), &plans[w]))) return rc2;
                             if (plans[w]->launches.size() < plans[w]->head + 2) return fail(Q3_ERR_INTERNAL, "%s: a column plan without a classifier", who);
+                            // one argmax key per workgroup of the classifier launch
+                            if ((rc2 = record_args(e, k > 0, (int)plans[w]->launches[plans[w]->head + 1].grid.x, parts, args[w]))) return rc2;
                         }
                         if ((rc2 = b->score_rows.grow(n_rec, e->stream))) return rc2;
                         if ((rc2 = b->score_out.grow(n_rec, e->stream))) return rc2;
-                        if ((rc2 = b->score_probs.grow(n_probs, e->stream))) return rc2;
                         if ((rc2 = b->score_top.grow(n_top, e->stream))) return rc2;
                         if ((rc2 = b->score_rank.grow(n_rank, e->stream))) return rc2;
-                        if ((rc2 = b->score_top_keys.grow(n_keys, e->stream))) return rc2;
-                        if ((rc2 = b->score_top_above.grow(n_above, e->stream))) return rc2;
                         if (n_rec) HIP_TRY(hipMemcpyAsync(b->score_rows, rows.data(), sizeof(ScoreRow) * n_rec, hipMemcpyHostToDevice, e->stream));
                         return (int)Q3_OK;
                     },
@@ -220,35 +222,12 @@ int score_run(q3_engine* e, const char* who, const int32_t* prompts, const size_
                             if ((rc2 = tm.mark(e->stream))) return rc2;
                             if ((rc2 = plan_enqueue_range(e, p, p.head, p.head + 2))) return rc2;
                             if ((rc2 = tm.mark(e->stream))) return rc2;
-                            ScoreArgs a{};
-                            a.rows = tab;
-                            a.logits = b->logits;
-                            a.slots = b->slots;
-                            a.probs = b->score_probs;
-                            a.out = b->score_out;
-                            a.probs_stride = (long long)probs_stride;
-                            a.slot_stride = b->nslots;
-                            a.nslots = (int)p.launches[p.head + 1].grid.x;      // one key per workgroup of the classifier launch
-                            a.n = V;
-                            if (a.nslots < 1 || a.nslots > b->nslots) return fail(Q3_ERR_INTERNAL, "%s: %d argmax slots of %d", who, a.nslots, b->nslots);
-                            if ((rc2 = launch_now(e->stream, k_score_exp, dim3(kScoreExpParts, (unsigned)c.m), dim3(256), 0, a))) return rc2;
-                            if ((rc2 = tm.mark(e->stream))) return rc2;
-                            if ((rc2 = launch_now(e->stream, k_score_sum, dim3((unsigned)c.m), dim3(kSampThreads), 0, a))) return rc2;
-                            if ((rc2 = tm.mark(e->stream))) return rc2;
-                            if (!k) continue;
-                            ScoreTopArgs ta{};
-                            ta.rows = tab;
-                            ta.logits = b->logits;
-                            ta.part_keys = b->score_top_keys;
-                            ta.part_above = b->score_top_above;
-                            ta.top = b->score_top;
-                            ta.rank = rank ? b->score_rank : nullptr;
-                            ta.n = V;
-                            ta.k = k;
-                            ta.parts = parts;
-                            if ((rc2 = launch_now(e->stream, k_score_top_part, dim3((unsigned)parts, (unsigned)c.m), dim3(256), 0, ta))) return rc2;
-                            if ((rc2 = launch_now(e->stream, k_score_top_merge, dim3((unsigned)c.m), dim3(256), 0, ta))) return rc2;
-                            if ((rc2 = tm.mark(e->stream))) return rc2;
+                            const TableRows src{tab, b->score_out, b->score_top, rank ? (int*)b->score_rank : nullptr, k};
+                            if ((rc2 = record_launches(args[wi], src, c.m, [&](bool ends_group, auto kernel, dim3 grid, dim3 blk, const RecordArgs& a, const TableRows& s) {
+                                    const int rc3 = launch_now(e->stream, kernel, grid, blk, 0, a, s);
+                                    return rc3 || !ends_group ? rc3 : tm.mark(e->stream);
+                                })))
+                                return rc2;
                         }
                         return (int)Q3_OK;
                     }, st, true);

@@ -1,13 +1,15 @@
 // q3_score_top.h -- the k best tokens of every scored column and the rank of its target (include/qwen3_hip.h section 2m).
 //
-// The rows are those of q3_score.h: l[0 .. V) of a chunk's m columns in the classifier's output.  The key of entry i is
+// The rows, the arguments and the row sources are those of q3_score.h: l[0 .. V) of the classifier's output, RecordArgs, and a
+// source that names every row's record, target, k and destinations.  The key of entry i is
 //     ((uint64)total_order_key(l[i]) << 32) | i,
 // the key the classifier leaves per workgroup in the argmax slots and spec_col_best folds.  Keys are distinct integers, so the k
 // largest of a row and the number of keys above the target's are the same however the row is cut:
-//   k_score_top_part   grid (parts, m): the k largest keys of one slice of a row, sorted, and the slice's count of keys above the target's;
-//   k_score_top_merge  grid m: one wave takes the k largest of the parts' sorted lists, as {logit, index}, and sums the counts.
-// Only a thread's own loop index, its own counters and the host-checked table entries become addresses: no logit and no key read
-// back from memory does, so a row that holds a NaN is wrong but harmless.
+//   k_score_top_part   grid (parts, rows): the k largest keys of one slice of a row, sorted, and the slice's count of keys above the target's;
+//   k_score_top_merge  grid rows: one wave takes the k largest of the parts' sorted lists, as {logit, index}, and sums the counts.
+// Only a thread's own loop index, its own counters and what the source hands out (host-checked table entries; the pass's out[j] and
+// its committed token clamped to [0, V)) become addresses: no logit and no key read back from memory does, so a row that holds a NaN
+// is wrong but harmless.
 #pragma once
 
 namespace q3 {
@@ -20,18 +22,6 @@ constexpr int kScoreTopE = 10;          // keys a thread of the part kernel hold
 struct ScoreTop {
     float logit;
     int index;
-};
-
-struct ScoreTopArgs {
-    const ScoreRow* rows;               // the chunk's table, m entries
-    const float* logits;                // [kScoreCols][n]
-    unsigned long long* part_keys;      // [kScoreCols][k][parts]: entry j of every slice's largest keys, descending, 0 behind the last
-    int* part_above;                    // [kScoreCols][parts]: keys of the slice above the target's key
-    ScoreTop* top;                      // the call's [records][k]
-    int* rank;                          // the call's [records], or null
-    int n;                              // vocab_size
-    int k;                              // 1 .. kScoreTopMax, <= n
-    int parts;                          // 1 .. kScoreTopParts: gridDim.x of the part kernel
 };
 
 __device__ __forceinline__ unsigned wave_max_u32(unsigned v) {
@@ -51,7 +41,7 @@ __device__ __forceinline__ unsigned long long wave_max_key(unsigned long long ke
     return ((unsigned long long)mh << 32) | ml;
 }
 
-// grid = (parts, m), 256 threads.  Slice p of a row is [p per, min(n, (p + 1) per)), per = ceil(n / parts), walked in tiles of
+// grid = (parts, rows), 256 threads.  Slice p of a row is [p per, min(n, (p + 1) per)), per = ceil(n / parts), walked in tiles of
 // 256 * kScoreTopE entries.  A thread holds the high words of its entries of the tile in registers (entry e of thread t is
 // tile + 256 e + t: the index is never stored) and, from the second tile on, one key of the best so far.  A round takes the
 // workgroup's largest key: every thread keeps the largest it holds, every wave the largest of its threads, and only the wave that
@@ -130,14 +120,16 @@ __device__ __forceinline__ void score_top_slice(const float* l, int n, int k, in
     if (tid < k) keys_out[(size_t)tid * (size_t)parts] = tid < have ? best[tid] : 0ull;
     if (ABOVE && tid == 0) *above_out = (above_lds[0] + above_lds[1]) + (above_lds[2] + above_lds[3]);
 }
-__global__ __launch_bounds__(256) void k_score_top_part(const ScoreTopArgs a) {
-    const size_t row = blockIdx.y;
-    const int part = blockIdx.x;
-    const ScoreRow R = a.rows[row];
-    const float* l = a.logits + row * (size_t)a.n;
-    const unsigned long long tkey = ((unsigned long long)total_order_key(l[R.target]) << 32) | (unsigned)R.target;
-    score_top_slice<true>(l, a.n, a.k, a.parts, part, tkey, a.part_keys + row * (size_t)a.k * (size_t)a.parts + (size_t)part,
-                          a.part_above + row * (size_t)a.parts + (size_t)part);
+template <class Src>
+__global__ __launch_bounds__(256) void k_score_top_part(const RecordArgs a, const Src src) {
+    const int j = blockIdx.y, part = blockIdx.x;
+    const int k = src.k();
+    if (!src.top_live(j, k)) return;
+    const float* l = a.logits + (size_t)j * (size_t)a.n;
+    const int target = src.target(a, j, [&] { return record_best(a, j); });
+    const unsigned long long tkey = ((unsigned long long)total_order_key(l[target]) << 32) | (unsigned)target;
+    score_top_slice<true>(l, a.n, k, a.parts, part, tkey, a.part_keys + (size_t)j * (size_t)k * (size_t)a.parts + (size_t)part,
+                          a.part_above + (size_t)j * (size_t)a.parts + (size_t)part);
 }
 
 // One wave merges the lists of a row as they stand in LDS, entry j of part p at [j * parts + p]: lane p walks the list of part p
@@ -157,30 +149,34 @@ __device__ __forceinline__ unsigned long long score_top_merge_wave(const unsigne
     return mine;
 }
 
-// grid = m, 256 threads.  All copy the row's lists into LDS as they stand, entry j of part p at [j][p]; then wave 0 alone goes on.
+// grid = rows, 256 threads.  All copy the row's lists into LDS as they stand, entry j of part p at [j][p]; then wave 0 alone goes on.
 // Lane p walks the list of part p from its head; a round takes the wave's largest head and the lane that held it steps on (its own
 // counter, below k).  Lane j keeps the j-th winner and stores it as {logit, index}; the rank is the sum of the parts' counts.
-__global__ __launch_bounds__(256) void k_score_top_merge(const ScoreTopArgs a) {
+template <class Src>
+__global__ __launch_bounds__(256) void k_score_top_merge(const RecordArgs a, const Src src) {
     __shared__ unsigned long long lists[kScoreTopMax * kScoreTopParts];
     const int lane = threadIdx.x;
-    const size_t row = blockIdx.x;
-    const int total = a.k * a.parts;
-    const unsigned long long* src = a.part_keys + row * (size_t)total;
+    const int j = blockIdx.x;
+    const int k = src.k();
+    if (!src.top_live(j, k)) return;
+    const int total = k * a.parts;
+    const unsigned long long* keys = a.part_keys + (size_t)j * (size_t)total;
 #pragma unroll 8
-    for (int i = threadIdx.x; i < total; i += 256) lists[i] = src[i];
+    for (int i = threadIdx.x; i < total; i += 256) lists[i] = keys[i];
     __syncthreads();
     if (threadIdx.x >= 64) return;
-    const ScoreRow R = a.rows[row];
-    const unsigned long long mine = score_top_merge_wave(lists, a.k, a.parts, lane);
-    if (lane < a.k) {
+    const int o = src.out(j);
+    const unsigned long long mine = score_top_merge_wave(lists, k, a.parts, lane);
+    if (lane < k) {
         ScoreTop t;
         t.logit = key_to_float((unsigned)(mine >> 32));
         t.index = (int)(unsigned)(mine & 0xffffffffull);
-        a.top[(size_t)R.out * (size_t)a.k + (size_t)lane] = t;
+        src.top()[(size_t)o * (size_t)k + (size_t)lane] = t;
     }
-    if (a.rank) {
-        const int above = group_sum_i32(lane < a.parts ? a.part_above[row * (size_t)a.parts + (size_t)lane] : 0, 64);
-        if (lane == 0) a.rank[R.out] = above;
+    int* const rank = src.rank();
+    if (rank) {
+        const int above = group_sum_i32(lane < a.parts ? a.part_above[(size_t)j * (size_t)a.parts + (size_t)lane] : 0, 64);
+        if (lane == 0) rank[o] = above;
     }
 }
 

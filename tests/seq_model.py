@@ -11,7 +11,7 @@ must return, and checks an engine op by op.
 
 Shape: small-hd128 (dim 512, 8 heads over 4 kv heads, head_dim 128, group 64, vocabulary 2,048) with 576 positions declared instead
 of 256: the score rows of the dense blocks (att_pf) are sized to the context end rounded up to 256, so on 256 positions they are
-allocated once and can never grow.  score_probs of q3_score_many is sized by the vocabulary alone (32 rows of it), so within an engine
+allocated once and can never grow.  record_exps of q3_score_many is sized by the vocabulary alone (32 rows of it), so within an engine
 it is allocated once and can never grow: it is not among BUFFERS."""
 import dataclasses
 import functools

@@ -297,6 +297,52 @@ def test_a_sequence_of_calls_on_one_engine(q3, model):
         gr.assert_same(second, gr.expected(t, some, a[0], 64), a[0], 64, "the second logprobs call")
 
 
+def test_score_top_calls_between_loops_with_records(q3, model):
+    """The exps, the part lists and the part counts are one scratch for the score calls and the loops: greedy loop at 64,
+    score_top_many with k = 5 (and the loop's records read again), sampled loop at 3, score_top_many with k = 64, score_many, greedy
+    loop at 5, all on one engine.  Every result -- tokens, records, tops, ranks -- is, byte for byte, that of the same call made
+    first on a fresh engine."""
+    path, shape, prompts, _ = model
+    some, n_new = prompts[:6], N_NEW[:6]
+    sampler = (TEMPERATURE[:6], TOPP, SEEDS[:6])
+
+    def raw(arrays):
+        return [None if a is None else a.tobytes() for a in arrays]
+
+    def records(t):
+        return [raw(per_request) for per_request in t.read_gen_logprobs()]
+
+    def loop(name, k, smp):
+        def call(t):
+            t.set_gen_logprobs(k)
+            rows = run_loop(t, name, some, n_new, smp)
+            return rows, records(t)
+        return call
+
+    def score(k):
+        def call(t):
+            if k:
+                recs, tops, ranks, _ = t.score_top_many(some, k)
+            else:
+                recs, tops, ranks = t.score_many(some)[0], None, None
+            return [raw(x) for x in (recs, tops or [], ranks or [])]
+        return call
+
+    steps = [("greedy loop at 64", loop("greedy", 64, None)), ("score_top_many, k 5", score(5)), ("sampled loop at 3", loop("sampled", 3, sampler)),
+             ("score_top_many, k 64", score(64)), ("score_many", score(0)), ("greedy loop at 5", loop("greedy", 5, None))]
+    want = []
+    for _, call in steps:
+        with engine(q3, path, slots=4) as t:
+            want.append(call(t))
+    with engine(q3, path, slots=4) as t:
+        for i, ((what, call), w) in enumerate(zip(steps, want)):
+            assert call(t) == w, f"{what}: other bytes than on a fresh engine"
+            if i == 0:
+                first = records(t)
+            if i == 1:
+                assert records(t) == first == want[0][1], "the loop's records behind score_top_many"
+
+
 def test_generate_many_with_logprobs(q3, model):
     """generation.generate_many(logprobs=) over every option combination: the rows of the call without it, the tuples of
     top_logprobs() on prompt + row, the engine's setting put back"""

@@ -181,8 +181,8 @@ def write_md(results, ab, out):
             cond2.append((r["model"], cfg, ok0, ok5))
             md.append(f"| {cfg} | {c['passes']} | {fmt(m['off'])} | {fmt(m['0'])} | {fmt(m['5'])} | {fmt(m['64'])} | {fmt(m['today 0'])} | {fmt(m['today 5'])} | "
                       f"{'yes' if ok0 else 'NO'} | {'yes' if ok5 else 'NO'} |")
-        md += ["", "Per-pass cost of the records, us: ((b) - off) / passes, medians.  The 0 column is k_genlp_exp + k_genlp_sum; 5 - 0 and 64 - 0 are",
-               "k_genlp_top_part + k_genlp_top_merge on top of them.", "", "| configuration | 0 | 5 | 64 | spread of off per pass |", "|---|---|---|---|---|"]
+        md += ["", "Per-pass cost of the records, us: ((b) - off) / passes, medians.  The 0 column is k_score_exp + k_score_sum over the pass's rows;",
+               "5 - 0 and 64 - 0 are k_score_top_part + k_score_top_merge on top of them.", "", "| configuration | 0 | 5 | 64 | spread of off per pass |", "|---|---|---|---|---|"]
         for cfg, c in r["configs"].items():
             m, p = c["ms"], max(1, c["passes"])
             md.append(f"| {cfg} | " + " | ".join(f"{1e3 * (m[k]['median'] - m['off']['median']) / p:+.1f}" for k in ("0", "5", "64")) +
