@@ -94,18 +94,13 @@ struct BatchCtx {
     DevMem<SpecIO> spec_io;      // device: block input and result
     PinMem<SpecIO> h_spec;       // pinned staging of the same
     DevMem<float> spec_snap;     // key / value rows a rejected draft would leave behind, [2][layers][kSpecMax - 1][kv_dim]
-    // ... under the sampler (q3_verify_draw / q3_generate_lookup_draw): allocated by the first sampled pass (spec_draw_alloc)
-    DevMem<SamplerState> spec_samp;      // [kSpecMax] column sampler states
-    DevMem<float> spec_probs, spec_sp;
-    DevMem<unsigned long long> spec_keys;
-    SampleArgs spec_sargs{};
+    // ... under the sampler (q3_verify_draw / q3_generate_lookup_draw, and the sampled column passes): the draw site of kSpecMax
+    // columns, allocated by the first sampled pass (spec_draw_alloc); draw_cols.ss are the column sampler states
+    DrawSite draw_cols;
     bool has_kv = false;         // per-stream KV caches allocated (q3_batch_init); prefill-only contexts have none
     // per-stream device samplers (q3_batch_sampler_set)
     bool sampling = false;
-    DevMem<SamplerState> d_sampler;
-    DevMem<float> d_probs, d_sp;
-    DevMem<unsigned long long> d_keys;
-    SampleArgs sargs{};
+    DrawSite draw_decode;        // max_streams columns, allocated by the first q3_batch_sampler_set; draw_decode.ss: slot i = stream i
     size_t kv_stream = 0;        // floats per stream in key / value
     // column passes (q3_batch_step_cols / q3_generate_many_greedy)
     DevMem<int> col_slot;        // device [kColsMax]: KV slot of every column of the pass in flight
@@ -119,11 +114,11 @@ struct BatchCtx {
     DevMem<int> cols_ncols;
     DevMem<int32_t> cols_prompts, cols_out;
     // ... under the sampler (q3_batch_step_cols_draw / q3_generate_many_sampled): allocated by the first sampled pass (cols_draw_alloc),
-    // the column sampler states and the draw scratch are those of spec_draw_alloc
+    // the column sampler states and the draw scratch are draw_cols'
     DevMem<ColsDraw> cols_draw;                         // device
     PinMem<ColsDrawHost> h_cols_draw;
     DevMem<ColsStep> cols_step;                         // device
-    DevMem<SamplerState> cols_slot_samp;                // [kMaxStreams] the loop's per-slot states (a single pass uses d_sampler)
+    DevMem<SamplerState> cols_slot_samp;                // [kMaxStreams] the loop's per-slot states (a single pass uses draw_decode.ss)
     DevMem<ColAux> cols_aux;                            // the loop's table of ColAux and per-request sampler parameters: grow-only
     DevMem<float> cols_temp, cols_topp;
     DevMem<unsigned long long> cols_seeds;
@@ -415,7 +410,7 @@ int q3_prefill_batched(q3_engine* e, const int32_t* tokens, size_t n_tokens, siz
     HIP_TRY(hipGetLastError());
     if (e->sampling) {
         // the reference draws one (discarded) sample per prompt position: n_tokens - 1 coins, then the real draw
-        if (n_tokens > 1) hipLaunchKernelGGL(k_rng_skip, dim3(1), dim3(1), 0, e->stream, e->d_sampler, (int)(n_tokens - 1));
+        if (n_tokens > 1) hipLaunchKernelGGL(k_rng_skip, dim3(1), dim3(1), 0, e->stream, e->draw.ss, (int)(n_tokens - 1));
         if ((rc = e->enqueue_sample())) return rc;
     }
     HIP_TRY(hipMemcpyAsync(e->h_tokens, e->d_out_tokens, 4, hipMemcpyDeviceToHost, e->stream));
@@ -472,37 +467,13 @@ int q3_batch_sampler_set(q3_engine* e, float temperature, float topp, const uint
     BatchCtx* b = e->batch;
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(hipStreamSynchronize(e->stream));
-    const int n = e->cfg.vocab_size, B = b->max_streams;
-    const int blen = 4 * ((n + 4095) / 4096);
-    size_t n2 = 1;
-    while (n2 < (size_t)n) n2 <<= 1;
-    const size_t scratch = (size_t)kSampThreads * blen;
-    if (!b->d_sampler) {          // one group, committed whole (q3_sampler_set)
-        DevMem<SamplerState> ss; DevMem<float> probs, sp; DevMem<unsigned long long> keys;
-        int rc;
-        if ((rc = ss.alloc(B)) || (rc = probs.alloc(scratch * B)) || (rc = sp.alloc(scratch * B)) || (rc = keys.alloc(2 * n2 * B))) return rc;
-        b->d_sampler = std::move(ss); b->d_probs = std::move(probs); b->d_sp = std::move(sp); b->d_keys = std::move(keys);
-    }
+    const int B = b->max_streams;
+    int rc;
+    if (!b->draw_decode && (rc = b->draw_decode.alloc(e->cfg.vocab_size, B, false))) return rc;
     std::vector<SamplerState> h(B);
     for (int i = 0; i < B; ++i) h[i] = SamplerState{rng_seeds ? rng_seeds[i] : 0ull, temperature, topp, {0, 0, 0, 0}};
-    HIP_TRY(hipMemcpy(b->d_sampler, h.data(), sizeof(SamplerState) * B, hipMemcpyHostToDevice));
-    SampleArgs a{};
-    a.logits = b->logits;
-    a.n = n;
-    a.blen = blen;
-    a.probs = b->d_probs;
-    a.keys = b->d_keys;
-    a.sp = b->d_sp;
-    a.ss = b->d_sampler;
-    a.st = b->st;
-    a.out_tokens = b->out_tokens;
-    a.out_cap = b->out_cap;
-    a.sb_logits = n;
-    a.sb_scratch = (long long)scratch;
-    a.sb_keys = 2 * (long long)n2;
-    a.keys2_off = (long long)n2;
-    a.pre_exp = dev_knob("Q3_SAMPLER_PRE_EXP", 1);
-    b->sargs = a;
+    HIP_TRY(hipMemcpy(b->draw_decode.ss, h.data(), sizeof(SamplerState) * B, hipMemcpyHostToDevice));
+    draw_args(b->draw_decode, DrawForm::Decode, b->logits, b->st, b->out_tokens, b->out_cap);
     const bool on = temperature != 0.0f;
     plans_drop(b, PlanDrop::Step);                        // the step's launches carry these arguments: re-plan on the next call
     b->sampling = on;
@@ -545,41 +516,18 @@ int q3_batch_read_state(q3_engine* e, int stream, int kind, size_t offset, size_
 
 namespace {
 
-// Column sampler states and the draw scratch of up to kSpecMax columns (probs / sp / keys: ~5.3 MB per column at a 151,936-entry
-// vocabulary), allocated by the first pass that samples -- greedy users of the context never pay for it -- and freed with it.
+// The column site: sampler states and the draw scratch of up to kSpecMax columns (probs / sp / keys: ~5.3 MB per column at a
+// 151,936-entry vocabulary), allocated by the first pass that samples -- greedy users of the context never pay for it -- and freed
+// with it.  Its states are cleared on the stream before the context sees any of it.
 int spec_draw_alloc(q3_engine* e) {
     BatchCtx* b = e->batch;
     HIP_TRY(hipSetDevice(e->device));
-    const int n = e->cfg.vocab_size;
-    const int blen = 4 * ((n + 4095) / 4096);
-    size_t n2 = 1;
-    while (n2 < (size_t)n) n2 <<= 1;
-    const size_t scratch = (size_t)kSampThreads * blen;
-    // one group, committed whole (q3_sampler_set): the callers take spec_samp for all four
-    DevMem<SamplerState> samp; DevMem<float> probs, sp; DevMem<unsigned long long> keys;
-    int rc;
-    if ((rc = samp.alloc(kSpecMax)) || (rc = probs.alloc(scratch * kSpecMax)) || (rc = sp.alloc(scratch * kSpecMax)) ||
-        (rc = keys.alloc(2 * n2 * kSpecMax)))
-        return rc;
-    HIP_TRY(hipMemsetAsync(samp, 0, sizeof(SamplerState) * kSpecMax, e->stream));
-    b->spec_samp = std::move(samp); b->spec_probs = std::move(probs); b->spec_sp = std::move(sp); b->spec_keys = std::move(keys);
-    SampleArgs a{};
-    a.logits = b->logits;
-    a.n = n;
-    a.blen = blen;
-    a.probs = b->spec_probs;
-    a.keys = b->spec_keys;
-    a.sp = b->spec_sp;
-    a.ss = b->spec_samp;
-    a.st = b->st;
-    a.out_tokens = e->d_out_tokens;      // never written: a column's State::step stays 0, and out_cap 0 closes the window
-    a.out_cap = 0;
-    a.sb_logits = n;
-    a.sb_scratch = (long long)scratch;
-    a.sb_keys = 2 * (long long)n2;
-    a.keys2_off = (long long)n2;
-    a.pre_exp = 1;
-    b->spec_sargs = a;
+    DrawSite site;
+    if (int rc = site.alloc(e->cfg.vocab_size, kSpecMax, false)) return rc;
+    HIP_TRY(hipMemsetAsync(site.ss, 0, sizeof(SamplerState) * kSpecMax, e->stream));
+    // out_tokens is never written: a column's State::step stays 0, and out_cap 0 closes the window
+    draw_args(site, DrawForm::Columns, b->logits, b->st, e->d_out_tokens, 0);
+    b->draw_cols = std::move(site);
     return Q3_OK;
 }
 
@@ -593,7 +541,7 @@ int spec_prepare(q3_engine* e, const char* who, bool draw = false) {
         return fail(Q3_ERR_UNSUPPORTED, "%s is greedy only: the engine's sampler is set to a temperature > 0 (speculative sampling is not implemented)", who);
     int rc;
     if (!e->batch && (rc = batch_alloc(e, kMaxStreams, 0, false, prefill_block_cap(e)))) return rc;
-    if (e->sampling && !e->batch->spec_samp && (rc = spec_draw_alloc(e))) return rc;
+    if (e->sampling && !e->batch->draw_cols && (rc = spec_draw_alloc(e))) return rc;
     return Q3_OK;
 }
 

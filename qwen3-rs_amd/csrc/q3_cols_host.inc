@@ -222,10 +222,10 @@ void genlp_call_enter(q3_engine* e) {
 int cols_draw_alloc(q3_engine* e) {
     BatchCtx* b = e->batch;
     int rc;
-    if (!b->spec_samp && (rc = spec_draw_alloc(e))) return rc;
+    if (!b->draw_cols && (rc = spec_draw_alloc(e))) return rc;
     if (b->h_cols_draw) return Q3_OK;
     HIP_TRY(hipSetDevice(e->device));
-    // one group, committed whole (q3_sampler_set)
+    // one group, committed whole (DrawSite::alloc)
     DevMem<ColsDraw> draw; DevMem<ColsStep> step; DevMem<SamplerState> slot_samp; PinMem<ColsDrawHost> h_draw;
     if ((rc = draw.alloc(1)) || (rc = step.alloc(1)) || (rc = slot_samp.alloc(kMaxStreams)) || (rc = h_draw.alloc(1))) return rc;
     HIP_TRY(hipMemsetAsync(draw, 0, sizeof(ColsDraw), e->stream));
@@ -263,13 +263,13 @@ int cols_sampler_upload(q3_engine* e, SamplerState* slot_ss, const ColAux* aux, 
 // of one row.  Every later pass of a table is set up by the turn kernel that ends the pass before it.
 int cols_turn_setup(q3_engine* e, bool draw) {
     BatchCtx* b = e->batch;
-    if (draw) return launch_now(e->stream, k_cols_turn_draw, dim3(1), dim3(kWG), 0, b->cols_ctl, b->cols_draw, b->spec_samp, b->st, b->col_slot);
+    if (draw) return launch_now(e->stream, k_cols_turn_draw, dim3(1), dim3(kWG), 0, b->cols_ctl, b->cols_draw, b->draw_cols.ss, b->st, b->col_slot);
     return launch_now(e->stream, k_cols_turn, dim3(1), dim3(kWG), 0, b->cols_ctl, b->slots, b->nslots, 0, b->st, b->col_slot);
 }
 
 // One host-made pass.  draw = false: the states and the slot table are written here and the greedy plan commits the argmaxes.
 // draw = true: the pass goes through a one-pass table, set up by a k_cols_turn_draw launch in front of the sampled plan -- the
-// column sampler states derive from the slot states in device memory (the batch sampler's d_sampler: slot i = stream i).
+// column sampler states derive from the slot states in device memory (the batch sampler's draw_decode.ss: slot i = stream i).
 int cols_step(q3_engine* e, const int32_t* slots, const int32_t* tokens, const int32_t* pos, int n_cols, const uint8_t* keep, float* logits_out,
               int32_t* next_out, bool draw) {
     int rc;
@@ -303,7 +303,7 @@ int cols_step(q3_engine* e, const int32_t* slots, const int32_t* tokens, const i
         h->ctl.ncols = &b->cols_step->ncols;
         h->ctl.prompts = b->cols_step->tokens;
         memset(&hd->dr, 0, sizeof(ColsDraw));
-        hd->dr.slot_ss = b->d_sampler;
+        hd->dr.slot_ss = b->draw_decode.ss;
         hd->dr.aux = b->cols_step->aux;
         hd->step.ncols = n_cols;
         for (int j = 0; j < kColsMax; ++j) {
@@ -659,7 +659,7 @@ int q3_batch_prefill_slots(q3_engine* e, const int32_t* slots, const int32_t* to
     ColsJob job;
     q3_dense_stats dst{0, 0, 0};
     dense_job_add(e, job, in, draw, nullptr, nullptr, nullptr, dst);
-    const ColsJobSampler smp{b->d_sampler, nullptr, nullptr, nullptr, 0, true};
+    const ColsJobSampler smp{b->draw_decode.ss, nullptr, nullptr, nullptr, 0, true};
     if ((rc = cols_job_run(e, job, draw, smp, tokens, n_tok, nullptr, 0))) return rc;
     if (stats) *stats = dst;
     return Q3_OK;

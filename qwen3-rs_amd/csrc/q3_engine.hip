@@ -288,8 +288,7 @@ int env_int(const char* name, int dflt) {
 
 // slices per column of the top-k selection (k_topk_part's gridDim.x): one list per lane of the draw's merge.  A slice of the
 // 151,936-entry vocabulary is then 2,374 entries, one tile of the part kernel (Q3_TOPK_PARTS, developer build: another split, the same draws)
-int topk_parts(int n) {
-    (void)n;
+int topk_parts() {
     const int p = dev_knob("Q3_TOPK_PARTS", kScoreTopParts);
     return p < 1 ? 1 : (p > kScoreTopParts ? kScoreTopParts : p);
 }
@@ -298,6 +297,7 @@ int topk_parts(int n) {
 }  // namespace
 
 #include "q3_mem.h"
+#include "q3_draw_host.inc"
 
 struct BatchCtx;
 struct q3_engine;
@@ -354,23 +354,18 @@ struct q3_engine {
                dev_knob("Q3_VALUE_T", 1) != 0;
     }
     BatchCtx* batch = nullptr;                 // batched decode state (q3_batch_init), see q3_batch_host.inc
-    // device-side Sampler (q3_sampler_set): temperature > 0 makes every token draw go through k_sample
+    // device-side Sampler (q3_sampler_set): temperature > 0 makes every token draw go through the draw site's launches
     bool sampling = false;
-    DevMem<SamplerState> d_sampler;
-    DevMem<float> d_samp_hist;           // pipelined draw: mass histogram, per-workgroup candidate counts
-    DevMem<int> d_samp_counts;
-    DevMem<float> d_probs, d_sp;
-    DevMem<unsigned long long> d_keys;
-    size_t keys_n2 = 0;
-    std::vector<Launch> sample_plan;     // the draw behind a forward (q3_sampler_set)
+    DrawSite draw;                       // one column, with the pipelined draw's hist / counts: allocated by the first q3_sampler_set
+    std::vector<Launch> sample_plan;     // the draw behind a forward (build_sample_plans)
     // top-k sampling (q3_sampler_top_k, section 2n): engine-wide, 0 = off.  The value also stands in device memory, where every
     // top-k pass reads it; the slices' lists hold the columns of the widest pass (kSpecMax).  Allocated by the first k > 0.
     int top_k = 0;
     DevMem<int> d_top_k;
     DevMem<unsigned long long> d_topk_keys;
-    std::vector<Launch> sample_plan_topk;    // the second form of sample_plan: k_topk_part, k_topk_draw
-    TopkArgs topk_args(const SampleArgs& s) const;
-    int build_sample_plan_topk();
+    std::vector<Launch> sample_plan_topk;    // the second form of sample_plan: the top-k launches, once both exist
+    TopkArgs topk_args(const SampleArgs& s) const { return ::topk_args(s, d_top_k, d_topk_keys); }
+    int build_sample_plans();
     // log-probabilities of generated tokens (q3_gen_logprobs, section 2o): engine-wide, -1 = off; 0: a record per token the
     // q3_generate_many_* loops produce; 1 .. kScoreTopMax: also that many best tokens and the rank.  What it needs on the device
     // belongs to the batched state (genlp_alloc, q3_cols_host.inc)
@@ -959,41 +954,24 @@ int q3_engine::enqueue_sample() {
     return Q3_OK;
 }
 
-// the top-k launches' view of a draw site: its logits, states and outputs are the site's SampleArgs', the lists are the engine's
-TopkArgs q3_engine::topk_args(const SampleArgs& s) const {
-    TopkArgs t{};
-    t.logits = s.logits;
-    t.sb_logits = s.sb_logits;
-    t.n = s.n;
-    t.parts = topk_parts(s.n);
-    t.k = d_top_k;
-    t.part_keys = d_topk_keys;
-    t.ss = s.ss;
-    t.st = s.st;
-    t.out_tokens = s.out_tokens;
-    t.out_cap = s.out_cap;
-    return t;
-}
-
-// sample_plan's second form, once the sampler state and the top-k buffers both exist (q3_sampler_set / q3_sampler_top_k, in either order)
-int q3_engine::build_sample_plan_topk() {
+// sample_plan and, once the top-k lists exist too, its second form, from the site's arguments as the last q3_sampler_set left
+// them (q3_sampler_set / q3_sampler_top_k, in either order)
+int q3_engine::build_sample_plans() {
+    sample_plan.clear();
     sample_plan_topk.clear();
-    if (!d_sampler || !d_top_k) return Q3_OK;
-    SampleArgs s{};
-    s.logits = d_logits;
-    s.n = cfg.vocab_size;
-    s.ss = d_sampler;
-    s.st = d_state;
-    s.out_tokens = d_out_tokens;
-    s.out_cap = out_cap;
-    const TopkArgs t = topk_args(s);
-    Launch part, draw;
-    int rc;
-    if ((rc = make_launch(part, F_NEXT, k_topk_part, dim3((unsigned)t.parts, 1), dim3(256), 0, t)) ||
-        (rc = make_launch(draw, F_NEXT, k_topk_draw, dim3(1), dim3(64), 0, t)))
-        return rc;
-    sample_plan_topk = {part, draw};
-    return Q3_OK;
+    if (!draw) return Q3_OK;
+    const auto into = [](std::vector<Launch>& plan) {
+        return [&plan](auto kernel, dim3 grid, dim3 block, size_t smem, const auto& a) {
+            Launch L;
+            const int rc = make_launch(L, F_NEXT, kernel, grid, block, smem, a);
+            if (rc == Q3_OK) plan.push_back(L);
+            return rc;
+        };
+    };
+    if (int rc = draw_launches(draw, 1, (unsigned)n_cu, nullptr, into(sample_plan))) return rc;
+    if (!d_top_k) return Q3_OK;
+    const TopkArgs t = topk_args(draw.args);
+    return draw_launches(draw, 1, (unsigned)n_cu, &t, into(sample_plan_topk));
 }
 
 int q3_engine::set_state(size_t token, size_t pos) {
@@ -1235,61 +1213,14 @@ int q3_sampler_set(q3_engine* e, float temperature, float topp, uint64_t rng_see
     if (int rc = sampler_check(temperature, topp)) return rc;
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(hipStreamSynchronize(e->stream));
-    const int n = e->cfg.vocab_size;
-    const int blen = 4 * ((n + 4095) / 4096);
-    if (!e->d_sampler) {
-        size_t n2 = 1;
-        while (n2 < (size_t)n) n2 <<= 1;
-        // one group, committed whole: a failed allocation leaves the engine with none of it, and the next call starts over
-        DevMem<SamplerState> ss; DevMem<float> probs, sp, hist; DevMem<unsigned long long> keys; DevMem<int> counts;
-        int rc;
-        if ((rc = ss.alloc(1)) || (rc = probs.alloc((size_t)kSampThreads * blen)) || (rc = sp.alloc((size_t)kSampThreads * blen)) ||
-            (rc = keys.alloc(2 * n2)) || (rc = hist.alloc(kSampHistBins)) || (rc = counts.alloc(kSampGrid)))
-            return rc;
-        e->d_sampler = std::move(ss); e->d_probs = std::move(probs); e->d_sp = std::move(sp);
-        e->d_keys = std::move(keys); e->d_samp_hist = std::move(hist); e->d_samp_counts = std::move(counts);
-        e->keys_n2 = n2;
-    }
+    int rc;
+    if (!e->draw && (rc = e->draw.alloc(e->cfg.vocab_size, 1, true))) return rc;
     SamplerState h{};
     h.rng = rng_seed; h.temperature = temperature; h.topp = topp;
-    HIP_TRY(hipMemcpy(e->d_sampler, &h, sizeof(h), hipMemcpyHostToDevice));
-    SampleArgs a{};
-    a.logits = e->d_logits;
-    a.n = n;
-    a.blen = blen;
-    a.probs = e->d_probs;
-    a.keys = e->d_keys;
-    a.keys2_off = (long long)e->keys_n2;
-    a.sp = e->d_sp;
-    a.ss = e->d_sampler;
-    a.st = e->d_state;
-    a.out_tokens = e->d_out_tokens;
-    a.out_cap = e->out_cap;
-    a.pre_exp = dev_knob("Q3_SAMPLER_PRE_EXP", 1);
-    a.phase = (a.pre_exp && dev_knob("Q3_SAMPLER_PIPELINE", 1)) ? 1 : 0;
-    a.hist = e->d_samp_hist;
-    a.counts = e->d_samp_counts;
-    a.stamps = e->d_stamps ? e->d_stamps + 16 * (size_t)(5 * e->cfg.n_layers + 3) : nullptr;
-    // the draw behind every forward.  Pipelined (phase 1): the single-workgroup kernel keeps the order-sensitive parts (exact sum;
-    // sort + exact walks), the element-wise passes over the vocabulary in between run on the whole chip
-    e->sample_plan.clear();
-    int rc = Q3_OK;
-    auto add = [&](void (*k)(const SampleArgs), dim3 grid, dim3 block, size_t smem, const SampleArgs& sa) {
-        Launch L;
-        if (rc == Q3_OK && (rc = make_launch(L, F_NEXT, k, grid, block, smem, sa)) == Q3_OK) e->sample_plan.push_back(L);
-    };
-    if (a.pre_exp) add(k_sample_exp, dim3((unsigned)e->n_cu, 1), dim3(256), 0, a);
-    add(k_sample, dim3(1), dim3(kSampThreads), 4 * kSegFloats, a);
-    if (a.phase == 1) {
-        SampleArgs tail = a;
-        tail.phase = 2;
-        add(k_sample_norm_hist, dim3(kSampGrid), dim3(256), 0, a);
-        add(k_sample_count, dim3(kSampGrid), dim3(256), 0, a);
-        add(k_sample_scatter, dim3(kSampGrid), dim3(256), 0, a);
-        add(k_sample, dim3(1), dim3(kSampThreads), 4 * kSegFloats, tail);
-    }
-    if (rc) return rc;
-    if ((rc = e->build_sample_plan_topk())) return rc;
+    HIP_TRY(hipMemcpy(e->draw.ss, &h, sizeof(h), hipMemcpyHostToDevice));
+    draw_args(e->draw, DrawForm::Engine, e->d_logits, e->d_state, e->d_out_tokens, e->out_cap,
+              e->d_stamps ? e->d_stamps + 16 * (size_t)(5 * e->cfg.n_layers + 3) : nullptr);
+    if ((rc = e->build_sample_plans())) return rc;
     e->sampling = temperature != 0.0f;                       // sampler.rs:119-120: temperature 0 is the argmax path
     return Q3_OK;
 }
@@ -1302,12 +1233,12 @@ int q3_sampler_top_k(q3_engine* e, int top_k) {
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(hipStreamSynchronize(e->stream));
     if (top_k > 0 && !e->d_top_k) {
-        // one group, committed whole (q3_sampler_set)
+        // one group, committed whole (DrawSite::alloc)
         DevMem<int> k; DevMem<unsigned long long> keys;
         int rc;
         if ((rc = k.alloc(1)) || (rc = keys.alloc((size_t)kSpecMax * kTopkColKeys))) return rc;
         e->d_top_k = std::move(k); e->d_topk_keys = std::move(keys);
-        if ((rc = e->build_sample_plan_topk())) return rc;
+        if ((rc = e->build_sample_plans())) return rc;
     }
     // 0 is never read: the plans without top-k run.  Two non-zero values share every plan and graph
     if (top_k > 0) HIP_TRY(hipMemcpy(e->d_top_k, &top_k, sizeof(int), hipMemcpyHostToDevice));
@@ -1324,11 +1255,11 @@ int q3_sampler_get_top_k(const q3_engine* e, int* top_k) {
 
 int q3_sampler_get_rng(q3_engine* e, uint64_t* rng_state) {
     g_err[0] = 0;
-    if (!e || !rng_state || !e->d_sampler) return fail(Q3_ERR_ARG, "q3_sampler_set has not been called");
+    if (!e || !rng_state || !e->draw) return fail(Q3_ERR_ARG, "q3_sampler_set has not been called");
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(hipStreamSynchronize(e->stream));
     SamplerState h;
-    HIP_TRY(hipMemcpy(&h, e->d_sampler, sizeof(h), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&h, e->draw.ss, sizeof(h), hipMemcpyDeviceToHost));
     *rng_state = h.rng;
     return Q3_OK;
 }
@@ -1556,6 +1487,41 @@ int op_end() {
     return Q3_OK;
 }
 bool group_ok(size_t G) { return G >= 16 && G <= 1024 && (G & (G - 1)) == 0; }
+
+// what q3_op_sample and q3_op_sample_top_k check alike, in front of the top-k entry point's own checks
+int op_draw_check(const float* logits, size_t n, float temperature, float topp, const uint64_t* rng_state, const int32_t* index, int device) {
+    int rc = op_begin(device);
+    if (rc) return rc;
+    if (!logits || !rng_state || !index || n == 0) return fail(Q3_ERR_ARG, "null argument");
+    if (!(temperature > 0.0f)) return fail(Q3_ERR_ARG, "temperature must be positive (0 is q3_op_argmax)");
+    return sampler_check(temperature, topp);
+}
+// The body of q3_op_sample (top_k == 0) and of q3_op_sample_top_k (1 <= top_k <= kTopkMax, the caller's check): one draw of a
+// temporary one-column site over the caller's logits.  The top-k launches read none of the site's scratch, so only its state is made.
+int op_draw(const float* logits, size_t n, float temperature, float topp, int top_k, uint64_t* rng_state, int32_t* index) {
+    int rc;
+    DrawSite site;
+    OpBuf dl, dk, dkeys, dst, dout;
+    SamplerState h{*rng_state, temperature, topp, {0, 0, 0, 0}};
+    State st{};
+    st.step = 1;                                            // "one forward done": the draw is stored in out_tokens[0]
+    site.n = (int)n;
+    if ((rc = dl.upload(logits, 4 * n)) || (rc = top_k ? site.ss.alloc(1) : site.alloc((int)n, 1, false)) ||
+        (top_k && ((rc = dk.upload(&top_k, sizeof(int))) || (rc = dkeys.alloc(8 * (size_t)kTopkColKeys)))) ||
+        (rc = dst.upload(&st, sizeof(st))) || (rc = dout.alloc(16)))
+        return rc;
+    HIP_TRY(hipMemcpy(site.ss, &h, sizeof(h), hipMemcpyHostToDevice));
+    draw_args(site, DrawForm::Operator, dl.as<float>(), dst.as<State>(), dout.as<int32_t>(), 4);
+    const TopkArgs t = topk_args(site.args, dk.as<int>(), dkeys.as<unsigned long long>());
+    rc = draw_launches(site, 1, 0, top_k ? &t : nullptr, [](auto kernel, dim3 grid, dim3 block, size_t smem, const auto& a) {
+        return launch_now(0, kernel, grid, block, smem, a);
+    });
+    if (rc || (rc = op_end())) return rc;
+    HIP_TRY(hipMemcpy(&h, site.ss, sizeof(h), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(index, dout.p, 4, hipMemcpyDeviceToHost));
+    *rng_state = h.rng;
+    return Q3_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -1919,74 +1885,16 @@ int q3_dev_bench_gemv(size_t n, size_t d, size_t group_size, int wg_per_cu, int 
 #endif  // Q3_DEV
 
 int q3_op_sample(const float* logits, size_t n, float temperature, float topp, uint64_t* rng_state, int32_t* index, int device) {
-    int rc = op_begin(device);
-    if (rc) return rc;
-    if (!logits || !rng_state || !index || n == 0) return fail(Q3_ERR_ARG, "null argument");
-    if (!(temperature > 0.0f)) return fail(Q3_ERR_ARG, "temperature must be positive (0 is q3_op_argmax)");
-    if ((rc = sampler_check(temperature, topp))) return rc;
-    const int blen = 4 * (((int)n + 4095) / 4096);
-    size_t n2 = 1;
-    while (n2 < n) n2 <<= 1;
-    OpBuf dl, dp, ds, dk, dss, dst, dout;
-    SamplerState h{*rng_state, temperature, topp, {0, 0, 0, 0}};
-    State st{};
-    st.step = 1;                                            // "one forward done": the draw is stored in out_tokens[0]
-    if ((rc = dl.upload(logits, 4 * n)) || (rc = dp.alloc(4 * (size_t)kSampThreads * blen)) ||
-        (rc = ds.alloc(4 * (size_t)kSampThreads * blen)) || (rc = dk.alloc(2 * 8 * n2)) || (rc = dss.upload(&h, sizeof(h))) ||
-        (rc = dst.upload(&st, sizeof(st))) || (rc = dout.alloc(16)))
-        return rc;
-    SampleArgs a{};
-    a.logits = dl.as<float>();
-    a.n = (int)n;
-    a.blen = blen;
-    a.probs = dp.as<float>();
-    a.sp = ds.as<float>();
-    a.keys = dk.as<unsigned long long>();
-    a.keys2_off = (long long)n2;
-    a.ss = dss.as<SamplerState>();
-    a.st = dst.as<State>();
-    a.out_tokens = dout.as<int32_t>();
-    a.out_cap = 4;
-    if ((rc = launch_now(0, k_sample, dim3(1), dim3(kSampThreads), 4 * kSegFloats, a)) || (rc = op_end())) return rc;
-    HIP_TRY(hipMemcpy(&h, dss.p, sizeof(h), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(index, dout.p, 4, hipMemcpyDeviceToHost));
-    *rng_state = h.rng;
-    return Q3_OK;
+    if (int rc = op_draw_check(logits, n, temperature, topp, rng_state, index, device)) return rc;
+    return op_draw(logits, n, temperature, topp, 0, rng_state, index);
 }
 
 int q3_op_sample_top_k(const float* logits, size_t n, float temperature, float topp, int top_k, uint64_t* rng_state, int32_t* index, int device) {
-    int rc = op_begin(device);
-    if (rc) return rc;
-    if (!logits || !rng_state || !index || n == 0) return fail(Q3_ERR_ARG, "null argument");
-    if (!(temperature > 0.0f)) return fail(Q3_ERR_ARG, "temperature must be positive (0 is q3_op_argmax)");
-    if ((rc = sampler_check(temperature, topp))) return rc;
+    if (int rc = op_draw_check(logits, n, temperature, topp, rng_state, index, device)) return rc;
     if (n > (size_t)INT32_MAX) return fail(Q3_ERR_ARG, "more than 2^31 logits");
     if (top_k < 1 || top_k > kTopkMax || (size_t)top_k > n)
         return fail(Q3_ERR_ARG, "top_k %d out of range (1..%d, at most n %zu)", top_k, kTopkMax, n);
-    OpBuf dl, dk, dkeys, dss, dst, dout;
-    SamplerState h{*rng_state, temperature, topp, {0, 0, 0, 0}};
-    State st{};
-    st.step = 1;                                            // "one forward done": the draw is stored in out_tokens[0]
-    if ((rc = dl.upload(logits, 4 * n)) || (rc = dk.upload(&top_k, sizeof(int))) || (rc = dkeys.alloc(8 * (size_t)kTopkColKeys)) ||
-        (rc = dss.upload(&h, sizeof(h))) || (rc = dst.upload(&st, sizeof(st))) || (rc = dout.alloc(16)))
-        return rc;
-    TopkArgs a{};
-    a.logits = dl.as<float>();
-    a.n = (int)n;
-    a.parts = topk_parts((int)n);
-    a.k = dk.as<int>();
-    a.part_keys = dkeys.as<unsigned long long>();
-    a.ss = dss.as<SamplerState>();
-    a.st = dst.as<State>();
-    a.out_tokens = dout.as<int32_t>();
-    a.out_cap = 4;
-    if ((rc = launch_now(0, k_topk_part, dim3((unsigned)a.parts, 1), dim3(256), 0, a)) ||
-        (rc = launch_now(0, k_topk_draw, dim3(1), dim3(64), 0, a)) || (rc = op_end()))
-        return rc;
-    HIP_TRY(hipMemcpy(&h, dss.p, sizeof(h), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(index, dout.p, 4, hipMemcpyDeviceToHost));
-    *rng_state = h.rng;
-    return Q3_OK;
+    return op_draw(logits, n, temperature, topp, top_k, rng_state, index);
 }
 
 int q3_op_argmax(const float* logits, size_t n, int32_t* index, int device) {

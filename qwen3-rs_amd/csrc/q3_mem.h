@@ -5,7 +5,7 @@
 // of pointers is kept anywhere.  Both convert to T*, so kernel-argument structs, make_launch, hipMemcpyAsync, pointer arithmetic
 // and `if (!buf)` take them as they took the raw pointer.
 // An allocation group -- buffers of which a later call takes all for granted once it sees the first -- is allocated into locals
-// and moved into its owner together (q3_sampler_set): after a failure the owner holds none of it and the next call starts over.
+// and moved into its owner together (DrawSite::alloc, q3_draw_host.inc): after a failure the owner holds none of it and the next call starts over.
 // The allocator is a compile-time policy {allocate, release; for DevMem::grow also Stream, wait}, each returning 0 or a Q3 status.
 // The library names the HIP defaults only; tests/mem_host.cpp defines Q3_MEM_NO_HIP and exercises the types over a counting one.
 #pragma once

@@ -439,17 +439,15 @@ struct PlanBuilder {
     // behind the element-wise passes spread over the chip), behind the per-column maximum they read.  Columns that do not draw
     // (interior prompt positions, pads, temperature-0 slots of a column pass) return at once in both sampler launches
     int draw_columns() {
-        int rc;
-        if ((rc = add(F_NEXT, k_spec_colmax, dim3(1), dim3(kWG), 0, b->st, b->slots, b->nslots, nslots_used, n))) return rc;
-        if (key.topk) return draw_topk(b->spec_sargs);
-        if ((rc = add(F_NEXT, k_sample_exp, dim3(64, (unsigned)n), dim3(256), 0, b->spec_sargs))) return rc;
-        return add(F_NEXT, k_sample, dim3((unsigned)n), dim3(kSampThreads), 4 * kSegFloats, b->spec_sargs);
+        if (int rc = add(F_NEXT, k_spec_colmax, dim3(1), dim3(kWG), 0, b->st, b->slots, b->nslots, nslots_used, n)) return rc;
+        return draw(b->draw_cols);
     }
-    // the top-k form of a site's draws (q3_topk.h): the selection over the slices of every column, then one wave per column
-    int draw_topk(const SampleArgs& s) {
-        const TopkArgs t = e->topk_args(s);
-        if (int rc = add(F_NEXT, k_topk_part, dim3((unsigned)t.parts, (unsigned)n), dim3(256), 0, t)) return rc;
-        return add(F_NEXT, k_topk_draw, dim3((unsigned)n), dim3(64), 0, t);
+    // the draws of a site's first n columns, plain or top-k as the key says (draw_launches)
+    int draw(const DrawSite& site) {
+        const TopkArgs t = e->topk_args(site.args);
+        return draw_launches(site, n, kDrawExpParts, key.topk ? &t : nullptr, [&](auto kernel, dim3 grid, dim3 blk, size_t smem, const auto& a) {
+            return add(F_NEXT, kernel, grid, blk, smem, a);
+        });
     }
 
     // the records of the columns the turn kernel is about to commit (PassRows, q3_genlp.h; genlp_alloc has run, and plan_get has
@@ -472,7 +470,7 @@ struct PlanBuilder {
             // k_spec_sampler_states set up
             if (key.draw) {
                 if ((rc = draw_columns())) return rc;
-                rc = add(F_NEXT, k_spec_commit_draw, dim3(1), dim3(64), 0, b->spec_io, b->st, b->spec_samp, e->d_state, e->d_sampler, e->d_out_tokens, e->out_cap);
+                rc = add(F_NEXT, k_spec_commit_draw, dim3(1), dim3(64), 0, b->spec_io, b->st, b->draw_cols.ss, e->d_state, e->draw.ss, e->d_out_tokens, e->out_cap);
             } else {
                 rc = add(F_NEXT, k_spec_commit, dim3(1), dim3(kWG), 0, b->spec_io, b->slots, b->nslots, nslots_used, e->d_state, e->d_out_tokens, e->out_cap);
             }
@@ -484,15 +482,13 @@ struct PlanBuilder {
             if (key.draw && (rc = draw_columns())) return rc;
             if (key.genlp && (rc = gen_logprobs())) return rc;
             if (!key.draw) return add(F_NEXT, k_cols_turn, dim3(1), dim3(kWG), 0, b->cols_ctl, b->slots, b->nslots, nslots_used, b->st, b->col_slot);
-            return add(F_NEXT, k_cols_turn_draw, dim3(1), dim3(kWG), 0, b->cols_ctl, b->cols_draw, b->spec_samp, b->st, b->col_slot);
+            return add(F_NEXT, k_cols_turn_draw, dim3(1), dim3(kWG), 0, b->cols_ctl, b->cols_draw, b->draw_cols.ss, b->st, b->col_slot);
         }
         if ((rc = add(F_NEXT, k_next_batch, dim3((unsigned)n), dim3(kWG), 0, b->st, b->slots, b->nslots, nslots_used, b->out_tokens, b->out_cap))) return rc;
         if (!b->sampling) return Q3_OK;
         // Sampler::sample per stream on the logits of this step (one workgroup per stream), behind its element-wise passes spread
         // over the chip
-        if (key.topk) return draw_topk(b->sargs);
-        if (b->sargs.pre_exp && (rc = add(F_NEXT, k_sample_exp, dim3(64, (unsigned)n), dim3(256), 0, b->sargs))) return rc;
-        return add(F_NEXT, k_sample, dim3((unsigned)n), dim3(kSampThreads), 4 * kSegFloats, b->sargs);
+        return draw(b->draw_decode);
     }
 
     int build() {
@@ -500,7 +496,7 @@ struct PlanBuilder {
         int rc;
         if (verify) {
             if ((rc = add(F_NEXT, k_spec_snapshot, dim3(spec_grid), dim3(kWG), 0, b->st, b->spec_io, n, e->d_key, e->d_value, b->spec_snap, L, c.seq_len, kvd))) return rc;
-            if (key.draw && (rc = add(F_NEXT, k_spec_sampler_states, dim3(1), dim3(64), 0, b->spec_io, n, e->d_sampler, b->spec_samp, b->st))) return rc;
+            if (key.draw && (rc = add(F_NEXT, k_spec_sampler_states, dim3(1), dim3(64), 0, b->spec_io, n, e->draw.ss, b->draw_cols.ss, b->st))) return rc;
         }
         for (int l = 0; l < L; ++l)
             if ((rc = layer(l))) return rc;
