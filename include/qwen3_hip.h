@@ -931,6 +931,54 @@ int q3_gen_logprobs_get(const q3_engine* e, int* top_n);
 int q3_gen_logprobs_read(q3_engine* e, size_t first, size_t count, q3_score_rec* recs, q3_score_top* top /* [count][top_n] or NULL */,
                          int32_t* rank /* [count] or NULL */);
 
+/* ------------------------------------------------------------------------------------------------
+ * 2p. (behind 2o so that the earlier sections stay as they were.)  Presence and frequency penalties: a token becomes less likely
+ * because its request has already produced it (presence_penalty / frequency_penalty of the completion APIs, the remedy for endless
+ * repetition), inside the five q3_generate_many_* loops, where no logit reaches the host.
+ * THE RULE.  Request r has produced y_0 .. y_{j-1}; its next token y_j is taken from a classifier row l[0 .. V).  c[v] is the number
+ * of i < j with y_i == v: prompt tokens, a shared prefix and other requests' tokens do not count.  The PENALISED row is
+ *     c[v] == 0:  l'[v] = l[v]                                          (the same bits, -0.0 and NaN payloads included)
+ *     c[v] >  0:  l'[v] = l[v] - (presence + frequency * (float)c[v])
+ * with every operation of the second line rounded to f32 on its own: multiply, then add, then subtract, nothing fused.  y_j is what
+ * the engine takes from l without the setting, taken from l' instead: in a greedy call and for a temperature-0 request the index of
+ * the largest key ((uint64)total_order_key(l'[v]) << 32) | v, so equal values go to the HIGHER index; otherwise Sampler::sample, or
+ * section 2n's draw among the top_k, over l' -- the softmax maximum is the largest penalised value, and the penalties come in front of
+ * temperature, top-k and top-p.  ONE coin per draw as before: the rng advances exactly as without penalties.  y_0 is taken from the raw
+ * row: all counts are zero.  The stop decision, the schedule, the cache rows and the coins of discarded prompt positions are unchanged.
+ * SECTION 2o's RECORDS STAY ON THE RAW ROW l: under penalties the records of a call still equal q3_score_many on prompt + output, but
+ * "argmax == token, rank == 0, bits(target) == bits(max)" of a greedy or temperature-0 request NO LONGER HOLD in general -- the
+ * committed token is the argmax of l', the record's argmax that of l.
+ * A NaN logit is outside the standard and harmless: only loop indices, ColEnt::out, slot numbers and the committed token clamped to
+ * [0, V) become addresses.
+ * What runs (csrc/q3_penalty.h).  A fourth axis on the column plans, built on first use; the existing forms and their graphs are
+ * untouched, and at (0, 0) every entry point launches exactly what it launched before this section existed.  Behind the classifier:
+ * k_pen_apply -- grid (64 slices, width): l' of every emitting column into a buffer of its own (the classifier's output is never
+ * written) and the largest key of every slice; a column that emits nothing leaves key 0 and returns.  Sampled plans fold those keys
+ * (k_spec_colmax) and draw over l'; the records, if any, follow on the raw rows; k_pen_count -- one workgroup -- adds the token about
+ * to be committed to its KV slot's counts; the turn kernel of a greedy plan folds the slices' keys in place of the classifier's.
+ * The column that emits a request's first token (the emitting column fed from the prompt) copies its row and clears its slot's counts.
+ * The values stand in device memory and are read when a pass runs: two non-zero settings share every plan and graph.
+ * IT DOES NOT TOUCH q3_batch_step_cols[_draw], section 2b, the verify paths or single-stream decode; a single-stream caller runs
+ * q3_generate_many_* with one request.  The setting is engine-wide: no per-request values, no penalty over the prompt.
+ * ------------------------------------------------------------------------------------------------ */
+
+/* The engine-wide setting, default (0, 0) = off.  It holds for every token q3_generate_many_greedy, _sampled, _dense, _stop and
+ * _prefix produce, greedy and sampled, and survives q3_sampler_set, q3_batch_sampler_set, q3_batch_init, q3_sampler_top_k,
+ * q3_gen_logprobs and every generate call.
+ * Execution: waits for the stream.  The first non-zero setting allocates the penalty state in the batched state -- counts
+ * [max_streams][V] u32, penalised rows [32][V] f32, slice keys [32][64] and the two values, about 39 MB at V = 151,936 and 32 slots,
+ * released with the state; with no batched state yet, the first generate call under the setting does.  Changing between two non-zero
+ * settings rebuilds and recaptures nothing; switching between (0, 0) and a non-zero setting selects the other form of the kept plans.
+ * Q3_ERR_ARG: a value that is not finite or lies outside [-2, 2] (checked first, then the null engine, before anything touches the
+ * GPU).  A refused call changes nothing. */
+int q3_sampler_penalties(q3_engine* e, float presence, float frequency);
+int q3_sampler_get_penalties(const q3_engine* e, float* presence, float* frequency);
+
+/* The rule above on a host vector: k_pen_apply once over logits[0 .. n) and counts[0 .. n).  out receives l', argmax the index of the
+ * largest key of l'.  Q3_ERR_ARG (before anything touches the GPU): the values as above; a null pointer; n == 0 or n >= 2^31. */
+int q3_op_penalize(const float* logits, const uint32_t* counts, size_t n, float presence, float frequency, float* out /* [n] */, int32_t* argmax,
+                   int device);
+
 #ifdef __cplusplus
 }
 #endif

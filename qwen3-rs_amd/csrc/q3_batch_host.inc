@@ -19,6 +19,9 @@ enum class PlanKind { Decode, Prefill, Verify, Cols, SlotPrefill };
 // topk: the draws of the plan are the top-k form (q3_topk.h); plan_get sets it from the engine's top_k wherever the plan draws
 // genlp: Cols plans of the q3_generate_many_* loops only (cols_key sets it from the engine's q3_gen_logprobs): kGenlpRecs, the record
 // launches (record_launches, q3_plan_host.inc) stand in front of the turn kernel; kGenlpTop, the top launches behind them
+// pen: Cols plans of the q3_generate_many_* loops only (cols_key sets it from the engine's q3_sampler_penalties): k_pen_apply stands
+// behind the classifier, the draws and the turn kernel take the penalised rows, k_pen_count stands in front of the turn kernel
+// (q3_penalty.h); the values of the setting are read from device memory when a pass runs
 enum { kGenlpOff = 0, kGenlpRecs = 1, kGenlpTop = 2, kGenlpForms = 3 };
 struct PlanKey {
     PlanKind kind = PlanKind::Decode;
@@ -26,7 +29,10 @@ struct PlanKey {
     bool draw = false;
     bool topk = false;
     int genlp = kGenlpOff;
-    bool operator==(const PlanKey& o) const { return kind == o.kind && n == o.n && draw == o.draw && topk == o.topk && genlp == o.genlp; }
+    bool pen = false;
+    bool operator==(const PlanKey& o) const {
+        return kind == o.kind && n == o.n && draw == o.draw && topk == o.topk && genlp == o.genlp && pen == o.pen;
+    }
 };
 // The launches of one key, built by batch_build_plan (q3_plan_host.inc): a value, moved to where its kind is kept.
 struct Plan {
@@ -106,10 +112,12 @@ struct BatchCtx {
     DevMem<int> col_slot;        // device [kColsMax]: KV slot of every column of the pass in flight
     DevMem<ColsCtl> cols_ctl;    // device
     PinMem<ColsHost> h_cols;
-    Plan cols_plans[kGenlpForms][3][kColsNW];           // [no records | records | records and top][greedy | sampled | sampled with
-                                                        // top-k][width], built on first use (q3_batch_init starts over); the sampled
-                                                        // ones: the same layers and classifier, then the draws and k_cols_turn_draw;
-                                                        // with records: the record launches in front of the turn kernel
+    Plan cols_plans[2][kGenlpForms][3][kColsNW];        // [plain | under penalties][no records | records | records and top][greedy |
+                                                        // sampled | sampled with top-k][width], built on first use (q3_batch_init
+                                                        // starts over); the sampled ones: the same layers and classifier, then the
+                                                        // draws and k_cols_turn_draw; with records: the record launches in front of
+                                                        // the turn kernel; under penalties: k_pen_apply behind the classifier and
+                                                        // k_pen_count in front of the turn kernel
     DevMem<ColEnt> cols_table;                          // the loop's pass table, prompts and output: grow-only device buffers
     DevMem<int> cols_ncols;
     DevMem<int32_t> cols_prompts, cols_out;
@@ -169,6 +177,14 @@ struct BatchCtx {
     size_t genlp_count = 0;
     int genlp_top_n = 0;
     bool genlp_valid = false;
+    // presence and frequency penalties (q3_sampler_penalties, section 2p).  One group, made by pen_alloc (q3_cols_host.inc) on the first
+    // non-zero setting or by the first generate call under one, never replaced while the context lives: the produced-token counts of
+    // every KV slot [max_streams][V], the penalised rows of a pass [kColsMax][V], their slices' largest keys [kColsMax][kPenSlices] and
+    // the setting as the passes read it
+    DevMem<unsigned> pen_counts;
+    DevMem<float> pen_logits;
+    DevMem<unsigned long long> pen_slots;
+    DevMem<PenCtl> pen_ctl;
     // packed-matrix directory
     struct PM { size_t q_off, s_off; int ntiles, ng; };
     std::vector<PM> m_qkv, m_wo, m_w13, m_w2;
@@ -527,6 +543,7 @@ int spec_draw_alloc(q3_engine* e) {
     HIP_TRY(hipMemsetAsync(site.ss, 0, sizeof(SamplerState) * kSpecMax, e->stream));
     // out_tokens is never written: a column's State::step stays 0, and out_cap 0 closes the window
     draw_args(site, DrawForm::Columns, b->logits, b->st, e->d_out_tokens, 0);
+    if (b->pen_logits) draw_args_pen(site, b->pen_logits);
     b->draw_cols = std::move(site);
     return Q3_OK;
 }

@@ -164,9 +164,10 @@ int cols_prepare(q3_engine* e, const char* who, bool draw = false) {
 // the key of the column plan a pass of n live columns runs: the narrowest width that holds it.  draw: the sampled plan of that
 // width (cols_draw_alloc has run by the time it is built: its launches carry the buffers allocated there).
 // lp: the q3_gen_logprobs value a q3_generate_many_* loop runs under (-1 off, 0 records, > 0 records and top): the plan's third axis.
-// Every other caller keeps the plans without records.
-PlanKey cols_key(int n, bool draw, int lp = -1) {
-    return PlanKey{PlanKind::Cols, kColsWidths[cols_width_index(n)], draw, false, lp < 0 ? kGenlpOff : (lp == 0 ? kGenlpRecs : kGenlpTop)};
+// pen: the loop runs under a non-zero q3_sampler_penalties (section 2p): the plan's fourth axis.
+// Every other caller keeps the plans without records and without penalties.
+PlanKey cols_key(int n, bool draw, int lp = -1, bool pen = false) {
+    return PlanKey{PlanKind::Cols, kColsWidths[cols_width_index(n)], draw, false, lp < 0 ? kGenlpOff : (lp == 0 ? kGenlpRecs : kGenlpTop), pen};
 }
 
 // What the plans with records carry of section 2o's own, on first use: the control block and its pinned copy (the scratch of the
@@ -379,8 +380,9 @@ struct ColsJobSampler {                 // the sampler side of a job (draw)
 // pads of every pass (they repeat the pass's last live column and emit nothing), then the whole job on the stream: the only
 // uploads of the call are the table, the run table, the prompts and the per-request sampler parameters; one synchronisation.
 // lp >= 0 (the generate loops under q3_gen_logprobs): the passes run the plans with records, which fill the call's n_out records.
+// pen (the generate loops under a non-zero q3_sampler_penalties): the passes run the plans under penalties.
 int cols_job_run(q3_engine* e, ColsJob& job, bool draw, const ColsJobSampler& smp, const int32_t* prompts, size_t n_prompt, int32_t* out_tokens, size_t n_out,
-                 int lp = -1) {
+                 int lp = -1, bool pen = false) {
     int rc;
     BatchCtx* b = e->batch;
     const size_t n_passes = job.ncols.size();
@@ -398,7 +400,7 @@ int cols_job_run(q3_engine* e, ColsJob& job, bool draw, const ColsJobSampler& sm
     if (lp >= 0 && (rc = genlp_alloc(e))) return rc;
     Plan* plans[kColsNW] = {nullptr};
     for (int w = 0; w < kColsNW; ++w)
-        if (width_used[w] && (rc = plan_get(e, cols_key(kColsWidths[w], draw, lp), &plans[w]))) return rc;
+        if (width_used[w] && (rc = plan_get(e, cols_key(kColsWidths[w], draw, lp, pen), &plans[w]))) return rc;
     std::vector<Plan*> wide_plans(job.steps.size(), nullptr);
     if (!job.runs.empty()) {
         if ((rc = dense_scratch_get(e))) return rc;
@@ -573,7 +575,7 @@ int cols_generate(q3_engine* e, const ColsRequests& rq, int32_t* out_tokens, q3_
         return rc;
     if (draw && (rc = cols_draw_alloc(e))) return rc;        // the loop's per-slot sampler states are allocated there
     const ColsJobSampler smp{b->cols_slot_samp, rq.temperature, rq.topp, rq.seeds, n_requests, false};
-    if ((rc = cols_job_run(e, job, draw, smp, rq.prompts, rq.n_prompt, out_tokens, rq.n_out, e->gen_logprobs))) return rc;
+    if ((rc = cols_job_run(e, job, draw, smp, rq.prompts, rq.n_prompt, out_tokens, rq.n_out, e->gen_logprobs, e->pen_on()))) return rc;
     if (stats) *stats = s.stats;
     if (dstats) *dstats = dst;
     return Q3_OK;
@@ -700,6 +702,35 @@ int q3_gen_logprobs_get(const q3_engine* e, int* top_n) {
     g_err[0] = 0;
     if (!e || !top_n) return fail(Q3_ERR_ARG, "null argument");
     *top_n = e->gen_logprobs;
+    return Q3_OK;
+}
+
+/* ---- section 2p: presence and frequency penalties ---- */
+
+int q3_sampler_penalties(q3_engine* e, float presence, float frequency) {
+    g_err[0] = 0;
+    if (int rc = penalties_check(presence, frequency)) return rc;
+    if (!e) return fail(Q3_ERR_ARG, "null engine");
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    const float p0 = e->pen_presence, f0 = e->pen_frequency;
+    e->pen_presence = presence;
+    e->pen_frequency = frequency;
+    // a batched state that is not there yet gets the penalty state from the first generate call that runs under the setting
+    int rc = Q3_OK;
+    if (e->batch && e->batch->has_kv) {
+        if (e->batch->pen_ctl) rc = pen_ctl_upload(e);
+        else if (e->pen_on()) rc = pen_alloc(e);
+    }
+    if (rc) { e->pen_presence = p0; e->pen_frequency = f0; }
+    return rc;
+}
+
+int q3_sampler_get_penalties(const q3_engine* e, float* presence, float* frequency) {
+    g_err[0] = 0;
+    if (!e || !presence || !frequency) return fail(Q3_ERR_ARG, "null argument");
+    *presence = e->pen_presence;
+    *frequency = e->pen_frequency;
     return Q3_OK;
 }
 

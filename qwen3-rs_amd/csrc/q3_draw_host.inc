@@ -35,6 +35,7 @@ struct DrawSite {
     DevMem<int> counts;
     int n = 0;                           // vocabulary size
     SampleArgs args{}, tail{};           // draw_args: what its launches carry; tail: the second k_sample of the pipelined draw
+    SampleArgs pen{};                    // draw_args_pen: args over the penalised rows of section 2p (the column site alone; logits null: not set)
     explicit operator bool() const { return ss != nullptr; }
 
     // One group, committed whole: a failed allocation leaves the site with none of it, and the next call starts over.
@@ -88,6 +89,17 @@ void draw_args(DrawSite& s, DrawForm form, const float* logits, State* st, int32
     s.tail.phase = 2;
 }
 
+// The one place the arguments of a draw over PENALISED rows are stated (section 2p): what draw_args left in s.args, with the rows of
+// q3_penalty.h's buffer -- [columns][n], the classifier's stride -- in place of the classifier's output.  Whoever makes the second of
+// the two (the column site, the penalty state) calls it; both exist before a plan that draws under penalties is built.
+void draw_args_pen(DrawSite& s, const float* pen_logits) {
+    s.pen = s.args;
+    s.pen.logits = pen_logits;
+    s.pen.sb_logits = s.n;
+}
+// the arguments a site's launches carry: over the classifier's rows, or (pen) over the penalised ones
+const SampleArgs& draw_site_args(const DrawSite& s, bool pen) { return pen ? s.pen : s.args; }
+
 // the top-k launches' view of a draw: its logits, states and outputs are the site's SampleArgs', k and the slices' lists are given
 TopkArgs topk_args(const SampleArgs& s, int* k, unsigned long long* part_keys) {
     TopkArgs t{};
@@ -110,8 +122,8 @@ TopkArgs topk_args(const SampleArgs& s, int* k, unsigned long long* part_keys) {
 // passes over the vocabulary in between run on the whole chip.  topk: the selection over the slices of every column, then one
 // wave per column (q3_topk.h).  put(kernel, grid, block, lds_bytes, args) appends one launch to a plan or enqueues it at once.
 template <class Put>
-int draw_launches(const DrawSite& site, int cols, unsigned exp_parts, const TopkArgs* topk, Put&& put) {
-    const SampleArgs& a = site.args;
+int draw_launches(const DrawSite& site, int cols, unsigned exp_parts, const TopkArgs* topk, Put&& put, bool pen = false) {
+    const SampleArgs& a = draw_site_args(site, pen);
     int rc;
     const dim3 per_col((unsigned)cols);
     if (topk) {

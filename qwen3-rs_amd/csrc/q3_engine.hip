@@ -44,6 +44,7 @@
 #include "q3_score_top.h"
 #include "q3_topk.h"
 #include "q3_genlp.h"
+#include "q3_penalty.h"
 #include "q3_lookup.h"
 
 namespace {
@@ -74,6 +75,13 @@ int sampler_check(float temperature, float topp, long req = -1) {
     char who[40] = "";
     if (req >= 0) snprintf(who, sizeof who, "request %ld: ", req);
     return bad_t ? fail(Q3_ERR_ARG, "%sTemperature must be non-negative", who) : fail(Q3_ERR_ARG, "%sTop-p must be between 0.0 and 1.0", who);
+}
+
+// what q3_sampler_penalties and q3_op_penalize refuse about their values (section 2p): finite, inside [-2, 2]
+int penalties_check(float presence, float frequency) {
+    const auto ok = [](float v) { return v >= -2.0f && v <= 2.0f; };      // false for a NaN
+    if (ok(presence) && ok(frequency)) return Q3_OK;
+    return fail(Q3_ERR_ARG, "penalties (%g, %g) out of range: finite values in -2 .. 2", (double)presence, (double)frequency);
 }
 
 constexpr int32_t kMagic = 0x616a6331;   // configuration.rs:8
@@ -370,6 +378,10 @@ struct q3_engine {
     // q3_generate_many_* loops produce; 1 .. kScoreTopMax: also that many best tokens and the rank.  What it needs on the device
     // belongs to the batched state (genlp_alloc, q3_cols_host.inc)
     int gen_logprobs = -1;
+    // presence and frequency penalties (q3_sampler_penalties, section 2p): engine-wide, (0, 0) = off.  The values also stand in device
+    // memory, in the batched state (pen_alloc, q3_cols_host.inc), where every pass under the setting reads them
+    float pen_presence = 0.0f, pen_frequency = 0.0f;
+    bool pen_on() const { return pen_presence != 0.0f || pen_frequency != 0.0f; }
     int enqueue_sample();
 
     int load(const char* path, uint32_t ctx_len);
@@ -1895,6 +1907,36 @@ int q3_op_sample_top_k(const float* logits, size_t n, float temperature, float t
     if (top_k < 1 || top_k > kTopkMax || (size_t)top_k > n)
         return fail(Q3_ERR_ARG, "top_k %d out of range (1..%d, at most n %zu)", top_k, kTopkMax, n);
     return op_draw(logits, n, temperature, topp, top_k, rng_state, index);
+}
+
+int q3_op_penalize(const float* logits, const uint32_t* counts, size_t n, float presence, float frequency, float* out, int32_t* argmax, int device) {
+    g_err[0] = 0;
+    int rc;
+    if ((rc = penalties_check(presence, frequency))) return rc;
+    if (!logits || !counts || !out || !argmax || n == 0) return fail(Q3_ERR_ARG, "null argument");
+    if (n > (size_t)INT32_MAX) return fail(Q3_ERR_ARG, "more than 2^31 logits");
+    if ((rc = op_begin(device))) return rc;
+    OpBuf dl, dc, dout, dkeys, dctl;
+    const PenCtl h{presence, frequency};
+    if ((rc = dl.upload(logits, 4 * n)) || (rc = dc.upload(counts, 4 * n)) || (rc = dout.alloc(4 * n)) || (rc = dkeys.alloc(8 * (size_t)kPenSlices)) ||
+        (rc = dctl.upload(&h, sizeof(h))))
+        return rc;
+    // one row, emitting, the counts as given: k_pen_apply without a pass (PenArgs::cols null)
+    PenArgs a{};
+    a.logits = dl.as<float>();
+    a.pen_logits = dout.as<float>();
+    a.counts = dc.as<unsigned>();
+    a.pen_slots = dkeys.as<unsigned long long>();
+    a.ctl = dctl.as<PenCtl>();
+    a.n = (int)n;
+    a.max_streams = 1;
+    if ((rc = launch_now(0, k_pen_apply, dim3(kPenSlices, 1), dim3(kPenThreads), 0, a)) || (rc = op_end())) return rc;
+    unsigned long long keys[kPenSlices], best = 0ull;
+    HIP_TRY(hipMemcpy(out, dout.p, 4 * n, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(keys, dkeys.p, sizeof keys, hipMemcpyDeviceToHost));
+    for (int i = 0; i < kPenSlices; ++i) best = std::max(best, keys[i]);
+    *argmax = (int32_t)(best & 0xffffffffull);
+    return Q3_OK;
 }
 
 int q3_op_argmax(const float* logits, size_t n, int32_t* index, int device) {

@@ -31,15 +31,17 @@ struct PassRows {
     const ColsDraw* draw;               // sampled plans: mode[] of the pass in flight; null in a greedy plan
     const State* st;                    // sampled plans: State::token holds the draw, State::argmax the row's largest key
     const GenlpCtl* ctl;
+    int pen;                            // 1: a plan under penalties (q3_penalty.h) -- State::argmax holds the largest key of the PENALISED
+                                        // row in a greedy plan too (k_spec_colmax over its slices), and the committed token is that key's
     // the record of column j, or -1: the column emits nothing
     __device__ __forceinline__ int out(int j) const { return j < cols->n_live ? cols->out[j] : -1; }
     __device__ __forceinline__ bool live(int j) const { return out(j) >= 0; }
     __device__ __forceinline__ bool top_live(int j, int k) const { return live(j) && k >= 1 && k <= kScoreTopMax; }
     // the token the turn kernel commits for column j (best(): the fold of the row's slots, which a sampled plan also holds in
-    // State::argmax, where k_cols_turn_draw reads it), clamped to the vocabulary
+    // State::argmax, where k_cols_turn_draw reads it; under penalties the fold of the penalised row's slices), clamped to the vocabulary
     template <class Best>
     __device__ __forceinline__ int target(const RecordArgs& a, int j, Best&& best) const {
-        const int t = draw ? cols_commit_token(draw->mode[j], st[j].argmax, st[j].token) : cols_commit_token(kColArgmax, best(), 0);
+        const int t = draw ? cols_commit_token(draw->mode[j], st[j].argmax, st[j].token) : cols_commit_token(kColArgmax, pen ? st[j].argmax : best(), 0);
         return min(max(t, 0), a.n - 1);
     }
     __device__ __forceinline__ int k() const { return ctl->top_n; }

@@ -135,6 +135,49 @@ int record_launches(const RecordArgs& a, const Src& src, int rows, Put&& put) {
     return put(true, k_score_top_merge<Src>, dim3((unsigned)rows), dim3(256), a, src);
 }
 
+// ---- the penalty state (q3_penalty.h, section 2p): what a plan under penalties points at, made here and nowhere else: on first use,
+// at its full size, and never again while the context lives -- so a captured plan's pointers hold whatever call comes next.  One
+// group, committed whole.  The counts need no clearing: a request's first output clears its slot's.  The setting goes to the device
+// with it; q3_sampler_penalties rewrites that word alone.
+int pen_ctl_upload(q3_engine* e) {
+    const PenCtl h{e->pen_presence, e->pen_frequency};
+    HIP_TRY(hipMemcpy(e->batch->pen_ctl, &h, sizeof(PenCtl), hipMemcpyHostToDevice));
+    return Q3_OK;
+}
+int pen_alloc(q3_engine* e) {
+    BatchCtx* b = e->batch;
+    if (b->pen_ctl) return Q3_OK;
+    int rc;
+    HIP_TRY(hipSetDevice(e->device));
+    const size_t V = (size_t)e->cfg.vocab_size;
+    DevMem<unsigned> counts; DevMem<float> rows; DevMem<unsigned long long> keys; DevMem<PenCtl> ctl;
+    if ((rc = counts.alloc((size_t)b->max_streams * V)) || (rc = rows.alloc((size_t)kColsMax * V)) || (rc = keys.alloc((size_t)kColsMax * kPenSlices)) ||
+        (rc = ctl.alloc(1)))
+        return rc;
+    HIP_TRY(hipMemsetAsync(keys, 0, 8 * (size_t)kColsMax * kPenSlices, e->stream));
+    b->pen_counts = std::move(counts); b->pen_logits = std::move(rows); b->pen_slots = std::move(keys); b->pen_ctl = std::move(ctl);
+    if (b->draw_cols) draw_args_pen(b->draw_cols, b->pen_logits);
+    return pen_ctl_upload(e);
+}
+// The arguments of k_pen_apply and k_pen_count over the pass in flight (pen_alloc has run; nothing is written here).  draw: the plan
+// is a sampled one, whose columns carry a mode
+PenArgs pen_args(const q3_engine* e, bool draw) {
+    const BatchCtx* b = e->batch;
+    PenArgs a{};
+    a.logits = b->logits;
+    a.pen_logits = b->pen_logits;
+    a.counts = b->pen_counts;
+    a.pen_slots = b->pen_slots;
+    a.ctl = b->pen_ctl;
+    a.cols = b->cols_ctl;
+    a.draw = draw ? (const ColsDraw*)b->cols_draw : nullptr;
+    a.st = b->st;
+    a.col_slot = b->col_slot;
+    a.n = e->cfg.vocab_size;
+    a.max_streams = b->max_streams;
+    return a;
+}
+
 // ---- the builder: the launches of key.n streams (Decode), block positions (Prefill, Verify; draw: Verify under the sampler),
 // columns (Cols; draw: the sampled column plan) or columns of a dense block over the slots (SlotPrefill), appended to `out`.
 // It reads the engine and the context and writes neither.
@@ -439,15 +482,26 @@ struct PlanBuilder {
     // behind the element-wise passes spread over the chip), behind the per-column maximum they read.  Columns that do not draw
     // (interior prompt positions, pads, temperature-0 slots of a column pass) return at once in both sampler launches
     int draw_columns() {
-        if (int rc = add(F_NEXT, k_spec_colmax, dim3(1), dim3(kWG), 0, b->st, b->slots, b->nslots, nslots_used, n)) return rc;
+        if (int rc = colmax()) return rc;
         return draw(b->draw_cols);
     }
-    // the draws of a site's first n columns, plain or top-k as the key says (draw_launches)
+    // State::argmax of every column: the fold of the classifier's argmax slots, or under penalties of the penalised row's slices
+    int colmax() {
+        if (key.pen) return add(F_NEXT, k_spec_colmax, dim3(1), dim3(kWG), 0, b->st, b->pen_slots, kPenSlices, kPenSlices, n);
+        return add(F_NEXT, k_spec_colmax, dim3(1), dim3(kWG), 0, b->st, b->slots, b->nslots, nslots_used, n);
+    }
+    // the draws of a site's first n columns, plain or top-k as the key says (draw_launches); under penalties over the penalised rows
     int draw(const DrawSite& site) {
-        const TopkArgs t = e->topk_args(site.args);
+        if (key.pen && !site.pen.logits) return fail(Q3_ERR_INTERNAL, "a sampled plan under penalties before draw_args_pen");
+        const TopkArgs t = e->topk_args(draw_site_args(site, key.pen));
         return draw_launches(site, n, kDrawExpParts, key.topk ? &t : nullptr, [&](auto kernel, dim3 grid, dim3 blk, size_t smem, const auto& a) {
             return add(F_NEXT, kernel, grid, blk, smem, a);
-        });
+        }, key.pen);
+    }
+    // the penalised rows of the emitting columns and their slices' largest keys, behind the classifier (pen_alloc has run)
+    int penalize() {
+        if (!b->pen_ctl) return fail(Q3_ERR_INTERNAL, "a plan under penalties before pen_alloc");
+        return add(F_NEXT, k_pen_apply, dim3(kPenSlices, (unsigned)n), dim3(kPenThreads), 0, pen_args(e, key.draw));
     }
 
     // the records of the columns the turn kernel is about to commit (PassRows, q3_genlp.h; genlp_alloc has run, and plan_get has
@@ -456,7 +510,7 @@ struct PlanBuilder {
         if (!b->genlp_ctl) return fail(Q3_ERR_INTERNAL, "a plan with records before genlp_alloc");
         RecordArgs a;
         if (int rc = record_args(e, key.genlp == kGenlpTop, nslots_used, kScoreTopParts, a)) return rc;
-        const PassRows src{b->cols_ctl, key.draw ? (const ColsDraw*)b->cols_draw : nullptr, b->st, b->genlp_ctl};
+        const PassRows src{b->cols_ctl, key.draw ? (const ColsDraw*)b->cols_draw : nullptr, b->st, b->genlp_ctl, key.pen ? 1 : 0};
         return record_launches(a, src, n, [&](bool, auto kernel, dim3 grid, dim3 blk, const RecordArgs& ra, const PassRows& rs) {
             return add(F_NEXT, kernel, grid, blk, 0, ra, rs);
         });
@@ -479,8 +533,15 @@ struct PlanBuilder {
         }
         if (cols) {
             // sampled: the draws over the column sampler states k_cols_turn_draw set up
+            // under penalties (section 2p): the draws and the turn kernel take the penalised rows and their slices' keys; the records
+            // stay on the raw rows, their target alone is the token committed from the penalised ones (a greedy plan with records
+            // gets it from State::argmax as a sampled one does)
+            if (key.pen && (rc = penalize())) return rc;
             if (key.draw && (rc = draw_columns())) return rc;
+            if (key.pen && key.genlp && !key.draw && (rc = colmax())) return rc;
             if (key.genlp && (rc = gen_logprobs())) return rc;
+            if (key.pen && (rc = add(F_NEXT, k_pen_count, dim3(1), dim3(64), 0, pen_args(e, key.draw)))) return rc;
+            if (!key.draw && key.pen) return add(F_NEXT, k_cols_turn, dim3(1), dim3(kWG), 0, b->cols_ctl, b->pen_slots, kPenSlices, kPenSlices, b->st, b->col_slot);
             if (!key.draw) return add(F_NEXT, k_cols_turn, dim3(1), dim3(kWG), 0, b->cols_ctl, b->slots, b->nslots, nslots_used, b->st, b->col_slot);
             return add(F_NEXT, k_cols_turn_draw, dim3(1), dim3(kWG), 0, b->cols_ctl, b->cols_draw, b->draw_cols.ss, b->st, b->col_slot);
         }
@@ -536,10 +597,10 @@ int plan_get(q3_engine* e, PlanKey key, Plan** out) {
     bool hit;
     // the engine's top_k holds wherever the plan draws: the sampled Verify and Cols plans, and the Decode plan under the batch sampler
     key.topk = e->top_k > 0 && (key.draw || (key.kind == PlanKind::Decode && b->sampling));
-    if (key.kind != PlanKind::Cols) key.genlp = kGenlpOff;
+    if (key.kind != PlanKind::Cols) { key.genlp = kGenlpOff; key.pen = false; }
     if (key.genlp < kGenlpOff || key.genlp >= kGenlpForms) return fail(Q3_ERR_INTERNAL, "plan form %d", key.genlp);
     if (key.kind == PlanKind::Cols) {
-        home = &b->cols_plans[key.genlp][key.draw ? (key.topk ? 2 : 1) : 0][cols_width_index(key.n)];
+        home = &b->cols_plans[key.pen ? 1 : 0][key.genlp][key.draw ? (key.topk ? 2 : 1) : 0][cols_width_index(key.n)];
         hit = !home->launches.empty();
     } else if (key.kind == PlanKind::SlotPrefill) {
         if (key.n <= kColsMax || key.n > b->dense.cap)
@@ -554,6 +615,9 @@ int plan_get(q3_engine* e, PlanKey key, Plan** out) {
         // the scratch a plan with records points at exists before the plan does
         if (key.genlp != kGenlpOff)
             if (int rc = record_scratch(e, key.genlp == kGenlpTop)) return rc;
+        // ... and so does the penalty state a plan under penalties points at
+        if (key.pen)
+            if (int rc = pen_alloc(e)) return rc;
         Plan built;
         if (int rc = batch_build_plan(e, key, built)) return rc;
         if (key.kind == PlanKind::SlotPrefill) home = &b->dense_plans[key.n];

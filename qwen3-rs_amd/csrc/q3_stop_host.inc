@@ -84,7 +84,7 @@ int cols_generate_stop(q3_engine* e, const ColsRequests& rq, const int32_t* stop
         if (hs->n_live < 1 || hs->n_live > kColsMax) return fail(Q3_ERR_INTERNAL, "the scheduler laid out a pass of %d columns", hs->n_live);
         if (++passes > pass_cap) return fail(Q3_ERR_INTERNAL, "the scheduler asks for more than %zu passes", pass_cap);
         Plan* plan;                                        // built on first use of a width: the stream is idle here
-        if ((rc = plan_get(e, cols_key(hs->n_live, draw, lp), &plan))) return rc;
+        if ((rc = plan_get(e, cols_key(hs->n_live, draw, lp, e->pen_on()), &plan))) return rc;
         if ((rc = plan_enqueue(e, *plan))) return rc;      // ends with the turn kernel: cursor == n_passes, it commits and sets nothing up
     }
     std::vector<int> got(n_requests);

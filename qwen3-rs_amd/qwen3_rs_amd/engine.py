@@ -37,7 +37,9 @@ EXPORTED_SYMBOLS = [
     "q3_score_top_many",
     "q3_sampler_top_k", "q3_sampler_get_top_k", "q3_op_sample_top_k",
     "q3_gen_logprobs", "q3_gen_logprobs_get", "q3_gen_logprobs_read",
+    "q3_sampler_penalties", "q3_sampler_get_penalties", "q3_op_penalize",
 ]
+PENALTY_MAX = 2.0        # |presence|, |frequency| <= 2 (section 2p)
 VERIFY_MAX = 32          # Q3_VERIFY_MAX
 COLS_MAX = 32            # Q3_COLS_MAX
 STOP_MAX = 8             # Q3_STOP_MAX
@@ -297,8 +299,22 @@ def _bind(path: str) -> C.CDLL:
     L.q3_op_argmax.argtypes = [fp, sz, C.POINTER(C.c_int32), C.c_int]
     L.q3_op_sample.argtypes = [fp, sz, C.c_float, C.c_float, C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.c_int]
     L.q3_op_sample_top_k.argtypes = [fp, sz, C.c_float, C.c_float, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.c_int]
+    L.q3_sampler_penalties.argtypes = [C.c_void_p, C.c_float, C.c_float]
+    L.q3_sampler_get_penalties.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    L.q3_op_penalize.argtypes = [fp, C.POINTER(C.c_uint32), sz, C.c_float, C.c_float, fp, C.POINTER(C.c_int32), C.c_int]
     _libs[path] = L
     return L
+
+
+def _check_penalties(presence, frequency):
+    """the values q3_sampler_penalties and q3_op_penalize accept (finite, -2 .. 2 once rounded to f32), checked before the call"""
+    for name, v in (("presence", presence), ("frequency", frequency)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise TypeError(f"{name} penalty must be a number, got {v!r}")
+        with np.errstate(over="ignore"):
+            f = np.float32(v)
+        if not np.isfinite(f) or abs(f) > np.float32(PENALTY_MAX):
+            raise ValueError(f"{name} penalty {v} out of range (finite, -{PENALTY_MAX}..{PENALTY_MAX})")
 
 
 def _check(rc: int):
@@ -891,6 +907,21 @@ class Transformer:
         _check(self._lib.q3_gen_logprobs_get(self._h, C.byref(out)))
         return int(out.value)
 
+    # ---- presence and frequency penalties (include/qwen3_hip.h section 2p)
+    def set_penalties(self, presence: float, frequency: float):
+        """Presence and frequency penalties of every generate_many_* call (q3_sampler_penalties): a token the request has produced c > 0
+        times has presence + frequency * c taken off its logit before the argmax or the draw; prompt tokens do not count.  (0, 0)
+        turns them off (the default).  The setting is the engine's: it survives set_sampler, batch_init, set_top_k, set_gen_logprobs
+        and every generate_many call, and it does not touch batch_step_cols, forward_batch, verify or single-stream decode."""
+        _check_penalties(presence, frequency)
+        _check(self._lib.q3_sampler_penalties(self._h, float(presence), float(frequency)))
+
+    def get_penalties(self):
+        """the engine's (presence, frequency) (q3_sampler_get_penalties); (0.0, 0.0): off"""
+        p, f = C.c_float(0.0), C.c_float(0.0)
+        _check(self._lib.q3_sampler_get_penalties(self._h, C.byref(p), C.byref(f)))
+        return float(p.value), float(f.value)
+
     def read_gen_logprobs(self, n_per_row=None):
         """The records of the last generate_many_* call (q3_gen_logprobs_read), which ran under set_gen_logprobs(top_n >= 0): per
         request (records, tops, ranks) -- SCORE_DTYPE[n], TOP_DTYPE[n, top_n], int32[n], entry j for the request's j-th token; tops
@@ -1138,6 +1169,19 @@ class _Ops:
         out, st = C.c_int32(-1), C.c_uint64(rng_state)
         _check(load_library().q3_op_sample_top_k(self._fp(logits), logits.size, temperature, topp, top_k, C.byref(st), C.byref(out), self.device))
         return int(out.value), int(st.value)
+
+    def penalize(self, logits, counts, presence: float, frequency: float):
+        """The penalised row of include/qwen3_hip.h section 2p on the device (q3_op_penalize): l' = l where counts is 0, else
+        l - (presence + frequency * counts), every step rounded to f32.  Returns (l' as float32[n], the index of its largest key)."""
+        _check_penalties(presence, frequency)
+        logits = np.ascontiguousarray(logits, dtype=np.float32)
+        counts = np.ascontiguousarray(counts, dtype=np.uint32)
+        if logits.ndim != 1 or logits.shape != counts.shape or logits.size == 0:
+            raise ValueError("logits and counts must be non-empty vectors of one length")
+        out, idx = np.empty_like(logits), C.c_int32(-1)
+        _check(load_library().q3_op_penalize(self._fp(logits), counts.ctypes.data_as(C.POINTER(C.c_uint32)), logits.size, float(presence),
+                                             float(frequency), self._fp(out), C.byref(idx), self.device))
+        return out, int(idx.value)
 
 
 ops = _Ops()

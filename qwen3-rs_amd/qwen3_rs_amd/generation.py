@@ -165,7 +165,8 @@ def common_prefix_len(prompts: Sequence[Sequence[int]]) -> int:
 
 
 def generate_many(transformer, prompts: Sequence[Sequence[int]], max_new_tokens: int, stop_tokens: Iterable[int] = (), sampler=None,
-                  dense_min: int = 0, stop_on_device: bool = False, shared_prefix=None, logprobs: Optional[int] = None):
+                  dense_min: int = 0, stop_on_device: bool = False, shared_prefix=None, logprobs: Optional[int] = None,
+                  presence_penalty: float = 0.0, frequency_penalty: float = 0.0):
     """Many greedy generations served through the slots of Transformer.batch_init in ragged column passes
     (Transformer.generate_many_greedy).  Row r holds what Transformer.prefill(prompts[r], 0) followed by generate_greedy returns on
     an engine of its own: every prompt token goes through the model (chat's prompt loop, generation.rs:116-123), then up to
@@ -193,9 +194,26 @@ def generate_many(transformer, prompts: Sequence[Sequence[int]], max_new_tokens:
     whatever sampler drew the tokens.  Works with every option above; the rows are the same with or without it.
     Returns (rows, ColsStats); with logprobs set (rows, ColsStats, per row a tuple (logprobs[n], top_ids[n, k], top_logprobs[n, k],
     rank[n]) in the shape top_logprobs() uses, n the row's length, k = logprobs; with logprobs=0 the two middle entries are empty
-    and so is rank)."""
+    and so is rank).
+    presence_penalty, frequency_penalty: -2 .. 2 (Transformer.set_penalties, set for this call and put back afterwards, also when the
+    call raises): a token the row has produced c > 0 times has presence_penalty + frequency_penalty * c taken off its logit before the
+    argmax or the draw, in front of temperature, top-k and top-p; prompt tokens do not count.  Works with every option above; the
+    logprobs stay those of the raw distribution."""
     if any(len(p) == 0 for p in prompts):
         raise ValueError("Please provide a prompt")
+    # (an engine stand-in without the setting serves a call without penalties as it did)
+    if hasattr(transformer, "get_penalties") or presence_penalty != 0.0 or frequency_penalty != 0.0:
+        pen_before = transformer.get_penalties()
+        transformer.set_penalties(presence_penalty, frequency_penalty)
+        try:
+            return _generate_many_lp(transformer, prompts, max_new_tokens, stop_tokens, sampler, dense_min, stop_on_device, shared_prefix, logprobs)
+        finally:
+            transformer.set_penalties(*pen_before)
+    return _generate_many_lp(transformer, prompts, max_new_tokens, stop_tokens, sampler, dense_min, stop_on_device, shared_prefix, logprobs)
+
+
+def _generate_many_lp(transformer, prompts, max_new_tokens, stop_tokens, sampler, dense_min, stop_on_device, shared_prefix, logprobs):
+    """generate_many behind its penalties handling"""
     if logprobs is not None:
         if isinstance(logprobs, bool) or not isinstance(logprobs, (int, np.integer)) or logprobs < 0 or logprobs > 64:
             raise ValueError(f"logprobs {logprobs!r} out of range (None, or 0..64)")
