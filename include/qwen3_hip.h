@@ -979,6 +979,71 @@ int q3_sampler_get_penalties(const q3_engine* e, float* presence, float* frequen
 int q3_op_penalize(const float* logits, const uint32_t* counts, size_t n, float presence, float frequency, float* out /* [n] */, int32_t* argmax,
                    int device);
 
+/* ------------------------------------------------------------------------------------------------
+ * 2q. (behind 2p so that the earlier sections stay as they were.)  Logit bias, banned and allowed tokens, min_tokens: the caller
+ * constrains which tokens may come (logit_bias, bad_words, allowed_token_ids or guided choice, min_tokens of the completion APIs),
+ * inside the five q3_generate_many_* loops, where no logit reaches the host and a request's next column depends on the token it just
+ * committed.
+ * THE RULE.  Request r is about to produce its output y_g (g = 0: the token behind the prompt) from classifier row l[0 .. V).  It has
+ * a list of at most Q3_BIAS_MAX entries with distinct tokens, and a mode.  An entry is ACTIVE for y_g when until == 0 || g < until.
+ * The ADJUSTED row is
+ *     v listed, active, bias +-0:     a[v] = l[v]            (the same bits)
+ *     v listed, active, otherwise:    a[v] = l[v] + bias     (one f32 rounding; bias -inf gives -inf)
+ *     v listed, not active:           a[v] = l[v]            (the same bits, under both modes)
+ *     v unlisted, Q3_BIAS_ADD:        a[v] = l[v]            (the same bits, -0.0 and NaN payloads included)
+ *     v unlisted, Q3_BIAS_ALLOW:      a[v] = -inf            (bits 0xFF800000)
+ * Section 2p's penalties, if set, then apply to a in place of l: c[v] > 0 gives a[v] - (presence + frequency * c[v]) with the same
+ * three roundings, c[v] == 0 the bits of a[v].  Everything downstream takes this row exactly as section 2p defines it for l': greedy
+ * and temperature-0 requests the largest key ((uint64)total_order_key << 32) | v, so equal values go to the HIGHER index; sampled
+ * requests Sampler::sample, or section 2n's draw among the top_k, over it -- one coin per draw, the softmax maximum the largest
+ * adjusted value.  Unlike the penalties THE RULE APPLIES TO y_0 TOO.  The stop decision, the schedule, the cache rows and the coins of
+ * discarded prompt positions are unchanged.  SECTION 2o's RECORDS STAY ON THE RAW ROW l, as under 2p: the record's target is the
+ * committed token, its log-probability, argmax and rank are those of the unconstrained distribution.
+ * min_tokens needs nothing of the scheduler: a stop token carried as {eos, -inf, until = min_tokens} cannot be committed for
+ * g < min_tokens, so the stop rule never sees it.
+ * A BANNED TOKEN has probability exactly 0 under the sampler (exp(-inf - max) == 0).  The reference sampler's fall-through -- index
+ * n - 1, or the last index of the nucleus, when rounding leaves the coin above the cumulative sum -- is kept as it is: the standard
+ * is bit-equality with q3_op_sample / q3_op_sample_top_k on the adjusted row, not "a banned token can never appear".
+ * +inf + (-inf) is NaN.  A NaN logit is outside the standard and harmless, as in 2p: only loop indices, ColsCtl::out, slot numbers,
+ * request and entry indices clamped to their arrays and the committed token clamped to [0, V) become addresses.
+ * What runs (csrc/q3_bias.h).  One more form on the fourth axis of the column plans (off / penalties / adjusted), built on first use.
+ * k_bias_apply stands where k_pen_apply stands, with its grid (64 slices, width), its row buffer and its slice keys, so the turn
+ * kernels, k_spec_colmax, the sampler and the top-k selection run as under penalties.  A column learns its request and g from
+ * ColsCtl::out[j] == o_off[r] + g by a search over the call's o_off; a slice whose part of the list is empty copies.  Whether
+ * penalties apply on top is read from device memory when a pass runs; without them no counts array is allocated or read.  The lists,
+ * their offsets, the modes and o_off are uploaded by every generate call under a table: two tables share every plan and graph.  With
+ * no table set every entry point launches exactly what it launched before this section existed.
+ * IT DOES NOT TOUCH q3_batch_step_cols[_draw], section 2b, the verify paths, single-stream decode, q3_embed_many, q3_choice_many,
+ * q3_score_many or q3_score_top_many.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct q3_bias_entry { int32_t token; float bias; uint32_t until; } q3_bias_entry;
+#define Q3_BIAS_MAX   4096
+#define Q3_BIAS_ADD   0
+#define Q3_BIAS_ALLOW 1
+
+/* The engine-wide table, default none = off.  n_lists == 0 turns it off; n_lists == 1: the one list holds for every request of every
+ * call; n_lists > 1: list r belongs to request r, and a q3_generate_many_* call whose n_requests != n_lists returns Q3_ERR_ARG before
+ * anything runs.  entries: the lists one behind the other, list i of n_entries[i] entries in any order (the library keeps a copy,
+ * sorted by token).  mode: per list, or NULL for Q3_BIAS_ADD throughout.  The table holds for every token q3_generate_many_greedy,
+ * _sampled, _dense, _stop and _prefix produce, and survives q3_sampler_set, q3_batch_sampler_set, q3_batch_init, q3_sampler_top_k,
+ * q3_gen_logprobs, q3_sampler_penalties and every generate call.
+ * Execution: waits for the stream; the device side is made by the first generate call under a table.
+ * Q3_ERR_ARG, checked before the engine or the GPU is touched: a null array with a non-zero count; a list longer than Q3_BIAS_MAX; a
+ * token twice in one list; a negative token; a bias that is NaN, +inf, or finite outside [-100, 100]; a mode other than 0 or 1; an
+ * ALLOW list with no finite-bias entry.  Then the null engine, then what needs the model: a token >= vocab_size; an ADD list whose
+ * -inf entries number >= vocab_size.  A refused call changes nothing. */
+int q3_logit_bias_set(q3_engine* e, const q3_bias_entry* entries /* concatenated */, const size_t* n_entries /* [n_lists] */,
+                      const uint8_t* mode /* [n_lists] or NULL: all ADD */, size_t n_lists);
+int q3_logit_bias_get(const q3_engine* e, size_t* n_lists, size_t* n_entries_total);
+
+/* The rule above on a host vector: k_bias_apply once over logits[0 .. n) for output index g of a request with the one list given,
+ * then the penalties over counts[0 .. n) where counts is not NULL.  out receives the row, argmax the index of its largest key.
+ * Q3_ERR_ARG (before anything touches the GPU): the list as above with vocab_size n; the penalty values as in 2p; a null pointer;
+ * n == 0 or n >= 2^31. */
+int q3_op_logit_bias(const float* logits, size_t n, const q3_bias_entry* entries, size_t n_entries, int mode, uint32_t g,
+                     const uint32_t* counts /* or NULL: no penalties */, float presence, float frequency, float* out /* [n] */, int32_t* argmax,
+                     int device);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,7 +21,9 @@ enum class PlanKind { Decode, Prefill, Verify, Cols, SlotPrefill };
 // launches (record_launches, q3_plan_host.inc) stand in front of the turn kernel; kGenlpTop, the top launches behind them
 // pen: Cols plans of the q3_generate_many_* loops only (cols_key sets it from the engine's q3_sampler_penalties): k_pen_apply stands
 // behind the classifier, the draws and the turn kernel take the penalised rows, k_pen_count stands in front of the turn kernel
-// (q3_penalty.h); the values of the setting are read from device memory when a pass runs
+// (q3_penalty.h); the values of the setting are read from device memory when a pass runs.  kPenAdj (cols_key sets it where a table
+// of q3_logit_bias_set holds, section 2q): k_bias_apply and k_bias_count (q3_bias.h) stand in their places, and whether penalties apply
+// on top is read from device memory when a pass runs (kPenOff / kPenOn / kPenAdj: q3_bias.h)
 enum { kGenlpOff = 0, kGenlpRecs = 1, kGenlpTop = 2, kGenlpForms = 3 };
 struct PlanKey {
     PlanKind kind = PlanKind::Decode;
@@ -29,7 +31,7 @@ struct PlanKey {
     bool draw = false;
     bool topk = false;
     int genlp = kGenlpOff;
-    bool pen = false;
+    int pen = kPenOff;
     bool operator==(const PlanKey& o) const {
         return kind == o.kind && n == o.n && draw == o.draw && topk == o.topk && genlp == o.genlp && pen == o.pen;
     }
@@ -112,12 +114,13 @@ struct BatchCtx {
     DevMem<int> col_slot;        // device [kColsMax]: KV slot of every column of the pass in flight
     DevMem<ColsCtl> cols_ctl;    // device
     PinMem<ColsHost> h_cols;
-    Plan cols_plans[2][kGenlpForms][3][kColsNW];        // [plain | under penalties][no records | records | records and top][greedy |
+    Plan cols_plans[kPenForms][kGenlpForms][3][kColsNW];   // [plain | under penalties | adjusted rows][no records | records | records and top][greedy |
                                                         // sampled | sampled with top-k][width], built on first use (q3_batch_init
                                                         // starts over); the sampled ones: the same layers and classifier, then the
                                                         // draws and k_cols_turn_draw; with records: the record launches in front of
                                                         // the turn kernel; under penalties: k_pen_apply behind the classifier and
-                                                        // k_pen_count in front of the turn kernel
+                                                        // k_pen_count in front of the turn kernel; adjusted rows: k_bias_apply and
+                                                        // k_bias_count in their places
     DevMem<ColEnt> cols_table;                          // the loop's pass table, prompts and output: grow-only device buffers
     DevMem<int> cols_ncols;
     DevMem<int32_t> cols_prompts, cols_out;
@@ -177,14 +180,22 @@ struct BatchCtx {
     size_t genlp_count = 0;
     int genlp_top_n = 0;
     bool genlp_valid = false;
-    // presence and frequency penalties (q3_sampler_penalties, section 2p).  One group, made by pen_alloc (q3_cols_host.inc) on the first
-    // non-zero setting or by the first generate call under one, never replaced while the context lives: the produced-token counts of
-    // every KV slot [max_streams][V], the penalised rows of a pass [kColsMax][V], their slices' largest keys [kColsMax][kPenSlices] and
-    // the setting as the passes read it
+    // presence and frequency penalties (q3_sampler_penalties, section 2p), made by pen_alloc (q3_plan_host.inc) on the first non-zero
+    // setting or by the first generate call under one, never replaced while the context lives: the produced-token counts of every KV
+    // slot [max_streams][V], and -- a group of their own (adj_alloc), which the adjusted rows of section 2q share and a table without
+    // penalties makes alone -- the penalised rows of a pass [kColsMax][V], their slices' largest keys [kColsMax][kPenSlices] and the
+    // setting as the passes read it
     DevMem<unsigned> pen_counts;
     DevMem<float> pen_logits;
     DevMem<unsigned long long> pen_slots;
     DevMem<PenCtl> pen_ctl;
+    // the table of q3_logit_bias_set as the call in flight reads it (section 2q; bias_call_begin, q3_plan_host.inc): the control block
+    // the plans of the adjusted form point at, made once, and behind it the grow-only buffers every generate call under a table fills
+    DevMem<BiasCtl> bias_ctl;
+    DevMem<BiasEntry> bias_entries;
+    DevMem<unsigned> bias_off;
+    DevMem<unsigned char> bias_modes;
+    DevMem<int> bias_ooff;
     // packed-matrix directory
     struct PM { size_t q_off, s_off; int ntiles, ng; };
     std::vector<PM> m_qkv, m_wo, m_w13, m_w2;

@@ -73,6 +73,8 @@ int cols_requests_check(q3_engine* e, const int32_t* prompts, const size_t* prom
         if (prompts[i] < 0 || prompts[i] >= e->cfg.vocab_size)
             return fail(Q3_ERR_ARG, "index out of range: token %d (vocab_size %d)", prompts[i], e->cfg.vocab_size);
     if (n_requests > (size_t)INT32_MAX / 5) return fail(Q3_ERR_ARG, "more than 2^31 / 5 requests in one call");
+    if (e->bias.n_lists() > 1 && e->bias.n_lists() != n_requests)
+        return fail(Q3_ERR_ARG, "q3_logit_bias_set holds %zu lists, one per request, and the call has %zu requests", e->bias.n_lists(), n_requests);
     for (size_t r = 0; draw && r < n_requests; ++r)
         if ((rc = sampler_check(temperature[r], topp[r], (long)r))) return rc;
     rq.prompts = prompts;
@@ -164,9 +166,10 @@ int cols_prepare(q3_engine* e, const char* who, bool draw = false) {
 // the key of the column plan a pass of n live columns runs: the narrowest width that holds it.  draw: the sampled plan of that
 // width (cols_draw_alloc has run by the time it is built: its launches carry the buffers allocated there).
 // lp: the q3_gen_logprobs value a q3_generate_many_* loop runs under (-1 off, 0 records, > 0 records and top): the plan's third axis.
-// pen: the loop runs under a non-zero q3_sampler_penalties (section 2p): the plan's fourth axis.
+// pen: kPenOn, the loop runs under a non-zero q3_sampler_penalties (section 2p); kPenAdj, under a table of q3_logit_bias_set (section
+// 2q), with or without penalties: the plan's fourth axis (q3_engine::pen_form).
 // Every other caller keeps the plans without records and without penalties.
-PlanKey cols_key(int n, bool draw, int lp = -1, bool pen = false) {
+PlanKey cols_key(int n, bool draw, int lp = -1, int pen = kPenOff) {
     return PlanKey{PlanKind::Cols, kColsWidths[cols_width_index(n)], draw, false, lp < 0 ? kGenlpOff : (lp == 0 ? kGenlpRecs : kGenlpTop), pen};
 }
 
@@ -380,9 +383,10 @@ struct ColsJobSampler {                 // the sampler side of a job (draw)
 // pads of every pass (they repeat the pass's last live column and emit nothing), then the whole job on the stream: the only
 // uploads of the call are the table, the run table, the prompts and the per-request sampler parameters; one synchronisation.
 // lp >= 0 (the generate loops under q3_gen_logprobs): the passes run the plans with records, which fill the call's n_out records.
-// pen (the generate loops under a non-zero q3_sampler_penalties): the passes run the plans under penalties.
+// pen (the generate loops under a non-zero q3_sampler_penalties, or kPenAdj under a table of q3_logit_bias_set, whose bias_call_begin
+// has run): the passes run the plans of that form.
 int cols_job_run(q3_engine* e, ColsJob& job, bool draw, const ColsJobSampler& smp, const int32_t* prompts, size_t n_prompt, int32_t* out_tokens, size_t n_out,
-                 int lp = -1, bool pen = false) {
+                 int lp = -1, int pen = kPenOff) {
     int rc;
     BatchCtx* b = e->batch;
     const size_t n_passes = job.ncols.size();
@@ -575,7 +579,9 @@ int cols_generate(q3_engine* e, const ColsRequests& rq, int32_t* out_tokens, q3_
         return rc;
     if (draw && (rc = cols_draw_alloc(e))) return rc;        // the loop's per-slot sampler states are allocated there
     const ColsJobSampler smp{b->cols_slot_samp, rq.temperature, rq.topp, rq.seeds, n_requests, false};
-    if ((rc = cols_job_run(e, job, draw, smp, rq.prompts, rq.n_prompt, out_tokens, rq.n_out, e->gen_logprobs, e->pen_on()))) return rc;
+    const int pen = e->pen_form();
+    if (pen == kPenAdj && (rc = bias_call_begin(e, rq.o_off.data(), n_requests, rq.n_out))) return rc;     // the call's table, on the stream in front of its passes
+    if ((rc = cols_job_run(e, job, draw, smp, rq.prompts, rq.n_prompt, out_tokens, rq.n_out, e->gen_logprobs, pen))) return rc;
     if (stats) *stats = s.stats;
     if (dstats) *dstats = dst;
     return Q3_OK;
@@ -719,8 +725,9 @@ int q3_sampler_penalties(q3_engine* e, float presence, float frequency) {
     // a batched state that is not there yet gets the penalty state from the first generate call that runs under the setting
     int rc = Q3_OK;
     if (e->batch && e->batch->has_kv) {
-        if (e->batch->pen_ctl) rc = pen_ctl_upload(e);
-        else if (e->pen_on()) rc = pen_alloc(e);
+        // (the rows, keys and setting may stand there without counts: a table of section 2q made them)
+        if (e->pen_on()) rc = pen_alloc(e);
+        if (!rc && e->batch->pen_ctl) rc = pen_ctl_upload(e);
     }
     if (rc) { e->pen_presence = p0; e->pen_frequency = f0; }
     return rc;
@@ -731,6 +738,28 @@ int q3_sampler_get_penalties(const q3_engine* e, float* presence, float* frequen
     if (!e || !presence || !frequency) return fail(Q3_ERR_ARG, "null argument");
     *presence = e->pen_presence;
     *frequency = e->pen_frequency;
+    return Q3_OK;
+}
+
+/* ---- section 2q: logit bias, banned and allowed tokens ---- */
+
+int q3_logit_bias_set(q3_engine* e, const q3_bias_entry* entries, const size_t* n_entries, const uint8_t* mode, size_t n_lists) {
+    g_err[0] = 0;
+    BiasTable t;
+    if (int rc = bias_check(entries, n_entries, mode, n_lists, -1, t)) return rc;
+    if (!e) return fail(Q3_ERR_ARG, "null engine");
+    if (int rc = bias_check(entries, n_entries, mode, n_lists, (long)e->cfg.vocab_size, t)) return rc;
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    e->bias = std::move(t);
+    return Q3_OK;
+}
+
+int q3_logit_bias_get(const q3_engine* e, size_t* n_lists, size_t* n_entries_total) {
+    g_err[0] = 0;
+    if (!e || !n_lists || !n_entries_total) return fail(Q3_ERR_ARG, "null argument");
+    *n_lists = e->bias.n_lists();
+    *n_entries_total = e->bias.entries.size();
     return Q3_OK;
 }
 

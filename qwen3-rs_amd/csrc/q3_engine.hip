@@ -45,6 +45,7 @@
 #include "q3_topk.h"
 #include "q3_genlp.h"
 #include "q3_penalty.h"
+#include "q3_bias.h"
 #include "q3_lookup.h"
 
 namespace {
@@ -82,6 +83,62 @@ int penalties_check(float presence, float frequency) {
     const auto ok = [](float v) { return v >= -2.0f && v <= 2.0f; };      // false for a NaN
     if (ok(presence) && ok(frequency)) return Q3_OK;
     return fail(Q3_ERR_ARG, "penalties (%g, %g) out of range: finite values in -2 .. 2", (double)presence, (double)frequency);
+}
+
+// The table of q3_logit_bias_set as the engine keeps it (section 2q): the lists one behind the other, each sorted by token.
+struct BiasTable {
+    std::vector<BiasEntry> entries;
+    std::vector<unsigned> off;           // [n_lists + 1]; empty: no table
+    std::vector<unsigned char> modes;    // [n_lists]
+    size_t n_lists() const { return modes.size(); }
+};
+static_assert(sizeof(BiasEntry) == sizeof(q3_bias_entry) && sizeof(BiasEntry) == 12, "BiasEntry is q3_bias_entry");
+
+// What q3_logit_bias_set and q3_op_logit_bias refuse about a table, the engine and the GPU untouched: a null array with a non-zero
+// count, a list of more than kBiasMax entries, a negative token, a bias that is NaN, +inf or finite outside [-100, 100], a mode other
+// than 0 or 1, a token twice in one list, an ALLOW list with no finite bias.  vocab >= 0, the checks that need a model: a token >=
+// vocab, an ADD list that bans every token.  On success `out` holds the table, every list sorted by token.
+int bias_check(const q3_bias_entry* entries, const size_t* n_entries, const uint8_t* mode, size_t n_lists, long vocab, BiasTable& out) {
+    out = BiasTable{};
+    if (n_lists == 0) return Q3_OK;
+    if (!n_entries) return fail(Q3_ERR_ARG, "null n_entries with %zu lists", n_lists);
+    if (n_lists > (size_t)INT32_MAX) return fail(Q3_ERR_ARG, "more than 2^31 lists");
+    size_t total = 0;
+    for (size_t i = 0; i < n_lists; ++i) {
+        if (n_entries[i] > (size_t)kBiasMax) return fail(Q3_ERR_ARG, "list %zu: %zu entries, at most %d", i, n_entries[i], kBiasMax);
+        if (mode && mode[i] != kBiasAdd && mode[i] != kBiasAllow) return fail(Q3_ERR_ARG, "list %zu: mode %d is neither ADD (0) nor ALLOW (1)", i, (int)mode[i]);
+        total += n_entries[i];
+    }
+    if (total > 0 && !entries) return fail(Q3_ERR_ARG, "null entries with %zu of them", total);
+    out.entries.resize(total);
+    out.off.resize(n_lists + 1);
+    out.modes.resize(n_lists);
+    size_t at = 0;
+    for (size_t i = 0; i < n_lists; ++i) {
+        const size_t n = n_entries[i];
+        out.off[i] = (unsigned)at;
+        out.modes[i] = mode ? mode[i] : (unsigned char)kBiasAdd;
+        size_t finite = 0, banned = 0;
+        for (size_t k = 0; k < n; ++k) {
+            const q3_bias_entry& x = entries[at + k];
+            if (x.token < 0) return fail(Q3_ERR_ARG, "list %zu: negative token %d", i, x.token);
+            if (vocab >= 0 && x.token >= vocab) return fail(Q3_ERR_ARG, "index out of range: list %zu token %d (vocab_size %ld)", i, x.token, vocab);
+            const bool ninf = x.bias == -INFINITY;
+            if (!ninf && !(x.bias >= -100.0f && x.bias <= 100.0f))      // false for a NaN
+                return fail(Q3_ERR_ARG, "list %zu token %d: bias %g is neither -inf nor a finite value in -100 .. 100", i, x.token, (double)x.bias);
+            if (ninf) ++banned; else ++finite;
+            out.entries[at + k] = BiasEntry{x.token, x.bias, x.until};
+        }
+        std::sort(out.entries.begin() + at, out.entries.begin() + at + n, [](const BiasEntry& a, const BiasEntry& b) { return a.token < b.token; });
+        for (size_t k = 1; k < n; ++k)
+            if (out.entries[at + k].token == out.entries[at + k - 1].token)
+                return fail(Q3_ERR_ARG, "list %zu: token %d twice", i, out.entries[at + k].token);
+        if (out.modes[i] == kBiasAllow && finite == 0) return fail(Q3_ERR_ARG, "list %zu: an ALLOW list without a finite bias allows no token", i);
+        if (out.modes[i] == kBiasAdd && vocab >= 0 && banned >= (size_t)vocab) return fail(Q3_ERR_ARG, "list %zu bans every token of the vocabulary", i);
+        at += n;
+    }
+    out.off[n_lists] = (unsigned)at;
+    return Q3_OK;
 }
 
 constexpr int32_t kMagic = 0x616a6331;   // configuration.rs:8
@@ -382,6 +439,11 @@ struct q3_engine {
     // memory, in the batched state (pen_alloc, q3_cols_host.inc), where every pass under the setting reads them
     float pen_presence = 0.0f, pen_frequency = 0.0f;
     bool pen_on() const { return pen_presence != 0.0f || pen_frequency != 0.0f; }
+    // logit bias, banned and allowed tokens (q3_logit_bias_set, section 2q): engine-wide, no list = off.  Every generate call under a
+    // table sends it to the device (bias_call_begin, q3_plan_host.inc)
+    BiasTable bias;
+    // the form of the column plans the q3_generate_many_* loops run (PlanKey::pen): under a table the adjusted one, whatever the penalties
+    int pen_form() const { return bias.n_lists() ? kPenAdj : (pen_on() ? kPenOn : kPenOff); }
     int enqueue_sample();
 
     int load(const char* path, uint32_t ctx_len);
@@ -1931,6 +1993,50 @@ int q3_op_penalize(const float* logits, const uint32_t* counts, size_t n, float 
     a.n = (int)n;
     a.max_streams = 1;
     if ((rc = launch_now(0, k_pen_apply, dim3(kPenSlices, 1), dim3(kPenThreads), 0, a)) || (rc = op_end())) return rc;
+    unsigned long long keys[kPenSlices], best = 0ull;
+    HIP_TRY(hipMemcpy(out, dout.p, 4 * n, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(keys, dkeys.p, sizeof keys, hipMemcpyDeviceToHost));
+    for (int i = 0; i < kPenSlices; ++i) best = std::max(best, keys[i]);
+    *argmax = (int32_t)(best & 0xffffffffull);
+    return Q3_OK;
+}
+
+int q3_op_logit_bias(const float* logits, size_t n, const q3_bias_entry* entries, size_t n_entries, int mode, uint32_t g, const uint32_t* counts,
+                     float presence, float frequency, float* out, int32_t* argmax, int device) {
+    g_err[0] = 0;
+    int rc;
+    if (mode != kBiasAdd && mode != kBiasAllow) return fail(Q3_ERR_ARG, "mode %d is neither ADD (0) nor ALLOW (1)", mode);
+    if ((rc = penalties_check(presence, frequency))) return rc;
+    if (!logits || !out || !argmax || n == 0) return fail(Q3_ERR_ARG, "null argument");
+    if (n > (size_t)INT32_MAX) return fail(Q3_ERR_ARG, "more than 2^31 logits");
+    BiasTable t;
+    const uint8_t m = (uint8_t)mode;
+    if ((rc = bias_check(entries, &n_entries, &m, 1, (long)n, t))) return rc;
+    if ((rc = op_begin(device))) return rc;
+    OpBuf dl, dc, dout, dkeys, dpen, dent, doff, dmode, dctl;
+    const PenCtl hp{presence, frequency};
+    if ((rc = dl.upload(logits, 4 * n)) || (rc = dout.alloc(4 * n)) || (rc = dkeys.alloc(8 * (size_t)kPenSlices)) || (rc = dpen.upload(&hp, sizeof(hp))) ||
+        (rc = dent.upload(t.entries.data(), sizeof(BiasEntry) * t.entries.size())) || (rc = doff.upload(t.off.data(), 4 * t.off.size())) ||
+        (rc = dmode.upload(t.modes.data(), 1)) || (counts && (rc = dc.upload(counts, 4 * n))))
+        return rc;
+    BiasCtl h{};
+    h.entries = dent.as<BiasEntry>();
+    h.list_off = doff.as<unsigned>();
+    h.modes = dmode.as<unsigned char>();
+    h.counts = counts ? dc.as<unsigned>() : nullptr;
+    h.n_lists = 1;
+    h.n_requests = 1;
+    h.g_op = g;
+    if ((rc = dctl.upload(&h, sizeof(h)))) return rc;
+    // one row, emitting, request 0 at output g, the counts as given: k_bias_apply without a pass (PenArgs::cols null)
+    PenArgs a{};
+    a.logits = dl.as<float>();
+    a.pen_logits = dout.as<float>();
+    a.pen_slots = dkeys.as<unsigned long long>();
+    a.ctl = dpen.as<PenCtl>();
+    a.n = (int)n;
+    a.max_streams = 1;
+    if ((rc = launch_now(0, k_bias_apply, dim3(kPenSlices, 1), dim3(kPenThreads), 0, a, (const BiasCtl*)dctl.as<BiasCtl>())) || (rc = op_end())) return rc;
     unsigned long long keys[kPenSlices], best = 0ull;
     HIP_TRY(hipMemcpy(out, dout.p, 4 * n, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(keys, dkeys.p, sizeof keys, hipMemcpyDeviceToHost));

@@ -123,8 +123,7 @@ __global__ __launch_bounds__(kPenThreads) void k_pen_apply(const PenArgs a) {
 
 // one workgroup of kColsMax threads, a thread per column, in front of the turn kernel: the token an emitting column is about to
 // commit enters its slot's counts.  A pass has at most one emitting column per slot, so plain loads and stores do.
-__global__ __launch_bounds__(64) void k_pen_count(const PenArgs a) {
-    const int j = threadIdx.x;
+__device__ __forceinline__ void pen_count_column(const PenArgs& a, int j) {
     if (j >= kColsMax || !pen_emits(a.cols, j)) return;
     unsigned long long best;
     if (a.draw) {
@@ -139,5 +138,7 @@ __global__ __launch_bounds__(64) void k_pen_count(const PenArgs a) {
     const int kv = min(max(a.col_slot[j], 0), a.max_streams - 1);
     a.counts[(size_t)kv * (size_t)a.n + (size_t)token] += 1u;
 }
+
+__global__ __launch_bounds__(64) void k_pen_count(const PenArgs a) { pen_count_column(a, threadIdx.x); }
 
 }  // namespace q3

@@ -136,31 +136,42 @@ int record_launches(const RecordArgs& a, const Src& src, int rows, Put&& put) {
 }
 
 // ---- the penalty state (q3_penalty.h, section 2p): what a plan under penalties points at, made here and nowhere else: on first use,
-// at its full size, and never again while the context lives -- so a captured plan's pointers hold whatever call comes next.  One
-// group, committed whole.  The counts need no clearing: a request's first output clears its slot's.  The setting goes to the device
-// with it; q3_sampler_penalties rewrites that word alone.
+// at its full size, and never again while the context lives -- so a captured plan's pointers hold whatever call comes next.  Two
+// groups, each committed whole: the rows, their keys and the setting (adj_alloc), which a table of section 2q needs too, and the
+// counts on top (pen_alloc), which only penalties need.  The counts need no clearing: a request's first output clears its slot's.
+// The setting goes to the device with the first group; q3_sampler_penalties rewrites that word alone.
 int pen_ctl_upload(q3_engine* e) {
     const PenCtl h{e->pen_presence, e->pen_frequency};
     HIP_TRY(hipMemcpy(e->batch->pen_ctl, &h, sizeof(PenCtl), hipMemcpyHostToDevice));
     return Q3_OK;
 }
-int pen_alloc(q3_engine* e) {
+// the rows, their slices' keys and the setting: what a table without penalties needs of it (section 2q), and no counts
+int adj_alloc(q3_engine* e) {
     BatchCtx* b = e->batch;
     if (b->pen_ctl) return Q3_OK;
     int rc;
     HIP_TRY(hipSetDevice(e->device));
     const size_t V = (size_t)e->cfg.vocab_size;
-    DevMem<unsigned> counts; DevMem<float> rows; DevMem<unsigned long long> keys; DevMem<PenCtl> ctl;
-    if ((rc = counts.alloc((size_t)b->max_streams * V)) || (rc = rows.alloc((size_t)kColsMax * V)) || (rc = keys.alloc((size_t)kColsMax * kPenSlices)) ||
-        (rc = ctl.alloc(1)))
-        return rc;
+    DevMem<float> rows; DevMem<unsigned long long> keys; DevMem<PenCtl> ctl;
+    if ((rc = rows.alloc((size_t)kColsMax * V)) || (rc = keys.alloc((size_t)kColsMax * kPenSlices)) || (rc = ctl.alloc(1))) return rc;
     HIP_TRY(hipMemsetAsync(keys, 0, 8 * (size_t)kColsMax * kPenSlices, e->stream));
-    b->pen_counts = std::move(counts); b->pen_logits = std::move(rows); b->pen_slots = std::move(keys); b->pen_ctl = std::move(ctl);
+    b->pen_logits = std::move(rows); b->pen_slots = std::move(keys); b->pen_ctl = std::move(ctl);
     if (b->draw_cols) draw_args_pen(b->draw_cols, b->pen_logits);
     return pen_ctl_upload(e);
 }
-// The arguments of k_pen_apply and k_pen_count over the pass in flight (pen_alloc has run; nothing is written here).  draw: the plan
-// is a sampled one, whose columns carry a mode
+int pen_alloc(q3_engine* e) {
+    BatchCtx* b = e->batch;
+    if (b->pen_counts) return Q3_OK;
+    int rc;
+    if ((rc = adj_alloc(e))) return rc;
+    DevMem<unsigned> counts;
+    if ((rc = counts.alloc((size_t)b->max_streams * (size_t)e->cfg.vocab_size))) return rc;
+    b->pen_counts = std::move(counts);
+    return Q3_OK;
+}
+// The arguments of k_pen_apply and k_pen_count over the pass in flight (pen_alloc has run; nothing is written here), and of
+// k_bias_apply and k_bias_count (bias_alloc has run: counts may be null here, those two take the counts from BiasCtl).  draw: the
+// plan is a sampled one, whose columns carry a mode
 PenArgs pen_args(const q3_engine* e, bool draw) {
     const BatchCtx* b = e->batch;
     PenArgs a{};
@@ -176,6 +187,49 @@ PenArgs pen_args(const q3_engine* e, bool draw) {
     a.n = e->cfg.vocab_size;
     a.max_streams = b->max_streams;
     return a;
+}
+
+// ---- the table of q3_logit_bias_set on the device (q3_bias.h, section 2q).  bias_alloc: what a plan of the adjusted form points at,
+// made once -- the rows and keys it shares with the penalties, and the control block.  bias_call_begin: every generate call under a
+// table, on the stream in front of its passes: the lists, their offsets and modes, the call's o_off with n_out behind it, the counts
+// where penalties are set (null otherwise: none is allocated or read), and the control block that names them all.
+int bias_alloc(q3_engine* e) {
+    BatchCtx* b = e->batch;
+    int rc;
+    if ((rc = adj_alloc(e))) return rc;
+    if (b->bias_ctl) return Q3_OK;
+    DevMem<BiasCtl> ctl;
+    if ((rc = ctl.alloc(1))) return rc;
+    HIP_TRY(hipMemsetAsync(ctl, 0, sizeof(BiasCtl), e->stream));
+    b->bias_ctl = std::move(ctl);
+    return Q3_OK;
+}
+int bias_call_begin(q3_engine* e, const int* o_off, size_t n_requests, size_t n_out_total) {
+    BatchCtx* b = e->batch;
+    const BiasTable& t = e->bias;
+    int rc;
+    const size_t n_lists = t.n_lists(), n_ent = t.entries.size();
+    if ((rc = bias_alloc(e))) return rc;
+    if (e->pen_on() && (rc = pen_alloc(e))) return rc;
+    if ((rc = b->bias_entries.grow(std::max<size_t>(n_ent, 1), e->stream)) || (rc = b->bias_off.grow(n_lists + 1, e->stream)) ||
+        (rc = b->bias_modes.grow(n_lists, e->stream)) || (rc = b->bias_ooff.grow(n_requests + 1, e->stream)))
+        return rc;
+    const int n_out = (int)n_out_total;
+    if (n_ent) HIP_TRY(hipMemcpyAsync(b->bias_entries, t.entries.data(), sizeof(BiasEntry) * n_ent, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(b->bias_off, t.off.data(), 4 * (n_lists + 1), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(b->bias_modes, t.modes.data(), n_lists, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(b->bias_ooff, o_off, 4 * n_requests, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(b->bias_ooff + n_requests, &n_out, 4, hipMemcpyHostToDevice, e->stream));
+    BiasCtl h{};
+    h.entries = b->bias_entries;
+    h.list_off = b->bias_off;
+    h.modes = b->bias_modes;
+    h.o_off = b->bias_ooff;
+    h.counts = e->pen_on() ? (unsigned*)b->pen_counts : nullptr;
+    h.n_lists = (int)n_lists;
+    h.n_requests = (int)n_requests;
+    HIP_TRY(hipMemcpyAsync(b->bias_ctl, &h, sizeof(BiasCtl), hipMemcpyHostToDevice, e->stream));
+    return Q3_OK;
 }
 
 // ---- the builder: the launches of key.n streams (Decode), block positions (Prefill, Verify; draw: Verify under the sampler),
@@ -499,8 +553,13 @@ struct PlanBuilder {
         }, key.pen);
     }
     // the penalised rows of the emitting columns and their slices' largest keys, behind the classifier (pen_alloc has run)
+    // (kPenAdj: the adjusted rows of section 2q in their place, bias_alloc has run)
     int penalize() {
         if (!b->pen_ctl) return fail(Q3_ERR_INTERNAL, "a plan under penalties before pen_alloc");
+        if (key.pen == kPenAdj) {
+            if (!b->bias_ctl) return fail(Q3_ERR_INTERNAL, "a plan of the adjusted form before bias_alloc");
+            return add(F_NEXT, k_bias_apply, dim3(kPenSlices, (unsigned)n), dim3(kPenThreads), 0, pen_args(e, key.draw), (const BiasCtl*)b->bias_ctl);
+        }
         return add(F_NEXT, k_pen_apply, dim3(kPenSlices, (unsigned)n), dim3(kPenThreads), 0, pen_args(e, key.draw));
     }
 
@@ -510,7 +569,7 @@ struct PlanBuilder {
         if (!b->genlp_ctl) return fail(Q3_ERR_INTERNAL, "a plan with records before genlp_alloc");
         RecordArgs a;
         if (int rc = record_args(e, key.genlp == kGenlpTop, nslots_used, kScoreTopParts, a)) return rc;
-        const PassRows src{b->cols_ctl, key.draw ? (const ColsDraw*)b->cols_draw : nullptr, b->st, b->genlp_ctl, key.pen ? 1 : 0};
+        const PassRows src{b->cols_ctl, key.draw ? (const ColsDraw*)b->cols_draw : nullptr, b->st, b->genlp_ctl, key.pen != kPenOff ? 1 : 0};
         return record_launches(a, src, n, [&](bool, auto kernel, dim3 grid, dim3 blk, const RecordArgs& ra, const PassRows& rs) {
             return add(F_NEXT, kernel, grid, blk, 0, ra, rs);
         });
@@ -540,7 +599,8 @@ struct PlanBuilder {
             if (key.draw && (rc = draw_columns())) return rc;
             if (key.pen && key.genlp && !key.draw && (rc = colmax())) return rc;
             if (key.genlp && (rc = gen_logprobs())) return rc;
-            if (key.pen && (rc = add(F_NEXT, k_pen_count, dim3(1), dim3(64), 0, pen_args(e, key.draw)))) return rc;
+            if (key.pen == kPenOn && (rc = add(F_NEXT, k_pen_count, dim3(1), dim3(64), 0, pen_args(e, key.draw)))) return rc;
+            if (key.pen == kPenAdj && (rc = add(F_NEXT, k_bias_count, dim3(1), dim3(64), 0, pen_args(e, key.draw), (const BiasCtl*)b->bias_ctl))) return rc;
             if (!key.draw && key.pen) return add(F_NEXT, k_cols_turn, dim3(1), dim3(kWG), 0, b->cols_ctl, b->pen_slots, kPenSlices, kPenSlices, b->st, b->col_slot);
             if (!key.draw) return add(F_NEXT, k_cols_turn, dim3(1), dim3(kWG), 0, b->cols_ctl, b->slots, b->nslots, nslots_used, b->st, b->col_slot);
             return add(F_NEXT, k_cols_turn_draw, dim3(1), dim3(kWG), 0, b->cols_ctl, b->cols_draw, b->draw_cols.ss, b->st, b->col_slot);
@@ -597,10 +657,11 @@ int plan_get(q3_engine* e, PlanKey key, Plan** out) {
     bool hit;
     // the engine's top_k holds wherever the plan draws: the sampled Verify and Cols plans, and the Decode plan under the batch sampler
     key.topk = e->top_k > 0 && (key.draw || (key.kind == PlanKind::Decode && b->sampling));
-    if (key.kind != PlanKind::Cols) { key.genlp = kGenlpOff; key.pen = false; }
+    if (key.kind != PlanKind::Cols) { key.genlp = kGenlpOff; key.pen = kPenOff; }
     if (key.genlp < kGenlpOff || key.genlp >= kGenlpForms) return fail(Q3_ERR_INTERNAL, "plan form %d", key.genlp);
+    if (key.pen < kPenOff || key.pen >= kPenForms) return fail(Q3_ERR_INTERNAL, "plan form %d", key.pen);
     if (key.kind == PlanKind::Cols) {
-        home = &b->cols_plans[key.pen ? 1 : 0][key.genlp][key.draw ? (key.topk ? 2 : 1) : 0][cols_width_index(key.n)];
+        home = &b->cols_plans[key.pen][key.genlp][key.draw ? (key.topk ? 2 : 1) : 0][cols_width_index(key.n)];
         hit = !home->launches.empty();
     } else if (key.kind == PlanKind::SlotPrefill) {
         if (key.n <= kColsMax || key.n > b->dense.cap)
@@ -617,7 +678,7 @@ int plan_get(q3_engine* e, PlanKey key, Plan** out) {
             if (int rc = record_scratch(e, key.genlp == kGenlpTop)) return rc;
         // ... and so does the penalty state a plan under penalties points at
         if (key.pen)
-            if (int rc = pen_alloc(e)) return rc;
+            if (int rc = key.pen == kPenAdj ? bias_alloc(e) : pen_alloc(e)) return rc;
         Plan built;
         if (int rc = batch_build_plan(e, key, built)) return rc;
         if (key.kind == PlanKind::SlotPrefill) home = &b->dense_plans[key.n];

@@ -38,6 +38,8 @@ int cols_generate_stop(q3_engine* e, const ColsRequests& rq, const int32_t* stop
     if ((rc = b->cols_prompts.grow(rq.n_prompt, e->stream))) return rc;
     if ((rc = b->cols_out.grow(rq.n_out, e->stream))) return rc;
     if (lp >= 0 && (rc = genlp_call_begin(e, lp, rq.n_out))) return rc;
+    const int pen = e->pen_form();
+    if (pen == kPenAdj && (rc = bias_call_begin(e, rq.o_off.data(), n_requests, rq.n_out))) return rc;     // the call's table (section 2q)
 
     // uploaded once: the prompts, the per-request records, the sampler parameters, the scheduler state with the stop list
     int* dreq = b->cols_req;
@@ -84,7 +86,7 @@ int cols_generate_stop(q3_engine* e, const ColsRequests& rq, const int32_t* stop
         if (hs->n_live < 1 || hs->n_live > kColsMax) return fail(Q3_ERR_INTERNAL, "the scheduler laid out a pass of %d columns", hs->n_live);
         if (++passes > pass_cap) return fail(Q3_ERR_INTERNAL, "the scheduler asks for more than %zu passes", pass_cap);
         Plan* plan;                                        // built on first use of a width: the stream is idle here
-        if ((rc = plan_get(e, cols_key(hs->n_live, draw, lp, e->pen_on()), &plan))) return rc;
+        if ((rc = plan_get(e, cols_key(hs->n_live, draw, lp, pen), &plan))) return rc;
         if ((rc = plan_enqueue(e, *plan))) return rc;      // ends with the turn kernel: cursor == n_passes, it commits and sets nothing up
     }
     std::vector<int> got(n_requests);

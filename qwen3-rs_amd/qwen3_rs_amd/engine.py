@@ -38,8 +38,13 @@ EXPORTED_SYMBOLS = [
     "q3_sampler_top_k", "q3_sampler_get_top_k", "q3_op_sample_top_k",
     "q3_gen_logprobs", "q3_gen_logprobs_get", "q3_gen_logprobs_read",
     "q3_sampler_penalties", "q3_sampler_get_penalties", "q3_op_penalize",
+    "q3_logit_bias_set", "q3_logit_bias_get", "q3_op_logit_bias",
 ]
 PENALTY_MAX = 2.0        # |presence|, |frequency| <= 2 (section 2p)
+BIAS_MAX = 4096          # Q3_BIAS_MAX: entries per list (section 2q)
+BIAS_LIMIT = 100.0       # a finite bias lies in -100 .. 100; -inf bans
+BIAS_ADD, BIAS_ALLOW = 0, 1
+BIAS_DTYPE = np.dtype([("token", np.int32), ("bias", np.float32), ("until", np.uint32)])     # q3_bias_entry
 VERIFY_MAX = 32          # Q3_VERIFY_MAX
 COLS_MAX = 32            # Q3_COLS_MAX
 STOP_MAX = 8             # Q3_STOP_MAX
@@ -302,8 +307,74 @@ def _bind(path: str) -> C.CDLL:
     L.q3_sampler_penalties.argtypes = [C.c_void_p, C.c_float, C.c_float]
     L.q3_sampler_get_penalties.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.q3_op_penalize.argtypes = [fp, C.POINTER(C.c_uint32), sz, C.c_float, C.c_float, fp, C.POINTER(C.c_int32), C.c_int]
+    L.q3_logit_bias_set.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_uint8), sz]
+    L.q3_logit_bias_get.argtypes = [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    L.q3_op_logit_bias.argtypes = [fp, sz, C.c_void_p, sz, C.c_int, C.c_uint32, C.POINTER(C.c_uint32), C.c_float, C.c_float, fp, C.POINTER(C.c_int32),
+                                   C.c_int]
     _libs[path] = L
     return L
+
+
+def _check_bias_list(entries, mode=BIAS_ADD, who="list"):
+    """One list of q3_logit_bias_set / q3_op_logit_bias as the library accepts it, checked before the call: a dict {token: bias} or a
+    sequence of (token, bias) / (token, bias, until).  Returns [(token, bias, until)] sorted by token."""
+    if isinstance(mode, bool) or not isinstance(mode, (int, np.integer)):
+        raise TypeError(f"{who}: mode must be BIAS_ADD (0) or BIAS_ALLOW (1), got {mode!r}")
+    if mode not in (BIAS_ADD, BIAS_ALLOW):
+        raise ValueError(f"{who}: mode {mode} is neither BIAS_ADD (0) nor BIAS_ALLOW (1)")
+    if isinstance(entries, (str, bytes)) or not hasattr(entries, "__iter__"):
+        raise TypeError(f"{who}: a dict {{token: bias}} or a sequence of (token, bias[, until]), got {entries!r}")
+    items = [(k, v, 0) for k, v in entries.items()] if isinstance(entries, dict) else [tuple(x) if hasattr(x, "__iter__") else x for x in entries]
+    out, seen = [], set()
+    for x in items:
+        if not isinstance(x, tuple) or len(x) not in (2, 3):
+            raise TypeError(f"{who}: an entry is (token, bias) or (token, bias, until), got {x!r}")
+        token, bias, until = x if len(x) == 3 else (x[0], x[1], 0)
+        if isinstance(token, bool) or not isinstance(token, (int, np.integer)):
+            raise TypeError(f"{who}: token must be an integer, got {token!r}")
+        if isinstance(until, bool) or not isinstance(until, (int, np.integer)):
+            raise TypeError(f"{who}: until must be an integer, got {until!r}")
+        if isinstance(bias, bool) or not isinstance(bias, (int, float, np.integer, np.floating)):
+            raise TypeError(f"{who}: bias must be a number, got {bias!r}")
+        if token < 0 or token > 0x7fffffff:
+            raise ValueError(f"{who}: token {token} out of range")
+        if until < 0 or until > 0xffffffff:
+            raise ValueError(f"{who}: until {until} out of range")
+        with np.errstate(over="ignore"):
+            f = np.float32(bias)
+        if not (f == -np.inf or abs(f) <= np.float32(BIAS_LIMIT)):        # false for a NaN and for +inf
+            raise ValueError(f"{who}: bias {bias} of token {token} is neither -inf nor finite in -{BIAS_LIMIT}..{BIAS_LIMIT}")
+        if int(token) in seen:
+            raise ValueError(f"{who}: token {token} twice")
+        seen.add(int(token))
+        out.append((int(token), float(f), int(until)))
+    if len(out) > BIAS_MAX:
+        raise ValueError(f"{who}: {len(out)} entries, at most {BIAS_MAX}")
+    if mode == BIAS_ALLOW and not any(np.isfinite(b) for _, b, _ in out):
+        raise ValueError(f"{who}: an ALLOW list without a finite bias allows no token")
+    return sorted(out)
+
+
+def _check_bias_table(lists, modes):
+    """(lists, modes) of Transformer.set_logit_bias, checked and normalised: per list [(token, bias, until)], per list a mode"""
+    if isinstance(lists, (dict, str, bytes)) or not hasattr(lists, "__iter__"):
+        raise TypeError(f"lists must be a sequence of lists (one for all requests, or one per request), got {lists!r}")
+    lists = list(lists)
+    if modes is None:
+        modes = [BIAS_ADD] * len(lists)
+    if isinstance(modes, (str, bytes)) or not hasattr(modes, "__iter__"):
+        raise TypeError(f"modes must be None or one mode per list, got {modes!r}")
+    modes = list(modes)
+    if len(modes) != len(lists):
+        raise ValueError(f"{len(lists)} lists and {len(modes)} modes")
+    return [_check_bias_list(l, m, f"list {i}") for i, (l, m) in enumerate(zip(lists, modes))], [int(m) for m in modes]
+
+
+def _bias_array(entries):
+    a = np.zeros(len(entries), dtype=BIAS_DTYPE)
+    for i, (token, bias, until) in enumerate(entries):
+        a[i] = (token, bias, until)
+    return a
 
 
 def _check_penalties(presence, frequency):
@@ -922,6 +993,32 @@ class Transformer:
         _check(self._lib.q3_sampler_get_penalties(self._h, C.byref(p), C.byref(f)))
         return float(p.value), float(f.value)
 
+    # ---- logit bias, banned and allowed tokens (include/qwen3_hip.h section 2q)
+    def set_logit_bias(self, lists, modes=None):
+        """The table of every generate_many_* call (q3_logit_bias_set).  lists: [] turns it off (the default); one list holds for every
+        request of every call; several, list r belongs to request r and a call with another number of requests raises.  A list is a
+        dict {token: bias} or a sequence of (token, bias[, until]): an entry acts on a request's output g while until == 0 or
+        g < until; bias is added to the token's logit before the penalties, the argmax or the draw; -inf bans the token.  modes: per
+        list BIAS_ADD (unlisted tokens keep their logits; the default) or BIAS_ALLOW (unlisted tokens become -inf).  The setting is
+        the engine's: it survives set_sampler, batch_init, set_top_k, set_gen_logprobs, set_penalties and every generate_many call,
+        and it does not touch batch_step_cols, forward_batch, verify, score, choose, embed or single-stream decode."""
+        lists, modes = _check_bias_table(lists, modes)
+        flat = _bias_array([x for l in lists for x in l])
+        n = (C.c_size_t * max(len(lists), 1))(*[len(l) for l in lists])
+        m = (C.c_uint8 * max(len(lists), 1))(*modes)
+        _check(self._lib.q3_logit_bias_set(self._h, flat.ctypes.data_as(C.c_void_p) if flat.size else None, n, m, len(lists)))
+        self._logit_bias = (lists, modes)
+
+    def get_logit_bias(self):
+        """the engine's table as (lists, modes) in the form set_logit_bias takes them, every list [(token, bias, until)] sorted by token;
+        ([], []): off.  The library holds the table and tells its size (q3_logit_bias_get); the lists are the copy kept here."""
+        n_lists, n_total = C.c_size_t(0), C.c_size_t(0)
+        _check(self._lib.q3_logit_bias_get(self._h, C.byref(n_lists), C.byref(n_total)))
+        lists, modes = getattr(self, "_logit_bias", ([], []))
+        if (int(n_lists.value), int(n_total.value)) != (len(lists), sum(len(l) for l in lists)):
+            raise Q3Error(-5, "the engine's logit-bias table was not set through this object")
+        return [list(l) for l in lists], list(modes)
+
     def read_gen_logprobs(self, n_per_row=None):
         """The records of the last generate_many_* call (q3_gen_logprobs_read), which ran under set_gen_logprobs(top_n >= 0): per
         request (records, tops, ranks) -- SCORE_DTYPE[n], TOP_DTYPE[n, top_n], int32[n], entry j for the request's j-th token; tops
@@ -1181,6 +1278,33 @@ class _Ops:
         out, idx = np.empty_like(logits), C.c_int32(-1)
         _check(load_library().q3_op_penalize(self._fp(logits), counts.ctypes.data_as(C.POINTER(C.c_uint32)), logits.size, float(presence),
                                              float(frequency), self._fp(out), C.byref(idx), self.device))
+        return out, int(idx.value)
+
+    def logit_bias(self, logits, entries, mode: int = BIAS_ADD, g: int = 0, counts=None, presence: float = 0.0, frequency: float = 0.0):
+        """The adjusted row of include/qwen3_hip.h section 2q on the device (q3_op_logit_bias): the list `entries` (set_logit_bias's
+        form) under `mode` for a request's output index g, then with counts the penalties of section 2p on top.  Returns (the row as
+        float32[n], the index of its largest key)."""
+        ent = _check_bias_list(entries, mode, "entries")
+        _check_penalties(presence, frequency)
+        if isinstance(g, bool) or not isinstance(g, (int, np.integer)):
+            raise TypeError(f"g must be an integer, got {g!r}")
+        if g < 0 or g > 0xffffffff:
+            raise ValueError(f"g {g} out of range")
+        logits = np.ascontiguousarray(logits, dtype=np.float32)
+        if logits.ndim != 1 or logits.size == 0:
+            raise ValueError("logits must be a non-empty vector")
+        cp = None
+        if counts is not None:
+            counts = np.ascontiguousarray(counts, dtype=np.uint32)
+            if counts.shape != logits.shape:
+                raise ValueError("logits and counts must be vectors of one length")
+            cp = counts.ctypes.data_as(C.POINTER(C.c_uint32))
+        if any(t >= logits.size for t, _, _ in ent):
+            raise ValueError(f"a token of the list lies outside the {logits.size} logits")
+        flat = _bias_array(ent)
+        out, idx = np.empty_like(logits), C.c_int32(-1)
+        _check(load_library().q3_op_logit_bias(self._fp(logits), logits.size, flat.ctypes.data_as(C.c_void_p) if flat.size else None, len(ent), int(mode),
+                                               int(g), cp, float(presence), float(frequency), self._fp(out), C.byref(idx), self.device))
         return out, int(idx.value)
 
 

@@ -10,7 +10,7 @@ from typing import Callable, Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .engine import SCORE_DTYPE, TOP_DTYPE
+from .engine import SCORE_DTYPE, TOP_DTYPE, BIAS_ADD, BIAS_ALLOW
 
 
 def sample_argmax(logits: np.ndarray) -> int:
@@ -166,7 +166,8 @@ def common_prefix_len(prompts: Sequence[Sequence[int]]) -> int:
 
 def generate_many(transformer, prompts: Sequence[Sequence[int]], max_new_tokens: int, stop_tokens: Iterable[int] = (), sampler=None,
                   dense_min: int = 0, stop_on_device: bool = False, shared_prefix=None, logprobs: Optional[int] = None,
-                  presence_penalty: float = 0.0, frequency_penalty: float = 0.0):
+                  presence_penalty: float = 0.0, frequency_penalty: float = 0.0, logit_bias=None, banned_tokens=None, allowed_tokens=None,
+                  min_tokens=0):
     """Many greedy generations served through the slots of Transformer.batch_init in ragged column passes
     (Transformer.generate_many_greedy).  Row r holds what Transformer.prefill(prompts[r], 0) followed by generate_greedy returns on
     an engine of its own: every prompt token goes through the model (chat's prompt loop, generation.rs:116-123), then up to
@@ -198,9 +199,94 @@ def generate_many(transformer, prompts: Sequence[Sequence[int]], max_new_tokens:
     presence_penalty, frequency_penalty: -2 .. 2 (Transformer.set_penalties, set for this call and put back afterwards, also when the
     call raises): a token the row has produced c > 0 times has presence_penalty + frequency_penalty * c taken off its logit before the
     argmax or the draw, in front of temperature, top-k and top-p; prompt tokens do not count.  Works with every option above; the
-    logprobs stay those of the raw distribution."""
+    logprobs stay those of the raw distribution.
+    logit_bias, banned_tokens, allowed_tokens, min_tokens: the caller constrains which tokens may come (Transformer.set_logit_bias,
+    set for this call and put back afterwards, also when the call raises).  Each is one value for all requests or a sequence of one
+    per request.  logit_bias: {token: bias}, bias (-100 .. 100, or -inf) added to the token's logit.  banned_tokens: tokens that
+    never come.  allowed_tokens: the only tokens that may come ("answer with one of these labels").  min_tokens, with stop_tokens:
+    no stop token among a row's first min_tokens tokens (a stop token that also carries a logit_bias is a ValueError).  They act on
+    every generated token, the first included, in front of the penalties, temperature, top-k and top-p; the logprobs stay those of
+    the raw distribution.  Works with every option above.  With none of the four given the call touches no table: one set with
+    Transformer.set_logit_bias simply holds."""
     if any(len(p) == 0 for p in prompts):
         raise ValueError("Please provide a prompt")
+    args = (transformer, prompts, max_new_tokens, stop_tokens, sampler, dense_min, stop_on_device, shared_prefix, logprobs, presence_penalty,
+            frequency_penalty)
+    if logit_bias is None and banned_tokens is None and allowed_tokens is None and np.isscalar(min_tokens) and min_tokens == 0:
+        return _generate_many_pen(*args)
+    lists, modes = merge_logit_bias(len(prompts), logit_bias, banned_tokens, allowed_tokens, min_tokens, stop_tokens)
+    if len(lists) > 1:
+        # the engine sees the requests the context leaves room for, and one list for each of them
+        live = _live_requests(transformer, prompts, max_new_tokens, shared_prefix)
+        lists, modes = [lists[r] for r in live], [modes[r] for r in live]
+    bias_before = transformer.get_logit_bias()
+    transformer.set_logit_bias(lists, modes)
+    try:
+        return _generate_many_pen(*args)
+    finally:
+        transformer.set_logit_bias(*bias_before)
+
+
+def _live_requests(transformer, prompts, max_new_tokens, shared_prefix):
+    """the requests _generate_many hands to the engine: those the batch context leaves room for at least one new token"""
+    ahead = 0 if shared_prefix is None or shared_prefix is False or shared_prefix is True else len(list(shared_prefix))
+    ctx = getattr(transformer, "_batch_ctx", transformer.get_config().seq_len)
+    return [r for r, p in enumerate(prompts) if min(max_new_tokens, ctx - ahead - len(p) + 1) > 0]
+
+
+def merge_logit_bias(n_requests, logit_bias=None, banned_tokens=None, allowed_tokens=None, min_tokens=0, stop_tokens=()):
+    """generate_many's four arguments as the (lists, modes) of Transformer.set_logit_bias: one list where every argument is a single
+    value, else one per request.  Per list: logit_bias {token: bias} gives (token, bias, 0); a banned token (token, -inf, 0); with
+    allowed_tokens the mode is BIAS_ALLOW and an allowed token without an entry gets (token, 0.0, 0); min_tokens = m > 0 gives
+    (stop, -inf, m) per stop token -- skipped where the token is banned already or unlisted under BIAS_ALLOW, in place of the 0.0 of a
+    token that is merely allowed, and a ValueError where logit_bias names the token."""
+    def per_request(v, single):
+        return v is not None and not single(v)
+
+    def is_tokens(v):
+        v = list(v)
+        return all(isinstance(t, (int, np.integer)) for t in v)
+    per = {"logit_bias": per_request(logit_bias, lambda v: isinstance(v, dict)), "banned_tokens": per_request(banned_tokens, is_tokens),
+           "allowed_tokens": per_request(allowed_tokens, is_tokens), "min_tokens": not np.isscalar(min_tokens)}
+    given = {"logit_bias": logit_bias, "banned_tokens": banned_tokens, "allowed_tokens": allowed_tokens, "min_tokens": min_tokens}
+    for name, p in per.items():
+        if p:
+            given[name] = list(given[name])
+            if len(given[name]) != n_requests:
+                raise ValueError(f"{name}: {len(given[name])} values for {n_requests} requests")
+    stop = sorted(set(int(t) for t in stop_tokens))
+    lists, modes = [], []
+    for r in range(n_requests if any(per.values()) else 1):
+        at = lambda name: given[name][r] if per[name] else given[name]
+        bias, banned, allowed, m = at("logit_bias"), at("banned_tokens"), at("allowed_tokens"), at("min_tokens")
+        if bias is not None and not isinstance(bias, dict):
+            raise TypeError(f"logit_bias must be a dict {{token: bias}}, got {bias!r}")
+        if isinstance(m, bool) or not isinstance(m, (int, np.integer)):
+            raise TypeError(f"min_tokens must be an integer, got {m!r}")
+        if m < 0:
+            raise ValueError(f"min_tokens {m} is negative")
+        named = dict(bias or {})
+        ent = {t: (b, 0) for t, b in named.items()}
+        for t in (banned if banned is not None else ()):
+            ent[t] = (float("-inf"), 0)
+        if allowed is not None:
+            allowed = list(allowed)
+            for t in allowed:
+                ent.setdefault(t, (0.0, 0))
+        for t in (stop if m > 0 else ()):
+            if t in named:
+                raise ValueError(f"min_tokens: stop token {t} also carries a logit_bias")
+            if ent.get(t) == (float("-inf"), 0) or (allowed is not None and t not in ent):
+                continue
+            ent[t] = (float("-inf"), int(m))
+        lists.append([(t, b, u) for t, (b, u) in sorted(ent.items())])
+        modes.append(BIAS_ALLOW if allowed is not None else BIAS_ADD)
+    return lists, modes
+
+
+def _generate_many_pen(transformer, prompts, max_new_tokens, stop_tokens, sampler, dense_min, stop_on_device, shared_prefix, logprobs, presence_penalty,
+                       frequency_penalty):
+    """generate_many behind its logit-bias handling"""
     # (an engine stand-in without the setting serves a call without penalties as it did)
     if hasattr(transformer, "get_penalties") or presence_penalty != 0.0 or frequency_penalty != 0.0:
         pen_before = transformer.get_penalties()
