@@ -8,6 +8,10 @@ must return, and checks an engine op by op.
                                 and the request rule of the header ("row r is what a fresh engine gives after prefill + generate_greedy")
     FakeEngine                  the Transformer surface answered from Reference with explicit Python state; a switch injects a leak
     run(engine, ops, reference) executes the ops, checks outputs, untouched caches and filled rows after every op
+    make_settings_sequence(seed) the settings dimension: SETTING_KINDS -- the engine-wide settings of sections 2m to 2q (top_k,
+                                gen_logprobs, penalties, the logit-bias table), q3_gen_logprobs_read and q3_score_top_many -- among the
+                                kinds of the pair matrix; Tables derives every table from Reference alone; run() reads the records
+                                behind every loop op and the four getters behind every op
 
 Shape: small-hd128 (dim 512, 8 heads over 4 kv heads, head_dim 128, group 64, vocabulary 2,048) with 576 positions declared instead
 of 256: the score rows of the dense blocks (att_pf) are sized to the context end rounded up to 256, so on 256 positions they are
@@ -24,6 +28,7 @@ NAME = "small-hd128"
 DENSE_CAP = 2048                      # Q3_PREFILL_M as the tests leave it
 COLS_MAX = 32
 WIDTHS = (1, 2, 4, 8, 16, 32)
+SETTING_BUFFERS = ("genlp_recs", "genlp_top", "genlp_rank", "bias_entries", "bias_off", "bias_ooff", "score_top", "score_rank")
 BUFFERS = ("cols_table", "cols_ncols", "cols_prompts", "cols_out", "cols_aux", "cols_temp", "cols_topp", "cols_seeds", "cols_req",
            "dense_runs", "embed_rows", "embed_out", "att_pf", "score_rows", "score_out", "choice_cand", "choice_out")
 SCORE_COLS = 32                       # kScoreCols: the scored columns of a block go through the classifier that many at a time
@@ -86,8 +91,20 @@ def _make_catalogue():
     return cat
 
 
-CAT = _make_catalogue()
-SMALL, MEDIUM, LARGE, ONE = range(0, 12), range(12, 18), range(18, 88), range(88, 91)
+def _extend_catalogue(cat):
+    """91 .. 114, behind the 91 entries of the pair matrix so that their indices keep their meaning: the requests of the settings
+    sequences, 6 to 12 new tokens behind prompts of 2 to 40 -- long enough for a produced token to come again (a count of 2 under the
+    penalties) and for an allowed list of three tokens to force one"""
+    rng = random.Random(78)
+    temps, topps = (0.0, 0.7, 0.9, 1.1), (0.9, 0.95, 1.0, 0.0)
+    for i in range(91, 115):
+        n = (2, 40, 7, 33)[i - 91] if i < 95 else rng.randint(2, 40)
+        cat.append((i % N_BASES, n, rng.randint(6, 12), temps[(i // 2) % 4], topps[i % 4], 1000 + i))
+    return cat
+
+
+CAT = _extend_catalogue(_make_catalogue())
+SMALL, MEDIUM, LARGE, ONE, LONG = range(0, 12), range(12, 18), range(18, 88), range(88, 91), range(91, 115)
 PREFIXES = ((5, 7), (4, 37), (3, 44))          # resident prefixes: base, length (one narrow, two wide)
 DEEP = {1: (2, 300), 2: (2, 530)}              # the runs that end past 256 and past 512 positions
 
@@ -254,11 +271,24 @@ def score_chunks(op, streams):
     return out
 
 
-def needs(op, streams, sampling, prefix_len, rows=None, stop=()):
+def form_of(draw, st):
+    """(draw, topk, genlp, pen) of the column plans a loop op runs under the settings st: the plan key's four axes.  topk is on a
+    sampled plan alone (plan_get clears it on a greedy one); genlp 0 off, 1 records, 2 records + top; pen 0 off, 1 penalties, 2 the
+    adjusted form, which a table selects with or without penalties"""
+    return (bool(draw), bool(draw and st["top_k"]), 0 if st["genlp"] < 0 else 1 if st["genlp"] == 0 else 2, 2 if st["table"] is not None else 1 if any(st["pen"]) else 0)
+
+
+def needs(op, streams, sampling, prefix_len, rows=None, stop=(), st=None, table=None):
     """What an op asks of the grow-only buffers, by the sizes at the call sites of cols_job_run, cols_generate_stop, cols_sampler_upload,
     q3_embed_many, q3_choice_many and q3_score_many, and which kept plans it runs: dict(buffer -> elements), cols = {(draw, width
-    index)}, dense = {block width}; for a score op also chunk_cols, the column plans that only its classifier chunks run (not its walk)."""
+    index)}, dense = {block width}; for a score op also chunk_cols, the column plans that only its classifier chunks run (not its walk).
+    st: the settings in force (settings_walk) and table: the set_logit_bias op whose table holds -- then also the per-call buffers of
+    genlp_call_begin and bias_call_begin, the tops and ranks of q3_score_top_many, and forms = {(draw, topk, genlp, pen, width index)},
+    the column plans of a loop op by their whole key."""
     kind = op["op"]
+    top_k = op["k"] if kind.startswith("score_top_many") else 0
+    if top_k:
+        kind = "score_many" + kind[len("score_top_many"):]
     need, cols, dense = {}, set(), set()
 
     def job(n_passes, n_prompt, n_out, n_runs, draw, per_request, max_end):
@@ -287,6 +317,15 @@ def needs(op, streams, sampling, prefix_len, rows=None, stop=()):
             cols |= {(draw, width_index(sum(b[2]))) for b in narrow}
             dense |= {b[0] for b in wide}
         cols |= {(draw, width_index(n)) for n in plan["passes"]}
+        if st is not None:
+            if st["genlp"] >= 0:
+                need["genlp_recs"] = sum(n_new)
+                if st["genlp"] > 0:
+                    need.update(genlp_top=sum(n_new) * st["genlp"], genlp_rank=sum(n_new))
+            if table is not None:
+                n_ent = table_lens(table)[0]
+                need.update(bias_entries=sum(n_ent), bias_off=len(n_ent) + 1, bias_ooff=len(lens) + 1)
+            return dict(need=need, cols=cols, dense=dense, forms={form_of(d, st) + (w,) for d, w in cols})
     elif kind in ("batch_prefill_slots", "batch_prefix_set"):
         runs = [(0, len(toks(op["prompt"])))] if kind == "batch_prefix_set" else [(f, len(toks(p))) for p, f in zip(op["prompts"], op["first"])]
         draw = sampling and kind == "batch_prefill_slots"
@@ -321,6 +360,8 @@ def needs(op, streams, sampling, prefix_len, rows=None, stop=()):
             cols |= chunks
             n_rec = sum(n - f for n, f in zip(lens, op["score_from"] or [1] * len(lens)))
             need.update(score_rows=n_rec, score_out=n_rec)
+            if top_k:
+                need.update(score_top=n_rec * top_k, score_rank=n_rec)
         else:
             need["embed_out"] = len(lens) * (op.get("out_dim") or DIM)
         if max_end:
@@ -749,6 +790,355 @@ def make_sequence(seed, n_ops=N_OPS):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
+# the settings dimension: the engine-wide settings of sections 2m to 2q among the calls above.  These kinds are no part of KINDS or
+# ALL_PAIRS: the pair matrix and its twelve seeds stay what they were (tests/test_call_sequences_host.py holds their digests)
+# ---------------------------------------------------------------------------------------------------------------------------------
+SETTING_KINDS = ("set_top_k", "set_gen_logprobs", "set_penalties", "set_logit_bias", "read_gen_logprobs", "score_top_many", "score_top_many_prefix",
+                 "refused_set_top_k", "refused_set_gen_logprobs", "refused_set_penalties", "refused_set_logit_bias", "refused_bias_lists",
+                 "refused_score_top")
+SETTERS = ("set_top_k", "set_gen_logprobs", "set_penalties", "set_logit_bias")
+TOP_KS = (0, 1, 5, 20, 64)
+GEN_LPS = (-1, 0, 3, 64)
+PENALTIES = ((0.0, 0.0), (0.5, 0.25), (-0.5, 0.75), (1.0, -0.25), (1.5, 2.0))      # a negative presence, a negative frequency, both positive
+BIAS_FORMS = ("off", "one", "per", "big")
+# a loop kind in its greedy and in its sampled form
+VARIANTS = (("generate_many_greedy", False), ("generate_many_sampled", True), ("generate_many_dense", False), ("generate_many_dense", True),
+            ("generate_many_stop", False), ("generate_many_stop", True), ("generate_many_prefix", False), ("generate_many_prefix", True))
+SETTING_SEEDS = (31, 32, 33, 34, 35, 36)
+SETTING_EDGE_SEED = SETTING_SEEDS[1]
+OFF = dict(top_k=0, genlp=-1, pen=0, bias="off")
+
+
+def setting_states():
+    """The states every loop variant has to run under: every value class of every setting alone, every pair of settings on, all
+    four on.  dict(top_k, genlp, pen = index into PENALTIES, bias = form)"""
+    rng = random.Random(5)
+    alone = ([dict(OFF, top_k=v) for v in TOP_KS[1:]] + [dict(OFF, genlp=v) for v in GEN_LPS[1:]] + [dict(OFF, pen=i) for i in range(1, len(PENALTIES))]
+             + [dict(OFF, bias=f) for f in BIAS_FORMS[1:]])
+    pick = dict(top_k=TOP_KS[1:], genlp=GEN_LPS[1:], pen=range(1, len(PENALTIES)), bias=BIAS_FORMS[1:])
+    names = list(pick)
+    pairs = [dict(OFF, **{a: rng.choice(pick[a]), b: rng.choice(pick[b])}) for i, a in enumerate(names) for b in names[i + 1:]]
+    return alone + pairs + [{a: rng.choice(pick[a]) for a in names}]
+
+
+def form_states():
+    """one state per column-plan form that exists: (needs a sampled loop, state) -- top_k on or off, the three genlp forms, the three
+    forms of the penalty axis"""
+    return [(draw, dict(top_k=5 if topk else 0, genlp=lp, pen=2 if pen == 1 else 0, bias="per" if pen == 2 else "off"))
+            for draw, topk in ((False, False), (True, False), (True, True)) for lp in (-1, 0, 3) for pen in range(3)]
+
+
+def is_big(state):
+    """what the small phases of the growth epoch leave out: 64 tops per record and the long lists"""
+    return state["genlp"] == 64 or state["bias"] in ("one", "big")
+
+
+class _SGen(_Gen):
+    """_Gen with the four settings tracked and the emitters of SETTING_KINDS"""
+
+    def __init__(self, seed, avoid=frozenset()):
+        super().__init__(seed, avoid)
+        self.state = dict(OFF)
+        self.n_lists = 0                     # of a per-request table in force
+        self.users = 0                       # loop ops under the table in force
+        self.force = None
+        self.built = set()                   # (form, width index) of the column plans of the epoch
+
+    def _reqs(self, dense=False, one=False):
+        if self.force is not None:
+            return list(self.force)
+        return super()._reqs(dense, one)
+
+    def st(self):
+        s = self.state
+        return dict(top_k=s["top_k"], genlp=s["genlp"], pen=PENALTIES[s["pen"]], table=None if s["bias"] == "off" else 0)
+
+    def emit(self, kind, **force):
+        if kind not in SETTING_KINDS:
+            op = super().emit(kind, **force)
+            if kind == "batch_init":
+                self.built = set()
+            return op
+        r, S = self.rng, self.streams
+        op = {"op": kind}
+        if kind == "set_top_k":
+            op["k"] = self.state["top_k"] = force["k"]
+        elif kind == "set_gen_logprobs":
+            op["n"] = self.state["genlp"] = force["n"]
+        elif kind == "set_penalties":
+            self.state["pen"] = force["i"]
+            op["p"], op["f"] = PENALTIES[force["i"]]
+        elif kind == "set_logit_bias":
+            self.state["bias"] = force["form"]
+            self.n_lists = force.get("n", 0) if force["form"] == "per" else 0
+            self.users = 0
+            op.update(form=force["form"], n=self.n_lists, par=force.get("par", r.randrange(2)), seed=r.getrandbits(24))
+        elif kind in ("score_top_many", "score_top_many_prefix", "refused_score_top"):
+            op["reqs"] = force.get("reqs") or r.sample(SMALL, r.randint(1, 2))
+            op["k"] = force.get("k") or (r.choice((0, 65)) if kind == "refused_score_top" else r.choice((1, 5)))
+            op["score_from"] = None if "reqs" in force else self._score_from(op["reqs"])
+            if kind != "refused_score_top":
+                used = min(len(op["reqs"]), S)
+                self.slots[:used] = [None] * used
+        elif kind == "refused_set_top_k":
+            op["k"] = r.choice((65, -1))
+        elif kind == "refused_set_gen_logprobs":
+            op["n"] = r.choice((-2, 65))
+        elif kind == "refused_set_penalties":
+            op["bad"] = r.choice(("2.5", "nan"))
+        elif kind == "refused_set_logit_bias":
+            op.update(bad=r.choice(("twice", "vocab", "inf", "allow")), at=r.randrange(100))
+        elif kind == "refused_bias_lists":
+            op.update(kind="generate_many_stop", reqs=r.sample(LONG, self.n_lists + 1), sampled=self.bs_on, stop_at=[])
+        self.ops.append(op)
+        return op
+
+    def legal(self, kind):
+        if kind == "score_top_many_prefix":
+            return self.prefix is not None
+        if kind == "refused_bias_lists":
+            return self.n_lists > 1
+        return super().legal(kind)
+
+    # -- the settings
+    def goto(self, state, n=None):
+        """the setting ops that lead to `state` (n: the lists of a per-request table), in a seeded order"""
+        todo = [k for k in state if state[k] != self.state[k] or (k == "bias" and state[k] == "per" and n != self.n_lists)]
+        self.rng.shuffle(todo)
+        for k in todo:
+            self.set(k, state[k], n)
+
+    def owed(self, pair):
+        """a kind of SETTING_KINDS, legal here, that no sequence has in that place yet: pair(kind) is the ordered pair it would make"""
+        seen = pairs_of(self.ops) | self.avoid
+        kinds = [k for k in SETTING_KINDS if pair(k) not in seen and self.legal(k)]
+        return self.rng.choice(kinds) if kinds else None
+
+    def one(self, kind):
+        """one op of a setting kind that leaves the settings as they are: a setter sets the value in force once more"""
+        if kind in SETTERS:
+            k = ("top_k", "genlp", "pen", "bias")[SETTERS.index(kind)]
+            return self.set(k, self.state[k], self.n_lists)
+        return self.emit(kind)
+
+    def set(self, k, v, n=None, **force):
+        if k == "bias":
+            return self.emit("set_logit_bias", form=v, n=n, **force)
+        if k == "top_k":
+            self.emit("set_top_k", k=v)
+        elif k == "genlp":
+            self.emit("set_gen_logprobs", n=v)
+        elif k == "pen":
+            self.emit("set_penalties", i=v)
+
+    # -- one loop op
+    def loop(self, variant, reqs):
+        kind, sampled = variant
+        if self.state["bias"] == "per":
+            assert len(reqs) == self.n_lists, (len(reqs), self.n_lists)
+        if kind == "generate_many_greedy" and self.bs_on:
+            self.emit("set_batch_sampler_off")
+        if kind == "generate_many_prefix" and self.prefix is None:
+            self.emit("batch_prefix_set")
+        if kind in ("generate_many_dense", "generate_many_stop", "generate_many_prefix") and not sampled and self.bs_on:
+            self.emit("set_batch_sampler_off")
+        self.force = list(reqs)
+        op = super().emit(kind)
+        self.force = None
+        if kind not in ("generate_many_greedy", "generate_many_sampled"):
+            op["sampled"] = sampled
+            if sampled:
+                self.bs_known = False
+        if kind == "generate_many_dense":
+            op["dense_min"] = self.rng.choice((8, 32))
+        self.users += 1
+        if kind in ("generate_many_greedy", "generate_many_sampled", "generate_many_dense"):
+            self.built |= needs(op, self.streams, self.bs_on, 0, st=self.st())["forms"]
+        return op
+
+    def reqs(self, n=None, lo=1, hi=3):
+        if self.state["bias"] == "per":
+            n = self.n_lists
+        return self.rng.sample(LONG, n or self.rng.randint(lo, hi))
+
+    def reqs_for(self, variant, new):
+        """a request list whose column plans all exist in the epoch (new False) or of which one does not (new True)"""
+        draw = variant[1]
+        best = None
+        for _ in range(60):
+            reqs = self.reqs(lo=1, hi=min(4, 2 * self.streams))
+            lens, n_new = [CAT[i][1] for i in reqs], [CAT[i][2] for i in reqs]
+            forms = {form_of(draw, self.st()) + (width_index(n),) for n in many_plan(lens, n_new, self.streams)["passes"]}
+            if bool(forms - self.built) == new:
+                return reqs
+            best = best or reqs
+        return best
+
+    def filler(self, pool):
+        """one op of another kind between two loop ops"""
+        kind = self.rng.choice(pool)
+        if not self.legal(kind) or (self.ops[-1]["op"], kind) in ILLEGAL or kind in NEED_DRAWS or kind in GREEDY_ONLY:
+            kind = "read_gen_logprobs"
+        self.one(kind)
+
+
+# the kinds of the pair matrix that are no loop and start nothing over: what stands between the loop ops of a settings sequence, and
+# what has to leave the settings alone
+QUIET = tuple(k for k in KINDS if k not in MANY and k != "batch_init")
+BETWEEN = ("read_gen_logprobs", "score_top_many", "batch_step_cols_draw", "batch_prefill_slots", "embed_many", "choice_many", "score_many",
+           "verify_draw", "forward", "generate_lookup_draw", "set_sampler", "batch_reset_kv", "batch_copy_rows", "prefill_batched",
+           "generate_greedy", "refused_stop")
+
+
+def _settings_sequence(seed, avoid=frozenset()):
+    """190 to 260 ops in three epochs (what the coverage tests/test_call_sequences_host.py asserts takes: some 65 loop ops, the
+    setting ops that lead from one state to the next, and every setting kind in front of and behind every loop kind).  Epoch 0 is the one whose per-call buffers grow behind cached plans (small - medium - small -
+    large - small, the whole context, few slots); epochs 1 and 2 start the batched state over with other slot counts, the last one
+    with more, under the settings in force.  The loop variants run through the states of setting_states() that fall to this seed,
+    a variant at a time, other kinds between them; a toggle stretch switches one setting on, to another value and off under kept
+    plans; a stretch under all four settings goes through the quiet kinds that fall to this seed."""
+    g = _SGen(seed, avoid)
+    r = g.rng
+    at = SETTING_SEEDS.index(seed) if seed in SETTING_SEEDS else seed % 6
+    states = setting_states()
+    cells = [(v, s) for si, s in enumerate(states) for vi, v in enumerate(VARIANTS) if (si + vi) % len(SETTING_SEEDS) == at]
+    for fi, (draw, state) in enumerate(form_states()):          # every form, on two loop kinds: the second finds the first one's plans
+        if fi % len(SETTING_SEEDS) == at:
+            cells += [(v, state) for v in VARIANTS if v[1] == draw and v[0] != "generate_many_prefix"][:2]
+    small = [c for c in cells if not is_big(c[1])]
+    big = [c for c in cells if is_big(c[1])]
+    r.shuffle(small)
+    key = lambda c: sorted((k, str(v)) for k, v in c[1].items())
+    small.sort(key=key)
+    big.sort(key=key)
+    b = r.choice((2, 3, 4))
+    a = r.choice([v for v in (2, 3, 5) if v != b])
+    c = r.choice((6, 8))
+
+    def cut(cells, k):
+        """k, moved on to where the state changes: the cells of one state stay in one epoch"""
+        while 0 < k < len(cells) and cells[k - 1][1] == cells[k][1]:
+            k += 1
+        return k
+
+    def run(cells, fill=0.3):
+        reqs = state_before = None
+        for variant, state in cells:
+            n = r.randint(2, 3) if state["bias"] == "per" else None
+            if state == state_before:                           # the same requests: the widths of the loop op in front
+                n = len(reqs)
+            if state["bias"] != "off" and (g.state["bias"] != "off" and (g.users >= 3 or state["bias"] != g.state["bias"])):
+                g.emit("set_logit_bias", form="off")        # a table is made for the loop ops behind it: a few, so that its bans fit the list
+            g.goto(state, n)
+            x = g.owed(lambda k: (k, variant[0]))
+            if x:
+                g.one(x)
+            reqs = reqs if state == state_before and (state["bias"] != "per" or len(reqs) == g.n_lists) else g.reqs()
+            state_before = state
+            g.loop(variant, reqs)
+            x = g.owed(lambda k: (variant[0], k))
+            if x:
+                g.one(x)
+            elif r.random() < fill:
+                g.filler(BETWEEN)
+
+    def grow(size, reqs, variant_a, variant_b):
+        """the medium and the large phase: 64 tops per record, the long list, then one list per request, a score call with tops"""
+        g.goto(dict(genlp=64, pen=r.randrange(1, len(PENALTIES))))
+        g.emit("set_logit_bias", form=size)
+        g.loop(variant_a, reqs)
+        g.emit("read_gen_logprobs")
+        g.emit("set_logit_bias", form="per", n=len(reqs))
+        g.loop(variant_b, reqs)
+        g.emit("refused_bias_lists")
+        g.emit("read_gen_logprobs")                             # refused: the failed call has left nothing to read
+        g.emit("score_top_many", reqs=reqs, k=64)
+        g.emit("set_logit_bias", form="off")
+
+    def small_again(variant_a, variant_b):
+        """the same kinds, small: 3 tops, one short list per request"""
+        g.goto(dict(genlp=3))
+        g.emit("set_logit_bias", form="per", n=2)
+        g.loop(variant_a, g.reqs())
+        g.loop(variant_b, g.reqs())
+        g.emit("score_top_many", k=r.choice((1, 5)))
+        g.emit("set_logit_bias", form="off")
+
+    va, vb = r.choice(VARIANTS[:2]), r.choice(VARIANTS[4:6])
+    # epoch 0: the growth epoch
+    g.emit("batch_init", streams=b, ctx=0)
+    g.growth = True
+    for _ in range(2):
+        g.emit("batch_prefill_slots", wide=True)               # a dense plan, and its second use
+    small_again(va, vb)
+    third, two = cut(small, len(small) // 3), cut(small, 2 * len(small) // 3)
+    half = cut(big, len(big) // 2)
+    run(small[:third])
+    small_again(va, vb)
+    grow("one", list(LONG[:7]), va, vb)
+    small_again(va, vb)
+    run(small[third:two])
+    grow("big", list(LONG[:12]), va, vb)
+    small_again(va, vb)
+    g.growth = False
+    # the toggle stretch: one setting on, to another value, off and on again, under the kept plans of both forms; behind every
+    # switch a loop op on kept widths and one that builds a width
+    name = ("top_k", "genlp", "pen", "bias", "top_k", "pen")[at]
+    vals = dict(top_k=(5, 20), genlp=(0, 3), pen=(1, 2), bias=("per", "per"))[name]
+    tv = VARIANTS[1] if name == "top_k" else r.choice(VARIANTS[:2])
+    g.goto(dict(OFF))
+    g.loop(tv, g.reqs())
+    for v in (vals[0], OFF[name], vals[0], vals[1], OFF[name]):
+        if name == "bias" and g.state["bias"] != "off" and v != "off":
+            g.emit("set_logit_bias", form="off")
+        g.set(name, v, 2)
+        g.loop(tv, g.reqs_for(tv, False))
+        g.loop(tv, g.reqs_for(tv, True))
+    # all four on across q3_batch_init to another slot count
+    all_on = dict(states[-1], bias="per")
+    g.goto(all_on, 2)
+    g.emit("batch_init", streams=a, ctx=256)
+    g.loop(r.choice(VARIANTS), g.reqs())
+    # epoch 1: the rest of the small states and the first of the big ones
+    run(small[two:] + big[:half])
+    # all four on, across the state changers and the quiet kinds that fall to this seed, a loop op behind them
+    g.emit("set_logit_bias", form="off")
+    g.goto(dict(all_on, bias="off"))
+    g.emit("set_logit_bias", form="per", n=3, par=1)           # its first list allows three tokens
+    quiet = [k for i, k in enumerate(QUIET) if i % len(SETTING_SEEDS) == at] + ["set_sampler", "set_batch_sampler_on", "batch_step_cols_draw",
+                                                                                 "set_batch_sampler_off", "batch_step_cols_draw", "batch_reset_kv"]
+    for k in quiet:
+        g.enable(k)
+        if g.legal(k) and (g.ops[-1]["op"], k) not in ILLEGAL:
+            g.emit(k)
+    g.loop(r.choice(VARIANTS), g.reqs())
+    g.emit("read_gen_logprobs")
+    # epoch 2: more slots, under all four
+    g.emit("batch_init", streams=c, ctx=r.choice((192, 256)))
+    g.emit("read_gen_logprobs")
+    g.loop(r.choice(VARIANTS), g.reqs())
+    run(big[half:])
+    g.goto(dict(OFF))
+    g.loop(r.choice(VARIANTS), g.reqs())
+    return g.ops
+
+
+@functools.lru_cache(maxsize=None)
+def _cached_settings_sequence(seed):
+    avoid = set()
+    if seed in SETTING_SEEDS:                                   # as for SEEDS: away from the pairs the seeds in front have
+        for s in SETTING_SEEDS[:SETTING_SEEDS.index(seed)]:
+            avoid |= pairs_of(_cached_settings_sequence(s))
+    return _settings_sequence(seed, frozenset(avoid))
+
+
+def make_settings_sequence(seed):
+    """The ops of a settings seed: deterministic, legal in the state the ops before them leave"""
+    import copy
+    return copy.deepcopy(_cached_settings_sequence(seed))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
 # the reference: the C oracle, memoised
 # ---------------------------------------------------------------------------------------------------------------------------------
 class _Node:
@@ -829,34 +1219,73 @@ class Reference:
         out["target"], (out["max"], out["sum"], out["argmax"]) = node.logits[target], node.wide
         return out
 
-    def draw(self, logits, T, P, state):
-        """(token, rng state afterwards): Sampler::sample with that state, the argmax and no coin at temperature 0"""
+    def draw(self, logits, T, P, state, top_k=0):
+        """(token, rng state afterwards): Sampler::sample with that state, the argmax and no coin at temperature 0; under top_k > 0
+        section 2n's draw among the survivors (topk_ref.sample_top_k over the same oracle sampler)"""
         if not T > 0:
             return self.oracle.sample_argmax(logits), state
+        if top_k:
+            import topk_ref
+            return topk_ref.sample_top_k(self.oracle, logits, T, P, top_k, state)
         s = self.oracle.Sampler(VOCAB, T, P, state)
         tok = s.sample(logits)
         return tok, int(s.rng_state.value)
 
-    def generate(self, prompt, n_new, sampler=None):
+    def generate(self, prompt, n_new, sampler=None, top_k=0, presence=0.0, frequency=0.0, entries=(), mode=0, dev=()):
         """The header's rule for request rows: what a fresh engine returns for prefill(prompt) and generate_greedy behind it, after
         set_sampler(temperature, topp, seed) when sampler = (temperature, topp, seed) -- one discarded sample per prompt position
-        in front of the last.  Returns (the n_new tokens, the rng state afterwards)."""
-        key = (tuple(prompt), n_new, sampler)
+        in front of the last.  Under the engine-wide settings of sections 2n, 2p and 2q output g is taken from
+        bias_ref.rule(row, entries, mode, g, counts, presence, frequency) -- the table first, the penalties over the request's own
+        outputs on top -- by the largest key (pen_ref.argmax_key) or by the draw among the top_k.  dev: deviations from the rule,
+        the injected leaks of FakeEngine alone -- ("counts0", ((token, count), ..)) counts the request does not start from zero with,
+        ("per_g", ((entries, mode, g), ..)) the list and the output index each output is adjusted by, ("adjusted",) the records
+        are taken on the adjusted row.
+        Returns (the n_new tokens, the rng state afterwards, per token the node whose logits it was taken from, per token the row a
+        record is taken on: None for the node's own logits)."""
+        key = (tuple(prompt), n_new, sampler, top_k, presence, frequency, tuple(entries), mode, dev)
         if key not in self._memo:
             T, P, state = sampler if sampler else (0.0, 1.0, 0)
-            n, tok, out = self.root, None, []
+            plain = not (top_k or presence or frequency or entries or mode or dev)
+            dev_of = dict((d[0], d[1:]) for d in dev)
+            n, tok, out, nodes, rows = self.root, None, [], [], []
             for t in prompt:
                 n = self.child(n, t)
-                if T > 0:
+                if T > 0 and plain:
                     tok, state = self.draw(n.logits, T, P, state)
-            if not T > 0:
-                tok = self.oracle.sample_argmax(n.logits)
-            out.append(tok)
-            while len(out) < n_new:
-                n = self.child(n, tok)
-                tok, state = self.draw(n.logits, T, P, state)
+            if plain:
+                if not T > 0:
+                    tok = self.oracle.sample_argmax(n.logits)
                 out.append(tok)
-            self._memo[key] = (out, state)
+                nodes.append(n)
+                while len(out) < n_new:
+                    n = self.child(n, tok)
+                    tok, state = self.draw(n.logits, T, P, state)
+                    out.append(tok)
+                    nodes.append(n)
+                rows = [None] * n_new
+            else:
+                import bias_ref
+                import pen_ref
+                if T > 0:
+                    state = xorshift(state, len(prompt) - 1)           # a discarded prompt-position draw burns its coin and selects nothing
+                counts = np.zeros(VOCAB, dtype=np.uint32)
+                for t, c in (dev_of["counts0"][0] if "counts0" in dev_of else ()):
+                    counts[t] = c
+                pen = bool(presence or frequency)
+                for g in range(n_new):
+                    if g:
+                        n = self.child(n, tok)
+                    en, mo, ge = dev_of["per_g"][0][g] if "per_g" in dev_of else (entries, mode, g)
+                    row = bias_ref.rule(n.logits, en, mo, ge, counts if pen else None, presence, frequency)
+                    if T > 0:
+                        tok, state = self.draw(row, T, P, state, top_k)
+                    else:
+                        tok = pen_ref.argmax_key(row)
+                    counts[tok] += 1
+                    out.append(int(tok))
+                    nodes.append(n)
+                    rows.append(row if "adjusted" in dev_of else None)
+            self._memo[key] = (out, state, nodes, rows)
         return self._memo[key]
 
 
@@ -884,6 +1313,8 @@ class _Cache:
 
 
 LEAKS = ("sampler", "prefix", "length", "slot_rng", "stale_cand")
+SETTING_LEAKS = ("pen_counts", "pen_prompt", "bias_stale", "bias_ooff", "genlp_stale", "genlp_penalised", "topk_init", "settings_touch_cols",
+                 "score_top_shared")
 
 
 class FakeEngine:
@@ -896,10 +1327,22 @@ class FakeEngine:
         "slot_rng": a choice or score call advances the sampler state of every slot it fills by one coin per prompt token, as a dense
                    generate loop does and these calls must not
         "stale_cand": choice_many answers with the previous call's candidate ids at every index that call had: a candidate buffer
-                   that is uploaded only where it has grown"""
+                   that is uploaded only where it has grown
+    and of SETTING_LEAKS, over the state of sections 2m to 2q --
+        "pen_counts": a slot's produced-token counts are not cleared for its next occupant, within a call and across calls
+        "pen_prompt": the prompt's tokens enter the counts
+        "bias_stale": a call under a shorter table sees the previous table's entries at the indices it did not overwrite: they
+                   stand behind its last list
+        "bias_ooff": a column finds its request and its output index g from the previous call's o_off
+        "genlp_stale": the entries of the record buffers that a call does not write keep the previous call's bytes (no clear)
+        "genlp_penalised": the records are taken on the adjusted row
+        "topk_init": batch_init resets top_k to 0
+        "settings_touch_cols": batch_step_cols_draw adjusts its rows by the table's first list and the slot's counts
+        "score_top_shared": score_top_many behind a loop with tops answers the first chunk's tops and ranks from the part lists
+                   the loop's last pass left"""
 
     def __init__(self, ref, leak=None):
-        assert leak is None or leak in LEAKS
+        assert leak is None or leak in LEAKS + SETTING_LEAKS
         self.ref, self.leak = ref, leak
         self.single = _Cache(ref, SEQ)
         self.slots, self.streams, self.ctx = [], 0, 0
@@ -909,6 +1352,69 @@ class FakeEngine:
         self.loop_rng = {}
         self.last_cand = []
         self.touched = {}
+        # the engine-wide settings: they outlive batch_init, both samplers and every call
+        self.k_top, self.genlp, self.pen, self.bias = 0, -1, (0.0, 0.0), ([], [])
+        self.gen = None                      # the records of the last loop call: dict(k, cap, got, recs, tops, ranks), None: nothing to read
+        self.dev = {}                        # what the leaks need of the device: counts per slot, the buffers a call found in place
+
+    # -- the settings (sections 2m to 2q)
+    def set_top_k(self, k):
+        if isinstance(k, bool) or not isinstance(k, int) or not 0 <= k <= 64:
+            raise ValueError("top_k out of range")
+        self.k_top = k
+
+    top_k = property(lambda self: self.k_top)
+
+    def set_gen_logprobs(self, top_n):
+        if not -1 <= top_n <= 64:
+            raise ValueError("logprobs out of range")
+        self.genlp = top_n
+
+    def get_gen_logprobs(self):
+        return self.genlp
+
+    def set_penalties(self, presence, frequency):
+        with np.errstate(over="ignore"):
+            v = [np.float32(presence), np.float32(frequency)]
+        if not all(np.isfinite(x) and abs(x) <= 2 for x in v):
+            raise ValueError("penalty out of range")
+        self.pen = (float(v[0]), float(v[1]))
+
+    def get_penalties(self):
+        return self.pen
+
+    def set_logit_bias(self, lists, modes=None):
+        lists = [list(l.items()) if isinstance(l, dict) else list(l) for l in lists]
+        modes = [0] * len(lists) if modes is None else [int(m) for m in modes]
+        if len(modes) != len(lists):
+            raise ValueError("one mode per list")
+        norm = []
+        for l, m in zip(lists, modes):
+            ent = sorted((int(e[0]), float(np.float32(e[1])), int(e[2]) if len(e) > 2 else 0) for e in l)
+            if (len({e[0] for e in ent}) != len(ent) or any(not 0 <= e[0] < VOCAB for e in ent)
+                    or any(not (e[1] == -np.inf or abs(e[1]) <= 100) for e in ent) or m not in (0, 1)
+                    or (m == 1 and not any(np.isfinite(e[1]) for e in ent))):
+                raise ValueError("a token twice or out of range, a bias that is neither -inf nor within 100, or an ALLOW list that allows nothing")
+            norm.append(ent)
+        self.bias = (norm, modes)
+
+    def get_logit_bias(self):
+        return [list(l) for l in self.bias[0]], list(self.bias[1])
+
+    def read_gen_logprobs(self, n_per_row=None):
+        import score_top_ref
+        g = self.gen
+        if g is None:
+            raise IndexError("the last generate_many call left no records")
+        want = g["got"] if n_per_row is None else [int(v) for v in n_per_row]
+        if len(want) != len(g["cap"]) or any(w < 0 or w > c for w, c in zip(want, g["cap"])):
+            raise IndexError("n_per_row")
+        k, out, at = g["k"], [], 0
+        tops = g["tops"].reshape(-1, k) if k else np.zeros((sum(g["cap"]), 0), dtype=score_top_ref.DTYPE)
+        for c, w in zip(g["cap"], want):
+            out.append((g["recs"][at:at + w].copy(), tops[at:at + w].copy(), g["ranks"][at:at + w].copy() if k > 0 else g["ranks"][:0].copy()))
+            at += c
+        return out
 
     # -- state
     def _cache(self, cid):
@@ -937,7 +1443,7 @@ class FakeEngine:
             raise IndexError("token outside the vocabulary")
 
     def _sdraw(self, logits):
-        tok, self.srng = self.ref.draw(logits, self.sT, self.sP, self.srng)
+        tok, self.srng = self.ref.draw(logits, self.sT, self.sP, self.srng, self.k_top)
         return tok
 
     # -- the single stream
@@ -972,7 +1478,7 @@ class FakeEngine:
         for i, t in enumerate(tokens):
             lg = self._feed("single", t, pos + i).logits
             logits.append(lg)
-            nxt.append(self.ref.draw(lg, self.sT, self.sP, xorshift(self.srng, i) if self.sT > 0 else 0)[0])
+            nxt.append(self.ref.draw(lg, self.sT, self.sP, xorshift(self.srng, i) if self.sT > 0 else 0, self.k_top)[0])
         a = 0
         while a + 1 < n and tokens[a + 1] == nxt[a]:
             a += 1
@@ -1018,6 +1524,9 @@ class FakeEngine:
         self.streams, self.ctx = streams, min(ctx, SEQ) if ctx else SEQ
         self.slots = [_Cache(self.ref, self.ctx) for _ in range(streams)]
         self.bT, self.brng, self.loop_rng, self.last_cand = 0.0, [], {}, []
+        self.gen, self.dev = None, {}            # the records and every buffer of the settings belong to the batched state
+        if self.leak == "topk_init":
+            self.k_top = 0
         if self.leak != "prefix":
             self.prefix = []
         self.touched.update({s: "all" for s in range(streams)})
@@ -1040,7 +1549,7 @@ class FakeEngine:
     def _bdraw(self, slot, logits):
         if not self.bT > 0:
             return self.ref.draw(logits, 0.0, 1.0, 0)[0]
-        tok, self.brng[slot] = self.ref.draw(logits, self.bT, self.bP, self.brng[slot])
+        tok, self.brng[slot] = self.ref.draw(logits, self.bT, self.bP, self.brng[slot], self.k_top)
         return tok
 
     def _batch_args(self, tokens, pos):
@@ -1062,7 +1571,7 @@ class FakeEngine:
                 out[i, k] = tok
         return out
 
-    def _cols(self, slots, tokens, pos, keep, draw):
+    def _cols(self, slots, tokens, pos, keep, draw, want_draw=False):
         if not 1 <= len(slots) <= COLS_MAX or any(s < 0 or s >= self.streams for s in slots) or any(p >= self.ctx for p in pos):
             raise IndexError("column out of range")
         self._check_tokens(tokens)
@@ -1071,10 +1580,17 @@ class FakeEngine:
             k = k + 1 if j and slots[j - 1] == s else 0
             lg = self._feed(s, t, p).logits
             logits.append(lg)
+            if self.leak == "settings_touch_cols" and want_draw:
+                import bias_ref
+                en, mo = bias_ref.list_of(self.bias, 0)
+                lg = bias_ref.rule(lg, en, mo, 0, self.dev.get("counts", {}).get(s) if any(self.pen) else None, *self.pen)
             if draw and keep is not None and not keep[j]:
                 out.append(-1)
+            elif not draw and lg is not logits[-1]:
+                import pen_ref
+                out.append(pen_ref.argmax_key(lg))
             else:
-                out.append(self.ref.draw(lg, self.bT if draw else 0.0, self.bP, xorshift(self.brng[s], k) if draw else 0)[0])
+                out.append(self.ref.draw(lg, self.bT if draw else 0.0, self.bP, xorshift(self.brng[s], k) if draw else 0, self.k_top)[0])
             if draw and (j + 1 == len(slots) or slots[j + 1] != s):
                 self.brng[s] = xorshift(self.brng[s], k + 1)
         return np.stack(logits), out
@@ -1085,7 +1601,7 @@ class FakeEngine:
         return self._cols(slots, tokens, pos, None, False)
 
     def batch_step_cols_draw(self, slots, tokens, pos, keep=None, want_logits=True):
-        return self._cols(slots, tokens, pos, keep, self.bT > 0)
+        return self._cols(slots, tokens, pos, keep, self.bT > 0, True)
 
     def batch_prefill_slots(self, slots, prompts, first):
         if any(s < 0 or s >= self.streams for s in slots):
@@ -1100,11 +1616,15 @@ class FakeEngine:
         return _q3().dense_pack([len(p) for p in prompts], DENSE_CAP)[1]
 
     def _many(self, prompts, n_new, sampler, dense_min=0, stop=(), prefix=(), carry=False):
+        self.gen = None                          # every loop call starts here: the records of the call before are gone
         for p in prompts:
             self._check_tokens(p)
         if sampler is None and self.bT > 0:
             raise Refused(-5, "greedy only")
         n = len(prompts)
+        lists, modes = self.bias
+        if len(lists) > 1 and len(lists) != n:
+            raise IndexError("one list per request")
         per = [None] * n
         if sampler is not None:
             T, P, seeds = [v if isinstance(v, (list, tuple)) else [v] * n for v in sampler]
@@ -1120,7 +1640,8 @@ class FakeEngine:
                         if s in self.loop_rng:
                             per[r] = (per[r][0], per[r][1], self.loop_rng[s])
                         self.loop_rng[s] = self.ref.generate(full[r], n_new[r], per[r])[1]
-        rows = [self.ref.generate(full[r], n_new[r], per[r])[0] for r in range(n)]
+        res = self._rows(full, lens, n_new, per)
+        rows = [x[0] for x in res]
         plan = plan or many_plan(lens, n_new, self.streams, dense_min, rows, stop)
         out = [cut_at_stop(r, stop) for r in rows]
         assert [len(r) for r in out] == list(plan["n_out"])
@@ -1128,7 +1649,107 @@ class FakeEngine:
             for r in occ:
                 for i, t in enumerate(full[r] + out[r][:-1]):
                     self._feed(s, t, i)
+        if self.genlp >= 0:
+            self._records(n_new, out, res)
         return out, plan
+
+    def _rows(self, full, lens, n_new, per):
+        """Reference.generate per request under the settings: (tokens, rng state, nodes, record rows) each"""
+        import bias_ref
+        lists, modes = self.bias
+        pen = any(self.pen)
+        n = len(full)
+        tables = [bias_ref.list_of(self.bias, r) for r in range(n)]
+        if self.leak == "bias_stale" and lists:
+            # the flat entries of this table over what the buffer held: the tail of the longer table before stands behind the last list
+            flat = [e for l in lists for e in l]
+            old = self.dev.get("bias_flat", [])
+            self.dev["bias_flat"] = flat + old[len(flat):]
+            have = {e[0] for e in lists[-1]}
+            tail = []
+            for e in old[len(flat):]:
+                if e[0] not in have:
+                    have.add(e[0])
+                    tail.append(e)
+            if tail:
+                last = len(lists) - 1
+                tables = [(sorted(list(en) + tail), mo) if (len(lists) == 1 or r == last) else (en, mo) for r, (en, mo) in enumerate(tables)]
+        per_g = [None] * n
+        o_off = [sum(n_new[:r]) for r in range(n)]
+        if self.leak == "bias_ooff" and lists:
+            prev = self.dev.get("o_off")
+            if prev:
+                for r in range(n):
+                    found = []
+                    for g in range(n_new[r]):
+                        o = o_off[r] + g
+                        q = max(i for i, v in enumerate(prev) if v <= o)
+                        en, mo = bias_ref.list_of(self.bias, min(q, len(lists) - 1))
+                        found.append((tuple(en), mo, o - prev[q]))
+                    per_g[r] = tuple(found)
+            self.dev["o_off"] = o_off
+        counts0 = [None] * n
+        if pen and self.leak in ("pen_counts", "pen_prompt"):
+            left = self.dev.setdefault("counts", {})
+            for s, occ in sorted(many_plan(lens, n_new, self.streams)["occupants"].items()):
+                for r in occ:
+                    if self.leak == "pen_prompt":
+                        c = {}
+                        for t in full[r][len(full[r]) - lens[r]:]:
+                            c[t] = c.get(t, 0) + 1
+                    else:
+                        c = dict(left.get(s, {}))
+                    counts0[r] = tuple(sorted(c.items()))
+                    got = self._one(full[r], n_new[r], per[r], tables[r], per_g[r], counts0[r])[0]
+                    for t in got:
+                        c[t] = c.get(t, 0) + 1
+                    left[s] = c
+        res = [self._one(full[r], n_new[r], per[r], tables[r], per_g[r], counts0[r]) for r in range(n)]
+        if pen and self.leak == "settings_touch_cols":          # the counts that leak keeps per slot: the last occupant's
+            cs = self.dev.setdefault("counts", {})
+            for s, occ in many_plan(lens, n_new, self.streams)["occupants"].items():
+                c = np.zeros(VOCAB, dtype=np.uint32)
+                for t in res[occ[-1]][0]:
+                    c[t] += 1
+                cs[s] = c
+        return res
+
+    def _one(self, prompt, n_new, sampler, table, per_g, counts0):
+        dev = ()
+        if per_g:
+            dev += (("per_g", per_g),)
+        if counts0:
+            dev += (("counts0", counts0),)
+        if self.leak == "genlp_penalised" and self.genlp >= 0:
+            dev += (("adjusted",),)
+        return self.ref.generate(prompt, n_new, sampler, self.k_top if sampler else 0, self.pen[0], self.pen[1], tuple(tuple(e) for e in table[0]), table[1], dev)
+
+    def _records(self, n_new, out, res):
+        """the record buffers of the call as read_gen_logprobs finds them: indexed as the output tokens, cleared in front of the call"""
+        import score_ref
+        import score_top_ref as tr
+        k, total = self.genlp, sum(n_new)
+        old = self.dev.get("genlp") if self.leak == "genlp_stale" else None
+        recs, tops, ranks = np.zeros(total, dtype=score_ref.DTYPE), np.zeros(total * k, dtype=tr.DTYPE), np.zeros(total, dtype=np.int32)
+        if old:
+            for new, was in zip((recs, tops, ranks), old):
+                m = min(new.size, was.size)
+                new[:m] = was[:m]
+        at = 0
+        last = []
+        for r, row in enumerate(out):
+            _, _, nodes, adj = res[r]
+            for j, tok in enumerate(row):
+                l = nodes[j].logits if adj[j] is None else adj[j]
+                recs[at + j] = self.ref.record(nodes[j], tok) if adj[j] is None else score_ref.record(l, tok)
+                if k:
+                    tops[(at + j) * k:(at + j + 1) * k] = tr.top(l, k)
+                    ranks[at + j] = tr.rank(l, tok)
+            last.append(nodes[len(row) - 1])
+            at += n_new[r]
+        self.gen = dict(k=k, cap=[int(v) for v in n_new], got=[len(r) for r in out], recs=recs, tops=tops, ranks=ranks)
+        self.dev["genlp"] = (recs, tops, ranks)
+        self.dev["loop_last"] = last if k else None          # the rows of the loop's last columns, whose part lists a leak hands on
 
     def generate_many_greedy(self, prompts, n_new):
         out, plan = self._many(prompts, n_new, None)
@@ -1236,11 +1857,32 @@ class FakeEngine:
         return out, _q3().ScoreStats(*sched)
 
 
+    def score_top_many(self, prompts, k, score_from=None, use_prefix=False):
+        import score_top_ref as tr
+        if not 1 <= k <= 64:
+            raise IndexError("k out of range")
+        recs, st = self.score_many(prompts, score_from, use_prefix)
+        sf = [1] * len(prompts) if score_from is None else list(score_from)
+        P = len(self.prefix) if use_prefix else 0
+        tops, ranks, seen = [], [], 0
+        shared = self.dev.pop("loop_last", None) if self.leak == "score_top_shared" else None
+        for r, (p, f) in enumerate(zip(prompts, sf)):
+            nodes = self.ref._path(self.ref.node((self.prefix if use_prefix else []) + list(p)))[P:]
+            rows = [nodes[i].logits for i in range(f - 1, len(p) - 1)]
+            if shared:
+                rows = [shared[(seen + i) % len(shared)].logits if seen + i < SCORE_COLS else l for i, l in enumerate(rows)]
+            seen += len(rows)
+            tops.append(np.stack([tr.top(l, k) for l in rows]) if rows else np.zeros((0, k), dtype=tr.DTYPE))
+            ranks.append(np.array([tr.rank(l, p[f + i]) for i, l in enumerate(rows)], dtype=np.int32))
+        return recs, tops, ranks, st
+
+
 # ---------------------------------------------------------------------------------------------------------------------------------
 # running a sequence
 # ---------------------------------------------------------------------------------------------------------------------------------
-def _requests(op, ref, prefix):
-    """prompts, n_new, the sampler triple or None, and the stop tokens of a loop op"""
+def _requests(op, ref, prefix, top_k=0, pen=(0.0, 0.0)):
+    """prompts, n_new, the sampler triple or None, and the stop tokens of a loop op.  A stop token is a token of a request's own row
+    as the settings in force give it with no table set (a table is derived from those rows and from these stop tokens: Tables)"""
     reqs = [CAT[i] for i in op["reqs"]]
     prompts = [toks((k, n)) for k, n, *_ in reqs]
     n_new = [c[2] for c in reqs]
@@ -1249,15 +1891,164 @@ def _requests(op, ref, prefix):
     stop = []
     for i, j in op.get("stop_at", ()):
         k, n, nn, T, P, seed = CAT[i]
-        row = ref.generate(tuple(list(prefix) + toks((k, n))), nn, (T, P, seed) if sampled and T > 0 else None)[0]
+        smp = (T, P, seed) if sampled and T > 0 else None
+        row = ref.generate(tuple(list(prefix) + toks((k, n))), nn, smp, top_k if smp else 0, pen[0], pen[1])[0]
         if row[j] not in stop:
             stop.append(row[j])
     return prompts, n_new, sampler, stop
 
 
-def call(e, op, ref, prefix=()):
-    """One op on an engine (a Transformer or a FakeEngine): what it returned, in a form that compares with ==/bitwise"""
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the engine-wide settings along a sequence, and the tables of its set_logit_bias ops
+# ---------------------------------------------------------------------------------------------------------------------------------
+def settings_walk(ops):
+    """per op what is in force in front of it: dict(top_k, genlp, pen, table = the index of the set_logit_bias op whose table holds or
+    None, prefix = the resident prefix as a PREFIXES entry or None, streams).  A refused call changes nothing."""
+    st = dict(top_k=0, genlp=-1, pen=(0.0, 0.0), table=None, prefix=None, streams=0)
+    out = []
+    for i, op in enumerate(ops):
+        out.append(dict(st))
+        k = op["op"]
+        if k == "set_top_k":
+            st["top_k"] = op["k"]
+        elif k == "set_gen_logprobs":
+            st["genlp"] = op["n"]
+        elif k == "set_penalties":
+            st["pen"] = (float(np.float32(op["p"])), float(np.float32(op["f"])))
+        elif k == "set_logit_bias":
+            st["table"] = None if op["form"] == "off" else i
+        elif k == "batch_prefix_set":
+            st["prefix"] = op["prompt"]
+        elif k == "batch_init":
+            st["prefix"], st["streams"] = None, op["streams"]
+    return out
+
+
+BIAS_SIZES = {"one": 40, "big": 320, "add": 5, "allow": 3}          # entries per list: static, so that needs() knows them without an oracle
+NEG_INF = float("-inf")
+
+
+def table_lens(op):
+    """the list lengths and modes of a set_logit_bias op: per request ALLOW (three tokens) and ADD lists in turn"""
+    if op["form"] == "off":
+        return [], []
+    if op["form"] in ("one", "big"):
+        return [BIAS_SIZES[op["form"]]], [0]
+    modes = [(r + op["par"]) % 2 for r in range(op["n"])]
+    return [BIAS_SIZES["allow"] if m else BIAS_SIZES["add"] for m in modes], modes
+
+
+class Tables:
+    """The tables of the set_logit_bias ops of a sequence, from Reference alone, so that they bind on any logits: every loop op that
+    runs under a table finds, for every one of its requests, a token banned that the request produces without the table (under the
+    other settings in force, in front of its first stop token) -- for good ({tok, -inf, 0}) or up to that output (the min_tokens form
+    {tok, -inf, g + 1}) -- or an allowed list of three tokens that holds none of its first tokens.  The lists are filled up to the
+    static lengths of table_lens with seeded tokens of bias +0, -0, a small finite one or -inf, some with until > 0."""
+
+    def __init__(self, ops, ref):
+        self.ops, self.ref, self.st, self.memo = ops, ref, settings_walk(ops), {}
+
+    def users(self, i):
+        return [j for j in range(i + 1, len(self.ops)) if self.ops[j]["op"] in MANY and self.st[j]["table"] == i]
+
+    def plain_rows(self, j):
+        """the requests of loop op j with no table set: per request the row cut at its first stop token"""
+        return self.rows(j, table=False)
+
+    def rows(self, j, table=True, **other):
+        """The rows of loop op j by Reference alone, each cut at its first stop token, under the settings in force in front of it;
+        table False: with no table set; other: top_k or pen replaced.  The stop tokens are the op's own in every case."""
+        op, st = self.ops[j], self.st[j]
+        prefix = toks(st["prefix"]) if op["op"] == "generate_many_prefix" else []
+        prompts, n_new, sampler, stop = _requests(op, self.ref, prefix, st["top_k"], st["pen"])
+        st = dict(st, **other)
+        lists = self.get(st["table"]) if table and st["table"] is not None else ([], [])
+        import bias_ref
+        rows = []
+        for r, p in enumerate(prompts):
+            smp = (sampler[0][r], sampler[1][r], sampler[2][r]) if sampler and sampler[0][r] > 0 else None
+            en, mo = bias_ref.list_of(lists, r)
+            row = self.ref.generate(tuple(prefix + p), n_new[r], smp, st["top_k"] if smp else 0, st["pen"][0], st["pen"][1], tuple(tuple(e) for e in en), mo)[0]
+            rows.append(cut_at_stop(row, stop))
+        return rows
+
+    def get(self, i):
+        if i not in self.memo:
+            op = self.ops[i]
+            lens, modes = table_lens(op)
+            rng = random.Random(op["seed"])
+            used = [self.plain_rows(j) for j in self.users(i)]
+            lists = []
+            for li, (n, mode) in enumerate(zip(lens, modes)):
+                mine = [rows if len(lens) == 1 else [rows[li]] for rows in used]       # the rows this list has to bind on
+                ent = {}
+                if mode:                                                                  # ALLOW: none of the first tokens
+                    first = {row[0] for rows in mine for row in rows}
+                    while len(ent) < n:
+                        t = rng.randrange(VOCAB)
+                        if t not in first and t not in ent:
+                            ent[t] = ((0.0, 0), (-0.0, 0), (NEG_INF, 2))[len(ent)]      # the third: allowed from output 2 on
+                else:
+                    for rows in mine:
+                        for row in rows:
+                            g = rng.randrange(len(row))
+                            until = rng.choice((0, g + 1))
+                            if row[g] in ent:
+                                until = 0 if 0 in (until, ent[row[g]][1]) else max(until, ent[row[g]][1])
+                            ent[row[g]] = (NEG_INF, until)
+                    assert len(ent) <= n, f"op {i}: {len(ent)} banned tokens for a list of {n}"
+                    produced = {t for rows in mine for row in rows for t in row}
+                    while len(ent) < n:
+                        t = rng.randrange(VOCAB)
+                        if t not in ent and t not in produced:
+                            ent[t] = (rng.choice((0.0, -0.0, 0.25, -0.5, NEG_INF)), rng.choice((0, 0, 3)))
+                lists.append(sorted((t, b, u) for t, (b, u) in ent.items()))
+            self.memo[i] = (lists, modes)
+        return self.memo[i]
+
+
+def _setting(fn, *args):
+    """a setting call: the binding checks the values itself and raises ValueError where the library answers Q3_ERR_ARG"""
+    try:
+        return fn(*args)
+    except ValueError as err:
+        raise IndexError(str(err)) from None
+
+
+def _fields(arrays, names):
+    return [tuple(np.ascontiguousarray(a[f]) for f in names) for a in arrays]
+
+
+def call(e, op, ref, prefix=(), env=None):
+    """One op on an engine (a Transformer or a FakeEngine): what it returned, in a form that compares with ==/bitwise.  env: what the
+    model knows in front of the op and the op does not say -- dict(top_k, pen: the settings in force, which the stop tokens of a loop
+    op are derived under; table: the (lists, modes) of a set_logit_bias op; cap: the n_new of the last loop call with records)"""
     k = op["op"]
+    env = env or {}
+    if k == "refused_bias_lists":                   # a loop op with one request more than the table has lists
+        return call(e, dict(op, op=op["kind"]), ref, prefix, env)
+    if k in ("set_top_k", "refused_set_top_k"):
+        return _setting(e.set_top_k, op["k"])
+    if k in ("set_gen_logprobs", "refused_set_gen_logprobs"):
+        return _setting(e.set_gen_logprobs, op["n"])
+    if k == "set_penalties":
+        return _setting(e.set_penalties, op["p"], op["f"])
+    if k == "refused_set_penalties":
+        return _setting(e.set_penalties, *{"2.5": (2.5, 0.0), "nan": (0.5, float("nan"))}[op["bad"]])
+    if k == "set_logit_bias":
+        return _setting(e.set_logit_bias, *env["table"])
+    if k == "refused_set_logit_bias":
+        t = 7 + op["at"]
+        lists, modes = {"twice": ([[(t, 1.0), (t + 1, 0.5), (t, -1.0)]], None), "vocab": ([[(t, 1.0)], [(VOCAB, 1.0)]], None),
+                        "inf": ([[(t, float("inf"))]], None), "allow": ([[(t, NEG_INF), (t + 1, NEG_INF, 4)]], [1])}[op["bad"]]
+        return _setting(e.set_logit_bias, lists, modes)
+    if k == "read_gen_logprobs":
+        got = e.read_gen_logprobs(env.get("cap"))
+        return [tuple(np.ascontiguousarray(a).tobytes() for a in g) for g in got]
+    if k in ("score_top_many", "score_top_many_prefix", "refused_score_top"):
+        prompts = [toks(CAT[i][:2]) for i in op["reqs"]]
+        recs, tops, ranks, st = e.score_top_many(prompts, op["k"], op["score_from"], use_prefix=k == "score_top_many_prefix")
+        return _fields(recs, ("target", "max", "sum", "argmax")), _fields(tops, ("logit", "index")), [np.asarray(r) for r in ranks], st
     if k in ("forward_batch", "forward_batch_s", "refused_batch"):
         lg, am = e.forward_batch(op["tokens"], op["pos"])
         return lg, am
@@ -1284,7 +2075,7 @@ def call(e, op, ref, prefix=()):
     if k in ("batch_step_cols_draw", "refused_cols"):
         return e.batch_step_cols_draw(op["slots"], op["tokens"], op["pos"], keep=op.get("keep"), want_logits=True)
     if k in MANY or k == "refused_stop":
-        prompts, n_new, sampler, stop = _requests(op, ref, prefix if k == "generate_many_prefix" else ())
+        prompts, n_new, sampler, stop = _requests(op, ref, prefix if k == "generate_many_prefix" else (), env.get("top_k", 0), env.get("pen", (0.0, 0.0)))
         if k == "generate_many_greedy":
             return e.generate_many_greedy(prompts, n_new)
         if k == "generate_many_sampled":
@@ -1347,10 +2138,10 @@ def call(e, op, ref, prefix=()):
     raise ValueError(k)
 
 
-def outcome(e, op, ref, prefix):
+def outcome(e, op, ref, prefix, env=None):
     """call(), with a refusal turned into ("refused", code): IndexError is how the binding reports Q3_ERR_ARG"""
     try:
-        return call(e, op, ref, prefix)
+        return call(e, op, ref, prefix, env)
     except IndexError:
         return ("refused", -3)
     except RuntimeError as err:
@@ -1383,21 +2174,29 @@ def _read(e, cid, L, ctx, kvd):
 class _Lane:
     """one engine under test, the clean model beside it and the last verified copy of every cache"""
 
-    def __init__(self, engine, ref):
-        self.e, self.ref, self.m = engine, ref, FakeEngine(ref)
+    def __init__(self, engine, ref, tables=None):
+        self.e, self.ref, self.m, self.tables = engine, ref, FakeEngine(ref), tables
+        self.last_read = None                # the bytes read behind the last loop op with records
         self.snap = {"single": tuple(np.array(a, copy=True) for a in _read(engine, "single", ref.L, SEQ, ref.kvd))}
 
-    def step(self, op):
+    def step(self, op, i=None):
         m, ref = self.m, self.ref
         refusal = op["op"].startswith("refused")
         m.touched = {}
         prefix = list(m.prefix)
-        want = outcome(m, op, ref, prefix)
-        got = outcome(self.e, op, ref, prefix)
+        env = dict(top_k=m.k_top, pen=m.pen, cap=m.gen and m.gen["cap"], table=self.tables.get(i) if op["op"] == "set_logit_bias" and op["form"] != "off" else ([], None))
+        want = outcome(m, op, ref, prefix, env)
+        got = outcome(self.e, op, ref, prefix, env)
         if refusal:
             assert isinstance(want, tuple) and want[0] == "refused", f"the model accepts this call: {want!r}"
             assert not m.touched
-        assert same(got, want), f"the call returned {_short(got)}, the reference gives {_short(want)}"
+        if op["op"] == "read_gen_logprobs" and not (isinstance(want, tuple) and want[0] == "refused"):
+            # the records of the last loop call, whatever ran in between: the bytes the read behind that call returned
+            assert not (isinstance(got, tuple) and got and got[0] == "refused"), f"the read is refused ({got!r}), the reference holds records"
+            assert got == self.last_read, "read_gen_logprobs returns other bytes than the read behind the loop call"
+        else:
+            assert same(got, want), f"the call returned {_short(got)}, the reference gives {_short(want)}"
+        self.settings(op, want)
         if op["op"] == "batch_init":
             self.snap = {"single": self.snap["single"]}
         for cid in ["single"] + list(range(m.streams)):
@@ -1425,6 +2224,26 @@ class _Lane:
             assert self.e.sampler_rng_state() == m.srng, "single-stream rng state"
 
 
+    def settings(self, op, want):
+        """after every op: the four getters give the model's settings; behind a successful loop op under gen_logprobs >= 0 the records
+        are read -- every request's whole stretch of the buffers -- and held to the reference by section 2o's standard
+        (genlp_ref.assert_same): target and sum by bits, argmax equal, max by value, tops by bits and index, ranks equal; the entries at
+        and behind a request's n_out are all-zero bytes"""
+        import genlp_ref
+        e, m = self.e, self.m
+        got = (e.top_k, e.get_gen_logprobs(), tuple(e.get_penalties()), e.get_logit_bias())
+        assert got == (m.k_top, m.genlp, m.pen, m.get_logit_bias()), f"the settings read back as {_short(got)}, the reference holds {_short((m.k_top, m.genlp, m.pen, m.get_logit_bias()))}"
+        if op["op"] in MANY:
+            self.last_read = None
+            if m.gen is not None:
+                cap, n_out, k = m.gen["cap"], m.gen["got"], m.gen["k"]
+                full = e.read_gen_logprobs(cap)
+                rows = want[0]
+                genlp_ref.assert_same([tuple(a[:n] for a in f) for f, n in zip(full, n_out)], m.read_gen_logprobs(), rows, k, f"records under gen_logprobs {k}")
+                genlp_ref.assert_zero_behind(full, n_out, "records")
+                self.last_read = [tuple(np.ascontiguousarray(a).tobytes() for a in f) for f in full]
+
+
 def _where(a, b, lo, hi):
     bad = np.argwhere(_bits(np.ascontiguousarray(a)) != _bits(np.ascontiguousarray(b)))
     bad = [x for x in bad if not lo <= x[1] < hi]
@@ -1441,11 +2260,12 @@ def run(engines, ops, ref, seed=None):
     and embeddings bit for bit); every cache the op does not name, and every row of a named cache outside what the op writes, is
     bit-unchanged against the copy taken before it; the rows a cache is known to hold equal the oracle's; the resident prefix and the
     single-stream rng state are the reference's."""
-    lanes = [_Lane(e, ref) for e in (engines if isinstance(engines, (list, tuple)) else [engines])]
+    tables = Tables(ops, ref)
+    lanes = [_Lane(e, ref, tables) for e in (engines if isinstance(engines, (list, tuple)) else [engines])]
     for i, op in enumerate(ops):
         for j, lane in enumerate(lanes):
             try:
-                lane.step(op)
+                lane.step(op, i)
             except AssertionError as err:
                 raise AssertionError(f"seed {seed}, engine {j}, op {i} ({op['op']}): {err}\nops = {ops[:i + 1]!r}") from None
     return lanes

@@ -3,7 +3,10 @@ its cached column and dense plans with their graphs, its grow-only device buffer
 orders in which every kind of call follows every other, the buffers grow behind cached plans and the batched state is started over
 with other shapes.  After every op its outputs are compared with the C oracle (logits and embeddings bit for bit), every cache the op
 does not name with a copy taken before it, and the rows it fills with the oracle's.  tests/test_call_sequences_host.py holds the
-sequences to what they have to contain."""
+sequences to what they have to contain.
+The settings sequences (seq_model.SETTING_KINDS) put the engine-wide settings of sections 2m to 2q -- top_k, gen_logprobs, penalties,
+the logit-bias table -- among those calls: every loop op runs under the settings in force, its records are read and held to the
+reference behind it, and the four getters are compared after every op."""
 import numpy as np
 import pytest
 
@@ -63,3 +66,27 @@ def test_two_engines_interleaved_op_by_op(q3, models):
     seed = sm.SEEDS[-1]
     with engine(q3, path) as a, engine(q3, path, graph=False) as b:
         sm.run([a, b], sm.make_sequence(seed), ref, seed)
+
+
+@pytest.mark.parametrize("graph", [True, False], ids=["graph", "eager"])
+@pytest.mark.parametrize("seed", sm.SETTING_SEEDS)
+def test_settings_sequence(q3, models, seed, graph):
+    path, ref = models()
+    with engine(q3, path, graph) as t:
+        sm.run(t, sm.make_settings_sequence(seed), ref, seed)
+
+
+def test_settings_sequence_on_an_edge_valued_checkpoint(q3, models):
+    """tied classifier rows: the ties go to the higher index in the argmax key of a penalised or adjusted row, among the top-k
+    survivors and in the tops of the records alike"""
+    path, ref = models("all")
+    with engine(q3, path) as t:
+        sm.run(t, sm.make_settings_sequence(sm.SETTING_EDGE_SEED), ref, sm.SETTING_EDGE_SEED)
+
+
+def test_settings_on_two_engines_interleaved_op_by_op(q3, models):
+    """the settings are an engine's own: the same settings sequence on two engines of one process, one with graphs and one without"""
+    path, ref = models()
+    seed = sm.SETTING_SEEDS[-1]
+    with engine(q3, path) as a, engine(q3, path, graph=False) as b:
+        sm.run([a, b], sm.make_settings_sequence(seed), ref, seed)

@@ -287,3 +287,341 @@ def first_visible(leak, ops):
                 if moved & set(o["slots"] if k == "batch_step_cols_draw" else range(len(o.get("tokens") or o["first"]))):
                     return i
     return None
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the settings dimension (include/qwen3_hip.h sections 2m to 2q): seq_model.SETTING_KINDS among the kinds above
+# ---------------------------------------------------------------------------------------------------------------------------------
+DIGESTS = {     # sha256 of repr(make_sequence(seed)), taken on the commit in front of the settings dimension: the pair matrix is what it was
+    11: "4d26709c8664306e778e3935a9a79ee3731cc9791167a553be0de85ea8850acf", 12: "8f61442e23a555efdbcb9cddb7762a2497c88d289fd50912a62fcd5aff472bb8",
+    13: "41e7a79d99faddfde6dccaa81fc0af81896052396cb734edf1c8c9369becd5e1", 14: "9e9d1748b9ba0c5cda6ffca017c83244765417bbeac585650c41272d55c6fd8e",
+    15: "cdd530f7a7bfb5e54d4f0b486f339f23bd39a643dd461f38ec7abbe62938ac64", 16: "b91985aa91249373f3ba4a5d1eabdf76506eedb2caa2367134fe9ed169b9ce7c",
+    17: "c91d2c4bb98a9e2f2e4161cf204c7b6c21af20c35f82527b8ee6682fba607353", 18: "c4f859fa9092c7a6d09daf99028cbc6106ddec695abd20795bb40f1e0931eda7",
+    19: "1392baa1e8b453a6a9db6f560c4598440b3e550b45983f7c7311e2280f296702", 20: "e73478e01c08389f201268a7551a82724fdcb88d09bf41823c700a34844c6c16",
+    21: "662ba61668959c62606c6c8a938bf95aea9c3755c4601b1d409a32c3db9874fb", 22: "561bf964657cec81481be031f1421f812d180a565c4d69e42fe5d84440b55f30",
+}
+SETTINGS = ("top_k", "genlp", "pen", "bias")
+
+
+def test_the_twelve_sequences_are_what_they_were(sequences):
+    import hashlib
+    assert set(DIGESTS) == set(sm.SEEDS)
+    for seed, ops in sequences.items():
+        assert hashlib.sha256(repr(ops).encode()).hexdigest() == DIGESTS[seed], seed
+    assert not set(sm.SETTING_KINDS) & set(sm.KINDS) and len(sm.CAT) == 115 and len(sm.KINDS) == 45
+    assert [c[2] for c in sm.CAT[91:]] and all(6 <= c[2] <= 12 and 2 <= c[1] <= 40 for c in sm.CAT[91:])
+    assert {2, 40} <= {c[1] for c in sm.CAT[91:]}
+
+
+@pytest.fixture(scope="module")
+def ssequences(q3):
+    return {seed: sm.make_settings_sequence(seed) for seed in sm.SETTING_SEEDS}
+
+
+def swalk(ops):
+    """per op: dict(epoch, st = the settings in force in front of it, on = the settings that are on, nd = seq_model.needs with the
+    forms of a loop op, streams, draw = a loop op runs sampled plans)"""
+    st = sm.settings_walk(ops)
+    streams = epoch = 0
+    sampling, prefix_len = False, 0
+    out = []
+    for i, op in enumerate(ops):
+        k = op["op"]
+        before = streams
+        if k == "batch_init":
+            epoch += 1
+            streams, sampling, prefix_len = op["streams"], False, 0
+        rows, stop = None, ()
+        if k in ("generate_many_stop", "generate_many_prefix") and op["stop_at"]:
+            rows, stop = [[0] * sm.CAT[j][2] for j in op["reqs"]], (1,)
+        known = k in sm.KINDS or k in ("score_top_many", "score_top_many_prefix")
+        table = ops[st[i]["table"]] if st[i]["table"] is not None else None
+        nd = sm.needs(op, streams, sampling, prefix_len, rows, stop, st=st[i], table=table) if known and not k.startswith("refused") else None
+        s = st[i]
+        on = tuple(n for n, v in zip(SETTINGS, (s["top_k"] > 0, s["genlp"] >= 0, any(s["pen"]), s["table"] is not None)) if v)
+        out.append(dict(epoch=epoch, st=s, on=on, nd=nd, streams=streams, before=before, draw=k == "generate_many_sampled" or bool(op.get("sampled")),
+                        form=table["form"] if table else "off"))
+        if k == "set_batch_sampler_on":
+            sampling = True
+        elif k == "set_batch_sampler_off":
+            sampling = False
+        elif k == "batch_prefix_set":
+            prefix_len = op["prompt"][1]
+    return out
+
+
+def value_of(info, name):
+    s = info["st"]
+    return {"top_k": s["top_k"], "genlp": s["genlp"], "pen": s["pen"], "bias": info["form"]}[name]
+
+
+def test_the_setting_kinds_and_their_values(ssequences):
+    seen = {k: set() for k in sm.SETTING_KINDS}
+    per_modes, longest, untils, zeros = set(), 0, 0, set()
+    for seed, ops in ssequences.items():
+        assert all(o["op"] in sm.KINDS + sm.SETTING_KINDS for o in ops)
+        assert eval(repr(ops)) == ops                      # the literal of a failure message
+        assert ops == sm.make_settings_sequence(seed)
+        for o in ops:
+            k = o["op"]
+            if k in seen:
+                seen[k].add(o.get("k", o.get("n", (o.get("p"), o.get("f")) if k == "set_penalties" else o.get("bad"))) if k != "set_logit_bias" else o["form"])
+            if k == "set_logit_bias" and o["form"] != "off":
+                lens, modes = sm.table_lens(o)
+                longest = max(longest, max(lens))
+                if o["form"] == "per":
+                    per_modes |= set(modes)
+    assert seen["set_top_k"] == set(sm.TOP_KS) == {0, 1, 5, 20, 64}
+    assert seen["set_gen_logprobs"] == set(sm.GEN_LPS) == {-1, 0, 3, 64}
+    pens = seen["set_penalties"]
+    assert pens == set(sm.PENALTIES) and (0.0, 0.0) in pens and len(pens) >= 4
+    assert any(p < 0 for p, f in pens) and any(f < 0 for p, f in pens) and any(p > 0 and f > 0 for p, f in pens)
+    assert all(-2 <= v <= 2 for pf in pens for v in pf)
+    assert seen["set_logit_bias"] == set(sm.BIAS_FORMS) and per_modes == {0, 1} and longest >= 300
+    assert seen["refused_set_top_k"] == {65, -1} and seen["refused_set_gen_logprobs"] == {-2, 65}
+    assert seen["refused_set_penalties"] == {"2.5", "nan"} and seen["refused_set_logit_bias"] == {"twice", "vocab", "inf", "allow"}
+    assert seen["refused_score_top"] == {0, 65}
+    assert {1, 5, 64} <= seen["score_top_many"] | seen["score_top_many_prefix"] and seen["score_top_many_prefix"]
+    assert seen["read_gen_logprobs"] and seen["refused_bias_lists"]
+
+
+def test_the_reads_of_the_records(ssequences):
+    """read_gen_logprobs stands where it is refused for each of the header's reasons, right behind a loop op with records and behind
+    ops of other kinds with the records still there"""
+    seen, behind = set(), set()
+    for ops in ssequences.values():
+        left = "none"
+        for i, (op, f) in enumerate(zip(ops, swalk(ops))):
+            k = op["op"]
+            if k == "batch_init":
+                left = "none"                                   # no loop call under the setting since q3_batch_init
+            elif k in sm.MANY:
+                left = "records" if f["st"]["genlp"] >= 0 else "off"
+            elif k in ("refused_stop", "refused_bias_lists"):
+                left = "failed"
+            elif k == "read_gen_logprobs":
+                seen.add(left)
+                if left == "records":
+                    behind.add("loop" if ops[i - 1]["op"] in sm.MANY else "read" if ops[i - 1]["op"] == k else "setter" if ops[i - 1]["op"] in sm.SETTERS else "other")
+    assert seen == {"none", "off", "failed", "records"}, seen
+    assert behind == {"loop", "read", "setter", "other"} or behind >= {"loop", "setter", "other"}, behind
+
+
+def test_every_loop_variant_under_every_value_class(ssequences, capsys):
+    ran = set()                     # (kind, sampled, the state of the four settings by value class)
+    forms, hits = {}, {}
+    for seed, ops in ssequences.items():
+        info = swalk(ops)
+        built = {}
+        for i, (op, f) in enumerate(zip(ops, info)):
+            if op["op"] not in sm.MANY:
+                continue
+            ran.add((op["op"], f["draw"], tuple(value_of(f, n) for n in SETTINGS)))
+            for key in f["nd"]["forms"]:
+                at = (seed, f["epoch"]) + key
+                built[at] = built.get(at, 0) + 1
+        for at, n in built.items():
+            forms[at[2:6]] = forms.get(at[2:6], 0) + 1
+            if n >= 2:
+                hits[at[2:6]] = hits.get(at[2:6], 0) + 1
+    off = (0, -1, (0.0, 0.0), "off")
+    missing = []
+    for kind, sampled in sm.VARIANTS:
+        alone = ([(v,) + off[1:] for v in sm.TOP_KS[1:]] + [(0, v) + off[2:] for v in sm.GEN_LPS[1:]] + [off[:2] + (v, "off") for v in sm.PENALTIES[1:]]
+                 + [off[:3] + (v,) for v in sm.BIAS_FORMS[1:]])
+        missing += [(kind, sampled, s) for s in alone if (kind, sampled, s) not in ran]
+        on = lambda s: tuple(a != b for a, b in zip(s, off))
+        masks = {on(s) for k, d, s in ran if (k, d) == (kind, sampled)}
+        missing += [(kind, sampled, m) for m in [tuple(i in (a, b) for i in range(4)) for a in range(4) for b in range(a + 1, 4)] + [(True,) * 4] if m not in masks]
+    assert not missing, f"{len(missing)} (loop kind, sampled, state) never run: {missing[:10]}"
+    # the column plans by their key.  The library keeps top_k on sampled plans alone (plan_get clears PlanKey::topk on a greedy
+    # plan), so 27 forms exist, not 36: the nine (draw 0, topk 1) cannot be reached by any sequence.
+    exist = {(d, t, g, p) for d in (False, True) for t in (False, True) for g in range(3) for p in range(3) if d or not t}
+    with capsys.disabled():
+        print(f"\ncolumn-plan forms (draw, topk, genlp, pen) reached, with the (seed, epoch, width)s that run them: "
+              + ", ".join(f"{tuple(int(v) for v in k)}: {n}" for k, n in sorted(forms.items())))
+        print(f"{len(forms)} of the {len(exist)} forms that exist; not reached: {sorted(tuple(int(v) for v in k) for k in exist - set(forms))}")
+    assert set(forms) <= exist and len(forms) >= 27
+    assert set(hits) == set(forms), f"forms never run a second time on a kept plan: {sorted(set(forms) - set(hits))}"
+
+
+def test_every_transition_under_kept_plans(ssequences, capsys):
+    found, pairs = {}, set()
+    for seed, ops in ssequences.items():
+        info = swalk(ops)
+        pairs |= sm.pairs_of(ops)
+        built, epoch = set(), 0
+        reuse_at, new_at = {}, {}               # per loop op: does it run a kept (form, width), does it build one
+        snap = {}
+        for i, (op, f) in enumerate(zip(ops, info)):
+            if f["epoch"] != epoch:
+                built, epoch = set(), f["epoch"]
+            snap[i] = set(built)
+            if op["op"] in sm.MANY:
+                reuse_at[i], new_at[i] = bool(f["nd"]["forms"] & built), bool(f["nd"]["forms"] - built)
+                built |= f["nd"]["forms"]
+        for i, op in enumerate(ops[:-1]):
+            if op["op"] not in sm.SETTERS:
+                continue
+            name = SETTINGS[sm.SETTERS.index(op["op"])]
+            off = {"top_k": 0, "genlp": -1, "pen": (0.0, 0.0), "bias": "off"}[name]
+            a, b = value_of(info[i], name), value_of(info[i + 1], name)
+            what = "off->on" if a == off != b else "on->off" if a != off == b else "on->other" if a != b or (name == "bias" and a != off) else None
+            if what is None:
+                continue
+            # the column plans of both neighbouring forms exist in the epoch (on either draw side)
+            both = any({sm.form_of(d, info[i]["st"]), sm.form_of(d, info[i + 1]["st"])} <= {k[:4] for k in snap[i]} for d in (False, True))
+            end = next((j for j in range(i + 1, len(ops)) if ops[j]["op"] in (op["op"], "batch_init")), len(ops))
+            loops = [j for j in range(i + 1, end) if j in reuse_at]
+            if both and any(reuse_at[j] for j in loops) and any(new_at[j] for j in loops):
+                found.setdefault((name, what), []).append((seed, i))
+    with capsys.disabled():
+        print("\ntransitions under kept plans of both forms, a loop op on kept widths and one that builds a width behind them: "
+              + ", ".join(f"{n} {w}: {len(v)}" for (n, w), v in sorted(found.items())))
+    for name in SETTINGS:
+        for what in ("off->on", "on->other", "on->off"):
+            assert (name, what) in found, (name, what)
+    missing = [(a, b) for a in sm.SETTING_KINDS for b in sm.MANY if (a, b) not in pairs] + [(b, a) for a in sm.SETTING_KINDS for b in sm.MANY if (b, a) not in pairs]
+    assert not missing, f"{len(missing)} (setting kind, loop kind) pairs never adjacent: {missing}"
+
+
+def test_every_setting_in_force_across_state_changes(ssequences):
+    across = {}
+    quiet = set()
+    for seed, ops in ssequences.items():
+        info = swalk(ops)
+        for i, (op, f) in enumerate(zip(ops, info)):
+            k = op["op"]
+            later = any(o["op"] in sm.MANY for o in ops[i + 1:])
+            if k == "batch_init" and i and later:
+                for name in f["on"]:
+                    across.setdefault((name, "batch_init"), set()).add("larger" if op["streams"] > f["before"] else "other" if op["streams"] != f["before"] else "same")
+            if k in ("set_sampler", "set_batch_sampler_on", "set_batch_sampler_off", "batch_reset_kv") and later:
+                for name in f["on"]:
+                    across.setdefault((name, k), set()).add("x")
+            if len(f["on"]) == 4 and len(info[min(i + 1, len(ops) - 1)]["on"]) == 4 and later:
+                quiet.add(k)
+    for name in SETTINGS:
+        assert {"larger", "other"} <= across.get((name, "batch_init"), set()), (name, across.get((name, "batch_init")))
+        for k in ("set_sampler", "set_batch_sampler_on", "set_batch_sampler_off", "batch_reset_kv"):
+            assert (name, k) in across, (name, k)
+    missing = [k for k in sm.KINDS if k not in sm.MANY and k not in quiet]
+    assert not missing, f"kinds that never run under all four settings: {missing}"
+
+
+def test_the_settings_buffers_grow_twice_behind_cached_plans(ssequences, capsys):
+    """the rule of test_every_grow_only_buffer_grows_twice_behind_cached_plans for the per-call buffers of sections 2m, 2o and 2q"""
+    for seed, ops in ssequences.items():
+        info = swalk(ops)
+        grown = {b: [] for b in sm.SETTING_BUFFERS}
+        best = {}
+        cap = {}
+        cols_built, dense_built, cols_hit, dense_hit = set(), set(), False, False
+        last_epoch = 0
+        for i, f in enumerate(info):
+            epoch, nd = f["epoch"], f["nd"]
+            if epoch != last_epoch:
+                cap, cols_built, dense_built, cols_hit, dense_hit, last_epoch = {}, set(), set(), False, False, epoch
+            if nd is None:
+                continue
+            plans = nd.get("forms") or nd["cols"]
+            for b, n in nd["need"].items():
+                if b in grown and n > best.get(b, 0) and cap.get(b, 0) > 0 and cols_hit and dense_hit:
+                    later = [j for j in range(i + 1, len(ops)) if info[j]["epoch"] == epoch and ops[j]["op"] == ops[i]["op"] and info[j]["nd"]
+                             and 0 < info[j]["nd"]["need"].get(b, 0) < n]
+                    if later:
+                        grown[b].append(i)
+                best[b] = max(best.get(b, 0), n)
+                if b == "att_pf" and n > cap.get(b, 0):
+                    dense_built = set()
+                cap[b] = max(cap.get(b, 0), n)
+            cols_hit |= bool(plans & cols_built)
+            dense_hit |= bool(nd["dense"] & dense_built)
+            cols_built |= plans
+            dense_built |= nd["dense"]
+        with capsys.disabled():
+            print(f"\nseed {seed}: calls that grow a settings buffer behind cached plans, a smaller one following: " + ", ".join(f"{b} {len(v)}" for b, v in grown.items()), end="")
+        for b, v in grown.items():
+            assert len(v) >= 2, f"seed {seed}: {b} grows {len(v)} times ({v})"
+
+
+def test_slots_are_reused_under_penalties(ssequences):
+    reused = per_request = 0
+    for ops in ssequences.values():
+        for op, f in zip(ops, swalk(ops)):
+            if op["op"] in sm.MANY and "pen" in f["on"] and len(op["reqs"]) > f["streams"]:
+                reused += 1
+                per_request += f["form"] == "per"
+    assert reused >= 10 and per_request >= 4, (reused, per_request)
+
+
+def test_the_settings_bind(ssequences, reference, capsys):
+    """non-vacuity, from Reference alone: the penalties, the tables and top_k change the rows of the ops that run under them"""
+    pen = pen_differs = twice = table = sampled_k = k_differs = 0
+    for seed, ops in ssequences.items():
+        tables = sm.Tables(ops, reference)
+        for j, (op, f) in enumerate(zip(ops, swalk(ops))):
+            if op["op"] not in sm.MANY:
+                continue
+            rows = tables.rows(j)
+            if "pen" in f["on"]:
+                pen += 1
+                pen_differs += rows != tables.rows(j, pen=(0.0, 0.0))
+                twice += any(len(set(r)) < len(r) for r in rows)
+            if "bias" in f["on"]:
+                table += 1
+                assert rows != tables.rows(j, table=False), f"seed {seed}, op {j}: the table changes nothing"
+                assert all(a != b for a, b in zip(rows, tables.rows(j, table=False))), f"seed {seed}, op {j}: a request the table leaves alone"
+            if f["draw"] and f["st"]["top_k"] in (1, 5) and any(sm.CAT[i][3] > 0 for i in op["reqs"]):
+                sampled_k += 1
+                k_differs += rows != tables.rows(j, top_k=0)
+    with capsys.disabled():
+        print(f"\nloop ops under penalties: {pen}, rows differ from (0, 0) in {pen_differs}, a count reaches 2 in {twice}; under a table: {table}, all differ; "
+              f"sampled under top_k 1 or 5: {sampled_k}, rows differ from top_k 0 in {k_differs}")
+    assert pen and 2 * pen_differs >= pen and twice >= 10
+    assert table and sampled_k and 2 * k_differs >= sampled_k
+
+
+def test_the_harness_catches_the_settings_leaks(ssequences, reference, capsys):
+    import time
+    t0 = time.time()
+    for seed, ops in ssequences.items():
+        sm.run(sm.FakeEngine(reference), ops, reference, seed)
+    with capsys.disabled():
+        print(f"\n{sum(len(o) for o in ssequences.values())} ops on the fake engine in {time.time() - t0:.1f} s")
+    for leak in sm.SETTING_LEAKS:
+        caught = {}
+        for seed, ops in ssequences.items():
+            try:
+                sm.run(sm.FakeEngine(reference, leak=leak), ops, reference, seed)
+            except AssertionError as err:
+                msg = str(err)
+                assert msg.startswith(f"seed {seed}, engine 0, op ") and "\nops = [" in msg
+                at = int(msg.split("op ")[1].split(" ")[0])
+                assert eval(msg.split("\nops = ")[1]) == ops[:at + 1]
+                caught[seed] = (at, ops[at]["op"])
+        with capsys.disabled():
+            print(f"leak {leak!r} first shows at (op, kind) per seed: {caught}")
+        assert len(caught) >= 4, f"leak {leak!r} shows in {len(caught)} of {len(ssequences)} seeds"
+        for seed, (at, _) in caught.items():            # where the leaked state can be told from the ops alone: at that op, no later
+            first = settings_first_visible(leak, ssequences[seed])
+            assert first is None or at == first, f"leak {leak!r}, seed {seed}: reported at op {at}, visible from op {first}"
+
+
+def settings_first_visible(leak, ops):
+    """the first op behind which the leaked state is observable through the API, for the leaks whose place the ops alone tell"""
+    info = swalk(ops)
+    if leak == "topk_init":              # q3_sampler_get_top_k behind the first q3_batch_init under top_k > 0
+        return next((i for i, o in enumerate(ops) if o["op"] == "batch_init" and info[i]["st"]["top_k"] > 0), None)
+    if leak == "score_top_shared":       # the first score call with tops behind a loop op with tops in the same batched state
+        tops = False
+        for i, o in enumerate(ops):
+            if o["op"] == "batch_init":
+                tops = False
+            elif o["op"] in sm.MANY:
+                tops = info[i]["st"]["genlp"] > 0
+            elif o["op"] in ("score_top_many", "score_top_many_prefix") and tops:
+                return i
+    if leak == "genlp_penalised":        # the first loop op with records under penalties or a table: its sums are the adjusted row's
+        return next((i for i, o in enumerate(ops) if o["op"] in sm.MANY and info[i]["st"]["genlp"] >= 0 and {"pen", "bias"} & set(info[i]["on"])), None)
+    return None
