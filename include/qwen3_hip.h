@@ -1044,6 +1044,62 @@ int q3_op_logit_bias(const float* logits, size_t n, const q3_bias_entry* entries
                      const uint32_t* counts /* or NULL: no penalties */, float presence, float frequency, float* out /* [n] */, int32_t* argmax,
                      int device);
 
+/* ------------------------------------------------------------------------------------------------
+ * 2r. (behind 2q so that the earlier sections stay as they were.)  Guided decoding: a constraint that changes with what the request
+ * has produced so far -- one of several multi-token labels, a regular expression, a fixed JSON skeleton, multi-token banned
+ * sequences -- as a token automaton whose state lives on the device beside the KV slot and advances where the token is committed,
+ * inside the five q3_generate_many_* loops.
+ * THE RULE.  A GUIDE is a table next[n_states][V] of int16_t: next[s][v] >= 0, in state s token v may come and leads to that state;
+ * -1, it may not; and a list start[].  Request r is about to produce y_g from classifier row l[0 .. V):
+ *     start state   s_0 = start[r], or start[0] where there is one entry.  s_0 == -1: the request is unguided, its row is l and it
+ *                   advances no state.
+ *     masked row    m[v] = l[v] (the same bits) where next[s_g][v] >= 0, bits 0xFF800000 (-inf) otherwise.
+ *     bias          section 2q's table, if set, applies to m in place of l; section 2p's penalties on top, exactly as there.
+ *     downstream    everything downstream takes that row as 2q defines it: greedy and temperature-0 requests the largest key, equal
+ *                   values to the HIGHER index; sampled requests Sampler::sample or section 2n's draw among the top_k; one coin per
+ *                   draw.
+ *     state step    after the commit s_{g+1} = next[s_g][y_g] where that is >= 0, else s_g.
+ * THE ELSE BRANCH OF THE STATE STEP IS REACHABLE: the sampler's fall-through (2q: index n - 1 ... is kept as it is) and a row with
+ * no finite entry -- a bias table that bans a state's only tokens, the caller's mistake, under greedy it commits V - 1 by the key
+ * rule -- can commit a token the state forbids.  The state then stays.  Only indices clamped to their arrays become addresses.
+ * As in 2q THE RULE HOLDS FOR y_0 TOO, SECTION 2o's RECORDS STAY ON THE RAW ROW l with the committed token as target, and the stop
+ * decision, the schedule, the cache rows and the coins of discarded prompt positions are unchanged.  Termination stays with the
+ * stop tokens: an automaton that wants to end lets EOS through in its accepting states.
+ * What runs (csrc/q3_guide.h).  One more form on the fourth axis of the column plans (off / penalties / adjusted / masked), chosen
+ * whenever a guide is set, whatever the table and the penalties, built on first use.  k_guide_apply stands where k_bias_apply
+ * stands, with its grid, slices and outputs: it reads the state -- start[r] where g == 0, else the KV slot's -- streams the state's
+ * row of the table beside the logits, then applies 2q and 2p as k_bias_apply does (with no table: one empty ADD list).
+ * k_guide_step stands where k_bias_count stands: it writes the slot's next state from the token about to be committed, starting
+ * from start[r] for g == 0 so that a reused slot needs no reset, then counts where penalties are set.  The table goes to the device
+ * once per q3_guide_set (and again after q3_batch_init), at the first generate call under it; start[] and a control block go with
+ * every call.  The plans point at the control block: two guides share every plan and graph.  With no guide set every entry point
+ * launches exactly what it launched before this section existed.
+ * IT DOES NOT TOUCH q3_batch_step_cols[_draw], section 2b, the verify paths, single-stream decode, q3_embed_many, q3_choice_many,
+ * q3_score_many or q3_score_top_many.
+ * ------------------------------------------------------------------------------------------------ */
+#define Q3_GUIDE_MAX_STATES 4096
+
+/* The engine-wide guide, default none = off.  n_states == 0 turns it off.  n_start == 1: every request of every call starts in
+ * start[0]; n_start > 1: request r starts in start[r], and a q3_generate_many_* call whose n_requests != n_start returns Q3_ERR_ARG
+ * before anything runs.  The library keeps a copy of both arrays.  The guide holds for every token q3_generate_many_greedy,
+ * _sampled, _dense, _stop and _prefix produce, and survives q3_sampler_set, q3_batch_sampler_set, q3_batch_init, q3_sampler_top_k,
+ * q3_gen_logprobs, q3_sampler_penalties, q3_logit_bias_set and every generate call.
+ * Execution: waits for the stream; the device side is made by the first generate call under a guide.
+ * Q3_ERR_ARG, checked before the engine or the GPU is touched: a null array with a non-zero count; n_states > Q3_GUIDE_MAX_STATES;
+ * n_start == 0 with states; a start outside [-1, n_states); an entry of next outside [-1, n_states); a state whose row allows no
+ * token; vocab == 0 or vocab >= 2^31.  Then the null engine, then vocab != vocab_size.  A refused call changes nothing. */
+int q3_guide_set(q3_engine* e, const int16_t* next /* [n_states][vocab] */, size_t n_states, size_t vocab,
+                 const int32_t* start /* [n_start] */, size_t n_start);
+int q3_guide_get(const q3_engine* e, size_t* n_states, size_t* n_start);
+
+/* The rule above on a host vector: k_guide_apply once over logits[0 .. n) for a request in the state whose row of the table is
+ * next_row[0 .. n), at output index g with the one list given (n_entries == 0: none), then the penalties over counts[0 .. n) where
+ * counts is not NULL.  out receives the row, argmax the index of its largest key.  Q3_ERR_ARG (before anything touches the GPU):
+ * what q3_op_logit_bias refuses, and a null next_row. */
+int q3_op_guide(const float* logits, size_t n, const int16_t* next_row /* [n] */, const q3_bias_entry* entries, size_t n_entries,
+                int mode, uint32_t g, const uint32_t* counts /* or NULL: no penalties */, float presence, float frequency, float* out /* [n] */,
+                int32_t* argmax, int device);
+
 #ifdef __cplusplus
 }
 #endif

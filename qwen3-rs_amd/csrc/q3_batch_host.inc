@@ -23,7 +23,8 @@ enum class PlanKind { Decode, Prefill, Verify, Cols, SlotPrefill };
 // behind the classifier, the draws and the turn kernel take the penalised rows, k_pen_count stands in front of the turn kernel
 // (q3_penalty.h); the values of the setting are read from device memory when a pass runs.  kPenAdj (cols_key sets it where a table
 // of q3_logit_bias_set holds, section 2q): k_bias_apply and k_bias_count (q3_bias.h) stand in their places, and whether penalties apply
-// on top is read from device memory when a pass runs (kPenOff / kPenOn / kPenAdj: q3_bias.h)
+// on top is read from device memory when a pass runs (kPenOff / kPenOn / kPenAdj: q3_bias.h).  kPenGuide (where a guide of q3_guide_set
+// holds, section 2r, whatever the table and the penalties): k_guide_apply and k_guide_step (q3_guide.h) stand in those places
 enum { kGenlpOff = 0, kGenlpRecs = 1, kGenlpTop = 2, kGenlpForms = 3 };
 struct PlanKey {
     PlanKind kind = PlanKind::Decode;
@@ -114,13 +115,13 @@ struct BatchCtx {
     DevMem<int> col_slot;        // device [kColsMax]: KV slot of every column of the pass in flight
     DevMem<ColsCtl> cols_ctl;    // device
     PinMem<ColsHost> h_cols;
-    Plan cols_plans[kPenForms][kGenlpForms][3][kColsNW];   // [plain | under penalties | adjusted rows][no records | records | records and top][greedy |
+    Plan cols_plans[kPenForms][kGenlpForms][3][kColsNW];   // [plain | under penalties | adjusted rows | masked rows][no records | records | records and top][greedy |
                                                         // sampled | sampled with top-k][width], built on first use (q3_batch_init
                                                         // starts over); the sampled ones: the same layers and classifier, then the
                                                         // draws and k_cols_turn_draw; with records: the record launches in front of
                                                         // the turn kernel; under penalties: k_pen_apply behind the classifier and
                                                         // k_pen_count in front of the turn kernel; adjusted rows: k_bias_apply and
-                                                        // k_bias_count in their places
+                                                        // k_bias_count in their places; masked rows: k_guide_apply and k_guide_step
     DevMem<ColEnt> cols_table;                          // the loop's pass table, prompts and output: grow-only device buffers
     DevMem<int> cols_ncols;
     DevMem<int32_t> cols_prompts, cols_out;
@@ -196,6 +197,14 @@ struct BatchCtx {
     DevMem<unsigned> bias_off;
     DevMem<unsigned char> bias_modes;
     DevMem<int> bias_ooff;
+    // the guide of q3_guide_set (section 2r; guide_alloc and guide_call_begin, q3_plan_host.inc): the control block the plans of the
+    // masked form point at and the state of the request in every KV slot [max_streams], made once; the table, uploaded when
+    // guide_serial is not the serial of the engine's guide (a new q3_guide_set, or this context is new); start[] of the call in flight
+    DevMem<GuideCtl> guide_ctl;
+    DevMem<int> guide_state;
+    DevMem<short> guide_next;
+    DevMem<int> guide_start;
+    unsigned long long guide_serial = 0;
     // packed-matrix directory
     struct PM { size_t q_off, s_off; int ntiles, ng; };
     std::vector<PM> m_qkv, m_wo, m_w13, m_w2;

@@ -26,8 +26,9 @@ constexpr int kBiasMax = 4096;          // Q3_BIAS_MAX
 enum { kBiasAdd = 0, kBiasAllow = 1 };  // Q3_BIAS_ADD, Q3_BIAS_ALLOW
 
 // the forms of a column plan on the PlanKey::pen axis (q3_batch_host.inc): the classifier's rows as they are, section 2p's penalised
-// rows, or the adjusted rows of this header with or without penalties on top
-enum { kPenOff = 0, kPenOn = 1, kPenAdj = 2, kPenForms = 3 };
+// rows, the adjusted rows of this header with or without penalties on top, or the masked rows of q3_guide.h (section 2r) with or
+// without a table of this header and penalties on top
+enum { kPenOff = 0, kPenOn = 1, kPenAdj = 2, kPenGuide = 3, kPenForms = 4 };
 
 struct BiasEntry {                      // q3_bias_entry
     int token;

@@ -75,6 +75,8 @@ int cols_requests_check(q3_engine* e, const int32_t* prompts, const size_t* prom
     if (n_requests > (size_t)INT32_MAX / 5) return fail(Q3_ERR_ARG, "more than 2^31 / 5 requests in one call");
     if (e->bias.n_lists() > 1 && e->bias.n_lists() != n_requests)
         return fail(Q3_ERR_ARG, "q3_logit_bias_set holds %zu lists, one per request, and the call has %zu requests", e->bias.n_lists(), n_requests);
+    if (e->guide.n_states && e->guide.start.size() > 1 && e->guide.start.size() != n_requests)
+        return fail(Q3_ERR_ARG, "q3_guide_set holds %zu start states, one per request, and the call has %zu requests", e->guide.start.size(), n_requests);
     for (size_t r = 0; draw && r < n_requests; ++r)
         if ((rc = sampler_check(temperature[r], topp[r], (long)r))) return rc;
     rq.prompts = prompts;
@@ -581,6 +583,7 @@ int cols_generate(q3_engine* e, const ColsRequests& rq, int32_t* out_tokens, q3_
     const ColsJobSampler smp{b->cols_slot_samp, rq.temperature, rq.topp, rq.seeds, n_requests, false};
     const int pen = e->pen_form();
     if (pen == kPenAdj && (rc = bias_call_begin(e, rq.o_off.data(), n_requests, rq.n_out))) return rc;     // the call's table, on the stream in front of its passes
+    if (pen == kPenGuide && (rc = guide_call_begin(e, rq.o_off.data(), n_requests, rq.n_out))) return rc;  // the call's guide and table (section 2r)
     if ((rc = cols_job_run(e, job, draw, smp, rq.prompts, rq.n_prompt, out_tokens, rq.n_out, e->gen_logprobs, pen))) return rc;
     if (stats) *stats = s.stats;
     if (dstats) *dstats = dst;
@@ -760,6 +763,35 @@ int q3_logit_bias_get(const q3_engine* e, size_t* n_lists, size_t* n_entries_tot
     if (!e || !n_lists || !n_entries_total) return fail(Q3_ERR_ARG, "null argument");
     *n_lists = e->bias.n_lists();
     *n_entries_total = e->bias.entries.size();
+    return Q3_OK;
+}
+
+/* ---- section 2r: guided decoding ---- */
+
+int q3_guide_set(q3_engine* e, const int16_t* next, size_t n_states, size_t vocab, const int32_t* start, size_t n_start) {
+    g_err[0] = 0;
+    if (int rc = guide_check(next, n_states, vocab, start, n_start)) return rc;
+    if (!e) return fail(Q3_ERR_ARG, "null engine");
+    if (n_states && vocab != (size_t)e->cfg.vocab_size) return fail(Q3_ERR_ARG, "a guide over %zu tokens (vocab_size %d)", vocab, e->cfg.vocab_size);
+    GuideTable t;
+    if (n_states) {
+        t.next.assign(next, next + n_states * vocab);
+        t.start.assign(start, start + n_start);
+        t.n_states = n_states;
+        t.vocab = vocab;
+    }
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    t.serial = ++e->guide_serial;
+    e->guide = std::move(t);
+    return Q3_OK;
+}
+
+int q3_guide_get(const q3_engine* e, size_t* n_states, size_t* n_start) {
+    g_err[0] = 0;
+    if (!e || !n_states || !n_start) return fail(Q3_ERR_ARG, "null argument");
+    *n_states = e->guide.n_states;
+    *n_start = e->guide.start.size();
     return Q3_OK;
 }
 

@@ -46,6 +46,7 @@
 #include "q3_genlp.h"
 #include "q3_penalty.h"
 #include "q3_bias.h"
+#include "q3_guide.h"
 #include "q3_lookup.h"
 
 namespace {
@@ -138,6 +139,42 @@ int bias_check(const q3_bias_entry* entries, const size_t* n_entries, const uint
         at += n;
     }
     out.off[n_lists] = (unsigned)at;
+    return Q3_OK;
+}
+
+// The guide of q3_guide_set as the engine keeps it (section 2r).  serial: which q3_guide_set made it, so the batched state knows
+// whether the table it holds on the device is this one (guide_call_begin, q3_plan_host.inc).
+struct GuideTable {
+    std::vector<int16_t> next;           // [n_states][vocab]; empty: no guide
+    std::vector<int> start;              // [n_start]
+    size_t n_states = 0, vocab = 0;
+    unsigned long long serial = 0;
+};
+
+// What q3_guide_set refuses about a guide, the engine and the GPU untouched: a null array with a non-zero count, more than
+// kGuideMaxStates states, states without a start entry, vocab == 0 or >= 2^31, a start or an entry of next outside [-1, n_states),
+// a state whose row allows no token.
+int guide_check(const int16_t* next, size_t n_states, size_t vocab, const int32_t* start, size_t n_start) {
+    if (!next && n_states) return fail(Q3_ERR_ARG, "null next with %zu states", n_states);
+    if (!start && n_start) return fail(Q3_ERR_ARG, "null start with %zu entries", n_start);
+    if (n_states == 0) return Q3_OK;
+    if (n_states > (size_t)kGuideMaxStates) return fail(Q3_ERR_ARG, "%zu states, at most %d", n_states, kGuideMaxStates);
+    if (vocab == 0 || vocab > (size_t)INT32_MAX) return fail(Q3_ERR_ARG, "a guide over %zu tokens: 1 .. 2^31 - 1", vocab);
+    if (n_start == 0) return fail(Q3_ERR_ARG, "%zu states and no start state", n_states);
+    if (n_start > (size_t)INT32_MAX) return fail(Q3_ERR_ARG, "more than 2^31 start states");
+    for (size_t r = 0; r < n_start; ++r)
+        if (start[r] < -1 || start[r] >= (int32_t)n_states)
+            return fail(Q3_ERR_ARG, "start[%zu] = %d: -1 (unguided) or a state below %zu", r, start[r], n_states);
+    for (size_t s = 0; s < n_states; ++s) {
+        const int16_t* row = next + s * vocab;
+        bool any = false;
+        for (size_t v = 0; v < vocab; ++v) {
+            if (row[v] < -1 || (size_t)(row[v] + 1) > n_states)
+                return fail(Q3_ERR_ARG, "next[%zu][%zu] = %d: -1 (forbidden) or a state below %zu", s, v, (int)row[v], n_states);
+            any |= row[v] >= 0;
+        }
+        if (!any) return fail(Q3_ERR_ARG, "state %zu allows no token", s);
+    }
     return Q3_OK;
 }
 
@@ -442,8 +479,13 @@ struct q3_engine {
     // logit bias, banned and allowed tokens (q3_logit_bias_set, section 2q): engine-wide, no list = off.  Every generate call under a
     // table sends it to the device (bias_call_begin, q3_plan_host.inc)
     BiasTable bias;
-    // the form of the column plans the q3_generate_many_* loops run (PlanKey::pen): under a table the adjusted one, whatever the penalties
-    int pen_form() const { return bias.n_lists() ? kPenAdj : (pen_on() ? kPenOn : kPenOff); }
+    // the guide (q3_guide_set, section 2r): engine-wide, no state = off.  Its table goes to the device once, start[] with every
+    // generate call under it (guide_call_begin, q3_plan_host.inc)
+    GuideTable guide;
+    unsigned long long guide_serial = 0;
+    // the form of the column plans the q3_generate_many_* loops run (PlanKey::pen): under a guide the masked one, whatever the table and
+    // the penalties; under a table the adjusted one, whatever the penalties
+    int pen_form() const { return guide.n_states ? kPenGuide : (bias.n_lists() ? kPenAdj : (pen_on() ? kPenOn : kPenOff)); }
     int enqueue_sample();
 
     int load(const char* path, uint32_t ctx_len);
@@ -2037,6 +2079,61 @@ int q3_op_logit_bias(const float* logits, size_t n, const q3_bias_entry* entries
     a.n = (int)n;
     a.max_streams = 1;
     if ((rc = launch_now(0, k_bias_apply, dim3(kPenSlices, 1), dim3(kPenThreads), 0, a, (const BiasCtl*)dctl.as<BiasCtl>())) || (rc = op_end())) return rc;
+    unsigned long long keys[kPenSlices], best = 0ull;
+    HIP_TRY(hipMemcpy(out, dout.p, 4 * n, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(keys, dkeys.p, sizeof keys, hipMemcpyDeviceToHost));
+    for (int i = 0; i < kPenSlices; ++i) best = std::max(best, keys[i]);
+    *argmax = (int32_t)(best & 0xffffffffull);
+    return Q3_OK;
+}
+
+int q3_op_guide(const float* logits, size_t n, const int16_t* next_row, const q3_bias_entry* entries, size_t n_entries, int mode, uint32_t g,
+                const uint32_t* counts, float presence, float frequency, float* out, int32_t* argmax, int device) {
+    g_err[0] = 0;
+    int rc;
+    if (mode != kBiasAdd && mode != kBiasAllow) return fail(Q3_ERR_ARG, "mode %d is neither ADD (0) nor ALLOW (1)", mode);
+    if ((rc = penalties_check(presence, frequency))) return rc;
+    if (!logits || !next_row || !out || !argmax || n == 0) return fail(Q3_ERR_ARG, "null argument");
+    if (n > (size_t)INT32_MAX) return fail(Q3_ERR_ARG, "more than 2^31 logits");
+    BiasTable t;
+    const uint8_t m = (uint8_t)mode;
+    if ((rc = bias_check(entries, &n_entries, &m, 1, (long)n, t))) return rc;
+    if ((rc = op_begin(device))) return rc;
+    OpBuf dl, dc, dout, dkeys, dpen, dent, doff, dmode, dctl, dnext, dstate, dgctl;
+    const PenCtl hp{presence, frequency};
+    const int zero = 0;
+    if ((rc = dl.upload(logits, 4 * n)) || (rc = dout.alloc(4 * n)) || (rc = dkeys.alloc(8 * (size_t)kPenSlices)) || (rc = dpen.upload(&hp, sizeof(hp))) ||
+        (rc = dent.upload(t.entries.data(), sizeof(BiasEntry) * t.entries.size())) || (rc = doff.upload(t.off.data(), 4 * t.off.size())) ||
+        (rc = dmode.upload(t.modes.data(), 1)) || (counts && (rc = dc.upload(counts, 4 * n))) || (rc = dnext.upload(next_row, 2 * n)) ||
+        (rc = dstate.upload(&zero, sizeof(zero))))
+        return rc;
+    BiasCtl h{};
+    h.entries = dent.as<BiasEntry>();
+    h.list_off = doff.as<unsigned>();
+    h.modes = dmode.as<unsigned char>();
+    h.counts = counts ? dc.as<unsigned>() : nullptr;
+    h.n_lists = 1;
+    h.n_requests = 1;
+    h.g_op = g;
+    // a guide of the one state given, which request 0 starts in and its slot is in: the row holds whatever g is
+    GuideCtl hg{};
+    hg.next = dnext.as<short>();
+    hg.start = dstate.as<int>();
+    hg.state = dstate.as<int>();
+    hg.n_states = 1;
+    hg.n_start = 1;
+    if ((rc = dctl.upload(&h, sizeof(h))) || (rc = dgctl.upload(&hg, sizeof(hg)))) return rc;
+    // one row, emitting, request 0 at output g, the counts as given: k_guide_apply without a pass (PenArgs::cols null)
+    PenArgs a{};
+    a.logits = dl.as<float>();
+    a.pen_logits = dout.as<float>();
+    a.pen_slots = dkeys.as<unsigned long long>();
+    a.ctl = dpen.as<PenCtl>();
+    a.n = (int)n;
+    a.max_streams = 1;
+    if ((rc = launch_now(0, k_guide_apply, dim3(kPenSlices, 1), dim3(kPenThreads), 0, a, (const BiasCtl*)dctl.as<BiasCtl>(), (const GuideCtl*)dgctl.as<GuideCtl>())) ||
+        (rc = op_end()))
+        return rc;
     unsigned long long keys[kPenSlices], best = 0ull;
     HIP_TRY(hipMemcpy(out, dout.p, 4 * n, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(keys, dkeys.p, sizeof keys, hipMemcpyDeviceToHost));

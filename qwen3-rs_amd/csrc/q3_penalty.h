@@ -123,8 +123,8 @@ __global__ __launch_bounds__(kPenThreads) void k_pen_apply(const PenArgs a) {
 
 // one workgroup of kColsMax threads, a thread per column, in front of the turn kernel: the token an emitting column is about to
 // commit enters its slot's counts.  A pass has at most one emitting column per slot, so plain loads and stores do.
-__device__ __forceinline__ void pen_count_column(const PenArgs& a, int j) {
-    if (j >= kColsMax || !pen_emits(a.cols, j)) return;
+// (pen_commit_column: that token of emitting column j, clamped to [0, V))
+__device__ __forceinline__ int pen_commit_column(const PenArgs& a, int j) {
     unsigned long long best;
     if (a.draw) {
         best = a.st[j].argmax;
@@ -134,7 +134,11 @@ __device__ __forceinline__ void pen_count_column(const PenArgs& a, int j) {
         for (int i = 0; i < kPenSlices; ++i) best = max(best, s[i]);
     }
     const int t = cols_commit_token(a.draw ? a.draw->mode[j] : kColArgmax, best, a.st[j].token);
-    const int token = min(max(t, 0), a.n - 1);
+    return min(max(t, 0), a.n - 1);
+}
+__device__ __forceinline__ void pen_count_column(const PenArgs& a, int j) {
+    if (j >= kColsMax || !pen_emits(a.cols, j)) return;
+    const int token = pen_commit_column(a, j);
     const int kv = min(max(a.col_slot[j], 0), a.max_streams - 1);
     a.counts[(size_t)kv * (size_t)a.n + (size_t)token] += 1u;
 }

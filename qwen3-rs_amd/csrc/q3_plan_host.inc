@@ -206,7 +206,9 @@ int bias_alloc(q3_engine* e) {
 }
 int bias_call_begin(q3_engine* e, const int* o_off, size_t n_requests, size_t n_out_total) {
     BatchCtx* b = e->batch;
-    const BiasTable& t = e->bias;
+    // (a guide without a table, section 2r: one empty ADD list)
+    static const BiasTable none{{}, {0u, 0u}, {(unsigned char)kBiasAdd}};
+    const BiasTable& t = e->bias.n_lists() ? e->bias : none;
     int rc;
     const size_t n_lists = t.n_lists(), n_ent = t.entries.size();
     if ((rc = bias_alloc(e))) return rc;
@@ -229,6 +231,46 @@ int bias_call_begin(q3_engine* e, const int* o_off, size_t n_requests, size_t n_
     h.n_lists = (int)n_lists;
     h.n_requests = (int)n_requests;
     HIP_TRY(hipMemcpyAsync(b->bias_ctl, &h, sizeof(BiasCtl), hipMemcpyHostToDevice, e->stream));
+    return Q3_OK;
+}
+
+// ---- the guide of q3_guide_set on the device (q3_guide.h, section 2r).  guide_alloc: what a plan of the masked form points at on
+// top of the adjusted form's, made once -- the control block and the slots' states.  guide_call_begin: every generate call under a
+// guide, on the stream in front of its passes: bias_call_begin (the table of section 2q or one empty ADD list, o_off, the counts),
+// the guide's table where the device does not hold it yet -- once per q3_guide_set and per batched state, never per call -- then
+// start[] and the control block.
+int guide_alloc(q3_engine* e) {
+    BatchCtx* b = e->batch;
+    int rc;
+    if ((rc = bias_alloc(e))) return rc;
+    if (b->guide_ctl) return Q3_OK;
+    DevMem<GuideCtl> ctl; DevMem<int> state;
+    if ((rc = ctl.alloc(1)) || (rc = state.alloc((size_t)b->max_streams))) return rc;
+    HIP_TRY(hipMemsetAsync(ctl, 0, sizeof(GuideCtl), e->stream));
+    HIP_TRY(hipMemsetAsync(state, 0xff, sizeof(int) * (size_t)b->max_streams, e->stream));
+    b->guide_ctl = std::move(ctl); b->guide_state = std::move(state);
+    return Q3_OK;
+}
+int guide_call_begin(q3_engine* e, const int* o_off, size_t n_requests, size_t n_out_total) {
+    BatchCtx* b = e->batch;
+    const GuideTable& t = e->guide;
+    int rc;
+    if ((rc = guide_alloc(e)) || (rc = bias_call_begin(e, o_off, n_requests, n_out_total))) return rc;
+    if (b->guide_serial != t.serial) {
+        b->guide_serial = 0;
+        if ((rc = b->guide_next.grow(t.next.size(), e->stream))) return rc;
+        HIP_TRY(hipMemcpyAsync(b->guide_next, t.next.data(), sizeof(int16_t) * t.next.size(), hipMemcpyHostToDevice, e->stream));
+        b->guide_serial = t.serial;
+    }
+    if ((rc = b->guide_start.grow(t.start.size(), e->stream))) return rc;
+    HIP_TRY(hipMemcpyAsync(b->guide_start, t.start.data(), sizeof(int) * t.start.size(), hipMemcpyHostToDevice, e->stream));
+    GuideCtl h{};
+    h.next = b->guide_next;
+    h.start = b->guide_start;
+    h.state = b->guide_state;
+    h.n_states = (int)t.n_states;
+    h.n_start = (int)t.start.size();
+    HIP_TRY(hipMemcpyAsync(b->guide_ctl, &h, sizeof(GuideCtl), hipMemcpyHostToDevice, e->stream));
     return Q3_OK;
 }
 
@@ -554,8 +596,14 @@ struct PlanBuilder {
     }
     // the penalised rows of the emitting columns and their slices' largest keys, behind the classifier (pen_alloc has run)
     // (kPenAdj: the adjusted rows of section 2q in their place, bias_alloc has run)
+    // (kPenGuide: the masked rows of section 2r, guide_alloc has run)
     int penalize() {
         if (!b->pen_ctl) return fail(Q3_ERR_INTERNAL, "a plan under penalties before pen_alloc");
+        if (key.pen == kPenGuide) {
+            if (!b->bias_ctl || !b->guide_ctl) return fail(Q3_ERR_INTERNAL, "a plan of the masked form before guide_alloc");
+            return add(F_NEXT, k_guide_apply, dim3(kPenSlices, (unsigned)n), dim3(kPenThreads), 0, pen_args(e, key.draw), (const BiasCtl*)b->bias_ctl,
+                       (const GuideCtl*)b->guide_ctl);
+        }
         if (key.pen == kPenAdj) {
             if (!b->bias_ctl) return fail(Q3_ERR_INTERNAL, "a plan of the adjusted form before bias_alloc");
             return add(F_NEXT, k_bias_apply, dim3(kPenSlices, (unsigned)n), dim3(kPenThreads), 0, pen_args(e, key.draw), (const BiasCtl*)b->bias_ctl);
@@ -601,6 +649,9 @@ struct PlanBuilder {
             if (key.genlp && (rc = gen_logprobs())) return rc;
             if (key.pen == kPenOn && (rc = add(F_NEXT, k_pen_count, dim3(1), dim3(64), 0, pen_args(e, key.draw)))) return rc;
             if (key.pen == kPenAdj && (rc = add(F_NEXT, k_bias_count, dim3(1), dim3(64), 0, pen_args(e, key.draw), (const BiasCtl*)b->bias_ctl))) return rc;
+            if (key.pen == kPenGuide &&
+                (rc = add(F_NEXT, k_guide_step, dim3(1), dim3(64), 0, pen_args(e, key.draw), (const BiasCtl*)b->bias_ctl, (const GuideCtl*)b->guide_ctl)))
+                return rc;
             if (!key.draw && key.pen) return add(F_NEXT, k_cols_turn, dim3(1), dim3(kWG), 0, b->cols_ctl, b->pen_slots, kPenSlices, kPenSlices, b->st, b->col_slot);
             if (!key.draw) return add(F_NEXT, k_cols_turn, dim3(1), dim3(kWG), 0, b->cols_ctl, b->slots, b->nslots, nslots_used, b->st, b->col_slot);
             return add(F_NEXT, k_cols_turn_draw, dim3(1), dim3(kWG), 0, b->cols_ctl, b->cols_draw, b->draw_cols.ss, b->st, b->col_slot);
@@ -678,7 +729,7 @@ int plan_get(q3_engine* e, PlanKey key, Plan** out) {
             if (int rc = record_scratch(e, key.genlp == kGenlpTop)) return rc;
         // ... and so does the penalty state a plan under penalties points at
         if (key.pen)
-            if (int rc = key.pen == kPenAdj ? bias_alloc(e) : pen_alloc(e)) return rc;
+            if (int rc = key.pen == kPenGuide ? guide_alloc(e) : (key.pen == kPenAdj ? bias_alloc(e) : pen_alloc(e))) return rc;
         Plan built;
         if (int rc = batch_build_plan(e, key, built)) return rc;
         if (key.kind == PlanKind::SlotPrefill) home = &b->dense_plans[key.n];

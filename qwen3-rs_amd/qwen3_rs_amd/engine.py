@@ -39,7 +39,9 @@ EXPORTED_SYMBOLS = [
     "q3_gen_logprobs", "q3_gen_logprobs_get", "q3_gen_logprobs_read",
     "q3_sampler_penalties", "q3_sampler_get_penalties", "q3_op_penalize",
     "q3_logit_bias_set", "q3_logit_bias_get", "q3_op_logit_bias",
+    "q3_guide_set", "q3_guide_get", "q3_op_guide",
 ]
+GUIDE_MAX_STATES = 4096  # Q3_GUIDE_MAX_STATES (section 2r)
 PENALTY_MAX = 2.0        # |presence|, |frequency| <= 2 (section 2p)
 BIAS_MAX = 4096          # Q3_BIAS_MAX: entries per list (section 2q)
 BIAS_LIMIT = 100.0       # a finite bias lies in -100 .. 100; -inf bans
@@ -311,6 +313,10 @@ def _bind(path: str) -> C.CDLL:
     L.q3_logit_bias_get.argtypes = [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     L.q3_op_logit_bias.argtypes = [fp, sz, C.c_void_p, sz, C.c_int, C.c_uint32, C.POINTER(C.c_uint32), C.c_float, C.c_float, fp, C.POINTER(C.c_int32),
                                    C.c_int]
+    L.q3_guide_set.argtypes = [C.c_void_p, C.c_void_p, sz, sz, C.POINTER(C.c_int32), sz]
+    L.q3_guide_get.argtypes = [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    L.q3_op_guide.argtypes = [fp, sz, C.c_void_p, C.c_void_p, sz, C.c_int, C.c_uint32, C.POINTER(C.c_uint32), C.c_float, C.c_float, fp,
+                              C.POINTER(C.c_int32), C.c_int]
     _libs[path] = L
     return L
 
@@ -1019,6 +1025,45 @@ class Transformer:
             raise Q3Error(-5, "the engine's logit-bias table was not set through this object")
         return [list(l) for l in lists], list(modes)
 
+    # ---- guided decoding (include/qwen3_hip.h section 2r)
+    def set_guide(self, next, start):
+        """The guide of every generate_many_* call (q3_guide_set).  next: a table [n_states][vocab_size] of integers, next[s][v] >= 0:
+        in state s token v may come and leads to that state, -1: it may not (guide.Automaton builds such tables); None or an empty
+        table turns the guide off (the default).  start: one state for every request of every call, or a sequence of one per request
+        (-1: that request is unguided), and a call with another number of requests raises.  In state s a request's next token is
+        taken from its row with the forbidden tokens at -inf, in front of set_logit_bias and set_penalties; the committed token
+        moves the state.  The setting is the engine's: it survives set_sampler, batch_init, set_top_k, set_gen_logprobs,
+        set_penalties, set_logit_bias and every generate_many call, and it does not touch batch_step_cols, forward_batch, verify,
+        score, choose, embed or single-stream decode."""
+        if next is None or np.size(next) == 0:
+            _check(self._lib.q3_guide_set(self._h, None, 0, 0, None, 0))
+            self._guide = (None, [])
+            return
+        table = np.asarray(next)
+        if table.ndim != 2 or not np.issubdtype(table.dtype, np.integer):
+            raise TypeError("next must be an integer table [n_states][vocab_size]")
+        if table.min() < -1 or table.max() > 0x7fff:
+            raise ValueError("an entry of next lies outside -1 .. 32767")
+        table = np.ascontiguousarray(table, dtype=np.int16)
+        starts = [start] if isinstance(start, (int, np.integer)) and not isinstance(start, bool) else list(start)
+        if any(isinstance(x, bool) or not isinstance(x, (int, np.integer)) for x in starts):
+            raise TypeError(f"start must be an integer or a sequence of integers, got {start!r}")
+        if any(x < -1 or x > 0x7fffffff for x in starts):
+            raise ValueError("a start state lies outside -1 .. 2^31 - 1")
+        st = (C.c_int32 * max(len(starts), 1))(*starts)
+        _check(self._lib.q3_guide_set(self._h, table.ctypes.data_as(C.c_void_p), table.shape[0], table.shape[1], st, len(starts)))
+        self._guide = (table, [int(x) for x in starts])
+
+    def get_guide(self):
+        """the engine's guide as (next, start) in the form set_guide takes them; (None, []): off.  The library holds the guide and
+        tells its size (q3_guide_get); the arrays are the copy kept here."""
+        n_states, n_start = C.c_size_t(0), C.c_size_t(0)
+        _check(self._lib.q3_guide_get(self._h, C.byref(n_states), C.byref(n_start)))
+        table, starts = getattr(self, "_guide", (None, []))
+        if (int(n_states.value), int(n_start.value)) != (0 if table is None else table.shape[0], len(starts)):
+            raise Q3Error(-5, "the engine's guide was not set through this object")
+        return table, list(starts)
+
     def read_gen_logprobs(self, n_per_row=None):
         """The records of the last generate_many_* call (q3_gen_logprobs_read), which ran under set_gen_logprobs(top_n >= 0): per
         request (records, tops, ranks) -- SCORE_DTYPE[n], TOP_DTYPE[n, top_n], int32[n], entry j for the request's j-th token; tops
@@ -1305,6 +1350,40 @@ class _Ops:
         out, idx = np.empty_like(logits), C.c_int32(-1)
         _check(load_library().q3_op_logit_bias(self._fp(logits), logits.size, flat.ctypes.data_as(C.c_void_p) if flat.size else None, len(ent), int(mode),
                                                int(g), cp, float(presence), float(frequency), self._fp(out), C.byref(idx), self.device))
+        return out, int(idx.value)
+
+    def guide(self, logits, next_row, entries=(), mode: int = BIAS_ADD, g: int = 0, counts=None, presence: float = 0.0, frequency: float = 0.0):
+        """The masked row of include/qwen3_hip.h section 2r on the device (q3_op_guide): tokens whose entry of `next_row` (one state's
+        row of a guide's table) is negative become -inf, then the list `entries` under `mode` for output index g and, with counts,
+        the penalties apply as in ops.logit_bias.  Returns (the row as float32[n], the index of its largest key)."""
+        ent = _check_bias_list(entries, mode, "entries")
+        _check_penalties(presence, frequency)
+        if isinstance(g, bool) or not isinstance(g, (int, np.integer)):
+            raise TypeError(f"g must be an integer, got {g!r}")
+        if g < 0 or g > 0xffffffff:
+            raise ValueError(f"g {g} out of range")
+        logits = np.ascontiguousarray(logits, dtype=np.float32)
+        if logits.ndim != 1 or logits.size == 0:
+            raise ValueError("logits must be a non-empty vector")
+        next_row = np.asarray(next_row)
+        if next_row.shape != logits.shape or not np.issubdtype(next_row.dtype, np.integer):
+            raise ValueError("next_row must be an integer vector of the length of logits")
+        if next_row.min() < -0x8000 or next_row.max() > 0x7fff:
+            raise ValueError("an entry of next_row does not fit int16")
+        next_row = np.ascontiguousarray(next_row, dtype=np.int16)
+        cp = None
+        if counts is not None:
+            counts = np.ascontiguousarray(counts, dtype=np.uint32)
+            if counts.shape != logits.shape:
+                raise ValueError("logits and counts must be vectors of one length")
+            cp = counts.ctypes.data_as(C.POINTER(C.c_uint32))
+        if any(t >= logits.size for t, _, _ in ent):
+            raise ValueError(f"a token of the list lies outside the {logits.size} logits")
+        flat = _bias_array(ent)
+        out, idx = np.empty_like(logits), C.c_int32(-1)
+        _check(load_library().q3_op_guide(self._fp(logits), logits.size, next_row.ctypes.data_as(C.c_void_p),
+                                          flat.ctypes.data_as(C.c_void_p) if flat.size else None, len(ent), int(mode), int(g), cp, float(presence),
+                                          float(frequency), self._fp(out), C.byref(idx), self.device))
         return out, int(idx.value)
 
 

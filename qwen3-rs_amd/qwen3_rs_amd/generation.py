@@ -11,6 +11,7 @@ from typing import Callable, Iterable, List, Optional, Sequence, Tuple
 import numpy as np
 
 from .engine import SCORE_DTYPE, TOP_DTYPE, BIAS_ADD, BIAS_ALLOW
+from .guide import Automaton, merge_guides
 
 
 def sample_argmax(logits: np.ndarray) -> int:
@@ -167,7 +168,7 @@ def common_prefix_len(prompts: Sequence[Sequence[int]]) -> int:
 def generate_many(transformer, prompts: Sequence[Sequence[int]], max_new_tokens: int, stop_tokens: Iterable[int] = (), sampler=None,
                   dense_min: int = 0, stop_on_device: bool = False, shared_prefix=None, logprobs: Optional[int] = None,
                   presence_penalty: float = 0.0, frequency_penalty: float = 0.0, logit_bias=None, banned_tokens=None, allowed_tokens=None,
-                  min_tokens=0):
+                  min_tokens=0, guide=None):
     """Many greedy generations served through the slots of Transformer.batch_init in ragged column passes
     (Transformer.generate_many_greedy).  Row r holds what Transformer.prefill(prompts[r], 0) followed by generate_greedy returns on
     an engine of its own: every prompt token goes through the model (chat's prompt loop, generation.rs:116-123), then up to
@@ -207,9 +208,34 @@ def generate_many(transformer, prompts: Sequence[Sequence[int]], max_new_tokens:
     no stop token among a row's first min_tokens tokens (a stop token that also carries a logit_bias is a ValueError).  They act on
     every generated token, the first included, in front of the penalties, temperature, top-k and top-p; the logprobs stay those of
     the raw distribution.  Works with every option above.  With none of the four given the call touches no table: one set with
-    Transformer.set_logit_bias simply holds."""
+    Transformer.set_logit_bias simply holds.
+    guide: a constraint that changes with what the row has produced so far (guide.Automaton; Transformer.set_guide, set for this call
+    and put back afterwards, also when the call raises): one Automaton for all requests, or a sequence of one per request in which
+    None leaves a request unguided.  In state s only the tokens the automaton allows there may come, the first token included, in
+    front of logit_bias and the penalties; the committed token moves the state.  A row ends at its stop token as ever: an automaton
+    that wants to end allows a stop token in its accepting states.  Works with every option above; the logprobs stay those of the
+    raw distribution.  With guide=None the call touches no guide: one set with Transformer.set_guide simply holds."""
     if any(len(p) == 0 for p in prompts):
         raise ValueError("Please provide a prompt")
+    args = (transformer, prompts, max_new_tokens, stop_tokens, sampler, dense_min, stop_on_device, shared_prefix, logprobs, presence_penalty,
+            frequency_penalty, logit_bias, banned_tokens, allowed_tokens, min_tokens)
+    if guide is None:
+        return _generate_many_bias(*args)
+    table, start = merge_guides(guide, len(prompts))
+    if len(start) > 1:
+        # the engine sees the requests the context leaves room for, and one start state for each of them
+        start = [start[r] for r in _live_requests(transformer, prompts, max_new_tokens, shared_prefix)]
+    guide_before = transformer.get_guide()
+    transformer.set_guide(table, start)
+    try:
+        return _generate_many_bias(*args)
+    finally:
+        transformer.set_guide(*guide_before)
+
+
+def _generate_many_bias(transformer, prompts, max_new_tokens, stop_tokens, sampler, dense_min, stop_on_device, shared_prefix, logprobs, presence_penalty,
+                        frequency_penalty, logit_bias, banned_tokens, allowed_tokens, min_tokens):
+    """generate_many behind its guide handling"""
     args = (transformer, prompts, max_new_tokens, stop_tokens, sampler, dense_min, stop_on_device, shared_prefix, logprobs, presence_penalty,
             frequency_penalty)
     if logit_bias is None and banned_tokens is None and allowed_tokens is None and np.isscalar(min_tokens) and min_tokens == 0:
