@@ -1100,6 +1100,58 @@ int q3_op_guide(const float* logits, size_t n, const int16_t* next_row /* [n] */
                 int mode, uint32_t g, const uint32_t* counts /* or NULL: no penalties */, float presence, float frequency, float* out /* [n] */,
                 int32_t* argmax, int device);
 
+/* ------------------------------------------------------------------------------------------------
+ * 2s. (behind 2r so that the earlier sections stay as they were.)  Sparse guides: section 2r's guide on a compressed table, for
+ * automata whose dense table does not fit -- one dense state costs 2 V bytes, 304 KB at V = 151,936, and a dense state number ends
+ * at 32,767 -- such as the lift of a regular expression to the tokens of a real vocabulary.
+ * THE RULE IS 2r's, UNCHANGED: the masked row with 0xFF800000 (-inf) for forbidden tokens, 2q's table on m in place of l, 2p's
+ * penalties on top, the state step s_{g+1} = next[s_g][y_g] where that is >= 0, else s_g, start[r] == -1 for an unguided request,
+ * y_0 under the rule too, section 2o's records on the RAW ROW l, and the stop decision, the schedule, the cache rows and the coins
+ * untouched.  ONLY THE STATEMENT OF next[s][v] CHANGES:
+ *     dflt[n_states]          int32_t: what every unlisted token does in state s: -1 forbidden, otherwise the state it leads to.
+ *     row_off[n_states + 1]   uint32_t: state s owns edges[row_off[s] .. row_off[s + 1]).
+ *     edges[n_edges]          q3_guide_edge { token, next }: within a state the tokens ascend strictly; next is -1 or a state.
+ *     next[s][v]              the edge's next where v is listed in state s, else dflt[s].
+ * ONE GUIDE HOLDS AT A TIME: setting either form clears the other, q3_guide_set(e, NULL, 0, 0, NULL, 0) clears both, and so does
+ * q3_guide_set_sparse with n_states == 0.  q3_guide_get answers for the dense form alone and reads 0, 0 under a sparse guide;
+ * q3_guide_get_sparse reads 0, 0, 0 under a dense one.
+ * What runs (csrc/q3_guide_sparse.h).  A fifth form on the fourth axis of the column plans, chosen whenever a sparse guide is set.
+ * k_guide_sp_apply stands where k_guide_apply stands, with its grid, slices and outputs: the workgroup finds its slice's part of
+ * the state's edges by two searches; where that is empty the allowed bit is dflt[s] >= 0 for the whole slice and nothing more is
+ * read; otherwise a byte per token in LDS takes the default, the slice's edges stream over it, and the logits stream with the byte
+ * beside them -- 8 V + 8 E_s bytes per emitting column, E_s the state's edges, against 2r's 10 V.  k_guide_sp_step stands where
+ * k_guide_step stands: one search of the state's edges for the committed token, else dflt.  The arrays go to the device once per
+ * q3_guide_set_sparse (and again after q3_batch_init), at the first generate call under it; start[] and a control block go with
+ * every call; two sparse guides share every plan and graph.  The kernels and plans of 2r, 2q and 2p are as they were, and with no
+ * sparse guide set every entry point launches exactly what it launched before this section existed.
+ * IT DOES NOT TOUCH q3_batch_step_cols[_draw], section 2b, the verify paths, single-stream decode, q3_embed_many, q3_choice_many,
+ * q3_score_many or q3_score_top_many.
+ * ------------------------------------------------------------------------------------------------ */
+#define Q3_GUIDE_SPARSE_MAX_STATES 1048576
+#define Q3_GUIDE_SPARSE_MAX_EDGES 134217728
+typedef struct q3_guide_edge { int32_t token; int32_t next; } q3_guide_edge;
+
+/* The engine-wide sparse guide; start[], n_start, what it holds for and what it survives are q3_guide_set's.  The library keeps a
+ * copy of the arrays.  Execution: waits for the stream; the device side is made by the first generate call under the guide.
+ * Q3_ERR_ARG, checked before the engine or the GPU is touched: a null array with a non-zero count; n_states >
+ * Q3_GUIDE_SPARSE_MAX_STATES; n_edges > Q3_GUIDE_SPARSE_MAX_EDGES; n_start == 0 with states; vocab == 0 or vocab >= 2^31; a start,
+ * a dflt or an edge's next outside [-1, n_states); row_off[0] != 0, an offset below the one before it, row_off[n_states] !=
+ * n_edges; an edge's token outside [0, vocab) or not above the token before it in its state; a state that allows no token.  Then
+ * the null engine, then vocab != vocab_size.  A refused call changes nothing. */
+int q3_guide_set_sparse(q3_engine* e, const int32_t* dflt /* [n_states] */, const uint32_t* row_off /* [n_states + 1] */,
+                        const q3_guide_edge* edges /* [n_edges] */, size_t n_states, size_t n_edges, size_t vocab,
+                        const int32_t* start /* [n_start] */, size_t n_start);
+int q3_guide_get_sparse(const q3_engine* e, size_t* n_states, size_t* n_edges, size_t* n_start);
+
+/* The rule on a host vector: k_guide_sp_apply once over logits[0 .. n) for a request in a state with default dflt and the edges
+ * given, at output index g with the one list given, then the penalties where counts is not NULL: q3_op_guide with the state's row
+ * in the sparse statement.  Q3_ERR_ARG (before anything touches the GPU): what q3_op_logit_bias refuses; null edges with a count;
+ * more edges than logits; a token outside [0, n) or not ascending strictly; dflt or a next outside [-1,
+ * Q3_GUIDE_SPARSE_MAX_STATES). */
+int q3_op_guide_sparse(const float* logits, size_t n, int32_t dflt, const q3_guide_edge* edges, size_t n_edges, const q3_bias_entry* entries,
+                       size_t n_entries, int mode, uint32_t g, const uint32_t* counts /* or NULL: no penalties */, float presence, float frequency,
+                       float* out /* [n] */, int32_t* argmax, int device);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,7 +24,8 @@ enum class PlanKind { Decode, Prefill, Verify, Cols, SlotPrefill };
 // (q3_penalty.h); the values of the setting are read from device memory when a pass runs.  kPenAdj (cols_key sets it where a table
 // of q3_logit_bias_set holds, section 2q): k_bias_apply and k_bias_count (q3_bias.h) stand in their places, and whether penalties apply
 // on top is read from device memory when a pass runs (kPenOff / kPenOn / kPenAdj: q3_bias.h).  kPenGuide (where a guide of q3_guide_set
-// holds, section 2r, whatever the table and the penalties): k_guide_apply and k_guide_step (q3_guide.h) stand in those places
+// holds, section 2r, whatever the table and the penalties): k_guide_apply and k_guide_step (q3_guide.h) stand in those places.
+// kPenGuideSp (where a sparse guide of q3_guide_set_sparse holds, section 2s): k_guide_sp_apply and k_guide_sp_step (q3_guide_sparse.h)
 enum { kGenlpOff = 0, kGenlpRecs = 1, kGenlpTop = 2, kGenlpForms = 3 };
 struct PlanKey {
     PlanKind kind = PlanKind::Decode;
@@ -115,13 +116,14 @@ struct BatchCtx {
     DevMem<int> col_slot;        // device [kColsMax]: KV slot of every column of the pass in flight
     DevMem<ColsCtl> cols_ctl;    // device
     PinMem<ColsHost> h_cols;
-    Plan cols_plans[kPenForms][kGenlpForms][3][kColsNW];   // [plain | under penalties | adjusted rows | masked rows][no records | records | records and top][greedy |
+    Plan cols_plans[kPenForms][kGenlpForms][3][kColsNW];   // [plain | under penalties | adjusted rows | masked rows | masked rows, sparse][no records | records | records and top][greedy |
                                                         // sampled | sampled with top-k][width], built on first use (q3_batch_init
                                                         // starts over); the sampled ones: the same layers and classifier, then the
                                                         // draws and k_cols_turn_draw; with records: the record launches in front of
                                                         // the turn kernel; under penalties: k_pen_apply behind the classifier and
                                                         // k_pen_count in front of the turn kernel; adjusted rows: k_bias_apply and
-                                                        // k_bias_count in their places; masked rows: k_guide_apply and k_guide_step
+                                                        // k_bias_count in their places; masked rows: k_guide_apply and k_guide_step,
+                                                        // or k_guide_sp_apply and k_guide_sp_step under a sparse guide
     DevMem<ColEnt> cols_table;                          // the loop's pass table, prompts and output: grow-only device buffers
     DevMem<int> cols_ncols;
     DevMem<int32_t> cols_prompts, cols_out;
@@ -205,6 +207,15 @@ struct BatchCtx {
     DevMem<short> guide_next;
     DevMem<int> guide_start;
     unsigned long long guide_serial = 0;
+    // the sparse guide of q3_guide_set_sparse (section 2s; guide_sp_alloc and guide_sp_call_begin): the same, with the three arrays
+    // of the compressed table in the table's place
+    DevMem<GuideSpCtl> guide_sp_ctl;
+    DevMem<int> guide_sp_state;
+    DevMem<int> guide_sp_dflt;
+    DevMem<unsigned> guide_sp_off;
+    DevMem<GuideEdge> guide_sp_edges;
+    DevMem<int> guide_sp_start;
+    unsigned long long guide_sp_serial = 0;
     // packed-matrix directory
     struct PM { size_t q_off, s_off; int ntiles, ng; };
     std::vector<PM> m_qkv, m_wo, m_w13, m_w2;

@@ -26,9 +26,9 @@ constexpr int kBiasMax = 4096;          // Q3_BIAS_MAX
 enum { kBiasAdd = 0, kBiasAllow = 1 };  // Q3_BIAS_ADD, Q3_BIAS_ALLOW
 
 // the forms of a column plan on the PlanKey::pen axis (q3_batch_host.inc): the classifier's rows as they are, section 2p's penalised
-// rows, the adjusted rows of this header with or without penalties on top, or the masked rows of q3_guide.h (section 2r) with or
-// without a table of this header and penalties on top
-enum { kPenOff = 0, kPenOn = 1, kPenAdj = 2, kPenGuide = 3, kPenForms = 4 };
+// rows, the adjusted rows of this header with or without penalties on top, or the masked rows of q3_guide.h (section 2r) or of
+// q3_guide_sparse.h (section 2s) with or without a table of this header and penalties on top
+enum { kPenOff = 0, kPenOn = 1, kPenAdj = 2, kPenGuide = 3, kPenGuideSp = 4, kPenForms = 5 };
 
 struct BiasEntry {                      // q3_bias_entry
     int token;

@@ -77,6 +77,8 @@ int cols_requests_check(q3_engine* e, const int32_t* prompts, const size_t* prom
         return fail(Q3_ERR_ARG, "q3_logit_bias_set holds %zu lists, one per request, and the call has %zu requests", e->bias.n_lists(), n_requests);
     if (e->guide.n_states && e->guide.start.size() > 1 && e->guide.start.size() != n_requests)
         return fail(Q3_ERR_ARG, "q3_guide_set holds %zu start states, one per request, and the call has %zu requests", e->guide.start.size(), n_requests);
+    if (e->guide_sp.n_states && e->guide_sp.start.size() > 1 && e->guide_sp.start.size() != n_requests)
+        return fail(Q3_ERR_ARG, "q3_guide_set_sparse holds %zu start states, one per request, and the call has %zu requests", e->guide_sp.start.size(), n_requests);
     for (size_t r = 0; draw && r < n_requests; ++r)
         if ((rc = sampler_check(temperature[r], topp[r], (long)r))) return rc;
     rq.prompts = prompts;
@@ -584,6 +586,7 @@ int cols_generate(q3_engine* e, const ColsRequests& rq, int32_t* out_tokens, q3_
     const int pen = e->pen_form();
     if (pen == kPenAdj && (rc = bias_call_begin(e, rq.o_off.data(), n_requests, rq.n_out))) return rc;     // the call's table, on the stream in front of its passes
     if (pen == kPenGuide && (rc = guide_call_begin(e, rq.o_off.data(), n_requests, rq.n_out))) return rc;  // the call's guide and table (section 2r)
+    if (pen == kPenGuideSp && (rc = guide_sp_call_begin(e, rq.o_off.data(), n_requests, rq.n_out))) return rc;  // ... in its sparse form (section 2s)
     if ((rc = cols_job_run(e, job, draw, smp, rq.prompts, rq.n_prompt, out_tokens, rq.n_out, e->gen_logprobs, pen))) return rc;
     if (stats) *stats = s.stats;
     if (dstats) *dstats = dst;
@@ -784,6 +787,7 @@ int q3_guide_set(q3_engine* e, const int16_t* next, size_t n_states, size_t voca
     HIP_TRY(hipStreamSynchronize(e->stream));
     t.serial = ++e->guide_serial;
     e->guide = std::move(t);
+    e->guide_sp = GuideSparse{};         // one guide holds at a time (section 2s)
     return Q3_OK;
 }
 
@@ -792,6 +796,41 @@ int q3_guide_get(const q3_engine* e, size_t* n_states, size_t* n_start) {
     if (!e || !n_states || !n_start) return fail(Q3_ERR_ARG, "null argument");
     *n_states = e->guide.n_states;
     *n_start = e->guide.start.size();
+    return Q3_OK;
+}
+
+/* ---- section 2s: sparse guides ---- */
+
+int q3_guide_set_sparse(q3_engine* e, const int32_t* dflt, const uint32_t* row_off, const q3_guide_edge* edges, size_t n_states, size_t n_edges, size_t vocab,
+                        const int32_t* start, size_t n_start) {
+    g_err[0] = 0;
+    if (int rc = guide_sparse_check(dflt, row_off, edges, n_states, n_edges, vocab, start, n_start)) return rc;
+    if (!e) return fail(Q3_ERR_ARG, "null engine");
+    if (n_states && vocab != (size_t)e->cfg.vocab_size) return fail(Q3_ERR_ARG, "a guide over %zu tokens (vocab_size %d)", vocab, e->cfg.vocab_size);
+    GuideSparse t;
+    if (n_states) {
+        t.dflt.assign(dflt, dflt + n_states);
+        t.row_off.assign(row_off, row_off + n_states + 1);
+        t.edges.resize(n_edges);
+        if (n_edges) memcpy(t.edges.data(), edges, sizeof(GuideEdge) * n_edges);
+        t.start.assign(start, start + n_start);
+        t.n_states = n_states;
+        t.vocab = vocab;
+    }
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    t.serial = ++e->guide_serial;
+    e->guide_sp = std::move(t);
+    e->guide = GuideTable{};             // one guide holds at a time
+    return Q3_OK;
+}
+
+int q3_guide_get_sparse(const q3_engine* e, size_t* n_states, size_t* n_edges, size_t* n_start) {
+    g_err[0] = 0;
+    if (!e || !n_states || !n_edges || !n_start) return fail(Q3_ERR_ARG, "null argument");
+    *n_states = e->guide_sp.n_states;
+    *n_edges = e->guide_sp.edges.size();
+    *n_start = e->guide_sp.start.size();
     return Q3_OK;
 }
 

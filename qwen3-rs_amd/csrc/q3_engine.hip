@@ -47,6 +47,7 @@
 #include "q3_penalty.h"
 #include "q3_bias.h"
 #include "q3_guide.h"
+#include "q3_guide_sparse.h"
 #include "q3_lookup.h"
 
 namespace {
@@ -94,6 +95,7 @@ struct BiasTable {
     size_t n_lists() const { return modes.size(); }
 };
 static_assert(sizeof(BiasEntry) == sizeof(q3_bias_entry) && sizeof(BiasEntry) == 12, "BiasEntry is q3_bias_entry");
+static_assert(sizeof(GuideEdge) == sizeof(q3_guide_edge) && sizeof(GuideEdge) == 8, "GuideEdge is q3_guide_edge");
 
 // What q3_logit_bias_set and q3_op_logit_bias refuse about a table, the engine and the GPU untouched: a null array with a non-zero
 // count, a list of more than kBiasMax entries, a negative token, a bias that is NaN, +inf or finite outside [-100, 100], a mode other
@@ -174,6 +176,60 @@ int guide_check(const int16_t* next, size_t n_states, size_t vocab, const int32_
             any |= row[v] >= 0;
         }
         if (!any) return fail(Q3_ERR_ARG, "state %zu allows no token", s);
+    }
+    return Q3_OK;
+}
+
+// The sparse guide of q3_guide_set_sparse as the engine keeps it (section 2s); serial as in GuideTable, from the same counter.
+struct GuideSparse {
+    std::vector<int> dflt;               // [n_states]; empty: no sparse guide
+    std::vector<uint32_t> row_off;       // [n_states + 1]
+    std::vector<GuideEdge> edges;        // [n_edges]
+    std::vector<int> start;              // [n_start]
+    size_t n_states = 0, vocab = 0;
+    unsigned long long serial = 0;
+};
+
+// What q3_guide_set_sparse refuses about a guide, the engine and the GPU untouched: a null array with a non-zero count, the caps,
+// states without a start entry, vocab == 0 or >= 2^31, row_off[0] != 0, offsets that decrease or do not end at n_edges, a token
+// outside [0, vocab) or not strictly ascending within its state, a next, dflt or start outside [-1, n_states), a state that allows
+// no token.
+int guide_sparse_check(const int32_t* dflt, const uint32_t* row_off, const q3_guide_edge* edges, size_t n_states, size_t n_edges, size_t vocab,
+                       const int32_t* start, size_t n_start) {
+    if (!dflt && n_states) return fail(Q3_ERR_ARG, "null dflt with %zu states", n_states);
+    if (!row_off && n_states) return fail(Q3_ERR_ARG, "null row_off with %zu states", n_states);
+    if (!edges && n_edges) return fail(Q3_ERR_ARG, "null edges with %zu edges", n_edges);
+    if (!start && n_start) return fail(Q3_ERR_ARG, "null start with %zu entries", n_start);
+    if (n_states == 0) {
+        if (n_edges) return fail(Q3_ERR_ARG, "%zu edges and no state", n_edges);
+        return Q3_OK;
+    }
+    if (n_states > (size_t)kGuideSpMaxStates) return fail(Q3_ERR_ARG, "%zu states, at most %d", n_states, kGuideSpMaxStates);
+    if (n_edges > (size_t)kGuideSpMaxEdges) return fail(Q3_ERR_ARG, "%zu edges, at most %d", n_edges, kGuideSpMaxEdges);
+    if (vocab == 0 || vocab > (size_t)INT32_MAX) return fail(Q3_ERR_ARG, "a guide over %zu tokens: 1 .. 2^31 - 1", vocab);
+    if (n_start == 0) return fail(Q3_ERR_ARG, "%zu states and no start state", n_states);
+    if (n_start > (size_t)INT32_MAX) return fail(Q3_ERR_ARG, "more than 2^31 start states");
+    for (size_t r = 0; r < n_start; ++r)
+        if (start[r] < -1 || start[r] >= (int32_t)n_states)
+            return fail(Q3_ERR_ARG, "start[%zu] = %d: -1 (unguided) or a state below %zu", r, start[r], n_states);
+    if (row_off[0] != 0u) return fail(Q3_ERR_ARG, "row_off[0] = %u, not 0", row_off[0]);
+    for (size_t s = 0; s < n_states; ++s)
+        if (row_off[s + 1] < row_off[s]) return fail(Q3_ERR_ARG, "row_off[%zu] = %u below row_off[%zu] = %u", s + 1, row_off[s + 1], s, row_off[s]);
+    if ((size_t)row_off[n_states] != n_edges) return fail(Q3_ERR_ARG, "row_off[%zu] = %u does not end at the %zu edges", n_states, row_off[n_states], n_edges);
+    for (size_t s = 0; s < n_states; ++s) {
+        if (dflt[s] < -1 || dflt[s] >= (int32_t)n_states) return fail(Q3_ERR_ARG, "dflt[%zu] = %d: -1 (forbidden) or a state below %zu", s, dflt[s], n_states);
+        size_t ok = 0;                 // listed tokens that are allowed
+        for (size_t k = row_off[s]; k < row_off[s + 1]; ++k) {
+            const q3_guide_edge& ge = edges[k];
+            if (ge.token < 0 || (size_t)ge.token >= vocab) return fail(Q3_ERR_ARG, "edges[%zu].token = %d of state %zu outside the %zu tokens", k, ge.token, s, vocab);
+            if (k > row_off[s] && ge.token <= edges[k - 1].token)
+                return fail(Q3_ERR_ARG, "edges[%zu].token = %d of state %zu is not above its predecessor %d: tokens ascend strictly", k, ge.token, s, edges[k - 1].token);
+            if (ge.next < -1 || ge.next >= (int32_t)n_states)
+                return fail(Q3_ERR_ARG, "edges[%zu].next = %d of state %zu: -1 (forbidden) or a state below %zu", k, ge.next, s, n_states);
+            ok += ge.next >= 0;
+        }
+        const size_t listed = row_off[s + 1] - row_off[s];
+        if (ok == 0 && (dflt[s] < 0 || listed == vocab)) return fail(Q3_ERR_ARG, "state %zu allows no token", s);
     }
     return Q3_OK;
 }
@@ -483,9 +539,11 @@ struct q3_engine {
     // generate call under it (guide_call_begin, q3_plan_host.inc)
     GuideTable guide;
     unsigned long long guide_serial = 0;
-    // the form of the column plans the q3_generate_many_* loops run (PlanKey::pen): under a guide the masked one, whatever the table and
-    // the penalties; under a table the adjusted one, whatever the penalties
-    int pen_form() const { return guide.n_states ? kPenGuide : (bias.n_lists() ? kPenAdj : (pen_on() ? kPenOn : kPenOff)); }
+    // the sparse guide (q3_guide_set_sparse, section 2s): the same rule on a compressed table; at most one of the two forms holds
+    GuideSparse guide_sp;
+    // the form of the column plans the q3_generate_many_* loops run (PlanKey::pen): under a guide the masked one of its form, whatever
+    // the table and the penalties; under a table the adjusted one, whatever the penalties
+    int pen_form() const { return guide_sp.n_states ? kPenGuideSp : guide.n_states ? kPenGuide : (bias.n_lists() ? kPenAdj : (pen_on() ? kPenOn : kPenOff)); }
     int enqueue_sample();
 
     int load(const char* path, uint32_t ctx_len);
@@ -2132,6 +2190,78 @@ int q3_op_guide(const float* logits, size_t n, const int16_t* next_row, const q3
     a.n = (int)n;
     a.max_streams = 1;
     if ((rc = launch_now(0, k_guide_apply, dim3(kPenSlices, 1), dim3(kPenThreads), 0, a, (const BiasCtl*)dctl.as<BiasCtl>(), (const GuideCtl*)dgctl.as<GuideCtl>())) ||
+        (rc = op_end()))
+        return rc;
+    unsigned long long keys[kPenSlices], best = 0ull;
+    HIP_TRY(hipMemcpy(out, dout.p, 4 * n, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(keys, dkeys.p, sizeof keys, hipMemcpyDeviceToHost));
+    for (int i = 0; i < kPenSlices; ++i) best = std::max(best, keys[i]);
+    *argmax = (int32_t)(best & 0xffffffffull);
+    return Q3_OK;
+}
+
+int q3_op_guide_sparse(const float* logits, size_t n, int32_t dflt, const q3_guide_edge* edges, size_t n_edges, const q3_bias_entry* entries,
+                       size_t n_entries, int mode, uint32_t g, const uint32_t* counts, float presence, float frequency, float* out, int32_t* argmax,
+                       int device) {
+    g_err[0] = 0;
+    int rc;
+    if (mode != kBiasAdd && mode != kBiasAllow) return fail(Q3_ERR_ARG, "mode %d is neither ADD (0) nor ALLOW (1)", mode);
+    if ((rc = penalties_check(presence, frequency))) return rc;
+    if (!logits || !out || !argmax || n == 0) return fail(Q3_ERR_ARG, "null argument");
+    if (n > (size_t)INT32_MAX) return fail(Q3_ERR_ARG, "more than 2^31 logits");
+    if (!edges && n_edges) return fail(Q3_ERR_ARG, "null edges with %zu edges", n_edges);
+    if (n_edges > n) return fail(Q3_ERR_ARG, "%zu edges over %zu logits", n_edges, n);
+    if (dflt < -1 || dflt >= kGuideSpMaxStates) return fail(Q3_ERR_ARG, "dflt = %d: -1 (forbidden) or a state below %d", dflt, kGuideSpMaxStates);
+    for (size_t k = 0; k < n_edges; ++k) {
+        if (edges[k].token < 0 || (size_t)edges[k].token >= n) return fail(Q3_ERR_ARG, "edges[%zu].token = %d outside the %zu logits", k, edges[k].token, n);
+        if (k && edges[k].token <= edges[k - 1].token) return fail(Q3_ERR_ARG, "edges[%zu].token = %d is not above its predecessor: tokens ascend strictly", k, edges[k].token);
+        if (edges[k].next < -1 || edges[k].next >= kGuideSpMaxStates)
+            return fail(Q3_ERR_ARG, "edges[%zu].next = %d: -1 (forbidden) or a state below %d", k, edges[k].next, kGuideSpMaxStates);
+    }
+    BiasTable t;
+    const uint8_t m = (uint8_t)mode;
+    if ((rc = bias_check(entries, &n_entries, &m, 1, (long)n, t))) return rc;
+    if ((rc = op_begin(device))) return rc;
+    OpBuf dl, dc, dout, dkeys, dpen, dent, doff, dmode, dctl, ddflt, droff, dedges, dstate, dgctl;
+    const PenCtl hp{presence, frequency};
+    const int zero = 0;
+    const uint32_t roff[2] = {0u, (uint32_t)n_edges};
+    const q3_guide_edge none{0, -1};
+    if ((rc = dl.upload(logits, 4 * n)) || (rc = dout.alloc(4 * n)) || (rc = dkeys.alloc(8 * (size_t)kPenSlices)) || (rc = dpen.upload(&hp, sizeof(hp))) ||
+        (rc = dent.upload(t.entries.data(), sizeof(BiasEntry) * t.entries.size())) || (rc = doff.upload(t.off.data(), 4 * t.off.size())) ||
+        (rc = dmode.upload(t.modes.data(), 1)) || (counts && (rc = dc.upload(counts, 4 * n))) || (rc = ddflt.upload(&dflt, sizeof(dflt))) ||
+        (rc = droff.upload(roff, sizeof(roff))) || (rc = dedges.upload(n_edges ? edges : &none, sizeof(GuideEdge) * std::max(n_edges, (size_t)1))) ||
+        (rc = dstate.upload(&zero, sizeof(zero))))
+        return rc;
+    BiasCtl h{};
+    h.entries = dent.as<BiasEntry>();
+    h.list_off = doff.as<unsigned>();
+    h.modes = dmode.as<unsigned char>();
+    h.counts = counts ? dc.as<unsigned>() : nullptr;
+    h.n_lists = 1;
+    h.n_requests = 1;
+    h.g_op = g;
+    // a guide of the one state given, which request 0 starts in and its slot is in: the row holds whatever g is
+    GuideSpCtl hg{};
+    hg.dflt = ddflt.as<int>();
+    hg.row_off = droff.as<unsigned>();
+    hg.edges = dedges.as<GuideEdge>();
+    hg.start = dstate.as<int>();
+    hg.state = dstate.as<int>();
+    hg.n_states = 1;
+    hg.n_start = 1;
+    hg.n_edges = (int)n_edges;
+    if ((rc = dctl.upload(&h, sizeof(h))) || (rc = dgctl.upload(&hg, sizeof(hg)))) return rc;
+    // one row, emitting, request 0 at output g, the counts as given: k_guide_sp_apply without a pass (PenArgs::cols null)
+    PenArgs a{};
+    a.logits = dl.as<float>();
+    a.pen_logits = dout.as<float>();
+    a.pen_slots = dkeys.as<unsigned long long>();
+    a.ctl = dpen.as<PenCtl>();
+    a.n = (int)n;
+    a.max_streams = 1;
+    if ((rc = launch_now(0, k_guide_sp_apply, dim3(kPenSlices, 1), dim3(kPenThreads), 0, a, (const BiasCtl*)dctl.as<BiasCtl>(),
+                         (const GuideSpCtl*)dgctl.as<GuideSpCtl>())) ||
         (rc = op_end()))
         return rc;
     unsigned long long keys[kPenSlices], best = 0ull;

@@ -274,6 +274,52 @@ int guide_call_begin(q3_engine* e, const int* o_off, size_t n_requests, size_t n
     return Q3_OK;
 }
 
+// ---- the sparse guide of q3_guide_set_sparse on the device (q3_guide_sparse.h, section 2s): guide_alloc and guide_call_begin over
+// the compressed table.  The three arrays go up where the device does not hold this guide yet, start[] and the control block with
+// every call.
+int guide_sp_alloc(q3_engine* e) {
+    BatchCtx* b = e->batch;
+    int rc;
+    if ((rc = bias_alloc(e))) return rc;
+    if (b->guide_sp_ctl) return Q3_OK;
+    DevMem<GuideSpCtl> ctl; DevMem<int> state;
+    if ((rc = ctl.alloc(1)) || (rc = state.alloc((size_t)b->max_streams))) return rc;
+    HIP_TRY(hipMemsetAsync(ctl, 0, sizeof(GuideSpCtl), e->stream));
+    HIP_TRY(hipMemsetAsync(state, 0xff, sizeof(int) * (size_t)b->max_streams, e->stream));
+    b->guide_sp_ctl = std::move(ctl); b->guide_sp_state = std::move(state);
+    return Q3_OK;
+}
+int guide_sp_call_begin(q3_engine* e, const int* o_off, size_t n_requests, size_t n_out_total) {
+    BatchCtx* b = e->batch;
+    const GuideSparse& t = e->guide_sp;
+    int rc;
+    if ((rc = guide_sp_alloc(e)) || (rc = bias_call_begin(e, o_off, n_requests, n_out_total))) return rc;
+    if (b->guide_sp_serial != t.serial) {
+        b->guide_sp_serial = 0;
+        if ((rc = b->guide_sp_dflt.grow(t.dflt.size(), e->stream)) || (rc = b->guide_sp_off.grow(t.row_off.size(), e->stream)) ||
+            (rc = b->guide_sp_edges.grow(std::max(t.edges.size(), (size_t)1), e->stream)))
+            return rc;
+        HIP_TRY(hipMemcpyAsync(b->guide_sp_dflt, t.dflt.data(), sizeof(int) * t.dflt.size(), hipMemcpyHostToDevice, e->stream));
+        HIP_TRY(hipMemcpyAsync(b->guide_sp_off, t.row_off.data(), sizeof(uint32_t) * t.row_off.size(), hipMemcpyHostToDevice, e->stream));
+        if (!t.edges.empty())
+            HIP_TRY(hipMemcpyAsync(b->guide_sp_edges, t.edges.data(), sizeof(GuideEdge) * t.edges.size(), hipMemcpyHostToDevice, e->stream));
+        b->guide_sp_serial = t.serial;
+    }
+    if ((rc = b->guide_sp_start.grow(t.start.size(), e->stream))) return rc;
+    HIP_TRY(hipMemcpyAsync(b->guide_sp_start, t.start.data(), sizeof(int) * t.start.size(), hipMemcpyHostToDevice, e->stream));
+    GuideSpCtl h{};
+    h.dflt = b->guide_sp_dflt;
+    h.row_off = b->guide_sp_off;
+    h.edges = b->guide_sp_edges;
+    h.start = b->guide_sp_start;
+    h.state = b->guide_sp_state;
+    h.n_states = (int)t.n_states;
+    h.n_start = (int)t.start.size();
+    h.n_edges = (int)t.edges.size();
+    HIP_TRY(hipMemcpyAsync(b->guide_sp_ctl, &h, sizeof(GuideSpCtl), hipMemcpyHostToDevice, e->stream));
+    return Q3_OK;
+}
+
 // ---- the builder: the launches of key.n streams (Decode), block positions (Prefill, Verify; draw: Verify under the sampler),
 // columns (Cols; draw: the sampled column plan) or columns of a dense block over the slots (SlotPrefill), appended to `out`.
 // It reads the engine and the context and writes neither.
@@ -596,13 +642,18 @@ struct PlanBuilder {
     }
     // the penalised rows of the emitting columns and their slices' largest keys, behind the classifier (pen_alloc has run)
     // (kPenAdj: the adjusted rows of section 2q in their place, bias_alloc has run)
-    // (kPenGuide: the masked rows of section 2r, guide_alloc has run)
+    // (kPenGuide: the masked rows of section 2r, guide_alloc has run; kPenGuideSp: of section 2s, guide_sp_alloc has run)
     int penalize() {
         if (!b->pen_ctl) return fail(Q3_ERR_INTERNAL, "a plan under penalties before pen_alloc");
         if (key.pen == kPenGuide) {
             if (!b->bias_ctl || !b->guide_ctl) return fail(Q3_ERR_INTERNAL, "a plan of the masked form before guide_alloc");
             return add(F_NEXT, k_guide_apply, dim3(kPenSlices, (unsigned)n), dim3(kPenThreads), 0, pen_args(e, key.draw), (const BiasCtl*)b->bias_ctl,
                        (const GuideCtl*)b->guide_ctl);
+        }
+        if (key.pen == kPenGuideSp) {
+            if (!b->bias_ctl || !b->guide_sp_ctl) return fail(Q3_ERR_INTERNAL, "a plan of the sparse masked form before guide_sp_alloc");
+            return add(F_NEXT, k_guide_sp_apply, dim3(kPenSlices, (unsigned)n), dim3(kPenThreads), 0, pen_args(e, key.draw), (const BiasCtl*)b->bias_ctl,
+                       (const GuideSpCtl*)b->guide_sp_ctl);
         }
         if (key.pen == kPenAdj) {
             if (!b->bias_ctl) return fail(Q3_ERR_INTERNAL, "a plan of the adjusted form before bias_alloc");
@@ -651,6 +702,9 @@ struct PlanBuilder {
             if (key.pen == kPenAdj && (rc = add(F_NEXT, k_bias_count, dim3(1), dim3(64), 0, pen_args(e, key.draw), (const BiasCtl*)b->bias_ctl))) return rc;
             if (key.pen == kPenGuide &&
                 (rc = add(F_NEXT, k_guide_step, dim3(1), dim3(64), 0, pen_args(e, key.draw), (const BiasCtl*)b->bias_ctl, (const GuideCtl*)b->guide_ctl)))
+                return rc;
+            if (key.pen == kPenGuideSp &&
+                (rc = add(F_NEXT, k_guide_sp_step, dim3(1), dim3(64), 0, pen_args(e, key.draw), (const BiasCtl*)b->bias_ctl, (const GuideSpCtl*)b->guide_sp_ctl)))
                 return rc;
             if (!key.draw && key.pen) return add(F_NEXT, k_cols_turn, dim3(1), dim3(kWG), 0, b->cols_ctl, b->pen_slots, kPenSlices, kPenSlices, b->st, b->col_slot);
             if (!key.draw) return add(F_NEXT, k_cols_turn, dim3(1), dim3(kWG), 0, b->cols_ctl, b->slots, b->nslots, nslots_used, b->st, b->col_slot);
@@ -729,7 +783,8 @@ int plan_get(q3_engine* e, PlanKey key, Plan** out) {
             if (int rc = record_scratch(e, key.genlp == kGenlpTop)) return rc;
         // ... and so does the penalty state a plan under penalties points at
         if (key.pen)
-            if (int rc = key.pen == kPenGuide ? guide_alloc(e) : (key.pen == kPenAdj ? bias_alloc(e) : pen_alloc(e))) return rc;
+            if (int rc = key.pen == kPenGuideSp ? guide_sp_alloc(e) : key.pen == kPenGuide ? guide_alloc(e) : (key.pen == kPenAdj ? bias_alloc(e) : pen_alloc(e)))
+                return rc;
         Plan built;
         if (int rc = batch_build_plan(e, key, built)) return rc;
         if (key.kind == PlanKind::SlotPrefill) home = &b->dense_plans[key.n];

@@ -41,6 +41,7 @@ int cols_generate_stop(q3_engine* e, const ColsRequests& rq, const int32_t* stop
     const int pen = e->pen_form();
     if (pen == kPenAdj && (rc = bias_call_begin(e, rq.o_off.data(), n_requests, rq.n_out))) return rc;     // the call's table (section 2q)
     if (pen == kPenGuide && (rc = guide_call_begin(e, rq.o_off.data(), n_requests, rq.n_out))) return rc;  // the call's guide and table (section 2r)
+    if (pen == kPenGuideSp && (rc = guide_sp_call_begin(e, rq.o_off.data(), n_requests, rq.n_out))) return rc;  // ... in its sparse form (section 2s)
 
     // uploaded once: the prompts, the per-request records, the sampler parameters, the scheduler state with the stop list
     int* dreq = b->cols_req;

@@ -40,8 +40,12 @@ EXPORTED_SYMBOLS = [
     "q3_sampler_penalties", "q3_sampler_get_penalties", "q3_op_penalize",
     "q3_logit_bias_set", "q3_logit_bias_get", "q3_op_logit_bias",
     "q3_guide_set", "q3_guide_get", "q3_op_guide",
+    "q3_guide_set_sparse", "q3_guide_get_sparse", "q3_op_guide_sparse",
 ]
 GUIDE_MAX_STATES = 4096  # Q3_GUIDE_MAX_STATES (section 2r)
+GUIDE_SPARSE_MAX_STATES = 1 << 20   # Q3_GUIDE_SPARSE_MAX_STATES (section 2s)
+GUIDE_SPARSE_MAX_EDGES = 1 << 27    # Q3_GUIDE_SPARSE_MAX_EDGES
+EDGE_DTYPE = np.dtype([("token", np.int32), ("next", np.int32)])   # q3_guide_edge
 PENALTY_MAX = 2.0        # |presence|, |frequency| <= 2 (section 2p)
 BIAS_MAX = 4096          # Q3_BIAS_MAX: entries per list (section 2q)
 BIAS_LIMIT = 100.0       # a finite bias lies in -100 .. 100; -inf bans
@@ -317,6 +321,10 @@ def _bind(path: str) -> C.CDLL:
     L.q3_guide_get.argtypes = [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     L.q3_op_guide.argtypes = [fp, sz, C.c_void_p, C.c_void_p, sz, C.c_int, C.c_uint32, C.POINTER(C.c_uint32), C.c_float, C.c_float, fp,
                               C.POINTER(C.c_int32), C.c_int]
+    L.q3_guide_set_sparse.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, sz, sz, sz, C.POINTER(C.c_int32), sz]
+    L.q3_guide_get_sparse.argtypes = [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    L.q3_op_guide_sparse.argtypes = [fp, sz, C.c_int32, C.c_void_p, sz, C.c_void_p, sz, C.c_int, C.c_uint32, C.POINTER(C.c_uint32), C.c_float, C.c_float, fp,
+                                     C.POINTER(C.c_int32), C.c_int]
     _libs[path] = L
     return L
 
@@ -1037,7 +1045,7 @@ class Transformer:
         score, choose, embed or single-stream decode."""
         if next is None or np.size(next) == 0:
             _check(self._lib.q3_guide_set(self._h, None, 0, 0, None, 0))
-            self._guide = (None, [])
+            self._guide, self._guide_sparse = (None, []), None
             return
         table = np.asarray(next)
         if table.ndim != 2 or not np.issubdtype(table.dtype, np.integer):
@@ -1053,6 +1061,57 @@ class Transformer:
         st = (C.c_int32 * max(len(starts), 1))(*starts)
         _check(self._lib.q3_guide_set(self._h, table.ctypes.data_as(C.c_void_p), table.shape[0], table.shape[1], st, len(starts)))
         self._guide = (table, [int(x) for x in starts])
+        self._guide_sparse = None
+
+    # ---- sparse guides (include/qwen3_hip.h section 2s)
+    def set_guide_sparse(self, default, offsets, tokens, targets, start):
+        """The guide of every generate_many_* call in its sparse form (q3_guide_set_sparse): the rule of set_guide with next[s][v]
+        stated as default[s] for every token state s does not list, and targets[k] for tokens[k], offsets[s] <= k < offsets[s + 1]
+        (guide.SparseAutomaton holds such arrays).  Up to GUIDE_SPARSE_MAX_STATES states.  start, what the guide holds for and what
+        it survives are set_guide's.  One guide holds at a time: this call clears a guide of set_guide and the other way round;
+        default None or empty turns both off."""
+        if default is None or np.size(default) == 0:
+            _check(self._lib.q3_guide_set_sparse(self._h, None, None, None, 0, 0, 0, None, 0))
+            self._guide, self._guide_sparse = (None, []), None
+            return
+        arrays = []
+        for name, a in (("default", default), ("offsets", offsets), ("tokens", tokens), ("targets", targets)):
+            a = np.asarray(a)
+            if a.ndim != 1 or (a.size and not np.issubdtype(a.dtype, np.integer)):
+                raise TypeError(f"{name} must be a vector of integers")
+            if a.size and (a.min() < -1 or a.max() > 0x7fffffff):
+                raise ValueError(f"an entry of {name} lies outside -1 .. 2^31 - 1")
+            arrays.append(a)
+        default, offsets, tokens, targets = arrays
+        if offsets.size != default.size + 1 or tokens.size != targets.size or (offsets.size and offsets.min() < 0):
+            raise ValueError("offsets must hold one entry more than default, none negative, and tokens as many as targets")
+        dflt = np.ascontiguousarray(default, dtype=np.int32)
+        off = np.ascontiguousarray(offsets, dtype=np.uint32)
+        edges = np.empty(tokens.size, dtype=EDGE_DTYPE)
+        edges["token"], edges["next"] = tokens, targets
+        starts = [start] if isinstance(start, (int, np.integer)) and not isinstance(start, bool) else list(start)
+        if any(isinstance(x, bool) or not isinstance(x, (int, np.integer)) for x in starts):
+            raise TypeError(f"start must be an integer or a sequence of integers, got {start!r}")
+        if any(x < -1 or x > 0x7fffffff for x in starts):
+            raise ValueError("a start state lies outside -1 .. 2^31 - 1")
+        st = (C.c_int32 * max(len(starts), 1))(*starts)
+        _check(self._lib.q3_guide_set_sparse(self._h, dflt.ctypes.data_as(C.c_void_p), off.ctypes.data_as(C.c_void_p),
+                                             edges.ctypes.data_as(C.c_void_p) if edges.size else None, dflt.size, edges.size,
+                                             self.get_config().vocab_size, st, len(starts)))
+        self._guide_sparse = (dflt, off.astype(np.int64), edges["token"].copy(), edges["next"].copy(), [int(x) for x in starts])
+        self._guide = (None, [])
+
+    def get_guide_sparse(self):
+        """the engine's sparse guide as (default, offsets, tokens, targets, start) in the form set_guide_sparse takes them;
+        (None, None, None, None, []): none set.  The library holds the guide and tells its size (q3_guide_get_sparse); the arrays are
+        the copy kept here."""
+        n_states, n_edges, n_start = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+        _check(self._lib.q3_guide_get_sparse(self._h, C.byref(n_states), C.byref(n_edges), C.byref(n_start)))
+        kept = getattr(self, "_guide_sparse", None)
+        have = (0, 0, 0) if kept is None else (kept[0].size, kept[2].size, len(kept[4]))
+        if (int(n_states.value), int(n_edges.value), int(n_start.value)) != have:
+            raise Q3Error(-5, "the engine's sparse guide was not set through this object")
+        return (None, None, None, None, []) if kept is None else (kept[0], kept[1], kept[2], kept[3], list(kept[4]))
 
     def get_guide(self):
         """the engine's guide as (next, start) in the form set_guide takes them; (None, []): off.  The library holds the guide and
@@ -1384,6 +1443,46 @@ class _Ops:
         _check(load_library().q3_op_guide(self._fp(logits), logits.size, next_row.ctypes.data_as(C.c_void_p),
                                           flat.ctypes.data_as(C.c_void_p) if flat.size else None, len(ent), int(mode), int(g), cp, float(presence),
                                           float(frequency), self._fp(out), C.byref(idx), self.device))
+        return out, int(idx.value)
+
+    def guide_sparse(self, logits, default, tokens=(), targets=(), entries=(), mode: int = BIAS_ADD, g: int = 0, counts=None, presence: float = 0.0,
+                     frequency: float = 0.0):
+        """ops.guide with the state's row in the sparse statement of section 2s (q3_op_guide_sparse): token tokens[k] does targets[k],
+        every other token does `default`; negative: forbidden.  tokens ascend strictly.  Returns (the row as float32[n], the index of
+        its largest key)."""
+        ent = _check_bias_list(entries, mode, "entries")
+        _check_penalties(presence, frequency)
+        if isinstance(g, bool) or not isinstance(g, (int, np.integer)):
+            raise TypeError(f"g must be an integer, got {g!r}")
+        if g < 0 or g > 0xffffffff:
+            raise ValueError(f"g {g} out of range")
+        if isinstance(default, bool) or not isinstance(default, (int, np.integer)):
+            raise TypeError(f"default must be an integer, got {default!r}")
+        logits = np.ascontiguousarray(logits, dtype=np.float32)
+        if logits.ndim != 1 or logits.size == 0:
+            raise ValueError("logits must be a non-empty vector")
+        tokens, targets = np.asarray(tokens), np.asarray(targets)
+        if tokens.ndim != 1 or tokens.shape != targets.shape or (tokens.size and not (np.issubdtype(tokens.dtype, np.integer) and np.issubdtype(targets.dtype, np.integer))):
+            raise ValueError("tokens and targets must be integer vectors of one length")
+        if tokens.size and (tokens.min() < 0 or tokens.max() >= logits.size or (np.diff(tokens) <= 0).any()):
+            raise ValueError(f"tokens must ascend strictly inside the {logits.size} logits")
+        if not -1 <= default < GUIDE_SPARSE_MAX_STATES or (targets.size and (targets.min() < -1 or targets.max() >= GUIDE_SPARSE_MAX_STATES)):
+            raise ValueError(f"default or a target lies outside -1 .. {GUIDE_SPARSE_MAX_STATES - 1}")
+        edges = np.empty(tokens.size, dtype=EDGE_DTYPE)
+        edges["token"], edges["next"] = tokens, targets
+        cp = None
+        if counts is not None:
+            counts = np.ascontiguousarray(counts, dtype=np.uint32)
+            if counts.shape != logits.shape:
+                raise ValueError("logits and counts must be vectors of one length")
+            cp = counts.ctypes.data_as(C.POINTER(C.c_uint32))
+        if any(t >= logits.size for t, _, _ in ent):
+            raise ValueError(f"a token of the list lies outside the {logits.size} logits")
+        flat = _bias_array(ent)
+        out, idx = np.empty_like(logits), C.c_int32(-1)
+        _check(load_library().q3_op_guide_sparse(self._fp(logits), logits.size, int(default), edges.ctypes.data_as(C.c_void_p) if edges.size else None,
+                                                 edges.size, flat.ctypes.data_as(C.c_void_p) if flat.size else None, len(ent), int(mode), int(g), cp,
+                                                 float(presence), float(frequency), self._fp(out), C.byref(idx), self.device))
         return out, int(idx.value)
 
 

@@ -11,7 +11,7 @@ from typing import Callable, Iterable, List, Optional, Sequence, Tuple
 import numpy as np
 
 from .engine import SCORE_DTYPE, TOP_DTYPE, BIAS_ADD, BIAS_ALLOW
-from .guide import Automaton, merge_guides
+from .guide import Automaton, SparseAutomaton, merge_guides
 
 
 def sample_argmax(logits: np.ndarray) -> int:
@@ -168,7 +168,7 @@ def common_prefix_len(prompts: Sequence[Sequence[int]]) -> int:
 def generate_many(transformer, prompts: Sequence[Sequence[int]], max_new_tokens: int, stop_tokens: Iterable[int] = (), sampler=None,
                   dense_min: int = 0, stop_on_device: bool = False, shared_prefix=None, logprobs: Optional[int] = None,
                   presence_penalty: float = 0.0, frequency_penalty: float = 0.0, logit_bias=None, banned_tokens=None, allowed_tokens=None,
-                  min_tokens=0, guide=None):
+                  min_tokens=0, guide=None, regex: Optional[str] = None, tokenizer=None):
     """Many greedy generations served through the slots of Transformer.batch_init in ragged column passes
     (Transformer.generate_many_greedy).  Row r holds what Transformer.prefill(prompts[r], 0) followed by generate_greedy returns on
     an engine of its own: every prompt token goes through the model (chat's prompt loop, generation.rs:116-123), then up to
@@ -214,9 +214,22 @@ def generate_many(transformer, prompts: Sequence[Sequence[int]], max_new_tokens:
     None leaves a request unguided.  In state s only the tokens the automaton allows there may come, the first token included, in
     front of logit_bias and the penalties; the committed token moves the state.  A row ends at its stop token as ever: an automaton
     that wants to end allows a stop token in its accepting states.  Works with every option above; the logprobs stay those of the
-    raw distribution.  With guide=None the call touches no guide: one set with Transformer.set_guide simply holds."""
+    raw distribution.  With guide=None the call touches no guide: one set with Transformer.set_guide simply holds.  guide.SparseAutomaton
+    is taken wherever Automaton is (Transformer.set_guide_sparse); in a sequence that mixes the two the dense ones are converted, and
+    the engine's previous guide, of either form, is put back.
+    regex: shorthand for guide=SparseAutomaton.from_regex(regex, tokenizer.vocab, eos) with eos the one stop token of stop_tokens:
+    every row spells a prefix of a full match of the pattern (guide.regex_dfa states the syntax), and ends with eos only behind a
+    full match.  `tokenizer` is a Tokenizer or anything with a list `vocab` of the tokens' bytes.  Compiled automata are kept per
+    (pattern, tokenizer, eos).  Not together with guide=."""
     if any(len(p) == 0 for p in prompts):
         raise ValueError("Please provide a prompt")
+    if regex is not None:
+        if guide is not None:
+            raise ValueError("regex= and guide= exclude each other")
+        stop_tokens = [int(t) for t in stop_tokens]
+        if tokenizer is None or len(stop_tokens) != 1:
+            raise ValueError("regex= needs tokenizer= and exactly one stop token, the end of a full match")
+        guide = _regex_guide(regex, tokenizer, stop_tokens[0])
     args = (transformer, prompts, max_new_tokens, stop_tokens, sampler, dense_min, stop_on_device, shared_prefix, logprobs, presence_penalty,
             frequency_penalty, logit_bias, banned_tokens, allowed_tokens, min_tokens)
     if guide is None:
@@ -226,11 +239,30 @@ def generate_many(transformer, prompts: Sequence[Sequence[int]], max_new_tokens:
         # the engine sees the requests the context leaves room for, and one start state for each of them
         start = [start[r] for r in _live_requests(transformer, prompts, max_new_tokens, shared_prefix)]
     guide_before = transformer.get_guide()
-    transformer.set_guide(table, start)
+    sparse_before = transformer.get_guide_sparse() if hasattr(transformer, "get_guide_sparse") else None
+    if isinstance(table, SparseAutomaton):
+        transformer.set_guide_sparse(table.default, table.offsets, table.tokens, table.targets, start)
+    else:
+        transformer.set_guide(table, start)
     try:
         return _generate_many_bias(*args)
     finally:
-        transformer.set_guide(*guide_before)
+        # one guide holds at a time: putting back the form that held clears the other
+        if sparse_before is not None and sparse_before[0] is not None:
+            transformer.set_guide_sparse(*sparse_before)
+        else:
+            transformer.set_guide(*guide_before)
+
+
+_REGEX_GUIDES: dict = {}
+
+
+def _regex_guide(pattern: str, tokenizer, eos: int) -> SparseAutomaton:
+    """SparseAutomaton.from_regex, compiled once per (pattern, tokenizer, eos); the tokenizer is kept beside it so that its id stays its own"""
+    key = (pattern, id(tokenizer), int(eos))
+    if key not in _REGEX_GUIDES:
+        _REGEX_GUIDES[key] = (SparseAutomaton.from_regex(pattern, tokenizer.vocab, int(eos)), tokenizer)
+    return _REGEX_GUIDES[key][0]
 
 
 def _generate_many_bias(transformer, prompts, max_new_tokens, stop_tokens, sampler, dense_min, stop_on_device, shared_prefix, logprobs, presence_penalty,
