@@ -1152,6 +1152,79 @@ int q3_op_guide_sparse(const float* logits, size_t n, int32_t dflt, const q3_gui
                        size_t n_entries, int mode, uint32_t g, const uint32_t* counts /* or NULL: no penalties */, float presence, float frequency,
                        float* out /* [n] */, int32_t* argmax, int device);
 
+/* ------------------------------------------------------------------------------------------------
+ * 2t. (behind 2s so that the earlier sections stay as they were.)  Stop sequences: a request ends where the tokens it has produced
+ * complete one of several SEQUENCES, as the stop=[...] of a serving API asks -- "\n\n", "Question:", "</answer>" -- where section
+ * 2h ends it at a single token.  A STOP AUTOMATON is stated in section 2s's arrays -- dflt[n_states], row_off[n_states + 1],
+ * edges[n_edges] of q3_guide_edge, start[n_start], next[s][v] the edge's next where v is listed in state s, else dflt[s] -- and ONLY
+ * THE READING OF next[s][v] == -1 CHANGES: here it means "the sequence is complete, and the request ends with this token".
+ *     start      request r starts in start[r], or in start[0] where n_start == 1; start[r] == -1: no stop sequences for request r.
+ *     step       only GENERATED tokens move the state, y_0 being the first token stepped; prompt tokens and a shared prefix (2i)
+ *                never do.  With s_0 = start and x = next[s_g][y_g]: x == -1 ends the request with n_out[r] = g + 1, the
+ *                completing token included, as with a stop token; otherwise s_{g+1} = x.
+ *     n_emit[r]  the smallest of: the index of the first stop token + 1, the index of the first completing token + 1, n_new[r].
+ * Everything section 2h promises holds with this n_emit: the tokens are bit-identical to the loops at the cap, the passes and stats
+ * are those of q3_cols_schedule(prompt_len, n_emit), -1 stands behind the last token, no coin is drawn behind the end, and the next
+ * occupant of a slot starts from its own start state whatever state the previous occupant left.
+ * IT IS INDEPENDENT OF EVERY OTHER ENGINE-WIDE SETTING: logits, cache rows, coins, the records of 2o, penalties (2p), bias and
+ * min_tokens (2q) and guides (2r, 2s) are untouched, and a guide and a stop automaton may both be set.  min_tokens of section 2q
+ * bans stop TOKENS among a row's first tokens; it does NOT delay a sequence match.
+ * HONOURED BY THE TWO LOOPS THAT HAVE A DEVICE SCHEDULER: q3_generate_many_stop, also with n_stop == 0, and
+ * q3_generate_many_prefix, which under a stop automaton runs the loop of section 2h also with n_stop == 0.
+ * q3_generate_many_greedy, q3_generate_many_sampled and q3_generate_many_dense return exactly n_new tokens by contract and do not
+ * read it, as they do not know stop tokens.
+ * What runs (csrc/q3_stop_seq.h).  One __host__ __device__ function, stop_seq_next, steps a state: one search of the state's edges for
+ * the token, else dflt; the device loop, the host twin below and q3_op_stop_seq all call it.  While a stop automaton is set,
+ * k_cols_sched_seq stands where k_cols_sched stands -- one workgroup, one launch per pass, between two passes: it stages the
+ * scheduler state and the slots' last tokens in LDS as k_cols_sched does; then thread i < max_streams steps slot i where that slot
+ * produced a token in the pass just committed, from the request's start state on its first output and from the slot's stored state
+ * otherwise, and sets a per-slot "sequence complete" flag; behind a barrier thread 0 runs the scheduler step, whose rule 5 reads
+ * end = g == n_new || stop token || flag.  The searches of the slots run in parallel lanes, log2(E_s) dependent loads each.  The
+ * per-slot states live in device memory beside the scheduler state, in a struct of their own.  No plan key, column plan or turn
+ * kernel changes and no launch or synchronisation is added per pass.  The arrays go to the device once per q3_stop_seq_set (and
+ * again after q3_batch_init), at the first generate call under it; start[] and a control block go with every call.  With no stop
+ * automaton set every entry point launches exactly what it launched before this section existed.
+ * Only clamped values become addresses: states to [-1, n_states), edge indices to the state's range inside [0, n_edges], the token
+ * to [0, vocab).
+ * ------------------------------------------------------------------------------------------------ */
+#define Q3_STOP_SEQ_MAX_STATES 65536
+#define Q3_STOP_SEQ_MAX_EDGES 16777216
+
+/* The engine-wide stop automaton; it survives what q3_guide_set_sparse survives, and n_states == 0 clears it.  The library keeps a
+ * copy of the arrays.  Execution: waits for the stream; the device side is made by the first generate call under it.
+ * Q3_ERR_ARG, checked before the engine or the GPU is touched, by the code and in the order of q3_guide_set_sparse with the caps
+ * above in the place of its own: a null array with a non-zero count; edges without states; n_states > Q3_STOP_SEQ_MAX_STATES;
+ * n_edges > Q3_STOP_SEQ_MAX_EDGES; vocab == 0 or vocab >= 2^31; n_start == 0 with states; a start outside [-1, n_states);
+ * row_off[0] != 0, an offset below the one before it, row_off[n_states] != n_edges; a dflt outside [-1, n_states); an edge's token
+ * outside [0, vocab) or not above the token before it in its state; an edge's next outside [-1, n_states).  NOT refused: a state
+ * that allows no token -- dflt[s] == -1 with no edges says that every token completes a sequence there.  Then the null engine,
+ * then vocab != vocab_size.  A refused call changes nothing.
+ * A q3_generate_many_* call whose number of requests is neither n_start nor meets n_start == 1 is refused (Q3_ERR_ARG). */
+int q3_stop_seq_set(q3_engine* e, const int32_t* dflt /* [n_states] */, const uint32_t* row_off /* [n_states + 1] */,
+                    const q3_guide_edge* edges /* [n_edges] */, size_t n_states, size_t n_edges, size_t vocab,
+                    const int32_t* start /* [n_start] */, size_t n_start);
+int q3_stop_seq_get(const q3_engine* e, size_t* n_states, size_t* n_edges, size_t* n_start);
+
+/* q3_cols_schedule_stop under a stop automaton (host only, never touches the GPU): the passes q3_generate_many_stop runs when
+ * request r would produce rows[..] and ends at its first stop token or completed sequence.  The host steps the function the device
+ * runs, pass by pass.  n_states == 0: q3_cols_schedule_stop, entry for entry.  A token of rows outside [0, vocab) is clamped into it.
+ * Q3_ERR_ARG: null rows and the stop-list refusals of q3_cols_schedule_stop; then what q3_stop_seq_set refuses about the arrays; then
+ * what q3_cols_schedule rejects; then n_start != 1 && n_start != n_requests. */
+int q3_cols_schedule_stop_seq(const size_t* prompt_len, const size_t* n_new, size_t n_requests, int max_streams,
+                              const int32_t* rows /* concatenated, n_new[r] each */, const int32_t* stop_tokens, size_t n_stop,
+                              const int32_t* dflt, const uint32_t* row_off, const q3_guide_edge* edges, size_t n_states, size_t n_edges,
+                              size_t vocab, const int32_t* start, size_t n_start,
+                              int32_t* table /* [cap][4]: pass, slot, pos, request */, size_t cap, size_t* n_entries, size_t* n_out,
+                              q3_cols_stats* stats);
+
+/* One token stream over the tables, on the host with the step function the kernel calls: from start_state, token after token until
+ * one completes a sequence.  *n_emit = the index of the completing token + 1, or n_tokens; *end_state = the state behind the last
+ * token stepped, or -1 on a match.  start_state == -1 steps nothing: n_tokens and -1.  A token outside [0, vocab) is clamped into it.
+ * Q3_ERR_ARG: what q3_stop_seq_set refuses about the arrays with start_state as the one start; no states; null tokens with a count;
+ * a null n_emit or end_state. */
+int q3_op_stop_seq(const int32_t* dflt, const uint32_t* row_off, const q3_guide_edge* edges, size_t n_states, size_t n_edges, size_t vocab,
+                   int32_t start_state, const int32_t* tokens, size_t n_tokens, size_t* n_emit, int32_t* end_state);
+
 #ifdef __cplusplus
 }
 #endif

@@ -216,6 +216,15 @@ struct BatchCtx {
     DevMem<GuideEdge> guide_sp_edges;
     DevMem<int> guide_sp_start;
     unsigned long long guide_sp_serial = 0;
+    // the stop automaton of q3_stop_seq_set (section 2t; stop_seq_call_begin, q3_stop_host.inc): the control block and the slots'
+    // states beside cols_stop, made once; the three arrays, uploaded when stop_seq_serial is not the serial of the engine's
+    // automaton; start[] of the call in flight
+    DevMem<StopSeqDev> stop_seq_dev;
+    DevMem<int> stop_seq_dflt;
+    DevMem<unsigned> stop_seq_off;
+    DevMem<GuideEdge> stop_seq_edges;
+    DevMem<int> stop_seq_start;
+    unsigned long long stop_seq_serial = 0;
     // packed-matrix directory
     struct PM { size_t q_off, s_off; int ntiles, ng; };
     std::vector<PM> m_qkv, m_wo, m_w13, m_w2;

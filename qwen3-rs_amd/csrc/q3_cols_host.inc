@@ -79,6 +79,8 @@ int cols_requests_check(q3_engine* e, const int32_t* prompts, const size_t* prom
         return fail(Q3_ERR_ARG, "q3_guide_set holds %zu start states, one per request, and the call has %zu requests", e->guide.start.size(), n_requests);
     if (e->guide_sp.n_states && e->guide_sp.start.size() > 1 && e->guide_sp.start.size() != n_requests)
         return fail(Q3_ERR_ARG, "q3_guide_set_sparse holds %zu start states, one per request, and the call has %zu requests", e->guide_sp.start.size(), n_requests);
+    if (e->stop_seq.n_states && e->stop_seq.start.size() > 1 && e->stop_seq.start.size() != n_requests)
+        return fail(Q3_ERR_ARG, "q3_stop_seq_set holds %zu start states, one per request, and the call has %zu requests", e->stop_seq.start.size(), n_requests);
     for (size_t r = 0; draw && r < n_requests; ++r)
         if ((rc = sampler_check(temperature[r], topp[r], (long)r))) return rc;
     rq.prompts = prompts;
@@ -108,15 +110,20 @@ void cols_sched_init(ColsSched& s, int max_streams, const ColsRequests& rq, cons
 // The schedule on the host: cols_sched_step (q3_stop.h) pass after pass until no request is queued or held.  on_pass(pass, row,
 // aux, slot_last) sees every pass as the step wrote it and may set slot_last[i], the token slot i produced in it (zero unless set:
 // with an empty stop list no value of it is looked at).  Every pass advances at least one column of a request that has
-// prompt_len + n_new - 1 of them at the most: a scheduler that asks for more passes than that is wrong
+// prompt_len + n_new - 1 of them at the most: a scheduler that asks for more passes than that is wrong.
+// seq: null, or the stop automaton of section 2t over host arrays: the automaton phase of k_cols_sched_seq (stop_seq_slot,
+// q3_stop_seq.h) runs in front of every step, over slot states kept here
 template <class OnPass>
-int cols_sched_walk(ColsSched& s, const ColsRequests& rq, OnPass&& on_pass) {
+int cols_sched_walk(ColsSched& s, const ColsRequests& rq, OnPass&& on_pass, const StopSeqCtl* seq = nullptr) {
     const size_t pass_cap = rq.n_prompt + rq.n_out;
     ColEnt row[kColsMax];
     ColAux aux[kColsMax];
     int slot_last[kColsMax] = {0};
+    int seq_state[kColsMax], seq_done[kColsMax] = {0};
+    for (int i = 0; i < kColsMax; ++i) seq_state[i] = -1;
     for (size_t pass = 0;; ++pass) {
-        cols_sched_step(s, slot_last, row, aux);
+        for (int i = 0; seq && i < s.max_streams; ++i) seq_done[i] = stop_seq_slot(*seq, s.slot[i], &seq_state[i], slot_last[i]);
+        cols_sched_step(s, slot_last, row, aux, seq ? seq_done : nullptr);
         if (s.status.done) return Q3_OK;
         if (s.status.n_live < 1) return fail(Q3_ERR_INTERNAL, "the scheduler laid out a pass of %d columns", s.status.n_live);
         if (pass >= pass_cap) return fail(Q3_ERR_INTERNAL, "the scheduler asks for more than %zu passes", pass_cap);
@@ -126,10 +133,13 @@ int cols_sched_walk(ColsSched& s, const ColsRequests& rq, OnPass&& on_pass) {
 
 // q3_cols_schedule (rows == nullptr, no stop list) and q3_cols_schedule_stop: the table of the walk above
 int cols_schedule_table(const size_t* prompt_len, const size_t* n_new, size_t n_requests, int max_streams, const int32_t* rows,
-                        const int32_t* stop_tokens, size_t n_stop, int32_t* table, size_t cap, size_t* n_entries, size_t* n_out, q3_cols_stats* stats) {
+                        const int32_t* stop_tokens, size_t n_stop, int32_t* table, size_t cap, size_t* n_entries, size_t* n_out, q3_cols_stats* stats,
+                        const StopSeqCtl* seq = nullptr) {
     int rc;
     ColsRequests rq;
     if ((rc = cols_requests_lengths(prompt_len, n_new, n_requests, max_streams, rq))) return rc;
+    if (seq && seq->n_start != 1 && (size_t)seq->n_start != n_requests)
+        return fail(Q3_ERR_ARG, "the stop automaton holds %d start states, one per request, and the schedule has %zu requests", seq->n_start, n_requests);
     std::vector<int> got(n_requests, 0);
     ColsSched s;
     cols_sched_init(s, max_streams, rq, stop_tokens, n_stop, got.data());
@@ -146,7 +156,7 @@ int cols_schedule_table(const size_t* prompt_len, const size_t* n_new, size_t n_
                 ++n;
                 if (rows && c.out >= 0) slot_last[c.slot] = rows[c.out];       // what the turn kernel commits: the token this column produces
             }
-        })))
+        }, seq)))
         return rc;
     if (n_entries) *n_entries = n;
     if (n_out)
@@ -831,6 +841,40 @@ int q3_guide_get_sparse(const q3_engine* e, size_t* n_states, size_t* n_edges, s
     *n_states = e->guide_sp.n_states;
     *n_edges = e->guide_sp.edges.size();
     *n_start = e->guide_sp.start.size();
+    return Q3_OK;
+}
+
+/* ---- section 2t: stop sequences (the loop and the host twin: q3_stop_host.inc) ---- */
+
+int q3_stop_seq_set(q3_engine* e, const int32_t* dflt, const uint32_t* row_off, const q3_guide_edge* edges, size_t n_states, size_t n_edges, size_t vocab,
+                    const int32_t* start, size_t n_start) {
+    g_err[0] = 0;
+    if (int rc = stop_seq_check(dflt, row_off, edges, n_states, n_edges, vocab, start, n_start)) return rc;
+    if (!e) return fail(Q3_ERR_ARG, "null engine");
+    if (n_states && vocab != (size_t)e->cfg.vocab_size) return fail(Q3_ERR_ARG, "a stop automaton over %zu tokens (vocab_size %d)", vocab, e->cfg.vocab_size);
+    GuideSparse t;
+    if (n_states) {
+        t.dflt.assign(dflt, dflt + n_states);
+        t.row_off.assign(row_off, row_off + n_states + 1);
+        t.edges.resize(n_edges);
+        if (n_edges) memcpy(t.edges.data(), edges, sizeof(GuideEdge) * n_edges);
+        t.start.assign(start, start + n_start);
+        t.n_states = n_states;
+        t.vocab = vocab;
+    }
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    t.serial = ++e->guide_serial;
+    e->stop_seq = std::move(t);
+    return Q3_OK;
+}
+
+int q3_stop_seq_get(const q3_engine* e, size_t* n_states, size_t* n_edges, size_t* n_start) {
+    g_err[0] = 0;
+    if (!e || !n_states || !n_edges || !n_start) return fail(Q3_ERR_ARG, "null argument");
+    *n_states = e->stop_seq.n_states;
+    *n_edges = e->stop_seq.edges.size();
+    *n_start = e->stop_seq.start.size();
     return Q3_OK;
 }
 

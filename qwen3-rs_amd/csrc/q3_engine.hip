@@ -48,6 +48,7 @@
 #include "q3_bias.h"
 #include "q3_guide.h"
 #include "q3_guide_sparse.h"
+#include "q3_stop_seq.h"
 #include "q3_lookup.h"
 
 namespace {
@@ -193,9 +194,10 @@ struct GuideSparse {
 // What q3_guide_set_sparse refuses about a guide, the engine and the GPU untouched: a null array with a non-zero count, the caps,
 // states without a start entry, vocab == 0 or >= 2^31, row_off[0] != 0, offsets that decrease or do not end at n_edges, a token
 // outside [0, vocab) or not strictly ascending within its state, a next, dflt or start outside [-1, n_states), a state that allows
-// no token.
-int guide_sparse_check(const int32_t* dflt, const uint32_t* row_off, const q3_guide_edge* edges, size_t n_states, size_t n_edges, size_t vocab,
-                       const int32_t* start, size_t n_start) {
+// no token.  The stop automaton of section 2t is stated in the same arrays and checked here too (sparse_table_check with its own
+// caps and dead_ok: there -1 ends the request, and a state whose every token does so is legal).
+int sparse_table_check(const int32_t* dflt, const uint32_t* row_off, const q3_guide_edge* edges, size_t n_states, size_t n_edges, size_t vocab,
+                       const int32_t* start, size_t n_start, int max_states, int max_edges, bool dead_ok, const char* what) {
     if (!dflt && n_states) return fail(Q3_ERR_ARG, "null dflt with %zu states", n_states);
     if (!row_off && n_states) return fail(Q3_ERR_ARG, "null row_off with %zu states", n_states);
     if (!edges && n_edges) return fail(Q3_ERR_ARG, "null edges with %zu edges", n_edges);
@@ -204,9 +206,9 @@ int guide_sparse_check(const int32_t* dflt, const uint32_t* row_off, const q3_gu
         if (n_edges) return fail(Q3_ERR_ARG, "%zu edges and no state", n_edges);
         return Q3_OK;
     }
-    if (n_states > (size_t)kGuideSpMaxStates) return fail(Q3_ERR_ARG, "%zu states, at most %d", n_states, kGuideSpMaxStates);
-    if (n_edges > (size_t)kGuideSpMaxEdges) return fail(Q3_ERR_ARG, "%zu edges, at most %d", n_edges, kGuideSpMaxEdges);
-    if (vocab == 0 || vocab > (size_t)INT32_MAX) return fail(Q3_ERR_ARG, "a guide over %zu tokens: 1 .. 2^31 - 1", vocab);
+    if (n_states > (size_t)max_states) return fail(Q3_ERR_ARG, "%zu states, at most %d", n_states, max_states);
+    if (n_edges > (size_t)max_edges) return fail(Q3_ERR_ARG, "%zu edges, at most %d", n_edges, max_edges);
+    if (vocab == 0 || vocab > (size_t)INT32_MAX) return fail(Q3_ERR_ARG, "a %s over %zu tokens: 1 .. 2^31 - 1", what, vocab);
     if (n_start == 0) return fail(Q3_ERR_ARG, "%zu states and no start state", n_states);
     if (n_start > (size_t)INT32_MAX) return fail(Q3_ERR_ARG, "more than 2^31 start states");
     for (size_t r = 0; r < n_start; ++r)
@@ -229,9 +231,18 @@ int guide_sparse_check(const int32_t* dflt, const uint32_t* row_off, const q3_gu
             ok += ge.next >= 0;
         }
         const size_t listed = row_off[s + 1] - row_off[s];
-        if (ok == 0 && (dflt[s] < 0 || listed == vocab)) return fail(Q3_ERR_ARG, "state %zu allows no token", s);
+        if (!dead_ok && ok == 0 && (dflt[s] < 0 || listed == vocab)) return fail(Q3_ERR_ARG, "state %zu allows no token", s);
     }
     return Q3_OK;
+}
+int guide_sparse_check(const int32_t* dflt, const uint32_t* row_off, const q3_guide_edge* edges, size_t n_states, size_t n_edges, size_t vocab,
+                       const int32_t* start, size_t n_start) {
+    return sparse_table_check(dflt, row_off, edges, n_states, n_edges, vocab, start, n_start, kGuideSpMaxStates, kGuideSpMaxEdges, false, "guide");
+}
+// what q3_stop_seq_set, q3_op_stop_seq and q3_cols_schedule_stop_seq refuse about a stop automaton (section 2t)
+int stop_seq_check(const int32_t* dflt, const uint32_t* row_off, const q3_guide_edge* edges, size_t n_states, size_t n_edges, size_t vocab,
+                   const int32_t* start, size_t n_start) {
+    return sparse_table_check(dflt, row_off, edges, n_states, n_edges, vocab, start, n_start, kStopSeqMaxStates, kStopSeqMaxEdges, true, "stop automaton");
 }
 
 constexpr int32_t kMagic = 0x616a6331;   // configuration.rs:8
@@ -541,6 +552,8 @@ struct q3_engine {
     unsigned long long guide_serial = 0;
     // the sparse guide (q3_guide_set_sparse, section 2s): the same rule on a compressed table; at most one of the two forms holds
     GuideSparse guide_sp;
+    // the stop automaton (q3_stop_seq_set, section 2t): section 2s's arrays, read by the scheduler of the stop loop and by nothing else
+    GuideSparse stop_seq;
     // the form of the column plans the q3_generate_many_* loops run (PlanKey::pen): under a guide the masked one of its form, whatever
     // the table and the penalties; under a table the adjusted one, whatever the penalties
     int pen_form() const { return guide_sp.n_states ? kPenGuideSp : guide.n_states ? kPenGuide : (bias.n_lists() ? kPenAdj : (pen_on() ? kPenOn : kPenOff)); }

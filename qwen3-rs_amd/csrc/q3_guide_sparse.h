@@ -58,8 +58,9 @@ __device__ __forceinline__ void guide_sp_range(const GuideSpCtl& gc, int s, int&
     hi = (int)min(max(gc.row_off[s + 1], (unsigned)lo), (unsigned)gc.n_edges);
 }
 
-// the first index of e[lo .. hi) whose token is not below `token` (hi where there is none)
-__device__ __forceinline__ int guide_sp_lower(const GuideEdge* e, int lo, int hi, int token) {
+// the first index of e[lo .. hi) whose token is not below `token` (hi where there is none); the host steps the stop sequences of
+// q3_stop_seq.h through it too
+__host__ __device__ __forceinline__ int guide_sp_lower(const GuideEdge* e, int lo, int hi, int token) {
     while (lo < hi) {
         const int mid = (lo + hi) >> 1;
         if (e[mid].token < token) lo = mid + 1;

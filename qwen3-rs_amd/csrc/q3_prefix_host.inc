@@ -181,8 +181,8 @@ int q3_generate_many_prefix(q3_engine* e, const int32_t* prompts, const size_t* 
             if (temperature[r] > 0.0f) seeds_p[r] = rng_skip(seeds[r], P);
         rq.seeds = seeds_p.data();
     }
-    if (n_stop > 0) return cols_generate_stop(e, rq, stop_tokens, n_stop, out_tokens, n_out, stats);
-    // no stop token: the tabled, device-resident loop of sections 2e / 2f
+    if (n_stop > 0 || e->stop_seq.n_states) return cols_generate_stop(e, rq, stop_tokens, n_stop, out_tokens, n_out, stats);
+    // no stop token and no stop automaton (section 2t): the tabled, device-resident loop of sections 2e / 2f
     if ((rc = cols_generate(e, rq, out_tokens, stats))) return rc;
     for (size_t r = 0; r < n_requests; ++r) n_out[r] = n_new[r];
     return Q3_OK;

@@ -7,7 +7,8 @@
 // one table (cols_generate); q3_cols_schedule and q3_cols_schedule_stop step it on the host too, which is how the CPU tests reach
 // it.  A request that ends at a stop token is a request whose n_new is not known in advance, so there the table is made one pass
 // at a time, behind the pass whose tokens decide it: the same function runs in k_cols_sched on the device (one thread, between
-// two passes).
+// two passes).  Under a stop automaton (section 2t) k_cols_sched_seq of q3_stop_seq.h stands in its place: the slots' automata step
+// in parallel lanes first, and the step takes their "sequence complete" flags as its last argument.
 #pragma once
 
 namespace q3 {
@@ -38,30 +39,35 @@ struct ColsSched {
     SchedStatus status;
 };
 
+// Whether slot t produced a token in the pass laid out last (rule 4): a decode column, or a prompt run that reaches the prompt's
+// last token.  Asked before the step has taken the pass into fed and g; the step and the automaton phase of the stop sequences
+// (q3_stop_seq.h) both ask here, so they cannot disagree.
+__host__ __device__ inline bool sched_slot_emitted(const SchedSlot& t) {
+    return t.req >= 0 && (t.took < 0 || (t.took > 0 && t.fed + t.took == t.plen));
+}
+
 // One step: rules 4 and 5 for the pass just committed (slot_last[i] = the token slot i produced in it), then rules 1 to 3 for the
 // next pass, written as one row of kColsMax entries -- pads as cols_job_run makes them -- and, where aux is not null, the
 // ColAux row of the sampled plans.  With n_stop == 0 the values of slot_last decide nothing.  No arrays of its own: the per-slot
-// record of the pass in flight is SchedSlot::took.
-__host__ __device__ inline void cols_sched_step(ColsSched& s, const int* slot_last, ColEnt* row, ColAux* aux) {
+// record of the pass in flight is SchedSlot::took.  seq_done: null, or per slot whether the token it produced completes a stop
+// sequence (section 2t; read where the slot emitted).
+__host__ __device__ inline void cols_sched_step(ColsSched& s, const int* slot_last, ColEnt* row, ColAux* aux, const int* seq_done) {
     const int ms = s.max_streams;
-    // 4. a run that reached its prompt's last token produced y_0; 5. a request ends at n_new tokens or at a stop token
+    // 4. a run that reached its prompt's last token produced y_0; 5. a request ends at n_new tokens, at a stop token or where a
+    // stop sequence is complete
     for (int i = 0; i < ms; ++i) {
         SchedSlot& t = s.slot[i];
         if (t.req < 0) continue;
-        bool kept = false;
+        const bool kept = sched_slot_emitted(t);
         if (t.took < 0) {
             ++t.g;
-            kept = true;
         } else if (t.took > 0) {
             t.fed += t.took;
-            if (t.fed == t.plen) {
-                t.g = 1;
-                kept = true;
-            }
+            if (kept) t.g = 1;
         }
         t.took = 0;
         if (!kept) continue;
-        bool end = t.g == t.nnew;
+        bool end = t.g == t.nnew || (seq_done && seq_done[i] != 0);
         const int tok = slot_last[i];
         for (int k = 0; k < s.n_stop; ++k) end = end || tok == s.stop[k];
         if (end) {
@@ -155,7 +161,7 @@ __global__ __launch_bounds__(64) void k_cols_sched(ColsStopDev* d, ColsCtl* ctl,
     for (int i = t; i < nw; i += 64) sw[i] = gw[i];
     if (t < kColsMax) last[t] = ctl->slot_last[t];
     __syncthreads();
-    if (t == 0) cols_sched_step(s, last, row, draw ? aux : nullptr);
+    if (t == 0) cols_sched_step(s, last, row, draw ? aux : nullptr, nullptr);
     __syncthreads();
     for (int i = t; i < nw; i += 64) gw[i] = sw[i];
     const SchedStatus st = s.status;

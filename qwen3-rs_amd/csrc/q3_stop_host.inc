@@ -14,6 +14,47 @@ int stop_list_check(const int32_t* stop_tokens, size_t n_stop) {
     return Q3_OK;
 }
 
+// The stop automaton of q3_stop_seq_set on the device (q3_stop_seq.h, section 2t), on the stream in front of a call's first pass:
+// the control block with the slots' states, made once and cleared to -1 then -- a later call finds the states its predecessor left,
+// and a request's first output never reads them; the three arrays where the device does not hold this automaton yet -- once per
+// q3_stop_seq_set and per batched state, never per call; start[] and the control block with every call.
+int stop_seq_call_begin(q3_engine* e) {
+    BatchCtx* b = e->batch;
+    const GuideSparse& t = e->stop_seq;
+    int rc;
+    if (!b->stop_seq_dev) {
+        DevMem<StopSeqDev> dev;
+        if ((rc = dev.alloc(1))) return rc;
+        HIP_TRY(hipMemsetAsync(dev, 0xff, sizeof(StopSeqDev), e->stream));
+        b->stop_seq_dev = std::move(dev);
+    }
+    if (b->stop_seq_serial != t.serial) {
+        b->stop_seq_serial = 0;
+        if ((rc = b->stop_seq_dflt.grow(t.dflt.size(), e->stream)) || (rc = b->stop_seq_off.grow(t.row_off.size(), e->stream)) ||
+            (rc = b->stop_seq_edges.grow(std::max(t.edges.size(), (size_t)1), e->stream)))
+            return rc;
+        HIP_TRY(hipMemcpyAsync(b->stop_seq_dflt, t.dflt.data(), sizeof(int) * t.dflt.size(), hipMemcpyHostToDevice, e->stream));
+        HIP_TRY(hipMemcpyAsync(b->stop_seq_off, t.row_off.data(), sizeof(uint32_t) * t.row_off.size(), hipMemcpyHostToDevice, e->stream));
+        if (!t.edges.empty())
+            HIP_TRY(hipMemcpyAsync(b->stop_seq_edges, t.edges.data(), sizeof(GuideEdge) * t.edges.size(), hipMemcpyHostToDevice, e->stream));
+        b->stop_seq_serial = t.serial;
+    }
+    if ((rc = b->stop_seq_start.grow(t.start.size(), e->stream))) return rc;
+    HIP_TRY(hipMemcpyAsync(b->stop_seq_start, t.start.data(), sizeof(int) * t.start.size(), hipMemcpyHostToDevice, e->stream));
+    StopSeqCtl h{};
+    h.dflt = b->stop_seq_dflt;
+    h.row_off = b->stop_seq_off;
+    h.edges = b->stop_seq_edges;
+    h.start = b->stop_seq_start;
+    h.n_states = (int)t.n_states;
+    h.n_start = (int)t.start.size();
+    h.n_edges = (int)t.edges.size();
+    h.vocab = (int)t.vocab;
+    StopSeqDev* dev = b->stop_seq_dev;
+    HIP_TRY(hipMemcpyAsync(&dev->ctl, &h, sizeof(StopSeqCtl), hipMemcpyHostToDevice, e->stream));
+    return Q3_OK;
+}
+
 // rq: checked by cols_requests_check, with the prefix in front of the prompts as its pos_base
 int cols_generate_stop(q3_engine* e, const ColsRequests& rq, const int32_t* stop_tokens, size_t n_stop, int32_t* out_tokens, size_t* n_out,
                        q3_cols_stats* stats) {
@@ -42,6 +83,8 @@ int cols_generate_stop(q3_engine* e, const ColsRequests& rq, const int32_t* stop
     if (pen == kPenAdj && (rc = bias_call_begin(e, rq.o_off.data(), n_requests, rq.n_out))) return rc;     // the call's table (section 2q)
     if (pen == kPenGuide && (rc = guide_call_begin(e, rq.o_off.data(), n_requests, rq.n_out))) return rc;  // the call's guide and table (section 2r)
     if (pen == kPenGuideSp && (rc = guide_sp_call_begin(e, rq.o_off.data(), n_requests, rq.n_out))) return rc;  // ... in its sparse form (section 2s)
+    const bool seq = e->stop_seq.n_states != 0;            // a stop automaton holds (section 2t): k_cols_sched_seq stands for k_cols_sched
+    if (seq && (rc = stop_seq_call_begin(e))) return rc;
 
     // uploaded once: the prompts, the per-request records, the sampler parameters, the scheduler state with the stop list
     int* dreq = b->cols_req;
@@ -79,7 +122,9 @@ int cols_generate_stop(q3_engine* e, const ColsRequests& rq, const int32_t* stop
     SchedStatus* hs = b->h_cols_stop;
     size_t passes = 0;
     for (;;) {
-        if ((rc = launch_now(e->stream, k_cols_sched, dim3(1), dim3(64), 0, d, b->cols_ctl, draw ? 1 : 0))) return rc;
+        if (seq) rc = launch_now(e->stream, k_cols_sched_seq, dim3(1), dim3(64), 0, d, b->cols_ctl, (StopSeqDev*)b->stop_seq_dev, draw ? 1 : 0);
+        else rc = launch_now(e->stream, k_cols_sched, dim3(1), dim3(64), 0, d, b->cols_ctl, draw ? 1 : 0);
+        if (rc) return rc;
         // the pass is set up by a launch of its own, like pass 0 of the kept loops (n_live is 0: nothing to commit)
         if ((rc = cols_turn_setup(e, draw))) return rc;
         HIP_TRY(hipMemcpyAsync(hs, &d->status, sizeof(SchedStatus), hipMemcpyDeviceToHost, e->stream));
@@ -130,6 +175,41 @@ int q3_cols_schedule_stop(const size_t* prompt_len, const size_t* n_new, size_t 
     if (!rows) return fail(Q3_ERR_ARG, "null rows");
     if ((rc = stop_list_check(stop_tokens, n_stop))) return rc;
     return cols_schedule_table(prompt_len, n_new, n_requests, max_streams, rows, stop_tokens, n_stop, table, cap, n_entries, n_out, stats);
+}
+
+/* ---- section 2t: the host twin of the loop under a stop automaton, and one token stream over the tables ---- */
+
+int q3_cols_schedule_stop_seq(const size_t* prompt_len, const size_t* n_new, size_t n_requests, int max_streams, const int32_t* rows,
+                              const int32_t* stop_tokens, size_t n_stop, const int32_t* dflt, const uint32_t* row_off, const q3_guide_edge* edges,
+                              size_t n_states, size_t n_edges, size_t vocab, const int32_t* start, size_t n_start, int32_t* table, size_t cap,
+                              size_t* n_entries, size_t* n_out, q3_cols_stats* stats) {
+    g_err[0] = 0;
+    int rc;
+    if (!rows) return fail(Q3_ERR_ARG, "null rows");
+    if ((rc = stop_list_check(stop_tokens, n_stop))) return rc;
+    if ((rc = stop_seq_check(dflt, row_off, edges, n_states, n_edges, vocab, start, n_start))) return rc;
+    static_assert(sizeof(GuideEdge) == sizeof(q3_guide_edge), "one layout");
+    const StopSeqCtl c{dflt, row_off, reinterpret_cast<const GuideEdge*>(edges), start, (int)n_states, (int)n_start, (int)n_edges, (int)vocab};
+    return cols_schedule_table(prompt_len, n_new, n_requests, max_streams, rows, stop_tokens, n_stop, table, cap, n_entries, n_out, stats,
+                               n_states ? &c : nullptr);
+}
+
+int q3_op_stop_seq(const int32_t* dflt, const uint32_t* row_off, const q3_guide_edge* edges, size_t n_states, size_t n_edges, size_t vocab,
+                   int32_t start_state, const int32_t* tokens, size_t n_tokens, size_t* n_emit, int32_t* end_state) {
+    g_err[0] = 0;
+    int rc;
+    if ((rc = stop_seq_check(dflt, row_off, edges, n_states, n_edges, vocab, &start_state, 1))) return rc;
+    if (n_states == 0) return fail(Q3_ERR_ARG, "a stop automaton of no states");
+    if (!tokens && n_tokens) return fail(Q3_ERR_ARG, "null tokens with %zu tokens", n_tokens);
+    if (!n_emit || !end_state) return fail(Q3_ERR_ARG, "null argument");
+    const StopSeqCtl c{dflt, row_off, reinterpret_cast<const GuideEdge*>(edges), &start_state, (int)n_states, 1, (int)n_edges, (int)vocab};
+    int s = start_state;
+    size_t g = 0;
+    for (; s >= 0 && g < n_tokens; ++g) s = stop_seq_next(c, s, tokens[g]);
+    // a match ends the walk behind the completing token; start -1 steps nothing
+    *n_emit = start_state < 0 ? n_tokens : g;
+    *end_state = s;
+    return Q3_OK;
 }
 
 }  // extern "C"

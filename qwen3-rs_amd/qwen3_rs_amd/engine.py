@@ -41,11 +41,14 @@ EXPORTED_SYMBOLS = [
     "q3_logit_bias_set", "q3_logit_bias_get", "q3_op_logit_bias",
     "q3_guide_set", "q3_guide_get", "q3_op_guide",
     "q3_guide_set_sparse", "q3_guide_get_sparse", "q3_op_guide_sparse",
+    "q3_stop_seq_set", "q3_stop_seq_get", "q3_cols_schedule_stop_seq", "q3_op_stop_seq",
 ]
 GUIDE_MAX_STATES = 4096  # Q3_GUIDE_MAX_STATES (section 2r)
 GUIDE_SPARSE_MAX_STATES = 1 << 20   # Q3_GUIDE_SPARSE_MAX_STATES (section 2s)
 GUIDE_SPARSE_MAX_EDGES = 1 << 27    # Q3_GUIDE_SPARSE_MAX_EDGES
 EDGE_DTYPE = np.dtype([("token", np.int32), ("next", np.int32)])   # q3_guide_edge
+STOP_SEQ_MAX_STATES = 1 << 16       # Q3_STOP_SEQ_MAX_STATES (section 2t)
+STOP_SEQ_MAX_EDGES = 1 << 24        # Q3_STOP_SEQ_MAX_EDGES
 PENALTY_MAX = 2.0        # |presence|, |frequency| <= 2 (section 2p)
 BIAS_MAX = 4096          # Q3_BIAS_MAX: entries per list (section 2q)
 BIAS_LIMIT = 100.0       # a finite bias lies in -100 .. 100; -inf bans
@@ -325,6 +328,11 @@ def _bind(path: str) -> C.CDLL:
     L.q3_guide_get_sparse.argtypes = [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     L.q3_op_guide_sparse.argtypes = [fp, sz, C.c_int32, C.c_void_p, sz, C.c_void_p, sz, C.c_int, C.c_uint32, C.POINTER(C.c_uint32), C.c_float, C.c_float, fp,
                                      C.POINTER(C.c_int32), C.c_int]
+    L.q3_stop_seq_set.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, sz, sz, sz, C.POINTER(C.c_int32), sz]
+    L.q3_stop_seq_get.argtypes = [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    L.q3_cols_schedule_stop_seq.argtypes = [szp, szp, sz, C.c_int, i32p, i32p, sz, C.c_void_p, C.c_void_p, C.c_void_p, sz, sz, sz, C.POINTER(C.c_int32), sz,
+                                            i32p, sz, szp, szp, C.POINTER(_ColsStats)]
+    L.q3_op_stop_seq.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, sz, sz, sz, C.c_int32, i32p, sz, C.POINTER(C.c_size_t), C.POINTER(C.c_int32)]
     _libs[path] = L
     return L
 
@@ -475,6 +483,53 @@ def cols_schedule_stop(prompt_len, n_new, max_streams: int, rows, stop_tokens):
     _check(L.q3_cols_schedule_stop(pl, nn, nr, max_streams, flat, stop, len(stop_tokens), None, 0, C.byref(n), n_out, C.byref(st)))
     table = (C.c_int32 * max(1, 4 * n.value))()
     _check(L.q3_cols_schedule_stop(pl, nn, nr, max_streams, flat, stop, len(stop_tokens), table, n.value, C.byref(n), n_out, C.byref(st)))
+    cols = [tuple(int(table[4 * i + k]) for k in range(4)) for i in range(n.value)]
+    return cols, [int(n_out[r]) for r in range(nr)], ColsStats(st.passes, st.live_columns, st.prompt_columns, st.decode_columns)
+
+
+def _sparse_tables(default, offsets, tokens, targets):
+    """the arrays of a SparseAutomaton as the library takes them: (dflt int32, row_off uint32, edges EDGE_DTYPE), checked for type
+    and range of the integer formats only -- what the tables may say is the library's to refuse"""
+    arrays = []
+    for name, a in (("default", default), ("offsets", offsets), ("tokens", tokens), ("targets", targets)):
+        a = np.asarray(a)
+        if a.ndim != 1 or (a.size and not np.issubdtype(a.dtype, np.integer)):
+            raise TypeError(f"{name} must be a vector of integers")
+        if a.size and (a.min() < -0x80000000 or a.max() > (0xffffffff if name == "offsets" else 0x7fffffff)):
+            raise ValueError(f"an entry of {name} does not fit its 32 bits")
+        arrays.append(a)
+    default, offsets, tokens, targets = arrays
+    if tokens.size != targets.size or (offsets.size and offsets.min() < 0):
+        raise ValueError("tokens must hold as many entries as targets, and no offset may be negative")
+    edges = np.empty(tokens.size, dtype=EDGE_DTYPE)
+    edges["token"], edges["next"] = tokens, targets
+    return np.ascontiguousarray(default, dtype=np.int32), np.ascontiguousarray(offsets, dtype=np.uint32), edges
+
+
+def _void(a):
+    return a.ctypes.data_as(C.c_void_p) if a.size else None
+
+
+def cols_schedule_stop_seq(prompt_len, n_new, max_streams: int, rows, stop_tokens, tables, vocab_size: int, start):
+    """cols_schedule_stop under a stop automaton (q3_cols_schedule_stop_seq, host only: the scheduler step and the automaton step of
+    the device loop, run on the host).  tables: (default, offsets, tokens, targets) as guide.SparseAutomaton holds them, or None for
+    no automaton; start: one start state, or one per request (-1: no stop sequences for that request).
+    Returns ([(pass, slot, pos, request), ...] in column order, n_out per request, ColsStats)."""
+    if len(prompt_len) != len(n_new) or len(rows) != len(n_new) or any(len(r) != int(k) for r, k in zip(rows, n_new)):
+        raise ValueError("one n_new and one row of n_new tokens per prompt")
+    L = load_library()
+    nr = len(prompt_len)
+    pl, nn, n, st = _size_array(prompt_len), _size_array(n_new), C.c_size_t(0), _ColsStats()
+    flat, stop, n_out = _i32_array([t for r in rows for t in r]), _i32_array(stop_tokens), _size_array([0] * nr)
+    if tables is None:
+        auto = (None, None, None, 0, 0, 0, None, 0)
+    else:
+        dflt, off, edges = _sparse_tables(*tables)
+        starts = [int(start)] if isinstance(start, (int, np.integer)) else [int(x) for x in start]
+        auto = (_void(dflt), _void(off), _void(edges), dflt.size, edges.size, int(vocab_size), _i32_array(starts), len(starts))
+    _check(L.q3_cols_schedule_stop_seq(pl, nn, nr, max_streams, flat, stop, len(stop_tokens), *auto, None, 0, C.byref(n), n_out, C.byref(st)))
+    table = (C.c_int32 * max(1, 4 * n.value))()
+    _check(L.q3_cols_schedule_stop_seq(pl, nn, nr, max_streams, flat, stop, len(stop_tokens), *auto, table, n.value, C.byref(n), n_out, C.byref(st)))
     cols = [tuple(int(table[4 * i + k]) for k in range(4)) for i in range(n.value)]
     return cols, [int(n_out[r]) for r in range(nr)], ColsStats(st.passes, st.live_columns, st.prompt_columns, st.decode_columns)
 
@@ -875,6 +930,46 @@ class Transformer:
         generate_many_greedy / generate_many_sampled -- on the full prompts prefix + suffixes[r]; the passes are those of the
         suffixes alone.  Arguments and return value as for generate_many_stop."""
         return self._generate_many_stop(self._lib.q3_generate_many_prefix, suffixes, n_new, stop_tokens, sampler, raw)
+
+    # ---- stop sequences (include/qwen3_hip.h section 2t)
+    cols_schedule_stop_seq = staticmethod(cols_schedule_stop_seq)
+
+    def set_stop_sequences(self, automaton, start=None):
+        """The stop automaton of every generate_many_stop / generate_many_prefix call (q3_stop_seq_set): a guide.SparseAutomaton (or
+        anything with its default, offsets, tokens, targets and start) in which a target of -1 means "the sequence is complete": a
+        request ends with the token that completes one, as it ends with a stop token (stops.stop_automaton and
+        stops.stop_automaton_from_strings build them).  start: None for the automaton's own start state, one state for every
+        request, or a sequence of one per request (-1: no stop sequences for that request); a call with another number of requests
+        raises.  None turns it off (the default).  Only generated tokens move the state.  The setting is the engine's: it survives
+        what set_guide_sparse survives, it is independent of guides, bias, penalties, logprobs and min_tokens, and the loops without
+        a device scheduler (generate_many_greedy / _sampled / _dense) do not read it."""
+        if automaton is None:
+            _check(self._lib.q3_stop_seq_set(self._h, None, None, None, 0, 0, 0, None, 0))
+            self._stop_seq = None
+            return
+        dflt, off, edges = _sparse_tables(automaton.default, automaton.offsets, automaton.tokens, automaton.targets)
+        if start is None:
+            start = automaton.start
+        starts = [start] if isinstance(start, (int, np.integer)) and not isinstance(start, bool) else list(start)
+        if any(isinstance(x, bool) or not isinstance(x, (int, np.integer)) for x in starts):
+            raise TypeError(f"start must be an integer or a sequence of integers, got {start!r}")
+        if any(x < -1 or x > 0x7fffffff for x in starts):
+            raise ValueError("a start state lies outside -1 .. 2^31 - 1")
+        st = (C.c_int32 * max(len(starts), 1))(*starts)
+        vocab = int(getattr(automaton, "vocab_size", self.get_config().vocab_size))      # another vocabulary than the engine's is refused
+        _check(self._lib.q3_stop_seq_set(self._h, _void(dflt), _void(off), _void(edges), dflt.size, edges.size, vocab, st, len(starts)))
+        self._stop_seq = (automaton, [int(x) for x in starts], (dflt.size, edges.size))
+
+    def get_stop_sequences(self):
+        """the engine's stop automaton as (automaton, start) in the form set_stop_sequences takes them; (None, []): none set.  The
+        library holds the tables and tells their size (q3_stop_seq_get); the automaton is the object kept here."""
+        n_states, n_edges, n_start = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+        _check(self._lib.q3_stop_seq_get(self._h, C.byref(n_states), C.byref(n_edges), C.byref(n_start)))
+        kept = getattr(self, "_stop_seq", None)
+        have = (0, 0, 0) if kept is None else (kept[2][0], kept[2][1], len(kept[1]))
+        if (int(n_states.value), int(n_edges.value), int(n_start.value)) != have:
+            raise Q3Error(-5, "the engine's stop automaton was not set through this object")
+        return (None, []) if kept is None else (kept[0], list(kept[1]))
 
     # ---- embeddings (include/qwen3_hip.h section 2j)
     def embed_many(self, prompts, normalize: bool = True, out_dim: Optional[int] = None, use_prefix: bool = False):
@@ -1484,6 +1579,17 @@ class _Ops:
                                                  edges.size, flat.ctypes.data_as(C.c_void_p) if flat.size else None, len(ent), int(mode), int(g), cp,
                                                  float(presence), float(frequency), self._fp(out), C.byref(idx), self.device))
         return out, int(idx.value)
+
+    def stop_seq(self, default, offsets, tokens, targets, vocab_size: int, start_state: int, stream):
+        """One token stream over a stop automaton, on the host with the step function the device loop calls (q3_op_stop_seq): from
+        start_state, token after token until next[state][token] is -1.  Returns (n_emit, end_state): the index of the completing
+        token + 1 or len(stream), and the state behind the last token stepped or -1 on a match."""
+        dflt, off, edges = _sparse_tables(default, offsets, tokens, targets)
+        toks = [int(t) for t in stream]
+        n_emit, end = C.c_size_t(0), C.c_int32(0)
+        _check(load_library().q3_op_stop_seq(_void(dflt), _void(off), _void(edges), dflt.size, edges.size, int(vocab_size), int(start_state),
+                                             _i32_array(toks) if toks else None, len(toks), C.byref(n_emit), C.byref(end)))
+        return int(n_emit.value), int(end.value)
 
 
 ops = _Ops()

@@ -12,6 +12,7 @@ import numpy as np
 
 from .engine import SCORE_DTYPE, TOP_DTYPE, BIAS_ADD, BIAS_ALLOW
 from .guide import Automaton, SparseAutomaton, merge_guides
+from .stops import compile_stop, first_match
 
 
 def sample_argmax(logits: np.ndarray) -> int:
@@ -168,7 +169,7 @@ def common_prefix_len(prompts: Sequence[Sequence[int]]) -> int:
 def generate_many(transformer, prompts: Sequence[Sequence[int]], max_new_tokens: int, stop_tokens: Iterable[int] = (), sampler=None,
                   dense_min: int = 0, stop_on_device: bool = False, shared_prefix=None, logprobs: Optional[int] = None,
                   presence_penalty: float = 0.0, frequency_penalty: float = 0.0, logit_bias=None, banned_tokens=None, allowed_tokens=None,
-                  min_tokens=0, guide=None, regex: Optional[str] = None, tokenizer=None):
+                  min_tokens=0, guide=None, regex: Optional[str] = None, tokenizer=None, stop=None):
     """Many greedy generations served through the slots of Transformer.batch_init in ragged column passes
     (Transformer.generate_many_greedy).  Row r holds what Transformer.prefill(prompts[r], 0) followed by generate_greedy returns on
     an engine of its own: every prompt token goes through the model (chat's prompt loop, generation.rs:116-123), then up to
@@ -220,7 +221,16 @@ def generate_many(transformer, prompts: Sequence[Sequence[int]], max_new_tokens:
     regex: shorthand for guide=SparseAutomaton.from_regex(regex, tokenizer.vocab, eos) with eos the one stop token of stop_tokens:
     every row spells a prefix of a full match of the pattern (guide.regex_dfa states the syntax), and ends with eos only behind a
     full match.  `tokenizer` is a Tokenizer or anything with a list `vocab` of the tokens' bytes.  Compiled automata are kept per
-    (pattern, tokenizer, eos).  Not together with guide=."""
+    (pattern, tokenizer, eos).  Not together with guide=.
+    stop: stop SEQUENCES, the stop=[...] of a serving API: a list of strings (needs tokenizer=; a string may end inside a token or span
+    several tokens), a list of token lists, a SparseAutomaton of stops.stop_automaton / stops.stop_automaton_from_strings, or a
+    sequence of one such value per request in which None gives a request no stop sequences.  A row ends with the token that
+    completes a sequence, as it ends with a stop token, whichever comes first; stops.cut_at_stop(text, strings) then gives the text
+    in front of the stop string.  Only generated tokens count.  min_tokens does not delay a sequence.  By default the rows are cut
+    on the host (SparseAutomaton.walk); with stop_on_device=True the automaton goes to the engine for this call
+    (Transformer.set_stop_sequences, put back afterwards, also when the call raises) and the device loop ends the requests
+    (Transformer.generate_many_stop, also without stop_tokens, or generate_many_prefix): the same rows in fewer passes.  Works
+    with every option above except dense_min > 0 under stop_on_device (ValueError)."""
     if any(len(p) == 0 for p in prompts):
         raise ValueError("Please provide a prompt")
     if regex is not None:
@@ -230,8 +240,9 @@ def generate_many(transformer, prompts: Sequence[Sequence[int]], max_new_tokens:
         if tokenizer is None or len(stop_tokens) != 1:
             raise ValueError("regex= needs tokenizer= and exactly one stop token, the end of a full match")
         guide = _regex_guide(regex, tokenizer, stop_tokens[0])
+    stop_seq = None if stop is None else compile_stop(stop, len(prompts), transformer.get_config().vocab_size, tokenizer)
     args = (transformer, prompts, max_new_tokens, stop_tokens, sampler, dense_min, stop_on_device, shared_prefix, logprobs, presence_penalty,
-            frequency_penalty, logit_bias, banned_tokens, allowed_tokens, min_tokens)
+            frequency_penalty, logit_bias, banned_tokens, allowed_tokens, min_tokens, stop_seq)
     if guide is None:
         return _generate_many_bias(*args)
     table, start = merge_guides(guide, len(prompts))
@@ -266,10 +277,10 @@ def _regex_guide(pattern: str, tokenizer, eos: int) -> SparseAutomaton:
 
 
 def _generate_many_bias(transformer, prompts, max_new_tokens, stop_tokens, sampler, dense_min, stop_on_device, shared_prefix, logprobs, presence_penalty,
-                        frequency_penalty, logit_bias, banned_tokens, allowed_tokens, min_tokens):
+                        frequency_penalty, logit_bias, banned_tokens, allowed_tokens, min_tokens, stop_seq=None):
     """generate_many behind its guide handling"""
     args = (transformer, prompts, max_new_tokens, stop_tokens, sampler, dense_min, stop_on_device, shared_prefix, logprobs, presence_penalty,
-            frequency_penalty)
+            frequency_penalty, stop_seq)
     if logit_bias is None and banned_tokens is None and allowed_tokens is None and np.isscalar(min_tokens) and min_tokens == 0:
         return _generate_many_pen(*args)
     lists, modes = merge_logit_bias(len(prompts), logit_bias, banned_tokens, allowed_tokens, min_tokens, stop_tokens)
@@ -343,20 +354,21 @@ def merge_logit_bias(n_requests, logit_bias=None, banned_tokens=None, allowed_to
 
 
 def _generate_many_pen(transformer, prompts, max_new_tokens, stop_tokens, sampler, dense_min, stop_on_device, shared_prefix, logprobs, presence_penalty,
-                       frequency_penalty):
+                       frequency_penalty, stop_seq=None):
     """generate_many behind its logit-bias handling"""
     # (an engine stand-in without the setting serves a call without penalties as it did)
     if hasattr(transformer, "get_penalties") or presence_penalty != 0.0 or frequency_penalty != 0.0:
         pen_before = transformer.get_penalties()
         transformer.set_penalties(presence_penalty, frequency_penalty)
         try:
-            return _generate_many_lp(transformer, prompts, max_new_tokens, stop_tokens, sampler, dense_min, stop_on_device, shared_prefix, logprobs)
+            return _generate_many_lp(transformer, prompts, max_new_tokens, stop_tokens, sampler, dense_min, stop_on_device, shared_prefix, logprobs,
+                                     stop_seq)
         finally:
             transformer.set_penalties(*pen_before)
-    return _generate_many_lp(transformer, prompts, max_new_tokens, stop_tokens, sampler, dense_min, stop_on_device, shared_prefix, logprobs)
+    return _generate_many_lp(transformer, prompts, max_new_tokens, stop_tokens, sampler, dense_min, stop_on_device, shared_prefix, logprobs, stop_seq)
 
 
-def _generate_many_lp(transformer, prompts, max_new_tokens, stop_tokens, sampler, dense_min, stop_on_device, shared_prefix, logprobs):
+def _generate_many_lp(transformer, prompts, max_new_tokens, stop_tokens, sampler, dense_min, stop_on_device, shared_prefix, logprobs, stop_seq=None):
     """generate_many behind its penalties handling"""
     if logprobs is not None:
         if isinstance(logprobs, bool) or not isinstance(logprobs, (int, np.integer)) or logprobs < 0 or logprobs > 64:
@@ -364,7 +376,8 @@ def _generate_many_lp(transformer, prompts, max_new_tokens, stop_tokens, sampler
         before = transformer.get_gen_logprobs()
         transformer.set_gen_logprobs(int(logprobs))
         try:
-            rows, stats, recs = _generate_many(transformer, prompts, max_new_tokens, stop_tokens, sampler, dense_min, stop_on_device, shared_prefix, True)
+            rows, stats, recs = _generate_many(transformer, prompts, max_new_tokens, stop_tokens, sampler, dense_min, stop_on_device, shared_prefix, True,
+                                               stop_seq)
         finally:
             transformer.set_gen_logprobs(before)
         k = int(logprobs)
@@ -376,11 +389,12 @@ def _generate_many_lp(transformer, prompts, max_new_tokens, stop_tokens, sampler
             out.append((logprobs_of(r), np.array(t["index"], dtype=np.int32).reshape(len(r), k), top_logprobs_of(r, t).reshape(len(r), k),
                         np.asarray(q, dtype=np.int32)))
         return rows, stats, out
-    return _generate_many(transformer, prompts, max_new_tokens, stop_tokens, sampler, dense_min, stop_on_device, shared_prefix, False)[:2]
+    return _generate_many(transformer, prompts, max_new_tokens, stop_tokens, sampler, dense_min, stop_on_device, shared_prefix, False, stop_seq)[:2]
 
 
-def _generate_many(transformer, prompts, max_new_tokens, stop_tokens, sampler, dense_min, stop_on_device, shared_prefix, read_logprobs):
-    """generate_many behind its logprobs handling: (rows, ColsStats, per row the engine's (records, tops, ranks) or None)"""
+def _generate_many(transformer, prompts, max_new_tokens, stop_tokens, sampler, dense_min, stop_on_device, shared_prefix, read_logprobs, stop_seq=None):
+    """generate_many behind its logprobs handling: (rows, ColsStats, per row the engine's (records, tops, ranks) or None).
+    stop_seq: None, or stops.compile_stop's (automaton, start) with one start state or one per prompt"""
     stop = set(stop_tokens)
     if stop_on_device and dense_min > 0:
         raise ValueError("stop_on_device=True runs column passes only: no dense_min > 0")
@@ -404,20 +418,35 @@ def _generate_many(transformer, prompts, max_new_tokens, stop_tokens, sampler, d
         if sampler is not None:
             temperature, topp, seeds = ([v] * len(prompts) if np.isscalar(v) else list(v) for v in sampler)
             per_live = tuple([v[r] for r in live] for v in (temperature, topp, seeds))
-        if prefix:
-            if transformer.batch_prefix_get() != prefix:
-                transformer.batch_prefix_set(prefix)
-            got, stats = transformer.generate_many_prefix(live_prompts, live_new, sorted(stop) if stop_on_device else (), per_live)
-        elif stop_on_device and stop:
-            got, stats = transformer.generate_many_stop(live_prompts, live_new, sorted(stop), per_live)
-        elif dense_min > 0:
-            got, stats, _ = transformer.generate_many_dense(live_prompts, live_new, per_live, dense_min)
-        elif sampler is None:
-            got, stats = transformer.generate_many_greedy(live_prompts, live_new)
-        else:
-            got, stats = transformer.generate_many_sampled(live_prompts, live_new, *per_live)
-        for r, toks in zip(live, got):
-            k = next((i for i, t in enumerate(toks) if t in stop), None)
+        seq_start = None
+        if stop_seq is not None:
+            # the engine sees the requests the context leaves room for, and one start state for each of them
+            seq_start = list(stop_seq[1]) if len(stop_seq[1]) == 1 else [stop_seq[1][r] for r in live]
+        seq_on_device = stop_seq is not None and stop_on_device
+        if seq_on_device:
+            seq_before = transformer.get_stop_sequences()
+            transformer.set_stop_sequences(stop_seq[0], seq_start)
+        try:
+            if prefix:
+                if transformer.batch_prefix_get() != prefix:
+                    transformer.batch_prefix_set(prefix)
+                got, stats = transformer.generate_many_prefix(live_prompts, live_new, sorted(stop) if stop_on_device else (), per_live)
+            elif stop_on_device and (stop or seq_on_device):
+                got, stats = transformer.generate_many_stop(live_prompts, live_new, sorted(stop), per_live)
+            elif dense_min > 0:
+                got, stats, _ = transformer.generate_many_dense(live_prompts, live_new, per_live, dense_min)
+            elif sampler is None:
+                got, stats = transformer.generate_many_greedy(live_prompts, live_new)
+            else:
+                got, stats = transformer.generate_many_sampled(live_prompts, live_new, *per_live)
+        finally:
+            if seq_on_device:
+                transformer.set_stop_sequences(*seq_before)
+        for i, (r, toks) in enumerate(zip(live, got)):
+            k = next((j for j, t in enumerate(toks) if t in stop), None)
+            if stop_seq is not None:
+                m = first_match(stop_seq[0], seq_start[0 if len(seq_start) == 1 else i], toks)
+                k = m if k is None else (k if m is None else min(k, m))
             rows[r] = toks if k is None else toks[:k + 1]
         if read_logprobs:
             for r, rec in zip(live, transformer.read_gen_logprobs()):

@@ -198,7 +198,9 @@ class SparseAutomaton:
     state behind it); state s lists tokens[offsets[s] .. offsets[s + 1]), strictly ascending, with targets beside them (-1 or a
     state).  next[s][v] is the target where v is listed in s, else default[s].  Up to GUIDE_SPARSE_MAX_STATES states."""
 
-    def __init__(self, default, offsets, tokens, targets, start: int = 0, vocab_size: Optional[int] = None):
+    def __init__(self, default, offsets, tokens, targets, start: int = 0, vocab_size: Optional[int] = None, dead_ok: bool = False):
+        """dead_ok: a state that allows no token is legal -- the stop automata of stops.py, where -1 reads "the sequence is complete"
+        and a state may say so of every token"""
         for name, a in (("default", default), ("offsets", offsets), ("tokens", tokens), ("targets", targets)):
             a = np.asarray(a)
             if a.ndim != 1 or (a.size and not np.issubdtype(a.dtype, np.integer)):
@@ -228,8 +230,9 @@ class SparseAutomaton:
         listed = np.diff(offsets)
         allowed = np.bincount(owner[targets >= 0], minlength=S) if E else np.zeros(S, dtype=np.int64)
         dead = np.flatnonzero((allowed == 0) & ((default < 0) | (listed == V)))
-        if dead.size:
+        if dead.size and not dead_ok:
             raise ValueError(f"state {int(dead[0])} allows no token")
+        self.dead_ok = bool(dead_ok)
         if isinstance(start, bool) or not isinstance(start, (int, np.integer)):
             raise TypeError(f"start must be an integer, got {start!r}")
         if not 0 <= start < S:
@@ -804,7 +807,7 @@ def merge_guides(guide, n_requests: int):
         return SparseAutomaton(np.concatenate([shift(t.default, b) for t, b in zip(tables, bases)]),
                                np.concatenate([t.offsets[:-1] + e for t, e in zip(tables, edges)] + [edges[-1:]]),
                                np.concatenate([t.tokens for t in tables]), np.concatenate([shift(t.targets, b) for t, b in zip(tables, bases)]),
-                               0, tables[0].vocab_size), start
+                               0, tables[0].vocab_size, dead_ok=any(t.dead_ok for t in tables)), start
     if at > GUIDE_MAX_STATES:
         raise ValueError(f"guide: {at} states in all, at most {GUIDE_MAX_STATES}")
     bases = np.cumsum([0] + [t.n_states for t in tables[:-1]])

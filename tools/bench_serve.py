@@ -49,6 +49,17 @@ with the prefix resident; the rows must be equal.  Also: q3_batch_prefix_set on 
 the 31 other slots through q3_batch_copy_rows (one launch of k_kv_rows_bcast, the loop's broadcast but for one destination) with
 its achieved bytes per second (read once + written 31 times), next to a loop of 2 * layers * 31 hipMemcpyAsync calls that move the
 same bytes between buffers of the same layout.  Appends a section to <out>/serve_cols.md and writes <out>/serve_cols_prefix.json.
+
+    python tools/bench_serve.py --stop-seq [--ab PARENT_TREE] [--models qwen3-0.6b,qwen3-8b]
+
+Stop sequences in the device loop (section 2t), on the requests and the stop set of --stop.  Three comparisons, the calls taken by
+turns, best of 3 rounds behind a warm-up round: (a) q3_generate_many_stop with no automaton -- the path of the commit before; with
+--ab PARENT_TREE (a checkout of that commit with its library built) the same call also runs in child processes of that tree, ours
+and theirs by turns, twice each, which gives the run-to-run spread; (b) the same call under an automaton of four strings lifted
+over the full vocabulary that never matches: (b) - (a) over the passes is what k_cols_sched_seq costs over k_cols_sched; (c) an
+automaton of token sequences that ends the requests where the stop set ends them, with n_stop == 0, against the loop at the cap plus
+the host cut.  Also: the automaton's states, edges and bytes, and the host time of stop_automaton_from_strings.  Writes
+<out>/stop_seq.json and <out>/stop_seq.md.
 """
 import argparse
 import json
@@ -58,7 +69,9 @@ import sys
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "qwen3-rs_amd"))
+# (--tree, the worker of --stop-seq --ab: the package and the library of another checkout run the call)
+_TREE = sys.argv[sys.argv.index("--tree") + 1] if "--tree" in sys.argv[:-1] else ROOT
+sys.path.insert(0, os.path.join(os.path.abspath(_TREE), "qwen3-rs_amd"))
 
 AB_MARK = "## Batch-32 decode A/B"
 DENSE_MARK = "## Dense blocks over the slots"
@@ -315,6 +328,141 @@ def worker_stop(name, ctx, ckpt_dir, seed):
            "at_cap": {"passes": st_a.passes, "seconds": dt_a}, "stop": {"passes": st_b.passes, "seconds": dt_b},
            "n_emit": {"passes": st_c.passes, "seconds": dt_c}, "per_pass_us": 1e6 * (dt_b - dt_c) / max(1, st_b.passes)}
     print("RESULT " + json.dumps(res))
+
+
+def synthetic_token_bytes(vocab_size):
+    """a stand-in vocabulary for the lift: token v spells its number and a comma"""
+    return [b"%d," % v for v in range(vocab_size)]
+
+
+NEVER = ["12,34,x", "7,7,7,x", "99,100,x", "5,x"]       # they share bytes with thousands of tokens and end in a byte no token has
+
+
+def worker_stop_seq(name, ctx, ckpt_dir, seed, parent_only):
+    import numpy as np
+    import qwen3_rs_amd as q3
+    ck = q3.checkpoint
+    shape = ck.SHAPES[name]
+    path = os.path.join(ckpt_dir, f"{name}-seed{seed}.q3bin")
+    ck.ensure_synthetic_checkpoint(path, shape, seed=seed)
+    rng = np.random.default_rng(7)
+    n_req, ms, cap = 64, 32, 256
+    plen = [int(v) for v in rng.integers(1, 200, 8)]
+    distinct = [ck.iter_prompt_tokens(shape, seed + 50 + r, n) for r, n in enumerate(plen)]
+    prompts = [distinct[r % 8] for r in range(n_req)]
+    nnew = [cap] * n_req
+    res = {"model": name, "ctx": ctx, "requests": n_req, "slots": ms, "cap": cap}
+    with q3.TransformerBuilder(path).with_ctx_length(ctx).build() as t:
+        t.batch_init(ms, ctx)
+        rows, _ = t.generate_many_greedy(prompts, nnew)
+        stop = pick_stop_set(rows)
+        emit = n_emit_of(rows, set(stop))
+        want = [r[:e] for r, e in zip(rows, emit)]
+        calls = {"a": lambda: t.generate_many_stop(prompts, nnew, stop)}
+        if not parent_only:
+            from qwen3_rs_amd.stops import first_match
+            t0 = time.perf_counter()
+            never = q3.stop_automaton_from_strings(NEVER, synthetic_token_bytes(shape.vocab_size))
+            res["lift_seconds"] = time.perf_counter() - t0
+            res["never"] = {"strings": NEVER, "vocab": shape.vocab_size, "states": never.n_states, "edges": never.n_edges, "bytes": 4 * never.n_states + 4 * (never.n_states + 1) + 8 * never.n_edges}
+            # the sequences that end the requests where the stop set ends them: the two tokens up to each row's stop token
+            seqs = sorted({tuple(r[e - 2:e]) for r, e in zip(rows, emit) if 2 <= e < len(r)})
+            ends = q3.stop_automaton(seqs, shape.vocab_size)
+            semit = [len(r) if (m := first_match(ends, ends.start, r)) is None else m + 1 for r in rows]
+            swant = [r[:e] for r, e in zip(rows, semit)]
+            res["ends"] = {"sequences": len(seqs), "states": ends.n_states, "edges": ends.n_edges, "sum_n_emit": sum(semit)}
+
+            def under(automaton, stop_tokens):
+                t.set_stop_sequences(automaton)
+                try:
+                    return t.generate_many_stop(prompts, nnew, stop_tokens)
+                finally:
+                    t.set_stop_sequences(None)
+
+            def host_cut():
+                got, st = t.generate_many_greedy(prompts, nnew)
+                return [r if (m := first_match(ends, ends.start, r)) is None else r[:m + 1] for r in got], st   # the cut is part of what is timed
+            calls.update({"b": lambda: under(never, stop), "c_device": lambda: under(ends, []), "c_host": host_cut})
+        best, out = {}, {}
+        for rnd in range(4):                                               # round 0 warms up: plans of every width the schedules use
+            for k, call in calls.items():
+                t0 = time.perf_counter()
+                out[k] = call()
+                dt = time.perf_counter() - t0
+                if rnd:
+                    best[k] = min(best.get(k, dt), dt)
+    res.update({"stop_set": stop, "sum_n_new": sum(nnew), "sum_n_emit": sum(emit),
+                "runs": {k: {"seconds": best[k], "passes": out[k][1].passes} for k in calls},
+                "rows_equal": all(out[k][0] == (swant if k.startswith("c_") else want) for k in calls)})
+    if not parent_only:
+        res["per_pass_us"] = 1e6 * (best["b"] - best["a"]) / max(1, out["a"][1].passes)
+        res["passes_equal"] = out["a"][1].passes == out["b"][1].passes
+    print("RESULT " + json.dumps(res))
+
+
+def main_stop_seq(a):
+    results, failed = [], False
+    for name in a.models.split(","):
+        def child(tree, parent_only):
+            cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--worker", name, "--ctx", str(a.ctx), "--ckpt-dir", a.ckpt_dir, "--seed", str(a.seed), "--stop-seq"]
+            if parent_only:
+                cmd += ["--tree", tree]
+            p = subprocess.run(cmd, capture_output=True, text=True)
+            sys.stderr.write(p.stderr[-2000:])
+            if p.returncode != 0:
+                print(f"[bench_serve] {name}: exit status {p.returncode}; stopping here", file=sys.stderr)
+                return None
+            return json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")][-1][7:])
+        r = child(ROOT, False)
+        if r is None:
+            failed = True
+            break
+        if a.ab:                                                           # theirs, ours, theirs: a fault in one child starts no other
+            r["ab"] = {"ours": [r["runs"]["a"]["seconds"]], "parent": []}
+            for tree, key in ((a.ab, "parent"), (ROOT, "ours"), (a.ab, "parent")):
+                x = child(tree, True)
+                if x is None:
+                    failed = True
+                    break
+                r["ab"][key].append(x["runs"]["a"]["seconds"])
+                r["rows_equal"] = r["rows_equal"] and x["rows_equal"] and x["runs"]["a"]["passes"] == r["runs"]["a"]["passes"]
+            if failed:
+                break
+        results.append(r)
+    os.makedirs(a.out, exist_ok=True)
+    with open(os.path.join(a.out, "stop_seq.json"), "w") as f:
+        json.dump(results, f, indent=1)
+    lines = ["# Stop sequences in the device loop", "",
+             "Written by `tools/bench_serve.py --stop-seq` (synthetic full-size checkpoints, one MI355X, context %d per slot): the requests and" % a.ctx,
+             "the stop set of `--stop` -- 64 requests through 32 slots, a cap of 256 new tokens.  Wall time per call, the calls taken by turns,",
+             "best of 3 rounds behind a warm-up round.", "",
+             "(a) `q3_generate_many_stop` with no automaton: the path of the commit before.  (b) the same call under an automaton of four strings",
+             "lifted over the full vocabulary that never matches; us per pass = ((b) - (a)) / passes: what `k_cols_sched_seq` costs over `k_cols_sched`.",
+             "(c) an automaton of token sequences that ends the requests, n_stop == 0, on the device against the loop at the cap plus the host cut.",
+             "Every timed call of (b) and (c) sets the automaton in front and clears it behind, so it also uploads the table anew: us per pass is an",
+             "upper bound.  `profiles/serve_cols.md` gives 33 us per pass for the scheduler launch and the synchronisation of one pass.", "",
+             "| model | run | passes | seconds | us per pass over (a) | rows equal |", "|---|---|---|---|---|---|"]
+    label = {"a": "(a) no automaton", "b": "(b) never matches", "c_device": "(c) ends requests, device", "c_host": "(c) at the cap + host cut"}
+    for r in results:
+        for k in ("a", "b", "c_device", "c_host"):
+            lines.append(f"| {r['model']} | {label[k]} | {r['runs'][k]['passes']} | {r['runs'][k]['seconds']:.4f} | "
+                         f"{r['per_pass_us']:.1f} | {r['rows_equal']} |" if k == "b" else
+                         f"| {r['model']} | {label[k]} | {r['runs'][k]['passes']} | {r['runs'][k]['seconds']:.4f} | | |")
+    lines += ["", "The automaton of (b) and its lift on the host (`stop_automaton_from_strings` over a vocabulary whose token v spells `v,`):", "",
+              "| model | vocabulary | strings | states | edges | table bytes | lift seconds |", "|---|---|---|---|---|---|---|"]
+    for r in results:
+        n = r["never"]
+        lines.append(f"| {r['model']} | {n.get('vocab', '')} | {' '.join(repr(s) for s in n['strings'])} | {n['states']} | {n['edges']} | {n['bytes']} | {r['lift_seconds']:.2f} |")
+    if a.ab:
+        lines += ["", "(a) in processes of their own, this tree and a checkout of the commit before by turns (seconds, best of 3 each):", "",
+                  "| model | this tree | the commit before |", "|---|---|---|"]
+        for r in results:
+            lines.append(f"| {r['model']} | {' '.join(f'{x:.4f}' for x in r['ab']['ours'])} | {' '.join(f'{x:.4f}' for x in r['ab']['parent'])} |")
+    if not results:
+        lines.append("not taken")
+    with open(os.path.join(a.out, "stop_seq.md"), "w") as f:
+        f.write("\n".join(lines) + "\n")
+    return 0 if not failed and results and all(r["rows_equal"] and r["passes_equal"] for r in results) else 1
 
 
 def main_stop(a):
@@ -582,6 +730,9 @@ def main():
     ap.add_argument("--topp", type=float, default=0.95)
     ap.add_argument("--dense-min", type=int, help="long prompts through dense blocks against the column loop (appends to serve_cols.md; context 2,304)")
     ap.add_argument("--stop", action="store_true", help="stop tokens in the device loop against the loop at the cap (appends to serve_cols.md)")
+    ap.add_argument("--stop-seq", action="store_true", help="stop sequences in the device loop: no automaton, one that never matches, one that ends requests (writes stop_seq.md)")
+    ap.add_argument("--ab", help="with --stop-seq: a checkout of the commit before, its library built; (a) also runs there")
+    ap.add_argument("--tree", help=argparse.SUPPRESS)                  # worker of --ab: the tree whose package and library run (a)
     ap.add_argument("--prefix", type=int, help="requests that share a prefix of this many tokens against the loops on the full prompts (appends to serve_cols.md)")
     a = ap.parse_args()
     if a.prefix is not None:
@@ -590,6 +741,11 @@ def main():
             worker_prefix(a.worker, a.ctx, a.ckpt_dir, a.seed, a.prefix)
             return 0
         return main_prefix(a)
+    if a.stop_seq:
+        if a.worker:
+            worker_stop_seq(a.worker, a.ctx, a.ckpt_dir, a.seed, a.tree is not None)
+            return 0
+        return main_stop_seq(a)
     if a.stop:
         if a.worker:
             worker_stop(a.worker, a.ctx, a.ckpt_dir, a.seed)
