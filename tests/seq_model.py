@@ -12,6 +12,10 @@ must return, and checks an engine op by op.
                                 gen_logprobs, penalties, the logit-bias table), q3_gen_logprobs_read and q3_score_top_many -- among the
                                 kinds of the pair matrix; Tables derives every table from Reference alone; run() reads the records
                                 behind every loop op and the four getters behind every op
+    make_guide_sequence(seed)   the guide dimension: GUIDE_KINDS -- the dense guide of section 2r, the sparse guide of 2s, the stop
+                                automaton of 2t, their refusals -- among the kinds above; Tables derives every automaton from Reference
+                                alone; run() holds tokens, n_out, the -1 fill, stats and records to the reference under them and reads
+                                the three getters behind every op
 
 Shape: small-hd128 (dim 512, 8 heads over 4 kv heads, head_dim 128, group 64, vocabulary 2,048) with 576 positions declared instead
 of 256: the score rows of the dense blocks (att_pf) are sized to the context end rounded up to 256, so on 256 positions they are
@@ -190,14 +194,18 @@ def _pass_sizes(table):
     return [sizes[p] for p in sorted(sizes)]
 
 
-def many_plan(lens, n_new, streams, dense_min=0, rows=None, stop=()):
+def many_plan(lens, n_new, streams, dense_min=0, rows=None, stop=(), emit=None):
     """What a generate_many call does with requests of lens[r] prompt tokens: dict(table, stats, n_out, occupants = per slot the
     requests it held in order, passes = live columns per column pass, blocks = [(width, wide, run lengths)] of the dense requests
-    in order)."""
+    in order).  emit: the n_emit of the stop loop under a stop automaton (section 2t) -- its passes and stats are those of
+    q3_cols_schedule(prompt_len, n_emit)."""
     q3 = _q3()
     dense = [bool(dense_min) and n - 1 >= dense_min for n in lens]
     seen = [1 if d else n for n, d in zip(lens, dense)]
-    if stop:
+    if emit is not None:
+        table, stats = q3.cols_schedule(seen, list(emit), streams)
+        n_out = list(emit)
+    elif stop:
         table, n_out, stats = q3.cols_schedule_stop(seen, list(n_new), streams, rows, list(stop))
     else:
         table, stats = q3.cols_schedule(seen, list(n_new), streams)
@@ -274,8 +282,10 @@ def score_chunks(op, streams):
 def form_of(draw, st):
     """(draw, topk, genlp, pen) of the column plans a loop op runs under the settings st: the plan key's four axes.  topk is on a
     sampled plan alone (plan_get clears it on a greedy one); genlp 0 off, 1 records, 2 records + top; pen 0 off, 1 penalties, 2 the
-    adjusted form, which a table selects with or without penalties"""
-    return (bool(draw), bool(draw and st["top_k"]), 0 if st["genlp"] < 0 else 1 if st["genlp"] == 0 else 2, 2 if st["table"] is not None else 1 if any(st["pen"]) else 0)
+    adjusted form, which a table selects with or without penalties, 3 the masked form of a dense guide and 4 that of a sparse one,
+    which a guide selects whatever the table and the penalties (st["gform"], where the walk tracks it)"""
+    pen = {"dense": 3, "sparse": 4}.get(st.get("gform"), 2 if st["table"] is not None else 1 if any(st["pen"]) else 0)
+    return (bool(draw), bool(draw and st["top_k"]), 0 if st["genlp"] < 0 else 1 if st["genlp"] == 0 else 2, pen)
 
 
 def needs(op, streams, sampling, prefix_len, rows=None, stop=(), st=None, table=None):
@@ -1139,6 +1149,331 @@ def make_settings_sequence(seed):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
+# the guide dimension: the dense guide of section 2r, the sparse guide of 2s and the stop automaton of 2t among the calls above.
+# These kinds are no part of KINDS or SETTING_KINDS: the twelve sequences of the pair matrix and the six settings sequences stay
+# what they were (tests/test_call_sequences_host.py holds the digests of all eighteen)
+# ---------------------------------------------------------------------------------------------------------------------------------
+GUIDE_KINDS = ("set_guide", "set_guide_sparse", "set_stop_seq", "refused_set_guide", "refused_set_guide_sparse", "refused_set_stop_seq",
+               "refused_guide_starts")
+GUIDE_SETTERS = GUIDE_KINDS[:3]
+GUIDE_FORMS = ("off", "all", "trie", "cycle", "per", "big")
+SPARSE_FORMS = ("off", "all", "trie", "cycle", "per", "dflt", "half", "big")
+STOP_FORMS = ("off", "hit1", "hit2", "hit3", "overlap", "never", "per", "any", "big")
+# one refused form per reason group of the header: a state that allows no token, a start outside [-1, n_states), another vocabulary
+# (for q3_guide_set_sparse, whose vocabulary the binding states itself: a token outside it), an entry, a dflt or an edge outside the
+# states, a token that does not ascend, row_off[n_states] != n_edges
+GUIDE_REFUSALS = {"refused_set_guide": ("dead", "start", "vocab", "entry"), "refused_set_guide_sparse": ("dead", "ascend", "row_off", "start", "vocab"),
+                  "refused_set_stop_seq": ("ascend", "row_off", "start", "vocab", "dflt")}
+GUIDE_BUFFERS = ("guide_next", "guide_start", "guide_sp_dflt", "guide_sp_off", "guide_sp_edges", "guide_sp_start", "stop_seq_dflt", "stop_seq_off",
+                 "stop_seq_edges", "stop_seq_start")
+GUIDE_SEEDS = (41, 42, 43, 44, 45, 46)
+GUIDE_EDGE_SEED = GUIDE_SEEDS[1]
+G_OFF = dict(OFF, guide=("off", "off"), stop="off")         # guide: (which of the two forms, the automaton's form)
+STOP_VARIANTS = VARIANTS[4:]                                # the two loops with a device scheduler: they honour the stop automaton
+
+
+def guide_states():
+    """The states every loop variant has to run under: every guide form and every stop form alone (the forms "big" run where the
+    buffers grow), a guide with a stop automaton, a guide with each of the four earlier settings at one value"""
+    alone = ([dict(G_OFF, guide=("dense", f)) for f in GUIDE_FORMS[1:-1]] + [dict(G_OFF, guide=("sparse", f)) for f in SPARSE_FORMS[1:-1]]
+             + [dict(G_OFF, stop=f) for f in STOP_FORMS[1:-1]])
+    both = [dict(G_OFF, guide=("dense", "cycle"), stop="hit2"), dict(G_OFF, guide=("sparse", "trie"), stop="hit1")]
+    other = [dict(G_OFF, guide=("dense", "cycle"), top_k=5), dict(G_OFF, guide=("sparse", "cycle"), genlp=3), dict(G_OFF, guide=("dense", "trie"), pen=1),
+             dict(G_OFF, guide=("sparse", "half"), bias="per")]
+    return alone + both + other
+
+
+def guide_form_states():
+    """one state per column-plan form under a guide: (needs a sampled loop, state) -- top_k on or off, the three genlp forms, the two
+    guide forms of the penalty axis: 18"""
+    return [(draw, dict(G_OFF, top_k=5 if topk else 0, genlp=lp, guide=(kind, "cycle")))
+            for draw, topk in ((False, False), (True, False), (True, True)) for lp in (-1, 0, 3) for kind in ("dense", "sparse")]
+
+
+class _GGen(_SGen):
+    """_SGen with the guide and the stop automaton tracked as two more settings, and the emitters of GUIDE_KINDS"""
+
+    def __init__(self, seed, avoid=frozenset()):
+        super().__init__(seed, avoid)
+        self.state = dict(G_OFF)
+        self.n_of = dict(guide=0, stop=0)    # the start states of a per-request form in force
+
+    def st(self):
+        s = super().st()
+        s["gform"] = None if self.state["guide"][0] == "off" else self.state["guide"][0]
+        return s
+
+    def need(self):
+        """the number of requests a loop op must have: the lists of a per-request table, the start states of a per-request automaton"""
+        n = {v for v in (self.n_lists, self.n_of["guide"], self.n_of["stop"]) if v > 1}
+        assert len(n) <= 1, n
+        return n.pop() if n else 0
+
+    def reqs(self, n=None, lo=2, hi=4):
+        return self.rng.sample(LONG, self.need() or n or self.rng.randint(lo, hi))
+
+    def reqs_for(self, variant, new):
+        """one request whose column plans all exist in the epoch (new False) or of which one does not (new True): its prompt alone
+        decides the widths, so that a form keeps widths to build through several visits"""
+        order = list(LONG)
+        self.rng.shuffle(order)
+        for i in ([] if self.need() else order):
+            forms = {form_of(variant[1], self.st()) + (width_index(n),) for n in many_plan([CAT[i][1]], [CAT[i][2]], self.streams)["passes"]}
+            if bool(forms - self.built) == new:
+                return [i]
+        return super().reqs_for(variant, new)
+
+    def loop(self, variant, reqs):
+        op = super().loop(variant, reqs)
+        if op["op"] in ("generate_many_stop", "generate_many_prefix"):          # by the request list, as the host tests count them
+            rows, stop = ([[0] * CAT[i][2] for i in op["reqs"]], (1,)) if op["stop_at"] else (None, ())
+            self.built |= needs(op, self.streams, self.bs_on, 0, rows, stop, st=self.st())["forms"]
+        return op
+
+    def legal(self, kind):
+        if kind == "refused_guide_starts":
+            return max(self.n_of.values()) > 1
+        return super().legal(kind)
+
+    def emit(self, kind, **force):
+        if kind not in GUIDE_KINDS:
+            return super().emit(kind, **force)
+        r = self.rng
+        op = {"op": kind}
+        if kind in GUIDE_SETTERS:
+            form = force["form"]
+            op.update(form=form, seed=r.getrandbits(24))
+            per = form in ("per", "big")
+            if per:
+                op["n"] = force["n"]
+            for k in ("size", "early", "ns"):
+                if force.get(k):
+                    op[k] = force[k]
+            if kind == "set_stop_seq":
+                self.state["stop"], self.n_of["stop"] = form, force["n"] if per else 0
+            else:
+                self.state["guide"] = ("off", "off") if form == "off" else ("dense" if kind == "set_guide" else "sparse", form)
+                self.n_of["guide"] = force["n"] if per else 0
+        elif kind == "refused_guide_starts":
+            which = "guide" if self.n_of["guide"] > 1 else "stop"
+            op.update(kind="generate_many_stop", reqs=r.sample(LONG, self.n_of[which] + 1), sampled=self.bs_on, stop_at=[],
+                      of=self.state["guide"][0] if which == "guide" else "stop")
+        else:
+            op.update(bad=force.get("bad") or r.choice(GUIDE_REFUSALS[kind]), at=r.randrange(100))
+        self.ops.append(op)
+        return op
+
+    def set(self, k, v, n=None, **force):
+        if k == "guide":
+            if v[0] == "off":
+                return self.emit("set_guide" if self.state["guide"][0] != "sparse" else "set_guide_sparse", form="off")
+            return self.emit("set_guide" if v[0] == "dense" else "set_guide_sparse", form=v[1], n=n, **force)
+        if k == "stop":
+            return self.emit("set_stop_seq", form=v, n=n, **force)
+        return super().set(k, v, n, **force)
+
+    def goto(self, state, n=None):
+        per = dict(bias=lambda v: v == "per", guide=lambda v: v[1] in ("per", "big"), stop=lambda v: v in ("per", "big"))
+        have = dict(bias=self.n_lists, guide=self.n_of["guide"], stop=self.n_of["stop"])
+        todo = [k for k in state if state[k] != self.state[k] or (k in per and per[k](state[k]) and n != have[k])]
+        self.rng.shuffle(todo)
+        for k in todo:
+            self.set(k, state[k], n)
+
+    def owed(self, pair):
+        seen = pairs_of(self.ops) | self.avoid
+        kinds = [k for k in GUIDE_KINDS if pair(k) not in seen and self.legal(k)]
+        return self.rng.choice(kinds) if kinds else None
+
+    def one(self, kind):
+        """one op of a guide kind that leaves the forms in force: a setter sets the form in force once more, with another automaton"""
+        if kind == "set_stop_seq":
+            return self.emit(kind, form=self.state["stop"], n=self.n_of["stop"])
+        if kind in GUIDE_SETTERS:
+            kinds = dict(dense="set_guide", sparse="set_guide_sparse")
+            if kinds.get(self.state["guide"][0], kind) != kind:                  # the other form is in force: it stays in force
+                return self.emit("refused_" + kind)
+            return self.emit(kind, form=self.state["guide"][1], n=self.n_of["guide"])
+        if kind in GUIDE_KINDS:
+            return self.emit(kind)
+        return super().one(kind)
+
+
+def _guide_sequence(seed, avoid=frozenset()):
+    """Three epochs in the shape of a settings sequence.  Epoch 0 is the one whose arrays grow behind cached plans (small - medium -
+    small - large - small: the dense table, the sparse arrays, the stop automaton and their start states), then a toggle stretch:
+    guide off -> dense -> dense (another table, the same states) -> sparse -> dense -> off and stop automaton off -> on -> another ->
+    off under kept plans, two loop ops behind every switch.  Epochs 1 and 2 start the batched state over with other slot counts, the
+    last one with more, under a guide and a stop automaton.  The loop variants run through the states of guide_states() and
+    guide_form_states() that fall to this seed; a stretch under a guide and a stop automaton goes through the quiet kinds that fall
+    to this seed; one op runs under a table that bans a state's only tokens (the else branch of the state step), one under
+    min_tokens with a sequence that completes in front of it."""
+    g = _GGen(seed, avoid)
+    r = g.rng
+    at = GUIDE_SEEDS.index(seed) if seed in GUIDE_SEEDS else seed % 6
+    n_seeds = len(GUIDE_SEEDS)
+    cells = [(v, s) for si, s in enumerate(guide_states()) for vi, v in enumerate(VARIANTS) if (si + vi) % n_seeds == at]
+    for fi, (draw, state) in enumerate(guide_form_states()):    # every form, on two loop kinds: the second finds the first one's plans
+        if fi % n_seeds == at:
+            cells += [(v, state) for v in VARIANTS if v[1] == draw and v[0] != "generate_many_prefix"][:2]
+    r.shuffle(cells)
+    cells.sort(key=lambda c: sorted((k, str(v)) for k, v in c[1].items()))
+    b = r.choice((2, 3))
+    a = r.choice([v for v in (2, 3, 4) if v != b])
+    c = r.choice((6, 8))
+    kind_of = lambda k: "dense" if k % 2 == at % 2 else "sparse"
+    both = lambda k: dict(G_OFF, guide=(kind_of(k), "cycle"), stop="hit2")
+
+    def cut(k):
+        while 0 < k < len(cells) and cells[k - 1][1] == cells[k][1]:
+            k += 1
+        return k
+
+    def run(cells, fill=0.25):
+        reqs = before = None
+        for variant, state in cells:
+            per = state["bias"] == "per" or state["guide"][1] == "per" or state["stop"] == "per"
+            n = (len(reqs) if state == before else r.randint(3, 4)) if per else None
+            if state["bias"] != "off" and g.state["bias"] != "off" and (g.users >= 3 or state["bias"] != g.state["bias"]):
+                g.emit("set_logit_bias", form="off")
+            g.goto(state, n)
+            x = g.owed(lambda k: (k, variant[0]))
+            if x:
+                g.one(x)
+            reqs = reqs if state == before and (not g.need() or len(reqs) == g.need()) else g.reqs()
+            before = state
+            g.loop(variant, reqs)
+            x = g.owed(lambda k: (variant[0], k))
+            if x:
+                g.one(x)
+            elif r.random() < fill:
+                g.filler(BETWEEN)
+
+    def grow(k, reqs):
+        """the medium and the large phase: the dense table "big" with one start per request, then the sparse arrays and the stop
+        automaton "big"; a call with one request more is refused under each of the three"""
+        n = len(reqs)
+        va, vb, vc = VARIANTS[(2 * at + k) % 8], VARIANTS[(2 * at + k + 3) % 8], STOP_VARIANTS[(2 * at + k) % 4]
+        g.goto(dict(G_OFF))
+        g.emit("set_guide", form="big", size=k + 1, n=n)
+        g.loop(va, reqs)
+        if k == 0:
+            g.emit("refused_guide_starts")
+        if vb not in STOP_VARIANTS:                             # a loop that does not read it runs beside the large stop automaton
+            g.emit("set_stop_seq", form="big", size=k + 1, n=n)
+        g.emit("set_guide_sparse", form="big", size=k + 1, n=n)
+        g.loop(vb, reqs)
+        if k == 1:
+            g.emit("refused_guide_starts")
+        g.emit("set_guide_sparse", form="off")
+        if vb in STOP_VARIANTS:
+            g.emit("set_stop_seq", form="big", size=k + 1, n=n)
+        g.emit("refused_guide_starts")
+        g.loop(vc, reqs)                                        # the stop automaton alone, on a loop that honours it: its arrays grow here
+        g.emit("set_stop_seq", form="off")
+        return va, vb, vc
+
+    def small_again(va, vb, vc):
+        """the same kinds, small"""
+        g.goto(dict(G_OFF))
+        g.emit("set_guide", form="cycle")
+        g.loop(va, g.reqs())
+        g.emit("set_guide_sparse", form="dflt")
+        g.loop(vb, g.reqs())
+        g.emit("set_stop_seq", form="hit1")
+        g.loop(vc, g.reqs())
+        g.emit("set_guide_sparse", form="off")
+        g.emit("set_stop_seq", form="off")
+
+    # epoch 0: the growth epoch
+    g.emit("batch_init", streams=b, ctx=0)
+    g.growth = True
+    for _ in range(2):
+        g.emit("batch_prefill_slots", wide=True)               # a dense plan, and its second use
+    third, two = cut(len(cells) // 3), cut(2 * len(cells) // 3)
+    firsts = [(VARIANTS[(2 * at + k) % 8], VARIANTS[(2 * at + k + 3) % 8], STOP_VARIANTS[(2 * at + k) % 4]) for k in (0, 1)]
+    small_again(*firsts[0])
+    small_again(*firsts[1])
+    run(cells[:third])
+    grow(0, list(LONG[:7]))
+    small_again(*firsts[0])
+    grow(1, list(LONG[:12]))
+    small_again(*firsts[1])
+    small_again(*firsts[0])
+    g.growth = False
+    for kind, vals in GUIDE_REFUSALS.items():                   # every refusal value falls to a seed
+        g.emit(kind, bad=vals[at % len(vals)])
+    # the toggle stretch of the guide, under the kept plans of all three forms: behind every switch a loop op on kept widths and one
+    # that builds a width
+    tv = r.choice(VARIANTS[:2])
+    g.goto(dict(G_OFF, genlp=0))                                # (with records: forms of which the epoch has built few widths)
+    g.loop(tv, [LONG[0]])
+    for kind in ("set_guide", "set_guide_sparse"):
+        g.emit(kind, form="cycle", ns=4)
+        g.loop(tv, [LONG[0]])
+    g.emit("set_guide_sparse", form="off")
+    for kind, form in (("set_guide", "cycle"), ("set_guide", "cycle"), ("set_guide_sparse", "cycle"), ("set_guide", "cycle"), ("set_guide", "off")):
+        g.emit(kind, form=form, ns=4 if form == "cycle" else None)
+        g.loop(tv, g.reqs_for(tv, False))
+        g.loop(tv, g.reqs_for(tv, True))
+    # ... and of the stop automaton, on a loop that honours it
+    sv = r.choice(STOP_VARIANTS)
+    g.loop(sv, [LONG[0]])
+    for form in ("hit2", "overlap", "off"):                     # (overlap: every seed ends a request over a fall-back edge)
+        g.emit("set_stop_seq", form=form)
+        g.loop(sv, g.reqs_for(sv, False))
+        g.loop(sv, g.reqs_for(sv, True))
+    # a guide and a stop automaton across q3_batch_init to another slot count
+    g.goto(both(0))
+    g.emit("batch_init", streams=a, ctx=256)
+    g.loop(r.choice(STOP_VARIANTS), g.reqs())
+    # epoch 1: the second third of the cells
+    run(cells[third:two])
+    # the else branch of the state step: a table that bans the three tokens the cycle's small state allows, under greedy
+    g.goto(dict(G_OFF, guide=(kind_of(1), "cycle")))
+    g.emit("set_logit_bias", form="kill")
+    g.loop(r.choice((VARIANTS[0], VARIANTS[4])), g.reqs())
+    g.emit("set_logit_bias", form="off")
+    # min_tokens does not delay a sequence match: a sequence that completes with the first token, under a list with until = 4
+    g.goto(dict(G_OFF))
+    g.emit("set_stop_seq", form="hit1", early=True)
+    g.emit("set_logit_bias", form="min")
+    g.loop(r.choice(STOP_VARIANTS), g.reqs())
+    g.emit("set_logit_bias", form="off")
+    # a guide and a stop automaton, across the state changers and the quiet kinds that fall to this seed, a loop op behind them
+    g.goto(both(1))
+    quiet = [k for i, k in enumerate(QUIET) if i % n_seeds == at] + ["set_sampler", "set_batch_sampler_on", "batch_step_cols_draw",
+                                                                      "set_batch_sampler_off", "batch_step_cols_draw", "batch_reset_kv"]
+    for k in quiet:
+        g.enable(k)
+        if g.legal(k) and (g.ops[-1]["op"], k) not in ILLEGAL:
+            g.emit(k)
+    g.loop(r.choice(STOP_VARIANTS), g.reqs())
+    # epoch 2: more slots, under both
+    g.emit("batch_init", streams=c, ctx=r.choice((192, 256)))
+    g.loop(r.choice(STOP_VARIANTS), g.reqs())
+    run(cells[two:])
+    g.goto(dict(G_OFF))
+    g.loop(r.choice(VARIANTS), g.reqs())
+    return g.ops
+
+
+@functools.lru_cache(maxsize=None)
+def _cached_guide_sequence(seed):
+    avoid = set()
+    if seed in GUIDE_SEEDS:                                     # as for SEEDS: away from the pairs the seeds in front have
+        for s in GUIDE_SEEDS[:GUIDE_SEEDS.index(seed)]:
+            avoid |= pairs_of(_cached_guide_sequence(s))
+    return _guide_sequence(seed, frozenset(avoid))
+
+
+def make_guide_sequence(seed):
+    """The ops of a guide seed: deterministic, legal in the state the ops before them leave"""
+    import copy
+    return copy.deepcopy(_cached_guide_sequence(seed))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
 # the reference: the C oracle, memoised
 # ---------------------------------------------------------------------------------------------------------------------------------
 class _Node:
@@ -1231,7 +1566,7 @@ class Reference:
         tok = s.sample(logits)
         return tok, int(s.rng_state.value)
 
-    def generate(self, prompt, n_new, sampler=None, top_k=0, presence=0.0, frequency=0.0, entries=(), mode=0, dev=()):
+    def generate(self, prompt, n_new, sampler=None, top_k=0, presence=0.0, frequency=0.0, entries=(), mode=0, dev=(), guide=None, start=-1):
         """The header's rule for request rows: what a fresh engine returns for prefill(prompt) and generate_greedy behind it, after
         set_sampler(temperature, topp, seed) when sampler = (temperature, topp, seed) -- one discarded sample per prompt position
         in front of the last.  Under the engine-wide settings of sections 2n, 2p and 2q output g is taken from
@@ -1240,12 +1575,18 @@ class Reference:
         the injected leaks of FakeEngine alone -- ("counts0", ((token, count), ..)) counts the request does not start from zero with,
         ("per_g", ((entries, mode, g), ..)) the list and the output index each output is adjusted by, ("adjusted",) the records
         are taken on the adjusted row.
+        guide (a Guide) and start >= 0: sections 2r and 2s -- the row of output g is masked by the guide's row of state s_g first
+        (guide_ref.mask), bias_ref.rule runs on the masked row, and behind the commit s_{g+1} = next[s_g][y_g] where that is >= 0,
+        else s_g; the records stay on the raw row.  Deviations: ("g0state", s) the request starts in s and not in start, ("y0_raw",)
+        output 0 is not masked, ("masked_records",) the records are taken on the masked row.
         Returns (the n_new tokens, the rng state afterwards, per token the node whose logits it was taken from, per token the row a
         record is taken on: None for the node's own logits)."""
-        key = (tuple(prompt), n_new, sampler, top_k, presence, frequency, tuple(entries), mode, dev)
+        if guide is None or start < 0:
+            guide, start = None, -1
+        key = (tuple(prompt), n_new, sampler, top_k, presence, frequency, tuple(entries), mode, dev, guide.key if guide else None, start)
         if key not in self._memo:
             T, P, state = sampler if sampler else (0.0, 1.0, 0)
-            plain = not (top_k or presence or frequency or entries or mode or dev)
+            plain = not (top_k or presence or frequency or entries or mode or dev or guide)
             dev_of = dict((d[0], d[1:]) for d in dev)
             n, tok, out, nodes, rows = self.root, None, [], [], []
             for t in prompt:
@@ -1272,19 +1613,26 @@ class Reference:
                 for t, c in (dev_of["counts0"][0] if "counts0" in dev_of else ()):
                     counts[t] = c
                 pen = bool(presence or frequency)
+                s = dev_of["g0state"][0] if "g0state" in dev_of else start
                 for g in range(n_new):
                     if g:
                         n = self.child(n, tok)
                     en, mo, ge = dev_of["per_g"][0][g] if "per_g" in dev_of else (entries, mode, g)
-                    row = bias_ref.rule(n.logits, en, mo, ge, counts if pen else None, presence, frequency)
+                    raw = n.logits
+                    if guide is not None and s >= 0 and not (g == 0 and "y0_raw" in dev_of):
+                        import guide_ref
+                        raw = guide_ref.mask(n.logits, guide.row(s))
+                    row = bias_ref.rule(raw, en, mo, ge, counts if pen else None, presence, frequency)
                     if T > 0:
                         tok, state = self.draw(row, T, P, state, top_k)
                     else:
                         tok = pen_ref.argmax_key(row)
                     counts[tok] += 1
+                    if guide is not None and s >= 0:
+                        s = guide.step(s, int(tok))
                     out.append(int(tok))
                     nodes.append(n)
-                    rows.append(row if "adjusted" in dev_of else None)
+                    rows.append(row if "adjusted" in dev_of else raw if "masked_records" in dev_of and raw is not n.logits else None)
             self._memo[key] = (out, state, nodes, rows)
         return self._memo[key]
 
@@ -1294,6 +1642,100 @@ def cut_at_stop(row, stop):
         if t in stop:
             return row[:i + 1]
     return row
+
+
+class Guide:
+    """A guide as the reference reads it, in either statement: kind "dense" with next[n_states][V], or "sparse" with the four arrays
+    (default, offsets, tokens, targets); starts as the setter takes them.  row(s) is next[s][0 .. V) in both."""
+
+    def __init__(self, kind, arrays, starts):
+        import hashlib
+        self.kind, self.starts = kind, [int(s) for s in starts]
+        h = hashlib.blake2b(digest_size=16)
+        if kind == "dense":
+            self.next = np.ascontiguousarray(arrays, dtype=np.int16)
+            self.n_states = self.next.shape[0]
+            h.update(self.next.tobytes())
+        else:
+            d, o, t, x = arrays
+            self.default, self.offsets = np.ascontiguousarray(d, dtype=np.int32), np.ascontiguousarray(o, dtype=np.int64)
+            self.tokens, self.targets = np.ascontiguousarray(t, dtype=np.int32), np.ascontiguousarray(x, dtype=np.int32)
+            self.n_states = self.default.size
+            for a in (self.default, self.offsets, self.tokens, self.targets):
+                h.update(a.tobytes())
+                h.update(b"|")
+        self.key = (kind, h.hexdigest())
+        self._rows = {}
+
+    def row(self, s):
+        if self.kind == "dense":
+            return self.next[s]
+        if s not in self._rows:
+            a, b = int(self.offsets[s]), int(self.offsets[s + 1])
+            row = np.full(VOCAB, self.default[s], dtype=np.int32)
+            row[self.tokens[a:b]] = self.targets[a:b]
+            self._rows[s] = row
+        return self._rows[s]
+
+    def step(self, s, tok):
+        """the state step with its else branch"""
+        if s < 0:
+            return s
+        to = int(self.row(s)[tok])
+        return to if to >= 0 else s
+
+    def state_of(self, s, tokens):
+        for t in tokens:
+            s = self.step(s, t)
+        return s
+
+    def start_of(self, r):
+        return self.starts[0] if len(self.starts) == 1 else self.starts[r]
+
+    def sizes(self):
+        """what the grow-only arrays of the form hold (guide_call_begin, guide_sp_call_begin)"""
+        if self.kind == "dense":
+            return dict(guide_next=self.next.size, guide_start=len(self.starts))
+        return dict(guide_sp_dflt=self.n_states, guide_sp_off=self.n_states + 1, guide_sp_edges=max(self.tokens.size, 1), guide_sp_start=len(self.starts))
+
+
+def stop_next(a, s, tok):
+    """next[s][tok] of a stop automaton in section 2s's arrays"""
+    lo, hi = int(a.offsets[s]), int(a.offsets[s + 1])
+    k = lo + int(np.searchsorted(a.tokens[lo:hi], tok))
+    return int(a.targets[k]) if k < hi and a.tokens[k] == tok else int(a.default[s])
+
+
+def stop_emit(a, start, row, from_index=0):
+    """(n_emit, the state left) of one row under the stop automaton a stepped from `start`, by the automaton itself: what the leaks of
+    FakeEngine need, which start somewhere else than the rule says.  Matches in front of from_index do not end the row."""
+    s = start
+    if s < 0:
+        return len(row), -1
+    for i, t in enumerate(row):
+        x = stop_next(a, s, t)
+        if x < 0:
+            if i >= from_index:
+                return i + 1, -1
+            x = a.start
+        s = x
+    return len(row), s
+
+
+def check_sparse_arrays(default, offsets, tokens, targets, starts, vocab, dead_ok):
+    """what q3_guide_set_sparse and q3_stop_seq_set refuse about their arrays (IndexError: the binding's Q3_ERR_ARG)"""
+    d, o, t, x = (np.asarray(v, dtype=np.int64) for v in (default, offsets, tokens, targets))
+    S, E = d.size, t.size
+    bad = (S == 0 or not starts or o.size != S + 1 or x.size != E or vocab != VOCAB or any(not -1 <= s < S for s in starts)
+           or o[0] != 0 or (np.diff(o) < 0).any() or o[-1] != E or d.min() < -1 or d.max() >= S
+           or (E and (t.min() < 0 or t.max() >= vocab or x.min() < -1 or x.max() >= S)))
+    if not bad:
+        own = np.repeat(np.arange(S), np.diff(o))
+        bad = E > 1 and bool(((np.diff(t) <= 0) & (own[1:] == own[:-1])).any())
+        allowed = np.bincount(own[x >= 0], minlength=S) if E else np.zeros(S, dtype=np.int64)
+        bad = bad or (not dead_ok and bool(((allowed == 0) & ((d < 0) | (np.diff(o) == vocab))).any()))
+    if bad:
+        raise IndexError("the arrays of a sparse automaton are refused")
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -1315,6 +1757,9 @@ class _Cache:
 LEAKS = ("sampler", "prefix", "length", "slot_rng", "stale_cand")
 SETTING_LEAKS = ("pen_counts", "pen_prompt", "bias_stale", "bias_ooff", "genlp_stale", "genlp_penalised", "topk_init", "settings_touch_cols",
                  "score_top_shared")
+GUIDE_LEAKS = ("guide_slot_state", "guide_y0_raw", "guide_init_dropped", "guide_both_forms", "guide_table_stale", "guide_start_shared",
+               "guide_touch_cols", "guide_records_masked", "stop_prompt_steps", "stop_slot_state", "stop_in_plain_loops", "stop_min_tokens",
+               "stop_init_dropped")
 
 
 class FakeEngine:
@@ -1339,10 +1784,26 @@ class FakeEngine:
         "topk_init": batch_init resets top_k to 0
         "settings_touch_cols": batch_step_cols_draw adjusts its rows by the table's first list and the slot's counts
         "score_top_shared": score_top_many behind a loop with tops answers the first chunk's tops and ranks from the part lists
-                   the loop's last pass left"""
+                   the loop's last pass left
+    and of GUIDE_LEAKS, over the state of sections 2r to 2t --
+        "guide_slot_state": a reused slot's first output is taken in the state its predecessor left, not in start[r]
+        "guide_y0_raw": output 0 is not masked
+        "guide_init_dropped": batch_init clears the guide
+        "guide_both_forms": setting the sparse form leaves the dense one in force
+        "guide_table_stale": a set_guide with the state count of the table before keeps that table (a serial number that is not bumped)
+        "guide_start_shared": every request starts in start[0]
+        "guide_touch_cols": batch_step_cols_draw masks its rows by the guide's start state
+        "guide_records_masked": the records are taken on the masked row
+        "stop_prompt_steps": the tokens in front of the first output -- the resident prefix and the prompt -- move the stop state
+        "stop_slot_state": the next occupant of a slot continues from the stop state its predecessor left
+        "stop_in_plain_loops": generate_many_greedy, _sampled and _dense cut their rows
+        "stop_min_tokens": a sequence match in front of the largest `until` of the request's list does not end the request
+        "stop_init_dropped": batch_init clears the stop automaton"""
 
     def __init__(self, ref, leak=None):
-        assert leak is None or leak in LEAKS + SETTING_LEAKS
+        assert leak is None or leak in LEAKS + SETTING_LEAKS + GUIDE_LEAKS
+        self.guide = self.guide_held = None  # the Guide in force (either form), and the one a leak keeps on the device
+        self.stopa = None                    # (automaton, starts): the stop automaton in force
         self.ref, self.leak = ref, leak
         self.single = _Cache(ref, SEQ)
         self.slots, self.streams, self.ctx = [], 0, 0
@@ -1400,6 +1861,63 @@ class FakeEngine:
 
     def get_logit_bias(self):
         return [list(l) for l in self.bias[0]], list(self.bias[1])
+
+    # -- guides and the stop automaton (sections 2r to 2t)
+    @staticmethod
+    def _starts(start):
+        starts = [start] if isinstance(start, (int, np.integer)) else list(start)
+        if any(s < -1 for s in starts):
+            raise IndexError("a start state below -1")
+        return [int(s) for s in starts]
+
+    def set_guide(self, next, start):
+        self.left_dense = None
+        if next is None or np.size(next) == 0:
+            self.guide = self.guide_held = None
+            return
+        t, starts = np.asarray(next), self._starts(start)
+        S = t.shape[0]
+        if (t.ndim != 2 or t.shape[1] != VOCAB or S > 4096 or not starts or t.min() < -1 or t.max() >= S or any(s >= S for s in starts)
+                or not (t >= 0).any(axis=1).all()):
+            raise IndexError("a table with another vocabulary, an entry or a start outside its states, or a state that allows no token")
+        held = self.guide_held
+        self.guide = self.guide_held = Guide("dense", t, starts)
+        if self.leak == "guide_table_stale" and held is not None and held.kind == "dense" and held.n_states == S:
+            self.guide_held = Guide("dense", held.next, starts)
+
+    def set_guide_sparse(self, default, offsets, tokens, targets, start):
+        if default is None or np.size(default) == 0:
+            self.guide = self.guide_held = self.left_dense = None
+            return
+        starts = self._starts(start)
+        check_sparse_arrays(default, offsets, tokens, targets, starts, VOCAB, False)
+        self.left_dense = self.guide if self.leak == "guide_both_forms" and self.guide is not None and self.guide.kind == "dense" else None
+        self.guide = self.guide_held = Guide("sparse", (default, offsets, tokens, targets), starts)
+
+    left_dense = None
+
+    def get_guide(self):
+        g = self.left_dense or self.guide
+        return (g.next, list(g.starts)) if g is not None and g.kind == "dense" else (None, [])
+
+    def get_guide_sparse(self):
+        g = self.guide
+        return (g.default, g.offsets, g.tokens, g.targets, list(g.starts)) if g is not None and g.kind == "sparse" else (None, None, None, None, [])
+
+    def set_stop_sequences(self, automaton, start=None):
+        if automaton is None:
+            self.stopa = None
+            return
+        starts = self._starts(automaton.start if start is None else start)
+        check_sparse_arrays(automaton.default, automaton.offsets, automaton.tokens, automaton.targets, starts, int(getattr(automaton, "vocab_size", VOCAB)), True)
+        self.stopa = (automaton, starts)
+
+    def get_stop_sequences(self):
+        return (None, []) if self.stopa is None else (self.stopa[0], list(self.stopa[1]))
+
+    def _guide_now(self):
+        """the guide the loops run under"""
+        return self.left_dense or self.guide_held
 
     def read_gen_logprobs(self, n_per_row=None):
         import score_top_ref
@@ -1527,6 +2045,10 @@ class FakeEngine:
         self.gen, self.dev = None, {}            # the records and every buffer of the settings belong to the batched state
         if self.leak == "topk_init":
             self.k_top = 0
+        if self.leak == "guide_init_dropped":
+            self.guide = self.guide_held = self.left_dense = None
+        if self.leak == "stop_init_dropped":
+            self.stopa = None
         if self.leak != "prefix":
             self.prefix = []
         self.touched.update({s: "all" for s in range(streams)})
@@ -1584,6 +2106,9 @@ class FakeEngine:
                 import bias_ref
                 en, mo = bias_ref.list_of(self.bias, 0)
                 lg = bias_ref.rule(lg, en, mo, 0, self.dev.get("counts", {}).get(s) if any(self.pen) else None, *self.pen)
+            if self.leak == "guide_touch_cols" and want_draw and self._guide_now() is not None and self._guide_now().starts[0] >= 0:
+                import guide_ref
+                lg = guide_ref.mask(lg, self._guide_now().row(self._guide_now().starts[0]))
             if draw and keep is not None and not keep[j]:
                 out.append(-1)
             elif not draw and lg is not logits[-1]:
@@ -1615,7 +2140,8 @@ class FakeEngine:
                 self.brng[s] = xorshift(self.brng[s], len(p))
         return _q3().dense_pack([len(p) for p in prompts], DENSE_CAP)[1]
 
-    def _many(self, prompts, n_new, sampler, dense_min=0, stop=(), prefix=(), carry=False):
+    def _many(self, prompts, n_new, sampler, dense_min=0, stop=(), prefix=(), carry=False, sched=False):
+        """sched: one of the two loops with a device scheduler, which honour the stop automaton"""
         self.gen = None                          # every loop call starts here: the records of the call before are gone
         for p in prompts:
             self._check_tokens(p)
@@ -1625,6 +2151,9 @@ class FakeEngine:
         lists, modes = self.bias
         if len(lists) > 1 and len(lists) != n:
             raise IndexError("one list per request")
+        gd, sa = self._guide_now(), self.stopa
+        if any(len(s) > 1 and len(s) != n for s in ([gd.starts] if gd else []) + ([sa[1]] if sa else [])):
+            raise IndexError("one start state per request")
         per = [None] * n
         if sampler is not None:
             T, P, seeds = [v if isinstance(v, (list, tuple)) else [v] * n for v in sampler]
@@ -1642,9 +2171,13 @@ class FakeEngine:
                         self.loop_rng[s] = self.ref.generate(full[r], n_new[r], per[r])[1]
         res = self._rows(full, lens, n_new, per)
         rows = [x[0] for x in res]
-        plan = plan or many_plan(lens, n_new, self.streams, dense_min, rows, stop)
         out = [cut_at_stop(r, stop) for r in rows]
-        assert [len(r) for r in out] == list(plan["n_out"])
+        emit = None
+        if sa is not None and (sched or self.leak == "stop_in_plain_loops"):
+            emit = self._stop_emits(sa, [list(prefix) + list(p) for p in prompts], rows, stop, lens, n_new)
+            out = [r[:k] for r, k in zip(rows, emit)]
+        plan = plan or many_plan(lens, n_new, self.streams, dense_min, rows, stop, emit if sched else None)
+        assert [len(r) for r in out] == list(plan["n_out"]) or self.leak == "stop_in_plain_loops"
         for s, occ in sorted(plan["occupants"].items()):
             for r in occ:
                 for i, t in enumerate(full[r] + out[r][:-1]):
@@ -1653,12 +2186,59 @@ class FakeEngine:
             self._records(n_new, out, res)
         return out, plan
 
+    def _stop_emits(self, sa, prompts, rows, stop, lens, n_new):
+        """n_emit per request under the stop automaton: the smallest of the first stop token's index + 1, the first completed
+        sequence's index + 1 and n_new, by stop_seq_ref's plain sub-list search over the sequences the automaton was compiled from
+        (automaton.seqs; None: the automaton whose one state completes with every token)"""
+        import bias_ref
+        import stop_seq_ref
+        a, starts = sa
+        per = [starts[0] if len(starts) == 1 else starts[r] for r in range(len(rows))]
+        cuts = [len(cut_at_stop(r, stop)) for r in rows]
+        if self.leak == "stop_prompt_steps":
+            emit = []
+            for r, row in enumerate(rows):
+                s = per[r]
+                for t in (prompts[r] if s >= 0 else ()):
+                    x = stop_next(a, s, t)
+                    s = x if x >= 0 else a.start
+                emit.append(min(cuts[r], stop_emit(a, s, row)[0]))
+            return emit
+        if self.leak == "stop_min_tokens":
+            floors = [max([e[2] for e in bias_ref.list_of(self.bias, r)[0]] + [1]) for r in range(len(rows))]
+            return [min(cuts[r], stop_emit(a, per[r], row, floors[r] - 1)[0]) for r, row in enumerate(rows)]
+        if a.seqs is None:
+            emit = [1 if per[r] >= 0 else cuts[r] for r in range(len(rows))]
+        else:
+            emit = stop_seq_ref.n_emit_rows(rows, a.seqs, stop, per)
+        if self.leak == "stop_slot_state":
+            left = self.dev.setdefault("stop_state", {})
+            for s, occ in sorted(many_plan(lens, n_new, self.streams, emit=emit)["occupants"].items()):
+                for r in occ:
+                    use = min(left[s], a.default.size - 1) if left.get(s, -1) >= 0 and per[r] >= 0 else per[r]
+                    emit[r] = min(cuts[r], stop_emit(a, use, rows[r])[0])
+                    left[s] = stop_emit(a, use, rows[r][:emit[r]])[1]
+        return emit
+
     def _rows(self, full, lens, n_new, per):
         """Reference.generate per request under the settings: (tokens, rng state, nodes, record rows) each"""
         import bias_ref
         lists, modes = self.bias
         pen = any(self.pen)
         n = len(full)
+        gd = self._guide_now()
+        self._gctx = None
+        if gd is not None:
+            starts = [gd.starts[0] if self.leak == "guide_start_shared" else gd.start_of(r) for r in range(n)]
+            self._gctx = dict(guide=gd, start=starts, g0=[None] * n)
+            if self.leak == "guide_slot_state":
+                left = self.dev.setdefault("guide_state", {})
+                for s, occ in sorted(many_plan(lens, n_new, self.streams)["occupants"].items()):
+                    for r in occ:
+                        if left.get(s, -1) >= 0 and starts[r] >= 0:
+                            self._gctx["g0"][r] = min(left[s], gd.n_states - 1)
+                        got = self._one(full[r], n_new[r], per[r], bias_ref.list_of(self.bias, r), None, None, r)[0]
+                        left[s] = gd.state_of(starts[r] if self._gctx["g0"][r] is None else self._gctx["g0"][r], got)
         tables = [bias_ref.list_of(self.bias, r) for r in range(n)]
         if self.leak == "bias_stale" and lists:
             # the flat entries of this table over what the buffer held: the tail of the longer table before stands behind the last list
@@ -1700,11 +2280,11 @@ class FakeEngine:
                     else:
                         c = dict(left.get(s, {}))
                     counts0[r] = tuple(sorted(c.items()))
-                    got = self._one(full[r], n_new[r], per[r], tables[r], per_g[r], counts0[r])[0]
+                    got = self._one(full[r], n_new[r], per[r], tables[r], per_g[r], counts0[r], r)[0]
                     for t in got:
                         c[t] = c.get(t, 0) + 1
                     left[s] = c
-        res = [self._one(full[r], n_new[r], per[r], tables[r], per_g[r], counts0[r]) for r in range(n)]
+        res = [self._one(full[r], n_new[r], per[r], tables[r], per_g[r], counts0[r], r) for r in range(n)]
         if pen and self.leak == "settings_touch_cols":          # the counts that leak keeps per slot: the last occupant's
             cs = self.dev.setdefault("counts", {})
             for s, occ in many_plan(lens, n_new, self.streams)["occupants"].items():
@@ -1714,7 +2294,7 @@ class FakeEngine:
                 cs[s] = c
         return res
 
-    def _one(self, prompt, n_new, sampler, table, per_g, counts0):
+    def _one(self, prompt, n_new, sampler, table, per_g, counts0, r=None):
         dev = ()
         if per_g:
             dev += (("per_g", per_g),)
@@ -1722,7 +2302,19 @@ class FakeEngine:
             dev += (("counts0", counts0),)
         if self.leak == "genlp_penalised" and self.genlp >= 0:
             dev += (("adjusted",),)
-        return self.ref.generate(prompt, n_new, sampler, self.k_top if sampler else 0, self.pen[0], self.pen[1], tuple(tuple(e) for e in table[0]), table[1], dev)
+        guide, start = None, -1
+        if self._gctx is not None and self._gctx["start"][r] >= 0:
+            guide, start = self._gctx["guide"], self._gctx["start"][r]
+            if self._gctx["g0"][r] is not None:
+                dev += (("g0state", self._gctx["g0"][r]),)
+            if self.leak == "guide_y0_raw":
+                dev += (("y0_raw",),)
+            if self.leak == "guide_records_masked" and self.genlp >= 0:
+                dev += (("masked_records",),)
+        return self.ref.generate(prompt, n_new, sampler, self.k_top if sampler else 0, self.pen[0], self.pen[1], tuple(tuple(e) for e in table[0]), table[1], dev,
+                                 guide, start)
+
+    _gctx = None
 
     def _records(self, n_new, out, res):
         """the record buffers of the call as read_gen_logprobs finds them: indexed as the output tokens, cleared in front of the call"""
@@ -1764,15 +2356,23 @@ class FakeEngine:
         live = sum(sum(b[2]) for b in plan["blocks"])
         return out, plan["stats"], _q3().DenseStats(len(plan["blocks"]), live, sum(b[0] for b in plan["blocks"]) - live)
 
-    def generate_many_stop(self, prompts, n_new, stop_tokens, sampler=None):
-        out, plan = self._many(prompts, n_new, sampler, 0, tuple(stop_tokens))
-        return out, plan["stats"]
+    @staticmethod
+    def _raw(out, n_new, stats, raw):
+        """raw: (the output buffer as the library fills it -- -1 behind every request's last token --, n_out, stats)"""
+        if not raw:
+            return out, stats
+        buf = [t for row, k in zip(out, n_new) for t in list(row) + [-1] * (k - len(row))]
+        return buf, [len(r) for r in out], stats
 
-    def generate_many_prefix(self, suffixes, n_new, stop_tokens=(), sampler=None):
+    def generate_many_stop(self, prompts, n_new, stop_tokens, sampler=None, raw=False):
+        out, plan = self._many(prompts, n_new, sampler, 0, tuple(stop_tokens), sched=True)
+        return self._raw(out, n_new, plan["stats"], raw)
+
+    def generate_many_prefix(self, suffixes, n_new, stop_tokens=(), sampler=None, raw=False):
         if not self.prefix:
             raise IndexError("no resident prefix")
-        out, plan = self._many(suffixes, n_new, sampler, 0, tuple(stop_tokens), self.prefix)
-        return out, plan["stats"]
+        out, plan = self._many(suffixes, n_new, sampler, 0, tuple(stop_tokens), self.prefix, sched=True)
+        return self._raw(out, n_new, plan["stats"], raw)
 
     def batch_copy_rows(self, src, dst, first, n):
         if not 1 <= len(dst) <= self.streams - 1 or any(s < 0 or s >= self.streams or s == src for s in dst) or first + n > self.ctx:
@@ -1904,11 +2504,16 @@ def _requests(op, ref, prefix, top_k=0, pen=(0.0, 0.0)):
 def settings_walk(ops):
     """per op what is in force in front of it: dict(top_k, genlp, pen, table = the index of the set_logit_bias op whose table holds or
     None, prefix = the resident prefix as a PREFIXES entry or None, streams).  A refused call changes nothing."""
-    st = dict(top_k=0, genlp=-1, pen=(0.0, 0.0), table=None, prefix=None, streams=0)
+    st = dict(top_k=0, genlp=-1, pen=(0.0, 0.0), table=None, prefix=None, streams=0, guide=None, gform=None, stop=None)
     out = []
     for i, op in enumerate(ops):
         out.append(dict(st))
         k = op["op"]
+        if k in ("set_guide", "set_guide_sparse"):           # guide, stop: the index of the setter op whose automaton holds, or None;
+            on = op["form"] != "off"                         # gform: which of the two guide forms; setting either clears the other
+            st["guide"], st["gform"] = (i, "dense" if k == "set_guide" else "sparse") if on else (None, None)
+        elif k == "set_stop_seq":
+            st["stop"] = i if op["form"] != "off" else None
         if k == "set_top_k":
             st["top_k"] = op["k"]
         elif k == "set_gen_logprobs":
@@ -1924,7 +2529,7 @@ def settings_walk(ops):
     return out
 
 
-BIAS_SIZES = {"one": 40, "big": 320, "add": 5, "allow": 3}          # entries per list: static, so that needs() knows them without an oracle
+BIAS_SIZES = {"one": 40, "big": 320, "add": 5, "allow": 3, "kill": 3, "min": 4}     # entries per list: static, so that needs() knows them without an oracle
 NEG_INF = float("-inf")
 
 
@@ -1932,10 +2537,80 @@ def table_lens(op):
     """the list lengths and modes of a set_logit_bias op: per request ALLOW (three tokens) and ADD lists in turn"""
     if op["form"] == "off":
         return [], []
-    if op["form"] in ("one", "big"):
+    if op["form"] in ("one", "big", "kill", "min"):          # (kill, min: the two lists of the guide sequences, see Tables.get)
         return [BIAS_SIZES[op["form"]]], [0]
     modes = [(r + op["par"]) % 2 for r in range(op["n"])]
     return [BIAS_SIZES["allow"] if m else BIAS_SIZES["add"] for m in modes], modes
+
+
+GUIDE_BIG = {1: 1024, 2: 1536}                   # the states of the dense form "big" by op["size"]: guide_next grows twice
+SPARSE_BIG = {1: (64, 128), 2: (128, 256)}       # (states, edges per state) of the sparse form "big"
+STOP_BIG = {1: 150, 2: 300}                      # the sequences of the stop form "big" that never complete
+
+
+def cycle_small(seed):
+    """the three tokens the small state of a cycle allows, from the seed alone: a "kill" table bans exactly these"""
+    return sorted(random.Random(seed ^ 0x5A5A).sample(range(1, VOCAB - 1), 3))
+
+
+def guide_arrays(dense, form, seed, forbid, size=1, ns=None):
+    """(n_states, the arrays of a guide form): next[n_states][V] for a dense guide, (default, offsets, tokens, targets) for a sparse
+    one -- through SparseAutomaton.from_dense for the forms both have.  forbid: tokens no state allows (but a cycle's small state,
+    whose three tokens come from the seed alone); ns: the states of a cycle, where the op fixes them."""
+    from qwen3_rs_amd.guide import Automaton, SparseAutomaton
+    V = VOCAB
+    rng, r = np.random.default_rng(seed), random.Random(seed)
+    forbid = np.array(sorted(forbid), dtype=np.int64)
+    ok = np.ones(V, dtype=bool)
+    ok[forbid] = False
+    if not dense and form in ("dflt", "half", "big"):
+        if form == "dflt":                       # s0: all but `forbid`; s1: no edges, everything allowed; s2: three tokens, the rest forbidden by default
+            rows = [(1, forbid, np.full(forbid.size, -1)), (2, forbid[:0], forbid[:0]), (-1, np.array(cycle_small(seed)), np.zeros(3, dtype=np.int64))]
+        elif form == "half":                     # s0: allowed by default, about V/2 forbidding edges with 0 and V - 1 among them; s1: no edges
+            ban = np.zeros(V, dtype=bool)
+            ban[rng.choice(V, V // 2, replace=False)] = True
+            ban[[0, V - 1]] = True
+            ban[forbid] = True
+            t = np.flatnonzero(ban)
+            rows = [(1, t, np.full(t.size, -1)), (0, forbid[:0], forbid[:0])]
+        else:                                    # a chain of states, each with its own few allowed tokens
+            S, K = SPARSE_BIG[size]
+            pool = np.flatnonzero(ok)
+            rows = [(-1, np.sort(rng.choice(pool, K, replace=False)), np.full(K, (s + 1) % S)) for s in range(S)]
+        off = np.zeros(len(rows) + 1, dtype=np.int64)
+        np.cumsum([t.size for _, t, _ in rows], out=off[1:])
+        return len(rows), (np.array([d for d, _, _ in rows], dtype=np.int32), off, np.concatenate([t for _, t, _ in rows]).astype(np.int32),
+                           np.concatenate([x for _, _, x in rows]).astype(np.int32))
+    if form == "all":                            # two states, everything allowed: the masked form on the raw row
+        nxt = np.zeros((2, V), dtype=np.int16)
+        nxt[0] = 1
+    elif form == "trie":                         # three labels of 2, 3 and 4 tokens, then eos, then a free state
+        firsts = r.sample([t for t in range(V - 1) if ok[t]], 3)
+        labels = [[f] + [r.randrange(V - 1) for _ in range(n - 1)] for f, n in zip(firsts, (2, 3, 4))]
+        nxt = Automaton.from_sequences(labels, V, V - 1).next.copy()
+        nxt[-1] = nxt.shape[0] - 1
+    elif form in ("cycle", "per"):               # 3 to 5 states of about V/2, V/16, 3, V/2 .. allowed tokens, each leading to the next
+        n = ns or r.choice((3, 4, 5))
+        nxt = np.full((n, V), -1, dtype=np.int16)
+        for s in range(n):
+            allow = np.zeros(V, dtype=bool)
+            if s == 2:
+                allow[cycle_small(seed)] = True
+            else:
+                allow[rng.choice(V, V // 16 if s == 1 else V // 2, replace=False)] = True
+                allow[0], allow[V - 1] = s == 1, s == 0         # 0 only in state 1, V - 1 only in state 0
+                allow &= ok
+            nxt[s, allow] = (s + 1) % n
+    elif form == "big":
+        S = GUIDE_BIG[size]
+        allow = (rng.random((S, V)) < 0.5) & ok
+        nxt = np.where(allow, ((np.arange(S) + 1) % S)[:, None], -1).astype(np.int16)
+    else:
+        raise ValueError(form)
+    if dense:
+        return nxt.shape[0], nxt
+    a = SparseAutomaton.from_dense(Automaton(nxt))
+    return a.n_states, (a.default, a.offsets, a.tokens, a.targets)
 
 
 class Tables:
@@ -1947,32 +2622,184 @@ class Tables:
 
     def __init__(self, ops, ref):
         self.ops, self.ref, self.st, self.memo = ops, ref, settings_walk(ops), {}
+        self.gmemo, self.smemo = {}, {}
 
-    def users(self, i):
-        return [j for j in range(i + 1, len(self.ops)) if self.ops[j]["op"] in MANY and self.st[j]["table"] == i]
+    def users(self, i, what="table"):
+        return [j for j in range(i + 1, len(self.ops)) if self.ops[j]["op"] in MANY and self.st[j][what] == i]
 
     def plain_rows(self, j):
-        """the requests of loop op j with no table set: per request the row cut at its first stop token"""
-        return self.rows(j, table=False)
+        """the requests of loop op j with no table and no guide set: per request the row cut at its first stop token"""
+        return self.rows(j, table=False, guide=False)
 
-    def rows(self, j, table=True, **other):
-        """The rows of loop op j by Reference alone, each cut at its first stop token, under the settings in force in front of it;
-        table False: with no table set; other: top_k or pen replaced.  The stop tokens are the op's own in every case."""
+    def rows(self, j, table=True, guide=True, cut=True, **other):
+        """The rows of loop op j by Reference alone, each cut at its first stop token (cut False: whole), under the settings in
+        force in front of it; table False: with no table set; guide False: with no guide set; other: top_k or pen replaced.  The
+        stop tokens are the op's own in every case.  The stop automaton is not applied: emits() is."""
         op, st = self.ops[j], self.st[j]
         prefix = toks(st["prefix"]) if op["op"] == "generate_many_prefix" else []
         prompts, n_new, sampler, stop = _requests(op, self.ref, prefix, st["top_k"], st["pen"])
         st = dict(st, **other)
         lists = self.get(st["table"]) if table and st["table"] is not None else ([], [])
+        gd = self.guide(st["guide"]) if guide and st["guide"] is not None else None
         import bias_ref
         rows = []
         for r, p in enumerate(prompts):
             smp = (sampler[0][r], sampler[1][r], sampler[2][r]) if sampler and sampler[0][r] > 0 else None
             en, mo = bias_ref.list_of(lists, r)
-            row = self.ref.generate(tuple(prefix + p), n_new[r], smp, st["top_k"] if smp else 0, st["pen"][0], st["pen"][1], tuple(tuple(e) for e in en), mo)[0]
-            rows.append(cut_at_stop(row, stop))
+            row = self.ref.generate(tuple(prefix + p), n_new[r], smp, st["top_k"] if smp else 0, st["pen"][0], st["pen"][1], tuple(tuple(e) for e in en), mo, (),
+                                    gd, gd.start_of(r) if gd else -1)[0]
+            rows.append(cut_at_stop(row, stop) if cut else row)
         return rows
 
+    def stop_tokens(self, j):
+        op, st = self.ops[j], self.st[j]
+        return _requests(op, self.ref, toks(st["prefix"]) if op["op"] == "generate_many_prefix" else [], st["top_k"], st["pen"])[3]
+
+    def emits(self, j):
+        """n_emit per request of loop op j: under a stop automaton, in the two loops that honour it, the smallest of the first stop
+        token's index + 1, the first completed sequence's index + 1 (stop_seq_ref) and n_new; else the cut at the stop tokens"""
+        import stop_seq_ref
+        op, st = self.ops[j], self.st[j]
+        whole = self.rows(j, cut=False)
+        stop = self.stop_tokens(j) if op["op"] in ("generate_many_stop", "generate_many_prefix") else []
+        if st["stop"] is None or op["op"] not in ("generate_many_stop", "generate_many_prefix"):
+            return [len(cut_at_stop(r, stop)) for r in whole]
+        a, starts = self.stop(st["stop"])
+        per = [starts[0] if len(starts) == 1 else starts[r] for r in range(len(whole))]
+        if a.seqs is None:
+            return [1 if s >= 0 else len(cut_at_stop(r, stop)) for r, s in zip(whole, per)]
+        return stop_seq_ref.n_emit_rows(whole, a.seqs, stop, per)
+
+    def seq_emits(self, j):
+        """per request of loop op j the index + 1 of the first token that completes a sequence of the stop automaton in force, by
+        stop_seq_ref alone; n_new where none does, the request has no stop sequences or the loop does not honour the automaton"""
+        import stop_seq_ref
+        op, st = self.ops[j], self.st[j]
+        whole = self.rows(j, cut=False)
+        if st["stop"] is None or op["op"] not in ("generate_many_stop", "generate_many_prefix"):
+            return [len(r) for r in whole]
+        a, starts = self.stop(st["stop"])
+        per = [starts[0] if len(starts) == 1 else starts[r] for r in range(len(whole))]
+        return [len(row) if s < 0 else 1 if a.seqs is None else stop_seq_ref.n_emit_seqs(row, a.seqs) for row, s in zip(whole, per)]
+
+    # -- the guides (sections 2r and 2s): from the op's seed, and from the first tokens its users' requests produce with no guide set
+    # (under the table and the other settings in force), which no state allows: every guided request's row differs from its unguided one
+    def guide(self, i):
+        if i not in self.gmemo:
+            op = self.ops[i]
+            dense = op["op"] == "set_guide"
+            forbid = sorted({row[0] for j in self.users(i, "guide") for row in self.rows(j, guide=False, cut=False)})
+            n_states, arrays = guide_arrays(dense, op["form"], op["seed"], forbid, op.get("size", 1), op.get("ns"))
+            r = random.Random(op["seed"] + 1)
+            if op["form"] == "per":              # one request unguided, the others in the cycle's states 0 and 1 in turn
+                free = r.randrange(op["n"])          # (n >= 3: both states remain among the others)
+                starts = [k % 2 for k in range(op["n"] - 1)]
+                starts.insert(free, -1)
+            elif op["form"] == "big":            # one start per request: guide_start grows with the request list
+                starts = [k % min(n_states, 7) for k in range(op["n"])]
+            else:
+                starts = [0]
+            self.gmemo[i] = Guide("dense" if dense else "sparse", arrays, starts)
+        return self.gmemo[i]
+
+    # -- the stop automata (section 2t): sequences taken from the rows the reference gives the requests of the op's users
+    def stop(self, i):
+        if i not in self.smemo:
+            self.smemo[i] = self._stop(i)
+        return self.smemo[i]
+
+    def _stop(self, i):
+        import stop_seq_ref
+        from qwen3_rs_amd.guide import SparseAutomaton
+        from qwen3_rs_amd.stops import stop_automaton
+        op = self.ops[i]
+        form, n = op["form"], op.get("n", 1)
+        rng = random.Random(op["seed"])
+        users = self.users(i, "stop")
+        used = [(self.rows(j, cut=False), self.rows(j)) for j in users]          # whole rows, and the rows cut at the stop tokens
+        prompts = [_requests(self.ops[j], self.ref, [], self.st[j]["top_k"], self.st[j]["pen"])[0] for j in users]
+        every = [row for whole, _ in used for row in whole]
+        produced = {t for row in every for t in row}
+
+        def unseen(k):
+            """k tokens no request produces"""
+            out = []
+            while len(out) < k:
+                t = rng.randrange(VOCAB)
+                if t not in produced:
+                    out.append(t)
+            return out
+
+        def hit(whole, cut, r, K, early=False):
+            """K tokens of request r that complete strictly inside its cap: in front of its first stop token where there is room"""
+            row = whole[r]
+            cand = [g for g in range(K - 1, len(row) - 1)]
+            front = [g for g in cand if g + 1 < len(cut[r])]
+            cand = front or cand
+            if not cand:
+                return None
+            g = min(cand) if early else rng.choice(cand)
+            return tuple(row[g - K + 1:g + 1])
+
+        starts = [0]
+        if form == "any":                        # one state, dflt -1, no edges: every token completes a sequence
+            a = SparseAutomaton([-1], [0, 0], [], [], 0, VOCAB, dead_ok=True)
+            a.seqs = None
+            return a, starts
+        seqs = []
+        if form in ("hit1", "hit2", "hit3"):
+            K = int(form[3])
+            seqs = [hit(whole, cut, rng.randrange(len(whole)), K, op.get("early", False)) for whole, cut in used]
+        elif form == "overlap":
+            # A = [a, b, x] never completes (x is produced nowhere); B = [b, c] completes behind a, b, where the automaton stands two
+            # tokens deep in A and takes the fall-back edge to B's first state
+            for whole, cut in used:
+                cand = [(r, g) for r, row in enumerate(whole) for g in range(2, len(row) - 1)
+                        if len({row[g - 2], row[g - 1], row[g]}) == 3 and stop_seq_ref.n_emit_seqs(row, [row[g - 1:g + 1]]) == g + 1]
+                cand = [(r, g) for r, g in cand if g + 1 <= len(cut[r])] or cand
+                if cand:
+                    r, g = rng.choice(cand)
+                    a_, b_, c_ = whole[r][g - 2:g + 1]
+                    seqs += [(a_, b_, unseen(1)[0]), (b_, c_)]
+        elif form == "per":                      # one start per request, one of them -1: that request has no stop sequences
+            starts = [0] * n
+            starts[rng.randrange(n)] = -1
+            seqs = [hit(whole, cut, r, rng.choice((1, 2))) for whole, cut in used for r in range(len(whole))]
+        elif form == "big":                      # many sequences no request produces, and one that hits per user
+            starts = [0] * n
+            seqs = [tuple(unseen(3)) for _ in range(STOP_BIG[op.get("size", 1)])] + [hit(whole, cut, rng.randrange(len(whole)), 2) for whole, cut in used]
+        seqs = sorted({q for q in seqs if q})
+        if form in ("hit2", "hit3", "overlap", "per", "big"):
+            # baits, which no request produces and a correct engine never completes: (the last token of a request's prompt, its first
+            # output) ends the request at y_0 where prompt tokens move the state; (the last token of request a, the first output of
+            # request b) ends b at y_0 where b takes a's slot and finds the state a left
+            baits = set()
+            for (whole, cuts), ps in zip(used, prompts):
+                baits |= {(p[-1], row[0]) for p, row in zip(ps, whole)}
+                baits |= {(x[-1], y[0]) for rows in (whole, cuts) for i, x in enumerate(rows) for k, y in enumerate(rows) if i != k}
+            seqs = sorted(set(seqs) | {q for q in baits if not stop_seq_ref.occurs(every, q) and not any(q[-len(s_):] == s_ for s_ in seqs if len(s_) < 2)})
+        if form == "never" or not seqs:          # a sequence no request produces
+            while True:
+                q = (rng.randrange(VOCAB), rng.randrange(VOCAB))
+                if not stop_seq_ref.occurs(every, q):
+                    seqs.append(q)
+                    break
+        a = stop_automaton(seqs, VOCAB)
+        a.seqs = [list(q) for q in seqs]
+        return a, starts
+
     def get(self, i):
+        if i not in self.memo and self.ops[i]["form"] in ("kill", "min"):
+            op = self.ops[i]
+            users = self.users(i)
+            if op["form"] == "kill":             # the three tokens the small state of the cycle in force allows, banned for good
+                g = self.ops[self.st[users[0]]["guide"]]
+                ent = [(t, NEG_INF, 0) for t in cycle_small(g["seed"])]
+            else:                                # min_tokens 4 for tokens no request produces: the rows stay, until > 0 stands in the list
+                produced = {t for j in users for row in self.plain_rows(j) for t in row}
+                rng = random.Random(op["seed"])
+                ent = sorted((t, NEG_INF, 4) for t in rng.sample([t for t in range(VOCAB) if t not in produced], 4))
+            self.memo[i] = ([ent], [0])
         if i not in self.memo:
             op = self.ops[i]
             lens, modes = table_lens(op)
@@ -2042,6 +2869,45 @@ def call(e, op, ref, prefix=(), env=None):
         lists, modes = {"twice": ([[(t, 1.0), (t + 1, 0.5), (t, -1.0)]], None), "vocab": ([[(t, 1.0)], [(VOCAB, 1.0)]], None),
                         "inf": ([[(t, float("inf"))]], None), "allow": ([[(t, NEG_INF), (t + 1, NEG_INF, 4)]], [1])}[op["bad"]]
         return _setting(e.set_logit_bias, lists, modes)
+    if k in ("set_guide", "set_guide_sparse"):
+        g = env["auto"]
+        if g is None:
+            return _setting(e.set_guide, None, 0) if k == "set_guide" else _setting(e.set_guide_sparse, None, None, None, None, 0)
+        if k == "set_guide":
+            return _setting(e.set_guide, g.next, g.starts)
+        return _setting(e.set_guide_sparse, g.default, g.offsets, g.tokens, g.targets, g.starts)
+    if k == "set_stop_seq":
+        return _setting(e.set_stop_sequences, *(env["auto"] or (None, None)))
+    if k == "refused_set_guide":
+        nxt = np.zeros((3, VOCAB + (op["bad"] == "vocab")), dtype=np.int16)
+        if op["bad"] == "dead":                  # a state that allows no token
+            nxt[1] = -1
+        elif op["bad"] == "entry":               # an entry outside [-1, n_states)
+            nxt[2, op["at"]] = 3
+        return _setting(e.set_guide, nxt, [0, 3] if op["bad"] == "start" else [0])
+    if k in ("refused_set_guide_sparse", "refused_set_stop_seq"):
+        import types
+        t = 5 + op["at"]
+        dflt, off, tok, tgt, start, vocab = [0, 0], [0, 2, 3], [t, t + 1, t], [1, -1, 1], [0], VOCAB
+        if op["bad"] == "dead":                  # (a guide only: a stop automaton may hold such a state)
+            dflt, tgt = [0, -1], [1, -1, -1]
+        elif op["bad"] == "ascend":
+            tok = [t + 1, t, t]
+        elif op["bad"] == "row_off":             # row_off[n_states] != n_edges
+            off = [0, 2, 2]
+        elif op["bad"] == "start":
+            start = [0, 2]
+        elif op["bad"] == "dflt":
+            dflt = [0, 2]
+        elif k == "refused_set_guide_sparse":    # "vocab": the binding states the engine's vocabulary itself; a token outside it
+            tok = [t, VOCAB, t]
+        else:
+            vocab = VOCAB + 1
+        if k == "refused_set_guide_sparse":
+            return _setting(e.set_guide_sparse, dflt, off, tok, tgt, start)
+        return _setting(e.set_stop_sequences, types.SimpleNamespace(default=dflt, offsets=off, tokens=tok, targets=tgt, start=0, vocab_size=vocab), start)
+    if k == "refused_guide_starts":              # a loop op with one request more than the automaton has start states
+        return call(e, dict(op, op=op["kind"]), ref, prefix, env)
     if k == "read_gen_logprobs":
         got = e.read_gen_logprobs(env.get("cap"))
         return [tuple(np.ascontiguousarray(a).tobytes() for a in g) for g in got]
@@ -2082,11 +2948,15 @@ def call(e, op, ref, prefix=(), env=None):
             return e.generate_many_sampled(prompts, n_new, *sampler)
         if k == "generate_many_dense":
             return e.generate_many_dense(prompts, n_new, sampler, op["dense_min"])
-        if k == "generate_many_prefix":
-            return e.generate_many_prefix(prompts, n_new, stop, sampler)
         if k == "refused_stop":
             prompts[op["bad"]][-1] = VOCAB
-        return e.generate_many_stop(prompts, n_new, stop, sampler)
+        # the two loops with a device scheduler: the rows, the stats, and the whole output buffer with n_out -- -1 stands behind
+        # every request's last token
+        fn = e.generate_many_prefix if k == "generate_many_prefix" else e.generate_many_stop
+        buf, got, st = fn(prompts, n_new, stop, sampler, raw=True)
+        buf = [int(t) for t in buf]
+        offs = [sum(n_new[:r]) for r in range(len(n_new))]
+        return [buf[o:o + g] for o, g in zip(offs, got)], st, buf, [int(g) for g in got]
     if k in ("batch_prefill_slots", "refused_dense"):
         return e.batch_prefill_slots(op["slots"], [toks(p) for p in op["prompts"]], op["first"])
     if k in ("batch_copy_rows", "refused_prefix"):
@@ -2185,6 +3055,8 @@ class _Lane:
         m.touched = {}
         prefix = list(m.prefix)
         env = dict(top_k=m.k_top, pen=m.pen, cap=m.gen and m.gen["cap"], table=self.tables.get(i) if op["op"] == "set_logit_bias" and op["form"] != "off" else ([], None))
+        if op["op"] in GUIDE_SETTERS:                # the automaton of the op, from the reference alone (None: off)
+            env["auto"] = None if op["form"] == "off" else self.tables.stop(i) if op["op"] == "set_stop_seq" else self.tables.guide(i)
         want = outcome(m, op, ref, prefix, env)
         got = outcome(self.e, op, ref, prefix, env)
         if refusal:
@@ -2233,6 +3105,16 @@ class _Lane:
         e, m = self.e, self.m
         got = (e.top_k, e.get_gen_logprobs(), tuple(e.get_penalties()), e.get_logit_bias())
         assert got == (m.k_top, m.genlp, m.pen, m.get_logit_bias()), f"the settings read back as {_short(got)}, the reference holds {_short((m.k_top, m.genlp, m.pen, m.get_logit_bias()))}"
+        # the getters of sections 2r to 2t.  The library reports the counts it holds (states, edges, start states; 0 for the form
+        # that is not set) and the binding answers with the copy its setter kept where they agree with it: what is compared here is
+        # those counts and that copy, not the device tables.  Where the counts disagree the binding raises, which fails here too
+        for name in ("get_guide", "get_guide_sparse", "get_stop_sequences"):
+            hold = getattr(m, name)()
+            try:
+                have = getattr(e, name)()
+            except RuntimeError as err:
+                raise AssertionError(f"{name} raises ({err}): the library holds other counts than the setter left; the reference holds {_short(hold)}") from None
+            assert same(have, hold), f"{name} reads back {_short(have)}, the reference holds {_short(hold)}"
         if op["op"] in MANY:
             self.last_read = None
             if m.gen is not None:

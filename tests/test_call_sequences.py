@@ -6,7 +6,12 @@ does not name with a copy taken before it, and the rows it fills with the oracle
 sequences to what they have to contain.
 The settings sequences (seq_model.SETTING_KINDS) put the engine-wide settings of sections 2m to 2q -- top_k, gen_logprobs, penalties,
 the logit-bias table -- among those calls: every loop op runs under the settings in force, its records are read and held to the
-reference behind it, and the four getters are compared after every op."""
+reference behind it, and the four getters are compared after every op.
+The guide sequences (seq_model.GUIDE_KINDS) add the dense guide of section 2r, the sparse guide of 2s and the stop automaton of 2t:
+every loop op runs under the automata in force -- tokens, n_out, the -1 fill behind the last token, the stats of
+q3_cols_schedule(prompt_len, n_emit), the records on the raw row and the rng state are the reference's -- the arrays grow behind
+cached plans, each guide form replaces the other under kept plans, the batched state is started over under both, and the three
+getters are compared after every op."""
 import numpy as np
 import pytest
 
@@ -90,3 +95,28 @@ def test_settings_on_two_engines_interleaved_op_by_op(q3, models):
     seed = sm.SETTING_SEEDS[-1]
     with engine(q3, path) as a, engine(q3, path, graph=False) as b:
         sm.run([a, b], sm.make_settings_sequence(seed), ref, seed)
+
+
+@pytest.mark.parametrize("graph", [True, False], ids=["graph", "eager"])
+@pytest.mark.parametrize("seed", sm.GUIDE_SEEDS)
+def test_guide_sequence(q3, models, seed, graph):
+    path, ref = models()
+    with engine(q3, path, graph) as t:
+        sm.run(t, sm.make_guide_sequence(seed), ref, seed)
+
+
+def test_guide_sequence_on_an_edge_valued_checkpoint(q3, models):
+    """tied classifier rows meet the -inf keys of the mask: among the allowed tokens the ties go to the higher index, and a row with
+    no finite entry commits V - 1"""
+    path, ref = models("all")
+    with engine(q3, path) as t:
+        sm.run(t, sm.make_guide_sequence(sm.GUIDE_EDGE_SEED), ref, sm.GUIDE_EDGE_SEED)
+
+
+def test_guides_on_two_engines_interleaved_op_by_op(q3, models):
+    """the guide and the stop automaton are an engine's own: the same guide sequence on two engines of one process, one with graphs
+    and one without"""
+    path, ref = models()
+    seed = sm.GUIDE_SEEDS[-1]
+    with engine(q3, path) as a, engine(q3, path, graph=False) as b:
+        sm.run([a, b], sm.make_guide_sequence(seed), ref, seed)

@@ -625,3 +625,365 @@ def settings_first_visible(leak, ops):
     if leak == "genlp_penalised":        # the first loop op with records under penalties or a table: its sums are the adjusted row's
         return next((i for i, o in enumerate(ops) if o["op"] in sm.MANY and info[i]["st"]["genlp"] >= 0 and {"pen", "bias"} & set(info[i]["on"])), None)
     return None
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the guide dimension (include/qwen3_hip.h sections 2r to 2t): seq_model.GUIDE_KINDS among the kinds above
+# ---------------------------------------------------------------------------------------------------------------------------------
+SETTING_DIGESTS = {     # sha256 of repr(make_settings_sequence(seed)), taken on the commit in front of the guide dimension
+    31: "228ab07a8d31334a95b12e9c3d5895505e6bba3a771efbcbd0f3c992d7278488", 32: "c85babe5281ba38e66b1917b2c46f49155e3a40453ce7b5e488fd79182f4babb",
+    33: "3593a99e74f5da32f61ffa01c24124385b1bdaf7e35395ef4db19ff994d0d49f", 34: "253ed416273c314674b3216bf10a065e21ef91c71b122a290e536b7e3a65f746",
+    35: "648d86aa2b4ad152984d5d38e53731c997bcc037775d8c5da23a92a9bcfe443f", 36: "4c2e186cf8db4b951808fdb7d3a91f7e76aa8c3d163248eab8987cc50d8dfb5c",
+}
+GUIDED = ("guide", "stop")
+PLAIN = ("generate_many_greedy", "generate_many_sampled", "generate_many_dense")
+SCHED = ("generate_many_stop", "generate_many_prefix")
+
+
+@pytest.fixture(scope="module")
+def gsequences(q3):
+    return {seed: sm.make_guide_sequence(seed) for seed in sm.GUIDE_SEEDS}
+
+
+@pytest.fixture(scope="module")
+def gtables(gsequences, reference):
+    return {seed: sm.Tables(ops, reference) for seed, ops in gsequences.items()}
+
+
+def gwalk(ops):
+    """swalk, with the guide and the stop automaton: gform "dense" / "sparse" / None and guide = the form of the automaton in force,
+    stop = the form of the stop automaton in force ("off": none), gi / si = the setter ops that hold"""
+    out = swalk(ops)
+    for f in out:
+        s = f["st"]
+        f.update(gform=s["gform"], guide=ops[s["guide"]]["form"] if s["guide"] is not None else "off", gi=s["guide"],
+                 stop=ops[s["stop"]]["form"] if s["stop"] is not None else "off", si=s["stop"])
+        f["on"] = f["on"] + tuple(n for n in GUIDED if f[n] != "off")
+    return out
+
+
+def test_the_six_settings_sequences_are_what_they_were(ssequences, gsequences):
+    import hashlib
+    assert set(SETTING_DIGESTS) == set(sm.SETTING_SEEDS)
+    for seed, ops in ssequences.items():
+        assert hashlib.sha256(repr(ops).encode()).hexdigest() == SETTING_DIGESTS[seed], seed
+    assert not set(sm.GUIDE_KINDS) & set(sm.KINDS + sm.SETTING_KINDS) and len(sm.CAT) == 115 and len(sm.KINDS) == 45 and len(sm.SETTING_KINDS) == 13
+    assert 4 <= len(sm.GUIDE_SEEDS) <= 6 and not set(sm.GUIDE_SEEDS) & set(sm.SEEDS + sm.SETTING_SEEDS)
+    longest = max(len(ops) for ops in ssequences.values())
+    for seed, ops in gsequences.items():
+        assert ops == sm.make_guide_sequence(seed) and sm._guide_sequence(seed) == sm._guide_sequence(seed)     # deterministic
+        assert eval(repr(ops)) == ops                          # the literal of a failure message
+        assert all(o["op"] in sm.KINDS + sm.SETTING_KINDS + sm.GUIDE_KINDS for o in ops)
+        assert len(ops) <= longest, (seed, len(ops), longest)
+
+
+def test_the_guide_kinds_their_forms_and_refusals(gsequences, capsys):
+    seen = {k: set() for k in sm.GUIDE_KINDS}
+    pairs = set()
+    for ops in gsequences.values():
+        pairs |= sm.pairs_of(ops)
+        for o in ops:
+            if o["op"] in seen:
+                seen[o["op"]].add(o.get("form") or o.get("bad") or o.get("of"))
+    with capsys.disabled():
+        print("\nguide kinds: " + ", ".join(f"{k} {sum(o['op'] == k for ops in gsequences.values() for o in ops)}" for k in sm.GUIDE_KINDS))
+    assert seen["set_guide"] == set(sm.GUIDE_FORMS) and seen["set_guide_sparse"] == set(sm.SPARSE_FORMS) and seen["set_stop_seq"] == set(sm.STOP_FORMS)
+    assert {"off", "all", "trie", "cycle", "per", "big"} == set(sm.GUIDE_FORMS) and {"dflt", "half"} <= set(sm.SPARSE_FORMS)
+    assert {"hit1", "hit2", "hit3", "overlap", "never", "per", "any", "big", "off"} == set(sm.STOP_FORMS)
+    for k, vals in sm.GUIDE_REFUSALS.items():
+        assert seen[k] == set(vals), (k, seen[k])
+    assert {"dead", "start", "vocab"} <= set(sm.GUIDE_REFUSALS["refused_set_guide"]) and {"dead", "ascend", "row_off", "start", "vocab"} <= set(sm.GUIDE_REFUSALS["refused_set_guide_sparse"])
+    assert {"ascend", "row_off", "start", "vocab"} <= set(sm.GUIDE_REFUSALS["refused_set_stop_seq"])
+    assert seen["refused_guide_starts"] == {"dense", "sparse", "stop"}
+    missing = [(a, b) for a in sm.GUIDE_SETTERS for b in sm.MANY if (a, b) not in pairs] + [(b, a) for a in sm.GUIDE_SETTERS for b in sm.MANY if (b, a) not in pairs]
+    assert not missing, f"{len(missing)} (setter, loop kind) pairs never adjacent: {missing}"
+    # the big forms are big: the dense table has 1,024 states and more, the sparse form grows all three arrays over every small form
+    assert min(sm.GUIDE_BIG.values()) >= 1024 and min(s * k for s, k in sm.SPARSE_BIG.values()) > 2 * sm.VOCAB
+
+
+def test_every_loop_variant_under_every_guide_and_stop_form(gsequences, capsys):
+    ran = set()                     # (kind, sampled, (guide kind, form), stop form, the earlier settings that are on)
+    forms, hits = {}, {}
+    for seed, ops in gsequences.items():
+        built = {}
+        for op, f in zip(ops, gwalk(ops)):
+            if op["op"] not in sm.MANY:
+                continue
+            ran.add((op["op"], f["draw"], (f["gform"] or "off", f["guide"]), f["stop"], tuple(n for n in f["on"] if n in SETTINGS)))
+            for key in f["nd"]["forms"]:
+                at = (seed, f["epoch"]) + key
+                built[at] = built.get(at, 0) + 1
+        for at, n in built.items():
+            forms[at[2:6]] = forms.get(at[2:6], 0) + 1
+            if n >= 2:
+                hits[at[2:6]] = hits.get(at[2:6], 0) + 1
+    missing = []
+    for kind, sampled in sm.VARIANTS:
+        mine = {s[2:] for s in ran if s[:2] == (kind, sampled)}
+        alone = ([(("dense", f), "off", ()) for f in sm.GUIDE_FORMS[1:-1]] + [(("sparse", f), "off", ()) for f in sm.SPARSE_FORMS[1:-1]]
+                 + [(("off", "off"), f, ()) for f in sm.STOP_FORMS[1:-1]])
+        missing += [(kind, sampled, s) for s in alone if s not in mine]
+        # the forms "big" run where the arrays grow: the two guides under every variant, the stop automaton alone under the two loops
+        # that read it and beside the sparse guide under the three that do not
+        missing += [(kind, sampled, g, "big") for g in ("dense", "sparse") if not any(s[0] == (g, "big") for s in mine)]
+        missing += [(kind, sampled, "stop big") for _ in (0,) if not any(s[1] == "big" and (kind in PLAIN or s[0][0] == "off") for s in mine)]
+        missing += [(kind, sampled, "guide x stop") for _ in (0,) if not any(s[0][0] != "off" and s[1] != "off" and s[0][1] != "big" for s in mine)]
+        missing += [(kind, sampled, "guide x " + n) for n in SETTINGS if not any(s[0][0] != "off" and n in s[2] for s in mine)]
+    assert not missing, f"{len(missing)} (loop kind, sampled, state) never run: {missing[:10]}"
+    # the column plans by their key: under a guide the penalty axis reads 3 (dense) or 4 (sparse) whatever the table and the penalties,
+    # and a greedy plan has no top_k (as for the 27 earlier forms): 2 x 3 x 3 = 18 forms exist
+    exist = {(d, t, g, p) for d in (False, True) for t in (False, True) for g in range(3) for p in (3, 4) if d or not t}
+    guided = {k: n for k, n in forms.items() if k[3] >= 3}
+    with capsys.disabled():
+        print(f"\ncolumn-plan forms (draw, topk, genlp, pen) under a guide, with the (seed, epoch, width)s that run them: "
+              + ", ".join(f"{tuple(int(v) for v in k)}: {n}" for k, n in sorted(guided.items())))
+        print(f"{len(guided)} of the {len(exist)} forms that exist; not reached: {sorted(tuple(int(v) for v in k) for k in exist - set(guided))}")
+    assert len(exist) == 18 and set(guided) == exist
+    assert exist <= set(hits), f"forms never run a second time on a kept plan: {sorted(exist - set(hits))}"
+
+
+def test_guide_and_stop_transitions_under_kept_plans(gsequences, capsys):
+    found = {}
+    for seed, ops in gsequences.items():
+        info = gwalk(ops)
+        built, epoch, sched_ran = set(), 0, False
+        reuse_at, new_at, snap, sched_before = {}, {}, {}, {}
+        for i, (op, f) in enumerate(zip(ops, info)):
+            if f["epoch"] != epoch:
+                built, epoch, sched_ran = set(), f["epoch"], False
+            snap[i], sched_before[i] = set(built), sched_ran
+            if op["op"] in sm.MANY:
+                reuse_at[i], new_at[i] = bool(f["nd"]["forms"] & built), bool(f["nd"]["forms"] - built)
+                built |= f["nd"]["forms"]
+                sched_ran |= op["op"] in SCHED
+        for i, op in enumerate(ops[:-1]):
+            a, b = info[i], info[i + 1]
+            if op["op"] in ("set_guide", "set_guide_sparse"):
+                what = ("off->on" if a["gform"] is None and b["gform"] else "on->off" if a["gform"] and b["gform"] is None else
+                        None if a["gform"] is None else "on->other table" if a["gform"] == b["gform"] else f"{a['gform']}->{b['gform']}")
+                if what is None:
+                    continue
+                # the column plans of both neighbouring forms exist in the epoch (on either draw side)
+                both = any({sm.form_of(d, a["st"]), sm.form_of(d, b["st"])} <= {k[:4] for k in snap[i]} for d in (False, True))
+                end = next((j for j in range(i + 1, len(ops)) if ops[j]["op"] in ("set_guide", "set_guide_sparse", "batch_init")), len(ops))
+                loops = [j for j in range(i + 1, end) if j in reuse_at]
+                if both and any(reuse_at[j] for j in loops) and any(new_at[j] for j in loops):
+                    found.setdefault(("guide", what), []).append((seed, i))
+            elif op["op"] == "set_stop_seq":
+                what = "off->on" if a["stop"] == "off" != b["stop"] else "on->off" if a["stop"] != "off" == b["stop"] else "on->other" if a["stop"] != "off" else None
+                if what is None:
+                    continue
+                # no plan key changes with the stop automaton: the scheduler kernel does.  The epoch has run a loop with a device
+                # scheduler, and two more follow the switch: one on kept widths and one that builds a width (and captures its graph) while
+                # the scheduler kernel of the new setting is in force
+                end = next((j for j in range(i + 1, len(ops)) if ops[j]["op"] in ("set_stop_seq", "batch_init")), len(ops))
+                loops = [j for j in range(i + 1, end) if ops[j]["op"] in SCHED]
+                if sched_before[i] and len(loops) >= 2 and any(reuse_at[j] for j in loops) and any(new_at[j] for j in loops):
+                    found.setdefault(("stop", what), []).append((seed, i))
+    with capsys.disabled():
+        print("\nguide and stop transitions under kept plans, loop ops on kept widths and on new ones behind them: "
+              + ", ".join(f"{n} {w}: {len(v)}" for (n, w), v in sorted(found.items())))
+    for what in ("off->on", "on->other table", "dense->sparse", "sparse->dense", "on->off"):
+        assert len({s for s, _ in found.get(("guide", what), [])}) == len(gsequences), (what, found.get(("guide", what)))
+    for what in ("off->on", "on->other", "on->off"):
+        assert len({s for s, _ in found.get(("stop", what), [])}) == len(gsequences), (what, found.get(("stop", what)))
+
+
+def guide_needs(op, f, tables):
+    """what a loop op asks of the grow-only arrays of sections 2r to 2t (guide_call_begin, guide_sp_call_begin, stop_seq_call_begin)"""
+    need = {}
+    if f["gi"] is not None:
+        need.update(tables.guide(f["gi"]).sizes())
+    if f["si"] is not None and op["op"] in SCHED:
+        a, starts = tables.stop(f["si"])
+        need.update(stop_seq_dflt=a.default.size, stop_seq_off=a.default.size + 1, stop_seq_edges=max(a.tokens.size, 1), stop_seq_start=len(starts))
+    return need
+
+
+def test_the_guide_buffers_grow_twice_behind_cached_plans(gsequences, gtables, capsys):
+    """the rule of test_the_settings_buffers_grow_twice_behind_cached_plans for the arrays of the two guides and the stop automaton"""
+    for seed, ops in gsequences.items():
+        info = gwalk(ops)
+        needs = [guide_needs(op, f, gtables[seed]) if op["op"] in sm.MANY else {} for op, f in zip(ops, info)]
+        grown = {b: [] for b in sm.GUIDE_BUFFERS}
+        best, cap = {}, {}
+        cols_built, dense_built, cols_hit, dense_hit = set(), set(), False, False
+        last_epoch = 0
+        for i, f in enumerate(info):
+            epoch, nd = f["epoch"], f["nd"]
+            if epoch != last_epoch:
+                cap, cols_built, dense_built, cols_hit, dense_hit, last_epoch = {}, set(), set(), False, False, epoch
+            if nd is None:
+                continue
+            for b, n in needs[i].items():
+                if n > best.get(b, 0) and cap.get(b, 0) > 0 and cols_hit and dense_hit:
+                    later = [j for j in range(i + 1, len(ops)) if info[j]["epoch"] == epoch and ops[j]["op"] == ops[i]["op"] and 0 < needs[j].get(b, 0) < n]
+                    if later:
+                        grown[b].append(i)
+                best[b] = max(best.get(b, 0), n)
+                cap[b] = max(cap.get(b, 0), n)
+            if nd["need"].get("att_pf", 0) > cap.get("att_pf", 0):
+                dense_built, cap["att_pf"] = set(), nd["need"]["att_pf"]
+            plans = nd.get("forms") or nd["cols"]
+            cols_hit |= bool(plans & cols_built)
+            dense_hit |= bool(nd["dense"] & dense_built)
+            cols_built |= plans
+            dense_built |= nd["dense"]
+        with capsys.disabled():
+            print(f"\nseed {seed}: calls that grow an array of the guides or the stop automaton behind cached plans, a smaller one following: "
+                  + ", ".join(f"{b} {len(v)}" for b, v in grown.items()), end="")
+        for b, v in grown.items():
+            assert len(v) >= 2, f"seed {seed}: {b} grows {len(v)} times ({v})"
+
+
+def test_guide_and_stop_in_force_across_state_changes(gsequences):
+    across, quiet = {}, set()
+    for seed, ops in gsequences.items():
+        info = gwalk(ops)
+        for i, (op, f) in enumerate(zip(ops, info)):
+            k = op["op"]
+            # in force across the op: set in front of it, and a loop op that reads it follows under the very same setter op
+            idx = dict(guide="gi", stop="si")
+            on = [n for n in GUIDED if f[idx[n]] is not None and any(
+                o["op"] in (sm.MANY if n == "guide" else SCHED) and info[j][idx[n]] == f[idx[n]] for j, o in enumerate(ops[i + 1:], i + 1))]
+            if k == "batch_init" and i:
+                for name in on:
+                    across.setdefault((name, "batch_init"), set()).add("larger" if op["streams"] > f["before"] else "other" if op["streams"] != f["before"] else "same")
+            if k in ("set_sampler", "set_batch_sampler_on", "set_batch_sampler_off", "batch_reset_kv") + sm.SETTERS:
+                for name in on:
+                    across.setdefault((name, k), set()).add("x")
+            if len(on) == 2:
+                quiet.add(k)
+    for name in GUIDED:
+        assert {"larger", "other"} <= across.get((name, "batch_init"), set()), (name, across.get((name, "batch_init")))
+        for k in ("set_sampler", "set_batch_sampler_on", "set_batch_sampler_off", "batch_reset_kv"):
+            assert (name, k) in across, (name, k)
+    for k in sm.SETTERS:                                        # the guide holds across the setters of the four earlier settings
+        assert ("guide", k) in across, k
+    missing = [k for k in sm.KINDS if k not in sm.MANY and k not in quiet]
+    assert not missing, f"kinds that never run under a guide and a stop automaton: {missing}"
+
+
+def test_slots_are_reused_under_guides_and_stop_automata(gsequences, gtables, capsys):
+    reused = per_request = ended = 0
+    for seed, ops in gsequences.items():
+        for j, (op, f) in enumerate(zip(ops, gwalk(ops))):
+            if op["op"] not in sm.MANY:
+                continue
+            if f["guide"] != "off" and len(op["reqs"]) > f["streams"]:
+                reused += 1
+                per_request += f["guide"] in ("per", "big")
+            if f["stop"] != "off" and op["op"] in SCHED and len(op["reqs"]) > f["streams"]:
+                lens, n_new = sm.op_requests(op)
+                emit, by_seq = gtables[seed].emits(j), gtables[seed].seq_emits(j)
+                occ = sm.many_plan(lens, n_new, f["streams"], emit=emit)["occupants"]
+                # ended early by a completed sequence (not by a stop token in front of it), and not the slot's last occupant
+                ended += any(emit[r] == by_seq[r] < n_new[r] for rs in occ.values() for r in rs[:-1])
+    with capsys.disabled():
+        print(f"\nloop ops under a guide with more requests than slots: {reused}, {per_request} of them with one start per request; loops with a "
+              f"device scheduler under a stop automaton in which a completed sequence ends a request early and another takes its slot: {ended}")
+    assert reused >= 10 and per_request >= 4 and ended >= 6, (reused, per_request, ended)
+
+
+def test_the_guides_and_the_stop_automata_bind(gsequences, gtables, capsys):
+    """non-vacuity, from Reference alone"""
+    import stop_seq_ref
+    guided = else_branch = compete = early_min = per_guides = 0
+    fall_back = {}                                              # seed -> requests that complete B two tokens deep in A
+    stops = {}                                                  # (seed, set_stop_seq op) -> requests a sequence ends before their cap
+    for seed, ops in gsequences.items():
+        t = gtables[seed]
+        for j, (op, f) in enumerate(zip(ops, gwalk(ops))):
+            if op["op"] not in sm.MANY:
+                continue
+            if f["gi"] is not None:
+                gd = t.guide(f["gi"])
+                if f["guide"] == "per":          # one request unguided, at least two that start in different states
+                    per_guides += 1
+                    assert -1 in gd.starts and len(set(gd.starts) - {-1}) >= 2 and len(gd.starts) == len(op["reqs"]), (seed, j, gd.starts)
+                whole = t.rows(j, cut=False)
+                for r, (row, free) in enumerate(zip(whole, t.rows(j, guide=False, cut=False))):
+                    s = gd.start_of(r)
+                    if s < 0:
+                        assert row == free, f"seed {seed}, op {j}: start -1 and the guide changes request {r}"
+                        continue
+                    assert f["guide"] == "all" or row != free, f"seed {seed}, op {j}: the guide leaves request {r} alone"
+                    guided += 1
+                    for tok in row:
+                        else_branch += int(gd.row(s)[tok]) < 0
+                        s = gd.step(s, tok)
+            if f["si"] is not None and op["op"] in SCHED:
+                a, starts = t.stop(f["si"])
+                whole, n_new = t.rows(j, cut=False), sm.op_requests(op)[1]
+                stop_tokens = t.stop_tokens(j)
+                emit, cuts = t.emits(j), [len(sm.cut_at_stop(r, stop_tokens)) for r in whole]
+                per = [starts[0] if len(starts) == 1 else starts[r] for r in range(len(whole))]
+                by_seq = [1 if a.seqs is None else stop_seq_ref.n_emit_seqs(row, a.seqs) if s >= 0 else len(row) for row, s in zip(whole, per)]
+                assert by_seq == t.seq_emits(j)
+                if f["stop"] == "overlap":       # the request ends with B = [b, c] behind a, b of an A = [a, b, x]: the fall-back edge is taken
+                    three = [q for q in a.seqs if len(q) == 3]
+                    fall_back[seed] = fall_back.get(seed, 0) + sum(
+                        e == q < k and q >= 3 and any(row[q - 3:q - 1] == A[:2] and row[q - 2:q] in a.seqs for A in three)
+                        for row, e, q, k in zip(whole, emit, by_seq, n_new))
+                assert emit == [min(c, q) for c, q in zip(cuts, by_seq)]
+                n = sum(q < k and q <= c for q, k, c in zip(by_seq, n_new, cuts))
+                stops[(seed, f["si"])] = stops.get((seed, f["si"]), 0) + n
+                assert f["stop"] != "never" or by_seq == n_new, f"seed {seed}, op {j}: a sequence no request produces ends a request"
+                compete += any(c < k and q < k for c, q, k in zip(cuts, by_seq, n_new))
+                lists = t.get(f["st"]["table"])[0] if f["st"]["table"] is not None else []
+                until = max([e[2] for e in (lists[0] if len(lists) == 1 else [])] + [0])
+                early_min += any(q < until for q in by_seq)
+    by_form, vain = {}, []
+    for (seed, i), n in stops.items():
+        form = gsequences[seed][i]["form"]
+        if form != "never":
+            by_form[form] = by_form.get(form, 0) + (n > 0)
+            vain += [(seed, i, form)] * (n == 0)
+    with capsys.disabled():
+        print(f"\nguided requests: {guided}, every one differs from its unguided row (form all apart); else branch of the state step taken {else_branch} times; "
+              f"stop automata that end a request before its cap, by form: {by_form}; in vain: {vain}; ops with a stop token and a sequence competing "
+              f"in one request: {compete}; ops under min_tokens with a sequence that completes in front of it: {early_min}")
+        print(f"requests that end over the fall-back edge of an overlap automaton, per seed: {fall_back}; loop ops under per-request guide starts: {per_guides}")
+    assert guided and else_branch >= 1 and compete >= 1 and early_min >= 1 and per_guides >= 8
+    assert all(fall_back.get(seed, 0) >= 1 for seed in gsequences), fall_back
+    assert set(by_form) >= set(sm.STOP_FORMS[1:]) - {"never"} and all(n > 0 for n in by_form.values())
+    assert 10 * len(vain) <= len(stops), vain
+
+
+def test_the_harness_catches_the_guide_leaks(gsequences, reference, capsys):
+    import time
+    t0 = time.time()
+    for seed, ops in gsequences.items():
+        sm.run(sm.FakeEngine(reference), ops, reference, seed)
+    with capsys.disabled():
+        print(f"\n{sum(len(o) for o in gsequences.values())} ops on the fake engine in {time.time() - t0:.1f} s")
+    for leak in sm.GUIDE_LEAKS:
+        caught = {}
+        for seed, ops in gsequences.items():
+            try:
+                sm.run(sm.FakeEngine(reference, leak=leak), ops, reference, seed)
+            except AssertionError as err:
+                msg = str(err)
+                assert msg.startswith(f"seed {seed}, engine 0, op ") and "\nops = [" in msg
+                at = int(msg.split("op ")[1].split(" ")[0])
+                assert eval(msg.split("\nops = ")[1]) == ops[:at + 1]
+                caught[seed] = (at, ops[at]["op"])
+        with capsys.disabled():
+            print(f"leak {leak!r} first shows at (op, kind) per seed: {caught}")
+        assert len(caught) >= (4 if len(gsequences) >= 5 else len(gsequences)), f"leak {leak!r} shows in {len(caught)} of {len(gsequences)} seeds"
+        for seed, ops in gsequences.items():            # where the leaked state can be told from the ops alone: at that op, no later
+            first = guide_first_visible(leak, ops)
+            assert first is None or caught.get(seed, (None,))[0] == first, f"leak {leak!r}, seed {seed}: reported at {caught.get(seed)}, visible from op {first}"
+
+
+def guide_first_visible(leak, ops):
+    """the first op behind which the leaked state is observable through the API, for the leaks whose place the ops alone tell"""
+    info = gwalk(ops)
+    if leak in ("guide_init_dropped", "stop_init_dropped"):     # the getter behind the first q3_batch_init under the automaton
+        name = leak.split("_")[0]
+        return next((i for i, o in enumerate(ops) if o["op"] == "batch_init" and info[i][name] != "off"), None)
+    if leak == "guide_both_forms":       # q3_guide_get behind the first q3_guide_set_sparse over a dense guide
+        return next((i for i, o in enumerate(ops) if o["op"] == "set_guide_sparse" and o["form"] != "off" and info[i]["gform"] == "dense"), None)
+    if leak == "stop_in_plain_loops":    # the first loop without a device scheduler under an automaton made to end its requests
+        return next((i for i, o in enumerate(ops) if o["op"] in PLAIN and info[i]["stop"] in ("hit1", "hit2", "hit3", "any", "big")), None)
+    return None
