@@ -1225,6 +1225,59 @@ int q3_cols_schedule_stop_seq(const size_t* prompt_len, const size_t* n_new, siz
 int q3_op_stop_seq(const int32_t* dflt, const uint32_t* row_off, const q3_guide_edge* edges, size_t n_states, size_t n_edges, size_t vocab,
                    int32_t start_state, const int32_t* tokens, size_t n_tokens, size_t* n_emit, int32_t* end_state);
 
+/* ------------------------------------------------------------------------------------------------
+ * 2u. (behind 2t so that the earlier sections stay as they were.)  Prompt-lookup drafts inside the stop loop: idle columns verify
+ * tokens.  The loop of section 2h gives a decode-phase slot one column per pass (rule 2), and a pass runs the plan of the next width
+ * in {1, 2, 4, 8, 16, 32}: 5 decoding requests pay for 8 columns and throw 3 away.  Here the columns between a pass's base columns --
+ * those of rules 2 and 3 -- and its plan width carry drafted continuations of the decoding slots, at no extra pass over the weights.
+ *     draft      the rule of section 2c over S = the request's prompt ++ the tokens it has produced, with g = ngram: the continuation
+ *                of the latest earlier occurrence of S's last g tokens, at most draft_len tokens, at most n_new - produced - 1 (the
+ *                decode column itself produces one token), and never past the batch context.
+ *     rule 6     with base = the columns of rules 2 and 3 and W = max(the plan width that holds base, fill_width), the W - base spare
+ *                columns go to decode-phase slots in slot order, each taking at most its draft's length.  A slot's draft columns sit
+ *                directly behind its decode column at the positions that follow it, so the slot's columns stay one run of
+ *                consecutive positions (section 2e).  Draft columns emit nothing.  Rules 1 to 3 lay out the base columns as ever.
+ *     accept     behind the pass, per decode-phase slot: draft k stands while it equals the argmax of the column in front of it;
+ *                the argmax behind a standing draft is the request's next token.  The walk ends at a stop token and at n_new, and
+ *                rules 4 and 5 see the request advanced by 1 + the drafts that stood.
+ * A column reads rows 0 .. its own position of its slot, every key and value row of a pass is written before any is read, and a
+ * row a rejected draft left behind is written again before any later column reads it: no cache row is saved or restored.
+ * out_tokens AND n_out ARE BIT-IDENTICAL TO q3_generate_many_stop ON THE SAME REQUESTS AND STOP LIST, FOR ANY ngram, draft_len AND
+ * fill_width: a draft that stands is by construction the token the plain loop produces.  What changes is the number of passes.
+ * fill_width == 0: drafts ride only in columns that would have been pads, and every pass has the width the plain loop gives its base
+ * columns.  A larger fill_width lets a pass widen to that many columns to carry drafts.
+ * stats counts the passes run; live_columns includes the draft columns, decode_columns and prompt_columns do not.
+ * What runs (csrc/q3_lookup_dev.h).  Between two passes, on the stream: k_lookup_draft, one workgroup per KV slot -- the accept walk
+ * of the slot, then the search for its next draft over S where S lies in device memory (candidate starts from the end of S in
+ * LDS-staged chunks of Q3_LOOKUP_CHUNK; a per-wave and per-workgroup maximum of the matching start; the first chunk with a match
+ * ends the search) -- and k_cols_sched_lookup where k_cols_sched stands.  The drafts lie behind the call's prompts, where the turn
+ * kernel reads any prompt token: no plan, plan key or turn kernel changes, and one synchronisation per pass as in 2h.
+ * FIRST VERSION, GREEDY AND PLAIN ONLY.  Q3_ERR_UNSUPPORTED, naming the setting, and the engine stays usable: a sampling batch
+ * (q3_batch_sampler_set at temperature > 0); q3_sampler_penalties, q3_logit_bias_set, q3_guide_set or q3_guide_set_sparse in force;
+ * q3_gen_logprobs on; a stop automaton of q3_stop_seq_set; a resident prefix of q3_batch_prefix_set; a Q3_FLAG_FAST engine.
+ * ------------------------------------------------------------------------------------------------ */
+#define Q3_LOOKUP_DRAFT_MAX 31   /* = Q3_VERIFY_MAX - 1 */
+#define Q3_LOOKUP_CHUNK 4096
+
+typedef struct q3_lookup_stats {
+    uint64_t drafted;  /* draft columns put through a pass */
+    uint64_t accepted; /* ... of which stood */
+} q3_lookup_stats;
+
+/* The greedy q3_generate_many_stop with drafts.  Arguments and output layout are that call's without the sampler arrays; ngram >= 1,
+ * 1 <= draft_len <= Q3_LOOKUP_DRAFT_MAX, fill_width one of 0, 1, 2, 4, 8, 16, 32.  stats and lookup_stats may be NULL.
+ * Q3_ERR_ARG: ngram, draft_len or fill_width out of range; everything q3_generate_many_stop rejects.
+ * Q3_ERR_UNSUPPORTED: the list above.  Q3_ERR_INTERNAL: as for q3_generate_many_stop. */
+int q3_generate_many_lookup(q3_engine* e, const int32_t* prompts /* concatenated */, const size_t* prompt_len, const size_t* n_new,
+                            size_t n_requests, const int32_t* stop_tokens, size_t n_stop, int ngram, int draft_len, int fill_width,
+                            int32_t* out_tokens /* concatenated, n_new[r] each */, size_t* n_out /* [n_requests] */, q3_cols_stats* stats,
+                            q3_lookup_stats* lookup_stats);
+
+/* The device drafter alone, on one sequence: q3_lookup_draft computed by the search kernel of this section.  *len_out = the draft's
+ * length (0: none), draft_out (room for draft_len tokens) its tokens.  `device` as in q3_create.
+ * Q3_ERR_ARG: a null argument; n >= 2^31; ngram < 1; draft_len outside 1 .. Q3_LOOKUP_DRAFT_MAX. */
+int q3_op_lookup_draft(const int32_t* seq, size_t n, int ngram, int draft_len, int32_t* draft_out, int32_t* len_out, int device);
+
 #ifdef __cplusplus
 }
 #endif

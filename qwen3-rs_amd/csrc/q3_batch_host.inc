@@ -141,6 +141,9 @@ struct BatchCtx {
     DevMem<ColsStopDev> cols_stop;                      // device
     PinMem<SchedStatus> h_cols_stop;
     DevMem<int> cols_req;
+    // ... with prompt-lookup drafts (q3_generate_many_lookup): the per-slot draft records, the call's arguments and its counts;
+    // allocated by the first call.  The drafts themselves lie behind the call's prompts in cols_prompts
+    DevMem<LookupDev> lookup_dev;
     // dense blocks over the per-stream caches (q3_batch_prefill_slots / q3_generate_many_dense): scratch of prefill_block_cap()
     // columns beside the 32-column one, allocated on first use; plans by block width, kept (no graph: the launches are enqueued
     // as they are, like q3_prefill_batched's); the run tables of a call, grow-only

@@ -50,6 +50,7 @@
 #include "q3_guide_sparse.h"
 #include "q3_stop_seq.h"
 #include "q3_lookup.h"
+#include "q3_lookup_dev.h"
 
 namespace {
 
@@ -2308,6 +2309,7 @@ int q3_op_argmax(const float* logits, size_t n, int32_t* index, int device) {
 #include "q3_dense_host.inc"
 #include "q3_cols_host.inc"
 #include "q3_stop_host.inc"
+#include "q3_lookup_host.inc"
 #include "q3_prefix_host.inc"
 #include "q3_embed_host.inc"
 #include "q3_choice_host.inc"

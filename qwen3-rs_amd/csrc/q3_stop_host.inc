@@ -55,9 +55,19 @@ int stop_seq_call_begin(q3_engine* e) {
     return Q3_OK;
 }
 
-// rq: checked by cols_requests_check, with the prefix in front of the prompts as its pos_base
+// What q3_generate_many_lookup (section 2u) adds to the loop below, and its hooks (q3_lookup_host.inc)
+struct LookupArgs {
+    int ngram, draft_len, fill_width;
+    q3_lookup_stats* stats;             // filled by the time the loop returns Q3_OK
+};
+int lookup_call_begin(q3_engine* e, const LookupArgs& a, size_t n_prompt);
+int lookup_sched_launch(q3_engine* e, size_t n_prompt);
+int lookup_call_end(q3_engine* e, q3_lookup_stats* out);
+
+// rq: checked by cols_requests_check, with the prefix in front of the prompts as its pos_base.  lk: null, or the loop takes drafts:
+// greedy, plain form, no records, no stop automaton and no prefix (the entry point has refused the rest)
 int cols_generate_stop(q3_engine* e, const ColsRequests& rq, const int32_t* stop_tokens, size_t n_stop, int32_t* out_tokens, size_t* n_out,
-                       q3_cols_stats* stats) {
+                       q3_cols_stats* stats, const LookupArgs* lk = nullptr) {
     int rc;
     const bool draw = rq.draw();
     const size_t n_requests = rq.size();
@@ -76,7 +86,8 @@ int cols_generate_stop(q3_engine* e, const ColsRequests& rq, const int32_t* stop
     if (!b->cols_stop && (rc = b->cols_stop.alloc(1))) return rc;
     if (!b->h_cols_stop && (rc = b->h_cols_stop.alloc(1))) return rc;
     if ((rc = b->cols_req.grow(5 * n_requests, e->stream))) return rc;
-    if ((rc = b->cols_prompts.grow(rq.n_prompt, e->stream))) return rc;
+    // (under lk the slots' drafts lie behind the prompts, where the turn kernel reads them as it reads a prompt token)
+    if ((rc = b->cols_prompts.grow(rq.n_prompt + (lk ? (size_t)kColsMax * kLookupDraftMax : 0), e->stream))) return rc;
     if ((rc = b->cols_out.grow(rq.n_out, e->stream))) return rc;
     if (lp >= 0 && (rc = genlp_call_begin(e, lp, rq.n_out))) return rc;
     const int pen = e->pen_form();
@@ -104,6 +115,7 @@ int cols_generate_stop(q3_engine* e, const ColsRequests& rq, const int32_t* stop
     sched.o_off = dreq + 3 * n_requests;
     HIP_TRY(hipMemsetAsync(d, 0, sizeof(ColsStopDev), e->stream));
     HIP_TRY(hipMemcpyAsync(&d->sched, &sched, sizeof(ColsSched), hipMemcpyHostToDevice, e->stream));
+    if (lk && (rc = lookup_call_begin(e, *lk, rq.n_prompt))) return rc;
     if (draw && (rc = cols_sampler_upload(e, b->cols_slot_samp, d->aux, rq.temperature, rq.topp, rq.seeds, n_requests))) return rc;
     // the control block of the turn kernels: a table of one row, empty until k_cols_sched fills it
     ColsHost* h = b->h_cols;
@@ -122,7 +134,8 @@ int cols_generate_stop(q3_engine* e, const ColsRequests& rq, const int32_t* stop
     SchedStatus* hs = b->h_cols_stop;
     size_t passes = 0;
     for (;;) {
-        if (seq) rc = launch_now(e->stream, k_cols_sched_seq, dim3(1), dim3(64), 0, d, b->cols_ctl, (StopSeqDev*)b->stop_seq_dev, draw ? 1 : 0);
+        if (lk) rc = lookup_sched_launch(e, rq.n_prompt);
+        else if (seq) rc = launch_now(e->stream, k_cols_sched_seq, dim3(1), dim3(64), 0, d, b->cols_ctl, (StopSeqDev*)b->stop_seq_dev, draw ? 1 : 0);
         else rc = launch_now(e->stream, k_cols_sched, dim3(1), dim3(64), 0, d, b->cols_ctl, draw ? 1 : 0);
         if (rc) return rc;
         // the pass is set up by a launch of its own, like pass 0 of the kept loops (n_live is 0: nothing to commit)
@@ -141,6 +154,7 @@ int cols_generate_stop(q3_engine* e, const ColsRequests& rq, const int32_t* stop
     HIP_TRY(hipMemcpyAsync(out_tokens, b->cols_out, 4 * rq.n_out, hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipMemcpyAsync(got.data(), dreq + 4 * n_requests, 4 * n_requests, hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipMemcpyAsync(&st, &d->sched.stats, sizeof(q3_cols_stats), hipMemcpyDeviceToHost, e->stream));
+    if (lk && (rc = lookup_call_end(e, lk->stats))) return rc;
     HIP_TRY(hipStreamSynchronize(e->stream));
     if (st.passes != passes) return fail(Q3_ERR_INTERNAL, "the scheduler counted %llu passes, the host ran %zu", (unsigned long long)st.passes, passes);
     for (size_t r = 0; r < n_requests; ++r) n_out[r] = (size_t)got[r];

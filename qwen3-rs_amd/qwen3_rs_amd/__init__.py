@@ -12,7 +12,7 @@ from .engine import (Q3Error, ModelConfig, Transformer, TransformerBuilder, lib_
                      EMBED_L2, EMBED_PREFIX, CHOICE_PREFIX, CHOICE_PER_REQUEST, CHOICE_MAX, ScoreStats, SCORE_PREFIX, SCORE_DTYPE, score_pack,
                      SCORE_TOP_MAX, TOP_DTYPE, TOP_K_MAX, op_sample_top_k, BIAS_MAX, BIAS_ADD, BIAS_ALLOW, BIAS_DTYPE, GUIDE_MAX_STATES,
                      GUIDE_SPARSE_MAX_STATES, GUIDE_SPARSE_MAX_EDGES, EDGE_DTYPE, STOP_SEQ_MAX_STATES, STOP_SEQ_MAX_EDGES,
-                     cols_schedule_stop_seq)
+                     cols_schedule_stop_seq, LookupStats, LOOKUP_DRAFT_MAX, LOOKUP_CHUNK, op_lookup_draft)
 from .generation import (generate, chat_turn, generate_many, embed, common_prefix_len, TokenMetrics, sample_argmax, choose, rerank,
                          normalise_logits, RERANK_TEMPLATE, RERANK_INSTRUCTION, score, loglikelihood, perplexity, logprobs_of,
                          top_logprobs, top_logprobs_of, merge_logit_bias)
@@ -31,4 +31,4 @@ __all__ = ["GUIDE_MAX_STATES", "GUIDE_SPARSE_MAX_STATES", "GUIDE_SPARSE_MAX_EDGE
            "ScoreStats", "SCORE_PREFIX", "SCORE_DTYPE", "score_pack", "score", "loglikelihood", "perplexity", "logprobs_of",
            "SCORE_TOP_MAX", "TOP_DTYPE", "top_logprobs", "top_logprobs_of", "TOP_K_MAX", "op_sample_top_k",
            "STOP_SEQ_MAX_STATES", "STOP_SEQ_MAX_EDGES", "cols_schedule_stop_seq", "stops", "stop_automaton", "stop_automaton_from_strings",
-           "cut_at_stop"]
+           "cut_at_stop", "LookupStats", "LOOKUP_DRAFT_MAX", "LOOKUP_CHUNK", "op_lookup_draft"]

@@ -42,7 +42,10 @@ EXPORTED_SYMBOLS = [
     "q3_guide_set", "q3_guide_get", "q3_op_guide",
     "q3_guide_set_sparse", "q3_guide_get_sparse", "q3_op_guide_sparse",
     "q3_stop_seq_set", "q3_stop_seq_get", "q3_cols_schedule_stop_seq", "q3_op_stop_seq",
+    "q3_generate_many_lookup", "q3_op_lookup_draft",
 ]
+LOOKUP_DRAFT_MAX = 31    # Q3_LOOKUP_DRAFT_MAX (section 2u)
+LOOKUP_CHUNK = 4096      # Q3_LOOKUP_CHUNK
 GUIDE_MAX_STATES = 4096  # Q3_GUIDE_MAX_STATES (section 2r)
 GUIDE_SPARSE_MAX_STATES = 1 << 20   # Q3_GUIDE_SPARSE_MAX_STATES (section 2s)
 GUIDE_SPARSE_MAX_EDGES = 1 << 27    # Q3_GUIDE_SPARSE_MAX_EDGES
@@ -106,6 +109,17 @@ class ColsStats:
     live_columns: int
     prompt_columns: int
     decode_columns: int
+
+
+class _LookupStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("drafted", "accepted")]
+
+
+@dataclasses.dataclass(frozen=True)
+class LookupStats:
+    """q3_lookup_stats: the draft columns of a generate_many_lookup call and how many of them stood"""
+    drafted: int
+    accepted: int
 
 
 class _DenseStats(C.Structure):
@@ -285,6 +299,9 @@ def _bind(path: str) -> C.CDLL:
                                          C.POINTER(_DenseStats)]
     L.q3_generate_many_stop.argtypes = [C.c_void_p, i32p, szp, szp, sz, fp, fp, C.POINTER(C.c_uint64), i32p, sz, i32p, szp, C.POINTER(_ColsStats)]
     L.q3_cols_schedule_stop.argtypes = [szp, szp, sz, C.c_int, i32p, i32p, sz, i32p, sz, szp, szp, C.POINTER(_ColsStats)]
+    L.q3_generate_many_lookup.argtypes = [C.c_void_p, i32p, szp, szp, sz, i32p, sz, C.c_int, C.c_int, C.c_int, i32p, szp, C.POINTER(_ColsStats),
+                                          C.POINTER(_LookupStats)]
+    L.q3_op_lookup_draft.argtypes = [i32p, sz, C.c_int, C.c_int, i32p, i32p, C.c_int]
     L.q3_batch_copy_rows.argtypes = [C.c_void_p, C.c_int, i32p, C.c_int, sz, sz]
     L.q3_batch_prefix_set.argtypes = [C.c_void_p, i32p, sz]
     L.q3_batch_prefix_get.argtypes = [C.c_void_p, szp, i32p, sz]
@@ -441,6 +458,14 @@ def lookup_draft(seq, ngram: int, draft_len: int) -> List[int]:
     out = (C.c_int32 * max(1, draft_len))()
     k = load_library().q3_lookup_draft(_i32_array(seq), len(seq), ngram, draft_len, out)
     return [int(out[i]) for i in range(k)]
+
+
+def op_lookup_draft(seq, ngram: int, draft_len: int, device: int = 0) -> List[int]:
+    """lookup_draft computed by the search kernel of the batched loops (q3_op_lookup_draft): the same draft, from the device"""
+    out = (C.c_int32 * LOOKUP_DRAFT_MAX)()
+    k = C.c_int32(0)
+    _check(load_library().q3_op_lookup_draft(_i32_array(seq), len(seq), ngram, draft_len, out, C.byref(k), device))
+    return [int(out[i]) for i in range(k.value)]
 
 
 def lookup_trace(seq, n_corpus: int, ngram: int, draft_len: int) -> List[List[int]]:
@@ -902,6 +927,25 @@ class Transformer:
             return n_out
         rows, stats, out, got = self._generate_many(prompts, n_new, sampler, call)
         return (out, got, stats) if raw else (rows, stats)
+
+    # ---- prompt-lookup drafts in the stop loop (include/qwen3_hip.h section 2u)
+    def generate_many_lookup(self, prompts, n_new, stop_tokens=(), ngram: int = 3, draft_len: int = 8, fill_width: int = 0, raw: bool = False):
+        """The greedy generate_many_stop in which the spare columns of a pass verify prompt-lookup drafts of the decoding requests
+        (q3_generate_many_lookup): the same rows in fewer passes.  A draft is the continuation of the latest earlier occurrence
+        of the request's last ngram tokens in its prompt and output, at most draft_len (1 .. 31) tokens.  fill_width 0: drafts
+        ride only in columns that would be pads; 1, 2, 4, 8, 16 or 32: a pass may widen to that many columns to carry them.
+        Returns (rows, ColsStats, LookupStats); raw=True: (the output buffer, n_out per request, ColsStats, LookupStats).
+        The LookupStats of the last call also stay in self.last_lookup_stats."""
+        ls = _LookupStats()
+
+        def call(rq, smp, out, st):
+            stop, n_out = [int(t) for t in stop_tokens], _size_array([0] * len(prompts))
+            self._batch_rc(self._lib.q3_generate_many_lookup(*rq, _i32_array(stop), len(stop), int(ngram), int(draft_len), int(fill_width), out, n_out,
+                                                             st, C.byref(ls)))
+            return n_out
+        rows, stats, out, got = self._generate_many(prompts, n_new, None, call)
+        self.last_lookup_stats = LookupStats(ls.drafted, ls.accepted)
+        return (out, got, stats, self.last_lookup_stats) if raw else (rows, stats, self.last_lookup_stats)
 
     # ---- a shared prompt prefix (include/qwen3_hip.h section 2i)
     def batch_copy_rows(self, src_slot: int, dst_slots, first_pos: int, n_rows: int):

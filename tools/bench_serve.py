@@ -60,6 +60,16 @@ over the full vocabulary that never matches: (b) - (a) over the passes is what k
 automaton of token sequences that ends the requests where the stop set ends them, with n_stop == 0, against the loop at the cap plus
 the host cut.  Also: the automaton's states, edges and bytes, and the host time of stop_automaton_from_strings.  Writes
 <out>/stop_seq.json and <out>/stop_seq.md.
+
+    python tools/bench_serve.py --lookup 8 [--models qwen3-0.6b,qwen3-8b]
+
+Prompt-lookup drafts in the stop loop (section 2u).  Per model and for 4, 8 and 20 concurrent requests (as many slots; prompts of 64
+tokens, 128 new tokens, no stop token): q3_generate_many_stop and q3_generate_many_lookup(ngram 3, draft_len N) at fill_width 0 and 32,
+the three calls taken by turns, best of 5 rounds behind a warm-up round; the rows must be equal.  Reported: seconds and passes of
+each, the cost of a pass of each (seconds / passes), what a lookup pass costs over a plain pass, and the break-even accepted drafts
+per pass -- a lookup pass yields (decode columns + accepted) tokens, so it pays when accepted / pass exceeds decode columns per pass
+* (lookup pass cost / plain pass cost - 1).  The synthetic checkpoints cycle under greedy decoding: their acceptance says nothing
+about real text and is listed only to show what the passes carried.  Writes <out>/serve_lookup.json and <out>/serve_lookup.md.
 """
 import argparse
 import json
@@ -328,6 +338,79 @@ def worker_stop(name, ctx, ckpt_dir, seed):
            "at_cap": {"passes": st_a.passes, "seconds": dt_a}, "stop": {"passes": st_b.passes, "seconds": dt_b},
            "n_emit": {"passes": st_c.passes, "seconds": dt_c}, "per_pass_us": 1e6 * (dt_b - dt_c) / max(1, st_b.passes)}
     print("RESULT " + json.dumps(res))
+
+
+def worker_lookup(name, ctx, ckpt_dir, seed, draft_len):
+    import qwen3_rs_amd as q3
+    ck = q3.checkpoint
+    shape = ck.SHAPES[name]
+    path = os.path.join(ckpt_dir, f"{name}-seed{seed}.q3bin")
+    ck.ensure_synthetic_checkpoint(path, shape, seed=seed)
+    runs = []
+    with q3.TransformerBuilder(path).with_ctx_length(ctx).build() as t:
+        for n_req in (4, 8, 20):
+            t.batch_init(n_req, ctx)
+            prompts = [ck.iter_prompt_tokens(shape, seed + 50 + r, 64) for r in range(n_req)]
+            nnew = [128] * n_req
+            calls = {"plain": lambda: t.generate_many_stop(prompts, nnew, []),
+                     "fill0": lambda: t.generate_many_lookup(prompts, nnew, [], ngram=3, draft_len=draft_len, fill_width=0),
+                     "fill32": lambda: t.generate_many_lookup(prompts, nnew, [], ngram=3, draft_len=draft_len, fill_width=32)}
+            best, out = {k: float("inf") for k in calls}, {}
+            for rnd in range(6):                                       # round 0 builds the plans of every width
+                for k, call in calls.items():
+                    t0 = time.perf_counter()
+                    out[k] = call()
+                    if rnd:
+                        best[k] = min(best[k], time.perf_counter() - t0)
+            r = {"requests": n_req, "rows_equal": out["fill0"][0] == out["plain"][0] and out["fill32"][0] == out["plain"][0]}
+            for k in calls:
+                st = out[k][1]
+                r[k] = {"seconds": best[k], "passes": st.passes, "live_columns": st.live_columns, "decode_columns": st.decode_columns,
+                        "pass_us": 1e6 * best[k] / st.passes}
+                if k != "plain":
+                    ls = out[k][2]
+                    ratio = r[k]["pass_us"] / r["plain"]["pass_us"]
+                    r[k].update(drafted=ls.drafted, accepted=ls.accepted, over_plain_us=r[k]["pass_us"] - r["plain"]["pass_us"],
+                                break_even=st.decode_columns / st.passes * (ratio - 1.0))
+            runs.append(r)
+    print("RESULT " + json.dumps({"model": name, "ctx": ctx, "draft_len": draft_len, "runs": runs}))
+
+
+def main_lookup(a):
+    results = []
+    for name in a.models.split(","):
+        cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--worker", name, "--ctx", str(a.ctx),
+               "--ckpt-dir", a.ckpt_dir, "--seed", str(a.seed), "--lookup", str(a.lookup)]
+        p = subprocess.run(cmd, capture_output=True, text=True)
+        sys.stderr.write(p.stderr[-2000:])
+        if p.returncode != 0:
+            print(f"[bench_serve] {name}: exit status {p.returncode}; stopping here", file=sys.stderr)
+            break
+        results.append(json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")][-1][7:]))
+    os.makedirs(a.out, exist_ok=True)
+    with open(os.path.join(a.out, "serve_lookup.json"), "w") as f:
+        json.dump(results, f, indent=1)
+    lines = ["# Prompt-lookup drafts in the stop loop: what a pass costs", "",
+             "Written by `tools/bench_serve.py --lookup %d` (synthetic full-size checkpoints, one MI355X, context %d per slot): as many" % (a.lookup, a.ctx),
+             "slots as requests, prompts of 64 tokens, 128 new tokens, no stop token, ngram 3.  Wall time per call, `q3_generate_many_stop`",
+             "(plain) and `q3_generate_many_lookup` at fill_width 0 and 32 taken by turns, best of 5 rounds behind a warm-up round.",
+             "us per pass = seconds / passes, host synchronisation included.  over plain = a lookup pass less a plain pass: at fill_width 0",
+             "the two kernels between the passes (`k_lookup_draft`, `k_cols_sched_lookup` in the place of `k_cols_sched`), at 32 also the wider plan.",
+             "break-even = accepted drafts per pass above which the loop yields more tokens per second than the plain loop.",
+             "The checkpoints are synthetic and cycle under greedy decoding: drafted and accepted say what the passes carried, nothing about real text.", "",
+             "| model | requests | loop | passes | seconds | us per pass | over plain us | break-even accepted / pass | drafted | accepted | rows equal |",
+             "|---|---|---|---|---|---|---|---|---|---|---|"]
+    for res in results:
+        for r in res["runs"]:
+            for k in ("plain", "fill0", "fill32"):
+                d = r[k]
+                lines.append(f"| {res['model']} | {r['requests']} | {k} | {d['passes']} | {d['seconds']:.4f} | {d['pass_us']:.1f} | " +
+                             (f"{d['over_plain_us']:.1f} | {d['break_even']:.2f} | {d['drafted']} | {d['accepted']} | {r['rows_equal']} |" if k != "plain" else " | | | | |"))
+    if not results:
+        lines.append("not taken")
+    with open(os.path.join(a.out, "serve_lookup.md"), "w") as f:
+        f.write("\n".join(lines) + "\n")
+    return 0 if len(results) == len(a.models.split(",")) and all(r["rows_equal"] for res in results for r in res["runs"]) else 1
 
 
 def synthetic_token_bytes(vocab_size):
@@ -734,7 +817,13 @@ def main():
     ap.add_argument("--ab", help="with --stop-seq: a checkout of the commit before, its library built; (a) also runs there")
     ap.add_argument("--tree", help=argparse.SUPPRESS)                  # worker of --ab: the tree whose package and library run (a)
     ap.add_argument("--prefix", type=int, help="requests that share a prefix of this many tokens against the loops on the full prompts (appends to serve_cols.md)")
+    ap.add_argument("--lookup", type=int, help="prompt-lookup drafts of this many tokens in the stop loop against the plain loop (writes serve_lookup.md)")
     a = ap.parse_args()
+    if a.lookup is not None:
+        if a.worker:
+            worker_lookup(a.worker, a.ctx, a.ckpt_dir, a.seed, a.lookup)
+            return 0
+        return main_lookup(a)
     if a.prefix is not None:
         a.ctx = max(a.ctx, (a.prefix + 64 + 32 + 255) // 256 * 256)
         if a.worker:
