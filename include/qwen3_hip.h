@@ -396,7 +396,8 @@ int q3_generate_lookup_draw(q3_engine* e, const int32_t* corpus, size_t n_corpus
  * whose positions are not consecutive; a token outside the vocabulary; a position >= the batch context.
  * Q3_ERR_UNSUPPORTED: a Q3_FLAG_FAST engine (its block and decode kernels are not bit-equal to each other, as in section 2c);
  * a batch sampler set to a temperature > 0 (q3_batch_sampler_set); the shapes the short prefill block refuses ("needs the
- * per-kv-head attention kernel"). */
+ * per-kv-head attention kernel"): more than 7 query heads per kv head -- except 8 at head_dim 128 (Qwen3-32B), which run as two
+ * workgroups of 4 heads per kv group --, a head_dim that is no power of two in 16 .. 256, score rows beyond the LDS bound. */
 int q3_batch_step_cols(q3_engine* e, const int32_t* slots, const int32_t* tokens, const int32_t* pos, int n_cols,
                        float* logits_out /* [n_cols][vocab] or NULL */, int32_t* next_out /* [n_cols] or NULL */);
 
@@ -493,7 +494,7 @@ int q3_generate_many_sampled(q3_engine* e, const int32_t* prompts /* concatenate
  * 32-column scratch of q3_batch_init, is allocated by the first call that needs it and released with the batched state
  * (q3_batch_init starts it over); using it rebuilds none of the kept plans of sections 2b, 2e and 2f.  A block of 32 columns or
  * fewer is an ordinary column pass of its live columns (under a sampler every one with keep = 0); a shape the dense kernels do not
- * take (group size other than 64, head_dim other than 128, other than 2 or 4 query heads per kv head) packs with a cap of 32, so
+ * take (group size other than 64, head_dim other than 128, other than 2, 4, 5 or 8 query heads per kv head) packs with a cap of 32, so
  * every shape q3_batch_step_cols accepts works.
  * ------------------------------------------------------------------------------------------------ */
 typedef struct q3_dense_stats { uint64_t blocks, live_columns, pad_columns; } q3_dense_stats;

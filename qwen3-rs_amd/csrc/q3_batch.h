@@ -1043,6 +1043,14 @@ __global__ __launch_bounds__(kDgWaves * 64) void k_dgemm(const BGemmArgs a) {
 // kv_mul query heads (grouped-query sharing), 32 streams x 8 kv heads = 256 workgroups = one per CU.  Every
 // sum is walked in the reference order (layers.rs:346-419,495-506), so the result is bit-identical to k_attn in
 // reference-order mode; Q3_FLAG_FAST engines use this exact path too (exact is always admissible).
+// 8 query heads per kv head (head_dim 128: Qwen3-32B) run as TWO workgroups of 4 heads per kv group
+// (AttnArgs::head_parts = 2, grid.x = 2 x kv heads, honoured by the 4-head instantiations only): a 9-wave
+// workgroup is over the 512-thread bound, and with 4 score rows per workgroup the LDS bound allows the contexts
+// it allows for 4 heads.  Both parts stage the K / V chunks (the second read hits L2).  In decode
+// (k_in_cache == 0) both form the position's key row in their own LDS and patch it into the staged chunk; part 0
+// alone stores it.  A part's staging load may touch cache row `pos` while that store is in flight, but the commit
+// skips that row, so the loaded value is never used.  This holds because no other workgroup of the launch reads
+// key row `pos` of that (slot, kv head): decode has one column per slot.
 // ------------------------------------------------------------------------------------------------
 constexpr int kGqaTch = 64;             // most timesteps staged per LDS round (one score dot per lane and chunk)
 constexpr int kGqaSlots = 8;            // float4 staging registers per thread (tch*hd/4 <= slots * threads); 16 made the kernel spill
@@ -1099,20 +1107,23 @@ __device__ __forceinline__ void gqa_store(const AttnArgs& a0, size_t sbi, int h,
     }
 }
 
-// HD_T / KVM_T: head_dim and kv_mul as compile-time constants for the listed models (128 with 2 or 4 query heads per kv
-// head) -- the staging index arithmetic (row = idx / (hd/4), ...) then folds to a pointer increment per slot; 0 = read
-// them from the arguments.
+// HD_T / KVM_T: head_dim and the workgroup's query heads as compile-time constants for the listed models (128 with 2 or 4
+// query heads per kv head, or 8 as two parts of 4) -- the staging index arithmetic (row = idx / (hd/4), ...) then folds to a
+// pointer increment per slot; 0 = read them from the arguments.
 template <int HD_T, int KVM_T>
 __global__ __launch_bounds__(512) void k_attn_gqa(const AttnArgs a0) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     GQA_STAMP(0);
+    // kv_mul: the query heads of THIS workgroup (the whole kv group; <128, 4>: or one of its two parts, AttnArgs::head_parts)
+    const bool split = KVM_T == 4 && a0.head_parts == 2;
     const int hd = HD_T ? HD_T : a0.hd, kv_mul = KVM_T ? KVM_T : a0.n_heads / a0.n_kv_heads, nw = kv_mul + 1;
-    const int kvh = blockIdx.x;
+    const int kvh = split ? blockIdx.x >> 1 : blockIdx.x;
+    const bool store_k = !split || (blockIdx.x & 1) == 0;      // every part forms the key row for its own LDS copy; part 0 stores it
     const size_t sbi = blockIdx.y;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nthr = nw * 64;
     const bool kwave = wave == kv_mul;
     const bool own_k = a0.k_in_cache == 0;         // decode: this kernel normalises + rotates the position's key row
-    const int h = kvh * kv_mul + (kwave ? 0 : wave);
+    const int h = blockIdx.x * kv_mul + (kwave ? 0 : wave);    // (parts are consecutive: first head = blockIdx.x * kv_mul)
     const size_t kvd = (size_t)a0.n_kv_heads * hd;
     const int ast = gqa_att_stride(a0.seq_len);
     const int kld = hd + kKPad;
@@ -1181,7 +1192,7 @@ __global__ __launch_bounds__(512) void k_attn_gqa(const AttnArgs a0) {
     wave_lds_sync();
     if (!kwave || own_k) wave_norm_rope(kwave ? k_s : q_s + wave * hd, raw_w, sq + wave * hd, rr, hd, 1);   // layers.rs:346-372
     __syncthreads();
-    if (kwave && own_k) {                                   // K is normalised + rotated in place in the cache
+    if (kwave && own_k && store_k) {                        // K is normalised + rotated in place in the cache
         float* krow = key_cache + (size_t)pos * kvd + (size_t)kvh * hd;
         for (int i = lane; i < hd; i += 64) krow[i] = k_s[i];
     }
@@ -1326,7 +1337,8 @@ __global__ __launch_bounds__(512) void k_attn_gqa(const AttnArgs a0) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// k_attn_gqa with the roles split by wave (head_dim 128, KVM = 2 or 4 query heads per kv head; 512 threads): waves
+// k_attn_gqa with the roles split by wave (head_dim 128, KVM = 2 or 4 query heads per workgroup -- the kv group, or with
+// AttnArgs::head_parts = 2 one half of a group of 8, as in k_attn_gqa; 512 threads): waves
 // 0..KVM-1 own one query head each and do nothing but arithmetic -- the score dots, the softmax, the two V chains per lane
 // -- while the other 8-KVM waves only move data: the K (then V) chunks travel global -> registers -> one of TWO LDS tiles,
 // two chunks ahead of the arithmetic, with ONE barrier per chunk.  In k_attn_gqa every wave staged and then computed: at a
@@ -1348,13 +1360,16 @@ __global__ __launch_bounds__(kG2Threads) void k_attn_gqa2(const AttnArgs a0) {
     constexpr int NF4 = TCH * (hd / 4);                        // float4 per chunk
     constexpr int NSLOT = (NF4 + NST - 1) / NST;               // 8 (KVM 4) / 6 (KVM 2) staging registers per set
     constexpr int TILE = TCH * kld;
-    const int kvh = blockIdx.x;
+    // KVM: the query heads of THIS workgroup (the whole kv group; <4>: or one of its two parts, AttnArgs::head_parts)
+    const bool split = KVM == 4 && a0.head_parts == 2;
+    const int kvh = split ? blockIdx.x >> 1 : blockIdx.x;
+    const bool store_k = !split || (blockIdx.x & 1) == 0;      // every part forms the key row for its own LDS copy; part 0 stores it
     const size_t sbi = blockIdx.y;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const bool head = wave < KVM, kwave = wave == KVM, stager = wave >= KVM;
     const int sid = tid - KVM * 64;                            // staging thread index (stagers only)
     const bool own_k = a0.k_in_cache == 0;
-    const int h = kvh * KVM + (head ? wave : 0);
+    const int h = blockIdx.x * KVM + (head ? wave : 0);        // (parts are consecutive: first head = blockIdx.x * KVM)
     const size_t kvd = (size_t)a0.n_kv_heads * hd;
     const int ast = gqa_att_stride(a0.seq_len);
 
@@ -1424,7 +1439,7 @@ __global__ __launch_bounds__(kG2Threads) void k_attn_gqa2(const AttnArgs a0) {
         wave_lds_sync();
         if (head || own_k) wave_norm_rope(kwave ? k_s : q_s + wave * hd, raw_w, sq + wave * hd, rr, hd, 1);   // layers.rs:346-372
         wave_lds_sync();
-        if (kwave && own_k) {                                   // K is normalised + rotated in place in the cache
+        if (kwave && own_k && store_k) {                        // K is normalised + rotated in place in the cache
             float* krow = key_cache + (size_t)pos * kvd + (size_t)kvh * hd;
             krow[lane] = k_s[lane];
             krow[lane + 64] = k_s[lane + 64];
@@ -1630,14 +1645,21 @@ __device__ __forceinline__ float row_exact_sum(const float* row, int np) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// k_attn_pf2 (round 3; head_dim 128, KVM = 2 or 4 query heads per kv head): dense-prefill attention with the wave-uniform
+// k_attn_pf2 (round 3; head_dim 128, KVM = 2, 4 or 8 query heads per kv head): dense-prefill attention with the wave-uniform
 // operands in SCALAR registers and one wave per (position, head PAIR).  (Its first form, k_attn_pf -- q read from LDS, one wave
 // per position, the K row held in 128 registers -- ran 240 us per (layer, block) where this one runs 126; removed.)
 // One workgroup per kv head x NP consecutive positions; the K / V chunks (64 timesteps) are staged in LDS once for its
 // NP x KVM query rows; wave w owns position w / (KVM/2) and the two query heads of pair w % (KVM/2) -- 16 waves for
-// Qwen3-4B/8B (four per SIMD: the latency of one wave's scalar loads, barriers and softmax passes is another wave's
-// issue slot; with one wave per position the kernel ran two per SIMD and waited half of the time).  Arithmetic and order per
-// (head, position) are those of k_attn_gqa2 / k_attn / the reference (layers.rs:346-419,495-506): bit-identical results.
+// Qwen3-4B/8B with NP = 8 and for 8 heads per kv head (Qwen3-32B) with NP = 4 (four per SIMD: the latency of one wave's scalar
+// loads, barriers and softmax passes is another wave's issue slot; with one wave per position the kernel ran two per SIMD and
+// waited half of the time).  Arithmetic and order per (head, position) are those of k_attn_gqa2 / k_attn / the reference
+// (layers.rs:346-419,495-506): bit-identical results.
+// An odd KVM (5: Qwen3-14B) pairs its last head ACROSS POSITIONS: after the NP x (KVM/2) pair waves come NP / 2 waves that take
+// head KVM - 1 of positions 2x and 2x + 1 -- two q rows against the same K element and the same V element, which is what the
+// packed chains do anyway, so no lane does phantom work (NP = 4: 8 + 2 = 10 waves, 640 threads, a guarded seventh staging
+// slot).  The wave's rows a and b then have contexts np_a <= np_b (equal where a block repeats a run's last column): the wave
+// walks np_b, row a keeps its own maximum, sum and inv and is padded with +0.0 to the chunk end of np_b, and a wave whose
+// second position is past n_pos runs row a alone (row b's arithmetic runs on row a's memory, nothing of it is stored).
 //   * q is normalised + rotated by k_knorm_rope (one launch for the block's K and q heads) and stored pair-interleaved; the
 //     score loop reads it with s_load (constant address space) and forms the two heads' products with one v_pk_mul_f32
 //     (K element broadcast by op_sel) and extends the two chains with one v_pk_add_f32: 2 VALU per dim and pair, no LDS
@@ -1658,28 +1680,48 @@ typedef const float __attribute__((address_space(4))) kfloat;      // constant a
 constexpr int kWaitLgkm0 = 0xc07f;                                 // s_waitcnt lgkmcnt(0) only (vmcnt 63, expcnt 7)
 constexpr int kPfTch = 128;                                        // timesteps per staged chunk: two per lane in the score loop (half the barriers of 64)
 __host__ __device__ inline size_t attn_pf2_smem_bytes() { return 4 * (2 * (size_t)kPfTch * (kG2Hd + kKPad)) + 32 * 8; }
-__host__ __device__ constexpr int attn_pf2_threads(int kvm, int np) { return 64 * np * (kvm / 2); }
+// waves per workgroup: NP x KVM / 2 head pairs, and for an odd KVM one cross-position wave per two positions
+__host__ __device__ constexpr int attn_pf2_waves(int kvm, int np) { return np * (kvm / 2) + ((kvm & 1) ? np / 2 : 0); }
+__host__ __device__ constexpr int attn_pf2_threads(int kvm, int np) { return 64 * attn_pf2_waves(kvm, np); }
+// where k_attn_pf2 reads element d of query head h of column p in q_out: the heads of a pair interleaved element by element
+// ([column][pair][d][2]); the last head of an odd kv group is interleaved with the same head of the column pair's other column,
+// the 2 x hd floats of the pair spread over that head's two hd-float places, column p & ~1 first
+__device__ __forceinline__ size_t attn_pf2_q_index(int p, int h, int d, int n_heads, int kvm) {
+    constexpr int hd = kG2Hd;
+    if (!(kvm & 1)) return ((size_t)p * n_heads + (size_t)(h & ~1)) * hd + 2 * d + (h & 1);
+    const int g = h / kvm, j = h - g * kvm;
+    if (j < kvm - 1) return ((size_t)p * n_heads + (size_t)(g * kvm + (j & ~1))) * hd + 2 * d + (j & 1);
+    const int e = 2 * d + (p & 1);
+    return ((size_t)((p & ~1) + (e >= hd ? 1 : 0)) * n_heads + (size_t)h) * hd + (e & (hd - 1));
+}
 
 template <int KVM, int NP>
-__global__ __launch_bounds__(64 * NP * (KVM / 2), NP * (KVM / 2) / 4) void k_attn_pf2(const AttnArgs a0) {
+__global__ __launch_bounds__(64 * attn_pf2_waves(KVM, NP), attn_pf2_waves(KVM, NP) / 4) void k_attn_pf2(const AttnArgs a0) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    constexpr int hd = kG2Hd, kld = hd + kKPad, TCH = kPfTch, TILE = TCH * kld;
-    constexpr int NPRW = KVM / 2, NW = NP * NPRW, NTHR = 64 * NW, NSL = TCH * (hd / 4) / NTHR;
+    constexpr int hd = kG2Hd, kld = hd + kKPad, TCH = kPfTch, TILE = TCH * kld, NF4 = TCH * (hd / 4);
+    constexpr bool ODD = (KVM & 1) != 0;
+    constexpr int NPRW = KVM / 2, NW = attn_pf2_waves(KVM, NP), NTHR = 64 * NW, NSL = (NF4 + NTHR - 1) / NTHR;
+    constexpr bool GUARD = NSL * NTHR != NF4;                      // 640 threads: the last staging slot is partly past the chunk
     constexpr int DS = 16, TS = 16;                                // dims per score stage, timesteps per V stage
-    static_assert(NSL >= 1 && hd % DS == 0 && TCH % TS == 0, "");
+    static_assert(NSL >= 1 && NW <= 16 && NP % 2 == 0 && hd % DS == 0 && TCH % TS == 0, "");
     float* tiles = (float*)smem_raw;                               // 2 x [TCH][kld]   (V: [TCH][hd])
     unsigned long long* etab = (unsigned long long*)(tiles + 2 * TILE);
     const int kvh = blockIdx.x;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int pw = wave / NPRW, pr = wave - pw * NPRW;             // position within the workgroup, head pair within the kv group
+    const bool xw = ODD && wave >= NP * NPRW;                      // cross-position wave: head KVM - 1 of positions pw, pw + 1
+    const int pw = xw ? 2 * (wave - NP * NPRW) : wave / NPRW;      // (first) position within the workgroup
+    const int pr = xw ? 0 : wave - pw * NPRW;                      // head pair within the kv group
     const int pi0 = blockIdx.y * NP;
     const int n_pos = a0.n_pos;
     const int pi = min(pi0 + pw, n_pos - 1);
+    const int pi_b = xw ? min(pi0 + pw + 1, n_pos - 1) : pi;       // row b's column
     const bool live = pi0 + pw < n_pos;                            // wave-uniform
+    const bool two = !xw || pi0 + pw + 1 < n_pos;                  // row b exists (else the wave runs row a alone)
     const size_t kvd = (size_t)a0.n_kv_heads * hd;
     const int ast = a0.att_stride;
-    const int pos = __builtin_amdgcn_readfirstlane(a0.st[pi].pos);
+    const int np_a = __builtin_amdgcn_readfirstlane(a0.st[pi].pos) + 1;
+    const int pos = xw ? __builtin_amdgcn_readfirstlane(a0.st[pi_b].pos) : np_a - 1;       // np_a <= np: the wave walks np
     const int pos_last = __builtin_amdgcn_readfirstlane(a0.st[min(pi0 + NP - 1, n_pos - 1)].pos);
     // Within a workgroup positions are non-decreasing and all of one slot: a block is one ascending run (q3_prefill_batched), or runs
     // of several slots that each start at a column that is a multiple of 8 >= NP, the columns up to the next run repeating the run's
@@ -1698,7 +1740,7 @@ __global__ __launch_bounds__(64 * NP * (KVM / 2), NP * (KVM / 2) / 4) void k_att
     auto issue = [&](const float* gbase, int t0) {
 #pragma unroll
         for (int u = 0; u < NSL; ++u) {
-            const int idx = tid + u * NTHR;
+            const int idx = GUARD ? min(tid + u * NTHR, NF4 - 1) : tid + u * NTHR;
             const int row = min(t0 + (idx >> 5), np_max - 1), c = idx & 31;
             sr[u] = *(const v4f*)(gbase + (size_t)row * kvd + 4 * c);
         }
@@ -1707,15 +1749,19 @@ __global__ __launch_bounds__(64 * NP * (KVM / 2), NP * (KVM / 2) / 4) void k_att
 #pragma unroll
         for (int u = 0; u < NSL; ++u) {
             const int idx = tid + u * NTHR;
-            *(v4f*)(tile + (idx >> 5) * ld + 4 * (idx & 31)) = sr[u];
+            if (!GUARD || idx < NF4) *(v4f*)(tile + (idx >> 5) * ld + 4 * (idx & 31)) = sr[u];
         }
     };
     issue(kbase, 0);
     const float scale = 1.0f / sqrtf((float)hd);                   // (head_dim as f32).sqrt().recip()
-    const int head0 = kvh * KVM + 2 * pr;                          // this wave's heads: head0, head0 + 1
-    float* rows = a0.att_global + ((size_t)pi * a0.n_heads + (size_t)head0) * ast;       // score rows: rows, rows + ast
-    // the pair's query rows, interleaved element by element: [d][2]
+    const int head0 = kvh * KVM + (xw ? KVM - 1 : 2 * pr);         // this wave's heads: head0, head0 + 1 (cross-position wave: head0 twice)
+    const int head_b = xw ? head0 : head0 + 1;
+    float* rows = a0.att_global + ((size_t)pi * a0.n_heads + (size_t)head0) * ast;       // score rows a and b (pair waves: rows + ast)
+    float* rows_b = a0.att_global + ((size_t)pi_b * a0.n_heads + (size_t)head_b) * ast;
+    // the pair's query rows, interleaved element by element: [d][2] (attn_pf2_q_index); the cross-position pair's second half lies in
+    // the next column's place (allocated even where that column is past the block: the scratch holds an even number of columns)
     kfloat* qk = (kfloat*)(unsigned long long)(a0.q_out + ((size_t)pi * a0.n_heads + (size_t)head0) * hd);
+    kfloat* qk_hi = xw ? (kfloat*)(unsigned long long)(a0.q_out + ((size_t)(pi + 1) * a0.n_heads + (size_t)head0) * hd) : qk + hd;
 
     // ---- scores: att[h][t] = (q_h . K[t]) * scale, one timestep per lane, the head pair as one packed chain   layers.rs:391-401
     float mx0 = -__builtin_inff(), mx1 = -__builtin_inff();
@@ -1736,7 +1782,7 @@ __global__ __launch_bounds__(64 * NP * (KVM / 2), NP * (KVM / 2) / 4) void k_att
             v4f kc[DS / 4], kn[DS / 4], lc[DS / 4], ln[DS / 4];
             auto ldq = [&](float (&q)[2 * DS], int bb) {
 #pragma unroll
-                for (int i = 0; i < 2 * DS; ++i) q[i] = qk[2 * DS * bb + i];
+                for (int i = 0; i < 2 * DS; ++i) q[i] = (ODD && bb >= hd / DS / 2) ? qk_hi[2 * DS * bb - hd + i] : qk[2 * DS * bb + i];
             };
             ldq(qc, 0);
 #pragma unroll
@@ -1780,20 +1826,11 @@ __global__ __launch_bounds__(64 * NP * (KVM / 2), NP * (KVM / 2) / 4) void k_att
                 }
             }
             if (it == 8) GQA_STAMP(10);
-            if (t < np) {
-                const float s0 = d.x * scale, s1 = d.y * scale;
-                rows[t] = s0;
-                rows[(size_t)ast + t] = s1;
-                mx0 = fmaxf(mx0, s0);                              // running row maxima stay in registers (no pass over the row)
-                mx1 = fmaxf(mx1, s1);
-            }
-            if (t1 < np) {
-                const float s0 = e.x * scale, s1 = e.y * scale;
-                rows[t1] = s0;
-                rows[(size_t)ast + t1] = s1;
-                mx0 = fmaxf(mx0, s0);
-                mx1 = fmaxf(mx1, s1);
-            }
+            // (row a ends at np_a <= np; a wave alone on row a stores nothing of row b, whose place is row a's)
+            if (t < np_a) { const float s0 = d.x * scale; rows[t] = s0; mx0 = fmaxf(mx0, s0); }       // running row maxima stay in registers
+            if (two && t < np) { const float s1 = d.y * scale; rows_b[t] = s1; mx1 = fmaxf(mx1, s1); }
+            if (t1 < np_a) { const float s0 = e.x * scale; rows[t1] = s0; mx0 = fmaxf(mx0, s0); }
+            if (two && t1 < np) { const float s1 = e.y * scale; rows_b[t1] = s1; mx1 = fmaxf(mx1, s1); }
         }
     }
     GQA_STAMP(1);
@@ -1806,19 +1843,20 @@ __global__ __launch_bounds__(64 * NP * (KVM / 2), NP * (KVM / 2) / 4) void k_att
     if (live) {
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // this wave's score stores have landed (it reads them back)
-        const int np64 = (np + TCH - 1) & ~(TCH - 1);
+        const int np64 = (np + TCH - 1) & ~(TCH - 1);            // the chunk end the WAVE walks: row a is padded that far too
 #pragma unroll 1
-        for (int h = 0; h < 2; ++h) {
-            float* row = rows + (size_t)h * ast;
+        for (int h = 0; h < (two ? 2 : 1); ++h) {
+            float* row = h ? rows_b : rows;
+            const int nph = h ? np : np_a;                         // this row's context
             const float m = group_max_f32(h ? mx1 : mx0, 64);
             {   // four exps per lane and step (their f64 chains interleave)
                 float xc[4], xn[4];
 #pragma unroll
-                for (int u = 0; u < 4; ++u) xc[u] = row[min(64 * u + lane, np - 1)];
+                for (int u = 0; u < 4; ++u) xc[u] = row[min(64 * u + lane, nph - 1)];
 #pragma unroll 1
-                for (int t0 = 0; t0 < np; t0 += 256) {
+                for (int t0 = 0; t0 < nph; t0 += 256) {
 #pragma unroll
-                    for (int u = 0; u < 4; ++u) xn[u] = row[min(t0 + 256 + 64 * u + lane, np - 1)];
+                    for (int u = 0; u < 4; ++u) xn[u] = row[min(t0 + 256 + 64 * u + lane, nph - 1)];
                     float ev[4], xx[4];
                     bool sp = false;
 #pragma unroll
@@ -1834,23 +1872,23 @@ __global__ __launch_bounds__(64 * NP * (KVM / 2), NP * (KVM / 2) / 4) void k_att
 #pragma unroll
                     for (int u = 0; u < 4; ++u) {
                         const int t = t0 + 64 * u + lane;
-                        if (t < np) row[t] = ev[u];
+                        if (t < nph) row[t] = ev[u];
                         xc[u] = xn[u];
                     }
                 }
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            const float sum = row_exact_sum(row, np);
+            const float sum = row_exact_sum(row, nph);
             const float inv = 1.0f / sum;
 #pragma unroll 1
             for (int t0 = 0; t0 < np64; t0 += 512) {               // layers.rs:503-505; +0.0 past the context
                 float e[8];
 #pragma unroll
-                for (int u = 0; u < 8; ++u) e[u] = row[min(t0 + 64 * u + lane, np - 1)];
+                for (int u = 0; u < 8; ++u) e[u] = row[min(t0 + 64 * u + lane, nph - 1)];
 #pragma unroll
                 for (int u = 0; u < 8; ++u) {
                     const int t = t0 + 64 * u + lane;
-                    if (t < np64) row[t] = (t < np) ? e[u] * inv : 0.0f;
+                    if (t < np64) row[t] = (t < nph) ? e[u] * inv : 0.0f;
                 }
             }
         }
@@ -1871,10 +1909,11 @@ __global__ __launch_bounds__(64 * NP * (KVM / 2), NP * (KVM / 2) / 4) void k_att
         if (live && c0 < np) {
             const float* v0 = tile + lane;
             const float* prow = rows + c0;
+            const float* prow_b = rows_b + c0;
             v16f pc0, pc1, pn0, pn1;
             v2f vc[TS], vn[TS];
             asm volatile("s_load_dwordx16 %0, %1, 0x0" : "=s"(pc0) : "s"(prow) : "memory");
-            asm volatile("s_load_dwordx16 %0, %1, 0x0" : "=s"(pc1) : "s"(prow + (size_t)ast) : "memory");
+            asm volatile("s_load_dwordx16 %0, %1, 0x0" : "=s"(pc1) : "s"(prow_b) : "memory");
 #pragma unroll
             for (int u = 0; u < TS; ++u) vc[u] = (v2f){v0[u * hd], v0[u * hd + 64]};
 #pragma unroll
@@ -1883,7 +1922,7 @@ __global__ __launch_bounds__(64 * NP * (KVM / 2), NP * (KVM / 2) / 4) void k_att
                 __builtin_amdgcn_sched_barrier(0);
                 if (tb + TS < TCH) {
                     asm volatile("s_load_dwordx16 %0, %1, 0x0" : "=s"(pn0) : "s"(prow + tb + TS) : "memory");
-                    asm volatile("s_load_dwordx16 %0, %1, 0x0" : "=s"(pn1) : "s"(prow + (size_t)ast + tb + TS) : "memory");
+                    asm volatile("s_load_dwordx16 %0, %1, 0x0" : "=s"(pn1) : "s"(prow_b + tb + TS) : "memory");
 #pragma unroll
                     for (int u = 0; u < TS; ++u) vn[u] = (v2f){v0[(tb + TS + u) * hd], v0[(tb + TS + u) * hd + 64]};
                 }
@@ -1908,7 +1947,7 @@ __global__ __launch_bounds__(64 * NP * (KVM / 2), NP * (KVM / 2) / 4) void k_att
     if (live) {
         const float oa[4] = {o0.x, o0.y, 0.0f, 0.0f}, ob[4] = {o1.x, o1.y, 0.0f, 0.0f};
         gqa_store(a0, (size_t)pi, head0, hd, lane, oa);
-        gqa_store(a0, (size_t)pi, head0 + 1, hd, lane, ob);
+        if (two) gqa_store(a0, (size_t)pi_b, head_b, hd, lane, ob);
     }
     GQA_STAMP(4);
 }
@@ -1927,7 +1966,8 @@ __global__ __launch_bounds__(64) void k_knorm_rope(const AttnArgs a) {
     RopeRegs rr;
     if ((int)blockIdx.x >= a.n_kv_heads) {
         // query head (k_attn_pf2 only): normalised + rotated q goes to q_out, the two heads of a pair interleaved element by
-        // element ([position][pair][d][2]) so that the score loop fetches (q_h[d], q_h+1[d]) as one scalar pair
+        // element ([position][pair][d][2]) so that the score loop fetches (q_h[d], q_h+1[d]) as one scalar pair; the last head of an
+        // odd kv group pairs with the next column's (attn_pf2_q_index)
         const int h = (int)blockIdx.x - a.n_kv_heads;
         const float* qsrc = a.q + sbi * a.sb_q + (size_t)h * hd;
         rope_regs_load(rr, a.q_norm_w, a.rope + (size_t)pos * hd, hd);
@@ -1935,8 +1975,8 @@ __global__ __launch_bounds__(64) void k_knorm_rope(const AttnArgs a) {
         wave_lds_sync();
         wave_norm_rope(dst, raw, sq, rr, hd, 1);
         wave_lds_sync();
-        float* qrow = a.q_out + (sbi * a.n_heads + (size_t)(h & ~1)) * hd + (h & 1);
-        for (int i = lane; i < hd; i += 64) qrow[2 * i] = dst[i];
+        const int kvm = a.n_heads / a.n_kv_heads;
+        for (int i = lane; i < hd; i += 64) a.q_out[attn_pf2_q_index((int)sbi, h, i, a.n_heads, kvm)] = dst[i];
         return;
     }
     const int kvh = blockIdx.x;
@@ -1965,7 +2005,7 @@ __global__ __launch_bounds__(256) void k_knorm_rope_blk(const AttnArgs a, int n_
     float* raw = (float*)smem_raw;                                 // [64][132]
     float* fv = raw + kKnbVec * kKnbLd;                            // [64] RMSNorm factors
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int hs_n = a.n_kv_heads + (with_q ? a.n_heads : 0);
+    const int hs_n = a.n_kv_heads + (with_q ? a.n_heads : 0), kvm = a.n_heads / a.n_kv_heads;
     const long nvec = (long)n_pos * hs_n;
     const long v0 = (long)blockIdx.x * kKnbVec;
     auto vec_src = [&](long v, int& p, int& hs) -> const float* {
@@ -2030,9 +2070,11 @@ __global__ __launch_bounds__(256) void k_knorm_rope_blk(const AttnArgs a, int n_
         const float* src = raw + (size_t)vl * kKnbLd;
         float* dst_lo;
         int dstep;
+        const int h = hs - a.n_kv_heads;
+        const bool is_x = is_q && (kvm & 1) && h % kvm == kvm - 1; // last head of an odd kv group: interleaved across two columns
         if (is_q) {
-            const int h = hs - a.n_kv_heads;
             dst_lo = a.q_out + ((size_t)p * a.n_heads + (size_t)(h & ~1)) * hd + (h & 1);     // pair-interleaved: [d][2]
+            if (kvm & 1) dst_lo = a.q_out + attn_pf2_q_index(p, h, 0, a.n_heads, kvm);
             dstep = 2;
         } else {
             dst_lo = a.key_cache + col_slot_of(a.col_slot, (size_t)p) * a.sb_kv + (size_t)pos * ((size_t)a.n_kv_heads * hd) + (size_t)hs * hd;
@@ -2046,8 +2088,9 @@ __global__ __launch_bounds__(256) void k_knorm_rope_blk(const AttnArgs a, int n_
             const float c = cs[2 * i], sn = cs[2 * i + 1];
             const float a0 = xv * c, b0 = yv * sn;
             const float a1 = xv * sn, b1 = yv * c;
+            float* d_hi = is_x ? a.q_out + attn_pf2_q_index(p, h, i + half, a.n_heads, kvm) : dst_lo + (size_t)dstep * (i + half);
             dst_lo[(size_t)dstep * i] = a0 - b0;                   // layers.rs:181-182
-            dst_lo[(size_t)dstep * (i + half)] = a1 + b1;
+            *d_hi = a1 + b1;
         }
     }
 }

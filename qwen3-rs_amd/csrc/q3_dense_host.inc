@@ -79,7 +79,7 @@ int dense_pack_check(const size_t* run_len, size_t n_runs, int block_cap) {
 bool dense_capable(const q3_engine* e) {
     const q3_config& c = e->cfg;
     const int kv_mul = c.n_heads / c.n_kv_heads;
-    return c.group_size == 64 && c.head_dim == kG2Hd && (kv_mul == 2 || kv_mul == 4);
+    return c.group_size == 64 && attn_pf2_shape_ok(c.head_dim, kv_mul);
 }
 // columns per block: Q3_PREFILL_M as for q3_prefill_batched; a shape the dense kernels refuse is walked 32 columns at a time.
 // Read once per batched state, by its first dense call: every later call packs for the width the scratch was (or will be)

@@ -105,6 +105,9 @@ struct AttnArgs {
     // column pass (q3_batch_step_cols): column -> KV slot of the batched state, [columns] on the device.  Only the cache base goes
     // through it (slot * sb_kv); q, k_raw, xb, the packed activations and State stay indexed by column.  nullptr: column = slot.
     const int* col_slot;
+    // k_attn_gqa<128, 4> / k_attn_gqa2<4>: 2 = two workgroups per kv group of 8 query heads, 4 consecutive heads each
+    // (grid.x = 2 * n_kv_heads).  0 or 1: one workgroup per kv group.  No other value, and no other instantiation reads it.
+    int head_parts;
 };
 // the KV slot of column sb
 __device__ __forceinline__ size_t col_slot_of(const int* __restrict__ table, size_t sb) { return table != nullptr ? (size_t)table[sb] : sb; }

@@ -68,19 +68,26 @@ BGemmFn pick_dgemm(int ng, int& depth) {
     depth = ng % 16 == 0 ? 16 : (ng % 8 == 0 ? 8 : 0);
     return depth == 16 ? (BGemmFn)k_dgemm<16> : (depth == 8 ? (BGemmFn)k_dgemm<8> : nullptr);
 }
-// per-kv-head decode attention: k_attn_gqa2 (staging and arithmetic on separate waves; head_dim 128, 2 or 4 query heads per kv head)
-// or k_attn_gqa, specialised for head_dim 128 with the same two ratios
+// per-kv-head decode attention: k_attn_gqa2 (staging and arithmetic on separate waves; head_dim 128, 2 or 4 query heads per workgroup)
+// or k_attn_gqa, specialised for head_dim 128 with the same two counts.  kvm: the query heads of one workgroup (attn_head_parts)
 AttnFn attn_gqa_fn(bool gqa2, int hd, int kvm) {
     if (gqa2) return kvm == 4 ? (AttnFn)k_attn_gqa2<4> : (AttnFn)k_attn_gqa2<2>;
     if (hd == 128 && kvm == 4) return (AttnFn)k_attn_gqa<128, 4>;
     if (hd == 128 && kvm == 2) return (AttnFn)k_attn_gqa<128, 2>;
     return (AttnFn)k_attn_gqa<0, 0>;
 }
-// dense prefill attention: query heads per kv head (2 | 4) x positions per workgroup (4 | 8)
+// workgroups per kv group of the per-kv-head kernels: 8 query heads per kv head at head_dim 128 run as two parts of 4
+int attn_head_parts(int hd, int kv_mul) { return hd == kG2Hd && kv_mul == 8 ? 2 : 1; }
+// dense prefill attention: query heads per kv head (2 | 4 | 5 | 8) x positions per workgroup (4 | 8; 2 | 4 for 8 heads: at most 16
+// waves; 4 for 5 heads: 10 waves, the fifth head paired across positions)
 AttnFn attn_pf2_fn(int kvm, int np) {
+    if (kvm == 5) return (AttnFn)k_attn_pf2<5, 4>;
+    if (kvm == 8) return np == 4 ? (AttnFn)k_attn_pf2<8, 4> : (AttnFn)k_attn_pf2<8, 2>;
     if (np == 8) return kvm == 4 ? (AttnFn)k_attn_pf2<4, 8> : (AttnFn)k_attn_pf2<2, 8>;
     return kvm == 4 ? (AttnFn)k_attn_pf2<4, 4> : (AttnFn)k_attn_pf2<2, 4>;
 }
+// the shapes k_attn_pf2 takes
+bool attn_pf2_shape_ok(int hd, int kv_mul) { return hd == kG2Hd && (kv_mul == 2 || kv_mul == 4 || kv_mul == 5 || kv_mul == 8); }
 
 // ---- the record launches (q3_score.h, q3_score_top.h): what q3_score_many / q3_score_top_many enqueue behind the classifier of a
 // chunk and what a plan with records holds in front of its turn kernel.
@@ -536,11 +543,13 @@ struct PlanBuilder {
         a.col_slot = sc.col_slot;
         a.tch = att_tch < attn_tch(hd) ? att_tch : attn_tch(hd);
         const int kv_mul = c.n_heads / c.n_kv_heads;
-        const bool gqa = kv_mul <= 7 && hd <= 256 && (hd & (hd - 1)) == 0 && hd >= 16 &&
-                         attn_gqa_smem_bytes(hd, kv_mul, S) <= 150 * 1024 && dev_knob("Q3_BATCH_ATT_GQA", 1);
-        // dense prefill, head_dim 128 with 2 or 4 query heads per kv head: k_attn_pf2 (Q3_PREFILL_ATT_PF=0: k_attn_gqa2)
-        const bool use_pf = dense && hd == kG2Hd && (kv_mul == 2 || kv_mul == 4) && sc.att_pf != nullptr && dev_knob("Q3_PREFILL_ATT_PF", 1);
-        if (slotpf && !use_pf) return fail(Q3_ERR_UNSUPPORTED, "a dense block over the slots needs k_attn_pf2 (head_dim 128, 2 or 4 query heads per kv head)");
+        // a workgroup of the per-kv-head kernels takes the kv group's heads, at most 7 -- or 4 of 8 (head_dim 128: two parts per group)
+        const int parts = attn_head_parts(hd, kv_mul), wg_heads = kv_mul / parts;
+        const bool gqa = wg_heads <= 7 && hd <= 256 && (hd & (hd - 1)) == 0 && hd >= 16 &&
+                         attn_gqa_smem_bytes(hd, wg_heads, S) <= 150 * 1024 && dev_knob("Q3_BATCH_ATT_GQA", 1);
+        // dense prefill, head_dim 128 with 2, 4, 5 or 8 query heads per kv head: k_attn_pf2 (Q3_PREFILL_ATT_PF=0: k_attn_gqa2)
+        const bool use_pf = dense && attn_pf2_shape_ok(hd, kv_mul) && sc.att_pf != nullptr && dev_knob("Q3_PREFILL_ATT_PF", 1);
+        if (slotpf && !use_pf) return fail(Q3_ERR_UNSUPPORTED, "a dense block over the slots needs k_attn_pf2 (head_dim 128, 2, 4, 5 or 8 query heads per kv head)");
         if (block && !gqa && !use_pf) return fail(Q3_ERR_UNSUPPORTED, "batched prefill needs the per-kv-head attention kernel");
         if (block) {   // all key rows of the block enter the cache before any position attends
             if (use_pf) a.q_out = sc.qn;                        // the same launch normalises + rotates the block's query heads
@@ -564,8 +573,9 @@ struct PlanBuilder {
             a.group = G;
             *packed = true;
             a.stamps = stamp_cells();
-            // 8 positions per workgroup once that still gives every CU a workgroup
-            const int npw = (dev_knob("Q3_PREFILL_ATT_NP", 0) == 8 || (dev_knob("Q3_PREFILL_ATT_NP", 0) == 0 && (long)c.n_kv_heads * ((n + 7) / 8) >= e->n_cu)) ? 8 : 4;
+            // the larger workgroup (8 positions; 4 for 8 heads per kv head: 16 waves either way) once that still gives every CU a workgroup
+            const int np_hi = kv_mul == 8 ? 4 : 8, np_knob = dev_knob("Q3_PREFILL_ATT_NP", 0);
+            const int npw = kv_mul == 5 ? 4 : (np_knob == np_hi || (np_knob == 0 && (long)c.n_kv_heads * ((n + np_hi - 1) / np_hi) >= e->n_cu)) ? np_hi : np_hi / 2;
             return add(F_ATTN, attn_pf2_fn(kv_mul, npw), dim3((unsigned)c.n_kv_heads, (unsigned)((n + npw - 1) / npw)),
                        dim3((unsigned)attn_pf2_threads(kv_mul, npw)), attn_pf2_smem_bytes(), a);
         }
@@ -579,11 +589,12 @@ struct PlanBuilder {
                 *packed = true;
             }
             a.stamps = stamp_cells();
-            // head_dim 128 with 2 or 4 query heads per kv head: staging and arithmetic on separate waves, two LDS tiles
-            const bool gqa2 = hd == kG2Hd && (kv_mul == 2 || kv_mul == 4) && attn_gqa2_smem_bytes(kv_mul, S) <= 150 * 1024 && dev_knob("Q3_BATCH_ATT_GQA2", 1);
-            return add(F_ATTN, attn_gqa_fn(gqa2, hd, kv_mul), dim3((unsigned)c.n_kv_heads, (unsigned)n),
-                       dim3(gqa2 ? (unsigned)kG2Threads : (unsigned)(kv_mul + 1) * 64),
-                       gqa2 ? attn_gqa2_smem_bytes(kv_mul, S) : attn_gqa_smem_bytes(hd, kv_mul, S), a);
+            a.head_parts = parts;
+            // head_dim 128 with 2 or 4 query heads per workgroup: staging and arithmetic on separate waves, two LDS tiles
+            const bool gqa2 = hd == kG2Hd && (wg_heads == 2 || wg_heads == 4) && attn_gqa2_smem_bytes(wg_heads, S) <= 150 * 1024 && dev_knob("Q3_BATCH_ATT_GQA2", 1);
+            return add(F_ATTN, attn_gqa_fn(gqa2, hd, wg_heads), dim3((unsigned)(c.n_kv_heads * parts), (unsigned)n),
+                       dim3(gqa2 ? (unsigned)kG2Threads : (unsigned)(wg_heads + 1) * 64),
+                       gqa2 ? attn_gqa2_smem_bytes(wg_heads, S) : attn_gqa_smem_bytes(hd, wg_heads, S), a);
         }
         return add(F_ATTN, k_attn_streams, dim3((unsigned)c.n_heads, (unsigned)n), dim3(kWG), attn_smem_bytes(hd, a.att_global ? 0 : S, a.tch), a);
     }

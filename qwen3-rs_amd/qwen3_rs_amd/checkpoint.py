@@ -110,6 +110,14 @@ SHAPES: Dict[str, ModelShape] = {
     "qwen3-0.6b-dims-l2": ModelShape(1024, 3072, 2, 16, 8, 4096, 1024, 128, True, 64),
     "qwen3-4b-dims-l2": ModelShape(2560, 9728, 2, 32, 8, 16384, 4096, 128, True, 64),
     "qwen3-8b-dims-l2": ModelShape(4096, 12288, 2, 32, 8, 16384, 4096, 128, False, 64),
+    # the two larger dense Qwen3 models (HF config.json values): 5 and 8 query heads per kv head
+    "qwen3-14b": ModelShape(5120, 17408, 40, 40, 8, 151936, 40960, 128, False),
+    "qwen3-32b": ModelShape(5120, 25600, 64, 64, 8, 151936, 40960, 128, False),
+    "qwen3-14b-dims-l2": ModelShape(5120, 17408, 2, 40, 8, 16384, 4096, 128, False, 64),
+    "qwen3-32b-dims-l2": ModelShape(5120, 25600, 2, 64, 8, 16384, 4096, 128, False, 64),
+    # small shapes with their head ratios (10 / 2 and 16 / 2 heads)
+    "small-kvm5": ModelShape(512, 1024, 2, 10, 2, 2048, 512, 128, True, 64),
+    "small-kvm8": ModelShape(512, 1024, 2, 16, 2, 2048, 512, 128, True, 64),
 }
 
 

@@ -61,7 +61,7 @@ if __name__ == "__main__":
         for B in (3, 16, 32):
             ok = check(nm, B) and ok
     if os.environ.get("Q3_BATCH_TIMING", "1") != "0":
-        for nm in ("qwen3-8b-dims-l2",):
+        for nm in ("qwen3-8b-dims-l2", "qwen3-14b-dims-l2", "qwen3-32b-dims-l2"):
             for B in (16, 32):
                 timing(nm, B)
     sys.exit(0 if ok else 1)
