@@ -199,7 +199,12 @@ const char* q3_build_id(void);
  * Group sizes 512 and 1024 are single-stream only: q3_forward, q3_prefill, the greedy / sampled loops and the operator entry
  * points take them (any power of two in [16, 1024]), while q3_batch_init -- and with it everything of sections 2b to 2i,
  * q3_prefill_batched and q3_verify included -- answers Q3_ERR_UNSUPPORTED ("batched decode needs group_size 64, 128 or 256 ...")
- * and leaves the engine usable.  At 128 and 256 every batched block holds at most 32 columns (no dense kernels). */
+ * and leaves the engine usable.  At 128 and 256 every batched block holds at most 32 columns (no dense kernels).
+ * Any context up to the engine's seq_len is served.  Head_dim 128 with 2, 4, 5 or 8 query heads per kv head reads every K / V row
+ * once per kv group (per half group at 8) at every context: where the group's score rows pass the 150 KB LDS bound (about 6,900
+ * positions at 4 or 8 heads per kv head, 5,400 at 5, 16,400 at 2) they lie in global scratch.  Other layouts past their bound
+ * decode with one workgroup per query head (every K / V row read n_heads / n_kv_heads times), and their block plans (column passes,
+ * q3_verify, short prefill blocks) are refused as section 2e says. */
 int q3_batch_init(q3_engine* e, int max_streams, uint32_t ctx_len);
 
 /* One step: stream i runs forward(tokens[i], pos[i]).  logits_out ([n_streams][vocab_size], host) and
@@ -239,7 +244,8 @@ int q3_batch_read_state(q3_engine* e, int stream, int kind, size_t offset, size_
  * so every returned token is the token q3_generate_greedy returns, bit-identical logits and cache rows included.
  * Refused with Q3_ERR_UNSUPPORTED: a Q3_FLAG_FAST engine (its block and single-stream kernels are not bit-equal to each
  * other), an engine whose sampler is set to a temperature > 0 (these two names are greedy only: section 2d holds for any
- * sampler setting), and the shapes q3_batch_init refuses.  The packed weight copy of q3_prefill_batched is allocated on first use and shared with it and
+ * sampler setting), the shapes q3_batch_init refuses, and the shapes the short block refuses (section 2e, q3_batch_step_cols: a context
+ * is among them only outside head_dim 128 with 2, 4, 5 or 8 query heads per kv head).  The packed weight copy of q3_prefill_batched is allocated on first use and shared with it and
  * with q3_batch_init.  No environment variable: everything is an argument.
  * ------------------------------------------------------------------------------------------------ */
 #define Q3_VERIFY_MAX 32
@@ -397,7 +403,10 @@ int q3_generate_lookup_draw(q3_engine* e, const int32_t* corpus, size_t n_corpus
  * Q3_ERR_UNSUPPORTED: a Q3_FLAG_FAST engine (its block and decode kernels are not bit-equal to each other, as in section 2c);
  * a batch sampler set to a temperature > 0 (q3_batch_sampler_set); the shapes the short prefill block refuses ("needs the
  * per-kv-head attention kernel"): more than 7 query heads per kv head -- except 8 at head_dim 128 (Qwen3-32B), which run as two
- * workgroups of 4 heads per kv group --, a head_dim that is no power of two in 16 .. 256, score rows beyond the LDS bound. */
+ * workgroups of 4 heads per kv group --, a head_dim that is no power of two in 16 .. 256; and, at any layout but head_dim 128
+ * with 2, 4, 5 or 8 query heads per kv head, a context whose score rows (one of seq_len floats per query head of a kv group) pass
+ * the 150 KB LDS bound.  The listed layouts have no such bound: past it their score rows lie in global scratch (allocated by the
+ * first plan that needs them: 4 * max(max_streams, Q3_COLS_MAX) * n_heads * engine seq_len bytes, rounded up to 256 positions). */
 int q3_batch_step_cols(q3_engine* e, const int32_t* slots, const int32_t* tokens, const int32_t* pos, int n_cols,
                        float* logits_out /* [n_cols][vocab] or NULL */, int32_t* next_out /* [n_cols] or NULL */);
 

@@ -1601,6 +1601,307 @@ __global__ __launch_bounds__(kG2Threads) void k_attn_gqa2(const AttnArgs a0) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// k_attn_gqa2 with the score rows OUTSIDE LDS (head_dim 128, KVM = 2, 4 or 5 query heads per workgroup; 8 per kv head as two
+// parts of 4): for the contexts at which KVM rows of seq_len floats no longer fit beside the two tiles.  Its LDS use does not
+// depend on the context (attn_gqa2g_smem_bytes: 72 / 76 / 78 KB), so it serves every position up to seq_len.  The roles are
+// those of k_attn_gqa2 -- head waves 0..KVM-1 do arithmetic, the other 8 - KVM waves move K (then V) chunks of 64 timesteps
+// global -> registers -> one of two LDS tiles with one barrier per chunk -- and so are the prologue, the own_k case and the
+// epilogue.  What differs is where a head's row lives, AttnArgs::att_global + column * sb_att + head * att_stride:
+//   * scores: lane t of a head wave stores its chunk's score straight to the row (one coalesced 256-byte store per head and
+//     chunk) and keeps a running maximum in a register, so the row is not read back for the maximum;
+//   * softmax: the row becomes exp(x - m) in place, padded with +0.0 to a multiple of 256, as float4 per lane; the staging
+//     waves KVM .. 7 take every other 256-entry block of heads 0 .. 7 - KVM.  The head wave folds the reference-order sum out
+//     of the global row (seq_chain / seq_sum_blocks, the np < 256 split of k_attn_gqa) and scales the row in place;
+//   * values: with every V chunk the staging waves bring the chunk's 64 probabilities of each head into LDS (KVM x 64 floats
+//     beside each tile), and the head waves run k_attn_gqa2's two-chain fold on them.
+// A row is written and read by the waves of ONE workgroup (the two parts of a group of 8 own disjoint rows): every hand-off
+// is a __threadfence_block() (the writer's stores have completed) in front of the barrier.  At these sizes a row lives in
+// L2 / MALL; its traffic is a few passes of 4 * np bytes per head against 1,024 * np bytes of K and V per kv head.
+// Same operations in the same order as k_attn_gqa per (head, position): bit-identical results.
+// ------------------------------------------------------------------------------------------------
+__host__ __device__ inline size_t attn_gqa2g_smem_bytes(int kv_mul) {
+    return 4 * ((size_t)(kv_mul + 1) * kG2Hd * 3 + 64 + 2 * (size_t)kv_mul * kG2Tch + 2 * (size_t)kG2Tch * (kG2Hd + kKPad));
+}
+template <int KVM>
+__global__ __launch_bounds__(kG2Threads) void k_attn_gqa2g(const AttnArgs a0) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    static_assert(KVM == 2 || KVM == 4 || KVM == 5, "query heads per workgroup");
+    constexpr int hd = kG2Hd, kld = hd + kKPad, TCH = kG2Tch, nw = KVM + 1;
+    constexpr int NST = (kG2Waves - KVM) * 64;                 // staging threads
+    constexpr int NF4 = TCH * (hd / 4);                        // float4 per chunk
+    constexpr int NSLOT = (NF4 + NST - 1) / NST;               // 6 (KVM 2) / 8 (KVM 4) / 11 (KVM 5) staging registers per set
+    constexpr int TILE = TCH * kld, PT = KVM * TCH;
+    constexpr int NPF4 = PT / 4;                               // float4 of probabilities per chunk, one per staging thread
+    static_assert(NPF4 <= NST, "one probability float4 per staging thread");
+    // KVM: the query heads of THIS workgroup (the whole kv group; <4>: or one of its two parts, AttnArgs::head_parts)
+    const bool split = KVM == 4 && a0.head_parts == 2;
+    const int kvh = split ? blockIdx.x >> 1 : blockIdx.x;
+    const bool store_k = !split || (blockIdx.x & 1) == 0;      // every part forms the key row for its own LDS copy; part 0 stores it
+    const size_t sbi = blockIdx.y;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const bool head = wave < KVM, kwave = wave == KVM, stager = wave >= KVM;
+    const int sid = tid - KVM * 64;                            // staging thread index (stagers only)
+    const bool own_k = a0.k_in_cache == 0;
+    const int h = blockIdx.x * KVM + (head ? wave : 0);        // (parts are consecutive: first head = blockIdx.x * KVM)
+    const size_t kvd = (size_t)a0.n_kv_heads * hd;
+    const size_t ast = (size_t)a0.att_stride;
+
+    float* q_s = (float*)smem_raw;                 // [KVM][hd]
+    float* k_s = q_s + KVM * hd;                   // [hd]
+    float* raw = k_s + hd;                         // [nw][hd]
+    float* sq = raw + nw * hd;                     // [nw][hd]
+    float* red = sq + nw * hd;                     // [64]: per-head max
+    float* probs = red + 64;                       // 2 x [KVM][TCH]: the probabilities of the V chunk in each tile
+    float* tiles = probs + 2 * PT;                 // 2 x [TCH][kld]  (V: [TCH][hd])
+
+    const State* st = a0.st + sbi;
+    const int pos = __builtin_amdgcn_readfirstlane(a0.pos_override >= 0 ? a0.pos_override : st->pos);
+    const int np = pos + 1;
+    const float* qsrc = a0.q + sbi * a0.sb_q + (size_t)h * hd;
+    const float* ksrc = a0.k_raw + sbi * a0.sb_kraw + (size_t)kvh * hd;
+    const size_t kvs = col_slot_of(a0.col_slot, sbi) * a0.sb_kv;      // this column's KV slot
+    float* key_cache = a0.key_cache + kvs;
+    const float* kbase = key_cache + (size_t)kvh * hd;
+    const float* vbase = a0.value_cache + kvs + (size_t)kvh * hd;
+    float* row0 = a0.att_global + sbi * a0.sb_att + (size_t)(blockIdx.x * KVM) * ast;    // the workgroup's KVM rows
+    float* att = row0 + (size_t)(head ? wave : 0) * ast;
+    const float* cs = a0.rope + (size_t)pos * hd;
+    const int skip = own_k ? pos : -1;             // this row of the K cache is produced here, not read
+
+    v4f ra[NSLOT], rb[NSLOT], pa, pb;
+    // rows clamped to the context (valid, written rows); float4 slots past the chunk re-read its last one
+    auto issue = [&](v4f (&R)[NSLOT], const float* gbase, int t0) {
+#pragma unroll
+        for (int u = 0; u < NSLOT; ++u) {
+            const int idx = min(sid + u * NST, NF4 - 1);
+            const int row = min(t0 + (idx >> 5), np - 1), c = idx & 31;
+            R[u] = *(const v4f*)(gbase + (size_t)row * kvd + 4 * c);
+        }
+    };
+    auto commit = [&](const v4f (&R)[NSLOT], float* tile, int ld, int t0, int skip_row) {
+#pragma unroll
+        for (int u = 0; u < NSLOT; ++u) {
+            const int idx = sid + u * NST;
+            const int row = idx >> 5, c = idx & 31;
+            if (idx < NF4 && t0 + row < np && t0 + row != skip_row) *(v4f*)(tile + row * ld + 4 * c) = R[u];
+        }
+    };
+    // the chunk's probabilities, head sid / 16, entries t0 + 4 * (sid % 16) ...: inside the row's padded length (t0 + 64 <= npad)
+    auto issue_p = [&](v4f& P, int t0) {
+        if (sid < NPF4) P = *(const v4f*)(row0 + (size_t)(sid >> 4) * ast + t0 + 4 * (sid & 15));
+    };
+    auto commit_p = [&](const v4f& P, float* pt) {
+        if (sid < NPF4) *(v4f*)(pt + 4 * sid) = P;
+    };
+    // the position's own key row (normalised + rotated here) goes into the tile that holds timestep pos
+    auto fix_k = [&](float* tile, int t0) {
+        if (kwave && own_k && pos >= t0 && pos < t0 + TCH) {
+            tile[(pos - t0) * kld + lane] = k_s[lane];
+            tile[(pos - t0) * kld + lane + 64] = k_s[lane + 64];
+        }
+    };
+
+    // ---- raw q heads / raw k row, norm weights and rope pairs; the staging waves request K chunks 0 and 1
+    float r[2] = {0.0f, 0.0f};
+    RopeRegs rr;
+    if (wave <= KVM) {
+#pragma unroll
+        for (int u = 0; u < 2; ++u) r[u] = kwave ? (own_k ? ksrc[lane + 64 * u] : 0.0f) : qsrc[lane + 64 * u];
+        rope_regs_load(rr, kwave ? a0.k_norm_w : a0.q_norm_w, cs, hd);
+    }
+    if (stager) {
+        issue(ra, kbase, 0);
+        if (TCH < np) issue(rb, kbase, TCH);
+    }
+    if (wave <= KVM) {
+        float* raw_w = raw + wave * hd;
+        raw_w[lane] = r[0];
+        raw_w[lane + 64] = r[1];
+        wave_lds_sync();
+        if (head || own_k) wave_norm_rope(kwave ? k_s : q_s + wave * hd, raw_w, sq + wave * hd, rr, hd, 1);   // layers.rs:346-372
+        wave_lds_sync();
+        if (kwave && own_k && store_k) {                        // K is normalised + rotated in place in the cache
+            float* krow = key_cache + (size_t)pos * kvd + (size_t)kvh * hd;
+            krow[lane] = k_s[lane];
+            krow[lane + 64] = k_s[lane + 64];
+        }
+    }
+    const float scale = 1.0f / sqrtf((float)hd);   // (head_dim as f32).sqrt().recip()
+    if (stager) {
+        commit(ra, tiles, kld, 0, skip);
+        fix_k(tiles, 0);
+        if (2 * TCH < np) issue(ra, kbase, 2 * TCH);
+    }
+    __syncthreads();
+
+    // ---- scores: row[t] = (q . K[t]) * scale, one timestep per lane, stored to the global row      layers.rs:391-401
+    float mx = -__builtin_inff();                  // the lane's running maximum of its scores
+    auto dots = [&](const float* tile, int t0) {
+        const int t = lane;
+        if (t0 + t < np) {
+            const v4f* k4 = (const v4f*)(tile + t * kld);
+            const v4f* q4 = (const v4f*)(q_s + wave * hd);
+            float dot = -0.0f;
+#pragma unroll
+            for (int i = 0; i < hd / 4; i += 8) {
+                v4f kk[8], qq[8];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) { kk[u] = k4[i + u]; qq[u] = q4[i + u]; }
+#pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    const v4f pr = qq[u] * kk[u];          // products are independent of the chain: packed multiplies
+                    dot = dot + pr.x;
+                    dot = dot + pr.y;
+                    dot = dot + pr.z;
+                    dot = dot + pr.w;
+                }
+            }
+            const float s = dot * scale;
+            att[t0 + t] = s;
+            mx = fmaxf(mx, s);
+        }
+    };
+    for (int c0 = 0; c0 < np; c0 += 2 * TCH) {
+        if (stager && c0 + TCH < np) {
+            commit(rb, tiles + TILE, kld, c0 + TCH, skip);
+            fix_k(tiles + TILE, c0 + TCH);
+            if (c0 + 3 * TCH < np) issue(rb, kbase, c0 + 3 * TCH);
+        }
+        if (head) dots(tiles, c0);
+        __syncthreads();
+        if (c0 + TCH >= np) break;
+        if (stager && c0 + 2 * TCH < np) {
+            commit(ra, tiles, kld, c0 + 2 * TCH, skip);
+            fix_k(tiles, c0 + 2 * TCH);
+            if (c0 + 4 * TCH < np) issue(ra, kbase, c0 + 4 * TCH);
+        }
+        if (head) dots(tiles + TILE, c0 + TCH);
+        __syncthreads();
+    }
+
+    // ---- softmax over the global rows, one wave per head (+ a helper wave for the exps)            layers.rs:495-506
+    if (stager) {                                   // V chunks 0 and 1 travel under the softmax
+        issue(ra, vbase, 0);
+        if (TCH < np) issue(rb, vbase, TCH);
+    }
+    const int npad = (np + 255) & ~255;
+    if (head) {
+        mx = group_max_f32(mx, 64);
+        if (lane == 0) red[wave] = mx;
+    }
+    __threadfence_block();                          // the scores are in memory before another wave reads them
+    __syncthreads();
+    {
+        // head wave j takes the even 256-entry blocks of its row and staging wave KVM + j, where there is one, the odd ones
+        const int j = head ? wave : wave - KVM;
+        if (j < KVM) {
+            const bool shared = KVM + j < kG2Waves;
+            float* row = row0 + (size_t)j * ast;
+            const float m = red[j];
+            const int step = shared ? 512 : 256;
+            for (int t = (head ? 0 : 256) + 4 * lane; t < npad; t += 2 * step) {
+                const int t1 = t + step;
+                const v4f z = {0.0f, 0.0f, 0.0f, 0.0f};
+                const v4f x0 = t < np ? *(const v4f*)(row + t) : z;            // (both loads before the first exp)
+                const v4f x1 = t1 < np ? *(const v4f*)(row + t1) : z;
+                v4f e0, e1;                                                     // +0.0 padding: sums unchanged
+                e0.x = t + 0 < np ? q3_expf(x0.x - m) : 0.0f; e0.y = t + 1 < np ? q3_expf(x0.y - m) : 0.0f;
+                e0.z = t + 2 < np ? q3_expf(x0.z - m) : 0.0f; e0.w = t + 3 < np ? q3_expf(x0.w - m) : 0.0f;
+                *(v4f*)(row + t) = e0;
+                if (t1 < npad) {
+                    e1.x = t1 + 0 < np ? q3_expf(x1.x - m) : 0.0f; e1.y = t1 + 1 < np ? q3_expf(x1.y - m) : 0.0f;
+                    e1.z = t1 + 2 < np ? q3_expf(x1.z - m) : 0.0f; e1.w = t1 + 3 < np ? q3_expf(x1.w - m) : 0.0f;
+                    *(v4f*)(row + t1) = e1;
+                }
+            }
+        }
+    }
+    __threadfence_block();                          // the exps of both waves of a row are in memory before its head wave sums them
+    __syncthreads();
+    if (head) {
+        float sum;
+        if (np < 256) {
+            const int nq4 = np >> 2;
+            sum = seq_chain(-0.0f, (const v4f*)att, nq4);
+            for (int t = nq4 << 2; t < np; ++t) sum = sum + att[t];
+        } else {
+            sum = seq_sum_blocks(att, 64, npad >> 6, npad >> 6, nullptr);
+        }
+        const float inv = 1.0f / sum;
+        for (int t = 4 * lane; t < np; t += 256) {              // (the padding stays +0.0)
+            v4f p = *(const v4f*)(att + t);
+            p.x = p.x * inv; p.y = p.y * inv; p.z = p.z * inv; p.w = p.w * inv;
+            *(v4f*)(att + t) = p;
+        }
+    }
+    // under the sums: V chunk 0 lands in tile 0 (free since the last score barrier), chunk 2 is requested
+    if (stager) {
+        commit(ra, tiles, hd, 0, -1);
+        if (2 * TCH < np) issue(ra, vbase, 2 * TCH);
+    }
+    __threadfence_block();                          // the probabilities are in memory before the staging waves fetch them
+    __syncthreads();
+
+    // ---- xb = sum_t p[t] * V[t]  (fill(0.0) then += in t order)                layers.rs:406-417
+    // k_attn_gqa2's fold: the lane's two element chains (lane, lane + 64) advance together and share the probability reads
+    float o0 = 0.0f, o1 = 0.0f;
+    auto fold = [&](const float* tile, const float* pt, int t0) {
+        const int cnt = min(TCH, np - t0);
+        const float* w = pt + wave * TCH;
+        const v4f* w4 = (const v4f*)w;
+        const float* v0 = tile + lane;
+        int t = 0;
+        for (; t + 8 <= cnt; t += 8, v0 += 8 * hd) {
+            const v4f wa = w4[t >> 2], wb = w4[(t >> 2) + 1];
+            float x0[8], x1[8];
+#pragma unroll
+            for (int x = 0; x < 8; ++x) { x0[x] = v0[x * hd]; x1[x] = v0[x * hd + 64]; }
+            const float ww[8] = {wa.x, wa.y, wa.z, wa.w, wb.x, wb.y, wb.z, wb.w};
+#pragma unroll
+            for (int x = 0; x < 8; ++x) {
+                const float p0 = ww[x] * x0[x], p1 = ww[x] * x1[x];
+                o0 = o0 + p0;
+                o1 = o1 + p1;
+            }
+        }
+        for (; t < cnt; ++t, v0 += hd) {
+            const float wt = w[t];
+            const float p0 = wt * v0[0], p1 = wt * v0[64];
+            o0 = o0 + p0;
+            o1 = o1 + p1;
+        }
+    };
+    if (stager) {
+        issue_p(pa, 0);
+        if (TCH < np) issue_p(pb, TCH);
+        commit_p(pa, probs);
+        if (2 * TCH < np) issue_p(pa, 2 * TCH);
+    }
+    __syncthreads();
+    for (int c0 = 0; c0 < np; c0 += 2 * TCH) {
+        if (stager && c0 + TCH < np) {
+            commit(rb, tiles + TILE, hd, c0 + TCH, -1);
+            commit_p(pb, probs + PT);
+            if (c0 + 3 * TCH < np) { issue(rb, vbase, c0 + 3 * TCH); issue_p(pb, c0 + 3 * TCH); }
+        }
+        if (head) fold(tiles, probs, c0);
+        __syncthreads();
+        if (c0 + TCH >= np) break;
+        if (stager && c0 + 2 * TCH < np) {
+            commit(ra, tiles, hd, c0 + 2 * TCH, -1);
+            commit_p(pa, probs);
+            if (c0 + 4 * TCH < np) { issue(ra, vbase, c0 + 4 * TCH); issue_p(pa, c0 + 4 * TCH); }
+        }
+        if (head) fold(tiles + TILE, probs + PT, c0 + TCH);
+        __syncthreads();
+    }
+    if (head) {
+        const float o[4] = {o0, o1, 0.0f, 0.0f};
+        gqa_store(a0, sbi, h, hd, lane, o);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // Dense-prefill attention helpers (k_attn_pf2 below)
 // ------------------------------------------------------------------------------------------------
 // exact sequential sum (from -0.0) of row[0 .. np): NQ float4 per lane, blocks of 4*NQ consecutive terms, terms past np are +0.0

@@ -86,7 +86,9 @@ struct BatchCtx {
     DevMem<float> ps;
     DevMem<float> qn;            // k_attn_pf2: normalised + rotated queries of the block, head pairs interleaved [cap][n_heads/2][hd][2]
     DevMem<float> x, q, kraw, xb, hb, logits;
-    DevMem<float> key, value, att;
+    DevMem<float> key, value;
+    DevMem<float> att;           // score rows in global scratch [att_cols][n_heads][att_stride] (k_attn_gqa2g; k_attn_streams past its LDS
+    int att_cols = 0, att_stride = 0;   // bound): made by the first plan that needs them (att_rows_alloc, q3_plan_host.inc)
     DevMem<int8_t> xq_p;
     DevMem<float> xs_p;
     DevMem<State> st;
@@ -350,7 +352,6 @@ int batch_alloc(q3_engine* e, int max_streams, uint32_t ctx_len, bool with_kv, i
     if ((rc = b->xq_p.alloc(nt_max * 16 * maxn)) || (rc = b->xs_p.alloc(nt_max * 16 * (maxn / G)))) return rc;
     HIP_TRY(hipMemsetAsync(b->xq_p, 0, nt_max * 16 * maxn, e->stream));          // idle stream columns: finite operands
     HIP_TRY(hipMemsetAsync(b->xs_p, 0, 4 * nt_max * 16 * (maxn / G), e->stream));
-    if (S > (size_t)dev_knob("Q3_ATT_LDS_MAX", 4096) && (rc = b->att.alloc(B * c.n_heads * S))) return rc;
     if ((rc = b->st.alloc(C))) return rc;
     HIP_TRY(hipMemsetAsync(b->st, 0, sizeof(State) * C, e->stream));
     if (dev_knob("Q3_STAMPS", 0)) {

@@ -66,7 +66,7 @@ struct AttnArgs {
     const float* k_norm_w;    // [hd]
     const float* rope;        // [seq_len][hd/2][2] (cos,sin) host-built with glibc powf/cosf/sinf
     float* xb;                // [n_heads*hd] out
-    float* att_global;        // [n_heads][seq_len] scratch when scores do not fit in LDS (else nullptr)
+    float* att_global;        // [n_heads][seq_len] scratch when scores do not fit in LDS (else nullptr); k_attn_gqa2g: [n_heads][att_stride]
     const State* st;
     int pos_override;         // >= 0: use this pos instead of st->pos (operator-level entry point)
     int n_heads, n_kv_heads, hd, seq_len;
@@ -105,7 +105,7 @@ struct AttnArgs {
     // column pass (q3_batch_step_cols): column -> KV slot of the batched state, [columns] on the device.  Only the cache base goes
     // through it (slot * sb_kv); q, k_raw, xb, the packed activations and State stay indexed by column.  nullptr: column = slot.
     const int* col_slot;
-    // k_attn_gqa<128, 4> / k_attn_gqa2<4>: 2 = two workgroups per kv group of 8 query heads, 4 consecutive heads each
+    // k_attn_gqa<128, 4> / k_attn_gqa2<4> / k_attn_gqa2g<4>: 2 = two workgroups per kv group of 8 query heads, 4 consecutive heads each
     // (grid.x = 2 * n_kv_heads).  0 or 1: one workgroup per kv group.  No other value, and no other instantiation reads it.
     int head_parts;
 };

@@ -78,6 +78,23 @@ AttnFn attn_gqa_fn(bool gqa2, int hd, int kvm) {
 }
 // workgroups per kv group of the per-kv-head kernels: 8 query heads per kv head at head_dim 128 run as two parts of 4
 int attn_head_parts(int hd, int kv_mul) { return hd == kG2Hd && kv_mul == 8 ? 2 : 1; }
+// Which per-kv-head kernel serves a context of S positions.  While the score rows fit LDS (150 KB with the tiles) the choice is
+// k_attn_gqa2, then k_attn_gqa; past that, head_dim 128 with 2, 4 or 5 query heads per workgroup has k_attn_gqa2g, whose rows lie
+// in global scratch (Q3_BATCH_ATT_GQA2G=0: none, as before it existed).  None: k_attn_streams for decode, a refusal for blocks.
+enum class AttnGqa { None, Gqa, Gqa2, Gqa2g };
+AttnGqa attn_gqa_kind(int hd, int kv_mul, int S) {
+    const int wg_heads = kv_mul / attn_head_parts(hd, kv_mul);
+    // a workgroup of the per-kv-head kernels takes the kv group's heads, at most 7 -- or 4 of 8 (head_dim 128: two parts per group)
+    if (wg_heads > 7 || hd > 256 || (hd & (hd - 1)) != 0 || hd < 16 || !dev_knob("Q3_BATCH_ATT_GQA", 1)) return AttnGqa::None;
+    if (attn_gqa_smem_bytes(hd, wg_heads, S) <= 150 * 1024) {
+        // head_dim 128 with 2 or 4 query heads per workgroup: staging and arithmetic on separate waves, two LDS tiles
+        const bool gqa2 = hd == kG2Hd && (wg_heads == 2 || wg_heads == 4) && attn_gqa2_smem_bytes(wg_heads, S) <= 150 * 1024 && dev_knob("Q3_BATCH_ATT_GQA2", 1);
+        return gqa2 ? AttnGqa::Gqa2 : AttnGqa::Gqa;
+    }
+    const bool gqa2g = hd == kG2Hd && (wg_heads == 2 || wg_heads == 4 || wg_heads == 5) && dev_knob("Q3_BATCH_ATT_GQA2G", 1);
+    return gqa2g ? AttnGqa::Gqa2g : AttnGqa::None;
+}
+AttnFn attn_gqa2g_fn(int kvm) { return kvm == 5 ? (AttnFn)k_attn_gqa2g<5> : (kvm == 4 ? (AttnFn)k_attn_gqa2g<4> : (AttnFn)k_attn_gqa2g<2>); }
 // dense prefill attention: query heads per kv head (2 | 4 | 5 | 8) x positions per workgroup (4 | 8; 2 | 4 for 8 heads: at most 16
 // waves; 4 for 5 heads: 10 waves, the fifth head paired across positions)
 AttnFn attn_pf2_fn(int kvm, int np) {
@@ -369,6 +386,14 @@ struct PlanBuilder {
     const int att_tch = dev_knob("Q3_BATCH_ATT_TCH", 32);
     const int att_lds_max = dev_knob("Q3_ATT_LDS_MAX", 4096);
     const bool bq_spec = G == 64 && dev_knob("Q3_BQUANT_SPEC", 1) != 0;
+    // the attention kernel of the plan, decided once: the plan's launches and the scratch plan_get makes for them agree
+    const int kv_mul = c.n_heads / c.n_kv_heads;
+    const AttnGqa gqa_kind = attn_gqa_kind(hd, kv_mul, S);
+    // dense prefill, head_dim 128 with 2, 4, 5 or 8 query heads per kv head: k_attn_pf2 (Q3_PREFILL_ATT_PF=0: k_attn_gqa2)
+    const bool use_pf = dense && attn_pf2_shape_ok(hd, kv_mul) && sc.att_pf != nullptr && dev_knob("Q3_PREFILL_ATT_PF", 1);
+    const bool gqa2g = !use_pf && gqa_kind == AttnGqa::Gqa2g;
+    // score rows in global scratch (BatchCtx::att): k_attn_gqa2g's, or those of k_attn_streams past its LDS bound
+    bool att_rows() const { return gqa2g || (!use_pf && !block && gqa_kind == AttnGqa::None && S > att_lds_max); }
     // the copies of k_spec_snapshot / k_spec_restore: up to (n - 1) rows of kv_dim floats per layer and cache, a float4 per thread
     const unsigned spec_grid = (unsigned)std::min<long>(8L * e->n_cu, std::max<long>(1, ((long)L * (kSpecMax - 1) * (kvd / 4) + kWG - 1) / kWG));
     int nslots_used = 0;         // argmax slots the classifier launch fills: what the tail launches read
@@ -530,7 +555,7 @@ struct PlanBuilder {
         a.k_norm_w = e->k_ln + (size_t)l * hd;
         a.rope = e->d_rope;
         a.xb = sc.xb;
-        a.att_global = S > att_lds_max ? b->att : nullptr;
+        a.att_global = att_rows() && !gqa2g ? (float*)b->att : nullptr;     // k_attn_streams: [stream][head][S] at the front of the rows
         a.st = sc.st;
         a.pos_override = -1;
         a.n_heads = c.n_heads;
@@ -542,13 +567,8 @@ struct PlanBuilder {
         a.sb_att = (long long)c.n_heads * S;
         a.col_slot = sc.col_slot;
         a.tch = att_tch < attn_tch(hd) ? att_tch : attn_tch(hd);
-        const int kv_mul = c.n_heads / c.n_kv_heads;
-        // a workgroup of the per-kv-head kernels takes the kv group's heads, at most 7 -- or 4 of 8 (head_dim 128: two parts per group)
         const int parts = attn_head_parts(hd, kv_mul), wg_heads = kv_mul / parts;
-        const bool gqa = wg_heads <= 7 && hd <= 256 && (hd & (hd - 1)) == 0 && hd >= 16 &&
-                         attn_gqa_smem_bytes(hd, wg_heads, S) <= 150 * 1024 && dev_knob("Q3_BATCH_ATT_GQA", 1);
-        // dense prefill, head_dim 128 with 2, 4, 5 or 8 query heads per kv head: k_attn_pf2 (Q3_PREFILL_ATT_PF=0: k_attn_gqa2)
-        const bool use_pf = dense && attn_pf2_shape_ok(hd, kv_mul) && sc.att_pf != nullptr && dev_knob("Q3_PREFILL_ATT_PF", 1);
+        const bool gqa = gqa_kind != AttnGqa::None;
         if (slotpf && !use_pf) return fail(Q3_ERR_UNSUPPORTED, "a dense block over the slots needs k_attn_pf2 (head_dim 128, 2, 4, 5 or 8 query heads per kv head)");
         if (block && !gqa && !use_pf) return fail(Q3_ERR_UNSUPPORTED, "batched prefill needs the per-kv-head attention kernel");
         if (block) {   // all key rows of the block enter the cache before any position attends
@@ -590,8 +610,16 @@ struct PlanBuilder {
             }
             a.stamps = stamp_cells();
             a.head_parts = parts;
-            // head_dim 128 with 2 or 4 query heads per workgroup: staging and arithmetic on separate waves, two LDS tiles
-            const bool gqa2 = hd == kG2Hd && (wg_heads == 2 || wg_heads == 4) && attn_gqa2_smem_bytes(wg_heads, S) <= 150 * 1024 && dev_knob("Q3_BATCH_ATT_GQA2", 1);
+            if (gqa2g) {   // the score rows in global scratch, [column][head][att_stride]: any position of the context
+                if (!b->att) return fail(Q3_ERR_INTERNAL, "k_attn_gqa2g before its score rows");
+                if (n > b->att_cols) return fail(Q3_ERR_UNSUPPORTED, "a block of %d columns past the LDS bound of the score rows needs k_attn_pf2 (score rows for %d columns)", n, b->att_cols);
+                a.att_global = b->att;
+                a.att_stride = b->att_stride;
+                a.sb_att = (long long)c.n_heads * b->att_stride;
+                return add(F_ATTN, attn_gqa2g_fn(wg_heads), dim3((unsigned)(c.n_kv_heads * parts), (unsigned)n), dim3((unsigned)kG2Threads),
+                           attn_gqa2g_smem_bytes(wg_heads), a);
+            }
+            const bool gqa2 = gqa_kind == AttnGqa::Gqa2;
             return add(F_ATTN, attn_gqa_fn(gqa2, hd, wg_heads), dim3((unsigned)(c.n_kv_heads * parts), (unsigned)n),
                        dim3(gqa2 ? (unsigned)kG2Threads : (unsigned)(wg_heads + 1) * 64),
                        gqa2 ? attn_gqa2_smem_bytes(wg_heads, S) : attn_gqa_smem_bytes(hd, wg_heads, S), a);
@@ -757,6 +785,21 @@ int batch_build_plan(const q3_engine* e, PlanKey key, Plan& out) {
     return rc;
 }
 
+// The score rows of the plans whose attention keeps them in global scratch (PlanBuilder::att_rows), made by the first such plan and
+// never replaced while the context lives, so every kept plan's pointers hold: [columns][n_heads][stride], for the widest plan that
+// can ask (a decode step of max_streams, a column pass or a verify block of kColsMax) over the longest context a plan of this
+// engine can have (a block over the engine's own cache runs at seq_len whatever the context's length is).
+int att_rows_alloc(q3_engine* e, PlanKey key) {
+    BatchCtx* b = e->batch;
+    Plan none;
+    if (b->att || !PlanBuilder(e, key, none).att_rows()) return Q3_OK;
+    const int cols = std::max(b->max_streams, (int)kColsMax), stride = gqa_att_stride(e->cfg.seq_len);
+    if (int rc = b->att.alloc((size_t)cols * e->cfg.n_heads * stride)) return rc;
+    b->att_cols = cols;
+    b->att_stride = stride;
+    return Q3_OK;
+}
+
 int cols_width_index(int n) {
     int w = 0;
     while (kColsWidths[w] < n) ++w;
@@ -796,6 +839,8 @@ int plan_get(q3_engine* e, PlanKey key, Plan** out) {
         if (key.pen)
             if (int rc = key.pen == kPenGuideSp ? guide_sp_alloc(e) : key.pen == kPenGuide ? guide_alloc(e) : (key.pen == kPenAdj ? bias_alloc(e) : pen_alloc(e)))
                 return rc;
+        // ... and the score rows of an attention kernel that keeps them in global scratch
+        if (int rc = att_rows_alloc(e, key)) return rc;
         Plan built;
         if (int rc = batch_build_plan(e, key, built)) return rc;
         if (key.kind == PlanKind::SlotPrefill) home = &b->dense_plans[key.n];
