@@ -1288,6 +1288,34 @@ int q3_generate_many_lookup(q3_engine* e, const int32_t* prompts /* concatenated
  * Q3_ERR_ARG: a null argument; n >= 2^31; ngram < 1; draft_len outside 1 .. Q3_LOOKUP_DRAFT_MAX. */
 int q3_op_lookup_draft(const int32_t* seq, size_t n, int ngram, int draft_len, int32_t* draft_out, int32_t* len_out, int device);
 
+/* ------------------------------------------------------------------------------------------------
+ * 2v. (behind 2u so that the earlier sections stay as they were.)  Q4 checkpoints: int4 layer weights and a W4A8 decode GEMV.
+ * FORMAT.  A Q4 file is the checkpoint of section 1 with the magic number 0x616A6334 ("ajc4") in place of 0x616A6331: version 1,
+ * the same 13 header ints, the same 256-byte header, the same tensor and layer order.  The norms, embed_tokens and lm_head are
+ * written as ever (int8 values, one f32 scale per group).  Each of the seven per-layer matrices (q, k, v, o, gate, down, up) is
+ * uint8[size / 2] then f32[size / group]: two's-complement nibbles in [-8, 7] with one f32 scale per group of `group` columns.
+ * NIBBLE LAYOUT.  Row-major by runs of 16 consecutive columns c0 .. c15, 8 bytes per run:
+ *     byte b     (b = 0..3):  low nibble = q[c_b],       high nibble = q[c_(4+b)]
+ *     byte 4 + b (b = 0..3):  low nibble = q[c_(8+b)],   high nibble = q[c_(12+b)]
+ * so that for a dword w of a run, (w << 4) & 0xF0F0F0F0 and w & 0xF0F0F0F0 are int8x4 operands equal to 16 x the low and the high
+ * nibbles, lined up with the four dwords of the 16 activation bytes of the run.  Rows must be multiples of 16 columns.
+ * IDENTITY.  A Q4 file computes, bit for bit, what the int8 file with the same scales and the nibbles written as int8 values
+ * computes (the expanded file; qwen3_rs_amd.checkpoint.expand_q4_checkpoint writes it): the i32 group dots are exact -- the kernel
+ * forms 16 x the dot and shifts it back behind the integer group sum -- and the f32 terms and their order are the same code.
+ * WHAT RUNS.  Single-stream decode launches the WB = 4 forms of k_gemv (csrc/q3_gemv.h) for the five GEMV launches of a layer -- 8-byte loads per
+ * lane, half the weight bytes per token -- and the int8 kernel for the classifier; same plan, same graph.  The batched paths of
+ * sections 2b .. 2u expand the layer matrices once into their int8 MFMA-ordered copy (k_pack_weights) and run as on the expanded
+ * file: no byte is saved there.  q3_config and Q3_ABI_VERSION are unchanged; q3_parse_header accepts either magic.
+ * ------------------------------------------------------------------------------------------------ */
+/* 8, or 4 for an engine created from a Q4 file (the width of the per-layer matrices; embedding and classifier are int8). */
+int q3_weight_bits(const q3_engine* e);
+
+/* q3_op_gemv_role over nibble rows: wq4 holds n / 2 bytes per weight row in the layout above, everything else (arguments, roles,
+ * flags, launch_info, errors) is q3_op_gemv_role's.  Every role but Q3_ROLE_NORM_LOGITS (Q3_ERR_ARG: the classifier is int8). */
+int q3_op_gemv_role_w4(int role, float* out, float* tap_out, int32_t* argmax_index, int32_t* launch_info, const float* in,
+                       const float* norm_w, const int8_t* pre_q, const float* pre_s, const uint8_t* wq4, const float* ws, size_t n,
+                       size_t rows, size_t rows_kv, size_t head_dim, size_t group_size, uint32_t flags, int device);
+
 #ifdef __cplusplus
 }
 #endif

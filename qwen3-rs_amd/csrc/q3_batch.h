@@ -29,6 +29,9 @@ constexpr int kMaxStreams = 32;
 // One-time repack of a [rows][n] int8 matrix (+ [rows][n/G] scales) into row-tile order.
 // Destination tile of source tile t is tile0 + t * tile_stride (q|k|v concatenated; w1/w3 interleaved).
 // ------------------------------------------------------------------------------------------------
+// WB = 4: the source rows are the nibble rows of a Q4 checkpoint (8 bytes per 16-column run, include/qwen3_hip.h section 2v); a
+// piece is expanded to its 16 int8 bytes on the way, so the packed copy -- and everything that reads it -- is the int8 one.
+template <int WB = 8>
 __global__ __launch_bounds__(kWG) void k_pack_weights(const int8_t* __restrict__ wq, const float* __restrict__ ws,
                                                       int8_t* __restrict__ pq, float* __restrict__ ps, int rows, int n,
                                                       int G, int tile0, int tile_stride) {
@@ -46,7 +49,21 @@ __global__ __launch_bounds__(kWG) void k_pack_weights(const int8_t* __restrict__
         const size_t src = (t * 16 + r) * (size_t)n + (size_t)g * G + (size_t)(q * nj + j) * 16;
         const size_t dt = (size_t)tile0 + t * (size_t)tile_stride;
         const size_t dst = (((dt * ng + g) * nj + j) * 64 + lane) * 16;
-        *(v4i*)(pq + dst) = *(const v4i*)(wq + src);
+        if constexpr (WB == 4) {
+            // (w << 4) & 0xF0F0F0F0 and w & 0xF0F0F0F0 are 16 x the low / high nibbles as int8x4: an arithmetic shift of each byte
+            // by 4 gives the int8 values, columns 0-3 | 4-7 from dword 0 and 8-11 | 12-15 from dword 1
+            const v2i w = *(const v2i*)(wq + (src >> 1));
+            auto sar4 = [](int v) {      // per-byte arithmetic >> 4 of an int8x4 whose low nibbles are zero
+                const unsigned u = (unsigned)v;
+                return (int)((u >> 4) | (((u & 0x80808080u) >> 7) * 0xF0u));   // 0x0N, sign bytes filled with 0xF0: no carry between bytes
+            };
+            v4i o;
+            o.x = sar4((w.x << 4) & (int)0xF0F0F0F0u);
+            o.y = sar4(w.x & (int)0xF0F0F0F0u);
+            o.z = sar4((w.y << 4) & (int)0xF0F0F0F0u);
+            o.w = sar4(w.y & (int)0xF0F0F0F0u);
+            *(v4i*)(pq + dst) = o;
+        } else *(v4i*)(pq + dst) = *(const v4i*)(wq + src);
     }
     const size_t nsc = (size_t)rows * ng;
     for (size_t p = (size_t)blockIdx.x * kWG + threadIdx.x; p < nsc; p += (size_t)gridDim.x * kWG) {

@@ -319,18 +319,19 @@ int batch_alloc(q3_engine* e, int max_streams, uint32_t ctx_len, bool with_kv, i
     b->m_cls = reserve(V, dim);
     int rc;
     if ((rc = b->pq.alloc(qbytes)) || (rc = b->ps.alloc(sfloats))) return rc;
-    auto pack = [&](const QT& t, int rows, int n, const BatchCtx::PM& m, int tile0, int tile_stride) {
-        hipLaunchKernelGGL(k_pack_weights, dim3(e->n_cu * 8), dim3(kWG), 0, e->stream, t.q, t.s, b->pq + m.q_off, b->ps + m.s_off,
+    // bits: 8, or the engine's weight_bits for a layer matrix (a Q4 checkpoint: expanded to int8 on the way, section 2v)
+    auto pack = [&](const QT& t, int rows, int n, const BatchCtx::PM& m, int tile0, int tile_stride, int bits = 8) {
+        hipLaunchKernelGGL(bits == 4 ? k_pack_weights<4> : k_pack_weights<8>, dim3(e->n_cu * 8), dim3(kWG), 0, e->stream, t.q, t.s, b->pq + m.q_off, b->ps + m.s_off,
                            rows, n, G, tile0, tile_stride);
     };
     for (int l = 0; l < L; ++l) {
-        pack(e->wq[l], ahd, dim, b->m_qkv[l], 0, 1);
-        pack(e->wk[l], kvd, dim, b->m_qkv[l], ahd / 16, 1);
-        pack(e->wv[l], kvd, dim, b->m_qkv[l], (ahd + kvd) / 16, 1);
-        pack(e->wo[l], dim, ahd, b->m_wo[l], 0, 1);
-        pack(e->w1[l], H, dim, b->m_w13[l], 0, 2);
-        pack(e->w3[l], H, dim, b->m_w13[l], 1, 2);
-        pack(e->w2[l], dim, H, b->m_w2[l], 0, 1);
+        pack(e->wq[l], ahd, dim, b->m_qkv[l], 0, 1, e->weight_bits);
+        pack(e->wk[l], kvd, dim, b->m_qkv[l], ahd / 16, 1, e->weight_bits);
+        pack(e->wv[l], kvd, dim, b->m_qkv[l], (ahd + kvd) / 16, 1, e->weight_bits);
+        pack(e->wo[l], dim, ahd, b->m_wo[l], 0, 1, e->weight_bits);
+        pack(e->w1[l], H, dim, b->m_w13[l], 0, 2, e->weight_bits);
+        pack(e->w3[l], H, dim, b->m_w13[l], 1, 2, e->weight_bits);
+        pack(e->w2[l], dim, H, b->m_w2[l], 0, 1, e->weight_bits);
     }
     pack(e->wcls, V, dim, b->m_cls, 0, 1);
     HIP_TRY(hipGetLastError());

@@ -247,6 +247,7 @@ int stop_seq_check(const int32_t* dflt, const uint32_t* row_off, const q3_guide_
 }
 
 constexpr int32_t kMagic = 0x616a6331;   // configuration.rs:8
+constexpr int32_t kMagicQ4 = 0x616a6334;  // "ajc4": the seven per-layer matrices as nibbles (include/qwen3_hip.h section 2v)
 constexpr int32_t kVersion = 1;          // configuration.rs:10
 constexpr size_t kHeaderSize = 256;      // configuration.rs:12
 constexpr size_t kConfigSize = 52;       // 13 x i32
@@ -263,7 +264,7 @@ int parse_header(const uint8_t* d, size_t len, q3_config* c) {
     if (len < kHeaderSize)
         return fail(Q3_ERR_FORMAT, "Cannot skip %zu bytes: insufficient data", kHeaderSize - kConfigSize);
     const int32_t magic = rd_i32(d), version = rd_i32(d + 4);
-    if (magic != kMagic)
+    if (magic != kMagic && magic != kMagicQ4)
         return fail(Q3_ERR_FORMAT, "Invalid model configuration: Invalid checkpoint magic number: expected %#x, got %#x",
                     kMagic, (unsigned)magic);
     if (version != kVersion)
@@ -338,8 +339,9 @@ inline void launch(const Launch& L, hipStream_t st) { L.thunk(L, st); }
 namespace q3inst {
 typedef void (*GemvFn)(const q3::GemvArgs);
 struct GemvCfg { int pro, epi, n, wgt, ept, ru, ju, pf; GemvFn fn; };
-GemvFn gemv_pick(int pro, int epi, int G, int RU, int JU, int FIN, int PF);       // generic run-time-n kernels
-const GemvCfg* find_cfg(int pro, int epi, int n, int G, bool fast = false);              // shape-specialised kernels
+// wb: weight bits of the matrix (8, or 4: k_gemv's WB = 4 forms, the layer matrices of a Q4 checkpoint)
+GemvFn gemv_pick(int pro, int epi, int G, int RU, int JU, int FIN, int PF, int wb = 8);       // generic run-time-n kernels
+const GemvCfg* find_cfg(int pro, int epi, int n, int G, bool fast = false, int wb = 8, bool wide = false);   // shape-specialised kernels
 }
 using q3inst::GemvCfg;
 using q3inst::find_cfg;
@@ -482,6 +484,7 @@ struct q3_engine {
     // device memory
     DevMem<uint8_t> d_blob;
     size_t blob_bytes = 0;
+    int weight_bits = 8;                       // of the seven per-layer matrices: 8, or 4 for a Q4 file (section 2v); embedding and classifier are int8
     const float *rms_att = nullptr, *rms_ffn = nullptr, *rms_final = nullptr, *q_ln = nullptr, *k_ln = nullptr;
     QT tok, wcls;
     std::vector<QT> wq, wk, wv, wo, w1, w2, w3;
@@ -713,11 +716,12 @@ void apply_cfg(GemvLaunch& Ln, GemvArgs& a, const GemvCfg& c, int units, int n_c
 // table entry when there is one, the generic run-time-n kernel otherwise.  units = output rows (SwiGLU: hidden units);
 // hd = head_dim for EPI_QKV (row batches must not straddle the q|k|v segments), 1 otherwise.  build_plan and the operator
 // entry point q3_op_gemv_role both select through this function.
-int plan_role(GemvLaunch& Ln, GemvArgs& a, int pro, int epi, int n, int units, int G, bool fast_fold, int hd, int n_cu) {
+int plan_role(GemvLaunch& Ln, GemvArgs& a, int pro, int epi, int n, int units, int G, bool fast_fold, int hd, int n_cu, int wb = 8) {
     const int small_cap = dev_knob("Q3_WG_PER_CU_SMALL", 2);   // two workgroups per CU: half the rows (and fold chains) per wave
     const int big_cap = dev_knob("Q3_WG_PER_CU_LMHEAD", 2);   // all workgroups resident at once (the NORM prologue keeps ~190 VGPRs live)
     const bool norm = pro == PRO_NORM || pro == PRO_EMBED_NORM;
-    const GemvCfg* cfg = find_cfg(pro, epi, n, G, fast_fold);
+    if (wb == 4 && epi == EPI_LOGITS) return fail(Q3_ERR_UNSUPPORTED, "the classifier has no 4-bit kernel");
+    const GemvCfg* cfg = find_cfg(pro, epi, n, G, fast_fold, wb, wb == 4 && dev_knob("Q3_W4_WIDE", 0) != 0);
     if (cfg && epi == EPI_QKV && (hd % cfg->ru) != 0) cfg = nullptr;           // batches must not straddle the q|k|v segments
     if (cfg) {
         apply_cfg(Ln, a, *cfg, units, n_cu);
@@ -729,7 +733,7 @@ int plan_role(GemvLaunch& Ln, GemvArgs& a, int pro, int epi, int n, int units, i
     } else {
         const GemvShape gs = epi == EPI_LOGITS ? plan_gemv(units, n, G, false, 1, n_cu, big_cap, false)
                                                : plan_gemv(units, n, G, epi == EPI_SWIGLU, epi == EPI_QKV ? hd : 1, n_cu, small_cap);
-        Ln.fn = q3inst::gemv_pick(pro, epi, G, gs.RU, gs.JU, epi == EPI_LOGITS ? 0 : gs.FIN, gs.PF);
+        Ln.fn = q3inst::gemv_pick(pro, epi, G, gs.RU, gs.JU, epi == EPI_LOGITS ? 0 : gs.FIN, gs.PF, wb);
         a.vr = gs.RU;
         Ln.grid = gs.grid;
         Ln.smem = gemv_smem_bytes(n, G, a.vr, norm);
@@ -762,6 +766,7 @@ int q3_engine::load(const char* path, uint32_t ctx_len) {
 
     int rc = parse_header(base, flen, &cfg);
     if (rc) return rc;
+    weight_bits = rd_i32(base) == kMagicQ4 ? 4 : 8;
     if (ctx_len != 0 && (int64_t)ctx_len < (int64_t)cfg.seq_len) cfg.seq_len = (int32_t)ctx_len;  // models/mod.rs:65-67
     if (cfg.architecture_id != 1) return fail(Q3_ERR_FORMAT, "Unknown architecture_id: %d", cfg.architecture_id);
     if ((rc = check_supported(cfg))) return rc;
@@ -784,10 +789,11 @@ int q3_engine::load(const char* path, uint32_t ctx_len) {
         return o;
     };
     struct QOff { size_t q, s; };
-    auto take_q = [&](size_t count, size_t size_each, std::vector<QOff>& out) {   // models/mod.rs:83-110
+    // bits: 8, or weight_bits for the seven per-layer matrices (a Q4 file holds size/2 bytes of nibbles there)
+    auto take_q = [&](size_t count, size_t size_each, std::vector<QOff>& out, int bits = 8) {   // models/mod.rs:83-110
         for (size_t i = 0; i < count; ++i) {
             QOff o;
-            o.q = take(size_each, "quantized tensor data");
+            o.q = take(size_each * bits / 8, "quantized tensor data");
             o.s = take(4 * (size_each / G), "scale factors");
             out.push_back(o);
         }
@@ -799,13 +805,13 @@ int q3_engine::load(const char* path, uint32_t ctx_len) {
     const size_t o_k_ln = take(4 * L * hd, "key layer norm weights");
     std::vector<QOff> otok, owq, owk, owv, owo, ow1, ow2, ow3, ocls;
     take_q(1, V * dim, otok);
-    take_q(L, dim * ahd, owq);
-    take_q(L, dim * kvd, owk);
-    take_q(L, dim * kvd, owv);
-    take_q(L, ahd * dim, owo);
-    take_q(L, dim * H, ow1);
-    take_q(L, H * dim, ow2);
-    take_q(L, dim * H, ow3);
+    take_q(L, dim * ahd, owq, weight_bits);
+    take_q(L, dim * kvd, owk, weight_bits);
+    take_q(L, dim * kvd, owv, weight_bits);
+    take_q(L, ahd * dim, owo, weight_bits);
+    take_q(L, dim * H, ow1, weight_bits);
+    take_q(L, H * dim, ow2, weight_bits);
+    take_q(L, dim * H, ow3, weight_bits);
     if (!cfg.shared_classifier) take_q(1, dim * V, ocls);
     if (!ok) return Q3_ERR_FORMAT;
 
@@ -816,6 +822,9 @@ int q3_engine::load(const char* path, uint32_t ctx_len) {
     for (auto* v : {&otok, &owq, &owk, &owv, &owo, &ow1, &ow2, &ow3, &ocls})
         for (auto& o : *v) all_aligned = all_aligned && aligned(o.q) && aligned(o.s);
     if (!all_aligned) return fail(Q3_ERR_UNSUPPORTED, "checkpoint sections are not 16-byte aligned");
+    // the W4 GEMV reads a nibble row in 8-byte pieces, one per 16 columns: every row of n/2 bytes must start on one
+    if (weight_bits == 4 && (dim % 16 || ahd % 16 || H % 16))
+        return fail(Q3_ERR_UNSUPPORTED, "4-bit rows of dim %zu / all_heads_dim %zu / hidden_dim %zu are not 8-byte aligned (multiples of 16 columns needed)", dim, ahd, H);
 
     HIP_TRY(hipSetDevice(device));
     hipDeviceProp_t prop;
@@ -947,7 +956,7 @@ int q3_engine::build_plan() {
     // one fused GEMV role: resolve kernel and shape (plan_role), stamp, record
     auto gemv = [&](Launch& Ln, Family fam, GemvArgs a, int pro, int epi, int n, int units, int qkv_hd, bool stamped) -> int {
         GemvLaunch g;
-        if ((rc = plan_role(g, a, pro, epi, n, units, G, fast_fold, qkv_hd, n_cu))) return rc;
+        if ((rc = plan_role(g, a, pro, epi, n, units, G, fast_fold, qkv_hd, n_cu, weight_bits))) return rc;   // (layer launches only)
         if (stamped) stamp(a);
         return make_launch(Ln, fam, g.fn, dim3(g.grid), dim3(g.block), g.smem, a);
     };
@@ -981,7 +990,7 @@ int q3_engine::build_plan() {
         // the short plan only ever runs at pos < split_pos
         const bool att_short = (hd == 64 || hd == 128) && split_pos <= kShortMaxT && dev_knob("Q3_ATT_SHORT", 1);
         // k_attn_short can hand Wo its operand quantized (qwen3.rs:152 fused into the attention epilogue)
-        const GemvCfg* wo_preq = att_short ? find_cfg(PRO_PREQR, EPI_RESID, ahd, G, fast_fold) : nullptr;
+        const GemvCfg* wo_preq = att_short ? find_cfg(PRO_PREQR, EPI_RESID, ahd, G, fast_fold, weight_bits) : nullptr;
         {   // QK-norm + RoPE + attention                                        layers.rs:346-419
             AttnArgs a{};
             a.q = d_q;
@@ -1188,6 +1197,8 @@ int q3_parse_header(const uint8_t* data, size_t len, q3_config* out) {
     g_err[0] = 0;
     return parse_header(data, len, out);
 }
+
+int q3_weight_bits(const q3_engine* e) { return e ? e->weight_bits : 0; }
 
 int q3_create(const char* checkpoint_path, uint32_t ctx_len, int device, uint32_t flags, q3_engine** out) {
     g_err[0] = 0;
@@ -1769,11 +1780,17 @@ int q3_op_matmul(float* xout, const int8_t* xq, const float* xs, const int8_t* w
     return Q3_OK;
 }
 
-int q3_op_gemv_role(int role, float* out, float* tap_out, int32_t* argmax_index, int32_t* launch_info, const float* in,
-                    const float* norm_w, const int8_t* pre_q, const float* pre_s, const int8_t* wq, const float* ws, size_t n,
-                    size_t rows, size_t rows_kv, size_t head_dim, size_t group_size, uint32_t flags, int device) {
+}  // extern "C"
+
+namespace {
+// q3_op_gemv_role (wb = 8) and q3_op_gemv_role_w4 (wb = 4: wq holds n/2 bytes of nibbles per row, section 2v)
+int op_gemv_role(int role, float* out, float* tap_out, int32_t* argmax_index, int32_t* launch_info, const float* in,
+                 const float* norm_w, const int8_t* pre_q, const float* pre_s, const int8_t* wq, const float* ws, size_t n,
+                 size_t rows, size_t rows_kv, size_t head_dim, size_t group_size, uint32_t flags, int device, int wb) {
     int rc = op_begin(device);
     if (rc) return rc;
+    const size_t nrow = n * (size_t)wb / 8;       // weight bytes per row
+    if (wb == 4 && role == Q3_ROLE_NORM_LOGITS) return fail(Q3_ERR_ARG, "Q3_ROLE_NORM_LOGITS has no 4-bit form: the classifier of a Q4 checkpoint is int8");
     int pro, epi;
     switch (role) {
         case Q3_ROLE_NORM_QKV: pro = PRO_NORM; epi = EPI_QKV; break;
@@ -1799,14 +1816,14 @@ int q3_op_gemv_role(int role, float* out, float* tap_out, int32_t* argmax_index,
     // follows the flag alone, i.e. the product's selection)
     const bool fast = (flags & Q3_FLAG_FAST) != 0;
     const int G = (int)group_size;
-    if (pro == PRO_PREQR && !find_cfg(pro, epi, (int)n, G, fast))     // the planner falls back to PRO_QUANT: no generic kernel reads xq into registers
+    if (pro == PRO_PREQR && !find_cfg(pro, epi, (int)n, G, fast, wb))     // the planner falls back to PRO_QUANT: no generic kernel reads xq into registers
         return fail(Q3_ERR_UNSUPPORTED, "PRO_PREQR has no kernel for n = %zu, group %d", n, G);
     hipDeviceProp_t prop;
     HIP_TRY(hipGetDeviceProperties(&prop, device));
     const size_t wrows = qkv ? rows + 2 * rows_kv : (epi == EPI_SWIGLU ? 2 * rows : rows);   // weight rows
     const size_t orows = qkv ? rows + 2 * rows_kv : rows;                                    // output floats
     OpBuf din, dnw, dpq, dps, dwq, dws, dout, dtap, dst, dcell, dslots, dtok;
-    if ((rc = dwq.upload(wq, wrows * n)) || (rc = dws.upload(ws, 4 * (wrows * n / group_size)))) return rc;
+    if ((rc = dwq.upload(wq, wrows * nrow)) || (rc = dws.upload(ws, 4 * (wrows * n / group_size)))) return rc;
     if (pro == PRO_PREQR) {
         if ((rc = dpq.upload(pre_q, n)) || (rc = dps.upload(pre_s, 4 * (n / group_size)))) return rc;
     } else if ((rc = din.upload(in, 4 * n))) return rc;
@@ -1836,8 +1853,8 @@ int q3_op_gemv_role(int role, float* out, float* tap_out, int32_t* argmax_index,
         const float* s0 = dws.as<float>();
         float* o0 = dout.as<float>();
         a.seg[0] = Seg{w0, s0, o0, (int)rows, 0};
-        a.seg[1] = Seg{w0 + rows * n, s0 + rows * ng, o0 + rows, (int)rows_kv, 0};
-        a.seg[2] = Seg{w0 + (rows + rows_kv) * n, s0 + (rows + rows_kv) * ng, o0 + rows + rows_kv, (int)rows_kv, (int)rows_kv};
+        a.seg[1] = Seg{w0 + rows * nrow, s0 + rows * ng, o0 + rows, (int)rows_kv, 0};
+        a.seg[2] = Seg{w0 + (rows + rows_kv) * nrow, s0 + (rows + rows_kv) * ng, o0 + rows + rows_kv, (int)rows_kv, (int)rows_kv};
         a.total_rows = units = (int)orows;
         for (int k = 0; k < 2; ++k) {
             a.qkv_dw[k] = (const char*)a.seg[k + 1].wq - (const char*)a.seg[k].wq;
@@ -1846,13 +1863,13 @@ int q3_op_gemv_role(int role, float* out, float* tap_out, int32_t* argmax_index,
         }
     } else if (epi == EPI_SWIGLU) {
         a.seg[0] = Seg{dwq.as<int8_t>(), dws.as<float>(), dout.as<float>(), (int)rows, 0};
-        a.seg[1] = Seg{dwq.as<int8_t>() + rows * n, dws.as<float>() + rows * ng, nullptr, (int)rows, 0};
+        a.seg[1] = Seg{dwq.as<int8_t>() + rows * nrow, dws.as<float>() + rows * ng, nullptr, (int)rows, 0};
         a.total_rows = 2 * (int)rows;
     } else {
         a.seg[0] = Seg{dwq.as<int8_t>(), dws.as<float>(), dout.as<float>(), (int)rows, 0};
         a.total_rows = (int)rows;
     }
-    if ((rc = plan_role(Ln, a, pro, epi, (int)n, units, G, fast, qkv ? (int)head_dim : 1, prop.multiProcessorCount))) return rc;
+    if ((rc = plan_role(Ln, a, pro, epi, (int)n, units, G, fast, qkv ? (int)head_dim : 1, prop.multiProcessorCount, wb))) return rc;
     if (epi == EPI_LOGITS) {    // the engine's form: the argmax bookkeeping of k_next folded into the classifier launch
         if ((rc = dslots.alloc(8 * (size_t)Ln.grid)) || (rc = dcell.alloc(16)) || (rc = dtok.alloc(4))) return rc;
         HIP_TRY(hipMemset(dcell.p, 0, 16));
@@ -1869,13 +1886,30 @@ int q3_op_gemv_role(int role, float* out, float* tap_out, int32_t* argmax_index,
         *argmax_index = (int32_t)(unsigned)(st0.argmax & 0xffffffffull);
     }
     if (launch_info) {
-        const GemvCfg* c = find_cfg(pro, epi, (int)n, G, fast);
+        const GemvCfg* c = find_cfg(pro, epi, (int)n, G, fast, wb, wb == 4 && dev_knob("Q3_W4_WIDE", 0) != 0);
         launch_info[0] = (c != nullptr && Ln.fn == c->fn) ? 1 : 0;
         launch_info[1] = (int32_t)Ln.grid;
         launch_info[2] = (int32_t)Ln.block;
         launch_info[3] = a.vr;
     }
     return Q3_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int q3_op_gemv_role(int role, float* out, float* tap_out, int32_t* argmax_index, int32_t* launch_info, const float* in,
+                    const float* norm_w, const int8_t* pre_q, const float* pre_s, const int8_t* wq, const float* ws, size_t n,
+                    size_t rows, size_t rows_kv, size_t head_dim, size_t group_size, uint32_t flags, int device) {
+    return op_gemv_role(role, out, tap_out, argmax_index, launch_info, in, norm_w, pre_q, pre_s, wq, ws, n, rows, rows_kv, head_dim,
+                        group_size, flags, device, 8);
+}
+
+int q3_op_gemv_role_w4(int role, float* out, float* tap_out, int32_t* argmax_index, int32_t* launch_info, const float* in,
+                       const float* norm_w, const int8_t* pre_q, const float* pre_s, const uint8_t* wq4, const float* ws, size_t n,
+                       size_t rows, size_t rows_kv, size_t head_dim, size_t group_size, uint32_t flags, int device) {
+    return op_gemv_role(role, out, tap_out, argmax_index, launch_info, in, norm_w, pre_q, pre_s, (const int8_t*)wq4, ws, n, rows, rows_kv,
+                        head_dim, group_size, flags, device, 4);
 }
 
 int q3_op_rmsnorm(float* out, const float* in, const float* weight, size_t n, uint32_t flags, int device) {

@@ -1036,11 +1036,39 @@ __device__ __forceinline__ int lpg_sum(int v, int lpg) {
     return group_sum_i32(v, lpg);
 }
 
-template <int RU, int JU>
+// WB = weight bits.  8: a lane's 16 columns of a unit are 16 int8 bytes (v4i).  4 (Q4 checkpoints): the same 16 columns are 8
+// bytes of two's-complement nibbles (v2i) -- byte b < 4 holds columns b (low nibble) and 4+b (high), byte 4+b columns 8+b and
+// 12+b, so that  (w << 4) & 0xF0F0F0F0  and  w & 0xF0F0F0F0  of each dword ARE int8x4 operands, 16 x the nibbles, lined up with the
+// x, y, z, w dwords of the lane's 16 activation bytes: two VALU instructions per dword, no sign extension.
+typedef int v2i __attribute__((ext_vector_type(2)));
+template <int WB> struct WVec { typedef v4i type; };
+template <> struct WVec<4> { typedef v2i type; };
+template <int RU, int JU, int WB = 8>
 struct Tile {
-    v4i w[RU][JU];
+    typename WVec<WB>::type w[RU][JU];
     float sc[RU][JU];
 };
+// the i32 dot of a lane's 16 columns with its 16 activation bytes; WB = 4: 16 x that dot (dot16_scale undoes it, exactly,
+// behind the integer group sum: every addend is a multiple of 16 and 16 * 8 * 127 * 1024 < 2^31 at the largest group)
+template <int WB>
+__device__ __forceinline__ int dot16(const typename WVec<WB>::type& w, const v4i& xv) {
+    if constexpr (WB == 8) {
+        int d = __builtin_amdgcn_sdot4(w.x, xv.x, 0, false);
+        d = __builtin_amdgcn_sdot4(w.y, xv.y, d, false);
+        d = __builtin_amdgcn_sdot4(w.z, xv.z, d, false);
+        d = __builtin_amdgcn_sdot4(w.w, xv.w, d, false);
+        return d;
+    } else {
+        constexpr int kHi = (int)0xF0F0F0F0u;
+        int d = __builtin_amdgcn_sdot4((w.x << 4) & kHi, xv.x, 0, false);
+        d = __builtin_amdgcn_sdot4(w.x & kHi, xv.y, d, false);
+        d = __builtin_amdgcn_sdot4((w.y << 4) & kHi, xv.z, d, false);
+        d = __builtin_amdgcn_sdot4(w.y & kHi, xv.w, d, false);
+        return d;
+    }
+}
+template <int WB>
+__device__ __forceinline__ int dot16_scale(int d) { return WB == 4 ? d >> 4 : d; }
 
 // weight rows of one wave batch: `parts` runs (2 for SwiGLU's w1|w3 pair, else 1) of `hu` consecutive
 // rows, the first `cnt` of each run live.  base + row*stride addressing, no pointer arrays.
@@ -1094,8 +1122,15 @@ __device__ __forceinline__ float ordered_row_sum(const float* t, int ng) {
 // N_T > 0 (round 3): contraction length, workgroup width WGT and elements per prologue thread EPT are compile-time (group
 // 64, register fold): the prologue is pro2_*, every index derived from n folds, and one workgroup of up to 16 waves per CU
 // replaces two of four.  N_T == 0: the generic run-time-n kernel (any group size; 256 threads).
-template <int PRO, int EPI, int LPG_T, int RU, int JU, int FIN = 0, int PF = 0, int N_T = 0, int WGT = kWG, int EPT = 4>
+// WB = 4 (the W4A8 forms: the layer matrices of a Q4 checkpoint): the same lane-to-column map with 8-byte loads -- a unit is
+// 512 B of a weight row, a tile's registers halve -- and everything outside load_tile / dot16 is the code the int8 forms run.
+// Seg::wq of those launches points at nibble rows (n / 2 bytes each, 8-byte aligned); the scales, the activation and the outputs
+// are what the int8 forms see.
+template <int PRO, int EPI, int LPG_T, int RU, int JU, int FIN = 0, int PF = 0, int N_T = 0, int WGT = kWG, int EPT = 4, int WB = 8>
 __global__ __launch_bounds__(WGT) void k_gemv(const GemvArgs a) {
+    typedef typename WVec<WB>::type wvec;
+    constexpr int WSH = (WB == 4) ? 1 : 0;             // weight bytes per row = n >> WSH
+    static_assert(WB == 8 || (WB == 4 && EPI != EPI_LOGITS), "Q4 checkpoints keep an int8 classifier");
     static_assert(N_T > 0 || (WGT == kWG && EPT == 4), "the generic prologue is written for 256 threads");
     static_assert(N_T == 0 || (LPG_T == 4 && FIN >= 1), "specialised shapes: group 64, register fold");
     static_assert(PRO != PRO_PREQR || (N_T > 0 && (N_T + 1023) / 1024 == JU), "register-direct xq: one tile per row");
@@ -1213,10 +1248,10 @@ __global__ __launch_bounds__(WGT) void k_gemv(const GemvArgs a) {
         rs.row0 = l0;
         rs.hu = HU;
         rs.cnt = min(HU, rows - l0);
-        rs.w[0] = wq + (size_t)l0 * n;
+        rs.w[0] = wq + (size_t)l0 * (n >> WSH);
         rs.s[0] = ws + (size_t)l0 * ng;
         if (EPI == EPI_SWIGLU) {
-            rs.w[1] = a.seg[1].wq + (size_t)l0 * n;
+            rs.w[1] = a.seg[1].wq + (size_t)l0 * (n >> WSH);
             rs.s[1] = a.seg[1].ws + (size_t)l0 * ng;
         } else {
             rs.w[1] = rs.w[0];
@@ -1228,7 +1263,7 @@ __global__ __launch_bounds__(WGT) void k_gemv(const GemvArgs a) {
         return rs;
     };
     const bool chunks_fit = (nchunks % (64 * JU)) == 0;      // every lane of every j-tile is inside the row
-    auto load_tile = [&](Tile<RU, JU>& T, const RowSrc& rs, int jt) {
+    auto load_tile = [&](Tile<RU, JU, WB>& T, const RowSrc& rs, int jt) {
         if (chunks_fit && rs.cnt == HU) {
             // exact fit (all listed models' layer shapes): base + constant strides, no clamps
             const int c0 = lane + 64 * JU * jt;
@@ -1236,7 +1271,7 @@ __global__ __launch_bounds__(WGT) void k_gemv(const GemvArgs a) {
             for (int r = 0; r < RU; ++r) {
                 const int part = (EPI == EPI_SWIGLU && r >= HU) ? 1 : 0;
                 const int lr = r - part * HU;
-                const v4i* wrow = (const v4i*)(rs.w[part] + (size_t)lr * n) + c0;
+                const wvec* wrow = (const wvec*)(rs.w[part] + (size_t)lr * (n >> WSH)) + c0;
                 const float* srow = rs.s[part] + (size_t)lr * ng + (c0 >> lpg_shift);
 #pragma unroll
                 for (int j = 0; j < JU; ++j) {
@@ -1250,18 +1285,18 @@ __global__ __launch_bounds__(WGT) void k_gemv(const GemvArgs a) {
         for (int r = 0; r < RU; ++r) {
             const int part = (EPI == EPI_SWIGLU && r >= HU) ? 1 : 0;
             const int lr = min(r - part * HU, rs.cnt - 1);     // tail rows re-read the last live row
-            const int8_t* wrow = rs.w[part] + (size_t)lr * n;
+            const int8_t* wrow = rs.w[part] + (size_t)lr * (n >> WSH);
             const float* srow = rs.s[part] + (size_t)lr * ng;
 #pragma unroll
             for (int j = 0; j < JU; ++j) {
                 const int c = min(lane + 64 * (jt * JU + j), nchunks - 1);   // tail chunks clamp
-                T.w[r][j] = __builtin_nontemporal_load((const v4i*)wrow + c);
+                T.w[r][j] = __builtin_nontemporal_load((const wvec*)wrow + c);
                 T.sc[r][j] = __builtin_nontemporal_load(srow + (c >> lpg_shift));
             }
         }
     };
     float racc[RU];                                  // FIN: running row sums (wave-uniform)
-    auto compute_tile = [&](const Tile<RU, JU>& T, const RowSrc& rs, int jt) {
+    auto compute_tile = [&](const Tile<RU, JU, WB>& T, const RowSrc& rs, int jt) {
         if constexpr (FIN != 0) {
             static_assert(FIN == 0 || LPG_T == 4, "the register fold is written for group 64");
             if (jt == 0) {
@@ -1284,11 +1319,8 @@ __global__ __launch_bounds__(WGT) void k_gemv(const GemvArgs a) {
                 float t[RU], acc[RU];
 #pragma unroll
                 for (int r = 0; r < RU; ++r) {
-                    int d = __builtin_amdgcn_sdot4(T.w[r][j].x, xv.x, 0, false);
-                    d = __builtin_amdgcn_sdot4(T.w[r][j].y, xv.y, d, false);
-                    d = __builtin_amdgcn_sdot4(T.w[r][j].z, xv.z, d, false);
-                    d = __builtin_amdgcn_sdot4(T.w[r][j].w, xv.w, d, false);
-                    d = group_sum_i32_t<4>(d);
+                    int d = dot16<WB>(T.w[r][j], xv);
+                    d = dot16_scale<WB>(group_sum_i32_t<4>(d));
                     t[r] = (float)d * T.sc[r][j];   // tensor.rs:59  ((dot as f32) * ws) * xs -- identical in the 4 lanes of a group
                     t[r] = t[r] * xsc;
                     t[r] = cok ? t[r] : -0.0f;
@@ -1334,11 +1366,8 @@ __global__ __launch_bounds__(WGT) void k_gemv(const GemvArgs a) {
             const float xsc = sm.xs[cc >> lpg_shift];
 #pragma unroll
             for (int r = 0; r < RU; ++r) {
-                int d = __builtin_amdgcn_sdot4(T.w[r][j].x, xv.x, 0, false);
-                d = __builtin_amdgcn_sdot4(T.w[r][j].y, xv.y, d, false);
-                d = __builtin_amdgcn_sdot4(T.w[r][j].z, xv.z, d, false);
-                d = __builtin_amdgcn_sdot4(T.w[r][j].w, xv.w, d, false);
-                d = lpg_sum<LPG_T>(d, lpg);
+                int d = dot16<WB>(T.w[r][j], xv);
+                d = dot16_scale<WB>(lpg_sum<LPG_T>(d, lpg));
                 const int part = (EPI == EPI_SWIGLU && r >= HU) ? 1 : 0;
                 if (cok && (c & (lpg - 1)) == 0 && (r - part * HU) < rs.cnt) {
                     float t = (float)d * T.sc[r][j];   // tensor.rs:59  ((dot as f32) * ws) * xs
@@ -1400,7 +1429,7 @@ __global__ __launch_bounds__(WGT) void k_gemv(const GemvArgs a) {
     // emits counted vmcnt(N) waits and the next tile streams in while the current one is reduced.
     int cb = gw, cjt = 0;
     const bool any = cb < nb;
-    Tile<RU, JU> TA, TB;
+    Tile<RU, JU, WB> TA, TB;
     RowSrc RA, RB;
     RA = batch_rows(min(cb, nb - 1));         // (idle waves re-read a valid batch; nothing is stored)
     load_tile(TA, RA, 0);                     // ... then the first weight tile ...

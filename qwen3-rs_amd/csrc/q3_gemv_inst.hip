@@ -12,21 +12,38 @@ namespace {
 // single-row-run fallback (RU = 1, or 2 for SwiGLU).  Variants (k_gemv FIN / PF): FIN = DPP-chain fold of the group terms
 // (group 64, rows a whole number of tiles), PF = second tile requested before the prologue (streaming launches).
 // Instantiated: (FIN,PF) = (0,0) everywhere; (1,0) and (1,1) for the layer kernels; (0,1) for the classifier.
-template <int PRO, int EPI, int LPG_T, int RU, int FIN = 0, int PF = 0>
+// WB = 4: the W4A8 forms of the same tile shapes (the layer matrices of a Q4 checkpoint)
+template <int WB, int PRO, int EPI, int LPG_T, int RU, int JU, int FIN, int PF>
+constexpr GemvFn kern() { return (GemvFn)k_gemv<PRO, EPI, LPG_T, RU, JU, FIN, PF, 0, kWG, 4, WB>; }
+template <int PRO, int EPI, int LPG_T, int RU, int FIN = 0, int PF = 0, int WB = 8>
 GemvFn pick_ju(int JU) {
-    if (JU == 1) return (GemvFn)k_gemv<PRO, EPI, LPG_T, RU, 1, FIN, PF>;
-    if (JU == 2) { if constexpr (RU <= 4) return (GemvFn)k_gemv<PRO, EPI, LPG_T, RU, 2, FIN, PF>; }
-    if (JU == 3) { if constexpr (RU <= 2) return (GemvFn)k_gemv<PRO, EPI, LPG_T, RU, 3, FIN, PF>; }
-    if (JU == 4) { if constexpr (RU <= 2) return (GemvFn)k_gemv<PRO, EPI, LPG_T, RU, 4, FIN, PF>; }
+    if (JU == 1) return kern<WB, PRO, EPI, LPG_T, RU, 1, FIN, PF>();
+    if (JU == 2) { if constexpr (RU <= 4) return kern<WB, PRO, EPI, LPG_T, RU, 2, FIN, PF>(); }
+    if (JU == 3) { if constexpr (RU <= 2) return kern<WB, PRO, EPI, LPG_T, RU, 3, FIN, PF>(); }
+    if (JU == 4) { if constexpr (RU <= 2) return kern<WB, PRO, EPI, LPG_T, RU, 4, FIN, PF>(); }
     return nullptr;
 }
-template <int PRO, int EPI, int FIN, int PF>
+template <int PRO, int EPI, int FIN, int PF, int WB = 8>
 GemvFn pick_ru64(int RU, int JU) {
     constexpr bool sw = (EPI == EPI_SWIGLU);
-    if (RU == 8) return pick_ju<PRO, EPI, 4, 8, FIN, PF>(JU);
-    if (RU == 4) return pick_ju<PRO, EPI, 4, 4, FIN, PF>(JU);
-    if (RU == 2) return pick_ju<PRO, EPI, 4, 2, FIN, PF>(JU);
-    if constexpr (!sw) { if (RU == 1) return pick_ju<PRO, EPI, 4, 1, FIN, PF>(JU); }
+    if (RU == 8) return pick_ju<PRO, EPI, 4, 8, FIN, PF, WB>(JU);
+    if (RU == 4) return pick_ju<PRO, EPI, 4, 4, FIN, PF, WB>(JU);
+    if (RU == 2) return pick_ju<PRO, EPI, 4, 2, FIN, PF, WB>(JU);
+    if constexpr (!sw) { if (RU == 1) return pick_ju<PRO, EPI, 4, 1, FIN, PF, WB>(JU); }
+    return nullptr;
+}
+// W4 generic kernels: group 64 in the register-fold forms the planner selects for it, every other group size in the
+// single-row-run form
+template <int PRO, int EPI>
+GemvFn pick_w4(int G, int RU, int JU, int FIN, int PF) {
+    constexpr bool sw = (EPI == EPI_SWIGLU);
+    if (G == 64) {
+        if (FIN && PF) return pick_ru64<PRO, EPI, 1, 1, 4>(RU, JU);
+        if (FIN) return pick_ru64<PRO, EPI, 1, 0, 4>(RU, JU);
+        return nullptr;
+    }
+    if constexpr (sw) { if (RU == 2) return pick_ju<PRO, EPI, 0, 2, 0, 0, 4>(JU); }
+    else { if (RU == 1) return pick_ju<PRO, EPI, 0, 1, 0, 0, 4>(JU); }
     return nullptr;
 }
 template <int PRO, int EPI>
@@ -109,16 +126,86 @@ Q3_CFG_LIST
 #undef Q3_CFG_FIN
 }  // namespace
 
+namespace {
+// ------------------------------------------------------------------------------------------------
+// The W4 forms of the listed shapes (k_gemv with WB = 4, the layer matrices of a Q4 checkpoint; the classifier stays int8).  A unit is
+// 512 B here and a tile's registers halve, so the rows / chunks per wave are a sweep of their own (DESIGN 4.22 has its table:
+// the Q8 shapes against the wider tiles of Q3_CFG_LIST_W4_WIDE).  Prologue widths (WGT, EPT) are the int8 table's: the
+// prologue is the same code on the same vector.
+// ------------------------------------------------------------------------------------------------
+#undef Q3_CFG
+#define Q3_CFG(PRO, EPI, N, WGT, EPT, RU, JU, PF) \
+    {PRO, EPI, N, WGT, EPT, RU, JU, PF, (GemvFn)k_gemv<PRO, EPI, 4, RU, JU, Q3_CFG_FIN, PF, N, WGT, EPT, 4>}
+#define Q3_CFG_LIST_W4 \
+    Q3_CFG_NORM_QKV(1024, 512, 2, 2, 1, 0), \
+    Q3_CFG_NORM_QKV(2560, 768, 4, 2, 3, 0), \
+    Q3_CFG_NORM_QKV(4096, 1024, 4, 1, 4, 0), \
+    Q3_CFG(PRO_NORM, EPI_SWIGLU, 1024, 512, 2, 4, 1, 0), \
+    Q3_CFG(PRO_NORM, EPI_SWIGLU, 2560, 512, 4, 2, 3, 0), \
+    Q3_CFG(PRO_NORM, EPI_SWIGLU, 4096, 1024, 4, 2, 4, 0), \
+    Q3_CFG(PRO_PREQR, EPI_RESID, 2048, 256, 4, 1, 2, 0), \
+    Q3_CFG(PRO_PREQR, EPI_RESID, 4096, 256, 4, 1, 4, 0), \
+    Q3_CFG(PRO_QUANT, EPI_RESID, 3072, 256, 4, 1, 3, 0), \
+    Q3_CFG(PRO_QUANT, EPI_RESID, 9728, 1024, 4, 1, 2, 1), \
+    Q3_CFG(PRO_QUANT, EPI_RESID, 12288, 1024, 4, 1, 4, 1), \
+    Q3_CFG(PRO_QUANT, EPI_RESID, 2048, 512, 4, 1, 2, 0), \
+    Q3_CFG(PRO_QUANT, EPI_RESID, 4096, 1024, 4, 1, 4, 0)
+#define Q3_CFG_FIN 1
+const GemvCfg kGemvCfgsW4[] = {
+Q3_CFG_LIST_W4
+};
+#undef Q3_CFG_FIN
+#define Q3_CFG_FIN 2
+const GemvCfg kGemvCfgsW4Fast[] = {
+Q3_CFG_LIST_W4
+};
+#undef Q3_CFG_FIN
+#ifdef Q3_DEV
+// developer build, Q3_W4_WIDE=1: the sweep's other side -- twice the rows per wave where a launch has more row batches than
+// waves (up to 16 units in flight), the whole 12 KiB-column row of W2 as two tiles
+#define Q3_CFG_LIST_W4_WIDE \
+    Q3_CFG_NORM_QKV(4096, 1024, 4, 2, 4, 0), \
+    Q3_CFG(PRO_NORM, EPI_SWIGLU, 1024, 512, 2, 8, 1, 0), \
+    Q3_CFG(PRO_NORM, EPI_SWIGLU, 2560, 512, 4, 4, 3, 0), \
+    Q3_CFG(PRO_NORM, EPI_SWIGLU, 4096, 1024, 4, 4, 4, 0), \
+    Q3_CFG(PRO_QUANT, EPI_RESID, 9728, 1024, 4, 1, 5, 1), \
+    Q3_CFG(PRO_QUANT, EPI_RESID, 12288, 1024, 4, 1, 6, 1)
+#define Q3_CFG_FIN 1
+const GemvCfg kGemvCfgsW4Wide[] = {
+Q3_CFG_LIST_W4_WIDE
+};
+#undef Q3_CFG_FIN
+#endif
+}  // namespace
+
 namespace q3inst {
-const GemvCfg* find_cfg(int pro, int epi, int n, int G, bool fast) {
+// wb: weight bits of the matrix the launch reads (8, or 4 for the layer matrices of a Q4 checkpoint); wide: developer sweep
+const GemvCfg* find_cfg(int pro, int epi, int n, int G, bool fast, int wb, bool wide) {
     if (G != 64) return nullptr;
+    if (wb == 4) {
+#ifdef Q3_DEV
+        if (wide && !fast)
+            for (const GemvCfg& c : kGemvCfgsW4Wide)
+                if (c.pro == pro && c.epi == epi && c.n == n) return &c;
+#endif
+        for (const GemvCfg& c : fast ? kGemvCfgsW4Fast : kGemvCfgsW4)
+            if (c.pro == pro && c.epi == epi && c.n == n) return &c;
+        return nullptr;
+    }
     for (const GemvCfg& c : fast ? kGemvCfgsFast : kGemvCfgs)   // (fast: tolerance mode, the same forms with the tree fold)
         if (c.pro == pro && c.epi == epi && c.n == n) return &c;
     return nullptr;                  // not a listed shape: the caller takes the generic kernel
 }
 
 // the (prologue, epilogue) pairs the engine and the operator entry points use
-GemvFn gemv_pick(int pro, int epi, int G, int RU, int JU, int FIN, int PF) {
+GemvFn gemv_pick(int pro, int epi, int G, int RU, int JU, int FIN, int PF, int wb) {
+    if (wb == 4) {
+        if (pro == PRO_EMBED_NORM && epi == EPI_QKV) return pick_w4<PRO_EMBED_NORM, EPI_QKV>(G, RU, JU, FIN, PF);
+        if (pro == PRO_NORM && epi == EPI_QKV) return pick_w4<PRO_NORM, EPI_QKV>(G, RU, JU, FIN, PF);
+        if (pro == PRO_QUANT && epi == EPI_RESID) return pick_w4<PRO_QUANT, EPI_RESID>(G, RU, JU, FIN, PF);
+        if (pro == PRO_NORM && epi == EPI_SWIGLU) return pick_w4<PRO_NORM, EPI_SWIGLU>(G, RU, JU, FIN, PF);
+        return nullptr;
+    }
     if (pro == PRO_EMBED_NORM && epi == EPI_QKV) return pick<PRO_EMBED_NORM, EPI_QKV>(G, RU, JU, FIN, PF);
     if (pro == PRO_NORM && epi == EPI_QKV) return pick<PRO_NORM, EPI_QKV>(G, RU, JU, FIN, PF);
     if (pro == PRO_QUANT && epi == EPI_RESID) return pick<PRO_QUANT, EPI_RESID>(G, RU, JU, FIN, PF);

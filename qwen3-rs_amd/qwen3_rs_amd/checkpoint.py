@@ -10,6 +10,10 @@ the reference writer byte for byte:
   tensor body   int8[size] then f32[size/group]               model_exporter.rs:302-303, models/mod.rs:92-101
   quantizer     quantize_q80, model_exporter.rs:104-162; round_half_to_even :321-338
 
+Beside it stands the Q4 form (include/qwen3_hip.h section 2v): its own magic number, the seven per-layer matrices as nibbles
+(pack_q4), everything else as above.  ModelShape.weight_bits tells the two apart; expand_q4_checkpoint writes the Q8 file that
+computes the same thing.
+
 numpy only; nothing here touches the GPU or the oracle.
 """
 from __future__ import annotations
@@ -23,6 +27,7 @@ from typing import BinaryIO, Dict, Iterator, List, Tuple
 import numpy as np
 
 MAGIC_NUMBER = 0x616A6331  # "ajc1", model_exporter.rs:34
+MAGIC_NUMBER_Q4 = 0x616A6334  # "ajc4": a Q4 file (weight_bits 4); the reference's reader refuses it instead of misreading it
 VERSION = 1                # model_exporter.rs:35
 HEADER_SIZE = 256          # model_exporter.rs:36
 MIN_GROUP_SIZE = 4         # model_exporter.rs:37
@@ -43,6 +48,10 @@ class ModelShape:
     shared_classifier: bool
     group_size: int = 64
     architecture_id: int = ARCH_QWEN3
+    weight_bits: int = 8       # of the seven per-layer matrices: 8, or 4 (a Q4 file); embed_tokens and lm_head are always int8
+
+    def tensor_bits(self, name: str) -> int:
+        return 8 if name in ("embed_tokens", "lm_head") else self.weight_bits
 
     @property
     def all_heads_dim(self) -> int:
@@ -76,21 +85,23 @@ class ModelShape:
     def file_size(self) -> int:
         g = self.group_size
         n = HEADER_SIZE + 4 * sum(c for _, c in self.norm_tensors())
-        for _, cnt, r, c in self.quantized_tensors():
-            n += cnt * (r * c + 4 * (r * c // g))
+        for name, cnt, r, c in self.quantized_tensors():
+            n += cnt * (r * c * self.tensor_bits(name) // 8 + 4 * (r * c // g))
         return n
 
     def weight_bytes_per_token(self) -> Tuple[int, int]:
-        """Algorithmic bytes streamed per decoded token: (int8 bytes, f32 scale bytes) of the L layers'
+        """Algorithmic bytes streamed per decoded token: (weight bytes, f32 scale bytes) of the L layers'
         seven matrices plus the classifier, each read once."""
         g = self.group_size
-        q = 0
+        q = n = 0
         for name, cnt, r, c in self.quantized_tensors():
             if name in ("embed_tokens", "lm_head"):
                 continue
-            q += cnt * r * c
-        q += self.vocab_size * self.dim  # classifier (tied or not) is streamed once
-        return q, 4 * (q // g)
+            q += cnt * r * c * self.weight_bits // 8
+            n += cnt * r * c
+        q += self.vocab_size * self.dim  # classifier (tied or not) is streamed once, int8
+        n += self.vocab_size * self.dim
+        return q, 4 * (n // g)
 
 
 # The four models the reference README lists (README.md:33-37); HF config.json values.
@@ -149,9 +160,54 @@ def quantize_q80(w: np.ndarray, group_size: int) -> Tuple[np.ndarray, np.ndarray
     return q.reshape(-1), scale, err
 
 
+def quantize_q40(w: np.ndarray, group_size: int) -> Tuple[np.ndarray, np.ndarray, float]:
+    """quantize_q80's rule at 4 bits: scale = gmax / 7 in f32 (1.0 for an all-zero group), q = clip(rint(w / scale), -7, 7).
+    Returns (int8[n] in [-7, 7], f32 scales[n/group], max_error)."""
+    w = np.ascontiguousarray(w, dtype=np.float32).reshape(-1)
+    if w.size % group_size != 0:
+        raise ValueError("Weight length is not a multiple of group_size")
+    g = w.reshape(-1, group_size)
+    gmax = np.max(np.abs(g), axis=1)
+    scale = np.where(gmax > 0, gmax / np.float32(7.0), np.float32(1.0)).astype(np.float32)
+    q = np.clip(np.rint(g / scale[:, None]), -7.0, 7.0)
+    q = np.where(np.isnan(q), 0.0, q).astype(np.int8)
+    err = float(np.max(np.abs(q.astype(np.float32) * scale[:, None] - g))) if w.size else 0.0
+    return q.reshape(-1), scale, err
+
+
+def pack_q4(q: np.ndarray) -> np.ndarray:
+    """int8 values in [-8, 7], row-major with rows of a multiple of 16 columns -> uint8[size / 2] in the nibble layout of a Q4
+    file: per run of 16 columns c0..c15, byte b < 4 = q[c_b] | q[c_(4+b)] << 4 and byte 4 + b = q[c_(8+b)] | q[c_(12+b)] << 4
+    (two's-complement nibbles)."""
+    q = np.ascontiguousarray(q, dtype=np.int8).reshape(-1)
+    if q.size % 16:
+        raise ValueError("pack_q4 needs whole runs of 16 columns")
+    if q.size and (q.min() < -8 or q.max() > 7):
+        raise ValueError("pack_q4 needs values in [-8, 7]")
+    u = (q.view(np.uint8) & 0x0F).reshape(-1, 4, 4)          # [run][quarter k][b] = column 4k + b
+    out = np.empty((u.shape[0], 2, 4), dtype=np.uint8)
+    out[:, 0] = u[:, 0] | (u[:, 1] << 4)
+    out[:, 1] = u[:, 2] | (u[:, 3] << 4)
+    return out.reshape(-1)
+
+
+def unpack_q4(p: np.ndarray) -> np.ndarray:
+    """pack_q4's inverse: uint8[m] -> int8[2 m] in [-8, 7]."""
+    p = np.ascontiguousarray(p, dtype=np.uint8).reshape(-1)
+    if p.size % 8:
+        raise ValueError("unpack_q4 needs whole runs of 8 bytes")
+    b = p.reshape(-1, 2, 4)
+    u = np.empty((b.shape[0], 4, 4), dtype=np.uint8)
+    u[:, 0], u[:, 1] = b[:, 0] & 0x0F, b[:, 0] >> 4
+    u[:, 2], u[:, 3] = b[:, 1] & 0x0F, b[:, 1] >> 4
+    return ((u.astype(np.int16) ^ 8) - 8).astype(np.int8).reshape(-1)
+
+
 def header_bytes(shape: ModelShape) -> bytes:
-    """model_exporter.rs:164-191"""
-    h = struct.pack("<Ii11I", MAGIC_NUMBER, VERSION, shape.architecture_id, shape.dim, shape.hidden_dim,
+    """model_exporter.rs:164-191 (a Q4 shape: its own magic number)"""
+    if shape.weight_bits not in (4, 8):
+        raise ValueError(f"weight_bits must be 8 or 4, got {shape.weight_bits}")
+    h = struct.pack("<Ii11I", MAGIC_NUMBER_Q4 if shape.weight_bits == 4 else MAGIC_NUMBER, VERSION, shape.architecture_id, shape.dim, shape.hidden_dim,
                     shape.n_layers, shape.n_heads, shape.n_kv_heads, shape.vocab_size, shape.max_seq_len,
                     shape.head_dim, int(shape.shared_classifier), shape.group_size)
     return h + b"\0" * (HEADER_SIZE - len(h))
@@ -164,28 +220,29 @@ def read_header(path: str) -> ModelShape:
     if len(raw) < HEADER_SIZE:
         raise ValueError("Insufficient data for header")
     (magic, version, arch, dim, hidden, L, nh, nkv, vocab, seq, hd, shared, group) = struct.unpack("<13i", raw[:52])
-    if magic != MAGIC_NUMBER:
+    if magic not in (MAGIC_NUMBER, MAGIC_NUMBER_Q4):
         raise ValueError(f"Invalid checkpoint magic number: expected {MAGIC_NUMBER:#x}, got {magic:#x}")
     if version != VERSION:
         raise ValueError(f"Unsupported checkpoint version: expected {VERSION}, got {version}")
-    return ModelShape(dim, hidden, L, nh, nkv, vocab, seq, hd, shared != 0, group, arch)
+    return ModelShape(dim, hidden, L, nh, nkv, vocab, seq, hd, shared != 0, group, arch, 4 if magic == MAGIC_NUMBER_Q4 else 8)
 
 
 def _tensor_rng(seed: int, tensor_idx: int, item: int, chunk: int) -> np.random.Generator:
     return np.random.Generator(np.random.PCG64([seed, tensor_idx, item, chunk]))
 
 
-def _synth_chunk(seed: int, tidx: int, item: int, chunk: int, n: int, sigma: float, group: int):
+def _synth_chunk(seed: int, tidx: int, item: int, chunk: int, n: int, sigma: float, group: int, bits: int = 8):
     """One chunk of a synthetic tensor: N(0, sigma^2) f32 pushed through quantize_q80's rule (model_exporter.rs:119-136;
-    same arithmetic as quantize_q80 above without its max-error pass)."""
+    same arithmetic as quantize_q80 above without its max-error pass), or quantize_q40's for bits = 4."""
     w = _tensor_rng(seed, tidx, item, chunk).standard_normal(n, dtype=np.float32)
     w *= np.float32(sigma)
     g = w.reshape(-1, group)
+    qmax = np.float32(7.0 if bits == 4 else 127.0)
     gmax = np.max(np.abs(g), axis=1)
-    scale = np.where(gmax > 0, gmax / np.float32(127.0), np.float32(1.0)).astype(np.float32)
+    scale = np.where(gmax > 0, gmax / qmax, np.float32(1.0)).astype(np.float32)
     np.divide(g, scale[:, None], out=g)
     np.rint(g, out=g)
-    np.clip(g, -127.0, 127.0, out=g)
+    np.clip(g, -qmax, qmax, out=g)
     return g.astype(np.int8).reshape(-1), scale
 
 
@@ -215,7 +272,8 @@ def write_synthetic_checkpoint(path: str, shape: ModelShape, seed: int = 1234, *
             def submit(k):
                 tidx, name, item, rows, cols = items[k]
                 sigma = 0.05 if name in ("embed_tokens", "lm_head") else float(cols) ** -0.5
-                return [pool.submit(_synth_chunk, seed, tidx, item, ci, min(chunk_rows, rows - r0) * cols, sigma, g)
+                return [pool.submit(_synth_chunk, seed, tidx, item, ci, min(chunk_rows, rows - r0) * cols, sigma, g,
+                                    shape.tensor_bits(name))
                         for ci, r0 in enumerate(range(0, rows, chunk_rows))]
             pending, nxt, in_flight = {}, 0, 0
             for k in range(len(items)):
@@ -240,7 +298,7 @@ def write_synthetic_checkpoint(path: str, shape: ModelShape, seed: int = 1234, *
                         s0[1] = 1.0
                     qs[0], ss[0] = q0, s0
                 for q in qs:
-                    f.write(q.tobytes())
+                    f.write((pack_q4(q) if shape.tensor_bits(name) == 4 else q).tobytes())
                 for sc in ss:
                     f.write(sc.astype("<f4").tobytes())
         n = f.tell()
@@ -271,11 +329,39 @@ def tensor_offsets(shape: ModelShape) -> Dict[str, Tuple[int, ...]]:
     g = shape.group_size
     for name, cnt, rows, cols in shape.quantized_tensors():
         size = rows * cols
-        stride = size + 4 * (size // g)
-        out[name] = (off, off + size, stride)
+        qbytes = size * shape.tensor_bits(name) // 8
+        stride = qbytes + 4 * (size // g)
+        out[name] = (off, off + qbytes, stride)
         off += cnt * stride
     out["__end__"] = (off,)
     return out
+
+
+def expand_q4_checkpoint(src: str, dst: str) -> ModelShape:
+    """Write the Q8 file that computes what the Q4 file `src` computes: the reference magic, every nibble as an int8 value, the
+    scales and everything else copied.  Returns the shape written (weight_bits 8)."""
+    s4 = read_header(src)
+    if s4.weight_bits != 4:
+        raise ValueError(f"{src} is not a Q4 checkpoint")
+    s8 = dataclasses.replace(s4, weight_bits=8)
+    g = s4.group_size
+    tmp = dst + ".tmp"
+    with open(src, "rb") as f, open(tmp, "wb") as o:
+        f.seek(HEADER_SIZE)
+        o.write(header_bytes(s8))
+        o.write(f.read(4 * sum(c for _, c in s4.norm_tensors())))
+        for name, cnt, rows, cols in s4.quantized_tensors():
+            size = rows * cols
+            for _ in range(cnt):
+                if s4.tensor_bits(name) == 4:
+                    o.write(unpack_q4(np.frombuffer(f.read(size // 2), dtype=np.uint8)).tobytes())
+                else:
+                    o.write(f.read(size))
+                o.write(f.read(4 * (size // g)))
+        n = o.tell()
+    os.replace(tmp, dst)
+    assert n == s8.file_size(), (n, s8.file_size())
+    return s8
 
 
 def iter_prompt_tokens(shape: ModelShape, seed: int, n: int) -> List[int]:

@@ -1,6 +1,6 @@
 """`qwen3` command line on the MI355X engine: the flags of qwen3-cli/src/main.rs:18-93.
 
-    python -m qwen3_rs_amd.cli export <MODEL_PATH> <OUTPUT_PATH> [--group-size 64]
+    python -m qwen3_rs_amd.cli export <MODEL_PATH> <OUTPUT_PATH> [--group-size 64] [--weight-bits 4]
     python -m qwen3_rs_amd.cli inference <checkpoint> [-t 1.0] [-p 0.9] [-s SEED] [-c CTX] [-m generate|chat]
                                          [-i INPUT] [-y SYSTEM] [-r 0|1] [--lookup DRAFT_LEN] [--speculate DRAFT_LEN]
                                          [-k TOP_K]
@@ -268,6 +268,7 @@ def build_parser() -> argparse.ArgumentParser:
     ex.add_argument("MODEL_PATH")
     ex.add_argument("OUTPUT_PATH")
     ex.add_argument("--group-size", "-g", type=int, default=64)
+    ex.add_argument("--weight-bits", type=int, default=8, choices=(8, 4), help="4: a Q4 checkpoint (int4 layer matrices)")
     inf = sub.add_parser("inference", help="Qwen3 inference")
     inf.add_argument("checkpoint")
     inf.add_argument("-t", "--temperature", type=float, default=1.0)
@@ -324,7 +325,7 @@ def main(argv=None) -> int:
             return 1
         try:
             info = export_mod.load_model_info(a.MODEL_PATH)
-            shape = export_mod.export_model(a.MODEL_PATH, a.OUTPUT_PATH, a.group_size, log=lambda m: print(m, file=sys.stderr))
+            shape = export_mod.export_model(a.MODEL_PATH, a.OUTPUT_PATH, a.group_size, log=lambda m: print(m, file=sys.stderr), weight_bits=a.weight_bits)
             if os.path.exists(os.path.join(a.MODEL_PATH, "tokenizer.json")):
                 print("wrote", export_tokenizer(a.MODEL_PATH, a.OUTPUT_PATH, info.bos_token_id, info.eos_token_id), file=sys.stderr)
             else:

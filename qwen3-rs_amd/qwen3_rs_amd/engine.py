@@ -42,7 +42,7 @@ EXPORTED_SYMBOLS = [
     "q3_guide_set", "q3_guide_get", "q3_op_guide",
     "q3_guide_set_sparse", "q3_guide_get_sparse", "q3_op_guide_sparse",
     "q3_stop_seq_set", "q3_stop_seq_get", "q3_cols_schedule_stop_seq", "q3_op_stop_seq",
-    "q3_generate_many_lookup", "q3_op_lookup_draft",
+    "q3_generate_many_lookup", "q3_op_lookup_draft", "q3_weight_bits", "q3_op_gemv_role_w4",
 ]
 LOOKUP_DRAFT_MAX = 31    # Q3_LOOKUP_DRAFT_MAX (section 2u)
 LOOKUP_CHUNK = 4096      # Q3_LOOKUP_CHUNK
@@ -322,6 +322,8 @@ def _bind(path: str) -> C.CDLL:
     L.q3_op_dequantize.argtypes = [i8p, fp, fp, sz, sz, C.c_int]
     L.q3_op_matmul.argtypes = [fp, i8p, fp, i8p, fp, sz, sz, sz, C.c_int]
     L.q3_op_gemv_role.argtypes = [C.c_int, fp, fp, i32p, i32p, fp, fp, i8p, fp, i8p, fp, sz, sz, sz, sz, sz, C.c_uint32, C.c_int]
+    L.q3_op_gemv_role_w4.argtypes = [C.c_int, fp, fp, i32p, i32p, fp, fp, i8p, fp, u8p, fp, sz, sz, sz, sz, sz, C.c_uint32, C.c_int]
+    L.q3_weight_bits.argtypes = [C.c_void_p]
     L.q3_op_rmsnorm.argtypes = [fp, fp, fp, sz, C.c_uint32, C.c_int]
     L.q3_op_softmax.argtypes = [fp, sz, C.c_uint32, C.c_int]
     L.q3_op_swiglu.argtypes = [fp, fp, sz, C.c_int]
@@ -622,6 +624,11 @@ class Transformer:
 
     def get_config(self) -> ModelConfig:
         return self._config
+
+    @property
+    def weight_bits(self) -> int:
+        """8, or 4 for a Q4 checkpoint (the width of the per-layer matrices; embedding and classifier are int8)"""
+        return int(self._lib.q3_weight_bits(self._h))
 
     # -- extensions -------------------------------------------------------------------------------
     def forward_argmax(self, token: int, pos: int) -> int:
@@ -1408,15 +1415,20 @@ class _Ops:
                                            group_size, self.device))
         return out
 
+    def gemv_role_w4(self, role: int, wq4, ws, n: int, rows: int, group_size: int, **kw) -> dict:
+        """gemv_role over the nibble rows of a Q4 checkpoint (q3_op_gemv_role_w4): wq4 = checkpoint.pack_q4 of the int8 weights,
+        n / 2 bytes per row; every role but ROLE_NORM_LOGITS."""
+        return self.gemv_role(role, wq4, ws, n, rows, group_size, _bits=4, **kw)
+
     def gemv_role(self, role: int, wq, ws, n: int, rows: int, group_size: int, x=None, norm_w=None, pre_q=None, pre_s=None,
-                  out=None, rows_kv: int = 0, head_dim: int = 0, strict: bool = True) -> dict:
+                  out=None, rows_kv: int = 0, head_dim: int = 0, strict: bool = True, _bits: int = 8) -> dict:
         """one fused GEMV launch of the decode plan (q3_op_gemv_role; role = ROLE_*).  Returns {"out", "tap" (NORM roles),
         "argmax" (LOGITS), "info": [table entry?, grid, threads per workgroup, rows per wave batch]}."""
-        wq = np.ascontiguousarray(wq, dtype=np.int8)
+        wq = np.ascontiguousarray(wq, dtype=np.uint8 if _bits == 4 else np.int8)
         ws = np.ascontiguousarray(ws, dtype=np.float32)
         n_out = rows + 2 * rows_kv if role == ROLE_NORM_QKV else rows
         n_w = n_out if role != ROLE_NORM_SWIGLU else 2 * rows
-        if wq.size != n_w * n or ws.size != n_w * (n // group_size):
+        if wq.size != n_w * n * _bits // 8 or ws.size != n_w * (n // group_size):
             raise ValueError(f"weights: {n_w} rows of {n} expected")
         norm = role in (ROLE_NORM_QKV, ROLE_NORM_SWIGLU, ROLE_NORM_LOGITS)
         o = np.zeros(n_out, dtype=np.float32) if out is None else np.array(out, dtype=np.float32, copy=True)
@@ -1445,10 +1457,11 @@ class _Ops:
         tap = np.zeros(n, dtype=np.float32) if norm else None
         am = np.full(1, -1, dtype=np.int32)
         info = np.zeros(4, dtype=np.int32)
-        _check(load_library().q3_op_gemv_role(role, self._fp(o), self._fp(tap) if norm else null_f, i32(am), i32(info),
-                                              f32(x, n), f32(norm_w, n), pq, f32(pre_s, n // group_size), self._i8(wq),
-                                              self._fp(ws), n, rows, rows_kv, head_dim, group_size,
-                                              0 if strict else FLAG_FAST, self.device))
+        L = load_library()
+        fn, wp = (L.q3_op_gemv_role_w4, wq.ctypes.data_as(C.POINTER(C.c_uint8))) if _bits == 4 else (L.q3_op_gemv_role, self._i8(wq))
+        _check(fn(role, self._fp(o), self._fp(tap) if norm else null_f, i32(am), i32(info), f32(x, n), f32(norm_w, n), pq,
+                  f32(pre_s, n // group_size), wp, self._fp(ws), n, rows, rows_kv, head_dim, group_size,
+                  0 if strict else FLAG_FAST, self.device))
         return {"out": o, "tap": tap, "argmax": int(am[0]), "info": [int(v) for v in info]}
 
     def rmsnorm(self, x, w, strict: bool = True) -> np.ndarray:

@@ -22,7 +22,7 @@ from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 
-from .checkpoint import ARCH_QWEN3, ModelShape, find_optimal_group_size, header_bytes, quantize_q80
+from .checkpoint import ARCH_QWEN3, ModelShape, find_optimal_group_size, header_bytes, pack_q4, quantize_q40, quantize_q80
 
 ARCH_NAME = "Qwen3ForCausalLM"                       # models/qwen3.rs:11
 EMBED_TOKENS_KEY = "model.embed_tokens.weight"       # models/qwen3.rs:12
@@ -189,16 +189,19 @@ def detect_shared_classifier(reader: TensorReader) -> bool:
     return False
 
 
-def export_model(model_dir: str, output_path: str, group_size: int = 64, log=None) -> ModelShape:
-    """lib.rs:22-36 + model_exporter.rs:65-101: writes `output_path`, returns the header that was written."""
+def export_model(model_dir: str, output_path: str, group_size: int = 64, log=None, weight_bits: int = 8) -> ModelShape:
+    """lib.rs:22-36 + model_exporter.rs:65-101: writes `output_path`, returns the header that was written.
+    weight_bits = 4: a Q4 file -- the seven per-layer matrices through quantize_q40 and pack_q4, everything else as at 8."""
     log = log or (lambda *_: None)
+    if weight_bits not in (4, 8):
+        raise ExportError(f"weight_bits must be 8 or 4, got {weight_bits}")
     info = load_model_info(model_dir)
     reader = TensorReader(model_dir)
     try:
         g = find_optimal_group_size(info.dim, group_size)                          # model_exporter.rs:39-44
         shared = detect_shared_classifier(reader)
         shape = ModelShape(info.dim, info.hidden_dim, info.n_layers, info.n_heads, info.n_kv_heads, info.vocab_size,
-                           info.max_seq_len, info.head_dim, shared, g, ARCH_QWEN3)
+                           info.max_seq_len, info.head_dim, shared, g, ARCH_QWEN3, weight_bits)
         with open(output_path, "wb") as out:
             out.write(header_bytes(shape))                                         # :164-191
             for pattern, layered, required in NORM_WEIGHT_LAYERS:                  # :193-228
@@ -228,12 +231,16 @@ def export_model(model_dir: str, output_path: str, group_size: int = 64, log=Non
                         w = merge_lora(w, la, lb, info.lora.lora_alpha, info.lora.r)
                 if w.size == 0:
                     continue
-                q, s, err = quantize_q80(w, g)
+                if weight_bits == 4 and comp is not None:
+                    q, s, err = quantize_q40(w, g)
+                    q = pack_q4(q)
+                else:
+                    q, s, err = quantize_q80(w, g)
                 worst = max(worst, err)
                 out.write(q.tobytes())
                 out.write(s.astype("<f4").tobytes())
                 log(f"quantized {name} ({w.size} weights, max error {err:.6g})")
-        log(f"Quantized {len(tensors)} weight tensors to Q8_0 with max error: {worst:.8f}")
+        log(f"Quantized {len(tensors)} weight tensors to {'Q4_0 (layers) / Q8_0' if weight_bits == 4 else 'Q8_0'} with max error: {worst:.8f}")
         return shape
     finally:
         reader.close()
@@ -245,9 +252,10 @@ def main(argv=None) -> int:
     ap.add_argument("model_dir")
     ap.add_argument("output")
     ap.add_argument("--group-size", type=int, default=64)
+    ap.add_argument("--weight-bits", type=int, default=8, choices=(8, 4), help="4: a Q4 checkpoint (int4 layer matrices)")
     a = ap.parse_args(argv)
     try:
-        shape = export_model(a.model_dir, a.output, a.group_size, log=lambda m: print(m, file=sys.stderr))
+        shape = export_model(a.model_dir, a.output, a.group_size, log=lambda m: print(m, file=sys.stderr), weight_bits=a.weight_bits)
     except ExportError as err:
         print(f"error: {err}", file=sys.stderr)
         return 1
