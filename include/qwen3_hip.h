@@ -1303,9 +1303,18 @@ int q3_op_lookup_draft(const int32_t* seq, size_t n, int ngram, int draft_len, i
  * computes (the expanded file; qwen3_rs_amd.checkpoint.expand_q4_checkpoint writes it): the i32 group dots are exact -- the kernel
  * forms 16 x the dot and shifts it back behind the integer group sum -- and the f32 terms and their order are the same code.
  * WHAT RUNS.  Single-stream decode launches the WB = 4 forms of k_gemv (csrc/q3_gemv.h) for the five GEMV launches of a layer -- 8-byte loads per
- * lane, half the weight bytes per token -- and the int8 kernel for the classifier; same plan, same graph.  The batched paths of
- * sections 2b .. 2u expand the layer matrices once into their int8 MFMA-ordered copy (k_pack_weights) and run as on the expanded
- * file: no byte is saved there.  q3_config and Q3_ABI_VERSION are unchanged; q3_parse_header accepts either magic.
+ * lane, half the weight bytes per token -- and the int8 kernel for the classifier; same plan, same graph.
+ * BATCHED PATHS.  q3_batch_init expands every layer matrix of a Q4 engine into the int8 MFMA-ordered copy (k_pack_weights) and
+ * keeps a second, nibble-packed copy of the q | k | v and the gate | up matrices (k_pack_weights_w4: one 16-byte piece per lane
+ * and pair of 64-byte MFMA steps, the 8-byte runs above kept as they are).  The QKV and W1|W3 launches of every plan of at most 32
+ * columns -- batched decode, column passes, verify passes, short prefill blocks -- read the nibbles: the WB = 4 form of k_bgemm
+ * (csrc/q3_batch.h), half the weight bytes of the two launches, the same bits.  A matrix whose rows are not a whole number of
+ * step pairs (dim % 128 != 0) has no such copy and runs the int8 kernel.  Wo and W2 (k_dgemm), the dense blocks (more than 32
+ * columns), the classifier and every fallback read the int8 copy: the 4-bit form of k_dgemm was slower than the int8 one.
+ * MEMORY.  Per weight of q | k | v | gate | up a Q4 engine with a batched context holds 0.5 B (the file's rows, single-stream
+ * decode) + 1 B (expanded copy) + 0.5 B (nibble-packed copy) = 2 B, per weight of o | down 0.5 + 1 = 1.5 B, where a Q8 engine
+ * holds 1 + 1 = 2 B of either; scales, embedding and classifier are the same in both.  On the 8B shape that is 12.7 GB of layer
+ * matrices against 13.9 GB.  q3_config and Q3_ABI_VERSION are unchanged; q3_parse_header accepts either magic.
  * ------------------------------------------------------------------------------------------------ */
 /* 8, or 4 for an engine created from a Q4 file (the width of the per-layer matrices; embedding and classifier are int8). */
 int q3_weight_bits(const q3_engine* e);
@@ -1315,6 +1324,24 @@ int q3_weight_bits(const q3_engine* e);
 int q3_op_gemv_role_w4(int role, float* out, float* tap_out, int32_t* argmax_index, int32_t* launch_info, const float* in,
                        const float* norm_w, const int8_t* pre_q, const float* pre_s, const uint8_t* wq4, const float* ws, size_t n,
                        size_t rows, size_t rows_kv, size_t head_dim, size_t group_size, uint32_t flags, int device);
+
+/* 4 when layer matmuls of the batched decode plans of this engine read nibbles (a Q4 engine after q3_batch_init, at least one
+ * layer matrix with a nibble-packed copy: QKV and W1|W3), 8 otherwise -- a Q8 engine, no batched context, or no eligible matrix. */
+int q3_batch_weight_bits(const q3_engine* e);
+
+/* One matmul launch of the batched decode plans alone, over nibble rows: wq4 / ws are the weight rows in checkpoint order (n / 2
+ * bytes and n / group_size scales per row), xq / xs the already-quantized activation columns ([n_cols][n] int8, [n_cols][n /
+ * group_size] scales, n_cols <= 32).  role picks the epilogue, the prologue half of the name does not apply:
+ *   Q3_ROLE_QUANT_RESID   `rows` weight rows;  out[n_cols][rows] += the product (out is read and written)
+ *   Q3_ROLE_NORM_SWIGLU   2 * rows weight rows, gate rows then up rows;  out[n_cols][rows] = silu(gate) * up
+ *   Q3_ROLE_NORM_QKV      rows + 2 * rows_kv weight rows (q | k | v);  out[n_cols][rows + 2 * rows_kv], a column's q, k, v in a row
+ * The operands are packed as q3_batch_init and the activation prologue pack them and the launch is the one the planner picks for
+ * this shape and column count on this device.  launch_info (4 ints, may be null): [0] 1 = k_dgemm, 0 = k_bgemm; [1] the weight
+ * width the launch read: 4, or 8 where the planner keeps the int8 kernel on the expanded copy, same result (n % 128 != 0, and
+ * every Q3_ROLE_QUANT_RESID launch); [2] grid; [3] threads per workgroup.  group_size 64, 128 or 256; rows and rows_kv multiples of 16.
+ * Q3_ERR_ARG: a null pointer, another role, n_cols outside 1 .. 32.  Q3_ERR_UNSUPPORTED: the shape limits above. */
+int q3_op_bmatmul_w4(int role, float* out, int32_t* launch_info, const int8_t* xq, const float* xs, size_t n_cols, const uint8_t* wq4,
+                     const float* ws, size_t n, size_t rows, size_t rows_kv, size_t group_size, int device);
 
 #ifdef __cplusplus
 }

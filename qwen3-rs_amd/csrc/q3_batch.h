@@ -30,7 +30,8 @@ constexpr int kMaxStreams = 32;
 // Destination tile of source tile t is tile0 + t * tile_stride (q|k|v concatenated; w1/w3 interleaved).
 // ------------------------------------------------------------------------------------------------
 // WB = 4: the source rows are the nibble rows of a Q4 checkpoint (8 bytes per 16-column run, include/qwen3_hip.h section 2v); a
-// piece is expanded to its 16 int8 bytes on the way, so the packed copy -- and everything that reads it -- is the int8 one.
+// piece is expanded to its 16 int8 bytes on the way, so the packed copy -- and everything that reads it (the dense blocks, the
+// classifier-side code, every fallback) -- is the int8 one.  The decode matmuls read the nibbles in place: k_pack_weights_w4 below.
 template <int WB = 8>
 __global__ __launch_bounds__(kWG) void k_pack_weights(const int8_t* __restrict__ wq, const float* __restrict__ ws,
                                                       int8_t* __restrict__ pq, float* __restrict__ ps, int rows, int n,
@@ -75,6 +76,42 @@ __global__ __launch_bounds__(kWG) void k_pack_weights(const int8_t* __restrict__
         ps[(dt * ng + g) * 16 + r] = ws[(t * 16 + r) * (size_t)ng + g];
     }
 }
+
+// The nibble-packed, MFMA-ordered copy of a Q4 layer matrix (the WB = 4 form of k_bgemm reads it; the scales are the
+// int8 copy's).  Number the 64-byte MFMA steps of a row t = g * NJ + j: lane (r, q) of step t owns the same 16 columns
+// [g*G + (q*NJ + j)*16, +16) of row r as in the int8 layout -- the packed activations stay as they are -- and its 8-byte run of
+// the checkpoint (nibble order of section 2v kept) is one half of a 16-byte piece shared by the steps 2p and 2p + 1:
+// [tile][pair p][lane][16 B], bytes 0-7 step 2p, bytes 8-15 step 2p + 1.  A wave's dwordx4 load is 1 KiB contiguous and carries
+// two MFMA steps; a tile is one sequential 8*K-byte stream.  Needs an even step count per row: n % 128 == 0 (host).
+__global__ __launch_bounds__(kWG) void k_pack_weights_w4(const int8_t* __restrict__ wq4, int8_t* __restrict__ pq4, int rows, int n,
+                                                         int G, int tile0, int tile_stride) {
+    const int nj = G >> 6, npair = n >> 7;
+    const size_t pieces = (size_t)(rows >> 4) * (size_t)npair * 64;
+    for (size_t p = (size_t)blockIdx.x * kWG + threadIdx.x; p < pieces; p += (size_t)gridDim.x * kWG) {
+        // destination-major enumeration: p = (t*npair + pair)*64 + lane
+        const int lane = (int)(p & 63);
+        const size_t rest = p >> 6;
+        const int pair = (int)(rest % npair);
+        const size_t t = rest / npair;
+        const int r = lane & 15, q = lane >> 4;
+        v2i h[2];
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const int step = 2 * pair + k, g = step / nj, j = step - g * nj;
+            const size_t col = (size_t)g * G + (size_t)(q * nj + j) * 16;
+            h[k] = *(const v2i*)(wq4 + (((t * 16 + r) * (size_t)n + col) >> 1));
+        }
+        const size_t dt = (size_t)tile0 + t * (size_t)tile_stride;
+        *(v4i*)(pq4 + ((dt * npair + pair) * 64 + lane) * 16) = (v4i){h[0].x, h[0].y, h[1].x, h[1].y};
+    }
+}
+// The int8x4 operands of one MFMA step from its 8-byte run (lo = columns 0-3 | 4-7, hi = 8-11 | 12-15): 16 x the nibbles, in
+// column order.  The i32 group dot is then exactly 16 x the true dot (64 * 16 * 8 * 127 * NJ < 2^31) and an arithmetic >> 4 of
+// the accumulator gives it back bit for bit: whatever follows is the int8 kernel's code on the int8 kernel's values.
+__device__ __forceinline__ v4i w4_operand(const int lo, const int hi) {
+    return (v4i){(lo << 4) & (int)0xF0F0F0F0u, lo & (int)0xF0F0F0F0u, (hi << 4) & (int)0xF0F0F0F0u, hi & (int)0xF0F0F0F0u};
+}
+__device__ __forceinline__ v4i w4_dots(const v4i c) { return (v4i){c.x >> 4, c.y >> 4, c.z >> 4, c.w >> 4}; }
 
 // ------------------------------------------------------------------------------------------------
 // Per-stream activation prologue: exactly the GEMV prologue (embedding / RMSNorm / quantize, same code), one
@@ -350,7 +387,11 @@ __host__ __device__ inline size_t bgemm_smem_bytes(int RT, int NT) {
     return 4 * ((size_t)RT * PG * NT * 256 + (size_t)RT * PG * 16 + (size_t)NT * PG * 16);
 }
 
-template <int EPI, int RT, int NT, int NJ>
+// WB = 4: a.wq is the nibble-packed copy (k_pack_weights_w4).  A wave's groups of a phase are consecutive and GW is even, so its
+// steps start at an even step and its pairs never straddle waves: Frag::a holds one piece per pair (half the registers; slot
+// i of the wave's pairs lives in a[rt][i / NJ][i % NJ]), issue_group requests the pieces whose second step closes in its group,
+// the MFMA loop unpacks in front of each step and shifts the group dot back.  Terms, fold, scale chunks and epilogues: the int8 code.
+template <int EPI, int RT, int NT, int NJ, int WB = 8>
 __global__ __launch_bounds__(kBThreads) void k_bgemm(const BGemmArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     constexpr int PG = BPhase<RT>::PG;        // groups per phase
@@ -365,6 +406,7 @@ __global__ __launch_bounds__(kBThreads) void k_bgemm(const BGemmArgs a) {
     const int nph = (ng + PG - 1) / PG;
     const int ntasks = a.ntiles / RT;
     const size_t tile_v4 = (size_t)ng * NJ * 64;              // v4i per packed tile (weights or activations)
+    const int npair = (ng * NJ) >> 1;                         // WB = 4: pieces per lane and weight tile (v4i per tile: npair * 64)
     const bool fold_thread = tid < NT * 256;                  // (stream, row) accumulator owner
     // The term tile of a (row tile, group, stream tile) is the MFMA result layout itself: lane l = 16 q + s of the producing
     // wave writes its four rows (4q .. 4q+3 of stream s) as ONE contiguous 16-byte piece at float 4 l, and fold thread
@@ -396,8 +438,17 @@ __global__ __launch_bounds__(kBThreads) void k_bgemm(const BGemmArgs a) {
 #pragma unroll
         for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
-            for (int j = 0; j < NJ; ++j)
+            for (int j = 0; j < NJ; ++j) {
+                if constexpr (WB == 4) {
+                    const int m = k * NJ + j;                 // step of the wave's phase; an odd one closes pair m / 2
+                    if (m & 1) {                              // (the tail phase clamps to a whole pair: a pair is all valid or all past the row)
+                        const int pr = min((((p * PG + wave * GW) * NJ) >> 1) + (m >> 1), npair - 1);
+                        F.a[rt][(m >> 1) / NJ][(m >> 1) % NJ] =
+                            __builtin_nontemporal_load((const v4i*)a.wq + ((size_t)(task * RT + rt) * npair + pr) * 64 + lane);
+                    }
+                } else
                 F.a[rt][k][j] = __builtin_nontemporal_load((const v4i*)a.wq + (size_t)(task * RT + rt) * tile_v4 + ((size_t)g * NJ + j) * 64 + lane);
+            }
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
@@ -443,8 +494,16 @@ __global__ __launch_bounds__(kBThreads) void k_bgemm(const BGemmArgs a) {
                 for (int nt = 0; nt < NT; ++nt) {
                     v4i c = {0, 0, 0, 0};
 #pragma unroll
-                    for (int j = 0; j < NJ; ++j)
+                    for (int j = 0; j < NJ; ++j) {
+                        if constexpr (WB == 4) {
+                            const int m = k * NJ + j;
+                            const v4i pc = cur.a[rt][(m >> 1) / NJ][(m >> 1) % NJ];
+                            const v4i wa = (m & 1) ? w4_operand(pc.z, pc.w) : w4_operand(pc.x, pc.y);
+                            c = __builtin_amdgcn_mfma_i32_16x16x64_i8(wa, cur.b[nt][k][j], c, 0, 0, 0);
+                        } else
                         c = __builtin_amdgcn_mfma_i32_16x16x64_i8(cur.a[rt][k][j], cur.b[nt][k][j], c, 0, 0, 0);
+                    }
+                    if constexpr (WB == 4) c = w4_dots(c);
                     cacc[rt][nt] = c;
                 }
             if (more) issue_group(nxt, ntask, np, k);

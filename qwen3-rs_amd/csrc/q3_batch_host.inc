@@ -84,6 +84,7 @@ struct BatchCtx {
     int att_pf_stride = 0;
     DevMem<int8_t> pq;           // packed weights, all matrices
     DevMem<float> ps;
+    DevMem<int8_t> pq4;          // Q4 engines: the nibble-packed copies of the layer matrices (k_pack_weights_w4; PM::q4_off)
     DevMem<float> qn;            // k_attn_pf2: normalised + rotated queries of the block, head pairs interleaved [cap][n_heads/2][hd][2]
     DevMem<float> x, q, kraw, xb, hb, logits;
     DevMem<float> key, value;
@@ -231,7 +232,8 @@ struct BatchCtx {
     DevMem<int> stop_seq_start;
     unsigned long long stop_seq_serial = 0;
     // packed-matrix directory
-    struct PM { size_t q_off, s_off; int ntiles, ng; };
+    // q4_off: the matrix in pq4, SIZE_MAX where it has no nibble-packed copy (an int8 matrix; an odd count of MFMA steps per row)
+    struct PM { size_t q_off, s_off; int ntiles, ng; size_t q4_off = SIZE_MAX; };
     std::vector<PM> m_qkv, m_wo, m_w13, m_w2;
     PM m_cls{};
 };
@@ -299,8 +301,13 @@ int batch_alloc(q3_engine* e, int max_streams, uint32_t ctx_len, bool with_kv, i
     const size_t S = b->ctx, B = max_streams, C = (size_t)(cap > kSpecMax ? cap : kSpecMax), BL = kSpecMax;
 
     // ---- packed weight directory
-    size_t qbytes = 0, sfloats = 0;
-    auto reserve = [&](int rows, int n) {
+    // A Q4 engine keeps a second, nibble-packed copy of QKV and W1|W3 where their rows are an even number of 64-byte MFMA steps
+    // (n % 128 == 0): the decode, column-pass and verify launches of the two read it (half the weight bytes).  Wo and W2 have no
+    // such copy -- the WB = 4 form of k_dgemm lost its A/B (profiles/w4_batch.md) -- and they, the dense blocks and every fallback
+    // read the expanded int8 copy.  Developer build: Q3_BATCH_W4=0 makes no such copy -- the expanded path, as before.
+    const bool w4 = e->weight_bits == 4 && dev_knob("Q3_BATCH_W4", 1) != 0;
+    size_t qbytes = 0, sfloats = 0, q4bytes = 0;
+    auto reserve = [&](int rows, int n, bool nibbles) {
         BatchCtx::PM m;
         m.q_off = qbytes;
         m.s_off = sfloats;
@@ -308,21 +315,27 @@ int batch_alloc(q3_engine* e, int max_streams, uint32_t ctx_len, bool with_kv, i
         m.ng = n / G;
         qbytes += (size_t)rows * n;
         sfloats += (size_t)rows * (n / G);
+        if (nibbles && w4 && n % 128 == 0) {
+            m.q4_off = q4bytes;
+            q4bytes += (size_t)rows * n / 2;
+        }
         return m;
     };
     for (int l = 0; l < L; ++l) {
-        b->m_qkv.push_back(reserve(ahd + 2 * kvd, dim));
-        b->m_wo.push_back(reserve(dim, ahd));
-        b->m_w13.push_back(reserve(2 * H, dim));
-        b->m_w2.push_back(reserve(dim, H));
+        b->m_qkv.push_back(reserve(ahd + 2 * kvd, dim, true));
+        b->m_wo.push_back(reserve(dim, ahd, false));
+        b->m_w13.push_back(reserve(2 * H, dim, true));
+        b->m_w2.push_back(reserve(dim, H, false));
     }
-    b->m_cls = reserve(V, dim);
+    b->m_cls = reserve(V, dim, false);
     int rc;
-    if ((rc = b->pq.alloc(qbytes)) || (rc = b->ps.alloc(sfloats))) return rc;
+    if ((rc = b->pq.alloc(qbytes)) || (rc = b->ps.alloc(sfloats)) || (q4bytes && (rc = b->pq4.alloc(q4bytes)))) return rc;
     // bits: 8, or the engine's weight_bits for a layer matrix (a Q4 checkpoint: expanded to int8 on the way, section 2v)
     auto pack = [&](const QT& t, int rows, int n, const BatchCtx::PM& m, int tile0, int tile_stride, int bits = 8) {
         hipLaunchKernelGGL(bits == 4 ? k_pack_weights<4> : k_pack_weights<8>, dim3(e->n_cu * 8), dim3(kWG), 0, e->stream, t.q, t.s, b->pq + m.q_off, b->ps + m.s_off,
                            rows, n, G, tile0, tile_stride);
+        if (m.q4_off != SIZE_MAX)
+            hipLaunchKernelGGL(k_pack_weights_w4, dim3(e->n_cu * 8), dim3(kWG), 0, e->stream, t.q, b->pq4 + m.q4_off, rows, n, G, tile0, tile_stride);
     };
     for (int l = 0; l < L; ++l) {
         pack(e->wq[l], ahd, dim, b->m_qkv[l], 0, 1, e->weight_bits);
@@ -416,6 +429,8 @@ int prefill_block_cap(const q3_engine* e) {
 extern "C" {
 
 int q3_batch_init(q3_engine* e, int max_streams, uint32_t ctx_len) { return batch_alloc(e, max_streams, ctx_len, true); }
+
+int q3_batch_weight_bits(const q3_engine* e) { return e && e->batch && e->batch->pq4 ? 4 : 8; }
 
 /* q3_prefill with the prompt walked in blocks of up to 32 consecutive positions: each block is ONE pass over the
  * weights on the matrix cores (the positions of the block play the role of the streams of q3_forward_batch, all

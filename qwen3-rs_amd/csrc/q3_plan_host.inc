@@ -31,17 +31,28 @@ BQuantFn bquant_fn(int pro, int nn, int parts, bool spec) {
 #define Q3_BY_EPI(epi, F, ...)                                                                     \
     ((epi) == EPI_QKV ? F<EPI_QKV>(__VA_ARGS__) : (epi) == EPI_RESID ? F<EPI_RESID>(__VA_ARGS__) : \
      (epi) == EPI_SWIGLU ? F<EPI_SWIGLU>(__VA_ARGS__) : F<EPI_LOGITS>(__VA_ARGS__))
+// wb: 8, or 4 for the nibble-packed copy of a Q4 layer matrix: QKV and W1|W3 (the classifier is int8 in a Q4 file; the residual
+// launches keep the int8 kernels)
 template <int EPI, int RT, int NT>
-BGemmFn pick_bgemm_nj(int NJ) {
+BGemmFn pick_bgemm_nj(int NJ, int wb) {
+    if constexpr (EPI == EPI_QKV || EPI == EPI_SWIGLU) {
+        if (wb == 4) {
+            if (NJ == 1) return (BGemmFn)k_bgemm<EPI, RT, NT, 1, 4>;
+            if (NJ == 2) return (BGemmFn)k_bgemm<EPI, RT, NT, 2, 4>;
+            if (NJ == 4) return (BGemmFn)k_bgemm<EPI, RT, NT, 4, 4>;
+            return nullptr;
+        }
+    }
+    if (wb != 8) return nullptr;
     if (NJ == 1) return (BGemmFn)k_bgemm<EPI, RT, NT, 1>;
     if (NJ == 2) return (BGemmFn)k_bgemm<EPI, RT, NT, 2>;
     if (NJ == 4) return (BGemmFn)k_bgemm<EPI, RT, NT, 4>;
     return nullptr;
 }
 template <int EPI>
-BGemmFn pick_bgemm(int RT, int NT, int NJ) {
-    if (RT == 2) return NT == 1 ? pick_bgemm_nj<EPI, 2, 1>(NJ) : pick_bgemm_nj<EPI, 2, 2>(NJ);
-    if constexpr (EPI != EPI_SWIGLU) return NT == 1 ? pick_bgemm_nj<EPI, 1, 1>(NJ) : pick_bgemm_nj<EPI, 1, 2>(NJ);
+BGemmFn pick_bgemm(int RT, int NT, int NJ, int wb) {
+    if (RT == 2) return NT == 1 ? pick_bgemm_nj<EPI, 2, 1>(NJ, wb) : pick_bgemm_nj<EPI, 2, 2>(NJ, wb);
+    if constexpr (EPI != EPI_SWIGLU) return NT == 1 ? pick_bgemm_nj<EPI, 1, 1>(NJ, wb) : pick_bgemm_nj<EPI, 1, 2>(NJ, wb);
     return nullptr;
 }
 // the dense prefill kernels have no classifier form
@@ -64,9 +75,55 @@ BGemmFn pick_pgemm3(int ptw, int gs) {      // quantization groups per barrier: 
     return nullptr;
 }
 // k_dgemm of a residual launch (Wo, W2) at group 64: the 16-group ring where the row length allows it, else 8; nullptr: k_bgemm
+// (int8 only: its WB = 4 form, a ring slot per pair of groups, lost the A/B on both residual launches -- profiles/w4_batch.md)
 BGemmFn pick_dgemm(int ng, int& depth) {
     depth = ng % 16 == 0 ? 16 : (ng % 8 == 0 ? 8 : 0);
     return depth == 16 ? (BGemmFn)k_dgemm<16> : (depth == 8 ? (BGemmFn)k_dgemm<8> : nullptr);
+}
+// the launches that read the nibble-packed copy of a Q4 layer matrix: QKV and W1|W3 (k_bgemm); the residual launches stay int8
+bool w4_epi(int epi) { return epi == EPI_QKV || epi == EPI_SWIGLU; }
+// The launch of a matmul over at most 32 columns (decode, column-pass, verify and short prefill plans; q3_op_bmatmul_w4): k_dgemm
+// for the residual launches at group 64 where `dgemm` allows it and the row length has a ring, else k_bgemm.  ntiles x ng: the
+// packed matrix; wb: the width of the copy the launch reads.
+struct DecodeGemm {
+    BGemmFn fn = nullptr;
+    unsigned grid = 1, blk = 0;
+    size_t smem = 0;
+    bool dg = false;             // k_dgemm
+};
+DecodeGemm decode_gemm(int epi, int ntiles, int ng, int NT, int NJ, int n_cu, bool dgemm, int wb) {
+    DecodeGemm d;
+    int depth = 0;
+    if ((d.fn = (dgemm && epi == EPI_RESID) ? pick_dgemm(ng, depth) : nullptr)) {
+        // decode, group 64, residual launches (Wo, W2): every wave owns a (row tile, stream tile) accumulator tile for the whole
+        // contraction (k_dgemm).  Same-box A/B on the 8B shape (profiles/r04_batch32_dgemm.md): the residual launches gain 3-4 % of
+        // the step; QKV (11.6 vs 12.9 us), W1|W3 with the fused quantizer (27.7 vs 22.5 + 4.8 us) and the classifier (131-136 vs
+        // 130 us) in this form do not beat k_bgemm
+        d.dg = true;
+        d.grid = (unsigned)(((long)ntiles * NT + kDgWaves - 1) / kDgWaves);
+        d.blk = (unsigned)kDgWaves * 64;
+        d.smem = dgemm_smem_bytes(depth);
+        return d;
+    }
+    // one workgroup per row task (RT tiles), two workgroups per CU (64 KiB term tile each).  Two tiles per task
+    // share the activation fragments (cost ~1.7x one tile) -- worth it once that saves rounds over the CUs.
+    const long slots = (long)n_cu * dev_knob("Q3_BATCH_WG_PER_CU", 2);
+    int RT = 2;
+    if (epi != EPI_SWIGLU) {
+        const long r1 = (ntiles + slots - 1) / slots, r2 = (ntiles / 2 + slots - 1) / slots;
+        RT = (ntiles % 2 == 0 && r2 * 17 < r1 * 10) ? 2 : 1;
+        // between one and two row tiles per CU (QKV of the 4B / 8B shapes: 384 tiles) single-tile tasks put two workgroups
+        // on half of the CUs and one on the rest; pairs give 192 CUs one task each (r04 same-box A/B: 3.376 -> 3.358 ms / step)
+        if (ntiles % 2 == 0 && ntiles > n_cu && ntiles / 2 <= n_cu) RT = 2;
+        const int force_rt = dev_knob("Q3_BATCH_RT", 0);
+        if (force_rt && (ntiles % force_rt) == 0) RT = force_rt;
+    }
+    const long ntasks = ntiles / RT;
+    d.grid = (unsigned)(ntasks < slots ? ntasks : slots);
+    d.blk = kBThreads;
+    d.smem = bgemm_smem_bytes(RT, NT);
+    d.fn = Q3_BY_EPI(epi, pick_bgemm, RT, NT, NJ, wb);
+    return d;
 }
 // per-kv-head decode attention: k_attn_gqa2 (staging and arithmetic on separate waves; head_dim 128, 2 or 4 query heads per workgroup)
 // or k_attn_gqa, specialised for head_dim 128 with the same two counts.  kvm: the query heads of one workgroup (attn_head_parts)
@@ -471,7 +528,6 @@ struct PlanBuilder {
         BGemmFn fn = nullptr;
         unsigned grid = 1, blk = 0;
         size_t smem = 0;
-        int depth = 0;
         // LDS-staged workgroup tiles of 4 row tiles x 8 or 4 position tiles (k_pgemm3, round 4), two workgroups per CU, the grid walks
         // the (row block, position block) list.  Tile width by measurement (4B shape, us per 256 positions, profiles/r04_prefill_ab.txt):
         // W1|W3 (608 tiles of 4 x 8) 45.5 vs 50.8 for 4 x 4 vs 53.2 k_pgemm; Wo / W2 (80 tiles of 4 x 8) 46.5 vs 33.9 vs 39.0; QKV 22.2 vs
@@ -503,40 +559,22 @@ struct PlanBuilder {
             if (!(fn = Q3_BY_EPI(epi, pick_pgemm, RT, PT))) return fail(Q3_ERR_UNSUPPORTED, "no dense prefill kernel for tile %d x %d", RT, PT);
             grid = (unsigned)std::min<long>((nt_ + 3) / 4, 3L * e->n_cu);
             blk = kPgThreads;
-        } else if ((fn = (dgemm && epi == EPI_RESID) ? pick_dgemm(m.ng, depth) : nullptr)) {
-            // decode, group 64, residual launches (Wo, W2): every wave owns a (row tile, stream tile) accumulator tile for the whole
-            // contraction (k_dgemm).  Same-box A/B on the 8B shape (profiles/r04_batch32_dgemm.md): the residual launches gain 3-4 % of
-            // the step; QKV (11.6 vs 12.9 us), W1|W3 with the fused quantizer (27.7 vs 22.5 + 4.8 us) and the classifier (131-136 vs
-            // 130 us) in this form do not beat k_bgemm
-            grid = (unsigned)(((long)m.ntiles * NT + kDgWaves - 1) / kDgWaves);
-            blk = (unsigned)kDgWaves * 64;
-            smem = dgemm_smem_bytes(depth);
         } else {
-            a.stamps = stamp_cells();
-            // one workgroup per row task (RT tiles), two workgroups per CU (64 KiB term tile each).  Two tiles per task
-            // share the activation fragments (cost ~1.7x one tile) -- worth it once that saves rounds over the CUs.
-            const long slots = (long)e->n_cu * dev_knob("Q3_BATCH_WG_PER_CU", 2);
-            int RT = 2;
-            if (epi != EPI_SWIGLU) {
-                const long r1 = (m.ntiles + slots - 1) / slots, r2 = (m.ntiles / 2 + slots - 1) / slots;
-                RT = (m.ntiles % 2 == 0 && r2 * 17 < r1 * 10) ? 2 : 1;
-                // between one and two row tiles per CU (QKV of the 4B / 8B shapes: 384 tiles) single-tile tasks put two workgroups
-                // on half of the CUs and one on the rest; pairs give 192 CUs one task each (r04 same-box A/B: 3.376 -> 3.358 ms / step)
-                if (m.ntiles % 2 == 0 && m.ntiles > e->n_cu && m.ntiles / 2 <= e->n_cu) RT = 2;
-                const int force_rt = dev_knob("Q3_BATCH_RT", 0);
-                if (force_rt && (m.ntiles % force_rt) == 0) RT = force_rt;
-            }
-            const long ntasks = m.ntiles / RT;
-            grid = (unsigned)(ntasks < slots ? ntasks : slots);
-            blk = kBThreads;
-            smem = bgemm_smem_bytes(RT, NT);
+            // at most 32 columns: the layer matrices of a Q4 engine are read as nibbles where they have that copy (BatchCtx::PM)
+            const bool w4 = w4_epi(epi) && m.q4_off != SIZE_MAX;
+            if (w4) a.wq = b->pq4 + m.q4_off;
+            const DecodeGemm d = decode_gemm(epi, m.ntiles, m.ng, NT, NJ, e->n_cu, dgemm, w4 ? 4 : 8);
+            if (!(fn = d.fn)) return fail(Q3_ERR_UNSUPPORTED, "no batched kernel for group size %d", G);
+            grid = d.grid;
+            blk = d.blk;
+            smem = d.smem;
+            if (!d.dg) a.stamps = stamp_cells();
             if (epi == EPI_LOGITS) {
                 if ((int)grid > b->nslots) return fail(Q3_ERR_HIP, "argmax slot capacity");
                 a.slots = b->slots;
                 a.nslots = b->nslots;
                 nslots_used = (int)grid;
             }
-            if (!(fn = Q3_BY_EPI(epi, pick_bgemm, RT, NT, NJ))) return fail(Q3_ERR_UNSUPPORTED, "no batched kernel for group size %d", G);
         }
         return add(fam, fn, dim3(grid), dim3(blk), smem, a);
     }
@@ -876,3 +914,94 @@ void plans_drop(BatchCtx* b, PlanDrop what) {
 }
 
 }  // namespace
+
+extern "C" {
+
+// One matmul launch of the batched decode plans over the nibble rows of a Q4 matrix (section 2v): the operands are packed as
+// q3_batch_init and k_bquant leave them, the launch is decode_gemm()'s.
+int q3_op_bmatmul_w4(int role, float* out, int32_t* launch_info, const int8_t* xq, const float* xs, size_t n_cols, const uint8_t* wq4,
+                     const float* ws, size_t n, size_t rows, size_t rows_kv, size_t group_size, int device) {
+    int rc = op_begin(device);
+    if (rc) return rc;
+    int epi;
+    switch (role) {
+        case Q3_ROLE_NORM_QKV: epi = EPI_QKV; break;
+        case Q3_ROLE_NORM_SWIGLU: epi = EPI_SWIGLU; break;
+        case Q3_ROLE_QUANT_RESID: epi = EPI_RESID; break;
+        default: return fail(Q3_ERR_ARG, "role %d has no batched 4-bit matmul (QKV, SWIGLU and QUANT_RESID have)", role);
+    }
+    if (!out || !xq || !xs || !wq4 || !ws) return fail(Q3_ERR_ARG, "null pointer");
+    if (n_cols == 0 || n_cols > (size_t)kMaxStreams) return fail(Q3_ERR_ARG, "n_cols %zu out of range (1..%d)", n_cols, kMaxStreams);
+    const bool qkv = epi == EPI_QKV;
+    if ((group_size != 64 && group_size != 128 && group_size != 256) || n == 0 || n % group_size || n > 65536 || rows == 0 || rows % 16 ||
+        rows > (1u << 22) || (qkv && (rows_kv == 0 || rows_kv % 16 || rows_kv > (1u << 22))))
+        return fail(Q3_ERR_UNSUPPORTED, "unsupported n/group_size/rows (group 64, 128 or 256; heights in multiples of the 16-row tile)");
+    const int G = (int)group_size, ng = (int)(n / group_size), NJ = G / 64, NT = n_cols <= 16 ? 1 : 2;
+    const size_t wrows = qkv ? rows + 2 * rows_kv : (epi == EPI_SWIGLU ? 2 * rows : rows);   // weight rows
+    const size_t orows = qkv ? rows + 2 * rows_kv : rows;                                    // output floats per column
+    hipDeviceProp_t prop;
+    HIP_TRY(hipGetDeviceProperties(&prop, device));
+    const int n_cu = prop.multiProcessorCount;
+    const bool w4 = w4_epi(epi) && n % 128 == 0 && dev_knob("Q3_BATCH_W4", 1) != 0;
+
+    // activations: whole stream tiles, idle columns zero; k_pack_weights<8> writes the operand order of k_bquant (streams for rows)
+    const size_t xcols = (size_t)NT * 16;
+    std::vector<int8_t> hxq(xcols * n, 0);
+    std::vector<float> hxs(xcols * ng, 0.0f);
+    memcpy(hxq.data(), xq, n_cols * n);
+    memcpy(hxs.data(), xs, 4 * n_cols * (size_t)ng);
+    OpBuf dxq, dxs, dwq, dws, dxp, dxsp, dpq, dps, dpq4, dout, dst;
+    if ((rc = dxq.upload(hxq.data(), xcols * n)) || (rc = dxs.upload(hxs.data(), 4 * xcols * ng)) || (rc = dwq.upload(wq4, wrows * n / 2)) ||
+        (rc = dws.upload(ws, 4 * wrows * ng)) || (rc = dxp.alloc(xcols * n)) || (rc = dxsp.alloc(4 * xcols * ng)) ||
+        (rc = dpq.alloc(wrows * n)) || (rc = dps.alloc(4 * wrows * ng)) || (w4 && (rc = dpq4.alloc(wrows * n / 2))))
+        return rc;
+    if (epi == EPI_RESID) rc = dout.upload(out, 4 * n_cols * orows);      // x += W xq
+    else rc = dout.alloc(4 * n_cols * orows);
+    if (rc) return rc;
+    std::vector<State> st0(n_cols, State{});                              // position 0 of every column's own cache row
+    if ((rc = dst.upload(st0.data(), sizeof(State) * n_cols))) return rc;
+    const dim3 pgrid((unsigned)n_cu * 8), pblk(kWG);
+    hipLaunchKernelGGL(k_pack_weights<8>, pgrid, pblk, 0, 0, dxq.as<int8_t>(), dxs.as<float>(), dxp.as<int8_t>(), dxsp.as<float>(), (int)xcols, (int)n, G, 0, 1);
+    // segments of the weight rows: q | k | v concatenated, w1 | w3 interleaved by tiles, as batch_alloc lays them out
+    struct SegRows { size_t row0, nrows; int tile0, tile_stride; };
+    SegRows segs[3] = {{0, wrows, 0, 1}, {0, 0, 0, 1}, {0, 0, 0, 1}};
+    int nseg = 1;
+    if (epi == EPI_SWIGLU) { segs[0] = {0, rows, 0, 2}; segs[1] = {rows, rows, 1, 2}; nseg = 2; }
+    for (int i = 0; i < nseg; ++i) {
+        const int8_t* q = dwq.as<int8_t>() + segs[i].row0 * (n / 2);
+        const float* s = dws.as<float>() + segs[i].row0 * ng;
+        hipLaunchKernelGGL(k_pack_weights<4>, pgrid, pblk, 0, 0, q, s, dpq.as<int8_t>(), dps.as<float>(), (int)segs[i].nrows, (int)n, G, segs[i].tile0, segs[i].tile_stride);
+        if (w4) hipLaunchKernelGGL(k_pack_weights_w4, pgrid, pblk, 0, 0, q, dpq4.as<int8_t>(), (int)segs[i].nrows, (int)n, G, segs[i].tile0, segs[i].tile_stride);
+    }
+    HIP_TRY(hipGetLastError());
+
+    BGemmArgs a{};
+    a.wq = w4 ? dpq4.as<int8_t>() : dpq.as<int8_t>();
+    a.ws = dps.as<float>();
+    a.xq = dxp.as<int8_t>();
+    a.xs = dxsp.as<float>();
+    a.ng = ng;
+    a.ntiles = (int)(wrows / 16);
+    a.n_streams = (int)n_cols;
+    a.st = dst.as<State>();
+    a.out0 = dout.as<float>();
+    a.out0_stride = (long long)orows;
+    if (qkv) {
+        a.out1 = a.out0 + rows; a.out1_stride = (long long)orows;
+        a.out2 = a.out0 + rows + rows_kv; a.out2_stride = (long long)orows;
+        a.rows0 = (int)rows; a.rows1 = (int)rows_kv; a.pos_stride = (int)rows_kv;
+    }
+    const DecodeGemm d = decode_gemm(epi, a.ntiles, ng, NT, NJ, n_cu, G == 64 && dev_knob("Q3_BATCH_DGEMM", 1) != 0, w4 ? 4 : 8);
+    if (!d.fn) return fail(Q3_ERR_UNSUPPORTED, "no batched kernel for this shape");
+    if ((rc = launch_now(0, d.fn, dim3(d.grid), dim3(d.blk), d.smem, a)) || (rc = op_end())) return rc;
+    HIP_TRY(hipMemcpy(out, dout.p, 4 * n_cols * orows, hipMemcpyDeviceToHost));
+    if (launch_info) {
+        launch_info[0] = d.dg ? 1 : 0;
+        launch_info[1] = w4 ? 4 : 8;
+        launch_info[2] = (int32_t)d.grid;
+        launch_info[3] = (int32_t)d.blk;
+    }
+    return Q3_OK;
+}
+
+}  // extern "C"

@@ -43,6 +43,7 @@ EXPORTED_SYMBOLS = [
     "q3_guide_set_sparse", "q3_guide_get_sparse", "q3_op_guide_sparse",
     "q3_stop_seq_set", "q3_stop_seq_get", "q3_cols_schedule_stop_seq", "q3_op_stop_seq",
     "q3_generate_many_lookup", "q3_op_lookup_draft", "q3_weight_bits", "q3_op_gemv_role_w4",
+    "q3_batch_weight_bits", "q3_op_bmatmul_w4",
 ]
 LOOKUP_DRAFT_MAX = 31    # Q3_LOOKUP_DRAFT_MAX (section 2u)
 LOOKUP_CHUNK = 4096      # Q3_LOOKUP_CHUNK
@@ -324,6 +325,8 @@ def _bind(path: str) -> C.CDLL:
     L.q3_op_gemv_role.argtypes = [C.c_int, fp, fp, i32p, i32p, fp, fp, i8p, fp, i8p, fp, sz, sz, sz, sz, sz, C.c_uint32, C.c_int]
     L.q3_op_gemv_role_w4.argtypes = [C.c_int, fp, fp, i32p, i32p, fp, fp, i8p, fp, u8p, fp, sz, sz, sz, sz, sz, C.c_uint32, C.c_int]
     L.q3_weight_bits.argtypes = [C.c_void_p]
+    L.q3_batch_weight_bits.argtypes = [C.c_void_p]
+    L.q3_op_bmatmul_w4.argtypes = [C.c_int, fp, i32p, i8p, fp, sz, u8p, fp, sz, sz, sz, sz, C.c_int]
     L.q3_op_rmsnorm.argtypes = [fp, fp, fp, sz, C.c_uint32, C.c_int]
     L.q3_op_softmax.argtypes = [fp, sz, C.c_uint32, C.c_int]
     L.q3_op_swiglu.argtypes = [fp, fp, sz, C.c_int]
@@ -629,6 +632,11 @@ class Transformer:
     def weight_bits(self) -> int:
         """8, or 4 for a Q4 checkpoint (the width of the per-layer matrices; embedding and classifier are int8)"""
         return int(self._lib.q3_weight_bits(self._h))
+
+    @property
+    def batch_weight_bits(self) -> int:
+        """4 when the layer matmuls of the batched decode plans read nibbles (a Q4 engine after batch_init), 8 otherwise"""
+        return int(self._lib.q3_batch_weight_bits(self._h))
 
     # -- extensions -------------------------------------------------------------------------------
     def forward_argmax(self, token: int, pos: int) -> int:
@@ -1419,6 +1427,30 @@ class _Ops:
         """gemv_role over the nibble rows of a Q4 checkpoint (q3_op_gemv_role_w4): wq4 = checkpoint.pack_q4 of the int8 weights,
         n / 2 bytes per row; every role but ROLE_NORM_LOGITS."""
         return self.gemv_role(role, wq4, ws, n, rows, group_size, _bits=4, **kw)
+
+    def bmatmul_w4(self, role: int, wq4, ws, xq, xs, n: int, rows: int, group_size: int, rows_kv: int = 0, out=None) -> dict:
+        """one matmul launch of the batched decode plans over the nibble rows of a Q4 matrix (q3_op_bmatmul_w4): wq4 =
+        checkpoint.pack_q4 of the weight rows, xq [n_cols][n] int8 and xs [n_cols][n / group_size] the quantized activation
+        columns (n_cols <= 32).  role = ROLE_QUANT_RESID (out += product), ROLE_NORM_SWIGLU (gate rows then up rows) or
+        ROLE_NORM_QKV (q | k | v rows).  Returns {"out": [n_cols][rows (+ 2 rows_kv)], "info": [k_dgemm?, weight width read (4,
+        or 8: the int8 fallback), grid, threads per workgroup]}."""
+        xq = np.ascontiguousarray(xq, dtype=np.int8)
+        n_cols = xq.size // n
+        xs = np.ascontiguousarray(xs, dtype=np.float32)
+        wq4 = np.ascontiguousarray(wq4, dtype=np.uint8)
+        ws = np.ascontiguousarray(ws, dtype=np.float32)
+        n_out = rows + 2 * rows_kv if role == ROLE_NORM_QKV else rows
+        n_w = 2 * rows if role == ROLE_NORM_SWIGLU else n_out
+        if wq4.size != n_w * n // 2 or ws.size != n_w * (n // group_size):
+            raise ValueError(f"weights: {n_w} rows of {n} expected")
+        if xq.size != n_cols * n or xs.size != n_cols * (n // group_size):
+            raise ValueError("activations: n_cols columns of n int8 and n / group_size scales expected")
+        o = np.zeros((n_cols, n_out), dtype=np.float32) if out is None else np.array(out, dtype=np.float32, copy=True).reshape(n_cols, n_out)
+        info = np.zeros(4, dtype=np.int32)
+        _check(load_library().q3_op_bmatmul_w4(role, self._fp(o), info.ctypes.data_as(C.POINTER(C.c_int32)), self._i8(xq), self._fp(xs),
+                                               n_cols, wq4.ctypes.data_as(C.POINTER(C.c_uint8)), self._fp(ws), n, rows, rows_kv,
+                                               group_size, self.device))
+        return {"out": o, "info": [int(v) for v in info]}
 
     def gemv_role(self, role: int, wq, ws, n: int, rows: int, group_size: int, x=None, norm_w=None, pre_q=None, pre_s=None,
                   out=None, rows_kv: int = 0, head_dim: int = 0, strict: bool = True, _bits: int = 8) -> dict:
