@@ -1262,7 +1262,7 @@ int q3_op_stop_seq(const int32_t* dflt, const uint32_t* row_off, const q3_guide_
  * LDS-staged chunks of Q3_LOOKUP_CHUNK; a per-wave and per-workgroup maximum of the matching start; the first chunk with a match
  * ends the search) -- and k_cols_sched_lookup where k_cols_sched stands.  The drafts lie behind the call's prompts, where the turn
  * kernel reads any prompt token: no plan, plan key or turn kernel changes, and one synchronisation per pass as in 2h.
- * FIRST VERSION, GREEDY AND PLAIN ONLY.  Q3_ERR_UNSUPPORTED, naming the setting, and the engine stays usable: a sampling batch
+ * GREEDY AND PLAIN ONLY (section 2w drafts under per-request samplers).  Q3_ERR_UNSUPPORTED, naming the setting, and the engine stays usable: a sampling batch
  * (q3_batch_sampler_set at temperature > 0); q3_sampler_penalties, q3_logit_bias_set, q3_guide_set or q3_guide_set_sparse in force;
  * q3_gen_logprobs on; a stop automaton of q3_stop_seq_set; a resident prefix of q3_batch_prefix_set; a Q3_FLAG_FAST engine.
  * ------------------------------------------------------------------------------------------------ */
@@ -1342,6 +1342,45 @@ int q3_batch_weight_bits(const q3_engine* e);
  * Q3_ERR_ARG: a null pointer, another role, n_cols outside 1 .. 32.  Q3_ERR_UNSUPPORTED: the shape limits above. */
 int q3_op_bmatmul_w4(int role, float* out, int32_t* launch_info, const int8_t* xq, const float* xs, size_t n_cols, const uint8_t* wq4,
                      const float* ws, size_t n, size_t rows, size_t rows_kv, size_t group_size, int device);
+
+/* ------------------------------------------------------------------------------------------------
+ * 2w. (behind 2v so that the earlier sections stay as they were.)  Prompt-lookup drafts under the sampler: section 2u for the
+ * sampled stop loop.  Drafts, rule 6 and the layout of a pass are section 2u's.  What changes is what a draft is held against:
+ *     the rule   of section 2d: a draft stands exactly when it is the token the sampler draws with the coin the plain loop would
+ *                use at that position.
+ *     draws      a decode-phase slot's run in a pass is its decode column and d draft columns.  Column j of the run is drawn with
+ *                the request's rng advanced j coins past the slot's state -- the state the plain loop has in front of its draw at
+ *                that position if every draft in front of it stands.  Draft columns still emit nothing.
+ *     accept     behind the pass, per decode-phase slot: draft k stands while it equals the token drawn from the column in front
+ *                of it; the draw behind the last standing draft is the request's next token.  The walk ends at a stop token and at
+ *                n_new.  The slot's rng is committed advanced by exactly 1 + standing drafts coins: the coins of rejected columns
+ *                are not spent, and the next pass draws position p + 1 + accepted with the coin the plain loop uses there.
+ *     T = 0      a request with temperature 0 follows the argmax rule of section 2u and spends no coin.
+ * out_tokens, n_out, EVERY SLOT'S RNG STATE AFTER THE CALL AND EVERY CACHE ROW A LATER COLUMN CAN READ ARE BIT-IDENTICAL TO
+ * q3_generate_many_stop ON THE SAME REQUESTS, STOP LIST AND SAMPLER ARRAYS, FOR ANY ngram, draft_len AND fill_width.
+ * q3_sampler_top_k in force is honoured: the draws are the launches of the sampled column plans, top-k form included.
+ * What runs (csrc/q3_lookup_dev.h).  k_cols_sched_lookup also writes the sampled plans' per-column record of every pass (run index,
+ * drawn, not last) on the device, so nothing is patched from the host between passes; the draws of a pass are the sampled plan's
+ * own, one workgroup per column, draft columns next to decode columns; k_lookup_draft walks the drawn tokens and commits the
+ * slot's rng from the sampler state the last standing column left.  One synchronisation per pass; no plan or plan key changes.
+ * Q3_ERR_UNSUPPORTED, naming the setting, and the engine stays usable: q3_sampler_penalties, q3_logit_bias_set, q3_guide_set or
+ * q3_guide_set_sparse in force; q3_gen_logprobs on; a stop automaton of q3_stop_seq_set; a resident prefix of q3_batch_prefix_set;
+ * a Q3_FLAG_FAST engine.
+ * ------------------------------------------------------------------------------------------------ */
+/* The sampled q3_generate_many_stop with drafts.  Arguments and output layout are q3_generate_many_lookup's plus the three
+ * per-request sampler arrays of q3_generate_many_stop, all required.  ngram, draft_len and fill_width are checked first.
+ * Q3_ERR_ARG: ngram, draft_len or fill_width out of range; a null engine; everything the sampled q3_generate_many_stop rejects.
+ * Q3_ERR_UNSUPPORTED: the list above.  Q3_ERR_INTERNAL: as for q3_generate_many_stop. */
+int q3_generate_many_lookup_draw(q3_engine* e, const int32_t* prompts /* concatenated */, const size_t* prompt_len, const size_t* n_new,
+                                 size_t n_requests, const float* temperature, const float* topp, const uint64_t* seeds,
+                                 const int32_t* stop_tokens, size_t n_stop, int ngram, int draft_len, int fill_width,
+                                 int32_t* out_tokens /* concatenated, n_new[r] each */, size_t* n_out /* [n_requests] */, q3_cols_stats* stats,
+                                 q3_lookup_stats* lookup_stats);
+
+/* The rng state of KV slot `slot` as the last sampled q3_generate_many_* loop left it (the loops of sections 2f, 2h, 2i and this
+ * one keep one sampler per slot; a request loads its seed into the slot it is admitted to).  Waits for the stream.
+ * Q3_ERR_ARG: a null argument; no sampled loop has run on this batched state; slot outside 0 .. max_streams - 1. */
+int q3_batch_slot_rng(q3_engine* e, int slot, uint64_t* rng_state);
 
 #ifdef __cplusplus
 }

@@ -17,7 +17,14 @@
 // suffix, last token of the window first, and stops at its first -- largest -- match; a butterfly over the wave's lanes and one LDS
 // word per wave give the workgroup's largest match, and the first chunk that holds one ends the search.  LDS holds the last
 // kLookupGram tokens of every window; where ngram is longer the tokens in front are compared from device memory, only for the
-// starts that passed in LDS.  No floating point anywhere in this file.
+// starts that passed in LDS.  No floating point arithmetic anywhere in this file.
+//
+// Under the sampler (section 2w) the same two kernels run next to the sampled plans' ColsDraw.  The step also writes the ColAux
+// row: column j of a decode-phase slot's run -- its decode column and the drafts behind it -- is drawn with the slot's rng advanced
+// j coins, keep set, last clear, so the plan's draw launches draw every column of the run, a workgroup each, and the turn kernel
+// leaves the slot's rng alone.  ColsCtl::next then holds the DRAWN token of every column (the argmax for a temperature-0 slot), the
+// walk reads it as it reads the argmaxes, and commits the slot's rng itself: the state the last standing column left behind its
+// coin, 1 + standing drafts coins past the slot's state.  The coins of rejected columns are not spent.
 #pragma once
 
 namespace q3 {
@@ -128,8 +135,10 @@ __host__ __device__ inline int lookup_accept(const SchedSlot& t, const LookupSlo
 }
 
 // One workgroup per KV slot, between two passes: the accept walk, then the draft of the next pass.  tail: the scratch behind the
-// call's prompts.
-__global__ __launch_bounds__(kLookupThreads) void k_lookup_draft(const ColsStopDev* d, ColsCtl* ctl, LookupDev* lk, int* tail) {
+// call's prompts.  dr: null, or the loop draws (section 2w): cs[j] is the sampler state of column j behind its coin, and the walk
+// commits the rng of a slot that draws -- a temperature-0 slot spends no coin, as in the plain loop.
+__global__ __launch_bounds__(kLookupThreads) void k_lookup_draft(const ColsStopDev* d, ColsCtl* ctl, LookupDev* lk, int* tail, const ColsDraw* dr,
+                                                                 const SamplerState* cs) {
     __shared__ int sh_g;
     const int i = blockIdx.x;
     const SchedSlot t = d->sched.slot[i];
@@ -140,6 +149,10 @@ __global__ __launch_bounds__(kLookupThreads) void k_lookup_draft(const ColsStopD
         if (t.req >= 0 && t.took < 0) {
             committed = lookup_accept(t, ls, d->sched.stop, d->sched.n_stop, ctl->next, draft, ctl->out_tokens + t.ooff, &ctl->slot_last[i]);
             g = t.g + committed;
+            if (dr != nullptr) {
+                SamplerState* ss = dr->slot_ss + i;
+                if (ss->temperature != 0.0f) ss->rng = cs[ls.col0 + committed - 1].rng;
+            }
         } else if (sched_slot_emitted(t)) {
             g = 1;                                          // a prompt run that produced y_0
         }
@@ -161,8 +174,10 @@ __global__ __launch_bounds__(kLookupThreads) void k_lookup_draft(const ColsStopD
 
 // cols_sched_step (q3_stop.h) with drafts.  Rules 4 and 5 read the walk's count where the slot had a decode column; rules 1 to 3 lay
 // out the same base columns; rule 6 puts up to max(plan width of the base columns, fill_width) - base columns draft columns directly
-// behind the decode columns of their slots, in slot order, at most dlen each.  Draft columns emit nothing.
-__host__ __device__ inline void cols_sched_step_lookup(ColsSched& s, LookupDev& lk, const int* slot_last, ColEnt* row) {
+// behind the decode columns of their slots, in slot order, at most dlen each.  Draft columns emit nothing.  aux: null, or the ColAux
+// row of the sampled plans: prompt runs as cols_sched_step writes them, the columns of a decode-phase slot's run by their index in
+// the run, every one drawn, none last (k_lookup_draft commits that slot's rng).
+__host__ __device__ inline void cols_sched_step_lookup(ColsSched& s, LookupDev& lk, const int* slot_last, ColEnt* row, ColAux* aux) {
     const int ms = s.max_streams;
     for (int i = 0; i < ms; ++i) {
         SchedSlot& t = s.slot[i];
@@ -232,10 +247,15 @@ __host__ __device__ inline void cols_sched_step_lookup(ColsSched& s, LookupDev& 
         LookupSlot& ls = lk.slot[i];
         const int pos = s.pos_base + t.fed + t.g - 1;
         row[cols] = ColEnt{i, pos, -1, t.ooff + t.g};
+        if (aux) aux[cols] = ColAux{-1, 0, 1, 0};
         ls.col0 = cols++;
         ls.nd = ls.dlen < spare ? ls.dlen : spare;
         spare -= ls.nd;
-        for (int k = 0; k < ls.nd; ++k) row[cols++] = ColEnt{i, pos + 1 + k, lk.draft_src0 + i * kLookupDraftMax + k, -1};
+        for (int k = 0; k < ls.nd; ++k) {
+            row[cols] = ColEnt{i, pos + 1 + k, lk.draft_src0 + i * kLookupDraftMax + k, -1};
+            if (aux) aux[cols] = ColAux{-1, 1 + k, 1, 0};
+            ++cols;
+        }
         ++s.stats.decode_columns;
     }
     // 3. prompt-phase slots
@@ -244,25 +264,32 @@ __host__ __device__ inline void cols_sched_step_lookup(ColsSched& s, LookupDev& 
         if (t.req < 0 || t.took <= 0) continue;
         for (int k = 0; k < t.took; ++k) {
             const int pos = t.fed + k;
-            row[cols++] = ColEnt{i, s.pos_base + pos, t.poff + pos, pos + 1 == t.plen ? t.ooff : -1};
+            const int out = pos + 1 == t.plen ? t.ooff : -1;
+            row[cols] = ColEnt{i, s.pos_base + pos, t.poff + pos, out};
+            if (aux) aux[cols] = ColAux{pos == 0 ? t.req : -1, k, out >= 0 ? 1 : 0, k == t.took - 1 ? 1 : 0};
+            ++cols;
         }
         s.stats.prompt_columns += (uint64_t)t.took;
     }
     ColEnt pad = row[cols - 1];
     pad.out = -1;
-    for (int j = cols; j < kColsMax; ++j) row[j] = pad;
+    for (int j = cols; j < kColsMax; ++j) {
+        row[j] = pad;
+        if (aux) aux[j] = ColAux{-1, aux[cols - 1].k, 0, 0};
+    }
     s.stats.live_columns += (uint64_t)cols;
     ++s.stats.passes;
     s.status = SchedStatus{cols, 0};
 }
 
 // k_cols_sched with the step above: the scheduler state, the lookup state and ColsCtl::slot_last are staged in LDS, one thread
-// steps, and the states and the row go back.  One workgroup, behind k_lookup_draft.
-__global__ __launch_bounds__(64) void k_cols_sched_lookup(ColsStopDev* d, ColsCtl* ctl, LookupDev* lk) {
-    static_assert(sizeof(ColsSched) % 4 == 0 && sizeof(LookupDev) % 4 == 0 && sizeof(ColEnt) == 16, "copied as words");
+// steps, and the states, the row and (draw) the ColAux row go back.  One workgroup, behind k_lookup_draft.
+__global__ __launch_bounds__(64) void k_cols_sched_lookup(ColsStopDev* d, ColsCtl* ctl, LookupDev* lk, int draw) {
+    static_assert(sizeof(ColsSched) % 4 == 0 && sizeof(LookupDev) % 4 == 0 && sizeof(ColEnt) == 16 && sizeof(ColAux) == 16, "copied as words");
     __shared__ ColsSched s;
     __shared__ LookupDev l;
     __shared__ ColEnt row[kColsMax];
+    __shared__ ColAux aux[kColsMax];
     __shared__ int last[kColsMax];
     const int t = threadIdx.x;
     constexpr int nw = (int)(sizeof(ColsSched) / 4), nl = (int)(sizeof(LookupDev) / 4);
@@ -274,12 +301,15 @@ __global__ __launch_bounds__(64) void k_cols_sched_lookup(ColsStopDev* d, ColsCt
     for (int i = t; i < nl; i += 64) lw[i] = glw[i];
     if (t < kColsMax) last[t] = ctl->slot_last[t];
     __syncthreads();
-    if (t == 0) cols_sched_step_lookup(s, l, last, row);
+    if (t == 0) cols_sched_step_lookup(s, l, last, row, draw ? aux : nullptr);
     __syncthreads();
     for (int i = t; i < nw; i += 64) gw[i] = sw[i];
     for (int i = t; i < nl; i += 64) glw[i] = lw[i];
     const SchedStatus st = s.status;
-    if (t < kColsMax && st.n_live > 0) d->row[t] = row[t];
+    if (t < kColsMax && st.n_live > 0) {
+        d->row[t] = row[t];
+        if (draw) d->aux[t] = aux[t];
+    }
     if (t == 0) {
         d->ncols = st.n_live;
         ctl->cursor = 0;

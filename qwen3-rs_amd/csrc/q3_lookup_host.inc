@@ -1,4 +1,4 @@
-// q3_lookup_host.inc -- host side of prompt-lookup drafts in the stop loop (include/qwen3_hip.h section 2u; included by
+// q3_lookup_host.inc -- host side of prompt-lookup drafts in the stop loop (include/qwen3_hip.h sections 2u and 2w; included by
 // q3_engine.hip behind q3_stop_host.inc, same translation unit).
 //
 // The loop is cols_generate_stop's: it takes a LookupArgs and calls the three hooks below where the lookup loop differs -- room for
@@ -24,15 +24,17 @@ int lookup_call_begin(q3_engine* e, const LookupArgs& a, size_t n_prompt) {
     return Q3_OK;
 }
 
-// between two passes: accept and draft per slot, then the step
-int lookup_sched_launch(q3_engine* e, size_t n_prompt) {
+// between two passes: accept and draft per slot, then the step.  draw (section 2w; cols_draw_alloc has run): the walk reads the column
+// sampler states the pass's draws left and commits the slots' rng, the step writes the ColAux row of the next pass
+int lookup_sched_launch(q3_engine* e, size_t n_prompt, bool draw) {
     BatchCtx* b = e->batch;
     ColsStopDev* d = b->cols_stop;
     int rc;
     if ((rc = launch_now(e->stream, k_lookup_draft, dim3(b->max_streams), dim3(kLookupThreads), 0, (const ColsStopDev*)d, (ColsCtl*)b->cols_ctl,
-                         (LookupDev*)b->lookup_dev, (int*)(b->cols_prompts + n_prompt))))
+                         (LookupDev*)b->lookup_dev, (int*)(b->cols_prompts + n_prompt), draw ? (const ColsDraw*)b->cols_draw : nullptr,
+                         draw ? (const SamplerState*)b->draw_cols.ss : nullptr)))
         return rc;
-    return launch_now(e->stream, k_cols_sched_lookup, dim3(1), dim3(64), 0, d, (ColsCtl*)b->cols_ctl, (LookupDev*)b->lookup_dev);
+    return launch_now(e->stream, k_cols_sched_lookup, dim3(1), dim3(64), 0, d, (ColsCtl*)b->cols_ctl, (LookupDev*)b->lookup_dev, draw ? 1 : 0);
 }
 
 // behind the last pass: the counts (the caller synchronises)
@@ -41,9 +43,64 @@ int lookup_call_end(q3_engine* e, q3_lookup_stats* out) {
     return Q3_OK;
 }
 
+// what both entry points refuse about their draft arguments, and about the engine's settings (sections 2u and 2w)
+int lookup_args_check(int ngram, int draft_len, int fill_width) {
+    if (ngram < 1) return fail(Q3_ERR_ARG, "ngram %d must be >= 1", ngram);
+    if (draft_len < 1 || draft_len > kLookupDraftMax) return fail(Q3_ERR_ARG, "draft_len %d out of range (1..%d)", draft_len, kLookupDraftMax);
+    if (fill_width != 0 && (fill_width < 1 || fill_width > kColsMax || (fill_width & (fill_width - 1))))
+        return fail(Q3_ERR_ARG, "fill_width %d is not 0 or a pass width (1, 2, 4, 8, 16, 32)", fill_width);
+    return Q3_OK;
+}
+int lookup_refusals(q3_engine* e, const char* who) {
+    static const char* const kPenNames[] = {"", "q3_sampler_penalties", "q3_logit_bias_set", "q3_guide_set", "q3_guide_set_sparse"};
+    static_assert(kPenOff == 0 && kPenOn == 1 && kPenAdj == 2 && kPenGuide == 3 && kPenGuideSp == 4, "kPenNames is indexed by the form");
+    const char* name = nullptr;
+    if (e->pen_form() != kPenOff) name = kPenNames[e->pen_form()];
+    else if (e->gen_logprobs >= 0) name = "q3_gen_logprobs";
+    else if (e->stop_seq.n_states) name = "q3_stop_seq_set";
+    else if (e->batch->prefix_n) name = "q3_batch_prefix_set";
+    if (name) return fail(Q3_ERR_UNSUPPORTED, "%s does not draft under %s: clear it, or call q3_generate_many_stop", who, name);
+    return Q3_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int q3_generate_many_lookup_draw(q3_engine* e, const int32_t* prompts, const size_t* prompt_len, const size_t* n_new, size_t n_requests,
+                                 const float* temperature, const float* topp, const uint64_t* seeds, const int32_t* stop_tokens, size_t n_stop,
+                                 int ngram, int draft_len, int fill_width, int32_t* out_tokens, size_t* n_out, q3_cols_stats* stats,
+                                 q3_lookup_stats* lookup_stats) {
+    g_err[0] = 0;
+    genlp_call_enter(e);
+    if (stats) *stats = q3_cols_stats{0, 0, 0, 0};
+    if (lookup_stats) *lookup_stats = q3_lookup_stats{0, 0};
+    int rc;
+    if ((rc = lookup_args_check(ngram, draft_len, fill_width))) return rc;          // in front of the engine: no device is touched
+    if ((rc = cols_prepare(e, "q3_generate_many_lookup_draw", true))) return rc;
+    if ((rc = lookup_refusals(e, "q3_generate_many_lookup_draw"))) return rc;
+    ColsRequests rq;
+    if ((rc = cols_requests_check(e, prompts, prompt_len, n_new, n_requests, true, temperature, topp, seeds, 0, out_tokens, rq))) return rc;
+    if (rq.n_prompt > (size_t)INT32_MAX - (size_t)kColsMax * kLookupDraftMax) return fail(Q3_ERR_ARG, "more than 2^31 tokens in one call");
+    q3_lookup_stats ls{0, 0};
+    const LookupArgs a{ngram, draft_len, fill_width, &ls};
+    if ((rc = cols_generate_stop(e, rq, stop_tokens, n_stop, out_tokens, n_out, stats, &a))) return rc;
+    if (lookup_stats) *lookup_stats = ls;
+    return Q3_OK;
+}
+
+int q3_batch_slot_rng(q3_engine* e, int slot, uint64_t* rng_state) {
+    g_err[0] = 0;
+    if (!e || !rng_state) return fail(Q3_ERR_ARG, "null argument");
+    if (!e->batch || !e->batch->cols_slot_samp) return fail(Q3_ERR_ARG, "no sampled q3_generate_many_* loop has run on this batched state");
+    if (slot < 0 || slot >= e->batch->max_streams) return fail(Q3_ERR_ARG, "slot %d out of range (0..%d)", slot, e->batch->max_streams - 1);
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    SamplerState h;
+    HIP_TRY(hipMemcpy(&h, e->batch->cols_slot_samp + slot, sizeof(h), hipMemcpyDeviceToHost));
+    *rng_state = h.rng;
+    return Q3_OK;
+}
 
 int q3_generate_many_lookup(q3_engine* e, const int32_t* prompts, const size_t* prompt_len, const size_t* n_new, size_t n_requests,
                             const int32_t* stop_tokens, size_t n_stop, int ngram, int draft_len, int fill_width, int32_t* out_tokens, size_t* n_out,
@@ -54,18 +111,8 @@ int q3_generate_many_lookup(q3_engine* e, const int32_t* prompts, const size_t* 
     if (lookup_stats) *lookup_stats = q3_lookup_stats{0, 0};
     int rc;
     if ((rc = cols_prepare(e, "q3_generate_many_lookup"))) return rc;
-    if (ngram < 1) return fail(Q3_ERR_ARG, "ngram %d must be >= 1", ngram);
-    if (draft_len < 1 || draft_len > kLookupDraftMax) return fail(Q3_ERR_ARG, "draft_len %d out of range (1..%d)", draft_len, kLookupDraftMax);
-    if (fill_width != 0 && (fill_width < 1 || fill_width > kColsMax || (fill_width & (fill_width - 1))))
-        return fail(Q3_ERR_ARG, "fill_width %d is not 0 or a pass width (1, 2, 4, 8, 16, 32)", fill_width);
-    // the first version drafts under the plain greedy loop only
-    static const char* const kPenNames[] = {"", "q3_sampler_penalties", "q3_logit_bias_set", "q3_guide_set", "q3_guide_set_sparse"};
-    static_assert(kPenOff == 0 && kPenOn == 1 && kPenAdj == 2 && kPenGuide == 3 && kPenGuideSp == 4, "kPenNames is indexed by the form");
-    const int pen = e->pen_form();
-    if (pen != kPenOff) return fail(Q3_ERR_UNSUPPORTED, "q3_generate_many_lookup does not draft under %s: clear it, or call q3_generate_many_stop", kPenNames[pen]);
-    if (e->gen_logprobs >= 0) return fail(Q3_ERR_UNSUPPORTED, "q3_generate_many_lookup does not draft under q3_gen_logprobs: turn it off, or call q3_generate_many_stop");
-    if (e->stop_seq.n_states) return fail(Q3_ERR_UNSUPPORTED, "q3_generate_many_lookup does not draft under q3_stop_seq_set: clear it, or call q3_generate_many_stop");
-    if (e->batch->prefix_n) return fail(Q3_ERR_UNSUPPORTED, "q3_generate_many_lookup does not draft behind q3_batch_prefix_set: release the prefix, or call q3_generate_many_prefix");
+    if ((rc = lookup_args_check(ngram, draft_len, fill_width))) return rc;
+    if ((rc = lookup_refusals(e, "q3_generate_many_lookup"))) return rc;             // greedy and plain only
     ColsRequests rq;
     if ((rc = cols_requests_check(e, prompts, prompt_len, n_new, n_requests, false, nullptr, nullptr, nullptr, 0, out_tokens, rq))) return rc;
     if (rq.n_prompt > (size_t)INT32_MAX - (size_t)kColsMax * kLookupDraftMax) return fail(Q3_ERR_ARG, "more than 2^31 tokens in one call");

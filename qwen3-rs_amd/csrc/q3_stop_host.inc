@@ -61,11 +61,12 @@ struct LookupArgs {
     q3_lookup_stats* stats;             // filled by the time the loop returns Q3_OK
 };
 int lookup_call_begin(q3_engine* e, const LookupArgs& a, size_t n_prompt);
-int lookup_sched_launch(q3_engine* e, size_t n_prompt);
+int lookup_sched_launch(q3_engine* e, size_t n_prompt, bool draw);
 int lookup_call_end(q3_engine* e, q3_lookup_stats* out);
 
 // rq: checked by cols_requests_check, with the prefix in front of the prompts as its pos_base.  lk: null, or the loop takes drafts:
-// greedy, plain form, no records, no stop automaton and no prefix (the entry point has refused the rest)
+// greedy (section 2u) or under the sampler arrays of rq (section 2w), plain form, no records, no stop automaton and no prefix (the
+// entry point has refused the rest)
 int cols_generate_stop(q3_engine* e, const ColsRequests& rq, const int32_t* stop_tokens, size_t n_stop, int32_t* out_tokens, size_t* n_out,
                        q3_cols_stats* stats, const LookupArgs* lk = nullptr) {
     int rc;
@@ -134,7 +135,7 @@ int cols_generate_stop(q3_engine* e, const ColsRequests& rq, const int32_t* stop
     SchedStatus* hs = b->h_cols_stop;
     size_t passes = 0;
     for (;;) {
-        if (lk) rc = lookup_sched_launch(e, rq.n_prompt);
+        if (lk) rc = lookup_sched_launch(e, rq.n_prompt, draw);
         else if (seq) rc = launch_now(e->stream, k_cols_sched_seq, dim3(1), dim3(64), 0, d, b->cols_ctl, (StopSeqDev*)b->stop_seq_dev, draw ? 1 : 0);
         else rc = launch_now(e->stream, k_cols_sched, dim3(1), dim3(64), 0, d, b->cols_ctl, draw ? 1 : 0);
         if (rc) return rc;

@@ -44,6 +44,7 @@ EXPORTED_SYMBOLS = [
     "q3_stop_seq_set", "q3_stop_seq_get", "q3_cols_schedule_stop_seq", "q3_op_stop_seq",
     "q3_generate_many_lookup", "q3_op_lookup_draft", "q3_weight_bits", "q3_op_gemv_role_w4",
     "q3_batch_weight_bits", "q3_op_bmatmul_w4",
+    "q3_generate_many_lookup_draw", "q3_batch_slot_rng",
 ]
 LOOKUP_DRAFT_MAX = 31    # Q3_LOOKUP_DRAFT_MAX (section 2u)
 LOOKUP_CHUNK = 4096      # Q3_LOOKUP_CHUNK
@@ -303,6 +304,9 @@ def _bind(path: str) -> C.CDLL:
     L.q3_generate_many_lookup.argtypes = [C.c_void_p, i32p, szp, szp, sz, i32p, sz, C.c_int, C.c_int, C.c_int, i32p, szp, C.POINTER(_ColsStats),
                                           C.POINTER(_LookupStats)]
     L.q3_op_lookup_draft.argtypes = [i32p, sz, C.c_int, C.c_int, i32p, i32p, C.c_int]
+    L.q3_generate_many_lookup_draw.argtypes = [C.c_void_p, i32p, szp, szp, sz, fp, fp, C.POINTER(C.c_uint64), i32p, sz, C.c_int, C.c_int, C.c_int, i32p,
+                                               szp, C.POINTER(_ColsStats), C.POINTER(_LookupStats)]
+    L.q3_batch_slot_rng.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint64)]
     L.q3_batch_copy_rows.argtypes = [C.c_void_p, C.c_int, i32p, C.c_int, sz, sz]
     L.q3_batch_prefix_set.argtypes = [C.c_void_p, i32p, sz]
     L.q3_batch_prefix_get.argtypes = [C.c_void_p, szp, i32p, sz]
@@ -961,6 +965,30 @@ class Transformer:
         rows, stats, out, got = self._generate_many(prompts, n_new, None, call)
         self.last_lookup_stats = LookupStats(ls.drafted, ls.accepted)
         return (out, got, stats, self.last_lookup_stats) if raw else (rows, stats, self.last_lookup_stats)
+
+    # ---- prompt-lookup drafts under the sampler (include/qwen3_hip.h section 2w)
+    def generate_many_lookup_draw(self, prompts, n_new, sampler, stop_tokens=(), ngram: int = 3, draft_len: int = 8, fill_width: int = 0,
+                                  raw: bool = False):
+        """generate_many_stop under sampler = (temperature, topp, seeds), one value per request or a scalar each, with the drafts of
+        generate_many_lookup (q3_generate_many_lookup_draw): a draft stands exactly when it is the token the sampler draws with the
+        coin the plain loop uses at that position, so rows, slot rng states and cache rows equal the plain sampled loop's at any
+        temperature; a temperature-0 request follows the argmax.  Arguments and return value as for generate_many_lookup."""
+        ls = _LookupStats()
+
+        def call(rq, smp, out, st):
+            stop, n_out = [int(t) for t in stop_tokens], _size_array([0] * len(prompts))
+            self._batch_rc(self._lib.q3_generate_many_lookup_draw(*rq, *smp, _i32_array(stop), len(stop), int(ngram), int(draft_len), int(fill_width),
+                                                                  out, n_out, st, C.byref(ls)))
+            return n_out
+        rows, stats, out, got = self._generate_many(prompts, n_new, sampler, call)
+        self.last_lookup_stats = LookupStats(ls.drafted, ls.accepted)
+        return (out, got, stats, self.last_lookup_stats) if raw else (rows, stats, self.last_lookup_stats)
+
+    def batch_slot_rng(self, slot: int) -> int:
+        """the rng state of KV slot `slot` as the last sampled generate_many_* loop left it (q3_batch_slot_rng)"""
+        out = C.c_uint64(0)
+        _check(self._lib.q3_batch_slot_rng(self._h, int(slot), C.byref(out)))
+        return int(out.value)
 
     # ---- a shared prompt prefix (include/qwen3_hip.h section 2i)
     def batch_copy_rows(self, src_slot: int, dst_slots, first_pos: int, n_rows: int):

@@ -235,19 +235,19 @@ def generate_many(transformer, prompts: Sequence[Sequence[int]], max_new_tokens:
     lookup=N (1 .. 31, with stop_on_device=True): the spare columns of every pass verify prompt-lookup drafts of up to N tokens for the
     decoding requests (Transformer.generate_many_lookup): the same rows in fewer passes where the text repeats itself.  lookup_ngram:
     the tokens a match must share; lookup_fill: 0 keeps every pass at the width it would have, 1 .. 32 lets passes widen to carry
-    drafts.  The first version is greedy and plain: with sampler, shared_prefix, logprobs, penalties, logit bias, guide, regex or
-    stop= it is a ValueError here (and the engine refuses what is set on it directly).  The call's LookupStats are
-    transformer.last_lookup_stats."""
+    drafts.  With sampler= the drafts are held against the draws (Transformer.generate_many_lookup_draw): the rows of the sampled
+    loop.  With shared_prefix, logprobs, penalties, logit bias, guide, regex or stop= it is a ValueError here (and the engine
+    refuses what is set on it directly).  The call's LookupStats are transformer.last_lookup_stats."""
     if lookup:
         if not stop_on_device:
             raise ValueError("lookup= runs in the device loop: it needs stop_on_device=True")
-        named = {"sampler": sampler is not None, "shared_prefix": shared_prefix not in (None, False), "logprobs": logprobs is not None,
+        named = {"shared_prefix": shared_prefix not in (None, False), "logprobs": logprobs is not None,
                  "presence_penalty": presence_penalty != 0.0, "frequency_penalty": frequency_penalty != 0.0, "logit_bias": logit_bias is not None,
                  "banned_tokens": banned_tokens is not None, "allowed_tokens": allowed_tokens is not None,
                  "min_tokens": not (np.isscalar(min_tokens) and min_tokens == 0), "guide": guide is not None, "regex": regex is not None,
                  "stop": stop is not None, "dense_min": dense_min > 0}
         if any(named.values()):
-            raise ValueError("lookup= is greedy and plain in this version: not together with " + ", ".join(k for k, v in named.items() if v))
+            raise ValueError("lookup= runs the plain loops only: not together with " + ", ".join(k for k, v in named.items() if v))
     if any(len(p) == 0 for p in prompts):
         raise ValueError("Please provide a prompt")
     if regex is not None:
@@ -259,7 +259,7 @@ def generate_many(transformer, prompts: Sequence[Sequence[int]], max_new_tokens:
         guide = _regex_guide(regex, tokenizer, stop_tokens[0])
     stop_seq = None if stop is None else compile_stop(stop, len(prompts), transformer.get_config().vocab_size, tokenizer)
     if lookup:
-        return _generate_many(transformer, prompts, max_new_tokens, stop_tokens, None, 0, True, None, False, None,
+        return _generate_many(transformer, prompts, max_new_tokens, stop_tokens, sampler, 0, True, None, False, None,
                               (int(lookup), int(lookup_ngram), int(lookup_fill)))[:2]
     args = (transformer, prompts, max_new_tokens, stop_tokens, sampler, dense_min, stop_on_device, shared_prefix, logprobs, presence_penalty,
             frequency_penalty, logit_bias, banned_tokens, allowed_tokens, min_tokens, stop_seq)
@@ -416,7 +416,8 @@ def _generate_many(transformer, prompts, max_new_tokens, stop_tokens, sampler, d
                    lookup=None):
     """generate_many behind its logprobs handling: (rows, ColsStats, per row the engine's (records, tops, ranks) or None).
     stop_seq: None, or stops.compile_stop's (automaton, start) with one start state or one per prompt.
-    lookup: None, or (draft_len, ngram, fill_width) of Transformer.generate_many_lookup (greedy, stop_on_device, nothing else set)"""
+    lookup: None, or (draft_len, ngram, fill_width) of Transformer.generate_many_lookup, under a sampler of generate_many_lookup_draw
+    (stop_on_device, nothing else set)"""
     stop = set(stop_tokens)
     if stop_on_device and dense_min > 0:
         raise ValueError("stop_on_device=True runs column passes only: no dense_min > 0")
@@ -449,7 +450,10 @@ def _generate_many(transformer, prompts, max_new_tokens, stop_tokens, sampler, d
             seq_before = transformer.get_stop_sequences()
             transformer.set_stop_sequences(stop_seq[0], seq_start)
         try:
-            if lookup is not None:
+            if lookup is not None and sampler is not None:
+                got, stats, _ = transformer.generate_many_lookup_draw(live_prompts, live_new, per_live, sorted(stop), ngram=lookup[1],
+                                                                      draft_len=lookup[0], fill_width=lookup[2])
+            elif lookup is not None:
                 got, stats, _ = transformer.generate_many_lookup(live_prompts, live_new, sorted(stop), ngram=lookup[1], draft_len=lookup[0],
                                                                  fill_width=lookup[2])
             elif prefix:

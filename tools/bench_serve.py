@@ -70,6 +70,9 @@ each, the cost of a pass of each (seconds / passes), what a lookup pass costs ov
 per pass -- a lookup pass yields (decode columns + accepted) tokens, so it pays when accepted / pass exceeds decode columns per pass
 * (lookup pass cost / plain pass cost - 1).  The synthetic checkpoints cycle under greedy decoding: their acceptance says nothing
 about real text and is listed only to show what the passes carried.  Writes <out>/serve_lookup.json and <out>/serve_lookup.md.
+With --temperature T [--topp P] (section 2w): the sampled q3_generate_many_stop against q3_generate_many_lookup_draw, medians and
+spreads of 7 rounds; with --ab PARENT_TREE the plain sampled call also runs in child processes of that checkout, in front of and
+behind ours.  Writes <out>/serve_lookup_draw.json.  Either form rewrites <out>/serve_lookup.md from both JSON files.
 """
 import argparse
 import json
@@ -79,7 +82,7 @@ import sys
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-# (--tree, the worker of --stop-seq --ab: the package and the library of another checkout run the call)
+# (--tree, the worker of --ab: the package and the library of another checkout run the call)
 _TREE = sys.argv[sys.argv.index("--tree") + 1] if "--tree" in sys.argv[:-1] else ROOT
 sys.path.insert(0, os.path.join(os.path.abspath(_TREE), "qwen3-rs_amd"))
 
@@ -390,27 +393,132 @@ def main_lookup(a):
     os.makedirs(a.out, exist_ok=True)
     with open(os.path.join(a.out, "serve_lookup.json"), "w") as f:
         json.dump(results, f, indent=1)
-    lines = ["# Prompt-lookup drafts in the stop loop: what a pass costs", "",
-             "Written by `tools/bench_serve.py --lookup %d` (synthetic full-size checkpoints, one MI355X, context %d per slot): as many" % (a.lookup, a.ctx),
-             "slots as requests, prompts of 64 tokens, 128 new tokens, no stop token, ngram 3.  Wall time per call, `q3_generate_many_stop`",
-             "(plain) and `q3_generate_many_lookup` at fill_width 0 and 32 taken by turns, best of 5 rounds behind a warm-up round.",
-             "us per pass = seconds / passes, host synchronisation included.  over plain = a lookup pass less a plain pass: at fill_width 0",
-             "the two kernels between the passes (`k_lookup_draft`, `k_cols_sched_lookup` in the place of `k_cols_sched`), at 32 also the wider plan.",
-             "break-even = accepted drafts per pass above which the loop yields more tokens per second than the plain loop.",
-             "The checkpoints are synthetic and cycle under greedy decoding: drafted and accepted say what the passes carried, nothing about real text.", "",
-             "| model | requests | loop | passes | seconds | us per pass | over plain us | break-even accepted / pass | drafted | accepted | rows equal |",
-             "|---|---|---|---|---|---|---|---|---|---|---|"]
-    for res in results:
-        for r in res["runs"]:
-            for k in ("plain", "fill0", "fill32"):
-                d = r[k]
-                lines.append(f"| {res['model']} | {r['requests']} | {k} | {d['passes']} | {d['seconds']:.4f} | {d['pass_us']:.1f} | " +
-                             (f"{d['over_plain_us']:.1f} | {d['break_even']:.2f} | {d['drafted']} | {d['accepted']} | {r['rows_equal']} |" if k != "plain" else " | | | | |"))
-    if not results:
-        lines.append("not taken")
-    with open(os.path.join(a.out, "serve_lookup.md"), "w") as f:
-        f.write("\n".join(lines) + "\n")
+    write_lookup_md(a.out)
     return 0 if len(results) == len(a.models.split(",")) and all(r["rows_equal"] for res in results for r in res["runs"]) else 1
+
+
+def worker_lookup_draw(name, ctx, ckpt_dir, seed, draft_len, temperature, topp, plain_only):
+    """--lookup N --temperature T: the sampled stop loop against q3_generate_many_lookup_draw at fill_width 0 and 32, by turns.
+    plain_only (--tree, the worker of --ab): the sampled stop loop alone, in the package and library of that checkout"""
+    import qwen3_rs_amd as q3
+    ck = q3.checkpoint
+    shape = ck.SHAPES[name]
+    path = os.path.join(ckpt_dir, f"{name}-seed{seed}.q3bin")
+    ck.ensure_synthetic_checkpoint(path, shape, seed=seed)
+    runs = []
+    with q3.TransformerBuilder(path).with_ctx_length(ctx).build() as t:
+        for n_req in (4, 8, 20):
+            t.batch_init(n_req, ctx)
+            prompts = [ck.iter_prompt_tokens(shape, seed + 50 + r, 64) for r in range(n_req)]
+            nnew = [128] * n_req
+            smp = (temperature, topp, [seed + 7 * r for r in range(n_req)])
+            calls = {"plain": lambda: t.generate_many_stop(prompts, nnew, [], smp),
+                     "fill0": lambda: t.generate_many_lookup_draw(prompts, nnew, smp, [], ngram=3, draft_len=draft_len, fill_width=0),
+                     "fill32": lambda: t.generate_many_lookup_draw(prompts, nnew, smp, [], ngram=3, draft_len=draft_len, fill_width=32)}
+            if plain_only:
+                calls = {"plain": calls["plain"]}
+            secs, out = {k: [] for k in calls}, {}
+            for rnd in range(8):                                       # round 0 builds the plans of every width
+                for k, call in calls.items():
+                    t0 = time.perf_counter()
+                    out[k] = call()
+                    if rnd:
+                        secs[k].append(time.perf_counter() - t0)
+            r = {"requests": n_req, "rows_equal": all(out[k][0] == out["plain"][0] for k in calls)}
+            for k in calls:
+                st = out[k][1]
+                us = sorted(1e6 * s / st.passes for s in secs[k])
+                r[k] = {"passes": st.passes, "decode_columns": st.decode_columns, "pass_us": median(us), "pass_us_min": us[0], "pass_us_max": us[-1], "rounds_us": us}
+                if k != "plain":
+                    ls = out[k][2]
+                    r[k].update(drafted=ls.drafted, accepted=ls.accepted, over_plain_us=r[k]["pass_us"] - r["plain"]["pass_us"],
+                                break_even=st.decode_columns / st.passes * (r[k]["pass_us"] / r["plain"]["pass_us"] - 1.0))
+            runs.append(r)
+    print("RESULT " + json.dumps({"model": name, "ctx": ctx, "draft_len": draft_len, "temperature": temperature, "topp": topp, "runs": runs}))
+
+
+def main_lookup_draw(a):
+    def child(name, tree):
+        cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--worker", name, "--ctx", str(a.ctx), "--ckpt-dir", a.ckpt_dir,
+               "--seed", str(a.seed), "--lookup", str(a.lookup), "--temperature", str(a.temperature), "--topp", str(a.topp)] + (["--tree", tree] if tree else [])
+        p = subprocess.run(cmd, capture_output=True, text=True)
+        sys.stderr.write(p.stderr[-2000:])
+        if p.returncode != 0:
+            print(f"[bench_serve] {name}: exit status {p.returncode}; stopping here", file=sys.stderr)
+            return None
+        return json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")][-1][7:])
+    results = []
+    for name in a.models.split(","):
+        # --ab: the commit before runs the plain sampled loop in processes of its own, in front of and behind ours; a fault in one child starts no other
+        runs = []
+        for tree in ([a.ab, None, a.ab] if a.ab else [None]):
+            runs.append(child(name, tree))
+            if runs[-1] is None:
+                break
+        if runs[-1] is None:
+            break
+        res = runs[1 if a.ab else 0]
+        for i, r in enumerate(res["runs"]):
+            if a.ab:
+                us = sorted(runs[0]["runs"][i]["plain"]["rounds_us"] + runs[2]["runs"][i]["plain"]["rounds_us"])
+                r["parent_plain"] = {"pass_us": median(us), "pass_us_min": us[0], "pass_us_max": us[-1], "rounds_us": us}
+        results.append(res)
+    os.makedirs(a.out, exist_ok=True)
+    with open(os.path.join(a.out, "serve_lookup_draw.json"), "w") as f:
+        json.dump(results, f, indent=1)
+    write_lookup_md(a.out)
+    return 0 if len(results) == len(a.models.split(",")) and all(r["rows_equal"] for res in results for r in res["runs"]) else 1
+
+
+def write_lookup_md(out):
+    """<out>/serve_lookup.md from <out>/serve_lookup.json (--lookup N) and <out>/serve_lookup_draw.json (--lookup N --temperature T),
+    whichever exist: either run rewrites the whole file, and neither drops the other's table"""
+    def load(name):
+        path = os.path.join(out, name)
+        return json.load(open(path)) if os.path.exists(path) else []
+    greedy, drawn = load("serve_lookup.json"), load("serve_lookup_draw.json")
+    lines = ["# Prompt-lookup drafts in the stop loop: what a pass costs", ""]
+    if greedy:
+        lines += ["Written by `tools/bench_serve.py --lookup %d` (synthetic full-size checkpoints, one MI355X, context %d per slot): as many" % (greedy[0]["draft_len"], greedy[0]["ctx"]),
+                  "slots as requests, prompts of 64 tokens, 128 new tokens, no stop token, ngram 3.  Wall time per call, `q3_generate_many_stop`",
+                  "(plain) and `q3_generate_many_lookup` at fill_width 0 and 32 taken by turns, best of 5 rounds behind a warm-up round.",
+                  "us per pass = seconds / passes, host synchronisation included.  over plain = a lookup pass less a plain pass: at fill_width 0",
+                  "the two kernels between the passes (`k_lookup_draft`, `k_cols_sched_lookup` in the place of `k_cols_sched`), at 32 also the wider plan.",
+                  "break-even = accepted drafts per pass above which the loop yields more tokens per second than the plain loop.",
+                  "The checkpoints are synthetic and cycle under greedy decoding: drafted and accepted say what the passes carried, nothing about real text.", "",
+                  "| model | requests | loop | passes | seconds | us per pass | over plain us | break-even accepted / pass | drafted | accepted | rows equal |",
+                  "|---|---|---|---|---|---|---|---|---|---|---|"]
+        for res in greedy:
+            for r in res["runs"]:
+                for k in ("plain", "fill0", "fill32"):
+                    d = r[k]
+                    lines.append(f"| {res['model']} | {r['requests']} | {k} | {d['passes']} | {d['seconds']:.4f} | {d['pass_us']:.1f} | " +
+                                 (f"{d['over_plain_us']:.1f} | {d['break_even']:.2f} | {d['drafted']} | {d['accepted']} | {r['rows_equal']} |" if k != "plain" else " | | | | |"))
+    if drawn:
+        T, P, N = drawn[0]["temperature"], drawn[0]["topp"], drawn[0]["draft_len"]
+        lines += ["", "## Under the sampler (temperature %g, top-p %g)" % (T, P), "",
+                  "Written by `tools/bench_serve.py --lookup %d --temperature %g --topp %g [--ab PARENT_TREE]`: the same requests, one seed per request, the" % (N, T, P),
+                  "sampled `q3_generate_many_stop` (plain) and `q3_generate_many_lookup_draw` at fill_width 0 and 32 by turns in one process, 7 rounds",
+                  "behind a warm-up round.  us per pass = wall time / passes: median (min .. max) of the rounds.  A sampled pass draws every column",
+                  "of its plan width, one workgroup per column, so draft columns add no draw launches.  Synthetic logits are near flat: a sampled",
+                  "draft almost never stands, so accepted says nothing about real text; break-even is what a real text has to reach.",
+                  "plain, commit before (with --ab): the plain call in a checkout of the commit before this loop existed, in processes of its own in",
+                  "front of and behind ours, 14 rounds together; it shows whether the plain sampled loop moved.", "",
+                  "| model | requests | loop | passes | us per pass | over plain us | break-even accepted / pass | drafted | accepted | rows equal |",
+                  "|---|---|---|---|---|---|---|---|---|---|"]
+        for res in drawn:
+            for r in res["runs"]:
+                if "parent_plain" in r:
+                    d = r["parent_plain"]
+                    lines.append(f"| {res['model']} | {r['requests']} | plain, commit before | {r['plain']['passes']} | {d['pass_us']:.1f} ({d['pass_us_min']:.1f} .. {d['pass_us_max']:.1f}) | | | | | |")
+                for k in ("plain", "fill0", "fill32"):
+                    d = r[k]
+                    lines.append(f"| {res['model']} | {r['requests']} | {k} | {d['passes']} | {d['pass_us']:.1f} ({d['pass_us_min']:.1f} .. {d['pass_us_max']:.1f}) | " +
+                                 (f"{d['over_plain_us']:.1f} | {d['break_even']:.2f} | {d['drafted']} | {d['accepted']} | {r['rows_equal']} |" if k != "plain" else " | | | | |"))
+    if not greedy and not drawn:
+        lines.append("not taken")
+    with open(os.path.join(out, "serve_lookup.md"), "w") as f:
+        f.write("\n".join(lines) + "\n")
 
 
 def synthetic_token_bytes(vocab_size):
@@ -814,11 +922,16 @@ def main():
     ap.add_argument("--dense-min", type=int, help="long prompts through dense blocks against the column loop (appends to serve_cols.md; context 2,304)")
     ap.add_argument("--stop", action="store_true", help="stop tokens in the device loop against the loop at the cap (appends to serve_cols.md)")
     ap.add_argument("--stop-seq", action="store_true", help="stop sequences in the device loop: no automaton, one that never matches, one that ends requests (writes stop_seq.md)")
-    ap.add_argument("--ab", help="with --stop-seq: a checkout of the commit before, its library built; (a) also runs there")
+    ap.add_argument("--ab", help="with --stop-seq or --lookup N --temperature T: a checkout of the commit before, its library built; the plain call also runs there")
     ap.add_argument("--tree", help=argparse.SUPPRESS)                  # worker of --ab: the tree whose package and library run (a)
     ap.add_argument("--prefix", type=int, help="requests that share a prefix of this many tokens against the loops on the full prompts (appends to serve_cols.md)")
     ap.add_argument("--lookup", type=int, help="prompt-lookup drafts of this many tokens in the stop loop against the plain loop (writes serve_lookup.md)")
     a = ap.parse_args()
+    if a.lookup is not None and a.temperature is not None:
+        if a.worker:
+            worker_lookup_draw(a.worker, a.ctx, a.ckpt_dir, a.seed, a.lookup, a.temperature, a.topp, a.tree is not None)
+            return 0
+        return main_lookup_draw(a)
     if a.lookup is not None:
         if a.worker:
             worker_lookup(a.worker, a.ctx, a.ckpt_dir, a.seed, a.lookup)
