@@ -83,7 +83,13 @@ typedef struct q3_engine q3_engine;
                            group-quant matmul, the integer group dots and each group term ((dot as f32) * ws) * xs
                            (tensor.rs:53-60) are exact in both modes; only the ORDER in which a row's group terms are
                            added differs (a tree instead of the ascending chain).  quantize, SwiGLU, expf and the
-                           sampler are identical in both modes. */
+                           sampler are identical in both modes.
+                           One kernel goes further than reordering: the attention of a dense prefill block (more than 32
+                           positions of q3_prefill_batched; head_dim 128 with 2, 4, 5 or 8 query heads per kv head) runs on
+                           the bf16 matrix cores at split precision -- every operand as bf16 hi + lo, every product as
+                           hi*hi + hi*lo + lo*hi in f32, about 16 bits per product instead of 24 -- with an online softmax
+                           (k_attn_pf_mfma, q3_op_attention_block; budget in DESIGN.md 4.24).  Such an engine allocates
+                           no score rows for its prefill blocks. */
 #define Q3_FLAG_NO_GRAPH 2u /* launch kernels eagerly instead of replaying a captured hipGraph */
 #define Q3_FLAG_NO_VALUE_T 4u /* do not keep the TRANSPOSED copy of the value cache.  Reference-order engines whose context
                            can reach the split attention path (seq_len > 256, a multiple of 4) keep the value cache twice:
@@ -340,6 +346,15 @@ int q3_op_expf(float* x, size_t n, int device);
 int q3_op_attention(float* xb, float* q, float* key_cache_layer, const float* value_cache_layer,
                     const float* q_norm_w, const float* k_norm_w, size_t pos, size_t seq_len, size_t n_heads,
                     size_t n_kv_heads, size_t head_dim, uint32_t flags, int device);
+/* The dense-prefill attention of a Q3_FLAG_FAST engine alone (k_attn_pf_mfma: causal, split-precision bf16 on the matrix
+ * cores): column i of a block of n_pos columns is position first_pos + i of one sequence and attends to rows
+ * 0 .. first_pos + i of the layer.  q: the block's normalised, rotated queries [n_pos][n_heads * head_dim]; key_layer /
+ * value_layer: [first_pos + n_pos or more rows][n_kv_heads * head_dim], the block's own rows included; xb: [n_pos][n_heads *
+ * head_dim] out.  Not bit-equal to anything: held to the float64 budget of DESIGN.md 4.24.
+ * Q3_ERR_UNSUPPORTED, before any launch: flags without Q3_FLAG_FAST (the reference-order block kernel is reached through
+ * q3_prefill_batched); head_dim other than 128; n_heads / n_kv_heads other than 2, 4, 5 or 8. */
+int q3_op_attention_block(float* xb, const float* q, const float* key_layer, const float* value_layer, size_t n_pos,
+                          size_t first_pos, size_t n_heads, size_t n_kv_heads, size_t head_dim, uint32_t flags, int device);
 /* Sampler::sample with temperature > 0 on caller logits: one draw, *rng_state advanced by one coin   sampler.rs:118-139 */
 int q3_op_sample(const float* logits, size_t n, float temperature, float topp, uint64_t* rng_state, int32_t* index, int device);
 /* Sampler::sample_argmax                                                sampler.rs:57-59 */

@@ -2063,7 +2063,7 @@ __host__ __device__ constexpr int attn_pf2_threads(int kvm, int np) { return 64 
 // where k_attn_pf2 reads element d of query head h of column p in q_out: the heads of a pair interleaved element by element
 // ([column][pair][d][2]); the last head of an odd kv group is interleaved with the same head of the column pair's other column,
 // the 2 x hd floats of the pair spread over that head's two hd-float places, column p & ~1 first
-__device__ __forceinline__ size_t attn_pf2_q_index(int p, int h, int d, int n_heads, int kvm) {
+__host__ __device__ __forceinline__ size_t attn_pf2_q_index(int p, int h, int d, int n_heads, int kvm) {
     constexpr int hd = kG2Hd;
     if (!(kvm & 1)) return ((size_t)p * n_heads + (size_t)(h & ~1)) * hd + 2 * d + (h & 1);
     const int g = h / kvm, j = h - g * kvm;

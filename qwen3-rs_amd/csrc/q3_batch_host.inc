@@ -414,6 +414,13 @@ int att_rows_grow(q3_engine* e, DevMem<float>& att_pf, int& stride, size_t colum
     return Q3_OK;
 }
 
+// The dense blocks of a Q3_FLAG_FAST engine run k_attn_pf_mfma (q3_attn_mfma.h), which keeps no score rows: such an engine never
+// allocates them (Q3_PREFILL_ATT_MFMA=0, developer build: k_attn_pf2 and its rows).  The plan builder asks the same question.
+bool attn_pf2_shape_ok(int hd, int kv_mul);
+bool prefill_att_mfma(const q3_engine* e) {
+    return (e->flags & Q3_FLAG_FAST) && attn_pf2_shape_ok(e->cfg.head_dim, e->cfg.n_heads / e->cfg.n_kv_heads) && dev_knob("Q3_PREFILL_ATT_MFMA", 1);
+}
+
 // positions per weight pass of a prefill-only context (Q3_PREFILL_M)
 int prefill_block_cap(const q3_engine* e) {
     int M = env_int("Q3_PREFILL_M", 2048);
@@ -450,13 +457,14 @@ int q3_prefill_batched(q3_engine* e, const int32_t* tokens, size_t n_tokens, siz
     // decode kernels).  A context created by q3_batch_init keeps its 32-column scratch and walks 32 positions per pass.
     // Round 4: default 2,048 (was 256, and capped there by a 256-thread state kernel): the launches of a block cover more tiles -- 4B
     // shape, 2,048-token prompt: 23.5k tok/s at 256, 25.5k at 512, 30.6k at 1,024, 32.3k at 2,048 (profiles/r04_prefill_ab.txt).
-    // The score rows of k_attn_pf2 take 4 * M * n_heads * context bytes (1 GiB at M = 2,048, 32 heads, 4,096 positions).
+    // The score rows of k_attn_pf2 take 4 * M * n_heads * context bytes (1 GiB at M = 2,048, 32 heads, 4,096 positions); a
+    // Q3_FLAG_FAST engine has none (k_attn_pf_mfma).
     if (!e->batch && (rc = batch_alloc(e, kMaxStreams, 0, false, prefill_block_cap(e)))) return rc;
     BatchCtx* b = e->batch;
     HIP_TRY(hipSetDevice(e->device));
     const size_t B = (size_t)b->cap;
-    // score rows of k_attn_pf2: [block position][head][context so far, rounded up]
-    if (B > (size_t)kMaxStreams &&
+    // score rows of k_attn_pf2: [block position][head][context so far, rounded up]; none for k_attn_pf_mfma
+    if (B > (size_t)kMaxStreams && !prefill_att_mfma(e) &&
         (rc = att_rows_grow(e, b->att_pf, b->att_pf_stride, B, (int)(((first_pos + n_tokens) + 255) & ~(size_t)255), PlanDrop::Step, "dense prefill", "positions")))
         return rc;
     memcpy(e->h_tokens, tokens, 4 * n_tokens);

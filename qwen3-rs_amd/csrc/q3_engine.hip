@@ -35,6 +35,7 @@
 #include "../../include/qwen3_hip.h"
 #include "q3_kernels.h"
 #include "q3_batch.h"
+#include "q3_attn_mfma.h"
 #include "q3_sampler.h"
 #include "q3_stop.h"
 #include "q3_prefix.h"
@@ -2036,6 +2037,52 @@ int q3_op_attention(float* xb, float* q, float* key_cache_layer, const float* va
     HIP_TRY(hipMemcpy(xb, dxb.p, 4 * ahd, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(q, dq.p, 4 * ahd, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(key_cache_layer + pos * kvd, (float*)dk.p + pos * kvd, 4 * kvd, hipMemcpyDeviceToHost));
+    return Q3_OK;
+}
+
+int q3_op_attention_block(float* xb, const float* q, const float* key_layer, const float* value_layer, size_t n_pos, size_t first_pos,
+                          size_t n_heads, size_t n_kv_heads, size_t head_dim, uint32_t flags, int device) {
+    int rc = op_begin(device);
+    if (rc) return rc;
+    if (!xb || !q || !key_layer || !value_layer || n_pos == 0 || n_kv_heads == 0 || n_heads % n_kv_heads) return fail(Q3_ERR_ARG, "null argument, empty block or head counts");
+    if (flags & ~Q3_FLAG_FAST) return fail(Q3_ERR_ARG, "unknown flag bits 0x%x (Q3_FLAG_FAST expected)", (unsigned)flags);
+    if (!(flags & Q3_FLAG_FAST))
+        return fail(Q3_ERR_UNSUPPORTED, "the block attention operator is the tolerance-mode kernel: the reference-order block kernel runs inside q3_prefill_batched");
+    const int kvm = (int)(n_heads / n_kv_heads);
+    const AttnMfmaFn fn = head_dim == (size_t)kG2Hd ? attn_pf_mfma_fn(kvm) : nullptr;
+    if (!fn) return fail(Q3_ERR_UNSUPPORTED, "k_attn_pf_mfma takes head_dim 128 with 2, 4, 5 or 8 query heads per kv head");
+    if (first_pos + n_pos > (size_t)INT32_MAX) return fail(Q3_ERR_ARG, "first_pos + n_pos out of range");
+    const size_t ahd = n_heads * head_dim, kvd = n_kv_heads * head_dim, rows = first_pos + n_pos;
+    const size_t qcols = (n_pos + 1) & ~(size_t)1;              // an odd kv group pairs its last head across two columns
+    // the kernel's query layout (attn_pf2_q_index), as k_knorm_rope writes it
+    std::vector<float> qi(qcols * ahd, 0.0f);
+    for (size_t p = 0; p < n_pos; ++p)
+        for (size_t h = 0; h < n_heads; ++h)
+            for (size_t d = 0; d < head_dim; ++d) qi[attn_pf2_q_index((int)p, (int)h, (int)d, (int)n_heads, kvm)] = q[p * ahd + h * head_dim + d];
+    std::vector<State> st(n_pos);
+    for (size_t p = 0; p < n_pos; ++p) st[p] = State{0, (int)(first_pos + p), 0, 0, 0ull};
+    DevMem<float> dq, dk, dv, dxb;
+    DevMem<State> dst;
+    if ((rc = dq.alloc(qi.size())) || (rc = dk.alloc(rows * kvd)) || (rc = dv.alloc(rows * kvd)) || (rc = dxb.alloc(n_pos * ahd)) || (rc = dst.alloc(n_pos)))
+        return rc;
+    HIP_TRY(hipMemcpy(dq, qi.data(), 4 * qi.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dk, key_layer, 4 * rows * kvd, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dv, value_layer, 4 * rows * kvd, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dst, st.data(), sizeof(State) * n_pos, hipMemcpyHostToDevice));
+    AttnArgs a{};
+    a.q_out = dq;
+    a.key_cache = dk;
+    a.value_cache = dv;
+    a.xb = dxb;
+    a.st = dst;
+    a.pos_override = -1;
+    a.n_heads = (int)n_heads;
+    a.n_kv_heads = (int)n_kv_heads;
+    a.hd = (int)head_dim;
+    a.n_pos = (int)n_pos;
+    a.sb_xb = (long long)ahd;
+    if ((rc = launch_now(0, fn, attn_pf_mfma_grid((int)n_kv_heads, kvm, (int)n_pos), dim3(512), attn_pf_mfma_smem_bytes(), a)) || (rc = op_end())) return rc;
+    HIP_TRY(hipMemcpy(xb, dxb, 4 * n_pos * ahd, hipMemcpyDeviceToHost));
     return Q3_OK;
 }
 

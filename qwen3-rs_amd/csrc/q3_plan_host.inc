@@ -447,7 +447,9 @@ struct PlanBuilder {
     const int kv_mul = c.n_heads / c.n_kv_heads;
     const AttnGqa gqa_kind = attn_gqa_kind(hd, kv_mul, S);
     // dense prefill, head_dim 128 with 2, 4, 5 or 8 query heads per kv head: k_attn_pf2 (Q3_PREFILL_ATT_PF=0: k_attn_gqa2)
-    const bool use_pf = dense && attn_pf2_shape_ok(hd, kv_mul) && sc.att_pf != nullptr && dev_knob("Q3_PREFILL_ATT_PF", 1);
+    // ... of a Q3_FLAG_FAST engine over its own cache: k_attn_pf_mfma behind the same k_knorm_rope launch, no score rows
+    const bool use_mf = dense && !slotpf && prefill_att_mfma(e);
+    const bool use_pf = use_mf || (dense && attn_pf2_shape_ok(hd, kv_mul) && sc.att_pf != nullptr && dev_knob("Q3_PREFILL_ATT_PF", 1));
     const bool gqa2g = !use_pf && gqa_kind == AttnGqa::Gqa2g;
     // score rows in global scratch (BatchCtx::att): k_attn_gqa2g's, or those of k_attn_streams past its LDS bound
     bool att_rows() const { return gqa2g || (!use_pf && !block && gqa_kind == AttnGqa::None && S > att_lds_max); }
@@ -620,6 +622,12 @@ struct PlanBuilder {
             }
             if (rc) return rc;
             a.k_in_cache = 1;
+        }
+        if (use_mf) {
+            // split-precision bf16 MFMA, a tile of columns x the kv head's query heads per workgroup; xb stays f32 (*packed false: the
+            // layer's QUANT prologue quantizes it)
+            a.n_pos = n;
+            return add(F_ATTN, attn_pf_mfma_fn(kv_mul), attn_pf_mfma_grid(c.n_kv_heads, kv_mul, n), dim3(512), attn_pf_mfma_smem_bytes(), a);
         }
         if (use_pf) {
             // NP consecutive positions x the kv head's query heads per workgroup, one wave per (position, head pair)

@@ -45,6 +45,7 @@ EXPORTED_SYMBOLS = [
     "q3_generate_many_lookup", "q3_op_lookup_draft", "q3_weight_bits", "q3_op_gemv_role_w4",
     "q3_batch_weight_bits", "q3_op_bmatmul_w4",
     "q3_generate_many_lookup_draw", "q3_batch_slot_rng",
+    "q3_op_attention_block",
 ]
 LOOKUP_DRAFT_MAX = 31    # Q3_LOOKUP_DRAFT_MAX (section 2u)
 LOOKUP_CHUNK = 4096      # Q3_LOOKUP_CHUNK
@@ -336,6 +337,7 @@ def _bind(path: str) -> C.CDLL:
     L.q3_op_swiglu.argtypes = [fp, fp, sz, C.c_int]
     L.q3_op_expf.argtypes = [fp, sz, C.c_int]
     L.q3_op_attention.argtypes = [fp, fp, fp, fp, fp, fp, sz, sz, sz, sz, sz, C.c_uint32, C.c_int]
+    L.q3_op_attention_block.argtypes = [fp, fp, fp, fp, sz, sz, sz, sz, sz, C.c_uint32, C.c_int]
     L.q3_op_argmax.argtypes = [fp, sz, C.POINTER(C.c_int32), C.c_int]
     L.q3_op_sample.argtypes = [fp, sz, C.c_float, C.c_float, C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.c_int]
     L.q3_op_sample_top_k.argtypes = [fp, sz, C.c_float, C.c_float, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.c_int]
@@ -1561,6 +1563,23 @@ class _Ops:
                                               self._fp(kw), pos, seq_len, n_heads, n_kv_heads, head_dim,
                                               0 if strict else FLAG_FAST, self.device))
         return xb, q, k
+
+    def attention_block(self, q, key_layer, value_layer, first_pos, n_heads, n_kv_heads, head_dim, strict: bool = False):
+        """The dense-prefill attention kernel of tolerance mode alone (q3_op_attention_block): q [n_pos][n_heads * head_dim]
+        normalised and rotated, column i at position first_pos + i over rows 0 .. first_pos + i of the key / value layer
+        ([rows][n_kv_heads * head_dim], at least first_pos + n_pos rows).  Returns xb [n_pos][n_heads * head_dim].  strict=True is
+        refused: the reference-order block kernel runs inside prefill(batched=True)."""
+        q = np.ascontiguousarray(q, dtype=np.float32)
+        k = np.ascontiguousarray(key_layer, dtype=np.float32)
+        v = np.ascontiguousarray(value_layer, dtype=np.float32)
+        ahd, kvd = n_heads * head_dim, n_kv_heads * head_dim
+        n_pos = q.size // ahd
+        if q.size != n_pos * ahd or min(k.size, v.size) < (first_pos + n_pos) * kvd:
+            raise ValueError("q: whole columns; key / value layer: first_pos + n_pos rows")
+        xb = np.zeros((n_pos, ahd), dtype=np.float32)
+        _check(load_library().q3_op_attention_block(self._fp(xb), self._fp(q), self._fp(k), self._fp(v), n_pos, first_pos, n_heads,
+                                                    n_kv_heads, head_dim, 0 if strict else FLAG_FAST, self.device))
+        return xb
 
     def argmax(self, logits) -> int:
         logits = np.ascontiguousarray(logits, dtype=np.float32)
