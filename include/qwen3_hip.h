@@ -756,8 +756,11 @@ int q3_embed_many(q3_engine* e, const int32_t* prompts /* concatenated */, const
  * Every failing call leaves the engine usable.
  * Q3_ERR_ARG: everything q3_embed_many refuses (out_dim aside); a null cand; k == 0 or k > Q3_CHOICE_MAX; a candidate outside
  * [0, vocab_size); unknown flag bits.
- * Q3_ERR_UNSUPPORTED: what q3_embed_many refuses; dim > 4096, more than the norm prologue holds (refused before anything is
- * enqueued). */
+ * dim > 4096 (Qwen3-14B and 32B: 5120): the same values from two launches behind a block in the place of k_choice_rows, chosen by
+ * dim alone -- k_choice_norm, one workgroup per prompt that ends in the block, leaves xq / xs in a buffer of the batched state, and
+ * k_choice_stream, one workgroup per (prompt, part of 32 candidates), streams the candidates' rows 1 KiB at a time against them.
+ * Q3_ERR_UNSUPPORTED: what q3_embed_many refuses; dim > 16384, more than the norm prologue walks (no engine loads such a
+ * checkpoint; refused before anything is enqueued). */
 int q3_choice_many(q3_engine* e, const int32_t* prompts /* concatenated */, const size_t* prompt_len, size_t n_requests,
                    const int32_t* cand, size_t k, uint32_t flags, float* out /* host, [n_requests][k] */, q3_embed_stats* stats);
 

@@ -165,6 +165,9 @@ struct BatchCtx {
     // choice logits (q3_choice_many): the uploaded candidate ids and the output rows [n_requests][k], grow-only
     DevMem<int32_t> choice_cand;
     DevMem<float> choice_out;
+    // dim > 4096: the quantized final-norm vectors [rows of one block][dim] and their scales, k_choice_norm to k_choice_stream
+    DevMem<int8_t> choice_xq;
+    DevMem<float> choice_xs;
     // the scratch of the record kernels (q3_score.h), shared by the score calls and the plans with records and made by record_scratch
     // (q3_plan_host.inc) alone, on first use at its full size, never replaced while the context lives: the exps of 32 rows, and -- from
     // the first use with k > 0 on -- the parts' lists and counts of 32 rows ([32][64][64] keys, [32][64] counts)

@@ -2,7 +2,8 @@
 // q3_embed_host.inc, same translation unit).
 //
 // The walk is q3_embed_many's (embed_walk, q3_embed_host.inc): the same waves, blocks, runs and row table, the same plans.  Behind
-// each block k_choice_rows (q3_choice.h) computes, for every prompt that ends in it, the classifier's rows of its candidates.
+// each block k_choice_rows (q3_choice.h) computes, for every prompt that ends in it, the classifier's rows of its candidates; at a dim
+// past the four KiB of a row that kernel holds in registers, k_choice_norm and k_choice_stream do (the form depends on dim alone).
 
 extern "C" {
 
@@ -25,8 +26,10 @@ int q3_choice_many(q3_engine* e, const int32_t* prompts, const size_t* prompt_le
         if (cand[i] < 0 || cand[i] >= e->cfg.vocab_size)
             return fail(Q3_ERR_ARG, "index out of range: candidate %d (vocab_size %d)", cand[i], e->cfg.vocab_size);
     const int dim = e->cfg.dim, G = e->cfg.group_size;
-    if (dim > 4 * kWG * kProSlots)
-        return fail(Q3_ERR_UNSUPPORTED, "q3_choice_many: dim %d exceeds the %d elements the RMSNorm prologue holds", dim, 4 * kWG * kProSlots);
+    // one form per dim: k_choice_rows holds a row in kChoiceJ KiB of registers; past that, k_choice_norm + k_choice_stream
+    const bool wide = dim > 1024 * kChoiceJ;
+    if (dim > kChoiceMaxDim)
+        return fail(Q3_ERR_UNSUPPORTED, "q3_choice_many: dim %d exceeds the %d elements the RMSNorm prologue walks", dim, kChoiceMaxDim);
 
     ChoiceArgs a{};
     a.norm_w = e->rms_final;
@@ -38,21 +41,48 @@ int q3_choice_many(q3_engine* e, const int32_t* prompts, const size_t* prompt_le
     a.k = (int)k;
     const size_t smem = choice_smem_bytes(dim, G);
     const unsigned parts = (unsigned)((k + kChoicePart - 1) / kChoicePart);
+    ChoiceNormArgs na{};
+    na.norm_w = e->rms_final;
+    na.n = dim;
+    na.group = G;
+    ChoiceStreamArgs sa{};
+    sa.wq = e->wcls.q;
+    sa.ws = e->wcls.s;
+    sa.cand_stride = a.cand_stride;
+    sa.n = dim;
+    sa.group = G;
+    sa.k = (int)k;
     q3_embed_stats st;
     if ((rc = embed_walk(e, prompts, prompt_len, n_requests, (flags & Q3_CHOICE_PREFIX) != 0,
-                         [&](const std::vector<DenseRun>&, const std::vector<EmbedStep>&) {
+                         [&](const std::vector<DenseRun>&, const std::vector<EmbedStep>& steps) {
                              int rc2;
                              if ((rc2 = b->choice_cand.grow(n_cand, e->stream))) return rc2;
                              if ((rc2 = b->choice_out.grow(n_out, e->stream))) return rc2;
+                             if (wide) {                     // the quantized final-norm vectors of the prompts that end in one block
+                                 size_t most = 0;
+                                 for (const EmbedStep& s : steps) most = std::max(most, s.ng);
+                                 if ((rc2 = b->choice_xq.grow(most * (size_t)dim, e->stream))) return rc2;
+                                 if ((rc2 = b->choice_xs.grow(most * (size_t)(dim / G), e->stream))) return rc2;
+                                 na.xq = b->choice_xq;
+                                 na.xs = b->choice_xs;
+                                 sa.xq = b->choice_xq;
+                                 sa.xs = b->choice_xs;
+                             }
                              HIP_TRY(hipMemcpyAsync(b->choice_cand, cand, 4 * n_cand, hipMemcpyHostToDevice, e->stream));
-                             a.cand = b->choice_cand;
-                             a.out = b->choice_out;
+                             a.cand = sa.cand = b->choice_cand;
+                             a.out = sa.out = b->choice_out;
                              return (int)Q3_OK;
                          },
                          [&](const EmbedRow* rows, size_t n_rows, const float* x, size_t) {
-                             a.rows = rows;
-                             a.x = x;
-                             return launch_now(e->stream, k_choice_rows, dim3((unsigned)n_rows, parts), dim3(kWG), smem, a);
+                             if (!wide) {
+                                 a.rows = rows;
+                                 a.x = x;
+                                 return launch_now(e->stream, k_choice_rows, dim3((unsigned)n_rows, parts), dim3(kWG), smem, a);
+                             }
+                             na.rows = sa.rows = rows;
+                             na.x = x;
+                             if (int rc2 = launch_now(e->stream, k_choice_norm, dim3((unsigned)n_rows), dim3(kWG), choice_norm_smem_bytes(dim, G), na)) return rc2;
+                             return launch_now(e->stream, k_choice_stream, dim3((unsigned)n_rows, parts), dim3(kWG), choice_stream_smem_bytes(dim, G), sa);
                          }, st)))
         return rc;
     // one copy back, one synchronisation
